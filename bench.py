@@ -534,6 +534,37 @@ def corpus_hostile(capi, synth, episodes, minutes, jobs=20, check=2):
                     "kernel times from one job run alone; results against the oracle: tests/test_gpu_hostile.py, bench.py --corpus hostile"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, lib, results, runs, hashes_per_episode):
+    """--dump-outputs: what the last timed job handed its caller, so that two builds can be compared output for output.
+    Every value is an integer below 2**53, so float64 holds it exactly.
+      results.npy              one row per video: has_result, has_opening, opening start, opening end, has_ending,
+                               ending start, ending end (flags 0 / 1, times in ns, 0 where absent: every value finite)
+      runs_found.npy           [runs found over all pairs]
+      frame_hashes.npy         the opening-window hashes, one row per episode of frame_hash_episodes.npy: every episode,
+                               or a fixed seeded sample of them when all would exceed DUMP_LIMIT_BYTES in all
+      frame_hash_episodes.npy  the episode index of each row of frame_hashes.npy"""
+    import numpy as np
+    n = len(results)
+    res = np.zeros((n, 7))
+    for i, r in enumerate(results):
+        res[i, 0] = r is not None
+        if r is not None and r.opening is not None:
+            res[i, 1:4] = (1, *r.opening)
+        if r is not None and r.ending is not None:
+            res[i, 4:7] = (1, *r.ending)
+    room = DUMP_LIMIT_BYTES - res.nbytes - 1024                 # (the .npy headers and runs_found)
+    m = min(n, room // (8 * hashes_per_episode + 8))           # a row of hashes and its episode index
+    ids = np.arange(n) if m == n else np.sort(np.random.default_rng(0).choice(n, m, replace=False))
+    hashes = np.stack([lib.frame_hashes(int(v)).opening_data()[0] for v in ids]).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("results", res), ("runs_found", np.array([runs], dtype=np.float64)), ("frame_hashes", hashes),
+                    ("frame_hash_episodes", ids.astype(np.float64))):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 # ---- launching N ranks -----------------------------------------------------------------------------------------------
 # Every rank of an N > 1 run is TWO processes: a supervisor that never touches a GPU and the worker it starts.  A
 # collective that never completes (the first multi-rank RCCL bring-up happens on the driver's clock) cannot be
@@ -676,8 +707,13 @@ def main() -> None:
     ap.add_argument("--launch-timeout", type=float, default=120.0,
                     help="N > 1: seconds the ranks of one attempt get before they are killed and restarted over the "
                          "host-staged transport (an 8-rank run takes ~15 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed job returned as DIR/<name>.npy (float64, "
+                         "at most 64 MB): per-video results, runs found and opening-window frame hashes")
     ap.add_argument("--selftest-worker", choices=["ok", "hang", "fail"], help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus, args.launch_timeout))
@@ -853,6 +889,8 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     device_state = telemetry.stop() if telemetry else None
     scan_form, scan_products = capi.scan_last_launch()           # of the timed jobs (a counting launch below is the vector form's)
+    if args.dump_outputs and rank == 0:                          # before any later job overwrites the hash arena
+        dump_outputs(args.dump_outputs, lib, state["results"], state["runs"], kept[0])
     extra_steps = min(args.steps, 10)
     timed[0], acc[0] = list(kernel_names), extra_ms
     capi.set_kernel_timing("all")

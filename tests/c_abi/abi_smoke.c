@@ -11,7 +11,15 @@ int main(void) {
   NeedleAudioAnalyzer *analyzer = NULL;
   const NeedleAudioComparator *comparator = NULL;
   const FrameHashes *frame_hashes = NULL;
+  const char *const *videos = NULL;
+  size_t num_videos = 0;
   const char *paths[] = {"/tmp/needle-abi-smoke-a.wav", "/tmp/needle-abi-smoke-b.wav"};
+
+  if (needle_util_find_video_files(paths, 2, false, true, &videos, &num_videos) == NeedleError_Ok) return 8; /* the files do not exist */
+  err = needle_audio_analyzer_new_default(paths, 2, &analyzer);
+  if (err != NeedleError_Ok || analyzer == NULL) return 9;
+  needle_audio_analyzer_free(analyzer);
+  analyzer = NULL;
 
   err = needle_audio_analyzer_new(paths, 2, 0.5f, 0.25f, false, false, true, &analyzer);
   if (err != NeedleError_Ok || analyzer == NULL) return 1;

@@ -223,24 +223,14 @@ def test_compute_entry_points_fail_loudly_without_a_gpu(has_gpu):
 
 def test_c_program_links_against_header_and_library(tmp_path):
     """An ordinary C consumer of needle.h (same call sequence as the reference's examples, which CI only
-    compiles: .github/workflows/test.yml:39-40) builds with -Wall -Werror and runs."""
+    compiles: .github/workflows/test.yml:39-40, and every needle_* function those examples call) builds with
+    -Wall -Werror and runs."""
     exe = str(tmp_path / "abi_smoke")
     subprocess.run(["gcc", "-Wall", "-Werror", "-std=c11", os.path.join(HERE, "c_abi", "abi_smoke.c"),
                     "-I", os.path.join(ROOT, "include"), "-L", os.path.dirname(capi.LIB_PATH), "-lneedle_capi",
                     "-Wl,-rpath," + os.path.dirname(capi.LIB_PATH), "-o", exe], check=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
     assert "abi smoke ok" in out
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/needle-capi/examples"), reason="reference tree not present")
-def test_reference_examples_compile_unchanged(tmp_path):
-    """needle-capi/examples/*.c compile and link, unmodified and in place, against OUR header and library
-    (the reference's own ABI gate; nothing is copied into the repo)."""
-    for name in ("analyzer", "comparator", "full"):
-        src = f"/root/reference/needle-capi/examples/{name}.c"
-        subprocess.run(["gcc", src, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-L",
-                        os.path.dirname(capi.LIB_PATH), "-lneedle_capi", "-o", str(tmp_path / f"{name}.out")],
-                       check=True)
 
 
 # ---- libchromaprint-compatible entry points (include/needle_chromaprint.h) ---------------------------------------

@@ -1,6 +1,6 @@
 import os, sys
 import numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from needle_amd import capi
 capi.set_kernel_timing("all")
 for rate, ch in ((96000, 2), (32000, 2), (16000, 2), (24000, 2), (8000, 2)):
