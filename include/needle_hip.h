@@ -91,10 +91,12 @@ enum NeedleError needle_hip_epilogue_host_fallbacks(uint64_t *jobs, bool reset);
 /* ---- fingerprint: the chromaprint Context replacement -------------------------------------------
  * Replaces chromaprint::Context::{start,feed,finish,get_fingerprint_raw,get_delay,get_item_duration,
  * sample_rate} as called from analyzer.rs:176,179,218,275,286,288-289,300.  Batched: many streams
- * per call.  PCM is interleaved s16 at needle_hip_fingerprint_sample_rate() Hz, `channels` = 1 or 2
- * (the reference always feeds 2, analyzer.rs:218; stereo is down-mixed (L+R)/2 with C truncation on
- * the device).  `step` keeps raw items 0, step, 2*step, ... (analyzer.rs:293-304; step = 1 returns
+ * per call.  PCM is interleaved s16 at needle_hip_fingerprint_sample_rate() Hz, `channels` = 1 to
+ * NEEDLE_HIP_MAX_CHANNELS in needle_hip_fingerprint_host (the reference always feeds 2, analyzer.rs:218; stereo is
+ * down-mixed (L+R)/2 with C truncation on the device, 3-8 channels by needle_hip_downmix_host's arithmetic), 1 or 2
+ * in the _device, _audit_device and _debug forms.  `step` keeps raw items 0, step, 2*step, ... (analyzer.rs:293-304; step = 1 returns
  * chromaprint's full raw fingerprint). */
+#define NEEDLE_HIP_MAX_CHANNELS 8                 /* interleaved channels the analyze paths accept (1..8) */
 int needle_hip_fingerprint_sample_rate(void);      /* 11025 */
 int needle_hip_fingerprint_delay_ms(void);         /* 2600  (chromaprint_get_delay_ms) */
 int needle_hip_fingerprint_item_duration_ms(void); /* 123   (chromaprint_get_item_duration_ms) */
@@ -159,6 +161,12 @@ enum NeedleError needle_hip_fingerprint_debug(const int16_t *pcm, size_t num_val
 size_t needle_hip_resample_out_len(size_t samples_per_channel, int sample_rate);
 enum NeedleError needle_hip_resample_host(const int16_t *const *pcm, const size_t *num_values, size_t num_streams,
                                           int channels, int sample_rate, int16_t *const *out);
+/* The down-mix on its own (`channels` = 1..NEEDLE_HIP_MAX_CHANNELS): out[i][n] = (sum of the `channels` values of frame n
+ * of pcm[i]) / channels, C integer division (truncation toward zero); out[i] must hold num_values[i] / channels values
+ * (a trailing partial frame is dropped).  Every analyze path applies it on the device to 3-8 channel input before the
+ * resampler and the fingerprinter; 1 and 2 channels keep their own paths. */
+enum NeedleError needle_hip_downmix_host(const int16_t *const *pcm, const size_t *num_values, size_t num_streams,
+                                         int channels, int16_t *const *out);
 
 /* ---- search: the LCS-Hamming DP replacement -------------------------------------------------------
  * Replaces Comparator::longest_common_hash_match's two table sweeps (comparator.rs:175-247).  For a
@@ -269,7 +277,9 @@ void needle_hip_library_free(NeedleHipLibrary *library);
 enum NeedleError needle_hip_library_include_endings(NeedleHipLibrary *library, float ending_search_percentage);
 size_t needle_hip_library_rows_per_video(const NeedleHipLibrary *library);
 /* Lengths (values per stream, all videos) are metadata every rank holds; pcm[i] may be NULL for
- * videos this rank does not own.  Crops to the opening window and uploads. */
+ * videos this rank does not own.  Crops to the opening window and uploads.  `channels` = 1..NEEDLE_HIP_MAX_CHANNELS in
+ * set_pcm, set_pcm_device and stream_pcm, num_values in interleaved values; 3-8 channel windows are down-mixed on the
+ * device on the way in (set_pcm through a staging buffer of at most 2 GiB), so the resident PCM is mono. */
 enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *library, const int16_t *const *pcm,
                                             const size_t *num_values, int channels);
 /* The same for PCM that is already in HBM (decoded or generated on the device): d_pcm[i] are DEVICE pointers, NULL for

@@ -29,6 +29,7 @@ DEFAULT_ENDING_SEARCH_PERCENTAGE = 0.25
 DEFAULT_MIN_OPENING_DURATION = 20
 DEFAULT_MIN_ENDING_DURATION = 20
 DEFAULT_HASH_DURATION = 0.3
+MAX_CHANNELS = 8  # NEEDLE_HIP_MAX_CHANNELS: interleaved channels the analyze paths accept
 
 
 class NeedleError(RuntimeError):
@@ -76,7 +77,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_host_free", "needle_hip_last_kernel_ms", "needle_hip_set_kernel_timing", "needle_hip_fingerprint_sample_rate",
     "needle_hip_fingerprint_delay_ms", "needle_hip_fingerprint_item_duration_ms", "needle_hip_fingerprint_num_items",
     "needle_hip_fingerprint_num_kept", "needle_hip_fingerprint_host", "needle_hip_fingerprint_device",
-    "needle_hip_fingerprint_debug", "needle_hip_resample_out_len", "needle_hip_resample_host",
+    "needle_hip_fingerprint_debug", "needle_hip_resample_out_len", "needle_hip_resample_host", "needle_hip_downmix_host",
     "needle_hip_hamming_runs_device", "needle_hip_hamming_runs_host",
     "needle_hip_frame_hashes_new", "needle_hip_frame_hashes_free", "needle_hip_frame_hashes_len",
     "needle_hip_frame_hashes_copy", "needle_hip_frame_hashes_hash_duration_ns", "needle_hip_frame_hashes_md5",
@@ -158,6 +159,7 @@ def lib():
     L.needle_hip_resample_out_len.argtypes = [sz, C.c_int]
     L.needle_hip_resample_out_len.restype = sz
     L.needle_hip_resample_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, C.c_int, C.c_int, C.POINTER(vp)]
+    L.needle_hip_downmix_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, C.c_int, C.POINTER(vp)]
     L.needle_hip_hamming_runs_device.argtypes = [vp, C.POINTER(Seq), sz, C.POINTER(Problem), sz, u32, vp, u32, vp, b]
     L.needle_hip_hamming_runs_host.argtypes = [vp, sz, C.POINTER(Seq), sz, C.POINTER(Problem), sz, u32,
                                                C.POINTER(C.POINTER(Run)), C.POINTER(sz)]
@@ -596,6 +598,20 @@ def resample(pcms: Sequence[np.ndarray], channels: int, sample_rate: int) -> Lis
     lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
     optrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
     check(lib().needle_hip_resample_host(ptrs, lens, n, channels, sample_rate, optrs))
+    return [o[:k] for o, k in zip(outs, lens_out)]
+
+
+def downmix(pcms: Sequence[np.ndarray], channels: int) -> List[np.ndarray]:
+    """needle_hip_downmix_host: interleaved s16 with `channels` (1..MAX_CHANNELS) channels -> mono s16,
+    (sum of a frame) // channels with C truncation toward zero; a trailing partial frame is dropped."""
+    arrs = [np.ascontiguousarray(p, dtype=np.int16) for p in pcms]
+    n = len(arrs)
+    lens_out = [a.size // max(channels, 1) for a in arrs]
+    outs = [np.zeros(max(k, 1), dtype=np.int16) for k in lens_out]
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    optrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    check(lib().needle_hip_downmix_host(ptrs, lens, n, channels, optrs))
     return [o[:k] for o, k in zip(outs, lens_out)]
 
 

@@ -85,7 +85,8 @@ Status Analyzer::run_pcm(const std::vector<PcmView> &pcm, int channels, int samp
     return Status::Make(NeedleError_InvalidArgument, "one PCM stream per video is required");
   if (sample_rate < 2000 || sample_rate > 768000)
     return Status::Make(NeedleError_InvalidArgument, "unsupported sample rate");
-  if (channels != 1 && channels != 2) return Status::Make(NeedleError_InvalidArgument, "channels must be 1 or 2");
+  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
+    return Status::Make(NeedleError_InvalidArgument, "channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
   uint32_t step = 0;
   if (!step_for_hash_duration(hash_duration, &step))  // the reference panics in step_by(0), :293-304
     return Status::Make(NeedleError_AnalyzerInvalidHashDuration,

@@ -582,6 +582,20 @@ enum NeedleError needle_hip_resample_host(const int16_t *const *pcm, const size_
   });
 }
 
+enum NeedleError needle_hip_downmix_host(const int16_t *const *pcm, const size_t *num_values, size_t num_streams,
+                                         int channels, int16_t *const *out) {
+  if (!pcm || !num_values || !out) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const int16_t *> p(pcm, pcm + num_streams);
+    std::vector<size_t> n(num_values, num_values + num_streams);
+    std::vector<int16_t *> o(out, out + num_streams);
+    for (size_t i = 0; i < num_streams; i++)
+      if ((!p[i] && n[i]) || (!o[i] && channels > 0 && n[i] >= (size_t)channels)) return NeedleError_NullArgument;
+    Status s = gpu_downmix_host(p, n, channels, o);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 // ============================================================================================================
 // search
 // ============================================================================================================

@@ -201,4 +201,17 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
 Status gpu_resample_host(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values, int channels,
                          int rate, std::vector<std::vector<int16_t>> *out);
 
+// ---- down-mix of 3-8 channel PCM (downmix.hip) -------------------------------------------------------------
+// mono[n] = (sum of the C values of frame n) / C, C integer division; a trailing partial frame is dropped.
+struct DownmixSpan {
+  const int16_t *src;  // interleaved C-channel frames (device); any 2-byte alignment
+  int16_t *dst;        // mono (device), a buffer of its own
+  uint64_t frames;
+};
+// one launch on the library stream for all spans; returns after enqueueing unless `sync`
+Status gpu_downmix_device(const std::vector<DownmixSpan> &spans, int channels, bool sync);
+// host arrays in and out (out[i] holds num_values[i] / channels values), in batches of bounded device memory
+Status gpu_downmix_host(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values, int channels,
+                        const std::vector<int16_t *> &out);
+
 }  // namespace needle

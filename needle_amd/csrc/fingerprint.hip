@@ -999,6 +999,7 @@ namespace {
 // gone when static destructors run).  The arenas grow to the largest batch seen (at most 2 GiB of PCM).
 struct HostEntryWorkspace {
   DeviceBuffer<int16_t> d_pcm, d_mono;
+  DeviceBuffer<int16_t> d_mixed;  // 3-8 channel input down-mixed to mono (what the resampler or fingerprinter then reads)
   DeviceBuffer<uint32_t> d_items;
 };
 
@@ -1047,10 +1048,13 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
   Status s = ensure_device();
   if (!s.ok()) return s;
-  if (channels != 1 && channels != 2)
-    return Status::Make(NeedleError_InvalidArgument, "fingerprint: channels must be 1 or 2");
+  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
+    return Status::Make(NeedleError_InvalidArgument, "fingerprint: channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
   if (step == 0) return Status::Make(NeedleError_InvalidArgument, "fingerprint: step must be >= 1");
   const bool resample = rate != kSampleRate;
+  // 3-8 channels: each launch group is down-mixed into d_mixed first and goes on as mono (downmix -> resample ->
+  // fingerprint, the oracle's order); 1 and 2 channels are read by the resampler / STFT kernels themselves
+  const bool mix = channels > 2;
   const size_t n = num_values.size();
   if (items) items->assign(n, {});
   // Batches bounded by bytes so the device arena stays modest for huge libraries.
@@ -1067,15 +1071,16 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
   } drain_uploads{up};
   OverlapEvents *ev = overlap_events();
   HostEntryWorkspace *ws = host_entry_workspace();  // grow-only arenas, guarded by gpu_mutex()
-  DeviceBuffer<int16_t> &d_pcm = ws->d_pcm, &d_mono = ws->d_mono;
+  DeviceBuffer<int16_t> &d_pcm = ws->d_pcm, &d_mono = ws->d_mono, &d_mixed = ws->d_mixed;
   DeviceBuffer<uint32_t> &d_items = ws->d_items;
   size_t begin = 0, descriptor_slot = 0;
   bool first_batch = true;
   while (begin < n) {
     std::vector<StreamSpan> spans;        // what the fingerprinter reads (11025 Hz; mono if resampled)
     std::vector<ResampleSpan> rspans;     // what the resampler reads, when the input rate differs
+    std::vector<ResampleSpan> mspans;     // what the down-mix reads and writes: (in_off, frames, offset in d_mixed)
     std::vector<uint64_t> in_off;
-    uint64_t values = 0, mono = 0, kept = 0;
+    uint64_t values = 0, mono = 0, mixed = 0, kept = 0;
     size_t end = begin;
     while (end < n) {
       if (!spans.empty() && values + num_values[end] > kMaxBatchValues) break;
@@ -1083,12 +1088,18 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
       const size_t out_samples = resample ? resample_out_len(in_samples, rate) : in_samples;
       const uint64_t item_off = d_items_out ? (*item_off_out)[end] : kept;
       in_off.push_back(values);
+      uint64_t src_off = values;  // where the resampler or the fingerprinter reads this stream
+      if (mix) {
+        mspans.push_back(ResampleSpan{values, in_samples, mixed});
+        src_off = mixed;
+        mixed += (in_samples + 7) & ~(uint64_t)7;  // 16-byte aligned, as the arena's streams
+      }
       if (resample) {
-        rspans.push_back(ResampleSpan{values, in_samples, mono});
+        rspans.push_back(ResampleSpan{src_off, in_samples, mono});
         spans.push_back(StreamSpan{mono, out_samples, item_off});
         mono += (out_samples + 1) & ~(uint64_t)1;
       } else {
-        spans.push_back(StreamSpan{values, num_values[end], item_off});
+        spans.push_back(StreamSpan{src_off, mix ? in_samples : num_values[end], item_off});
       }
       values += (num_values[end] + 7) & ~(uint64_t)7;  // keep every stream 16-byte aligned in the arena
       kept += num_kept(out_samples, step);
@@ -1106,6 +1117,7 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
     if (!(s = d_pcm.reserve(std::max<uint64_t>(values, 1))).ok()) return s;
     if (!d_items_out && !(s = d_items.reserve(std::max<uint64_t>(kept, 1))).ok()) return s;
     if (resample && !(s = d_mono.reserve(std::max<uint64_t>(mono, 1))).ok()) return s;
+    if (mix && !(s = d_mixed.reserve(std::max<uint64_t>(mixed, 1))).ok()) return s;
     uint32_t *const d_out = d_items_out ? d_items_out : d_items.ptr;
     lap("device allocations");
     // the copies must not overtake kernels that still read the PCM arena: those of the previous batch, or of an
@@ -1121,12 +1133,22 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
       NEEDLE_HIP_TRY(hipStreamWaitEvent(stream, ev->landed, 0));
       const std::vector<StreamSpan> group(spans.begin() + launched, spans.begin() + upto);
       Status gs;
-      if (resample) {  // decode-rate PCM -> mono 11025 Hz, on the device, then straight into the fingerprinter
+      const int16_t *src = d_pcm.ptr;
+      int src_channels = channels;
+      if (mix) {  // C-channel PCM -> mono, into d_mixed (behind the same event as the kernels it feeds)
+        std::vector<DownmixSpan> mgroup;
+        for (size_t k = launched; k < upto; k++)
+          mgroup.push_back(DownmixSpan{d_pcm.ptr + mspans[k].in_off, d_mixed.ptr + mspans[k].out_off, mspans[k].n_in});
+        gs = gpu_downmix_device(mgroup, channels, false);
+        src = d_mixed.ptr;
+        src_channels = 1;
+      }
+      if (gs.ok() && resample) {  // decode-rate PCM -> mono 11025 Hz, on the device, then straight into the fingerprinter
         const std::vector<ResampleSpan> rgroup(rspans.begin() + launched, rspans.begin() + upto);
-        gs = gpu_resample_device(d_pcm.ptr, rgroup, channels, rate, d_mono.ptr, false);
+        gs = gpu_resample_device(src, rgroup, src_channels, rate, d_mono.ptr, false);
         if (gs.ok()) gs = gpu_fingerprint_device(d_mono.ptr, group, 1, step, d_out, false, nullptr, nullptr, descriptor_slot++);
-      } else {
-        gs = gpu_fingerprint_device(d_pcm.ptr, group, channels, step, d_out, false, nullptr, nullptr, descriptor_slot++);
+      } else if (gs.ok()) {
+        gs = gpu_fingerprint_device(src, group, src_channels, step, d_out, false, nullptr, nullptr, descriptor_slot++);
       }
       launched = upto;
       pending_values = 0;

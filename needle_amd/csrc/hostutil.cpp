@@ -458,9 +458,9 @@ Status wav_probe(const std::string &path, WavInfo *out) {
       if (!have_fmt) break;
       const bool integer = out->format == 1 && (out->bits == 8 || out->bits == 16 || out->bits == 24 || out->bits == 32);
       const bool floating = out->format == 3 && (out->bits == 32 || out->bits == 64);
-      if ((!integer && !floating) || out->channels < 1 || out->channels > 2)
+      if ((!integer && !floating) || out->channels < 1 || out->channels > NEEDLE_HIP_MAX_CHANNELS)
         return Status::Make(NeedleError_Unknown,
-                            "unsupported WAV encoding (need PCM 8/16/24/32-bit or IEEE float, 1-2 channels): " + path);
+                            "unsupported WAV encoding (need PCM 8/16/24/32-bit or IEEE float, 1-8 channels): " + path);
       const uint64_t avail = std::min(len, size - body);  // a truncated file ends the data chunk early
       out->data_offset = body;
       out->frames = avail / ((uint64_t)out->bits / 8) / (uint64_t)out->channels;

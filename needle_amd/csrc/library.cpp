@@ -278,13 +278,15 @@ enum NeedleError needle_hip_library_include_endings(NeedleHipLibrary *lib, float
 namespace {
 // Search windows of every video (analyzer.rs:378,390) from the stream lengths, arena geometry, and -- for the videos
 // whose PCM this rank holds -- where each window starts in the caller's buffer.  `resident`: the windows get offsets
-// into the device PCM arena (set_pcm); otherwise nothing of the PCM is kept (stream_pcm).
+// into the device PCM arena (set_pcm); otherwise nothing of the PCM is kept (stream_pcm).  `len` is in the caller's
+// (interleaved) values; 3-8 channel PCM is kept resident as mono (down-mixed on the way in), so lib->channels and the
+// windows' `values` describe the arena, not the input.
 Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values, int channels, bool resident,
                     std::vector<const int16_t *> *src, std::vector<size_t> *len, std::vector<uint64_t> *dst,
                     std::vector<uint64_t> *rows_of_src, uint64_t *total_values) {
   Status s = ensure_device();
   if (!s.ok()) return s;
-  lib->channels = channels;
+  lib->channels = channels > 2 ? 1 : channels;
   const size_t R = lib->regions();
   lib->win.assign(lib->rows(), Window{});
   uint64_t total = 0;
@@ -300,13 +302,13 @@ Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size
       Window &w = lib->win[v * R + r];
       const size_t count = r == 0 ? open_samples : samples - end_first;
       first_sample[v * R + r] = r == 0 ? 0 : end_first;
-      w.values = count * (size_t)channels;
+      w.values = count * (size_t)lib->channels;
       w.kept = (uint32_t)num_kept(count, lib->step);
       w.seek = r == 0 ? 0 : seek;
       max_kept = std::max(max_kept, w.kept);
       if (pcm[v] && resident) {
         w.pcm_off = total;
-        total += (w.values + 1) & ~(uint64_t)1;
+        total += channels > 2 ? (w.values + 7) & ~(uint64_t)7 : (w.values + 1) & ~(uint64_t)1;  // (down-mix: 16-byte stores)
       }
     }
   }
@@ -334,7 +336,7 @@ Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size
       const Window &w = lib->win[v * R + r];
       if (!pcm[v] || !w.values) continue;
       src->push_back(pcm[v] + first_sample[v * R + r] * (size_t)channels);
-      len->push_back(w.values);
+      len->push_back(w.values / (size_t)lib->channels * (size_t)channels);
       if (dst) dst->push_back(w.pcm_off);
       if (rows_of_src) rows_of_src->push_back(v * R + r);
     }
@@ -347,6 +349,50 @@ Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size
   lib->problems_for[0] = ~(size_t)0;
   return Status::Ok();
 }
+
+// set_pcm of 3-8 channel PCM: the windows go to the device in groups through a staging buffer of at most
+// NEEDLE_HIP_MAX_BATCH_VALUES values (2 GiB) and are down-mixed into their places in the resident mono PCM (a window
+// longer than the buffer in pieces of whole 8-frame groups), all in library-stream order; the caller synchronises.
+Status upload_mixed(NeedleHipLibrary *lib, const std::vector<const int16_t *> &src, const std::vector<size_t> &len,
+                    const std::vector<uint64_t> &dst, int channels, DeviceBuffer<int16_t> *stage) {
+  uint64_t max_values = 1ull << 30;
+  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) max_values = (uint64_t)std::max(1ll, atoll(e));  // tests
+  const uint64_t C = (uint64_t)channels;
+  const uint64_t piece = std::max<uint64_t>(8, max_values / C / 8 * 8);  // frames
+  uint64_t total = 0;
+  for (size_t l : len) total += (l + 7) & ~(uint64_t)7;
+  const uint64_t cap = std::max<uint64_t>(std::min(total, max_values), 8 * C) + 8;
+  Status s = stage->reserve(cap);
+  if (!s.ok()) return s;
+  std::vector<const int16_t *> up_src;
+  std::vector<size_t> up_len;
+  std::vector<uint64_t> up_off;
+  std::vector<DownmixSpan> mix;
+  uint64_t used = 0;
+  auto flush = [&]() -> Status {
+    Status fs = up_src.empty() ? Status::Ok() : gpu_upload_pcm(up_src, up_len, up_off, stage->ptr);
+    if (fs.ok() && !mix.empty()) fs = gpu_downmix_device(mix, channels, false);  // the next group's copies follow it in stream order
+    up_src.clear();
+    up_len.clear();
+    up_off.clear();
+    mix.clear();
+    used = 0;
+    return fs;
+  };
+  for (size_t i = 0; i < src.size(); i++) {
+    const uint64_t frames = len[i] / C;
+    for (uint64_t f = 0; f < frames; f += piece) {
+      const uint64_t n = std::min(piece, frames - f), values = (n * C + 7) & ~(uint64_t)7;
+      if (used + values > cap && !(s = flush()).ok()) return s;
+      up_src.push_back(src[i] + f * C);
+      up_len.push_back(n * C);
+      up_off.push_back(used);
+      mix.push_back(DownmixSpan{stage->ptr + used, lib->d_pcm.ptr + dst[i] + f, n});
+      used += values;
+    }
+  }
+  return flush();
+}
 }  // namespace
 
 extern "C" {
@@ -354,7 +400,7 @@ extern "C" {
 enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values,
                                             int channels) {
   if (!lib || !pcm || !num_values) return NeedleError_NullArgument;
-  if (channels != 1 && channels != 2) return NeedleError_InvalidArgument;
+  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     std::vector<const int16_t *> src;
     std::vector<size_t> len;
@@ -363,7 +409,8 @@ enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t
     Status s = plan_windows(lib, pcm, num_values, channels, true, &src, &len, &dst, nullptr, &total);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
-    s = gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
+    DeviceBuffer<int16_t> stage;  // (3-8 channels; freed after the drain below)
+    s = channels > 2 ? upload_mixed(lib, src, len, dst, channels, &stage) : gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
     // also on the error path: copies already enqueued read the caller's buffers asynchronously
     const bool drained = hipStreamSynchronize(library_stream()) == hipSuccess;
     if (!s.ok()) return report(s);
@@ -377,7 +424,7 @@ enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t
 enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const int16_t *const *d_pcm,
                                                    const size_t *num_values, int channels) {
   if (!lib || !d_pcm || !num_values) return NeedleError_NullArgument;
-  if (channels != 1 && channels != 2) return NeedleError_InvalidArgument;
+  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     std::vector<const int16_t *> src;
     std::vector<size_t> len;
@@ -387,9 +434,15 @@ enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const 
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
     hipStream_t stream = library_stream();
-    for (size_t i = 0; i < src.size(); i++)  // the search windows only, device to device, in stream order
-      if (hipMemcpyAsync(lib->d_pcm.ptr + dst[i], src[i], len[i] * sizeof(int16_t), hipMemcpyDeviceToDevice, stream) != hipSuccess)
-        return report(Status::Make(NeedleError_Unknown, "device-to-device PCM copy failed"));
+    if (channels > 2) {  // the search windows are down-mixed straight out of the caller's buffers into the resident mono PCM
+      std::vector<DownmixSpan> mix;
+      for (size_t i = 0; i < src.size(); i++) mix.push_back(DownmixSpan{src[i], lib->d_pcm.ptr + dst[i], len[i] / (size_t)channels});
+      if (!(s = gpu_downmix_device(mix, channels, false)).ok()) return report(s);
+    } else {
+      for (size_t i = 0; i < src.size(); i++)  // the search windows only, device to device, in stream order
+        if (hipMemcpyAsync(lib->d_pcm.ptr + dst[i], src[i], len[i] * sizeof(int16_t), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+          return report(Status::Make(NeedleError_Unknown, "device-to-device PCM copy failed"));
+    }
     if (hipStreamSynchronize(stream) != hipSuccess) return report(Status::Make(NeedleError_Unknown, "PCM copy failed"));
     lib->have_pcm = true;
     lib->pcm_resident = true;
@@ -400,7 +453,7 @@ enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const 
 enum NeedleError needle_hip_library_stream_pcm(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values,
                                                int channels) {
   if (!lib || !pcm || !num_values) return NeedleError_NullArgument;
-  if (channels != 1 && channels != 2) return NeedleError_InvalidArgument;
+  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     std::vector<const int16_t *> src;
     std::vector<size_t> len;
@@ -1003,7 +1056,7 @@ void needle_hip_comm_shard(size_t units, int world_size, int rank, size_t *first
 enum NeedleError needle_hip_library_rank_videos(const NeedleHipLibrary *lib, const size_t *num_values, int channels, int world_size,
                                                 int rank, size_t *first_video, size_t *video_count) {
   if (!lib || !num_values || !first_video || !video_count) return NeedleError_NullArgument;
-  if ((channels != 1 && channels != 2) || world_size < 1 || rank < 0 || rank >= world_size) return NeedleError_InvalidArgument;
+  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS || world_size < 1 || rank < 0 || rank >= world_size) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     // the geometry plan_windows will arrive at for these lengths, without touching the library
     NeedleHipLibrary plan;

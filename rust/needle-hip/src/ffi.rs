@@ -197,6 +197,15 @@ extern "C" {
         output: *mut *mut NeedleHipLibrary,
     ) -> NeedleError;
     pub fn needle_hip_library_free(library: *mut NeedleHipLibrary);
+    /// 1..=MAX_CHANNELS interleaved channels -> mono, `(sum of a frame) / channels` with C truncation; `out[i]` holds
+    /// `num_values[i] / channels` values.
+    pub fn needle_hip_downmix_host(
+        pcm: *const *const i16,
+        num_values: *const usize,
+        num_streams: usize,
+        channels: c_int,
+        out: *const *mut i16,
+    ) -> NeedleError;
     pub fn needle_hip_library_include_endings(library: *mut NeedleHipLibrary, ending_search_percentage: f32) -> NeedleError;
     pub fn needle_hip_library_set_pcm(
         library: *mut NeedleHipLibrary,

@@ -429,6 +429,24 @@ pub fn device_count() -> Result<i32> {
     Ok(n)
 }
 
+/// Interleaved channels the analyze paths accept (`NEEDLE_HIP_MAX_CHANNELS`): 1..=8.
+pub const MAX_CHANNELS: i32 = 8;
+
+/// The device down-mix on its own: each stream of interleaved s16 with `channels` (1..=MAX_CHANNELS) channels to mono,
+/// `(sum of a frame) / channels` with C truncation, a trailing partial frame dropped.  Every analyze path applies it to
+/// 3-8 channel input; this form is for callers that want the mono signal itself.
+pub fn downmix(pcm: &[&[i16]], channels: i32) -> Result<Vec<Vec<i16>>> {
+    let per = channels.max(1) as usize;
+    let mut out: Vec<Vec<i16>> = pcm.iter().map(|s| vec![0i16; s.len() / per]).collect();
+    let ptrs: Vec<*const i16> = pcm.iter().map(|s| s.as_ptr()).collect();
+    let lens: Vec<usize> = pcm.iter().map(|s| s.len()).collect();
+    let optrs: Vec<*mut i16> = out.iter_mut().map(|o| o.as_mut_ptr()).collect();
+    unsafe {
+        check(ffi::needle_hip_downmix_host(ptrs.as_ptr(), lens.as_ptr(), pcm.len(), channels, optrs.as_ptr()))?;
+    }
+    Ok(out)
+}
+
 /// Frame-hash file next to a video: `Path::with_extension("needle.dat")` (data.rs:8-13,117-119).
 pub fn frame_hash_path(video: impl AsRef<Path>) -> PathBuf {
     video.as_ref().with_extension("needle.dat")
