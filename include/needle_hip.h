@@ -262,6 +262,27 @@ enum NeedleError needle_hip_comparator_results_from_runs(const struct NeedleAudi
                                                          const NeedleHipRun *runs, size_t num_runs, size_t first_video,
                                                          size_t video_count, NeedleHipSearchResult *results);
 
+/* ---- Incremental index: a growing library searched one append at a time ---------------------------------
+ * Results equal needle_hip_comparator_run_with_frame_hashes over ALL videos added so far, in insertion order, bit for
+ * bit; an append searches only the pairs it adds (old x new and new x new) and recomputes the best match only of the
+ * videos whose candidate list changed.  The index copies the comparator's parameters (threshold, minimum durations,
+ * padding, include_endings) at creation: later changes to the comparator do not affect it.  The videos' hashes are
+ * copied; the caller may free its FrameHashes after an add.  One GPU: the index runs on the device that was current when
+ * it was created (no sharding across ranks).  No display, skip files or removal of a video. */
+typedef struct NeedleHipIndex NeedleHipIndex;
+enum NeedleError needle_hip_index_new(const struct NeedleAudioComparator *comparator, NeedleHipIndex **output);
+void needle_hip_index_free(NeedleHipIndex *index);
+size_t needle_hip_index_len(const NeedleHipIndex *index); /* videos added (0 for NULL) */
+/* Appends k >= 1 videos.  Fails as run_with_frame_hashes would over the longer list (no ending data with endings on,
+ * padding or hash duration beyond a match's end, more than 2^32 hashes or sequence pairs: NeedleError_InvalidArgument);
+ * after a failure the index is exactly as it was before the call. */
+enum NeedleError needle_hip_index_add(NeedleHipIndex *index, const FrameHashes *const *frame_hashes, size_t k);
+/* One result per video added, in insertion order; n >= needle_hip_index_len(index) (NeedleError_InvalidArgument otherwise). */
+enum NeedleError needle_hip_index_results(const NeedleHipIndex *index, NeedleHipSearchResult *results, size_t n);
+/* Video pairs handed to the scan: over the index's life (*total) and by the last successful add (*last).  A pair none
+ * of whose sequences can hold a run long enough is left out, as in the full search.  Either pointer may be NULL. */
+enum NeedleError needle_hip_index_pairs_searched(const NeedleHipIndex *index, uint64_t *total, uint64_t *last);
+
 /* ---- Library: an HBM-resident analyze+search job, shardable across GPUs ----------------------------
  * One object per process/GPU describing ALL videos of a job.  PCM of the videos this rank owns is
  * uploaded once and stays in HBM; hashes live in a padded device arena [video * rows_per_video][stride] so a

@@ -97,7 +97,9 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_comparator_results_from_runs", "needle_hip_library_job_runs", "needle_hip_library_job_comm_bytes",
     "needle_hip_library_job_form",
     "needle_hip_host_threads", "needle_hip_fingerprint_audit_device", "needle_hip_library_audit",
-    "needle_hip_scan_counts", "needle_hip_scan_last_launch", "needle_hip_epilogue_host_fallbacks"]
+    "needle_hip_scan_counts", "needle_hip_scan_last_launch", "needle_hip_epilogue_host_fallbacks",
+    "needle_hip_index_new", "needle_hip_index_free", "needle_hip_index_len", "needle_hip_index_add",
+    "needle_hip_index_results", "needle_hip_index_pairs_searched"]
 
 _LIB = None
 
@@ -210,6 +212,14 @@ def lib():
     L.needle_hip_host_alloc_free.argtypes = [vp]
     L.needle_hip_library_job_begin.argtypes = [vp, vp, C.c_int]
     L.needle_hip_library_job_end.argtypes = [vp, vp, C.c_int, C.POINTER(CSearchResult), C.POINTER(sz)]
+    L.needle_hip_index_new.argtypes = [vp, C.POINTER(vp)]
+    L.needle_hip_index_free.argtypes = [vp]
+    L.needle_hip_index_free.restype = None
+    L.needle_hip_index_len.argtypes = [vp]
+    L.needle_hip_index_len.restype = sz
+    L.needle_hip_index_add.argtypes = [vp, C.POINTER(vp), sz]
+    L.needle_hip_index_results.argtypes = [vp, C.POINTER(CSearchResult), sz]
+    L.needle_hip_index_pairs_searched.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     _LIB = L
     return L
 
@@ -560,6 +570,44 @@ class Comparator:
     def __del__(self):
         if getattr(self, "_h", None):
             lib().needle_audio_comparator_free(self._h)
+            self._h = None
+
+
+class Index:
+    """An incremental search index (needle_hip_index_*): results() equals Comparator.run_with_frame_hashes over every video
+    added so far, in insertion order; add() searches only the pairs it adds.  The comparator's parameters are copied at
+    creation.  One GPU: the device current at creation."""
+
+    def __init__(self, comparator: Comparator):
+        self._h = None
+        out = C.c_void_p()
+        check(lib().needle_hip_index_new(comparator.handle(), C.byref(out)))
+        self._h = out
+
+    def add(self, frame_hashes: Sequence[FrameHashes]) -> None:
+        """Appends the videos; on failure (NeedleError) the index is as it was before the call."""
+        k = len(frame_hashes)
+        ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
+        check(lib().needle_hip_index_add(self._h, ptrs, k))
+
+    def results(self) -> List[Optional[SearchResult]]:
+        n = len(self)
+        res = (CSearchResult * max(n, 1))()
+        check(lib().needle_hip_index_results(self._h, res, n))
+        return _results(res, n)
+
+    def pairs_searched(self) -> Tuple[int, int]:
+        """(total, last): video pairs handed to the scan over the index's life and by the last add."""
+        total, last = C.c_uint64(), C.c_uint64()
+        check(lib().needle_hip_index_pairs_searched(self._h, C.byref(total), C.byref(last)))
+        return total.value, last.value
+
+    def __len__(self) -> int:
+        return int(lib().needle_hip_index_len(self._h))
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().needle_hip_index_free(self._h)
             self._h = None
 
 

@@ -17,6 +17,7 @@
 
 #include "epilogue.h"
 #include "hipctx.h"
+#include "index.h"
 #include "needle_core.h"
 
 using namespace needle;
@@ -31,6 +32,10 @@ struct NeedleAudioAnalyzer {
 };
 struct NeedleAudioComparator {
   Comparator inner;
+};
+struct NeedleHipIndex {
+  explicit NeedleHipIndex(const Comparator &c) : inner(c) {}
+  Index inner;
 };
 
 namespace {
@@ -769,6 +774,61 @@ enum NeedleError needle_hip_comparator_results_from_runs(const struct NeedleAudi
     for (size_t i = 0; i < num_videos; i++) fill_result(res[i], &results[i]);
     return NeedleError_Ok;
   });
+}
+
+enum NeedleError needle_hip_index_new(const struct NeedleAudioComparator *comparator, NeedleHipIndex **output) {
+  if (!comparator || !output) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    NeedleHipIndex *index = new NeedleHipIndex(comparator->inner);
+    Status s = index->inner.init();
+    if (!s.ok()) {
+      delete index;
+      return report(s);
+    }
+    *output = index;
+    return NeedleError_Ok;
+  });
+}
+
+void needle_hip_index_free(NeedleHipIndex *index) {
+  if (!index) return;
+  guarded([&]() -> NeedleError {
+    delete index;
+    return NeedleError_Ok;
+  });
+}
+
+size_t needle_hip_index_len(const NeedleHipIndex *index) { return index ? index->inner.size() : 0; }
+
+enum NeedleError needle_hip_index_add(NeedleHipIndex *index, const FrameHashes *const *frame_hashes, size_t k) {
+  if (!index) return NeedleError_NullArgument;
+  if (k == 0) return report(Status::Make(NeedleError_InvalidArgument, "index add: no videos"));
+  if (!frame_hashes) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    Status s = index->inner.add(fh);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_index_results(const NeedleHipIndex *index, NeedleHipSearchResult *results, size_t n) {
+  if (!index) return NeedleError_NullArgument;
+  const std::vector<NeedleHipSearchResult> &have = index->inner.results();
+  if (n < have.size()) return report(Status::Make(NeedleError_InvalidArgument, "index results: buffer shorter than the index"));
+  if (!results && !have.empty()) return NeedleError_NullArgument;
+  if (!have.empty()) std::memcpy(results, have.data(), have.size() * sizeof(NeedleHipSearchResult));
+  return NeedleError_Ok;
+}
+
+enum NeedleError needle_hip_index_pairs_searched(const NeedleHipIndex *index, uint64_t *total, uint64_t *last) {
+  if (!index) return NeedleError_NullArgument;
+  if (total) *total = index->inner.pairs_total();
+  if (last) *last = index->inner.pairs_last();
+  return NeedleError_Ok;
 }
 
 }  // extern "C"

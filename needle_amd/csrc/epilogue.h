@@ -84,4 +84,51 @@ Status gpu_search_results_host(const uint32_t *hashes, size_t num_hashes, const 
                                std::vector<NeedleHipSearchResult> *results, uint32_t *failed, std::vector<NeedleHipRun> *runs,
                                size_t *num_runs);
 
+// ---- the incremental index (index.cpp) -------------------------------------------------------------------------------------
+// A store in HBM, growing only, owned by one NeedleHipIndex: the heap entries of every pair searched so far, per bucket
+// b = p(i, j) * regions + r with the column-major pair id p(i, j) = j (j - 1) / 2 + i (an append adds ids at the end), the
+// buckets' start / valid counts, the videos' row tables (length, timestamps), hash durations and the hash arena.
+struct IndexStore;
+IndexStore *index_store_new();  // on the current device
+void index_store_free(IndexStore *store);
+
+// DeviceEntry's layout (epilogue.hip), for the entries the host computes when an append falls back (static_assert there)
+struct IndexEntry {
+  uint64_t src_start, src_end, dst_start, dst_end;
+  uint32_t score, src_hash, dst_hash, pad;
+};
+
+// One append: videos [n0, n1) join the n0 the store holds.  Rows are video * regions + region.
+struct IndexAppend {
+  uint32_t n0 = 0, n1 = 0, regions = 1, threshold = 0;
+  bool include_endings = false, large_ok = false;
+  ns_t min_opening_duration = 0, min_ending_duration = 0, time_padding = 0;
+  const uint32_t *hashes = nullptr;  // the new rows' hashes, appended to the arena behind the committed ones
+  size_t num_hashes = 0;
+  const NeedleHipSeq *seqs = nullptr;  // ALL rows, offsets into the arena after the append
+  size_t num_seqs = 0;
+  const NeedleHipProblem *problems = nullptr;  // the new pairs only; tag = (p(i, j) - p(0, n0)) * regions + region
+  size_t num_problems = 0;
+  const uint32_t *row_len = nullptr, *row_ts = nullptr;  // the new rows: length, offset of their timestamps in the store's table
+  size_t num_rows = 0;
+  const uint64_t *ts = nullptr;  // timestamps appended to the store's table
+  size_t num_ts = 0;
+  const uint64_t *hash_duration = nullptr;  // per new video
+};
+struct IndexAppendOut {
+  uint32_t found = 0;   // runs the scan found
+  uint32_t failed = 0;  // videos whose padding / hash duration exceed the match end, | kEpilogueBucketTooLarge
+  std::vector<uint32_t> videos;                 // the videos whose candidate list changed ...
+  std::vector<NeedleHipSearchResult> results;   // ... and their new results
+  std::vector<NeedleHipRun> runs;               // kEpilogueBucketTooLarge: the append's run list, for the host
+};
+// Upload, scan of the new pairs, entries into the store, best_match over the changed videos, all on the library stream;
+// one wait, for the final copy.  Nothing is committed: the caller does that (index_store_commit) once the results are good.
+Status gpu_index_append(IndexStore *store, const IndexAppend &append, IndexAppendOut *out);
+// The fallback: the append's new buckets computed on the host (start[b] relative to the append's first entry, valid[b],
+// the entries), uploaded into the store; then best_match as above.
+Status gpu_index_append_host_entries(IndexStore *store, const IndexAppend &append, const std::vector<uint32_t> &start,
+                                     const std::vector<uint32_t> &valid, const std::vector<IndexEntry> &entries, IndexAppendOut *out);
+void index_store_commit(IndexStore *store, const IndexAppend &append, uint32_t entries_written);
+
 }  // namespace needle

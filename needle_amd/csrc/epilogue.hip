@@ -177,6 +177,31 @@ __device__ __forceinline__ void pair_at_device(uint64_t n, uint64_t index, uint3
   *pj = (uint32_t)(i + 1 + (index - row_start(n, i)));
 }
 
+// pairs (i, j), i < j, j-major: p(i, j) = j (j - 1) / 2 + i (the incremental index's store, index.cpp): an id does not depend
+// on the number of videos, so appending videos only adds ids at the end.  The inverse, exact like pair_at_device.
+__device__ __forceinline__ uint64_t column_start(uint64_t j) { return j * (j - 1) / 2; }
+__device__ __forceinline__ void column_pair_at(uint64_t index, uint32_t *pi, uint32_t *pj) {
+  uint64_t j = (uint64_t)((1.0 + sqrt(1.0 + 8.0 * (double)index)) / 2.0);
+  if (j < 1) j = 1;
+  while (j > 1 && column_start(j) > index) j--;
+  while (column_start(j + 1) <= index) j++;
+  *pi = (uint32_t)(index - column_start(j));
+  *pj = (uint32_t)j;
+}
+
+// How pair_entries_kernel / pair_entries_large_kernel turn a bucket's pair into its two videos.  Built in the kernel from
+// EpilogueParams and the kernel's trailing arguments (none for the library job's form: its code is what it was).
+struct RowMajorPairs {  // NeedleHipRun.problem / regions = the pair's index in the reference's i-major list over pr.n videos
+  uint64_t n;
+  __device__ explicit RowMajorPairs(const EpilogueParams &pr) : n(pr.n) {}
+  __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const { pair_at_device(n, p, i, j); }
+};
+struct ColumnMajorPairs {  // an index append: problem / regions = p(i, j) - first, first = the append's first new pair
+  uint64_t first;
+  __device__ ColumnMajorPairs(const EpilogueParams &, uint64_t first_pair) : first(first_pair) {}
+  __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const { column_pair_at(first + p, i, j); }
+};
+
 // A slab's runs into one block per destination rank (gpu_direct_runs).  A wave asks a block's counter once per destination
 // for all its lanes' runs (a returning atomic per run on `world` addresses would be the kernel).
 __global__ __launch_bounds__(256) void direct_runs_kernel(const uint32_t *__restrict__ found, const NeedleHipRun *__restrict__ runs,
@@ -227,12 +252,13 @@ __device__ __forceinline__ bool entry_greater(const DeviceEntry &a, const Device
 
 // One thread per bucket.  row tables: length, offset of the row's timestamps in `ts` (un-seeked, shared by rows of equal
 // length), seek added to every timestamp of the row.
+template <class Pairs, class... Extra>
 __global__ __launch_bounds__(64) void pair_entries_kernel(EpilogueParams pr, const uint32_t *__restrict__ start,
                                                           NeedleHipRun *__restrict__ sorted, const uint32_t *__restrict__ row_len,
                                                           const uint32_t *__restrict__ row_ts, const uint64_t *__restrict__ row_seek,
                                                           const uint64_t *__restrict__ ts, DeviceEntry *__restrict__ entries,
                                                           uint32_t *__restrict__ valid, uint32_t *__restrict__ failed,
-                                                          uint32_t *__restrict__ large_count, uint32_t *__restrict__ large_list) {
+                                                          uint32_t *__restrict__ large_count, uint32_t *__restrict__ large_list, Extra... extra) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= pr.buckets) return;
   const uint32_t lo = start[b], hi = start[b + 1];
@@ -262,7 +288,7 @@ __global__ __launch_bounds__(64) void pair_entries_kernel(EpilogueParams pr, con
     }
     const uint32_t region = b % pr.regions;
     uint32_t vi, vj;
-    pair_at_device(pr.n, b / pr.regions, &vi, &vj);
+    Pairs(pr, extra...).at(b / pr.regions, &vi, &vj);
     const uint32_t src_row = vi * pr.rows_per_video + region, dst_row = vj * pr.rows_per_video + region;
     const uint32_t src_len = row_len[src_row], dst_len = row_len[dst_row];
     const uint64_t *src_ts = ts + row_ts[src_row], *dst_ts = ts + row_ts[dst_row];
@@ -309,12 +335,13 @@ __global__ __launch_bounds__(64) void pair_entries_kernel(EpilogueParams pr, con
 //      dst_end - len, dst_end; two runs of a bucket never share (src_end, dst_end), so the hashes are never reached;
 //   3. ONE lane replays BinaryHeap::push over the valid elements in walk order, in place (the heap never holds more than the
 //      elements already consumed); then every thread builds the DeviceEntry of its heap slots.
+template <class Pairs, class... Extra>
 __global__ __launch_bounds__(256) void pair_entries_large_kernel(EpilogueParams pr, const uint32_t *__restrict__ start,
                                                                  const NeedleHipRun *__restrict__ sorted, const uint32_t *__restrict__ row_len,
                                                                  const uint32_t *__restrict__ row_ts, const uint64_t *__restrict__ row_seek,
                                                                  const uint64_t *__restrict__ ts, DeviceEntry *__restrict__ entries,
                                                                  uint32_t *__restrict__ valid, const uint32_t *__restrict__ large_count,
-                                                                 const uint32_t *__restrict__ large_list) {
+                                                                 const uint32_t *__restrict__ large_list, Extra... extra) {
   extern __shared__ unsigned long long arr[];  // kEpilogueLargeLimit elements
   __shared__ uint32_t heap_size;
   const uint32_t t = threadIdx.x;
@@ -350,7 +377,7 @@ __global__ __launch_bounds__(256) void pair_entries_large_kernel(EpilogueParams 
       }
     const uint32_t region = b % pr.regions;
     uint32_t vi, vj;
-    pair_at_device(pr.n, b / pr.regions, &vi, &vj);
+    Pairs(pr, extra...).at(b / pr.regions, &vi, &vj);
     const uint32_t src_row = vi * pr.rows_per_video + region, dst_row = vj * pr.rows_per_video + region;
     const uint32_t src_len = row_len[src_row], dst_len = row_len[dst_row];
     const uint64_t *src_ts = ts + row_ts[src_row], *dst_ts = ts + row_ts[dst_row];
@@ -431,12 +458,40 @@ constexpr int kImageRows = 512;   // candidates of a stage of the links' b side 
 constexpr int kImagePitch = 12;   // words per row of the stage's image: 8 of +-1 bytes + 4 (16-byte reads of sixteen rows: sixteen groups of banks)
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
+// Which videos best_match_kernel's workgroups take, where a video's pairs' buckets are and where its result goes.  Built in the
+// kernel from EpilogueParams and the kernel's trailing arguments (none for the library job's form: its code is what it was).
+struct RowMajorVideos {  // the library job: videos [v0, v1), buckets in the i-major pair order over n videos, results[v]
+  uint64_t n;
+  uint32_t v0;
+  uint64_t hash_duration;
+  __device__ explicit RowMajorVideos(const EpilogueParams &pr) : n(pr.n), v0(pr.v0), hash_duration(pr.hash_duration) {}
+  __device__ bool live(uint32_t) const { return true; }
+  __device__ uint32_t video(uint32_t block) const { return v0 + block; }
+  __device__ uint64_t pair(uint32_t q, uint32_t v) const {  // (q, v) for q < v, then (v, q + 1)
+    return q < v ? row_start(n, q) + (v - q - 1) : row_start(n, v) + (q - v);
+  }
+  __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
+  __device__ uint64_t video_hash_duration(uint32_t) const { return hash_duration; }
+};
+struct IndexVideos {  // an index append: the videos listed (*count of them), buckets in the store's j-major order, results[block]
+  const uint32_t *list, *count;
+  const uint64_t *hash_durations;  // per video: a candidate of video v is always v's side of its pair (comparator.rs:410-432)
+  __device__ IndexVideos(const EpilogueParams &, const uint32_t *l, const uint32_t *c, const uint64_t *hd)
+      : list(l), count(c), hash_durations(hd) {}
+  __device__ bool live(uint32_t block) const { return block < *count; }
+  __device__ uint32_t video(uint32_t block) const { return list[block]; }
+  __device__ uint64_t pair(uint32_t q, uint32_t v) const { return q < v ? column_start(v) + q : column_start(q + 1) + v; }
+  __device__ uint32_t out(uint32_t block, uint32_t) const { return block; }
+  __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
+};
+
 // One workgroup per wanted video.
+template <class Videos, class... Extra>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void best_match_kernel(EpilogueParams pr, const uint32_t *__restrict__ start,
                                                          const uint32_t *__restrict__ valid, const DeviceEntry *__restrict__ entries,
                                                          Candidate *__restrict__ cand_pool, unsigned long long *__restrict__ cand_cursor,
                                                          uint32_t *__restrict__ links_pool, NeedleHipSearchResult *__restrict__ results,
-                                                         uint32_t *__restrict__ failed) {
+                                                         uint32_t *__restrict__ failed, Extra... extra) {
   __shared__ uint32_t scan[256];
   __shared__ uint32_t carry;
   __shared__ unsigned long long pool_base;
@@ -449,13 +504,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
   __shared__ BestKey best[2][256];
   // a bucket too large for one lane (pair_entries_kernel): the whole job is the host form's, nothing here would be read
   if (__builtin_nontemporal_load(failed) & kEpilogueBucketTooLarge) return;
-  const uint32_t v = pr.v0 + blockIdx.x, t = threadIdx.x;
-  const uint64_t n = pr.n;
+  const Videos videos(pr, extra...);
+  if (!videos.live(blockIdx.x)) return;
+  const uint32_t v = videos.video(blockIdx.x), t = threadIdx.x;
   const uint32_t slots = pr.n - 1;  // the video's pairs in lexicographic order: (q, v) for q < v, then (v, q + 1)
-  auto bucket_of = [&](uint32_t q) -> uint64_t {
-    const uint64_t p = q < v ? row_start(n, q) + (v - q - 1) : row_start(n, v) + (q - v);
-    return p * pr.regions;
-  };
+  auto bucket_of = [&](uint32_t q) -> uint64_t { return videos.pair(q, v) * pr.regions; };
   // pass 1: candidates per pair slot -> total
   if (t == 0) carry = 0;
   __syncthreads();
@@ -475,7 +528,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
   NeedleHipSearchResult res;
   memset(&res, 0, sizeof(res));
   if (c == 0) {  // no pair of this video has an entry: the reference pushes nothing for it (:608-617)
-    if (t == 0) results[v] = res;
+    if (t == 0) results[videos.out(blockIdx.x, v)] = res;
     return;
   }
   if (t == 0) pool_base = atomicAdd(cand_cursor, (unsigned long long)c);
@@ -689,12 +742,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
       const BestKey w = best[which][0];
       if (!w.have) continue;
       const Candidate cd = cand[w.index];
-      if (cd.end < pr.time_padding || cd.end - pr.time_padding < pr.hash_duration) {  // Duration underflow panics upstream
+      const uint64_t hash_duration = videos.video_hash_duration(v);
+      if (cd.end < pr.time_padding || cd.end - pr.time_padding < hash_duration) {  // Duration underflow panics upstream
         bad = true;
         break;
       }
-      const uint64_t s = cd.start + pr.time_padding;                    // :479
-      const uint64_t e = cd.end - pr.time_padding - pr.hash_duration;   // :481
+      const uint64_t s = cd.start + pr.time_padding;                 // :479
+      const uint64_t e = cd.end - pr.time_padding - hash_duration;   // :481
       if (which == 0) {
         res.has_opening = true;
         res.opening_start_ns = s;
@@ -706,9 +760,64 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
       }
     }
     if (bad) atomicAdd(failed, 1u);
-    results[v] = res;
+    results[videos.out(blockIdx.x, v)] = res;
   }
 }
+
+// ---- the incremental index's store (index.cpp) ----------------------------------------------------------------------------
+// The append's buckets into the store: start = where the entries were written (the store's entry count before the append plus
+// the bucket's start in the append's counting sort), valid = the heap's size.
+__global__ __launch_bounds__(256) void index_store_buckets_kernel(uint32_t buckets, const uint32_t *__restrict__ local_start,
+                                                                  const uint32_t *__restrict__ local_valid, uint32_t entries_base,
+                                                                  uint32_t *__restrict__ store_start, uint32_t *__restrict__ store_valid) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < buckets; b += gridDim.x * blockDim.x) {
+    store_start[b] = entries_base + local_start[b];
+    store_valid[b] = local_valid[b];
+  }
+}
+
+// The videos whose candidate list an append changed: an old video i with an entry in a new pair (i, j).  `valid` = the new
+// buckets' counts in the store, `first` = the append's first pair id.
+__global__ __launch_bounds__(256) void index_changed_kernel(uint32_t buckets, uint32_t regions, uint64_t first,
+                                                            const uint32_t *__restrict__ valid, uint32_t *__restrict__ flag) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < buckets; b += gridDim.x * blockDim.x) {
+    if (valid[b] == 0) continue;
+    uint32_t i, j;
+    column_pair_at(first + b / regions, &i, &j);
+    flag[i] = 1u;
+  }
+}
+// ... listed, with every new video [n0, n1) (its result is computed even when it has no candidate: then it is "none")
+__global__ __launch_bounds__(256) void index_list_kernel(uint32_t n0, uint32_t n1, const uint32_t *__restrict__ flag,
+                                                         uint32_t *__restrict__ count, uint32_t *__restrict__ list) {
+  for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n1; v += gridDim.x * blockDim.x)
+    if (v >= n0 || flag[v]) list[atomicAdd(count, 1u)] = v;
+}
+
+// A device array that keeps its contents when it grows (amortised doubling, a device-to-device copy on `stream`).
+template <class T>
+struct GrowBuffer {
+  DeviceBuffer<T> buf;
+  Status reserve(size_t n, size_t keep, hipStream_t stream) {
+    if (n <= buf.count) return Status::Ok();
+    const size_t want = std::max<size_t>(n, 2 * buf.count);
+    T *p = nullptr;
+    NEEDLE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T)));
+    if (keep && buf.ptr) {
+      const hipError_t e = hipMemcpyAsync(p, buf.ptr, keep * sizeof(T), hipMemcpyDeviceToDevice, stream);
+      const hipError_t w = e == hipSuccess ? hipStreamSynchronize(stream) : e;  // (the old buffer is released below)
+      if (w != hipSuccess) {
+        (void)hipFree(p);
+        return Status::Make(NeedleError_Unknown, std::string("HIP error: ") + hipGetErrorString(w) + " growing an index buffer");
+      }
+    }
+    buf.release();
+    buf.ptr = p;
+    buf.count = want;
+    return Status::Ok();
+  }
+  T *ptr() const { return buf.ptr; }
+};
 
 struct EpilogueWorkspace {
   DeviceBuffer<uint32_t> count, start, fill, sums, valid, links, ctl, row_len, row_ts, large_list;
@@ -816,7 +925,7 @@ Status gpu_epilogue_enqueue(const EpilogueJob &job, hipStream_t stream, NeedleHi
       !(s = ws->large_list.reserve(runs / (kEpilogueBucketLimit + 1) + 1)).ok())
     return s;
   if (!ws->large_attr_set) {
-    NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pair_entries_large_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pair_entries_large_kernel<RowMajorPairs>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)(kEpilogueLargeLimit * sizeof(unsigned long long))));
     ws->large_attr_set = true;
   }
@@ -860,23 +969,284 @@ Status gpu_epilogue_enqueue(const EpilogueJob &job, hipStream_t stream, NeedleHi
   }
   {
     KernelTimer timer("epilogue_entries", stream);
-    hipLaunchKernelGGL(pair_entries_kernel, dim3((pr.buckets + 63) / 64), dim3(64), 0, stream, pr, ws->start.ptr, ws->sorted.ptr,
+    hipLaunchKernelGGL(pair_entries_kernel<RowMajorPairs>, dim3((pr.buckets + 63) / 64), dim3(64), 0, stream, pr, ws->start.ptr, ws->sorted.ptr,
                        ws->row_len.ptr, ws->row_ts.ptr, ws->row_seek.ptr, ws->ts.ptr, ws->entries.ptr, ws->valid.ptr, ws->ctl.ptr + 2,
                        ws->ctl.ptr + 3, ws->large_list.ptr);
     // the buckets one lane should not order (a stride loop over a list that is empty on ordinary audio: ~2 us then)
-    hipLaunchKernelGGL(pair_entries_large_kernel, dim3(512), dim3(256), kEpilogueLargeLimit * sizeof(unsigned long long), stream, pr,
+    hipLaunchKernelGGL(pair_entries_large_kernel<RowMajorPairs>, dim3(512), dim3(256), kEpilogueLargeLimit * sizeof(unsigned long long), stream, pr,
                        ws->start.ptr, ws->sorted.ptr, ws->row_len.ptr, ws->row_ts.ptr, ws->row_seek.ptr, ws->ts.ptr, ws->entries.ptr,
                        ws->valid.ptr, ws->ctl.ptr + 3, ws->large_list.ptr);
   }
   if (pr.v1 > pr.v0) {
     KernelTimer timer("epilogue_best_match", stream);
-    hipLaunchKernelGGL(best_match_kernel, dim3(pr.v1 - pr.v0), dim3(256), 0, stream, pr, ws->start.ptr, ws->valid.ptr, ws->entries.ptr,
+    hipLaunchKernelGGL(best_match_kernel<RowMajorVideos>, dim3(pr.v1 - pr.v0), dim3(256), 0, stream, pr, ws->start.ptr, ws->valid.ptr, ws->entries.ptr,
                        ws->cand.ptr, reinterpret_cast<unsigned long long *>(ws->ctl.ptr), ws->links.ptr, ws->results.ptr, ws->ctl.ptr + 2);
   }
   NEEDLE_HIP_TRY(hipGetLastError());
   NEEDLE_HIP_TRY(hipMemcpyAsync(host_results, ws->results.ptr, (size_t)job.n * sizeof(NeedleHipSearchResult), hipMemcpyDeviceToHost, stream));
   NEEDLE_HIP_TRY(hipMemcpyAsync(host_failed, ws->ctl.ptr + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
   return Status::Ok();
+}
+
+
+// ---- the incremental index's store -------------------------------------------------------------------------------------------
+static_assert(sizeof(IndexEntry) == sizeof(DeviceEntry) && offsetof(IndexEntry, score) == offsetof(DeviceEntry, score) &&
+                  offsetof(IndexEntry, dst_hash) == offsetof(DeviceEntry, dst_hash),
+              "IndexEntry mirrors DeviceEntry");
+
+struct IndexStore {
+  // committed: what the index holds (an append that fails leaves these, and what lies below them, as they were)
+  uint32_t n = 0;
+  uint64_t buckets = 0, entries = 0, rows = 0, ts = 0, hashes = 0;
+  // resident, growing only: the per-pair entries and, per bucket b = p(i, j) * regions + r, where they start and how many
+  GrowBuffer<DeviceEntry> entry;
+  GrowBuffer<uint32_t> start, valid, row_len, row_ts, hash;
+  GrowBuffer<uint64_t> row_seek, ts_table, hash_duration;
+  // an append's scratch
+  DeviceBuffer<uint32_t> count, fill, lstart, sums, lvalid, ctl, large_list, flag, list, links, run_count;
+  DeviceBuffer<NeedleHipRun> runs, sorted;
+  DeviceBuffer<Candidate> cand;
+  DeviceBuffer<NeedleHipSearchResult> results;
+  void *pinned = nullptr;  // [found, failed, listed, pad] + list[n1] + results[n1]
+  size_t pinned_bytes = 0;
+  uint32_t capacity = 1u << 16;  // of the run list; grows to what an append found
+  bool large_attr_set = false;
+  bool used = false;  // an append has enqueued work (a store made without a device never has)
+  int device = 0;
+  ~IndexStore() {
+    if (pinned) (void)hipHostFree(pinned);
+  }
+};
+
+IndexStore *index_store_new() {
+  IndexStore *st = new IndexStore();
+  (void)hipGetDevice(&st->device);
+  return st;
+}
+void index_store_free(IndexStore *st) {
+  if (!st) return;
+  if (!st->used) {
+    delete st;
+    return;
+  }
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const int own = st->device;
+  if (dev != own) (void)hipSetDevice(own);
+  (void)hipStreamSynchronize(library_stream());  // (no launch of this append may still read the buffers)
+  delete st;
+  if (dev != own) (void)hipSetDevice(dev);
+}
+
+namespace {
+
+EpilogueParams index_params(const IndexStore *st, const IndexAppend &a, uint64_t buckets) {
+  EpilogueParams pr;
+  std::memset(&pr, 0, sizeof(pr));
+  pr.n = a.n1;
+  pr.regions = pr.rows_per_video = a.regions;
+  pr.buckets = (uint32_t)buckets;
+  pr.v0 = 0;
+  pr.v1 = a.n1;
+  pr.bound = a.threshold + a.threshold / 2;
+  pr.include_endings = a.include_endings ? 1u : 0u;
+  pr.min_duration[0] = a.min_opening_duration;
+  pr.min_duration[1] = a.min_ending_duration;
+  pr.time_padding = a.time_padding;
+  pr.large_ok = a.large_ok && getenv("NEEDLE_HIP_EPILOGUE_NO_LARGE") == nullptr ? 1u : 0u;
+  return pr;
+}
+
+// mark the changed videos, list them, best_match over the list; then the copies into pinned memory and a wait for them
+Status index_best_and_copy(IndexStore *st, const IndexAppend &a, uint64_t new_buckets, hipStream_t stream, IndexAppendOut *out) {
+  const EpilogueParams pr = index_params(st, a, new_buckets);
+  const uint64_t first = (uint64_t)a.n0 * (a.n0 - (a.n0 ? 1 : 0)) / 2;
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->flag.ptr, 0, std::max<size_t>(a.n1, 1) * sizeof(uint32_t), stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr, 0, 2 * sizeof(uint32_t), stream));  // the candidate cursor
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr + 4, 0, sizeof(uint32_t), stream));  // videos listed
+  {
+    KernelTimer timer("index_best_match", stream);
+    if (new_buckets) {
+      const uint32_t grid = (uint32_t)std::min<uint64_t>(4096, (new_buckets + 255) / 256);
+      hipLaunchKernelGGL(index_changed_kernel, dim3(grid), dim3(256), 0, stream, (uint32_t)new_buckets, a.regions, first,
+                         st->valid.ptr() + st->buckets, st->flag.ptr);
+    }
+    hipLaunchKernelGGL(index_list_kernel, dim3((a.n1 + 255) / 256), dim3(256), 0, stream, a.n0, a.n1, st->flag.ptr, st->ctl.ptr + 4,
+                       st->list.ptr);
+    // one workgroup per video at most; those beyond the list's length return at once
+    hipLaunchKernelGGL((best_match_kernel<IndexVideos, const uint32_t *, const uint32_t *, const uint64_t *>), dim3(a.n1), dim3(256), 0, stream, pr, st->start.ptr(), st->valid.ptr(),
+                       st->entry.ptr(), st->cand.ptr, reinterpret_cast<unsigned long long *>(st->ctl.ptr), st->links.ptr,
+                       st->results.ptr, st->ctl.ptr + 2, (const uint32_t *)st->list.ptr, (const uint32_t *)(st->ctl.ptr + 4),
+                       (const uint64_t *)st->hash_duration.ptr());
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  uint32_t *head = static_cast<uint32_t *>(st->pinned);
+  uint32_t *list = head + 4;
+  NeedleHipSearchResult *results = reinterpret_cast<NeedleHipSearchResult *>(list + ((a.n1 + 1) & ~1u));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(head, st->run_count.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(head + 1, st->ctl.ptr + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(head + 2, st->ctl.ptr + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(list, st->list.ptr, (size_t)a.n1 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(results, st->results.ptr, (size_t)a.n1 * sizeof(NeedleHipSearchResult), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  out->found = head[0];
+  out->failed = head[1];
+  const uint32_t listed = std::min(head[2], a.n1);
+  out->videos.assign(list, list + listed);
+  out->results.assign(results, results + listed);
+  return Status::Ok();
+}
+
+}  // namespace
+
+Status gpu_index_append(IndexStore *st, const IndexAppend &a, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != st->device) return Status::Make(NeedleError_InvalidArgument, "index: the current device is not the one the index was created on");
+  st->used = true;
+  if (a.n0 != st->n || a.n1 <= a.n0 || a.regions < 1 || a.regions > 2)
+    return Status::Make(NeedleError_InvalidArgument, "index append: inconsistent sizes");
+  hipStream_t stream = library_stream();
+  const uint64_t first = (uint64_t)a.n0 * (a.n0 - (a.n0 ? 1 : 0)) / 2;
+  const uint64_t new_buckets = ((uint64_t)a.n1 * (a.n1 - 1) / 2 - first) * a.regions;
+  const uint64_t rows1 = st->rows + a.num_rows, ts1 = st->ts + a.num_ts, hashes1 = st->hashes + a.num_hashes;
+  if (st->buckets + new_buckets >= 0xFFFFFFF0ull || hashes1 > UINT32_MAX)
+    return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
+  // the resident tables: the new videos' rows, timestamps, hash durations and hashes go in behind the committed ones
+  if (!(s = st->hash.reserve(std::max<uint64_t>(hashes1, 1), st->hashes, stream)).ok() ||
+      !(s = st->row_len.reserve(rows1, st->rows, stream)).ok() || !(s = st->row_ts.reserve(rows1, st->rows, stream)).ok() ||
+      !(s = st->row_seek.reserve(rows1, st->rows, stream)).ok() || !(s = st->ts_table.reserve(std::max<uint64_t>(ts1, 1), st->ts, stream)).ok() ||
+      !(s = st->hash_duration.reserve(a.n1, st->n, stream)).ok() ||
+      !(s = st->start.reserve(std::max<uint64_t>(st->buckets + new_buckets, 1), st->buckets, stream)).ok() ||
+      !(s = st->valid.reserve(std::max<uint64_t>(st->buckets + new_buckets, 1), st->buckets, stream)).ok())
+    return s;
+  if (a.num_hashes)
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->hash.ptr() + st->hashes, a.hashes, a.num_hashes * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->row_len.ptr() + st->rows, a.row_len, a.num_rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->row_ts.ptr() + st->rows, a.row_ts, a.num_rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->row_seek.ptr() + st->rows, 0, a.num_rows * sizeof(uint64_t), stream));
+  if (a.num_ts) NEEDLE_HIP_TRY(hipMemcpyAsync(st->ts_table.ptr() + st->ts, a.ts, a.num_ts * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->hash_duration.ptr() + st->n, a.hash_duration, (size_t)(a.n1 - a.n0) * sizeof(uint64_t),
+                                hipMemcpyHostToDevice, stream));
+  const size_t pinned_want = 16 + ((size_t)a.n1 + 2) * sizeof(uint32_t) + (size_t)a.n1 * sizeof(NeedleHipSearchResult);
+  if (pinned_want > st->pinned_bytes) {
+    if (st->pinned) (void)hipHostFree(st->pinned);
+    st->pinned = nullptr;
+    st->pinned_bytes = 0;
+    NEEDLE_HIP_TRY(hipHostMalloc(&st->pinned, 2 * pinned_want, hipHostMallocDefault));
+    st->pinned_bytes = 2 * pinned_want;
+  }
+  st->capacity = (uint32_t)std::min<uint64_t>(0x7fffffffu, std::max<uint64_t>(st->capacity, 3 * (uint64_t)a.num_problems));
+  for (int attempt = 0; attempt < 2; attempt++) {
+    const uint32_t capacity = st->capacity;
+    const uint64_t entries1 = st->entries + capacity;
+    if (entries1 >= 0xFFFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 heap entries");
+    const uint64_t cand = 2 * entries1;  // every entry is a candidate of its two videos
+    if (!(s = st->entry.reserve(entries1, st->entries, stream)).ok() || !(s = st->runs.reserve(capacity)).ok() ||
+        !(s = st->sorted.reserve(capacity)).ok() || !(s = st->run_count.reserve(1)).ok() ||
+        !(s = st->count.reserve(std::max<uint64_t>(new_buckets, 1))).ok() || !(s = st->fill.reserve(std::max<uint64_t>(new_buckets, 1))).ok() ||
+        !(s = st->lstart.reserve(new_buckets + 1)).ok() || !(s = st->lvalid.reserve(std::max<uint64_t>(new_buckets, 1))).ok() ||
+        !(s = st->sums.reserve((new_buckets + kScanBlock - 1) / kScanBlock + 1)).ok() || !(s = st->ctl.reserve(8)).ok() ||
+        !(s = st->large_list.reserve(capacity / (kEpilogueBucketLimit + 1) + 1)).ok() || !(s = st->flag.reserve(a.n1)).ok() ||
+        !(s = st->list.reserve(a.n1)).ok() || !(s = st->results.reserve(a.n1)).ok() || !(s = st->cand.reserve(cand)).ok() ||
+        !(s = st->links.reserve(cand)).ok())
+      return s;
+    if (!st->large_attr_set) {
+      NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pair_entries_large_kernel<ColumnMajorPairs, uint64_t>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kEpilogueLargeLimit * sizeof(unsigned long long))));
+      st->large_attr_set = true;
+    }
+    // the scan of the new pairs only (every form eligible), behind the uploads on the same stream
+    if (!(s = gpu_hamming_runs_device(st->hash.ptr(), a.seqs, a.num_seqs, a.problems, a.num_problems, a.threshold, st->runs.ptr,
+                                      capacity, st->run_count.ptr, false, false)).ok())
+      return s;
+    NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr, 0, 8 * sizeof(uint32_t), stream));
+    if (new_buckets) {
+      RunSegments segs;
+      std::memset(&segs, 0, sizeof(segs));
+      segs.count = 1;
+      segs.found[0] = st->run_count.ptr;
+      segs.runs[0] = st->runs.ptr;
+      segs.capacity[0] = capacity;
+      const EpilogueParams pr = index_params(st, a, new_buckets);
+      const uint32_t run_grid = (uint32_t)std::min<uint64_t>(4096, ((uint64_t)capacity + 255) / 256);
+      const uint32_t scan_blocks = (uint32_t)((new_buckets + kScanBlock - 1) / kScanBlock);
+      NEEDLE_HIP_TRY(hipMemsetAsync(st->count.ptr, 0, new_buckets * sizeof(uint32_t), stream));
+      NEEDLE_HIP_TRY(hipMemsetAsync(st->fill.ptr, 0, new_buckets * sizeof(uint32_t), stream));
+      {
+        KernelTimer timer("index_buckets", stream);
+        hipLaunchKernelGGL(bucket_count_kernel, dim3(run_grid), dim3(256), 0, stream, segs, pr.buckets, st->count.ptr);
+        hipLaunchKernelGGL(scan_block_sums_kernel, dim3(scan_blocks), dim3(256), 0, stream, st->count.ptr, pr.buckets, st->sums.ptr);
+        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, st->sums.ptr, scan_blocks);
+        hipLaunchKernelGGL(scan_apply_kernel, dim3(scan_blocks), dim3(256), 0, stream, st->count.ptr, pr.buckets, st->sums.ptr, st->lstart.ptr);
+        hipLaunchKernelGGL(bucket_scatter_kernel, dim3(run_grid), dim3(256), 0, stream, segs, pr.buckets, st->lstart.ptr, st->fill.ptr,
+                           st->sorted.ptr);
+      }
+      {
+        KernelTimer timer("index_entries", stream);
+        DeviceEntry *entries = st->entry.ptr() + st->entries;  // the new pairs' entries go straight in behind the committed ones
+        hipLaunchKernelGGL((pair_entries_kernel<ColumnMajorPairs, uint64_t>), dim3((pr.buckets + 63) / 64), dim3(64), 0, stream, pr,
+                           st->lstart.ptr, st->sorted.ptr, st->row_len.ptr(), st->row_ts.ptr(), st->row_seek.ptr(), st->ts_table.ptr(), entries,
+                           st->lvalid.ptr, st->ctl.ptr + 2, st->ctl.ptr + 3, st->large_list.ptr, first);
+        hipLaunchKernelGGL((pair_entries_large_kernel<ColumnMajorPairs, uint64_t>), dim3(512), dim3(256),
+                           kEpilogueLargeLimit * sizeof(unsigned long long), stream, pr, st->lstart.ptr, st->sorted.ptr, st->row_len.ptr(),
+                           st->row_ts.ptr(), st->row_seek.ptr(), st->ts_table.ptr(), entries, st->lvalid.ptr, st->ctl.ptr + 3,
+                           st->large_list.ptr, first);
+        hipLaunchKernelGGL(index_store_buckets_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (new_buckets + 255) / 256)), dim3(256), 0,
+                           stream, (uint32_t)new_buckets, st->lstart.ptr, st->lvalid.ptr, (uint32_t)st->entries,
+                           st->start.ptr() + st->buckets, st->valid.ptr() + st->buckets);
+      }
+      NEEDLE_HIP_TRY(hipGetLastError());
+    }
+    if (!(s = index_best_and_copy(st, a, new_buckets, stream, out)).ok()) return s;
+    if (out->found <= capacity) {
+      out->runs.clear();
+      if ((out->failed & kEpilogueBucketTooLarge) && out->found) {  // the host computes this append's entries (index.cpp)
+        out->runs.resize(out->found);
+        NEEDLE_HIP_TRY(hipMemcpy(out->runs.data(), st->runs.ptr, (size_t)out->found * sizeof(NeedleHipRun), hipMemcpyDeviceToHost));
+      }
+      return Status::Ok();
+    }
+    st->capacity = out->found;  // the scan is deterministic: a second pass with the exact size fits
+  }
+  return Status::Make(NeedleError_Unknown, "index append: run list did not fit after resize");
+}
+
+Status gpu_index_append_host_entries(IndexStore *st, const IndexAppend &a, const std::vector<uint32_t> &start,
+                                     const std::vector<uint32_t> &valid, const std::vector<IndexEntry> &entries, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  hipStream_t stream = library_stream();
+  const uint64_t first = (uint64_t)a.n0 * (a.n0 - (a.n0 ? 1 : 0)) / 2;
+  const uint64_t new_buckets = ((uint64_t)a.n1 * (a.n1 - 1) / 2 - first) * a.regions;
+  if (start.size() != new_buckets || valid.size() != new_buckets || st->entries + entries.size() > st->entry.buf.count)
+    return Status::Make(NeedleError_InvalidArgument, "index append: host entries do not fit the append");
+  std::vector<uint32_t> shifted(start);
+  for (uint32_t &x : shifted) x += (uint32_t)st->entries;
+  if (!entries.empty())
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->entry.ptr() + st->entries, entries.data(), entries.size() * sizeof(IndexEntry), hipMemcpyHostToDevice, stream));
+  if (new_buckets) {
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->start.ptr() + st->buckets, shifted.data(), new_buckets * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->valid.ptr() + st->buckets, valid.data(), new_buckets * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  }
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr + 2, 0, sizeof(uint32_t), stream));  // the failure word
+  const uint32_t found = out->found;
+  Status s = index_best_and_copy(st, a, new_buckets, stream, out);
+  out->found = found;
+  return s;
+}
+
+void index_store_commit(IndexStore *st, const IndexAppend &a, uint32_t found) {
+  const uint64_t first = (uint64_t)a.n0 * (a.n0 - (a.n0 ? 1 : 0)) / 2;
+  st->buckets += ((uint64_t)a.n1 * (a.n1 - 1) / 2 - first) * a.regions;
+  st->entries += found;
+  st->rows += a.num_rows;
+  st->ts += a.num_ts;
+  st->hashes += a.num_hashes;
+  st->n = a.n1;
 }
 
 }  // namespace needle

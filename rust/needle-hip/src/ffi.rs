@@ -41,6 +41,11 @@ pub struct NeedleHipLibrary {
 }
 
 #[repr(C)]
+pub struct NeedleHipIndex {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct NeedleHipSearchResult {
     pub has_result: bool,
@@ -197,6 +202,13 @@ extern "C" {
         output: *mut *mut NeedleHipLibrary,
     ) -> NeedleError;
     pub fn needle_hip_library_free(library: *mut NeedleHipLibrary);
+    // ---- incremental index (include/needle_hip.h "Incremental index") ----
+    pub fn needle_hip_index_new(comparator: *const NeedleAudioComparator, output: *mut *mut NeedleHipIndex) -> NeedleError;
+    pub fn needle_hip_index_free(index: *mut NeedleHipIndex);
+    pub fn needle_hip_index_len(index: *const NeedleHipIndex) -> usize;
+    pub fn needle_hip_index_add(index: *mut NeedleHipIndex, frame_hashes: *const *const FrameHashes, k: usize) -> NeedleError;
+    pub fn needle_hip_index_results(index: *const NeedleHipIndex, results: *mut NeedleHipSearchResult, n: usize) -> NeedleError;
+    pub fn needle_hip_index_pairs_searched(index: *const NeedleHipIndex, total: *mut u64, last: *mut u64) -> NeedleError;
     /// 1..=MAX_CHANNELS interleaved channels -> mono, `(sum of a frame) / channels` with C truncation; `out[i]` holds
     /// `num_values[i] / channels` values.
     pub fn needle_hip_downmix_host(

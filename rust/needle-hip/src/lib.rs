@@ -422,6 +422,69 @@ impl<P: AsRef<Path>> Comparator<P> {
     }
 }
 
+/// An incremental search index (include/needle_hip.h "Incremental index"): `results()` equals
+/// `Comparator::run_with_frame_hashes` over every video added so far, in insertion order (one slot per video, `None` where
+/// that call pushes no result); `add` searches only the pairs it adds.  The comparator's parameters are copied at
+/// creation.  One GPU: the device current at creation.
+pub struct Index {
+    raw: *mut ffi::NeedleHipIndex,
+}
+
+unsafe impl Send for Index {}
+
+impl Index {
+    pub fn new<P: AsRef<Path>>(comparator: &Comparator<P>) -> Result<Self> {
+        let handle = comparator.handle()?;
+        let mut raw = ptr::null_mut();
+        let status = unsafe { check(ffi::needle_hip_index_new(handle, &mut raw)) };
+        unsafe { ffi::needle_audio_comparator_free(handle) };
+        status?;
+        Ok(Index { raw })
+    }
+
+    /// Appends the videos (their hashes are copied).  On error the index is as it was before the call.
+    pub fn add(&mut self, frame_hashes: &[&FrameHashes]) -> Result<()> {
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        unsafe { check(ffi::needle_hip_index_add(self.raw, raw.as_ptr(), raw.len())) }
+    }
+
+    pub fn len(&self) -> usize {
+        unsafe { ffi::needle_hip_index_len(self.raw) }
+    }
+
+    pub fn is_empty(&self) -> bool {
+        self.len() == 0
+    }
+
+    pub fn results(&self) -> Result<Vec<Option<SearchResult>>> {
+        let mut results = vec![ffi::NeedleHipSearchResult::default(); self.len()];
+        unsafe { check(ffi::needle_hip_index_results(self.raw, results.as_mut_ptr(), results.len()))? };
+        let span = |a: u64, b: u64| (Duration::from_nanos(a), Duration::from_nanos(b));
+        Ok(results
+            .into_iter()
+            .map(|r| {
+                r.has_result.then(|| SearchResult {
+                    opening: r.has_opening.then(|| span(r.opening_start_ns, r.opening_end_ns)),
+                    ending: r.has_ending.then(|| span(r.ending_start_ns, r.ending_end_ns)),
+                })
+            })
+            .collect())
+    }
+
+    /// (total, last): video pairs handed to the scan over the index's life and by the last `add`.
+    pub fn pairs_searched(&self) -> Result<(u64, u64)> {
+        let (mut total, mut last) = (0u64, 0u64);
+        unsafe { check(ffi::needle_hip_index_pairs_searched(self.raw, &mut total, &mut last))? };
+        Ok((total, last))
+    }
+}
+
+impl Drop for Index {
+    fn drop(&mut self) {
+        unsafe { ffi::needle_hip_index_free(self.raw) };
+    }
+}
+
 /// Number of HIP devices the library sees (0 on a host without a GPU: every compute call then fails loudly).
 pub fn device_count() -> Result<i32> {
     let mut n = 0;
