@@ -645,6 +645,9 @@ Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan
         const bool busy = other.consumed_valid && hipEventQuery(other.consumed) == hipErrorNotReady;
         (void)hipGetLastError();
         if (!busy) stft = stream;
+        if (getenv("NEEDLE_HIP_TRACE"))
+          std::fprintf(stderr, "[needle_hip] pipelined first pass: pipe %d, %s\n", pipe,
+                       stft != stream ? "beside the other pipe" : "alone on the library stream");
       }
       DeviceBuffer<double> &chroma_buf = pp ? pp->chroma : ws->chroma;
       if (!(s = chroma_buf.reserve(frames * kBands)).ok()) return s;

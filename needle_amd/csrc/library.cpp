@@ -817,6 +817,14 @@ NeedleError job_search_and_gather(NeedleHipLibrary *lib, const NeedleAudioCompar
                                             reinterpret_cast<NeedleHipRun *>(mine + NeedleHipLibrary::kSlabHeader), j.slab_runs,
                                             reinterpret_cast<uint32_t *>(mine), false);
   if (e != NeedleError_Ok) return e;
+  {
+    // the form of THIS job's scan, taken as it is enqueued: by job_end the process's last launch may be another job's,
+    // with another comparator (threshold) and so another form
+    int32_t form = 0;
+    uint64_t products = 0;
+    gpu_scan_last_launch(&form, &products);
+    j.scan_form = (uint32_t)form;
+  }
   hipStream_t stream = library_stream(), down = download_stream();
   if (hipEventRecord(j.searched, stream) != hipSuccess || hipStreamWaitEvent(down, j.searched, 0) != hipSuccess)
     return report(Status::Make(NeedleError_Unknown, "stream ordering failed"));
@@ -1264,12 +1272,6 @@ enum NeedleError needle_hip_library_job_end(NeedleHipLibrary *lib, const struct 
     }
     j.ran_device_epilogue = device_results != nullptr;
     j.ran_sharded = sharded;
-    {
-      int32_t form = 0;
-      uint64_t products = 0;
-      gpu_scan_last_launch(&form, &products);  // (of this process's last scan launch: this job's, or the next one's -- the same shape)
-      j.scan_form = (uint32_t)form;
-    }
     if (!device_results) {
       const std::vector<const FrameHashesData *> fh = lib->shell_pointers();
       if (j.directed) {  // this rank's videos' runs are what it received: down they come, once
