@@ -268,7 +268,7 @@ enum NeedleError needle_hip_comparator_results_from_runs(const struct NeedleAudi
  * videos whose candidate list changed.  The index copies the comparator's parameters (threshold, minimum durations,
  * padding, include_endings) at creation: later changes to the comparator do not affect it.  The videos' hashes are
  * copied; the caller may free its FrameHashes after an add.  One GPU: the index runs on the device that was current when
- * it was created (no sharding across ranks).  No display, skip files or removal of a video. */
+ * it was created (no sharding across ranks).  Videos can be removed or replaced in place; no display or skip files. */
 typedef struct NeedleHipIndex NeedleHipIndex;
 enum NeedleError needle_hip_index_new(const struct NeedleAudioComparator *comparator, NeedleHipIndex **output);
 void needle_hip_index_free(NeedleHipIndex *index);
@@ -282,6 +282,20 @@ enum NeedleError needle_hip_index_results(const NeedleHipIndex *index, NeedleHip
 /* Video pairs handed to the scan: over the index's life (*total) and by the last successful add (*last).  A pair none
  * of whose sequences can hold a run long enough is left out, as in the full search.  Either pointer may be NULL. */
 enum NeedleError needle_hip_index_pairs_searched(const NeedleHipIndex *index, uint64_t *total, uint64_t *last);
+/* Removes the videos at k >= 1 distinct positions (< needle_hip_index_len).  The others keep their relative order.  Results
+ * then equal run_with_frame_hashes over the remaining list.  No pair is scanned (pairs_searched: *last = 0, total unchanged).
+ * Fails like a full search of that list would (padding / hash duration beyond the new winner's match end).  After any
+ * failure the index is exactly as it was.  NULL pointers: NeedleError_NullArgument; k == 0, a position out of range or
+ * repeated: NeedleError_InvalidArgument. */
+enum NeedleError needle_hip_index_remove(NeedleHipIndex *index, const size_t *positions, size_t k);
+/* Replaces the videos at k >= 1 distinct positions with frame_hashes[0..k), in place (positions[i] gets frame_hashes[i]).
+ * Only the pairs that involve a replaced video are scanned (*last = their number, total += it).  Otherwise it behaves like
+ * needle_hip_index_add (and fails like remove on bad positions). */
+enum NeedleError needle_hip_index_replace(NeedleHipIndex *index, const size_t *positions, const FrameHashes *const *frame_hashes,
+                                          size_t k);
+/* sizes[0] heap entries held (sum of the buckets' valid counts), sizes[1] entry slots in use, sizes[2] hashes in the
+ * device arena, sizes[3] timestamps in the device table.  After a remove or replace sizes[0] == sizes[1]. */
+enum NeedleError needle_hip_index_store_sizes(const NeedleHipIndex *index, uint64_t sizes[4]);
 
 /* ---- Library: an HBM-resident analyze+search job, shardable across GPUs ----------------------------
  * One object per process/GPU describing ALL videos of a job.  PCM of the videos this rank owns is

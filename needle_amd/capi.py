@@ -99,7 +99,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_host_threads", "needle_hip_fingerprint_audit_device", "needle_hip_library_audit",
     "needle_hip_scan_counts", "needle_hip_scan_last_launch", "needle_hip_epilogue_host_fallbacks",
     "needle_hip_index_new", "needle_hip_index_free", "needle_hip_index_len", "needle_hip_index_add",
-    "needle_hip_index_results", "needle_hip_index_pairs_searched"]
+    "needle_hip_index_results", "needle_hip_index_pairs_searched", "needle_hip_index_remove", "needle_hip_index_replace",
+    "needle_hip_index_store_sizes"]
 
 _LIB = None
 
@@ -574,8 +575,9 @@ class Comparator:
 
 
 class Index:
-    """An incremental search index (needle_hip_index_*): results() equals Comparator.run_with_frame_hashes over every video
-    added so far, in insertion order; add() searches only the pairs it adds.  The comparator's parameters are copied at
+    """An incremental search index (needle_hip_index_*): results() equals Comparator.run_with_frame_hashes over the
+    index's current list of videos; add() searches only the pairs it adds, remove() none, replace() those of the videos
+    replaced.  The comparator's parameters are copied at
     creation.  One GPU: the device current at creation."""
 
     def __init__(self, comparator: Comparator):
@@ -589,6 +591,28 @@ class Index:
         k = len(frame_hashes)
         ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
         check(lib().needle_hip_index_add(self._h, ptrs, k))
+
+    def remove(self, positions: Sequence[int]) -> None:
+        """Removes the videos at these distinct positions; the others keep their order.  On failure (NeedleError) the
+        index is as it was before the call."""
+        k = len(positions)
+        pos = (C.c_size_t * max(k, 1))(*positions)
+        check(lib().needle_hip_index_remove(self._h, pos, C.c_size_t(k)))
+
+    def replace(self, positions: Sequence[int], frame_hashes: Sequence[FrameHashes]) -> None:
+        """Replaces the video at positions[i] with frame_hashes[i], in place; searches only the pairs of those videos."""
+        k = len(positions)
+        if len(frame_hashes) != k:
+            raise ValueError("replace: one FrameHashes per position")
+        pos = (C.c_size_t * max(k, 1))(*positions)
+        ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
+        check(lib().needle_hip_index_replace(self._h, pos, ptrs, C.c_size_t(k)))
+
+    def store_sizes(self) -> Tuple[int, int, int, int]:
+        """(heap entries held, entry slots in use, hashes in the device arena, timestamps in the device table)."""
+        sizes = (C.c_uint64 * 4)()
+        check(lib().needle_hip_index_store_sizes(self._h, sizes))
+        return tuple(int(x) for x in sizes)
 
     def results(self) -> List[Optional[SearchResult]]:
         n = len(self)

@@ -831,6 +831,37 @@ enum NeedleError needle_hip_index_pairs_searched(const NeedleHipIndex *index, ui
   return NeedleError_Ok;
 }
 
+enum NeedleError needle_hip_index_remove(NeedleHipIndex *index, const size_t *positions, size_t k) {
+  if (!index || !positions) return NeedleError_NullArgument;
+  if (k == 0) return report(Status::Make(NeedleError_InvalidArgument, "index remove: no positions"));
+  return guarded([&]() -> NeedleError {
+    Status s = index->inner.remove(std::vector<size_t>(positions, positions + k));
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_index_replace(NeedleHipIndex *index, const size_t *positions, const FrameHashes *const *frame_hashes, size_t k) {
+  if (!index || !positions || !frame_hashes) return NeedleError_NullArgument;
+  if (k == 0) return report(Status::Make(NeedleError_InvalidArgument, "index replace: no positions"));
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    Status s = index->inner.replace(std::vector<size_t>(positions, positions + k), fh);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_index_store_sizes(const NeedleHipIndex *index, uint64_t sizes[4]) {
+  if (!index || !sizes) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = index->inner.store_sizes(sizes);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 }  // extern "C"
 
 // library.cpp needs these two without seeing the handle layouts twice

@@ -201,6 +201,11 @@ struct ColumnMajorPairs {  // an index append: problem / regions = p(i, j) - fir
   __device__ ColumnMajorPairs(const EpilogueParams &, uint64_t first_pair) : first(first_pair) {}
   __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const { column_pair_at(first + p, i, j); }
 };
+struct ListedPairs {  // an index edit: problem / regions = a listed pair, table[listed] = its id p(i, j) in the rebuilt store
+  const uint32_t *table;
+  __device__ ListedPairs(const EpilogueParams &, const uint32_t *pair_ids) : table(pair_ids) {}
+  __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const { column_pair_at(table[p], i, j); }
+};
 
 // A slab's runs into one block per destination rank (gpu_direct_runs).  A wave asks a block's counter once per destination
 // for all its lanes' runs (a returning atomic per run on `world` addresses would be the kernel).
@@ -794,6 +799,93 @@ __global__ __launch_bounds__(256) void index_list_kernel(uint32_t n0, uint32_t n
     if (v >= n0 || flag[v]) list[atomicAdd(count, 1u)] = v;
 }
 
+// ---- an index edit (removal / replacement): the store rebuilt under the new pair ids into the second set of buffers ----
+// The kept rows of the hash arena or of the timestamp table into the new one: a workgroup per row, consecutive elements.
+template <class T>
+__global__ __launch_bounds__(256) void index_copy_rows_kernel(const IndexSegment *__restrict__ rows, uint32_t num_rows,
+                                                              const T *__restrict__ from, T *__restrict__ to) {
+  for (uint32_t s = blockIdx.x; s < num_rows; s += gridDim.x) {
+    const IndexSegment g = rows[s];
+    for (uint64_t k = threadIdx.x; k < g.len; k += blockDim.x) to[g.dst + k] = from[g.src + k];
+  }
+}
+
+// A bucket of the rebuilt store whose pair is kept: its count and where its entries lie in the committed store.  Removal keeps
+// the relative order, so the old pair is (old i, old j) with the same roles.  The pairs with a fresh video are left to
+// index_edit_fresh_kernel.
+__global__ __launch_bounds__(256) void index_edit_buckets_kernel(uint32_t buckets, uint32_t regions, const uint32_t *__restrict__ old_of_new,
+                                                                 const uint32_t *__restrict__ old_start, const uint32_t *__restrict__ old_valid,
+                                                                 uint32_t *__restrict__ src, uint32_t *__restrict__ count) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < buckets; b += gridDim.x * blockDim.x) {
+    uint32_t i, j;
+    column_pair_at(b / regions, &i, &j);
+    const uint32_t oi = old_of_new[i], oj = old_of_new[j];
+    if (oi == kIndexFresh || oj == kIndexFresh) continue;
+    const uint64_t ob = (column_start(oj) + oi) * regions + b % regions;
+    src[b] = old_start[ob];
+    count[b] = old_valid[ob];
+  }
+}
+// ... and a listed pair's bucket: its entries were written behind the committed ones (`base`) by this edit
+__global__ __launch_bounds__(256) void index_edit_fresh_kernel(uint32_t listed, uint32_t regions, const uint32_t *__restrict__ pair_ids,
+                                                               const uint32_t *__restrict__ lstart, const uint32_t *__restrict__ lvalid,
+                                                               uint32_t base, uint32_t *__restrict__ src, uint32_t *__restrict__ count) {
+  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < listed; l += gridDim.x * blockDim.x) {
+    const uint64_t b = (uint64_t)pair_ids[l / regions] * regions + l % regions;
+    src[b] = base + lstart[l];
+    count[b] = lvalid[l];
+  }
+}
+
+// Every bucket's valid entries to its new start (start[0..buckets], start[buckets] = the total), so that the slots in use are
+// the entries held.  A lane per 16-byte word (an entry is three): consecutive lanes move consecutive words; a lane finds its
+// bucket by a binary search of the starts, the last one at or below its entry (empty buckets share their start).
+__global__ __launch_bounds__(256) void index_gather_kernel(uint32_t buckets, const uint32_t *__restrict__ start,
+                                                           const uint32_t *__restrict__ src, const uint4 *__restrict__ from,
+                                                           uint4 *__restrict__ to, uint64_t max_entries) {
+  const uint64_t words = 3 * min((uint64_t)start[buckets], max_entries);
+  for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < words; w += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t e = (uint32_t)(w / 3);
+    uint32_t lo = 0, hi = buckets;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) / 2;
+      if (start[mid] <= e) lo = mid;
+      else hi = mid;
+    }
+    to[w] = from[((uint64_t)src[lo] + (e - start[lo])) * 3 + w % 3];
+  }
+}
+
+// The videos whose candidate list an edit changed: every fresh video ...
+__global__ __launch_bounds__(256) void index_fresh_flags_kernel(uint32_t n, const uint32_t *__restrict__ old_of_new, uint32_t *__restrict__ flag) {
+  for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) flag[v] = old_of_new[v] == kIndexFresh ? 1u : 0u;
+}
+// ... every kept video with an entry in a pair of a video removed or replaced (the committed store, old ids) ...
+__global__ __launch_bounds__(256) void index_gone_partners_kernel(uint32_t n_old, uint32_t regions, const uint32_t *__restrict__ gone,
+                                                                  uint32_t num_gone, const uint32_t *__restrict__ valid,
+                                                                  const uint32_t *__restrict__ new_of_old, uint32_t *__restrict__ flag) {
+  const uint64_t total = (uint64_t)num_gone * n_old;
+  for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t x = gone[t / n_old], q = (uint32_t)(t % n_old);
+    if (q == x || new_of_old[q] == kIndexFresh) continue;
+    const uint64_t p = q < x ? column_start(x) + q : column_start(q) + x;
+    bool any = false;
+    for (uint32_t r = 0; r < regions; r++) any = any || valid[p * regions + r] != 0;
+    if (any) flag[new_of_old[q]] = 1u;
+  }
+}
+// ... and every video with an entry in a listed pair
+__global__ __launch_bounds__(256) void index_fresh_partners_kernel(uint32_t listed, uint32_t regions, const uint32_t *__restrict__ pair_ids,
+                                                                   const uint32_t *__restrict__ lvalid, uint32_t *__restrict__ flag) {
+  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < listed; l += gridDim.x * blockDim.x) {
+    if (lvalid[l] == 0) continue;
+    uint32_t i, j;
+    column_pair_at(pair_ids[l / regions], &i, &j);
+    flag[i] = 1u;
+    flag[j] = 1u;
+  }
+}
+
 // A device array that keeps its contents when it grows (amortised doubling, a device-to-device copy on `stream`).
 template <class T>
 struct GrowBuffer {
@@ -998,19 +1090,25 @@ struct IndexStore {
   // committed: what the index holds (an append that fails leaves these, and what lies below them, as they were)
   uint32_t n = 0;
   uint64_t buckets = 0, entries = 0, rows = 0, ts = 0, hashes = 0;
-  // resident, growing only: the per-pair entries and, per bucket b = p(i, j) * regions + r, where they start and how many
+  // resident: the per-pair entries and, per bucket b = p(i, j) * regions + r, where they start and how many
   GrowBuffer<DeviceEntry> entry;
   GrowBuffer<uint32_t> start, valid, row_len, row_ts, hash;
   GrowBuffer<uint64_t> row_seek, ts_table, hash_duration;
+  // the second set an edit gathers the rebuilt store into (index_store_switch swaps the two)
+  GrowBuffer<DeviceEntry> entry2;
+  GrowBuffer<uint32_t> start2, valid2, row_len2, row_ts2, hash2;
+  GrowBuffer<uint64_t> row_seek2, ts_table2, hash_duration2;
+  DeviceBuffer<uint32_t> src, old_of_new, new_of_old, gone, pair_ids;  // an edit's maps
+  DeviceBuffer<IndexSegment> segments;
   // an append's scratch
   DeviceBuffer<uint32_t> count, fill, lstart, sums, lvalid, ctl, large_list, flag, list, links, run_count;
   DeviceBuffer<NeedleHipRun> runs, sorted;
   DeviceBuffer<Candidate> cand;
   DeviceBuffer<NeedleHipSearchResult> results;
-  void *pinned = nullptr;  // [found, failed, listed, pad] + list[n1] + results[n1]
+  void *pinned = nullptr;  // [found, failed, listed, held] + list[n1] + results[n1]
   size_t pinned_bytes = 0;
   uint32_t capacity = 1u << 16;  // of the run list; grows to what an append found
-  bool large_attr_set = false;
+  bool large_attr_set = false, listed_attr_set = false;
   bool used = false;  // an append has enqueued work (a store made without a device never has)
   int device = 0;
   ~IndexStore() {
@@ -1041,14 +1139,15 @@ void index_store_free(IndexStore *st) {
 
 namespace {
 
-EpilogueParams index_params(const IndexStore *st, const IndexAppend &a, uint64_t buckets) {
+template <class Op>  // IndexAppend or IndexEdit; n = the videos after it
+EpilogueParams index_params(const Op &a, uint32_t n, uint64_t buckets) {
   EpilogueParams pr;
   std::memset(&pr, 0, sizeof(pr));
-  pr.n = a.n1;
+  pr.n = n;
   pr.regions = pr.rows_per_video = a.regions;
   pr.buckets = (uint32_t)buckets;
   pr.v0 = 0;
-  pr.v1 = a.n1;
+  pr.v1 = n;
   pr.bound = a.threshold + a.threshold / 2;
   pr.include_endings = a.include_endings ? 1u : 0u;
   pr.min_duration[0] = a.min_opening_duration;
@@ -1058,9 +1157,30 @@ EpilogueParams index_params(const IndexStore *st, const IndexAppend &a, uint64_t
   return pr;
 }
 
+// the runs found, the failure word, the listed videos' results (and `held`, an edit's entry count) into pinned memory; the wait
+Status index_copy_out(IndexStore *st, uint32_t n, const uint32_t *held, hipStream_t stream, IndexAppendOut *out) {
+  uint32_t *head = static_cast<uint32_t *>(st->pinned);
+  uint32_t *list = head + 4;
+  NeedleHipSearchResult *results = reinterpret_cast<NeedleHipSearchResult *>(list + ((n + 1) & ~1u));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(head, st->run_count.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(head + 1, st->ctl.ptr + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(head + 2, st->ctl.ptr + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  if (held) NEEDLE_HIP_TRY(hipMemcpyAsync(head + 3, held, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(list, st->list.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(results, st->results.ptr, (size_t)n * sizeof(NeedleHipSearchResult), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  out->found = head[0];
+  out->failed = head[1];
+  out->held = held ? head[3] : 0;
+  const uint32_t listed = std::min(head[2], n);
+  out->videos.assign(list, list + listed);
+  out->results.assign(results, results + listed);
+  return Status::Ok();
+}
+
 // mark the changed videos, list them, best_match over the list; then the copies into pinned memory and a wait for them
 Status index_best_and_copy(IndexStore *st, const IndexAppend &a, uint64_t new_buckets, hipStream_t stream, IndexAppendOut *out) {
-  const EpilogueParams pr = index_params(st, a, new_buckets);
+  const EpilogueParams pr = index_params(a, a.n1, new_buckets);
   const uint64_t first = (uint64_t)a.n0 * (a.n0 - (a.n0 ? 1 : 0)) / 2;
   NEEDLE_HIP_TRY(hipMemsetAsync(st->flag.ptr, 0, std::max<size_t>(a.n1, 1) * sizeof(uint32_t), stream));
   NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr, 0, 2 * sizeof(uint32_t), stream));  // the candidate cursor
@@ -1081,21 +1201,7 @@ Status index_best_and_copy(IndexStore *st, const IndexAppend &a, uint64_t new_bu
                        (const uint64_t *)st->hash_duration.ptr());
   }
   NEEDLE_HIP_TRY(hipGetLastError());
-  uint32_t *head = static_cast<uint32_t *>(st->pinned);
-  uint32_t *list = head + 4;
-  NeedleHipSearchResult *results = reinterpret_cast<NeedleHipSearchResult *>(list + ((a.n1 + 1) & ~1u));
-  NEEDLE_HIP_TRY(hipMemcpyAsync(head, st->run_count.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  NEEDLE_HIP_TRY(hipMemcpyAsync(head + 1, st->ctl.ptr + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  NEEDLE_HIP_TRY(hipMemcpyAsync(head + 2, st->ctl.ptr + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  NEEDLE_HIP_TRY(hipMemcpyAsync(list, st->list.ptr, (size_t)a.n1 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  NEEDLE_HIP_TRY(hipMemcpyAsync(results, st->results.ptr, (size_t)a.n1 * sizeof(NeedleHipSearchResult), hipMemcpyDeviceToHost, stream));
-  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
-  out->found = head[0];
-  out->failed = head[1];
-  const uint32_t listed = std::min(head[2], a.n1);
-  out->videos.assign(list, list + listed);
-  out->results.assign(results, results + listed);
-  return Status::Ok();
+  return index_copy_out(st, a.n1, nullptr, stream, out);
 }
 
 }  // namespace
@@ -1172,7 +1278,7 @@ Status gpu_index_append(IndexStore *st, const IndexAppend &a, IndexAppendOut *ou
       segs.found[0] = st->run_count.ptr;
       segs.runs[0] = st->runs.ptr;
       segs.capacity[0] = capacity;
-      const EpilogueParams pr = index_params(st, a, new_buckets);
+      const EpilogueParams pr = index_params(a, a.n1, new_buckets);
       const uint32_t run_grid = (uint32_t)std::min<uint64_t>(4096, ((uint64_t)capacity + 255) / 256);
       const uint32_t scan_blocks = (uint32_t)((new_buckets + kScanBlock - 1) / kScanBlock);
       NEEDLE_HIP_TRY(hipMemsetAsync(st->count.ptr, 0, new_buckets * sizeof(uint32_t), stream));
@@ -1247,6 +1353,287 @@ void index_store_commit(IndexStore *st, const IndexAppend &a, uint32_t found) {
   st->ts += a.num_ts;
   st->hashes += a.num_hashes;
   st->n = a.n1;
+}
+
+
+// ---- an edit: removal / replacement --------------------------------------------------------------------------------------
+namespace {
+
+uint64_t edit_buckets(const IndexEdit &e) { return (uint64_t)e.n_new * (e.n_new ? e.n_new - 1 : 0) / 2 * e.regions; }
+
+// The first half of an edit: the maps and the new rows' tables uploaded, the kept rows gathered into the second arena and
+// timestamp table, the fresh rows behind them; the scan of the listed pairs and their entries behind the committed ones.
+Status index_edit_tables(IndexStore *st, const IndexEdit &e, uint32_t capacity, hipStream_t stream) {
+  const uint32_t R = e.regions;
+  const uint64_t rows = (uint64_t)e.n_new * R, listed = (uint64_t)e.num_pairs * R;
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->old_of_new.ptr, e.old_of_new, e.n_new * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->new_of_old.ptr, e.new_of_old, e.n_old * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  if (e.num_gone) NEEDLE_HIP_TRY(hipMemcpyAsync(st->gone.ptr, e.gone, e.num_gone * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  if (e.num_pairs) NEEDLE_HIP_TRY(hipMemcpyAsync(st->pair_ids.ptr, e.pair_ids, e.num_pairs * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  if (e.num_hash_rows)
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->segments.ptr, e.hash_rows, e.num_hash_rows * sizeof(IndexSegment), hipMemcpyHostToDevice, stream));
+  if (e.num_ts_rows)
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->segments.ptr + e.num_hash_rows, e.ts_rows, e.num_ts_rows * sizeof(IndexSegment),
+                                  hipMemcpyHostToDevice, stream));
+  if (e.num_hashes)
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->hash2.ptr() + (e.total_hashes - e.num_hashes), e.hashes, e.num_hashes * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, stream));
+  if (e.num_ts)
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->ts_table2.ptr() + (e.total_ts - e.num_ts), e.ts, e.num_ts * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->row_len2.ptr(), e.row_len, rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->row_ts2.ptr(), e.row_ts, rows * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->row_seek2.ptr(), 0, rows * sizeof(uint64_t), stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->hash_duration2.ptr(), e.hash_duration, e.n_new * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+  {
+    KernelTimer timer("index_copy_rows", stream);
+    if (e.num_hash_rows)
+      hipLaunchKernelGGL(index_copy_rows_kernel<uint32_t>, dim3((uint32_t)std::min<size_t>(e.num_hash_rows, 4096)), dim3(256), 0, stream,
+                         (const IndexSegment *)st->segments.ptr, (uint32_t)e.num_hash_rows, (const uint32_t *)st->hash.ptr(), st->hash2.ptr());
+    if (e.num_ts_rows)
+      hipLaunchKernelGGL(index_copy_rows_kernel<uint64_t>, dim3((uint32_t)std::min<size_t>(e.num_ts_rows, 4096)), dim3(256), 0, stream,
+                         (const IndexSegment *)(st->segments.ptr + e.num_hash_rows), (uint32_t)e.num_ts_rows,
+                         (const uint64_t *)st->ts_table.ptr(), st->ts_table2.ptr());
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr, 0, 8 * sizeof(uint32_t), stream));
+  if (!e.num_problems) {
+    NEEDLE_HIP_TRY(hipMemsetAsync(st->run_count.ptr, 0, sizeof(uint32_t), stream));
+  } else {
+    Status s = gpu_hamming_runs_device(st->hash2.ptr(), e.seqs, rows, e.problems, e.num_problems, e.threshold, st->runs.ptr, capacity,
+                                       st->run_count.ptr, false, false);
+    if (!s.ok()) return s;
+  }
+  if (!listed) return Status::Ok();
+  RunSegments segs;
+  std::memset(&segs, 0, sizeof(segs));
+  segs.count = 1;
+  segs.found[0] = st->run_count.ptr;
+  segs.runs[0] = st->runs.ptr;
+  segs.capacity[0] = capacity;
+  const EpilogueParams pr = index_params(e, e.n_new, listed);
+  const uint32_t run_grid = (uint32_t)std::min<uint64_t>(4096, ((uint64_t)capacity + 255) / 256);
+  const uint32_t scan_blocks = (uint32_t)((listed + kScanBlock - 1) / kScanBlock);
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->count.ptr, 0, listed * sizeof(uint32_t), stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->fill.ptr, 0, listed * sizeof(uint32_t), stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->lvalid.ptr, 0, listed * sizeof(uint32_t), stream));  // (a bucket the device does not order: 0)
+  {
+    KernelTimer timer("index_buckets", stream);
+    hipLaunchKernelGGL(bucket_count_kernel, dim3(run_grid), dim3(256), 0, stream, segs, pr.buckets, st->count.ptr);
+    hipLaunchKernelGGL(scan_block_sums_kernel, dim3(scan_blocks), dim3(256), 0, stream, st->count.ptr, pr.buckets, st->sums.ptr);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, st->sums.ptr, scan_blocks);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3(scan_blocks), dim3(256), 0, stream, st->count.ptr, pr.buckets, st->sums.ptr, st->lstart.ptr);
+    hipLaunchKernelGGL(bucket_scatter_kernel, dim3(run_grid), dim3(256), 0, stream, segs, pr.buckets, st->lstart.ptr, st->fill.ptr, st->sorted.ptr);
+  }
+  {
+    KernelTimer timer("index_entries", stream);
+    DeviceEntry *entries = st->entry.ptr() + st->entries;  // behind the committed entries (not part of the store until gathered)
+    const uint32_t *pair_ids = st->pair_ids.ptr;
+    hipLaunchKernelGGL((pair_entries_kernel<ListedPairs, const uint32_t *>), dim3((pr.buckets + 63) / 64), dim3(64), 0, stream, pr,
+                       st->lstart.ptr, st->sorted.ptr, st->row_len2.ptr(), st->row_ts2.ptr(), st->row_seek2.ptr(), st->ts_table2.ptr(),
+                       entries, st->lvalid.ptr, st->ctl.ptr + 2, st->ctl.ptr + 3, st->large_list.ptr, pair_ids);
+    hipLaunchKernelGGL((pair_entries_large_kernel<ListedPairs, const uint32_t *>), dim3(512), dim3(256),
+                       kEpilogueLargeLimit * sizeof(unsigned long long), stream, pr, st->lstart.ptr, st->sorted.ptr, st->row_len2.ptr(),
+                       st->row_ts2.ptr(), st->row_seek2.ptr(), st->ts_table2.ptr(), entries, st->lvalid.ptr, st->ctl.ptr + 3,
+                       st->large_list.ptr, pair_ids);
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+
+// The second half: every bucket's count and source (kept pairs from the committed store, listed ones from this edit's
+// entries), their starts, the gather into the second entry buffer, the videos to recompute and their best match over the
+// rebuilt store; the copies and the wait.
+Status index_edit_rebuild(IndexStore *st, const IndexEdit &e, hipStream_t stream, IndexAppendOut *out) {
+  const uint32_t R = e.regions, n = e.n_new;
+  const uint64_t buckets = edit_buckets(e), listed = (uint64_t)e.num_pairs * R;
+  {
+    KernelTimer timer("index_rebuild", stream);
+    if (buckets) {
+      hipLaunchKernelGGL(index_edit_buckets_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (buckets + 255) / 256)), dim3(256), 0, stream,
+                         (uint32_t)buckets, R, (const uint32_t *)st->old_of_new.ptr, (const uint32_t *)st->start.ptr(),
+                         (const uint32_t *)st->valid.ptr(), st->src.ptr, st->valid2.ptr());
+      if (listed)
+        hipLaunchKernelGGL(index_edit_fresh_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (listed + 255) / 256)), dim3(256), 0, stream,
+                           (uint32_t)listed, R, (const uint32_t *)st->pair_ids.ptr, (const uint32_t *)st->lstart.ptr,
+                           (const uint32_t *)st->lvalid.ptr, (uint32_t)st->entries, st->src.ptr, st->valid2.ptr());
+      const uint32_t scan_blocks = (uint32_t)((buckets + kScanBlock - 1) / kScanBlock);
+      hipLaunchKernelGGL(scan_block_sums_kernel, dim3(scan_blocks), dim3(256), 0, stream, st->valid2.ptr(), (uint32_t)buckets, st->sums.ptr);
+      hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, stream, st->sums.ptr, scan_blocks);
+      hipLaunchKernelGGL(scan_apply_kernel, dim3(scan_blocks), dim3(256), 0, stream, st->valid2.ptr(), (uint32_t)buckets, st->sums.ptr,
+                         st->start2.ptr());
+    } else {
+      NEEDLE_HIP_TRY(hipMemsetAsync(st->start2.ptr(), 0, sizeof(uint32_t), stream));
+    }
+  }
+  if (buckets) {
+    KernelTimer timer("index_gather", stream);
+    const uint64_t max_entries = st->entry2.buf.count;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(8192, (3 * max_entries + 255) / 256);
+    hipLaunchKernelGGL(index_gather_kernel, dim3(std::max(grid, 1u)), dim3(256), 0, stream, (uint32_t)buckets, (const uint32_t *)st->start2.ptr(),
+                       (const uint32_t *)st->src.ptr, reinterpret_cast<const uint4 *>(st->entry.ptr()),
+                       reinterpret_cast<uint4 *>(st->entry2.ptr()), max_entries);
+  }
+  const EpilogueParams pr = index_params(e, n, buckets);
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr, 0, 2 * sizeof(uint32_t), stream));  // the candidate cursor
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr + 4, 0, sizeof(uint32_t), stream));  // videos listed
+  {
+    KernelTimer timer("index_best_match", stream);
+    hipLaunchKernelGGL(index_fresh_flags_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, (const uint32_t *)st->old_of_new.ptr, st->flag.ptr);
+    if (e.num_gone && e.n_old > 1) {
+      const uint64_t work = (uint64_t)e.num_gone * e.n_old;
+      hipLaunchKernelGGL(index_gone_partners_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (work + 255) / 256)), dim3(256), 0, stream, e.n_old,
+                         R, (const uint32_t *)st->gone.ptr, (uint32_t)e.num_gone, (const uint32_t *)st->valid.ptr(),
+                         (const uint32_t *)st->new_of_old.ptr, st->flag.ptr);
+    }
+    if (listed)
+      hipLaunchKernelGGL(index_fresh_partners_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (listed + 255) / 256)), dim3(256), 0, stream,
+                         (uint32_t)listed, R, (const uint32_t *)st->pair_ids.ptr, (const uint32_t *)st->lvalid.ptr, st->flag.ptr);
+    hipLaunchKernelGGL(index_list_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, n, (const uint32_t *)st->flag.ptr, st->ctl.ptr + 4,
+                       st->list.ptr);
+    hipLaunchKernelGGL((best_match_kernel<IndexVideos, const uint32_t *, const uint32_t *, const uint64_t *>), dim3(n), dim3(256), 0, stream,
+                       pr, st->start2.ptr(), st->valid2.ptr(), st->entry2.ptr(), st->cand.ptr,
+                       reinterpret_cast<unsigned long long *>(st->ctl.ptr), st->links.ptr, st->results.ptr, st->ctl.ptr + 2,
+                       (const uint32_t *)st->list.ptr, (const uint32_t *)(st->ctl.ptr + 4), (const uint64_t *)st->hash_duration2.ptr());
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  return index_copy_out(st, n, st->start2.ptr() + buckets, stream, out);
+}
+
+template <class T>
+void swap_buffers(GrowBuffer<T> &a, GrowBuffer<T> &b) {
+  std::swap(a.buf.ptr, b.buf.ptr);
+  std::swap(a.buf.count, b.buf.count);
+}
+
+}  // namespace
+
+Status gpu_index_edit(IndexStore *st, const IndexEdit &e, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != st->device) return Status::Make(NeedleError_InvalidArgument, "index: the current device is not the one the index was created on");
+  st->used = true;
+  if (e.n_old != st->n || e.n_new < 1 || e.regions < 1 || e.regions > 2)
+    return Status::Make(NeedleError_InvalidArgument, "index edit: inconsistent sizes");
+  hipStream_t stream = library_stream();
+  const uint64_t buckets = edit_buckets(e), listed = (uint64_t)e.num_pairs * e.regions, rows = (uint64_t)e.n_new * e.regions;
+  if (buckets >= 0xFFFFFFF0ull || e.total_hashes > UINT32_MAX || e.total_ts > UINT32_MAX)
+    return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
+  const uint64_t scan_len = std::max(buckets, listed);
+  if (!(s = st->hash2.reserve(std::max<uint64_t>(e.total_hashes, 1), 0, stream)).ok() ||
+      !(s = st->ts_table2.reserve(std::max<uint64_t>(e.total_ts, 1), 0, stream)).ok() ||
+      !(s = st->row_len2.reserve(rows, 0, stream)).ok() || !(s = st->row_ts2.reserve(rows, 0, stream)).ok() ||
+      !(s = st->row_seek2.reserve(rows, 0, stream)).ok() || !(s = st->hash_duration2.reserve(e.n_new, 0, stream)).ok() ||
+      !(s = st->start2.reserve(buckets + 1, 0, stream)).ok() || !(s = st->valid2.reserve(std::max<uint64_t>(buckets, 1), 0, stream)).ok() ||
+      !(s = st->src.reserve(std::max<uint64_t>(buckets, 1))).ok() || !(s = st->old_of_new.reserve(e.n_new)).ok() ||
+      !(s = st->new_of_old.reserve(std::max<uint32_t>(e.n_old, 1))).ok() || !(s = st->gone.reserve(std::max<size_t>(e.num_gone, 1))).ok() ||
+      !(s = st->pair_ids.reserve(std::max<size_t>(e.num_pairs, 1))).ok() ||
+      !(s = st->segments.reserve(std::max<size_t>(e.num_hash_rows + e.num_ts_rows, 1))).ok() ||
+      !(s = st->sums.reserve((scan_len + kScanBlock - 1) / kScanBlock + 1)).ok() || !(s = st->ctl.reserve(8)).ok() ||
+      !(s = st->run_count.reserve(1)).ok() || !(s = st->flag.reserve(e.n_new)).ok() || !(s = st->list.reserve(e.n_new)).ok() ||
+      !(s = st->results.reserve(e.n_new)).ok())
+    return s;
+  const size_t pinned_want = 16 + ((size_t)e.n_new + 2) * sizeof(uint32_t) + (size_t)e.n_new * sizeof(NeedleHipSearchResult);
+  if (pinned_want > st->pinned_bytes) {
+    if (st->pinned) (void)hipHostFree(st->pinned);
+    st->pinned = nullptr;
+    st->pinned_bytes = 0;
+    NEEDLE_HIP_TRY(hipHostMalloc(&st->pinned, 2 * pinned_want, hipHostMallocDefault));
+    st->pinned_bytes = 2 * pinned_want;
+  }
+  st->capacity = (uint32_t)std::min<uint64_t>(0x7fffffffu, std::max<uint64_t>(st->capacity, 3 * (uint64_t)e.num_problems));
+  for (int attempt = 0; attempt < 2; attempt++) {
+    const uint32_t capacity = st->capacity;
+    const uint64_t entries1 = st->entries + capacity;  // the committed slots and this edit's; the rebuilt store holds at most as many
+    if (entries1 >= 0xFFFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 heap entries");
+    const uint64_t cand = 2 * entries1;
+    if (!(s = st->entry.reserve(entries1, st->entries, stream)).ok() || !(s = st->entry2.reserve(entries1, 0, stream)).ok() ||
+        !(s = st->runs.reserve(capacity)).ok() || !(s = st->sorted.reserve(capacity)).ok() ||
+        !(s = st->count.reserve(std::max<uint64_t>(listed, 1))).ok() || !(s = st->fill.reserve(std::max<uint64_t>(listed, 1))).ok() ||
+        !(s = st->lstart.reserve(listed + 1)).ok() || !(s = st->lvalid.reserve(std::max<uint64_t>(listed, 1))).ok() ||
+        !(s = st->large_list.reserve(capacity / (kEpilogueBucketLimit + 1) + 1)).ok() || !(s = st->cand.reserve(cand)).ok() ||
+        !(s = st->links.reserve(cand)).ok())
+      return s;
+    if (!st->listed_attr_set) {
+      NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pair_entries_large_kernel<ListedPairs, const uint32_t *>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kEpilogueLargeLimit * sizeof(unsigned long long))));
+      st->listed_attr_set = true;
+    }
+    if (!(s = index_edit_tables(st, e, capacity, stream)).ok() || !(s = index_edit_rebuild(st, e, stream, out)).ok()) return s;
+    if (out->found <= capacity) {
+      out->runs.clear();
+      if ((out->failed & kEpilogueBucketTooLarge) && out->found) {  // the host computes the listed pairs' entries (index.cpp)
+        out->runs.resize(out->found);
+        NEEDLE_HIP_TRY(hipMemcpy(out->runs.data(), st->runs.ptr, (size_t)out->found * sizeof(NeedleHipRun), hipMemcpyDeviceToHost));
+      }
+      return Status::Ok();
+    }
+    st->capacity = out->found;  // the scan is deterministic: a second pass with the exact size fits
+  }
+  return Status::Make(NeedleError_Unknown, "index edit: run list did not fit after resize");
+}
+
+Status gpu_index_edit_host_entries(IndexStore *st, const IndexEdit &e, const std::vector<uint32_t> &start, const std::vector<uint32_t> &valid,
+                                   const std::vector<IndexEntry> &entries, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  hipStream_t stream = library_stream();
+  const uint64_t listed = (uint64_t)e.num_pairs * e.regions;
+  if (start.size() != listed || valid.size() != listed || st->entries + entries.size() > st->entry.buf.count || listed > st->lvalid.count)
+    return Status::Make(NeedleError_InvalidArgument, "index edit: host entries do not fit the edit");
+  if (!entries.empty())
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->entry.ptr() + st->entries, entries.data(), entries.size() * sizeof(IndexEntry), hipMemcpyHostToDevice, stream));
+  if (listed) {
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->lstart.ptr, start.data(), listed * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    NEEDLE_HIP_TRY(hipMemcpyAsync(st->lvalid.ptr, valid.data(), listed * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  }
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr + 2, 0, sizeof(uint32_t), stream));  // the failure word
+  const uint32_t found = out->found;
+  Status s = index_edit_rebuild(st, e, stream, out);
+  out->found = found;
+  return s;
+}
+
+void index_store_switch(IndexStore *st, const IndexEdit &e, uint32_t held) {
+  swap_buffers(st->entry, st->entry2);
+  swap_buffers(st->start, st->start2);
+  swap_buffers(st->valid, st->valid2);
+  swap_buffers(st->row_len, st->row_len2);
+  swap_buffers(st->row_ts, st->row_ts2);
+  swap_buffers(st->hash, st->hash2);
+  swap_buffers(st->row_seek, st->row_seek2);
+  swap_buffers(st->ts_table, st->ts_table2);
+  swap_buffers(st->hash_duration, st->hash_duration2);
+  st->n = e.n_new;
+  st->buckets = edit_buckets(e);
+  st->entries = held;
+  st->rows = (uint64_t)e.n_new * e.regions;
+  st->ts = e.total_ts;
+  st->hashes = e.total_hashes;
+}
+
+void index_store_clear(IndexStore *st) {
+  st->n = 0;
+  st->buckets = st->entries = st->rows = st->ts = st->hashes = 0;
+}
+
+Status index_store_sizes(IndexStore *st, uint64_t sizes[4]) {
+  sizes[0] = 0;
+  sizes[1] = st->entries;
+  sizes[2] = st->hashes;
+  sizes[3] = st->ts;
+  if (!st->buckets) return Status::Ok();
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != st->device) return Status::Make(NeedleError_InvalidArgument, "index: the current device is not the one the index was created on");
+  std::vector<uint32_t> valid(st->buckets);
+  hipStream_t stream = library_stream();
+  NEEDLE_HIP_TRY(hipMemcpyAsync(valid.data(), st->valid.ptr(), valid.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  for (uint32_t v : valid) sizes[0] += v;
+  return Status::Ok();
 }
 
 }  // namespace needle

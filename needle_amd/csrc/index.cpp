@@ -12,10 +12,63 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <unordered_map>
 
 #include "epilogue.h"
 
 namespace needle {
+
+namespace {
+
+void column_pair(uint64_t p, size_t *pi, size_t *pj) {  // p(i, j) = j (j - 1) / 2 + i, inverted
+  size_t j = (size_t)((1.0 + std::sqrt(1.0 + 8.0 * (double)p)) / 2.0);
+  while (j > 1 && (uint64_t)j * (j - 1) / 2 > p) j--;
+  while ((uint64_t)(j + 1) * j / 2 <= p) j++;
+  *pi = (size_t)(p - (uint64_t)j * (j - 1) / 2);
+  *pj = j;
+}
+
+// A bucket the device does not order (beyond kEpilogueLargeLimit runs, or rows the packed keys cannot stand for): the entries
+// of an operation's `buckets` buckets (tag = listed pair * R + region) from its run list, with the host form's own functions.
+// pair_of(listed pair) gives its two videos.  start[b] is relative to the operation's first entry.
+template <class PairOf, class RowSeq, class Video>
+void host_entries(const Comparator &cmp, size_t R, uint64_t buckets, const std::vector<NeedleHipRun> &runs, PairOf pair_of, RowSeq row_seq,
+                  Video video, std::vector<uint32_t> *start_out, std::vector<uint32_t> *valid_out, std::vector<IndexEntry> *entries_out) {
+  std::vector<uint32_t> start(buckets + 1, 0), valid(buckets, 0);
+  for (const NeedleHipRun &r : runs)
+    if (r.problem < buckets) start[r.problem + 1]++;
+  for (uint64_t b = 0; b < buckets; b++) start[b + 1] += start[b];
+  std::vector<NeedleHipRun> sorted(start[buckets]);
+  {
+    std::vector<uint32_t> fill(start.begin(), start.end() - 1);
+    for (const NeedleHipRun &r : runs)
+      if (r.problem < buckets) sorted[fill[r.problem]++] = r;
+  }
+  std::vector<IndexEntry> entries(runs.size());
+  std::vector<HeapEntry> tmp;
+  for (uint64_t b = 0; b < buckets; b++) {
+    const uint32_t lo = start[b], hi = start[b + 1];
+    if (hi == lo) continue;
+    std::sort(sorted.begin() + lo, sorted.begin() + hi, [](const NeedleHipRun &x, const NeedleHipRun &y) {
+      return x.src_end != y.src_end ? x.src_end > y.src_end : x.dst_end > y.dst_end;  // the reference's walk (:191-192)
+    });
+    const size_t r = b % R;
+    size_t i = 0, j = 0;
+    pair_of(b / R, &i, &j);
+    cmp.entries_from_runs(&sorted[lo], hi - lo, row_seq(i, r), row_seq(j, r), video(i).hash_duration, video(j).hash_duration, r == 0, &tmp);
+    for (size_t q = 0; q < tmp.size(); q++) {
+      const HeapEntry &e = tmp[q];
+      entries[lo + q] = IndexEntry{e.src_start, e.src_end, e.dst_start, e.dst_end, (uint32_t)e.score, e.src_match_hash, e.dst_match_hash, 0u};
+    }
+    valid[b] = (uint32_t)tmp.size();
+  }
+  start.pop_back();
+  start_out->swap(start);
+  valid_out->swap(valid);
+  entries_out->swap(entries);
+}
+
+}  // namespace
 
 Index::Index(const Comparator &comparator)
     : cmp_(comparator), include_endings_(comparator.include_endings()), regions_(comparator.include_endings() ? 2u : 1u) {}
@@ -41,6 +94,7 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
   // same region reads that table, as in run_with_frame_hashes' device epilogue)
   std::vector<NeedleHipSeq> seqs(seqs_);
   std::vector<uint32_t> min_len(min_len_), row_ts(row_ts_), new_row_len, new_row_ts, hashes;
+  std::vector<uint8_t> row_ok(row_ok_);
   std::vector<uint64_t> ts, hash_duration;
   uint64_t num_hashes = hashes_, num_ts = ts_;
   bool large_ok = large_ok_;
@@ -67,8 +121,10 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
         if (num_ts > UINT32_MAX) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 timestamps");
       }
       new_row_ts.push_back(row_ts.back());
-      large_ok = large_ok && seq.size() < 65536u;  // what pair_entries_large_kernel's packed keys stand on
-      for (size_t q = 1; q < seq.size() && large_ok; q++) large_ok = seq[q].ts > seq[q - 1].ts;
+      bool ok = seq.size() < 65536u;  // what pair_entries_large_kernel's packed keys stand on
+      for (size_t q = 1; q < seq.size() && ok; q++) ok = seq[q].ts > seq[q - 1].ts;
+      row_ok.push_back(ok);
+      large_ok = large_ok && ok;
     }
   }
   // the new pairs (i, j), j in [n0, n1), i < j, in column-major order; min_len and the pairs left out as in
@@ -121,40 +177,10 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
     // A bucket the device does not order (beyond kEpilogueLargeLimit runs, or rows the packed keys cannot stand for): this
     // append's new-pair entries are computed here from its run list, with the host form's own functions.
     note_epilogue_host_fallback("Index::add", out.runs.size(), n1);
-    const uint64_t buckets = new_pairs * R;
-    std::vector<uint32_t> start(buckets + 1, 0), valid(buckets, 0);
-    for (const NeedleHipRun &r : out.runs)
-      if (r.problem < buckets) start[r.problem + 1]++;
-    for (uint64_t b = 0; b < buckets; b++) start[b + 1] += start[b];
-    std::vector<NeedleHipRun> sorted(start[buckets]);
-    {
-      std::vector<uint32_t> fill(start.begin(), start.end() - 1);
-      for (const NeedleHipRun &r : out.runs)
-        if (r.problem < buckets) sorted[fill[r.problem]++] = r;
-    }
-    std::vector<IndexEntry> entries(out.runs.size());
-    std::vector<HeapEntry> tmp;
-    for (uint64_t b = 0; b < buckets; b++) {
-      const uint32_t lo = start[b], hi = start[b + 1];
-      if (hi == lo) continue;
-      std::sort(sorted.begin() + lo, sorted.begin() + hi, [](const NeedleHipRun &x, const NeedleHipRun &y) {
-        return x.src_end != y.src_end ? x.src_end > y.src_end : x.dst_end > y.dst_end;  // the reference's walk (:191-192)
-      });
-      const uint64_t p = first_pair + b / R;
-      const size_t r = b % R;
-      size_t j = (size_t)((1.0 + std::sqrt(1.0 + 8.0 * (double)p)) / 2.0);
-      while (j > 1 && (uint64_t)j * (j - 1) / 2 > p) j--;
-      while ((uint64_t)(j + 1) * j / 2 <= p) j++;
-      const size_t i = (size_t)(p - (uint64_t)j * (j - 1) / 2);
-      cmp_.entries_from_runs(&sorted[lo], hi - lo, row_seq(i, r), row_seq(j, r), video(i).hash_duration, video(j).hash_duration,
-                             r == 0, &tmp);
-      for (size_t q = 0; q < tmp.size(); q++) {
-        const HeapEntry &e = tmp[q];
-        entries[lo + q] = IndexEntry{e.src_start, e.src_end, e.dst_start, e.dst_end, (uint32_t)e.score, e.src_match_hash, e.dst_match_hash, 0u};
-      }
-      valid[b] = (uint32_t)tmp.size();
-    }
-    start.pop_back();
+    std::vector<uint32_t> start, valid;
+    std::vector<IndexEntry> entries;
+    host_entries(cmp_, R, new_pairs * R, out.runs, [&](uint64_t q, size_t *i, size_t *j) { column_pair(first_pair + q, i, j); }, row_seq,
+                 video, &start, &valid, &entries);
     if (!(s = gpu_index_append_host_entries(store_, a, start, valid, entries, &out)).ok()) return s;
   }
   if (out.failed)  // best_match_kernel: the winner's end minus padding / hash duration underflows (the reference panics)
@@ -168,11 +194,241 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
   hashes_ = num_hashes;
   ts_ = num_ts;
   large_ok_ = large_ok;
+  row_ok_.swap(row_ok);
   results_.resize(n1, NeedleHipSearchResult{});
   for (size_t q = 0; q < out.videos.size(); q++) results_[out.videos[q]] = out.results[q];
   pairs_last_ = searched;
   pairs_total_ += searched;
   return Status::Ok();
 }
+
+
+// Removal and replacement (DESIGN.md "Incremental index").  A pair's heap entries depend on the pair alone (its two sequences
+// and which of them is the source: the one first in the list), and removal keeps the others' relative order, so every kept
+// pair keeps its entries under its new id; a replacement keeps every position, and only the pairs of the replaced videos
+// are searched again.  find_best_match is a function of a video's candidate list in pair order: it is recomputed for the
+// fresh videos and for the videos with an entry in a pair that is dropped or new.  The store is rebuilt on the device.
+Status Index::remove(const std::vector<size_t> &positions) {
+  const size_t n0 = videos_.size();
+  if (positions.empty()) return Status::Make(NeedleError_InvalidArgument, "index remove: no positions");
+  std::vector<uint8_t> drop(n0, 0);
+  for (size_t p : positions) {
+    if (p >= n0) return Status::Make(NeedleError_InvalidArgument, "index remove: position out of range");
+    if (drop[p]) return Status::Make(NeedleError_InvalidArgument, "index remove: repeated position");
+    drop[p] = 1;
+  }
+  std::vector<uint32_t> old_of_new;
+  for (size_t q = 0; q < n0; q++)
+    if (!drop[q]) old_of_new.push_back((uint32_t)q);
+  return rebuild(old_of_new, std::vector<const FrameHashesData *>(old_of_new.size(), nullptr));
+}
+
+Status Index::replace(const std::vector<size_t> &positions, const std::vector<const FrameHashesData *> &fh) {
+  const size_t n0 = videos_.size();
+  if (positions.empty() || positions.size() != fh.size()) return Status::Make(NeedleError_InvalidArgument, "index replace: no positions");
+  std::vector<uint32_t> old_of_new(n0);
+  std::vector<const FrameHashesData *> fresh(n0, nullptr);
+  for (size_t q = 0; q < n0; q++) old_of_new[q] = (uint32_t)q;
+  for (size_t k = 0; k < positions.size(); k++) {
+    const size_t p = positions[k];
+    if (p >= n0) return Status::Make(NeedleError_InvalidArgument, "index replace: position out of range");
+    if (fresh[p]) return Status::Make(NeedleError_InvalidArgument, "index replace: repeated position");
+    old_of_new[p] = kIndexFresh;
+    fresh[p] = fh[k];
+  }
+  return rebuild(old_of_new, fresh);
+}
+
+Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector<const FrameHashesData *> &fresh) {
+  const size_t n0 = videos_.size(), n1 = old_of_new.size(), R = regions_;
+  if (n1 == 0) {  // every video removed: nothing is left to search or to hold
+    index_store_clear(store_);
+    videos_.clear();
+    seqs_.clear();
+    min_len_.clear();
+    row_ts_.clear();
+    row_ok_.clear();
+    results_.clear();
+    hashes_ = ts_ = 0;
+    large_ok_ = true;
+    pairs_last_ = 0;
+    return Status::Ok();
+  }
+  auto is_fresh = [&](size_t v) { return old_of_new[v] == kIndexFresh; };
+  auto video = [&](size_t v) -> const FrameHashesData & { return is_fresh(v) ? *fresh[v] : videos_[old_of_new[v]]; };
+  auto row_seq = [&](size_t v, size_t r) -> const std::vector<HashTs> & { return r == 0 ? video(v).opening : video(v).ending; };
+  if (include_endings_ && n1 > 1)
+    for (size_t v = 0; v < n1; v++)
+      if (video(v).ending.empty())  // comparator.rs:271-273 (every video is in some pair)
+        return Status::Make(NeedleError_Unknown, "no ending hash data present");
+  if (((uint64_t)n1 * (n1 - 1) / 2) * R >= 0xFFFFFFF0ull)
+    return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
+  std::vector<uint32_t> new_of_old(n0, kIndexFresh), gone;
+  for (size_t v = 0; v < n1; v++)
+    if (!is_fresh(v)) new_of_old[old_of_new[v]] = (uint32_t)v;
+  for (size_t q = 0; q < n0; q++)
+    if (new_of_old[q] == kIndexFresh) gone.push_back((uint32_t)q);
+  // The new rows.  Kept rows first, gathered on the device: their hashes in order, and each distinct run of the timestamp
+  // table they read once (rows that shared video 0's timestamps keep sharing them, whichever video is removed).  Then the
+  // fresh rows behind them, sharing the new video 0's timestamps where equal, as an append does.
+  std::vector<NeedleHipSeq> seqs(n1 * R);
+  std::vector<uint32_t> min_len(n1 * R), row_ts(n1 * R), row_len(n1 * R), hashes;
+  std::vector<uint8_t> row_ok(n1 * R);
+  std::vector<uint64_t> ts, hash_duration(n1);
+  std::vector<IndexSegment> hash_rows, ts_rows;
+  std::unordered_map<uint32_t, uint32_t> ts_at;  // a committed timestamp offset -> its offset in the new table
+  uint64_t num_hashes = 0, num_ts = 0;
+  for (size_t v = 0; v < n1; v++) {
+    if (is_fresh(v)) continue;
+    const size_t o = old_of_new[v];
+    hash_duration[v] = videos_[o].hash_duration;
+    for (size_t r = 0; r < R; r++) {
+      const size_t row = v * R + r, orow = o * R + r;
+      const uint32_t len = seqs_[orow].len;
+      seqs[row] = NeedleHipSeq{(uint32_t)num_hashes, len};
+      if (len) hash_rows.push_back(IndexSegment{seqs_[orow].offset, num_hashes, len});
+      num_hashes += len;
+      min_len[row] = min_len_[orow];
+      row_ok[row] = row_ok_[orow];
+      row_len[row] = len;
+      if (len == 0) continue;  // (row_ts 0: never read)
+      auto it = ts_at.find(row_ts_[orow]);
+      if (it != ts_at.end()) {
+        row_ts[row] = it->second;
+      } else {
+        ts_at.emplace(row_ts_[orow], (uint32_t)num_ts);
+        ts_rows.push_back(IndexSegment{row_ts_[orow], num_ts, len});
+        row_ts[row] = (uint32_t)num_ts;
+        num_ts += len;
+      }
+    }
+  }
+  for (size_t v = 0; v < n1; v++) {
+    if (!is_fresh(v)) continue;
+    hash_duration[v] = fresh[v]->hash_duration;
+    for (size_t r = 0; r < R; r++) {
+      const size_t row = v * R + r;
+      const std::vector<HashTs> &seq = row_seq(v, r);
+      if (num_hashes + seq.size() > UINT32_MAX)
+        return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
+      seqs[row] = NeedleHipSeq{(uint32_t)num_hashes, (uint32_t)seq.size()};
+      num_hashes += seq.size();
+      for (const HashTs &h : seq) hashes.push_back(h.hash);
+      min_len[row] = cmp_.min_run_length_for(seq, r == 0);
+      row_len[row] = (uint32_t)seq.size();
+      const std::vector<HashTs> &first = row_seq(0, r);
+      bool same = v > 0 && seq.size() == first.size();
+      for (size_t q = 0; q < seq.size() && same; q++) same = seq[q].ts == first[q].ts;
+      if (same) {
+        row_ts[row] = row_ts[r];
+      } else {
+        row_ts[row] = (uint32_t)num_ts;
+        for (const HashTs &h : seq) ts.push_back(h.ts);
+        num_ts += seq.size();
+        if (num_ts > UINT32_MAX) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 timestamps");
+      }
+      bool ok = seq.size() < 65536u;
+      for (size_t q = 1; q < seq.size() && ok; q++) ok = seq[q].ts > seq[q - 1].ts;
+      row_ok[row] = ok;
+    }
+  }
+  bool large_ok = true;
+  for (uint8_t ok : row_ok) large_ok = large_ok && ok;
+  // the pairs with a fresh video, each once (two fresh videos: under the later one), listed; their problems as in add
+  std::vector<uint32_t> pair_ids;
+  std::vector<NeedleHipProblem> problems;
+  uint64_t searched = 0;
+  auto list_pair = [&](size_t i, size_t j) {
+    const uint64_t l = pair_ids.size();
+    pair_ids.push_back((uint32_t)((uint64_t)j * (j - 1) / 2 + i));
+    bool any = false;
+    for (size_t r = 0; r < R; r++) {
+      const uint32_t a = min_len[i * R + r], b = min_len[j * R + r];
+      if (a == 0 || b == 0) continue;
+      problems.push_back(NeedleHipProblem{(uint32_t)(i * R + r), (uint32_t)(j * R + r), std::max(a, b), (uint32_t)(l * R + r)});
+      any = true;
+    }
+    searched += any;
+  };
+  for (size_t f = 0; f < n1; f++) {
+    if (!is_fresh(f)) continue;
+    for (size_t q = 0; q < f; q++) list_pair(q, f);
+    for (size_t q = f + 1; q < n1; q++)
+      if (!is_fresh(q)) list_pair(f, q);
+  }
+  IndexEdit e;
+  e.n_old = (uint32_t)n0;
+  e.n_new = (uint32_t)n1;
+  e.regions = (uint32_t)R;
+  e.threshold = cmp_.hash_match_threshold();
+  e.include_endings = include_endings_;
+  e.large_ok = large_ok;
+  e.min_opening_duration = cmp_.min_opening_duration();
+  e.min_ending_duration = cmp_.min_ending_duration();
+  e.time_padding = cmp_.time_padding();
+  e.old_of_new = old_of_new.data();
+  e.new_of_old = new_of_old.data();
+  e.gone = gone.data();
+  e.num_gone = gone.size();
+  e.hash_rows = hash_rows.data();
+  e.num_hash_rows = hash_rows.size();
+  e.ts_rows = ts_rows.data();
+  e.num_ts_rows = ts_rows.size();
+  e.hashes = hashes.data();
+  e.num_hashes = hashes.size();
+  e.total_hashes = num_hashes;
+  e.ts = ts.data();
+  e.num_ts = ts.size();
+  e.total_ts = num_ts;
+  e.seqs = seqs.data();
+  e.row_len = row_len.data();
+  e.row_ts = row_ts.data();
+  e.hash_duration = hash_duration.data();
+  e.problems = problems.data();
+  e.num_problems = problems.size();
+  e.pair_ids = pair_ids.data();
+  e.num_pairs = pair_ids.size();
+  IndexAppendOut out;
+  Status s = gpu_index_edit(store_, e, &out);
+  if (!s.ok()) return s;
+  if (out.failed & kEpilogueBucketTooLarge) {
+    note_epilogue_host_fallback("Index::replace", out.runs.size(), n1);
+    std::vector<uint32_t> start, valid;
+    std::vector<IndexEntry> entries;
+    host_entries(cmp_, R, (uint64_t)pair_ids.size() * R, out.runs,
+                 [&](uint64_t l, size_t *i, size_t *j) { column_pair(pair_ids[l], i, j); }, row_seq, video, &start, &valid, &entries);
+    if (!(s = gpu_index_edit_host_entries(store_, e, start, valid, entries, &out)).ok()) return s;
+  }
+  if (out.failed)  // best_match_kernel: the winner's end minus padding / hash duration underflows (the reference panics)
+    return Status::Make(NeedleError_Unknown, "overflow when subtracting durations (time_padding / hash_duration exceed the match end)");
+  // commit: nothing above changed the index
+  index_store_switch(store_, e, out.held);
+  std::vector<FrameHashesData> videos;
+  std::vector<NeedleHipSearchResult> results(n1, NeedleHipSearchResult{});
+  videos.reserve(n1);
+  for (size_t v = 0; v < n1; v++) {
+    if (is_fresh(v)) {
+      videos.push_back(*fresh[v]);
+    } else {
+      videos.push_back(std::move(videos_[old_of_new[v]]));
+      results[v] = results_[old_of_new[v]];
+    }
+  }
+  for (size_t q = 0; q < out.videos.size(); q++) results[out.videos[q]] = out.results[q];
+  videos_.swap(videos);
+  results_.swap(results);
+  seqs_.swap(seqs);
+  min_len_.swap(min_len);
+  row_ts_.swap(row_ts);
+  row_ok_.swap(row_ok);
+  hashes_ = num_hashes;
+  ts_ = num_ts;
+  large_ok_ = large_ok;
+  pairs_last_ = searched;
+  pairs_total_ += searched;
+  return Status::Ok();
+}
+
+Status Index::store_sizes(uint64_t sizes[4]) const { return index_store_sizes(store_, sizes); }
 
 }  // namespace needle

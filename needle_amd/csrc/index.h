@@ -9,7 +9,8 @@ namespace needle {
 
 struct IndexStore;
 
-// Results equal Comparator::run_with_frame_hashes over all videos added so far, in insertion order.  The index runs on
+// Results equal Comparator::run_with_frame_hashes over the index's current list: the videos added, in insertion order, less
+// those removed, with replacements in place.  The index runs on
 // the device that was current when it was created; one GPU only (no sharding across ranks).
 class Index {
  public:
@@ -21,6 +22,12 @@ class Index {
   size_t size() const { return videos_.size(); }
   // Appends the videos (copied); on failure the index is as it was before the call.
   Status add(const std::vector<const FrameHashesData *> &videos);
+  // Removes the videos at these distinct positions (the others keep their order) / replaces them in place (copied).  The
+  // results then equal run_with_frame_hashes over the new list; on failure the index is as it was before the call.
+  Status remove(const std::vector<size_t> &positions);
+  Status replace(const std::vector<size_t> &positions, const std::vector<const FrameHashesData *> &videos);
+  // heap entries held, entry slots in use, hashes in the arena, timestamps in the table
+  Status store_sizes(uint64_t sizes[4]) const;
   const std::vector<NeedleHipSearchResult> &results() const { return results_; }
   uint64_t pairs_total() const { return pairs_total_; }
   uint64_t pairs_last() const { return pairs_last_; }
@@ -36,8 +43,12 @@ class Index {
   std::vector<uint32_t> row_ts_;          // per row: offset of its timestamps in the store's table
   uint64_t hashes_ = 0, ts_ = 0;          // sizes of the device arena and timestamp table
   bool large_ok_ = true;                  // every row under 65 536 hashes, timestamps strictly increasing
+  std::vector<uint8_t> row_ok_;           // per row: that row's part of large_ok_
   std::vector<NeedleHipSearchResult> results_;
   uint64_t pairs_total_ = 0, pairs_last_ = 0;
+
+  // remove / replace: the new list is old_of_new[v] (an old position) or, where that is kIndexFresh, *fresh[v]
+  Status rebuild(const std::vector<uint32_t> &old_of_new, const std::vector<const FrameHashesData *> &fresh);
 };
 
 }  // namespace needle

@@ -209,6 +209,14 @@ extern "C" {
     pub fn needle_hip_index_add(index: *mut NeedleHipIndex, frame_hashes: *const *const FrameHashes, k: usize) -> NeedleError;
     pub fn needle_hip_index_results(index: *const NeedleHipIndex, results: *mut NeedleHipSearchResult, n: usize) -> NeedleError;
     pub fn needle_hip_index_pairs_searched(index: *const NeedleHipIndex, total: *mut u64, last: *mut u64) -> NeedleError;
+    pub fn needle_hip_index_remove(index: *mut NeedleHipIndex, positions: *const usize, k: usize) -> NeedleError;
+    pub fn needle_hip_index_replace(
+        index: *mut NeedleHipIndex,
+        positions: *const usize,
+        frame_hashes: *const *const FrameHashes,
+        k: usize,
+    ) -> NeedleError;
+    pub fn needle_hip_index_store_sizes(index: *const NeedleHipIndex, sizes: *mut u64) -> NeedleError;
     /// 1..=MAX_CHANNELS interleaved channels -> mono, `(sum of a frame) / channels` with C truncation; `out[i]` holds
     /// `num_values[i] / channels` values.
     pub fn needle_hip_downmix_host(

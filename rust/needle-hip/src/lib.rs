@@ -423,8 +423,8 @@ impl<P: AsRef<Path>> Comparator<P> {
 }
 
 /// An incremental search index (include/needle_hip.h "Incremental index"): `results()` equals
-/// `Comparator::run_with_frame_hashes` over every video added so far, in insertion order (one slot per video, `None` where
-/// that call pushes no result); `add` searches only the pairs it adds.  The comparator's parameters are copied at
+/// `Comparator::run_with_frame_hashes` over the index's current list of videos (one slot per video, `None` where that call
+/// pushes no result); `add` searches only the pairs it adds, `remove` none and `replace` those of the videos replaced.  The comparator's parameters are copied at
 /// creation.  One GPU: the device current at creation.
 pub struct Index {
     raw: *mut ffi::NeedleHipIndex,
@@ -446,6 +446,32 @@ impl Index {
     pub fn add(&mut self, frame_hashes: &[&FrameHashes]) -> Result<()> {
         let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
         unsafe { check(ffi::needle_hip_index_add(self.raw, raw.as_ptr(), raw.len())) }
+    }
+
+    /// Removes the videos at these distinct positions; the others keep their order.  No pair is searched.  On error the
+    /// index is as it was before the call.
+    pub fn remove(&mut self, positions: &[usize]) -> Result<()> {
+        unsafe { check(ffi::needle_hip_index_remove(self.raw, positions.as_ptr(), positions.len())) }
+    }
+
+    /// Replaces the video at `positions[i]` with `frame_hashes[i]`, in place; only the pairs of those videos are searched.
+    /// On error the index is as it was before the call.
+    pub fn replace(&mut self, positions: &[usize], frame_hashes: &[&FrameHashes]) -> Result<()> {
+        if positions.len() != frame_hashes.len() {
+            return Err(Error {
+                code: ffi::NeedleError::InvalidArgument,
+                message: "index replace: one FrameHashes per position".into(),
+            });
+        }
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        unsafe { check(ffi::needle_hip_index_replace(self.raw, positions.as_ptr(), raw.as_ptr(), raw.len())) }
+    }
+
+    /// [heap entries held, entry slots in use, hashes in the device arena, timestamps in the device table].
+    pub fn store_sizes(&self) -> Result<[u64; 4]> {
+        let mut sizes = [0u64; 4];
+        unsafe { check(ffi::needle_hip_index_store_sizes(self.raw, sizes.as_mut_ptr()))? };
+        Ok(sizes)
     }
 
     pub fn len(&self) -> usize {
