@@ -310,6 +310,12 @@ void needle_hip_library_free(NeedleHipLibrary *library);
 /* Analyzer::with_include_endings + with_ending_search_percentage (analyzer.rs:130-139): also fingerprint the
  * last `ending_search_percentage` of every video.  Call before set_pcm; the arena then has two rows per video. */
 enum NeedleError needle_hip_library_include_endings(NeedleHipLibrary *library, float ending_search_percentage);
+/* The sample rate of the PCM that set_pcm, set_pcm_device, stream_pcm and rank_videos will be given (2000..768000 Hz,
+ * default 11025).  Call after library_new and before set_pcm (InvalidArgument afterwards, the library unchanged).  The
+ * search windows are cut at that rate, as needle_hip_analyzer_run_pcm does, and resampled to 11025 Hz mono on the device
+ * on the way in: the resident PCM, and so every job's cost, is that of a mono 11025 Hz library.  The hashes equal
+ * needle_hip_analyzer_run_pcm's at that rate.  At 11025 nothing is resampled. */
+enum NeedleError needle_hip_library_set_sample_rate(NeedleHipLibrary *library, int sample_rate);
 size_t needle_hip_library_rows_per_video(const NeedleHipLibrary *library);
 /* Lengths (values per stream, all videos) are metadata every rank holds; pcm[i] may be NULL for
  * videos this rank does not own.  Crops to the opening window and uploads.  `channels` = 1..NEEDLE_HIP_MAX_CHANNELS in
@@ -318,8 +324,9 @@ size_t needle_hip_library_rows_per_video(const NeedleHipLibrary *library);
 enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *library, const int16_t *const *pcm,
                                             const size_t *num_values, int channels);
 /* The same for PCM that is already in HBM (decoded or generated on the device): d_pcm[i] are DEVICE pointers, NULL for
- * videos this rank does not own.  The search windows are copied device to device into the library's arena; the caller's
- * buffers are free on return. */
+ * videos this rank does not own.  The search windows are copied device to device into the library's arena (at another
+ * sample rate: resampled straight out of the caller's buffers, which need only 2-byte alignment); the caller's buffers
+ * are free on return. */
 enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *library, const int16_t *const *d_pcm,
                                                    const size_t *num_values, int channels);
 /* The streaming form ("analyze streamed from host-pinned PCM", BASELINE.json configs[4]): the search windows of the

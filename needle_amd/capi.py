@@ -83,7 +83,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_frame_hashes_copy", "needle_hip_frame_hashes_hash_duration_ns", "needle_hip_frame_hashes_md5",
     "needle_hip_frame_hashes_read", "needle_hip_frame_hashes_write", "needle_hip_header_md5",
     "needle_hip_analyzer_run_pcm", "needle_hip_comparator_run_with_frame_hashes", "needle_hip_library_new",
-    "needle_hip_library_free", "needle_hip_library_include_endings", "needle_hip_library_rows_per_video",
+    "needle_hip_library_free", "needle_hip_library_include_endings", "needle_hip_library_set_sample_rate",
+    "needle_hip_library_rows_per_video",
     "needle_hip_library_set_pcm", "needle_hip_library_set_pcm_device", "needle_hip_library_rank_videos",
     "needle_hip_library_analyze",
     "needle_hip_library_hash_arena", "needle_hip_library_use_hash_arena", "needle_hip_library_num_pairs", "needle_hip_library_search",
@@ -188,6 +189,7 @@ def lib():
     L.needle_hip_library_free.argtypes = [vp]
     L.needle_hip_library_free.restype = None
     L.needle_hip_library_include_endings.argtypes = [vp, f32]
+    L.needle_hip_library_set_sample_rate.argtypes = [vp, C.c_int]
     L.needle_hip_library_rows_per_video.argtypes = [vp]
     L.needle_hip_library_rows_per_video.restype = sz
     L.needle_hip_library_set_pcm.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.c_int]
@@ -793,6 +795,12 @@ class Library:
 
     def include_endings(self, ending_search_percentage: float = DEFAULT_ENDING_SEARCH_PERCENTAGE) -> "Library":
         check(lib().needle_hip_library_include_endings(self._h, ending_search_percentage))
+        return self
+
+    def set_sample_rate(self, sample_rate: int) -> "Library":
+        """The rate of the PCM set_pcm / set_pcm_device / stream_pcm / rank_videos will be given; resampled to 11025 Hz
+        mono on the device on the way in (needle_hip_library_set_sample_rate)."""
+        check(lib().needle_hip_library_set_sample_rate(self._h, sample_rate))
         return self
 
     def rows_per_video(self) -> int:

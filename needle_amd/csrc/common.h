@@ -136,7 +136,7 @@ Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan
 // executed; the kernels may still be running (library stream order).
 Status gpu_fingerprint_streamed_device(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values,
                                        int channels, uint32_t step, uint32_t *d_items,
-                                       const std::vector<uint64_t> &item_off);
+                                       const std::vector<uint64_t> &item_off, int rate = kSampleRate);
 // `rate` != 11025 routes the streams through the device resampler first (resample.hip).
 Status gpu_fingerprint_host(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values,
                             int channels, uint32_t step, std::vector<std::vector<uint32_t>> *items,
@@ -192,10 +192,29 @@ Status gpu_fingerprint_audit_device(const int16_t *d_pcm, const std::vector<Stre
 // ---- resampler front-end (resample.hip) -------------------------------------------------------------------
 struct ResampleSpan {
   uint64_t in_off;   // offset into the input arena, in s16 values
-  uint64_t n_in;     // samples per channel
-  uint64_t out_off;  // offset into the output arena, in samples
+  uint64_t n_in;     // samples per channel: the stream's true extent [0, n_in), zeros outside it
+  uint64_t out_off;  // offset into the output arena, in samples (of the stream's output 0)
+  // Optional, for streams that are not whole streams of the input arena:
+  //  * src: the stream's own source (any 2-byte alignment) instead of d_in + in_off.  With a piece, src points at
+  //    sample p0 (the piece's first), not at sample 0.
+  //  * tiles [t0, t1): only those output tiles (resample_tiling().tile_outputs each) are computed; t1 == 0: to the end.
+  //  * piece [p0, p1): the input samples that are there to be read (p1 == 0: the whole stream).  It must cover the taps
+  //    of the tiles' outputs (resample_piece); its edges are not the stream's, zeros come only from outside [0, n_in).
+  // The output is bit for bit the same slice of the whole stream's output.
+  const int16_t *src = nullptr;
+  uint64_t t0 = 0, t1 = 0;
+  uint64_t p0 = 0, p1 = 0;
 };
 size_t resample_out_len(size_t n_in, int rate);
+// The kernel gpu_resample_device picks for `rate` (environment overrides included) computes whole tiles of
+// tile_outputs consecutive outputs; output m reads input samples [m M / L - half + 1, m M / L + half + 1) (floor).
+struct ResampleTiling {
+  int L = 1, M = 1, half = 0;
+  uint64_t tile_outputs = 1;
+};
+Status resample_tiling(int rate, int channels, ResampleTiling *out);
+// the input samples [*p0, *p1) of a stream of n_in samples that tiles [t0, t1) read, p0 rounded down to a multiple of 8
+void resample_piece(const ResampleTiling &t, uint64_t n_in, uint64_t t0, uint64_t t1, uint64_t *p0, uint64_t *p1);
 Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> &spans, int channels, int rate,
                            int16_t *d_out, bool sync);
 Status gpu_resample_host(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values, int channels,

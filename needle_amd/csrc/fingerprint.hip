@@ -1215,11 +1215,11 @@ Status gpu_fingerprint_streamed(const std::vector<size_t> &num_values, const Pcm
 
 Status gpu_fingerprint_streamed_device(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values,
                                        int channels, uint32_t step, uint32_t *d_items,
-                                       const std::vector<uint64_t> &item_off) {
+                                       const std::vector<uint64_t> &item_off, int rate) {
   if (pcm.size() != num_values.size() || item_off.size() != num_values.size())
     return Status::Make(NeedleError_InvalidArgument, "fingerprint: one length and one item offset per stream are required");
   return fingerprint_in_batches(
-      num_values, channels, step, nullptr, kSampleRate,
+      num_values, channels, step, nullptr, rate,
       [&](size_t begin, size_t end, const std::vector<uint64_t> &in_off, int16_t *d_pcm, hipStream_t up,
           const StreamIssued &issued) -> Status {
         return gpu_upload_pcm(std::vector<const int16_t *>(pcm.begin() + begin, pcm.begin() + end),

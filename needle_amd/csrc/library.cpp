@@ -51,7 +51,8 @@ struct NeedleHipLibrary {
   bool endings = false;
   ns_t hash_duration = 0;
   uint32_t step = 0;
-  int channels = 1;
+  int channels = 1;            // of the resident PCM (1 whenever it was down-mixed or resampled on the way in)
+  int rate = kSampleRate;      // of the callers' PCM (needle_hip_library_set_sample_rate); the resident PCM is 11025 Hz
   bool have_pcm = false;      // windows and arena are set up (set_pcm or stream_pcm)
   bool pcm_resident = false;  // set_pcm: the PCM stays in HBM and analyze can be repeated
   std::vector<Window> win;  // [video * regions() + region]
@@ -273,42 +274,57 @@ enum NeedleError needle_hip_library_include_endings(NeedleHipLibrary *lib, float
   return NeedleError_Ok;
 }
 
+enum NeedleError needle_hip_library_set_sample_rate(NeedleHipLibrary *lib, int sample_rate) {
+  if (!lib) return NeedleError_NullArgument;
+  if (sample_rate < 2000 || sample_rate > 768000) return NeedleError_InvalidArgument;  // Analyzer::run_pcm's range
+  if (lib->have_pcm) return NeedleError_InvalidArgument;  // must precede set_pcm
+  lib->rate = sample_rate;
+  return NeedleError_Ok;
+}
+
 }  // extern "C"
 
 namespace {
+// Samples a window of `count` samples at `rate` keeps resident (11025 Hz).
+size_t resident_samples(size_t count, int rate) { return rate == kSampleRate ? count : resample_out_len(count, rate); }
+
 // Search windows of every video (analyzer.rs:378,390) from the stream lengths, arena geometry, and -- for the videos
 // whose PCM this rank holds -- where each window starts in the caller's buffer.  `resident`: the windows get offsets
 // into the device PCM arena (set_pcm); otherwise nothing of the PCM is kept (stream_pcm).  `len` is in the caller's
-// (interleaved) values; 3-8 channel PCM is kept resident as mono (down-mixed on the way in), so lib->channels and the
-// windows' `values` describe the arena, not the input.
+// (interleaved) values at lib->rate; windows are cut at that rate (as Analyzer::run_pcm does).  3-8 channel PCM and PCM
+// at any rate other than 11025 Hz are kept resident as 11025 Hz mono (down-mixed and resampled on the way in), so
+// lib->channels and the windows' `values` describe the arena, not the input; `len` is the input's.
 Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values, int channels, bool resident,
                     std::vector<const int16_t *> *src, std::vector<size_t> *len, std::vector<uint64_t> *dst,
                     std::vector<uint64_t> *rows_of_src, uint64_t *total_values) {
   Status s = ensure_device();
   if (!s.ok()) return s;
-  lib->channels = channels > 2 ? 1 : channels;
+  const bool resampled = lib->rate != kSampleRate;
+  lib->channels = channels > 2 || resampled ? 1 : channels;
   const size_t R = lib->regions();
   lib->win.assign(lib->rows(), Window{});
   uint64_t total = 0;
   uint32_t max_kept = 0;
-  std::vector<size_t> first_sample(lib->rows(), 0);
+  std::vector<size_t> first_sample(lib->rows(), 0), source_samples(lib->rows(), 0);
   for (size_t v = 0; v < lib->n; v++) {
     const size_t samples = num_values[v] / (size_t)channels;
     size_t open_samples = 0, end_first = 0;
     ns_t seek = 0;
-    s = Analyzer::windows(samples, kSampleRate, lib->opening_pct, lib->ending_pct, &open_samples, &end_first, &seek);
+    s = Analyzer::windows(samples, lib->rate, lib->opening_pct, lib->ending_pct, &open_samples, &end_first, &seek);
     if (!s.ok()) return s;
     for (size_t r = 0; r < R; r++) {
       Window &w = lib->win[v * R + r];
       const size_t count = r == 0 ? open_samples : samples - end_first;
+      const size_t kept_samples = resident_samples(count, lib->rate);
       first_sample[v * R + r] = r == 0 ? 0 : end_first;
-      w.values = count * (size_t)lib->channels;
-      w.kept = (uint32_t)num_kept(count, lib->step);
+      source_samples[v * R + r] = count;
+      w.values = kept_samples * (size_t)lib->channels;
+      w.kept = (uint32_t)num_kept(kept_samples, lib->step);
       w.seek = r == 0 ? 0 : seek;
       max_kept = std::max(max_kept, w.kept);
       if (pcm[v] && resident) {
         w.pcm_off = total;
-        total += channels > 2 ? (w.values + 7) & ~(uint64_t)7 : (w.values + 1) & ~(uint64_t)1;  // (down-mix: 16-byte stores)
+        total += channels > 2 || resampled ? (w.values + 7) & ~(uint64_t)7 : (w.values + 1) & ~(uint64_t)1;  // (down-mix: 16-byte stores)
       }
     }
   }
@@ -336,7 +352,7 @@ Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size
       const Window &w = lib->win[v * R + r];
       if (!pcm[v] || !w.values) continue;
       src->push_back(pcm[v] + first_sample[v * R + r] * (size_t)channels);
-      len->push_back(w.values / (size_t)lib->channels * (size_t)channels);
+      len->push_back(source_samples[v * R + r] * (size_t)channels);
       if (dst) dst->push_back(w.pcm_off);
       if (rows_of_src) rows_of_src->push_back(v * R + r);
     }
@@ -393,6 +409,102 @@ Status upload_mixed(NeedleHipLibrary *lib, const std::vector<const int16_t *> &s
   }
   return flush();
 }
+
+// set_pcm / set_pcm_device at a rate other than 11025 Hz: the windows are resampled on the device (resample.hip) into
+// their places in the resident mono PCM.  1-2 channel device windows are read straight out of the caller's buffers.  Host
+// windows, and 3-8 channel device windows (down-mixed first, at the source rate), go through a staging buffer of at most
+// NEEDLE_HIP_MAX_BATCH_VALUES values (2 GiB): a window is cut into pieces of whole output tiles of the resampler, each
+// staged with the input samples its tiles' taps read (one piece per window unless the window is longer than the buffer;
+// the output is bit for bit the whole window's).  All in library-stream order; the caller synchronises.
+Status upload_resampled(NeedleHipLibrary *lib, const std::vector<const int16_t *> &src, const std::vector<size_t> &len,
+                        const std::vector<uint64_t> &dst, int channels, bool from_host, DeviceBuffer<int16_t> *stage) {
+  const int rate = lib->rate, rs_channels = channels > 2 ? 1 : channels;  // (what the resampler reads)
+  const uint64_t C = (uint64_t)channels;
+  ResampleTiling tl;
+  Status s = resample_tiling(rate, rs_channels, &tl);
+  if (!s.ok()) return s;
+  if (!from_host && channels <= 2) {
+    std::vector<ResampleSpan> spans;
+    for (size_t i = 0; i < src.size(); i++) {
+      ResampleSpan sp{0, len[i] / C, dst[i]};
+      sp.src = src[i];
+      spans.push_back(sp);
+    }
+    return gpu_resample_device(nullptr, spans, channels, rate, lib->d_pcm.ptr, false);
+  }
+  uint64_t max_values = 1ull << 30;
+  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) max_values = (uint64_t)std::max(1ll, atoll(e));  // tests
+  // staged values per input sample: the frame uploaded (host) and its down-mixed sample (3-8 channels)
+  const uint64_t per_sample = (from_host ? C : 0) + (channels > 2 ? 1 : 0);
+  const uint64_t tile_in = tl.tile_outputs * (uint64_t)tl.M / (uint64_t)tl.L + 2 * (uint64_t)tl.half + 16;  // one tile's input at most
+  const uint64_t budget = std::max(max_values / per_sample, tile_in);  // input samples per piece at most
+  const uint64_t piece_tiles = std::max<uint64_t>(1, (budget - 2 * (uint64_t)tl.half - 16) * (uint64_t)tl.L /
+                                                         (tl.tile_outputs * (uint64_t)tl.M));
+  auto staged = [&](uint64_t samples) {  // staging values one piece takes, every part 16-byte aligned
+    return (from_host ? (samples * C + 7) & ~(uint64_t)7 : 0) + (channels > 2 ? (samples + 7) & ~(uint64_t)7 : 0);
+  };
+  struct Piece {
+    size_t i;
+    uint64_t t0, t1, p0, p1;
+  };
+  std::vector<Piece> pieces;
+  uint64_t total = 0, largest = 0;
+  for (size_t i = 0; i < src.size(); i++) {
+    const uint64_t n_in = len[i] / C, tiles = (resample_out_len(n_in, rate) + tl.tile_outputs - 1) / tl.tile_outputs;
+    for (uint64_t t0 = 0; t0 < tiles; t0 += piece_tiles) {
+      Piece pc{i, t0, std::min(tiles, t0 + piece_tiles), 0, 0};
+      resample_piece(tl, n_in, pc.t0, pc.t1, &pc.p0, &pc.p1);
+      pieces.push_back(pc);
+      total += staged(pc.p1 - pc.p0);
+      largest = std::max(largest, staged(pc.p1 - pc.p0));
+    }
+  }
+  const uint64_t cap = std::max(std::min(total, max_values), largest) + 8;
+  if (!(s = stage->reserve(cap)).ok()) return s;
+  std::vector<const int16_t *> up_src;
+  std::vector<size_t> up_len;
+  std::vector<uint64_t> up_off;
+  std::vector<DownmixSpan> mix;
+  std::vector<ResampleSpan> spans;
+  uint64_t used = 0;
+  auto flush = [&]() -> Status {  // the next group's copies follow these kernels in stream order
+    Status fs = up_src.empty() ? Status::Ok() : gpu_upload_pcm(up_src, up_len, up_off, stage->ptr);
+    if (fs.ok() && !mix.empty()) fs = gpu_downmix_device(mix, channels, false);
+    if (fs.ok() && !spans.empty()) fs = gpu_resample_device(nullptr, spans, rs_channels, rate, lib->d_pcm.ptr, false);
+    up_src.clear();
+    up_len.clear();
+    up_off.clear();
+    mix.clear();
+    spans.clear();
+    used = 0;
+    return fs;
+  };
+  for (const Piece &pc : pieces) {
+    const uint64_t n = pc.p1 - pc.p0;
+    if (used + staged(n) > cap && !(s = flush()).ok()) return s;
+    const int16_t *from = src[pc.i] + pc.p0 * C;  // the piece in the caller's buffer
+    if (from_host) {
+      up_src.push_back(from);
+      up_len.push_back(n * C);
+      up_off.push_back(used);
+      from = stage->ptr + used;
+      used += (n * C + 7) & ~(uint64_t)7;
+    }
+    if (channels > 2) {
+      mix.push_back(DownmixSpan{from, stage->ptr + used, n});
+      from = stage->ptr + used;
+      used += (n + 7) & ~(uint64_t)7;
+    }
+    ResampleSpan sp{0, len[pc.i] / C, dst[pc.i]};
+    sp.src = from;
+    sp.t0 = pc.t0;
+    sp.t1 = pc.t1;
+    sp.p0 = pc.p0;
+    sp.p1 = pc.p1;
+    spans.push_back(sp);
+  }
+  return flush();
+}
 }  // namespace
 
 extern "C" {
@@ -409,8 +521,10 @@ enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t
     Status s = plan_windows(lib, pcm, num_values, channels, true, &src, &len, &dst, nullptr, &total);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
-    DeviceBuffer<int16_t> stage;  // (3-8 channels; freed after the drain below)
-    s = channels > 2 ? upload_mixed(lib, src, len, dst, channels, &stage) : gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
+    DeviceBuffer<int16_t> stage;  // (3-8 channels or another rate; freed after the drain below)
+    s = lib->rate != kSampleRate ? upload_resampled(lib, src, len, dst, channels, true, &stage)
+        : channels > 2           ? upload_mixed(lib, src, len, dst, channels, &stage)
+                                 : gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
     // also on the error path: copies already enqueued read the caller's buffers asynchronously
     const bool drained = hipStreamSynchronize(library_stream()) == hipSuccess;
     if (!s.ok()) return report(s);
@@ -434,7 +548,13 @@ enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const 
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
     hipStream_t stream = library_stream();
-    if (channels > 2) {  // the search windows are down-mixed straight out of the caller's buffers into the resident mono PCM
+    DeviceBuffer<int16_t> stage;  // (3-8 channels at another rate; freed after the drain below)
+    if (lib->rate != kSampleRate) {  // resampled out of the caller's buffers (3-8 channels: down-mixed into staging first)
+      s = upload_resampled(lib, src, len, dst, channels, false, &stage);
+      const bool drained = hipStreamSynchronize(stream) == hipSuccess;
+      if (!s.ok()) return report(s);
+      if (!drained) return report(Status::Make(NeedleError_Unknown, "PCM resampling failed"));
+    } else if (channels > 2) {  // the search windows are down-mixed straight out of the caller's buffers into the resident mono PCM
       std::vector<DownmixSpan> mix;
       for (size_t i = 0; i < src.size(); i++) mix.push_back(DownmixSpan{src[i], lib->d_pcm.ptr + dst[i], len[i] / (size_t)channels});
       if (!(s = gpu_downmix_device(mix, channels, false)).ok()) return report(s);
@@ -463,7 +583,7 @@ enum NeedleError needle_hip_library_stream_pcm(NeedleHipLibrary *lib, const int1
     if (!s.ok()) return report(s);
     for (uint64_t &r : rows) r *= lib->stride;  // kept items of a window go straight to its arena row
     const auto t1 = std::chrono::steady_clock::now();
-    if (!(s = gpu_fingerprint_streamed_device(src, len, channels, lib->step, lib->arena, rows)).ok()) return report(s);
+    if (!(s = gpu_fingerprint_streamed_device(src, len, channels, lib->step, lib->arena, rows, lib->rate)).ok()) return report(s);
     if (getenv("NEEDLE_HIP_TRACE"))
       std::fprintf(stderr, "[needle_hip] stream_pcm: windows planned in %.2f ms, %zu windows streamed in %.2f ms\n",
                    std::chrono::duration<double, std::milli>(t1 - t0).count(), src.size(),
@@ -1078,10 +1198,10 @@ enum NeedleError needle_hip_library_rank_videos(const NeedleHipLibrary *lib, con
       size_t open_samples = 0, end_first = 0;
       ns_t seek = 0;
       const size_t samples = num_values[v] / (size_t)channels;
-      Status s = Analyzer::windows(samples, kSampleRate, lib->opening_pct, lib->ending_pct, &open_samples, &end_first, &seek);
+      Status s = Analyzer::windows(samples, lib->rate, lib->opening_pct, lib->ending_pct, &open_samples, &end_first, &seek);
       if (!s.ok()) return report(s);
       for (size_t r = 0; r < R; r++) {
-        plan.win[v * R + r].kept = (uint32_t)num_kept(r == 0 ? open_samples : samples - end_first, lib->step);
+        plan.win[v * R + r].kept = (uint32_t)num_kept(resident_samples(r == 0 ? open_samples : samples - end_first, lib->rate), lib->step);
         max_kept = std::max(max_kept, plan.win[v * R + r].kept);
       }
     }

@@ -117,13 +117,35 @@ std::mutex g_mu;
 std::map<std::pair<int, int>, Design> g_designs;  // (device, rate)
 
 struct RsStream {
-  uint64_t in_off;   // s16 values into the input arena
-  uint64_t n_in;     // samples per channel
-  uint64_t out_off;  // samples into the output arena
-  uint64_t n_out;
+  int64_t in_off;    // s16 values from the kernel's `in` to the stream's sample 0 (with a piece, that place need not be
+                     // inside any buffer: only the piece is read)
+  uint64_t n_in;     // samples per channel: zeros outside [0, n_in)
+  uint64_t out_off;  // samples into the output arena, of the stream's output 0
+  uint64_t n_out;    // outputs of the whole stream
   uint32_t block_base;
-  uint32_t pad;
+  uint32_t t0;       // the stream's first tile in this launch (ResampleSpan::t0)
+  uint64_t lo, hi;   // the piece: loads stay inside samples [lo, hi), which hold every sample a tap with a coefficient
+                     // other than zero meets; a whole stream is [0, n_in)
 };
+
+// One down-mixed input sample of the stream whose sample 0 is at src; 0 outside [0, n_in).  Branch-free: the load is
+// always issued, at an index clamped into the piece [lo, hi), so that unrolled staging loops keep their loads in flight.
+// A stereo sample is one 32-bit load, or two 16-bit loads when the stream is not 4-byte aligned (`odd`, uniform).
+template <int CH>
+__device__ __forceinline__ int rs_sample(const int16_t *src, uint64_t n_in, uint64_t lo, uint64_t hi, bool odd, long long idx) {
+  const bool ok = idx >= 0 && (uint64_t)idx < n_in;
+  const long long at = idx < (long long)lo ? (long long)lo : ((uint64_t)idx < hi ? idx : (long long)hi - 1);
+  int sv;
+  if (CH == 1) {
+    sv = src[at];
+  } else if (!odd) {
+    const int v = reinterpret_cast<const int *>(src)[at];
+    sv = ((int)(int16_t)v + (v >> 16)) / 2;  // integer down-mix, C truncation
+  } else {
+    sv = ((int)src[2 * at] + (int)src[2 * at + 1]) / 2;
+  }
+  return ok ? sv : 0;
+}
 
 constexpr int kMaxRegionSamples = 30000;  // f32 region of a tile in LDS (120 KB) at most
 constexpr int kThreads = 512;
@@ -166,27 +188,14 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const int16_t *__res
   const RsStream st = streams[lo];
   const int n = 1 << n_log2;
   const int tile_outputs = n * L;
-  const uint64_t tile = blockIdx.x - st.block_base;
+  const uint64_t tile = blockIdx.x - st.block_base + st.t0;
   const uint64_t tile_base = tile * (uint64_t)tile_outputs;          // first output of the tile
   const int half = geo.T / 2;
   // input index of region[0]: the first tap of the tile's first output, moved down by delta to a multiple of 4
   const long long first0 = (long long)(tile * (uint64_t)n * (uint64_t)M) - half + 1 - geo.delta;
   const int16_t *src = in + st.in_off;
-  // one down-mixed input sample, 0 outside the stream.  Branch-free (the load is always issued, at an index
-  // clamped into the stream) so that the unrolled staging loops keep their loads in flight; a stereo sample is
-  // one aligned 32-bit load.
-  auto sample = [&](long long idx) -> int {
-    const bool ok = idx >= 0 && (uint64_t)idx < st.n_in;
-    const long long at = idx < 0 ? 0 : ((uint64_t)idx < st.n_in ? idx : (long long)st.n_in - 1);
-    int sv;
-    if (CH == 1) {
-      sv = src[at];
-    } else {
-      const int v = reinterpret_cast<const int *>(src)[at];
-      sv = ((int)(int16_t)v + (v >> 16)) / 2;  // integer down-mix, C truncation
-    }
-    return ok ? sv : 0;
-  };
+  const bool odd = CH == 2 && (reinterpret_cast<uintptr_t>(src) & 3) != 0;
+  auto sample = [&](long long idx) -> int { return rs_sample<CH>(src, st.n_in, st.lo, st.hi, odd, idx); };
   // staging: `count` samples from input index `from`, by `nt` cooperating threads of which this is number `me`;
   // whole passes keep eight loads in flight per thread (one at a time would pay a memory latency per pass), the
   // ragged tail is a plain loop (no dummy loads: thousands of workgroups reading one dummy address made that
@@ -205,12 +214,13 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const int16_t *__res
   };
   // the same by groups of four samples: one 16-byte (stereo) or 8-byte (mono) load and one 128-bit LDS store per
   // group.  `from` and the stream's first sample are multiples of 4 samples from a 16-byte boundary; groups that
-  // stick out of the stream take the scalar path.
+  // stick out of the piece take the scalar path.
+  const long long first_group = ((long long)st.lo + 3) & ~3ll;  // first aligned group wholly inside the piece
+  const long long last_group = ((long long)st.hi - 4) & ~3ll;   // last aligned group wholly inside the piece
   auto stage_run4 = [&](float4 *dst, long long from, int groups, int me, int nt) {
     constexpr int kStageUnroll = 4;
-    const long long last_group = ((long long)st.n_in - 4) & ~3ll;  // last aligned group wholly inside the stream
     auto group = [&](long long idx) -> float4 {  // branch-free: out-of-range groups load a clamped one (fixed below)
-      const long long at = idx < 0 ? 0 : (idx > last_group ? last_group : idx);
+      const long long at = idx < first_group ? first_group : (idx > last_group ? last_group : idx);
       int s0, s1, s2, s3;
       if (CH == 1) {
         const int2 v = *reinterpret_cast<const int2 *>(src + at);
@@ -231,14 +241,14 @@ __global__ __launch_bounds__(kThreads) void resample_kernel(const int16_t *__res
       for (int u = 0; u < kStageUnroll; u++) dst[o + u * nt] = v[u];
     }
     for (; o < groups; o += nt) dst[o] = group(from + 4 * o);
-    // groups that stick out of the stream (only in its first and last tiles): sample by sample, zeros outside
+    // groups that stick out of the piece (only in its first and last tiles): sample by sample, zeros outside the stream
     for (o = me; o < groups; o += nt) {
       const long long idx = from + 4 * o;
-      if (idx < 0 || idx > last_group)
+      if (idx < first_group || idx > last_group)
         dst[o] = float4{(float)sample(idx), (float)sample(idx + 1), (float)sample(idx + 2), (float)sample(idx + 3)};
     }
   };
-  const bool by_groups = VEC4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && st.n_in >= 4;
+  const bool by_groups = VEC4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && first_group <= last_group;
   if (geo.pitch) {  // row r: its own M samples and the overlap into the next row
     const int tpr = kThreads >> n_log2;  // threads per row
     const int r = threadIdx.x / tpr;
@@ -399,28 +409,20 @@ __device__ __forceinline__ float4 group_to_f32(typename std::conditional<CH == 1
 // down-mixed samples from input index first0 + r M on, as f32, at lds4 + pitch r; zeros outside the stream.  blockDim.x /
 // 16 threads per row.
 template <int CH, bool VEC4>
-__device__ __forceinline__ void stage_quad_rows(float4 *lds4, const int16_t *src, uint64_t n_in, long long first0, int M,
-                                                int pitch, int groups) {
+__device__ __forceinline__ void stage_quad_rows(float4 *lds4, const int16_t *src, uint64_t n_in, uint64_t lo, uint64_t hi,
+                                                long long first0, int M, int pitch, int groups) {
   using raw_t = typename std::conditional<CH == 1, int2, int4>::type;  // four samples as they lie in memory
   float *stage = reinterpret_cast<float *>(lds4);
   const int tpr = blockDim.x / kQuadRows, row = threadIdx.x / tpr, me = threadIdx.x % tpr;
   const int count = 4 * groups;
-  auto sample = [&](long long idx) -> int {  // one down-mixed input sample, 0 outside the stream (branch-free load)
-    const bool ok = idx >= 0 && (uint64_t)idx < n_in;
-    const long long at = idx < 0 ? 0 : ((uint64_t)idx < n_in ? idx : (long long)n_in - 1);
-    int sv;
-    if (CH == 1) {
-      sv = src[at];
-    } else {
-      const int v = reinterpret_cast<const int *>(src)[at];
-      sv = ((int)(int16_t)v + (v >> 16)) / 2;  // integer down-mix, C truncation
-    }
-    return ok ? sv : 0;
-  };
-  const bool by_groups = VEC4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && n_in >= 4;
+  const bool odd = CH == 2 && (reinterpret_cast<uintptr_t>(src) & 3) != 0;
+  auto sample = [&](long long idx) -> int { return rs_sample<CH>(src, n_in, lo, hi, odd, idx); };
+  const long long first_group = ((long long)lo + 3) & ~3ll;  // first aligned group wholly inside the piece
+  const long long last_group = ((long long)hi - 4) & ~3ll;   // last aligned group wholly inside the piece
+  const bool by_groups = VEC4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && first_group <= last_group;
   const long long tile_last = first0 + (long long)(kQuadRows - 1) * M + 4 * (long long)groups;  // one past the last sample staged
-  if (by_groups && first0 >= 0 && tile_last <= (long long)n_in) {
-    // the tile lies inside the stream (all but the first and last tiles of a stream): a uniform base, 32-bit
+  if (by_groups && first0 >= (long long)lo && tile_last <= (long long)hi) {
+    // the tile lies inside the piece (all but the first and last tiles of a stream or piece): a uniform base, 32-bit
     // offsets, no clamps
     const raw_t *base = reinterpret_cast<const raw_t *>(src + (size_t)CH * first0);  // first0 is a multiple of 4
     const uint32_t row_groups = (uint32_t)(row * M) >> 2;                             // M is a multiple of 4 (VEC4)
@@ -433,13 +435,12 @@ __device__ __forceinline__ void stage_quad_rows(float4 *lds4, const int16_t *src
       for (int u = 0; u < kQuadGroupsInFlight; u++)
         if (o0 + u * tpr < groups) dst[o0 + u * tpr] = group_to_f32<CH>(v[u]);
     }
-  } else if (by_groups) {  // a tile that sticks out of its stream: clamped loads, then the groups outside sample by sample
+  } else if (by_groups) {  // a tile that sticks out of its piece: the groups outside it sample by sample
     float4 *dst = lds4 + pitch * row;
     const long long from = first0 + (long long)row * M;
-    const long long last_group = ((long long)n_in - 4) & ~3ll;  // last aligned group wholly inside the stream
     for (int o = me; o < groups; o += tpr) {
       const long long idx = from + 4 * (long long)o;
-      if (idx < 0 || idx > last_group)
+      if (idx < first_group || idx > last_group)
         dst[o] = float4{(float)sample(idx), (float)sample(idx + 1), (float)sample(idx + 2), (float)sample(idx + 3)};
       else
         dst[o] = group_to_f32<CH>(*reinterpret_cast<const raw_t *>(src + (size_t)CH * idx));
@@ -489,7 +490,7 @@ __global__ __launch_bounds__(SMALL ? 640 : 1024, SMALL ? 5 : 4) void resample_qu
   // so that some stage while others compute.
   const int quads = (L + 3) >> 2, quads_per_split = (quads + splits - 1) / splits;
   const uint32_t in_stream = blockIdx.x - st.block_base;
-  const uint64_t tile = in_stream / (uint32_t)splits;
+  const uint64_t tile = in_stream / (uint32_t)splits + st.t0;
   const int q0 = (int)(in_stream % (uint32_t)splits) * quads_per_split, q1 = min(quads, q0 + quads_per_split);
   if (q0 >= q1) return;
   const uint64_t tile_base = tile * (uint64_t)tile_outputs;
@@ -504,7 +505,7 @@ __global__ __launch_bounds__(SMALL ? 640 : 1024, SMALL ? 5 : 4) void resample_qu
   // lane has finished reading it (a barrier more, 4.7 KB of LDS less: three workgroups per CU at 48 kHz instead of two)
   int16_t *out_tile = reinterpret_cast<int16_t *>(lds4);
 
-  if (!(LAB & 1)) stage_quad_rows<CH, VEC4>(lds4, src, st.n_in, first0, M, geo.pitch, groups);
+  if (!(LAB & 1)) stage_quad_rows<CH, VEC4>(lds4, src, st.n_in, st.lo, st.hi, first0, M, geo.pitch, groups);
   __syncthreads();
 
   // ---- quads: DPP row dr of the workgroup takes quad u = round * rows + dr; lane j of the row takes row j ----------
@@ -615,25 +616,15 @@ __global__ __launch_bounds__(THREADS) void resample_dec_kernel(const int16_t *__
     if (streams[mid].block_base <= blockIdx.x) lo = mid; else hi = mid - 1;
   }
   const RsStream st = streams[lo];
-  const uint64_t tile = blockIdx.x - st.block_base;
+  const uint64_t tile = blockIdx.x - st.block_base + st.t0;
   const uint64_t tile_base = tile * (uint64_t)kTile;
   const long long first0 = (long long)(tile_base * (uint64_t)M) - half + 1 - kDelta;  // input index of region[0]
   const int16_t *src = in + st.in_off;
-  auto sample = [&](long long idx) -> int {  // one down-mixed input sample, 0 outside the stream
-    const bool ok = idx >= 0 && (uint64_t)idx < st.n_in;
-    const long long at = idx < 0 ? 0 : ((uint64_t)idx < st.n_in ? idx : (long long)st.n_in - 1);
-    int sv;
-    if (CH == 1) {
-      sv = src[at];
-    } else {
-      const int v = reinterpret_cast<const int *>(src)[at];
-      sv = ((int)(int16_t)v + (v >> 16)) / 2;
-    }
-    return ok ? sv : 0;
-  };
+  const bool odd = CH == 2 && (reinterpret_cast<uintptr_t>(src) & 3) != 0;
+  auto sample = [&](long long idx) -> int { return rs_sample<CH>(src, st.n_in, st.lo, st.hi, odd, idx); };
   // ---- staging by aligned groups of four samples (first0 is a multiple of 4) --------------------------------------
-  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0 && st.n_in >= 4;
-  if (aligned && first0 >= 0 && first0 + 4ll * kRegion <= (long long)st.n_in) {  // inside the stream: no clamps
+  const bool aligned = (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+  if (aligned && first0 >= (long long)st.lo && first0 + 4ll * kRegion <= (long long)st.hi) {  // inside the piece: no clamps
     const raw_t *base = reinterpret_cast<const raw_t *>(src + (size_t)CH * first0);
     constexpr int kInFlight = 6;
     for (int o0 = threadIdx.x; o0 < kRegion; o0 += THREADS * kInFlight) {
@@ -644,7 +635,7 @@ __global__ __launch_bounds__(THREADS) void resample_dec_kernel(const int16_t *__
       for (int u = 0; u < kInFlight; u++)
         if (o0 + u * THREADS < kRegion) region[o0 + u * THREADS] = group_to_f32<CH>(v[u]);
     }
-  } else {  // first / last tile of a stream, or an unaligned stream: sample by sample, zeros outside
+  } else {  // first / last tile of a stream or piece, or an unaligned stream: sample by sample, zeros outside
     for (int o = threadIdx.x; o < kRegion; o += THREADS) {
       const long long idx = first0 + 4ll * o;
       region[o] = float4{(float)sample(idx), (float)sample(idx + 1), (float)sample(idx + 2), (float)sample(idx + 3)};
@@ -692,21 +683,10 @@ size_t resample_out_len(size_t n_in, int rate) {
   return (size_t)(((unsigned long long)n_in * L + M - 1) / M);
 }
 
-// streams: (in_off in s16 values, n_in samples per channel, out_off samples); d_out receives mono s16 @ 11025 Hz
-Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> &spans, int channels, int rate,
-                           int16_t *d_out, bool sync) {
-  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
-  if (channels != 1 && channels != 2) return Status::Make(NeedleError_InvalidArgument, "resample: channels must be 1 or 2");
-  if (rate < 2000 || rate > 768000) return Status::Make(NeedleError_InvalidArgument, "resample: unsupported sample rate");
-  if (channels == 2) {  // the kernel reads a stereo sample as one aligned 32-bit word
-    if (reinterpret_cast<uintptr_t>(d_in) & 3) return Status::Make(NeedleError_InvalidArgument, "resample: stereo PCM must be 4-byte aligned");
-    for (const ResampleSpan &sp : spans)
-      if (sp.in_off & 1) return Status::Make(NeedleError_InvalidArgument, "resample: stereo streams must start on an even value offset");
-  }
-  Status s = ensure_device();
-  if (!s.ok()) return s;
-  int dev = 0;
-  NEEDLE_HIP_TRY(hipGetDevice(&dev));
+namespace {
+
+// the filter of `rate` on device `dev` and its tables, built on first use
+Status get_design(int dev, int rate, Design **out) {
   Design *d;
   {
     std::lock_guard<std::mutex> lock(g_mu);
@@ -804,6 +784,25 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
       }
     }
   }
+  *out = d;
+  return Status::Ok();
+}
+
+constexpr int kDecThreads = 256;
+
+// which kernel gpu_resample_device launches for a design, and its geometry
+struct KernelPlan {
+  int quad_splits = 1, quads_per_split = 1, quad_pitch = 0, quad_threads = 0;
+  size_t quad_lds = 0;
+  bool quad = false, dec = false, mfma = false;
+  int dec_q = 0;
+  int mf_splits = 1, mf_waves = 1, mf_groups = 0, mf_buffer_floats = 0;
+  size_t mf_lds = 0;
+  uint64_t tile_outputs = 1;  // consecutive outputs of a stream per tile
+  uint64_t blocks_per_tile() const { return dec ? 1 : mfma ? (uint64_t)mf_splits : quad ? (uint64_t)quad_splits : 1; }
+};
+
+KernelPlan plan_kernel(const Design *d) {
   // Decimation steps of 64 samples or more use the row layout; there the kernel with four consecutive outputs per
   // lane applies (NEEDLE_HIP_RESAMPLE_V1 forces the first kernel: tests and A/B timing).
   // a tile's rows are cut into `quad_splits` workgroups (see the kernel); the rows of a workgroup: the groups between
@@ -823,7 +822,6 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
                     (size_t)kQuadRows * 4 * quads_per_split * 2 <= quad_lds &&
                     quads_per_split <= kQuadMaxRounds * (quad_threads / 16) && getenv("NEEDLE_HIP_RESAMPLE_V1") == nullptr;
   // integer decimation by 4 or 2 (44.1 / 22.05 kHz): the kernel with scalar coefficients
-  constexpr int kDecThreads = 256;
   const int dec_q = d->L == 1 && d->T == 32 * d->M ? (d->M == 4 ? 5 : d->M == 2 ? 6 : 0) : 0;
   const bool dec = dec_q != 0 && getenv("NEEDLE_HIP_RESAMPLE_V1") == nullptr;
   // matrix-core kernel (resample_mfma.h): one wave per block of sixteen outputs of a row, at most `mf_waves` per
@@ -847,18 +845,94 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
                       mf_groups - mfma_rs::kCovered <= 64 * mfma_rs::kProducers)) &&
                     mf_lds <= 160 * 1024 && getenv("NEEDLE_HIP_RESAMPLE_QUAD") == nullptr;
   const uint64_t tile_outputs = dec ? (uint64_t)kDecThreads * dec_q : quad ? (uint64_t)kQuadRows * d->L : (uint64_t)d->n * d->L;
+  KernelPlan k;
+  k.quad_splits = quad_splits; k.quads_per_split = quads_per_split; k.quad_pitch = quad_pitch; k.quad_threads = quad_threads;
+  k.quad_lds = quad_lds; k.quad = quad; k.dec = dec; k.mfma = mfma; k.dec_q = dec_q;
+  k.mf_splits = mf_splits; k.mf_waves = mf_waves; k.mf_groups = mf_groups; k.mf_buffer_floats = mf_buffer_floats;
+  k.mf_lds = mf_lds; k.tile_outputs = tile_outputs;
+  return k;
+}
+
+}  // namespace
+
+Status resample_tiling(int rate, int channels, ResampleTiling *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  if (channels != 1 && channels != 2) return Status::Make(NeedleError_InvalidArgument, "resample: channels must be 1 or 2");
+  if (rate < 2000 || rate > 768000) return Status::Make(NeedleError_InvalidArgument, "resample: unsupported sample rate");
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  int dev = 0;
+  NEEDLE_HIP_TRY(hipGetDevice(&dev));
+  Design *d;
+  if (!(s = get_design(dev, rate, &d)).ok()) return s;
+  out->L = d->L;
+  out->M = d->M;
+  out->half = d->T / 2;
+  out->tile_outputs = plan_kernel(d).tile_outputs;
+  return Status::Ok();
+}
+
+void resample_piece(const ResampleTiling &t, uint64_t n_in, uint64_t t0, uint64_t t1, uint64_t *p0, uint64_t *p1) {
+  const uint64_t n_out = (n_in * (uint64_t)t.L + (uint64_t)t.M - 1) / (uint64_t)t.M;  // resample_out_len
+  const uint64_t a = std::min(t0 * t.tile_outputs, n_out), b = std::min(t1 * t.tile_outputs, n_out);
+  if (a >= b) {
+    *p0 = *p1 = 0;
+    return;
+  }
+  const long long first = (long long)(a * (uint64_t)t.M / (uint64_t)t.L) - t.half + 1;
+  const uint64_t last = (b - 1) * (uint64_t)t.M / (uint64_t)t.L + (uint64_t)t.half + 1;  // one past the last tap
+  *p0 = first <= 0 ? 0 : (uint64_t)first & ~(uint64_t)7;
+  *p1 = std::min(n_in, last);
+}
+
+// streams: (in_off in s16 values or an own source, n_in samples per channel, out_off samples, optional tiles and piece);
+// d_out receives mono s16 @ 11025 Hz.  Streams and sources may have any 2-byte alignment (16-byte aligned ones stage
+// fastest).
+Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> &spans, int channels, int rate,
+                           int16_t *d_out, bool sync) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  if (channels != 1 && channels != 2) return Status::Make(NeedleError_InvalidArgument, "resample: channels must be 1 or 2");
+  if (rate < 2000 || rate > 768000) return Status::Make(NeedleError_InvalidArgument, "resample: unsupported sample rate");
+  // the kernels read stream i at in_base + meta[i].in_off: the input arena, or else the first stream's own source
+  const int16_t *in_base = d_in;
+  for (const ResampleSpan &sp : spans)
+    if (!in_base && sp.src) in_base = sp.src;
+  for (const ResampleSpan &sp : spans)
+    if (!sp.src && !d_in) return Status::Make(NeedleError_NullArgument, "resample: a stream without a source and no input arena");
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  int dev = 0;
+  NEEDLE_HIP_TRY(hipGetDevice(&dev));
+  Design *d;
+  if (!(s = get_design(dev, rate, &d)).ok()) return s;
+  const KernelPlan kp = plan_kernel(d);
+  const int quad_splits = kp.quad_splits, quad_pitch = kp.quad_pitch, quad_threads = kp.quad_threads;
+  const size_t quad_lds = kp.quad_lds;
+  const bool quad = kp.quad, dec = kp.dec, mfma = kp.mfma;
+  const int mf_splits = kp.mf_splits, mf_waves = kp.mf_waves, mf_groups = kp.mf_groups, mf_buffer_floats = kp.mf_buffer_floats;
+  const size_t mf_lds = kp.mf_lds;
+  const uint64_t tile_outputs = kp.tile_outputs;
   std::vector<RsStream> meta;
   uint64_t blocks = 0;
   for (const ResampleSpan &sp : spans) {
     RsStream m;
-    m.in_off = sp.in_off;
+    m.lo = sp.p1 ? sp.p0 : 0;
+    m.hi = sp.p1 ? sp.p1 : sp.n_in;
+    // sample 0 of the stream, in values from in_base; with an own source that is where sample p0 lies
+    m.in_off = sp.src ? (int64_t)((intptr_t)sp.src - (intptr_t)in_base) / 2 - (int64_t)(m.lo * (uint64_t)channels)
+                      : (int64_t)(d_in - in_base) + (int64_t)sp.in_off;
     m.n_in = sp.n_in;
     m.out_off = sp.out_off;
     m.n_out = resample_out_len(sp.n_in, rate);
+    const uint64_t tiles = (m.n_out + tile_outputs - 1) / tile_outputs, t1 = sp.t1 ? std::min(sp.t1, tiles) : tiles;
+    if (!m.n_out || sp.t0 >= t1) continue;
+    if (m.lo >= m.hi || m.hi > m.n_in || sp.t0 > UINT32_MAX)
+      return Status::Make(NeedleError_InvalidArgument, "resample: a piece outside its stream");
     m.block_base = (uint32_t)blocks;
-    m.pad = 0;
-    blocks += (m.n_out + tile_outputs - 1) / tile_outputs * (dec ? 1 : mfma ? (uint64_t)mf_splits : quad ? (uint64_t)quad_splits : 1);
-    if (m.n_out) meta.push_back(m);
+    m.t0 = (uint32_t)sp.t0;
+    blocks += (t1 - sp.t0) * kp.blocks_per_tile();
+    if (blocks > 0x7FFFFFFFull) break;
+    meta.push_back(m);
   }
   if (blocks > 0x7FFFFFFFull) return Status::Make(NeedleError_InvalidArgument, "resample: batch too large for one launch");
   if (!meta.empty()) {
@@ -877,7 +951,7 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
     if (dec) {
       KernelTimer timer("resample");
       auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kDecThreads), 0, stream, d_in, w.first->ptr, (int)meta.size(),
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kDecThreads), 0, stream, in_base, w.first->ptr, (int)meta.size(),
                            d->d_coef_plain, d_out);
       };
       if (d->M == 4) {
@@ -933,7 +1007,7 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
           have = mf_lds;
         }
         KernelTimer timer("resample");
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(mf_threads), mf_lds, stream, d_in, w.first->ptr,
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(mf_threads), mf_lds, stream, in_base, w.first->ptr,
                            (int)meta.size(), d->d_coef_b, d->d_block_k0, mg, (uint32_t)blocks, mf_buffer_floats, d_out);
         return Status::Ok();
       };
@@ -1034,7 +1108,7 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
       KernelTimer timer("resample");
       const float4 *coefq = reinterpret_cast<const float4 *>(d->d_coefq);
       auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(threads), quad_lds, stream, d_in, w.first->ptr,
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(threads), quad_lds, stream, in_base, w.first->ptr,
                            (int)meta.size(), coefq, static_cast<const QuadInfo *>(d->d_quad_info), geo, d->steps, quad_splits,
                            skew_blocks, skew_unit, d_out);
       };
@@ -1103,7 +1177,7 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
     KernelTimer timer("resample");
     const float4 *coef4 = reinterpret_cast<const float4 *>(d->d_coef);
     auto launch = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kThreads), lds_bytes, stream, d_in, w.first->ptr,
+      hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(kThreads), lds_bytes, stream, in_base, w.first->ptr,
                          (int)meta.size(), coef4, geo, d_out);
     };
     if (channels == 1) {

@@ -1,5 +1,5 @@
 // Resampler on the matrix cores: the kernel for decimation steps M >= 64 with M % 4 == 0 (48, 32, 24, 16, 8 kHz ...).
-// Included by resample.hip only (it uses that file's RsStream and the down-mix helper).
+// Included by resample.hip only (it uses that file's RsStream and its sample helper rs_sample).
 //
 // Specification and oracle are unchanged (oracle/ora_resample.h): every output is a chain of f32 fused multiply-adds in
 // tap order.  v_mfma_f32_16x16x4_f32 IS such a chain -- D = fma(a3, b3, fma(a2, b2, fma(a1, b1, fma(a0, b0, C)))), one
@@ -55,20 +55,6 @@ struct Geom {
 // delta, a multiple of 4)
 
 template <int CH>
-__device__ __forceinline__ int downmixed(const int16_t *src, uint64_t n_in, long long idx) {
-  const bool ok = idx >= 0 && (uint64_t)idx < n_in;
-  const long long at = idx < 0 ? 0 : ((uint64_t)idx < n_in ? idx : (long long)n_in - 1);
-  int sv;
-  if (CH == 1) {
-    sv = src[at];
-  } else {
-    const int v = reinterpret_cast<const int *>(src)[at];
-    sv = ((int)(int16_t)v + (v >> 16)) / 2;  // integer down-mix, C truncation
-  }
-  return ok ? sv : 0;
-}
-
-template <int CH>
 struct Raw { typedef typename std::conditional<CH == 1, int2, int4>::type type; };
 
 // four down-mixed samples of one aligned group as f32.  The down-mix (L + R) / 2 with C truncation is done in f32 -- the sum
@@ -88,15 +74,16 @@ __device__ __forceinline__ float4 group_f32(typename Raw<CH>::type v) {
 
 // where a tile's samples come from
 struct TileSrc {
-  uint64_t in_off;     // the stream's first value, in s16 values from the arena's start
+  int64_t in_off;      // the stream's sample 0, in s16 values from the kernel's `in` (RsStream)
   uint64_t n_in;
+  uint64_t lo, hi;     // the piece that may be read (RsStream)
   long long first0;    // input sample at [0][row 0] of the region
-  bool fast;           // the tile lies inside its stream and the stream is 16-byte aligned: staged by aligned groups
+  bool fast;           // the tile lies inside its piece and the stream is 16-byte aligned: staged by aligned groups
 };
 
-__device__ __forceinline__ bool tile_is_fast(const int16_t *src, uint64_t n_in, long long first0, const Geom &geo) {
+__device__ __forceinline__ bool tile_is_fast(const int16_t *src, uint64_t lo, uint64_t hi, long long first0, const Geom &geo) {
   const long long tile_last = first0 + max((long long)(kRows - 1) * geo.M + 4ll * kCovered, (long long)kRows * geo.M + 4ll * geo.dup_hi);
-  return (reinterpret_cast<uintptr_t>(src) & 15) == 0 && first0 >= 0 && tile_last <= (long long)n_in;
+  return (reinterpret_cast<uintptr_t>(src) & 15) == 0 && first0 >= (long long)lo && tile_last <= (long long)hi;
 }
 
 // what a staging thread carries from the loads of a tile to its LDS writes
@@ -156,7 +143,7 @@ __device__ __forceinline__ void stage_pass(Staged<CH> &sg, float *lds, const int
   // (the tiles by value and flags, not by pointer: a pointer that may be null keeps both structures in scratch memory)
   const bool cur_fast = have_cur && cur.fast, next_fast = have_next && next.fast;
   // (derived from the kernel argument in every path, so that the loads are global_load, not flat_load)
-  const raw_t *tile_base = reinterpret_cast<const raw_t *>(in + (next_fast ? next.in_off + (uint64_t)CH * next.first0 : 0));
+  const raw_t *tile_base = reinterpret_cast<const raw_t *>(in + (next_fast ? next.in_off + (int64_t)CH * next.first0 : 0));
   const raw_t *base = tile_base + row_groups;
   const raw_t *tail_at = tile_base + (uint32_t)(kRows * geo.m_groups + geo.dup_lo + min(pt, max(tail_count, 1) - 1));
   if (cur_fast && next_fast) {  // the steady state
@@ -176,10 +163,12 @@ __device__ __forceinline__ void stage_pass(Staged<CH> &sg, float *lds, const int
 #pragma unroll
     for (int u = 0; u < kPrefetch; u++) NEEDLE_RS_WRITE(u);
     write_tail();
-  } else if (have_cur && !cur_fast && !(LAB & 2)) {  // first / last tiles of a stream, unaligned streams: sample by sample
+  } else if (have_cur && !cur_fast && !(LAB & 2)) {  // first / last tiles of a stream or piece, unaligned streams: sample by sample
     const long long from = cur.first0 + (long long)row * geo.M;
+    const int16_t *src = in + cur.in_off;
+    const bool odd = CH == 2 && (reinterpret_cast<uintptr_t>(src) & 3) != 0;
     for (int m = g0; m < 4 * groups; m += gstep)
-      lds[(size_t)m * kRows + row] = (float)downmixed<CH>(in + cur.in_off, cur.n_in, from + m);
+      lds[(size_t)m * kRows + row] = (float)rs_sample<CH>(src, cur.n_in, cur.lo, cur.hi, odd, from + m);
   }
   if (next_fast && !(LAB & 1)) {
 #pragma unroll
@@ -238,7 +227,7 @@ __global__ __launch_bounds__(1024) void resample_mfma_kernel(
       c.st = streams[c.at];
       c.next_base = c.at + 1 < num_streams ? streams[c.at + 1].block_base : 0xFFFFFFFFu;
     }
-    tile = (vb - c.st.block_base) / (uint32_t)geo.splits;
+    tile = (vb - c.st.block_base) / (uint32_t)geo.splits + c.st.t0;
   };
   auto first_of = [&](uint64_t tile) {
     return (long long)(tile * (uint64_t)kRows * (uint64_t)geo.M) - geo.half + 1 - geo.delta + region_start;
@@ -264,8 +253,10 @@ __global__ __launch_bounds__(1024) void resample_mfma_kernel(
       TileSrc ts;
       ts.in_off = cur.st.in_off;
       ts.n_in = cur.st.n_in;
+      ts.lo = cur.st.lo;
+      ts.hi = cur.st.hi;
       ts.first0 = first_of((LAB & 64) ? (tile & 31) + 1 : tile);  // (lab 64: every load hits the L2)
-      ts.fast = (LAB & 1) || tile_is_fast(in + ts.in_off, ts.n_in, ts.first0, geo);
+      ts.fast = (LAB & 1) || tile_is_fast(in + ts.in_off, ts.lo, ts.hi, ts.first0, geo);
       return ts;
     };
     TileSrc a = source(0), nx = a;

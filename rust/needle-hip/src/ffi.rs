@@ -227,6 +227,7 @@ extern "C" {
         out: *const *mut i16,
     ) -> NeedleError;
     pub fn needle_hip_library_include_endings(library: *mut NeedleHipLibrary, ending_search_percentage: f32) -> NeedleError;
+    pub fn needle_hip_library_set_sample_rate(library: *mut NeedleHipLibrary, sample_rate: c_int) -> NeedleError;
     pub fn needle_hip_library_set_pcm(
         library: *mut NeedleHipLibrary,
         pcm: *const *const i16,

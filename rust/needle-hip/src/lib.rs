@@ -592,6 +592,15 @@ pub mod multi_gpu {
             Ok(Library { raw, num_videos })
         }
 
+        /// The sample rate of the PCM `load_pcm` and `rank_videos` will be given (2000..768000 Hz, default 11025): the
+        /// windows are cut at that rate and resampled to 11025 Hz mono on the device on the way in
+        /// (`needle_hip_library_set_sample_rate`).  Call before `load_pcm`.
+        pub fn set_sample_rate(&mut self, sample_rate: u32) -> Result<&mut Self> {
+            let rate = c_int::try_from(sample_rate).unwrap_or(c_int::MAX);
+            unsafe { check(ffi::needle_hip_library_set_sample_rate(self.raw, rate))? };
+            Ok(self)
+        }
+
         /// The videos `[first, first + count)` whose PCM rank `rank` of `world_size` has to hold: the fingerprinting
         /// is cut by hashes (equal blocks of the arena), not by videos, so no rank idles; a pure function of the
         /// library's parameters and the stream lengths (`needle_hip_library_rank_videos`).
