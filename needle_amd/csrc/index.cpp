@@ -5,7 +5,7 @@
 // every existing pair keeps its source / destination roles, and every new pair of an old video v is (v, new), after all
 // of v's old pairs in the full search over the concatenated list.  So keeping every pair's entries, computing entries for
 // the new pairs only and re-running best_match for the videos whose candidate list changed is bit-identical to
-// Comparator::run_with_frame_hashes over all videos in insertion order.  The entries live on the device (epilogue.hip,
+// Comparator::run_with_frame_hashes over all videos in insertion order.  The entries live on the device (index_store.hip,
 // IndexStore) under column-major pair ids p(i, j) = j (j - 1) / 2 + i, which do not depend on the number of videos.
 #include "index.h"
 
@@ -15,6 +15,7 @@
 #include <unordered_map>
 
 #include "epilogue.h"
+#include "index_store.h"
 
 namespace needle {
 
@@ -68,6 +69,74 @@ void host_entries(const Comparator &cmp, size_t R, uint64_t buckets, const std::
   entries_out->swap(entries);
 }
 
+// After gpu_index_append / gpu_index_edit.  A bucket the device does not order: the operation's entries are computed here from
+// its run list and given back through upload(start, valid, entries), which runs its second half again.  Then the failure count.
+template <class PairOf, class RowSeq, class Video, class Upload>
+Status settle(const Comparator &cmp, const char *where, size_t R, size_t videos, uint64_t buckets, PairOf pair_of, RowSeq row_seq, Video video,
+              Upload upload, const IndexAppendOut &out) {
+  if (out.failed & kEpilogueBucketTooLarge) {
+    note_epilogue_host_fallback(where, out.runs.size(), videos);
+    std::vector<uint32_t> start, valid;
+    std::vector<IndexEntry> entries;
+    host_entries(cmp, R, buckets, out.runs, pair_of, row_seq, video, &start, &valid, &entries);
+    Status s = upload(start, valid, entries);  // (writes `out`)
+    if (!s.ok()) return s;
+  }
+  if (out.failed)  // best_match_kernel: the winner's end minus padding / hash duration underflows (the reference panics)
+    return Status::Make(NeedleError_Unknown, "overflow when subtracting durations (time_padding / hash_duration exceed the match end)");
+  return Status::Ok();
+}
+
+void set_options(const Comparator &cmp, size_t R, bool large_ok, IndexOptions *o) {
+  o->regions = (uint32_t)R;
+  o->threshold = cmp.hash_match_threshold();
+  o->include_endings = cmp.include_endings();
+  o->large_ok = large_ok;
+  o->min_opening_duration = cmp.min_opening_duration();
+  o->min_ending_duration = cmp.min_ending_duration();
+  o->time_padding = cmp.time_padding();
+}
+
+// Row `at` joins the index: its hashes (`hashes`) go behind the arena's, its timestamps (`ts`) behind the table's -- or, where
+// they equal those of video 0's row of the same region (`first`, row `at % R`; null for video 0 itself), it reads that table,
+// as in run_with_frame_hashes' device epilogue.  row_ok: what pair_entries_large_kernel's packed keys stand on.
+Status fresh_row(const Comparator &cmp, const std::vector<HashTs> &seq, const std::vector<HashTs> *first, size_t R, size_t at, IndexRows *rows,
+                 std::vector<uint32_t> *hashes, std::vector<uint64_t> *ts) {
+  if (rows->hashes + seq.size() > UINT32_MAX)  // offsets into the arena are 32-bit on the device (NeedleHipSeq.offset)
+    return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
+  rows->seqs[at] = NeedleHipSeq{(uint32_t)rows->hashes, (uint32_t)seq.size()};
+  rows->hashes += seq.size();
+  for (const HashTs &h : seq) hashes->push_back(h.hash);
+  rows->min_len[at] = cmp.min_run_length_for(seq, at % R == 0);
+  bool same = first && seq.size() == first->size();
+  for (size_t q = 0; q < seq.size() && same; q++) same = seq[q].ts == (*first)[q].ts;
+  if (same) {
+    rows->row_ts[at] = rows->row_ts[at % R];
+  } else {
+    rows->row_ts[at] = (uint32_t)rows->ts;
+    for (const HashTs &h : seq) ts->push_back(h.ts);
+    rows->ts += seq.size();
+    if (rows->ts > UINT32_MAX) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 timestamps");
+  }
+  bool ok = seq.size() < 65536u;
+  for (size_t q = 1; q < seq.size() && ok; q++) ok = seq[q].ts > seq[q - 1].ts;
+  rows->row_ok[at] = ok;
+  return Status::Ok();
+}
+
+// The problems of pair (i, j), tagged from `tag` on; min_len and the regions left out as in run_with_frame_hashes (one of
+// whose sequences can hold no run long enough).  Whether any region is searched.
+bool pair_problems(const std::vector<uint32_t> &min_len, size_t R, size_t i, size_t j, uint64_t tag, std::vector<NeedleHipProblem> *problems) {
+  bool any = false;
+  for (size_t r = 0; r < R; r++) {
+    const uint32_t a = min_len[i * R + r], b = min_len[j * R + r];
+    if (a == 0 || b == 0) continue;
+    problems->push_back(NeedleHipProblem{(uint32_t)(i * R + r), (uint32_t)(j * R + r), std::max(a, b), (uint32_t)(tag + r)});
+    any = true;
+  }
+  return any;
+}
+
 }  // namespace
 
 Index::Index(const Comparator &comparator)
@@ -90,45 +159,23 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
     for (size_t v = 0; v < n1; v++)
       if (video(v).ending.empty())  // comparator.rs:271-273 (every video is in some pair)
         return Status::Make(NeedleError_Unknown, "no ending hash data present");
-  // the new rows: hashes behind the arena's, timestamps behind the table's (a row whose timestamps equal video 0's of the
-  // same region reads that table, as in run_with_frame_hashes' device epilogue)
-  std::vector<NeedleHipSeq> seqs(seqs_);
-  std::vector<uint32_t> min_len(min_len_), row_ts(row_ts_), new_row_len, new_row_ts, hashes;
-  std::vector<uint8_t> row_ok(row_ok_);
+  IndexRows rows(rows_);
+  rows.seqs.resize(n1 * R);
+  rows.min_len.resize(n1 * R);
+  rows.row_ts.resize(n1 * R);
+  rows.row_ok.resize(n1 * R);
+  std::vector<uint32_t> new_row_len, hashes;
   std::vector<uint64_t> ts, hash_duration;
-  uint64_t num_hashes = hashes_, num_ts = ts_;
-  bool large_ok = large_ok_;
   for (size_t v = n0; v < n1; v++) {
     hash_duration.push_back(video(v).hash_duration);
-    for (size_t r = 0; r < R; r++) {
-      const std::vector<HashTs> &seq = row_seq(v, r);
-      if (num_hashes + seq.size() > UINT32_MAX)  // offsets into the arena are 32-bit on the device (NeedleHipSeq.offset)
-        return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
-      seqs.push_back(NeedleHipSeq{(uint32_t)num_hashes, (uint32_t)seq.size()});
-      num_hashes += seq.size();
-      for (const HashTs &h : seq) hashes.push_back(h.hash);
-      min_len.push_back(cmp_.min_run_length_for(seq, r == 0));
-      new_row_len.push_back((uint32_t)seq.size());
-      const std::vector<HashTs> &first = row_seq(0, r);
-      bool same = v > 0 && seq.size() == first.size();
-      for (size_t q = 0; q < seq.size() && same; q++) same = seq[q].ts == first[q].ts;
-      if (same) {
-        row_ts.push_back(row_ts[r]);
-      } else {
-        row_ts.push_back((uint32_t)num_ts);
-        for (const HashTs &h : seq) ts.push_back(h.ts);
-        num_ts += seq.size();
-        if (num_ts > UINT32_MAX) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 timestamps");
-      }
-      new_row_ts.push_back(row_ts.back());
-      bool ok = seq.size() < 65536u;  // what pair_entries_large_kernel's packed keys stand on
-      for (size_t q = 1; q < seq.size() && ok; q++) ok = seq[q].ts > seq[q - 1].ts;
-      row_ok.push_back(ok);
-      large_ok = large_ok && ok;
+    for (size_t at = v * R; at < (v + 1) * R; at++) {
+      Status s = fresh_row(cmp_, row_seq(v, at % R), v > 0 ? &row_seq(0, at % R) : nullptr, R, at, &rows, &hashes, &ts);
+      if (!s.ok()) return s;
+      new_row_len.push_back(rows.seqs[at].len);
+      rows.large_ok = rows.large_ok && rows.row_ok[at];
     }
   }
-  // the new pairs (i, j), j in [n0, n1), i < j, in column-major order; min_len and the pairs left out as in
-  // run_with_frame_hashes (a pair one of whose sequences can hold no run long enough)
+  // the new pairs (i, j), j in [n0, n1), i < j, in column-major order
   const uint64_t first_pair = (uint64_t)n0 * (n0 ? n0 - 1 : 0) / 2;
   const uint64_t new_pairs = (uint64_t)n1 * (n1 - 1) / 2 - first_pair;
   if (((uint64_t)n1 * (n1 - 1) / 2) * R >= 0xFFFFFFF0ull)  // problem tags and bucket ids are 32-bit on the device
@@ -137,35 +184,19 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
   problems.reserve(new_pairs * R);
   uint64_t searched = 0;
   for (size_t j = n0; j < n1; j++)
-    for (size_t i = 0; i < j; i++) {
-      const uint64_t rel = (uint64_t)j * (j - 1) / 2 + i - first_pair;
-      bool any = false;
-      for (size_t r = 0; r < R; r++) {
-        const uint32_t a = min_len[i * R + r], b = min_len[j * R + r];
-        if (a == 0 || b == 0) continue;
-        problems.push_back(NeedleHipProblem{(uint32_t)(i * R + r), (uint32_t)(j * R + r), std::max(a, b), (uint32_t)(rel * R + r)});
-        any = true;
-      }
-      searched += any;
-    }
+    for (size_t i = 0; i < j; i++) searched += pair_problems(rows.min_len, R, i, j, ((uint64_t)j * (j - 1) / 2 + i - first_pair) * R, &problems);
   IndexAppend a;
   a.n0 = (uint32_t)n0;
   a.n1 = (uint32_t)n1;
-  a.regions = (uint32_t)R;
-  a.threshold = cmp_.hash_match_threshold();
-  a.include_endings = include_endings_;
-  a.large_ok = large_ok;
-  a.min_opening_duration = cmp_.min_opening_duration();
-  a.min_ending_duration = cmp_.min_ending_duration();
-  a.time_padding = cmp_.time_padding();
+  set_options(cmp_, R, rows.large_ok, &a);
   a.hashes = hashes.data();
   a.num_hashes = hashes.size();
-  a.seqs = seqs.data();
-  a.num_seqs = seqs.size();
+  a.seqs = rows.seqs.data();
+  a.num_seqs = rows.seqs.size();
   a.problems = problems.data();
   a.num_problems = problems.size();
   a.row_len = new_row_len.data();
-  a.row_ts = new_row_ts.data();
+  a.row_ts = rows.row_ts.data() + n0 * R;
   a.num_rows = new_row_len.size();
   a.ts = ts.data();
   a.num_ts = ts.size();
@@ -173,28 +204,13 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
   IndexAppendOut out;
   Status s = gpu_index_append(store_, a, &out);
   if (!s.ok()) return s;
-  if (out.failed & kEpilogueBucketTooLarge) {
-    // A bucket the device does not order (beyond kEpilogueLargeLimit runs, or rows the packed keys cannot stand for): this
-    // append's new-pair entries are computed here from its run list, with the host form's own functions.
-    note_epilogue_host_fallback("Index::add", out.runs.size(), n1);
-    std::vector<uint32_t> start, valid;
-    std::vector<IndexEntry> entries;
-    host_entries(cmp_, R, new_pairs * R, out.runs, [&](uint64_t q, size_t *i, size_t *j) { column_pair(first_pair + q, i, j); }, row_seq,
-                 video, &start, &valid, &entries);
-    if (!(s = gpu_index_append_host_entries(store_, a, start, valid, entries, &out)).ok()) return s;
-  }
-  if (out.failed)  // best_match_kernel: the winner's end minus padding / hash duration underflows (the reference panics)
-    return Status::Make(NeedleError_Unknown, "overflow when subtracting durations (time_padding / hash_duration exceed the match end)");
+  s = settle(cmp_, "Index::add", R, n1, new_pairs * R, [&](uint64_t q, size_t *i, size_t *j) { column_pair(first_pair + q, i, j); }, row_seq, video,
+             [&](const auto &...computed) { return gpu_index_append_host_entries(store_, a, computed..., &out); }, out);
+  if (!s.ok()) return s;
   // commit: nothing above changed the index
   index_store_commit(store_, a, out.found);
   for (const FrameHashesData *d : fh) videos_.push_back(*d);
-  seqs_.swap(seqs);
-  min_len_.swap(min_len);
-  row_ts_.swap(row_ts);
-  hashes_ = num_hashes;
-  ts_ = num_ts;
-  large_ok_ = large_ok;
-  row_ok_.swap(row_ok);
+  rows_ = std::move(rows);
   results_.resize(n1, NeedleHipSearchResult{});
   for (size_t q = 0; q < out.videos.size(); q++) results_[out.videos[q]] = out.results[q];
   pairs_last_ = searched;
@@ -244,13 +260,8 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   if (n1 == 0) {  // every video removed: nothing is left to search or to hold
     index_store_clear(store_);
     videos_.clear();
-    seqs_.clear();
-    min_len_.clear();
-    row_ts_.clear();
-    row_ok_.clear();
+    rows_ = IndexRows();
     results_.clear();
-    hashes_ = ts_ = 0;
-    large_ok_ = true;
     pairs_last_ = 0;
     return Status::Ok();
   }
@@ -271,84 +282,53 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   // The new rows.  Kept rows first, gathered on the device: their hashes in order, and each distinct run of the timestamp
   // table they read once (rows that shared video 0's timestamps keep sharing them, whichever video is removed).  Then the
   // fresh rows behind them, sharing the new video 0's timestamps where equal, as an append does.
-  std::vector<NeedleHipSeq> seqs(n1 * R);
-  std::vector<uint32_t> min_len(n1 * R), row_ts(n1 * R), row_len(n1 * R), hashes;
-  std::vector<uint8_t> row_ok(n1 * R);
+  IndexRows rows(n1 * R);
+  std::vector<uint32_t> row_len(n1 * R), hashes;
   std::vector<uint64_t> ts, hash_duration(n1);
   std::vector<IndexSegment> hash_rows, ts_rows;
   std::unordered_map<uint32_t, uint32_t> ts_at;  // a committed timestamp offset -> its offset in the new table
-  uint64_t num_hashes = 0, num_ts = 0;
   for (size_t v = 0; v < n1; v++) {
     if (is_fresh(v)) continue;
     const size_t o = old_of_new[v];
     hash_duration[v] = videos_[o].hash_duration;
     for (size_t r = 0; r < R; r++) {
       const size_t row = v * R + r, orow = o * R + r;
-      const uint32_t len = seqs_[orow].len;
-      seqs[row] = NeedleHipSeq{(uint32_t)num_hashes, len};
-      if (len) hash_rows.push_back(IndexSegment{seqs_[orow].offset, num_hashes, len});
-      num_hashes += len;
-      min_len[row] = min_len_[orow];
-      row_ok[row] = row_ok_[orow];
+      const uint32_t len = rows_.seqs[orow].len;
+      rows.seqs[row] = NeedleHipSeq{(uint32_t)rows.hashes, len};
+      if (len) hash_rows.push_back(IndexSegment{rows_.seqs[orow].offset, rows.hashes, len});
+      rows.hashes += len;
+      rows.min_len[row] = rows_.min_len[orow];
+      rows.row_ok[row] = rows_.row_ok[orow];
       row_len[row] = len;
       if (len == 0) continue;  // (row_ts 0: never read)
-      auto it = ts_at.find(row_ts_[orow]);
+      auto it = ts_at.find(rows_.row_ts[orow]);
       if (it != ts_at.end()) {
-        row_ts[row] = it->second;
+        rows.row_ts[row] = it->second;
       } else {
-        ts_at.emplace(row_ts_[orow], (uint32_t)num_ts);
-        ts_rows.push_back(IndexSegment{row_ts_[orow], num_ts, len});
-        row_ts[row] = (uint32_t)num_ts;
-        num_ts += len;
+        ts_at.emplace(rows_.row_ts[orow], (uint32_t)rows.ts);
+        ts_rows.push_back(IndexSegment{rows_.row_ts[orow], rows.ts, len});
+        rows.row_ts[row] = (uint32_t)rows.ts;
+        rows.ts += len;
       }
     }
   }
   for (size_t v = 0; v < n1; v++) {
     if (!is_fresh(v)) continue;
     hash_duration[v] = fresh[v]->hash_duration;
-    for (size_t r = 0; r < R; r++) {
-      const size_t row = v * R + r;
-      const std::vector<HashTs> &seq = row_seq(v, r);
-      if (num_hashes + seq.size() > UINT32_MAX)
-        return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
-      seqs[row] = NeedleHipSeq{(uint32_t)num_hashes, (uint32_t)seq.size()};
-      num_hashes += seq.size();
-      for (const HashTs &h : seq) hashes.push_back(h.hash);
-      min_len[row] = cmp_.min_run_length_for(seq, r == 0);
-      row_len[row] = (uint32_t)seq.size();
-      const std::vector<HashTs> &first = row_seq(0, r);
-      bool same = v > 0 && seq.size() == first.size();
-      for (size_t q = 0; q < seq.size() && same; q++) same = seq[q].ts == first[q].ts;
-      if (same) {
-        row_ts[row] = row_ts[r];
-      } else {
-        row_ts[row] = (uint32_t)num_ts;
-        for (const HashTs &h : seq) ts.push_back(h.ts);
-        num_ts += seq.size();
-        if (num_ts > UINT32_MAX) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 timestamps");
-      }
-      bool ok = seq.size() < 65536u;
-      for (size_t q = 1; q < seq.size() && ok; q++) ok = seq[q].ts > seq[q - 1].ts;
-      row_ok[row] = ok;
+    for (size_t at = v * R; at < (v + 1) * R; at++) {
+      Status s = fresh_row(cmp_, row_seq(v, at % R), v > 0 ? &row_seq(0, at % R) : nullptr, R, at, &rows, &hashes, &ts);
+      if (!s.ok()) return s;
+      row_len[at] = rows.seqs[at].len;
     }
   }
-  bool large_ok = true;
-  for (uint8_t ok : row_ok) large_ok = large_ok && ok;
+  for (uint8_t ok : rows.row_ok) rows.large_ok = rows.large_ok && ok;
   // the pairs with a fresh video, each once (two fresh videos: under the later one), listed; their problems as in add
   std::vector<uint32_t> pair_ids;
   std::vector<NeedleHipProblem> problems;
   uint64_t searched = 0;
   auto list_pair = [&](size_t i, size_t j) {
-    const uint64_t l = pair_ids.size();
+    searched += pair_problems(rows.min_len, R, i, j, (uint64_t)pair_ids.size() * R, &problems);
     pair_ids.push_back((uint32_t)((uint64_t)j * (j - 1) / 2 + i));
-    bool any = false;
-    for (size_t r = 0; r < R; r++) {
-      const uint32_t a = min_len[i * R + r], b = min_len[j * R + r];
-      if (a == 0 || b == 0) continue;
-      problems.push_back(NeedleHipProblem{(uint32_t)(i * R + r), (uint32_t)(j * R + r), std::max(a, b), (uint32_t)(l * R + r)});
-      any = true;
-    }
-    searched += any;
   };
   for (size_t f = 0; f < n1; f++) {
     if (!is_fresh(f)) continue;
@@ -359,13 +339,7 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   IndexEdit e;
   e.n_old = (uint32_t)n0;
   e.n_new = (uint32_t)n1;
-  e.regions = (uint32_t)R;
-  e.threshold = cmp_.hash_match_threshold();
-  e.include_endings = include_endings_;
-  e.large_ok = large_ok;
-  e.min_opening_duration = cmp_.min_opening_duration();
-  e.min_ending_duration = cmp_.min_ending_duration();
-  e.time_padding = cmp_.time_padding();
+  set_options(cmp_, R, rows.large_ok, &e);
   e.old_of_new = old_of_new.data();
   e.new_of_old = new_of_old.data();
   e.gone = gone.data();
@@ -376,13 +350,13 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   e.num_ts_rows = ts_rows.size();
   e.hashes = hashes.data();
   e.num_hashes = hashes.size();
-  e.total_hashes = num_hashes;
+  e.total_hashes = rows.hashes;
   e.ts = ts.data();
   e.num_ts = ts.size();
-  e.total_ts = num_ts;
-  e.seqs = seqs.data();
+  e.total_ts = rows.ts;
+  e.seqs = rows.seqs.data();
   e.row_len = row_len.data();
-  e.row_ts = row_ts.data();
+  e.row_ts = rows.row_ts.data();
   e.hash_duration = hash_duration.data();
   e.problems = problems.data();
   e.num_problems = problems.size();
@@ -391,16 +365,9 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   IndexAppendOut out;
   Status s = gpu_index_edit(store_, e, &out);
   if (!s.ok()) return s;
-  if (out.failed & kEpilogueBucketTooLarge) {
-    note_epilogue_host_fallback("Index::replace", out.runs.size(), n1);
-    std::vector<uint32_t> start, valid;
-    std::vector<IndexEntry> entries;
-    host_entries(cmp_, R, (uint64_t)pair_ids.size() * R, out.runs,
-                 [&](uint64_t l, size_t *i, size_t *j) { column_pair(pair_ids[l], i, j); }, row_seq, video, &start, &valid, &entries);
-    if (!(s = gpu_index_edit_host_entries(store_, e, start, valid, entries, &out)).ok()) return s;
-  }
-  if (out.failed)  // best_match_kernel: the winner's end minus padding / hash duration underflows (the reference panics)
-    return Status::Make(NeedleError_Unknown, "overflow when subtracting durations (time_padding / hash_duration exceed the match end)");
+  s = settle(cmp_, "Index::replace", R, n1, (uint64_t)pair_ids.size() * R, [&](uint64_t l, size_t *i, size_t *j) { column_pair(pair_ids[l], i, j); },
+             row_seq, video, [&](const auto &...computed) { return gpu_index_edit_host_entries(store_, e, computed..., &out); }, out);
+  if (!s.ok()) return s;
   // commit: nothing above changed the index
   index_store_switch(store_, e, out.held);
   std::vector<FrameHashesData> videos;
@@ -417,13 +384,7 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   for (size_t q = 0; q < out.videos.size(); q++) results[out.videos[q]] = out.results[q];
   videos_.swap(videos);
   results_.swap(results);
-  seqs_.swap(seqs);
-  min_len_.swap(min_len);
-  row_ts_.swap(row_ts);
-  row_ok_.swap(row_ok);
-  hashes_ = num_hashes;
-  ts_ = num_ts;
-  large_ok_ = large_ok;
+  rows_ = std::move(rows);
   pairs_last_ = searched;
   pairs_total_ += searched;
   return Status::Ok();

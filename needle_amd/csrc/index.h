@@ -9,6 +9,16 @@ namespace needle {
 
 struct IndexStore;
 
+struct IndexRows {  // per row (video * regions + region), and the sizes of the device tables the rows point into
+  std::vector<NeedleHipSeq> seqs;        // its hashes in the device arena
+  std::vector<uint32_t> min_len;         // the shortest run that can pass the duration test (0: none)
+  std::vector<uint32_t> row_ts;          // offset of its timestamps in the store's table
+  std::vector<uint8_t> row_ok;           // under 65 536 hashes, timestamps strictly increasing ...
+  bool large_ok = true;                  // ... and every row is
+  uint64_t hashes = 0, ts = 0;           // sizes of the device arena and timestamp table
+  explicit IndexRows(size_t rows = 0) : seqs(rows), min_len(rows), row_ts(rows), row_ok(rows) {}
+};
+
 // Results equal Comparator::run_with_frame_hashes over the index's current list: the videos added, in insertion order, less
 // those removed, with replacements in place.  The index runs on
 // the device that was current when it was created; one GPU only (no sharding across ranks).
@@ -38,12 +48,7 @@ class Index {
   uint32_t regions_;
   IndexStore *store_ = nullptr;
   std::vector<FrameHashesData> videos_;
-  std::vector<NeedleHipSeq> seqs_;        // per row: its hashes in the device arena
-  std::vector<uint32_t> min_len_;         // per row: the shortest run that can pass the duration test (0: none)
-  std::vector<uint32_t> row_ts_;          // per row: offset of its timestamps in the store's table
-  uint64_t hashes_ = 0, ts_ = 0;          // sizes of the device arena and timestamp table
-  bool large_ok_ = true;                  // every row under 65 536 hashes, timestamps strictly increasing
-  std::vector<uint8_t> row_ok_;           // per row: that row's part of large_ok_
+  IndexRows rows_;
   std::vector<NeedleHipSearchResult> results_;
   uint64_t pairs_total_ = 0, pairs_last_ = 0;
 

@@ -1,0 +1,627 @@
+// The device store of the incremental index (index.cpp says why keeping every pair's entries is enough): the heap entries
+// of every pair searched so far and the tables that go with them, resident in HBM; an append searches the new pairs and
+// adds theirs behind, an edit (removal / replacement) rebuilds the store under the new pair ids into a second set of
+// tables.  The entries come from the library job's pipeline (epilogue_kernels.h) under the store's pair numberings.
+// Nothing committed is written before index_store_commit / index_store_switch: an operation that fails leaves the store
+// as it was.  tests: test_gpu_index.py, test_gpu_index_edit.py.
+#include <mutex>
+#include <string>
+
+#include "epilogue_kernels.h"
+#include "index_store.h"
+
+namespace needle {
+
+namespace {
+
+// The append's buckets into the store: start = where the entries were written (the store's entry count before the append plus
+// the bucket's start in the append's counting sort), valid = the heap's size.
+__global__ __launch_bounds__(256) void index_store_buckets_kernel(uint32_t buckets, const uint32_t *__restrict__ local_start,
+                                                                  const uint32_t *__restrict__ local_valid, uint32_t entries_base,
+                                                                  uint32_t *__restrict__ store_start, uint32_t *__restrict__ store_valid) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < buckets; b += gridDim.x * blockDim.x) {
+    store_start[b] = entries_base + local_start[b];
+    store_valid[b] = local_valid[b];
+  }
+}
+
+// The videos whose candidate list an append changed: an old video i with an entry in a new pair (i, j).  `valid` = the new
+// buckets' counts in the store, `first` = the append's first pair id.
+__global__ __launch_bounds__(256) void index_changed_kernel(uint32_t buckets, uint32_t regions, uint64_t first,
+                                                            const uint32_t *__restrict__ valid, uint32_t *__restrict__ flag) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < buckets; b += gridDim.x * blockDim.x) {
+    if (valid[b] == 0) continue;
+    uint32_t i, j;
+    column_pair_at(first + b / regions, &i, &j);
+    flag[i] = 1u;
+  }
+}
+// ... listed, with every new video [n0, n1) (its result is computed even when it has no candidate: then it is "none")
+__global__ __launch_bounds__(256) void index_list_kernel(uint32_t n0, uint32_t n1, const uint32_t *__restrict__ flag,
+                                                         uint32_t *__restrict__ count, uint32_t *__restrict__ list) {
+  for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n1; v += gridDim.x * blockDim.x)
+    if (v >= n0 || flag[v]) list[atomicAdd(count, 1u)] = v;
+}
+
+// ---- an index edit (removal / replacement): the store rebuilt under the new pair ids into the second set of buffers ----
+// The kept rows of the hash arena or of the timestamp table into the new one: a workgroup per row, consecutive elements.
+template <class T>
+__global__ __launch_bounds__(256) void index_copy_rows_kernel(const IndexSegment *__restrict__ rows, uint32_t num_rows,
+                                                              const T *__restrict__ from, T *__restrict__ to) {
+  for (uint32_t s = blockIdx.x; s < num_rows; s += gridDim.x) {
+    const IndexSegment g = rows[s];
+    for (uint64_t k = threadIdx.x; k < g.len; k += blockDim.x) to[g.dst + k] = from[g.src + k];
+  }
+}
+
+// A bucket of the rebuilt store whose pair is kept: its count and where its entries lie in the committed store.  Removal keeps
+// the relative order, so the old pair is (old i, old j) with the same roles.  The pairs with a fresh video are left to
+// index_edit_fresh_kernel.
+__global__ __launch_bounds__(256) void index_edit_buckets_kernel(uint32_t buckets, uint32_t regions, const uint32_t *__restrict__ old_of_new,
+                                                                 const uint32_t *__restrict__ old_start, const uint32_t *__restrict__ old_valid,
+                                                                 uint32_t *__restrict__ src, uint32_t *__restrict__ count) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < buckets; b += gridDim.x * blockDim.x) {
+    uint32_t i, j;
+    column_pair_at(b / regions, &i, &j);
+    const uint32_t oi = old_of_new[i], oj = old_of_new[j];
+    if (oi == kIndexFresh || oj == kIndexFresh) continue;
+    const uint64_t ob = (column_start(oj) + oi) * regions + b % regions;
+    src[b] = old_start[ob];
+    count[b] = old_valid[ob];
+  }
+}
+// ... and a listed pair's bucket: its entries were written behind the committed ones (`base`) by this edit
+__global__ __launch_bounds__(256) void index_edit_fresh_kernel(uint32_t listed, uint32_t regions, const uint32_t *__restrict__ pair_ids,
+                                                               const uint32_t *__restrict__ lstart, const uint32_t *__restrict__ lvalid,
+                                                               uint32_t base, uint32_t *__restrict__ src, uint32_t *__restrict__ count) {
+  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < listed; l += gridDim.x * blockDim.x) {
+    const uint64_t b = (uint64_t)pair_ids[l / regions] * regions + l % regions;
+    src[b] = base + lstart[l];
+    count[b] = lvalid[l];
+  }
+}
+
+// Every bucket's valid entries to its new start (start[0..buckets], start[buckets] = the total), so that the slots in use are
+// the entries held.  A lane per 16-byte word (an entry is three): consecutive lanes move consecutive words; a lane finds its
+// bucket by a binary search of the starts, the last one at or below its entry (empty buckets share their start).
+__global__ __launch_bounds__(256) void index_gather_kernel(uint32_t buckets, const uint32_t *__restrict__ start,
+                                                           const uint32_t *__restrict__ src, const uint4 *__restrict__ from,
+                                                           uint4 *__restrict__ to, uint64_t max_entries) {
+  const uint64_t words = 3 * min((uint64_t)start[buckets], max_entries);
+  for (uint64_t w = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; w < words; w += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t e = (uint32_t)(w / 3);
+    uint32_t lo = 0, hi = buckets;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) / 2;
+      if (start[mid] <= e) lo = mid;
+      else hi = mid;
+    }
+    to[w] = from[((uint64_t)src[lo] + (e - start[lo])) * 3 + w % 3];
+  }
+}
+
+// The videos whose candidate list an edit changed: every fresh video ...
+__global__ __launch_bounds__(256) void index_fresh_flags_kernel(uint32_t n, const uint32_t *__restrict__ old_of_new, uint32_t *__restrict__ flag) {
+  for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) flag[v] = old_of_new[v] == kIndexFresh ? 1u : 0u;
+}
+// ... every kept video with an entry in a pair of a video removed or replaced (the committed store, old ids) ...
+__global__ __launch_bounds__(256) void index_gone_partners_kernel(uint32_t n_old, uint32_t regions, const uint32_t *__restrict__ gone,
+                                                                  uint32_t num_gone, const uint32_t *__restrict__ valid,
+                                                                  const uint32_t *__restrict__ new_of_old, uint32_t *__restrict__ flag) {
+  const uint64_t total = (uint64_t)num_gone * n_old;
+  for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t x = gone[t / n_old], q = (uint32_t)(t % n_old);
+    if (q == x || new_of_old[q] == kIndexFresh) continue;
+    const uint64_t p = q < x ? column_start(x) + q : column_start(q) + x;
+    bool any = false;
+    for (uint32_t r = 0; r < regions; r++) any = any || valid[p * regions + r] != 0;
+    if (any) flag[new_of_old[q]] = 1u;
+  }
+}
+// ... and every video with an entry in a listed pair
+__global__ __launch_bounds__(256) void index_fresh_partners_kernel(uint32_t listed, uint32_t regions, const uint32_t *__restrict__ pair_ids,
+                                                                   const uint32_t *__restrict__ lvalid, uint32_t *__restrict__ flag) {
+  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < listed; l += gridDim.x * blockDim.x) {
+    if (lvalid[l] == 0) continue;
+    uint32_t i, j;
+    column_pair_at(pair_ids[l / regions], &i, &j);
+    flag[i] = 1u;
+    flag[j] = 1u;
+  }
+}
+
+// A device array that keeps its contents when it grows (amortised doubling, a device-to-device copy on `stream`).
+template <class T>
+struct GrowBuffer {
+  DeviceBuffer<T> buf;
+  Status reserve(size_t n, size_t keep, hipStream_t stream) {
+    if (n <= buf.count) return Status::Ok();
+    const size_t want = std::max<size_t>(n, 2 * buf.count);
+    T *p = nullptr;
+    NEEDLE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T)));
+    if (keep && buf.ptr) {
+      const hipError_t e = hipMemcpyAsync(p, buf.ptr, keep * sizeof(T), hipMemcpyDeviceToDevice, stream);
+      const hipError_t w = e == hipSuccess ? hipStreamSynchronize(stream) : e;  // (the old buffer is released below)
+      if (w != hipSuccess) {
+        (void)hipFree(p);
+        return Status::Make(NeedleError_Unknown, std::string("HIP error: ") + hipGetErrorString(w) + " growing an index buffer");
+      }
+    }
+    buf.release();
+    buf.ptr = p;
+    buf.count = want;
+    return Status::Ok();
+  }
+  T *ptr() const { return buf.ptr; }
+};
+
+// Every resident table of the store.  The store holds two sets: the current one, and the one an edit gathers the rebuilt
+// store into.
+struct StoreTables {
+  GrowBuffer<DeviceEntry> entry;  // the per-pair entries and, per bucket b = p(i, j) * regions + r, where they start and how many
+  GrowBuffer<uint32_t> start, valid, row_len, row_ts, hash;
+  GrowBuffer<uint64_t> row_seek, ts_table, hash_duration;
+};
+
+struct PinnedHead {  // what an operation reads back, in pinned memory: followed by list[n] and results[n]
+  uint32_t found, failed, listed, held;
+};
+static_assert(sizeof(PinnedHead) == 16 && offsetof(PinnedHead, held) == 12, "four words before the list");
+
+}  // namespace
+
+struct IndexStore {
+  // committed: what the index holds (an append that fails leaves these, and what lies below them, as they were)
+  uint32_t n = 0;
+  uint64_t buckets = 0, entries = 0, rows = 0, ts = 0, hashes = 0;
+  StoreTables tables[2];
+  StoreTables *cur = &tables[0], *next = &tables[1];  // (index_store_switch swaps the two)
+  DeviceBuffer<uint32_t> src, old_of_new, new_of_old, gone, pair_ids;  // an edit's maps
+  DeviceBuffer<IndexSegment> segments;
+  // an operation's scratch
+  EntriesScratch scratch;  // over the new (an append) or the listed (an edit) pairs' buckets
+  DeviceBuffer<EpilogueControl> ctl;
+  DeviceBuffer<uint32_t> flag, list, links, run_count;
+  DeviceBuffer<NeedleHipRun> runs;
+  DeviceBuffer<Candidate> cand;
+  DeviceBuffer<NeedleHipSearchResult> results;
+  PinnedHead *pinned = nullptr;
+  size_t pinned_bytes = 0;
+  uint32_t capacity = 1u << 16;  // of the run list; grows to what an append found
+  bool used = false;  // an append has enqueued work (a store made without a device never has)
+  int device = 0;
+  ~IndexStore() {
+    if (pinned) (void)hipHostFree(pinned);
+  }
+};
+
+IndexStore *index_store_new() {
+  IndexStore *st = new IndexStore();
+  (void)hipGetDevice(&st->device);
+  return st;
+}
+void index_store_free(IndexStore *st) {
+  if (!st) return;
+  if (!st->used) {
+    delete st;
+    return;
+  }
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const int own = st->device;
+  if (dev != own) (void)hipSetDevice(own);
+  (void)hipStreamSynchronize(library_stream());  // (no launch of this append may still read the buffers)
+  delete st;
+  if (dev != own) (void)hipSetDevice(dev);
+}
+
+namespace {
+
+uint64_t append_first_pair(const IndexAppend &a) { return (uint64_t)a.n0 * (a.n0 - (a.n0 ? 1 : 0)) / 2; }
+uint64_t append_buckets(const IndexAppend &a) { return ((uint64_t)a.n1 * (a.n1 - 1) / 2 - append_first_pair(a)) * a.regions; }
+uint64_t edit_buckets(const IndexEdit &e) { return (uint64_t)e.n_new * (e.n_new ? e.n_new - 1 : 0) / 2 * e.regions; }
+
+template <class T>
+hipError_t upload(T *dst, const T *src, size_t count, hipStream_t stream) {  // (pageable source: staged before the call returns)
+  return count ? hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, stream) : hipSuccess;
+}
+
+Status index_check_device(const IndexStore *st) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev != st->device) return Status::Make(NeedleError_InvalidArgument, "index: the current device is not the one the index was created on");
+  return Status::Ok();
+}
+
+// how an append and an edit begin
+Status index_enter(IndexStore *st) {
+  Status s = ensure_device();
+  if (!s.ok() || !(s = index_check_device(st)).ok()) return s;
+  st->used = true;
+  return Status::Ok();
+}
+
+// An operation's device work, which needs a capacity for the run list of its scan: enqueue(capacity, entry slots) is
+// given the store's, and once more the exact one if the scan found more.  Sizes what both operations use: the results
+// of up to `n` videos, the pipeline's scratch over `scratch_buckets` buckets, room for `capacity` new entries behind the
+// committed ones.  With kEpilogueBucketTooLarge, out->runs is the run list, for the host (index.cpp).
+template <class Enqueue>
+Status index_run(IndexStore *st, const char *what, size_t num_problems, uint64_t scratch_buckets, uint32_t n, hipStream_t stream,
+                 IndexAppendOut *out, Enqueue enqueue) {
+  Status s;
+  if (!(s = st->ctl.reserve(1)).ok() || !(s = st->run_count.reserve(1)).ok() || !(s = st->flag.reserve(n)).ok() ||
+      !(s = st->list.reserve(n)).ok() || !(s = st->results.reserve(n)).ok())
+    return s;
+  const size_t pinned_want = sizeof(PinnedHead) + ((size_t)n + 2) * sizeof(uint32_t) + (size_t)n * sizeof(NeedleHipSearchResult);
+  if (pinned_want > st->pinned_bytes) {
+    if (st->pinned) (void)hipHostFree(st->pinned);
+    st->pinned = nullptr;
+    st->pinned_bytes = 0;
+    NEEDLE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st->pinned), 2 * pinned_want, hipHostMallocDefault));
+    st->pinned_bytes = 2 * pinned_want;
+  }
+  st->capacity = (uint32_t)std::min<uint64_t>(0x7fffffffu, std::max<uint64_t>(st->capacity, 3 * (uint64_t)num_problems));
+  for (int attempt = 0; attempt < 2; attempt++) {
+    const uint32_t capacity = st->capacity;
+    const uint64_t entries1 = st->entries + capacity;  // the committed slots and this operation's
+    if (entries1 >= 0xFFFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 heap entries");
+    const uint64_t cand = 2 * entries1;  // every entry is a candidate of its two videos
+    if (!(s = st->cur->entry.reserve(entries1, st->entries, stream)).ok() || !(s = st->runs.reserve(capacity)).ok() ||
+        !(s = st->scratch.reserve(scratch_buckets, capacity)).ok() || !(s = st->cand.reserve(cand)).ok() ||
+        !(s = st->links.reserve(cand)).ok() || !(s = enqueue(capacity, entries1)).ok())
+      return s;
+    if (out->found <= capacity) {
+      out->runs.clear();
+      if ((out->failed & kEpilogueBucketTooLarge) && out->found) {
+        out->runs.resize(out->found);
+        NEEDLE_HIP_TRY(hipMemcpy(out->runs.data(), st->runs.ptr, (size_t)out->found * sizeof(NeedleHipRun), hipMemcpyDeviceToHost));
+      }
+      return Status::Ok();
+    }
+    st->capacity = out->found;  // the scan is deterministic: a second pass with the exact size fits
+  }
+  return Status::Make(NeedleError_Unknown, std::string(what) + ": run list did not fit after resize");
+}
+
+// The scan's run list (st->runs, st->run_count) sorted by bucket into the scratch.
+Status index_sort_runs(IndexStore *st, uint32_t buckets, uint32_t capacity, hipStream_t stream) {
+  RunSegments segs;
+  std::memset(&segs, 0, sizeof(segs));
+  segs.count = 1;
+  segs.found[0] = st->run_count.ptr;
+  segs.runs[0] = st->runs.ptr;
+  segs.capacity[0] = capacity;
+  return enqueue_bucket_sort("index_buckets", segs, buckets, capacity, &st->scratch, stream);
+}
+
+// The operation's buckets' entries from the sorted runs, behind the committed entries (part of the store once the append is
+// committed or the edit has gathered them), with the row tables `t`.  Inside the caller's timer.
+template <class Pairs, class... Extra>
+Status index_entries(IndexStore *st, const EpilogueParams &pr, const StoreTables &t, hipStream_t stream, Extra... extra) {
+  return enqueue_pair_entries<Pairs, Extra...>(st->device, pr, st->scratch, t.row_len.ptr(), t.row_ts.ptr(), t.row_seek.ptr(), t.ts_table.ptr(),
+                                              st->cur->entry.ptr() + st->entries, st->ctl.ptr, stream, extra...);
+}
+
+// Inside the caller's "index_best_match" timer, behind the kernels that flag the videos whose candidate list changed: those
+// and every video from `from` on listed, and best_match over the list in the tables `t`.
+void enqueue_list_and_match(IndexStore *st, const EpilogueParams &pr, uint32_t from, const StoreTables &t, hipStream_t stream) {
+  EpilogueControl *ctl = st->ctl.ptr;
+  hipLaunchKernelGGL(index_list_kernel, dim3((pr.n + 255) / 256), dim3(256), 0, stream, from, pr.n, st->flag.ptr, &ctl->listed, st->list.ptr);
+  // one workgroup per video at most; those beyond the list's length return at once
+  hipLaunchKernelGGL((best_match_kernel<IndexVideos, const uint32_t *, const uint32_t *, const uint64_t *>), dim3(pr.n), dim3(256), 0, stream, pr,
+                     t.start.ptr(), t.valid.ptr(), t.entry.ptr(), st->cand.ptr, &ctl->cand_cursor, st->links.ptr, st->results.ptr, &ctl->failed,
+                     st->list.ptr, &ctl->listed, t.hash_duration.ptr());
+}
+
+// the runs found, the failure word, the listed videos' results (and `held`, an edit's entry count) into pinned memory; the wait
+Status index_copy_out(IndexStore *st, uint32_t n, const uint32_t *held, hipStream_t stream, IndexAppendOut *out) {
+  PinnedHead *head = st->pinned;
+  uint32_t *list = reinterpret_cast<uint32_t *>(head + 1);
+  NeedleHipSearchResult *results = reinterpret_cast<NeedleHipSearchResult *>(list + ((n + 1) & ~1u));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(&head->found, st->run_count.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(&head->failed, &st->ctl.ptr->failed, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(&head->listed, &st->ctl.ptr->listed, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  if (held) NEEDLE_HIP_TRY(hipMemcpyAsync(&head->held, held, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(list, st->list.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipMemcpyAsync(results, st->results.ptr, (size_t)n * sizeof(NeedleHipSearchResult), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  out->found = head->found;
+  out->failed = head->failed;
+  out->held = held ? head->held : 0;
+  const uint32_t listed = std::min(head->listed, n);
+  out->videos.assign(list, list + listed);
+  out->results.assign(results, results + listed);
+  return Status::Ok();
+}
+
+// The fallback, both operations': the buckets' entries as the host computed them behind the committed ones, their start /
+// valid tables to where the device's would be, the failure word cleared; then `rerun`, the operation's second half (the
+// scan's `found` is kept).
+template <class Rerun>
+Status index_host_entries(IndexStore *st, uint64_t buckets, const std::vector<uint32_t> &start, const std::vector<uint32_t> &valid,
+                          const std::vector<IndexEntry> &entries, uint32_t *d_start, uint32_t *d_valid, size_t room, const char *misfit,
+                          hipStream_t stream, IndexAppendOut *out, Rerun rerun) {
+  if (start.size() != buckets || valid.size() != buckets || st->entries + entries.size() > st->cur->entry.buf.count || buckets > room)
+    return Status::Make(NeedleError_InvalidArgument, misfit);
+  static_assert(sizeof(IndexEntry) == sizeof(DeviceEntry) && offsetof(IndexEntry, score) == offsetof(DeviceEntry, score) &&
+                    offsetof(IndexEntry, dst_hash) == offsetof(DeviceEntry, dst_hash),
+                "IndexEntry mirrors DeviceEntry");
+  NEEDLE_HIP_TRY(upload(st->cur->entry.ptr() + st->entries, reinterpret_cast<const DeviceEntry *>(entries.data()), entries.size(), stream));
+  NEEDLE_HIP_TRY(upload(d_start, start.data(), buckets, stream));
+  NEEDLE_HIP_TRY(upload(d_valid, valid.data(), buckets, stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(&st->ctl.ptr->failed, 0, sizeof(uint32_t), stream));
+  const uint32_t found = out->found;
+  Status s = rerun();
+  out->found = found;
+  return s;
+}
+
+// ---- an append ------------------------------------------------------------------------------------------------------------
+// mark the changed videos, list them, best_match over the list; then the copies into pinned memory and a wait for them
+Status index_best_and_copy(IndexStore *st, const IndexAppend &a, hipStream_t stream, IndexAppendOut *out) {
+  const uint64_t new_buckets = append_buckets(a);
+  const EpilogueParams pr = epilogue_params(a, a.large_ok, a.n1, new_buckets);
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->flag.ptr, 0, std::max<size_t>(a.n1, 1) * sizeof(uint32_t), stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(&st->ctl.ptr->cand_cursor, 0, sizeof(st->ctl.ptr->cand_cursor), stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(&st->ctl.ptr->listed, 0, sizeof(uint32_t), stream));
+  {
+    KernelTimer timer("index_best_match", stream);
+    if (new_buckets) {
+      const uint32_t grid = (uint32_t)std::min<uint64_t>(4096, (new_buckets + 255) / 256);
+      hipLaunchKernelGGL(index_changed_kernel, dim3(grid), dim3(256), 0, stream, (uint32_t)new_buckets, a.regions, append_first_pair(a),
+                         st->cur->valid.ptr() + st->buckets, st->flag.ptr);
+    }
+    enqueue_list_and_match(st, pr, a.n0, *st->cur, stream);
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  return index_copy_out(st, a.n1, nullptr, stream, out);
+}
+
+}  // namespace
+
+Status gpu_index_append(IndexStore *st, const IndexAppend &a, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = index_enter(st);
+  if (!s.ok()) return s;
+  if (a.n0 != st->n || a.n1 <= a.n0 || a.regions < 1 || a.regions > 2)
+    return Status::Make(NeedleError_InvalidArgument, "index append: inconsistent sizes");
+  hipStream_t stream = library_stream();
+  StoreTables &t = *st->cur;
+  const uint64_t new_buckets = append_buckets(a), buckets1 = st->buckets + new_buckets;
+  const uint64_t rows1 = st->rows + a.num_rows, ts1 = st->ts + a.num_ts, hashes1 = st->hashes + a.num_hashes;
+  if (buckets1 >= 0xFFFFFFF0ull || hashes1 > UINT32_MAX)
+    return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
+  // the resident tables: the new videos' rows, timestamps, hash durations and hashes go in behind the committed ones
+  if (!(s = t.hash.reserve(std::max<uint64_t>(hashes1, 1), st->hashes, stream)).ok() || !(s = t.row_len.reserve(rows1, st->rows, stream)).ok() ||
+      !(s = t.row_ts.reserve(rows1, st->rows, stream)).ok() || !(s = t.row_seek.reserve(rows1, st->rows, stream)).ok() ||
+      !(s = t.ts_table.reserve(std::max<uint64_t>(ts1, 1), st->ts, stream)).ok() || !(s = t.hash_duration.reserve(a.n1, st->n, stream)).ok() ||
+      !(s = t.start.reserve(std::max<uint64_t>(buckets1, 1), st->buckets, stream)).ok() ||
+      !(s = t.valid.reserve(std::max<uint64_t>(buckets1, 1), st->buckets, stream)).ok())
+    return s;
+  NEEDLE_HIP_TRY(upload(t.hash.ptr() + st->hashes, a.hashes, a.num_hashes, stream));
+  NEEDLE_HIP_TRY(upload(t.row_len.ptr() + st->rows, a.row_len, a.num_rows, stream));
+  NEEDLE_HIP_TRY(upload(t.row_ts.ptr() + st->rows, a.row_ts, a.num_rows, stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(t.row_seek.ptr() + st->rows, 0, a.num_rows * sizeof(uint64_t), stream));
+  NEEDLE_HIP_TRY(upload(t.ts_table.ptr() + st->ts, a.ts, a.num_ts, stream));
+  NEEDLE_HIP_TRY(upload(t.hash_duration.ptr() + st->n, a.hash_duration, a.n1 - a.n0, stream));
+  return index_run(st, "index append", a.num_problems, new_buckets, a.n1, stream, out, [&](uint32_t capacity, uint64_t) -> Status {
+    // the scan of the new pairs only (every form eligible), behind the uploads on the same stream
+    Status s = gpu_hamming_runs_device(t.hash.ptr(), a.seqs, a.num_seqs, a.problems, a.num_problems, a.threshold, st->runs.ptr, capacity,
+                                       st->run_count.ptr, false, false);
+    if (!s.ok()) return s;
+    NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr, 0, sizeof(EpilogueControl), stream));
+    if (new_buckets) {
+      const EpilogueParams pr = epilogue_params(a, a.large_ok, a.n1, new_buckets);
+      if (!(s = index_sort_runs(st, pr.buckets, capacity, stream)).ok()) return s;
+      {
+        KernelTimer timer("index_entries", stream);
+        if (!(s = index_entries<ColumnMajorPairs, uint64_t>(st, pr, t, stream, append_first_pair(a))).ok()) return s;
+        // into the store's tables: start = where the entries were written
+        hipLaunchKernelGGL(index_store_buckets_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (new_buckets + 255) / 256)), dim3(256), 0,
+                           stream, pr.buckets, st->scratch.start.ptr, st->scratch.valid.ptr, (uint32_t)st->entries, t.start.ptr() + st->buckets,
+                           t.valid.ptr() + st->buckets);
+      }
+      NEEDLE_HIP_TRY(hipGetLastError());
+    }
+    return index_best_and_copy(st, a, stream, out);
+  });
+}
+
+Status gpu_index_append_host_entries(IndexStore *st, const IndexAppend &a, const std::vector<uint32_t> &start,
+                                     const std::vector<uint32_t> &valid, const std::vector<IndexEntry> &entries, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  hipStream_t stream = library_stream();
+  std::vector<uint32_t> shifted(start);  // relative to the append's first entry -> the store's slots
+  for (uint32_t &x : shifted) x += (uint32_t)st->entries;
+  return index_host_entries(st, append_buckets(a), shifted, valid, entries, st->cur->start.ptr() + st->buckets, st->cur->valid.ptr() + st->buckets,
+                            st->cur->valid.buf.count - st->buckets, "index append: host entries do not fit the append", stream, out,
+                            [&] { return index_best_and_copy(st, a, stream, out); });
+}
+
+void index_store_commit(IndexStore *st, const IndexAppend &a, uint32_t found) {
+  st->buckets += append_buckets(a);
+  st->entries += found;
+  st->rows += a.num_rows;
+  st->ts += a.num_ts;
+  st->hashes += a.num_hashes;
+  st->n = a.n1;
+}
+
+// ---- an edit: removal / replacement --------------------------------------------------------------------------------------
+namespace {
+
+// The first half of an edit: the maps and the new rows' tables uploaded, the kept rows gathered into the second arena and
+// timestamp table, the fresh rows behind them; the scan of the listed pairs and their entries behind the committed ones.
+Status index_edit_tables(IndexStore *st, const IndexEdit &e, uint32_t capacity, hipStream_t stream) {
+  const StoreTables &cur = *st->cur, &next = *st->next;
+  const uint32_t R = e.regions;
+  const uint64_t rows = (uint64_t)e.n_new * R, listed = (uint64_t)e.num_pairs * R;
+  NEEDLE_HIP_TRY(upload(st->old_of_new.ptr, e.old_of_new, e.n_new, stream));
+  NEEDLE_HIP_TRY(upload(st->new_of_old.ptr, e.new_of_old, e.n_old, stream));
+  NEEDLE_HIP_TRY(upload(st->gone.ptr, e.gone, e.num_gone, stream));
+  NEEDLE_HIP_TRY(upload(st->pair_ids.ptr, e.pair_ids, e.num_pairs, stream));
+  NEEDLE_HIP_TRY(upload(st->segments.ptr, e.hash_rows, e.num_hash_rows, stream));
+  NEEDLE_HIP_TRY(upload(st->segments.ptr + e.num_hash_rows, e.ts_rows, e.num_ts_rows, stream));
+  NEEDLE_HIP_TRY(upload(next.hash.ptr() + (e.total_hashes - e.num_hashes), e.hashes, e.num_hashes, stream));
+  NEEDLE_HIP_TRY(upload(next.ts_table.ptr() + (e.total_ts - e.num_ts), e.ts, e.num_ts, stream));
+  NEEDLE_HIP_TRY(upload(next.row_len.ptr(), e.row_len, rows, stream));
+  NEEDLE_HIP_TRY(upload(next.row_ts.ptr(), e.row_ts, rows, stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(next.row_seek.ptr(), 0, rows * sizeof(uint64_t), stream));
+  NEEDLE_HIP_TRY(upload(next.hash_duration.ptr(), e.hash_duration, e.n_new, stream));
+  {
+    KernelTimer timer("index_copy_rows", stream);
+    if (e.num_hash_rows)
+      hipLaunchKernelGGL(index_copy_rows_kernel<uint32_t>, dim3((uint32_t)std::min<size_t>(e.num_hash_rows, 4096)), dim3(256), 0, stream,
+                         (const IndexSegment *)st->segments.ptr, (uint32_t)e.num_hash_rows, (const uint32_t *)cur.hash.ptr(), next.hash.ptr());
+    if (e.num_ts_rows)
+      hipLaunchKernelGGL(index_copy_rows_kernel<uint64_t>, dim3((uint32_t)std::min<size_t>(e.num_ts_rows, 4096)), dim3(256), 0, stream,
+                         (const IndexSegment *)(st->segments.ptr + e.num_hash_rows), (uint32_t)e.num_ts_rows,
+                         (const uint64_t *)cur.ts_table.ptr(), next.ts_table.ptr());
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr, 0, sizeof(EpilogueControl), stream));
+  if (!e.num_problems) {
+    NEEDLE_HIP_TRY(hipMemsetAsync(st->run_count.ptr, 0, sizeof(uint32_t), stream));
+  } else {
+    Status s = gpu_hamming_runs_device(next.hash.ptr(), e.seqs, rows, e.problems, e.num_problems, e.threshold, st->runs.ptr, capacity,
+                                       st->run_count.ptr, false, false);
+    if (!s.ok()) return s;
+  }
+  if (!listed) return Status::Ok();
+  const EpilogueParams pr = epilogue_params(e, e.large_ok, e.n_new, listed);
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->scratch.valid.ptr, 0, listed * sizeof(uint32_t), stream));  // (a bucket the device does not order: 0)
+  Status s = index_sort_runs(st, pr.buckets, capacity, stream);
+  if (!s.ok()) return s;
+  {
+    KernelTimer timer("index_entries", stream);
+    if (!(s = index_entries<ListedPairs, const uint32_t *>(st, pr, next, stream, st->pair_ids.ptr)).ok()) return s;
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  return Status::Ok();
+}
+
+// The second half: every bucket's count and source (kept pairs from the committed store, listed ones from this edit's
+// entries), their starts, the gather into the second entry buffer, the videos to recompute and their best match over the
+// rebuilt store; the copies and the wait.
+Status index_edit_rebuild(IndexStore *st, const IndexEdit &e, hipStream_t stream, IndexAppendOut *out) {
+  const StoreTables &cur = *st->cur, &next = *st->next;
+  const uint32_t R = e.regions, n = e.n_new;
+  const uint64_t buckets = edit_buckets(e), listed = (uint64_t)e.num_pairs * R;
+  {
+    KernelTimer timer("index_rebuild", stream);
+    if (buckets) {
+      hipLaunchKernelGGL(index_edit_buckets_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (buckets + 255) / 256)), dim3(256), 0, stream,
+                         (uint32_t)buckets, R, (const uint32_t *)st->old_of_new.ptr, (const uint32_t *)cur.start.ptr(),
+                         (const uint32_t *)cur.valid.ptr(), st->src.ptr, next.valid.ptr());
+      if (listed)
+        hipLaunchKernelGGL(index_edit_fresh_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (listed + 255) / 256)), dim3(256), 0, stream,
+                           (uint32_t)listed, R, (const uint32_t *)st->pair_ids.ptr, (const uint32_t *)st->scratch.start.ptr,
+                           (const uint32_t *)st->scratch.valid.ptr, (uint32_t)st->entries, st->src.ptr, next.valid.ptr());
+      enqueue_exclusive_scan(next.valid.ptr(), (uint32_t)buckets, st->scratch.sums.ptr, next.start.ptr(), stream);
+    } else {
+      NEEDLE_HIP_TRY(hipMemsetAsync(next.start.ptr(), 0, sizeof(uint32_t), stream));
+    }
+  }
+  if (buckets) {
+    KernelTimer timer("index_gather", stream);
+    const uint64_t max_entries = next.entry.buf.count;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(8192, (3 * max_entries + 255) / 256);
+    hipLaunchKernelGGL(index_gather_kernel, dim3(std::max(grid, 1u)), dim3(256), 0, stream, (uint32_t)buckets, (const uint32_t *)next.start.ptr(),
+                       (const uint32_t *)st->src.ptr, reinterpret_cast<const uint4 *>(cur.entry.ptr()),
+                       reinterpret_cast<uint4 *>(next.entry.ptr()), max_entries);
+  }
+  const EpilogueParams pr = epilogue_params(e, e.large_ok, n, buckets);
+  NEEDLE_HIP_TRY(hipMemsetAsync(&st->ctl.ptr->cand_cursor, 0, sizeof(st->ctl.ptr->cand_cursor), stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(&st->ctl.ptr->listed, 0, sizeof(uint32_t), stream));
+  {
+    KernelTimer timer("index_best_match", stream);
+    hipLaunchKernelGGL(index_fresh_flags_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, (const uint32_t *)st->old_of_new.ptr, st->flag.ptr);
+    if (e.num_gone && e.n_old > 1) {
+      const uint64_t work = (uint64_t)e.num_gone * e.n_old;
+      hipLaunchKernelGGL(index_gone_partners_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (work + 255) / 256)), dim3(256), 0, stream, e.n_old,
+                         R, (const uint32_t *)st->gone.ptr, (uint32_t)e.num_gone, (const uint32_t *)cur.valid.ptr(),
+                         (const uint32_t *)st->new_of_old.ptr, st->flag.ptr);
+    }
+    if (listed)
+      hipLaunchKernelGGL(index_fresh_partners_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (listed + 255) / 256)), dim3(256), 0, stream,
+                         (uint32_t)listed, R, (const uint32_t *)st->pair_ids.ptr, (const uint32_t *)st->scratch.valid.ptr, st->flag.ptr);
+    enqueue_list_and_match(st, pr, n, next, stream);
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  return index_copy_out(st, n, next.start.ptr() + buckets, stream, out);
+}
+
+}  // namespace
+
+Status gpu_index_edit(IndexStore *st, const IndexEdit &e, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = index_enter(st);
+  if (!s.ok()) return s;
+  if (e.n_old != st->n || e.n_new < 1 || e.regions < 1 || e.regions > 2)
+    return Status::Make(NeedleError_InvalidArgument, "index edit: inconsistent sizes");
+  hipStream_t stream = library_stream();
+  StoreTables &next = *st->next;
+  const uint64_t buckets = edit_buckets(e), listed = (uint64_t)e.num_pairs * e.regions, rows = (uint64_t)e.n_new * e.regions;
+  if (buckets >= 0xFFFFFFF0ull || e.total_hashes > UINT32_MAX || e.total_ts > UINT32_MAX)
+    return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
+  if (!(s = next.hash.reserve(std::max<uint64_t>(e.total_hashes, 1), 0, stream)).ok() ||
+      !(s = next.ts_table.reserve(std::max<uint64_t>(e.total_ts, 1), 0, stream)).ok() || !(s = next.row_len.reserve(rows, 0, stream)).ok() ||
+      !(s = next.row_ts.reserve(rows, 0, stream)).ok() || !(s = next.row_seek.reserve(rows, 0, stream)).ok() ||
+      !(s = next.hash_duration.reserve(e.n_new, 0, stream)).ok() || !(s = next.start.reserve(buckets + 1, 0, stream)).ok() ||
+      !(s = next.valid.reserve(std::max<uint64_t>(buckets, 1), 0, stream)).ok() || !(s = st->src.reserve(std::max<uint64_t>(buckets, 1))).ok() ||
+      !(s = st->old_of_new.reserve(e.n_new)).ok() || !(s = st->new_of_old.reserve(std::max<uint32_t>(e.n_old, 1))).ok() ||
+      !(s = st->gone.reserve(std::max<size_t>(e.num_gone, 1))).ok() || !(s = st->pair_ids.reserve(std::max<size_t>(e.num_pairs, 1))).ok() ||
+      !(s = st->segments.reserve(std::max<size_t>(e.num_hash_rows + e.num_ts_rows, 1))).ok() ||
+      !(s = st->scratch.sums.reserve(EntriesScratch::sums_for(buckets))).ok())  // (the rebuilt store's scan; the listed buckets' is index_run's)
+    return s;
+  // the rebuilt store holds at most the committed slots and this edit's
+  return index_run(st, "index edit", e.num_problems, listed, e.n_new, stream, out, [&](uint32_t capacity, uint64_t entries1) -> Status {
+    Status s = next.entry.reserve(entries1, 0, stream);
+    if (!s.ok() || !(s = index_edit_tables(st, e, capacity, stream)).ok()) return s;
+    return index_edit_rebuild(st, e, stream, out);
+  });
+}
+
+Status gpu_index_edit_host_entries(IndexStore *st, const IndexEdit &e, const std::vector<uint32_t> &start, const std::vector<uint32_t> &valid,
+                                   const std::vector<IndexEntry> &entries, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  hipStream_t stream = library_stream();
+  return index_host_entries(st, (uint64_t)e.num_pairs * e.regions, start, valid, entries, st->scratch.start.ptr, st->scratch.valid.ptr,
+                            st->scratch.valid.count, "index edit: host entries do not fit the edit", stream, out,
+                            [&] { return index_edit_rebuild(st, e, stream, out); });
+}
+
+void index_store_switch(IndexStore *st, const IndexEdit &e, uint32_t held) {
+  std::swap(st->cur, st->next);
+  st->n = e.n_new;
+  st->buckets = edit_buckets(e);
+  st->entries = held;
+  st->rows = (uint64_t)e.n_new * e.regions;
+  st->ts = e.total_ts;
+  st->hashes = e.total_hashes;
+}
+
+void index_store_clear(IndexStore *st) {
+  st->n = 0;
+  st->buckets = st->entries = st->rows = st->ts = st->hashes = 0;
+}
+
+Status index_store_sizes(IndexStore *st, uint64_t sizes[4]) {
+  sizes[0] = 0;
+  sizes[1] = st->entries;
+  sizes[2] = st->hashes;
+  sizes[3] = st->ts;
+  if (!st->buckets) return Status::Ok();
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = index_check_device(st);
+  if (!s.ok()) return s;
+  std::vector<uint32_t> valid(st->buckets);
+  hipStream_t stream = library_stream();
+  NEEDLE_HIP_TRY(hipMemcpyAsync(valid.data(), st->cur->valid.ptr(), valid.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  for (uint32_t v : valid) sizes[0] += v;
+  return Status::Ok();
+}
+
+}  // namespace needle

@@ -1,4 +1,4 @@
-"""-m gpu: the incremental index (needle_hip_index_*, csrc/index.cpp + the store in csrc/epilogue.hip) against the oracle.
+"""-m gpu: the incremental index (needle_hip_index_*, csrc/index.cpp + the store in csrc/index_store.hip) against the oracle.
 After every append the index's results must equal, to the nanosecond, oracle.run_with_frame_hashes over ALL videos added so
 far in insertion order -- and capi.Comparator.run_with_frame_hashes over the same list -- while the scan saw only the new
 pairs.  What can go wrong is ORDER (a video's candidates: its old pairs, then its pairs with the new videos), which videos'
