@@ -50,7 +50,8 @@ enum NeedleError needle_hip_host_alloc_free(void *host_ptr);
 /* GPU timing of the most recent COMPLETED launch of a kernel (it never waits behind queued work unless no
  * launch has finished yet), measured with HIP events on the
  * library's own stream (rocprofv3 sees the same kernels).  Names: "stft_chroma", "fir_norm",
- * "classify", "hamming_runs", "simhash_runs", "resample".  Returns milliseconds, <0 if unknown or not timed. */
+ * "classify", "hamming_runs", "simhash_runs", "resample", "downmix", "convert".  Returns milliseconds, <0 if unknown or
+ * not timed. */
 double needle_hip_last_kernel_ms(const char *kernel);
 /* Selects the kernels that get those events: "all", a comma-separated list of names, or NULL / "" / "none".
  * Default: none (each event record is one more packet between dependent dispatches: timing all five kernels of
@@ -168,6 +169,35 @@ enum NeedleError needle_hip_resample_host(const int16_t *const *pcm, const size_
 enum NeedleError needle_hip_downmix_host(const int16_t *const *pcm, const size_t *num_values, size_t num_streams,
                                          int channels, int16_t *const *out);
 
+/* ---- sample formats: PCM as a decoder hands it over, converted to s16 on the device -------------------
+ * The values follow FFmpeg's AVSampleFormat numbering, so a caller can pass frame->format through.  Interleaved
+ * formats take one pointer per stream; planar ones take one pointer per CHANNEL: the pointer array then has
+ * num_streams * channels entries and pcm[i * channels + c] is plane c of stream i, holding num_values[i] / channels
+ * samples.  num_values[i] counts samples over all channels (frames x channels) whatever their width; a trailing
+ * partial frame is dropped.  Pointers need only the alignment of one sample.  Conversion of one sample to s16 (the WAV
+ * reader's arithmetic, so a WAV file and its raw samples give the same hashes):
+ *   U8 : (x - 128) << 8        S16: x        S32: x >> 16 (arithmetic shift)
+ *   F32: rint(x * 32768.0f) in f32, ties to even; NaN gives 0; otherwise clipped to [-32768, 32767]
+ *   F64: the same in f64 (it never passes through f32)
+ * Everything behind the conversion is the s16 path on the converted values: every result equals, bit for bit, what the
+ * s16 entry point gives for the host-converted, interleaved samples.  Any other value: NeedleError_InvalidArgument. */
+enum NeedleHipSampleFormat {
+  NEEDLE_HIP_SAMPLE_U8 = 0,
+  NEEDLE_HIP_SAMPLE_S16 = 1, /* what every entry point without a format takes, and the default everywhere */
+  NEEDLE_HIP_SAMPLE_S32 = 2,
+  NEEDLE_HIP_SAMPLE_F32 = 3,
+  NEEDLE_HIP_SAMPLE_F64 = 4,
+  NEEDLE_HIP_SAMPLE_U8P = 5, /* planar: one plane per channel */
+  NEEDLE_HIP_SAMPLE_S16P = 6,
+  NEEDLE_HIP_SAMPLE_S32P = 7,
+  NEEDLE_HIP_SAMPLE_F32P = 8,
+  NEEDLE_HIP_SAMPLE_F64P = 9
+};
+/* The conversion on its own: out[i] receives interleaved `channels`-channel s16, num_values[i] / channels * channels
+ * values, NOT down-mixed (the analyze paths fuse the down-mix of 3-8 channels into the same kernel). */
+enum NeedleError needle_hip_convert_host(const void *const *pcm, const size_t *num_values, size_t num_streams,
+                                         int channels, int format, int16_t *const *out);
+
 /* ---- search: the LCS-Hamming DP replacement -------------------------------------------------------
  * Replaces Comparator::longest_common_hash_match's two table sweeps (comparator.rs:175-247).  For a
  * problem (src, dst, min_len) it reports every maximal diagonal run of cells (i >= 1, j >= 1) with
@@ -235,6 +265,13 @@ enum NeedleError needle_hip_header_md5(const char *path, char out[33]);         
 enum NeedleError needle_hip_analyzer_run_pcm(struct NeedleAudioAnalyzer *analyzer, const int16_t *const *pcm,
                                              const size_t *num_values, int channels, int sample_rate,
                                              float hash_duration, bool persist);
+/* The same with the samples in `format` (enum NeedleHipSampleFormat; planar: analyzer videos * channels pointers): they
+ * are uploaded as they are and converted on the device, group by group under the uploads, in front of the down-mix
+ * (fused into the conversion), the resampler and the fingerprinter.  With NEEDLE_HIP_SAMPLE_S16 this is
+ * needle_hip_analyzer_run_pcm. */
+enum NeedleError needle_hip_analyzer_run_pcm_format(struct NeedleAudioAnalyzer *analyzer, const void *const *pcm,
+                                                    const size_t *num_values, int channels, int sample_rate, int format,
+                                                    float hash_duration, bool persist);
 
 /* ---- Comparator in memory ------------------------------------------------------------------------- */
 typedef struct NeedleHipSearchResult {
@@ -316,6 +353,14 @@ enum NeedleError needle_hip_library_include_endings(NeedleHipLibrary *library, f
  * on the way in: the resident PCM, and so every job's cost, is that of a mono 11025 Hz library.  The hashes equal
  * needle_hip_analyzer_run_pcm's at that rate.  At 11025 nothing is resampled. */
 enum NeedleError needle_hip_library_set_sample_rate(NeedleHipLibrary *library, int sample_rate);
+/* The sample format (enum NeedleHipSampleFormat, default NEEDLE_HIP_SAMPLE_S16) of the PCM that set_pcm, set_pcm_device
+ * and stream_pcm will be given.  Call after library_new and before set_pcm (InvalidArgument afterwards, the library
+ * unchanged).  Those three calls then read their pointer arrays in that format -- callers cast; for a planar format the
+ * array has num_videos * channels entries, all planes of a video this rank does not own NULL (a mix of NULL and
+ * non-NULL planes: NullArgument) -- and convert on the device on the way in: set_pcm stages the raw windows through a
+ * device buffer of at most 2 GiB, set_pcm_device converts straight out of the caller's buffers.  The resident PCM is
+ * what the s16 library would hold, so jobs, audit, frame_hashes and rank_videos do not depend on the format. */
+enum NeedleError needle_hip_library_set_sample_format(NeedleHipLibrary *library, int format);
 size_t needle_hip_library_rows_per_video(const NeedleHipLibrary *library);
 /* Lengths (values per stream, all videos) are metadata every rank holds; pcm[i] may be NULL for
  * videos this rank does not own.  Crops to the opening window and uploads.  `channels` = 1..NEEDLE_HIP_MAX_CHANNELS in

@@ -101,7 +101,45 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_scan_counts", "needle_hip_scan_last_launch", "needle_hip_epilogue_host_fallbacks",
     "needle_hip_index_new", "needle_hip_index_free", "needle_hip_index_len", "needle_hip_index_add",
     "needle_hip_index_results", "needle_hip_index_pairs_searched", "needle_hip_index_remove", "needle_hip_index_replace",
-    "needle_hip_index_store_sizes"]
+    "needle_hip_index_store_sizes",
+    "needle_hip_convert_host", "needle_hip_analyzer_run_pcm_format", "needle_hip_library_set_sample_format"]
+
+# enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
+SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
+SAMPLE_U8P, SAMPLE_S16P, SAMPLE_S32P, SAMPLE_F32P, SAMPLE_F64P = 5, 6, 7, 8, 9
+_SAMPLE_DTYPES = [np.uint8, np.int16, np.int32, np.float32, np.float64]
+
+
+def sample_format_dtype(sample_format: int):
+    """numpy dtype of one sample of `sample_format`."""
+    if not 0 <= sample_format <= 9:
+        raise ValueError(f"unknown sample format {sample_format}")
+    return np.dtype(_SAMPLE_DTYPES[sample_format % 5])
+
+
+def sample_format_planar(sample_format: int) -> bool:
+    return sample_format >= SAMPLE_U8P
+
+
+def _format_pointers(pcm, channels: int, sample_format: int):
+    """(arrays to keep alive, flat pointer list) of streams in `sample_format`: an interleaved stream is one array, a
+    planar one a sequence of `channels` planes (or a 2-D array [channels][frames]); None stays NULL (all planes)."""
+    dtype = sample_format_dtype(sample_format)
+    keep, ptrs = [], []
+    for p in pcm:
+        if not sample_format_planar(sample_format):
+            a = None if p is None else np.ascontiguousarray(p, dtype=dtype)
+            keep.append(a)
+            ptrs.append(None if a is None else a.ctypes.data)
+        elif p is None:
+            ptrs += [None] * channels
+        else:
+            planes = [np.ascontiguousarray(q, dtype=dtype) for q in p]
+            if len(planes) != channels:
+                raise ValueError(f"a planar stream needs {channels} planes, got {len(planes)}")
+            keep += planes
+            ptrs += [q.ctypes.data for q in planes]
+    return keep, ptrs
 
 _LIB = None
 
@@ -164,6 +202,7 @@ def lib():
     L.needle_hip_resample_out_len.restype = sz
     L.needle_hip_resample_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, C.c_int, C.c_int, C.POINTER(vp)]
     L.needle_hip_downmix_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, C.c_int, C.POINTER(vp)]
+    L.needle_hip_convert_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, C.c_int, C.c_int, C.POINTER(vp)]
     L.needle_hip_hamming_runs_device.argtypes = [vp, C.POINTER(Seq), sz, C.POINTER(Problem), sz, u32, vp, u32, vp, b]
     L.needle_hip_hamming_runs_host.argtypes = [vp, sz, C.POINTER(Seq), sz, C.POINTER(Problem), sz, u32,
                                                C.POINTER(C.POINTER(Run)), C.POINTER(sz)]
@@ -181,6 +220,7 @@ def lib():
     L.needle_hip_frame_hashes_write.argtypes = [vp, C.c_char_p]
     L.needle_hip_header_md5.argtypes = [C.c_char_p, C.c_char_p]
     L.needle_hip_analyzer_run_pcm.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.c_int, C.c_int, f32, b]
+    L.needle_hip_analyzer_run_pcm_format.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.c_int, C.c_int, C.c_int, f32, b]
     L.needle_hip_comparator_run_with_frame_hashes.argtypes = [vp, C.POINTER(vp), sz, b, b, b,
                                                               C.POINTER(CSearchResult)]
     L.needle_hip_comparator_results_from_runs.argtypes = [vp, C.POINTER(vp), sz, vp, sz, sz, sz,
@@ -190,6 +230,7 @@ def lib():
     L.needle_hip_library_free.restype = None
     L.needle_hip_library_include_endings.argtypes = [vp, f32]
     L.needle_hip_library_set_sample_rate.argtypes = [vp, C.c_int]
+    L.needle_hip_library_set_sample_format.argtypes = [vp, C.c_int]
     L.needle_hip_library_rows_per_video.argtypes = [vp]
     L.needle_hip_library_rows_per_video.restype = sz
     L.needle_hip_library_set_pcm.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.c_int]
@@ -478,9 +519,23 @@ class Analyzer:
         return self._collect()
 
     def run_pcm(self, pcm: Sequence[np.ndarray], channels: int = 1, sample_rate: int = 11025,
-                hash_duration: float = DEFAULT_HASH_DURATION, persist: bool = False) -> List[FrameHashes]:
-        """Same with decode already done: pcm[i] is the whole stream of video i (interleaved s16)."""
+                hash_duration: float = DEFAULT_HASH_DURATION, persist: bool = False,
+                sample_format: int = SAMPLE_S16) -> List[FrameHashes]:
+        """Same with decode already done: pcm[i] is the whole stream of video i (interleaved s16).  With another
+        `sample_format` (SAMPLE_*) the samples go to the device as they are and are converted there
+        (needle_hip_analyzer_run_pcm_format); a planar stream is a sequence of `channels` planes; num_values counts
+        samples over all channels."""
         h = self._handle()
+        if sample_format != SAMPLE_S16:
+            keep, flat = _format_pointers(pcm, channels, sample_format)
+            planar = sample_format_planar(sample_format)
+            sizes = [sum(q.size for q in p) if planar else np.size(p) for p in pcm]
+            ptrs = (C.c_void_p * max(len(flat), 1))(*flat)
+            lens = (C.c_size_t * max(len(sizes), 1))(*sizes)
+            check(lib().needle_hip_analyzer_run_pcm_format(h, ptrs, lens, channels, sample_rate, sample_format,
+                                                           hash_duration, persist))
+            del keep
+            return self._collect()
         arrs = [np.ascontiguousarray(p, dtype=np.int16) for p in pcm]
         ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
         lens = (C.c_size_t * max(len(arrs), 1))(*[a.size for a in arrs])
@@ -689,6 +744,25 @@ def downmix(pcms: Sequence[np.ndarray], channels: int) -> List[np.ndarray]:
     return [o[:k] for o, k in zip(outs, lens_out)]
 
 
+def convert(pcms: Sequence, channels: int, sample_format: int, num_values: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+    """needle_hip_convert_host: streams in `sample_format` (SAMPLE_*; a planar stream is a sequence of `channels` planes)
+    -> interleaved `channels`-channel s16, not down-mixed; a trailing partial frame is dropped.  num_values (samples
+    over all channels per stream) defaults to the arrays' sizes."""
+    keep, flat = _format_pointers(pcms, channels, sample_format)
+    n = len(pcms)
+    planar = sample_format_planar(sample_format)
+    if num_values is None:
+        num_values = [sum(q.size for q in p) if planar else np.size(p) for p in pcms]
+    lens_out = [int(v) // max(channels, 1) * channels for v in num_values]
+    outs = [np.zeros(max(k, 1), dtype=np.int16) for k in lens_out]
+    ptrs = (C.c_void_p * max(len(flat), 1))(*flat)
+    lens = (C.c_size_t * max(n, 1))(*[int(v) for v in num_values])
+    optrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    check(lib().needle_hip_convert_host(ptrs, lens, n, channels, sample_format, optrs))
+    del keep
+    return [o[:k] for o, k in zip(outs, lens_out)]
+
+
 def hamming_runs(seqs: Sequence[np.ndarray], problems: Sequence[Tuple[int, int, int]], threshold: int) -> np.ndarray:
     """needle_hip_hamming_runs_host.  problems: (src_seq, dst_seq, min_len); returns a structured array of
     (problem, src_end, dst_end, len), problem = index into `problems`."""
@@ -792,6 +866,7 @@ class Library:
         check(lib().needle_hip_library_new(num_videos, opening_search_percentage, hash_duration, C.byref(out)))
         self._h = out
         self.n = num_videos
+        self._format = SAMPLE_S16
 
     def include_endings(self, ending_search_percentage: float = DEFAULT_ENDING_SEARCH_PERCENTAGE) -> "Library":
         check(lib().needle_hip_library_include_endings(self._h, ending_search_percentage))
@@ -803,12 +878,26 @@ class Library:
         check(lib().needle_hip_library_set_sample_rate(self._h, sample_rate))
         return self
 
+    def set_sample_format(self, sample_format: int) -> "Library":
+        """The sample format (SAMPLE_*) of the PCM set_pcm / set_pcm_device / stream_pcm will be given; converted to s16
+        on the device on the way in (needle_hip_library_set_sample_format).  set_pcm and stream_pcm then pass arrays of
+        that format's dtype; a planar video is a sequence of `channels` planes (set_pcm_device: channels pointers per video)."""
+        check(lib().needle_hip_library_set_sample_format(self._h, sample_format))
+        self._format = sample_format
+        return self
+
     def rows_per_video(self) -> int:
         return lib().needle_hip_library_rows_per_video(self._h)
 
+    def _host_pointers(self, pcm, channels: int):
+        if self._format == SAMPLE_S16:
+            arrs = [None if p is None else np.ascontiguousarray(p, dtype=np.int16) for p in pcm]
+            return arrs, (C.c_void_p * self.n)(*[None if a is None else a.ctypes.data for a in arrs])
+        keep, flat = _format_pointers(pcm, channels, self._format)
+        return keep, (C.c_void_p * max(len(flat), 1))(*flat)
+
     def set_pcm(self, pcm: Sequence[Optional[np.ndarray]], num_values: Sequence[int], channels: int = 1) -> None:
-        arrs = [None if p is None else np.ascontiguousarray(p, dtype=np.int16) for p in pcm]
-        ptrs = (C.c_void_p * self.n)(*[None if a is None else a.ctypes.data for a in arrs])
+        arrs, ptrs = self._host_pointers(pcm, channels)
         lens = (C.c_size_t * self.n)(*list(num_values))
         check(lib().needle_hip_library_set_pcm(self._h, ptrs, lens, channels))
 
@@ -823,15 +912,14 @@ class Library:
 
     def set_pcm_device(self, d_ptrs: Sequence[Optional[int]], num_values: Sequence[int], channels: int = 1) -> None:
         """PCM already in HBM: device pointers (None for videos of other ranks), copied device to device."""
-        ptrs = (C.c_void_p * self.n)(*[None if p is None else int(p) for p in d_ptrs])
+        ptrs = (C.c_void_p * max(len(d_ptrs), self.n))(*[None if p is None else int(p) for p in d_ptrs])
         lens = (C.c_size_t * self.n)(*list(num_values))
         lib().needle_hip_library_set_pcm_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int]
         check(lib().needle_hip_library_set_pcm_device(self._h, ptrs, lens, channels))
 
     def stream_pcm(self, pcm: Sequence[Optional[np.ndarray]], num_values: Sequence[int], channels: int = 1) -> None:
         """Upload + fingerprint overlapped, PCM not kept (needle_hip_library_stream_pcm)."""
-        arrs = [None if p is None else np.ascontiguousarray(p, dtype=np.int16) for p in pcm]
-        ptrs = (C.c_void_p * self.n)(*[None if a is None else a.ctypes.data for a in arrs])
+        arrs, ptrs = self._host_pointers(pcm, channels)
         lens = (C.c_size_t * self.n)(*list(num_values))
         check(lib().needle_hip_library_stream_pcm(self._h, ptrs, lens, channels))
 

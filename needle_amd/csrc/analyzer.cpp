@@ -43,27 +43,30 @@ Status Analyzer::windows(size_t total_samples, int sample_rate, float opening_pc
 // One video's search windows, already cut: what process_frames (:180-284) feeds chromaprint for the opening
 // and, with include_endings, for the ending.
 struct Analyzer::WindowPcm {
-  const int16_t *opening = nullptr, *ending = nullptr;  // interleaved s16
-  size_t opening_values = 0, ending_values = 0;
+  // samples in the call's format: one pointer if interleaved, one per channel if planar
+  const void *opening[NEEDLE_HIP_MAX_CHANNELS] = {}, *ending[NEEDLE_HIP_MAX_CHANNELS] = {};
+  size_t opening_values = 0, ending_values = 0;  // over all channels
   ns_t seek = 0;  // timestamp of the first ending sample (:390)
 };
 
-Status Analyzer::fingerprint_windows(const std::vector<WindowPcm> &win, int channels, int sample_rate, uint32_t step,
+Status Analyzer::fingerprint_windows(const std::vector<WindowPcm> &win, int channels, int sample_rate, int format, uint32_t step,
                                      ns_t hash_duration, std::vector<FrameHashesData> *out) const {
-  std::vector<const int16_t *> ptrs;
+  std::vector<const void *> ptrs;
   std::vector<size_t> lens;
+  const size_t planes = sample_format_planes(format, channels);
   for (const WindowPcm &w : win) {
-    ptrs.push_back(w.opening);
+    ptrs.insert(ptrs.end(), w.opening, w.opening + planes);
     lens.push_back(w.opening_values);
     if (include_endings_) {
-      ptrs.push_back(w.ending);
+      ptrs.insert(ptrs.end(), w.ending, w.ending + planes);
       lens.push_back(w.ending_values);
     }
   }
   std::vector<std::vector<uint32_t>> kept;
   // PCM at another rate than chromaprint's 11025 Hz goes through the device resampler (the reference
   // resamples with swresample first, :180-187); the windows are cut at the stream's own rate
-  Status s = gpu_fingerprint_host(ptrs, lens, channels, step, &kept, sample_rate);
+  // (samples in another format than s16 are converted on the device in front of that, convert.hip)
+  Status s = gpu_fingerprint_host_format(ptrs, lens, channels, format, step, &kept, sample_rate);
   if (!s.ok()) return s;
   out->assign(win.size(), {});
   const size_t per = include_endings_ ? 2 : 1;
@@ -79,9 +82,22 @@ Status Analyzer::fingerprint_windows(const std::vector<WindowPcm> &win, int chan
 
 Status Analyzer::run_pcm(const std::vector<PcmView> &pcm, int channels, int sample_rate, ns_t hash_duration,
                          bool persist, std::vector<FrameHashesData> *out) const {
+  std::vector<const void *> planes(pcm.size());
+  std::vector<size_t> num_values(pcm.size());
+  for (size_t i = 0; i < pcm.size(); i++) {
+    planes[i] = pcm[i].data;
+    num_values[i] = pcm[i].num_values;
+  }
+  return run_pcm_format(planes, num_values, channels, sample_rate, NEEDLE_HIP_SAMPLE_S16, hash_duration, persist, out);
+}
+
+Status Analyzer::run_pcm_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels,
+                                int sample_rate, int format, ns_t hash_duration, bool persist,
+                                std::vector<FrameHashesData> *out) const {
   if (videos_.empty())  // :431-433
     return Status::Make(NeedleError_Unknown, "no paths provided to analyzer");
-  if (pcm.size() != videos_.size())
+  if (!sample_format_valid(format)) return Status::Make(NeedleError_InvalidArgument, "unknown sample format");
+  if (num_values.size() != videos_.size())
     return Status::Make(NeedleError_InvalidArgument, "one PCM stream per video is required");
   if (sample_rate < 2000 || sample_rate > 768000)
     return Status::Make(NeedleError_InvalidArgument, "unsupported sample rate");
@@ -93,19 +109,24 @@ Status Analyzer::run_pcm(const std::vector<PcmView> &pcm, int channels, int samp
                         "hash duration is shorter than one chromaprint item (123 ms)");
 
   const size_t n = videos_.size();
+  const size_t planes = sample_format_planes(format, channels), width = sample_format_width(format);
+  if (pcm.size() != n * planes) return Status::Make(NeedleError_InvalidArgument, "one pointer per plane of every video is required");
   std::vector<WindowPcm> win(n);
   for (size_t i = 0; i < n; i++) {
-    const size_t total = pcm[i].num_values / (size_t)channels;
+    const size_t total = num_values[i] / (size_t)channels;
     size_t open_samples = 0, end_first = 0;
     Status s = windows(total, sample_rate, opening_search_percentage_, ending_search_percentage_, &open_samples,
                        &end_first, &win[i].seek);
     if (!s.ok()) return s;
-    win[i].opening = pcm[i].data;
+    for (size_t c = 0; c < planes; c++) {  // a plane holds one sample per frame, an interleaved stream `channels`
+      const uint8_t *plane = static_cast<const uint8_t *>(pcm[i * planes + c]);
+      win[i].opening[c] = plane;
+      win[i].ending[c] = plane ? plane + end_first * (planes == 1 ? (size_t)channels : 1) * width : nullptr;
+    }
     win[i].opening_values = open_samples * (size_t)channels;
-    win[i].ending = pcm[i].data + end_first * (size_t)channels;
     win[i].ending_values = (total - end_first) * (size_t)channels;
   }
-  Status s = fingerprint_windows(win, channels, sample_rate, step, hash_duration, out);
+  Status s = fingerprint_windows(win, channels, sample_rate, format, step, hash_duration, out);
   if (!s.ok()) return s;
   for (size_t i = 0; i < n; i++) {
     FrameHashesData &fh = (*out)[i];

@@ -601,6 +601,26 @@ enum NeedleError needle_hip_downmix_host(const int16_t *const *pcm, const size_t
   });
 }
 
+enum NeedleError needle_hip_convert_host(const void *const *pcm, const size_t *num_values, size_t num_streams, int channels,
+                                         int format, int16_t *const *out) {
+  if (!pcm || !num_values || !out) return NeedleError_NullArgument;
+  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS || !sample_format_valid(format)) return NeedleError_InvalidArgument;
+  return guarded([&]() -> NeedleError {
+    const size_t planes = sample_format_planes(format, channels);
+    std::vector<const void *> p(pcm, pcm + num_streams * planes);
+    std::vector<size_t> n(num_values, num_values + num_streams);
+    std::vector<int16_t *> o(out, out + num_streams);
+    for (size_t i = 0; i < num_streams; i++) {
+      if (n[i] < (size_t)channels) continue;  // no whole frame: nothing is read or written
+      if (!o[i]) return NeedleError_NullArgument;
+      for (size_t c = 0; c < planes; c++)
+        if (!p[i * planes + c]) return NeedleError_NullArgument;
+    }
+    Status s = gpu_convert_host(p, n, channels, format, o);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 // ============================================================================================================
 // search
 // ============================================================================================================
@@ -729,6 +749,32 @@ enum NeedleError needle_hip_analyzer_run_pcm(struct NeedleAudioAnalyzer *analyze
     }
     std::vector<FrameHashesData> out;
     Status s = analyzer->inner.run_pcm(views, channels, sample_rate, hd, persist, &out);
+    if (!s.ok()) return report(s);
+    analyzer->frame_hashes.clear();
+    for (FrameHashesData &d : out) analyzer->frame_hashes.push_back(FrameHashes{std::move(d)});
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_analyzer_run_pcm_format(struct NeedleAudioAnalyzer *analyzer, const void *const *pcm,
+                                                    const size_t *num_values, int channels, int sample_rate, int format,
+                                                    float hash_duration, bool persist) {
+  if (!analyzer || !pcm || !num_values) return NeedleError_NullArgument;
+  if (!(hash_duration > 0.0f)) return NeedleError_AnalyzerInvalidHashDuration;
+  if (!sample_format_valid(format)) return NeedleError_InvalidArgument;
+  return guarded([&]() -> NeedleError {
+    bool ok = true;
+    const ns_t hd = duration_from_secs_f32(hash_duration, &ok);
+    if (!ok) return NeedleError_AnalyzerInvalidHashDuration;
+    if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
+      return report(Status::Make(NeedleError_InvalidArgument, "channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS)));
+    const size_t n = analyzer->inner.videos().size(), planes = sample_format_planes(format, channels);
+    std::vector<const void *> p(pcm, pcm + n * planes);
+    std::vector<size_t> lens(num_values, num_values + n);
+    for (size_t i = 0; i < n * planes; i++)
+      if (!p[i] && lens[i / planes]) return NeedleError_NullArgument;
+    std::vector<FrameHashesData> out;
+    Status s = analyzer->inner.run_pcm_format(p, lens, channels, sample_rate, format, hd, persist, &out);
     if (!s.ok()) return report(s);
     analyzer->frame_hashes.clear();
     for (FrameHashesData &d : out) analyzer->frame_hashes.push_back(FrameHashes{std::move(d)});

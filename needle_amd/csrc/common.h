@@ -233,4 +233,41 @@ Status gpu_downmix_device(const std::vector<DownmixSpan> &spans, int channels, b
 Status gpu_downmix_host(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values, int channels,
                         const std::vector<int16_t *> &out);
 
+// ---- sample formats (convert.hip): NeedleHipSampleFormat -> s16, on the device ------------------------------
+inline bool sample_format_valid(int format) { return format >= NEEDLE_HIP_SAMPLE_U8 && format <= NEEDLE_HIP_SAMPLE_F64P; }
+inline bool sample_format_planar(int format) { return format >= NEEDLE_HIP_SAMPLE_U8P; }
+inline size_t sample_format_width(int format) {  // bytes per sample
+  constexpr size_t width[5] = {1, 2, 4, 4, 8};
+  return width[format % 5];
+}
+// pointers a caller passes per stream: one per channel when planar
+inline size_t sample_format_planes(int format, int channels) { return sample_format_planar(format) ? (size_t)channels : 1; }
+// s16 units (2 bytes) a plane -- or an interleaved stream -- of `samples` samples takes in a raw staging arena: every
+// plane starts 16-byte aligned there (the kernel's vector path)
+inline uint64_t sample_plane_units(uint64_t samples, size_t width) { return ((samples * width + 15) & ~(uint64_t)15) / 2; }
+struct ConvertSpan {
+  const void *src[NEEDLE_HIP_MAX_CHANNELS];  // device; planar: plane c (frames samples each), interleaved: src[0] (frames * C
+                                             // samples).  Aligned to one sample at least.
+  int16_t *dst;                              // device, a buffer of its own: frames * C interleaved values, or frames mono ones
+  uint64_t frames;
+};
+// One launch on the library stream for all spans; returns after enqueueing unless `sync`.  `mix` (3-8 channels): the
+// down-mix of downmix.hip fused in, mono out; otherwise interleaved `channels`-channel s16 out.
+Status gpu_convert_device(const std::vector<ConvertSpan> &spans, int channels, int format, bool mix, bool sync);
+// Raw samples of any width from host pointers: stream i (bytes[i] bytes) goes to d_raw + dev_off[i] (offsets in s16
+// units, multiples of 8); otherwise as gpu_upload_pcm.
+Status gpu_upload_raw(const std::vector<const void *> &src, const std::vector<size_t> &bytes, const std::vector<uint64_t> &dev_off,
+                      int16_t *d_raw, ::ihipStream_t *stream = nullptr, const StreamIssued &issued = nullptr);
+// gpu_fingerprint_host / gpu_fingerprint_streamed_device with the streams in `format` (fingerprint.hip): uploaded as
+// they are, converted on the device group by group under the uploads.  pcm: sample_format_planes() pointers per stream.
+Status gpu_fingerprint_host_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels,
+                                   int format, uint32_t step, std::vector<std::vector<uint32_t>> *items, int rate = kSampleRate);
+Status gpu_fingerprint_streamed_device_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values,
+                                              int channels, int format, uint32_t step, uint32_t *d_items,
+                                              const std::vector<uint64_t> &item_off, int rate = kSampleRate);
+// host arrays in and out (pcm: sample_format_planes() pointers per stream; out[i] holds num_values[i] / channels * channels
+// interleaved s16 values, not down-mixed), in batches of bounded device memory
+Status gpu_convert_host(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels, int format,
+                        const std::vector<int16_t *> &out);
+
 }  // namespace needle

@@ -53,6 +53,7 @@ struct NeedleHipLibrary {
   uint32_t step = 0;
   int channels = 1;            // of the resident PCM (1 whenever it was down-mixed or resampled on the way in)
   int rate = kSampleRate;      // of the callers' PCM (needle_hip_library_set_sample_rate); the resident PCM is 11025 Hz
+  int format = NEEDLE_HIP_SAMPLE_S16;  // of the callers' PCM (needle_hip_library_set_sample_format); the resident PCM is s16
   bool have_pcm = false;      // windows and arena are set up (set_pcm or stream_pcm)
   bool pcm_resident = false;  // set_pcm: the PCM stays in HBM and analyze can be repeated
   std::vector<Window> win;  // [video * regions() + region]
@@ -282,6 +283,14 @@ enum NeedleError needle_hip_library_set_sample_rate(NeedleHipLibrary *lib, int s
   return NeedleError_Ok;
 }
 
+enum NeedleError needle_hip_library_set_sample_format(NeedleHipLibrary *lib, int format) {
+  if (!lib) return NeedleError_NullArgument;
+  if (!sample_format_valid(format)) return NeedleError_InvalidArgument;
+  if (lib->have_pcm) return NeedleError_InvalidArgument;  // must precede set_pcm
+  lib->format = format;
+  return NeedleError_Ok;
+}
+
 }  // extern "C"
 
 namespace {
@@ -293,13 +302,20 @@ size_t resident_samples(size_t count, int rate) { return rate == kSampleRate ? c
 // into the device PCM arena (set_pcm); otherwise nothing of the PCM is kept (stream_pcm).  `len` is in the caller's
 // (interleaved) values at lib->rate; windows are cut at that rate (as Analyzer::run_pcm does).  3-8 channel PCM and PCM
 // at any rate other than 11025 Hz are kept resident as 11025 Hz mono (down-mixed and resampled on the way in), so
-// lib->channels and the windows' `values` describe the arena, not the input; `len` is the input's.
-Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values, int channels, bool resident,
-                    std::vector<const int16_t *> *src, std::vector<size_t> *len, std::vector<uint64_t> *dst,
+// lib->channels and the windows' `values` describe the arena, not the input; `len` is the input's.  The samples are in
+// lib->format: `pcm` holds one pointer per video, or -- planar -- one per channel of every video, and `src` gets as many
+// per window (anything but interleaved s16 is converted on the way in, 3-8 channels to mono by the same kernel).
+Status plan_windows(NeedleHipLibrary *lib, const void *const *pcm, const size_t *num_values, int channels, bool resident,
+                    std::vector<const void *> *src, std::vector<size_t> *len, std::vector<uint64_t> *dst,
                     std::vector<uint64_t> *rows_of_src, uint64_t *total_values) {
   Status s = ensure_device();
   if (!s.ok()) return s;
-  const bool resampled = lib->rate != kSampleRate;
+  const bool resampled = lib->rate != kSampleRate, converted = lib->format != NEEDLE_HIP_SAMPLE_S16;
+  const size_t planes = sample_format_planes(lib->format, channels), width = sample_format_width(lib->format);
+  for (size_t v = 0; v < lib->n; v++)  // a video is held with all its planes or with none
+    for (size_t c = 1; c < planes; c++)
+      if (!pcm[v * planes + c] != !pcm[v * planes])
+        return Status::Make(NeedleError_NullArgument, "video " + std::to_string(v) + " has NULL and non-NULL planes");
   lib->channels = channels > 2 || resampled ? 1 : channels;
   const size_t R = lib->regions();
   lib->win.assign(lib->rows(), Window{});
@@ -322,9 +338,9 @@ Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size
       w.kept = (uint32_t)num_kept(kept_samples, lib->step);
       w.seek = r == 0 ? 0 : seek;
       max_kept = std::max(max_kept, w.kept);
-      if (pcm[v] && resident) {
+      if (pcm[v * planes] && resident) {
         w.pcm_off = total;
-        total += channels > 2 || resampled ? (w.values + 7) & ~(uint64_t)7 : (w.values + 1) & ~(uint64_t)1;  // (down-mix: 16-byte stores)
+        total += channels > 2 || resampled || converted ? (w.values + 7) & ~(uint64_t)7 : (w.values + 1) & ~(uint64_t)1;  // (down-mix: 16-byte stores)
       }
     }
   }
@@ -350,8 +366,10 @@ Status plan_windows(NeedleHipLibrary *lib, const int16_t *const *pcm, const size
   for (size_t v = 0; v < lib->n; v++) {
     for (size_t r = 0; r < R; r++) {
       const Window &w = lib->win[v * R + r];
-      if (!pcm[v] || !w.values) continue;
-      src->push_back(pcm[v] + first_sample[v * R + r] * (size_t)channels);
+      if (!pcm[v * planes] || !w.values) continue;
+      for (size_t c = 0; c < planes; c++)  // a plane holds one sample per frame, an interleaved stream `channels`
+        src->push_back(static_cast<const uint8_t *>(pcm[v * planes + c]) +
+                       first_sample[v * R + r] * (planes == 1 ? (size_t)channels : 1) * width);
       len->push_back(source_samples[v * R + r] * (size_t)channels);
       if (dst) dst->push_back(w.pcm_off);
       if (rows_of_src) rows_of_src->push_back(v * R + r);
@@ -505,6 +523,126 @@ Status upload_resampled(NeedleHipLibrary *lib, const std::vector<const int16_t *
   }
   return flush();
 }
+
+std::vector<const int16_t *> as_s16(const std::vector<const void *> &src) {
+  std::vector<const int16_t *> out(src.size());
+  for (size_t i = 0; i < src.size(); i++) out[i] = static_cast<const int16_t *>(src[i]);
+  return out;
+}
+
+// set_pcm / set_pcm_device in another sample format than interleaved s16 (lib->format): the windows are converted on the
+// device (convert.hip; 3-8 channels with the down-mix fused in) into their places in the resident PCM or, at another
+// rate than 11025 Hz, into staging from which the resampler writes them there.  Host windows are staged raw, every plane
+// 16-byte aligned; device windows are read straight out of the caller's buffers.  The staging buffer is bounded in BYTES
+// (2 GiB; NEEDLE_HIP_MAX_BATCH_VALUES counts values, for tests): a window is cut into pieces of whole 16-frame groups or,
+// resampled, of whole output tiles with the input their taps read, as upload_resampled does.  `src` holds
+// sample_format_planes() pointers per window.  All in library-stream order; the caller synchronises.
+Status upload_converted(NeedleHipLibrary *lib, const std::vector<const void *> &src, const std::vector<size_t> &len,
+                        const std::vector<uint64_t> &dst, int channels, bool from_host, DeviceBuffer<int16_t> *stage) {
+  const int format = lib->format, rate = lib->rate;
+  const bool resampled = rate != kSampleRate, mix = channels > 2;
+  const int out_channels = mix ? 1 : channels;  // of the converted s16
+  const uint64_t C = (uint64_t)channels, OC = (uint64_t)out_channels, W = sample_format_width(format);
+  const size_t P = sample_format_planes(format, channels);
+  const uint64_t per_frame = P == 1 ? C : 1;  // samples of one plane per frame
+  ResampleTiling tl;
+  Status s = resampled ? resample_tiling(rate, out_channels, &tl) : Status::Ok();
+  if (!s.ok()) return s;
+  uint64_t limit = 1ull << 30, budget = ~0ull;  // staging in s16 units; frames per piece
+  bool count_values = false;
+  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) {  // tests
+    limit = (uint64_t)std::max(1ll, atoll(e));
+    count_values = true;
+  }
+  if (from_host || resampled)
+    budget = count_values ? limit / ((from_host ? C : 0) + (resampled ? OC : 0))
+                          : 2 * limit / ((from_host ? C * W : 0) + (resampled ? 2 * OC : 0));
+  auto staged = [&](uint64_t frames) {  // staging units one piece takes, every part 16-byte aligned
+    return (from_host ? P * sample_plane_units(frames * per_frame, W) : 0) + (resampled ? (frames * OC + 7) & ~(uint64_t)7 : 0);
+  };
+  struct Piece {
+    size_t i;
+    uint64_t t0, t1, p0, p1;
+  };
+  std::vector<Piece> pieces;
+  uint64_t total = 0, largest = 0;
+  for (size_t i = 0; i < len.size(); i++) {
+    const uint64_t frames = len[i] / C;
+    if (resampled) {
+      const uint64_t tile_in = tl.tile_outputs * (uint64_t)tl.M / (uint64_t)tl.L + 2 * (uint64_t)tl.half + 16;  // one tile's input at most
+      const uint64_t piece_tiles = std::max<uint64_t>(1, (std::max(budget, tile_in) - 2 * (uint64_t)tl.half - 16) * (uint64_t)tl.L /
+                                                             (tl.tile_outputs * (uint64_t)tl.M));
+      const uint64_t tiles = (resample_out_len(frames, rate) + tl.tile_outputs - 1) / tl.tile_outputs;
+      for (uint64_t t0 = 0; t0 < tiles; t0 += std::min(piece_tiles, tiles - t0)) {
+        Piece pc{i, t0, std::min(tiles, t0 + piece_tiles), 0, 0};
+        resample_piece(tl, frames, pc.t0, pc.t1, &pc.p0, &pc.p1);
+        pieces.push_back(pc);
+      }
+    } else {
+      const uint64_t piece_frames = std::max<uint64_t>(16, budget / 16 * 16);
+      for (uint64_t f = 0; f < frames; f += std::min(piece_frames, frames - f))
+        pieces.push_back(Piece{i, 0, 0, f, f + std::min(piece_frames, frames - f)});
+    }
+  }
+  for (const Piece &pc : pieces) {
+    total += staged(pc.p1 - pc.p0);
+    largest = std::max(largest, staged(pc.p1 - pc.p0));
+  }
+  const uint64_t cap = std::max(std::min(total, limit), largest) + 8;
+  if (total && !(s = stage->reserve(cap)).ok()) return s;
+  std::vector<const void *> up_src;
+  std::vector<size_t> up_bytes;
+  std::vector<uint64_t> up_off;
+  std::vector<ConvertSpan> convert;
+  std::vector<ResampleSpan> spans;
+  uint64_t used = 0;
+  auto flush = [&]() -> Status {  // the next group's copies follow these kernels in stream order
+    Status fs = up_src.empty() ? Status::Ok() : gpu_upload_raw(up_src, up_bytes, up_off, stage->ptr);
+    if (fs.ok() && !convert.empty()) fs = gpu_convert_device(convert, channels, format, mix, false);
+    if (fs.ok() && !spans.empty()) fs = gpu_resample_device(nullptr, spans, out_channels, rate, lib->d_pcm.ptr, false);
+    up_src.clear();
+    up_bytes.clear();
+    up_off.clear();
+    convert.clear();
+    spans.clear();
+    used = 0;
+    return fs;
+  };
+  for (const Piece &pc : pieces) {
+    const uint64_t n = pc.p1 - pc.p0;
+    if (n == 0) continue;
+    if (total && used + staged(n) > cap && !(s = flush()).ok()) return s;
+    ConvertSpan cv{};
+    cv.frames = n;
+    for (size_t c = 0; c < P; c++) {
+      const uint8_t *from = static_cast<const uint8_t *>(src[pc.i * P + c]) + pc.p0 * per_frame * W;  // the piece in the caller's buffer
+      if (from_host) {
+        up_src.push_back(from);
+        up_bytes.push_back(n * per_frame * W);
+        up_off.push_back(used);
+        cv.src[c] = stage->ptr + used;
+        used += sample_plane_units(n * per_frame, W);
+      } else {
+        cv.src[c] = from;
+      }
+    }
+    if (resampled) {
+      cv.dst = stage->ptr + used;
+      ResampleSpan sp{0, len[pc.i] / C, dst[pc.i]};
+      sp.src = cv.dst;
+      sp.t0 = pc.t0;
+      sp.t1 = pc.t1;
+      sp.p0 = pc.p0;
+      sp.p1 = pc.p1;
+      spans.push_back(sp);
+      used += (n * OC + 7) & ~(uint64_t)7;
+    } else {
+      cv.dst = lib->d_pcm.ptr + dst[pc.i] + pc.p0 * OC;
+    }
+    convert.push_back(cv);
+  }
+  return flush();
+}
 }  // namespace
 
 extern "C" {
@@ -514,17 +652,19 @@ enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t
   if (!lib || !pcm || !num_values) return NeedleError_NullArgument;
   if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
-    std::vector<const int16_t *> src;
+    std::vector<const void *> planes;
     std::vector<size_t> len;
     std::vector<uint64_t> dst;
     uint64_t total = 0;
-    Status s = plan_windows(lib, pcm, num_values, channels, true, &src, &len, &dst, nullptr, &total);
+    Status s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
-    DeviceBuffer<int16_t> stage;  // (3-8 channels or another rate; freed after the drain below)
-    s = lib->rate != kSampleRate ? upload_resampled(lib, src, len, dst, channels, true, &stage)
-        : channels > 2           ? upload_mixed(lib, src, len, dst, channels, &stage)
-                                 : gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
+    DeviceBuffer<int16_t> stage;  // (3-8 channels, another rate or another sample format; freed after the drain below)
+    const std::vector<const int16_t *> src = as_s16(planes);
+    s = lib->format != NEEDLE_HIP_SAMPLE_S16 ? upload_converted(lib, planes, len, dst, channels, true, &stage)
+        : lib->rate != kSampleRate           ? upload_resampled(lib, src, len, dst, channels, true, &stage)
+        : channels > 2                       ? upload_mixed(lib, src, len, dst, channels, &stage)
+                                             : gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
     // also on the error path: copies already enqueued read the caller's buffers asynchronously
     const bool drained = hipStreamSynchronize(library_stream()) == hipSuccess;
     if (!s.ok()) return report(s);
@@ -540,16 +680,22 @@ enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const 
   if (!lib || !d_pcm || !num_values) return NeedleError_NullArgument;
   if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
-    std::vector<const int16_t *> src;
+    std::vector<const void *> planes;
     std::vector<size_t> len;
     std::vector<uint64_t> dst;
     uint64_t total = 0;
-    Status s = plan_windows(lib, d_pcm, num_values, channels, true, &src, &len, &dst, nullptr, &total);
+    Status s = plan_windows(lib, reinterpret_cast<const void *const *>(d_pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
     hipStream_t stream = library_stream();
     DeviceBuffer<int16_t> stage;  // (3-8 channels at another rate; freed after the drain below)
-    if (lib->rate != kSampleRate) {  // resampled out of the caller's buffers (3-8 channels: down-mixed into staging first)
+    const std::vector<const int16_t *> src = as_s16(planes);
+    if (lib->format != NEEDLE_HIP_SAMPLE_S16) {  // converted (down-mixed, resampled) straight out of the caller's buffers
+      s = upload_converted(lib, planes, len, dst, channels, false, &stage);
+      const bool drained = hipStreamSynchronize(stream) == hipSuccess;
+      if (!s.ok()) return report(s);
+      if (!drained) return report(Status::Make(NeedleError_Unknown, "PCM conversion failed"));
+    } else if (lib->rate != kSampleRate) {  // resampled out of the caller's buffers (3-8 channels: down-mixed into staging first)
       s = upload_resampled(lib, src, len, dst, channels, false, &stage);
       const bool drained = hipStreamSynchronize(stream) == hipSuccess;
       if (!s.ok()) return report(s);
@@ -575,15 +721,19 @@ enum NeedleError needle_hip_library_stream_pcm(NeedleHipLibrary *lib, const int1
   if (!lib || !pcm || !num_values) return NeedleError_NullArgument;
   if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
-    std::vector<const int16_t *> src;
+    std::vector<const void *> planes;
     std::vector<size_t> len;
     std::vector<uint64_t> rows;
     const auto t0 = std::chrono::steady_clock::now();
-    Status s = plan_windows(lib, pcm, num_values, channels, false, &src, &len, nullptr, &rows, nullptr);
+    Status s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, false, &planes, &len, nullptr, &rows, nullptr);
     if (!s.ok()) return report(s);
     for (uint64_t &r : rows) r *= lib->stride;  // kept items of a window go straight to its arena row
     const auto t1 = std::chrono::steady_clock::now();
-    if (!(s = gpu_fingerprint_streamed_device(src, len, channels, lib->step, lib->arena, rows, lib->rate)).ok()) return report(s);
+    const std::vector<const int16_t *> src = as_s16(planes);
+    s = lib->format != NEEDLE_HIP_SAMPLE_S16
+            ? gpu_fingerprint_streamed_device_format(planes, len, channels, lib->format, lib->step, lib->arena, rows, lib->rate)
+            : gpu_fingerprint_streamed_device(src, len, channels, lib->step, lib->arena, rows, lib->rate);
+    if (!s.ok()) return report(s);
     if (getenv("NEEDLE_HIP_TRACE"))
       std::fprintf(stderr, "[needle_hip] stream_pcm: windows planned in %.2f ms, %zu windows streamed in %.2f ms\n",
                    std::chrono::duration<double, std::milli>(t1 - t0).count(), src.size(),

@@ -50,6 +50,10 @@ class Analyzer {
   // Same, with FFmpeg's half of process_frames (:180-284) done by the caller.
   Status run_pcm(const std::vector<PcmView> &pcm, int channels, int sample_rate, ns_t hash_duration,
                  bool persist, std::vector<FrameHashesData> *out) const;
+  // Same with the samples in `format` (NeedleHipSampleFormat), converted on the device: `pcm` holds one pointer per
+  // video, or -- planar -- one per channel of every video.  With NEEDLE_HIP_SAMPLE_S16 this is run_pcm.
+  Status run_pcm_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels,
+                        int sample_rate, int format, ns_t hash_duration, bool persist, std::vector<FrameHashesData> *out) const;
 
   // Window arithmetic at the PCM boundary (DESIGN.md "PCM boundary"): samples per channel of the
   // opening window and first sample / seek offset of the ending window (:378,390).
@@ -59,7 +63,7 @@ class Analyzer {
  private:
   friend class Comparator;
   struct WindowPcm;
-  Status fingerprint_windows(const std::vector<WindowPcm> &win, int channels, int sample_rate, uint32_t step,
+  Status fingerprint_windows(const std::vector<WindowPcm> &win, int channels, int sample_rate, int format, uint32_t step,
                              ns_t hash_duration, std::vector<FrameHashesData> *out) const;
   std::vector<std::string> videos_;
   float opening_search_percentage_ = DEFAULT_OPENING_SEARCH_PERCENTAGE;

@@ -153,6 +153,19 @@ extern "C" {
         hash_duration: f32,
         persist: bool,
     ) -> NeedleError;
+    /// `needle_hip_analyzer_run_pcm` with the samples in `format` (`NeedleHipSampleFormat`, FFmpeg's `AVSampleFormat`
+    /// numbering: 0-4 u8 / s16 / s32 / f32 / f64 interleaved, 5-9 the same planar with videos x channels pointers),
+    /// converted to s16 on the device.
+    pub fn needle_hip_analyzer_run_pcm_format(
+        analyzer: *mut NeedleAudioAnalyzer,
+        pcm: *const *const c_void,
+        num_values: *const usize,
+        channels: c_int,
+        sample_rate: c_int,
+        format: c_int,
+        hash_duration: f32,
+        persist: bool,
+    ) -> NeedleError;
     pub fn needle_hip_comparator_run_with_frame_hashes(
         comparator: *const NeedleAudioComparator,
         frame_hashes: *const *const FrameHashes,
@@ -226,6 +239,18 @@ extern "C" {
         channels: c_int,
         out: *const *mut i16,
     ) -> NeedleError;
+    /// The conversion on its own: `out[i]` receives interleaved `channels`-channel s16 (`num_values[i] / channels * channels`
+    /// values), not down-mixed.
+    pub fn needle_hip_convert_host(
+        pcm: *const *const c_void,
+        num_values: *const usize,
+        num_streams: usize,
+        channels: c_int,
+        format: c_int,
+        out: *const *mut i16,
+    ) -> NeedleError;
+    /// The sample format of the PCM `set_pcm`, `set_pcm_device` and `stream_pcm` will be given (callers cast their pointers).
+    pub fn needle_hip_library_set_sample_format(library: *mut NeedleHipLibrary, format: c_int) -> NeedleError;
     pub fn needle_hip_library_include_endings(library: *mut NeedleHipLibrary, ending_search_percentage: f32) -> NeedleError;
     pub fn needle_hip_library_set_sample_rate(library: *mut NeedleHipLibrary, sample_rate: c_int) -> NeedleError;
     pub fn needle_hip_library_set_pcm(

@@ -273,6 +273,41 @@ impl<P: AsRef<Path>> Analyzer<P> {
         unsafe { ffi::needle_audio_analyzer_free(handle) };
         result
     }
+
+    /// `run_pcm` with the samples as the decoder hands them over (u8 / i16 / i32 / f32 / f64), converted on the device
+    /// (`needle_hip_analyzer_run_pcm_format`).  `planar`: `pcm` holds `channels` planes per video, one after the other;
+    /// otherwise one interleaved slice per video.
+    pub fn run_pcm_format<T: Sample>(
+        &self,
+        pcm: &[&[T]],
+        planar: bool,
+        channels: i32,
+        sample_rate: i32,
+        hash_duration: Duration,
+        persist: bool,
+    ) -> Result<Vec<FrameHashes>> {
+        let planes = if planar { channels.max(1) as usize } else { 1 };
+        assert_eq!(pcm.len(), self.videos.len() * planes, "one slice per plane of every video");
+        let ptrs: Vec<*const std::os::raw::c_void> = pcm.iter().map(|s| s.as_ptr() as *const _).collect();
+        let lens: Vec<usize> = pcm.chunks(planes).map(|s| s.iter().map(|p| p.len()).sum()).collect();
+        let format = if planar { T::PLANAR } else { T::INTERLEAVED };
+        let handle = self.handle()?;
+        let result = unsafe {
+            check(ffi::needle_hip_analyzer_run_pcm_format(
+                handle,
+                ptrs.as_ptr(),
+                lens.as_ptr(),
+                channels,
+                sample_rate,
+                format as i32,
+                hash_duration.as_secs_f32(),
+                persist,
+            ))
+        }
+        .and_then(|_| self.collect(handle));
+        unsafe { ffi::needle_audio_analyzer_free(handle) };
+        result
+    }
 }
 
 /// comparator.rs:65-69.  The reference keeps the fields private; accessors are an extension.
@@ -536,6 +571,68 @@ pub fn downmix(pcm: &[&[i16]], channels: i32) -> Result<Vec<Vec<i16>>> {
     Ok(out)
 }
 
+/// `NeedleHipSampleFormat`: how a decoder hands samples over (FFmpeg's `AVSampleFormat` numbering, so `frame.format` can
+/// be passed through).  The planar forms take one slice per channel.
+#[repr(i32)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum SampleFormat {
+    U8 = 0,
+    S16 = 1,
+    S32 = 2,
+    F32 = 3,
+    F64 = 4,
+    U8P = 5,
+    S16P = 6,
+    S32P = 7,
+    F32P = 8,
+    F64P = 9,
+}
+
+/// A sample type the device converts to s16 (`needle_hip.h`, "sample formats"): u8 `(x - 128) << 8`, i32 `x >> 16`,
+/// f32 / f64 `rint(x * 32768)` with NaN -> 0 and clipping.
+pub trait Sample: Copy {
+    const INTERLEAVED: SampleFormat;
+    const PLANAR: SampleFormat;
+}
+impl Sample for u8 {
+    const INTERLEAVED: SampleFormat = SampleFormat::U8;
+    const PLANAR: SampleFormat = SampleFormat::U8P;
+}
+impl Sample for i16 {
+    const INTERLEAVED: SampleFormat = SampleFormat::S16;
+    const PLANAR: SampleFormat = SampleFormat::S16P;
+}
+impl Sample for i32 {
+    const INTERLEAVED: SampleFormat = SampleFormat::S32;
+    const PLANAR: SampleFormat = SampleFormat::S32P;
+}
+impl Sample for f32 {
+    const INTERLEAVED: SampleFormat = SampleFormat::F32;
+    const PLANAR: SampleFormat = SampleFormat::F32P;
+}
+impl Sample for f64 {
+    const INTERLEAVED: SampleFormat = SampleFormat::F64;
+    const PLANAR: SampleFormat = SampleFormat::F64P;
+}
+
+/// The device sample-format conversion on its own (`needle_hip_convert_host`): every stream to interleaved
+/// `channels`-channel s16, not down-mixed.  `planar`: `pcm` holds `channels` slices (planes) per stream, one after the
+/// other, each of the stream's frame count; otherwise one interleaved slice per stream.
+pub fn convert<T: Sample>(pcm: &[&[T]], channels: i32, planar: bool) -> Result<Vec<Vec<i16>>> {
+    let per = channels.max(1) as usize;
+    let planes = if planar { per } else { 1 };
+    assert!(pcm.len() % planes == 0, "one slice per plane of every stream");
+    let lens: Vec<usize> = pcm.chunks(planes).map(|s| s.iter().map(|p| p.len()).sum()).collect();
+    let mut out: Vec<Vec<i16>> = lens.iter().map(|n| vec![0i16; n / per * per]).collect();
+    let ptrs: Vec<*const std::os::raw::c_void> = pcm.iter().map(|s| s.as_ptr() as *const _).collect();
+    let optrs: Vec<*mut i16> = out.iter_mut().map(|o| o.as_mut_ptr()).collect();
+    let format = if planar { T::PLANAR } else { T::INTERLEAVED };
+    unsafe {
+        check(ffi::needle_hip_convert_host(ptrs.as_ptr(), lens.as_ptr(), lens.len(), channels, format as i32, optrs.as_ptr()))?;
+    }
+    Ok(out)
+}
+
 /// Frame-hash file next to a video: `Path::with_extension("needle.dat")` (data.rs:8-13,117-119).
 pub fn frame_hash_path(video: impl AsRef<Path>) -> PathBuf {
     video.as_ref().with_extension("needle.dat")
@@ -545,7 +642,7 @@ pub fn frame_hash_path(video: impl AsRef<Path>) -> PathBuf {
 /// (analyzer.rs:437-445 over videos, comparator.rs:549-564 over pairs) is spread over the ranks of a communicator
 /// inside libneedle_capi.so: RCCL all-gathers on the library's own streams, no host round trips inside a job.
 pub mod multi_gpu {
-    use super::{check, ffi, Comparator, Result, SearchResult};
+    use super::{check, ffi, Comparator, Result, Sample, SampleFormat, SearchResult};
     use std::os::raw::c_int;
     use std::time::Duration;
 
@@ -581,6 +678,7 @@ pub mod multi_gpu {
     pub struct Library {
         raw: *mut ffi::NeedleHipLibrary,
         num_videos: usize,
+        format: SampleFormat,
     }
 
     impl Library {
@@ -589,7 +687,7 @@ pub mod multi_gpu {
             unsafe {
                 check(ffi::needle_hip_library_new(num_videos, opening_search_percentage, hash_duration.as_secs_f32(), &mut raw))?
             };
-            Ok(Library { raw, num_videos })
+            Ok(Library { raw, num_videos, format: SampleFormat::S16 })
         }
 
         /// The sample rate of the PCM `load_pcm` and `rank_videos` will be given (2000..768000 Hz, default 11025): the
@@ -598,6 +696,14 @@ pub mod multi_gpu {
         pub fn set_sample_rate(&mut self, sample_rate: u32) -> Result<&mut Self> {
             let rate = c_int::try_from(sample_rate).unwrap_or(c_int::MAX);
             unsafe { check(ffi::needle_hip_library_set_sample_rate(self.raw, rate))? };
+            Ok(self)
+        }
+
+        /// The sample format of the PCM `load_pcm_format` will be given (`needle_hip_library_set_sample_format`; default
+        /// s16, what `load_pcm` takes).  Call before loading.
+        pub fn set_sample_format(&mut self, format: SampleFormat) -> Result<&mut Self> {
+            unsafe { check(ffi::needle_hip_library_set_sample_format(self.raw, format as c_int))? };
+            self.format = format;
             Ok(self)
         }
 
@@ -626,6 +732,24 @@ pub mod multi_gpu {
         pub fn load_pcm(&mut self, pcm: &[Option<&[i16]>], num_values: &[usize], channels: usize, resident: bool) -> Result<()> {
             assert!(pcm.len() == self.num_videos && num_values.len() == self.num_videos);
             let ptrs: Vec<*const i16> = pcm.iter().map(|p| p.map_or(std::ptr::null(), |s| s.as_ptr())).collect();
+            unsafe {
+                if resident {
+                    check(ffi::needle_hip_library_set_pcm(self.raw, ptrs.as_ptr(), num_values.as_ptr(), channels as c_int))
+                } else {
+                    check(ffi::needle_hip_library_stream_pcm(self.raw, ptrs.as_ptr(), num_values.as_ptr(), channels as c_int))
+                }
+            }
+        }
+
+        /// `load_pcm` in the format chosen with `set_sample_format` (it must be `T`'s interleaved or planar one): the samples
+        /// are converted to s16 on the device on the way in.  Planar: `pcm` holds `channels` planes per video, one after
+        /// the other, all `None` for a video another rank owns.
+        pub fn load_pcm_format<T: Sample>(&mut self, pcm: &[Option<&[T]>], num_values: &[usize], channels: usize, resident: bool) -> Result<()> {
+            let planar = self.format == T::PLANAR && self.format != T::INTERLEAVED;
+            assert!(planar || self.format == T::INTERLEAVED, "set_sample_format first");
+            let planes = if planar { channels.max(1) } else { 1 };
+            assert!(pcm.len() == self.num_videos * planes && num_values.len() == self.num_videos);
+            let ptrs: Vec<*const i16> = pcm.iter().map(|p| p.map_or(std::ptr::null(), |s| s.as_ptr() as *const i16)).collect();
             unsafe {
                 if resident {
                     check(ffi::needle_hip_library_set_pcm(self.raw, ptrs.as_ptr(), num_values.as_ptr(), channels as c_int))
