@@ -499,6 +499,64 @@ enum NeedleError needle_hip_library_job_form(const NeedleHipLibrary *library, in
  * (LOCAL_WORLD_SIZE if the launcher exports it, else the world size); NEEDLE_HOST_THREADS overrides. */
 int needle_hip_host_threads(void);
 
+/* ---- Streaming fingerprinter: chromaprint's start / feed / finish, batched over lanes -------------------
+ * N lanes, one per decoder.  A feed takes whatever every lane has decoded since the last one; the per-lane state (the
+ * PCM tail from the first frame of the first item not yet emitted, and the first pass's chroma / energy rows of its
+ * frames: at most 76 KB per mono lane) stays in device memory and does not grow with the stream.  Every frame goes
+ * through the first pass once.  After `finish` a lane's items are bit for bit those of needle_hip_fingerprint_host (or
+ * of needle_hip_analyzer_run_pcm_format's opening hashes with the window set to the whole stream) over the
+ * concatenation of its chunks, however they were cut, also under NEEDLE_HIP_STFT=f64; items reported earlier are a
+ * prefix of that sequence and are never revised.
+ *
+ * channels 1..8, sample_rate 2000..768000 and every NeedleHipSampleFormat: what needle_hip_analyzer_run_pcm_format
+ * takes, through the same path -- conversion, the fused down-mix of 3-8 channels, the resampler, the fingerprinter.  At
+ * another rate than 11025 Hz a lane also keeps the source samples the resampler's next output tile still reads.
+ *
+ * A chunk is whole frames (num_values[i] % channels != 0: InvalidArgument, checked for every lane before any device
+ * work); a non-empty chunk for a finished lane is InvalidArgument until `reset`.  On return from `feed` the caller's
+ * buffers may be reused.  A feed of more than NEEDLE_HIP_MAX_BATCH_VALUES values (default 2^30) is cut internally.
+ * `ready` and `items` wait for outstanding device work.  A device failure poisons the feeder: every later call returns
+ * it.  One thread at a time per feeder.
+ *
+ * needle_hip_feeder_ready's kept_items is a function of the samples fed and of `finished` alone, not of how they were
+ * cut: it equals needle_hip_feeder_num_ready(...).  Finished that is num_kept(resample_out_len(n, rate), step).
+ * Unfinished, a feed resamples the whole output tiles whose taps lie inside the samples fed (the stream's end is not
+ * known, nothing may be clamped) and the first pass has seen the whole frame PAIRS of those outputs (the two-for-one
+ * transform pairs frames (2p, 2p + 1); a trailing odd frame waits for its partner).  The count therefore lags the
+ * one-shot's on the same prefix by at most L raw items -- ceil(L / step) kept items -- where, with T the resampler's
+ * tile and h its filter's half length in outputs, L = ceil((T + h) / 1365) + 1:
+ *     11025 Hz (no resampler)                          L = 1
+ *     44100 Hz (integer decimation, T = 1280)          L = 2
+ *     22050 Hz (integer decimation, T = 1536)          L = 3
+ *     48000 / 96000 Hz (matrix cores / DPP, T = 2352)  L = 3
+ *     32000 Hz (matrix cores, T = 7056)                L = 7
+ *     12345 Hz (a rate coprime-ish to 11025: the general form, T = 11760)   L = 10
+ * (T = 16 x 11025 / gcd(11025, rate) outside the integer decimations: a rate that shares little with 11025 has long
+ * tiles, and its items arrive in steps of that many outputs.) */
+typedef struct NeedleHipFeeder NeedleHipFeeder;
+enum NeedleError needle_hip_feeder_new(size_t lanes, int channels, int sample_rate, int format, uint32_t step,
+                                       NeedleHipFeeder **output);
+void needle_hip_feeder_free(NeedleHipFeeder *feeder);
+/* one entry per lane (planar formats: lanes * channels pointers, as in run_pcm_format); num_values[i] == 0: nothing for lane i */
+enum NeedleError needle_hip_feeder_feed(NeedleHipFeeder *feeder, const void *const *pcm, const size_t *num_values);
+enum NeedleError needle_hip_feeder_finish(NeedleHipFeeder *feeder, const size_t *lanes, size_t k); /* NULL: every unfinished lane */
+enum NeedleError needle_hip_feeder_reset(NeedleHipFeeder *feeder, const size_t *lanes, size_t k);  /* lane starts a new stream; NULL: every lane */
+enum NeedleError needle_hip_feeder_ready(NeedleHipFeeder *feeder, size_t lane, size_t *kept_items,
+                                         uint64_t *samples_per_channel_fed, bool *finished);
+enum NeedleError needle_hip_feeder_items(NeedleHipFeeder *feeder, size_t lane, size_t first, size_t count, uint32_t *items);
+/* FrameHashes of one video from two finished lanes: attach_timestamps (analyzer.rs:293-318) with ending_seek_ns as the
+ * ending window's seek offset (:314-318).  Requires step == the step of hash_duration.  ending_lane SIZE_MAX: no ending. */
+enum NeedleError needle_hip_feeder_frame_hashes(NeedleHipFeeder *feeder, size_t opening_lane, size_t ending_lane,
+                                                uint64_t ending_seek_ns, float hash_duration, const char *md5, FrameHashes **output);
+/* bytes[0]: the most state any one lane has carried from one round to the next so far, as the carry moved it (PCM
+ * tail, source-rate tail and rows; 0 before the second feed).  It does not grow with the stream: at most 22 frames'
+ * rows (112 B each), (24 x 1365 + 4096) samples of 11025 Hz PCM per tail channel and, at another rate, the inputs of one
+ * resampler tile plus its filter's length -- 76 176 B for a mono lane at 11025 Hz, 149 888 B for stereo at 11025 Hz,
+ * 117 760 B for stereo at 48 kHz.  bytes[1]: high-water of one round's staging (new samples and raw chunks). */
+enum NeedleError needle_hip_feeder_state_bytes(const NeedleHipFeeder *feeder, uint64_t bytes[2]);
+/* pure host arithmetic, no device: kept items a lane holds after that many samples */
+size_t needle_hip_feeder_num_ready(uint64_t samples_per_channel_fed, int sample_rate, int channels, uint32_t step, bool finished);
+
 #ifdef __cplusplus
 }
 #endif

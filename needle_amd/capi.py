@@ -102,7 +102,10 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_index_new", "needle_hip_index_free", "needle_hip_index_len", "needle_hip_index_add",
     "needle_hip_index_results", "needle_hip_index_pairs_searched", "needle_hip_index_remove", "needle_hip_index_replace",
     "needle_hip_index_store_sizes",
-    "needle_hip_convert_host", "needle_hip_analyzer_run_pcm_format", "needle_hip_library_set_sample_format"]
+    "needle_hip_convert_host", "needle_hip_analyzer_run_pcm_format", "needle_hip_library_set_sample_format",
+    "needle_hip_feeder_new", "needle_hip_feeder_free", "needle_hip_feeder_feed", "needle_hip_feeder_finish",
+    "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
+    "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready"]
 
 # enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
 SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
@@ -264,6 +267,18 @@ def lib():
     L.needle_hip_index_add.argtypes = [vp, C.POINTER(vp), sz]
     L.needle_hip_index_results.argtypes = [vp, C.POINTER(CSearchResult), sz]
     L.needle_hip_index_pairs_searched.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.needle_hip_feeder_new.argtypes = [sz, C.c_int, C.c_int, C.c_int, u32, C.POINTER(vp)]
+    L.needle_hip_feeder_free.argtypes = [vp]
+    L.needle_hip_feeder_free.restype = None
+    L.needle_hip_feeder_feed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.needle_hip_feeder_finish.argtypes = [vp, C.POINTER(sz), sz]
+    L.needle_hip_feeder_reset.argtypes = [vp, C.POINTER(sz), sz]
+    L.needle_hip_feeder_ready.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(u64), C.POINTER(b)]
+    L.needle_hip_feeder_items.argtypes = [vp, sz, sz, sz, vp]
+    L.needle_hip_feeder_frame_hashes.argtypes = [vp, sz, sz, u64, f32, C.c_char_p, C.POINTER(vp)]
+    L.needle_hip_feeder_state_bytes.argtypes = [vp, C.POINTER(u64)]
+    L.needle_hip_feeder_num_ready.argtypes = [u64, C.c_int, C.c_int, u32, b]
+    L.needle_hip_feeder_num_ready.restype = sz
     _LIB = L
     return L
 
@@ -693,6 +708,83 @@ class Index:
 
 
 # ---- kernel-level entry points ------------------------------------------------------------------------------
+def feeder_num_ready(samples_per_channel_fed: int, sample_rate: int = 11025, channels: int = 1, step: int = 1,
+                     finished: bool = False) -> int:
+    """Kept items a Feeder lane holds after that many samples (host arithmetic, no device)."""
+    return int(lib().needle_hip_feeder_num_ready(samples_per_channel_fed, sample_rate, channels, step, finished))
+
+
+class Feeder:
+    """needle_hip_feeder_*: chromaprint's start / feed / finish batched over `lanes`, state on the device."""
+
+    NO_LANE = C.c_size_t(-1).value  # SIZE_MAX: no ending lane
+
+    def __init__(self, lanes: int, channels: int = 1, sample_rate: int = 11025, sample_format: int = SAMPLE_S16,
+                 step: int = 1):
+        self._h = None
+        h = C.c_void_p()
+        check(lib().needle_hip_feeder_new(lanes, channels, sample_rate, sample_format, step, C.byref(h)))
+        self._h = h
+        self.lanes, self.channels, self.sample_rate, self.sample_format, self.step = lanes, channels, sample_rate, sample_format, step
+
+    def feed(self, pcm: Sequence) -> None:
+        """pcm[i]: what lane i has decoded since the last feed (interleaved: one array; planar: `channels` planes), or
+        None / an empty array for nothing."""
+        if len(pcm) != self.lanes:
+            raise ValueError(f"one chunk per lane: {self.lanes}, got {len(pcm)}")
+        planar = sample_format_planar(self.sample_format)
+        keep, flat = _format_pointers(pcm, self.channels, self.sample_format)
+        sizes = [0 if p is None else (sum(np.size(q) for q in p) if planar else np.size(p)) for p in pcm]
+        ptrs = (C.c_void_p * max(len(flat), 1))(*flat)
+        lens = (C.c_size_t * max(len(sizes), 1))(*sizes)
+        check(lib().needle_hip_feeder_feed(self._h, ptrs, lens))
+        del keep
+
+    def _lanes(self, lanes):
+        if lanes is None:
+            return None, 0
+        return (C.c_size_t * max(len(lanes), 1))(*lanes), len(lanes)
+
+    def finish(self, lanes: Optional[Sequence[int]] = None) -> None:
+        arr, k = self._lanes(lanes)
+        check(lib().needle_hip_feeder_finish(self._h, arr, k))
+
+    def reset(self, lanes: Optional[Sequence[int]] = None) -> None:
+        arr, k = self._lanes(lanes)
+        check(lib().needle_hip_feeder_reset(self._h, arr, k))
+
+    def ready(self, lane: int) -> Tuple[int, int, bool]:
+        """(kept items, samples per channel fed, finished) of a lane; waits for outstanding device work."""
+        kept, fed, fin = C.c_size_t(), C.c_uint64(), C.c_bool()
+        check(lib().needle_hip_feeder_ready(self._h, lane, C.byref(kept), C.byref(fed), C.byref(fin)))
+        return kept.value, fed.value, fin.value
+
+    def items(self, lane: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        if count is None:
+            count = self.ready(lane)[0] - first
+        out = np.zeros(max(count, 0), dtype=np.uint32)
+        check(lib().needle_hip_feeder_items(self._h, lane, first, count, out.ctypes.data if count else None))
+        return out
+
+    def frame_hashes(self, opening_lane: int, ending_lane: Optional[int] = None, ending_seek_ns: int = 0,
+                     hash_duration: float = DEFAULT_HASH_DURATION, md5: str = "") -> "FrameHashes":
+        h = C.c_void_p()
+        check(lib().needle_hip_feeder_frame_hashes(self._h, opening_lane, self.NO_LANE if ending_lane is None else ending_lane,
+                                                   ending_seek_ns, hash_duration, md5.encode(), C.byref(h)))
+        return FrameHashes(h.value, True)
+
+    def state_bytes(self) -> Tuple[int, int]:
+        """(the most bytes one lane has carried from one feed to the next, high-water of one feed's staging)"""
+        out = (C.c_uint64 * 2)()
+        check(lib().needle_hip_feeder_state_bytes(self._h, out))
+        return int(out[0]), int(out[1])
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().needle_hip_feeder_free(self._h)
+            self._h = None
+
+
 def fingerprint(pcms: Sequence[np.ndarray], channels: int = 1, step: int = 1) -> List[np.ndarray]:
     """needle_hip_fingerprint_host: raw chromaprint items (every `step`-th) of each stream."""
     arrs = [np.ascontiguousarray(p, dtype=np.int16) for p in pcms]

@@ -17,6 +17,7 @@
 
 #include "epilogue.h"
 #include "hipctx.h"
+#include "feeder.h"
 #include "index.h"
 #include "needle_core.h"
 
@@ -32,6 +33,9 @@ struct NeedleAudioAnalyzer {
 };
 struct NeedleAudioComparator {
   Comparator inner;
+};
+struct NeedleHipFeeder {
+  std::unique_ptr<Feeder> inner;
 };
 struct NeedleHipIndex {
   explicit NeedleHipIndex(const Comparator &c) : inner(c) {}
@@ -651,6 +655,99 @@ enum NeedleError needle_hip_hamming_runs_host(const uint32_t *hashes, size_t num
     *num_runs = out.size();
     return NeedleError_Ok;
   });
+}
+
+// ============================================================================================================
+// Streaming fingerprinter (feeder.hip)
+// ============================================================================================================
+enum NeedleError needle_hip_feeder_new(size_t lanes, int channels, int sample_rate, int format, uint32_t step,
+                                       NeedleHipFeeder **output) {
+  if (!output) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto f = std::make_unique<NeedleHipFeeder>();
+    Status s = Feeder::Create(lanes, channels, sample_rate, format, step, &f->inner);
+    if (!s.ok()) return report(s);
+    *output = f.release();
+    return NeedleError_Ok;
+  });
+}
+
+void needle_hip_feeder_free(NeedleHipFeeder *feeder) { delete feeder; }
+
+enum NeedleError needle_hip_feeder_feed(NeedleHipFeeder *feeder, const void *const *pcm, const size_t *num_values) {
+  if (!feeder || !pcm || !num_values) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->Feed(pcm, num_values);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_finish(NeedleHipFeeder *feeder, const size_t *lanes, size_t k) {
+  if (!feeder) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->Finish(lanes, k);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_reset(NeedleHipFeeder *feeder, const size_t *lanes, size_t k) {
+  if (!feeder) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->Reset(lanes, k);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_ready(NeedleHipFeeder *feeder, size_t lane, size_t *kept_items,
+                                         uint64_t *samples_per_channel_fed, bool *finished) {
+  if (!feeder) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->Ready(lane, kept_items, samples_per_channel_fed, finished);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_items(NeedleHipFeeder *feeder, size_t lane, size_t first, size_t count, uint32_t *items) {
+  if (!feeder || (count && !items)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->Items(lane, first, count, items);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_frame_hashes(NeedleHipFeeder *feeder, size_t opening_lane, size_t ending_lane,
+                                                uint64_t ending_seek_ns, float hash_duration, const char *md5, FrameHashes **output) {
+  if (!feeder || !output) return NeedleError_NullArgument;
+  if (!(hash_duration > 0.0f)) return NeedleError_AnalyzerInvalidHashDuration;
+  return guarded([&]() -> NeedleError {
+    bool ok = true;
+    const ns_t hd = duration_from_secs_f32(hash_duration, &ok);
+    uint32_t step = 0;
+    if (!ok || !step_for_hash_duration(hd, &step)) return NeedleError_AnalyzerInvalidHashDuration;
+    if (step != feeder->inner->step())
+      return report(Status::Make(NeedleError_InvalidArgument, "feeder: hash_duration asks for another step than the feeder's"));
+    const std::vector<uint32_t> *opening = nullptr, *ending = nullptr;
+    Status s = feeder->inner->FinishedItems(opening_lane, &opening);
+    if (s.ok() && ending_lane != SIZE_MAX) s = feeder->inner->FinishedItems(ending_lane, &ending);
+    if (!s.ok()) return report(s);
+    FrameHashesData d;
+    attach_timestamps(opening->data(), opening->size(), step, false, 0, &d.opening);
+    if (ending) attach_timestamps(ending->data(), ending->size(), step, true, ending_seek_ns, &d.ending);
+    d.hash_duration = hd;
+    d.md5 = md5 ? md5 : "";
+    *output = new FrameHashes{std::move(d)};
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_feeder_state_bytes(const NeedleHipFeeder *feeder, uint64_t bytes[2]) {
+  if (!feeder || !bytes) return NeedleError_NullArgument;
+  feeder->inner->StateBytes(bytes);
+  return NeedleError_Ok;
+}
+
+size_t needle_hip_feeder_num_ready(uint64_t samples_per_channel_fed, int sample_rate, int channels, uint32_t step, bool finished) {
+  return feeder_num_ready(samples_per_channel_fed, sample_rate, channels, step, finished);
 }
 
 // ============================================================================================================

@@ -1,5 +1,7 @@
-// libneedle_chromaprint.so: libchromaprint's streaming C API (the part needle uses) over the batched GPU
-// fingerprinter.  See include/needle_chromaprint.h.
+// libneedle_chromaprint.so: libchromaprint's streaming C API (the part needle uses) over the streaming GPU
+// fingerprinter: a context owns a one-lane feeder (needle_hip_feeder_*), chromaprint_feed gathers at most one block of
+// PCM on the host (4 s; NEEDLE_CHROMAPRINT_FEED_BLOCK: samples per channel) and feeds every full block,
+// chromaprint_finish flushes.  See include/needle_chromaprint.h.
 #include "../../include/needle_chromaprint.h"
 
 #include <cstdlib>
@@ -14,8 +16,19 @@ struct ChromaprintContextPrivate {
   int channels = 1;
   int rate = 11025;
   bool started = false, finished = false;
-  std::vector<int16_t> pcm;        // everything fed since start()
+  NeedleHipFeeder *feeder = nullptr;
+  size_t block_frames = 0;         // samples per channel gathered before they go to the feeder
+  std::vector<int16_t> block;      // at most that many, not yet fed
   std::vector<uint32_t> raw;       // raw fingerprint after finish()
+  ~ChromaprintContextPrivate() { needle_hip_feeder_free(feeder); }
+  bool flush() {
+    if (block.empty()) return true;
+    const void *ptrs[1] = {block.data()};
+    const size_t lens[1] = {block.size()};
+    const bool ok = needle_hip_feeder_feed(feeder, ptrs, lens) == NeedleError_Ok;
+    block.clear();
+    return ok;
+  }
 };
 
 extern "C" {
@@ -44,9 +57,14 @@ int chromaprint_start(ChromaprintContext *ctx, int sample_rate, int num_channels
   // resampler first, as libchromaprint's internal resampler would
   if (sample_rate < 2000 || sample_rate > 768000) return 0;
   if (num_channels != 1 && num_channels != 2) return 0;
+  needle_hip_feeder_free(ctx->feeder);
+  ctx->feeder = nullptr;
+  if (needle_hip_feeder_new(1, num_channels, sample_rate, NEEDLE_HIP_SAMPLE_S16, 1, &ctx->feeder) != NeedleError_Ok) return 0;
   ctx->channels = num_channels;
   ctx->rate = sample_rate;
-  ctx->pcm.clear();
+  ctx->block_frames = 4 * (size_t)sample_rate;
+  if (const char *e = std::getenv("NEEDLE_CHROMAPRINT_FEED_BLOCK")) ctx->block_frames = (size_t)std::atoll(e) > 0 ? (size_t)std::atoll(e) : 1;
+  ctx->block.clear();
   ctx->raw.clear();
   ctx->started = true;
   ctx->finished = false;
@@ -57,7 +75,15 @@ int chromaprint_feed(ChromaprintContext *ctx, const int16_t *data, int size) {
   if (!ctx || !ctx->started || ctx->finished || size < 0 || (size && !data)) return 0;
   if (size % ctx->channels != 0) return 0;
   try {
-    ctx->pcm.insert(ctx->pcm.end(), data, data + size);
+    const size_t cap = ctx->block_frames * (size_t)ctx->channels;
+    size_t left = (size_t)size;
+    while (left) {
+      const size_t take = left < cap - ctx->block.size() ? left : cap - ctx->block.size();
+      ctx->block.insert(ctx->block.end(), data, data + take);
+      data += take;
+      left -= take;
+      if (ctx->block.size() == cap && !ctx->flush()) return 0;
+    }
   } catch (...) {
     return 0;
   }
@@ -68,27 +94,13 @@ int chromaprint_finish(ChromaprintContext *ctx) {
   if (!ctx || !ctx->started) return 0;
   if (ctx->finished) return 1;
   try {
-    std::vector<int16_t> mono;
-    int channels = ctx->channels;
-    if (ctx->rate != needle_hip_fingerprint_sample_rate()) {  // down-mix + resample to mono 11025 Hz on the device
-      mono.assign(needle_hip_resample_out_len(ctx->pcm.size() / (size_t)ctx->channels, ctx->rate) + 1, 0);
-      const int16_t *in[1] = {ctx->pcm.data()};
-      const size_t in_len[1] = {ctx->pcm.size()};
-      int16_t *out[1] = {mono.data()};
-      if (needle_hip_resample_host(in, in_len, 1, ctx->channels, ctx->rate, out) != NeedleError_Ok) return 0;
-      mono.pop_back();
-      channels = 1;
-    }
-    const std::vector<int16_t> &pcm = ctx->rate == needle_hip_fingerprint_sample_rate() ? ctx->pcm : mono;
-    const size_t n = needle_hip_fingerprint_num_items(pcm.size() / (size_t)channels);
+    if (!ctx->flush() || needle_hip_feeder_finish(ctx->feeder, nullptr, 0) != NeedleError_Ok) return 0;
+    size_t n = 0;
+    if (needle_hip_feeder_ready(ctx->feeder, 0, &n, nullptr, nullptr) != NeedleError_Ok) return 0;
     ctx->raw.assign(n ? n : 1, 0);
-    const int16_t *ptrs[1] = {pcm.data()};
-    const size_t lens[1] = {pcm.size()};
-    uint32_t *outs[1] = {ctx->raw.data()};
-    if (needle_hip_fingerprint_host(ptrs, lens, 1, channels, 1, outs) != NeedleError_Ok) return 0;
+    if (needle_hip_feeder_items(ctx->feeder, 0, 0, n, ctx->raw.data()) != NeedleError_Ok) return 0;
     ctx->raw.resize(n);
-    ctx->pcm.clear();
-    ctx->pcm.shrink_to_fit();
+    ctx->block.shrink_to_fit();
   } catch (...) {
     return 0;
   }

@@ -189,6 +189,21 @@ Status gpu_fingerprint_cert_stats(uint64_t out[4], bool reset);
 Status gpu_fingerprint_audit_device(const int16_t *d_pcm, const std::vector<StreamSpan> &spans, int channels, uint32_t step,
                                     const uint32_t *d_items, uint64_t out[4], double *max_ratio, double *max_sigma);
 
+// One lane's share of a feed of the streaming fingerprinter (feeder.hip -> fingerprint.hip): where its PCM tail and its
+// chroma / energy rows lie in the feeder's buffers.  Rows [0, carried) hold first-pass rows of earlier feeds, rows
+// [carried, frames) are transformed now; `kept` new items, the first of them `first_item` rows in.
+struct FeedLane {
+  uint64_t pcm_off;     // s16 values: frame 0 of the lane's rows starts here
+  uint64_t item_off;    // where the new kept items go in d_items
+  uint32_t row_base;    // the lane's first chroma / energy row
+  uint32_t carried;     // even
+  uint32_t frames;      // carried + new
+  uint32_t first_item;
+  uint32_t kept;
+};
+Status gpu_fingerprint_feed_device(const int16_t *d_pcm, const std::vector<FeedLane> &lanes, int channels, uint32_t step,
+                                   double *d_chroma, float *d_energy, double *d_chroma64, uint32_t *d_items);
+
 // ---- resampler front-end (resample.hip) -------------------------------------------------------------------
 struct ResampleSpan {
   uint64_t in_off;   // offset into the input arena, in s16 values
@@ -201,6 +216,8 @@ struct ResampleSpan {
   //  * piece [p0, p1): the input samples that are there to be read (p1 == 0: the whole stream).  It must cover the taps
   //    of the tiles' outputs (resample_piece); its edges are not the stream's, zeros come only from outside [0, n_in).
   // The output is bit for bit the same slice of the whole stream's output.
+  // (out_off is taken modulo 2^64: with tiles, only the places of the outputs computed need lie in the arena -- the
+  // streaming feeder keeps a stream's tail alone, and its output 0 then lies in front of the arena.)
   const int16_t *src = nullptr;
   uint64_t t0 = 0, t1 = 0;
   uint64_t p0 = 0, p1 = 0;
@@ -213,6 +230,8 @@ struct ResampleTiling {
   uint64_t tile_outputs = 1;
 };
 Status resample_tiling(int rate, int channels, ResampleTiling *out);
+// the same without a device (the kernel's choice and its tiles are host arithmetic on the rate)
+Status resample_tiling_host(int rate, ResampleTiling *out);
 // the input samples [*p0, *p1) of a stream of n_in samples that tiles [t0, t1) read, p0 rounded down to a multiple of 8
 void resample_piece(const ResampleTiling &t, uint64_t n_in, uint64_t t0, uint64_t t1, uint64_t *p0, uint64_t *p1);
 Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> &spans, int channels, int rate,

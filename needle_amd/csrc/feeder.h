@@ -1,0 +1,37 @@
+// Streaming fingerprinter: chromaprint's start / feed / finish, batched over lanes, with the per-lane state on the
+// device (feeder.hip; include/needle_hip.h needle_hip_feeder_*).
+#pragma once
+
+#include <memory>
+
+#include "common.h"
+
+namespace needle {
+
+// Kept items a lane holds after `samples` samples per channel: host arithmetic only.  Unfinished, the first pass has
+// seen the whole frame PAIRS of the samples fed (a trailing odd frame waits for its partner); finished, every frame.
+size_t feeder_num_ready(uint64_t samples, int sample_rate, int channels, uint32_t step, bool finished);
+
+class Feeder {
+ public:
+  static Status Create(size_t lanes, int channels, int sample_rate, int format, uint32_t step, std::unique_ptr<Feeder> *out);
+  ~Feeder();
+  size_t lanes() const;
+  uint32_t step() const;
+  // pcm: sample_format_planes() pointers per lane; num_values[i] interleaved values (whole frames) of lane i
+  Status Feed(const void *const *pcm, const size_t *num_values);
+  Status Finish(const size_t *lanes, size_t k);  // nullptr: every unfinished lane
+  Status Reset(const size_t *lanes, size_t k);   // nullptr: every lane
+  // these wait for outstanding device work
+  Status Ready(size_t lane, size_t *kept_items, uint64_t *samples_fed, bool *finished);
+  Status Items(size_t lane, size_t first, size_t count, uint32_t *items);
+  Status FinishedItems(size_t lane, const std::vector<uint32_t> **items);  // InvalidArgument unless the lane is finished
+  void StateBytes(uint64_t bytes[2]) const;
+
+ private:
+  Feeder();
+  struct Impl;
+  std::unique_ptr<Impl> impl_;
+};
+
+}  // namespace needle

@@ -1,0 +1,535 @@
+// Streaming fingerprinter (include/needle_hip.h needle_hip_feeder_*): N lanes, one per decoder; a feed takes what every
+// lane has decoded since the last one, the per-lane state stays in HBM, and the items are bit for bit those of the
+// one-shot path over the concatenation of a lane's chunks.
+//
+// State of a lane, bounded whatever the stream's length (two sets of buffers, see below):
+//   * source-rate samples (converted, 3-8 channels down-mixed) the next resampler tile still reads -- other rates than
+//     11025 Hz only;
+//   * the 11025 Hz PCM tail, from the first frame of the first item not yet emitted (rounded down to a multiple of 4);
+//   * the first pass's chroma and energy rows of the tail's whole frame pairs.
+//
+// One round (a feed, or a piece of one that exceeds the staging bound):
+//   carry      feeder_carry_kernel: tails and rows of all lanes from the previous set of buffers to the front of their
+//              places in the other set -- source and destination never alias, 16-byte accesses (a lane's place starts
+//              at the same offset modulo 16 bytes as the data it inherits)
+//   land       the new chunks behind the carried tails: copied straight (s16, 1-2 channels), or staged raw and
+//              converted / down-mixed by convert.hip / downmix.hip; resample.hip then computes the whole output tiles
+//              whose taps lie inside the samples fed (nothing is clamped before `finish` tells the stream's end)
+//   fingerprint gpu_fingerprint_feed_device (fingerprint.hip): the first pass over the NEW frame pairs only, behind the
+//              carried rows; certification, recomputation and fix-up over carried + new.  Frame pairs are the
+//              one-shot's (2p, 2p + 1): the tail starts at an even frame and a trailing odd frame waits for its partner
+//              (or for `finish`, which transforms it alone as the one-shot does).
+// Every step is one launch over all lanes (tables searched by block, as in downmix.hip / convert.hip).
+#include "feeder.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "hipctx.h"
+
+namespace needle {
+
+namespace {
+
+constexpr uint32_t kLatency = (uint32_t)kItemLatency;  // frames - raw items
+
+// ---- the carry ------------------------------------------------------------------------------------------------------
+struct CarrySeg {
+  const uint4 *src;
+  uint4 *dst;
+  uint32_t n16;         // 16-byte words
+  uint32_t block_base;  // prefix of ceil(n16 / kCarryWordsPerBlock)
+};
+constexpr uint32_t kCarryThreads = 256, kCarryWordsPerThread = 4, kCarryWordsPerBlock = kCarryThreads * kCarryWordsPerThread;
+
+__global__ __launch_bounds__(kCarryThreads) void feeder_carry_kernel(const CarrySeg *__restrict__ segs, int num_segs,
+                                                                     uint32_t total_blocks) {
+  const uint32_t b = blockIdx.x;
+  if (b >= total_blocks) return;
+  int lo = 0, hi = num_segs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (segs[mid].block_base <= b) lo = mid; else hi = mid - 1;
+  }
+  const CarrySeg sg = segs[lo];
+  const uint32_t w0 = (b - sg.block_base) * kCarryWordsPerBlock + threadIdx.x;
+  uint4 v[kCarryWordsPerThread];
+#pragma unroll
+  for (uint32_t k = 0; k < kCarryWordsPerThread; k++) {
+    const uint32_t w = w0 + k * kCarryThreads;
+    v[k] = w < sg.n16 ? sg.src[w] : make_uint4(0u, 0u, 0u, 0u);
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < kCarryWordsPerThread; k++) {
+    const uint32_t w = w0 + k * kCarryThreads;
+    if (w < sg.n16) sg.dst[w] = v[k];
+  }
+}
+
+struct BufferSet {
+  DeviceBuffer<int16_t> src;     // source-rate tails + new samples (other rates than 11025 Hz)
+  DeviceBuffer<int16_t> pcm;     // 11025 Hz tails + new samples, lane after lane
+  DeviceBuffer<double> chroma;   // first-pass rows
+  DeviceBuffer<float> energy;
+};
+
+struct Lane {
+  uint64_t fed = 0;          // samples per channel fed (at the source rate)
+  uint64_t samples = 0;      // 11025 Hz samples per channel the tail reaches to
+  bool finished = false;
+  uint64_t frames_done = 0;  // frames through the first pass (even unless finished)
+  uint64_t items_done = 0;   // kept items emitted
+  uint64_t tail_frame = 0;   // the frame the lane's place in the current set starts at
+  uint64_t keep_frame = 0;   // ... and the one its place in the next set will start at (a multiple of 4, <= items_done * step)
+  uint64_t pcm_off = 0;      // current set, s16 values
+  uint32_t row_base = 0;     // current set
+  // other rates than 11025 Hz: the resampler's output tiles computed, and the source samples kept for the next one
+  uint64_t tiles_done = 0;
+  uint64_t src_p0 = 0;       // the source sample the lane's place in the current set starts at
+  uint64_t keep_p0 = 0;      // ... and the one its place in the next set will start at (resample_piece of the next tile)
+  uint64_t src_off = 0;      // current set, s16 values
+  std::vector<uint32_t> items;
+};
+
+// 11025 Hz samples of a stream's first `fed` source samples that are final: every tap inside the samples fed (output m
+// reads source samples up to m M / L + half), in whole tiles of the resampler -- or, finished, all of them.
+uint64_t final_outputs(const ResampleTiling &t, uint64_t fed, bool finished, uint64_t *tiles) {
+  const uint64_t L = (uint64_t)t.L, M = (uint64_t)t.M, half = (uint64_t)t.half;
+  if (finished) {
+    const uint64_t n_out = (fed * L + M - 1) / M;  // resample_out_len
+    *tiles = (n_out + t.tile_outputs - 1) / t.tile_outputs;
+    return n_out;
+  }
+  const uint64_t avail = fed > half ? ((fed - half) * L + M - 1) / M : 0;
+  *tiles = avail / t.tile_outputs;
+  return *tiles * t.tile_outputs;
+}
+
+}  // namespace
+
+size_t feeder_num_ready(uint64_t n, int sample_rate, int channels, uint32_t step, bool finished) {
+  if (step == 0 || channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS || sample_rate < 2000 || sample_rate > 768000) return 0;
+  const uint64_t out = resample_out_len((size_t)n, sample_rate);
+  if (finished) return num_kept((size_t)out, step);
+  uint64_t have = n;
+  if (sample_rate != kSampleRate) {
+    ResampleTiling t;
+    if (!resample_tiling_host(sample_rate, &t).ok()) return 0;
+    uint64_t tiles = 0;
+    have = final_outputs(t, n, false, &tiles);
+  }
+  const uint64_t frames = (uint64_t)num_frames((size_t)have) & ~(uint64_t)1;
+  const uint64_t raw = frames > kLatency ? frames - kLatency : 0;
+  return (size_t)((raw + step - 1) / step);
+}
+
+struct Feeder::Impl {
+  size_t n = 0;
+  int channels = 1, rate = kSampleRate, format = NEEDLE_HIP_SAMPLE_S16;
+  uint32_t step = 1;
+  int pcm_channels = 1;  // of the 11025 Hz tail: 3-8 channels arrive there down-mixed, resampled streams as mono
+  int src_channels = 1;  // of what lands: 3-8 channels are down-mixed on the way
+  bool resample = false;
+  ResampleTiling tiling;
+  bool direct = true;    // s16, 1-2 channels: chunks are copied straight behind the tails
+  size_t planes = 1, width = 2;
+  std::vector<Lane> lanes;
+  BufferSet sets[2];
+  int cur = 0;
+  DeviceBuffer<double> chroma64;  // the recomputation's rows (fingerprint.hip)
+  DeviceBuffer<int16_t> raw;      // chunks in the caller's format, as uploaded
+  DeviceBuffer<uint32_t> d_items;
+  DeviceBuffer<CarrySeg> d_segs;
+  PinnedStage seg_stage, item_stage;
+  hipEvent_t landed = nullptr;
+  struct Pending { size_t lane; uint64_t off, count; };
+  std::vector<Pending> pending;  // items on their way into item_stage
+  Status poison = Status::Ok();
+  uint64_t staging_high = 0;
+  uint64_t state_high = 0;  // the most bytes a round carried for one lane (tails and rows)
+
+  ~Impl() {
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    if (landed) {
+      (void)hipStreamSynchronize(library_stream());
+      (void)hipEventDestroy(landed);
+    }
+    for (PinnedStage *st : {&seg_stage, &item_stage}) {
+      if (st->ptr) (void)hipHostFree(st->ptr);
+      if (st->done) (void)hipEventDestroy(st->done);
+    }
+  }
+
+  // the items of the last round: wait for them and append them to their lanes
+  Status drain() {
+    if (pending.empty()) return Status::Ok();
+    NEEDLE_HIP_TRY(hipStreamSynchronize(library_stream()));
+    item_stage.pending = false;
+    const uint32_t *host = static_cast<const uint32_t *>(item_stage.ptr);
+    for (const Pending &p : pending) lanes[p.lane].items.insert(lanes[p.lane].items.end(), host + p.off, host + p.off + p.count);
+    pending.clear();
+    return Status::Ok();
+  }
+
+  struct Chunk {
+    const void *plane[NEEDLE_HIP_MAX_CHANNELS] = {};
+    uint64_t frames = 0;  // samples per channel
+    bool finish = false;
+  };
+
+  Status round(const std::vector<Chunk> &chunks) {
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    Status s = ensure_device();
+    if (!s.ok()) return s;
+    if (!(s = drain()).ok()) return s;
+    hipStream_t stream = library_stream();
+    if (!landed) NEEDLE_HIP_TRY(hipEventCreateWithFlags(&landed, hipEventDisableTiming));
+    if (resample) {  // the tiles this stream is counted in are the ones gpu_resample_device will plan
+      ResampleTiling now;
+      if (!(s = resample_tiling_host(rate, &now)).ok()) return s;
+      if (now.tile_outputs != tiling.tile_outputs) return Status::Make(NeedleError_Unknown, "feeder: the resampler's tiling changed under a stream");
+    }
+    BufferSet &from = sets[cur], &to = sets[cur ^ 1];
+    struct Plan {
+      uint64_t new_off = 0, carried_values = 0, src_off = 0, raw_off = 0;
+      uint64_t new_src_off = 0, carried_src = 0, from_src_off = 0, tiles = 0, samples = 0;
+      uint32_t row_base = 0, carried_rows = 0, src_row = 0;
+      uint64_t frames = 0, kept = 0;  // after the round
+    };
+    std::vector<Plan> plan(n);
+    std::vector<FeedLane> feed;
+    std::vector<size_t> feed_lane;
+    uint64_t cursor = 0, rows = 0, raw_units = 0, new_items = 0, new_values = 0, src_cursor = 0;
+    std::vector<ResampleSpan> rspans;
+    for (size_t i = 0; i < n; i++) {
+      const Lane &l = lanes[i];
+      const Chunk &c = chunks[i];
+      if (l.finished) continue;
+      Plan &p = plan[i];
+      p.carried_values = (l.samples - l.keep_frame * kHop) * (uint64_t)pcm_channels;
+      p.src_off = l.pcm_off + (l.keep_frame - l.tail_frame) * kHop * (uint64_t)pcm_channels;
+      p.carried_rows = (uint32_t)(l.frames_done - l.keep_frame);
+      p.src_row = l.row_base + (uint32_t)(l.keep_frame - l.tail_frame);
+      // the lane's place starts where its inherited data does modulo 16 bytes: the carry moves whole 16-byte words
+      p.new_off = ((cursor + 7) & ~(uint64_t)7) + (p.carried_values ? p.src_off % 8 : 0);
+      uint64_t samples = l.samples + c.frames;
+      if (resample) {
+        samples = final_outputs(tiling, l.fed + c.frames, c.finish, &p.tiles);
+        p.carried_src = (l.fed - l.keep_p0) * (uint64_t)src_channels;
+        p.from_src_off = l.src_off + (l.keep_p0 - l.src_p0) * (uint64_t)src_channels;  // a multiple of 8 values: no skew
+        p.new_src_off = (src_cursor + 7) & ~(uint64_t)7;
+        src_cursor = p.new_src_off + (l.fed + c.frames - l.keep_p0) * (uint64_t)src_channels + 8;
+      }
+      p.samples = samples;
+      cursor = p.new_off + samples * (uint64_t)pcm_channels - l.keep_frame * kHop * (uint64_t)pcm_channels + 8;
+      new_values += c.frames * (uint64_t)src_channels;
+      const uint64_t all = num_frames((size_t)samples);
+      p.frames = c.finish ? all : all & ~(uint64_t)1;
+      const uint64_t raw_items = p.frames > kLatency ? p.frames - kLatency : 0;
+      p.kept = (raw_items + step - 1) / step;
+      if (p.frames - l.keep_frame > 0x7FFFFFF0ull || rows > 0x7FFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "feeder: feed too large");
+      p.row_base = (uint32_t)rows;
+      rows += ((p.frames - l.keep_frame) + 3) & ~(uint64_t)1;
+      if (!direct && c.frames) {
+        p.raw_off = raw_units;
+        raw_units += planes * sample_plane_units(c.frames * (planes == 1 ? (uint64_t)channels : 1), width);
+      }
+      if (p.frames > l.frames_done) {
+        FeedLane f{};
+        f.pcm_off = p.new_off;
+        f.item_off = new_items;
+        f.row_base = p.row_base;
+        f.carried = p.carried_rows;
+        f.frames = (uint32_t)(p.frames - l.keep_frame);
+        f.first_item = (uint32_t)(l.items_done * step - l.keep_frame);
+        f.kept = (uint32_t)(p.kept - l.items_done);
+        new_items += f.kept;
+        feed.push_back(f);
+        feed_lane.push_back(i);
+      }
+    }
+    if (resample && !(s = to.src.reserve(src_cursor + 16)).ok()) return s;
+    if (!(s = to.pcm.reserve(cursor + 16)).ok() || !(s = to.chroma.reserve((rows + 2) * kBands)).ok() ||
+        !(s = to.energy.reserve((rows + 2) * 4)).ok() || !(s = chroma64.reserve((rows + 2) * kBands)).ok() ||
+        !(s = d_items.reserve(std::max<uint64_t>(new_items, 1))).ok() || !(s = raw.reserve(std::max<uint64_t>(raw_units, 1))).ok())
+      return s;
+    staging_high = std::max(staging_high, (new_values + raw_units) * 2);
+
+    // carry: tails and rows into the other set
+    std::vector<CarrySeg> segs;
+    uint32_t blocks = 0;
+    auto add_seg = [&](const void *src, void *dst, uint64_t bytes) {
+      const uintptr_t a = reinterpret_cast<uintptr_t>(src), head = a & 15;
+      CarrySeg sg;
+      sg.src = reinterpret_cast<const uint4 *>(a - head);
+      sg.dst = reinterpret_cast<uint4 *>(reinterpret_cast<uintptr_t>(dst) - head);
+      sg.n16 = (uint32_t)((head + bytes + 15) / 16);
+      sg.block_base = blocks;
+      blocks += (sg.n16 + kCarryWordsPerBlock - 1) / kCarryWordsPerBlock;
+      segs.push_back(sg);
+    };
+    for (size_t i = 0; i < n; i++) {
+      const Lane &l = lanes[i];
+      const Plan &p = plan[i];
+      if (l.finished) continue;
+      state_high = std::max(state_high, (p.carried_values + p.carried_src) * sizeof(int16_t) +
+                                            (uint64_t)p.carried_rows * (kBands * sizeof(double) + 4 * sizeof(float)));
+      if (p.carried_values) add_seg(from.pcm.ptr + p.src_off, to.pcm.ptr + p.new_off, p.carried_values * 2);
+      if (p.carried_src) add_seg(from.src.ptr + p.from_src_off, to.src.ptr + p.new_src_off, p.carried_src * 2);
+      if (p.carried_rows) {
+        add_seg(from.chroma.ptr + (uint64_t)p.src_row * kBands, to.chroma.ptr + (uint64_t)p.row_base * kBands,
+                (uint64_t)p.carried_rows * kBands * sizeof(double));
+        add_seg(from.energy.ptr + (uint64_t)p.src_row * 4, to.energy.ptr + (uint64_t)p.row_base * 4, (uint64_t)p.carried_rows * 4 * sizeof(float));
+      }
+    }
+    if (!segs.empty()) {
+      if (!(s = d_segs.reserve(segs.size())).ok() || !(s = seg_stage.acquire(segs.size() * sizeof(CarrySeg))).ok()) return s;
+      std::memcpy(seg_stage.ptr, segs.data(), segs.size() * sizeof(CarrySeg));
+      NEEDLE_HIP_TRY(hipMemcpyAsync(d_segs.ptr, seg_stage.ptr, segs.size() * sizeof(CarrySeg), hipMemcpyHostToDevice, stream));
+      seg_stage.mark(stream);
+      KernelTimer timer("feeder_carry");
+      hipLaunchKernelGGL(feeder_carry_kernel, dim3(blocks), dim3(kCarryThreads), 0, stream, d_segs.ptr, (int)segs.size(), blocks);
+      NEEDLE_HIP_TRY(hipGetLastError());
+    }
+
+    // land: the new chunks behind the carried tails.  The caller's buffers are theirs again when this returns, so no
+    // return, an error's included, leaves a copy reading them.
+    struct CopiesDone {
+      hipStream_t stream;
+      bool waited = false;
+      ~CopiesDone() { if (!waited) (void)hipStreamSynchronize(stream); }
+    } copies{stream};
+    std::vector<ConvertSpan> cspans;
+    std::vector<DownmixSpan> mspans;
+    for (size_t i = 0; i < n; i++) {
+      const Chunk &c = chunks[i];
+      const Plan &p = plan[i];
+      if (lanes[i].finished || !c.frames) continue;
+      int16_t *dst = resample ? to.src.ptr + p.new_src_off + p.carried_src : to.pcm.ptr + p.new_off + p.carried_values;
+      if (direct) {
+        NEEDLE_HIP_TRY(hipMemcpyAsync(dst, c.plane[0], c.frames * (uint64_t)channels * 2, hipMemcpyHostToDevice, stream));
+        continue;
+      }
+      const uint64_t plane_samples = c.frames * (planes == 1 ? (uint64_t)channels : 1), plane_units = sample_plane_units(plane_samples, width);
+      ConvertSpan sp{};
+      for (size_t k = 0; k < planes; k++) {
+        int16_t *at = raw.ptr + p.raw_off + k * plane_units;
+        NEEDLE_HIP_TRY(hipMemcpyAsync(at, c.plane[k], plane_samples * width, hipMemcpyHostToDevice, stream));
+        sp.src[k] = at;
+      }
+      sp.dst = dst;
+      sp.frames = c.frames;
+      if (format == NEEDLE_HIP_SAMPLE_S16) mspans.push_back(DownmixSpan{raw.ptr + p.raw_off, dst, c.frames});
+      else cspans.push_back(sp);
+    }
+    NEEDLE_HIP_TRY(hipEventRecord(landed, stream));  // the caller's buffers are free once this has executed
+    if (!cspans.empty() && !(s = gpu_convert_device(cspans, channels, format, channels > 2, false)).ok()) return s;
+    if (!mspans.empty() && !(s = gpu_downmix_device(mspans, channels, false)).ok()) return s;
+    if (resample) {  // the whole tiles whose taps lie inside the samples fed, behind the 11025 Hz tails
+      for (size_t i = 0; i < n; i++) {
+        const Lane &l = lanes[i];
+        const Plan &p = plan[i];
+        if (l.finished || p.tiles <= l.tiles_done) continue;
+        ResampleSpan sp{};
+        sp.n_in = l.fed + chunks[i].frames;
+        sp.out_off = p.new_off - l.keep_frame * kHop;  // of the stream's output 0 (modulo 2^64, common.h)
+        sp.src = to.src.ptr + p.new_src_off;
+        sp.t0 = l.tiles_done;
+        sp.t1 = p.tiles;
+        sp.p0 = l.keep_p0;
+        sp.p1 = sp.n_in;
+        rspans.push_back(sp);
+      }
+      if (!rspans.empty() && !(s = gpu_resample_device(nullptr, rspans, src_channels, rate, to.pcm.ptr, false)).ok()) return s;
+    }
+
+    if (!feed.empty()) {
+      if (!(s = gpu_fingerprint_feed_device(to.pcm.ptr, feed, pcm_channels, step, to.chroma.ptr, to.energy.ptr, chroma64.ptr, d_items.ptr)).ok())
+        return s;
+      if (new_items) {
+        if (!(s = item_stage.acquire(new_items * sizeof(uint32_t))).ok()) return s;
+        NEEDLE_HIP_TRY(hipMemcpyAsync(item_stage.ptr, d_items.ptr, new_items * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        item_stage.mark(stream);
+        for (size_t k = 0; k < feed.size(); k++)
+          if (feed[k].kept) pending.push_back(Pending{feed_lane[k], feed[k].item_off, feed[k].kept});
+      }
+    }
+    for (size_t i = 0; i < n; i++) {
+      Lane &l = lanes[i];
+      const Plan &p = plan[i];
+      if (l.finished) continue;
+      l.fed += chunks[i].frames;
+      l.samples = p.samples;
+      if (resample) {
+        l.src_p0 = l.keep_p0;
+        l.src_off = p.new_src_off;
+        l.tiles_done = p.tiles;
+        // what the next tile reads from (resample_piece)
+        const long long first = (long long)(l.tiles_done * tiling.tile_outputs * (uint64_t)tiling.M / (uint64_t)tiling.L) - tiling.half + 1;
+        l.keep_p0 = std::max(l.keep_p0, std::min<uint64_t>(first <= 0 ? 0 : (uint64_t)first & ~(uint64_t)7, l.fed & ~(uint64_t)7));
+      }
+      l.tail_frame = l.keep_frame;
+      l.pcm_off = p.new_off;
+      l.row_base = p.row_base;
+      l.frames_done = p.frames;
+      l.items_done = p.kept;
+      // (a multiple of 4 frames: a lane's two-pair chunks are then the groups of four frames the one-shot lists)
+      l.keep_frame = std::max(l.keep_frame, std::min(l.items_done * step, l.frames_done) & ~(uint64_t)3);
+      if (chunks[i].finish) l.finished = true;
+    }
+    cur ^= 1;
+    NEEDLE_HIP_TRY(hipEventSynchronize(landed));
+    copies.waited = true;
+    return Status::Ok();
+  }
+
+  Status guarded_round(const std::vector<Chunk> &chunks) {
+    Status s = round(chunks);
+    if (!s.ok() && s.code != NeedleError_InvalidArgument && s.code != NeedleError_NullArgument) poison = s;
+    return s;
+  }
+};
+
+Feeder::Feeder() : impl_(new Impl()) {}
+Feeder::~Feeder() = default;
+size_t Feeder::lanes() const { return impl_->n; }
+uint32_t Feeder::step() const { return impl_->step; }
+
+Status Feeder::Create(size_t lanes, int channels, int sample_rate, int format, uint32_t step, std::unique_ptr<Feeder> *out) {
+  if (lanes == 0 || lanes > (1u << 20)) return Status::Make(NeedleError_InvalidArgument, "feeder: lanes must be 1 to 1048576");
+  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
+    return Status::Make(NeedleError_InvalidArgument, "feeder: channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
+  if (sample_rate < 2000 || sample_rate > 768000) return Status::Make(NeedleError_InvalidArgument, "feeder: unsupported sample rate");
+  if (!sample_format_valid(format)) return Status::Make(NeedleError_InvalidArgument, "feeder: unknown sample format");
+  if (step == 0) return Status::Make(NeedleError_InvalidArgument, "feeder: step must be >= 1");
+  std::unique_ptr<Feeder> f(new Feeder());
+  Impl &m = *f->impl_;
+  m.n = lanes;
+  m.channels = channels;
+  m.rate = sample_rate;
+  m.format = format;
+  m.step = step;
+  m.src_channels = channels > 2 ? 1 : channels;
+  m.resample = sample_rate != kSampleRate;
+  m.pcm_channels = m.resample ? 1 : m.src_channels;
+  if (m.resample) {
+    Status s = resample_tiling_host(sample_rate, &m.tiling);
+    if (!s.ok()) return s;
+  }
+  m.direct = format == NEEDLE_HIP_SAMPLE_S16 && channels <= 2;
+  m.planes = sample_format_planes(format, channels);
+  m.width = sample_format_width(format);
+  m.lanes.resize(lanes);
+  *out = std::move(f);
+  return Status::Ok();
+}
+
+Status Feeder::Feed(const void *const *pcm, const size_t *num_values) {
+  Impl &m = *impl_;
+  if (!pcm || !num_values) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
+  if (!m.poison.ok()) return m.poison;
+  bool any = false;
+  for (size_t i = 0; i < m.n; i++) {
+    if (num_values[i] % (size_t)m.channels) return Status::Make(NeedleError_InvalidArgument, "feeder: a chunk must be whole frames");
+    if (!num_values[i]) continue;
+    if (m.lanes[i].finished) return Status::Make(NeedleError_InvalidArgument, "feeder: the lane is finished (reset it first)");
+    for (size_t k = 0; k < m.planes; k++)
+      if (!pcm[i * m.planes + k]) return Status::Make(NeedleError_NullArgument, "feeder: null chunk");
+    any = true;
+  }
+  if (!any) return Status::Ok();
+  // a feed beyond the staging bound is cut into rounds (the bound counts values, as in the one-shot entry points)
+  uint64_t bound = 1ull << 30;
+  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) bound = (uint64_t)std::max(1ll, atoll(e));
+  bound = std::max<uint64_t>(bound / (uint64_t)m.channels, 1);  // in frames
+  std::vector<uint64_t> done(m.n, 0);
+  for (;;) {
+    std::vector<Impl::Chunk> chunks(m.n);
+    uint64_t left = bound;
+    bool more = false;
+    for (size_t i = 0; i < m.n; i++) {
+      const uint64_t frames = num_values[i] / (size_t)m.channels, take = std::min(frames - done[i], left);
+      if (take) {
+        const uint64_t first = done[i] * (m.planes == 1 ? (uint64_t)m.channels : 1) * m.width;  // bytes into every plane
+        for (size_t k = 0; k < m.planes; k++) chunks[i].plane[k] = static_cast<const char *>(pcm[i * m.planes + k]) + first;
+        chunks[i].frames = take;
+        done[i] += take;
+        left -= take;
+      }
+      more = more || done[i] < frames;
+    }
+    Status s = m.guarded_round(chunks);
+    if (!s.ok() || !more) return s;
+  }
+}
+
+Status Feeder::Finish(const size_t *lanes, size_t k) {
+  Impl &m = *impl_;
+  if (!m.poison.ok()) return m.poison;
+  std::vector<Impl::Chunk> chunks(m.n);
+  bool any = false;
+  for (size_t j = 0; j < (lanes ? k : m.n); j++) {
+    const size_t i = lanes ? lanes[j] : j;
+    if (i >= m.n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+    if (m.lanes[i].finished) continue;
+    chunks[i].finish = true;
+    any = true;
+  }
+  return any ? m.guarded_round(chunks) : Status::Ok();
+}
+
+Status Feeder::Reset(const size_t *lanes, size_t k) {
+  Impl &m = *impl_;
+  if (!m.poison.ok()) return m.poison;
+  for (size_t j = 0; j < (lanes ? k : m.n); j++)
+    if (lanes && lanes[j] >= m.n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+  if (!m.pending.empty()) {
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    Status s = m.drain();
+    if (!s.ok()) return m.poison = s;
+  }
+  for (size_t j = 0; j < (lanes ? k : m.n); j++) m.lanes[lanes ? lanes[j] : j] = Lane();
+  return Status::Ok();
+}
+
+Status Feeder::Ready(size_t lane, size_t *kept_items, uint64_t *samples_fed, bool *finished) {
+  Impl &m = *impl_;
+  if (lane >= m.n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+  if (!m.poison.ok()) return m.poison;
+  if (!m.pending.empty()) {
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    Status s = m.drain();
+    if (!s.ok()) return m.poison = s;
+  }
+  if (kept_items) *kept_items = m.lanes[lane].items.size();
+  if (samples_fed) *samples_fed = m.lanes[lane].fed;
+  if (finished) *finished = m.lanes[lane].finished;
+  return Status::Ok();
+}
+
+Status Feeder::Items(size_t lane, size_t first, size_t count, uint32_t *items) {
+  size_t have = 0;
+  Status s = Ready(lane, &have, nullptr, nullptr);
+  if (!s.ok()) return s;
+  if (first > have || count > have - first) return Status::Make(NeedleError_InvalidArgument, "feeder: items out of range");
+  if (count && !items) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
+  if (count) std::memcpy(items, impl_->lanes[lane].items.data() + first, count * sizeof(uint32_t));
+  return Status::Ok();
+}
+
+Status Feeder::FinishedItems(size_t lane, const std::vector<uint32_t> **items) {
+  bool finished = false;
+  Status s = Ready(lane, nullptr, nullptr, &finished);
+  if (!s.ok()) return s;
+  if (!finished) return Status::Make(NeedleError_InvalidArgument, "feeder: the lane is not finished");
+  *items = &impl_->lanes[lane].items;
+  return Status::Ok();
+}
+
+void Feeder::StateBytes(uint64_t bytes[2]) const {
+  bytes[0] = impl_->state_high;
+  bytes[1] = impl_->staging_high;
+}
+
+}  // namespace needle

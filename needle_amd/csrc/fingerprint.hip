@@ -186,6 +186,9 @@ __global__ __launch_bounds__(256) void fir_norm_kernel(const double *__restrict_
 // spreads the lanes over all banks (pitch 12 would put every fourth lane on the same ones).
 constexpr int kTileRowsMax = 63 * 2 + 16;  // 64 items at the default step 2
 constexpr int kFeatPitch = 13;
+// PHASED (the feeder's classification table, gpu_fingerprint_feed_device): the stream's first kept item starts fir_base rows
+// into its frames instead of at row 0 -- the carried region starts at an even frame, an item of an odd step need not.
+template <bool PHASED = false>
 __global__ __launch_bounds__(256) void features_classify_kernel(const double *__restrict__ chroma,
                                                                 const FpStream *__restrict__ streams, int num_streams,
                                                                 const core::ClassifierThresholds *__restrict__ thr,
@@ -199,7 +202,7 @@ __global__ __launch_bounds__(256) void features_classify_kernel(const double *__
   const FpStream st = streams[si];
   const uint32_t k0 = (g - st.tile_base) * items_per_tile;
   const uint32_t count = min(items_per_tile, st.kept - k0);
-  const uint32_t x0 = k0 * step;  // raw item index = first feature row of the tile
+  const uint32_t x0 = k0 * step + (PHASED ? st.fir_base : 0u);  // raw item index = first feature row of the tile
   const uint32_t rows = (count - 1) * step + 16;
   double *mine = tiles[wave];
   const double *in = chroma + ((uint64_t)st.frame_base + x0) * kBands;
@@ -310,7 +313,9 @@ constexpr int kCertWaves = 2;
 constexpr int kHalfRows = kTileRowsMax / 2;  // SPLIT: even rows of a tile first, its odd rows from here on
 // SPLIT (chosen by the launcher when step == 2): the tile's rows lie de-interleaved in LDS (fp_core.h WindowStep ODD) --
 // same values, same additions in the same order; only where a row is kept differs.
-template <bool SPLIT>
+// PHASED: as in features_classify_kernel.  With SPLIT (a feed at step 2) the phase is even -- the tail starts at an even
+// frame and the items of an even step at even frames -- so an item still starts at an even row of its tile.
+template <bool SPLIT, bool PHASED = false>
 __global__ __launch_bounds__(64 * kCertWaves) void features_classify_cert_kernel(
     const double *__restrict__ chroma, const float *__restrict__ energy, const FpStream *__restrict__ streams, int num_streams,
     const core::ClassifierThresholds *__restrict__ thr, uint32_t step, uint32_t items_per_tile, uint32_t *__restrict__ items,
@@ -333,7 +338,7 @@ __global__ __launch_bounds__(64 * kCertWaves) void features_classify_cert_kernel
   const FpStream st = streams[si];
   const uint32_t k0 = (g - st.tile_base) * items_per_tile;
   const uint32_t count = min(items_per_tile, st.kept - k0);
-  const uint32_t x0 = k0 * step;
+  const uint32_t x0 = k0 * step + (PHASED ? st.fir_base : 0u);
   const uint32_t rows = (count - 1) * step + 16;
   double *mine = tiles[wave];
   float *sig = sigmas[wave];
@@ -540,6 +545,7 @@ struct FpWorkspace {
     return *descriptors[k];
   }
   bool lds_attr_set = false;  // the STFT kernel's 68 KiB of dynamic LDS needs an explicit opt-in
+  Descriptors feed_first, feed_second;  // the two tables of a feed (gpu_fingerprint_feed_device)
   // certified first pass: frame energies, control block (CertWork + chunk bitmap), the two lists, cumulative counts
   DeviceBuffer<float> energy;
   DeviceBuffer<uint32_t> cert_ctl, chunk_list;
@@ -572,6 +578,21 @@ FpWorkspace *workspace() {
   FpWorkspace *w = new FpWorkspace();
   g_ws[dev] = w;
   return w;
+}
+
+// the f64 STFT kernel's 68 KiB of dynamic LDS needs an explicit opt-in, once per device
+Status stft_lds_opt_in(FpWorkspace *ws) {
+  if (ws->lds_attr_set) return Status::Ok();
+  const void *variants[6] = {reinterpret_cast<const void *>(stft_chroma_kernel<1, 0, false>),
+                             reinterpret_cast<const void *>(stft_chroma_kernel<2, 0, false>),
+                             reinterpret_cast<const void *>(stft_chroma_kernel<1, 0, true>),
+                             reinterpret_cast<const void *>(stft_chroma_kernel<2, 0, true>),
+                             reinterpret_cast<const void *>(stft_chroma_kernel<1, 0, true, 3>),
+                             reinterpret_cast<const void *>(stft_chroma_kernel<2, 0, true, 3>)};
+  for (const void *fn : variants)
+    NEEDLE_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(core::kLds2Slots * sizeof(cd))));
+  ws->lds_attr_set = true;
+  return Status::Ok();
 }
 
 }  // namespace
@@ -657,18 +678,7 @@ Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan
       bool uploaded = false;
       if (!(s = desc.upload.put(&desc.streams, &desc.stage, meta, stream, &uploaded)).ok()) return s;
       const int n = (int)meta.size();
-      if (!ws->lds_attr_set) {
-        const void *variants[6] = {reinterpret_cast<const void *>(stft_chroma_kernel<1, 0, false>),
-                                   reinterpret_cast<const void *>(stft_chroma_kernel<2, 0, false>),
-                                   reinterpret_cast<const void *>(stft_chroma_kernel<1, 0, true>),
-                                   reinterpret_cast<const void *>(stft_chroma_kernel<2, 0, true>),
-                                   reinterpret_cast<const void *>(stft_chroma_kernel<1, 0, true, 3>),
-                                   reinterpret_cast<const void *>(stft_chroma_kernel<2, 0, true, 3>)};
-        for (const void *fn : variants)
-          NEEDLE_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(core::kLds2Slots * sizeof(cd))));
-        ws->lds_attr_set = true;
-      }
+      if (!(s = stft_lds_opt_in(ws)).ok()) return s;
       int cus = 256;
       {
         int dev = 0;
@@ -847,7 +857,7 @@ Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan
         }
       } else if (tiles > 0) {
         KernelTimer timer("features_classify");
-        hipLaunchKernelGGL(features_classify_kernel, dim3((uint32_t)((tiles + 3) / 4)), dim3(256), 0, stream,
+        hipLaunchKernelGGL(features_classify_kernel<false>, dim3((uint32_t)((tiles + 3) / 4)), dim3(256), 0, stream,
                            ws->chroma.ptr, desc.streams.ptr, n, tab.thr, step, items_per_tile, d_items, (uint32_t)tiles);
       }
       NEEDLE_HIP_TRY(hipGetLastError());
@@ -886,6 +896,151 @@ Status gpu_fingerprint_cert_stats(uint64_t out[4], bool reset) {
   out[2] = ws->chunks_total;
   out[3] = host.chunks_recomputed;
   if (reset) ws->items_total = ws->chunks_total = 0;
+  return Status::Ok();
+}
+
+// One feed of the streaming fingerprinter (feeder.hip) over all its lanes.  Two stream tables instead of one: the first
+// pass sees the NEW frame pairs only and writes their rows behind the rows carried from earlier feeds; certification,
+// recomputation and fix-up see carried + new frames, with the lane's first new item `first_item` rows in (PHASED).  The
+// recomputation writes its f64 rows into `d_chroma64`, a buffer of its own with the same row numbering, and the fix-up
+// reads them there: every frame of a listed item is in a listed chunk, and d_chroma keeps the first pass's rows for the
+// next feed's certification.  Same kernels, same arithmetic, same pairs as gpu_fingerprint_device on the whole stream.
+Status gpu_fingerprint_feed_device(const int16_t *d_pcm, const std::vector<FeedLane> &lanes, int channels, uint32_t step,
+                                   double *d_chroma, float *d_energy, double *d_chroma64, uint32_t *d_items) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  if (channels != 1 && channels != 2) return Status::Make(NeedleError_InvalidArgument, "fingerprint: channels must be 1 or 2");
+  if (step == 0) return Status::Make(NeedleError_InvalidArgument, "fingerprint: step must be >= 1");
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  FpTables tab;
+  if (!(s = get_tables(&tab)).ok()) return s;
+  hipStream_t stream = library_stream();
+  FpWorkspace *ws = workspace();
+  const uint32_t items_per_tile = (uint32_t)std::min<uint64_t>(64, (uint64_t)(kTileRowsMax - 16) / step + 1);
+  constexpr uint32_t kChunkPairs = NEEDLE_CHUNK_PAIRS;
+  std::vector<FpStream> first, second;
+  uint64_t pairs1 = 0, pairs2 = 0, kept = 0, tiles = 0, chunks1 = 0;
+  for (const FeedLane &l : lanes) {
+    if (l.frames < l.carried || (l.carried & 1u)) return Status::Make(NeedleError_InvalidArgument, "fingerprint: a feed's carried rows must be an even prefix");
+    const uint32_t fresh = l.frames - l.carried;
+    if (fresh) {
+      FpStream m{};
+      m.pcm_off = l.pcm_off + (uint64_t)l.carried * kHop * (uint64_t)channels;
+      m.frames = fresh;
+      m.frame_base = l.row_base + l.carried;
+      m.pair_base = (uint32_t)pairs1;
+      pairs1 += (fresh + 1) / 2;
+      chunks1 += ((fresh + 1) / 2 + kChunkPairs - 1) / kChunkPairs;
+      first.push_back(m);
+    }
+    if (l.kept) {
+      if ((uint64_t)l.first_item + (uint64_t)(l.kept - 1) * step + kItemLatency + 1 > l.frames)
+        return Status::Make(NeedleError_InvalidArgument, "fingerprint: a feed's items reach past its frames");
+      FpStream m{};
+      m.pcm_off = l.pcm_off;
+      m.item_off = l.item_off;
+      m.frames = l.frames;
+      m.frame_base = l.row_base;
+      m.fir_base = l.first_item;  // PHASED
+      m.kept = l.kept;
+      m.kept_base = (uint32_t)kept;
+      m.pair_base = (uint32_t)pairs2;
+      m.tile_base = (uint32_t)tiles;
+      tiles += (l.kept + items_per_tile - 1) / items_per_tile;
+      pairs2 += (l.frames + 1) / 2;
+      kept += l.kept;
+      second.push_back(m);
+    }
+  }
+  if (pairs1 == 0 && kept == 0) return Status::Ok();
+  if (pairs1 > 0x7FFFFFF0ull || pairs2 > 0x7FFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "fingerprint: feed too large");
+  if (!(s = stft_lds_opt_in(ws)).ok()) return s;
+  int cus = 256;
+  {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    cus = std::max(cus, 1);
+  }
+  if (!first.empty() && !(s = ws->feed_first.upload.put(&ws->feed_first.streams, &ws->feed_first.stage, first, stream)).ok()) return s;
+  if (!second.empty() && !(s = ws->feed_second.upload.put(&ws->feed_second.streams, &ws->feed_second.stage, second, stream)).ok()) return s;
+  const int n1 = (int)first.size(), n2 = (int)second.size();
+  const char *mode_env = getenv("NEEDLE_HIP_STFT");
+  const bool certified = !(mode_env && std::strcmp(mode_env, "f64") == 0);
+  if (!certified) {
+    if (pairs1) {
+      KernelTimer timer("stft_chroma");
+      const uint32_t ppb = (uint32_t)std::min<uint64_t>(kPairsPerBlock, std::max<uint64_t>(1, (pairs1 + 2ull * cus - 1) / (2ull * cus)));
+      const uint32_t grid = (uint32_t)(((pairs1 + ppb - 1) / ppb + 7) / 8 * 8);
+      auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), core::kLds2Slots * sizeof(cd), stream, d_pcm, ws->feed_first.streams.ptr, n1,
+                           tab.tw, tab.wcos, tab.wconst, tab.bin_slot, tab.fold_tab, d_chroma, (uint32_t)pairs1, ppb,
+                           stft::ChunkList{nullptr, nullptr});
+      };
+      if (channels == 1) launch(stft_chroma_kernel<1, 0, false>); else launch(stft_chroma_kernel<2, 0, false>);
+    }
+    if (tiles) {
+      KernelTimer timer("features_classify");
+      hipLaunchKernelGGL(features_classify_kernel<true>, dim3((uint32_t)((tiles + 3) / 4)), dim3(256), 0, stream, d_chroma,
+                         ws->feed_second.streams.ptr, n2, tab.thr, step, items_per_tile, d_items, (uint32_t)tiles);
+    }
+    NEEDLE_HIP_TRY(hipGetLastError());
+    return Status::Ok();
+  }
+  float cert_k = 64.0f;
+  if (const char *e = getenv("NEEDLE_HIP_CERT_K")) cert_k = std::max(0.0f, (float)atof(e));
+  const uint64_t nchunks = (std::max<uint64_t>(pairs2, 1) + kChunkPairs - 1) / kChunkPairs;
+  const size_t ctl_words = sizeof(CertWork) / 4 + (size_t)((nchunks + 31) / 32);
+  if (!(s = ws->cert_ctl.reserve(ctl_words)).ok() || !(s = ws->chunk_list.reserve(nchunks)).ok() ||
+      !(s = ws->item_list.reserve(std::max<uint64_t>(kept, 1))).ok())
+    return s;
+  if (!ws->stats) {
+    NEEDLE_HIP_TRY(hipMalloc((void **)&ws->stats, sizeof(CertStats)));
+    NEEDLE_HIP_TRY(hipMemsetAsync(ws->stats, 0, sizeof(CertStats), stream));
+  }
+  CertWork *work = reinterpret_cast<CertWork *>(ws->cert_ctl.ptr);
+  uint32_t *bitmap = ws->cert_ctl.ptr + sizeof(CertWork) / 4;
+  if (pairs1) {
+    KernelTimer timer("stft_chroma32");
+    const uint64_t slots = (uint64_t)kStft32WavesPerSimd * (uint64_t)cus;
+    const uint32_t ppb = (uint32_t)std::min<uint64_t>(kPairsPerBlock, std::max<uint64_t>(1, (pairs1 + slots - 1) / slots));
+    if (!(s = launch_stft_chroma32(channels, stft32_schedule(pairs1, ppb, 0, false), stream, d_pcm, ws->feed_first.streams.ptr, n1,
+                                   tab.tw32, tab.win32, tab.bin_slot, tab.fold_tab, d_chroma, d_energy, (uint32_t)pairs1,
+                                   ws->cert_ctl.ptr, (uint32_t)ctl_words)).ok())
+      return s;
+  } else {
+    NEEDLE_HIP_TRY(hipMemsetAsync(ws->cert_ctl.ptr, 0, ctl_words * sizeof(uint32_t), stream));
+  }
+  ws->chunks_total += chunks1;
+  if (tiles) {
+    {
+      KernelTimer timer("features_cert");
+      auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)((tiles + kCertWaves - 1) / kCertWaves)), dim3(64 * kCertWaves), 0, stream, d_chroma,
+                           d_energy, ws->feed_second.streams.ptr, n2, tab.thr, step, items_per_tile, d_items, (uint32_t)tiles, cert_k,
+                           kChunkPairs, work, bitmap, ws->chunk_list.ptr, ws->item_list.ptr);
+      };
+      // (an even step's items start at even rows of the even-aligned carried region: step 2 keeps its de-interleaved tile)
+      if (step == 2) launch(features_classify_cert_kernel<true, true>); else launch(features_classify_cert_kernel<false, true>);
+    }
+    {
+      KernelTimer timer("stft_fallback");
+      const uint32_t grid = (uint32_t)std::min<uint64_t>(2ull * (uint64_t)cus, nchunks);
+      const stft::ChunkList list{ws->chunk_list.ptr, &work->chunk_count};
+      auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), core::kLds2Slots * sizeof(cd), stream, d_pcm, ws->feed_second.streams.ptr, n2,
+                           tab.tw, tab.wcos, tab.wconst, tab.bin_slot, tab.fold_tab, d_chroma64, (uint32_t)pairs2, kChunkPairs, list);
+      };
+      if (channels == 1) launch(stft_chroma_kernel<1, 0, true>); else launch(stft_chroma_kernel<2, 0, true>);
+    }
+    {
+      KernelTimer timer("fixup_items");
+      hipLaunchKernelGGL(fixup_items_kernel, dim3(64), dim3(256), 0, stream, d_chroma64, tab.thr, work, ws->item_list.ptr, d_items,
+                         ws->stats, (uint32_t *)nullptr);
+    }
+    ws->items_total += kept;
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
   return Status::Ok();
 }
 

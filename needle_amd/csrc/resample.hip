@@ -685,6 +685,52 @@ size_t resample_out_len(size_t n_in, int rate) {
 
 namespace {
 
+// The filter of `rate` and everything about its kernels that is host arithmetic: what get_design uploads tables for, and
+// what plan_kernel reads -- so that the tiling of a rate can be had without a device (resample_tiling_host).  false: the
+// rate ratio is too large for these kernels.
+bool design_geometry(int rate, Design *d) {
+  design_filter(rate, d);
+  d->G = (((d->T + 3) / 4 + 1) + 3) & ~3;  // 16-byte groups per shifted row, a multiple of 4 for the kernel's unroll
+  // lanes per phase: 16 (one LDS lane group) when a tile then has plenty of outputs (L >= 256), more for small L;
+  // fewer when M is so large that 16 inputs M apart do not fit the LDS region
+  int n = 16;
+  while (n * d->L < 4096) n *= 2;  // small L: tiles of >= 4096 outputs amortise the per-tile latencies
+  auto footprint = [&](int lanes) {  // samples of LDS the tile's inputs take (row layout repeats the overlaps)
+    const bool rows = d->M >= kRowModeMinM && lanes <= kRowModeMaxN;
+    return rows ? (long long)lanes * (d->M + 4 * d->G + 8) : (long long)lanes * d->M + 4 * d->G + 8;
+  };
+  while (n > 1 && footprint(n) > kMaxRegionSamples) n /= 2;
+  if (footprint(n) > kMaxRegionSamples) return false;
+  d->n = n;
+  // resample_quad_kernel: the first taps of a lane's four outputs lie up to span = ceil(3 M / L) samples apart, 3
+  // more for the alignment of the first and 3 for a row's shift
+  const int span = (3 * d->M + d->L - 1) / d->L;
+  d->steps = (((d->T + span + 6 + 3) / 4) + 7) & ~7;
+  d->quad_pad = (span + 3) / 4 + 1;
+  d->row_len = d->quad_pad + std::max(d->G, d->steps) + 16;
+  d->delta = d->M % 4 == 0 ? ((1 - d->T / 2) % 4 + 4) % 4 : 0;
+  // resample_mfma_kernel: per block of sixteen outputs of a row, where the union of their windows starts and how many
+  // steps of four samples it needs
+  if (d->M % 4 == 0 && d->M >= kRowModeMinM && d->L >= 16) {
+    auto cp = [&](int o) { return (int)((long long)o * d->M / d->L); };
+    d->nblocks = (d->L + 15) / 16;
+    int need = 0;
+    for (int b = 0; b < d->nblocks; b++) need = std::max(need, cp(std::min(16 * b + 15, d->L - 1)) - cp(16 * b) + d->T);
+    for (int bucket : {12, 20, 36, 52})
+      if (d->mfma_steps == 0 && 4 * bucket >= need) d->mfma_steps = bucket;
+  }
+  if (d->mfma_steps) {
+    d->block_k0.assign((size_t)2 * d->nblocks, 0);  // window starts, then the steps a block needs (a multiple of 4)
+    for (int b = 0; b < d->nblocks; b++) {
+      const int c0 = (int)((long long)16 * b * d->M / d->L);
+      d->block_k0[b] = c0 + d->delta;
+      const int c_last = (int)((long long)std::min(16 * b + 15, d->L - 1) * d->M / d->L);
+      d->block_k0[d->nblocks + b] = std::min(d->mfma_steps, ((c_last - c0 + d->T + 3) / 4 + 3) & ~3);
+    }
+  }
+  return true;
+}
+
 // the filter of `rate` on device `dev` and its tables, built on first use
 Status get_design(int dev, int rate, Design **out) {
   Design *d;
@@ -692,20 +738,7 @@ Status get_design(int dev, int rate, Design **out) {
     std::lock_guard<std::mutex> lock(g_mu);
     d = &g_designs[{dev, rate}];
     if (d->T == 0) {
-      design_filter(rate, d);
-      d->G = (((d->T + 3) / 4 + 1) + 3) & ~3;  // 16-byte groups per shifted row, a multiple of 4 for the kernel's unroll
-      // lanes per phase: 16 (one LDS lane group) when a tile then has plenty of outputs (L >= 256), more for small L;
-      // fewer when M is so large that 16 inputs M apart do not fit the LDS region
-      int n = 16;
-      while (n * d->L < 4096) n *= 2;  // small L: tiles of >= 4096 outputs amortise the per-tile latencies
-      auto footprint = [&](int lanes) {  // samples of LDS the tile's inputs take (row layout repeats the overlaps)
-        const bool rows = d->M >= kRowModeMinM && lanes <= kRowModeMaxN;
-        return rows ? (long long)lanes * (d->M + 4 * d->G + 8) : (long long)lanes * d->M + 4 * d->G + 8;
-      };
-      while (n > 1 && footprint(n) > kMaxRegionSamples) n /= 2;
-      if (footprint(n) > kMaxRegionSamples)
-        return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
-      d->n = n;
+      if (!design_geometry(rate, d)) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
       std::vector<float> shifted((size_t)4 * d->L * 4 * d->G, 0.f);
       for (int a = 0; a < 4; a++)
         for (int p = 0; p < d->L; p++)
@@ -717,10 +750,6 @@ Status get_design(int dev, int rate, Design **out) {
       NEEDLE_HIP_TRY(hipMemcpy(d->d_coef_plain, d->coef.data(), d->coef.size() * sizeof(float), hipMemcpyHostToDevice));
       // resample_quad_kernel: the first taps of a lane's four outputs lie up to span = ceil(3 M / L) samples apart, 3
       // more for the alignment of the first and 3 for a row's shift
-      const int span = (3 * d->M + d->L - 1) / d->L;
-      d->steps = (((d->T + span + 6 + 3) / 4) + 7) & ~7;
-      d->quad_pad = (span + 3) / 4 + 1;
-      d->row_len = d->quad_pad + std::max(d->G, d->steps) + 16;
       std::vector<float> padded((size_t)4 * d->L * 4 * d->row_len, 0.f);
       for (int a = 0; a < 4; a++)
         for (int p = 0; p < d->L; p++)
@@ -729,7 +758,6 @@ Status get_design(int dev, int rate, Design **out) {
       NEEDLE_HIP_TRY(hipMalloc((void **)&d->d_coefq, padded.size() * sizeof(float)));
       NEEDLE_HIP_TRY(hipMemcpy(d->d_coefq, padded.data(), padded.size() * sizeof(float), hipMemcpyHostToDevice));
       // per quad: where its common window starts and which (shifted, delayed) coefficient row each output reads
-      d->delta = d->M % 4 == 0 ? ((1 - d->T / 2) % 4 + 4) % 4 : 0;
       const int quads = (d->L + 3) / 4;
       std::vector<QuadInfo> info((size_t)quads);
       for (int u = 0; u < quads; u++) {
@@ -749,23 +777,11 @@ Status get_design(int dev, int rate, Design **out) {
       NEEDLE_HIP_TRY(hipMemcpy(d->d_quad_info, info.data(), info.size() * sizeof(QuadInfo), hipMemcpyHostToDevice));
       // resample_mfma_kernel: per block of sixteen outputs of a row, where the union of their windows starts and the
       // coefficient of every (sample of the union, output) pair as the MFMA's B operand
-      if (d->M % 4 == 0 && d->M >= kRowModeMinM && d->L >= 16) {
-        auto cp = [&](int o) { return (int)((long long)o * d->M / d->L); };
-        d->nblocks = (d->L + 15) / 16;
-        int need = 0;
-        for (int b = 0; b < d->nblocks; b++) need = std::max(need, cp(std::min(16 * b + 15, d->L - 1)) - cp(16 * b) + d->T);
-        for (int bucket : {12, 20, 36, 52})
-          if (d->mfma_steps == 0 && 4 * bucket >= need) d->mfma_steps = bucket;
-      }
       if (d->mfma_steps) {
         const int S = d->mfma_steps;
         std::vector<float> cb((size_t)d->nblocks * S * 64, 0.f);
-        d->block_k0.assign((size_t)2 * d->nblocks, 0);  // window starts, then the steps a block needs (a multiple of 4)
         for (int b = 0; b < d->nblocks; b++) {
           const int c0 = (int)((long long)16 * b * d->M / d->L);
-          d->block_k0[b] = c0 + d->delta;
-          const int c_last = (int)((long long)std::min(16 * b + 15, d->L - 1) * d->M / d->L);
-          d->block_k0[d->nblocks + b] = std::min(S, ((c_last - c0 + d->T + 3) / 4 + 3) & ~3);
           for (int j = 0; j < 16; j++) {
             const int o = 16 * b + j;
             if (o >= d->L) continue;
@@ -869,6 +885,28 @@ Status resample_tiling(int rate, int channels, ResampleTiling *out) {
   out->M = d->M;
   out->half = d->T / 2;
   out->tile_outputs = plan_kernel(d).tile_outputs;
+  return Status::Ok();
+}
+
+Status resample_tiling_host(int rate, ResampleTiling *out) {
+  if (rate < 2000 || rate > 768000) return Status::Make(NeedleError_InvalidArgument, "resample: unsupported sample rate");
+  // the design is a function of the rate alone and is kept; the plan also reads the tuning switches of the environment
+  // and is made afresh, as gpu_resample_device makes it
+  static std::mutex mu;
+  static std::map<int, Design> known;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = known.find(rate);
+  if (it == known.end()) {
+    Design d;
+    if (!design_geometry(rate, &d)) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
+    d.coef = std::vector<float>();  // not needed for the geometry
+    it = known.emplace(rate, std::move(d)).first;
+  }
+  const Design &d = it->second;
+  out->L = d.L;
+  out->M = d.M;
+  out->half = d.T / 2;
+  out->tile_outputs = plan_kernel(&d).tile_outputs;
   return Status::Ok();
 }
 

@@ -41,6 +41,10 @@ pub struct NeedleHipLibrary {
 }
 
 #[repr(C)]
+pub struct NeedleHipFeeder {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct NeedleHipIndex {
     _private: [u8; 0],
 }
@@ -313,4 +317,42 @@ extern "C" {
     pub fn needle_hip_host_threads() -> c_int;
     pub fn needle_hip_host_alloc(host_ptr: *mut *mut c_void, bytes: usize) -> NeedleError;
     pub fn needle_hip_host_alloc_free(host_ptr: *mut c_void) -> NeedleError;
+    /// Streaming fingerprinter: chromaprint's start / feed / finish batched over lanes, state on the device.
+    pub fn needle_hip_feeder_new(
+        lanes: usize,
+        channels: c_int,
+        sample_rate: c_int,
+        format: c_int,
+        step: u32,
+        output: *mut *mut NeedleHipFeeder,
+    ) -> NeedleError;
+    pub fn needle_hip_feeder_free(feeder: *mut NeedleHipFeeder);
+    pub fn needle_hip_feeder_feed(feeder: *mut NeedleHipFeeder, pcm: *const *const c_void, num_values: *const usize) -> NeedleError;
+    pub fn needle_hip_feeder_finish(feeder: *mut NeedleHipFeeder, lanes: *const usize, k: usize) -> NeedleError;
+    pub fn needle_hip_feeder_reset(feeder: *mut NeedleHipFeeder, lanes: *const usize, k: usize) -> NeedleError;
+    pub fn needle_hip_feeder_ready(
+        feeder: *mut NeedleHipFeeder,
+        lane: usize,
+        kept_items: *mut usize,
+        samples_per_channel_fed: *mut u64,
+        finished: *mut bool,
+    ) -> NeedleError;
+    pub fn needle_hip_feeder_items(feeder: *mut NeedleHipFeeder, lane: usize, first: usize, count: usize, items: *mut u32) -> NeedleError;
+    pub fn needle_hip_feeder_frame_hashes(
+        feeder: *mut NeedleHipFeeder,
+        opening_lane: usize,
+        ending_lane: usize,
+        ending_seek_ns: u64,
+        hash_duration: f32,
+        md5: *const c_char,
+        output: *mut *mut FrameHashes,
+    ) -> NeedleError;
+    pub fn needle_hip_feeder_state_bytes(feeder: *const NeedleHipFeeder, bytes: *mut u64) -> NeedleError;
+    pub fn needle_hip_feeder_num_ready(
+        samples_per_channel_fed: u64,
+        sample_rate: c_int,
+        channels: c_int,
+        step: u32,
+        finished: bool,
+    ) -> usize;
 }

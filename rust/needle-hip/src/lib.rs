@@ -457,6 +457,91 @@ impl<P: AsRef<Path>> Comparator<P> {
     }
 }
 
+/// Streaming fingerprinter (`needle_hip_feeder_*`): chromaprint's start / feed / finish, batched over lanes -- one per
+/// decoder -- with the per-lane state on the device.  After `finish` a lane's items are bit for bit those of the one-shot
+/// path over the concatenation of its chunks.
+pub struct Feeder {
+    raw: *mut ffi::NeedleHipFeeder,
+    lanes: usize,
+    planes: usize,
+}
+
+unsafe impl Send for Feeder {}
+
+impl Feeder {
+    /// `T` and `planar` give the sample format, as in `Analyzer::run_pcm_format`.
+    pub fn new<T: Sample>(lanes: usize, channels: i32, sample_rate: i32, planar: bool, step: u32) -> Result<Self> {
+        let format = if planar { T::PLANAR } else { T::INTERLEAVED };
+        let mut raw = ptr::null_mut();
+        unsafe { check(ffi::needle_hip_feeder_new(lanes, channels, sample_rate, format as i32, step, &mut raw))? };
+        Ok(Feeder { raw, lanes, planes: if planar { channels.max(1) as usize } else { 1 } })
+    }
+
+    /// What every lane has decoded since the last feed: one slice per lane (planar: `channels` planes per lane, one after
+    /// the other); an empty slice is nothing for that lane.  The slices may be reused on return.
+    pub fn feed<T: Sample>(&mut self, pcm: &[&[T]]) -> Result<()> {
+        assert_eq!(pcm.len(), self.lanes * self.planes, "one slice per plane of every lane");
+        let ptrs: Vec<*const std::os::raw::c_void> = pcm.iter().map(|s| s.as_ptr() as *const _).collect();
+        let lens: Vec<usize> = pcm.chunks(self.planes).map(|s| s.iter().map(|p| p.len()).sum()).collect();
+        unsafe { check(ffi::needle_hip_feeder_feed(self.raw, ptrs.as_ptr(), lens.as_ptr())) }
+    }
+
+    /// `None`: every unfinished lane.
+    pub fn finish(&mut self, lanes: Option<&[usize]>) -> Result<()> {
+        let (p, k) = lanes.map_or((ptr::null(), 0), |l| (l.as_ptr(), l.len()));
+        unsafe { check(ffi::needle_hip_feeder_finish(self.raw, p, k)) }
+    }
+
+    /// The lanes start new streams (`None`: every lane).
+    pub fn reset(&mut self, lanes: Option<&[usize]>) -> Result<()> {
+        let (p, k) = lanes.map_or((ptr::null(), 0), |l| (l.as_ptr(), l.len()));
+        unsafe { check(ffi::needle_hip_feeder_reset(self.raw, p, k)) }
+    }
+
+    /// `(kept items, samples per channel fed, finished)` of a lane; waits for outstanding device work.
+    pub fn ready(&mut self, lane: usize) -> Result<(usize, u64, bool)> {
+        let (mut kept, mut fed, mut finished) = (0usize, 0u64, false);
+        unsafe { check(ffi::needle_hip_feeder_ready(self.raw, lane, &mut kept, &mut fed, &mut finished))? };
+        Ok((kept, fed, finished))
+    }
+
+    pub fn items(&mut self, lane: usize, first: usize, count: usize) -> Result<Vec<u32>> {
+        let mut out = vec![0u32; count];
+        unsafe { check(ffi::needle_hip_feeder_items(self.raw, lane, first, count, out.as_mut_ptr()))? };
+        Ok(out)
+    }
+
+    /// The `FrameHashes` of one video from its finished opening lane and, optionally, its ending lane with the seek offset of
+    /// the ending window (analyzer.rs:314-318).
+    pub fn frame_hashes(&mut self, opening_lane: usize, ending: Option<(usize, Duration)>, hash_duration: Duration, md5: &str) -> Result<FrameHashes> {
+        let md5 = CString::new(md5).map_err(|_| Error { code: ffi::NeedleError::InvalidUtf8String, message: "md5 holds a NUL".into() })?;
+        let (lane, seek) = ending.map_or((usize::MAX, 0u64), |(l, d)| (l, d.as_nanos() as u64));
+        let mut raw = ptr::null_mut();
+        unsafe {
+            check(ffi::needle_hip_feeder_frame_hashes(self.raw, opening_lane, lane, seek, hash_duration.as_secs_f32(), md5.as_ptr(), &mut raw))?;
+            FrameHashes::from_raw(raw)
+        }
+    }
+
+    /// `(the most state one lane has carried from one feed to the next, high-water of one feed's staging)` in bytes.
+    pub fn state_bytes(&self) -> Result<(u64, u64)> {
+        let mut bytes = [0u64; 2];
+        unsafe { check(ffi::needle_hip_feeder_state_bytes(self.raw, bytes.as_mut_ptr()))? };
+        Ok((bytes[0], bytes[1]))
+    }
+
+    /// Kept items a lane holds after that many samples (host arithmetic, no device).
+    pub fn num_ready(samples_per_channel_fed: u64, sample_rate: i32, channels: i32, step: u32, finished: bool) -> usize {
+        unsafe { ffi::needle_hip_feeder_num_ready(samples_per_channel_fed, sample_rate, channels, step, finished) }
+    }
+}
+
+impl Drop for Feeder {
+    fn drop(&mut self) {
+        unsafe { ffi::needle_hip_feeder_free(self.raw) };
+    }
+}
+
 /// An incremental search index (include/needle_hip.h "Incremental index"): `results()` equals
 /// `Comparator::run_with_frame_hashes` over the index's current list of videos (one slot per video, `None` where that call
 /// pushes no result); `add` searches only the pairs it adds, `remove` none and `replace` those of the videos replaced.  The comparator's parameters are copied at
