@@ -113,7 +113,7 @@ Status wav_probe(const std::string &path, WavInfo *out);  // reads chunk headers
 // frames [first, first+count) as interleaved s16 (count * channels values)
 Status wav_read_frames(const std::string &path, const WavInfo &info, uint64_t first, uint64_t count, int16_t *dst);
 
-// ---- GPU entry points used by the host classes (fingerprint.hip / search.hip) ----------------------------
+// ---- GPU entry points used by the host classes (fingerprint.hip, fingerprint_host.hip / search.hip) ----------------------------
 struct StreamSpan {
   uint64_t pcm_off;     // offset into the PCM arena, in s16 values
   uint64_t num_values;  // interleaved values
@@ -277,7 +277,7 @@ Status gpu_convert_device(const std::vector<ConvertSpan> &spans, int channels, i
 // units, multiples of 8); otherwise as gpu_upload_pcm.
 Status gpu_upload_raw(const std::vector<const void *> &src, const std::vector<size_t> &bytes, const std::vector<uint64_t> &dev_off,
                       int16_t *d_raw, ::ihipStream_t *stream = nullptr, const StreamIssued &issued = nullptr);
-// gpu_fingerprint_host / gpu_fingerprint_streamed_device with the streams in `format` (fingerprint.hip): uploaded as
+// gpu_fingerprint_host / gpu_fingerprint_streamed_device with the streams in `format` (fingerprint_host.hip): uploaded as
 // they are, converted on the device group by group under the uploads.  pcm: sample_format_planes() pointers per stream.
 Status gpu_fingerprint_host_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels,
                                    int format, uint32_t step, std::vector<std::vector<uint32_t>> *items, int rate = kSampleRate);

@@ -33,6 +33,7 @@ hipStream_t library_stream();
 hipStream_t download_stream();  // result downloads, ordered behind the library stream with events
 hipStream_t upload_stream();    // PCM uploads of the streaming analyzer; kernels follow on the library stream behind events
 hipStream_t stft_stream();    // CU-masked stream for a pipelined job's f32 STFT, or nullptr (hipctx.hip)
+int device_cu_count();          // compute units of the current device (256 on MI355X), asked once per device; >= 1
 
 template <typename T>
 struct DeviceBuffer {

@@ -207,6 +207,18 @@ hipStream_t stft_stream() {
   return s;
 }
 
+int device_cu_count() {
+  static std::map<int, int> counts;
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = counts.find(dev);
+  if (it != counts.end()) return it->second;
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  return counts[dev] = std::max(cus, 1);
+}
+
 // Host -> device PCM copies of the streaming analyzer go here, so that the fingerprint kernels of the streams that
 // have landed (library stream, behind an event) run underneath the copies of the streams that follow.
 hipStream_t upload_stream() {

@@ -5,7 +5,7 @@
 // 4096-point complex transform, radix 16 x 3 in place in one padded LDS image, wave-local power image, DPP fold -- in
 // f32: half the LDS bytes, half the registers (three to four workgroups per CU instead of two) and the f32 issue
 // rate.  Its chroma is NOT the contract's; it is a first pass whose every consumer is certified:
-// features_classify_cert_kernel (fingerprint.hip) accepts an item only if all 48 threshold comparisons clear a
+// features_classify_cert_kernel (classify_kernels.h) accepts an item only if all 48 threshold comparisons clear a
 // data-dependent radius, and every other item is recomputed from f64 chroma (stft_chroma_kernel over the listed
 // chunks of frame pairs + fixup_items_kernel).  What the radius needs from here is the total energy of the frame PAIR (one transform)
 // E = sum |x|^2 next to its 12 pitch-class sums: with a strong component outside chromaprint's band (a 5 kHz tone, a

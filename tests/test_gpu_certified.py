@@ -1,5 +1,5 @@
 """GPU tests (-m gpu) of the certified f32 first pass of the fingerprinter (needle_amd/csrc/stft32_kernel.h,
-features_classify_cert_kernel / fixup_items_kernel in fingerprint.hip).
+features_classify_cert_kernel / fixup_items_kernel in classify_kernels.h, launched from fingerprint.hip).
 
 The contract: every emitted u32 equals the f64 pipeline's (the oracle's), although most items never see an f64 FFT.
 What is tested: equality with the oracle on audio, on a zoo of hostile signals and on inputs CONSTRUCTED to put a
@@ -289,3 +289,27 @@ def test_adversarial_corpus_stays_inside_the_radius(monkeypatch):
     got = capi.fingerprint(pcms, step=1)                             # and the product's items are the oracle's
     for g, p in zip(got, pcms):
         assert g.tolist() == O.fingerprint(p).tolist()
+
+
+@pytest.mark.parametrize("stft", [None, "f64"])
+def test_audit_split_into_chunks_equals_the_audit_in_one_launch(stft, monkeypatch):
+    """The audit walks a library in chunks of bounded frames, like the one-shot driver, and sums its counts over them.
+    NEEDLE_HIP_MAX_FRAMES_PER_CHUNK -- the bound the parity tests give the one-shot -- cuts four ragged streams (94, 280,
+    159 and 62 frames) into one stream per chunk (1), into chunks of different sizes (200) and into single streams plus
+    a chunk of two (250): every count and both maxima -- integer counts and maxima over the same items -- must be the
+    one launch's, exactly, whichever pipeline wrote the items that are audited."""
+    _mode(monkeypatch, stft=stft)
+    monkeypatch.delenv("NEEDLE_HIP_MAX_FRAMES_PER_CHUNK", raising=False)
+    pcms = [synth.make_episode(30 + k, secs, 0.0).pcm for k, secs in enumerate((12.0, 35.0, 20.0, 8.0))]
+    kept = sum(len(fh.opening) for fh in O.analyze_batch(pcms, 1, O.duration_from_secs_f32(capi.DEFAULT_HASH_DURATION)))
+    lib = capi.Library(len(pcms), opening_search_percentage=1.0)
+    lib.set_pcm(pcms, [len(p) for p in pcms])
+    lib.analyze()
+    keys = ("items", "accepted", "mismatches", "accepted_mismatches", "max_error_over_s", "max_s")
+    one = lib.audit()
+    assert one["items"] == kept > 0 and one["mismatches"] == 0 and one["accepted_mismatches"] == 0, one
+    for bound in (1, 200, 250):
+        monkeypatch.setenv("NEEDLE_HIP_MAX_FRAMES_PER_CHUNK", str(bound))
+        cut = lib.audit()
+        print("audit in one launch:", one, "frames per chunk", bound, ":", cut)
+        assert {k: cut[k] for k in keys} == {k: one[k] for k in keys}, (bound, cut, one)

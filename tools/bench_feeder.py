@@ -175,7 +175,8 @@ def bench_launches(feeds):
             calls = {}
             for path in stats:
                 for row in csv.DictReader(open(path)):
-                    name = re.sub(r"\(.*", "", row["Name"]).replace("needle::(anonymous namespace)::", "").replace("void ", "")
+                    name = row["Name"].replace("needle::(anonymous namespace)::", "").replace("needle::stft::", "").replace("void ", "")
+                    name = re.sub(r"\(.*", "", name)   # (the argument list; after the namespaces, which hold a parenthesis too)
                     calls[name] = calls.get(name, 0) + int(row["Calls"])
             # feeds + the finish round
             out[str(lanes)] = {"rounds": feeds + 1, "calls": calls, "per_feed": round(sum(calls.values()) / (feeds + 1), 2)}
