@@ -557,6 +557,62 @@ enum NeedleError needle_hip_feeder_state_bytes(const NeedleHipFeeder *feeder, ui
 /* pure host arithmetic, no device: kept items a lane holds after that many samples */
 size_t needle_hip_feeder_num_ready(uint64_t samples_per_channel_fed, int sample_rate, int channels, uint32_t step, bool finished);
 
+/* ---- Streaming comparator: search as the hashes arrive ---------------------------------------------------
+ * The search half of the streaming path, the counterpart of the feeder.  A matcher holds S source sequences (the
+ * openings of a season, say: the videos of an index), resident on the device from creation on, a threshold, one
+ * min_len >= 1 per source, and N lanes.  A lane is a destination sequence that arrives in chunks of hashes -- from a
+ * feeder lane, or from anywhere else.
+ *
+ * Cells, matching, runs and simhashes are those of needle_hip_hamming_runs_host above, for the problems (source s, the
+ * lane's sequence, min_len[s]); NeedleHipRun.problem is the source's index.  After `finish` a lane's runs, as a set,
+ * equal what that call gives for the S problems over the concatenation of the lane's chunks, both simhashes included,
+ * however the chunks were cut (one-item feeds, empty feeds, a first feed of one item, which has no cell).
+ *
+ * When a run is reported.  After a lane has received columns [0, J) and is not finished it has reported exactly the
+ * runs of the complete list with
+ *     dst_end < J - 1                          (a later column has broken them), or
+ *     src_end == n_s - 1 && dst_end <= J - 1   (they reached the source's last row).
+ * A run that touches column J - 1 elsewhere is open; `finish` reports those of length >= min_len.  Runs are appended per
+ * lane in the order they were found and never revised; the order within one feed is unspecified.
+ * needle_hip_matcher_open returns (malloc'd, needle_hip_host_free) the runs still open at the last column fed whose
+ * length is already >= min_len: src_end, dst_end = J - 1 and len, the simhash fields zero.  It changes nothing.
+ *
+ * Every cell is evaluated once: the run lengths of all diagonals at the last column fed stay in device memory between
+ * feeds (one length per source row per lane, 2 bytes where every source is shorter than 65 536 hashes, else 4; two sets)
+ * and a feed evaluates the cells of its new columns only, in a fixed number of kernel launches (three) that does not
+ * depend on N, on S or on how many lanes have data.  A feed of more than 512 items for one lane is cut into strips of
+ * 512 columns, each a round of three launches.  A lane's hashes so far are kept on the device too (4 bytes per item: the
+ * destination simhash of a run reaches back into earlier chunks); the history is not bounded.
+ * Nothing is lost: when a round finds more runs than its device slab holds (silence against silence makes every
+ * diagonal a run) the slab grows and the round is repeated from the set of state buffers it did not write.
+ * NEEDLE_HIP_MATCHER_RUN_SLAB=<runs> sets the initial slab (default 4096).
+ *
+ * lanes == 0 or > 65535, num_sources == 0, a min_len of 0, a source outside `hashes`, a lane out of range, items for a
+ * finished lane before `reset`, unequal lane counts in feed_from_feeder: InvalidArgument, checked for every lane before
+ * any device work.  The sources are uploaded at creation: without a HIP device creation fails (there is no CPU path).
+ * A source shorter than 2 hashes has no cells and yields nothing.  On return from `feed` the caller's buffers may be
+ * reused.  A device failure poisons the matcher: every later call returns it.  One thread at a time per matcher. */
+typedef struct NeedleHipMatcher NeedleHipMatcher;
+enum NeedleError needle_hip_matcher_new(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *sources,
+                                        const uint32_t *min_len, size_t num_sources, size_t lanes, uint32_t threshold,
+                                        NeedleHipMatcher **output);
+void needle_hip_matcher_free(NeedleHipMatcher *matcher);
+/* one entry per lane, host hashes; num_items[i] == 0: nothing for lane i */
+enum NeedleError needle_hip_matcher_feed(NeedleHipMatcher *matcher, const uint32_t *const *items, const size_t *num_items);
+/* Moves, lane by lane (equal lane counts), the feeder's ready items the matcher has not yet taken -- those from
+ * items_fed on: the lane is fed from that feeder lane alone -- and finishes the lanes the feeder has finished. */
+enum NeedleError needle_hip_matcher_feed_from_feeder(NeedleHipMatcher *matcher, NeedleHipFeeder *feeder);
+enum NeedleError needle_hip_matcher_finish(NeedleHipMatcher *matcher, const size_t *lanes, size_t k); /* NULL: every unfinished lane */
+enum NeedleError needle_hip_matcher_reset(NeedleHipMatcher *matcher, const size_t *lanes, size_t k);  /* lane starts a new stream; NULL: every lane */
+enum NeedleError needle_hip_matcher_ready(NeedleHipMatcher *matcher, size_t lane, size_t *num_runs, uint64_t *items_fed,
+                                          bool *finished);
+enum NeedleError needle_hip_matcher_runs(NeedleHipMatcher *matcher, size_t lane, size_t first, size_t count, NeedleHipRun *runs);
+enum NeedleError needle_hip_matcher_open(NeedleHipMatcher *matcher, size_t lane, NeedleHipRun **runs, size_t *num_runs);
+/* stats[0] feeds that carried items, stats[1] kernel launches, stats[2] cells evaluated (over a finished lane at most
+ * (n_s - 1)(m - 1) + n_s per feed against source s; a repeated round counts again), stats[3] bytes of state on the device:
+ * the sources, the two sets of run lengths and the lanes' histories (4 bytes per item fed). */
+enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint64_t stats[4]);
+
 #ifdef __cplusplus
 }
 #endif

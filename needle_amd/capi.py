@@ -105,7 +105,10 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_convert_host", "needle_hip_analyzer_run_pcm_format", "needle_hip_library_set_sample_format",
     "needle_hip_feeder_new", "needle_hip_feeder_free", "needle_hip_feeder_feed", "needle_hip_feeder_finish",
     "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
-    "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready"]
+    "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready",
+    "needle_hip_matcher_new", "needle_hip_matcher_free", "needle_hip_matcher_feed", "needle_hip_matcher_feed_from_feeder",
+    "needle_hip_matcher_finish", "needle_hip_matcher_reset", "needle_hip_matcher_ready", "needle_hip_matcher_runs",
+    "needle_hip_matcher_open", "needle_hip_matcher_stats"]
 
 # enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
 SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
@@ -279,6 +282,17 @@ def lib():
     L.needle_hip_feeder_state_bytes.argtypes = [vp, C.POINTER(u64)]
     L.needle_hip_feeder_num_ready.argtypes = [u64, C.c_int, C.c_int, u32, b]
     L.needle_hip_feeder_num_ready.restype = sz
+    L.needle_hip_matcher_new.argtypes = [vp, sz, vp, vp, sz, sz, u32, C.POINTER(vp)]
+    L.needle_hip_matcher_free.argtypes = [vp]
+    L.needle_hip_matcher_free.restype = None
+    L.needle_hip_matcher_feed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.needle_hip_matcher_feed_from_feeder.argtypes = [vp, vp]
+    L.needle_hip_matcher_finish.argtypes = [vp, C.POINTER(sz), sz]
+    L.needle_hip_matcher_reset.argtypes = [vp, C.POINTER(sz), sz]
+    L.needle_hip_matcher_ready.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(u64), C.POINTER(b)]
+    L.needle_hip_matcher_runs.argtypes = [vp, sz, sz, sz, vp]
+    L.needle_hip_matcher_open.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz)]
+    L.needle_hip_matcher_stats.argtypes = [vp, C.POINTER(u64)]
     _LIB = L
     return L
 
@@ -782,6 +796,87 @@ class Feeder:
     def __del__(self):
         if getattr(self, "_h", None):
             lib().needle_hip_feeder_free(self._h)
+            self._h = None
+
+
+class Matcher:
+    """needle_hip_matcher_*: the streaming comparator.  `sources` (hash sequences, resident on the device from here on)
+    against `lanes` destination sequences that arrive in chunks; run lists are RUN_DTYPE arrays, `problem` = the source."""
+
+    def __init__(self, sources: Sequence[np.ndarray], min_len: Sequence[int], lanes: int, threshold: int):
+        self._h = None
+        arrs = [np.ascontiguousarray(s, dtype=np.uint32) for s in sources]
+        arena = np.concatenate(arrs) if arrs else np.zeros(0, dtype=np.uint32)
+        seqs = np.zeros((max(len(arrs), 1), 2), dtype=np.uint32)
+        seqs[:len(arrs), 1] = [a.size for a in arrs]
+        seqs[:len(arrs), 0] = np.cumsum([0] + [a.size for a in arrs])[:len(arrs)]
+        mins = np.ascontiguousarray(list(min_len) or [0], dtype=np.uint32)
+        if len(min_len) != len(arrs):
+            raise ValueError("one min_len per source")
+        h = C.c_void_p()
+        check(lib().needle_hip_matcher_new(arena.ctypes.data if arena.size else None, arena.size, seqs.ctypes.data, mins.ctypes.data,
+                                           len(arrs), lanes, threshold, C.byref(h)))
+        self._h = h
+        self.lanes, self.num_sources, self.threshold = lanes, len(arrs), threshold
+
+    def feed(self, items: Sequence) -> None:
+        """items[i]: the hashes lane i has received since the last feed, or None / an empty array for nothing."""
+        if len(items) != self.lanes:
+            raise ValueError(f"one chunk per lane: {self.lanes}, got {len(items)}")
+        keep = [None if a is None else np.ascontiguousarray(a, dtype=np.uint32) for a in items]
+        ptrs = (C.c_void_p * self.lanes)(*[None if a is None or a.size == 0 else a.ctypes.data for a in keep])
+        lens = (C.c_size_t * self.lanes)(*[0 if a is None else a.size for a in keep])
+        check(lib().needle_hip_matcher_feed(self._h, ptrs, lens))
+        del keep
+
+    def feed_from_feeder(self, feeder: "Feeder") -> None:
+        """Takes, lane by lane, the feeder's ready items this matcher has not yet taken; finishes the lanes it has finished."""
+        check(lib().needle_hip_matcher_feed_from_feeder(self._h, feeder._h))
+
+    def _lanes(self, lanes):
+        if lanes is None:
+            return None, 0
+        return (C.c_size_t * max(len(lanes), 1))(*lanes), len(lanes)
+
+    def finish(self, lanes: Optional[Sequence[int]] = None) -> None:
+        arr, k = self._lanes(lanes)
+        check(lib().needle_hip_matcher_finish(self._h, arr, k))
+
+    def reset(self, lanes: Optional[Sequence[int]] = None) -> None:
+        arr, k = self._lanes(lanes)
+        check(lib().needle_hip_matcher_reset(self._h, arr, k))
+
+    def ready(self, lane: int) -> Tuple[int, int, bool]:
+        """(runs reported, items fed, finished) of a lane."""
+        runs, fed, fin = C.c_size_t(), C.c_uint64(), C.c_bool()
+        check(lib().needle_hip_matcher_ready(self._h, lane, C.byref(runs), C.byref(fed), C.byref(fin)))
+        return runs.value, fed.value, fin.value
+
+    def runs(self, lane: int, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        if count is None:
+            count = self.ready(lane)[0] - first
+        out = np.zeros(max(count, 0), dtype=RUN_DTYPE)
+        check(lib().needle_hip_matcher_runs(self._h, lane, first, count, out.ctypes.data if count else None))
+        return out
+
+    def open(self, lane: int) -> np.ndarray:
+        """The runs still open at the last column fed whose length is already >= min_len (simhash fields zero)."""
+        ptr, n = C.c_void_p(), C.c_size_t()
+        check(lib().needle_hip_matcher_open(self._h, lane, C.byref(ptr), C.byref(n)))
+        try:
+            return np.frombuffer(C.string_at(ptr.value, n.value * RUN_DTYPE.itemsize), dtype=RUN_DTYPE).copy()
+        finally:
+            lib().needle_hip_host_free(ptr)
+
+    def stats(self) -> Tuple[int, int, int, int]:
+        """(feeds, kernel launches, cells evaluated, bytes of state on the device)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().needle_hip_matcher_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().needle_hip_matcher_free(self._h)
             self._h = None
 
 

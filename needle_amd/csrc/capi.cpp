@@ -19,6 +19,7 @@
 #include "hipctx.h"
 #include "feeder.h"
 #include "index.h"
+#include "matcher.h"
 #include "needle_core.h"
 
 using namespace needle;
@@ -36,6 +37,9 @@ struct NeedleAudioComparator {
 };
 struct NeedleHipFeeder {
   std::unique_ptr<Feeder> inner;
+};
+struct NeedleHipMatcher {
+  std::unique_ptr<Matcher> inner;
 };
 struct NeedleHipIndex {
   explicit NeedleHipIndex(const Comparator &c) : inner(c) {}
@@ -748,6 +752,94 @@ enum NeedleError needle_hip_feeder_state_bytes(const NeedleHipFeeder *feeder, ui
 
 size_t needle_hip_feeder_num_ready(uint64_t samples_per_channel_fed, int sample_rate, int channels, uint32_t step, bool finished) {
   return feeder_num_ready(samples_per_channel_fed, sample_rate, channels, step, finished);
+}
+
+// ============================================================================================================
+// Streaming comparator (matcher.hip)
+// ============================================================================================================
+enum NeedleError needle_hip_matcher_new(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *sources,
+                                        const uint32_t *min_len, size_t num_sources, size_t lanes, uint32_t threshold,
+                                        NeedleHipMatcher **output) {
+  if (!output || !sources || !min_len || (num_hashes && !hashes)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipMatcher>();
+    Status s = Matcher::Create(hashes, num_hashes, sources, min_len, num_sources, lanes, threshold, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
+void needle_hip_matcher_free(NeedleHipMatcher *matcher) { delete matcher; }
+
+enum NeedleError needle_hip_matcher_feed(NeedleHipMatcher *matcher, const uint32_t *const *items, const size_t *num_items) {
+  if (!matcher || !items || !num_items) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Feed(items, num_items);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_matcher_feed_from_feeder(NeedleHipMatcher *matcher, NeedleHipFeeder *feeder) {
+  if (!matcher || !feeder) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->FeedFromFeeder(feeder->inner.get());
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_matcher_finish(NeedleHipMatcher *matcher, const size_t *lanes, size_t k) {
+  if (!matcher) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Finish(lanes, k);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_matcher_reset(NeedleHipMatcher *matcher, const size_t *lanes, size_t k) {
+  if (!matcher) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Reset(lanes, k);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_matcher_ready(NeedleHipMatcher *matcher, size_t lane, size_t *num_runs, uint64_t *items_fed,
+                                          bool *finished) {
+  if (!matcher) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Ready(lane, num_runs, items_fed, finished);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_matcher_runs(NeedleHipMatcher *matcher, size_t lane, size_t first, size_t count, NeedleHipRun *runs) {
+  if (!matcher || (count && !runs)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Runs(lane, first, count, runs);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_matcher_open(NeedleHipMatcher *matcher, size_t lane, NeedleHipRun **runs, size_t *num_runs) {
+  if (!matcher || !runs || !num_runs) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<NeedleHipRun> out;
+    Status s = matcher->inner->Open(lane, &out);
+    if (!s.ok()) return report(s);
+    NeedleHipRun *buf = static_cast<NeedleHipRun *>(malloc(std::max<size_t>(out.size(), 1) * sizeof(NeedleHipRun)));
+    if (!buf) return report(Status::Make(NeedleError_Unknown, "out of memory"));
+    if (!out.empty()) memcpy(buf, out.data(), out.size() * sizeof(NeedleHipRun));
+    *runs = buf;
+    *num_runs = out.size();
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint64_t stats[4]) {
+  if (!matcher || !stats) return NeedleError_NullArgument;
+  matcher->inner->Stats(stats);
+  return NeedleError_Ok;
 }
 
 // ============================================================================================================

@@ -45,6 +45,10 @@ pub struct NeedleHipFeeder {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct NeedleHipMatcher {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct NeedleHipIndex {
     _private: [u8; 0],
 }
@@ -59,6 +63,14 @@ pub struct NeedleHipSearchResult {
     pub opening_end_ns: u64,
     pub ending_start_ns: u64,
     pub ending_end_ns: u64,
+}
+
+/// One sequence inside a hash arena (`NeedleHipSeq`, include/needle_hip.h).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct NeedleHipSeq {
+    pub offset: u32,
+    pub len: u32,
 }
 
 /// One matched segment of a pair (`NeedleHipRun`, include/needle_hip.h): what
@@ -355,4 +367,31 @@ extern "C" {
         step: u32,
         finished: bool,
     ) -> usize;
+    /// Streaming comparator: resident sources against lanes of hashes that arrive in chunks, run lengths on the device.
+    pub fn needle_hip_matcher_new(
+        hashes: *const u32,
+        num_hashes: usize,
+        sources: *const NeedleHipSeq,
+        min_len: *const u32,
+        num_sources: usize,
+        lanes: usize,
+        threshold: u32,
+        output: *mut *mut NeedleHipMatcher,
+    ) -> NeedleError;
+    pub fn needle_hip_matcher_free(matcher: *mut NeedleHipMatcher);
+    pub fn needle_hip_matcher_feed(matcher: *mut NeedleHipMatcher, items: *const *const u32, num_items: *const usize) -> NeedleError;
+    pub fn needle_hip_matcher_feed_from_feeder(matcher: *mut NeedleHipMatcher, feeder: *mut NeedleHipFeeder) -> NeedleError;
+    pub fn needle_hip_matcher_finish(matcher: *mut NeedleHipMatcher, lanes: *const usize, k: usize) -> NeedleError;
+    pub fn needle_hip_matcher_reset(matcher: *mut NeedleHipMatcher, lanes: *const usize, k: usize) -> NeedleError;
+    pub fn needle_hip_matcher_ready(
+        matcher: *mut NeedleHipMatcher,
+        lane: usize,
+        num_runs: *mut usize,
+        items_fed: *mut u64,
+        finished: *mut bool,
+    ) -> NeedleError;
+    pub fn needle_hip_matcher_runs(matcher: *mut NeedleHipMatcher, lane: usize, first: usize, count: usize, runs: *mut NeedleHipRun) -> NeedleError;
+    pub fn needle_hip_matcher_open(matcher: *mut NeedleHipMatcher, lane: usize, runs: *mut *mut NeedleHipRun, num_runs: *mut usize) -> NeedleError;
+    pub fn needle_hip_matcher_stats(matcher: *const NeedleHipMatcher, stats: *mut u64) -> NeedleError;
+    pub fn needle_hip_host_free(ptr: *mut c_void);
 }

@@ -542,6 +542,98 @@ impl Drop for Feeder {
     }
 }
 
+/// Streaming comparator (`needle_hip_matcher_*`): the search half of the streaming path.  The sources stay on the device;
+/// every lane is a destination sequence that arrives in chunks; a feed evaluates the cells of its new columns only.  After
+/// `finish` a lane's runs equal those of the one-shot scan over the concatenation of its chunks.
+pub struct Matcher {
+    raw: *mut ffi::NeedleHipMatcher,
+    lanes: usize,
+}
+
+unsafe impl Send for Matcher {}
+
+impl Matcher {
+    /// One `(hashes, min_len)` per source.  Fails without a HIP device: the sources are uploaded here.
+    pub fn new(sources: &[(&[u32], u32)], lanes: usize, threshold: u32) -> Result<Self> {
+        let mut arena: Vec<u32> = Vec::new();
+        let mut seqs = Vec::with_capacity(sources.len());
+        let mut min_len = Vec::with_capacity(sources.len());
+        for (hashes, min) in sources {
+            seqs.push(ffi::NeedleHipSeq { offset: arena.len() as u32, len: hashes.len() as u32 });
+            arena.extend_from_slice(hashes);
+            min_len.push(*min);
+        }
+        let mut raw = ptr::null_mut();
+        unsafe {
+            check(ffi::needle_hip_matcher_new(arena.as_ptr(), arena.len(), seqs.as_ptr(), min_len.as_ptr(), seqs.len(), lanes, threshold, &mut raw))?;
+        }
+        Ok(Matcher { raw, lanes })
+    }
+
+    /// The hashes every lane has received since the last feed: one slice per lane, an empty one for nothing.
+    pub fn feed(&mut self, items: &[&[u32]]) -> Result<()> {
+        assert_eq!(items.len(), self.lanes, "one slice per lane");
+        let ptrs: Vec<*const u32> = items.iter().map(|s| s.as_ptr()).collect();
+        let lens: Vec<usize> = items.iter().map(|s| s.len()).collect();
+        unsafe { check(ffi::needle_hip_matcher_feed(self.raw, ptrs.as_ptr(), lens.as_ptr())) }
+    }
+
+    /// Takes, lane by lane, the feeder's ready items this matcher has not yet taken, and finishes the lanes it has finished.
+    pub fn feed_from_feeder(&mut self, feeder: &mut Feeder) -> Result<()> {
+        unsafe { check(ffi::needle_hip_matcher_feed_from_feeder(self.raw, feeder.raw)) }
+    }
+
+    /// `None`: every unfinished lane.
+    pub fn finish(&mut self, lanes: Option<&[usize]>) -> Result<()> {
+        let (p, k) = lanes.map_or((ptr::null(), 0), |l| (l.as_ptr(), l.len()));
+        unsafe { check(ffi::needle_hip_matcher_finish(self.raw, p, k)) }
+    }
+
+    /// The lanes start new streams (`None`: every lane).
+    pub fn reset(&mut self, lanes: Option<&[usize]>) -> Result<()> {
+        let (p, k) = lanes.map_or((ptr::null(), 0), |l| (l.as_ptr(), l.len()));
+        unsafe { check(ffi::needle_hip_matcher_reset(self.raw, p, k)) }
+    }
+
+    /// `(runs reported, items fed, finished)` of a lane.
+    pub fn ready(&mut self, lane: usize) -> Result<(usize, u64, bool)> {
+        let (mut runs, mut fed, mut finished) = (0usize, 0u64, false);
+        unsafe { check(ffi::needle_hip_matcher_ready(self.raw, lane, &mut runs, &mut fed, &mut finished))? };
+        Ok((runs, fed, finished))
+    }
+
+    /// Runs `[first, first + count)` of a lane, in the order they were reported; `problem` is the source's index.
+    pub fn runs(&mut self, lane: usize, first: usize, count: usize) -> Result<Vec<ffi::NeedleHipRun>> {
+        let mut out = vec![ffi::NeedleHipRun::default(); count];
+        unsafe { check(ffi::needle_hip_matcher_runs(self.raw, lane, first, count, out.as_mut_ptr()))? };
+        Ok(out)
+    }
+
+    /// The runs still open at the last column fed whose length is already `>= min_len` (simhash fields zero).
+    pub fn open(&mut self, lane: usize) -> Result<Vec<ffi::NeedleHipRun>> {
+        let (mut runs, mut n) = (ptr::null_mut(), 0usize);
+        unsafe {
+            check(ffi::needle_hip_matcher_open(self.raw, lane, &mut runs, &mut n))?;
+            let out = std::slice::from_raw_parts(runs as *const ffi::NeedleHipRun, n).to_vec();
+            ffi::needle_hip_host_free(runs as *mut std::os::raw::c_void);
+            Ok(out)
+        }
+    }
+
+    /// `(feeds, kernel launches, cells evaluated, bytes of state on the device)`.
+    pub fn stats(&self) -> Result<(u64, u64, u64, u64)> {
+        let mut stats = [0u64; 4];
+        unsafe { check(ffi::needle_hip_matcher_stats(self.raw, stats.as_mut_ptr()))? };
+        Ok((stats[0], stats[1], stats[2], stats[3]))
+    }
+}
+
+impl Drop for Matcher {
+    fn drop(&mut self) {
+        unsafe { ffi::needle_hip_matcher_free(self.raw) };
+    }
+}
+
 /// An incremental search index (include/needle_hip.h "Incremental index"): `results()` equals
 /// `Comparator::run_with_frame_hashes` over the index's current list of videos (one slot per video, `None` where that call
 /// pushes no result); `add` searches only the pairs it adds, `remove` none and `replace` those of the videos replaced.  The comparator's parameters are copied at
