@@ -613,6 +613,67 @@ enum NeedleError needle_hip_matcher_open(NeedleHipMatcher *matcher, size_t lane,
  * the sources, the two sets of run lengths and the lanes' histories (4 bytes per item fed). */
 enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint64_t stats[4]);
 
+/* ---- Streaming all-pairs comparator: search a season as it is decoded ---------------------------------------
+ * In a matcher every lane is a destination and every source is complete at creation.  In a cross-matcher the lanes are
+ * matched AGAINST EACH OTHER: both sides of every pair grow, every cell is evaluated once, and the runs are there a
+ * finish round after the last lane ends.
+ *
+ * The N lanes are the N videos, in order.  Pair (a, b), a < b, is the problem (src = lane a, dst = lane b, min_len): it
+ * has the cells, matching, runs and simhashes of needle_hip_hamming_runs_host.  NeedleHipRun.problem is the pair's index
+ * in the comparator's i-major order (the order of needle_hip_comparator_run_with_frame_hashes: (0,1), (0,2), ...,
+ * (1,2), ...).  With one region, the run list therefore goes straight into needle_hip_comparator_results_from_runs; the
+ * epilogue applies the duration test, so min_len is a lower bound, as in the one-shot path.  One min_len >= 1 for the
+ * whole matcher: the lanes share one step, so the comparator's max(min_len[i], min_len[j]) is one number.
+ *
+ * When a run is reported.  Say lane a has received rows [0, Ja) and lane b columns [0, Jb).  The pair has then reported
+ * exactly those runs of its final list with
+ *     src_end < Ja - 1 && dst_end < Jb - 1      (an evaluated cell broke them).
+ * Everything still open on the pair's frontier is reported, if its length is >= min_len, in the round in which the pair
+ * becomes complete, that is when its second lane finishes.  Runs are appended to one list in the order found and never
+ * revised.  The order within a round is unspecified.
+ *
+ * Every cell is evaluated exactly once: over finished lanes of n_a and n_b items, pair (a, b) costs (n_a - 1)(n_b - 1)
+ * cells.  Between rounds a pair keeps the L-shaped frontier of its evaluated rectangle on the device (one run length per
+ * row at the last column, one per column at the last row; 2 bytes where max_items < 65 536, else 4; two sets), and every
+ * lane its hashes so far (the simhashes of a run reach back over earlier chunks on both sides).  A round -- a feed, a
+ * piece of one (at most 512 new items per lane), or a finish -- is three kernel launches, whatever the number of lanes
+ * and whichever of them have data; it uploads one lane table and the staged chunks in one copy, nothing per pair, and a
+ * pair neither of whose lanes has data costs no state traffic.  A round never writes state it reads: when it finds more
+ * runs than its device slab holds (silence against silence makes every diagonal a run) the slab grows to what was
+ * counted and the round is repeated; nothing is lost and nothing is reported twice.
+ * NEEDLE_HIP_CROSSMATCHER_RUN_SLAB=<runs> sets the initial slab (default 4096).
+ *
+ * Out of scope: `reset`, `open`, endings as a second region, several ranks, feeding the device epilogue or the index.
+ *
+ * lanes must be 2..256 (32 640 pairs: the pair index is a grid dimension).  max_items >= 2 is the capacity of every
+ * lane; state and histories are allocated at creation.  lanes or max_items out of range, min_len == 0, a feed that
+ * would take a lane past max_items, items for a finished lane, a lane index out of range, unequal lane counts in
+ * feed_from_feeder, first + count beyond the list in `runs`: InvalidArgument, checked for every lane before any device
+ * work, so a refused feed moves no lane.  NULL handles and NULL outputs: NullArgument.  Without a HIP device creation
+ * fails (there is no CPU path).  A device failure poisons the object: every later call returns it.  One thread at a
+ * time per object. */
+typedef struct NeedleHipCrossMatcher NeedleHipCrossMatcher;
+enum NeedleError needle_hip_crossmatcher_new(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold,
+                                             NeedleHipCrossMatcher **output);
+void needle_hip_crossmatcher_free(NeedleHipCrossMatcher *matcher);
+/* one entry per lane, host hashes; num_items[i] == 0: nothing for lane i */
+enum NeedleError needle_hip_crossmatcher_feed(NeedleHipCrossMatcher *matcher, const uint32_t *const *items, const size_t *num_items);
+/* As the matcher's: lane by lane (equal lane counts) the feeder's ready items beyond items_fed; finishes the lanes the
+ * feeder has finished. */
+enum NeedleError needle_hip_crossmatcher_feed_from_feeder(NeedleHipCrossMatcher *matcher, NeedleHipFeeder *feeder);
+enum NeedleError needle_hip_crossmatcher_finish(NeedleHipCrossMatcher *matcher, const size_t *lanes, size_t k); /* NULL: every unfinished lane */
+/* num_runs: the length of the list; complete: every lane is finished (the list is final) */
+enum NeedleError needle_hip_crossmatcher_ready(NeedleHipCrossMatcher *matcher, size_t *num_runs, bool *complete);
+enum NeedleError needle_hip_crossmatcher_lane(NeedleHipCrossMatcher *matcher, size_t lane, uint64_t *items_fed, bool *finished);
+enum NeedleError needle_hip_crossmatcher_runs(NeedleHipCrossMatcher *matcher, size_t first, size_t count, NeedleHipRun *runs);
+/* stats[0] feeds that carried items, stats[1] kernel launches, stats[2] cells evaluated (host arithmetic of what the
+ * kernel walks; a repeated round counts again), stats[3] bytes of device state: needle_hip_crossmatcher_state_bytes
+ * plus the run slab. */
+enum NeedleError needle_hip_crossmatcher_stats(const NeedleHipCrossMatcher *matcher, uint64_t stats[4]);
+/* pure host arithmetic, no device: pairs x 2 sets x 2 x max_items x (2 or 4) + lanes x max_items x 4 bytes
+ * (16.5 MB + 0.6 MB for 28 lanes of 5 441 items); 0 where lanes or max_items is out of range */
+size_t needle_hip_crossmatcher_state_bytes(size_t lanes, size_t max_items);
+
 #ifdef __cplusplus
 }
 #endif

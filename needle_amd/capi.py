@@ -108,7 +108,11 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready",
     "needle_hip_matcher_new", "needle_hip_matcher_free", "needle_hip_matcher_feed", "needle_hip_matcher_feed_from_feeder",
     "needle_hip_matcher_finish", "needle_hip_matcher_reset", "needle_hip_matcher_ready", "needle_hip_matcher_runs",
-    "needle_hip_matcher_open", "needle_hip_matcher_stats"]
+    "needle_hip_matcher_open", "needle_hip_matcher_stats",
+    "needle_hip_crossmatcher_new", "needle_hip_crossmatcher_free", "needle_hip_crossmatcher_feed",
+    "needle_hip_crossmatcher_feed_from_feeder", "needle_hip_crossmatcher_finish", "needle_hip_crossmatcher_ready",
+    "needle_hip_crossmatcher_lane", "needle_hip_crossmatcher_runs", "needle_hip_crossmatcher_stats",
+    "needle_hip_crossmatcher_state_bytes"]
 
 # enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
 SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
@@ -293,6 +297,18 @@ def lib():
     L.needle_hip_matcher_runs.argtypes = [vp, sz, sz, sz, vp]
     L.needle_hip_matcher_open.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz)]
     L.needle_hip_matcher_stats.argtypes = [vp, C.POINTER(u64)]
+    L.needle_hip_crossmatcher_new.argtypes = [sz, sz, u32, u32, C.POINTER(vp)]
+    L.needle_hip_crossmatcher_free.argtypes = [vp]
+    L.needle_hip_crossmatcher_free.restype = None
+    L.needle_hip_crossmatcher_feed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.needle_hip_crossmatcher_feed_from_feeder.argtypes = [vp, vp]
+    L.needle_hip_crossmatcher_finish.argtypes = [vp, C.POINTER(sz), sz]
+    L.needle_hip_crossmatcher_ready.argtypes = [vp, C.POINTER(sz), C.POINTER(b)]
+    L.needle_hip_crossmatcher_lane.argtypes = [vp, sz, C.POINTER(u64), C.POINTER(b)]
+    L.needle_hip_crossmatcher_runs.argtypes = [vp, sz, sz, vp]
+    L.needle_hip_crossmatcher_stats.argtypes = [vp, C.POINTER(u64)]
+    L.needle_hip_crossmatcher_state_bytes.argtypes = [sz, sz]
+    L.needle_hip_crossmatcher_state_bytes.restype = sz
     _LIB = L
     return L
 
@@ -877,6 +893,71 @@ class Matcher:
     def __del__(self):
         if getattr(self, "_h", None):
             lib().needle_hip_matcher_free(self._h)
+            self._h = None
+
+
+class CrossMatcher:
+    """needle_hip_crossmatcher_*: the streaming all-pairs comparator.  `lanes` sequences of at most `max_items` hashes arrive
+    in chunks and are matched against each other; the run list is one RUN_DTYPE array, `problem` = the pair's index in the
+    comparator's i-major order, so it goes straight into Comparator.results_from_runs."""
+
+    def __init__(self, lanes: int, max_items: int, min_len: int, threshold: int):
+        self._h = None
+        h = C.c_void_p()
+        check(lib().needle_hip_crossmatcher_new(lanes, max_items, min_len, threshold, C.byref(h)))
+        self._h = h
+        self.lanes, self.max_items, self.min_len, self.threshold = lanes, max_items, min_len, threshold
+
+    @staticmethod
+    def state_bytes(lanes: int, max_items: int) -> int:
+        return int(lib().needle_hip_crossmatcher_state_bytes(lanes, max_items))
+
+    def feed(self, items: Sequence) -> None:
+        """items[i]: the hashes lane i has received since the last feed, or None / an empty array for nothing."""
+        if len(items) != self.lanes:
+            raise ValueError(f"one chunk per lane: {self.lanes}, got {len(items)}")
+        keep = [None if a is None else np.ascontiguousarray(a, dtype=np.uint32) for a in items]
+        ptrs = (C.c_void_p * self.lanes)(*[None if a is None or a.size == 0 else a.ctypes.data for a in keep])
+        lens = (C.c_size_t * self.lanes)(*[0 if a is None else a.size for a in keep])
+        check(lib().needle_hip_crossmatcher_feed(self._h, ptrs, lens))
+        del keep
+
+    def feed_from_feeder(self, feeder: "Feeder") -> None:
+        """Takes, lane by lane, the feeder's ready items this matcher has not yet taken; finishes the lanes it has finished."""
+        check(lib().needle_hip_crossmatcher_feed_from_feeder(self._h, feeder._h))
+
+    def finish(self, lanes: Optional[Sequence[int]] = None) -> None:
+        arr, k = (None, 0) if lanes is None else ((C.c_size_t * max(len(lanes), 1))(*lanes), len(lanes))
+        check(lib().needle_hip_crossmatcher_finish(self._h, arr, k))
+
+    def ready(self) -> Tuple[int, bool]:
+        """(runs reported, every lane finished)"""
+        runs, complete = C.c_size_t(), C.c_bool()
+        check(lib().needle_hip_crossmatcher_ready(self._h, C.byref(runs), C.byref(complete)))
+        return runs.value, complete.value
+
+    def lane(self, lane: int) -> Tuple[int, bool]:
+        """(items fed, finished) of a lane."""
+        fed, fin = C.c_uint64(), C.c_bool()
+        check(lib().needle_hip_crossmatcher_lane(self._h, lane, C.byref(fed), C.byref(fin)))
+        return fed.value, fin.value
+
+    def runs(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        if count is None:
+            count = self.ready()[0] - first
+        out = np.zeros(max(count, 0), dtype=RUN_DTYPE)
+        check(lib().needle_hip_crossmatcher_runs(self._h, first, count, out.ctypes.data if count else None))
+        return out
+
+    def stats(self) -> Tuple[int, int, int, int]:
+        """(feeds, kernel launches, cells evaluated, bytes of state on the device)"""
+        out = (C.c_uint64 * 4)()
+        check(lib().needle_hip_crossmatcher_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().needle_hip_crossmatcher_free(self._h)
             self._h = None
 
 

@@ -15,6 +15,7 @@
 #include <fstream>
 #include <new>
 
+#include "crossmatch.h"
 #include "epilogue.h"
 #include "hipctx.h"
 #include "feeder.h"
@@ -40,6 +41,9 @@ struct NeedleHipFeeder {
 };
 struct NeedleHipMatcher {
   std::unique_ptr<Matcher> inner;
+};
+struct NeedleHipCrossMatcher {
+  std::unique_ptr<CrossMatcher> inner;
 };
 struct NeedleHipIndex {
   explicit NeedleHipIndex(const Comparator &c) : inner(c) {}
@@ -841,6 +845,79 @@ enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint6
   matcher->inner->Stats(stats);
   return NeedleError_Ok;
 }
+
+// ============================================================================================================
+// Streaming all-pairs comparator (crossmatch.hip)
+// ============================================================================================================
+enum NeedleError needle_hip_crossmatcher_new(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold,
+                                             NeedleHipCrossMatcher **output) {
+  if (!output) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipCrossMatcher>();
+    Status s = CrossMatcher::Create(lanes, max_items, min_len, threshold, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
+void needle_hip_crossmatcher_free(NeedleHipCrossMatcher *matcher) { delete matcher; }
+
+enum NeedleError needle_hip_crossmatcher_feed(NeedleHipCrossMatcher *matcher, const uint32_t *const *items, const size_t *num_items) {
+  if (!matcher || !items || !num_items) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Feed(items, num_items);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_crossmatcher_feed_from_feeder(NeedleHipCrossMatcher *matcher, NeedleHipFeeder *feeder) {
+  if (!matcher || !feeder) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->FeedFromFeeder(feeder->inner.get());
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_crossmatcher_finish(NeedleHipCrossMatcher *matcher, const size_t *lanes, size_t k) {
+  if (!matcher) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Finish(lanes, k);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_crossmatcher_ready(NeedleHipCrossMatcher *matcher, size_t *num_runs, bool *complete) {
+  if (!matcher || !num_runs || !complete) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Ready(num_runs, complete);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_crossmatcher_lane(NeedleHipCrossMatcher *matcher, size_t lane, uint64_t *items_fed, bool *finished) {
+  if (!matcher || !items_fed || !finished) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Lane(lane, items_fed, finished);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_crossmatcher_runs(NeedleHipCrossMatcher *matcher, size_t first, size_t count, NeedleHipRun *runs) {
+  if (!matcher || (count && !runs)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = matcher->inner->Runs(first, count, runs);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_crossmatcher_stats(const NeedleHipCrossMatcher *matcher, uint64_t stats[4]) {
+  if (!matcher || !stats) return NeedleError_NullArgument;
+  matcher->inner->Stats(stats);
+  return NeedleError_Ok;
+}
+
+size_t needle_hip_crossmatcher_state_bytes(size_t lanes, size_t max_items) { return CrossMatcher::StateBytes(lanes, max_items); }
 
 // ============================================================================================================
 // FrameHashes

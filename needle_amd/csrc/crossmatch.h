@@ -1,0 +1,35 @@
+// Streaming all-pairs comparator: N lanes whose hashes arrive in chunks, matched against each other; the L-shaped frontier
+// of every pair's evaluated rectangle carried in HBM between feeds (crossmatch.hip; include/needle_hip.h
+// needle_hip_crossmatcher_*).
+#pragma once
+
+#include <memory>
+
+#include "common.h"
+#include "feeder.h"
+
+namespace needle {
+
+class CrossMatcher {
+ public:
+  // Argument checks first, then the device: state and histories are allocated here, so without a device this fails.
+  static Status Create(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out);
+  ~CrossMatcher();
+  size_t lanes() const;
+  Status Feed(const uint32_t *const *items, const size_t *num_items);
+  Status FeedFromFeeder(Feeder *feeder);
+  Status Finish(const size_t *lanes, size_t k);  // nullptr: every unfinished lane
+  Status Ready(size_t *num_runs, bool *complete);
+  Status Lane(size_t lane, uint64_t *items_fed, bool *finished);
+  Status Runs(size_t first, size_t count, NeedleHipRun *runs);
+  void Stats(uint64_t stats[4]) const;  // feeds, kernel launches, cells evaluated, state bytes
+  // pairs x 2 sets x 2 (col, row) x max_items x (2 or 4) + lanes x max_items x 4; 0 where the arguments are out of range
+  static size_t StateBytes(size_t lanes, size_t max_items);
+
+ private:
+  CrossMatcher();
+  struct Impl;
+  std::unique_ptr<Impl> impl_;
+};
+
+}  // namespace needle

@@ -1,0 +1,501 @@
+// Streaming all-pairs comparator (include/needle_hip.h needle_hip_crossmatcher_*): N lanes whose hashes arrive in chunks,
+// matched against each other.  Pair (a, b), a < b, is the problem (src = lane a, dst = lane b): both of its sides grow, and
+// after any feeds its runs are those of needle_hip_hamming_runs_host over what the two lanes hold, reported as cells break them.
+//
+// State of a pair: the L-shaped frontier of its evaluated rectangle [0, Ja) x [0, Jb) -- col[i] = length of the matching
+// diagonal stretch that ends at cell (i, Jb - 1), row[j] the same at cell (Ja - 1, j) for j < Jb - 1 (the corner is col's);
+// row 0 and column 0 hold no cells, their lengths are 0 and never read.  u16 where max_items < 65 536, else u32; two sets
+// of each.  Per lane, its hashes so far (the simhashes of a run reach back over earlier chunks on both sides).
+//
+// One round (a feed, or a piece of one of at most kMaxStrip items per lane; also `finish`, with no items):
+//   land     crossmatch_land_kernel: the new chunks from the round's staging buffer to the end of their lanes' histories
+//   walk     crossmatch_walk_kernel: a thread walks a diagonal through the pair's new cells.  The "column" direction serves
+//            lane b's new columns: a diagonal that crosses column Jb - 1 at row i starts from col[i] (row 0: from 0), one
+//            that enters through row 1 at a new column starts at 0; either walks on, into lane a's new rows too, until it
+//            runs out of new columns or of rows.  The "row" direction is its transpose for lane a's new rows: from row[j]
+//            (j < Jb - 1: the corner went with col) or through column 1.  Every new cell lies on exactly one of these.  A
+//            diagonal that stops in the new last column writes its length to col, one that stops in the new last row to row.
+//            col of (a, b) flips to its other set when lane b has items, row when lane a has; a side that only gains entries
+//            (the other lane grew) appends them to its current set.  So a round never writes what it reads and can be repeated.
+//            In a finish round the pairs that become complete report what is open on their frontier instead.
+//   simhash  crossmatch_simhash_kernel: both simhashes of every run reported, one wave per run (simhash_wave.h)
+// Three launches whatever N and whichever lanes have data: nothing per pair is uploaded, a workgroup finds its pair from
+// blockIdx.y, the lanes' progress in the round's lane table and the pair's state by arithmetic; the workgroups of a pair
+// neither of whose lanes has data leave after reading two table entries.
+#include "crossmatch.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "hipctx.h"
+#include "simhash_wave.h"
+
+namespace needle {
+
+namespace {
+
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kMaxStrip = 512;      // new items of one round per lane
+constexpr uint32_t kCarriedRows = 1024;  // carried diagonals per workgroup: four per thread, one after the other
+// One direction of a pair: `side_blocks` workgroups of carried diagonals (the frontier entry they start from names them),
+// then kTopBlocks of 256 diagonals that enter through row (column) 1 at the strip's items 1 .. W - 1.
+constexpr uint32_t kTopBlocks = (kMaxStrip - 1 + kThreads - 1) / kThreads;
+constexpr uint32_t kParity = 1u;     // lane flags: the set that holds the state this lane's feeds flip
+constexpr uint32_t kFinished = 2u;   // finished before this round
+constexpr uint32_t kFinishing = 4u;  // finished by this round
+constexpr uint32_t kHeaderWords = 8;  // the slab: the run counter in word 0, the runs from byte 32
+constexpr uint32_t kHeadRuns = 127;   // runs that come down with the counter in one copy
+constexpr size_t kMaxLanes = 256;     // 32 640 pairs: the pair is a grid dimension
+
+struct CrossLane {
+  uint32_t fed, width;  // J and the new items [J, J + width)
+  uint32_t stage_off;   // of the new hashes inside the round's buffer, in words
+  uint32_t flags;
+};
+static_assert(sizeof(CrossLane) == 16, "lane table entries are 4 words");
+
+__global__ __launch_bounds__(kThreads) void crossmatch_land_kernel(const uint32_t *__restrict__ round_buf, uint32_t *__restrict__ hist,
+                                                                   uint32_t max_items, uint32_t *__restrict__ count) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *count = 0u;
+  const CrossLane ln = reinterpret_cast<const CrossLane *>(round_buf)[blockIdx.y];
+  const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
+  if (c < ln.width) hist[(uint64_t)blockIdx.y * max_items + ln.fed + c] = round_buf[ln.stage_off + c];
+}
+
+// What one direction of a pair's round works on.  X is the side the carried diagonals are numbered along, Y the side whose
+// new items [y0, y1) are the strip; kCol: X = lane a's rows, Y = lane b's columns; otherwise the transpose.
+template <typename T>
+struct CrossSide {
+  const uint32_t *xh, *yh;   // the two lanes' histories
+  uint32_t x0, x1, y0, y1;   // items before and after the round, at least 1 (item 0 is no cell)
+  uint32_t carried;          // carried diagonals: entries 0 .. carried - 1 of `from`
+  const T *from;             // frontier read, by position along X; nullptr: all zero (the other side had no cell yet)
+  T *to_last_y, *to_last_x;  // frontier written where a diagonal stops in Y's new last item (by X position) / in X's (by Y position)
+};
+
+template <typename T, bool kCol>
+__device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_t *__restrict__ rows, const CrossSide<T> &sd, uint32_t blk,
+                                           uint32_t side_blocks, bool emit_open, uint32_t pair, uint32_t a, uint32_t b, uint32_t threshold,
+                                           uint32_t min_len, NeedleHipRun *__restrict__ runs, uint32_t capacity, uint32_t *__restrict__ count) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u;
+  // The runs of one step leave the wave together: one returning atomic for all of them (matcher.hip, search.hip).  The lanes'
+  // indices travel in the simhash fields until the simhash kernel fills them.
+  auto push = [&](const bool want, const uint32_t x, const uint32_t y, const uint32_t len) {
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
+    if (mask == 0ull) return;
+    uint32_t base = 0u;
+    if (lane == 0u) base = atomicAdd(count, (uint32_t)__popcll(mask));
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (want && slot < capacity) runs[slot] = NeedleHipRun{pair, kCol ? x : y, kCol ? y : x, len, a, b};
+  };
+  const bool carried = blk < side_blocks;
+  const uint32_t t0 = blk * kCarriedRows;
+  if (emit_open) {  // no new cells, no state written: what is open on this side of the frontier
+    if (!carried || t0 >= sd.carried) return;  // (the whole workgroup)
+    for (uint32_t part = 0; part < kCarriedRows; part += kThreads) {
+      const uint32_t t = t0 + part + tid;
+      if (t - tid >= sd.carried) break;
+      const uint32_t run = t < sd.carried && t >= 1u && sd.from ? (uint32_t)sd.from[t] : 0u;
+      push(run >= min_len, t, sd.y0 - 1u, run);  // (min_len >= 1: an entry that was not read reports nothing)
+    }
+    return;
+  }
+  const uint32_t W = sd.y1 - sd.y0;
+  if (W == 0u) return;
+  // carried: the diagonals that leave frontier entries t0 ..; otherwise those that enter through X's item 1 at the strip's items q0 ..
+  const uint32_t q0 = carried ? 0u : (blk - side_blocks) * kThreads + 1u;
+  if (carried ? t0 >= sd.carried : q0 >= W) return;  // (the whole workgroup)
+  const uint32_t seg0 = carried ? t0 + 1u : 1u;       // first X item staged
+  const uint32_t steps = W - q0;                      // the most cells one of the workgroup's diagonals walks
+  {
+    const uint32_t seg_rows = min(sd.x1 - seg0, (carried ? kCarriedRows : kThreads) - 1u + steps);  // items seg0 .. <= x1 - 1
+    const uint32_t *__restrict__ src = sd.xh + seg0;
+    for (uint32_t k = tid; k < seg_rows; k += kThreads) rows[k] = src[k];
+    for (uint32_t k = tid; k < W; k += kThreads) strip[k] = sd.yh[sd.y0 + k];
+  }
+  __syncthreads();
+
+  // One diagonal per thread: first new cell (X = i0, Y = y0 + q), `rel` = i0's place in the staged items, `run` = the carried
+  // length.  It walks w cells (i0 + c, y0 + q + c).  Every thread of the workgroup comes through here together.
+  auto walk = [&](const bool live, const uint32_t i0, const uint32_t q, const uint32_t rel, uint32_t run) {
+    const uint32_t w = live ? min(W - q, sd.x1 - i0) : 0u;
+    for (uint32_t c = 0; c < steps; c++) {
+      bool ended = false;
+      uint32_t len = 0u;
+      if (c < w) {
+        const bool match = (uint32_t)__popc(rows[rel + c] ^ strip[q + c]) <= threshold;
+        ended = !match && run >= min_len;  // the run ended at the previous cell
+        len = run;
+        run = match ? run + 1u : 0u;
+      }
+      push(ended, i0 + c - 1u, sd.y0 + q + c - 1u, len);
+    }
+    if (!live) return;
+    // the last cell walked (with no cell: the frontier entry itself, which changes hands): it lies in Y's new last item or in
+    // X's last; the corner of the two belongs to col
+    const uint32_t x = i0 + w - 1u, y = sd.y0 + q + w - 1u;
+    const bool last_y = q + w == W, last_x = x == sd.x1 - 1u;
+    if (kCol ? last_y : !last_x) sd.to_last_y[x] = (T)run;
+    else sd.to_last_x[y] = (T)run;
+  };
+  if (carried) {
+    for (uint32_t part = 0; part < kCarriedRows; part += kThreads) {
+      const uint32_t t = t0 + part + tid;  // leaves frontier entry t (entry 0 is no cell: its length is 0)
+      if (t - tid >= sd.carried) break;    // (the whole workgroup)
+      const bool live = t < sd.carried;
+      const uint32_t run = live && t >= 1u && sd.from ? (uint32_t)sd.from[t] : 0u;
+      walk(live, t + 1u, 0u, part + tid, run);
+    }
+  } else {
+    const uint32_t q = q0 + tid;  // enters through X's item 1 at Y's item y0 + q
+    walk(q < W, 1u, q, 0u, 0u);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void crossmatch_walk_kernel(const uint32_t *__restrict__ hist, T *__restrict__ state,
+                                                                   const CrossLane *__restrict__ lanes, uint32_t num_lanes,
+                                                                   uint32_t max_items, uint32_t side_blocks, uint32_t threshold,
+                                                                   uint32_t min_len, NeedleHipRun *__restrict__ runs, uint32_t capacity,
+                                                                   uint32_t *__restrict__ count) {
+  __shared__ uint32_t strip[kMaxStrip];                // Y's new items
+  __shared__ uint32_t rows[kCarriedRows + kMaxStrip];  // the X items this workgroup's diagonals meet
+  // the pair of this workgroup, i-major as the comparator numbers them (pair_at in comparator.cpp): row a holds n - 1 - a pairs
+  const uint32_t pair = blockIdx.y;
+  uint32_t a = 0u, first = 0u;
+  while (pair - first >= num_lanes - 1u - a) {
+    first += num_lanes - 1u - a;
+    a++;
+  }
+  const uint32_t b = a + 1u + (pair - first);
+  const CrossLane la = lanes[a], lb = lanes[b];
+  const uint32_t done_a = la.flags & (kFinished | kFinishing), done_b = lb.flags & (kFinished | kFinishing);
+  const bool emit_open = done_a && done_b && ((la.flags | lb.flags) & kFinishing);  // the pair becomes complete in this round
+  if (la.width == 0u && lb.width == 0u && !emit_open) return;                       // no state traffic
+  const uint32_t a0 = max(la.fed, 1u), a1 = max(la.fed + la.width, 1u), b0 = max(lb.fed, 1u), b1 = max(lb.fed + lb.width, 1u);
+  if (a1 < 2u || b1 < 2u) return;  // no cells yet: whatever the sets hold is not read before it is written
+  const uint32_t per_side = side_blocks + kTopBlocks;
+  const bool col_dir = blockIdx.x < per_side;
+  T *base = state + (uint64_t)pair * 4u * max_items;  // col set 0, row set 0, col set 1, row set 1
+  const uint32_t cs = lb.flags & kParity, rs = la.flags & kParity;
+  const T *col_from = base + (uint64_t)(2u * cs) * max_items, *row_from = base + (uint64_t)(2u * rs + 1u) * max_items;
+  T *col_to = base + (uint64_t)(2u * (cs ^ (lb.width ? 1u : 0u))) * max_items;
+  T *row_to = base + (uint64_t)(2u * (rs ^ (la.width ? 1u : 0u)) + 1u) * max_items;
+  const uint32_t *ha = hist + (uint64_t)a * max_items, *hb = hist + (uint64_t)b * max_items;
+  const bool old_cells = a0 >= 2u && b0 >= 2u;
+  if (col_dir) {
+    const CrossSide<T> sd{ha, hb, a0, a1, b0, b1, a0, old_cells ? col_from : nullptr, col_to, row_to};
+    cross_walk<T, true>(strip, rows, sd, blockIdx.x, side_blocks, emit_open, pair, a, b, threshold, min_len, runs, capacity, count);
+  } else {
+    const CrossSide<T> sd{hb, ha, b0, b1, a0, a1, b0 - 1u, old_cells ? row_from : nullptr, row_to, col_to};
+    cross_walk<T, false>(strip, rows, sd, blockIdx.x - per_side, side_blocks, emit_open, pair, a, b, threshold, min_len, runs, capacity, count);
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void crossmatch_simhash_kernel(const uint32_t *__restrict__ hist, uint32_t max_items,
+                                                                      NeedleHipRun *__restrict__ runs, uint32_t capacity,
+                                                                      const uint32_t *__restrict__ count) {
+  const uint32_t total = min(*count, capacity);
+  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = (gridDim.x * blockDim.x) >> 6;
+  const uint32_t lane = threadIdx.x & 63;
+  const TransposeLane t = transpose_lane(lane);
+  for (uint32_t k = wave; k < total; k += waves) {
+    const NeedleHipRun r = runs[k];  // src_match_hash, dst_match_hash: the two lanes
+    const uint32_t src_hash = wave_simhash32(hist + (uint64_t)r.src_match_hash * max_items + (r.src_end - r.len), r.len + 1u, lane, t);
+    const uint32_t dst_hash = wave_simhash32(hist + (uint64_t)r.dst_match_hash * max_items + (r.dst_end - r.len), r.len + 1u, lane, t);
+    if (lane == 0) {
+      runs[k].src_match_hash = src_hash;
+      runs[k].dst_match_hash = dst_hash;
+    }
+  }
+}
+
+struct LaneState {
+  uint64_t fed = 0;
+  bool finished = false;
+  uint32_t parity = 0;
+};
+
+struct Piece {
+  const uint32_t *items = nullptr;
+  uint32_t width = 0;
+  bool finishing = false;
+};
+
+}  // namespace
+
+struct CrossMatcher::Impl {
+  size_t n = 0, max_items = 0;
+  uint32_t min_len = 0, threshold = 0;
+  bool narrow = true;  // u16 run lengths
+  std::vector<LaneState> lanes;
+  std::vector<NeedleHipRun> runs;
+  DeviceBuffer<uint32_t> hist, d_round, slab;
+  DeviceBuffer<uint8_t> state;
+  uint32_t capacity = 4096;  // runs the slab holds
+  PinnedStage round_stage, head_stage;
+  Status poison = Status::Ok();
+  uint64_t feeds = 0, launches = 0, cells = 0;
+
+  ~Impl() {
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    for (PinnedStage *st : {&round_stage, &head_stage}) {
+      if (st->ptr) (void)hipHostFree(st->ptr);
+      if (st->done) (void)hipEventDestroy(st->done);
+    }
+  }
+
+  size_t pairs() const { return n * (n - 1) / 2; }
+
+  // cells of all pairs when the lanes hold `fed` (+ `pieces`): sum over a < b of x_a x_b, x = max(items, 1) - 1
+  uint64_t cells_of(const std::vector<Piece> *pieces) const {
+    uint64_t sum = 0, squares = 0;
+    for (size_t i = 0; i < n; i++) {
+      const uint64_t x = std::max<uint64_t>(lanes[i].fed + (pieces ? (*pieces)[i].width : 0u), 1) - 1;
+      sum += x;
+      squares += x * x;
+    }
+    return (sum * sum - squares) / 2;
+  }
+
+  // One round over `pieces` (one per lane).
+  Status round(const std::vector<Piece> &pieces) {
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    Status s = ensure_device();
+    if (!s.ok()) return s;
+    hipStream_t stream = library_stream();
+    std::vector<CrossLane> lt(n);
+    uint64_t words = n * (sizeof(CrossLane) / 4), longest = 1;
+    for (size_t i = 0; i < n; i++) {
+      const LaneState &l = lanes[i];
+      lt[i] = CrossLane{(uint32_t)l.fed, pieces[i].width, (uint32_t)words,
+                        l.parity | (l.finished ? kFinished : 0u) | (pieces[i].finishing ? kFinishing : 0u)};
+      words += pieces[i].width;
+      longest = std::max(longest, l.fed + pieces[i].width);
+    }
+    const uint64_t round_cells = cells_of(&pieces) - cells_of(nullptr);
+    if (!(s = d_round.reserve(words)).ok() || !(s = round_stage.acquire(words * 4)).ok()) return s;
+    std::memcpy(round_stage.ptr, lt.data(), n * sizeof(CrossLane));
+    for (size_t i = 0; i < n; i++)
+      if (pieces[i].width) std::memcpy(static_cast<uint32_t *>(round_stage.ptr) + lt[i].stage_off, pieces[i].items, (size_t)pieces[i].width * 4);
+    NEEDLE_HIP_TRY(hipMemcpyAsync(d_round.ptr, round_stage.ptr, words * 4, hipMemcpyHostToDevice, stream));
+    round_stage.mark(stream);
+
+    const CrossLane *d_lanes = reinterpret_cast<const CrossLane *>(d_round.ptr);
+    const dim3 block(kThreads);
+    const uint32_t side_blocks = (uint32_t)((longest + kCarriedRows - 1) / kCarriedRows);  // of the longest lane: the others' leave at once
+    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), (uint32_t)pairs());
+    std::vector<NeedleHipRun> got;
+    for (;;) {
+      if (!(s = slab.reserve(kHeaderWords + (uint64_t)capacity * (sizeof(NeedleHipRun) / 4))).ok()) return s;
+      uint32_t *d_count = slab.ptr;
+      NeedleHipRun *d_runs = reinterpret_cast<NeedleHipRun *>(slab.ptr + kHeaderWords);
+      {
+        KernelTimer timer("crossmatch_land");
+        hipLaunchKernelGGL(crossmatch_land_kernel, dim3(kMaxStrip / kThreads, (uint32_t)n), block, 0, stream, d_round.ptr, hist.ptr,
+                           (uint32_t)max_items, d_count);
+        NEEDLE_HIP_TRY(hipGetLastError());
+      }
+      {
+        KernelTimer timer("crossmatch_walk");
+        if (narrow)
+          hipLaunchKernelGGL(crossmatch_walk_kernel<uint16_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint16_t *>(state.ptr),
+                             d_lanes, (uint32_t)n, (uint32_t)max_items, side_blocks, threshold, min_len, d_runs, capacity, d_count);
+        else
+          hipLaunchKernelGGL(crossmatch_walk_kernel<uint32_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint32_t *>(state.ptr),
+                             d_lanes, (uint32_t)n, (uint32_t)max_items, side_blocks, threshold, min_len, d_runs, capacity, d_count);
+        NEEDLE_HIP_TRY(hipGetLastError());
+      }
+      {
+        KernelTimer timer("crossmatch_simhash");
+        hipLaunchKernelGGL(crossmatch_simhash_kernel, dim3((uint32_t)device_cu_count() * 2u), block, 0, stream, hist.ptr, (uint32_t)max_items,
+                           d_runs, capacity, d_count);
+        NEEDLE_HIP_TRY(hipGetLastError());
+      }
+      launches += 3;
+      cells += round_cells;
+      // the counter and the first runs in one copy; the rest, if any, in a second one
+      const uint32_t head = std::min(capacity, kHeadRuns);
+      const size_t head_bytes = kHeaderWords * 4 + (size_t)head * sizeof(NeedleHipRun);
+      if (!(s = head_stage.acquire(head_bytes)).ok()) return s;
+      NEEDLE_HIP_TRY(hipMemcpyAsync(head_stage.ptr, slab.ptr, head_bytes, hipMemcpyDeviceToHost, stream));
+      NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+      round_stage.pending = false;
+      const uint32_t found = *static_cast<const uint32_t *>(head_stage.ptr);
+      if (found > capacity) {  // nothing is lost: a larger slab, and the round again (it wrote nothing that it reads)
+        capacity = std::max(found, capacity * 2);
+        continue;
+      }
+      got.resize(found);
+      const uint32_t first = std::min(found, head);
+      if (first) std::memcpy(got.data(), static_cast<const char *>(head_stage.ptr) + kHeaderWords * 4, (size_t)first * sizeof(NeedleHipRun));
+      if (found > first) NEEDLE_HIP_TRY(hipMemcpy(got.data() + first, d_runs + first, (size_t)(found - first) * sizeof(NeedleHipRun), hipMemcpyDeviceToHost));
+      break;
+    }
+    runs.insert(runs.end(), got.begin(), got.end());
+    for (size_t i = 0; i < n; i++) {
+      LaneState &l = lanes[i];
+      l.fed += pieces[i].width;
+      if (pieces[i].width) l.parity ^= kParity;
+      if (pieces[i].finishing) l.finished = true;
+    }
+    return Status::Ok();
+  }
+
+  Status guarded_round(const std::vector<Piece> &pieces) {
+    Status s = round(pieces);
+    if (!s.ok() && s.code != NeedleError_InvalidArgument && s.code != NeedleError_NullArgument) poison = s;
+    return s;
+  }
+};
+
+CrossMatcher::CrossMatcher() : impl_(new Impl()) {}
+CrossMatcher::~CrossMatcher() = default;
+size_t CrossMatcher::lanes() const { return impl_->n; }
+
+size_t CrossMatcher::StateBytes(size_t lanes, size_t max_items) {
+  if (lanes < 2 || lanes > kMaxLanes || max_items < 2 || max_items > 0x7FFFFFF0ull) return 0;
+  const size_t pairs = lanes * (lanes - 1) / 2;
+  return pairs * 2 * 2 * max_items * (max_items < 65536 ? sizeof(uint16_t) : sizeof(uint32_t)) + lanes * max_items * sizeof(uint32_t);
+}
+
+Status CrossMatcher::Create(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out) {
+  if (!out) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  if (lanes < 2 || lanes > kMaxLanes) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: lanes must be 2 to 256");
+  if (max_items < 2 || max_items > 0x7FFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: max_items must be 2 to 2^31 - 16");
+  if (min_len == 0) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: min_len must be >= 1");
+  std::unique_ptr<CrossMatcher> cm(new CrossMatcher());
+  Impl &m = *cm->impl_;
+  m.n = lanes;
+  m.max_items = max_items;
+  m.min_len = min_len;
+  m.threshold = threshold;
+  m.narrow = max_items < 65536;
+  m.lanes = std::vector<LaneState>(lanes);
+  if (const char *e = getenv("NEEDLE_HIP_CROSSMATCHER_RUN_SLAB")) m.capacity = (uint32_t)std::min<long long>(std::max(1ll, atoll(e)), 1ll << 26);
+
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  hipStream_t stream = library_stream();
+  const size_t hist_bytes = lanes * max_items * sizeof(uint32_t), state_bytes = StateBytes(lanes, max_items) - hist_bytes;
+  if (!(s = m.hist.reserve(lanes * max_items)).ok() || !(s = m.state.reserve(state_bytes)).ok()) return s;
+  NEEDLE_HIP_TRY(hipMemsetAsync(m.state.ptr, 0, state_bytes, stream));
+  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  *out = std::move(cm);
+  return Status::Ok();
+}
+
+Status CrossMatcher::Feed(const uint32_t *const *items, const size_t *num_items) {
+  Impl &m = *impl_;
+  if (!items || !num_items) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  if (!m.poison.ok()) return m.poison;
+  bool any = false;
+  for (size_t i = 0; i < m.n; i++) {
+    if (!num_items[i]) continue;
+    if (m.lanes[i].finished) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: the lane is finished");
+    if (!items[i]) return Status::Make(NeedleError_NullArgument, "crossmatcher: null chunk");
+    if (num_items[i] > m.max_items - m.lanes[i].fed) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: more than max_items in a lane");
+    any = true;
+  }
+  if (!any) return Status::Ok();
+  m.feeds++;
+  std::vector<size_t> done(m.n, 0);
+  for (;;) {  // a feed of more than a strip for one lane is cut into rounds
+    std::vector<Piece> pieces(m.n);
+    bool more = false;
+    for (size_t i = 0; i < m.n; i++) {
+      const size_t take = std::min<size_t>(num_items[i] - done[i], kMaxStrip);
+      if (take) pieces[i] = Piece{items[i] + done[i], (uint32_t)take, false};
+      done[i] += take;
+      more = more || done[i] < num_items[i];
+    }
+    Status s = m.guarded_round(pieces);
+    if (!s.ok() || !more) return s;
+  }
+}
+
+Status CrossMatcher::FeedFromFeeder(Feeder *feeder) {
+  Impl &m = *impl_;
+  if (!feeder) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  if (feeder->lanes() != m.n) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: the feeder has another number of lanes");
+  if (!m.poison.ok()) return m.poison;
+  std::vector<std::vector<uint32_t>> taken(m.n);
+  std::vector<const uint32_t *> ptrs(m.n, nullptr);
+  std::vector<size_t> counts(m.n, 0), finish;
+  for (size_t i = 0; i < m.n; i++) {
+    size_t kept = 0;
+    bool finished = false;
+    Status s = feeder->Ready(i, &kept, nullptr, &finished);
+    if (!s.ok()) return s;
+    const LaneState &l = m.lanes[i];
+    if (l.finished) {
+      if (kept != l.fed || !finished) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: the lane is finished");
+      continue;
+    }
+    if (kept < l.fed) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: the feeder's lane holds fewer items than the matcher has taken");
+    taken[i].resize(kept - l.fed);
+    if (!taken[i].empty() && !(s = feeder->Items(i, (size_t)l.fed, taken[i].size(), taken[i].data())).ok()) return s;
+    ptrs[i] = taken[i].data();
+    counts[i] = taken[i].size();
+    if (finished) finish.push_back(i);
+  }
+  Status s = Feed(ptrs.data(), counts.data());
+  if (!s.ok() || finish.empty()) return s;
+  return Finish(finish.data(), finish.size());
+}
+
+Status CrossMatcher::Finish(const size_t *lanes, size_t k) {
+  Impl &m = *impl_;
+  if (!m.poison.ok()) return m.poison;
+  std::vector<Piece> pieces(m.n);
+  bool any = false;
+  for (size_t j = 0; j < (lanes ? k : m.n); j++) {
+    const size_t i = lanes ? lanes[j] : j;
+    if (i >= m.n) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: lane out of range");
+    if (m.lanes[i].finished) continue;
+    pieces[i].finishing = any = true;
+  }
+  if (!any) return Status::Ok();
+  return m.guarded_round(pieces);
+}
+
+Status CrossMatcher::Ready(size_t *num_runs, bool *complete) {
+  Impl &m = *impl_;
+  if (!m.poison.ok()) return m.poison;
+  if (num_runs) *num_runs = m.runs.size();
+  if (complete) *complete = std::all_of(m.lanes.begin(), m.lanes.end(), [](const LaneState &l) { return l.finished; });
+  return Status::Ok();
+}
+
+Status CrossMatcher::Lane(size_t lane, uint64_t *items_fed, bool *finished) {
+  Impl &m = *impl_;
+  if (lane >= m.n) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: lane out of range");
+  if (!m.poison.ok()) return m.poison;
+  if (items_fed) *items_fed = m.lanes[lane].fed;
+  if (finished) *finished = m.lanes[lane].finished;
+  return Status::Ok();
+}
+
+Status CrossMatcher::Runs(size_t first, size_t count, NeedleHipRun *runs) {
+  size_t have = 0;
+  Status s = Ready(&have, nullptr);
+  if (!s.ok()) return s;
+  if (first > have || count > have - first) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: runs out of range");
+  if (count && !runs) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  if (count) std::memcpy(runs, impl_->runs.data() + first, count * sizeof(NeedleHipRun));
+  return Status::Ok();
+}
+
+void CrossMatcher::Stats(uint64_t stats[4]) const {
+  const Impl &m = *impl_;
+  stats[0] = m.feeds;
+  stats[1] = m.launches;
+  stats[2] = m.cells;
+  stats[3] = StateBytes(m.n, m.max_items) + kHeaderWords * 4 + (uint64_t)m.capacity * sizeof(NeedleHipRun);
+}
+
+}  // namespace needle

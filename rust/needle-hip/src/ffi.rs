@@ -49,6 +49,10 @@ pub struct NeedleHipMatcher {
     _private: [u8; 0],
 }
 #[repr(C)]
+pub struct NeedleHipCrossMatcher {
+    _private: [u8; 0],
+}
+#[repr(C)]
 pub struct NeedleHipIndex {
     _private: [u8; 0],
 }
@@ -393,5 +397,22 @@ extern "C" {
     pub fn needle_hip_matcher_runs(matcher: *mut NeedleHipMatcher, lane: usize, first: usize, count: usize, runs: *mut NeedleHipRun) -> NeedleError;
     pub fn needle_hip_matcher_open(matcher: *mut NeedleHipMatcher, lane: usize, runs: *mut *mut NeedleHipRun, num_runs: *mut usize) -> NeedleError;
     pub fn needle_hip_matcher_stats(matcher: *const NeedleHipMatcher, stats: *mut u64) -> NeedleError;
+
+    pub fn needle_hip_crossmatcher_new(
+        lanes: usize,
+        max_items: usize,
+        min_len: u32,
+        threshold: u32,
+        output: *mut *mut NeedleHipCrossMatcher,
+    ) -> NeedleError;
+    pub fn needle_hip_crossmatcher_free(matcher: *mut NeedleHipCrossMatcher);
+    pub fn needle_hip_crossmatcher_feed(matcher: *mut NeedleHipCrossMatcher, items: *const *const u32, num_items: *const usize) -> NeedleError;
+    pub fn needle_hip_crossmatcher_feed_from_feeder(matcher: *mut NeedleHipCrossMatcher, feeder: *mut NeedleHipFeeder) -> NeedleError;
+    pub fn needle_hip_crossmatcher_finish(matcher: *mut NeedleHipCrossMatcher, lanes: *const usize, k: usize) -> NeedleError;
+    pub fn needle_hip_crossmatcher_ready(matcher: *mut NeedleHipCrossMatcher, num_runs: *mut usize, complete: *mut bool) -> NeedleError;
+    pub fn needle_hip_crossmatcher_lane(matcher: *mut NeedleHipCrossMatcher, lane: usize, items_fed: *mut u64, finished: *mut bool) -> NeedleError;
+    pub fn needle_hip_crossmatcher_runs(matcher: *mut NeedleHipCrossMatcher, first: usize, count: usize, runs: *mut NeedleHipRun) -> NeedleError;
+    pub fn needle_hip_crossmatcher_stats(matcher: *const NeedleHipCrossMatcher, stats: *mut u64) -> NeedleError;
+    pub fn needle_hip_crossmatcher_state_bytes(lanes: usize, max_items: usize) -> usize;
     pub fn needle_hip_host_free(ptr: *mut c_void);
 }

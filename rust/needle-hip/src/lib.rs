@@ -634,6 +634,83 @@ impl Drop for Matcher {
     }
 }
 
+/// Streaming all-pairs comparator (`needle_hip_crossmatcher_*`): the lanes are the videos of a season, matched against each
+/// other as their hashes arrive.  `problem` of a run is the pair's index in the comparator's i-major order, so the list goes
+/// straight into the host epilogue.  After every lane is finished the runs equal the one-shot scan's over all pairs.
+pub struct CrossMatcher {
+    raw: *mut ffi::NeedleHipCrossMatcher,
+    lanes: usize,
+}
+
+unsafe impl Send for CrossMatcher {}
+
+impl CrossMatcher {
+    /// `lanes` in 2..=256, every lane holds at most `max_items`.  Fails without a HIP device: the state is allocated here.
+    pub fn new(lanes: usize, max_items: usize, min_len: u32, threshold: u32) -> Result<Self> {
+        let mut raw = ptr::null_mut();
+        unsafe { check(ffi::needle_hip_crossmatcher_new(lanes, max_items, min_len, threshold, &mut raw))? };
+        Ok(CrossMatcher { raw, lanes })
+    }
+
+    /// Bytes of device state such a matcher allocates (pure host arithmetic).
+    pub fn state_bytes(lanes: usize, max_items: usize) -> usize {
+        unsafe { ffi::needle_hip_crossmatcher_state_bytes(lanes, max_items) }
+    }
+
+    /// The hashes every lane has received since the last feed: one slice per lane, an empty one for nothing.
+    pub fn feed(&mut self, items: &[&[u32]]) -> Result<()> {
+        assert_eq!(items.len(), self.lanes, "one slice per lane");
+        let ptrs: Vec<*const u32> = items.iter().map(|s| s.as_ptr()).collect();
+        let lens: Vec<usize> = items.iter().map(|s| s.len()).collect();
+        unsafe { check(ffi::needle_hip_crossmatcher_feed(self.raw, ptrs.as_ptr(), lens.as_ptr())) }
+    }
+
+    /// Takes, lane by lane, the feeder's ready items this matcher has not yet taken, and finishes the lanes it has finished.
+    pub fn feed_from_feeder(&mut self, feeder: &mut Feeder) -> Result<()> {
+        unsafe { check(ffi::needle_hip_crossmatcher_feed_from_feeder(self.raw, feeder.raw)) }
+    }
+
+    /// `None`: every unfinished lane.
+    pub fn finish(&mut self, lanes: Option<&[usize]>) -> Result<()> {
+        let (p, k) = lanes.map_or((ptr::null(), 0), |l| (l.as_ptr(), l.len()));
+        unsafe { check(ffi::needle_hip_crossmatcher_finish(self.raw, p, k)) }
+    }
+
+    /// `(runs reported, every lane finished)`.
+    pub fn ready(&mut self) -> Result<(usize, bool)> {
+        let (mut runs, mut complete) = (0usize, false);
+        unsafe { check(ffi::needle_hip_crossmatcher_ready(self.raw, &mut runs, &mut complete))? };
+        Ok((runs, complete))
+    }
+
+    /// `(items fed, finished)` of a lane.
+    pub fn lane(&mut self, lane: usize) -> Result<(u64, bool)> {
+        let (mut fed, mut finished) = (0u64, false);
+        unsafe { check(ffi::needle_hip_crossmatcher_lane(self.raw, lane, &mut fed, &mut finished))? };
+        Ok((fed, finished))
+    }
+
+    /// Runs `[first, first + count)` of the list, in the order they were reported.
+    pub fn runs(&mut self, first: usize, count: usize) -> Result<Vec<ffi::NeedleHipRun>> {
+        let mut out = vec![ffi::NeedleHipRun::default(); count];
+        unsafe { check(ffi::needle_hip_crossmatcher_runs(self.raw, first, count, out.as_mut_ptr()))? };
+        Ok(out)
+    }
+
+    /// `(feeds, kernel launches, cells evaluated, bytes of state on the device)`.
+    pub fn stats(&self) -> Result<(u64, u64, u64, u64)> {
+        let mut stats = [0u64; 4];
+        unsafe { check(ffi::needle_hip_crossmatcher_stats(self.raw, stats.as_mut_ptr()))? };
+        Ok((stats[0], stats[1], stats[2], stats[3]))
+    }
+}
+
+impl Drop for CrossMatcher {
+    fn drop(&mut self) {
+        unsafe { ffi::needle_hip_crossmatcher_free(self.raw) };
+    }
+}
+
 /// An incremental search index (include/needle_hip.h "Incremental index"): `results()` equals
 /// `Comparator::run_with_frame_hashes` over the index's current list of videos (one slot per video, `None` where that call
 /// pushes no result); `add` searches only the pairs it adds, `remove` none and `replace` those of the videos replaced.  The comparator's parameters are copied at
