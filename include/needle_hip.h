@@ -643,10 +643,25 @@ enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint6
  * counted and the round is repeated; nothing is lost and nothing is reported twice.
  * NEEDLE_HIP_CROSSMATCHER_RUN_SLAB=<runs> sets the initial slab (default 4096).
  *
- * Out of scope: `reset`, `open`, endings as a second region, several ranks, feeding the device epilogue or the index.
+ * Regions: openings and endings in one object (needle_hip_crossmatcher_new_regions).  The lanes are videos x regions,
+ * regions = 1 or 2, lane = video * regions + region -- the numbering of the library's arena rows and of the comparator's
+ * sequences with include_endings, and of needle_hip_feeder_frame_hashes(f, 2v, 2v + 1, ...).  Only lanes of one region
+ * are matched against each other: the problem of pair (a, b) and region r is (src = lane a * R + r, dst = lane b * R + r,
+ * min_len[r]) and NeedleHipRun.problem = pair * regions + r, so the complete list goes unchanged into
+ * needle_hip_comparator_results_from_runs of a comparator with include_endings.  Every region has a capacity
+ * max_items[r] and a min_len[r] of its own (the ending window is half the opening window); the entries of the state are
+ * 2 bytes where every region's max_items is below 65 536, else 4, for the whole object.  Everything above holds per
+ * (pair, region): the frontier of (a, b, r) is reported in the round in which the second of lanes a * R + r and
+ * b * R + r finishes, whatever the other region does; a round is still three launches, one upload and one download.
+ * needle_hip_crossmatcher_new is the regions = 1 case.  feed, finish, lane, ready, runs and stats work over the
+ * videos * regions lanes: the arrays of feed have one entry per lane, feed_from_feeder wants a feeder of
+ * videos * regions lanes, `complete` means every lane of every region is finished, stats[2] sums over regions and pairs.
  *
- * lanes must be 2..256 (32 640 pairs: the pair index is a grid dimension).  max_items >= 2 is the capacity of every
- * lane; state and histories are allocated at creation.  lanes or max_items out of range, min_len == 0, a feed that
+ * Out of scope: `reset`, `open`, more than two regions, several ranks, feeding the device epilogue or the index.
+ *
+ * lanes (videos) must be 2..256 (32 640 pairs: pair * regions + region is a grid dimension).  max_items >= 2 is the
+ * capacity of every lane (of the region); state and histories are allocated at creation.  lanes, regions or max_items
+ * out of range, min_len == 0, a feed that
  * would take a lane past max_items, items for a finished lane, a lane index out of range, unequal lane counts in
  * feed_from_feeder, first + count beyond the list in `runs`: InvalidArgument, checked for every lane before any device
  * work, so a refused feed moves no lane.  NULL handles and NULL outputs: NullArgument.  Without a HIP device creation
@@ -655,6 +670,9 @@ enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint6
 typedef struct NeedleHipCrossMatcher NeedleHipCrossMatcher;
 enum NeedleError needle_hip_crossmatcher_new(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold,
                                              NeedleHipCrossMatcher **output);
+/* videos 2..256, regions 1..2; max_items[r] >= 2, min_len[r] >= 1 per region */
+enum NeedleError needle_hip_crossmatcher_new_regions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len,
+                                                     uint32_t threshold, NeedleHipCrossMatcher **output);
 void needle_hip_crossmatcher_free(NeedleHipCrossMatcher *matcher);
 /* one entry per lane, host hashes; num_items[i] == 0: nothing for lane i */
 enum NeedleError needle_hip_crossmatcher_feed(NeedleHipCrossMatcher *matcher, const uint32_t *const *items, const size_t *num_items);
@@ -673,6 +691,11 @@ enum NeedleError needle_hip_crossmatcher_stats(const NeedleHipCrossMatcher *matc
 /* pure host arithmetic, no device: pairs x 2 sets x 2 x max_items x (2 or 4) + lanes x max_items x 4 bytes
  * (16.5 MB + 0.6 MB for 28 lanes of 5 441 items); 0 where lanes or max_items is out of range */
 size_t needle_hip_crossmatcher_state_bytes(size_t lanes, size_t max_items);
+/* the sum over the regions of pairs x 2 sets x 2 x max_items[r] x w + videos x max_items[r] x 4 bytes, w = 2 where every
+ * max_items[r] < 65 536, else 4; 0 where an argument is out of range; regions = 1: needle_hip_crossmatcher_state_bytes */
+size_t needle_hip_crossmatcher_state_bytes_regions(size_t videos, size_t regions, const size_t *max_items);
+/* what the object was created with (regions = 1 for needle_hip_crossmatcher_new); it has videos * regions lanes */
+enum NeedleError needle_hip_crossmatcher_shape(const NeedleHipCrossMatcher *matcher, size_t *videos, size_t *regions);
 
 #ifdef __cplusplus
 }

@@ -112,7 +112,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_crossmatcher_new", "needle_hip_crossmatcher_free", "needle_hip_crossmatcher_feed",
     "needle_hip_crossmatcher_feed_from_feeder", "needle_hip_crossmatcher_finish", "needle_hip_crossmatcher_ready",
     "needle_hip_crossmatcher_lane", "needle_hip_crossmatcher_runs", "needle_hip_crossmatcher_stats",
-    "needle_hip_crossmatcher_state_bytes"]
+    "needle_hip_crossmatcher_state_bytes", "needle_hip_crossmatcher_new_regions",
+    "needle_hip_crossmatcher_state_bytes_regions", "needle_hip_crossmatcher_shape"]
 
 # enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
 SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
@@ -309,6 +310,10 @@ def lib():
     L.needle_hip_crossmatcher_stats.argtypes = [vp, C.POINTER(u64)]
     L.needle_hip_crossmatcher_state_bytes.argtypes = [sz, sz]
     L.needle_hip_crossmatcher_state_bytes.restype = sz
+    L.needle_hip_crossmatcher_new_regions.argtypes = [sz, sz, C.POINTER(sz), C.POINTER(u32), u32, C.POINTER(vp)]
+    L.needle_hip_crossmatcher_state_bytes_regions.argtypes = [sz, sz, C.POINTER(sz)]
+    L.needle_hip_crossmatcher_state_bytes_regions.restype = sz
+    L.needle_hip_crossmatcher_shape.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
     _LIB = L
     return L
 
@@ -899,7 +904,8 @@ class Matcher:
 class CrossMatcher:
     """needle_hip_crossmatcher_*: the streaming all-pairs comparator.  `lanes` sequences of at most `max_items` hashes arrive
     in chunks and are matched against each other; the run list is one RUN_DTYPE array, `problem` = the pair's index in the
-    comparator's i-major order, so it goes straight into Comparator.results_from_runs."""
+    comparator's i-major order, so it goes straight into Comparator.results_from_runs.  `with_regions`: openings and endings
+    in one object, lane = video * regions + region, `problem` = pair * regions + region."""
 
     def __init__(self, lanes: int, max_items: int, min_len: int, threshold: int):
         self._h = None
@@ -908,9 +914,34 @@ class CrossMatcher:
         self._h = h
         self.lanes, self.max_items, self.min_len, self.threshold = lanes, max_items, min_len, threshold
 
+    @classmethod
+    def with_regions(cls, videos: int, max_items: Sequence[int], min_len: Sequence[int], threshold: int) -> "CrossMatcher":
+        """`videos * len(max_items)` lanes; max_items[r] and min_len[r] are region r's capacity and shortest run."""
+        if len(max_items) != len(min_len):
+            raise ValueError(f"one max_items and one min_len per region: {len(max_items)} and {len(min_len)}")
+        regions = len(max_items)
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().needle_hip_crossmatcher_new_regions(videos, regions, (C.c_size_t * max(regions, 1))(*max_items),
+                                                        (C.c_uint32 * max(regions, 1))(*min_len), threshold, C.byref(h)))
+        self._h = h
+        self.lanes, self.max_items, self.min_len, self.threshold = videos * regions, tuple(max_items), tuple(min_len), threshold
+        return self
+
+    def shape(self) -> Tuple[int, int]:
+        """(videos, regions): the object has videos * regions lanes."""
+        videos, regions = C.c_size_t(), C.c_size_t()
+        check(lib().needle_hip_crossmatcher_shape(self._h, C.byref(videos), C.byref(regions)))
+        return videos.value, regions.value
+
     @staticmethod
-    def state_bytes(lanes: int, max_items: int) -> int:
-        return int(lib().needle_hip_crossmatcher_state_bytes(lanes, max_items))
+    def state_bytes(lanes: int, max_items) -> int:
+        """`max_items`: one capacity, or one per region (`lanes` is then the number of videos)."""
+        if isinstance(max_items, (int, np.integer)):
+            return int(lib().needle_hip_crossmatcher_state_bytes(lanes, max_items))
+        regions = len(max_items)
+        return int(lib().needle_hip_crossmatcher_state_bytes_regions(lanes, regions, (C.c_size_t * max(regions, 1))(*max_items)))
 
     def feed(self, items: Sequence) -> None:
         """items[i]: the hashes lane i has received since the last feed, or None / an empty array for nothing."""

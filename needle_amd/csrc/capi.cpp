@@ -861,6 +861,18 @@ enum NeedleError needle_hip_crossmatcher_new(size_t lanes, size_t max_items, uin
   });
 }
 
+enum NeedleError needle_hip_crossmatcher_new_regions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len,
+                                                     uint32_t threshold, NeedleHipCrossMatcher **output) {
+  if (!output || !max_items || !min_len) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipCrossMatcher>();
+    Status s = CrossMatcher::CreateRegions(videos, regions, max_items, min_len, threshold, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
 void needle_hip_crossmatcher_free(NeedleHipCrossMatcher *matcher) { delete matcher; }
 
 enum NeedleError needle_hip_crossmatcher_feed(NeedleHipCrossMatcher *matcher, const uint32_t *const *items, const size_t *num_items) {
@@ -918,6 +930,17 @@ enum NeedleError needle_hip_crossmatcher_stats(const NeedleHipCrossMatcher *matc
 }
 
 size_t needle_hip_crossmatcher_state_bytes(size_t lanes, size_t max_items) { return CrossMatcher::StateBytes(lanes, max_items); }
+
+size_t needle_hip_crossmatcher_state_bytes_regions(size_t videos, size_t regions, const size_t *max_items) {
+  return CrossMatcher::StateBytesRegions(videos, regions, max_items);
+}
+
+enum NeedleError needle_hip_crossmatcher_shape(const NeedleHipCrossMatcher *matcher, size_t *videos, size_t *regions) {
+  if (!matcher || !videos || !regions) return NeedleError_NullArgument;
+  *videos = matcher->inner->videos();
+  *regions = matcher->inner->regions();
+  return NeedleError_Ok;
+}
 
 // ============================================================================================================
 // FrameHashes

@@ -1,6 +1,7 @@
 // Streaming all-pairs comparator: N lanes whose hashes arrive in chunks, matched against each other; the L-shaped frontier
 // of every pair's evaluated rectangle carried in HBM between feeds (crossmatch.hip; include/needle_hip.h
-// needle_hip_crossmatcher_*).
+// needle_hip_crossmatcher_*).  With regions the lanes are videos x regions (lane = video * regions + region: openings and
+// endings), matched within a region only, each region with its own capacity and min_len.
 #pragma once
 
 #include <memory>
@@ -14,8 +15,13 @@ class CrossMatcher {
  public:
   // Argument checks first, then the device: state and histories are allocated here, so without a device this fails.
   static Status Create(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out);
+  // regions 1 or 2; max_items and min_len hold one entry per region.  Create is the one-region case.
+  static Status CreateRegions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                              std::unique_ptr<CrossMatcher> *out);
   ~CrossMatcher();
-  size_t lanes() const;
+  size_t lanes() const;  // videos * regions
+  size_t videos() const;
+  size_t regions() const;
   Status Feed(const uint32_t *const *items, const size_t *num_items);
   Status FeedFromFeeder(Feeder *feeder);
   Status Finish(const size_t *lanes, size_t k);  // nullptr: every unfinished lane
@@ -25,6 +31,8 @@ class CrossMatcher {
   void Stats(uint64_t stats[4]) const;  // feeds, kernel launches, cells evaluated, state bytes
   // pairs x 2 sets x 2 (col, row) x max_items x (2 or 4) + lanes x max_items x 4; 0 where the arguments are out of range
   static size_t StateBytes(size_t lanes, size_t max_items);
+  // the sum of that over the regions, with one entry width: 2 where every region's max_items < 65 536, else 4
+  static size_t StateBytesRegions(size_t videos, size_t regions, const size_t *max_items);
 
  private:
   CrossMatcher();

@@ -22,6 +22,14 @@
 // Three launches whatever N and whichever lanes have data: nothing per pair is uploaded, a workgroup finds its pair from
 // blockIdx.y, the lanes' progress in the round's lane table and the pair's state by arithmetic; the workgroups of a pair
 // neither of whose lanes has data leave after reading two table entries.
+//
+// Regions (needle_hip_crossmatcher_new_regions): the lanes are videos x R, lane = video * R + region (R = 1 or 2: openings
+// and endings, the numbering of the library's arena rows and of comparator.cpp's seqs), and only lanes of one region are
+// matched against each other.  blockIdx.y of the walk is pair * R + region, which is also NeedleHipRun.problem; the
+// workgroup reads lane-table entries a * R + r and b * R + r.  The regions have capacities and min_len of their own: the
+// histories (videos x max_items[r] words) and the frontiers (pairs x 4 x max_items[r] entries) lie region after region,
+// and a region's max_items, min_len and two bases travel by value in the kernels' arguments (CrossRegions).  Still three
+// launches, one upload and one download per round; R = 1 is the same code with the second region's fields unused.
 #include "crossmatch.h"
 
 #include <algorithm>
@@ -47,7 +55,8 @@ constexpr uint32_t kFinished = 2u;   // finished before this round
 constexpr uint32_t kFinishing = 4u;  // finished by this round
 constexpr uint32_t kHeaderWords = 8;  // the slab: the run counter in word 0, the runs from byte 32
 constexpr uint32_t kHeadRuns = 127;   // runs that come down with the counter in one copy
-constexpr size_t kMaxLanes = 256;     // 32 640 pairs: the pair is a grid dimension
+constexpr size_t kMaxLanes = 256;     // videos: 32 640 pairs, and pair * regions + region is a grid dimension (65 280 <= 65 535)
+constexpr size_t kMaxRegions = 2;
 
 struct CrossLane {
   uint32_t fed, width;  // J and the new items [J, J + width)
@@ -56,12 +65,30 @@ struct CrossLane {
 };
 static_assert(sizeof(CrossLane) == 16, "lane table entries are 4 words");
 
+// What the kernels know of the regions, by value: nothing per region is uploaded in a round.  Named fields and selects,
+// not arrays: an array indexed at run time can end up in scratch.
+struct CrossRegions {
+  uint32_t regions;                  // 1 or 2
+  uint32_t max_items0, max_items1;   // capacity of a lane
+  uint32_t min_len0, min_len1;
+  uint64_t hist0, hist1;             // first word of the region's histories: row `video` is max_items words
+  uint64_t state0, state1;           // first entry of the region's frontiers: pair p's four sets are 4 * max_items entries
+};
+
+__device__ __forceinline__ uint32_t region_max_items(const CrossRegions &rg, uint32_t r) { return r ? rg.max_items1 : rg.max_items0; }
+
+// the history row of lane `lane` = video * regions + region
+__device__ __forceinline__ uint64_t lane_row(const CrossRegions &rg, uint32_t lane) {
+  const uint32_t r = rg.regions == 2u ? lane & 1u : 0u, video = rg.regions == 2u ? lane >> 1 : lane;
+  return (r ? rg.hist1 : rg.hist0) + (uint64_t)video * region_max_items(rg, r);
+}
+
 __global__ __launch_bounds__(kThreads) void crossmatch_land_kernel(const uint32_t *__restrict__ round_buf, uint32_t *__restrict__ hist,
-                                                                   uint32_t max_items, uint32_t *__restrict__ count) {
+                                                                   CrossRegions rg, uint32_t *__restrict__ count) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *count = 0u;
   const CrossLane ln = reinterpret_cast<const CrossLane *>(round_buf)[blockIdx.y];
   const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-  if (c < ln.width) hist[(uint64_t)blockIdx.y * max_items + ln.fed + c] = round_buf[ln.stage_off + c];
+  if (c < ln.width) hist[lane_row(rg, blockIdx.y) + ln.fed + c] = round_buf[ln.stage_off + c];
 }
 
 // What one direction of a pair's round works on.  X is the side the carried diagonals are numbered along, Y the side whose
@@ -77,11 +104,11 @@ struct CrossSide {
 
 template <typename T, bool kCol>
 __device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_t *__restrict__ rows, const CrossSide<T> &sd, uint32_t blk,
-                                           uint32_t side_blocks, bool emit_open, uint32_t pair, uint32_t a, uint32_t b, uint32_t threshold,
+                                           uint32_t side_blocks, bool emit_open, uint32_t problem, uint32_t a, uint32_t b, uint32_t threshold,
                                            uint32_t min_len, NeedleHipRun *__restrict__ runs, uint32_t capacity, uint32_t *__restrict__ count) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
   // The runs of one step leave the wave together: one returning atomic for all of them (matcher.hip, search.hip).  The lanes'
-  // indices travel in the simhash fields until the simhash kernel fills them.
+  // indices (a, b: video * regions + region) travel in the simhash fields until the simhash kernel fills them.
   auto push = [&](const bool want, const uint32_t x, const uint32_t y, const uint32_t len) {
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
     if (mask == 0ull) return;
@@ -89,7 +116,7 @@ __device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_
     if (lane == 0u) base = atomicAdd(count, (uint32_t)__popcll(mask));
     base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
     const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-    if (want && slot < capacity) runs[slot] = NeedleHipRun{pair, kCol ? x : y, kCol ? y : x, len, a, b};
+    if (want && slot < capacity) runs[slot] = NeedleHipRun{problem, kCol ? x : y, kCol ? y : x, len, a, b};
   };
   const bool carried = blk < side_blocks;
   const uint32_t t0 = blk * kCarriedRows;
@@ -157,45 +184,51 @@ __device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void crossmatch_walk_kernel(const uint32_t *__restrict__ hist, T *__restrict__ state,
-                                                                   const CrossLane *__restrict__ lanes, uint32_t num_lanes,
-                                                                   uint32_t max_items, uint32_t side_blocks, uint32_t threshold,
-                                                                   uint32_t min_len, NeedleHipRun *__restrict__ runs, uint32_t capacity,
+                                                                   const CrossLane *__restrict__ lanes, uint32_t videos, CrossRegions rg,
+                                                                   uint32_t side_blocks, uint32_t threshold,
+                                                                   NeedleHipRun *__restrict__ runs, uint32_t capacity,
                                                                    uint32_t *__restrict__ count) {
   __shared__ uint32_t strip[kMaxStrip];                // Y's new items
   __shared__ uint32_t rows[kCarriedRows + kMaxStrip];  // the X items this workgroup's diagonals meet
-  // the pair of this workgroup, i-major as the comparator numbers them (pair_at in comparator.cpp): row a holds n - 1 - a pairs
-  const uint32_t pair = blockIdx.y;
+  // the problem of this workgroup: pair * regions + region, the pair i-major as the comparator numbers them (pair_at in
+  // comparator.cpp): row a holds n - 1 - a pairs
+  const uint32_t problem = blockIdx.y;
+  const bool two = rg.regions == 2u;
+  const uint32_t pair = two ? problem >> 1 : problem, r = two ? problem & 1u : 0u;
   uint32_t a = 0u, first = 0u;
-  while (pair - first >= num_lanes - 1u - a) {
-    first += num_lanes - 1u - a;
+  while (pair - first >= videos - 1u - a) {
+    first += videos - 1u - a;
     a++;
   }
   const uint32_t b = a + 1u + (pair - first);
-  const CrossLane la = lanes[a], lb = lanes[b];
+  const uint32_t lane_a = two ? 2u * a + r : a, lane_b = two ? 2u * b + r : b;
+  const CrossLane la = lanes[lane_a], lb = lanes[lane_b];
   const uint32_t done_a = la.flags & (kFinished | kFinishing), done_b = lb.flags & (kFinished | kFinishing);
-  const bool emit_open = done_a && done_b && ((la.flags | lb.flags) & kFinishing);  // the pair becomes complete in this round
+  const bool emit_open = done_a && done_b && ((la.flags | lb.flags) & kFinishing);  // the problem becomes complete in this round
   if (la.width == 0u && lb.width == 0u && !emit_open) return;                       // no state traffic
   const uint32_t a0 = max(la.fed, 1u), a1 = max(la.fed + la.width, 1u), b0 = max(lb.fed, 1u), b1 = max(lb.fed + lb.width, 1u);
   if (a1 < 2u || b1 < 2u) return;  // no cells yet: whatever the sets hold is not read before it is written
   const uint32_t per_side = side_blocks + kTopBlocks;
   const bool col_dir = blockIdx.x < per_side;
-  T *base = state + (uint64_t)pair * 4u * max_items;  // col set 0, row set 0, col set 1, row set 1
+  const uint32_t max_items = region_max_items(rg, r), min_len = r ? rg.min_len1 : rg.min_len0;
+  T *base = state + (r ? rg.state1 : rg.state0) + (uint64_t)pair * 4u * max_items;  // col set 0, row set 0, col set 1, row set 1
   const uint32_t cs = lb.flags & kParity, rs = la.flags & kParity;
   const T *col_from = base + (uint64_t)(2u * cs) * max_items, *row_from = base + (uint64_t)(2u * rs + 1u) * max_items;
   T *col_to = base + (uint64_t)(2u * (cs ^ (lb.width ? 1u : 0u))) * max_items;
   T *row_to = base + (uint64_t)(2u * (rs ^ (la.width ? 1u : 0u)) + 1u) * max_items;
-  const uint32_t *ha = hist + (uint64_t)a * max_items, *hb = hist + (uint64_t)b * max_items;
+  const uint32_t *region_hist = hist + (r ? rg.hist1 : rg.hist0);
+  const uint32_t *ha = region_hist + (uint64_t)a * max_items, *hb = region_hist + (uint64_t)b * max_items;
   const bool old_cells = a0 >= 2u && b0 >= 2u;
   if (col_dir) {
     const CrossSide<T> sd{ha, hb, a0, a1, b0, b1, a0, old_cells ? col_from : nullptr, col_to, row_to};
-    cross_walk<T, true>(strip, rows, sd, blockIdx.x, side_blocks, emit_open, pair, a, b, threshold, min_len, runs, capacity, count);
+    cross_walk<T, true>(strip, rows, sd, blockIdx.x, side_blocks, emit_open, problem, lane_a, lane_b, threshold, min_len, runs, capacity, count);
   } else {
     const CrossSide<T> sd{hb, ha, b0, b1, a0, a1, b0 - 1u, old_cells ? row_from : nullptr, row_to, col_to};
-    cross_walk<T, false>(strip, rows, sd, blockIdx.x - per_side, side_blocks, emit_open, pair, a, b, threshold, min_len, runs, capacity, count);
+    cross_walk<T, false>(strip, rows, sd, blockIdx.x - per_side, side_blocks, emit_open, problem, lane_a, lane_b, threshold, min_len, runs, capacity, count);
   }
 }
 
-__global__ __launch_bounds__(kThreads) void crossmatch_simhash_kernel(const uint32_t *__restrict__ hist, uint32_t max_items,
+__global__ __launch_bounds__(kThreads) void crossmatch_simhash_kernel(const uint32_t *__restrict__ hist, CrossRegions rg,
                                                                       NeedleHipRun *__restrict__ runs, uint32_t capacity,
                                                                       const uint32_t *__restrict__ count) {
   const uint32_t total = min(*count, capacity);
@@ -204,8 +237,8 @@ __global__ __launch_bounds__(kThreads) void crossmatch_simhash_kernel(const uint
   const TransposeLane t = transpose_lane(lane);
   for (uint32_t k = wave; k < total; k += waves) {
     const NeedleHipRun r = runs[k];  // src_match_hash, dst_match_hash: the two lanes
-    const uint32_t src_hash = wave_simhash32(hist + (uint64_t)r.src_match_hash * max_items + (r.src_end - r.len), r.len + 1u, lane, t);
-    const uint32_t dst_hash = wave_simhash32(hist + (uint64_t)r.dst_match_hash * max_items + (r.dst_end - r.len), r.len + 1u, lane, t);
+    const uint32_t src_hash = wave_simhash32(hist + lane_row(rg, r.src_match_hash) + (r.src_end - r.len), r.len + 1u, lane, t);
+    const uint32_t dst_hash = wave_simhash32(hist + lane_row(rg, r.dst_match_hash) + (r.dst_end - r.len), r.len + 1u, lane, t);
     if (lane == 0) {
       runs[k].src_match_hash = src_hash;
       runs[k].dst_match_hash = dst_hash;
@@ -228,9 +261,11 @@ struct Piece {
 }  // namespace
 
 struct CrossMatcher::Impl {
-  size_t n = 0, max_items = 0;
-  uint32_t min_len = 0, threshold = 0;
-  bool narrow = true;  // u16 run lengths
+  size_t n = 0, videos = 0, regions = 1;  // n = videos * regions lanes; lane = video * regions + region
+  size_t max_items[2] = {0, 0};
+  uint32_t min_len[2] = {0, 0}, threshold = 0;
+  bool narrow = true;  // u16 run lengths: one width for every region
+  CrossRegions rg{};
   std::vector<LaneState> lanes;
   std::vector<NeedleHipRun> runs;
   DeviceBuffer<uint32_t> hist, d_round, slab;
@@ -248,17 +283,23 @@ struct CrossMatcher::Impl {
     }
   }
 
-  size_t pairs() const { return n * (n - 1) / 2; }
+  size_t pairs() const { return videos * (videos - 1) / 2; }
+  size_t capacity_of(size_t lane) const { return max_items[lane % regions]; }
 
-  // cells of all pairs when the lanes hold `fed` (+ `pieces`): sum over a < b of x_a x_b, x = max(items, 1) - 1
+  // cells of all pairs of every region when the lanes hold `fed` (+ `pieces`): per region the sum over a < b of x_a x_b,
+  // x = max(items, 1) - 1
   uint64_t cells_of(const std::vector<Piece> *pieces) const {
-    uint64_t sum = 0, squares = 0;
-    for (size_t i = 0; i < n; i++) {
-      const uint64_t x = std::max<uint64_t>(lanes[i].fed + (pieces ? (*pieces)[i].width : 0u), 1) - 1;
-      sum += x;
-      squares += x * x;
+    uint64_t total = 0;
+    for (size_t r = 0; r < regions; r++) {
+      uint64_t sum = 0, squares = 0;
+      for (size_t i = r; i < n; i += regions) {
+        const uint64_t x = std::max<uint64_t>(lanes[i].fed + (pieces ? (*pieces)[i].width : 0u), 1) - 1;
+        sum += x;
+        squares += x * x;
+      }
+      total += (sum * sum - squares) / 2;
     }
-    return (sum * sum - squares) / 2;
+    return total;
   }
 
   // One round over `pieces` (one per lane).
@@ -286,8 +327,8 @@ struct CrossMatcher::Impl {
 
     const CrossLane *d_lanes = reinterpret_cast<const CrossLane *>(d_round.ptr);
     const dim3 block(kThreads);
-    const uint32_t side_blocks = (uint32_t)((longest + kCarriedRows - 1) / kCarriedRows);  // of the longest lane: the others' leave at once
-    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), (uint32_t)pairs());
+    const uint32_t side_blocks = (uint32_t)((longest + kCarriedRows - 1) / kCarriedRows);  // of the longest lane of any region: the others' leave at once
+    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), (uint32_t)(pairs() * regions));
     std::vector<NeedleHipRun> got;
     for (;;) {
       if (!(s = slab.reserve(kHeaderWords + (uint64_t)capacity * (sizeof(NeedleHipRun) / 4))).ok()) return s;
@@ -296,22 +337,22 @@ struct CrossMatcher::Impl {
       {
         KernelTimer timer("crossmatch_land");
         hipLaunchKernelGGL(crossmatch_land_kernel, dim3(kMaxStrip / kThreads, (uint32_t)n), block, 0, stream, d_round.ptr, hist.ptr,
-                           (uint32_t)max_items, d_count);
+                           rg, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       {
         KernelTimer timer("crossmatch_walk");
         if (narrow)
           hipLaunchKernelGGL(crossmatch_walk_kernel<uint16_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint16_t *>(state.ptr),
-                             d_lanes, (uint32_t)n, (uint32_t)max_items, side_blocks, threshold, min_len, d_runs, capacity, d_count);
+                             d_lanes, (uint32_t)videos, rg, side_blocks, threshold, d_runs, capacity, d_count);
         else
           hipLaunchKernelGGL(crossmatch_walk_kernel<uint32_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint32_t *>(state.ptr),
-                             d_lanes, (uint32_t)n, (uint32_t)max_items, side_blocks, threshold, min_len, d_runs, capacity, d_count);
+                             d_lanes, (uint32_t)videos, rg, side_blocks, threshold, d_runs, capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       {
         KernelTimer timer("crossmatch_simhash");
-        hipLaunchKernelGGL(crossmatch_simhash_kernel, dim3((uint32_t)device_cu_count() * 2u), block, 0, stream, hist.ptr, (uint32_t)max_items,
+        hipLaunchKernelGGL(crossmatch_simhash_kernel, dim3((uint32_t)device_cu_count() * 2u), block, 0, stream, hist.ptr, rg,
                            d_runs, capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
@@ -356,33 +397,69 @@ CrossMatcher::CrossMatcher() : impl_(new Impl()) {}
 CrossMatcher::~CrossMatcher() = default;
 size_t CrossMatcher::lanes() const { return impl_->n; }
 
-size_t CrossMatcher::StateBytes(size_t lanes, size_t max_items) {
-  if (lanes < 2 || lanes > kMaxLanes || max_items < 2 || max_items > 0x7FFFFFF0ull) return 0;
-  const size_t pairs = lanes * (lanes - 1) / 2;
-  return pairs * 2 * 2 * max_items * (max_items < 65536 ? sizeof(uint16_t) : sizeof(uint32_t)) + lanes * max_items * sizeof(uint32_t);
+size_t CrossMatcher::videos() const { return impl_->videos; }
+size_t CrossMatcher::regions() const { return impl_->regions; }
+
+size_t CrossMatcher::StateBytes(size_t lanes, size_t max_items) { return StateBytesRegions(lanes, 1, &max_items); }
+
+size_t CrossMatcher::StateBytesRegions(size_t videos, size_t regions, const size_t *max_items) {
+  if (videos < 2 || videos > kMaxLanes || regions < 1 || regions > kMaxRegions || !max_items) return 0;
+  bool narrow = true;
+  for (size_t r = 0; r < regions; r++) {
+    if (max_items[r] < 2 || max_items[r] > 0x7FFFFFF0ull) return 0;
+    narrow = narrow && max_items[r] < 65536;
+  }
+  const size_t pairs = videos * (videos - 1) / 2;
+  size_t bytes = 0;
+  for (size_t r = 0; r < regions; r++)
+    bytes += pairs * 2 * 2 * max_items[r] * (narrow ? sizeof(uint16_t) : sizeof(uint32_t)) + videos * max_items[r] * sizeof(uint32_t);
+  return bytes;
 }
 
 Status CrossMatcher::Create(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out) {
-  if (!out) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
-  if (lanes < 2 || lanes > kMaxLanes) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: lanes must be 2 to 256");
-  if (max_items < 2 || max_items > 0x7FFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: max_items must be 2 to 2^31 - 16");
-  if (min_len == 0) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: min_len must be >= 1");
+  return CreateRegions(lanes, 1, &max_items, &min_len, threshold, out);
+}
+
+Status CrossMatcher::CreateRegions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                                   std::unique_ptr<CrossMatcher> *out) {
+  if (!out || !max_items || !min_len) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  if (regions < 1 || regions > kMaxRegions) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: regions must be 1 or 2");
+  if (videos < 2 || videos > kMaxLanes) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: lanes (videos) must be 2 to 256");
+  for (size_t r = 0; r < regions; r++) {
+    if (max_items[r] < 2 || max_items[r] > 0x7FFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: max_items must be 2 to 2^31 - 16");
+    if (min_len[r] == 0) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: min_len must be >= 1");
+  }
   std::unique_ptr<CrossMatcher> cm(new CrossMatcher());
   Impl &m = *cm->impl_;
-  m.n = lanes;
-  m.max_items = max_items;
-  m.min_len = min_len;
+  m.videos = videos;
+  m.regions = regions;
+  m.n = videos * regions;
   m.threshold = threshold;
-  m.narrow = max_items < 65536;
-  m.lanes = std::vector<LaneState>(lanes);
+  m.lanes = std::vector<LaneState>(m.n);
+  // histories and frontiers region after region: the bases in words and in entries
+  size_t hist_words = 0, state_entries = 0;
+  for (size_t r = 0; r < regions; r++) {
+    m.max_items[r] = max_items[r];
+    m.min_len[r] = min_len[r];
+    m.narrow = m.narrow && max_items[r] < 65536;
+    (r ? m.rg.hist1 : m.rg.hist0) = hist_words;
+    (r ? m.rg.state1 : m.rg.state0) = state_entries;
+    hist_words += videos * max_items[r];
+    state_entries += m.pairs() * 4 * max_items[r];
+  }
+  m.rg.regions = (uint32_t)regions;
+  m.rg.max_items0 = (uint32_t)m.max_items[0];
+  m.rg.max_items1 = (uint32_t)m.max_items[regions - 1];
+  m.rg.min_len0 = m.min_len[0];
+  m.rg.min_len1 = m.min_len[regions - 1];
   if (const char *e = getenv("NEEDLE_HIP_CROSSMATCHER_RUN_SLAB")) m.capacity = (uint32_t)std::min<long long>(std::max(1ll, atoll(e)), 1ll << 26);
 
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
   Status s = ensure_device();
   if (!s.ok()) return s;
   hipStream_t stream = library_stream();
-  const size_t hist_bytes = lanes * max_items * sizeof(uint32_t), state_bytes = StateBytes(lanes, max_items) - hist_bytes;
-  if (!(s = m.hist.reserve(lanes * max_items)).ok() || !(s = m.state.reserve(state_bytes)).ok()) return s;
+  const size_t state_bytes = state_entries * (m.narrow ? sizeof(uint16_t) : sizeof(uint32_t));
+  if (!(s = m.hist.reserve(hist_words)).ok() || !(s = m.state.reserve(state_bytes)).ok()) return s;
   NEEDLE_HIP_TRY(hipMemsetAsync(m.state.ptr, 0, state_bytes, stream));
   NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
   *out = std::move(cm);
@@ -398,7 +475,7 @@ Status CrossMatcher::Feed(const uint32_t *const *items, const size_t *num_items)
     if (!num_items[i]) continue;
     if (m.lanes[i].finished) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: the lane is finished");
     if (!items[i]) return Status::Make(NeedleError_NullArgument, "crossmatcher: null chunk");
-    if (num_items[i] > m.max_items - m.lanes[i].fed) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: more than max_items in a lane");
+    if (num_items[i] > m.capacity_of(i) - m.lanes[i].fed) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: more than max_items in a lane");
     any = true;
   }
   if (!any) return Status::Ok();
@@ -495,7 +572,7 @@ void CrossMatcher::Stats(uint64_t stats[4]) const {
   stats[0] = m.feeds;
   stats[1] = m.launches;
   stats[2] = m.cells;
-  stats[3] = StateBytes(m.n, m.max_items) + kHeaderWords * 4 + (uint64_t)m.capacity * sizeof(NeedleHipRun);
+  stats[3] = StateBytesRegions(m.videos, m.regions, m.max_items) + kHeaderWords * 4 + (uint64_t)m.capacity * sizeof(NeedleHipRun);
 }
 
 }  // namespace needle

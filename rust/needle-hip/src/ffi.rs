@@ -405,6 +405,14 @@ extern "C" {
         threshold: u32,
         output: *mut *mut NeedleHipCrossMatcher,
     ) -> NeedleError;
+    pub fn needle_hip_crossmatcher_new_regions(
+        videos: usize,
+        regions: usize,
+        max_items: *const usize,
+        min_len: *const u32,
+        threshold: u32,
+        output: *mut *mut NeedleHipCrossMatcher,
+    ) -> NeedleError;
     pub fn needle_hip_crossmatcher_free(matcher: *mut NeedleHipCrossMatcher);
     pub fn needle_hip_crossmatcher_feed(matcher: *mut NeedleHipCrossMatcher, items: *const *const u32, num_items: *const usize) -> NeedleError;
     pub fn needle_hip_crossmatcher_feed_from_feeder(matcher: *mut NeedleHipCrossMatcher, feeder: *mut NeedleHipFeeder) -> NeedleError;
@@ -414,5 +422,7 @@ extern "C" {
     pub fn needle_hip_crossmatcher_runs(matcher: *mut NeedleHipCrossMatcher, first: usize, count: usize, runs: *mut NeedleHipRun) -> NeedleError;
     pub fn needle_hip_crossmatcher_stats(matcher: *const NeedleHipCrossMatcher, stats: *mut u64) -> NeedleError;
     pub fn needle_hip_crossmatcher_state_bytes(lanes: usize, max_items: usize) -> usize;
+    pub fn needle_hip_crossmatcher_state_bytes_regions(videos: usize, regions: usize, max_items: *const usize) -> usize;
+    pub fn needle_hip_crossmatcher_shape(matcher: *const NeedleHipCrossMatcher, videos: *mut usize, regions: *mut usize) -> NeedleError;
     pub fn needle_hip_host_free(ptr: *mut c_void);
 }

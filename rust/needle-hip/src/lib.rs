@@ -652,9 +652,33 @@ impl CrossMatcher {
         Ok(CrossMatcher { raw, lanes })
     }
 
+    /// Openings and endings in one object: `videos * max_items.len()` lanes, lane = video * regions + region, matched within a
+    /// region only; `max_items` and `min_len` hold one entry per region (1 or 2).  `problem` of a run is pair * regions + region.
+    pub fn with_regions(videos: usize, max_items: &[usize], min_len: &[u32], threshold: u32) -> Result<Self> {
+        assert_eq!(max_items.len(), min_len.len(), "one max_items and one min_len per region");
+        let regions = max_items.len();
+        let mut raw = ptr::null_mut();
+        unsafe {
+            check(ffi::needle_hip_crossmatcher_new_regions(videos, regions, max_items.as_ptr(), min_len.as_ptr(), threshold, &mut raw))?
+        };
+        Ok(CrossMatcher { raw, lanes: videos * regions })
+    }
+
+    /// `(videos, regions)`: the object has `videos * regions` lanes.
+    pub fn shape(&self) -> Result<(usize, usize)> {
+        let (mut videos, mut regions) = (0usize, 0usize);
+        unsafe { check(ffi::needle_hip_crossmatcher_shape(self.raw, &mut videos, &mut regions))? };
+        Ok((videos, regions))
+    }
+
     /// Bytes of device state such a matcher allocates (pure host arithmetic).
     pub fn state_bytes(lanes: usize, max_items: usize) -> usize {
         unsafe { ffi::needle_hip_crossmatcher_state_bytes(lanes, max_items) }
+    }
+
+    /// The same for one capacity per region; 0 where an argument is out of range.
+    pub fn state_bytes_regions(videos: usize, max_items: &[usize]) -> usize {
+        unsafe { ffi::needle_hip_crossmatcher_state_bytes_regions(videos, max_items.len(), max_items.as_ptr()) }
     }
 
     /// The hashes every lane has received since the last feed: one slice per lane, an empty one for nothing.

@@ -18,12 +18,21 @@ items per lane and feed).
   resources: registers, LDS and scratch of the new kernels and of every kernel of matcher.hip, search.hip, the fingerprint
              files and feeder.hip, from the compiler's remarks, for this tree and (--parent) for a checkout of the parent
              commit (tools/bench_matcher.py's reader; needs no GPU).
+  regions  : openings and endings in ONE object (needle_hip_crossmatcher_new_regions) against what a caller needed before it,
+             two single-region cross-matchers fed in turn on the parent commit's library: 28 videos, openings of 2 897 and
+             endings of 1 443 items, taken when the lanes hold 1 100 items, 4 new items per lane and feed.  Wall ms per feed
+             (median of 30 after 10; for the two objects a feed is both calls) and, in a pass of its own, the summed event
+             times of the kernels (mean of 30); five processes each, alternating.  The condition: one object's median <= the
+             yardstick's median + the spread (max - min) of the yardstick's own five.  The ratio is recorded, it is no
+             target.  And the single-region path on both trees: regions = 1 at 28 and 64 lanes holding 24 minutes, per-feed
+             wall and the walk kernel's event time, this tree and the parent alternating, the one that goes first alternating
+             too; the difference of the medians must lie within the parent's own spread.  (--parent, built)
   headline : bench.py --gpus 1 --steps 20 --warmup 5, parent and this tree alternating, four runs each, the tree that goes
              first alternating too (--parent, built).
 
 Sections that were not run keep what the file held, or "not measured".
 
-usage: python tools/bench_crossmatch.py [--only per_feed,tail,season,resources,headline] [--parent DIR]"""
+usage: python tools/bench_crossmatch.py [--only per_feed,tail,season,resources,regions,headline] [--parent DIR]"""
 import argparse
 import json
 import os
@@ -197,6 +206,100 @@ def bench_season(capi):
     return res
 
 
+_REGIONS_CHILD = """
+import json, statistics, sys, time
+import numpy as np
+from needle_amd import capi
+mode, videos, held = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
+caps = [int(x) for x in sys.argv[4].split(",")]
+chunk, threshold, min_len = 4, 10, 80
+kernels = ("crossmatch_land", "crossmatch_walk", "crossmatch_simhash")
+rng = np.random.default_rng(7)
+data = [rng.integers(0, 2 ** 32, (videos, c), dtype=np.uint64).astype(np.uint32) for c in caps]
+for d in data:                                       # one shared stretch of 360 items in every lane of a region
+    shared = rng.integers(0, 2 ** 32, 360, dtype=np.uint64).astype(np.uint32)
+    for k in range(videos):
+        at = 100 + 17 * (k % 40)
+        d[k, at:at + 360] = shared ^ (np.uint32(1) << rng.integers(0, 32, 360).astype(np.uint32))
+if mode == "one":                                    # one object, lane = video * regions + region
+    m = capi.CrossMatcher.with_regions(videos, caps, [min_len] * len(caps), threshold)
+    objects = [m]
+    def feed(a, b):
+        m.feed([data[r][v, a:b] for v in range(videos) for r in range(len(caps))])
+else:                                                # one single-region object per region, fed in turn
+    objects = [capi.CrossMatcher(videos, c, min_len, threshold) for c in caps]
+    def feed(a, b):
+        for o, d in zip(objects, data):
+            o.feed([row[a:b] for row in d])
+def timed(pos, count):
+    out = []
+    for _ in range(count):
+        t0 = time.perf_counter()
+        feed(pos, pos + chunk)
+        out.append((time.perf_counter() - t0) * 1e3)
+        pos += chunk
+    return out, pos
+feed(0, held)
+_, pos = timed(held, 10)
+wall, pos = timed(pos, 30)
+capi.set_kernel_timing(",".join(kernels) + ",sum")
+_, pos = timed(pos, 30)
+capi.synchronize()
+ms = {k: capi.last_kernel_ms(k) / 30 for k in kernels}
+capi.set_kernel_timing(None)
+for o in objects:
+    o.finish()
+print(json.dumps({"wall_ms_per_feed_median": statistics.median(wall), "wall_ms_min_max": [min(wall), max(wall)],
+                  "kernel_ms_per_feed": ms, "kernel_ms_per_feed_sum": sum(ms.values()),
+                  "launches": sum(o.stats()[1] for o in objects), "runs": sum(o.ready()[0] for o in objects),
+                  "state_bytes": sum(o.stats()[3] for o in objects)}))
+"""
+
+
+def bench_regions(root, parent):
+    def child(tree, mode, videos, held, caps):
+        run = subprocess.run([sys.executable, "-c", _REGIONS_CHILD, mode, str(videos), str(held), ",".join(str(c) for c in caps)], cwd=tree,
+                             env=dict(os.environ, PYTHONPATH=tree), stdout=subprocess.PIPE, text=True, timeout=600, check=True)
+        return json.loads(run.stdout.strip().splitlines()[-1])
+
+    def summary(runs, key):
+        vals = [r[key] if isinstance(key, str) else r[key[0]][key[1]] for r in runs]
+        return {"runs": [round(v, 5) for v in vals], "median": round(statistics.median(vals), 5), "spread": round(max(vals) - min(vals), 5)}
+    res = {"two_regions_in_one_object": NOT_MEASURED, "single_region_against_parent": NOT_MEASURED}
+    caps, held = (SEASON_ITEMS, 1443), 1100
+    one, two = [], []
+    for _ in range(5):                                                           # the two alternate, the yardstick first
+        two.append(child(parent, "two", SEASON_LANES, held, caps))
+        one.append(child(root, "one", SEASON_LANES, held, caps))
+        print("regions", two[-1]["wall_ms_per_feed_median"], one[-1]["wall_ms_per_feed_median"], file=sys.stderr, flush=True)
+    assert all(r["runs"] == one[0]["runs"] for r in one + two), [r["runs"] for r in one + two]
+    wall_one, wall_two = summary(one, "wall_ms_per_feed_median"), summary(two, "wall_ms_per_feed_median")
+    res["two_regions_in_one_object"] = {
+        "videos": SEASON_LANES, "max_items": list(caps), "items_held": held, "chunk_items": 4, "runs": one[0]["runs"],
+        "launches_in_the_process": {"one_object": one[0]["launches"], "two_objects": two[0]["launches"]},
+        "wall_ms_per_feed": {"one_object": wall_one, "two_objects_on_the_parent": wall_two},
+        "kernel_ms_per_feed_sum": {"one_object": summary(one, "kernel_ms_per_feed_sum"), "two_objects_on_the_parent": summary(two, "kernel_ms_per_feed_sum")},
+        "walk_kernel_ms_per_feed": {"one_object": summary(one, ("kernel_ms_per_feed", "crossmatch_walk")),
+                                    "two_objects_on_the_parent": summary(two, ("kernel_ms_per_feed", "crossmatch_walk"))},
+        "condition_one_within_yardstick_plus_its_spread": wall_one["median"] <= wall_two["median"] + wall_two["spread"],
+        "ratio_two_objects_to_one": round(wall_two["median"] / wall_one["median"], 3)}
+    single = {}
+    for lanes in (28, 64):
+        this, before = [], []
+        for k in range(4):                                                       # which tree goes first alternates
+            for name in (("parent", "this") if k % 2 == 0 else ("this", "parent")):
+                (before if name == "parent" else this).append(child(parent if name == "parent" else root, "two", lanes, 5760, (5760 + 400,)))
+        wall = {"this": summary(this, "wall_ms_per_feed_median"), "parent": summary(before, "wall_ms_per_feed_median")}
+        walk = {"this": summary(this, ("kernel_ms_per_feed", "crossmatch_walk")), "parent": summary(before, ("kernel_ms_per_feed", "crossmatch_walk"))}
+        single[f"{lanes} lanes at 24 min"] = {
+            "wall_ms_per_feed": wall, "walk_kernel_ms_per_feed": walk, "state_bytes": {"this": this[0]["state_bytes"], "parent": before[0]["state_bytes"]},
+            "wall_difference_within_parents_spread": abs(wall["this"]["median"] - wall["parent"]["median"]) <= wall["parent"]["spread"],
+            "walk_difference_within_parents_spread": abs(walk["this"]["median"] - walk["parent"]["median"]) <= walk["parent"]["spread"]}
+        print("regions single", lanes, single[f"{lanes} lanes at 24 min"], file=sys.stderr, flush=True)
+    res["single_region_against_parent"] = single
+    return res
+
+
 def bench_resources(root, parent):
     BM.RESOURCE_FILES = ["crossmatch.hip", "matcher.hip", "search.hip", "fingerprint.hip", "fingerprint32.hip", "feeder.hip"]
     this = BM.kernel_resources(root)
@@ -236,14 +339,16 @@ def bench_headline(root, parent, repeats=4):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="per_feed,tail,season,resources,headline")
+    ap.add_argument("--only", default="per_feed,tail,season,resources,regions,headline")
     ap.add_argument("--parent", default=None, help="a checkout of the parent commit, built (yardstick, resources, headline)")
     ap.add_argument("--repeats", type=int, default=4, help="headline runs per tree")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "crossmatch_bench.json"))
     args = ap.parse_args()
+    if args.parent:
+        args.parent = os.path.abspath(args.parent)
     from needle_amd import capi
     only = set(args.only.split(","))
-    keys = ("device", "per_feed", "tail", "season", "resources", "headline_vs_parent")
+    keys = ("device", "per_feed", "tail", "season", "resources", "regions", "headline_vs_parent")
     res = {k: NOT_MEASURED for k in keys}
     if os.path.exists(args.out):
         try:
@@ -264,6 +369,9 @@ def main():
             if name in only:
                 res[name] = run()
                 save()
+        if "regions" in only and args.parent:
+            res["regions"] = bench_regions(ROOT, args.parent)
+            save()
         if "headline" in only and args.parent:
             res["headline_vs_parent"] = bench_headline(ROOT, args.parent, args.repeats)
     save()
