@@ -657,7 +657,40 @@ enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint6
  * videos * regions lanes: the arrays of feed have one entry per lane, feed_from_feeder wants a feeder of
  * videos * regions lanes, `complete` means every lane of every region is finished, stats[2] sums over regions and pairs.
  *
- * Out of scope: `reset`, `open`, more than two regions, several ranks, feeding the device epilogue or the index.
+ * Resident videos: a new season joins a library (needle_hip_crossmatcher_new_resident).  K videos are known and complete,
+ * N are arriving; the video list is the K resident videos followed by the N arriving ones, V = K + N (the index's append
+ * order), so a resident is always the source of a pair with an arriving video.  The resident rows are given at creation as
+ * the matcher takes its sources: one hash arena and one NeedleHipSeq per row k * regions + r; they are uploaded once, and
+ * a row of 0 or 1 hashes is allowed and has no cells.  Only the arriving videos have lanes: lane = t * regions + r for
+ * arriving video t, whose index among all videos is K + t; feed, finish, lane, feed_from_feeder (a feeder of N * regions
+ * lanes), ready and shape work over these lanes as above.  The live problems are (a, b, r) with a < b and b >= K:
+ *   resident x arriving (a < K): only the destination grows.  The state is the col frontier alone, one run length per
+ *     resident row at the last column fed, sized by that row's own length and not by max_items, in two sets.  It costs
+ *     (n_a - 1)(n_b - 1) cells, each evaluated once; no row-direction work is done for it.
+ *   arriving x arriving (a >= K): the pair above, with its L frontier of 4 x max_items[r] entries.
+ *   resident x resident: no state, no work, never reported.
+ * NeedleHipRun.problem = pair_index(a, b, V) * regions + r with the indices among all V videos, in the comparator's
+ * i-major order: pair_index = a (2 V - a - 1) / 2 + (b - a - 1).  Every pair of an arriving video is live, so the complete
+ * list, given to needle_hip_comparator_results_from_runs(first_video = K, video_count = N) of a comparator over the V
+ * videos, yields the arriving videos' results, those of a full search over all K + N videos.  The reporting rule is the
+ * one above with Ja = n_a for a resident from the first round on: a run is reported in the round whose cells break it,
+ * and what is open on a frontier -- a run into the resident's last row or into the lane's last column -- in the round in
+ * which lane b finishes.  A round is still three launches, one upload and one download, whatever K is: the resident row
+ * table (offset, length, state base) goes up once at creation, nothing per pair or per resident row in a round; a resident
+ * problem whose arriving lane has no data and is not finishing leaves after its table reads, with no state traffic; a
+ * round never writes state it reads, so the repeat after a slab overflow works as above.  The entries are 2 bytes where
+ * every max_items[r] AND every resident row length is below 65 536, else 4, for the whole object.  min_len is per region,
+ * a lower bound (the epilogue applies the duration test).  stats[2] counts the resident cells too.
+ * Limits, checked before a device is asked for (InvalidArgument): regions 1 or 2; N 1..256 when K >= 1 (K = 0 is
+ * needle_hip_crossmatcher_new_regions, N 2..256); max_items[r] in [2, 2^31 - 16]; every resident row inside the arena
+ * (offset + len <= num_hashes) and len <= 2^31 - 16; min_len[r] >= 1; (K N + N (N - 1) / 2) x regions <= 65 535 live
+ * problems (a grid dimension: 1 000 residents + 28 arriving x 2 regions = 56 756 fits, 2 000 + 28 x 2 regions does not);
+ * V (V - 1) / 2 x regions < 2^32.  NULL arrays (hashes with num_hashes > 0, resident with num_resident > 0, max_items,
+ * min_len) or a NULL output: NullArgument.
+ *
+ * Out of scope: `reset`, `open`, more than two regions, several ranks, feeding the device epilogue or the index;
+ * refreshed results for the resident videos (their candidate lists also need the old pairs' runs); resident rows taken
+ * from a device arena.
  *
  * lanes (videos) must be 2..256 (32 640 pairs: pair * regions + region is a grid dimension).  max_items >= 2 is the
  * capacity of every lane (of the region); state and histories are allocated at creation.  lanes, regions or max_items
@@ -673,6 +706,11 @@ enum NeedleError needle_hip_crossmatcher_new(size_t lanes, size_t max_items, uin
 /* videos 2..256, regions 1..2; max_items[r] >= 2, min_len[r] >= 1 per region */
 enum NeedleError needle_hip_crossmatcher_new_regions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len,
                                                      uint32_t threshold, NeedleHipCrossMatcher **output);
+/* K = num_resident known videos (resident[k * regions + r] inside the arena `hashes`) in front of `videos` arriving ones;
+ * num_resident == 0 is needle_hip_crossmatcher_new_regions */
+enum NeedleError needle_hip_crossmatcher_new_resident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident,
+                                                      size_t num_resident, size_t videos, size_t regions, const size_t *max_items,
+                                                      const uint32_t *min_len, uint32_t threshold, NeedleHipCrossMatcher **output);
 void needle_hip_crossmatcher_free(NeedleHipCrossMatcher *matcher);
 /* one entry per lane, host hashes; num_items[i] == 0: nothing for lane i */
 enum NeedleError needle_hip_crossmatcher_feed(NeedleHipCrossMatcher *matcher, const uint32_t *const *items, const size_t *num_items);
@@ -694,7 +732,17 @@ size_t needle_hip_crossmatcher_state_bytes(size_t lanes, size_t max_items);
 /* the sum over the regions of pairs x 2 sets x 2 x max_items[r] x w + videos x max_items[r] x 4 bytes, w = 2 where every
  * max_items[r] < 65 536, else 4; 0 where an argument is out of range; regions = 1: needle_hip_crossmatcher_state_bytes */
 size_t needle_hip_crossmatcher_state_bytes_regions(size_t videos, size_t regions, const size_t *max_items);
-/* what the object was created with (regions = 1 for needle_hip_crossmatcher_new); it has videos * regions lanes */
+/* with P = N (N - 1) / 2 arriving pairs and S_r the sum of the resident lengths of region r, the sum over the regions of
+ * P x 4 x max_items[r] x w + N x max_items[r] x 4 + N x 2 x S_r x w + S_r x 4 bytes; w = 2 where every max_items[r] and
+ * every resident length < 65 536, else 4 (1 000 residents of 5 441, 28 arriving, one region: 648 218 976); the offsets of
+ * `resident` are not looked at; 0 where an argument is out of range; num_resident = 0:
+ * needle_hip_crossmatcher_state_bytes_regions.  stats[3] is this plus the resident table and the run slab. */
+size_t needle_hip_crossmatcher_state_bytes_resident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions,
+                                                    const size_t *max_items);
+/* the resident videos the object was created with; 0 for needle_hip_crossmatcher_new and _new_regions */
+enum NeedleError needle_hip_crossmatcher_resident(const NeedleHipCrossMatcher *matcher, size_t *num_resident);
+/* what the object was created with (regions = 1 for needle_hip_crossmatcher_new): the arriving videos and the regions; it
+ * has videos * regions lanes */
 enum NeedleError needle_hip_crossmatcher_shape(const NeedleHipCrossMatcher *matcher, size_t *videos, size_t *regions);
 
 #ifdef __cplusplus

@@ -113,7 +113,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_crossmatcher_feed_from_feeder", "needle_hip_crossmatcher_finish", "needle_hip_crossmatcher_ready",
     "needle_hip_crossmatcher_lane", "needle_hip_crossmatcher_runs", "needle_hip_crossmatcher_stats",
     "needle_hip_crossmatcher_state_bytes", "needle_hip_crossmatcher_new_regions",
-    "needle_hip_crossmatcher_state_bytes_regions", "needle_hip_crossmatcher_shape"]
+    "needle_hip_crossmatcher_state_bytes_regions", "needle_hip_crossmatcher_shape",
+    "needle_hip_crossmatcher_new_resident", "needle_hip_crossmatcher_state_bytes_resident", "needle_hip_crossmatcher_resident"]
 
 # enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
 SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
@@ -314,6 +315,10 @@ def lib():
     L.needle_hip_crossmatcher_state_bytes_regions.argtypes = [sz, sz, C.POINTER(sz)]
     L.needle_hip_crossmatcher_state_bytes_regions.restype = sz
     L.needle_hip_crossmatcher_shape.argtypes = [vp, C.POINTER(sz), C.POINTER(sz)]
+    L.needle_hip_crossmatcher_new_resident.argtypes = [vp, sz, vp, sz, sz, sz, C.POINTER(sz), C.POINTER(u32), u32, C.POINTER(vp)]
+    L.needle_hip_crossmatcher_state_bytes_resident.argtypes = [vp, sz, sz, sz, C.POINTER(sz)]
+    L.needle_hip_crossmatcher_state_bytes_resident.restype = sz
+    L.needle_hip_crossmatcher_resident.argtypes = [vp, C.POINTER(sz)]
     _LIB = L
     return L
 
@@ -905,7 +910,9 @@ class CrossMatcher:
     """needle_hip_crossmatcher_*: the streaming all-pairs comparator.  `lanes` sequences of at most `max_items` hashes arrive
     in chunks and are matched against each other; the run list is one RUN_DTYPE array, `problem` = the pair's index in the
     comparator's i-major order, so it goes straight into Comparator.results_from_runs.  `with_regions`: openings and endings
-    in one object, lane = video * regions + region, `problem` = pair * regions + region."""
+    in one object, lane = video * regions + region, `problem` = pair * regions + region.  `with_resident`: K known videos in
+    front of the arriving ones; only the arriving videos have lanes, `problem` numbers the pairs over all K + N videos, and
+    the list goes into Comparator.results_from_runs(first_video=K)."""
 
     def __init__(self, lanes: int, max_items: int, min_len: int, threshold: int):
         self._h = None
@@ -929,15 +936,58 @@ class CrossMatcher:
         self.lanes, self.max_items, self.min_len, self.threshold = videos * regions, tuple(max_items), tuple(min_len), threshold
         return self
 
+    @classmethod
+    def with_resident(cls, resident: Sequence[np.ndarray], videos: int, max_items: Sequence[int], min_len: Sequence[int],
+                      threshold: int) -> "CrossMatcher":
+        """`resident`: the K * regions hash sequences of the known videos in row order (video k, region r at k * regions + r),
+        regions = len(max_items); `videos` arriving videos with `videos * regions` lanes."""
+        if len(max_items) != len(min_len):
+            raise ValueError(f"one max_items and one min_len per region: {len(max_items)} and {len(min_len)}")
+        regions = len(max_items)
+        if regions and len(resident) % regions:
+            raise ValueError(f"one resident row per video and region: {len(resident)} rows, {regions} regions")
+        arrs = [np.ascontiguousarray(s, dtype=np.uint32) for s in resident]
+        arena = np.concatenate(arrs) if arrs else np.zeros(0, dtype=np.uint32)
+        seqs = np.zeros((max(len(arrs), 1), 2), dtype=np.uint32)
+        seqs[:len(arrs), 1] = [a.size for a in arrs]
+        seqs[:len(arrs), 0] = np.cumsum([0] + [a.size for a in arrs])[:len(arrs)]
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().needle_hip_crossmatcher_new_resident(arena.ctypes.data if arena.size else None, arena.size, seqs.ctypes.data,
+                                                         len(arrs) // max(regions, 1), videos, regions,
+                                                         (C.c_size_t * max(regions, 1))(*max_items),
+                                                         (C.c_uint32 * max(regions, 1))(*min_len), threshold, C.byref(h)))
+        self._h = h
+        self.lanes, self.max_items, self.min_len, self.threshold = videos * regions, tuple(max_items), tuple(min_len), threshold
+        return self
+
+    @property
+    def resident(self) -> int:
+        """The known videos the object was created with (0 without `with_resident`)."""
+        k = C.c_size_t()
+        check(lib().needle_hip_crossmatcher_resident(self._h, C.byref(k)))
+        return k.value
+
     def shape(self) -> Tuple[int, int]:
-        """(videos, regions): the object has videos * regions lanes."""
+        """(videos, regions): the arriving videos; the object has videos * regions lanes."""
         videos, regions = C.c_size_t(), C.c_size_t()
         check(lib().needle_hip_crossmatcher_shape(self._h, C.byref(videos), C.byref(regions)))
         return videos.value, regions.value
 
     @staticmethod
-    def state_bytes(lanes: int, max_items) -> int:
-        """`max_items`: one capacity, or one per region (`lanes` is then the number of videos)."""
+    def state_bytes(lanes: int, max_items, resident: Optional[Sequence[int]] = None) -> int:
+        """`max_items`: one capacity, or one per region (`lanes` is then the number of videos).  `resident`: the lengths of the
+        K * regions resident rows in row order (`lanes` is then the number of arriving videos)."""
+        if resident is not None:
+            caps = [max_items] if isinstance(max_items, (int, np.integer)) else list(max_items)
+            regions = len(caps)
+            if regions and len(resident) % regions:
+                raise ValueError(f"one resident row per video and region: {len(resident)} rows, {regions} regions")
+            seqs = np.zeros((max(len(resident), 1), 2), dtype=np.uint32)
+            seqs[:len(resident), 1] = list(resident)
+            return int(lib().needle_hip_crossmatcher_state_bytes_resident(seqs.ctypes.data, len(resident) // max(regions, 1), lanes, regions,
+                                                                          (C.c_size_t * max(regions, 1))(*caps)))
         if isinstance(max_items, (int, np.integer)):
             return int(lib().needle_hip_crossmatcher_state_bytes(lanes, max_items))
         regions = len(max_items)

@@ -873,6 +873,19 @@ enum NeedleError needle_hip_crossmatcher_new_regions(size_t videos, size_t regio
   });
 }
 
+enum NeedleError needle_hip_crossmatcher_new_resident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident,
+                                                      size_t num_resident, size_t videos, size_t regions, const size_t *max_items,
+                                                      const uint32_t *min_len, uint32_t threshold, NeedleHipCrossMatcher **output) {
+  if (!output || !max_items || !min_len || (num_resident && !resident) || (num_hashes && !hashes)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipCrossMatcher>();
+    Status s = CrossMatcher::CreateResident(hashes, num_hashes, resident, num_resident, videos, regions, max_items, min_len, threshold, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
 void needle_hip_crossmatcher_free(NeedleHipCrossMatcher *matcher) { delete matcher; }
 
 enum NeedleError needle_hip_crossmatcher_feed(NeedleHipCrossMatcher *matcher, const uint32_t *const *items, const size_t *num_items) {
@@ -933,6 +946,17 @@ size_t needle_hip_crossmatcher_state_bytes(size_t lanes, size_t max_items) { ret
 
 size_t needle_hip_crossmatcher_state_bytes_regions(size_t videos, size_t regions, const size_t *max_items) {
   return CrossMatcher::StateBytesRegions(videos, regions, max_items);
+}
+
+size_t needle_hip_crossmatcher_state_bytes_resident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions,
+                                                    const size_t *max_items) {
+  return CrossMatcher::StateBytesResident(resident, num_resident, videos, regions, max_items);
+}
+
+enum NeedleError needle_hip_crossmatcher_resident(const NeedleHipCrossMatcher *matcher, size_t *num_resident) {
+  if (!matcher || !num_resident) return NeedleError_NullArgument;
+  *num_resident = matcher->inner->residents();
+  return NeedleError_Ok;
 }
 
 enum NeedleError needle_hip_crossmatcher_shape(const NeedleHipCrossMatcher *matcher, size_t *videos, size_t *regions) {

@@ -18,8 +18,15 @@ class CrossMatcher {
   // regions 1 or 2; max_items and min_len hold one entry per region.  Create is the one-region case.
   static Status CreateRegions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
                               std::unique_ptr<CrossMatcher> *out);
+  // Resident videos: `resident` holds num_resident * regions rows of the arena `hashes` (row k * regions + r), complete
+  // and uploaded here; they come before the arriving videos in the video list, and only pairs with an arriving end are
+  // live.  Lanes, `videos()` and the feeds are the arriving videos'.  num_resident == 0 is CreateRegions.
+  static Status CreateResident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident, size_t videos,
+                               size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                               std::unique_ptr<CrossMatcher> *out);
   ~CrossMatcher();
   size_t lanes() const;  // videos * regions
+  size_t residents() const;
   size_t videos() const;
   size_t regions() const;
   Status Feed(const uint32_t *const *items, const size_t *num_items);
@@ -33,6 +40,9 @@ class CrossMatcher {
   static size_t StateBytes(size_t lanes, size_t max_items);
   // the sum of that over the regions, with one entry width: 2 where every region's max_items < 65 536, else 4
   static size_t StateBytesRegions(size_t videos, size_t regions, const size_t *max_items);
+  // with resident rows: per region also videos x 2 sets x S x (2 or 4) + S x 4, S = the region's resident hashes; the width
+  // is 4 as soon as one max_items or one resident row reaches 65 536
+  static size_t StateBytesResident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items);
 
  private:
   CrossMatcher();

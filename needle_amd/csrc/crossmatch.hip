@@ -30,6 +30,18 @@
 // histories (videos x max_items[r] words) and the frontiers (pairs x 4 x max_items[r] entries) lie region after region,
 // and a region's max_items, min_len and two bases travel by value in the kernels' arguments (CrossRegions).  Still three
 // launches, one upload and one download per round; R = 1 is the same code with the second region's fields unused.
+//
+// Resident videos (needle_hip_crossmatcher_new_resident): K videos that are complete at creation come before the N arriving
+// ones in the video list, V = K + N.  Only the arriving videos have lanes; a resident row (k, r) is a row of the resident
+// table (CrossResident: its length and the sum of the lengths before it in its region, uploaded once) and its hashes lie
+// behind the histories in the same buffer.  The live problems are (a, b, r) with b >= K.  blockIdx.y of the walk is the
+// live numbering q * R + r: q = t * K + k for resident k against arriving t, then the arriving pairs i-major; the
+// comparator's index over V videos, NeedleHipRun.problem, comes from (a, b) in closed form.  A resident is a lane that
+// holds all its items, finished before the first round, with no new items ever: only the column direction has cells, and the
+// state of (k, t, r) is the col frontier alone, two sets of len(k, r) entries at 2 * (t * S_r + prefix(k, r)) behind the
+// arriving pairs' frontiers (S_r = the region's resident hashes).  A diagonal that stops in the resident's last row has
+// nowhere to go on: its run, if long enough, is final and leaves with the round's runs; the host holds it back until the
+// arriving lane finishes, which is when the reporting rule hands out what is open on a frontier.  K = 0 is the object above.
 #include "crossmatch.h"
 
 #include <algorithm>
@@ -57,6 +69,8 @@ constexpr uint32_t kHeaderWords = 8;  // the slab: the run counter in word 0, th
 constexpr uint32_t kHeadRuns = 127;   // runs that come down with the counter in one copy
 constexpr size_t kMaxLanes = 256;     // videos: 32 640 pairs, and pair * regions + region is a grid dimension (65 280 <= 65 535)
 constexpr size_t kMaxRegions = 2;
+constexpr size_t kMaxProblems = 65535;  // live problems (with residents: K N + N (N - 1) / 2 pairs) x regions: gridDim.y
+constexpr uint64_t kMaxRowItems = 0x7FFFFFF0ull;
 
 struct CrossLane {
   uint32_t fed, width;  // J and the new items [J, J + width)
@@ -73,7 +87,19 @@ struct CrossRegions {
   uint32_t min_len0, min_len1;
   uint64_t hist0, hist1;             // first word of the region's histories: row `video` is max_items words
   uint64_t state0, state1;           // first entry of the region's frontiers: pair p's four sets are 4 * max_items entries
+  // resident videos: rows k * regions + r of the resident table
+  uint32_t residents;                // K; 0: none of the fields below is read
+  uint64_t res_hist0, res_hist1;     // first word of the region's resident hashes: row (k, r) starts `prefix` words on
+  uint64_t res_state0, res_state1;   // first entry of the region's resident frontiers: (t, k) at 2 * (t * res_total + prefix)
+  uint64_t res_total0, res_total1;   // S_r: the region's resident hashes
 };
+
+// One resident row, uploaded once at creation.
+struct CrossResident {
+  uint64_t prefix;  // the lengths of the region's rows before this one
+  uint32_t len, pad;
+};
+static_assert(sizeof(CrossResident) == 16, "resident table entries are 4 words");
 
 __device__ __forceinline__ uint32_t region_max_items(const CrossRegions &rg, uint32_t r) { return r ? rg.max_items1 : rg.max_items0; }
 
@@ -81,6 +107,15 @@ __device__ __forceinline__ uint32_t region_max_items(const CrossRegions &rg, uin
 __device__ __forceinline__ uint64_t lane_row(const CrossRegions &rg, uint32_t lane) {
   const uint32_t r = rg.regions == 2u ? lane & 1u : 0u, video = rg.regions == 2u ? lane >> 1 : lane;
   return (r ? rg.hist1 : rg.hist0) + (uint64_t)video * region_max_items(rg, r);
+}
+
+// the hashes of row `row` = video * regions + region over all V videos: a resident's through the table, an arriving one's
+// by arithmetic
+__device__ __forceinline__ uint64_t video_row(const CrossRegions &rg, const CrossResident *__restrict__ resident, uint32_t row) {
+  const uint32_t first = rg.residents * rg.regions;
+  if (row >= first) return lane_row(rg, row - first);
+  const uint32_t r = rg.regions == 2u ? row & 1u : 0u;
+  return (r ? rg.res_hist1 : rg.res_hist0) + resident[row].prefix;
 }
 
 __global__ __launch_bounds__(kThreads) void crossmatch_land_kernel(const uint32_t *__restrict__ round_buf, uint32_t *__restrict__ hist,
@@ -100,6 +135,7 @@ struct CrossSide {
   uint32_t carried;          // carried diagonals: entries 0 .. carried - 1 of `from`
   const T *from;             // frontier read, by position along X; nullptr: all zero (the other side had no cell yet)
   T *to_last_y, *to_last_x;  // frontier written where a diagonal stops in Y's new last item (by X position) / in X's (by Y position)
+  bool x_complete;           // kCol only: X is a resident row.  No to_last_x: a run that stops in X's last item is final
 };
 
 template <typename T, bool kCol>
@@ -107,8 +143,9 @@ __device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_
                                            uint32_t side_blocks, bool emit_open, uint32_t problem, uint32_t a, uint32_t b, uint32_t threshold,
                                            uint32_t min_len, NeedleHipRun *__restrict__ runs, uint32_t capacity, uint32_t *__restrict__ count) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  // The runs of one step leave the wave together: one returning atomic for all of them (matcher.hip, search.hip).  The lanes'
-  // indices (a, b: video * regions + region) travel in the simhash fields until the simhash kernel fills them.
+  // The runs of one step leave the wave together: one returning atomic for all of them (matcher.hip, search.hip).  The two
+  // rows (a, b: video * regions + region over all videos, residents first) travel in the simhash fields until the simhash
+  // kernel fills them.
   auto push = [&](const bool want, const uint32_t x, const uint32_t y, const uint32_t len) {
     const unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
     if (mask == 0ull) return;
@@ -160,13 +197,17 @@ __device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_
       }
       push(ended, i0 + c - 1u, sd.y0 + q + c - 1u, len);
     }
-    if (!live) return;
     // the last cell walked (with no cell: the frontier entry itself, which changes hands): it lies in Y's new last item or in
     // X's last; the corner of the two belongs to col
     const uint32_t x = i0 + w - 1u, y = sd.y0 + q + w - 1u;
     const bool last_y = q + w == W, last_x = x == sd.x1 - 1u;
-    if (kCol ? last_y : !last_x) sd.to_last_y[x] = (T)run;
-    else sd.to_last_x[y] = (T)run;
+    const bool to_y = kCol ? last_y : !last_x;
+    if constexpr (kCol) {  // a resident's last row: nothing carries the run, it leaves now (the whole workgroup asks)
+      if (sd.x_complete) push(live && !to_y && run >= min_len, x, y, run);
+    }
+    if (!live) return;
+    if (to_y) sd.to_last_y[x] = (T)run;
+    else if (!kCol || !sd.x_complete) sd.to_last_x[y] = (T)run;
   };
   if (carried) {
     for (uint32_t part = 0; part < kCarriedRows; part += kThreads) {
@@ -184,51 +225,81 @@ __device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_
 
 template <typename T>
 __global__ __launch_bounds__(kThreads) void crossmatch_walk_kernel(const uint32_t *__restrict__ hist, T *__restrict__ state,
-                                                                   const CrossLane *__restrict__ lanes, uint32_t videos, CrossRegions rg,
-                                                                   uint32_t side_blocks, uint32_t threshold,
+                                                                   const CrossLane *__restrict__ lanes,
+                                                                   const CrossResident *__restrict__ resident, uint32_t videos,
+                                                                   CrossRegions rg, uint32_t side_blocks, uint32_t threshold,
                                                                    NeedleHipRun *__restrict__ runs, uint32_t capacity,
                                                                    uint32_t *__restrict__ count) {
   __shared__ uint32_t strip[kMaxStrip];                // Y's new items
   __shared__ uint32_t rows[kCarriedRows + kMaxStrip];  // the X items this workgroup's diagonals meet
-  // the problem of this workgroup: pair * regions + region, the pair i-major as the comparator numbers them (pair_at in
-  // comparator.cpp): row a holds n - 1 - a pairs
-  const uint32_t problem = blockIdx.y;
+  // the live problem of this workgroup: q * regions + region; q = t * K + k for resident k against arriving video t, then
+  // the arriving pairs i-major as the comparator numbers them (pair_at in comparator.cpp): row ta holds videos - 1 - ta pairs
+  const uint32_t per_side = side_blocks + kTopBlocks;
+  const bool col_dir = blockIdx.x < per_side;
   const bool two = rg.regions == 2u;
-  const uint32_t pair = two ? problem >> 1 : problem, r = two ? problem & 1u : 0u;
-  uint32_t a = 0u, first = 0u;
-  while (pair - first >= videos - 1u - a) {
-    first += videos - 1u - a;
-    a++;
+  const uint32_t q = two ? blockIdx.y >> 1 : blockIdx.y, r = two ? blockIdx.y & 1u : 0u;
+  const uint32_t K = rg.residents, V = K + videos, first_lane = two ? 2u * K : K;
+  const bool res = q < K * videos;
+  uint32_t a, b, pair = 0u;  // videos of all V; the pair among the arriving ones
+  if (res) {
+    if (!col_dir) return;  // a resident gains no rows
+    const uint32_t t = q / K;
+    a = q - t * K;
+    b = K + t;
+  } else {
+    pair = q - K * videos;
+    uint32_t ta = 0u, first = 0u;
+    while (pair - first >= videos - 1u - ta) {
+      first += videos - 1u - ta;
+      ta++;
+    }
+    a = K + ta;
+    b = a + 1u + (pair - first);
   }
-  const uint32_t b = a + 1u + (pair - first);
-  const uint32_t lane_a = two ? 2u * a + r : a, lane_b = two ? 2u * b + r : b;
-  const CrossLane la = lanes[lane_a], lb = lanes[lane_b];
+  // the comparator's problem over V videos: row a of its pair numbering starts at a (2 V - a - 1) / 2
+  const uint32_t problem = (uint32_t)((uint64_t)a * (2u * V - a - 1u) / 2u + (b - a - 1u)) * rg.regions + r;
+  const uint32_t row_a = two ? 2u * a + r : a, row_b = two ? 2u * b + r : b;
+  const CrossLane lb = lanes[row_b - first_lane];
+  // a resident is a lane that holds all its items, finished long ago
+  CrossLane la;
+  uint64_t prefix = 0u;
+  if (res) {
+    const CrossResident rr = resident[row_a];
+    la = CrossLane{rr.len, 0u, 0u, kFinished};
+    prefix = rr.prefix;
+  } else {
+    la = lanes[row_a - first_lane];
+  }
   const uint32_t done_a = la.flags & (kFinished | kFinishing), done_b = lb.flags & (kFinished | kFinishing);
   const bool emit_open = done_a && done_b && ((la.flags | lb.flags) & kFinishing);  // the problem becomes complete in this round
   if (la.width == 0u && lb.width == 0u && !emit_open) return;                       // no state traffic
   const uint32_t a0 = max(la.fed, 1u), a1 = max(la.fed + la.width, 1u), b0 = max(lb.fed, 1u), b1 = max(lb.fed + lb.width, 1u);
   if (a1 < 2u || b1 < 2u) return;  // no cells yet: whatever the sets hold is not read before it is written
-  const uint32_t per_side = side_blocks + kTopBlocks;
-  const bool col_dir = blockIdx.x < per_side;
   const uint32_t max_items = region_max_items(rg, r), min_len = r ? rg.min_len1 : rg.min_len0;
-  T *base = state + (r ? rg.state1 : rg.state0) + (uint64_t)pair * 4u * max_items;  // col set 0, row set 0, col set 1, row set 1
+  // an arriving pair: col set 0, row set 0, col set 1, row set 1, each of max_items; a resident one: col set 0, col set 1,
+  // each of the row's own length
+  const uint64_t at = res ? (r ? rg.res_state1 : rg.res_state0) + 2u * ((uint64_t)(b - K) * (r ? rg.res_total1 : rg.res_total0) + prefix)
+                          : (r ? rg.state1 : rg.state0) + (uint64_t)pair * 4u * max_items;
+  const uint64_t col_stride = res ? (uint64_t)la.fed : 2u * (uint64_t)max_items;
+  T *base = state + at;
   const uint32_t cs = lb.flags & kParity, rs = la.flags & kParity;
-  const T *col_from = base + (uint64_t)(2u * cs) * max_items, *row_from = base + (uint64_t)(2u * rs + 1u) * max_items;
-  T *col_to = base + (uint64_t)(2u * (cs ^ (lb.width ? 1u : 0u))) * max_items;
-  T *row_to = base + (uint64_t)(2u * (rs ^ (la.width ? 1u : 0u)) + 1u) * max_items;
-  const uint32_t *region_hist = hist + (r ? rg.hist1 : rg.hist0);
-  const uint32_t *ha = region_hist + (uint64_t)a * max_items, *hb = region_hist + (uint64_t)b * max_items;
+  const T *col_from = base + cs * col_stride, *row_from = base + (uint64_t)(2u * rs + 1u) * max_items;
+  T *col_to = base + (cs ^ (lb.width ? 1u : 0u)) * col_stride;
+  T *row_to = base + (uint64_t)(2u * (rs ^ (la.width ? 1u : 0u)) + 1u) * max_items;  // (no resident reads or writes a row set)
+  const uint32_t *hb = hist + (r ? rg.hist1 : rg.hist0) + (uint64_t)(b - K) * max_items;
+  const uint32_t *ha = res ? hist + (r ? rg.res_hist1 : rg.res_hist0) + prefix : hist + (r ? rg.hist1 : rg.hist0) + (uint64_t)(a - K) * max_items;
   const bool old_cells = a0 >= 2u && b0 >= 2u;
   if (col_dir) {
-    const CrossSide<T> sd{ha, hb, a0, a1, b0, b1, a0, old_cells ? col_from : nullptr, col_to, row_to};
-    cross_walk<T, true>(strip, rows, sd, blockIdx.x, side_blocks, emit_open, problem, lane_a, lane_b, threshold, min_len, runs, capacity, count);
+    const CrossSide<T> sd{ha, hb, a0, a1, b0, b1, a0, old_cells ? col_from : nullptr, col_to, row_to, res};
+    cross_walk<T, true>(strip, rows, sd, blockIdx.x, side_blocks, emit_open, problem, row_a, row_b, threshold, min_len, runs, capacity, count);
   } else {
-    const CrossSide<T> sd{hb, ha, b0, b1, a0, a1, b0 - 1u, old_cells ? row_from : nullptr, row_to, col_to};
-    cross_walk<T, false>(strip, rows, sd, blockIdx.x - per_side, side_blocks, emit_open, problem, lane_a, lane_b, threshold, min_len, runs, capacity, count);
+    const CrossSide<T> sd{hb, ha, b0, b1, a0, a1, b0 - 1u, old_cells ? row_from : nullptr, row_to, col_to, false};
+    cross_walk<T, false>(strip, rows, sd, blockIdx.x - per_side, side_blocks, emit_open, problem, row_a, row_b, threshold, min_len, runs, capacity, count);
   }
 }
 
-__global__ __launch_bounds__(kThreads) void crossmatch_simhash_kernel(const uint32_t *__restrict__ hist, CrossRegions rg,
+__global__ __launch_bounds__(kThreads) void crossmatch_simhash_kernel(const uint32_t *__restrict__ hist,
+                                                                      const CrossResident *__restrict__ resident, CrossRegions rg,
                                                                       NeedleHipRun *__restrict__ runs, uint32_t capacity,
                                                                       const uint32_t *__restrict__ count) {
   const uint32_t total = min(*count, capacity);
@@ -236,9 +307,9 @@ __global__ __launch_bounds__(kThreads) void crossmatch_simhash_kernel(const uint
   const uint32_t lane = threadIdx.x & 63;
   const TransposeLane t = transpose_lane(lane);
   for (uint32_t k = wave; k < total; k += waves) {
-    const NeedleHipRun r = runs[k];  // src_match_hash, dst_match_hash: the two lanes
-    const uint32_t src_hash = wave_simhash32(hist + lane_row(rg, r.src_match_hash) + (r.src_end - r.len), r.len + 1u, lane, t);
-    const uint32_t dst_hash = wave_simhash32(hist + lane_row(rg, r.dst_match_hash) + (r.dst_end - r.len), r.len + 1u, lane, t);
+    const NeedleHipRun r = runs[k];  // src_match_hash, dst_match_hash: the two rows, video * regions + region over all videos
+    const uint32_t src_hash = wave_simhash32(hist + video_row(rg, resident, r.src_match_hash) + (r.src_end - r.len), r.len + 1u, lane, t);
+    const uint32_t dst_hash = wave_simhash32(hist + video_row(rg, resident, r.dst_match_hash) + (r.dst_end - r.len), r.len + 1u, lane, t);
     if (lane == 0) {
       runs[k].src_match_hash = src_hash;
       runs[k].dst_match_hash = dst_hash;
@@ -258,6 +329,26 @@ struct Piece {
   bool finishing = false;
 };
 
+// Shape checks shared by the state size and creation; nullptr: fine.  `resident` holds num_resident * regions rows.
+const char *shape_error(const NeedleHipSeq *resident, size_t num_resident, size_t num_hashes, bool check_arena, size_t videos, size_t regions,
+                        const size_t *max_items) {
+  if (regions < 1 || regions > kMaxRegions) return "crossmatcher: regions must be 1 or 2";
+  if (videos < (num_resident ? 1u : 2u) || videos > kMaxLanes)
+    return num_resident ? "crossmatcher: arriving videos must be 1 to 256" : "crossmatcher: lanes (videos) must be 2 to 256";
+  for (size_t r = 0; r < regions; r++)
+    if (max_items[r] < 2 || max_items[r] > kMaxRowItems) return "crossmatcher: max_items must be 2 to 2^31 - 16";
+  // (videos <= 256 and the first test bound num_resident before anything is multiplied)
+  if (num_resident > kMaxProblems || (num_resident * videos + videos * (videos - 1) / 2) * regions > kMaxProblems)
+    return "crossmatcher: more than 65 535 live problems ((K N + N (N - 1) / 2) x regions)";
+  const uint64_t all = num_resident + videos;
+  if (all * (all - 1) / 2 * regions >= (1ull << 32)) return "crossmatcher: the problem index over all videos does not fit 32 bits";
+  for (size_t i = 0; i < num_resident * regions; i++) {
+    if (resident[i].len > kMaxRowItems) return "crossmatcher: a resident row holds more than 2^31 - 16 hashes";
+    if (check_arena && (uint64_t)resident[i].offset + resident[i].len > num_hashes) return "crossmatcher: a resident row lies outside the hash arena";
+  }
+  return nullptr;
+}
+
 }  // namespace
 
 struct CrossMatcher::Impl {
@@ -268,6 +359,13 @@ struct CrossMatcher::Impl {
   CrossRegions rg{};
   std::vector<LaneState> lanes;
   std::vector<NeedleHipRun> runs;
+  // resident videos: K of them in front of the arriving ones; rows k * regions + r
+  size_t residents = 0;
+  std::vector<NeedleHipSeq> res_rows;               // (the offsets are the caller's arena's: only the lengths are used)
+  uint64_t res_cell_rows[2] = {0, 0};               // per region: the sum over its rows of max(len, 1) - 1
+  uint64_t res_longest = 0;
+  std::vector<std::vector<NeedleHipRun>> held;      // per lane: runs into a resident's last row, held back until it finishes
+  DeviceBuffer<CrossResident> d_resident;
   DeviceBuffer<uint32_t> hist, d_round, slab;
   DeviceBuffer<uint8_t> state;
   uint32_t capacity = 4096;  // runs the slab holds
@@ -284,10 +382,29 @@ struct CrossMatcher::Impl {
   }
 
   size_t pairs() const { return videos * (videos - 1) / 2; }
+  size_t live_pairs() const { return residents * videos + pairs(); }
+
+  // Is this run one into a resident's last row (crossmatch_walk_kernel hands those out early)?  The comparator's pair
+  // numbering over all videos: row a starts at a (2 V - a - 1) / 2, so a resident source is a pair before row K's start.
+  bool into_a_residents_last_row(const NeedleHipRun &run, size_t *lane) const {
+    if (!residents) return false;
+    const uint64_t all = residents + videos, pair = run.problem / regions, r = run.problem % regions;
+    auto row_start = [&](uint64_t a) { return a * (2 * all - a - 1) / 2; };
+    if (pair >= row_start(residents)) return false;
+    uint64_t lo = 0, hi = residents - 1;  // the last a whose row starts at or before `pair`
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi + 1) / 2;
+      if (row_start(mid) <= pair) lo = mid;
+      else hi = mid - 1;
+    }
+    const uint64_t b = lo + 1 + (pair - row_start(lo));
+    *lane = (size_t)((b - residents) * regions + r);
+    return (uint64_t)run.src_end + 1 == res_rows[lo * regions + r].len;
+  }
   size_t capacity_of(size_t lane) const { return max_items[lane % regions]; }
 
-  // cells of all pairs of every region when the lanes hold `fed` (+ `pieces`): per region the sum over a < b of x_a x_b,
-  // x = max(items, 1) - 1
+  // cells of all live pairs of every region when the lanes hold `fed` (+ `pieces`): per region the sum over a < b of x_a x_b,
+  // x = max(items, 1) - 1, and every resident row against every lane
   uint64_t cells_of(const std::vector<Piece> *pieces) const {
     uint64_t total = 0;
     for (size_t r = 0; r < regions; r++) {
@@ -297,7 +414,7 @@ struct CrossMatcher::Impl {
         sum += x;
         squares += x * x;
       }
-      total += (sum * sum - squares) / 2;
+      total += (sum * sum - squares) / 2 + res_cell_rows[r] * sum;
     }
     return total;
   }
@@ -309,7 +426,7 @@ struct CrossMatcher::Impl {
     if (!s.ok()) return s;
     hipStream_t stream = library_stream();
     std::vector<CrossLane> lt(n);
-    uint64_t words = n * (sizeof(CrossLane) / 4), longest = 1;
+    uint64_t words = n * (sizeof(CrossLane) / 4), longest = std::max<uint64_t>(res_longest, 1);
     for (size_t i = 0; i < n; i++) {
       const LaneState &l = lanes[i];
       lt[i] = CrossLane{(uint32_t)l.fed, pieces[i].width, (uint32_t)words,
@@ -327,8 +444,8 @@ struct CrossMatcher::Impl {
 
     const CrossLane *d_lanes = reinterpret_cast<const CrossLane *>(d_round.ptr);
     const dim3 block(kThreads);
-    const uint32_t side_blocks = (uint32_t)((longest + kCarriedRows - 1) / kCarriedRows);  // of the longest lane of any region: the others' leave at once
-    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), (uint32_t)(pairs() * regions));
+    const uint32_t side_blocks = (uint32_t)((longest + kCarriedRows - 1) / kCarriedRows);  // of the longest lane or resident row of any region: the others' leave at once
+    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), (uint32_t)(live_pairs() * regions));
     std::vector<NeedleHipRun> got;
     for (;;) {
       if (!(s = slab.reserve(kHeaderWords + (uint64_t)capacity * (sizeof(NeedleHipRun) / 4))).ok()) return s;
@@ -344,16 +461,16 @@ struct CrossMatcher::Impl {
         KernelTimer timer("crossmatch_walk");
         if (narrow)
           hipLaunchKernelGGL(crossmatch_walk_kernel<uint16_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint16_t *>(state.ptr),
-                             d_lanes, (uint32_t)videos, rg, side_blocks, threshold, d_runs, capacity, d_count);
+                             d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs, capacity, d_count);
         else
           hipLaunchKernelGGL(crossmatch_walk_kernel<uint32_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint32_t *>(state.ptr),
-                             d_lanes, (uint32_t)videos, rg, side_blocks, threshold, d_runs, capacity, d_count);
+                             d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs, capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       {
         KernelTimer timer("crossmatch_simhash");
-        hipLaunchKernelGGL(crossmatch_simhash_kernel, dim3((uint32_t)device_cu_count() * 2u), block, 0, stream, hist.ptr, rg,
-                           d_runs, capacity, d_count);
+        hipLaunchKernelGGL(crossmatch_simhash_kernel, dim3((uint32_t)device_cu_count() * 2u), block, 0, stream, hist.ptr, d_resident.ptr,
+                           rg, d_runs, capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       launches += 3;
@@ -376,12 +493,22 @@ struct CrossMatcher::Impl {
       if (found > first) NEEDLE_HIP_TRY(hipMemcpy(got.data() + first, d_runs + first, (size_t)(found - first) * sizeof(NeedleHipRun), hipMemcpyDeviceToHost));
       break;
     }
-    runs.insert(runs.end(), got.begin(), got.end());
+    // What is open on a frontier is reported when the pair becomes complete: a run into a resident's last row waits for its
+    // lane's finish round (the kernel kept no state for it).
+    for (const NeedleHipRun &run : got) {
+      size_t lane = 0;
+      if (into_a_residents_last_row(run, &lane) && !pieces[lane].finishing) held[lane].push_back(run);
+      else runs.push_back(run);
+    }
     for (size_t i = 0; i < n; i++) {
       LaneState &l = lanes[i];
       l.fed += pieces[i].width;
       if (pieces[i].width) l.parity ^= kParity;
-      if (pieces[i].finishing) l.finished = true;
+      if (pieces[i].finishing) {
+        l.finished = true;
+        runs.insert(runs.end(), held[i].begin(), held[i].end());
+        held[i] = std::vector<NeedleHipRun>();
+      }
     }
     return Status::Ok();
   }
@@ -400,19 +527,27 @@ size_t CrossMatcher::lanes() const { return impl_->n; }
 size_t CrossMatcher::videos() const { return impl_->videos; }
 size_t CrossMatcher::regions() const { return impl_->regions; }
 
+size_t CrossMatcher::residents() const { return impl_->residents; }
+
 size_t CrossMatcher::StateBytes(size_t lanes, size_t max_items) { return StateBytesRegions(lanes, 1, &max_items); }
 
 size_t CrossMatcher::StateBytesRegions(size_t videos, size_t regions, const size_t *max_items) {
-  if (videos < 2 || videos > kMaxLanes || regions < 1 || regions > kMaxRegions || !max_items) return 0;
+  return StateBytesResident(nullptr, 0, videos, regions, max_items);
+}
+
+size_t CrossMatcher::StateBytesResident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items) {
+  if (!max_items || (num_resident && !resident) || shape_error(resident, num_resident, 0, false, videos, regions, max_items)) return 0;
   bool narrow = true;
-  for (size_t r = 0; r < regions; r++) {
-    if (max_items[r] < 2 || max_items[r] > 0x7FFFFFF0ull) return 0;
-    narrow = narrow && max_items[r] < 65536;
-  }
-  const size_t pairs = videos * (videos - 1) / 2;
+  for (size_t r = 0; r < regions; r++) narrow = narrow && max_items[r] < 65536;
+  for (size_t i = 0; i < num_resident * regions; i++) narrow = narrow && resident[i].len < 65536;
+  const size_t pairs = videos * (videos - 1) / 2, width = narrow ? sizeof(uint16_t) : sizeof(uint32_t);
   size_t bytes = 0;
-  for (size_t r = 0; r < regions; r++)
-    bytes += pairs * 2 * 2 * max_items[r] * (narrow ? sizeof(uint16_t) : sizeof(uint32_t)) + videos * max_items[r] * sizeof(uint32_t);
+  for (size_t r = 0; r < regions; r++) {
+    size_t hashes = 0;  // S_r
+    for (size_t k = 0; k < num_resident; k++) hashes += resident[k * regions + r].len;
+    bytes += pairs * 2 * 2 * max_items[r] * width + videos * max_items[r] * sizeof(uint32_t)  // the arriving pairs' L frontiers, the histories
+             + videos * 2 * hashes * width + hashes * sizeof(uint32_t);                        // the resident col frontiers, the resident hashes
+  }
   return bytes;
 }
 
@@ -422,21 +557,42 @@ Status CrossMatcher::Create(size_t lanes, size_t max_items, uint32_t min_len, ui
 
 Status CrossMatcher::CreateRegions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
                                    std::unique_ptr<CrossMatcher> *out) {
-  if (!out || !max_items || !min_len) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
-  if (regions < 1 || regions > kMaxRegions) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: regions must be 1 or 2");
-  if (videos < 2 || videos > kMaxLanes) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: lanes (videos) must be 2 to 256");
-  for (size_t r = 0; r < regions; r++) {
-    if (max_items[r] < 2 || max_items[r] > 0x7FFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: max_items must be 2 to 2^31 - 16");
+  return CreateResident(nullptr, 0, nullptr, 0, videos, regions, max_items, min_len, threshold, out);
+}
+
+Status CrossMatcher::CreateResident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident, size_t videos,
+                                    size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                                    std::unique_ptr<CrossMatcher> *out) {
+  if (!out || !max_items || !min_len || (num_resident && !resident) || (num_hashes && !hashes))
+    return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  if (const char *what = shape_error(resident, num_resident, num_hashes, true, videos, regions, max_items))
+    return Status::Make(NeedleError_InvalidArgument, what);
+  for (size_t r = 0; r < regions; r++)
     if (min_len[r] == 0) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: min_len must be >= 1");
-  }
   std::unique_ptr<CrossMatcher> cm(new CrossMatcher());
   Impl &m = *cm->impl_;
   m.videos = videos;
   m.regions = regions;
+  m.residents = num_resident;
   m.n = videos * regions;
   m.threshold = threshold;
   m.lanes = std::vector<LaneState>(m.n);
-  // histories and frontiers region after region: the bases in words and in entries
+  m.held.resize(m.n);
+  m.res_rows.assign(resident, resident + num_resident * regions);
+  // the resident table: per region, a row's place among the region's resident hashes
+  std::vector<CrossResident> table(num_resident * regions);
+  size_t res_total[2] = {0, 0};
+  for (size_t k = 0; k < num_resident; k++)
+    for (size_t r = 0; r < regions; r++) {
+      const NeedleHipSeq &row = resident[k * regions + r];
+      table[k * regions + r] = CrossResident{res_total[r], row.len, 0u};
+      res_total[r] += row.len;
+      m.res_cell_rows[r] += std::max<uint64_t>(row.len, 1) - 1;
+      m.res_longest = std::max<uint64_t>(m.res_longest, row.len);
+      m.narrow = m.narrow && row.len < 65536;
+    }
+  // histories and frontiers region after region, then the resident hashes and the resident frontiers region after region:
+  // the bases in words and in entries
   size_t hist_words = 0, state_entries = 0;
   for (size_t r = 0; r < regions; r++) {
     m.max_items[r] = max_items[r];
@@ -447,7 +603,16 @@ Status CrossMatcher::CreateRegions(size_t videos, size_t regions, const size_t *
     hist_words += videos * max_items[r];
     state_entries += m.pairs() * 4 * max_items[r];
   }
+  const size_t first_resident_word = hist_words;
+  for (size_t r = 0; r < regions; r++) {
+    (r ? m.rg.res_hist1 : m.rg.res_hist0) = hist_words;
+    (r ? m.rg.res_state1 : m.rg.res_state0) = state_entries;
+    (r ? m.rg.res_total1 : m.rg.res_total0) = res_total[r];
+    hist_words += res_total[r];
+    state_entries += videos * 2 * res_total[r];
+  }
   m.rg.regions = (uint32_t)regions;
+  m.rg.residents = (uint32_t)num_resident;
   m.rg.max_items0 = (uint32_t)m.max_items[0];
   m.rg.max_items1 = (uint32_t)m.max_items[regions - 1];
   m.rg.min_len0 = m.min_len[0];
@@ -461,6 +626,20 @@ Status CrossMatcher::CreateRegions(size_t videos, size_t regions, const size_t *
   const size_t state_bytes = state_entries * (m.narrow ? sizeof(uint16_t) : sizeof(uint32_t));
   if (!(s = m.hist.reserve(hist_words)).ok() || !(s = m.state.reserve(state_bytes)).ok()) return s;
   NEEDLE_HIP_TRY(hipMemsetAsync(m.state.ptr, 0, state_bytes, stream));
+  if (num_resident) {  // the rows packed in table order, and the table: this once
+    std::vector<uint32_t> packed(hist_words - first_resident_word);
+    for (size_t i = 0; i < table.size(); i++) {
+      const size_t r = i % regions;
+      if (table[i].len)
+        std::memcpy(packed.data() + ((r ? m.rg.res_hist1 : m.rg.res_hist0) - first_resident_word) + table[i].prefix, hashes + resident[i].offset,
+                    (size_t)table[i].len * sizeof(uint32_t));
+    }
+    if (!(s = m.d_resident.reserve(table.size())).ok()) return s;
+    if (!packed.empty())
+      NEEDLE_HIP_TRY(hipMemcpyAsync(m.hist.ptr + first_resident_word, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_resident.ptr, table.data(), table.size() * sizeof(CrossResident), hipMemcpyHostToDevice, stream));
+    NEEDLE_HIP_TRY(hipStreamSynchronize(stream));  // (before `packed` goes)
+  }
   NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
   *out = std::move(cm);
   return Status::Ok();
@@ -572,7 +751,8 @@ void CrossMatcher::Stats(uint64_t stats[4]) const {
   stats[0] = m.feeds;
   stats[1] = m.launches;
   stats[2] = m.cells;
-  stats[3] = StateBytesRegions(m.videos, m.regions, m.max_items) + kHeaderWords * 4 + (uint64_t)m.capacity * sizeof(NeedleHipRun);
+  stats[3] = StateBytesResident(m.res_rows.data(), m.residents, m.videos, m.regions, m.max_items) + m.res_rows.size() * sizeof(CrossResident) +
+             kHeaderWords * 4 + (uint64_t)m.capacity * sizeof(NeedleHipRun);
 }
 
 }  // namespace needle

@@ -424,5 +424,25 @@ extern "C" {
     pub fn needle_hip_crossmatcher_state_bytes(lanes: usize, max_items: usize) -> usize;
     pub fn needle_hip_crossmatcher_state_bytes_regions(videos: usize, regions: usize, max_items: *const usize) -> usize;
     pub fn needle_hip_crossmatcher_shape(matcher: *const NeedleHipCrossMatcher, videos: *mut usize, regions: *mut usize) -> NeedleError;
+    pub fn needle_hip_crossmatcher_new_resident(
+        hashes: *const u32,
+        num_hashes: usize,
+        resident: *const NeedleHipSeq,
+        num_resident: usize,
+        videos: usize,
+        regions: usize,
+        max_items: *const usize,
+        min_len: *const u32,
+        threshold: u32,
+        output: *mut *mut NeedleHipCrossMatcher,
+    ) -> NeedleError;
+    pub fn needle_hip_crossmatcher_state_bytes_resident(
+        resident: *const NeedleHipSeq,
+        num_resident: usize,
+        videos: usize,
+        regions: usize,
+        max_items: *const usize,
+    ) -> usize;
+    pub fn needle_hip_crossmatcher_resident(matcher: *const NeedleHipCrossMatcher, num_resident: *mut usize) -> NeedleError;
     pub fn needle_hip_host_free(ptr: *mut c_void);
 }

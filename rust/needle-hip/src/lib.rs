@@ -664,7 +664,53 @@ impl CrossMatcher {
         Ok(CrossMatcher { raw, lanes: videos * regions })
     }
 
-    /// `(videos, regions)`: the object has `videos * regions` lanes.
+    /// A new season joins a library: `resident` holds the hashes of the K known videos in row order (video k, region r at
+    /// `k * regions + r`, regions = `max_items.len()`), uploaded here; `videos` arriving videos follow them in the video list
+    /// and own the `videos * regions` lanes.  Only pairs with an arriving end are searched; `problem` of a run numbers the
+    /// pairs over all K + `videos` videos, so the list goes into `results_from_runs` with `first_video = K`.
+    pub fn with_resident(resident: &[&[u32]], videos: usize, max_items: &[usize], min_len: &[u32], threshold: u32) -> Result<Self> {
+        assert_eq!(max_items.len(), min_len.len(), "one max_items and one min_len per region");
+        let regions = max_items.len();
+        assert!(regions > 0 && resident.len() % regions == 0, "one resident row per video and region");
+        let mut arena: Vec<u32> = Vec::new();
+        let mut seqs = Vec::with_capacity(resident.len());
+        for hashes in resident {
+            seqs.push(ffi::NeedleHipSeq { offset: arena.len() as u32, len: hashes.len() as u32 });
+            arena.extend_from_slice(hashes);
+        }
+        let mut raw = ptr::null_mut();
+        unsafe {
+            check(ffi::needle_hip_crossmatcher_new_resident(
+                arena.as_ptr(),
+                arena.len(),
+                seqs.as_ptr(),
+                seqs.len() / regions,
+                videos,
+                regions,
+                max_items.as_ptr(),
+                min_len.as_ptr(),
+                threshold,
+                &mut raw,
+            ))?
+        };
+        Ok(CrossMatcher { raw, lanes: videos * regions })
+    }
+
+    /// The known videos the object was created with (0 without `with_resident`).
+    pub fn resident(&self) -> Result<usize> {
+        let mut k = 0usize;
+        unsafe { check(ffi::needle_hip_crossmatcher_resident(self.raw, &mut k))? };
+        Ok(k)
+    }
+
+    /// Bytes of device state of a matcher with resident rows of these lengths (row order); 0 where an argument is out of range.
+    pub fn state_bytes_resident(resident_len: &[u32], videos: usize, max_items: &[usize]) -> usize {
+        let regions = max_items.len().max(1);
+        let seqs: Vec<ffi::NeedleHipSeq> = resident_len.iter().map(|&len| ffi::NeedleHipSeq { offset: 0, len }).collect();
+        unsafe { ffi::needle_hip_crossmatcher_state_bytes_resident(seqs.as_ptr(), seqs.len() / regions, videos, max_items.len(), max_items.as_ptr()) }
+    }
+
+    /// `(videos, regions)`: the arriving videos; the object has `videos * regions` lanes.
     pub fn shape(&self) -> Result<(usize, usize)> {
         let (mut videos, mut regions) = (0usize, 0usize);
         unsafe { check(ffi::needle_hip_crossmatcher_shape(self.raw, &mut videos, &mut regions))? };

@@ -27,12 +27,19 @@ items per lane and feed).
              target.  And the single-region path on both trees: regions = 1 at 28 and 64 lanes holding 24 minutes, per-feed
              wall and the walk kernel's event time, this tree and the parent alternating, the one that goes first alternating
              too; the difference of the medians must lie within the parent's own spread.  (--parent, built)
+  resident : a new season into a library in ONE object (needle_hip_crossmatcher_new_resident: 1 000 resident videos of 5 441
+             hashes, 28 arriving lanes, one region) against what a caller needed before it, one Matcher (1 000 sources, 28
+             lanes) plus one CrossMatcher(28) fed in turn on the parent commit's library: taken when the lanes hold 1 100 items,
+             4 new items per lane and feed.  Wall ms per feed (median of 30 after 10; for the two objects a feed is both
+             calls) and, in a pass of its own, the summed event times of the kernels (mean of 30); five processes each,
+             alternating.  The condition is the regions leg's; the ratio and the state bytes are recorded, neither is a
+             target.  The single-region, no-resident path on both trees is the regions leg's second half.  (--parent, built)
   headline : bench.py --gpus 1 --steps 20 --warmup 5, parent and this tree alternating, four runs each, the tree that goes
              first alternating too (--parent, built).
 
 Sections that were not run keep what the file held, or "not measured".
 
-usage: python tools/bench_crossmatch.py [--only per_feed,tail,season,resources,regions,headline] [--parent DIR]"""
+usage: python tools/bench_crossmatch.py [--only per_feed,tail,season,resources,regions,resident,headline] [--parent DIR]"""
 import argparse
 import json
 import os
@@ -300,6 +307,95 @@ def bench_regions(root, parent):
     return res
 
 
+_RESIDENT_CHILD = """
+import json, statistics, sys, time
+import numpy as np
+from needle_amd import capi
+mode, residents, videos, items, held = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5])
+chunk, threshold, min_len = 4, 10, 80
+rng = np.random.default_rng(7)
+rows = rng.integers(0, 2 ** 32, (residents, items), dtype=np.uint64).astype(np.uint32)
+data = rng.integers(0, 2 ** 32, (videos, items), dtype=np.uint64).astype(np.uint32)
+shared = rng.integers(0, 2 ** 32, 360, dtype=np.uint64).astype(np.uint32)      # one shared stretch of 360 items in every video
+for d in (rows, data):
+    for k in range(len(d)):
+        at = 100 + 17 * (k % 40)
+        d[k, at:at + 360] = shared ^ (np.uint32(1) << rng.integers(0, 32, 360).astype(np.uint32))
+if mode == "one":                                    # the residents and the arriving lanes in one object
+    m = capi.CrossMatcher.with_resident(list(rows), videos, [items], [min_len], threshold)
+    kernels = ("crossmatch_land", "crossmatch_walk", "crossmatch_simhash")
+    def feed(a, b):
+        m.feed([row[a:b] for row in data])
+    def finish():
+        m.finish()
+        return m.ready()[0], m.stats()[1], m.stats()[3]
+else:                                                # old x new in a Matcher, new x new in a CrossMatcher, fed in turn
+    old = capi.Matcher(list(rows), [min_len] * residents, videos, threshold)
+    new = capi.CrossMatcher(videos, items, min_len, threshold)
+    kernels = ("matcher_land", "matcher_strip", "matcher_simhash", "crossmatch_land", "crossmatch_walk", "crossmatch_simhash")
+    def feed(a, b):
+        chunks = [row[a:b] for row in data]
+        old.feed(chunks)
+        new.feed(chunks)
+    def finish():
+        old.finish()
+        new.finish()
+        return sum(old.ready(k)[0] for k in range(videos)) + new.ready()[0], old.stats()[1] + new.stats()[1], old.stats()[3] + new.stats()[3]
+def timed(pos, count):
+    out = []
+    for _ in range(count):
+        t0 = time.perf_counter()
+        feed(pos, pos + chunk)
+        out.append((time.perf_counter() - t0) * 1e3)
+        pos += chunk
+    return out, pos
+t0 = time.perf_counter()
+feed(0, held)
+fill = time.perf_counter() - t0
+_, pos = timed(held, 10)
+wall, pos = timed(pos, 30)
+capi.set_kernel_timing(",".join(kernels) + ",sum")
+_, pos = timed(pos, 30)
+capi.synchronize()
+ms = {k: capi.last_kernel_ms(k) / 30 for k in kernels}
+capi.set_kernel_timing(None)
+runs, launches, state = finish()
+print(json.dumps({"wall_ms_per_feed_median": statistics.median(wall), "wall_ms_min_max": [min(wall), max(wall)],
+                  "kernel_ms_per_feed": ms, "kernel_ms_per_feed_sum": sum(ms.values()), "fill_to_level_s": fill,
+                  "launches": launches, "runs": runs, "state_bytes": state}))
+"""
+
+
+def bench_resident(root, parent, residents=1000, videos=SEASON_LANES, items=5441, held=1100):
+    def child(tree, mode):
+        run = subprocess.run([sys.executable, "-c", _RESIDENT_CHILD, mode, str(residents), str(videos), str(items), str(held)], cwd=tree,
+                             env=dict(os.environ, PYTHONPATH=tree), stdout=subprocess.PIPE, text=True, timeout=900, check=True)
+        return json.loads(run.stdout.strip().splitlines()[-1])
+
+    def summary(runs, key):
+        vals = [r[key] for r in runs]
+        return {"runs": [round(v, 5) for v in vals], "median": round(statistics.median(vals), 5), "spread": round(max(vals) - min(vals), 5)}
+    one, parts = [], []
+    for _ in range(5):                                                           # the two alternate, the yardstick first
+        parts.append(child(parent, "parts"))
+        one.append(child(root, "one"))
+        print("resident", parts[-1]["wall_ms_per_feed_median"], one[-1]["wall_ms_per_feed_median"], file=sys.stderr, flush=True)
+    assert all(r["runs"] == one[0]["runs"] for r in one + parts), [r["runs"] for r in one + parts]
+    wall_one, wall_parts = summary(one, "wall_ms_per_feed_median"), summary(parts, "wall_ms_per_feed_median")
+    return {"residents": residents, "arriving_videos": videos, "items_per_video": items, "items_held": held, "chunk_items": CHUNK,
+            "live_problems": residents * videos + videos * (videos - 1) // 2, "runs": one[0]["runs"],
+            "resident_cells_per_feed": CHUNK * videos * residents * (items - 1),
+            "launches_in_the_process": {"one_object": one[0]["launches"], "matcher_plus_crossmatcher": parts[0]["launches"]},
+            "state_bytes": {"one_object": one[0]["state_bytes"], "matcher_plus_crossmatcher": parts[0]["state_bytes"]},
+            "fill_to_level_s": {"one_object": summary(one, "fill_to_level_s"), "matcher_plus_crossmatcher_on_the_parent": summary(parts, "fill_to_level_s")},
+            "wall_ms_per_feed": {"one_object": wall_one, "matcher_plus_crossmatcher_on_the_parent": wall_parts},
+            "kernel_ms_per_feed_sum": {"one_object": summary(one, "kernel_ms_per_feed_sum"),
+                                       "matcher_plus_crossmatcher_on_the_parent": summary(parts, "kernel_ms_per_feed_sum")},
+            "kernel_ms_per_feed": {"one_object": one[0]["kernel_ms_per_feed"], "matcher_plus_crossmatcher_on_the_parent": parts[0]["kernel_ms_per_feed"]},
+            "condition_one_within_yardstick_plus_its_spread": wall_one["median"] <= wall_parts["median"] + wall_parts["spread"],
+            "ratio_parts_to_one": round(wall_parts["median"] / wall_one["median"], 3)}
+
+
 def bench_resources(root, parent):
     BM.RESOURCE_FILES = ["crossmatch.hip", "matcher.hip", "search.hip", "fingerprint.hip", "fingerprint32.hip", "feeder.hip"]
     this = BM.kernel_resources(root)
@@ -339,7 +435,7 @@ def bench_headline(root, parent, repeats=4):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="per_feed,tail,season,resources,regions,headline")
+    ap.add_argument("--only", default="per_feed,tail,season,resources,regions,resident,headline")
     ap.add_argument("--parent", default=None, help="a checkout of the parent commit, built (yardstick, resources, headline)")
     ap.add_argument("--repeats", type=int, default=4, help="headline runs per tree")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "crossmatch_bench.json"))
@@ -348,7 +444,7 @@ def main():
         args.parent = os.path.abspath(args.parent)
     from needle_amd import capi
     only = set(args.only.split(","))
-    keys = ("device", "per_feed", "tail", "season", "resources", "regions", "headline_vs_parent")
+    keys = ("device", "per_feed", "tail", "season", "resources", "regions", "resident", "headline_vs_parent")
     res = {k: NOT_MEASURED for k in keys}
     if os.path.exists(args.out):
         try:
@@ -371,6 +467,9 @@ def main():
                 save()
         if "regions" in only and args.parent:
             res["regions"] = bench_regions(ROOT, args.parent)
+            save()
+        if "resident" in only and args.parent:
+            res["resident"] = bench_resident(ROOT, args.parent)
             save()
         if "headline" in only and args.parent:
             res["headline_vs_parent"] = bench_headline(ROOT, args.parent, args.repeats)
