@@ -316,8 +316,9 @@ size_t needle_hip_index_len(const NeedleHipIndex *index); /* videos added (0 for
 enum NeedleError needle_hip_index_add(NeedleHipIndex *index, const FrameHashes *const *frame_hashes, size_t k);
 /* One result per video added, in insertion order; n >= needle_hip_index_len(index) (NeedleError_InvalidArgument otherwise). */
 enum NeedleError needle_hip_index_results(const NeedleHipIndex *index, NeedleHipSearchResult *results, size_t n);
-/* Video pairs handed to the scan: over the index's life (*total) and by the last successful add (*last).  A pair none
- * of whose sequences can hold a run long enough is left out, as in the full search.  Either pointer may be NULL. */
+/* Video pairs that entered the index: over its life (*total) and by the last successful add (*last).  A pair none
+ * of whose sequences can hold a run long enough is left out, as in the full search.  Either pointer may be NULL.
+ * (needle_hip_index_pairs_scanned: those of them the one-shot scan searched.) */
 enum NeedleError needle_hip_index_pairs_searched(const NeedleHipIndex *index, uint64_t *total, uint64_t *last);
 /* Removes the videos at k >= 1 distinct positions (< needle_hip_index_len).  The others keep their relative order.  Results
  * then equal run_with_frame_hashes over the remaining list.  No pair is scanned (pairs_searched: *last = 0, total unchanged).
@@ -688,9 +689,9 @@ enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint6
  * V (V - 1) / 2 x regions < 2^32.  NULL arrays (hashes with num_hashes > 0, resident with num_resident > 0, max_items,
  * min_len) or a NULL output: NullArgument.
  *
- * Out of scope: `reset`, `open`, more than two regions, several ranks, feeding the device epilogue or the index;
- * refreshed results for the resident videos (their candidate lists also need the old pairs' runs); resident rows taken
- * from a device arena.
+ * Out of scope: `reset`, `open`, more than two regions, several ranks.  Feeding the index, refreshed results for the
+ * resident videos (their candidate lists also need the old pairs' entries, which the index holds) and resident rows taken
+ * from a device arena are what needle_hip_index_crossmatcher_new / needle_hip_index_add_matched below do.
  *
  * lanes (videos) must be 2..256 (32 640 pairs: pair * regions + region is a grid dimension).  max_items >= 2 is the
  * capacity of every lane (of the region); state and histories are allocated at creation.  lanes, regions or max_items
@@ -744,6 +745,37 @@ enum NeedleError needle_hip_crossmatcher_resident(const NeedleHipCrossMatcher *m
 /* what the object was created with (regions = 1 for needle_hip_crossmatcher_new): the arriving videos and the regions; it
  * has videos * regions lanes */
 enum NeedleError needle_hip_crossmatcher_shape(const NeedleHipCrossMatcher *matcher, size_t *videos, size_t *regions);
+
+/* ---- A streamed season into the index: its cross-matcher's runs in place of a second scan ------------------------
+ * decoders -> feeder -> cross-matcher (made from the index) -> index.  needle_hip_index_crossmatcher_new makes the
+ * object of needle_hip_crossmatcher_new_resident whose K resident videos are the index's, in the index's order: their rows
+ * are gathered on the device from the index's hash arena (one launch; no hashes are uploaded, only the row table).
+ * regions and threshold are the index's; max_items[r] and min_len[r] are the caller's.  The matcher remembers the index
+ * (by an id from a process-wide counter) and the index's generation, which every successful add, remove, replace and
+ * add_matched advances.
+ *
+ * needle_hip_index_add_matched appends the k = videos arriving videos of a complete matcher, with the runs it holds in
+ * place of the scan.  Afterwards the index is what needle_hip_index_add(frame_hashes, k) leaves: the results of all
+ * K + k videos (those of the K known ones refreshed), the same store, the same pairs_searched.  The run list goes up
+ * once; one kernel re-tags it for the store and drops what the scan's problems exclude (a region one of whose rows can hold
+ * no run long enough, a run shorter than max(min_len) of its two rows).  No pair is scanned: pairs_scanned *last = 0.
+ * frame_hashes[t] is arriving video t (rows: lanes t * regions + r), e.g. from needle_hip_feeder_frame_hashes.
+ *
+ * Refused, before anything is committed and with the index exactly as it was (NeedleError_InvalidArgument unless noted):
+ * a matcher not created from this index; a stale one (the index changed since its creation: a matcher is consumed once);
+ * one that is not complete; k != its videos; a row whose length is not its lane's items_fed; a row whose hashes differ
+ * from what the lane was fed (compared on the device); a min_len[r] above the smallest max(min_len) of a live pair whose
+ * two rows can both hold a run (the matcher has then lost runs); a run that does not lie inside its rows; whatever
+ * needle_hip_index_add refuses, in the same words; a poisoned matcher (its error); a matcher on another device.
+ * NULL index, matcher, arrays or output: NeedleError_NullArgument. */
+enum NeedleError needle_hip_index_crossmatcher_new(NeedleHipIndex *index, size_t videos, const size_t *max_items, const uint32_t *min_len,
+                                                   NeedleHipCrossMatcher **output);
+enum NeedleError needle_hip_index_add_matched(NeedleHipIndex *index, NeedleHipCrossMatcher *matcher,
+                                              const FrameHashes *const *frame_hashes, size_t k);
+/* Video pairs handed to the one-shot scan: over the index's life (*total) and by the last successful operation (*last: 0
+ * after add_matched and remove).  needle_hip_index_pairs_searched counts the pairs that entered the index either way.
+ * Either pointer may be NULL. */
+enum NeedleError needle_hip_index_pairs_scanned(const NeedleHipIndex *index, uint64_t *total, uint64_t *last);
 
 #ifdef __cplusplus
 }

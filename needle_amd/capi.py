@@ -101,7 +101,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_scan_counts", "needle_hip_scan_last_launch", "needle_hip_epilogue_host_fallbacks",
     "needle_hip_index_new", "needle_hip_index_free", "needle_hip_index_len", "needle_hip_index_add",
     "needle_hip_index_results", "needle_hip_index_pairs_searched", "needle_hip_index_remove", "needle_hip_index_replace",
-    "needle_hip_index_store_sizes",
+    "needle_hip_index_store_sizes", "needle_hip_index_crossmatcher_new", "needle_hip_index_add_matched",
+    "needle_hip_index_pairs_scanned",
     "needle_hip_convert_host", "needle_hip_analyzer_run_pcm_format", "needle_hip_library_set_sample_format",
     "needle_hip_feeder_new", "needle_hip_feeder_free", "needle_hip_feeder_feed", "needle_hip_feeder_finish",
     "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
@@ -276,6 +277,9 @@ def lib():
     L.needle_hip_index_add.argtypes = [vp, C.POINTER(vp), sz]
     L.needle_hip_index_results.argtypes = [vp, C.POINTER(CSearchResult), sz]
     L.needle_hip_index_pairs_searched.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.needle_hip_index_pairs_scanned.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.needle_hip_index_crossmatcher_new.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(u32), C.POINTER(vp)]
+    L.needle_hip_index_add_matched.argtypes = [vp, vp, C.POINTER(vp), sz]
     L.needle_hip_feeder_new.argtypes = [sz, C.c_int, C.c_int, C.c_int, u32, C.POINTER(vp)]
     L.needle_hip_feeder_free.argtypes = [vp]
     L.needle_hip_feeder_free.restype = None
@@ -697,6 +701,7 @@ class Index:
         out = C.c_void_p()
         check(lib().needle_hip_index_new(comparator.handle(), C.byref(out)))
         self._h = out
+        self.threshold = comparator._cfg["threshold"]   # copied, as the index copies it
 
     def add(self, frame_hashes: Sequence[FrameHashes]) -> None:
         """Appends the videos; on failure (NeedleError) the index is as it was before the call."""
@@ -720,6 +725,36 @@ class Index:
         ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
         check(lib().needle_hip_index_replace(self._h, pos, ptrs, C.c_size_t(k)))
 
+    def crossmatcher(self, videos: int, max_items: Sequence[int], min_len: Sequence[int]) -> "CrossMatcher":
+        """A CrossMatcher whose resident videos are this index's (their rows copied from the index's device arena) with
+        `videos` arriving ones; one max_items and one min_len per region of the index.  Feed it, then add_matched."""
+        if len(max_items) != len(min_len):
+            raise ValueError(f"one max_items and one min_len per region: {len(max_items)} and {len(min_len)}")
+        regions = len(max_items)
+        h = C.c_void_p()
+        check(lib().needle_hip_index_crossmatcher_new(self._h, videos, (C.c_size_t * max(regions, 1))(*max_items),
+                                                      (C.c_uint32 * max(regions, 1))(*min_len), C.byref(h)))
+        m = CrossMatcher.__new__(CrossMatcher)
+        m._h = h
+        videos, regions = m.shape()
+        m.lanes, m.max_items, m.min_len, m.threshold = videos * regions, tuple(max_items), tuple(min_len), self.threshold
+        return m
+
+    def add_matched(self, matcher: "CrossMatcher", frame_hashes: Sequence[FrameHashes]) -> None:
+        """Appends the matcher's arriving videos (complete, made by crossmatcher() since the last change) with the runs it
+        holds in place of a scan; afterwards the index is what add(frame_hashes) leaves.  On failure (NeedleError) the
+        index is as it was before the call."""
+        k = len(frame_hashes)
+        ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
+        check(lib().needle_hip_index_add_matched(self._h, matcher._h, ptrs, k))
+
+    def pairs_scanned(self) -> Tuple[int, int]:
+        """(total, last): video pairs handed to the one-shot scan over the index's life and by the last operation (0 after
+        add_matched)."""
+        total, last = C.c_uint64(), C.c_uint64()
+        check(lib().needle_hip_index_pairs_scanned(self._h, C.byref(total), C.byref(last)))
+        return total.value, last.value
+
     def store_sizes(self) -> Tuple[int, int, int, int]:
         """(heap entries held, entry slots in use, hashes in the device arena, timestamps in the device table)."""
         sizes = (C.c_uint64 * 4)()
@@ -733,7 +768,7 @@ class Index:
         return _results(res, n)
 
     def pairs_searched(self) -> Tuple[int, int]:
-        """(total, last): video pairs handed to the scan over the index's life and by the last add."""
+        """(total, last): video pairs that entered the index over its life and by the last add."""
         total, last = C.c_uint64(), C.c_uint64()
         check(lib().needle_hip_index_pairs_searched(self._h, C.byref(total), C.byref(last)))
         return total.value, last.value

@@ -1190,6 +1190,41 @@ enum NeedleError needle_hip_index_pairs_searched(const NeedleHipIndex *index, ui
   return NeedleError_Ok;
 }
 
+enum NeedleError needle_hip_index_pairs_scanned(const NeedleHipIndex *index, uint64_t *total, uint64_t *last) {
+  if (!index) return NeedleError_NullArgument;
+  if (total) *total = index->inner.scanned_total();
+  if (last) *last = index->inner.scanned_last();
+  return NeedleError_Ok;
+}
+
+enum NeedleError needle_hip_index_crossmatcher_new(NeedleHipIndex *index, size_t videos, const size_t *max_items, const uint32_t *min_len,
+                                                   NeedleHipCrossMatcher **output) {
+  if (!index || !max_items || !min_len || !output) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipCrossMatcher>();
+    Status s = index->inner.crossmatcher(videos, max_items, min_len, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_index_add_matched(NeedleHipIndex *index, NeedleHipCrossMatcher *matcher, const FrameHashes *const *frame_hashes,
+                                              size_t k) {
+  if (!index || !matcher) return NeedleError_NullArgument;
+  if (k == 0) return report(Status::Make(NeedleError_InvalidArgument, "index add: no videos"));
+  if (!frame_hashes) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    Status s = index->inner.add_matched(matcher->inner.get(), fh);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 enum NeedleError needle_hip_index_remove(NeedleHipIndex *index, const size_t *positions, size_t k) {
   if (!index || !positions) return NeedleError_NullArgument;
   if (k == 0) return report(Status::Make(NeedleError_InvalidArgument, "index remove: no positions"));

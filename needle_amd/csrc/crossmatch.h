@@ -5,6 +5,7 @@
 #pragma once
 
 #include <memory>
+#include <vector>
 
 #include "common.h"
 #include "feeder.h"
@@ -24,6 +25,11 @@ class CrossMatcher {
   static Status CreateResident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident, size_t videos,
                                size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
                                std::unique_ptr<CrossMatcher> *out);
+  // The same object with `hashes` an arena in DEVICE memory (the index store's): the rows are gathered into the histories
+  // by one launch, no hashes are uploaded; only the resident table goes up.
+  static Status CreateResidentDevice(const uint32_t *d_hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                                     size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                                     std::unique_ptr<CrossMatcher> *out);
   ~CrossMatcher();
   size_t lanes() const;  // videos * regions
   size_t residents() const;
@@ -44,7 +50,26 @@ class CrossMatcher {
   // is 4 as soon as one max_items or one resident row reaches 65 536
   static size_t StateBytesResident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items);
 
+  // The argument checks of creation without the arena's bounds and without a device: null where they pass, else what to say.
+  static const char *ShapeError(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items,
+                                const uint32_t *min_len);
+
+  // What an index needs of a matcher it made (Index::crossmatcher, Index::add_matched).
+  struct Origin {  // the index and its generation at creation; index_id 0: not made from an index
+    uint64_t index_id = 0, generation = 0;
+  };
+  void set_origin(const Origin &origin);
+  Origin origin() const;
+  int device() const;  // the device current at creation
+  uint32_t min_len(size_t region) const;
+  Status poisoned() const;                             // the device failure every call returns, or Ok
+  const std::vector<NeedleHipRun> &run_list() const;   // what Runs copies from
+  const uint32_t *history(size_t lane) const;          // device: the lane's hashes so far, items_fed of them
+
  private:
+  static Status CreateFrom(const uint32_t *hashes, bool on_device, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                           size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                           std::unique_ptr<CrossMatcher> *out);
   CrossMatcher();
   struct Impl;
   std::unique_ptr<Impl> impl_;

@@ -97,7 +97,8 @@ struct CrossRegions {
 // One resident row, uploaded once at creation.
 struct CrossResident {
   uint64_t prefix;  // the lengths of the region's rows before this one
-  uint32_t len, pad;
+  uint32_t len;
+  uint32_t src;     // where the row lies in the arena it was taken from (crossmatch_gather_resident_kernel; no round reads it)
 };
 static_assert(sizeof(CrossResident) == 16, "resident table entries are 4 words");
 
@@ -220,6 +221,20 @@ __device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_
   } else {
     const uint32_t q = q0 + tid;  // enters through X's item 1 at Y's item y0 + q
     walk(q < W, 1u, q, 0u, 0u);
+  }
+}
+
+// Resident rows from an arena in device memory (the index store's) to where CreateResident packs them: a workgroup per row,
+// consecutive lanes move consecutive words.  Creation checked every row against the arena (shape_error).
+__global__ __launch_bounds__(kThreads) void crossmatch_gather_resident_kernel(const uint32_t *__restrict__ arena,
+                                                                              const CrossResident *__restrict__ resident, uint32_t rows,
+                                                                              CrossRegions rg, uint32_t *__restrict__ hist) {
+  for (uint32_t row = blockIdx.x; row < rows; row += gridDim.x) {
+    const CrossResident rr = resident[row];
+    const uint32_t r = rg.regions == 2u ? row & 1u : 0u;
+    const uint32_t *__restrict__ from = arena + rr.src;
+    uint32_t *__restrict__ to = hist + (r ? rg.res_hist1 : rg.res_hist0) + rr.prefix;
+    for (uint32_t k = threadIdx.x; k < rr.len; k += kThreads) to[k] = from[k];
   }
 }
 
@@ -370,6 +385,8 @@ struct CrossMatcher::Impl {
   DeviceBuffer<uint8_t> state;
   uint32_t capacity = 4096;  // runs the slab holds
   PinnedStage round_stage, head_stage;
+  Origin origin;
+  int device = 0;
   Status poison = Status::Ok();
   uint64_t feeds = 0, launches = 0, cells = 0;
 
@@ -551,6 +568,14 @@ size_t CrossMatcher::StateBytesResident(const NeedleHipSeq *resident, size_t num
   return bytes;
 }
 
+const char *CrossMatcher::ShapeError(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items,
+                                     const uint32_t *min_len) {
+  if (const char *what = shape_error(resident, num_resident, 0, false, videos, regions, max_items)) return what;
+  for (size_t r = 0; r < regions; r++)
+    if (min_len[r] == 0) return "crossmatcher: min_len must be >= 1";
+  return nullptr;
+}
+
 Status CrossMatcher::Create(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out) {
   return CreateRegions(lanes, 1, &max_items, &min_len, threshold, out);
 }
@@ -563,12 +588,25 @@ Status CrossMatcher::CreateRegions(size_t videos, size_t regions, const size_t *
 Status CrossMatcher::CreateResident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident, size_t videos,
                                     size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
                                     std::unique_ptr<CrossMatcher> *out) {
+  return CreateFrom(hashes, false, num_hashes, resident, num_resident, videos, regions, max_items, min_len, threshold, out);
+}
+
+Status CrossMatcher::CreateResidentDevice(const uint32_t *d_hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                                          size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                                          std::unique_ptr<CrossMatcher> *out) {
+  return CreateFrom(d_hashes, true, num_hashes, resident, num_resident, videos, regions, max_items, min_len, threshold, out);
+}
+
+// Both ways in share everything but how the resident hashes reach the histories: packed on the host and uploaded, or
+// gathered from a device arena.
+Status CrossMatcher::CreateFrom(const uint32_t *hashes, bool on_device, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                                size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                                std::unique_ptr<CrossMatcher> *out) {
   if (!out || !max_items || !min_len || (num_resident && !resident) || (num_hashes && !hashes))
     return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
   if (const char *what = shape_error(resident, num_resident, num_hashes, true, videos, regions, max_items))
     return Status::Make(NeedleError_InvalidArgument, what);
-  for (size_t r = 0; r < regions; r++)
-    if (min_len[r] == 0) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: min_len must be >= 1");
+  if (const char *what = ShapeError(resident, num_resident, videos, regions, max_items, min_len)) return Status::Make(NeedleError_InvalidArgument, what);
   std::unique_ptr<CrossMatcher> cm(new CrossMatcher());
   Impl &m = *cm->impl_;
   m.videos = videos;
@@ -585,7 +623,7 @@ Status CrossMatcher::CreateResident(const uint32_t *hashes, size_t num_hashes, c
   for (size_t k = 0; k < num_resident; k++)
     for (size_t r = 0; r < regions; r++) {
       const NeedleHipSeq &row = resident[k * regions + r];
-      table[k * regions + r] = CrossResident{res_total[r], row.len, 0u};
+      table[k * regions + r] = CrossResident{res_total[r], row.len, row.offset};
       res_total[r] += row.len;
       m.res_cell_rows[r] += std::max<uint64_t>(row.len, 1) - 1;
       m.res_longest = std::max<uint64_t>(m.res_longest, row.len);
@@ -626,19 +664,28 @@ Status CrossMatcher::CreateResident(const uint32_t *hashes, size_t num_hashes, c
   const size_t state_bytes = state_entries * (m.narrow ? sizeof(uint16_t) : sizeof(uint32_t));
   if (!(s = m.hist.reserve(hist_words)).ok() || !(s = m.state.reserve(state_bytes)).ok()) return s;
   NEEDLE_HIP_TRY(hipMemsetAsync(m.state.ptr, 0, state_bytes, stream));
-  if (num_resident) {  // the rows packed in table order, and the table: this once
-    std::vector<uint32_t> packed(hist_words - first_resident_word);
-    for (size_t i = 0; i < table.size(); i++) {
-      const size_t r = i % regions;
-      if (table[i].len)
-        std::memcpy(packed.data() + ((r ? m.rg.res_hist1 : m.rg.res_hist0) - first_resident_word) + table[i].prefix, hashes + resident[i].offset,
-                    (size_t)table[i].len * sizeof(uint32_t));
-    }
+  (void)hipGetDevice(&m.device);
+  if (num_resident) {  // the table, and the rows in table order behind the histories: this once
     if (!(s = m.d_resident.reserve(table.size())).ok()) return s;
-    if (!packed.empty())
-      NEEDLE_HIP_TRY(hipMemcpyAsync(m.hist.ptr + first_resident_word, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_resident.ptr, table.data(), table.size() * sizeof(CrossResident), hipMemcpyHostToDevice, stream));
-    NEEDLE_HIP_TRY(hipStreamSynchronize(stream));  // (before `packed` goes)
+    if (on_device) {
+      KernelTimer timer("crossmatch_gather_resident", stream);
+      if (hist_words > first_resident_word)
+        hipLaunchKernelGGL(crossmatch_gather_resident_kernel, dim3((uint32_t)std::min<size_t>(table.size(), 4096)), dim3(kThreads), 0, stream,
+                           hashes, (const CrossResident *)m.d_resident.ptr, (uint32_t)table.size(), m.rg, m.hist.ptr);
+      NEEDLE_HIP_TRY(hipGetLastError());
+    } else {
+      std::vector<uint32_t> packed(hist_words - first_resident_word);
+      for (size_t i = 0; i < table.size(); i++) {
+        const size_t r = i % regions;
+        if (table[i].len)
+          std::memcpy(packed.data() + ((r ? m.rg.res_hist1 : m.rg.res_hist0) - first_resident_word) + table[i].prefix, hashes + resident[i].offset,
+                      (size_t)table[i].len * sizeof(uint32_t));
+      }
+      if (!packed.empty())
+        NEEDLE_HIP_TRY(hipMemcpyAsync(m.hist.ptr + first_resident_word, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+      NEEDLE_HIP_TRY(hipStreamSynchronize(stream));  // (before `packed` goes)
+    }
   }
   NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
   *out = std::move(cm);
@@ -744,6 +791,18 @@ Status CrossMatcher::Runs(size_t first, size_t count, NeedleHipRun *runs) {
   if (count && !runs) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
   if (count) std::memcpy(runs, impl_->runs.data() + first, count * sizeof(NeedleHipRun));
   return Status::Ok();
+}
+
+void CrossMatcher::set_origin(const Origin &origin) { impl_->origin = origin; }
+CrossMatcher::Origin CrossMatcher::origin() const { return impl_->origin; }
+int CrossMatcher::device() const { return impl_->device; }
+uint32_t CrossMatcher::min_len(size_t region) const { return impl_->min_len[region < kMaxRegions ? region : 0]; }
+Status CrossMatcher::poisoned() const { return impl_->poison; }
+const std::vector<NeedleHipRun> &CrossMatcher::run_list() const { return impl_->runs; }
+const uint32_t *CrossMatcher::history(size_t lane) const {
+  const Impl &m = *impl_;
+  const size_t r = lane % m.regions;
+  return m.hist.ptr + (r ? m.rg.hist1 : m.rg.hist0) + (lane / m.regions) * m.max_items[r];
 }
 
 void CrossMatcher::Stats(uint64_t stats[4]) const {

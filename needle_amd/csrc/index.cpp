@@ -10,6 +10,7 @@
 #include "index.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <unordered_map>
@@ -137,10 +138,20 @@ bool pair_problems(const std::vector<uint32_t> &min_len, size_t R, size_t i, siz
   return any;
 }
 
+std::atomic<uint64_t> next_index_id{1};
+
 }  // namespace
 
 Index::Index(const Comparator &comparator)
-    : cmp_(comparator), include_endings_(comparator.include_endings()), regions_(comparator.include_endings() ? 2u : 1u) {}
+    : cmp_(comparator), include_endings_(comparator.include_endings()), regions_(comparator.include_endings() ? 2u : 1u), id_(next_index_id++) {}
+
+void Index::changed(uint64_t searched, uint64_t scanned) {
+  pairs_last_ = searched;
+  pairs_total_ += searched;
+  scanned_last_ = scanned;
+  scanned_total_ += scanned;
+  generation_++;
+}
 
 Index::~Index() { index_store_free(store_); }
 
@@ -149,9 +160,50 @@ Status Index::init() {
   return Status::Ok();
 }
 
-Status Index::add(const std::vector<const FrameHashesData *> &fh) {
+Status Index::add(const std::vector<const FrameHashesData *> &fh) { return append(fh, nullptr); }
+
+Status Index::add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &fh) {
+  if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_matched: null argument");
+  return append(fh, matcher);
+}
+
+Status Index::crossmatcher(size_t videos, const size_t *max_items, const uint32_t *min_len, std::unique_ptr<CrossMatcher> *out) {
+  if (!out || !max_items || !min_len) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  // The argument checks first, with or without a device (no state is asked for: StateBytesResident is host arithmetic) ...
+  if (const char *what = CrossMatcher::ShapeError(rows_.seqs.data(), videos_.size(), videos, regions_, max_items, min_len))
+    return Status::Make(NeedleError_InvalidArgument, what);
+  // ... then the device, before anything is allocated on another one
+  const uint32_t *d_hashes = nullptr;
+  Status s = index_store_arena(store_, &d_hashes);
+  if (!s.ok()) return s;
+  std::unique_ptr<CrossMatcher> cm;
+  s = CrossMatcher::CreateResidentDevice(d_hashes, d_hashes ? rows_.hashes : 0, rows_.seqs.data(), videos_.size(), videos, regions_, max_items,
+                                         min_len, cmp_.hash_match_threshold(), &cm);
+  if (!s.ok()) return s;
+  cm->set_origin(CrossMatcher::Origin{id_, generation_});
+  *out = std::move(cm);
+  return Status::Ok();
+}
+
+// add and add_matched: with a matcher its runs stand in for the scan of the new pairs; everything else is one path.
+Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatcher *matcher) {
   if (fh.empty()) return Status::Make(NeedleError_InvalidArgument, "index add: no videos");
   const size_t k = fh.size(), n0 = videos_.size(), n1 = n0 + k, R = regions_;
+  if (matcher) {
+    Status s = matcher->poisoned();
+    if (!s.ok()) return s;
+    const CrossMatcher::Origin from = matcher->origin();
+    if (from.index_id != id_) return Status::Make(NeedleError_InvalidArgument, "index add_matched: the matcher was not created from this index");
+    if (from.generation != generation_)
+      return Status::Make(NeedleError_InvalidArgument, "index add_matched: the index has changed since the matcher was created");
+    if (matcher->device() != index_store_device(store_))
+      return Status::Make(NeedleError_InvalidArgument, "index add_matched: the matcher is on another device than the index");
+    bool complete = false;
+    if (!(s = matcher->Ready(nullptr, &complete)).ok()) return s;
+    if (!complete) return Status::Make(NeedleError_InvalidArgument, "index add_matched: the matcher is not complete");
+    if (k != matcher->videos() || R != matcher->regions() || n0 != matcher->residents())
+      return Status::Make(NeedleError_InvalidArgument, "index add_matched: not the matcher's number of videos");
+  }
   if (n1 >= 0xFFFFFFFFull) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 videos");
   auto video = [&](size_t v) -> const FrameHashesData & { return v < n0 ? videos_[v] : *fh[v - n0]; };
   auto row_seq = [&](size_t v, size_t r) -> const std::vector<HashTs> & { return r == 0 ? video(v).opening : video(v).ending; };
@@ -159,6 +211,13 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
     for (size_t v = 0; v < n1; v++)
       if (video(v).ending.empty())  // comparator.rs:271-273 (every video is in some pair)
         return Status::Make(NeedleError_Unknown, "no ending hash data present");
+  for (size_t lane = 0; matcher && lane < k * R; lane++) {
+    uint64_t fed = 0;
+    Status s = matcher->Lane(lane, &fed, nullptr);
+    if (!s.ok()) return s;
+    if (row_seq(n0 + lane / R, lane % R).size() != fed)
+      return Status::Make(NeedleError_InvalidArgument, "index add_matched: a video's row is not as long as what its lane was fed");
+  }
   IndexRows rows(rows_);
   rows.seqs.resize(n1 * R);
   rows.min_len.resize(n1 * R);
@@ -202,9 +261,37 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
   a.num_ts = ts.size();
   a.hash_duration = hash_duration.data();
   IndexAppendOut out;
-  Status s = gpu_index_append(store_, a, &out);
-  if (!s.ok()) return s;
-  s = settle(cmp_, "Index::add", R, n1, new_pairs * R, [&](uint64_t q, size_t *i, size_t *j) { column_pair(first_pair + q, i, j); }, row_seq, video,
+  Status s;
+  if (matcher) {
+    // The matcher had one min_len per region, a lower bound: beyond the smallest bound of a live pair it has lost runs.
+    for (size_t r = 0; r < R; r++) {
+      uint32_t least = UINT32_MAX;
+      for (size_t j = n0; j < n1; j++)
+        for (size_t i = 0; i < j; i++)
+          if (rows.min_len[i * R + r] && rows.min_len[j * R + r]) least = std::min(least, std::max(rows.min_len[i * R + r], rows.min_len[j * R + r]));
+      if (matcher->min_len(r) > least)
+        return Status::Make(NeedleError_InvalidArgument, "index add_matched: the matcher's min_len exceeds the shortest run a pair can hold");
+    }
+    std::vector<IndexSegment> lanes;
+    for (size_t at = n0 * R; at < n1 * R; at++)
+      if (rows.seqs[at].len)
+        lanes.push_back(IndexSegment{rows.seqs[at].offset, (uint64_t)(matcher->history(at - n0 * R) - matcher->history(0)), rows.seqs[at].len});
+    IndexMatched m;
+    m.runs = matcher->run_list().data();
+    m.num_runs = matcher->run_list().size();
+    m.min_len = rows.min_len.data();
+    m.history = matcher->history(0);
+    m.lanes = lanes.data();
+    m.num_lanes = lanes.size();
+    if (!(s = gpu_index_append_matched(store_, a, m, &out)).ok()) return s;
+    if (out.refused & kIngestOtherHashes)
+      return Status::Make(NeedleError_InvalidArgument, "index add_matched: a video's hashes differ from what its lane was fed");
+    if (out.refused) return Status::Make(NeedleError_InvalidArgument, "index add_matched: a run of the matcher does not lie inside its rows");
+  } else {
+    s = gpu_index_append(store_, a, &out);
+    if (!s.ok()) return s;
+  }
+  s = settle(cmp_, matcher ? "Index::add_matched" : "Index::add", R, n1, new_pairs * R, [&](uint64_t q, size_t *i, size_t *j) { column_pair(first_pair + q, i, j); }, row_seq, video,
              [&](const auto &...computed) { return gpu_index_append_host_entries(store_, a, computed..., &out); }, out);
   if (!s.ok()) return s;
   // commit: nothing above changed the index
@@ -213,8 +300,7 @@ Status Index::add(const std::vector<const FrameHashesData *> &fh) {
   rows_ = std::move(rows);
   results_.resize(n1, NeedleHipSearchResult{});
   for (size_t q = 0; q < out.videos.size(); q++) results_[out.videos[q]] = out.results[q];
-  pairs_last_ = searched;
-  pairs_total_ += searched;
+  changed(searched, matcher ? 0 : searched);
   return Status::Ok();
 }
 
@@ -262,7 +348,7 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
     videos_.clear();
     rows_ = IndexRows();
     results_.clear();
-    pairs_last_ = 0;
+    changed(0, 0);
     return Status::Ok();
   }
   auto is_fresh = [&](size_t v) { return old_of_new[v] == kIndexFresh; };
@@ -385,8 +471,7 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   videos_.swap(videos);
   results_.swap(results);
   rows_ = std::move(rows);
-  pairs_last_ = searched;
-  pairs_total_ += searched;
+  changed(searched, searched);
   return Status::Ok();
 }
 

@@ -1,8 +1,10 @@
 // NeedleHipIndex (index.cpp): an incremental search index that searches only the pairs an append adds.
 #pragma once
 
+#include <memory>
 #include <vector>
 
+#include "crossmatch.h"
 #include "needle_core.h"
 
 namespace needle {
@@ -32,6 +34,12 @@ class Index {
   size_t size() const { return videos_.size(); }
   // Appends the videos (copied); on failure the index is as it was before the call.
   Status add(const std::vector<const FrameHashesData *> &videos);
+  // A cross-matcher over the index's videos (its resident rows, gathered from the store's arena on the device) and `videos`
+  // arriving ones, with the index's regions and threshold.  It remembers the index and its generation.
+  Status crossmatcher(size_t videos, const size_t *max_items, const uint32_t *min_len, std::unique_ptr<CrossMatcher> *out);
+  // add() with the runs of a complete matcher made by crossmatcher() since the last change in place of the scan: the same
+  // index afterwards, no pair searched again.  Every check comes before the commit; on failure the index is as it was.
+  Status add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &videos);
   // Removes the videos at these distinct positions (the others keep their order) / replaces them in place (copied).  The
   // results then equal run_with_frame_hashes over the new list; on failure the index is as it was before the call.
   Status remove(const std::vector<size_t> &positions);
@@ -41,6 +49,9 @@ class Index {
   const std::vector<NeedleHipSearchResult> &results() const { return results_; }
   uint64_t pairs_total() const { return pairs_total_; }
   uint64_t pairs_last() const { return pairs_last_; }
+  // pairs handed to the one-shot scan (add_matched hands it none)
+  uint64_t scanned_total() const { return scanned_total_; }
+  uint64_t scanned_last() const { return scanned_last_; }
 
  private:
   Comparator cmp_;  // a copy: its parameters, and entries_from_runs for the host fallback
@@ -50,7 +61,12 @@ class Index {
   std::vector<FrameHashesData> videos_;
   IndexRows rows_;
   std::vector<NeedleHipSearchResult> results_;
-  uint64_t pairs_total_ = 0, pairs_last_ = 0;
+  uint64_t pairs_total_ = 0, pairs_last_ = 0, scanned_total_ = 0, scanned_last_ = 0;
+  const uint64_t id_;        // from a process-wide counter: what a matcher made here remembers, with ...
+  uint64_t generation_ = 1;  // ... this, which every successful change advances
+
+  Status append(const std::vector<const FrameHashesData *> &videos, CrossMatcher *matcher);
+  void changed(uint64_t searched, uint64_t scanned);  // the counters, at a commit
 
   // remove / replace: the new list is old_of_new[v] (an old position) or, where that is kIndexFresh, *fresh[v]
   Status rebuild(const std::vector<uint32_t> &old_of_new, const std::vector<const FrameHashesData *> &fresh);

@@ -20,6 +20,10 @@ struct IndexEntry {
   uint32_t score, src_hash, dst_hash, pad;
 };
 
+struct IndexSegment {  // `len` elements at `src` of one table and at `dst` of another (an edit's kept rows: committed -> new)
+  uint64_t src, dst, len;
+};
+
 struct IndexOptions : EpilogueOptions {  // of an append or an edit
   bool large_ok = false;  // after it, every row is under 65 536 hashes and its timestamps strictly increase
 };
@@ -46,6 +50,7 @@ struct IndexAppendOut {
   std::vector<uint32_t> videos;                 // the videos whose candidate list changed ...
   std::vector<NeedleHipSearchResult> results;   // ... and their new results
   std::vector<NeedleHipRun> runs;               // kEpilogueBucketTooLarge: the append's run list, for the host
+  uint32_t refused = 0;                         // (gpu_index_append_matched) kIngest* bits: the matcher's runs or hashes do not fit the rows
 };
 // Upload, scan of the new pairs, entries into the store, best_match over the changed videos, all on the library stream;
 // one wait, for the final copy.  Nothing is committed: the caller does that (index_store_commit) once the results are good.
@@ -56,14 +61,33 @@ Status gpu_index_append_host_entries(IndexStore *store, const IndexAppend &appen
                                      const std::vector<uint32_t> &valid, const std::vector<IndexEntry> &entries, IndexAppendOut *out);
 void index_store_commit(IndexStore *store, const IndexAppend &append, uint32_t entries_written);
 
+// The same append fed from a complete cross-matcher over the store's videos and the new ones in place of the scan: its run
+// list (host; problem = the i-major pair over all n1 videos * regions + region, needle_hip.h) goes up once and one kernel
+// leaves what the scan would have left, tagged for the append (pair_ids.h), less the runs the scan's problems exclude (a row
+// whose min_len is 0, a run shorter than the pair's max(min_len)).  Everything behind that is gpu_index_append's second half,
+// the fallback included (out->runs is then the ingested list).  The new rows are compared with the matcher's histories on the
+// device.  out->refused != 0: nothing is to be committed.
+struct IndexMatched {
+  const NeedleHipRun *runs = nullptr;
+  size_t num_runs = 0;
+  const uint32_t *min_len = nullptr;      // ALL rows after the append
+  const uint32_t *history = nullptr;      // device: the matcher's lane histories
+  const IndexSegment *lanes = nullptr;    // a new row: `len` hashes at `src` in the arena after the append, at `dst` in `history`
+  size_t num_lanes = 0;
+};
+constexpr uint32_t kIngestBadRun = 1u;       // a run outside its rows, of an old pair or of no pair
+constexpr uint32_t kIngestOtherHashes = 2u;  // a new row's hashes are not what its lane was fed
+Status gpu_index_append_matched(IndexStore *store, const IndexAppend &append, const IndexMatched &matched, IndexAppendOut *out);
+// The committed hash arena on the device (row offsets: IndexRows::seqs), for a cross-matcher's resident rows; null while empty.
+// Valid until the next operation on the store.
+Status index_store_arena(IndexStore *store, const uint32_t **d_hashes);
+int index_store_device(const IndexStore *store);  // the device that was current when the store was made
+
 // One removal or replacement: the store is rebuilt for a new list of n_new videos, each an old video kept in place of its
 // relative order (old_of_new[v] = its old position) or a fresh one (kIndexFresh: a replacement).  Pair ids are renumbered,
 // so every table is gathered into a second set of buffers; the committed ones are not written (index_store_switch makes
 // the new ones current).  Rows are video * regions + region.
 constexpr uint32_t kIndexFresh = 0xFFFFFFFFu;
-struct IndexSegment {  // a kept row: `len` elements from `src` in the committed table to `dst` in the new one
-  uint64_t src, dst, len;
-};
 struct IndexEdit : IndexOptions {
   uint32_t n_old = 0, n_new = 0;
   const uint32_t *old_of_new = nullptr;  // [n_new]: the old position, or kIndexFresh

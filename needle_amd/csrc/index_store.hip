@@ -9,6 +9,7 @@
 
 #include "epilogue_kernels.h"
 #include "index_store.h"
+#include "pair_ids.h"
 
 namespace needle {
 
@@ -41,6 +42,59 @@ __global__ __launch_bounds__(256) void index_list_kernel(uint32_t n0, uint32_t n
                                                          uint32_t *__restrict__ count, uint32_t *__restrict__ list) {
   for (uint32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n1; v += gridDim.x * blockDim.x)
     if (v >= n0 || flag[v]) list[atomicAdd(count, 1u)] = v;
+}
+
+// ---- an append fed from a cross-matcher (gpu_index_append_matched) -------------------------------------------------------------
+// The matcher's run list into the slab the scan of the new pairs would have left.  A run names its pair in the comparator's
+// i-major order over all V videos; the store wants the column-major id less the append's first (pair_ids.h).  The scan's
+// problems leave out a region one of whose rows can hold no run long enough (min_len 0) and apply max(min_len) of the two
+// rows, where the matcher had one lower bound per region: those runs are dropped here.  A run that does not lie inside its
+// two rows, or is not of a new pair, sets `error` and is dropped too, so nothing behind this reads outside a row.  The survivors
+// of a wave leave together: one returning atomic per wave (crossmatch.hip's push).  A wave's 64 lanes take 64 consecutive
+// runs, so every lane of a wave makes the same number of trips.
+__global__ __launch_bounds__(256) void index_ingest_runs_kernel(const NeedleHipRun *__restrict__ in, uint32_t num_runs, uint32_t videos,
+                                                                uint32_t n0, uint32_t regions, const uint32_t *__restrict__ min_len,
+                                                                const uint32_t *__restrict__ row_len, NeedleHipRun *__restrict__ out,
+                                                                uint32_t capacity, uint32_t *__restrict__ count, uint32_t *__restrict__ error) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < num_runs; base += stride) {
+    const uint64_t k = base + lane;
+    bool keep = false;
+    NeedleHipRun run{};
+    if (k < num_runs) {
+      run = in[k];
+      uint32_t a = 0, b = 0, r = 0;
+      bool good = decode_problem(run.problem, regions, videos, &a, &b, &r) && b >= n0;
+      if (good) {
+        const uint64_t row_a = (uint64_t)a * regions + r, row_b = (uint64_t)b * regions + r;
+        good = run.src_end < row_len[row_a] && run.dst_end < row_len[row_b] && run.len <= min(run.src_end, run.dst_end);
+        const uint32_t min_a = min_len[row_a], min_b = min_len[row_b];
+        keep = good && min_a != 0u && min_b != 0u && run.len >= max(min_a, min_b);
+        run.problem = (uint32_t)append_tag(a, b, r, n0, regions);
+      }
+      if (!good) atomicOr(error, kIngestBadRun);
+    }
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
+    if (mask == 0ull) continue;
+    uint32_t first = 0u;
+    if (lane == 0u) first = atomicAdd(count, (uint32_t)__popcll(mask));
+    first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+    const uint32_t slot = first + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+    if (keep && slot < capacity) out[slot] = run;
+  }
+}
+
+// The new rows in the arena against the hashes their lanes were fed (the matcher's histories): a workgroup per row.
+__global__ __launch_bounds__(256) void index_compare_rows_kernel(const IndexSegment *__restrict__ rows, uint32_t num_rows,
+                                                                 const uint32_t *__restrict__ arena, const uint32_t *__restrict__ history,
+                                                                 uint32_t *__restrict__ error) {
+  for (uint32_t s = blockIdx.x; s < num_rows; s += gridDim.x) {
+    const IndexSegment g = rows[s];
+    bool differ = false;
+    for (uint64_t k = threadIdx.x; k < g.len; k += blockDim.x) differ = differ || arena[g.src + k] != history[g.dst + k];
+    if (differ) atomicOr(error, kIngestOtherHashes);
+  }
 }
 
 // ---- an index edit (removal / replacement): the store rebuilt under the new pair ids into the second set of buffers ----
@@ -182,7 +236,8 @@ struct IndexStore {
   EntriesScratch scratch;  // over the new (an append) or the listed (an edit) pairs' buckets
   DeviceBuffer<EpilogueControl> ctl;
   DeviceBuffer<uint32_t> flag, list, links, run_count;
-  DeviceBuffer<NeedleHipRun> runs;
+  DeviceBuffer<NeedleHipRun> runs, matched_runs;  // the run list; a matcher's, as uploaded
+  DeviceBuffer<uint32_t> matched_min_len, matched_error;
   DeviceBuffer<Candidate> cand;
   DeviceBuffer<NeedleHipSearchResult> results;
   PinnedHead *pinned = nullptr;
@@ -380,19 +435,18 @@ Status index_best_and_copy(IndexStore *st, const IndexAppend &a, hipStream_t str
 
 }  // namespace
 
-Status gpu_index_append(IndexStore *st, const IndexAppend &a, IndexAppendOut *out) {
-  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
-  Status s = index_enter(st);
-  if (!s.ok()) return s;
+namespace {
+
+// The first half of an append: the new videos' rows, timestamps, hash durations and hashes go in behind the committed ones.
+Status index_append_tables(IndexStore *st, const IndexAppend &a, hipStream_t stream) {
   if (a.n0 != st->n || a.n1 <= a.n0 || a.regions < 1 || a.regions > 2)
     return Status::Make(NeedleError_InvalidArgument, "index append: inconsistent sizes");
-  hipStream_t stream = library_stream();
   StoreTables &t = *st->cur;
   const uint64_t new_buckets = append_buckets(a), buckets1 = st->buckets + new_buckets;
   const uint64_t rows1 = st->rows + a.num_rows, ts1 = st->ts + a.num_ts, hashes1 = st->hashes + a.num_hashes;
   if (buckets1 >= 0xFFFFFFF0ull || hashes1 > UINT32_MAX)
     return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
-  // the resident tables: the new videos' rows, timestamps, hash durations and hashes go in behind the committed ones
+  Status s;
   if (!(s = t.hash.reserve(std::max<uint64_t>(hashes1, 1), st->hashes, stream)).ok() || !(s = t.row_len.reserve(rows1, st->rows, stream)).ok() ||
       !(s = t.row_ts.reserve(rows1, st->rows, stream)).ok() || !(s = t.row_seek.reserve(rows1, st->rows, stream)).ok() ||
       !(s = t.ts_table.reserve(std::max<uint64_t>(ts1, 1), st->ts, stream)).ok() || !(s = t.hash_duration.reserve(a.n1, st->n, stream)).ok() ||
@@ -405,10 +459,18 @@ Status gpu_index_append(IndexStore *st, const IndexAppend &a, IndexAppendOut *ou
   NEEDLE_HIP_TRY(hipMemsetAsync(t.row_seek.ptr() + st->rows, 0, a.num_rows * sizeof(uint64_t), stream));
   NEEDLE_HIP_TRY(upload(t.ts_table.ptr() + st->ts, a.ts, a.num_ts, stream));
   NEEDLE_HIP_TRY(upload(t.hash_duration.ptr() + st->n, a.hash_duration, a.n1 - a.n0, stream));
+  return Status::Ok();
+}
+
+// The second half, behind the slab: fill(capacity) leaves the new pairs' runs, tagged for the append, in st->runs and their
+// number in st->run_count (the scan, or a matcher's list ingested); then the entries into the store, best_match over the
+// changed videos and the copies.
+template <class Fill>
+Status index_append_from_slab(IndexStore *st, const IndexAppend &a, hipStream_t stream, IndexAppendOut *out, Fill fill) {
+  StoreTables &t = *st->cur;
+  const uint64_t new_buckets = append_buckets(a);
   return index_run(st, "index append", a.num_problems, new_buckets, a.n1, stream, out, [&](uint32_t capacity, uint64_t) -> Status {
-    // the scan of the new pairs only (every form eligible), behind the uploads on the same stream
-    Status s = gpu_hamming_runs_device(t.hash.ptr(), a.seqs, a.num_seqs, a.problems, a.num_problems, a.threshold, st->runs.ptr, capacity,
-                                       st->run_count.ptr, false, false);
+    Status s = fill(capacity);
     if (!s.ok()) return s;
     NEEDLE_HIP_TRY(hipMemsetAsync(st->ctl.ptr, 0, sizeof(EpilogueControl), stream));
     if (new_buckets) {
@@ -426,6 +488,61 @@ Status gpu_index_append(IndexStore *st, const IndexAppend &a, IndexAppendOut *ou
     }
     return index_best_and_copy(st, a, stream, out);
   });
+}
+
+}  // namespace
+
+Status gpu_index_append(IndexStore *st, const IndexAppend &a, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = index_enter(st);
+  if (!s.ok()) return s;
+  hipStream_t stream = library_stream();
+  if (!(s = index_append_tables(st, a, stream)).ok()) return s;
+  return index_append_from_slab(st, a, stream, out, [&](uint32_t capacity) -> Status {
+    // the scan of the new pairs only (every form eligible), behind the uploads on the same stream
+    return gpu_hamming_runs_device(st->cur->hash.ptr(), a.seqs, a.num_seqs, a.problems, a.num_problems, a.threshold, st->runs.ptr, capacity,
+                                   st->run_count.ptr, false, false);
+  });
+}
+
+Status gpu_index_append_matched(IndexStore *st, const IndexAppend &a, const IndexMatched &m, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = index_enter(st);
+  if (!s.ok()) return s;
+  hipStream_t stream = library_stream();
+  if (m.num_runs > 0x7fffffffu) return Status::Make(NeedleError_InvalidArgument, "index add_matched: more than 2^31 runs");
+  if (!(s = index_append_tables(st, a, stream)).ok()) return s;
+  const size_t rows = (size_t)a.n1 * a.regions;
+  if (!(s = st->matched_runs.reserve(std::max<size_t>(m.num_runs, 1))).ok() || !(s = st->matched_min_len.reserve(rows)).ok() ||
+      !(s = st->matched_error.reserve(1)).ok() || !(s = st->segments.reserve(std::max<size_t>(m.num_lanes, 1))).ok())
+    return s;
+  NEEDLE_HIP_TRY(upload(st->matched_runs.ptr, m.runs, m.num_runs, stream));
+  NEEDLE_HIP_TRY(upload(st->matched_min_len.ptr, m.min_len, rows, stream));
+  NEEDLE_HIP_TRY(upload(st->segments.ptr, m.lanes, m.num_lanes, stream));
+  const uint32_t capacity_before = st->capacity;
+  st->capacity = std::max<uint32_t>(st->capacity, (uint32_t)m.num_runs);  // the survivors are at most the list: one pass
+  s = index_append_from_slab(st, a, stream, out, [&](uint32_t capacity) -> Status {
+    NEEDLE_HIP_TRY(hipMemsetAsync(st->matched_error.ptr, 0, sizeof(uint32_t), stream));
+    NEEDLE_HIP_TRY(hipMemsetAsync(st->run_count.ptr, 0, sizeof(uint32_t), stream));
+    KernelTimer timer("index_ingest", stream);
+    if (m.num_lanes)
+      hipLaunchKernelGGL(index_compare_rows_kernel, dim3((uint32_t)std::min<size_t>(m.num_lanes, 4096)), dim3(256), 0, stream,
+                         (const IndexSegment *)st->segments.ptr, (uint32_t)m.num_lanes, (const uint32_t *)st->cur->hash.ptr(), m.history,
+                         st->matched_error.ptr);
+    if (m.num_runs)
+      hipLaunchKernelGGL(index_ingest_runs_kernel, dim3((uint32_t)std::min<size_t>(4096, (m.num_runs + 255) / 256)), dim3(256), 0, stream,
+                         (const NeedleHipRun *)st->matched_runs.ptr, (uint32_t)m.num_runs, a.n1, a.n0, a.regions,
+                         (const uint32_t *)st->matched_min_len.ptr, (const uint32_t *)st->cur->row_len.ptr(), st->runs.ptr, capacity,
+                         st->run_count.ptr, st->matched_error.ptr);
+    NEEDLE_HIP_TRY(hipGetLastError());
+    return Status::Ok();
+  });
+  if (s.ok()) {
+    const hipError_t e = hipMemcpy(&out->refused, st->matched_error.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) s = Status::Make(NeedleError_Unknown, std::string("HIP error: ") + hipGetErrorString(e) + " reading the ingest's error word");
+  }
+  if (!s.ok() || out->refused) st->capacity = capacity_before;  // a call that commits nothing sizes nothing for the next one
+  return s;
 }
 
 Status gpu_index_append_host_entries(IndexStore *st, const IndexAppend &a, const std::vector<uint32_t> &start,
@@ -605,6 +722,17 @@ void index_store_switch(IndexStore *st, const IndexEdit &e, uint32_t held) {
 void index_store_clear(IndexStore *st) {
   st->n = 0;
   st->buckets = st->entries = st->rows = st->ts = st->hashes = 0;
+}
+
+int index_store_device(const IndexStore *st) { return st->device; }
+
+Status index_store_arena(IndexStore *st, const uint32_t **d_hashes) {
+  *d_hashes = nullptr;
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = ensure_device();
+  if (!s.ok() || !(s = index_check_device(st)).ok()) return s;
+  if (st->hashes) *d_hashes = st->cur->hash.ptr();
+  return Status::Ok();
 }
 
 Status index_store_sizes(IndexStore *st, uint64_t sizes[4]) {

@@ -250,6 +250,20 @@ extern "C" {
         k: usize,
     ) -> NeedleError;
     pub fn needle_hip_index_store_sizes(index: *const NeedleHipIndex, sizes: *mut u64) -> NeedleError;
+    pub fn needle_hip_index_crossmatcher_new(
+        index: *mut NeedleHipIndex,
+        videos: usize,
+        max_items: *const usize,
+        min_len: *const u32,
+        output: *mut *mut NeedleHipCrossMatcher,
+    ) -> NeedleError;
+    pub fn needle_hip_index_add_matched(
+        index: *mut NeedleHipIndex,
+        matcher: *mut NeedleHipCrossMatcher,
+        frame_hashes: *const *const FrameHashes,
+        k: usize,
+    ) -> NeedleError;
+    pub fn needle_hip_index_pairs_scanned(index: *const NeedleHipIndex, total: *mut u64, last: *mut u64) -> NeedleError;
     /// 1..=MAX_CHANNELS interleaved channels -> mono, `(sum of a frame) / channels` with C truncation; `out[i]` holds
     /// `num_values[i] / channels` values.
     pub fn needle_hip_downmix_host(

@@ -856,11 +856,37 @@ impl Index {
             .collect())
     }
 
-    /// (total, last): video pairs handed to the scan over the index's life and by the last `add`.
+    /// (total, last): video pairs that entered the index over its life and by the last `add`.
     pub fn pairs_searched(&self) -> Result<(u64, u64)> {
         let (mut total, mut last) = (0u64, 0u64);
         unsafe { check(ffi::needle_hip_index_pairs_searched(self.raw, &mut total, &mut last))? };
         Ok((total, last))
+    }
+
+    /// (total, last): video pairs handed to the one-shot scan over the index's life and by the last operation (0 after
+    /// `add_matched`).
+    pub fn pairs_scanned(&self) -> Result<(u64, u64)> {
+        let (mut total, mut last) = (0u64, 0u64);
+        unsafe { check(ffi::needle_hip_index_pairs_scanned(self.raw, &mut total, &mut last))? };
+        Ok((total, last))
+    }
+
+    /// A cross-matcher whose resident videos are this index's, in its order (their rows are copied from the index's device
+    /// arena), with `videos` arriving ones; regions and threshold are the index's, `max_items` and `min_len` hold one entry
+    /// per region.  Feed it as the season decodes, then hand it to `add_matched`.
+    pub fn crossmatcher(&mut self, videos: usize, max_items: &[usize], min_len: &[u32]) -> Result<CrossMatcher> {
+        assert_eq!(max_items.len(), min_len.len(), "one max_items and one min_len per region");
+        let mut raw = ptr::null_mut();
+        unsafe { check(ffi::needle_hip_index_crossmatcher_new(self.raw, videos, max_items.as_ptr(), min_len.as_ptr(), &mut raw))? };
+        Ok(CrossMatcher { raw, lanes: videos * max_items.len() })
+    }
+
+    /// Appends the arriving videos of `matcher` (complete, made by `crossmatcher` since the index last changed) with the runs
+    /// it holds in place of a scan: afterwards the index is what `add(frame_hashes)` leaves, and no pair was searched twice.
+    /// On error the index is as it was before the call.
+    pub fn add_matched(&mut self, matcher: &mut CrossMatcher, frame_hashes: &[&FrameHashes]) -> Result<()> {
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        unsafe { check(ffi::needle_hip_index_add_matched(self.raw, matcher.raw, raw.as_ptr(), raw.len())) }
     }
 }
 

@@ -9,13 +9,27 @@ default opening window of 50 %, analyzed once and reused):
                           epilogue_buckets + epilogue_entries and epilogue_best_match), from a separate pass with timing on
 Medians over --steps calls after --warmup.
 
-Usage: python tools/bench_index.py [--sizes 250,500,1000] [--steps K] [--warmup W] [--out profiles/index_bench.json]"""
+--matched: a streamed season into the index (needle_hip_index_crossmatcher_new, needle_hip_index_add_matched) with
+--resident K known videos and --arriving N new ones (1 000 and 28), one region, in place of the sizes above:
+  add_matched           : wall time of needle_hip_index_add_matched from a complete matcher, and its kernels (index_ingest in
+                          place of the scan's)
+  add                   : the same for needle_hip_index_add of the same N videos on the same index state
+  crossmatcher_from_index / crossmatcher_from_host : wall time of needle_hip_index_crossmatcher_new (rows gathered from the
+                          store's arena: crossmatch_gather_resident) against needle_hip_crossmatcher_new_resident over a
+                          host arena that is already packed
+  feed_s                : what the search cost while the season "decoded": every lane fed in strips of 512 hashes
+
+Usage: python tools/bench_index.py [--sizes 250,500,1000] [--steps K] [--warmup W] [--out profiles/index_bench.json]
+       python tools/bench_index.py --matched [--resident K] [--arriving N] [--steps K] [--warmup W] [--out ...]"""
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
 import sys
 import time
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from needle_amd import capi, synth  # noqa: E402
@@ -96,20 +110,101 @@ def bench(fhs, n, k, steps, warmup):
     return out
 
 
+MATCHED = ("index_ingest",) + INDEX
+GATHER = ("crossmatch_gather_resident",)
+
+
+def fed_matcher(index, rows, cap, min_len):
+    """A complete matcher made from `index` over the lanes `rows`, fed in strips; (matcher, creation ms, feed seconds)."""
+    made = []
+    ms = timed(lambda: made.append(index.crossmatcher(len(rows), cap, min_len)))
+    m = made[0]
+    t = time.perf_counter()
+    for at in range(0, max(len(x) for x in rows), 512):
+        m.feed([x[at:at + 512] for x in rows])
+    m.finish()
+    assert m.ready()[1]
+    return m, ms, time.perf_counter() - t
+
+
+def bench_matched(fhs, n, k, steps, warmup):
+    new = fhs[n:n + k]
+    rows = [fh.opening_data()[0] for fh in new]
+    cap = [max(len(x) for x in rows)]
+    ts = new[0].opening_data()[1]
+    min_len = [int(-(-capi.DEFAULT_MIN_OPENING_DURATION * 10 ** 9 // int(ts[1] - ts[0])))]   # evenly spaced timestamps: the index's own bound
+    resident = [fh.opening_data()[0] for fh in fhs[:n]]
+    arena = np.concatenate(resident)
+    seqs = np.zeros((n, 2), dtype=np.uint32)
+    seqs[:, 1] = [len(x) for x in resident]
+    seqs[:, 0] = np.cumsum([0] + [len(x) for x in resident])[:n]
+    matched, plain, from_index, from_host, feeds, runs = [], [], [], [], [], 0
+    want = None
+    for rep in range(warmup + steps + 1):
+        timing = rep == warmup + steps          # one more pass with the event timers on
+        a, b = capi.Index(comparator(n)), capi.Index(comparator(n))
+        a.add(fhs[:n])
+        b.add(fhs[:n])
+        if timing:
+            capi.set_kernel_timing(",".join(GATHER) + ",sum")
+        m, made_ms, feed_s = fed_matcher(a, rows, cap, min_len)
+        if timing:
+            gather_k = kernel_ms(GATHER)
+        h = C.c_void_p()
+        host_ms = timed(lambda: capi.check(capi.lib().needle_hip_crossmatcher_new_resident(
+            arena.ctypes.data, arena.size, seqs.ctypes.data, n, k, 1, (C.c_size_t * 1)(*cap), (C.c_uint32 * 1)(*min_len),
+            capi.DEFAULT_HASH_MATCH_THRESHOLD, C.byref(h))))
+        capi.lib().needle_hip_crossmatcher_free(h)
+        runs = m.ready()[0]
+        if timing:
+            capi.set_kernel_timing(",".join(SCAN + MATCHED) + ",sum")
+        a_ms = timed(lambda: a.add_matched(m, new))
+        if timing:
+            matched_k = kernel_ms(SCAN + MATCHED)
+            capi.set_kernel_timing(",".join(SCAN + INDEX) + ",sum")   # a new selection: the sums start again
+        b_ms = timed(lambda: b.add(new))
+        if timing:
+            plain_k = kernel_ms(SCAN + INDEX)
+            capi.set_kernel_timing(None)
+        got = [None if r is None else (r.opening, r.ending) for r in a.results()]
+        assert got == [None if r is None else (r.opening, r.ending) for r in b.results()], "add_matched and add disagree"
+        assert a.store_sizes() == b.store_sizes() and a.pairs_searched() == b.pairs_searched() and a.pairs_scanned()[1] == 0
+        if warmup <= rep < warmup + steps:
+            matched.append(a_ms)
+            plain.append(b_ms)
+            from_index.append(made_ms)
+            from_host.append(host_ms)
+            feeds.append(feed_s)
+        del m, a, b
+    med = statistics.median
+    return {"resident": n, "arriving": k, "matcher_runs": runs, "matcher_min_len": min_len[0],
+            "add_matched_ms": round(med(matched), 3), "add_ms": round(med(plain), 3),
+            "add_matched_ms_min_max": [round(min(matched), 3), round(max(matched), 3)], "add_ms_min_max": [round(min(plain), 3), round(max(plain), 3)],
+            "add_matched_kernels_ms": matched_k, "add_kernels_ms": plain_k,
+            "crossmatcher_from_index_ms": round(med(from_index), 3), "crossmatcher_from_host_ms": round(med(from_host), 3),
+            "crossmatcher_from_index_kernels_ms": gather_k, "feed_s": round(med(feeds), 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="250,500,1000")
+    ap.add_argument("--matched", action="store_true")
+    ap.add_argument("--resident", type=int, default=1000)
+    ap.add_argument("--arriving", type=int, default=28)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("bench_index.py needs a HIP device")
-    sizes = [int(x) for x in a.sizes.split(",")]
+    sizes = [int(x) for x in a.sizes.split(",")] if not a.matched else []
     t = time.perf_counter()
-    fhs = analyze(max(sizes) + 8)
+    fhs = analyze(a.resident + a.arriving if a.matched else max(sizes) + 8)
     doc = {"machine": "AMD Instinct MI355X (gfx950), one GPU", "device": capi.device_pci_bus_id(), "episode_s": EPISODE_S, "window_hashes": len(fhs[0].opening_data()[0]),
            "analyze_s": round(time.perf_counter() - t, 1), "steps": a.steps, "warmup": a.warmup, "sizes": {}}
+    if a.matched:
+        del doc["sizes"]
+        doc["matched"] = bench_matched(fhs, a.resident, a.arriving, a.steps, a.warmup)
     for n in sizes:
         row = {}
         for k in (1, 8):
