@@ -555,6 +555,25 @@ enum NeedleError needle_hip_feeder_frame_hashes(NeedleHipFeeder *feeder, size_t 
  * resampler tile plus its filter's length -- 76 176 B for a mono lane at 11025 Hz, 149 888 B for stereo at 11025 Hz,
  * 117 760 B for stereo at 48 kHz.  bytes[1]: high-water of one round's staging (new samples and raw chunks). */
 enum NeedleError needle_hip_feeder_state_bytes(const NeedleHipFeeder *feeder, uint64_t bytes[2]);
+/* The audit of the f32 first pass (NeedleHipCertAudit above), travelling with the stream: the feeder path never holds a
+ * window of PCM, so it cannot be audited from outside.  An audited round runs everything a round runs, then at most two
+ * more launches -- the f64 kernel over the round's NEW frame pairs, into f64 chroma rows the audit carries beside the
+ * first pass's (every pair goes through it once), and the audit kernel over carried + new -- and downloads nothing more:
+ * the counts stay on the device, one set per lane, until needle_hip_feeder_audit asks.  A lane's audit covers exactly the
+ * kept items its current stream has emitted so far (`items` == needle_hip_feeder_ready's kept_items after any round;
+ * counts never decrease within a stream; needle_hip_feeder_reset clears the lane's), `mismatches` compares the items the
+ * feeder itself emitted, K is NEEDLE_HIP_CERT_K as every feed reads it, and the six fields equal those of
+ * needle_hip_library_audit / needle_hip_fingerprint_audit_device over the same stream, however it was cut.
+ * A feeder that does not ask for the audit launches and keeps exactly what it did without it.
+ * With the audit on, needle_hip_feeder_state_bytes' bytes[0] counts the audit's carried rows too, 96 B each:
+ *     bytes[0] <= (bound without the audit) + 22 x 96 B      (78 288 B for a mono lane at 11025 Hz)
+ * and a round holds, besides, 96 B per new frame of every lane.
+ * set_audit: only while no lane holds samples (a new feeder, or every lane reset); otherwise InvalidArgument, nothing
+ * changed.  audit: lane < lanes: that lane's current stream; lane == SIZE_MAX: all lanes (counts summed, maxima taken);
+ * waits for the library stream; InvalidArgument when the audit is off.  Under NEEDLE_HIP_STFT=f64 there is no first pass
+ * to audit: set_audit(true), and a feed of an audited feeder, fail with InvalidArgument before any device work. */
+enum NeedleError needle_hip_feeder_set_audit(NeedleHipFeeder *feeder, bool on);
+enum NeedleError needle_hip_feeder_audit(NeedleHipFeeder *feeder, size_t lane, NeedleHipCertAudit *audit);
 /* pure host arithmetic, no device: kept items a lane holds after that many samples */
 size_t needle_hip_feeder_num_ready(uint64_t samples_per_channel_fed, int sample_rate, int channels, uint32_t step, bool finished);
 

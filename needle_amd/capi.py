@@ -106,7 +106,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_convert_host", "needle_hip_analyzer_run_pcm_format", "needle_hip_library_set_sample_format",
     "needle_hip_feeder_new", "needle_hip_feeder_free", "needle_hip_feeder_feed", "needle_hip_feeder_finish",
     "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
-    "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready",
+    "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready", "needle_hip_feeder_set_audit", "needle_hip_feeder_audit",
     "needle_hip_matcher_new", "needle_hip_matcher_free", "needle_hip_matcher_feed", "needle_hip_matcher_feed_from_feeder",
     "needle_hip_matcher_finish", "needle_hip_matcher_reset", "needle_hip_matcher_ready", "needle_hip_matcher_runs",
     "needle_hip_matcher_open", "needle_hip_matcher_stats",
@@ -290,6 +290,8 @@ def lib():
     L.needle_hip_feeder_items.argtypes = [vp, sz, sz, sz, vp]
     L.needle_hip_feeder_frame_hashes.argtypes = [vp, sz, sz, u64, f32, C.c_char_p, C.POINTER(vp)]
     L.needle_hip_feeder_state_bytes.argtypes = [vp, C.POINTER(u64)]
+    L.needle_hip_feeder_set_audit.argtypes = [vp, b]
+    L.needle_hip_feeder_audit.argtypes = [vp, sz, vp]
     L.needle_hip_feeder_num_ready.argtypes = [u64, C.c_int, C.c_int, u32, b]
     L.needle_hip_feeder_num_ready.restype = sz
     L.needle_hip_matcher_new.argtypes = [vp, sz, vp, vp, sz, sz, u32, C.POINTER(vp)]
@@ -853,6 +855,17 @@ class Feeder:
         out = (C.c_uint64 * 2)()
         check(lib().needle_hip_feeder_state_bytes(self._h, out))
         return int(out[0]), int(out[1])
+
+    def set_audit(self, on: bool) -> None:
+        """Switches the audit that travels with the stream (needle_hip_feeder_set_audit); only while no lane holds samples."""
+        check(lib().needle_hip_feeder_set_audit(self._h, bool(on)))
+
+    def audit(self, lane: Optional[int] = None) -> dict:
+        """The audit of a lane's current stream so far, or of all lanes (None: counts summed, maxima taken), as
+        Library.audit (needle_hip_feeder_audit); waits for outstanding device work."""
+        a = CCertAudit()
+        check(lib().needle_hip_feeder_audit(self._h, self.NO_LANE if lane is None else lane, C.byref(a)))
+        return a.as_dict()
 
     def __del__(self):
         if getattr(self, "_h", None):

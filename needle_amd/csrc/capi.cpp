@@ -754,6 +754,30 @@ enum NeedleError needle_hip_feeder_state_bytes(const NeedleHipFeeder *feeder, ui
   return NeedleError_Ok;
 }
 
+enum NeedleError needle_hip_feeder_set_audit(NeedleHipFeeder *feeder, bool on) {
+  if (!feeder) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->SetAudit(on);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_audit(NeedleHipFeeder *feeder, size_t lane, NeedleHipCertAudit *audit) {
+  if (!feeder || !audit) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    uint64_t c[4] = {0, 0, 0, 0};
+    NeedleHipCertAudit a{};
+    Status s = feeder->inner->Audit(lane, c, &a.max_error_over_s, &a.max_s);
+    if (!s.ok()) return report(s);
+    a.items = c[0];
+    a.accepted = c[1];
+    a.accepted_mismatches = c[2];
+    a.mismatches = c[3];
+    *audit = a;
+    return NeedleError_Ok;
+  });
+}
+
 size_t needle_hip_feeder_num_ready(uint64_t samples_per_channel_fed, int sample_rate, int channels, uint32_t step, bool finished) {
   return feeder_num_ready(samples_per_channel_fed, sample_rate, channels, step, finished);
 }

@@ -342,6 +342,11 @@ struct AuditCounts {
   unsigned long long items, accepted, accepted_wrong, final_wrong;
   unsigned long long max_ratio_bits, max_sigma_bits;  // doubles >= 0 compare like their bit patterns
 };
+// PHASED (an audited feed, gpu_fingerprint_feed_device): as in features_classify_cert_kernel, over the feed's `second`
+// table -- chroma32 / energy the feeder's first-pass rows, chroma64 the audit's own, `items` the round's.  `out` is then
+// one AuditCounts per feeder lane, and stream si of the table counts into out[lane_of[si]], lane_of the u32 array that
+// lies right behind the table's last stream (it travels with the table's upload).
+template <bool PHASED = false>
 __global__ __launch_bounds__(64) void audit_items_kernel(const double *__restrict__ chroma32, const float *__restrict__ energy,
                                                          const double *__restrict__ chroma64, const FpStream *__restrict__ streams,
                                                          int num_streams, const core::ClassifierThresholds *__restrict__ thr,
@@ -355,9 +360,10 @@ __global__ __launch_bounds__(64) void audit_items_kernel(const double *__restric
   const FpStream st = streams[si];
   const uint32_t k0 = (g - st.tile_base) * items_per_tile;
   const uint32_t count = min(items_per_tile, st.kept - k0);
-  const uint32_t x0 = k0 * step;
+  const uint32_t x0 = k0 * step + (PHASED ? st.fir_base : 0u);
   const uint32_t rows = (count - 1) * step + 16;
   const uint64_t row0 = (uint64_t)st.frame_base + x0;
+  if (PHASED) out += reinterpret_cast<const uint32_t *>(streams + num_streams)[si];
   for (uint32_t r = lane; r < rows; r += 64) {
     sig[r] = feature_row_cert(chroma32 + (row0 + r) * kBands, energy + (row0 + r) * stft::kEnergyParts, cert_k, tile32 + r * kFeatPitch);
     feature_row(chroma64 + (row0 + r) * kBands, tile64 + r * kFeatPitch);

@@ -200,9 +200,20 @@ struct FeedLane {
   uint32_t frames;      // carried + new
   uint32_t first_item;
   uint32_t kept;
+  uint32_t lane;        // the feeder's lane: where an audited feed counts this stream's items
+};
+// An audited feed (needle_hip_feeder_set_audit): behind everything a feed runs, the f64 kernel over the NEW frame pairs
+// into `rows64` -- rows the audit owns, numbered like d_chroma, the carried ones already there -- and audit_items_kernel
+// over carried + new, every new kept item counted into counts[lane] (kFeedAuditWords words per lane, resident).
+constexpr size_t kFeedAuditWords = 6;  // {items, accepted, accepted wrong, final wrong, max ratio bits, max sigma bits}
+struct FeedAudit {
+  double *rows64;
+  uint64_t *counts;
 };
 Status gpu_fingerprint_feed_device(const int16_t *d_pcm, const std::vector<FeedLane> &lanes, int channels, uint32_t step,
-                                   double *d_chroma, float *d_energy, double *d_chroma64, uint32_t *d_items);
+                                   double *d_chroma, float *d_energy, double *d_chroma64, uint32_t *d_items,
+                                   const FeedAudit *audit = nullptr);
+bool gpu_fingerprint_f64_mode();  // NEEDLE_HIP_STFT=f64: no first pass, nothing to audit
 
 // ---- resampler front-end (resample.hip) -------------------------------------------------------------------
 struct ResampleSpan {

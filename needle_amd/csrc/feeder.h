@@ -27,6 +27,11 @@ class Feeder {
   Status Items(size_t lane, size_t first, size_t count, uint32_t *items);
   Status FinishedItems(size_t lane, const std::vector<uint32_t> **items);  // InvalidArgument unless the lane is finished
   void StateBytes(uint64_t bytes[2]) const;
+  // The audit of the f32 first pass, travelling with the stream (needle_hip_feeder_set_audit / _audit).  SetAudit: only
+  // while no lane holds samples.  Audit: counts = {items, accepted, accepted mismatches, mismatches} of a lane's current
+  // stream, or of all lanes (SIZE_MAX: counts summed, maxima taken); waits for the library stream.
+  Status SetAudit(bool on);
+  Status Audit(size_t lane, uint64_t counts[4], double *max_ratio, double *max_sigma);
 
  private:
   Feeder();

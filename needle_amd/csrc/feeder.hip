@@ -6,7 +6,8 @@
 //   * source-rate samples (converted, 3-8 channels down-mixed) the next resampler tile still reads -- other rates than
 //     11025 Hz only;
 //   * the 11025 Hz PCM tail, from the first frame of the first item not yet emitted (rounded down to a multiple of 4);
-//   * the first pass's chroma and energy rows of the tail's whole frame pairs.
+//   * the first pass's chroma and energy rows of the tail's whole frame pairs;
+//   * audited (set_audit): the f64 kernel's chroma rows of the same frames, and six resident words of counts.
 //
 // One round (a feed, or a piece of one that exceeds the staging bound):
 //   carry      feeder_carry_kernel: tails and rows of all lanes from the previous set of buffers to the front of their
@@ -19,6 +20,8 @@
 //              carried rows; certification, recomputation and fix-up over carried + new.  Frame pairs are the
 //              one-shot's (2p, 2p + 1): the tail starts at an even frame and a trailing odd frame waits for its partner
 //              (or for `finish`, which transforms it alone as the one-shot does).
+//   audit      only if asked for (set_audit), two more launches there: the f64 kernel over the new pairs into the audit's
+//              own rows, audit_items_kernel over carried + new; the counts stay on the device until `audit` asks.
 // Every step is one launch over all lanes (tables searched by block, as in downmix.hip / convert.hip).
 #include "feeder.h"
 
@@ -72,6 +75,7 @@ struct BufferSet {
   DeviceBuffer<int16_t> pcm;     // 11025 Hz tails + new samples, lane after lane
   DeviceBuffer<double> chroma;   // first-pass rows
   DeviceBuffer<float> energy;
+  DeviceBuffer<double> audit64;  // the audit's f64 rows, numbered like chroma (empty unless audited)
 };
 
 struct Lane {
@@ -148,6 +152,8 @@ struct Feeder::Impl {
   Status poison = Status::Ok();
   uint64_t staging_high = 0;
   uint64_t state_high = 0;  // the most bytes a round carried for one lane (tails and rows)
+  bool audit = false;
+  DeviceBuffer<uint64_t> audit_counts;  // [n][kFeedAuditWords], zero where a lane's stream starts
 
   ~Impl() {
     std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
@@ -179,6 +185,8 @@ struct Feeder::Impl {
   };
 
   Status round(const std::vector<Chunk> &chunks) {
+    if (audit && gpu_fingerprint_f64_mode())
+      return Status::Make(NeedleError_InvalidArgument, "feeder: NEEDLE_HIP_STFT=f64 has no first pass to audit");
     std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
     Status s = ensure_device();
     if (!s.ok()) return s;
@@ -244,6 +252,7 @@ struct Feeder::Impl {
         f.frames = (uint32_t)(p.frames - l.keep_frame);
         f.first_item = (uint32_t)(l.items_done * step - l.keep_frame);
         f.kept = (uint32_t)(p.kept - l.items_done);
+        f.lane = (uint32_t)i;
         new_items += f.kept;
         feed.push_back(f);
         feed_lane.push_back(i);
@@ -254,6 +263,7 @@ struct Feeder::Impl {
         !(s = to.energy.reserve((rows + 2) * 4)).ok() || !(s = chroma64.reserve((rows + 2) * kBands)).ok() ||
         !(s = d_items.reserve(std::max<uint64_t>(new_items, 1))).ok() || !(s = raw.reserve(std::max<uint64_t>(raw_units, 1))).ok())
       return s;
+    if (audit && !(s = to.audit64.reserve((rows + 2) * kBands)).ok()) return s;
     staging_high = std::max(staging_high, (new_values + raw_units) * 2);
 
     // carry: tails and rows into the other set
@@ -274,13 +284,16 @@ struct Feeder::Impl {
       const Plan &p = plan[i];
       if (l.finished) continue;
       state_high = std::max(state_high, (p.carried_values + p.carried_src) * sizeof(int16_t) +
-                                            (uint64_t)p.carried_rows * (kBands * sizeof(double) + 4 * sizeof(float)));
+                                            (uint64_t)p.carried_rows * ((audit ? 2 : 1) * kBands * sizeof(double) + 4 * sizeof(float)));
       if (p.carried_values) add_seg(from.pcm.ptr + p.src_off, to.pcm.ptr + p.new_off, p.carried_values * 2);
       if (p.carried_src) add_seg(from.src.ptr + p.from_src_off, to.src.ptr + p.new_src_off, p.carried_src * 2);
       if (p.carried_rows) {
         add_seg(from.chroma.ptr + (uint64_t)p.src_row * kBands, to.chroma.ptr + (uint64_t)p.row_base * kBands,
                 (uint64_t)p.carried_rows * kBands * sizeof(double));
         add_seg(from.energy.ptr + (uint64_t)p.src_row * 4, to.energy.ptr + (uint64_t)p.row_base * 4, (uint64_t)p.carried_rows * 4 * sizeof(float));
+        if (audit)
+          add_seg(from.audit64.ptr + (uint64_t)p.src_row * kBands, to.audit64.ptr + (uint64_t)p.row_base * kBands,
+                  (uint64_t)p.carried_rows * kBands * sizeof(double));
       }
     }
     if (!segs.empty()) {
@@ -345,7 +358,9 @@ struct Feeder::Impl {
     }
 
     if (!feed.empty()) {
-      if (!(s = gpu_fingerprint_feed_device(to.pcm.ptr, feed, pcm_channels, step, to.chroma.ptr, to.energy.ptr, chroma64.ptr, d_items.ptr)).ok())
+      const FeedAudit audited{to.audit64.ptr, audit_counts.ptr};
+      if (!(s = gpu_fingerprint_feed_device(to.pcm.ptr, feed, pcm_channels, step, to.chroma.ptr, to.energy.ptr, chroma64.ptr, d_items.ptr,
+                                            audit ? &audited : nullptr)).ok())
         return s;
       if (new_items) {
         if (!(s = item_stage.acquire(new_items * sizeof(uint32_t))).ok()) return s;
@@ -489,7 +504,57 @@ Status Feeder::Reset(const size_t *lanes, size_t k) {
     Status s = m.drain();
     if (!s.ok()) return m.poison = s;
   }
+  if (m.audit) {  // a lane's audit is its current stream's (behind the rounds that still count into it: one stream)
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    for (size_t j = 0; j < (lanes ? k : m.n); j++) {
+      const hipError_t e = hipMemsetAsync(m.audit_counts.ptr + (lanes ? lanes[j] : j) * kFeedAuditWords, 0,
+                                          kFeedAuditWords * sizeof(uint64_t), library_stream());
+      if (e != hipSuccess) return m.poison = Status::Make(NeedleError_Unknown, std::string("HIP error: ") + hipGetErrorString(e));
+    }
+  }
   for (size_t j = 0; j < (lanes ? k : m.n); j++) m.lanes[lanes ? lanes[j] : j] = Lane();
+  return Status::Ok();
+}
+
+Status Feeder::SetAudit(bool on) {
+  Impl &m = *impl_;
+  if (!m.poison.ok()) return m.poison;
+  for (const Lane &l : m.lanes)
+    if (l.fed || l.finished) return Status::Make(NeedleError_InvalidArgument, "feeder: the audit is switched only while no lane holds samples");
+  if (on && gpu_fingerprint_f64_mode())
+    return Status::Make(NeedleError_InvalidArgument, "feeder: NEEDLE_HIP_STFT=f64 has no first pass to audit");
+  if (on) {
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    Status s = ensure_device();
+    if (!s.ok() || !(s = m.audit_counts.reserve(m.n * kFeedAuditWords)).ok()) return s;
+    NEEDLE_HIP_TRY(hipMemsetAsync(m.audit_counts.ptr, 0, m.n * kFeedAuditWords * sizeof(uint64_t), library_stream()));
+  }
+  m.audit = on;
+  return Status::Ok();
+}
+
+Status Feeder::Audit(size_t lane, uint64_t counts[4], double *max_ratio, double *max_sigma) {
+  Impl &m = *impl_;
+  if (!m.audit) return Status::Make(NeedleError_InvalidArgument, "feeder: the audit is off (set_audit)");
+  if (lane >= m.n && lane != SIZE_MAX) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+  if (!m.poison.ok()) return m.poison;
+  const size_t first = lane == SIZE_MAX ? 0 : lane, count = lane == SIZE_MAX ? m.n : 1;
+  std::vector<uint64_t> host(count * kFeedAuditWords);
+  {
+    std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+    hipStream_t stream = library_stream();
+    NEEDLE_HIP_TRY(hipMemcpyAsync(host.data(), m.audit_counts.ptr + first * kFeedAuditWords, host.size() * sizeof(uint64_t),
+                                  hipMemcpyDeviceToHost, stream));
+    NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  }
+  uint64_t bits[2] = {0, 0};  // doubles >= 0 compare like their bit patterns
+  for (int c = 0; c < 4; c++) counts[c] = 0;
+  for (size_t i = 0; i < count; i++) {
+    for (int c = 0; c < 4; c++) counts[c] += host[i * kFeedAuditWords + c];
+    for (int c = 0; c < 2; c++) bits[c] = std::max(bits[c], host[i * kFeedAuditWords + 4 + c]);
+  }
+  std::memcpy(max_ratio, &bits[0], sizeof(double));
+  std::memcpy(max_sigma, &bits[1], sizeof(double));
   return Status::Ok();
 }
 

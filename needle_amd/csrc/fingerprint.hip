@@ -292,6 +292,7 @@ Status plan_chunk(const std::vector<StreamSpan> &spans, size_t begin, int channe
 // certification, recomputation and fix-up, the lane's first new item `first_item` rows in (PHASED).
 struct FeedPlan {
   std::vector<FpStream> first, second;
+  std::vector<uint32_t> second_lane;  // the feeder's lane of every stream of `second` (an audited feed counts by it)
   uint64_t pairs1 = 0, pairs2 = 0, kept = 0, tiles = 0;
   uint64_t chunks1 = 0;  // chunks of the new pairs: what a feed adds to the count the recomputed chunks are a fraction of
 };
@@ -327,6 +328,7 @@ Status plan_feed(const std::vector<FeedLane> &lanes, int channels, uint32_t step
       plan->pairs2 += (l.frames + 1) / 2;
       plan->kept += l.kept;
       plan->second.push_back(m);
+      plan->second_lane.push_back(l.lane);
     }
   }
   return Status::Ok();
@@ -702,7 +704,8 @@ Status gpu_fingerprint_cert_stats(uint64_t out[4], bool reset) {
 // item is in a listed chunk, and d_chroma keeps the first pass's rows for the next feed's certification.  Same kernels,
 // same arithmetic, same pairs as gpu_fingerprint_device on the whole stream.
 Status gpu_fingerprint_feed_device(const int16_t *d_pcm, const std::vector<FeedLane> &lanes, int channels, uint32_t step,
-                                   double *d_chroma, float *d_energy, double *d_chroma64, uint32_t *d_items) {
+                                   double *d_chroma, float *d_energy, double *d_chroma64, uint32_t *d_items,
+                                   const FeedAudit *audit) {
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
   FpTables tab;
   Status s = begin_call(channels, step, &tab);
@@ -714,11 +717,18 @@ Status gpu_fingerprint_feed_device(const int16_t *d_pcm, const std::vector<FeedL
   if (!(s = plan_feed(lanes, channels, step, job.items_per_tile, &plan)).ok()) return s;
   if (plan.pairs1 == 0 && plan.kept == 0) return Status::Ok();
   if (plan.pairs1 > 0x7FFFFFF0ull || plan.pairs2 > 0x7FFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "fingerprint: feed too large");
+  if (audit && f64_mode()) return Status::Make(NeedleError_InvalidArgument, "fingerprint: NEEDLE_HIP_STFT=f64 has no first pass to audit");
   const uint64_t cus = (uint64_t)device_cu_count();
+  const size_t streams2 = plan.second.size();
+  if (audit && streams2) {  // the lanes of `second`, right behind its last stream (audit_items_kernel<PHASED>)
+    constexpr size_t per = sizeof(FpStream) / sizeof(uint32_t);
+    plan.second.resize(streams2 + (streams2 + per - 1) / per, FpStream{});
+    std::memcpy(static_cast<void *>(plan.second.data() + streams2), plan.second_lane.data(), streams2 * sizeof(uint32_t));
+  }
   if (!plan.first.empty() && !(s = ws->feed_first.upload.put(&ws->feed_first.streams, &ws->feed_first.stage, plan.first, stream)).ok()) return s;
   if (!plan.second.empty() && !(s = ws->feed_second.upload.put(&ws->feed_second.streams, &ws->feed_second.stage, plan.second, stream)).ok()) return s;
   const Table first{ws->feed_first.streams.ptr, (int)plan.first.size(), plan.pairs1};
-  const Table second{ws->feed_second.streams.ptr, (int)plan.second.size(), plan.pairs2};
+  const Table second{ws->feed_second.streams.ptr, (int)streams2, plan.pairs2};
   // a feed is a short launch: every slot of the device gets one workgroup, of at most kPairsPerBlock pairs
   auto pairs_per_slot = [&](uint64_t slots) {
     return (uint32_t)std::min<uint64_t>(kPairsPerBlock, std::max<uint64_t>(1, (plan.pairs1 + slots - 1) / slots));
@@ -730,9 +740,27 @@ Status gpu_fingerprint_feed_device(const int16_t *d_pcm, const std::vector<FeedL
   const FirstPass pass{first, stft32_schedule(plan.pairs1, ppb, 0, false), d_chroma, d_energy, ws->cert.ctl.ptr,
                        (uint32_t)layout.ctl_words, stream, nullptr, true};
   bool zeroed = false;
-  return enqueue_certified(job, ws, CertChain{pass, second, plan.tiles, plan.kept, true, d_chroma64, &ws->cert,
-                                              (uint32_t)std::min<uint64_t>(2 * cus, layout.nchunks), false, nullptr, plan.chunks1}, &zeroed);
+  s = enqueue_certified(job, ws, CertChain{pass, second, plan.tiles, plan.kept, true, d_chroma64, &ws->cert,
+                                           (uint32_t)std::min<uint64_t>(2 * cus, layout.nchunks), false, nullptr, plan.chunks1}, &zeroed);
+  if (!s.ok() || !audit) return s;
+  static_assert(sizeof(AuditCounts) == kFeedAuditWords * sizeof(uint64_t), "a feeder lane's audit counts are kFeedAuditWords words");
+  // The audit that travels with the stream: every new pair through the f64 kernel once, into the audit's own rows (not
+  // d_chroma64: that holds the listed chunks alone), then every new kept item examined as the one-shot audit examines it.
+  if (plan.pairs1) {
+    KernelTimer timer("audit_stft");
+    if (!(s = enqueue_f64(job, F64Chain{first, pairs_per_slot(2 * cus), audit->rows64, second, 0, true, false})).ok()) return s;
+  }
+  if (plan.tiles) {
+    KernelTimer timer("audit_items");
+    hipLaunchKernelGGL(audit_items_kernel<true>, dim3((uint32_t)plan.tiles), dim3(64), 0, stream, d_chroma, d_energy, audit->rows64,
+                       second.streams, second.n, tab.thr, step, job.items_per_tile, d_items, (uint32_t)plan.tiles, cert_k(),
+                       reinterpret_cast<AuditCounts *>(audit->counts));
+    NEEDLE_HIP_TRY(hipGetLastError());
+  }
+  return Status::Ok();
 }
+
+bool gpu_fingerprint_f64_mode() { return f64_mode(); }
 
 // Audit (include/needle_hip.h needle_hip_fingerprint_audit_device): both transforms over the same resident PCM, every
 // kept item compared on the device.  out = {items, accepted by the first pass, accepted items whose f32 bits are not the
@@ -772,7 +800,7 @@ Status gpu_fingerprint_audit_device(const int16_t *d_pcm, const std::vector<Stre
                                                 ctl.ptr, (uint32_t)(sizeof(CertWork) / 4), stream, nullptr, false})).ok() ||
         !(s = enqueue_f64(job, F64Chain{table, (uint32_t)kPairsPerBlock, chroma64.ptr, table, 0, false, false})).ok())
       return s;
-    hipLaunchKernelGGL(audit_items_kernel, dim3((uint32_t)plan.tiles), dim3(64), 0, stream, chroma32.ptr, energy.ptr, chroma64.ptr,
+    hipLaunchKernelGGL(audit_items_kernel<false>, dim3((uint32_t)plan.tiles), dim3(64), 0, stream, chroma32.ptr, energy.ptr, chroma64.ptr,
                        table.streams, table.n, tab.thr, step, job.items_per_tile, d_items, (uint32_t)plan.tiles, k, d_counts.ptr);
     NEEDLE_HIP_TRY(hipGetLastError());
   }

@@ -378,6 +378,8 @@ extern "C" {
         output: *mut *mut FrameHashes,
     ) -> NeedleError;
     pub fn needle_hip_feeder_state_bytes(feeder: *const NeedleHipFeeder, bytes: *mut u64) -> NeedleError;
+    pub fn needle_hip_feeder_set_audit(feeder: *mut NeedleHipFeeder, on: bool) -> NeedleError;
+    pub fn needle_hip_feeder_audit(feeder: *mut NeedleHipFeeder, lane: usize, audit: *mut NeedleHipCertAudit) -> NeedleError;
     pub fn needle_hip_feeder_num_ready(
         samples_per_channel_fed: u64,
         sample_rate: c_int,

@@ -530,6 +530,19 @@ impl Feeder {
         Ok((bytes[0], bytes[1]))
     }
 
+    /// Switches the audit of the f32 first pass that travels with the stream; only while no lane holds samples.
+    pub fn set_audit(&mut self, on: bool) -> Result<()> {
+        unsafe { check(ffi::needle_hip_feeder_set_audit(self.raw, on)) }
+    }
+
+    /// The audit of a lane's current stream so far, or of all lanes (`None`: counts summed, maxima taken):
+    /// `mismatches` and `accepted_mismatches` must be 0 (`needle_hip_feeder_audit`).  Waits for the library stream.
+    pub fn audit(&mut self, lane: Option<usize>) -> Result<ffi::NeedleHipCertAudit> {
+        let mut a = ffi::NeedleHipCertAudit::default();
+        unsafe { check(ffi::needle_hip_feeder_audit(self.raw, lane.unwrap_or(usize::MAX), &mut a))? };
+        Ok(a)
+    }
+
     /// Kept items a lane holds after that many samples (host arithmetic, no device).
     pub fn num_ready(samples_per_channel_fed: u64, sample_rate: i32, channels: i32, step: u32, finished: bool) -> usize {
         unsafe { ffi::needle_hip_feeder_num_ready(samples_per_channel_fed, sample_rate, channels, step, finished) }

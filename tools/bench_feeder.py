@@ -13,12 +13,17 @@
             paths, from the compiler's remarks (-Rpass-analysis=kernel-resource-usage, needs no device), for this tree
             and, with --parent DIR (a checkout of the parent commit), for that one; "unchanged" compares the kernels
             both have.
+  audit   : the audit that travels with the stream (needle_hip_feeder_set_audit): 28 lanes of 48 kHz planar-float stereo in
+            1-s chunks, wall ms per feed with the audit off and on, alternating, median of 30 after 10; the event times
+            per feed of the first pass and of the audit's two kernels, from a pass of their own; and, with --parent DIR
+            (built), the audit-off leg in five processes of each tree, alternating, the tree that goes first alternating
+            too: this tree's median must stay within the parent's median + the spread of the parent's five.
   headline: with --parent DIR (built), bench.py --gpus 1 --steps 20 --warmup 5 in both trees, alternating, --repeats
             times each: medians, the difference and each side's spread (max - min).
 Sections not asked for with --only keep the figures the output file already holds.
 
 Usage: python tools/bench_feeder.py [--repeats K] [--episodes N] [--out FILE] [--parent DIR]
-                                    [--only chunked,per_feed,state,launches,resources,headline]"""
+                                    [--only chunked,per_feed,state,launches,resources,headline,audit]"""
 import argparse
 import csv
 import glob
@@ -184,7 +189,7 @@ def bench_launches(feeds):
 
 
 RESOURCE_FILES = ["feeder.hip", "fingerprint.hip", "fingerprint32.hip"]
-RESOURCE_KERNELS = re.compile(r"feeder_carry_kernel|stft_chroma32_kernel|features_classify|stft_chroma_kernel|fixup_items_kernel")
+RESOURCE_KERNELS = re.compile(r"feeder_carry_kernel|stft_chroma32_kernel|features_classify|stft_chroma_kernel|fixup_items_kernel|audit_items_kernel")
 RESOURCE_KEYS = {"TotalSGPRs": "sgprs", "SGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
                  "Occupancy [waves/SIMD]": "occupancy", "LDS Size [bytes/block]": "lds"}
 
@@ -254,12 +259,85 @@ def bench_headline(root, parent, repeats):
             "spread_percent": {k: round(100.0 * (max(v) - min(v)) / med[k], 3) for k, v in values.items()}}
 
 
+def audit_lanes(lanes=28, rate=48000):
+    rng = np.random.default_rng(3)
+    return [[rng.uniform(-0.5, 0.5, rate).astype(np.float32) for _ in range(2)] for _ in range(lanes)]
+
+
+def timed_feed(f, chunks):
+    t0 = time.perf_counter()
+    f.feed(chunks)
+    f.ready(0)                                           # the feed's items are on the host
+    return (time.perf_counter() - t0) * 1e3
+
+
+# The audit-off leg as a program of its own, run with a tree as its working directory so that it loads that tree's
+# library: nothing in it is newer than the feeder itself.
+AUDIT_LEG = """
+import statistics, sys, time
+import numpy as np
+sys.path.insert(0, '.')
+from needle_amd import capi
+rng = np.random.default_rng(3)
+chunks = [[rng.uniform(-0.5, 0.5, 48000).astype(np.float32) for _ in range(2)] for _ in range(28)]
+f = capi.Feeder(28, 2, 48000, capi.SAMPLE_F32P, 2)
+times = []
+for k in range(40):
+    t0 = time.perf_counter()
+    f.feed(chunks)
+    f.ready(0)
+    times.append((time.perf_counter() - t0) * 1e3)
+print(statistics.median(times[10:]))
+"""
+
+
+def bench_audit(root, parent):
+    chunks = audit_lanes()
+    feeders = {}
+    for on in (False, True):
+        feeders[on] = capi.Feeder(len(chunks), 2, 48000, capi.SAMPLE_F32P, 2)
+        feeders[on].set_audit(on)
+    times = {False: [], True: []}
+    for k in range(40):
+        for on in ((False, True) if k % 2 == 0 else (True, False)):
+            times[on].append(timed_feed(feeders[on], chunks))
+    out = {"shape": "28 lanes, 48 kHz planar-float stereo, 1-s chunks, step 2",
+           "ms_per_feed": {"audit_off": statistics.median(times[False][10:]), "audit_on": statistics.median(times[True][10:])}}
+    a = feeders[True].audit()
+    out["audit"] = a
+    assert a["items"] == sum(feeders[True].ready(k)[0] for k in range(len(chunks))) and a["accepted_mismatches"] == 0
+    kernels = ["stft_chroma32", "features_cert", "stft_fallback", "fixup_items", "audit_stft", "audit_items"]
+    capi.set_kernel_timing(",".join(kernels) + ",sum")
+    for _ in range(30):
+        feeders[True].feed(chunks)
+    feeders[True].ready(0)
+    out["kernel_ms_per_feed"] = {k: round(capi.last_kernel_ms(k) / 30, 5) for k in kernels}
+    capi.set_kernel_timing(None)
+    out["state_bytes_per_lane"] = {"audit_off": feeders[False].state_bytes()[0], "audit_on": feeders[True].state_bytes()[0]}
+    del feeders
+    if parent:
+        def leg(tree):
+            run = subprocess.run([sys.executable, "-c", AUDIT_LEG], cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+                                 text=True, timeout=300, check=True)
+            return float(run.stdout.strip().splitlines()[-1])
+        runs = {"parent": [], "this": []}
+        for k in range(5):
+            for name in (("parent", "this") if k % 2 == 0 else ("this", "parent")):
+                runs[name].append(leg(parent if name == "parent" else root))
+        med = {k: statistics.median(v) for k, v in runs.items()}
+        spread = max(runs["parent"]) - min(runs["parent"])
+        out["audit_off_vs_parent"] = {"unit": "ms per feed, median of 30 after 10, five processes each", "runs": runs, "median": med,
+                                      "parent_spread": spread, "condition": "this <= parent + parent_spread",
+                                      "holds": med["this"] <= med["parent"] + spread}
+    return out
+
+
 def main():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--episodes", type=int, default=28)
-    ap.add_argument("--only", default="chunked,per_feed,state,launches,resources,headline")
+    ap.add_argument("--only", default="chunked,per_feed,state,launches,resources,headline,audit")
     ap.add_argument("--parent", default=None, help="a checkout of the parent commit (built, for the headline)")
     ap.add_argument("--out", default=os.path.join(root, "profiles", "feeder_bench.json"))
     ap.add_argument("--trace-child", type=int, default=0, help=argparse.SUPPRESS)
@@ -268,7 +346,7 @@ def main():
     if args.trace_child:
         return trace_child(args.trace_child, args.trace_feeds)
     only = set(args.only.split(","))
-    keys = ("device", "chunked", "per_feed", "state_bytes_per_lane", "kernel_launches_per_feed", "resources", "headline_vs_parent")
+    keys = ("device", "chunked", "per_feed", "state_bytes_per_lane", "kernel_launches_per_feed", "resources", "headline_vs_parent", "audit")
     res = {k: NOT_MEASURED for k in keys}
     if os.path.exists(args.out):                         # sections not run now keep their figures
         try:
@@ -295,6 +373,9 @@ def main():
             save()
         if "chunked" in only:
             res["chunked"] = bench_chunked(args.episodes, max(args.repeats, 5))
+            save()
+        if "audit" in only:
+            res["audit"] = bench_audit(root, args.parent)
             save()
         if "headline" in only and args.parent:
             res["headline_vs_parent"] = bench_headline(root, args.parent, max(args.repeats, 3))
