@@ -3,25 +3,17 @@
 // after any feeds its runs are those of needle_hip_hamming_runs_host over what the two lanes hold, reported as cells break them.
 //
 // State of a pair: the L-shaped frontier of its evaluated rectangle [0, Ja) x [0, Jb) -- col[i] = length of the matching
-// diagonal stretch that ends at cell (i, Jb - 1), row[j] the same at cell (Ja - 1, j) for j < Jb - 1 (the corner is col's);
-// row 0 and column 0 hold no cells, their lengths are 0 and never read.  u16 where max_items < 65 536, else u32; two sets
-// of each.  Per lane, its hashes so far (the simhashes of a run reach back over earlier chunks on both sides).
+// diagonal stretch that ends at cell (i, Jb - 1), row[j] the same at cell (Ja - 1, j) for j < Jb - 1 (the corner is col's).
+// u16 where max_items < 65 536, else u32; two sets of each.  Per lane, its hashes so far.
 //
-// One round (a feed, or a piece of one of at most kMaxStrip items per lane; also `finish`, with no items):
-//   land     crossmatch_land_kernel: the new chunks from the round's staging buffer to the end of their lanes' histories
-//   walk     crossmatch_walk_kernel: a thread walks a diagonal through the pair's new cells.  The "column" direction serves
-//            lane b's new columns: a diagonal that crosses column Jb - 1 at row i starts from col[i] (row 0: from 0), one
-//            that enters through row 1 at a new column starts at 0; either walks on, into lane a's new rows too, until it
-//            runs out of new columns or of rows.  The "row" direction is its transpose for lane a's new rows: from row[j]
-//            (j < Jb - 1: the corner went with col) or through column 1.  Every new cell lies on exactly one of these.  A
-//            diagonal that stops in the new last column writes its length to col, one that stops in the new last row to row.
-//            col of (a, b) flips to its other set when lane b has items, row when lane a has; a side that only gains entries
-//            (the other lane grew) appends them to its current set.  So a round never writes what it reads and can be repeated.
-//            In a finish round the pairs that become complete report what is open on their frontier instead.
-//   simhash  crossmatch_simhash_kernel: both simhashes of every run reported, one wave per run (simhash_wave.h)
-// Three launches whatever N and whichever lanes have data: nothing per pair is uploaded, a workgroup finds its pair from
-// blockIdx.y, the lanes' progress in the round's lane table and the pair's state by arithmetic; the workgroups of a pair
-// neither of whose lanes has data leave after reading two table entries.
+// One round (a feed, or a piece of one of at most kMaxStrip items per lane; also `finish`, with no items) is three launches
+// -- crossmatch_land_kernel, crossmatch_walk_kernel, crossmatch_simhash_kernel -- whatever N and whichever lanes have data.
+// The walk is stream_walk.h's, twice per pair: the column direction (X = lane a's rows, Y = lane b's new columns, from col)
+// and its transpose for lane a's new rows (from row[j], j < Jb - 1).  col of (a, b) flips to its other set when lane b has
+// items, row when lane a has; a side that only gains entries (the other lane grew) appends them to its current set.
+// Nothing per pair is uploaded: a workgroup finds its pair from blockIdx.y, the lanes' progress in the round's lane table
+// and the pair's state by arithmetic; the workgroups of a pair neither of whose lanes has data leave after reading two
+// table entries.
 //
 // Regions (needle_hip_crossmatcher_new_regions): the lanes are videos x R, lane = video * R + region (R = 1 or 2: openings
 // and endings, the numbering of the library's arena rows and of comparator.cpp's seqs), and only lanes of one region are
@@ -39,34 +31,25 @@
 // comparator's index over V videos, NeedleHipRun.problem, comes from (a, b) in closed form.  A resident is a lane that
 // holds all its items, finished before the first round, with no new items ever: only the column direction has cells, and the
 // state of (k, t, r) is the col frontier alone, two sets of len(k, r) entries at 2 * (t * S_r + prefix(k, r)) behind the
-// arriving pairs' frontiers (S_r = the region's resident hashes).  A diagonal that stops in the resident's last row has
-// nowhere to go on: its run, if long enough, is final and leaves with the round's runs; the host holds it back until the
-// arriving lane finishes, which is when the reporting rule hands out what is open on a frontier.  K = 0 is the object above.
+// arriving pairs' frontiers (S_r = the region's resident hashes).  A resident is a complete X (stream_walk.h): a run that
+// reaches its last row leaves with the round's runs, and the host holds it back until the arriving lane finishes, which is
+// when the reporting rule hands out what is open on a frontier.  K = 0 is the object above.
 #include "crossmatch.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "hipctx.h"
-#include "simhash_wave.h"
+#include "stream_round.h"
+#include "stream_walk.h"
 
 namespace needle {
 
 namespace {
 
-constexpr uint32_t kThreads = 256;
-constexpr uint32_t kMaxStrip = 512;      // new items of one round per lane
-constexpr uint32_t kCarriedRows = 1024;  // carried diagonals per workgroup: four per thread, one after the other
-// One direction of a pair: `side_blocks` workgroups of carried diagonals (the frontier entry they start from names them),
-// then kTopBlocks of 256 diagonals that enter through row (column) 1 at the strip's items 1 .. W - 1.
-constexpr uint32_t kTopBlocks = (kMaxStrip - 1 + kThreads - 1) / kThreads;
 constexpr uint32_t kParity = 1u;     // lane flags: the set that holds the state this lane's feeds flip
 constexpr uint32_t kFinished = 2u;   // finished before this round
 constexpr uint32_t kFinishing = 4u;  // finished by this round
-constexpr uint32_t kHeaderWords = 8;  // the slab: the run counter in word 0, the runs from byte 32
-constexpr uint32_t kHeadRuns = 127;   // runs that come down with the counter in one copy
 constexpr size_t kMaxLanes = 256;     // videos: 32 640 pairs, and pair * regions + region is a grid dimension (65 280 <= 65 535)
 constexpr size_t kMaxRegions = 2;
 constexpr size_t kMaxProblems = 65535;  // live problems (with residents: K N + N (N - 1) / 2 pairs) x regions: gridDim.y
@@ -121,107 +104,7 @@ __device__ __forceinline__ uint64_t video_row(const CrossRegions &rg, const Cros
 
 __global__ __launch_bounds__(kThreads) void crossmatch_land_kernel(const uint32_t *__restrict__ round_buf, uint32_t *__restrict__ hist,
                                                                    CrossRegions rg, uint32_t *__restrict__ count) {
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *count = 0u;
-  const CrossLane ln = reinterpret_cast<const CrossLane *>(round_buf)[blockIdx.y];
-  const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-  if (c < ln.width) hist[lane_row(rg, blockIdx.y) + ln.fed + c] = round_buf[ln.stage_off + c];
-}
-
-// What one direction of a pair's round works on.  X is the side the carried diagonals are numbered along, Y the side whose
-// new items [y0, y1) are the strip; kCol: X = lane a's rows, Y = lane b's columns; otherwise the transpose.
-template <typename T>
-struct CrossSide {
-  const uint32_t *xh, *yh;   // the two lanes' histories
-  uint32_t x0, x1, y0, y1;   // items before and after the round, at least 1 (item 0 is no cell)
-  uint32_t carried;          // carried diagonals: entries 0 .. carried - 1 of `from`
-  const T *from;             // frontier read, by position along X; nullptr: all zero (the other side had no cell yet)
-  T *to_last_y, *to_last_x;  // frontier written where a diagonal stops in Y's new last item (by X position) / in X's (by Y position)
-  bool x_complete;           // kCol only: X is a resident row.  No to_last_x: a run that stops in X's last item is final
-};
-
-template <typename T, bool kCol>
-__device__ __forceinline__ void cross_walk(uint32_t *__restrict__ strip, uint32_t *__restrict__ rows, const CrossSide<T> &sd, uint32_t blk,
-                                           uint32_t side_blocks, bool emit_open, uint32_t problem, uint32_t a, uint32_t b, uint32_t threshold,
-                                           uint32_t min_len, NeedleHipRun *__restrict__ runs, uint32_t capacity, uint32_t *__restrict__ count) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  // The runs of one step leave the wave together: one returning atomic for all of them (matcher.hip, search.hip).  The two
-  // rows (a, b: video * regions + region over all videos, residents first) travel in the simhash fields until the simhash
-  // kernel fills them.
-  auto push = [&](const bool want, const uint32_t x, const uint32_t y, const uint32_t len) {
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
-    if (mask == 0ull) return;
-    uint32_t base = 0u;
-    if (lane == 0u) base = atomicAdd(count, (uint32_t)__popcll(mask));
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-    if (want && slot < capacity) runs[slot] = NeedleHipRun{problem, kCol ? x : y, kCol ? y : x, len, a, b};
-  };
-  const bool carried = blk < side_blocks;
-  const uint32_t t0 = blk * kCarriedRows;
-  if (emit_open) {  // no new cells, no state written: what is open on this side of the frontier
-    if (!carried || t0 >= sd.carried) return;  // (the whole workgroup)
-    for (uint32_t part = 0; part < kCarriedRows; part += kThreads) {
-      const uint32_t t = t0 + part + tid;
-      if (t - tid >= sd.carried) break;
-      const uint32_t run = t < sd.carried && t >= 1u && sd.from ? (uint32_t)sd.from[t] : 0u;
-      push(run >= min_len, t, sd.y0 - 1u, run);  // (min_len >= 1: an entry that was not read reports nothing)
-    }
-    return;
-  }
-  const uint32_t W = sd.y1 - sd.y0;
-  if (W == 0u) return;
-  // carried: the diagonals that leave frontier entries t0 ..; otherwise those that enter through X's item 1 at the strip's items q0 ..
-  const uint32_t q0 = carried ? 0u : (blk - side_blocks) * kThreads + 1u;
-  if (carried ? t0 >= sd.carried : q0 >= W) return;  // (the whole workgroup)
-  const uint32_t seg0 = carried ? t0 + 1u : 1u;       // first X item staged
-  const uint32_t steps = W - q0;                      // the most cells one of the workgroup's diagonals walks
-  {
-    const uint32_t seg_rows = min(sd.x1 - seg0, (carried ? kCarriedRows : kThreads) - 1u + steps);  // items seg0 .. <= x1 - 1
-    const uint32_t *__restrict__ src = sd.xh + seg0;
-    for (uint32_t k = tid; k < seg_rows; k += kThreads) rows[k] = src[k];
-    for (uint32_t k = tid; k < W; k += kThreads) strip[k] = sd.yh[sd.y0 + k];
-  }
-  __syncthreads();
-
-  // One diagonal per thread: first new cell (X = i0, Y = y0 + q), `rel` = i0's place in the staged items, `run` = the carried
-  // length.  It walks w cells (i0 + c, y0 + q + c).  Every thread of the workgroup comes through here together.
-  auto walk = [&](const bool live, const uint32_t i0, const uint32_t q, const uint32_t rel, uint32_t run) {
-    const uint32_t w = live ? min(W - q, sd.x1 - i0) : 0u;
-    for (uint32_t c = 0; c < steps; c++) {
-      bool ended = false;
-      uint32_t len = 0u;
-      if (c < w) {
-        const bool match = (uint32_t)__popc(rows[rel + c] ^ strip[q + c]) <= threshold;
-        ended = !match && run >= min_len;  // the run ended at the previous cell
-        len = run;
-        run = match ? run + 1u : 0u;
-      }
-      push(ended, i0 + c - 1u, sd.y0 + q + c - 1u, len);
-    }
-    // the last cell walked (with no cell: the frontier entry itself, which changes hands): it lies in Y's new last item or in
-    // X's last; the corner of the two belongs to col
-    const uint32_t x = i0 + w - 1u, y = sd.y0 + q + w - 1u;
-    const bool last_y = q + w == W, last_x = x == sd.x1 - 1u;
-    const bool to_y = kCol ? last_y : !last_x;
-    if constexpr (kCol) {  // a resident's last row: nothing carries the run, it leaves now (the whole workgroup asks)
-      if (sd.x_complete) push(live && !to_y && run >= min_len, x, y, run);
-    }
-    if (!live) return;
-    if (to_y) sd.to_last_y[x] = (T)run;
-    else if (!kCol || !sd.x_complete) sd.to_last_x[y] = (T)run;
-  };
-  if (carried) {
-    for (uint32_t part = 0; part < kCarriedRows; part += kThreads) {
-      const uint32_t t = t0 + part + tid;  // leaves frontier entry t (entry 0 is no cell: its length is 0)
-      if (t - tid >= sd.carried) break;    // (the whole workgroup)
-      const bool live = t < sd.carried;
-      const uint32_t run = live && t >= 1u && sd.from ? (uint32_t)sd.from[t] : 0u;
-      walk(live, t + 1u, 0u, part + tid, run);
-    }
-  } else {
-    const uint32_t q = q0 + tid;  // enters through X's item 1 at Y's item y0 + q
-    walk(q < W, 1u, q, 0u, 0u);
-  }
+  land_chunks<CrossLane>(round_buf, count, [&](const CrossLane &) { return hist + lane_row(rg, blockIdx.y); });
 }
 
 // Resident rows from an arena in device memory (the index store's) to where CreateResident packs them: a workgroup per row,
@@ -304,12 +187,17 @@ __global__ __launch_bounds__(kThreads) void crossmatch_walk_kernel(const uint32_
   const uint32_t *hb = hist + (r ? rg.hist1 : rg.hist0) + (uint64_t)(b - K) * max_items;
   const uint32_t *ha = res ? hist + (r ? rg.res_hist1 : rg.res_hist0) + prefix : hist + (r ? rg.hist1 : rg.hist0) + (uint64_t)(a - K) * max_items;
   const bool old_cells = a0 >= 2u && b0 >= 2u;
-  if (col_dir) {
-    const CrossSide<T> sd{ha, hb, a0, a1, b0, b1, a0, old_cells ? col_from : nullptr, col_to, row_to, res};
-    cross_walk<T, true>(strip, rows, sd, blockIdx.x, side_blocks, emit_open, problem, row_a, row_b, threshold, min_len, runs, capacity, count);
+  // The two rows (video * regions + region over all videos, residents first) travel in the simhash fields until the simhash
+  // kernel fills them.
+  const auto sink = [&](const uint32_t src_end, const uint32_t dst_end, const uint32_t len) {
+    return NeedleHipRun{problem, src_end, dst_end, len, row_a, row_b};
+  };
+  if (col_dir) {  // a resident row is a complete X: its carried diagonals end one entry earlier
+    const WalkSide<T> sd{ha, hb, a1, b0, b1, res ? a0 - 1u : a0, old_cells ? col_from : nullptr, col_to, row_to, res};
+    stream_walk<T, true>(strip, rows, sd, blockIdx.x, side_blocks, emit_open, threshold, min_len, runs, capacity, count, sink);
   } else {
-    const CrossSide<T> sd{hb, ha, b0, b1, a0, a1, b0 - 1u, old_cells ? row_from : nullptr, row_to, col_to, false};
-    cross_walk<T, false>(strip, rows, sd, blockIdx.x - per_side, side_blocks, emit_open, problem, row_a, row_b, threshold, min_len, runs, capacity, count);
+    const WalkSide<T> sd{hb, ha, b1, a0, a1, b0 - 1u, old_cells ? row_from : nullptr, row_to, col_to, false};
+    stream_walk<T, false>(strip, rows, sd, blockIdx.x - per_side, side_blocks, emit_open, threshold, min_len, runs, capacity, count, sink);
   }
 }
 
@@ -317,19 +205,10 @@ __global__ __launch_bounds__(kThreads) void crossmatch_simhash_kernel(const uint
                                                                       const CrossResident *__restrict__ resident, CrossRegions rg,
                                                                       NeedleHipRun *__restrict__ runs, uint32_t capacity,
                                                                       const uint32_t *__restrict__ count) {
-  const uint32_t total = min(*count, capacity);
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = (gridDim.x * blockDim.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const TransposeLane t = transpose_lane(lane);
-  for (uint32_t k = wave; k < total; k += waves) {
-    const NeedleHipRun r = runs[k];  // src_match_hash, dst_match_hash: the two rows, video * regions + region over all videos
-    const uint32_t src_hash = wave_simhash32(hist + video_row(rg, resident, r.src_match_hash) + (r.src_end - r.len), r.len + 1u, lane, t);
-    const uint32_t dst_hash = wave_simhash32(hist + video_row(rg, resident, r.dst_match_hash) + (r.dst_end - r.len), r.len + 1u, lane, t);
-    if (lane == 0) {
-      runs[k].src_match_hash = src_hash;
-      runs[k].dst_match_hash = dst_hash;
-    }
-  }
+  // src_match_hash, dst_match_hash come in as the two rows, video * regions + region over all videos
+  simhash_runs(
+      runs, capacity, count, [&](const NeedleHipRun &r) { return hist + video_row(rg, resident, r.src_match_hash); },
+      [&](const NeedleHipRun &r) { return hist + video_row(rg, resident, r.dst_match_hash); });
 }
 
 struct LaneState {
@@ -381,10 +260,10 @@ struct CrossMatcher::Impl {
   uint64_t res_longest = 0;
   std::vector<std::vector<NeedleHipRun>> held;      // per lane: runs into a resident's last row, held back until it finishes
   DeviceBuffer<CrossResident> d_resident;
-  DeviceBuffer<uint32_t> hist, d_round, slab;
+  DeviceBuffer<uint32_t> hist, d_round;
   DeviceBuffer<uint8_t> state;
-  uint32_t capacity = 4096;  // runs the slab holds
-  PinnedStage round_stage, head_stage;
+  PinnedStage round_stage;
+  RunSlab<NeedleHipRun> slab;
   Origin origin;
   int device = 0;
   Status poison = Status::Ok();
@@ -392,10 +271,8 @@ struct CrossMatcher::Impl {
 
   ~Impl() {
     std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
-    for (PinnedStage *st : {&round_stage, &head_stage}) {
-      if (st->ptr) (void)hipHostFree(st->ptr);
-      if (st->done) (void)hipEventDestroy(st->done);
-    }
+    round_stage.release();
+    slab.head_stage.release();
   }
 
   size_t pairs() const { return videos * (videos - 1) / 2; }
@@ -452,12 +329,7 @@ struct CrossMatcher::Impl {
       longest = std::max(longest, l.fed + pieces[i].width);
     }
     const uint64_t round_cells = cells_of(&pieces) - cells_of(nullptr);
-    if (!(s = d_round.reserve(words)).ok() || !(s = round_stage.acquire(words * 4)).ok()) return s;
-    std::memcpy(round_stage.ptr, lt.data(), n * sizeof(CrossLane));
-    for (size_t i = 0; i < n; i++)
-      if (pieces[i].width) std::memcpy(static_cast<uint32_t *>(round_stage.ptr) + lt[i].stage_off, pieces[i].items, (size_t)pieces[i].width * 4);
-    NEEDLE_HIP_TRY(hipMemcpyAsync(d_round.ptr, round_stage.ptr, words * 4, hipMemcpyHostToDevice, stream));
-    round_stage.mark(stream);
+    if (!(s = upload_round(lt, pieces, words, &d_round, &round_stage, stream)).ok()) return s;
 
     const CrossLane *d_lanes = reinterpret_cast<const CrossLane *>(d_round.ptr);
     const dim3 block(kThreads);
@@ -465,9 +337,9 @@ struct CrossMatcher::Impl {
     const dim3 walk_grid(2u * (side_blocks + kTopBlocks), (uint32_t)(live_pairs() * regions));
     std::vector<NeedleHipRun> got;
     for (;;) {
-      if (!(s = slab.reserve(kHeaderWords + (uint64_t)capacity * (sizeof(NeedleHipRun) / 4))).ok()) return s;
-      uint32_t *d_count = slab.ptr;
-      NeedleHipRun *d_runs = reinterpret_cast<NeedleHipRun *>(slab.ptr + kHeaderWords);
+      uint32_t *d_count = nullptr;
+      NeedleHipRun *d_runs = nullptr;
+      if (!(s = slab.begin(&d_count, &d_runs)).ok()) return s;
       {
         KernelTimer timer("crossmatch_land");
         hipLaunchKernelGGL(crossmatch_land_kernel, dim3(kMaxStrip / kThreads, (uint32_t)n), block, 0, stream, d_round.ptr, hist.ptr,
@@ -478,37 +350,24 @@ struct CrossMatcher::Impl {
         KernelTimer timer("crossmatch_walk");
         if (narrow)
           hipLaunchKernelGGL(crossmatch_walk_kernel<uint16_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint16_t *>(state.ptr),
-                             d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs, capacity, d_count);
+                             d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs, slab.capacity, d_count);
         else
           hipLaunchKernelGGL(crossmatch_walk_kernel<uint32_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint32_t *>(state.ptr),
-                             d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs, capacity, d_count);
+                             d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs, slab.capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       {
         KernelTimer timer("crossmatch_simhash");
         hipLaunchKernelGGL(crossmatch_simhash_kernel, dim3((uint32_t)device_cu_count() * 2u), block, 0, stream, hist.ptr, d_resident.ptr,
-                           rg, d_runs, capacity, d_count);
+                           rg, d_runs, slab.capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       launches += 3;
       cells += round_cells;
-      // the counter and the first runs in one copy; the rest, if any, in a second one
-      const uint32_t head = std::min(capacity, kHeadRuns);
-      const size_t head_bytes = kHeaderWords * 4 + (size_t)head * sizeof(NeedleHipRun);
-      if (!(s = head_stage.acquire(head_bytes)).ok()) return s;
-      NEEDLE_HIP_TRY(hipMemcpyAsync(head_stage.ptr, slab.ptr, head_bytes, hipMemcpyDeviceToHost, stream));
-      NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+      bool again = false;  // a larger slab, and the round again (it wrote nothing that it reads)
+      if (!(s = slab.collect(stream, &got, &again)).ok()) return s;
       round_stage.pending = false;
-      const uint32_t found = *static_cast<const uint32_t *>(head_stage.ptr);
-      if (found > capacity) {  // nothing is lost: a larger slab, and the round again (it wrote nothing that it reads)
-        capacity = std::max(found, capacity * 2);
-        continue;
-      }
-      got.resize(found);
-      const uint32_t first = std::min(found, head);
-      if (first) std::memcpy(got.data(), static_cast<const char *>(head_stage.ptr) + kHeaderWords * 4, (size_t)first * sizeof(NeedleHipRun));
-      if (found > first) NEEDLE_HIP_TRY(hipMemcpy(got.data() + first, d_runs + first, (size_t)(found - first) * sizeof(NeedleHipRun), hipMemcpyDeviceToHost));
-      break;
+      if (!again) break;
     }
     // What is open on a frontier is reported when the pair becomes complete: a run into a resident's last row waits for its
     // lane's finish round (the kernel kept no state for it).
@@ -530,11 +389,7 @@ struct CrossMatcher::Impl {
     return Status::Ok();
   }
 
-  Status guarded_round(const std::vector<Piece> &pieces) {
-    Status s = round(pieces);
-    if (!s.ok() && s.code != NeedleError_InvalidArgument && s.code != NeedleError_NullArgument) poison = s;
-    return s;
-  }
+  Status guarded_round(const std::vector<Piece> &pieces) { return poison_on_failure(round(pieces), &poison); }
 };
 
 CrossMatcher::CrossMatcher() : impl_(new Impl()) {}
@@ -655,7 +510,7 @@ Status CrossMatcher::CreateFrom(const uint32_t *hashes, bool on_device, size_t n
   m.rg.max_items1 = (uint32_t)m.max_items[regions - 1];
   m.rg.min_len0 = m.min_len[0];
   m.rg.min_len1 = m.min_len[regions - 1];
-  if (const char *e = getenv("NEEDLE_HIP_CROSSMATCHER_RUN_SLAB")) m.capacity = (uint32_t)std::min<long long>(std::max(1ll, atoll(e)), 1ll << 26);
+  m.slab.capacity_from_env("NEEDLE_HIP_CROSSMATCHER_RUN_SLAB");
 
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
   Status s = ensure_device();
@@ -723,32 +578,14 @@ Status CrossMatcher::Feed(const uint32_t *const *items, const size_t *num_items)
 
 Status CrossMatcher::FeedFromFeeder(Feeder *feeder) {
   Impl &m = *impl_;
-  if (!feeder) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
-  if (feeder->lanes() != m.n) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: the feeder has another number of lanes");
-  if (!m.poison.ok()) return m.poison;
-  std::vector<std::vector<uint32_t>> taken(m.n);
-  std::vector<const uint32_t *> ptrs(m.n, nullptr);
-  std::vector<size_t> counts(m.n, 0), finish;
-  for (size_t i = 0; i < m.n; i++) {
-    size_t kept = 0;
-    bool finished = false;
-    Status s = feeder->Ready(i, &kept, nullptr, &finished);
-    if (!s.ok()) return s;
-    const LaneState &l = m.lanes[i];
-    if (l.finished) {
-      if (kept != l.fed || !finished) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: the lane is finished");
-      continue;
-    }
-    if (kept < l.fed) return Status::Make(NeedleError_InvalidArgument, "crossmatcher: the feeder's lane holds fewer items than the matcher has taken");
-    taken[i].resize(kept - l.fed);
-    if (!taken[i].empty() && !(s = feeder->Items(i, (size_t)l.fed, taken[i].size(), taken[i].data())).ok()) return s;
-    ptrs[i] = taken[i].data();
-    counts[i] = taken[i].size();
-    if (finished) finish.push_back(i);
-  }
-  Status s = Feed(ptrs.data(), counts.data());
-  if (!s.ok() || finish.empty()) return s;
-  return Finish(finish.data(), finish.size());
+  FeederTake take;
+  Status s = take_from_feeder(
+      feeder, m.n, m.poison, [&](size_t i, uint64_t *fed, bool *finished) { *fed = m.lanes[i].fed, *finished = m.lanes[i].finished; },
+      "crossmatcher: ", "", &take);
+  if (!s.ok()) return s;
+  s = Feed(take.ptrs.data(), take.counts.data());
+  if (!s.ok() || take.finish.empty()) return s;
+  return Finish(take.finish.data(), take.finish.size());
 }
 
 Status CrossMatcher::Finish(const size_t *lanes, size_t k) {
@@ -811,7 +648,7 @@ void CrossMatcher::Stats(uint64_t stats[4]) const {
   stats[1] = m.launches;
   stats[2] = m.cells;
   stats[3] = StateBytesResident(m.res_rows.data(), m.residents, m.videos, m.regions, m.max_items) + m.res_rows.size() * sizeof(CrossResident) +
-             kHeaderWords * 4 + (uint64_t)m.capacity * sizeof(NeedleHipRun);
+             m.slab.bytes();
 }
 
 }  // namespace needle

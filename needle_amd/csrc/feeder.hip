@@ -161,10 +161,8 @@ struct Feeder::Impl {
       (void)hipStreamSynchronize(library_stream());
       (void)hipEventDestroy(landed);
     }
-    for (PinnedStage *st : {&seg_stage, &item_stage}) {
-      if (st->ptr) (void)hipHostFree(st->ptr);
-      if (st->done) (void)hipEventDestroy(st->done);
-    }
+    seg_stage.release();
+    item_stage.release();
   }
 
   // the items of the last round: wait for them and append them to their lanes

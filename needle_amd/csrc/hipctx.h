@@ -85,6 +85,13 @@ struct PinnedStage {
   void mark(hipStream_t stream) {
     if (hipEventRecord(done, stream) == hipSuccess) pending = true;
   }
+  // Frees the buffer and the event, under gpu_mutex().  No destructor: some instances are function-local statics that are
+  // leaked on purpose (the runtime may be gone before they would be destroyed).
+  void release() {
+    if (ptr) (void)hipHostFree(ptr);
+    if (done) (void)hipEventDestroy(done);
+    *this = PinnedStage();
+  }
 };
 
 

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void index_list_kernel(uint32_t n0, uint32_t n
 // problems leave out a region one of whose rows can hold no run long enough (min_len 0) and apply max(min_len) of the two
 // rows, where the matcher had one lower bound per region: those runs are dropped here.  A run that does not lie inside its
 // two rows, or is not of a new pair, sets `error` and is dropped too, so nothing behind this reads outside a row.  The survivors
-// of a wave leave together: one returning atomic per wave (crossmatch.hip's push).  A wave's 64 lanes take 64 consecutive
+// of a wave leave together: one returning atomic per wave (stream_walk.h's push_runs).  A wave's 64 lanes take 64 consecutive
 // runs, so every lane of a wave makes the same number of trips.
 __global__ __launch_bounds__(256) void index_ingest_runs_kernel(const NeedleHipRun *__restrict__ in, uint32_t num_runs, uint32_t videos,
                                                                 uint32_t n0, uint32_t regions, const uint32_t *__restrict__ min_len,

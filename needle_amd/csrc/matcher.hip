@@ -3,47 +3,31 @@
 // cells of its new columns only and reports the runs those columns close, exactly the runs (and simhashes) that
 // needle_hip_hamming_runs_host finds over the concatenation of a lane's chunks.
 //
-// State of a (lane, source): one run length per source row -- state[i] = length of the matching diagonal stretch that ends
-// at cell (i, J - 1), J the lane's items so far (u16 where every source is shorter than 65 536 hashes, else u32) -- in
-// two sets of buffers; and, per lane, its hashes so far (the destination simhash of a run reaches back over earlier chunks).
+// This is stream_walk.h's walk in its column direction with X = a source, complete, and Y = the lane.  State of a (lane,
+// source): the frontier along the last column fed, one run length per source row (u16 where every source is shorter than
+// 65 536 hashes, else u32), in two sets of buffers: a round reads one and writes the other.  Per lane, its hashes so far.
 //
-// One round (a feed, or a strip of one that is wider than kMaxStrip columns; also `finish` and `open`, with no columns):
-//   land     matcher_land_kernel: the new chunks from the round's staging buffer to the end of their lanes' histories
-//   scan     matcher_strip_kernel: a thread walks a diagonal of the strip (four, one after the other, of those that cross
-//            column J - 1).  A diagonal that crosses column J - 1 starts from the carried length of the row it crosses it
-//            at; one that enters through row 1 inside the strip starts at 0.  It walks its cells of the strip and reports a run where a cell breaks it or where it reaches the source's last
-//            row; where it leaves through the strip's last column at row r it writes its length to row r of the OTHER set
-//            (the state, shifted by the strip's width).  The set it reads is never written, so a round can be repeated.
-//   simhash  matcher_simhash_kernel: both simhashes of every run reported, one wave per run (simhash_wave.h)
-// Three launches whatever N and S: every kernel finds its lane in the round's lane table (blockIdx.y) and its source in
-// the resident source table (through the resident list of every workgroup's source, blockIdx.x); only the lanes with data
-// are in the grid.
+// One round (a feed, or a strip of one that is wider than kMaxStrip columns; also `finish` and `open`, with no columns) is
+// three launches whatever N and S -- matcher_land_kernel, matcher_strip_kernel, matcher_simhash_kernel: every kernel finds
+// its lane in the round's lane table (blockIdx.y) and its source in the resident source table (through the resident list of
+// every workgroup's source, blockIdx.x); only the lanes with data are in the grid.
 #include "matcher.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 
-#include "hipctx.h"
-#include "simhash_wave.h"
+#include "stream_round.h"
+#include "stream_walk.h"
 
 namespace needle {
 
 namespace {
 
-constexpr uint32_t kThreads = 256;
-constexpr uint32_t kMaxStrip = 512;  // columns of one round per lane
-constexpr uint32_t kCarriedRows = 1024;  // diagonals that cross column J - 1 per workgroup: four per thread, one after the other
-// A source's workgroups: ceil((n - 1) / 1024) of diagonals that cross column J - 1 (the row they cross it at names them),
-// then kTopBlocks of 256 diagonals that enter through row 1 at the strip's columns 1 .. W - 1.  The count is that of the
-// widest strip, so the tables (sources, and the source of every workgroup) are built once; the workgroups a narrower strip
-// does not need leave at once.
-constexpr uint32_t kTopBlocks = (kMaxStrip - 1 + kThreads - 1) / kThreads;
-constexpr uint32_t kEmitOpen = 1u;  // no state is written: the diagonals that reach the last column are reported (finish, open)
+constexpr uint32_t kEmitOpen = 1u;  // no state is written: what is open on the frontier is reported (finish, open)
 constexpr uint32_t kNoHash = 2u;    // the runs keep zero simhashes (open)
-constexpr uint32_t kHeaderWords = 8;  // the slab: the run counter in word 0, the runs from byte 32
-constexpr uint32_t kHeadRuns = 127;   // runs that come down with the counter in one copy
 
+// A source's workgroups: ceil((n - 1) / kCarriedRows) of carried diagonals, then kTopBlocks of entering ones.  The count is
+// that of the widest strip, so the tables (sources, and the source of every workgroup) are built once.
 struct MatchSource {
   uint32_t src_off, n;  // arena offset and length (>= 2)
   uint32_t min_len, index;
@@ -57,19 +41,16 @@ struct MatchLane {
   void *to;          // ... and the one it writes
   uint32_t fed, width;      // J and the strip's columns [J, J + width)
   uint32_t stage_off;       // of the new hashes inside the round's buffer, in words
-  uint32_t lane, flags, pad;
+  uint32_t flags, pad[2];
 };
 static_assert(sizeof(MatchLane) == 48, "lane table entries are 12 words");
 
-struct MatchRun {  // NeedleHipRun + the lane (its slot in the round's table until the simhash kernel swaps the index in)
-  uint32_t problem, src_end, dst_end, len, src_hash, dst_hash, lane, pad;
+struct MatchRun {  // NeedleHipRun, of the source's table entry, + the lane's slot in the round's table: the host resolves both
+  uint32_t problem, src_end, dst_end, len, src_match_hash, dst_match_hash, lane, pad;
 };
 
 __global__ __launch_bounds__(kThreads) void matcher_land_kernel(const uint32_t *__restrict__ round_buf, uint32_t *__restrict__ count) {
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *count = 0u;
-  const MatchLane ln = reinterpret_cast<const MatchLane *>(round_buf)[blockIdx.y];
-  const uint32_t c = blockIdx.x * kThreads + threadIdx.x;
-  if (c < ln.width) ln.hist[ln.fed + c] = round_buf[ln.stage_off + c];
+  land_chunks<MatchLane>(round_buf, count, [](const MatchLane &ln) { return ln.hist; });
 }
 
 template <typename T>
@@ -79,76 +60,18 @@ __global__ __launch_bounds__(kThreads) void matcher_strip_kernel(const uint32_t 
                                                                  const MatchLane *__restrict__ lanes, uint32_t threshold,
                                                                  MatchRun *__restrict__ runs, uint32_t capacity,
                                                                  uint32_t *__restrict__ count) {
-  __shared__ uint32_t strip[kMaxStrip];               // dst[J .. J + W)
+  __shared__ uint32_t strip[kMaxStrip];                // dst[J .. J + W)
   __shared__ uint32_t rows[kCarriedRows + kMaxStrip];  // the source rows this workgroup's diagonals meet
   const uint32_t lo = block_source[blockIdx.x];
   const MatchSource sc = sources[lo];
   const MatchLane ln = lanes[blockIdx.y];
-  const uint32_t n = sc.n, W = ln.width, J = ln.fed, tid = threadIdx.x;
-  const uint32_t b = blockIdx.x - sc.block_base;
-  const bool carried = b < sc.carried_blocks;
-  // carried: the diagonals that cross column J - 1 at rows b * kCarriedRows ..; otherwise those that enter through row 1 at
-  // the strip's columns q0 ..
-  const uint32_t q0 = carried ? 0u : (b - sc.carried_blocks) * kThreads + 1u;
-  if (!carried && q0 >= W) return;  // (the whole workgroup)
-  const uint32_t seg0 = carried ? b * kCarriedRows + 1u : 1u;  // first row staged
-  const uint32_t steps = W - q0;                               // the most cells one of the workgroup's diagonals walks
-  {
-    const uint32_t seg_rows = steps ? min(n - seg0, (carried ? kCarriedRows : kThreads) - 1u + steps) : 0u;  // rows seg0 .. <= n - 1
-    const uint32_t *__restrict__ src = arena + sc.src_off + seg0;
-    for (uint32_t k = tid; k < seg_rows; k += kThreads) rows[k] = src[k];
-    for (uint32_t k = tid; k < W; k += kThreads) strip[k] = ln.hist[J + k];
-  }
-  __syncthreads();
-
-  const uint32_t lane = tid & 63u;
-  const uint32_t min_len = sc.min_len;
-  const bool emit_open = (ln.flags & kEmitOpen) != 0u;
-  // The runs of one step leave the wave together: one returning atomic for all of them (search.hip, round 6).
-  auto push = [&](const bool want, const uint32_t src_end, const uint32_t dst_end, const uint32_t len) {
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(want);
-    if (mask == 0ull) return;
-    uint32_t base = 0u;
-    if (lane == 0u) base = atomicAdd(count, (uint32_t)__popcll(mask));
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-    if (want && slot < capacity) runs[slot] = MatchRun{lo, src_end, dst_end, len, 0u, 0u, blockIdx.y, 0u};
-  };
-  // One diagonal per thread: first new cell (i0, J + q), `rel` = i0's place in the staged rows, `run` = the carried length.
-  // It walks w cells (i0 + c, J + q + c).  Every thread of the workgroup comes through here together.
-  auto walk = [&](const bool live, const uint32_t i0, const uint32_t q, const uint32_t rel, uint32_t run) {
-    const uint32_t w = live ? min(W - q, n - i0) : 0u;
-    for (uint32_t c = 0; c < steps; c++) {
-      bool ended = false;
-      uint32_t len = 0u;
-      if (c < w) {
-        // column 0 is no cell
-        const bool match = J + q + c >= 1u && (uint32_t)__popc(rows[rel + c] ^ strip[q + c]) <= threshold;
-        ended = !match && run >= min_len;  // the run ended at the previous cell
-        len = run;
-        run = match ? run + 1u : 0u;
-      }
-      push(ended, i0 + c - 1u, J + q + c - 1u, len);
-    }
-    // the last cell walked (with no columns: the cell of the carried length itself)
-    const uint32_t r = i0 + w - 1u, j = J + q + w - 1u;
-    const bool last_row = live && w > 0u && r == n - 1u;
-    const bool last_col = live && !last_row;  // then q + w == W
-    push((last_row || (last_col && emit_open)) && run >= min_len, r, j, run);
-    if (last_col && !emit_open) (static_cast<T *>(ln.to) + sc.row_off)[r] = (T)run;
-  };
-  if (carried) {
-    for (uint32_t part = 0; part < kCarriedRows; part += kThreads) {
-      const uint32_t t = b * kCarriedRows + part + tid;  // crosses column J - 1 at row t (row 0 is no cell: its length is 0)
-      if (t - tid >= n - 1u) break;                      // (the whole workgroup)
-      const bool live = t < n - 1u;
-      const uint32_t run = live && J > 0u && t >= 1u ? (uint32_t)(static_cast<const T *>(ln.from) + sc.row_off)[t] : 0u;
-      walk(live, t + 1u, 0u, part + tid, run);
-    }
-  } else {
-    const uint32_t q = q0 + tid;  // enters through row 1 at column J + q
-    walk(q < W, 1u, q, 0u, 0u);
-  }
+  // a lane that holds fewer than two items has no cell yet, whatever a reset left in its sets
+  const WalkSide<T> sd{arena + sc.src_off, ln.hist, sc.n, max(ln.fed, 1u), max(ln.fed + ln.width, 1u), sc.n - 1u,
+                       ln.fed >= 2u ? static_cast<const T *>(ln.from) + sc.row_off : nullptr, static_cast<T *>(ln.to) + sc.row_off, nullptr, true};
+  stream_walk<T, true>(strip, rows, sd, blockIdx.x - sc.block_base, sc.carried_blocks, (ln.flags & kEmitOpen) != 0u, threshold, sc.min_len, runs,
+                       capacity, count, [&](const uint32_t src_end, const uint32_t dst_end, const uint32_t len) {
+                         return MatchRun{lo, src_end, dst_end, len, 0u, 0u, blockIdx.y, 0u};
+                       });
 }
 
 __global__ __launch_bounds__(kThreads) void matcher_simhash_kernel(const uint32_t *__restrict__ arena,
@@ -156,26 +79,10 @@ __global__ __launch_bounds__(kThreads) void matcher_simhash_kernel(const uint32_
                                                                    const MatchLane *__restrict__ lanes,
                                                                    MatchRun *__restrict__ runs, uint32_t capacity,
                                                                    const uint32_t *__restrict__ count) {
-  const uint32_t total = min(*count, capacity);
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = (gridDim.x * blockDim.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const TransposeLane t = transpose_lane(lane);
-  for (uint32_t k = wave; k < total; k += waves) {
-    const MatchRun r = runs[k];
-    const MatchSource sc = sources[r.problem];
-    const MatchLane ln = lanes[r.lane];
-    uint32_t src_hash = 0u, dst_hash = 0u;
-    if ((ln.flags & kNoHash) == 0u) {  // (wave-uniform)
-      src_hash = wave_simhash32(arena + sc.src_off + (r.src_end - r.len), r.len + 1u, lane, t);
-      dst_hash = wave_simhash32(ln.hist + (r.dst_end - r.len), r.len + 1u, lane, t);
-    }
-    if (lane == 0) {
-      runs[k].problem = sc.index;
-      runs[k].lane = ln.lane;
-      runs[k].src_hash = src_hash;
-      runs[k].dst_hash = dst_hash;
-    }
-  }
+  simhash_runs(
+      runs, capacity, count,
+      [&](const MatchRun &r) -> const uint32_t * { return lanes[r.lane].flags & kNoHash ? nullptr : arena + sources[r.problem].src_off; },
+      [&](const MatchRun &r) -> const uint32_t * { return lanes[r.lane].flags & kNoHash ? nullptr : lanes[r.lane].hist; });
 }
 
 struct LaneState {
@@ -209,9 +116,9 @@ struct Matcher::Impl {
   std::vector<uint32_t> block_source;  // the table entry of every workgroup of the scan's grid
   DeviceBuffer<uint32_t> d_block_source;
   DeviceBuffer<uint8_t> state[2];
-  DeviceBuffer<uint32_t> d_round, slab;
-  uint32_t capacity = 4096;  // runs the slab holds
-  PinnedStage round_stage, head_stage;
+  DeviceBuffer<uint32_t> d_round;
+  PinnedStage round_stage;
+  RunSlab<MatchRun> slab;
   Status poison = Status::Ok();
   uint64_t feeds = 0, launches = 0, cells = 0, arena_bytes = 0;
 
@@ -219,10 +126,8 @@ struct Matcher::Impl {
     std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
     for (LaneState &l : lanes)
       if (l.hist) (void)hipFree(l.hist);
-    for (PinnedStage *st : {&round_stage, &head_stage}) {
-      if (st->ptr) (void)hipHostFree(st->ptr);
-      if (st->done) (void)hipEventDestroy(st->done);
-    }
+    round_stage.release();
+    slab.head_stage.release();
   }
 
   size_t state_elem() const { return narrow ? sizeof(uint16_t) : sizeof(uint32_t); }
@@ -271,26 +176,19 @@ struct Matcher::Impl {
       e.fed = (uint32_t)l.fed;
       e.width = p.width;
       e.stage_off = (uint32_t)words;
-      e.lane = (uint32_t)p.lane;
       e.flags = p.flags;
-      e.pad = 0;
       words += p.width;
       round_cells += cells_per_column * (uint64_t)(p.width - (l.fed == 0 && p.width ? 1u : 0u));
     }
-    if (!(s = d_round.reserve(words)).ok() || !(s = round_stage.acquire(words * 4)).ok()) return s;
-    std::memcpy(round_stage.ptr, lt.data(), k * sizeof(MatchLane));
-    for (size_t a = 0; a < k; a++)
-      if (pieces[a].width) std::memcpy(static_cast<uint32_t *>(round_stage.ptr) + lt[a].stage_off, pieces[a].items, (size_t)pieces[a].width * 4);
-    NEEDLE_HIP_TRY(hipMemcpyAsync(d_round.ptr, round_stage.ptr, words * 4, hipMemcpyHostToDevice, stream));
-    round_stage.mark(stream);
+    if (!(s = upload_round(lt, pieces, words, &d_round, &round_stage, stream)).ok()) return s;
 
     const MatchLane *d_lanes = reinterpret_cast<const MatchLane *>(d_round.ptr);
     const dim3 block(kThreads);
     std::vector<MatchRun> got;
     for (;;) {
-      if (!(s = slab.reserve(kHeaderWords + (uint64_t)capacity * (sizeof(MatchRun) / 4))).ok()) return s;
-      uint32_t *d_count = slab.ptr;
-      MatchRun *d_runs = reinterpret_cast<MatchRun *>(slab.ptr + kHeaderWords);
+      uint32_t *d_count = nullptr;
+      MatchRun *d_runs = nullptr;
+      if (!(s = slab.begin(&d_count, &d_runs)).ok()) return s;
       {
         KernelTimer timer("matcher_land");
         hipLaunchKernelGGL(matcher_land_kernel, dim3((std::max(widest, 1u) + kThreads - 1) / kThreads, (uint32_t)k), block, 0, stream,
@@ -301,42 +199,29 @@ struct Matcher::Impl {
         KernelTimer timer("matcher_strip");
         if (narrow)
           hipLaunchKernelGGL(matcher_strip_kernel<uint16_t>, dim3(total_blocks, (uint32_t)k), block, 0, stream, arena.ptr, d_table.ptr,
-                             d_block_source.ptr, d_lanes, threshold, d_runs, capacity, d_count);
+                             d_block_source.ptr, d_lanes, threshold, d_runs, slab.capacity, d_count);
         else
           hipLaunchKernelGGL(matcher_strip_kernel<uint32_t>, dim3(total_blocks, (uint32_t)k), block, 0, stream, arena.ptr, d_table.ptr,
-                             d_block_source.ptr, d_lanes, threshold, d_runs, capacity, d_count);
+                             d_block_source.ptr, d_lanes, threshold, d_runs, slab.capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       {
         KernelTimer timer("matcher_simhash");
         hipLaunchKernelGGL(matcher_simhash_kernel, dim3((uint32_t)device_cu_count() * 2u), block, 0, stream, arena.ptr, d_table.ptr, d_lanes,
-                           d_runs, capacity, d_count);
+                           d_runs, slab.capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       launches += 3;
       cells += round_cells;
-      // the counter and the first runs in one copy; the rest, if any, in a second one
-      const uint32_t head = std::min(capacity, kHeadRuns);
-      const size_t head_bytes = kHeaderWords * 4 + (size_t)head * sizeof(MatchRun);
-      if (!(s = head_stage.acquire(head_bytes)).ok()) return s;
-      NEEDLE_HIP_TRY(hipMemcpyAsync(head_stage.ptr, slab.ptr, head_bytes, hipMemcpyDeviceToHost, stream));
-      NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+      bool again = false;  // a larger slab, and the round again from the set it did not write
+      if (!(s = slab.collect(stream, &got, &again)).ok()) return s;
       round_stage.pending = false;
-      const uint32_t found = *static_cast<const uint32_t *>(head_stage.ptr);
-      if (found > capacity) {  // nothing is lost: a larger slab, and the round again from the set it did not write
-        capacity = std::max(found, capacity * 2);
-        continue;
-      }
-      got.resize(found);
-      const uint32_t first = std::min(found, head);
-      if (first) std::memcpy(got.data(), static_cast<const char *>(head_stage.ptr) + kHeaderWords * 4, (size_t)first * sizeof(MatchRun));
-      if (found > first) NEEDLE_HIP_TRY(hipMemcpy(got.data() + first, d_runs + first, (size_t)(found - first) * sizeof(MatchRun), hipMemcpyDeviceToHost));
-      break;
+      if (!again) break;
     }
     for (const MatchRun &r : got) {
-      const NeedleHipRun out{r.problem, r.src_end, r.dst_end, r.len, r.src_hash, r.dst_hash};
+      const NeedleHipRun out{table[r.problem].index, r.src_end, r.dst_end, r.len, r.src_match_hash, r.dst_match_hash};
       if (open_out) open_out->push_back(out);
-      else lanes[r.lane].runs.push_back(out);
+      else lanes[pieces[r.lane].lane].runs.push_back(out);
     }
     if (open_out) return Status::Ok();
     for (const Piece &p : pieces) {
@@ -352,9 +237,7 @@ struct Matcher::Impl {
   }
 
   Status guarded_round(const std::vector<Piece> &pieces, std::vector<NeedleHipRun> *open_out) {
-    Status s = round(pieces, open_out);
-    if (!s.ok() && s.code != NeedleError_InvalidArgument && s.code != NeedleError_NullArgument) poison = s;
-    return s;
+    return poison_on_failure(round(pieces, open_out), &poison);
   }
 };
 
@@ -397,7 +280,7 @@ Status Matcher::Create(const uint32_t *hashes, size_t num_hashes, const NeedleHi
   m.threshold = threshold;
   m.total_blocks = (uint32_t)blocks;
   m.lanes = std::vector<LaneState>(lanes);
-  if (const char *e = getenv("NEEDLE_HIP_MATCHER_RUN_SLAB")) m.capacity = (uint32_t)std::min<long long>(std::max(1ll, atoll(e)), 1ll << 26);
+  m.slab.capacity_from_env("NEEDLE_HIP_MATCHER_RUN_SLAB");
 
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
   Status s = ensure_device();
@@ -462,32 +345,14 @@ Status Matcher::Feed(const uint32_t *const *items, const size_t *num_items) {
 
 Status Matcher::FeedFromFeeder(Feeder *feeder) {
   Impl &m = *impl_;
-  if (!feeder) return Status::Make(NeedleError_NullArgument, "matcher: null argument");
-  if (feeder->lanes() != m.n) return Status::Make(NeedleError_InvalidArgument, "matcher: the feeder has another number of lanes");
-  if (!m.poison.ok()) return m.poison;
-  std::vector<std::vector<uint32_t>> taken(m.n);
-  std::vector<const uint32_t *> ptrs(m.n, nullptr);
-  std::vector<size_t> counts(m.n, 0), finish;
-  for (size_t i = 0; i < m.n; i++) {
-    size_t kept = 0;
-    bool finished = false;
-    Status s = feeder->Ready(i, &kept, nullptr, &finished);
-    if (!s.ok()) return s;
-    const LaneState &l = m.lanes[i];
-    if (l.finished) {
-      if (kept != l.fed || !finished) return Status::Make(NeedleError_InvalidArgument, "matcher: the lane is finished (reset it first)");
-      continue;
-    }
-    if (kept < l.fed) return Status::Make(NeedleError_InvalidArgument, "matcher: the feeder's lane holds fewer items than the matcher has taken");
-    taken[i].resize(kept - l.fed);
-    if (!taken[i].empty() && !(s = feeder->Items(i, (size_t)l.fed, taken[i].size(), taken[i].data())).ok()) return s;
-    ptrs[i] = taken[i].data();
-    counts[i] = taken[i].size();
-    if (finished) finish.push_back(i);
-  }
-  Status s = Feed(ptrs.data(), counts.data());
-  if (!s.ok() || finish.empty()) return s;
-  return Finish(finish.data(), finish.size());
+  FeederTake take;
+  Status s = take_from_feeder(
+      feeder, m.n, m.poison, [&](size_t i, uint64_t *fed, bool *finished) { *fed = m.lanes[i].fed, *finished = m.lanes[i].finished; }, "matcher: ",
+      " (reset it first)", &take);
+  if (!s.ok()) return s;
+  s = Feed(take.ptrs.data(), take.counts.data());
+  if (!s.ok() || take.finish.empty()) return s;
+  return Finish(take.finish.data(), take.finish.size());
 }
 
 Status Matcher::Finish(const size_t *lanes, size_t k) {

@@ -1,6 +1,6 @@
 // chromaprint's simhash32 of a slice of hashes by one wave (comparator.rs:149-153): the arithmetic the run-reporting
-// kernels share (search.hip simhash_runs_kernel, matcher.hip matcher_simhash_kernel).  How it works, and what it replaced,
-// is told in search.hip above simhash_runs_kernel.
+// kernels share (search.hip simhash_runs_kernel; stream_walk.h simhash_runs, the body of matcher_simhash_kernel and
+// crossmatch_simhash_kernel).  How it works, and what it replaced, is told in search.hip above simhash_runs_kernel.
 #pragma once
 
 #include <hip/hip_runtime.h>
