@@ -60,6 +60,10 @@ double needle_hip_last_kernel_ms(const char *kernel);
  * needle_hip_last_kernel_ms returns their SUM (it waits for them): a kernel that one job launches several times -- the
  * first pass of a library-scale job -- then reads as the job's total, not as its last launch's. */
 void needle_hip_set_kernel_timing(const char *kernels);
+/* With "sum": the launches of that name that have been given events since the last needle_hip_set_kernel_timing call;
+ * otherwise, and for an unknown name, 0.  Only the first 4096 launches of a name keep events: the count stops there, so a
+ * reader that may see more sets the selection again in between.  Further names: "ingest", "feeder_carry". */
+size_t needle_hip_kernel_launches(const char *kernel);
 /* Diagnostic for the search roofline: table cells per second this device sustains on the scan's
  * per-cell instruction sequence (xor, popcount, compare, select) with operands in registers -- the integer-VALU
  * ceiling a brute-force evaluation of every cell of comparator.rs:176-187 cannot exceed.  Takes ~10 ms. */
@@ -576,6 +580,46 @@ enum NeedleError needle_hip_feeder_set_audit(NeedleHipFeeder *feeder, bool on);
 enum NeedleError needle_hip_feeder_audit(NeedleHipFeeder *feeder, size_t lane, NeedleHipCertAudit *audit);
 /* pure host arithmetic, no device: kept items a lane holds after that many samples */
 size_t needle_hip_feeder_num_ready(uint64_t samples_per_channel_fed, int sample_rate, int channels, uint32_t step, bool finished);
+
+/* ---- A feeder whose lanes have a rate, a channel count and a sample format of their own -------------------
+ * A season is rarely uniform (stereo 44.1 kHz episodes among 5.1 48 kHz ones, one planar-float rip): such a feeder takes
+ * it whole, one lane per decoder as before, and is what the matchers' feed_from_feeder and frame_hashes want -- one
+ * feeder whose lanes are the season's.  Limits per lane: those of needle_hip_feeder_new (channels 1..8, sample_rate
+ * 2000..768000, every NeedleHipSampleFormat), checked for every lane before any device is asked for.
+ *
+ * The pointer array of `feed` is the concatenation, lane after lane, of each lane's planes: 1 pointer for an
+ * interleaved lane, channels_i for a planar one.  num_values[i] counts lane i's values (frames x channels_i); a chunk
+ * that is not whole frames of its own lane is InvalidArgument before any device work.  finish, reset, ready, items,
+ * frame_hashes, state_bytes, set_audit, audit and both feed_from_feeder mean what they mean above; ready's kept_items
+ * equals needle_hip_feeder_num_ready(samples, rate_i, channels_i, step, finished) with the lane's own rate.
+ *
+ * Every lane of such a feeder is reduced to MONO as it lands -- needle_hip_convert_host's conversion, then
+ * needle_hip_downmix_host's (sum of the frame) / channels, 2 channels included -- by one kernel launch per round whatever
+ * the mixture, so both tails of every lane are mono: state_bytes' bytes[0] stays within the mono bound of the lane's
+ * rate (76 176 B at 11025 Hz) whatever the channel count.  The items are those of the one-shot path all the same: every
+ * reader of stereo PCM there (the transform at 11025 Hz, the resampler elsewhere) begins with the same integer
+ * (L + R) / 2, C truncation.  Behind the landing a round is the round of needle_hip_feeder_new's feeder, the resampler
+ * launched once per distinct rate other than 11025 Hz among the lanes that complete output tiles in it.
+ *
+ * A feeder made by needle_hip_feeder_new is untouched by all this: its launches, its state (stereo tails stay stereo),
+ * its state_bytes; it refuses reset_format (InvalidArgument, nothing changed).  lane_format works on both kinds. */
+typedef struct NeedleHipLaneFormat {
+  int32_t channels;
+  int32_t sample_rate;
+  int32_t format; /* enum NeedleHipSampleFormat */
+} NeedleHipLaneFormat;
+enum NeedleError needle_hip_feeder_new_lanes(const NeedleHipLaneFormat *formats, size_t lanes, uint32_t step, NeedleHipFeeder **output);
+enum NeedleError needle_hip_feeder_lane_format(const NeedleHipFeeder *feeder, size_t lane, NeedleHipLaneFormat *format);
+/* lanes[j] starts a new stream in formats[j] (as needle_hip_feeder_reset, which keeps a lane's format); only on a feeder
+ * made by needle_hip_feeder_new_lanes.  Every lane and every format -- its limits, and that the resampler has a design for
+ * its rate (a few rates inside the limits have none: 11025 / 44101 is too long a ratio, as for needle_hip_feeder_new) -- is
+ * checked before any lane is reset: InvalidArgument, nothing changed, not for the lanes named earlier in the call either. */
+enum NeedleError needle_hip_feeder_reset_format(NeedleHipFeeder *feeder, const size_t *lanes, const NeedleHipLaneFormat *formats, size_t k);
+/* The front end of such a feeder on its own: out[i] receives mono s16, num_values[i] / channels_i values (a trailing
+ * partial frame is dropped); pcm is the concatenation of the streams' planes as in `feed`; sample_rate is not looked at.
+ * One kernel launch per batch of at most NEEDLE_HIP_MAX_BATCH_VALUES values, whatever the mixture of formats. */
+enum NeedleError needle_hip_convert_mono_host(const void *const *pcm, const size_t *num_values, const NeedleHipLaneFormat *formats,
+                                              size_t num_streams, int16_t *const *out);
 
 /* ---- Streaming comparator: search as the hashes arrive ---------------------------------------------------
  * The search half of the streaming path, the counterpart of the feeder.  A matcher holds S source sequences (the

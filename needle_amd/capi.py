@@ -74,7 +74,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_device_pci_bus_id", "needle_hip_fingerprint_cert_stats", "needle_hip_scan_issued_evaluations",
     "needle_hip_last_error_message",
     "needle_hip_version", "needle_hip_malloc", "needle_hip_free", "needle_hip_memcpy_h2d", "needle_hip_memcpy_d2h",
-    "needle_hip_host_free", "needle_hip_last_kernel_ms", "needle_hip_set_kernel_timing", "needle_hip_fingerprint_sample_rate",
+    "needle_hip_host_free", "needle_hip_last_kernel_ms", "needle_hip_set_kernel_timing", "needle_hip_kernel_launches", "needle_hip_fingerprint_sample_rate",
     "needle_hip_fingerprint_delay_ms", "needle_hip_fingerprint_item_duration_ms", "needle_hip_fingerprint_num_items",
     "needle_hip_fingerprint_num_kept", "needle_hip_fingerprint_host", "needle_hip_fingerprint_device",
     "needle_hip_fingerprint_debug", "needle_hip_resample_out_len", "needle_hip_resample_host", "needle_hip_downmix_host",
@@ -107,6 +107,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_feeder_new", "needle_hip_feeder_free", "needle_hip_feeder_feed", "needle_hip_feeder_finish",
     "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
     "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready", "needle_hip_feeder_set_audit", "needle_hip_feeder_audit",
+    "needle_hip_feeder_new_lanes", "needle_hip_feeder_lane_format", "needle_hip_feeder_reset_format", "needle_hip_convert_mono_host",
     "needle_hip_matcher_new", "needle_hip_matcher_free", "needle_hip_matcher_feed", "needle_hip_matcher_feed_from_feeder",
     "needle_hip_matcher_finish", "needle_hip_matcher_reset", "needle_hip_matcher_ready", "needle_hip_matcher_runs",
     "needle_hip_matcher_open", "needle_hip_matcher_stats",
@@ -154,6 +155,28 @@ def _format_pointers(pcm, channels: int, sample_format: int):
             ptrs += [q.ctypes.data for q in planes]
     return keep, ptrs
 
+
+class CLaneFormat(C.Structure):                          # NeedleHipLaneFormat
+    _fields_ = [("channels", C.c_int32), ("sample_rate", C.c_int32), ("format", C.c_int32)]
+
+
+def _lane_formats(formats):
+    """NeedleHipLaneFormat array of (channels, sample_rate, sample_format) triples."""
+    return (CLaneFormat * max(len(formats), 1))(*[CLaneFormat(int(c), int(r), int(f)) for c, r, f in formats])
+
+
+def _lane_pointers(pcm, formats):
+    """(arrays to keep alive, flat pointer list, values per stream) of streams that each have a format of their own: the
+    concatenation, stream after stream, of each stream's planes -- 1 pointer for an interleaved stream, `channels` for a
+    planar one."""
+    keep, flat, sizes = [], [], []
+    for p, (channels, _, sample_format) in zip(pcm, formats):
+        k, f = _format_pointers([p], channels, sample_format)
+        keep += k
+        flat += f
+        sizes.append(0 if p is None else (sum(np.size(q) for q in p) if sample_format_planar(sample_format) else np.size(p)))
+    return keep, flat, sizes
+
 _LIB = None
 
 
@@ -198,6 +221,8 @@ def lib():
     L.needle_hip_host_free.restype = None
     L.needle_hip_last_kernel_ms.argtypes = [C.c_char_p]
     L.needle_hip_last_kernel_ms.restype = C.c_double
+    L.needle_hip_kernel_launches.argtypes = [C.c_char_p]
+    L.needle_hip_kernel_launches.restype = sz
     L.needle_hip_set_kernel_timing.argtypes = [C.c_char_p]
     L.needle_hip_set_kernel_timing.restype = None
     L.needle_hip_fingerprint_sample_rate.restype = C.c_int
@@ -294,6 +319,10 @@ def lib():
     L.needle_hip_feeder_audit.argtypes = [vp, sz, vp]
     L.needle_hip_feeder_num_ready.argtypes = [u64, C.c_int, C.c_int, u32, b]
     L.needle_hip_feeder_num_ready.restype = sz
+    L.needle_hip_feeder_new_lanes.argtypes = [vp, sz, u32, C.POINTER(vp)]
+    L.needle_hip_feeder_lane_format.argtypes = [vp, sz, vp]
+    L.needle_hip_feeder_reset_format.argtypes = [vp, C.POINTER(sz), vp, sz]
+    L.needle_hip_convert_mono_host.argtypes = [C.POINTER(vp), C.POINTER(sz), vp, sz, C.POINTER(vp)]
     L.needle_hip_matcher_new.argtypes = [vp, sz, vp, vp, sz, sz, u32, C.POINTER(vp)]
     L.needle_hip_matcher_free.argtypes = [vp]
     L.needle_hip_matcher_free.restype = None
@@ -426,6 +455,11 @@ def int_valu_ceiling() -> float:
 
 def last_kernel_ms(name: str) -> float:
     return lib().needle_hip_last_kernel_ms(name.encode())
+
+
+def kernel_launches(name: str) -> int:
+    """Launches of that timer name since set_kernel_timing("...,sum") (needle_hip_kernel_launches)."""
+    return int(lib().needle_hip_kernel_launches(name.encode()))
 
 
 def set_kernel_timing(kernels: Optional[str]) -> None:
@@ -803,15 +837,48 @@ class Feeder:
         check(lib().needle_hip_feeder_new(lanes, channels, sample_rate, sample_format, step, C.byref(h)))
         self._h = h
         self.lanes, self.channels, self.sample_rate, self.sample_format, self.step = lanes, channels, sample_rate, sample_format, step
+        self.formats = None
+
+    @classmethod
+    def with_formats(cls, formats: Sequence[Tuple[int, int, int]], step: int = 1) -> "Feeder":
+        """needle_hip_feeder_new_lanes: one lane per (channels, sample_rate, sample_format) triple.  Every lane is
+        down-mixed to mono as it lands; the items are the one-shot path's."""
+        self = cls.__new__(cls)
+        self._h = None
+        formats = [tuple(int(v) for v in f) for f in formats]
+        h = C.c_void_p()
+        check(lib().needle_hip_feeder_new_lanes(_lane_formats(formats), len(formats), step, C.byref(h)))
+        self._h = h
+        self.lanes, self.step, self.formats = len(formats), step, formats
+        self.channels = self.sample_rate = self.sample_format = None  # per lane: lane_format
+        return self
+
+    def lane_format(self, lane: int) -> Tuple[int, int, int]:
+        """(channels, sample_rate, sample_format) of a lane, of either kind of feeder."""
+        f = CLaneFormat()
+        check(lib().needle_hip_feeder_lane_format(self._h, lane, C.byref(f)))
+        return f.channels, f.sample_rate, f.format
+
+    def reset_format(self, lanes: Sequence[int], formats: Sequence[Tuple[int, int, int]]) -> None:
+        """lanes[j] starts a new stream in formats[j] (needle_hip_feeder_reset_format; a with_formats feeder only)."""
+        if len(lanes) != len(formats):
+            raise ValueError("one format per lane")
+        arr, k = self._lanes(list(lanes))
+        check(lib().needle_hip_feeder_reset_format(self._h, arr, _lane_formats(formats), k))
+        for lane, f in zip(lanes, formats):
+            self.formats[lane] = tuple(int(v) for v in f)
 
     def feed(self, pcm: Sequence) -> None:
         """pcm[i]: what lane i has decoded since the last feed (interleaved: one array; planar: `channels` planes), or
         None / an empty array for nothing."""
         if len(pcm) != self.lanes:
             raise ValueError(f"one chunk per lane: {self.lanes}, got {len(pcm)}")
-        planar = sample_format_planar(self.sample_format)
-        keep, flat = _format_pointers(pcm, self.channels, self.sample_format)
-        sizes = [0 if p is None else (sum(np.size(q) for q in p) if planar else np.size(p)) for p in pcm]
+        if self.formats is not None:
+            keep, flat, sizes = _lane_pointers(pcm, self.formats)
+        else:
+            planar = sample_format_planar(self.sample_format)
+            keep, flat = _format_pointers(pcm, self.channels, self.sample_format)
+            sizes = [0 if p is None else (sum(np.size(q) for q in p) if planar else np.size(p)) for p in pcm]
         ptrs = (C.c_void_p * max(len(flat), 1))(*flat)
         lens = (C.c_size_t * max(len(sizes), 1))(*sizes)
         check(lib().needle_hip_feeder_feed(self._h, ptrs, lens))
@@ -1156,6 +1223,27 @@ def convert(pcms: Sequence, channels: int, sample_format: int, num_values: Optio
     lens = (C.c_size_t * max(n, 1))(*[int(v) for v in num_values])
     optrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
     check(lib().needle_hip_convert_host(ptrs, lens, n, channels, sample_format, optrs))
+    del keep
+    return [o[:k] for o, k in zip(outs, lens_out)]
+
+
+def convert_mono(pcms: Sequence, formats: Sequence[Tuple[int, int, int]], num_values: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+    """needle_hip_convert_mono_host: streams that each have a format of their own -- formats[i] = (channels, sample_rate,
+    sample_format), the rate is not looked at -- -> mono s16: `convert`, then `downmix`, in one kernel whatever the mixture.
+    num_values (samples over all channels per stream) defaults to the arrays' sizes."""
+    formats = [tuple(int(v) for v in f) for f in formats]
+    if len(formats) != len(pcms):
+        raise ValueError("one format per stream")
+    keep, flat, sizes = _lane_pointers(pcms, formats)
+    n = len(pcms)
+    if num_values is None:
+        num_values = sizes
+    lens_out = [int(v) // max(f[0], 1) for v, f in zip(num_values, formats)]
+    outs = [np.zeros(max(k, 1), dtype=np.int16) for k in lens_out]
+    ptrs = (C.c_void_p * max(len(flat), 1))(*flat)
+    lens = (C.c_size_t * max(n, 1))(*[int(v) for v in num_values])
+    optrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    check(lib().needle_hip_convert_mono_host(ptrs, lens, _lane_formats(formats), n, optrs))
     del keep
     return [o[:k] for o, k in zip(outs, lens_out)]
 

@@ -486,6 +486,7 @@ enum NeedleError needle_hip_int_valu_ceiling(double *cells_per_second) {
 
 double needle_hip_last_kernel_ms(const char *kernel) { return kernel ? kernel_ms(kernel) : -1.0; }
 void needle_hip_set_kernel_timing(const char *kernels) { set_kernel_timing(kernels); }
+size_t needle_hip_kernel_launches(const char *kernel) { return kernel ? kernel_launches(kernel) : 0; }
 
 // ============================================================================================================
 // fingerprint
@@ -633,6 +634,33 @@ enum NeedleError needle_hip_convert_host(const void *const *pcm, const size_t *n
   });
 }
 
+enum NeedleError needle_hip_convert_mono_host(const void *const *pcm, const size_t *num_values, const NeedleHipLaneFormat *formats,
+                                              size_t num_streams, int16_t *const *out) {
+  if (!pcm || !num_values || !formats || !out) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const void *> p;
+    std::vector<size_t> n(num_values, num_values + num_streams);
+    std::vector<int> channels(num_streams), fmts(num_streams);
+    std::vector<int16_t *> o(out, out + num_streams);
+    for (size_t i = 0; i < num_streams; i++) {  // every stream is checked before any pointer is counted off
+      channels[i] = formats[i].channels;
+      fmts[i] = formats[i].format;
+      if (channels[i] < 1 || channels[i] > NEEDLE_HIP_MAX_CHANNELS || !sample_format_valid(fmts[i])) return NeedleError_InvalidArgument;
+    }
+    for (size_t i = 0; i < num_streams; i++) {
+      const size_t planes = sample_format_planes(fmts[i], channels[i]);
+      if (n[i] >= (size_t)channels[i]) {  // otherwise no whole frame: nothing is read or written
+        if (!o[i]) return NeedleError_NullArgument;
+        for (size_t c = 0; c < planes; c++)
+          if (!pcm[p.size() + c]) return NeedleError_NullArgument;
+      }
+      p.insert(p.end(), pcm + p.size(), pcm + p.size() + planes);
+    }
+    Status s = gpu_convert_mono_host(p, n, channels, fmts, o);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 // ============================================================================================================
 // search
 // ============================================================================================================
@@ -677,6 +705,33 @@ enum NeedleError needle_hip_feeder_new(size_t lanes, int channels, int sample_ra
     if (!s.ok()) return report(s);
     *output = f.release();
     return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_feeder_new_lanes(const NeedleHipLaneFormat *formats, size_t lanes, uint32_t step, NeedleHipFeeder **output) {
+  if (!output || !formats) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto f = std::make_unique<NeedleHipFeeder>();
+    Status s = Feeder::CreateLanes(formats, lanes, step, &f->inner);
+    if (!s.ok()) return report(s);
+    *output = f.release();
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_feeder_lane_format(const NeedleHipFeeder *feeder, size_t lane, NeedleHipLaneFormat *format) {
+  if (!feeder || !format) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->LaneFormat(lane, format);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_reset_format(NeedleHipFeeder *feeder, const size_t *lanes, const NeedleHipLaneFormat *formats, size_t k) {
+  if (!feeder || !lanes || !formats) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->ResetFormat(lanes, formats, k);
+    return s.ok() ? NeedleError_Ok : report(s);
   });
 }
 

@@ -300,4 +300,20 @@ Status gpu_fingerprint_streamed_device_format(const std::vector<const void *> &p
 Status gpu_convert_host(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels, int format,
                         const std::vector<int16_t *> &out);
 
+// ---- the front end of a feeder whose lanes have formats of their own (convert.hip feeder_ingest_kernel) -----
+// A span in its own format -> mono s16: gpu_convert_host's conversion, then gpu_downmix_host's (sum of the frame's
+// `channels` converted values) / channels, whatever the channel count (1: the conversion alone).
+struct IngestSpan {
+  const void *src[NEEDLE_HIP_MAX_CHANNELS];  // device; as ConvertSpan's, by the span's own format and channels
+  int16_t *dst;                              // device, a buffer of its own: frames mono values, any 2-byte alignment
+  uint64_t frames;
+  int channels, format;
+};
+// one launch on the library stream for all spans, whatever mixture of formats; returns after enqueueing unless `sync`
+Status gpu_ingest_device(const std::vector<IngestSpan> &spans, bool sync);
+// host arrays in and out (pcm: the concatenation of every stream's sample_format_planes() pointers; out[i] holds
+// num_values[i] / channels[i] values), in batches of bounded device memory
+Status gpu_convert_mono_host(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values,
+                             const std::vector<int> &channels, const std::vector<int> &formats, const std::vector<int16_t *> &out);
+
 }  // namespace needle

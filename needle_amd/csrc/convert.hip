@@ -157,6 +157,146 @@ __global__ __launch_bounds__(kCvThreads) void convert_kernel(const CvStream *__r
   }
 }
 
+// ---- the ingest of a feeder whose lanes have formats of their own ---------------------------------------------------
+// One launch over spans of ANY mixture of sample type, layout and channel count, every one of them to mono s16:
+// to_s16 per sample, then (sum of the frame's C values) / C on the int sum (C = 1: the conversion alone).  The mould
+// is convert_kernel's -- virtual blocks of 256 lanes x 8 frames (16 of u8), grid stride, the span found by binary search
+// -- but format and C are read from the span's entry, uniform over the workgroup: the sample type is switched over, C
+// is a run-time loop.  A lane keeps FPL int sums at most, so the kernel's registers do not grow with C:
+//   planar       plane after plane, FPL samples of each in 16-byte loads, added into the lane's FPL sums;
+//   interleaved  the lane's FPL * C samples are C * FPL * sizeof(T) / 16 consecutive 16-byte words; their samples go by
+//                in frame order, so one running sum and a channel counter do, and each finished frame is shifted
+//                into the top of the lane's FPL / 2 output words (after FPL of them the first sits at the bottom).
+// Sources that are not all 16-byte aligned (`vec` = 0, found on the host: a lane's first sample lies a multiple of 16
+// bytes behind the span's) and the last frames of a span take the scalar path.
+struct IngestStream {
+  const void *src[NEEDLE_HIP_MAX_CHANNELS];  // planar: plane c; interleaved: src[0]
+  int16_t *dst;
+  uint64_t frames;
+  uint64_t block_base;  // first virtual block of this span
+  int32_t channels;
+  int32_t type;    // format % 5
+  int32_t planar;  // one plane per channel (and more than one channel)
+  int32_t vec;     // every source pointer is 16-byte aligned
+};
+
+namespace {
+
+// sum / C, C's division on the int sum, by a constant in every case: C is uniform over the workgroup, so the switch is
+// one scalar branch and the divide a multiply-high and shifts instead of the emulated run-time division
+__device__ __forceinline__ int div_channels(int sum, int C) {
+  switch (C) {
+    case 1: return sum;
+    case 2: return sum / 2;
+    case 3: return sum / 3;
+    case 4: return sum / 4;
+    case 5: return sum / 5;
+    case 6: return sum / 6;
+    case 7: return sum / 7;
+    default: return sum / 8;
+  }
+}
+
+template <typename T>
+__device__ __forceinline__ void ingest_block(const IngestStream *__restrict__ st, uint64_t block) {
+  constexpr int FPL = frames_per_lane<T>();
+  constexpr int NW = FPL / 2;  // output words of a lane, two s16 each
+  const uint64_t frames = st->frames;
+  const uint64_t f0 = block * ((uint64_t)kCvThreads * FPL) + (uint64_t)threadIdx.x * FPL;
+  if (f0 >= frames) return;
+  const int C = st->channels;
+  const bool planar = st->planar != 0;
+  int16_t *y = st->dst + f0;
+  if (f0 + FPL <= frames && st->vec) {
+    uint32_t w[NW];
+    if (planar) {
+      constexpr int NV = FPL * (int)sizeof(T) / 16;
+      int sum[FPL];
+#pragma unroll
+      for (int f = 0; f < FPL; f++) sum[f] = 0;
+      for (int c = 0; c < C; c++) {
+        const uint4 *x = reinterpret_cast<const uint4 *>(static_cast<const T *>(st->src[c]) + f0);
+        uint4 raw[NV];
+#pragma unroll
+        for (int k = 0; k < NV; k++) raw[k] = x[k];
+        T p[FPL];
+        __builtin_memcpy(p, raw, sizeof(raw));
+#pragma unroll
+        for (int f = 0; f < FPL; f++) sum[f] += to_s16<T>(p[f]);
+      }
+#pragma unroll
+      for (int i = 0; i < NW; i++)
+        w[i] = (uint32_t)(uint16_t)(int16_t)div_channels(sum[2 * i], C) | ((uint32_t)(uint16_t)(int16_t)div_channels(sum[2 * i + 1], C) << 16);
+    } else {
+      constexpr int SPW = 16 / (int)sizeof(T);  // samples per 16-byte word
+      const uint4 *x = reinterpret_cast<const uint4 *>(static_cast<const T *>(st->src[0]) + f0 * (uint64_t)C);
+      const int words = C * (FPL / SPW);
+#pragma unroll
+      for (int i = 0; i < NW; i++) w[i] = 0;
+      int sum = 0, ch = 0;
+      for (int k = 0; k < words; k++) {
+        const uint4 raw = x[k];
+        T p[SPW];
+        __builtin_memcpy(p, &raw, sizeof(raw));
+#pragma unroll
+        for (int e = 0; e < SPW; e++) {
+          sum += to_s16<T>(p[e]);
+          if (++ch == C) {  // (uniform over the workgroup: every lane starts at a frame)
+            const uint32_t m = (uint32_t)(uint16_t)(int16_t)div_channels(sum, C);
+#pragma unroll
+            for (int i = 0; i + 1 < NW; i++) w[i] = (w[i] >> 16) | (w[i + 1] << 16);
+            w[NW - 1] = (w[NW - 1] >> 16) | (m << 16);
+            sum = 0;
+            ch = 0;
+          }
+        }
+      }
+    }
+    if ((reinterpret_cast<uintptr_t>(y) & 15) == 0) {
+#pragma unroll
+      for (int k = 0; k < NW / 4; k++)
+        reinterpret_cast<uint4 *>(y)[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NW; i++) {
+        y[2 * i] = (int16_t)(w[i] & 0xFFFF);
+        y[2 * i + 1] = (int16_t)(w[i] >> 16);
+      }
+    }
+  } else {
+    const int nf = frames - f0 < (uint64_t)FPL ? (int)(frames - f0) : FPL;
+    for (int f = 0; f < nf; f++) {
+      int sum = 0;
+      for (int c = 0; c < C; c++)
+        sum += to_s16<T>(planar ? static_cast<const T *>(st->src[c])[f0 + f] : static_cast<const T *>(st->src[0])[(f0 + f) * (uint64_t)C + c]);
+      y[f] = (int16_t)div_channels(sum, C);
+    }
+  }
+}
+
+}  // namespace
+
+// (a span's virtual blocks are of its own sample type's size: the table's block bases are counted on the host)
+__global__ __launch_bounds__(kCvThreads) void feeder_ingest_kernel(const IngestStream *__restrict__ streams, int n, uint64_t blocks) {
+  for (uint64_t b = blockIdx.x; b < blocks; b += gridDim.x) {
+    int lo = 0, hi = n - 1;  // last span whose block_base <= b (zero-frame spans are not in the table)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (streams[mid].block_base <= b) lo = mid;
+      else hi = mid - 1;
+    }
+    const IngestStream *st = streams + lo;
+    const uint64_t block = b - st->block_base;
+    switch (st->type) {
+      case NEEDLE_HIP_SAMPLE_U8: ingest_block<uint8_t>(st, block); break;
+      case NEEDLE_HIP_SAMPLE_S16: ingest_block<int16_t>(st, block); break;
+      case NEEDLE_HIP_SAMPLE_S32: ingest_block<int32_t>(st, block); break;
+      case NEEDLE_HIP_SAMPLE_F32: ingest_block<float>(st, block); break;
+      default: ingest_block<double>(st, block); break;
+    }
+  }
+}
+
 namespace {
 
 using CvKernel = void (*)(const CvStream *, int, uint64_t);
@@ -348,6 +488,156 @@ Status gpu_convert_host(const std::vector<const void *> &pcm, const std::vector<
     for (size_t k = begin; k < end; k++) {
       const Piece &p = pieces[k];
       NEEDLE_HIP_TRY(hipMemcpy(out[p.stream] + p.first * C, d_out.ptr + p.out_off, p.frames * C * sizeof(int16_t), hipMemcpyDeviceToHost));
+    }
+    begin = end;
+  }
+  return Status::Ok();
+}
+
+Status gpu_ingest_device(const std::vector<IngestSpan> &spans, bool sync) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  int dev = 0;
+  NEEDLE_HIP_TRY(hipGetDevice(&dev));
+  std::vector<IngestStream> meta;
+  uint64_t blocks = 0;
+  for (const IngestSpan &sp : spans) {
+    if (sp.channels < 1 || sp.channels > NEEDLE_HIP_MAX_CHANNELS)
+      return Status::Make(NeedleError_InvalidArgument, "ingest: channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
+    if (!sample_format_valid(sp.format)) return Status::Make(NeedleError_InvalidArgument, "ingest: unknown sample format");
+    if (sp.frames == 0) continue;
+    IngestStream st{};
+    st.channels = sp.channels;
+    st.type = sp.format % 5;
+    st.planar = sample_format_planar(sp.format) && sp.channels > 1;
+    uintptr_t align = 0;
+    for (int c = 0; c < (st.planar ? sp.channels : 1); c++) {
+      if (!sp.src[c]) return Status::Make(NeedleError_NullArgument, "ingest: null stream pointer");
+      st.src[c] = sp.src[c];
+      align |= reinterpret_cast<uintptr_t>(sp.src[c]);
+    }
+    if (!sp.dst) return Status::Make(NeedleError_NullArgument, "ingest: null stream pointer");
+    st.vec = (align & 15) == 0;
+    st.dst = sp.dst;
+    st.frames = sp.frames;
+    st.block_base = blocks;
+    meta.push_back(st);
+    const uint64_t block_frames = (uint64_t)kCvThreads * (sample_format_width(sp.format) == 1 ? 16 : 8);
+    blocks += (sp.frames + block_frames - 1) / block_frames;
+  }
+  if (meta.size() > 0x7FFFFFFFull) return Status::Make(NeedleError_InvalidArgument, "ingest: too many spans for one launch");
+  hipStream_t stream = library_stream();
+  if (!meta.empty()) {
+    // descriptor table: per device, pinned staging, in stream order behind the previous launch (as the conversion's)
+    static std::map<int, std::pair<DeviceBuffer<IngestStream> *, PinnedStage *>> ws;
+    auto &w = ws[dev];
+    if (!w.first) {
+      w.first = new DeviceBuffer<IngestStream>();
+      w.second = new PinnedStage();
+    }
+    if (!(s = w.first->reserve(meta.size())).ok()) return s;
+    if (!(s = w.second->acquire(meta.size() * sizeof(IngestStream))).ok()) return s;
+    std::memcpy(w.second->ptr, meta.data(), meta.size() * sizeof(IngestStream));
+    NEEDLE_HIP_TRY(hipMemcpyAsync(w.first->ptr, w.second->ptr, meta.size() * sizeof(IngestStream), hipMemcpyHostToDevice, stream));
+    w.second->mark(stream);
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)std::max(cus, 1) * 8);  // the rest by grid stride
+    KernelTimer timer("ingest");
+    hipLaunchKernelGGL(feeder_ingest_kernel, dim3(grid), dim3(kCvThreads), 0, stream, w.first->ptr, (int)meta.size(), blocks);
+    NEEDLE_HIP_TRY(hipGetLastError());
+  }
+  if (sync) NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  return Status::Ok();
+}
+
+Status gpu_convert_mono_host(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values,
+                             const std::vector<int> &channels, const std::vector<int> &formats, const std::vector<int16_t *> &out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  const size_t n = num_values.size();
+  if (channels.size() != n || formats.size() != n || out.size() != n)
+    return Status::Make(NeedleError_InvalidArgument, "ingest: one length, one format and one output per stream are required");
+  std::vector<size_t> first_plane(n + 1, 0);  // of stream i in pcm
+  for (size_t i = 0; i < n; i++) {
+    if (channels[i] < 1 || channels[i] > NEEDLE_HIP_MAX_CHANNELS)
+      return Status::Make(NeedleError_InvalidArgument, "ingest: channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
+    if (!sample_format_valid(formats[i])) return Status::Make(NeedleError_InvalidArgument, "ingest: unknown sample format");
+    first_plane[i + 1] = first_plane[i] + sample_format_planes(formats[i], channels[i]);
+  }
+  if (pcm.size() != first_plane[n]) return Status::Make(NeedleError_InvalidArgument, "ingest: one pointer per stream and plane is required");
+  // Batches of at most NEEDLE_HIP_MAX_BATCH_VALUES input values (2^30 by default); a stream longer than that is cut into
+  // pieces of whole 16-frame groups (frames are independent of each other).
+  uint64_t max_values = 1ull << 30;
+  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) max_values = (uint64_t)std::max(1ll, atoll(e));  // tests
+  struct Piece {
+    size_t stream;
+    uint64_t first, frames, in_off, out_off;
+  };
+  std::vector<Piece> pieces;
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t C = (uint64_t)channels[i], frames = num_values[i] / C;
+    const uint64_t piece_frames = std::max<uint64_t>(16, max_values / C / 16 * 16);
+    for (uint64_t f = 0; f < frames; f += piece_frames) pieces.push_back(Piece{i, f, std::min(piece_frames, frames - f), 0, 0});
+  }
+  if (pieces.empty()) return Status::Ok();  // no whole frame anywhere: nothing is read or written
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  // A staged plane keeps its pointer's offset from 16-byte alignment (a piece starts a multiple of 16 bytes behind its
+  // plane), so the kernel takes the path the caller's own pointers ask for.
+  auto plane_units = [&](const Piece &p) {
+    const uint64_t C = (uint64_t)channels[p.stream], P = first_plane[p.stream + 1] - first_plane[p.stream];
+    return sample_plane_units(p.frames * (P == 1 ? C : 1), sample_format_width(formats[p.stream])) + 8;
+  };
+  hipStream_t stream = library_stream();
+  DeviceBuffer<int16_t> d_in, d_out;
+  size_t begin = 0;
+  while (begin < pieces.size()) {
+    uint64_t values = 0, in_total = 0, out_total = 0;
+    size_t end = begin;
+    while (end < pieces.size() && (end == begin || values + pieces[end].frames * (uint64_t)channels[pieces[end].stream] <= max_values)) {
+      Piece &p = pieces[end];
+      p.in_off = in_total;
+      p.out_off = out_total;
+      values += p.frames * (uint64_t)channels[p.stream];
+      in_total += plane_units(p) * (first_plane[p.stream + 1] - first_plane[p.stream]);
+      out_total += (p.frames + 7) & ~(uint64_t)7;
+      end++;
+    }
+    if (!(s = d_in.reserve(in_total)).ok() || !(s = d_out.reserve(out_total)).ok()) return s;
+    std::vector<IngestSpan> spans;
+    s = Status::Ok();
+    for (size_t k = begin; k < end && s.ok(); k++) {
+      const Piece &p = pieces[k];
+      const uint64_t C = (uint64_t)channels[p.stream], W = sample_format_width(formats[p.stream]);
+      const size_t P = first_plane[p.stream + 1] - first_plane[p.stream];
+      IngestSpan sp{};
+      for (size_t c = 0; c < P && s.ok(); c++) {
+        const void *plane = pcm[first_plane[p.stream] + c];
+        if (!plane || !out[p.stream]) {
+          s = Status::Make(NeedleError_NullArgument, "ingest: null stream pointer");
+          break;
+        }
+        const uint8_t *from = static_cast<const uint8_t *>(plane) + p.first * (P == 1 ? C : 1) * W;
+        uint8_t *at = reinterpret_cast<uint8_t *>(d_in.ptr + p.in_off + c * plane_units(p)) + (reinterpret_cast<uintptr_t>(from) & 15);
+        const hipError_t e = hipMemcpyAsync(at, from, p.frames * (P == 1 ? C : 1) * W, hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) s = Status::Make(NeedleError_Unknown, std::string("HIP error: ") + hipGetErrorString(e));
+        sp.src[c] = at;
+      }
+      sp.dst = d_out.ptr + p.out_off;
+      sp.frames = p.frames;
+      sp.channels = channels[p.stream];
+      sp.format = formats[p.stream];
+      spans.push_back(sp);
+    }
+    if (s.ok()) s = gpu_ingest_device(spans, false);
+    // also on the error path: copies already enqueued read the caller's buffers asynchronously
+    const bool drained = hipStreamSynchronize(stream) == hipSuccess;
+    if (!s.ok()) return s;
+    if (!drained) return Status::Make(NeedleError_Unknown, "ingest: upload or kernel failed");
+    for (size_t k = begin; k < end; k++) {
+      const Piece &p = pieces[k];
+      NEEDLE_HIP_TRY(hipMemcpy(out[p.stream] + p.first, d_out.ptr + p.out_off, p.frames * sizeof(int16_t), hipMemcpyDeviceToHost));
     }
     begin = end;
   }

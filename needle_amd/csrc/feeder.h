@@ -15,10 +15,16 @@ size_t feeder_num_ready(uint64_t samples, int sample_rate, int channels, uint32_
 class Feeder {
  public:
   static Status Create(size_t lanes, int channels, int sample_rate, int format, uint32_t step, std::unique_ptr<Feeder> *out);
+  // Every lane in a format of its own (needle_hip_feeder_new_lanes): such a feeder down-mixes every lane to mono as it
+  // lands (feeder_ingest_kernel), so its tails are mono whatever the channel count, and ResetFormat may give a lane
+  // another format with its next stream.  Create's feeder keeps one format and refuses ResetFormat.
+  static Status CreateLanes(const NeedleHipLaneFormat *formats, size_t lanes, uint32_t step, std::unique_ptr<Feeder> *out);
+  Status LaneFormat(size_t lane, NeedleHipLaneFormat *format) const;
+  Status ResetFormat(const size_t *lanes, const NeedleHipLaneFormat *formats, size_t k);
   ~Feeder();
   size_t lanes() const;
   uint32_t step() const;
-  // pcm: sample_format_planes() pointers per lane; num_values[i] interleaved values (whole frames) of lane i
+  // pcm: lane after lane, each lane's sample_format_planes() pointers; num_values[i] values (whole frames) of lane i
   Status Feed(const void *const *pcm, const size_t *num_values);
   Status Finish(const size_t *lanes, size_t k);  // nullptr: every unfinished lane
   Status Reset(const size_t *lanes, size_t k);   // nullptr: every lane

@@ -15,7 +15,12 @@
 //              at the same offset modulo 16 bytes as the data it inherits)
 //   land       the new chunks behind the carried tails: copied straight (s16, 1-2 channels), or staged raw and
 //              converted / down-mixed by convert.hip / downmix.hip; resample.hip then computes the whole output tiles
-//              whose taps lie inside the samples fed (nothing is clamped before `finish` tells the stream's end)
+//              whose taps lie inside the samples fed (nothing is clamped before `finish` tells the stream's end).
+//              A feeder whose lanes have formats of their own (CreateLanes) lands every lane as MONO instead: s16 mono
+//              chunks copied straight, all others staged raw and reduced by one feeder_ingest_kernel launch whatever
+//              the mixture (convert.hip); the resampler then runs once per distinct rate among the lanes that
+//              complete tiles.  Stereo loses nothing by it: every reader of a stereo tail starts with the same
+//              integer (L + R) / 2.
 //   fingerprint gpu_fingerprint_feed_device (fingerprint.hip): the first pass over the NEW frame pairs only, behind the
 //              carried rows; certification, recomputation and fix-up over carried + new.  Frame pairs are the
 //              one-shot's (2p, 2p + 1): the tail starts at an even frame and a trailing odd frame waits for its partner
@@ -28,6 +33,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
+#include <map>
 
 #include "hipctx.h"
 
@@ -130,14 +137,22 @@ size_t feeder_num_ready(uint64_t n, int sample_rate, int channels, uint32_t step
 
 struct Feeder::Impl {
   size_t n = 0;
-  int channels = 1, rate = kSampleRate, format = NEEDLE_HIP_SAMPLE_S16;
   uint32_t step = 1;
-  int pcm_channels = 1;  // of the 11025 Hz tail: 3-8 channels arrive there down-mixed, resampled streams as mono
+  bool mixed = false;    // made by CreateLanes: a format per lane, every lane mono behind the landing
+  int pcm_channels = 1;  // of the 11025 Hz tails: 3-8 channels arrive there down-mixed, resampled streams as mono
   int src_channels = 1;  // of what lands: 3-8 channels are down-mixed on the way
-  bool resample = false;
-  ResampleTiling tiling;
-  bool direct = true;    // s16, 1-2 channels: chunks are copied straight behind the tails
-  size_t planes = 1, width = 2;
+  // What a lane's stream is made of.  Create fills every lane alike; pcm_channels and src_channels are the feeder's in
+  // both kinds (1 when mixed), since the chain behind the landing runs once over all lanes.
+  struct Format {
+    int channels = 1, rate = kSampleRate, format = NEEDLE_HIP_SAMPLE_S16;
+    bool resample = false;
+    const ResampleTiling *tiling = nullptr;  // the rate's, in `tilings`
+    bool direct = true;  // chunks are copied straight behind the tails: s16 of 1-2 channels (mixed: s16 mono)
+    size_t planes = 1, width = 2;
+    size_t first_plane = 0;  // the lane's first pointer in feed's array
+  };
+  std::vector<Format> fmt;
+  std::map<int, ResampleTiling> tilings;  // of the distinct rates other than 11025 Hz, as counted when the lanes were made
   std::vector<Lane> lanes;
   BufferSet sets[2];
   int cur = 0;
@@ -182,6 +197,45 @@ struct Feeder::Impl {
     bool finish = false;
   };
 
+  // What a lane of the format (its limits checked by the caller) is made of, whole or not at all: a rate the resampler
+  // has no design for fails here, before anything of the feeder has changed but, perhaps, an entry of `tilings` that no
+  // lane uses (use_formats drops those).  first_plane is set by use_formats.
+  Status make_format(const NeedleHipLaneFormat &lf, Format *out) {
+    Format f;
+    f.channels = lf.channels;
+    f.rate = lf.sample_rate;
+    f.format = lf.format;
+    f.resample = lf.sample_rate != kSampleRate;
+    if (f.resample) {
+      auto it = tilings.find(f.rate);
+      if (it == tilings.end()) {
+        ResampleTiling t;
+        Status s = resample_tiling_host(f.rate, &t);
+        if (!s.ok()) return s;
+        it = tilings.emplace(f.rate, t).first;
+      }
+      f.tiling = &it->second;
+    }
+    f.direct = mixed ? f.format % 5 == NEEDLE_HIP_SAMPLE_S16 && f.channels == 1 : f.format == NEEDLE_HIP_SAMPLE_S16 && f.channels <= 2;
+    f.planes = sample_format_planes(f.format, f.channels);
+    f.width = sample_format_width(f.format);
+    *out = f;
+    return Status::Ok();
+  }
+  // after `fmt` has changed: every lane's place in feed's pointer array, and no tiling of a rate no lane has
+  void use_formats() {
+    size_t at = 0;
+    for (Format &f : fmt) {
+      f.first_plane = at;
+      at += f.planes;
+    }
+    for (auto it = tilings.begin(); it != tilings.end();) {
+      bool used = false;
+      for (const Format &f : fmt) used = used || f.tiling == &it->second;
+      it = used ? std::next(it) : tilings.erase(it);
+    }
+  }
+
   Status round(const std::vector<Chunk> &chunks) {
     if (audit && gpu_fingerprint_f64_mode())
       return Status::Make(NeedleError_InvalidArgument, "feeder: NEEDLE_HIP_STFT=f64 has no first pass to audit");
@@ -191,10 +245,10 @@ struct Feeder::Impl {
     if (!(s = drain()).ok()) return s;
     hipStream_t stream = library_stream();
     if (!landed) NEEDLE_HIP_TRY(hipEventCreateWithFlags(&landed, hipEventDisableTiming));
-    if (resample) {  // the tiles this stream is counted in are the ones gpu_resample_device will plan
+    for (const auto &known : tilings) {  // the tiles a stream is counted in are the ones gpu_resample_device will plan
       ResampleTiling now;
-      if (!(s = resample_tiling_host(rate, &now)).ok()) return s;
-      if (now.tile_outputs != tiling.tile_outputs) return Status::Make(NeedleError_Unknown, "feeder: the resampler's tiling changed under a stream");
+      if (!(s = resample_tiling_host(known.first, &now)).ok()) return s;
+      if (now.tile_outputs != known.second.tile_outputs) return Status::Make(NeedleError_Unknown, "feeder: the resampler's tiling changed under a stream");
     }
     BufferSet &from = sets[cur], &to = sets[cur ^ 1];
     struct Plan {
@@ -207,10 +261,12 @@ struct Feeder::Impl {
     std::vector<FeedLane> feed;
     std::vector<size_t> feed_lane;
     uint64_t cursor = 0, rows = 0, raw_units = 0, new_items = 0, new_values = 0, src_cursor = 0;
-    std::vector<ResampleSpan> rspans;
+    bool any_resample = false;
     for (size_t i = 0; i < n; i++) {
       const Lane &l = lanes[i];
       const Chunk &c = chunks[i];
+      const Format &f = fmt[i];
+      any_resample = any_resample || f.resample;
       if (l.finished) continue;
       Plan &p = plan[i];
       p.carried_values = (l.samples - l.keep_frame * kHop) * (uint64_t)pcm_channels;
@@ -220,8 +276,8 @@ struct Feeder::Impl {
       // the lane's place starts where its inherited data does modulo 16 bytes: the carry moves whole 16-byte words
       p.new_off = ((cursor + 7) & ~(uint64_t)7) + (p.carried_values ? p.src_off % 8 : 0);
       uint64_t samples = l.samples + c.frames;
-      if (resample) {
-        samples = final_outputs(tiling, l.fed + c.frames, c.finish, &p.tiles);
+      if (f.resample) {
+        samples = final_outputs(*f.tiling, l.fed + c.frames, c.finish, &p.tiles);
         p.carried_src = (l.fed - l.keep_p0) * (uint64_t)src_channels;
         p.from_src_off = l.src_off + (l.keep_p0 - l.src_p0) * (uint64_t)src_channels;  // a multiple of 8 values: no skew
         p.new_src_off = (src_cursor + 7) & ~(uint64_t)7;
@@ -237,26 +293,26 @@ struct Feeder::Impl {
       if (p.frames - l.keep_frame > 0x7FFFFFF0ull || rows > 0x7FFFFFF0ull) return Status::Make(NeedleError_InvalidArgument, "feeder: feed too large");
       p.row_base = (uint32_t)rows;
       rows += ((p.frames - l.keep_frame) + 3) & ~(uint64_t)1;
-      if (!direct && c.frames) {
+      if (!f.direct && c.frames) {
         p.raw_off = raw_units;
-        raw_units += planes * sample_plane_units(c.frames * (planes == 1 ? (uint64_t)channels : 1), width);
+        raw_units += f.planes * sample_plane_units(c.frames * (f.planes == 1 ? (uint64_t)f.channels : 1), f.width);
       }
       if (p.frames > l.frames_done) {
-        FeedLane f{};
-        f.pcm_off = p.new_off;
-        f.item_off = new_items;
-        f.row_base = p.row_base;
-        f.carried = p.carried_rows;
-        f.frames = (uint32_t)(p.frames - l.keep_frame);
-        f.first_item = (uint32_t)(l.items_done * step - l.keep_frame);
-        f.kept = (uint32_t)(p.kept - l.items_done);
-        f.lane = (uint32_t)i;
-        new_items += f.kept;
-        feed.push_back(f);
+        FeedLane fl{};
+        fl.pcm_off = p.new_off;
+        fl.item_off = new_items;
+        fl.row_base = p.row_base;
+        fl.carried = p.carried_rows;
+        fl.frames = (uint32_t)(p.frames - l.keep_frame);
+        fl.first_item = (uint32_t)(l.items_done * step - l.keep_frame);
+        fl.kept = (uint32_t)(p.kept - l.items_done);
+        fl.lane = (uint32_t)i;
+        new_items += fl.kept;
+        feed.push_back(fl);
         feed_lane.push_back(i);
       }
     }
-    if (resample && !(s = to.src.reserve(src_cursor + 16)).ok()) return s;
+    if (any_resample && !(s = to.src.reserve(src_cursor + 16)).ok()) return s;
     if (!(s = to.pcm.reserve(cursor + 16)).ok() || !(s = to.chroma.reserve((rows + 2) * kBands)).ok() ||
         !(s = to.energy.reserve((rows + 2) * 4)).ok() || !(s = chroma64.reserve((rows + 2) * kBands)).ok() ||
         !(s = d_items.reserve(std::max<uint64_t>(new_items, 1))).ok() || !(s = raw.reserve(std::max<uint64_t>(raw_units, 1))).ok())
@@ -313,35 +369,53 @@ struct Feeder::Impl {
     } copies{stream};
     std::vector<ConvertSpan> cspans;
     std::vector<DownmixSpan> mspans;
+    std::vector<IngestSpan> ispans;
     for (size_t i = 0; i < n; i++) {
       const Chunk &c = chunks[i];
       const Plan &p = plan[i];
+      const Format &f = fmt[i];
       if (lanes[i].finished || !c.frames) continue;
-      int16_t *dst = resample ? to.src.ptr + p.new_src_off + p.carried_src : to.pcm.ptr + p.new_off + p.carried_values;
-      if (direct) {
-        NEEDLE_HIP_TRY(hipMemcpyAsync(dst, c.plane[0], c.frames * (uint64_t)channels * 2, hipMemcpyHostToDevice, stream));
+      int16_t *dst = f.resample ? to.src.ptr + p.new_src_off + p.carried_src : to.pcm.ptr + p.new_off + p.carried_values;
+      if (f.direct) {
+        NEEDLE_HIP_TRY(hipMemcpyAsync(dst, c.plane[0], c.frames * (uint64_t)f.channels * 2, hipMemcpyHostToDevice, stream));
         continue;
       }
-      const uint64_t plane_samples = c.frames * (planes == 1 ? (uint64_t)channels : 1), plane_units = sample_plane_units(plane_samples, width);
+      const uint64_t plane_samples = c.frames * (f.planes == 1 ? (uint64_t)f.channels : 1), plane_units = sample_plane_units(plane_samples, f.width);
       ConvertSpan sp{};
-      for (size_t k = 0; k < planes; k++) {
+      for (size_t k = 0; k < f.planes; k++) {
         int16_t *at = raw.ptr + p.raw_off + k * plane_units;
-        NEEDLE_HIP_TRY(hipMemcpyAsync(at, c.plane[k], plane_samples * width, hipMemcpyHostToDevice, stream));
+        NEEDLE_HIP_TRY(hipMemcpyAsync(at, c.plane[k], plane_samples * f.width, hipMemcpyHostToDevice, stream));
         sp.src[k] = at;
       }
       sp.dst = dst;
       sp.frames = c.frames;
-      if (format == NEEDLE_HIP_SAMPLE_S16) mspans.push_back(DownmixSpan{raw.ptr + p.raw_off, dst, c.frames});
-      else cspans.push_back(sp);
+      if (mixed) {
+        IngestSpan in{};
+        std::memcpy(in.src, sp.src, sizeof(in.src));
+        in.dst = dst;
+        in.frames = c.frames;
+        in.channels = f.channels;
+        in.format = f.format;
+        ispans.push_back(in);
+      } else if (f.format == NEEDLE_HIP_SAMPLE_S16) {
+        mspans.push_back(DownmixSpan{raw.ptr + p.raw_off, dst, c.frames});
+      } else {
+        cspans.push_back(sp);
+      }
     }
     NEEDLE_HIP_TRY(hipEventRecord(landed, stream));  // the caller's buffers are free once this has executed
-    if (!cspans.empty() && !(s = gpu_convert_device(cspans, channels, format, channels > 2, false)).ok()) return s;
-    if (!mspans.empty() && !(s = gpu_downmix_device(mspans, channels, false)).ok()) return s;
-    if (resample) {  // the whole tiles whose taps lie inside the samples fed, behind the 11025 Hz tails
+    // (cspans and mspans: Create's feeder, every lane in the format of lane 0)
+    if (!cspans.empty() && !(s = gpu_convert_device(cspans, fmt[0].channels, fmt[0].format, fmt[0].channels > 2, false)).ok()) return s;
+    if (!mspans.empty() && !(s = gpu_downmix_device(mspans, fmt[0].channels, false)).ok()) return s;
+    if (!ispans.empty() && !(s = gpu_ingest_device(ispans, false)).ok()) return s;
+    // the whole tiles whose taps lie inside the samples fed, behind the 11025 Hz tails: the resampler's plan and tile
+    // shape belong to a rate, so one launch per distinct rate among the lanes that complete tiles
+    for (const auto &known : tilings) {
+      std::vector<ResampleSpan> rspans;
       for (size_t i = 0; i < n; i++) {
         const Lane &l = lanes[i];
         const Plan &p = plan[i];
-        if (l.finished || p.tiles <= l.tiles_done) continue;
+        if (fmt[i].rate != known.first || l.finished || p.tiles <= l.tiles_done) continue;
         ResampleSpan sp{};
         sp.n_in = l.fed + chunks[i].frames;
         sp.out_off = p.new_off - l.keep_frame * kHop;  // of the stream's output 0 (modulo 2^64, common.h)
@@ -352,7 +426,7 @@ struct Feeder::Impl {
         sp.p1 = sp.n_in;
         rspans.push_back(sp);
       }
-      if (!rspans.empty() && !(s = gpu_resample_device(nullptr, rspans, src_channels, rate, to.pcm.ptr, false)).ok()) return s;
+      if (!rspans.empty() && !(s = gpu_resample_device(nullptr, rspans, src_channels, known.first, to.pcm.ptr, false)).ok()) return s;
     }
 
     if (!feed.empty()) {
@@ -374,7 +448,8 @@ struct Feeder::Impl {
       if (l.finished) continue;
       l.fed += chunks[i].frames;
       l.samples = p.samples;
-      if (resample) {
+      if (fmt[i].resample) {
+        const ResampleTiling &tiling = *fmt[i].tiling;
         l.src_p0 = l.keep_p0;
         l.src_off = p.new_src_off;
         l.tiles_done = p.tiles;
@@ -409,33 +484,85 @@ Feeder::~Feeder() = default;
 size_t Feeder::lanes() const { return impl_->n; }
 uint32_t Feeder::step() const { return impl_->step; }
 
+namespace {
+
+Status check_lane_format(const NeedleHipLaneFormat &f) {
+  if (f.channels < 1 || f.channels > NEEDLE_HIP_MAX_CHANNELS)
+    return Status::Make(NeedleError_InvalidArgument, "feeder: channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
+  if (f.sample_rate < 2000 || f.sample_rate > 768000) return Status::Make(NeedleError_InvalidArgument, "feeder: unsupported sample rate");
+  if (!sample_format_valid(f.format)) return Status::Make(NeedleError_InvalidArgument, "feeder: unknown sample format");
+  return Status::Ok();
+}
+
+}  // namespace
+
 Status Feeder::Create(size_t lanes, int channels, int sample_rate, int format, uint32_t step, std::unique_ptr<Feeder> *out) {
   if (lanes == 0 || lanes > (1u << 20)) return Status::Make(NeedleError_InvalidArgument, "feeder: lanes must be 1 to 1048576");
-  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
-    return Status::Make(NeedleError_InvalidArgument, "feeder: channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
-  if (sample_rate < 2000 || sample_rate > 768000) return Status::Make(NeedleError_InvalidArgument, "feeder: unsupported sample rate");
-  if (!sample_format_valid(format)) return Status::Make(NeedleError_InvalidArgument, "feeder: unknown sample format");
+  const NeedleHipLaneFormat all{channels, sample_rate, format};
+  Status s = check_lane_format(all);
+  if (!s.ok()) return s;
   if (step == 0) return Status::Make(NeedleError_InvalidArgument, "feeder: step must be >= 1");
   std::unique_ptr<Feeder> f(new Feeder());
   Impl &m = *f->impl_;
   m.n = lanes;
-  m.channels = channels;
-  m.rate = sample_rate;
-  m.format = format;
   m.step = step;
   m.src_channels = channels > 2 ? 1 : channels;
-  m.resample = sample_rate != kSampleRate;
-  m.pcm_channels = m.resample ? 1 : m.src_channels;
-  if (m.resample) {
-    Status s = resample_tiling_host(sample_rate, &m.tiling);
-    if (!s.ok()) return s;
-  }
-  m.direct = format == NEEDLE_HIP_SAMPLE_S16 && channels <= 2;
-  m.planes = sample_format_planes(format, channels);
-  m.width = sample_format_width(format);
+  m.pcm_channels = sample_rate != kSampleRate ? 1 : m.src_channels;
+  Impl::Format made;
+  if (!(s = m.make_format(all, &made)).ok()) return s;
+  m.fmt.assign(lanes, made);
+  m.use_formats();
   m.lanes.resize(lanes);
   *out = std::move(f);
   return Status::Ok();
+}
+
+Status Feeder::CreateLanes(const NeedleHipLaneFormat *formats, size_t lanes, uint32_t step, std::unique_ptr<Feeder> *out) {
+  if (!formats || !out) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
+  if (lanes == 0 || lanes > (1u << 20)) return Status::Make(NeedleError_InvalidArgument, "feeder: lanes must be 1 to 1048576");
+  Status s;
+  for (size_t i = 0; i < lanes; i++)
+    if (!(s = check_lane_format(formats[i])).ok()) return s;
+  if (step == 0) return Status::Make(NeedleError_InvalidArgument, "feeder: step must be >= 1");
+  std::unique_ptr<Feeder> f(new Feeder());
+  Impl &m = *f->impl_;
+  m.n = lanes;
+  m.step = step;
+  m.mixed = true;  // src_channels = pcm_channels = 1
+  m.fmt.resize(lanes);
+  for (size_t i = 0; i < lanes; i++)
+    if (!(s = m.make_format(formats[i], &m.fmt[i])).ok()) return s;
+  m.use_formats();
+  m.lanes.resize(lanes);
+  *out = std::move(f);
+  return Status::Ok();
+}
+
+Status Feeder::LaneFormat(size_t lane, NeedleHipLaneFormat *format) const {
+  if (!format) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
+  if (lane >= impl_->n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+  const Impl::Format &f = impl_->fmt[lane];
+  *format = NeedleHipLaneFormat{f.channels, f.rate, f.format};
+  return Status::Ok();
+}
+
+Status Feeder::ResetFormat(const size_t *lanes, const NeedleHipLaneFormat *formats, size_t k) {
+  Impl &m = *impl_;
+  if (!lanes || !formats) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
+  if (!m.mixed) return Status::Make(NeedleError_InvalidArgument, "feeder: one format for all lanes (needle_hip_feeder_new): a lane cannot change it");
+  Status s = Status::Ok();
+  for (size_t j = 0; j < k; j++) {
+    if (lanes[j] >= m.n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+    if (!(s = check_lane_format(formats[j])).ok()) return s;
+  }
+  // every new format whole (a rate without a resampler design fails here) before any lane is reset or changed
+  std::vector<Impl::Format> made(k);
+  for (size_t j = 0; j < k && s.ok(); j++) s = m.make_format(formats[j], &made[j]);
+  if (s.ok()) s = Reset(lanes, k);
+  if (s.ok())
+    for (size_t j = 0; j < k; j++) m.fmt[lanes[j]] = made[j];
+  m.use_formats();
+  return s;
 }
 
 Status Feeder::Feed(const void *const *pcm, const size_t *num_values) {
@@ -444,31 +571,35 @@ Status Feeder::Feed(const void *const *pcm, const size_t *num_values) {
   if (!m.poison.ok()) return m.poison;
   bool any = false;
   for (size_t i = 0; i < m.n; i++) {
-    if (num_values[i] % (size_t)m.channels) return Status::Make(NeedleError_InvalidArgument, "feeder: a chunk must be whole frames");
+    const Impl::Format &f = m.fmt[i];
+    if (num_values[i] % (size_t)f.channels) return Status::Make(NeedleError_InvalidArgument, "feeder: a chunk must be whole frames");
     if (!num_values[i]) continue;
     if (m.lanes[i].finished) return Status::Make(NeedleError_InvalidArgument, "feeder: the lane is finished (reset it first)");
-    for (size_t k = 0; k < m.planes; k++)
-      if (!pcm[i * m.planes + k]) return Status::Make(NeedleError_NullArgument, "feeder: null chunk");
+    for (size_t k = 0; k < f.planes; k++)
+      if (!pcm[f.first_plane + k]) return Status::Make(NeedleError_NullArgument, "feeder: null chunk");
     any = true;
   }
   if (!any) return Status::Ok();
   // a feed beyond the staging bound is cut into rounds (the bound counts values, as in the one-shot entry points)
   uint64_t bound = 1ull << 30;
   if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) bound = (uint64_t)std::max(1ll, atoll(e));
-  bound = std::max<uint64_t>(bound / (uint64_t)m.channels, 1);  // in frames
   std::vector<uint64_t> done(m.n, 0);
   for (;;) {
     std::vector<Impl::Chunk> chunks(m.n);
-    uint64_t left = bound;
-    bool more = false;
+    uint64_t left = bound;  // values
+    bool more = false, took = false;
     for (size_t i = 0; i < m.n; i++) {
-      const uint64_t frames = num_values[i] / (size_t)m.channels, take = std::min(frames - done[i], left);
+      const Impl::Format &f = m.fmt[i];
+      const uint64_t frames = num_values[i] / (size_t)f.channels;
+      // (a round moves at least one frame, however small the bound)
+      const uint64_t fit = std::max<uint64_t>(left / (uint64_t)f.channels, took ? 0 : 1), take = std::min(frames - done[i], fit);
       if (take) {
-        const uint64_t first = done[i] * (m.planes == 1 ? (uint64_t)m.channels : 1) * m.width;  // bytes into every plane
-        for (size_t k = 0; k < m.planes; k++) chunks[i].plane[k] = static_cast<const char *>(pcm[i * m.planes + k]) + first;
+        const uint64_t first = done[i] * (f.planes == 1 ? (uint64_t)f.channels : 1) * f.width;  // bytes into every plane
+        for (size_t k = 0; k < f.planes; k++) chunks[i].plane[k] = static_cast<const char *>(pcm[f.first_plane + k]) + first;
         chunks[i].frames = take;
         done[i] += take;
-        left -= take;
+        left -= std::min(left, take * (uint64_t)f.channels);
+        took = true;
       }
       more = more || done[i] < frames;
     }

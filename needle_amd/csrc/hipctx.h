@@ -133,6 +133,7 @@ struct KernelTimer {
   int hist = -1;  // "sum" mode: this launch's own event pair
 };
 double kernel_ms(const std::string &name);
+size_t kernel_launches(const std::string &name);  // "sum" mode: launches of that name timed since the selection was set
 // A launch that carries its own events (hipExtLaunchKernelGGL: the dispatch packet's completion signal IS the stop
 // event -- no marker packets around the kernel): is `name` being timed, and if so, these are its newest start / stop events
 // (not owned; they must outlive the next two launches of that name).

@@ -291,6 +291,12 @@ void bind_kernel_events(const char *name, hipEvent_t start, hipEvent_t stop) {
   t.recorded[t.cur] = true;
 }
 
+size_t kernel_launches(const std::string &name) {
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = g_timers.find(timer_key(name.c_str()));
+  return it == g_timers.end() || !timing_selection().sum ? 0 : it->second.hist_n;
+}
+
 double kernel_ms(const std::string &name) {
   std::lock_guard<std::mutex> lock(g_mu);
   auto it = g_timers.find(timer_key(name.c_str()));

@@ -102,6 +102,15 @@ pub struct NeedleHipCertAudit {
     pub max_s: f64,
 }
 
+/// A feeder lane's (or a stream's) channel count, sample rate and `NeedleHipSampleFormat`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct NeedleHipLaneFormat {
+    pub channels: i32,
+    pub sample_rate: i32,
+    pub format: i32,
+}
+
 extern "C" {
     // ---- needle.h ------------------------------------------------------------------------------------
     pub fn needle_error_to_str(error: NeedleError) -> *const c_char;
@@ -355,6 +364,21 @@ extern "C" {
         format: c_int,
         step: u32,
         output: *mut *mut NeedleHipFeeder,
+    ) -> NeedleError;
+    pub fn needle_hip_feeder_new_lanes(formats: *const NeedleHipLaneFormat, lanes: usize, step: u32, output: *mut *mut NeedleHipFeeder) -> NeedleError;
+    pub fn needle_hip_feeder_lane_format(feeder: *const NeedleHipFeeder, lane: usize, format: *mut NeedleHipLaneFormat) -> NeedleError;
+    pub fn needle_hip_feeder_reset_format(
+        feeder: *mut NeedleHipFeeder,
+        lanes: *const usize,
+        formats: *const NeedleHipLaneFormat,
+        k: usize,
+    ) -> NeedleError;
+    pub fn needle_hip_convert_mono_host(
+        pcm: *const *const c_void,
+        num_values: *const usize,
+        formats: *const NeedleHipLaneFormat,
+        num_streams: usize,
+        out: *const *mut i16,
     ) -> NeedleError;
     pub fn needle_hip_feeder_free(feeder: *mut NeedleHipFeeder);
     pub fn needle_hip_feeder_feed(feeder: *mut NeedleHipFeeder, pcm: *const *const c_void, num_values: *const usize) -> NeedleError;

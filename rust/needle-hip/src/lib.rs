@@ -464,6 +464,14 @@ pub struct Feeder {
     raw: *mut ffi::NeedleHipFeeder,
     lanes: usize,
     planes: usize,
+    formats: Option<Vec<LaneFormat>>, // `with_formats`: every lane's own, kept up to date by `reset_format`
+}
+
+/// `(channels, sample rate, NeedleHipSampleFormat)` of a feeder lane.
+pub use ffi::NeedleHipLaneFormat as LaneFormat;
+
+fn format_planes(f: &LaneFormat) -> usize {
+    if f.format >= 5 { f.channels.max(1) as usize } else { 1 }
 }
 
 unsafe impl Send for Feeder {}
@@ -474,12 +482,55 @@ impl Feeder {
         let format = if planar { T::PLANAR } else { T::INTERLEAVED };
         let mut raw = ptr::null_mut();
         unsafe { check(ffi::needle_hip_feeder_new(lanes, channels, sample_rate, format as i32, step, &mut raw))? };
-        Ok(Feeder { raw, lanes, planes: if planar { channels.max(1) as usize } else { 1 } })
+        Ok(Feeder { raw, lanes, planes: if planar { channels.max(1) as usize } else { 1 }, formats: None })
+    }
+
+    /// One lane per format (`needle_hip_feeder_new_lanes`): a season whose episodes differ in channel count, rate and
+    /// sample format in one feeder.  Every lane is down-mixed to mono as it lands; the items are the one-shot path's.
+    /// Such a feeder is fed with `feed_lanes`.
+    pub fn with_formats(formats: &[LaneFormat], step: u32) -> Result<Self> {
+        let mut raw = ptr::null_mut();
+        unsafe { check(ffi::needle_hip_feeder_new_lanes(formats.as_ptr(), formats.len(), step, &mut raw))? };
+        Ok(Feeder { raw, lanes: formats.len(), planes: 0, formats: Some(formats.to_vec()) })
+    }
+
+    pub fn lane_format(&self, lane: usize) -> Result<LaneFormat> {
+        let mut f = LaneFormat::default();
+        unsafe { check(ffi::needle_hip_feeder_lane_format(self.raw, lane, &mut f))? };
+        Ok(f)
+    }
+
+    /// `lanes[j]` starts a new stream in `formats[j]`; only on a feeder made by `with_formats`.
+    pub fn reset_format(&mut self, lanes: &[usize], formats: &[LaneFormat]) -> Result<()> {
+        assert_eq!(lanes.len(), formats.len(), "one format per lane");
+        unsafe { check(ffi::needle_hip_feeder_reset_format(self.raw, lanes.as_ptr(), formats.as_ptr(), lanes.len()))? };
+        if let Some(mine) = self.formats.as_mut() {
+            for (&lane, f) in lanes.iter().zip(formats) {
+                mine[lane] = *f;
+            }
+        }
+        Ok(())
+    }
+
+    /// The feed of a `with_formats` feeder, whose lanes differ in sample type: per lane the raw bytes of its planes (1 of
+    /// an interleaved lane, `channels` of a planar one; an empty slice is nothing for that lane), aligned to one sample.
+    pub fn feed_lanes(&mut self, pcm: &[&[&[u8]]]) -> Result<()> {
+        let formats = self.formats.as_ref().expect("feed_lanes is the feed of a with_formats feeder");
+        assert_eq!(pcm.len(), self.lanes, "one entry per lane");
+        let (mut ptrs, mut lens) = (Vec::new(), Vec::with_capacity(self.lanes));
+        for (planes, f) in pcm.iter().zip(formats) {
+            assert_eq!(planes.len(), format_planes(f), "one slice per plane of the lane");
+            let width = [1usize, 2, 4, 4, 8][(f.format % 5) as usize];
+            ptrs.extend(planes.iter().map(|s| s.as_ptr() as *const std::os::raw::c_void));
+            lens.push(planes.iter().map(|p| p.len() / width).sum::<usize>());
+        }
+        unsafe { check(ffi::needle_hip_feeder_feed(self.raw, ptrs.as_ptr(), lens.as_ptr())) }
     }
 
     /// What every lane has decoded since the last feed: one slice per lane (planar: `channels` planes per lane, one after
     /// the other); an empty slice is nothing for that lane.  The slices may be reused on return.
     pub fn feed<T: Sample>(&mut self, pcm: &[&[T]]) -> Result<()> {
+        assert!(self.formats.is_none(), "a with_formats feeder is fed with feed_lanes");
         assert_eq!(pcm.len(), self.lanes * self.planes, "one slice per plane of every lane");
         let ptrs: Vec<*const std::os::raw::c_void> = pcm.iter().map(|s| s.as_ptr() as *const _).collect();
         let lens: Vec<usize> = pcm.chunks(self.planes).map(|s| s.iter().map(|p| p.len()).sum()).collect();
@@ -992,6 +1043,26 @@ pub fn convert<T: Sample>(pcm: &[&[T]], channels: i32, planar: bool) -> Result<V
     let format = if planar { T::PLANAR } else { T::INTERLEAVED };
     unsafe {
         check(ffi::needle_hip_convert_host(ptrs.as_ptr(), lens.as_ptr(), lens.len(), channels, format as i32, optrs.as_ptr()))?;
+    }
+    Ok(out)
+}
+
+/// `needle_hip_convert_mono_host`: streams that each have a format of their own -> mono s16 (`convert`, then `downmix`, in
+/// one kernel whatever the mixture).  Per stream the raw bytes of its planes, as in `Feeder::feed_lanes`; the formats'
+/// sample rates are not looked at.
+pub fn convert_mono(pcm: &[&[&[u8]]], formats: &[LaneFormat]) -> Result<Vec<Vec<i16>>> {
+    assert_eq!(pcm.len(), formats.len(), "one format per stream");
+    let (mut ptrs, mut lens) = (Vec::new(), Vec::with_capacity(pcm.len()));
+    for (planes, f) in pcm.iter().zip(formats) {
+        assert_eq!(planes.len(), format_planes(f), "one slice per plane of the stream");
+        let width = [1usize, 2, 4, 4, 8][(f.format % 5) as usize];
+        ptrs.extend(planes.iter().map(|s| s.as_ptr() as *const std::os::raw::c_void));
+        lens.push(planes.iter().map(|p| p.len() / width).sum::<usize>());
+    }
+    let mut out: Vec<Vec<i16>> = lens.iter().zip(formats).map(|(n, f)| vec![0i16; n / f.channels.max(1) as usize]).collect();
+    let optrs: Vec<*mut i16> = out.iter_mut().map(|o| o.as_mut_ptr()).collect();
+    unsafe {
+        check(ffi::needle_hip_convert_mono_host(ptrs.as_ptr(), lens.as_ptr(), formats.as_ptr(), formats.len(), optrs.as_ptr()))?;
     }
     Ok(out)
 }

@@ -20,10 +20,14 @@
             too: this tree's median must stay within the parent's median + the spread of the parent's five.
   headline: with --parent DIR (built), bench.py --gpus 1 --steps 20 --warmup 5 in both trees, alternating, --repeats
             times each: medians, the difference and each side's spread (max - min).
+  mixed:    28 lanes in four formats through one with_formats feeder against four uniform feeders of seven lanes fed in
+            turn: wall ms per feed, the front end's kernel times and launches (not in the default --only).
+  uniform:  with --parent DIR, the audit section's comparison with the parent alone: the uniform 28-lane leg, five
+            processes per tree (not in the default --only).
 Sections not asked for with --only keep the figures the output file already holds.
 
 Usage: python tools/bench_feeder.py [--repeats K] [--episodes N] [--out FILE] [--parent DIR]
-                                    [--only chunked,per_feed,state,launches,resources,headline,audit]"""
+                                    [--only chunked,per_feed,state,launches,resources,headline,audit,mixed,uniform]"""
 import argparse
 import csv
 import glob
@@ -188,8 +192,9 @@ def bench_launches(feeds):
     return out
 
 
-RESOURCE_FILES = ["feeder.hip", "fingerprint.hip", "fingerprint32.hip"]
-RESOURCE_KERNELS = re.compile(r"feeder_carry_kernel|stft_chroma32_kernel|features_classify|stft_chroma_kernel|fixup_items_kernel|audit_items_kernel")
+RESOURCE_FILES = ["feeder.hip", "fingerprint.hip", "fingerprint32.hip", "convert.hip", "downmix.hip"]
+RESOURCE_KERNELS = re.compile(r"feeder_carry_kernel|stft_chroma32_kernel|features_classify|stft_chroma_kernel|fixup_items_kernel|audit_items_kernel"
+                              r"|feeder_ingest_kernel|convert_kernel|downmix_kernel")
 RESOURCE_KEYS = {"TotalSGPRs": "sgprs", "SGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch",
                  "Occupancy [waves/SIMD]": "occupancy", "LDS Size [bytes/block]": "lds"}
 
@@ -291,6 +296,72 @@ print(statistics.median(times[10:]))
 """
 
 
+def uniform_vs_parent(root, parent):
+    """The 28-lane 48 kHz planar-float stereo leg in this tree and in the parent commit, five processes each, alternating."""
+    def leg(tree):
+        run = subprocess.run([sys.executable, "-c", AUDIT_LEG], cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+                             text=True, timeout=300, check=True)
+        return float(run.stdout.strip().splitlines()[-1])
+    runs = {"parent": [], "this": []}
+    for k in range(5):
+        for name in (("parent", "this") if k % 2 == 0 else ("this", "parent")):
+            runs[name].append(leg(parent if name == "parent" else root))
+    med = {k: statistics.median(v) for k, v in runs.items()}
+    spread = max(runs["parent"]) - min(runs["parent"])
+    return {"unit": "ms per feed, median of 30 after 10, five processes each", "runs": runs, "median": med,
+            "parent_spread": spread, "condition": "this <= parent + parent_spread", "holds": med["this"] <= med["parent"] + spread}
+
+
+MIXED_FORMATS = [(6, 48000, capi.SAMPLE_F32P), (2, 44100, capi.SAMPLE_S16), (2, 48000, capi.SAMPLE_F32P), (1, 11025, capi.SAMPLE_S16)]
+
+
+def bench_mixed():
+    """28 lanes in four formats, 1-s chunks: through one with_formats feeder, and through four uniform feeders of seven
+    lanes fed in turn.  Wall ms per feed of both (the items of the feed on the host), and the event times of the front
+    end's kernels: ingest against convert + downmix."""
+    rng = np.random.default_rng(4)
+
+    def second(ch, rate, fmt):
+        if fmt == capi.SAMPLE_F32P:
+            return [rng.uniform(-0.5, 0.5, rate).astype(np.float32) for _ in range(ch)]
+        return rng.integers(-20000, 20000, rate * ch, dtype=np.int16)
+    groups = [[second(*fmt) for _ in range(7)] for fmt in MIXED_FORMATS]
+    formats = [fmt for fmt in MIXED_FORMATS for _ in range(7)]
+    one = capi.Feeder.with_formats(formats, 2)
+    four = [capi.Feeder(7, ch, rate, fmt, 2) for ch, rate, fmt in MIXED_FORMATS]
+    chunks = [c for g in groups for c in g]
+
+    def feed_one():
+        one.feed(chunks)
+        one.ready(0)
+
+    def feed_four():
+        for f, g in zip(four, groups):
+            f.feed(g)
+        for f in four:
+            f.ready(0)
+    times = {"one_feeder": [], "four_feeders": []}
+    for k in range(40):
+        for name in (("one_feeder", "four_feeders") if k % 2 == 0 else ("four_feeders", "one_feeder")):
+            t0 = time.perf_counter()
+            (feed_one if name == "one_feeder" else feed_four)()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    out = {"shape": "28 lanes, seven each of 5.1 planar-float 48 kHz, stereo s16 44.1 kHz, stereo planar-float 48 kHz, mono s16 11025 Hz; 1-s chunks, step 2",
+           "ms_per_feed": {k: statistics.median(v[10:]) for k, v in times.items()}}
+    kernels = ["ingest", "convert", "downmix", "resample", "feeder_carry", "stft_chroma32"]
+    for name, fn in (("one_feeder", feed_one), ("four_feeders", feed_four)):
+        capi.set_kernel_timing(",".join(kernels) + ",sum")
+        for _ in range(30):
+            fn()
+        out.setdefault("kernel_ms_per_feed", {})[name] = {k: round(capi.last_kernel_ms(k) / 30, 5) for k in kernels if capi.last_kernel_ms(k) >= 0}
+        out.setdefault("launches_per_feed", {})[name] = {k: capi.kernel_launches(k) / 30 for k in kernels if capi.kernel_launches(k)}
+        capi.set_kernel_timing(None)
+    for k in range(28):
+        assert np.array_equal(one.items(k), four[k // 7].items(k % 7)), k
+    out["state_bytes_per_lane"] = {"one_feeder": one.state_bytes()[0], "four_feeders": [f.state_bytes()[0] for f in four]}
+    return out
+
+
 def bench_audit(root, parent):
     chunks = audit_lanes()
     feeders = {}
@@ -316,19 +387,7 @@ def bench_audit(root, parent):
     out["state_bytes_per_lane"] = {"audit_off": feeders[False].state_bytes()[0], "audit_on": feeders[True].state_bytes()[0]}
     del feeders
     if parent:
-        def leg(tree):
-            run = subprocess.run([sys.executable, "-c", AUDIT_LEG], cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
-                                 text=True, timeout=300, check=True)
-            return float(run.stdout.strip().splitlines()[-1])
-        runs = {"parent": [], "this": []}
-        for k in range(5):
-            for name in (("parent", "this") if k % 2 == 0 else ("this", "parent")):
-                runs[name].append(leg(parent if name == "parent" else root))
-        med = {k: statistics.median(v) for k, v in runs.items()}
-        spread = max(runs["parent"]) - min(runs["parent"])
-        out["audit_off_vs_parent"] = {"unit": "ms per feed, median of 30 after 10, five processes each", "runs": runs, "median": med,
-                                      "parent_spread": spread, "condition": "this <= parent + parent_spread",
-                                      "holds": med["this"] <= med["parent"] + spread}
+        out["audit_off_vs_parent"] = uniform_vs_parent(root, parent)
     return out
 
 
@@ -346,7 +405,8 @@ def main():
     if args.trace_child:
         return trace_child(args.trace_child, args.trace_feeds)
     only = set(args.only.split(","))
-    keys = ("device", "chunked", "per_feed", "state_bytes_per_lane", "kernel_launches_per_feed", "resources", "headline_vs_parent", "audit")
+    keys = ("device", "chunked", "per_feed", "state_bytes_per_lane", "kernel_launches_per_feed", "resources", "headline_vs_parent", "audit",
+            "mixed", "uniform_vs_parent")
     res = {k: NOT_MEASURED for k in keys}
     if os.path.exists(args.out):                         # sections not run now keep their figures
         try:
@@ -376,6 +436,12 @@ def main():
             save()
         if "audit" in only:
             res["audit"] = bench_audit(root, args.parent)
+            save()
+        if "mixed" in only:
+            res["mixed"] = bench_mixed()
+            save()
+        if "uniform" in only and args.parent:
+            res["uniform_vs_parent"] = uniform_vs_parent(root, args.parent)
             save()
         if "headline" in only and args.parent:
             res["headline_vs_parent"] = bench_headline(root, args.parent, max(args.repeats, 3))
