@@ -166,6 +166,50 @@ enum NeedleError needle_hip_fingerprint_debug(const int16_t *pcm, size_t num_val
 size_t needle_hip_resample_out_len(size_t samples_per_channel, int sample_rate);
 enum NeedleError needle_hip_resample_host(const int16_t *const *pcm, const size_t *num_values, size_t num_streams,
                                           int channels, int sample_rate, int16_t *const *out);
+/* Which kernel resamples PCM at `sample_rate`, and its geometry: what the launch itself reads, so a test can say which
+ * kernel it covers.  Host arithmetic only -- no device is touched and no coefficient is designed.  The tuning switches of
+ * the environment (NEEDLE_HIP_RESAMPLE_V1, _QUAD, _SPLITS) are honoured as the launch honours them.  A rate these kernels
+ * cannot take (its ratio to 11025 Hz in lowest terms is too large: resample to a rate that shares a larger factor with
+ * 11025 first) gives NeedleError_InvalidArgument with family REFUSED and L, M, T filled; a rate outside 2000..768000
+ * gives NeedleError_InvalidArgument and leaves *out zeroed.  Fields that do not apply to the family are 0. */
+enum NeedleHipResampleFamily {
+  NEEDLE_HIP_RESAMPLE_IDENTITY = 0, /* 11025 Hz: the general kernel with a single unit tap */
+  NEEDLE_HIP_RESAMPLE_DEC = 1,      /* integer decimation by 2 or 4, scalar coefficients */
+  NEEDLE_HIP_RESAMPLE_MFMA = 2,     /* matrix-core kernel */
+  NEEDLE_HIP_RESAMPLE_QUAD = 3,     /* four outputs per lane, DPP operands */
+  NEEDLE_HIP_RESAMPLE_GENERAL = 4,  /* one output per lane */
+  NEEDLE_HIP_RESAMPLE_REFUSED = 5
+};
+typedef struct NeedleHipResamplePlan {
+  int family;          /* enum NeedleHipResampleFamily */
+  int L, M, T;         /* 11025 / rate = L / M in lowest terms, T taps per output */
+  int tile_outputs;    /* consecutive outputs of a stream per tile */
+  int blocks_per_tile; /* workgroups a tile is cut into */
+  int threads;         /* per workgroup */
+  int lds_bytes;       /* dynamic LDS of the launch (dec: its static LDS is not counted) */
+  /* general kernel (and identity) */
+  int n;               /* lanes per phase */
+  int row_mode;        /* 1: the region is n rows, 0: contiguous */
+  int rows_in_lds;     /* 1: coefficient rows through a per-wave LDS scratch, 0: straight from global memory */
+  int vec4;            /* general and quad: M % 4 == 0, staging by aligned groups of four */
+  int groups;          /* G: 16-byte groups per shifted coefficient row */
+  int pitch;           /* general (row mode) and quad: 16-byte slots per row of samples */
+  int region_slots;    /* general: 16-byte slots of samples */
+  int delta;           /* samples the region starts before a tile's first tap, so that it starts at a multiple of 4 */
+  /* matrix-core kernel */
+  int mfma_steps;      /* 12, 20, 36 or 52: the kernel's STEPS */
+  int nblocks;         /* blocks of sixteen outputs per row */
+  int mf_splits, mf_waves, mf_groups;
+  int mf_long_row;     /* 1: a row is longer than the groups its staging threads move (dup_lo, dup_hi in use) */
+  int mf_dup_lo, mf_dup_hi;
+  /* quad kernel */
+  int quad_splits, quads_per_split, quad_threads;
+  int quad_rounds;     /* rounds of quads a workgroup makes */
+  int quad_small;      /* 1: the instantiations for at most 640 threads */
+  int quad_steps;      /* 16-byte groups of a row a quad multiplies */
+  int dec_q;           /* dec: outputs per lane */
+} NeedleHipResamplePlan;
+enum NeedleError needle_hip_resample_plan(int sample_rate, NeedleHipResamplePlan *out);
 /* The down-mix on its own (`channels` = 1..NEEDLE_HIP_MAX_CHANNELS): out[i][n] = (sum of the `channels` values of frame n
  * of pcm[i]) / channels, C integer division (truncation toward zero); out[i] must hold num_values[i] / channels values
  * (a trailing partial frame is dropped).  Every analyze path applies it on the device to 3-8 channel input before the
@@ -356,7 +400,8 @@ enum NeedleError needle_hip_library_include_endings(NeedleHipLibrary *library, f
  * default 11025).  Call after library_new and before set_pcm (InvalidArgument afterwards, the library unchanged).  The
  * search windows are cut at that rate, as needle_hip_analyzer_run_pcm does, and resampled to 11025 Hz mono on the device
  * on the way in: the resident PCM, and so every job's cost, is that of a mono 11025 Hz library.  The hashes equal
- * needle_hip_analyzer_run_pcm's at that rate.  At 11025 nothing is resampled. */
+ * needle_hip_analyzer_run_pcm's at that rate.  At 11025 nothing is resampled.  A rate the resampler refuses (see
+ * needle_hip_resample_plan) is NeedleError_InvalidArgument here, the library unchanged. */
 enum NeedleError needle_hip_library_set_sample_rate(NeedleHipLibrary *library, int sample_rate);
 /* The sample format (enum NeedleHipSampleFormat, default NEEDLE_HIP_SAMPLE_S16) of the PCM that set_pcm, set_pcm_device
  * and stream_pcm will be given.  Call after library_new and before set_pcm (InvalidArgument afterwards, the library

@@ -77,7 +77,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_host_free", "needle_hip_last_kernel_ms", "needle_hip_set_kernel_timing", "needle_hip_kernel_launches", "needle_hip_fingerprint_sample_rate",
     "needle_hip_fingerprint_delay_ms", "needle_hip_fingerprint_item_duration_ms", "needle_hip_fingerprint_num_items",
     "needle_hip_fingerprint_num_kept", "needle_hip_fingerprint_host", "needle_hip_fingerprint_device",
-    "needle_hip_fingerprint_debug", "needle_hip_resample_out_len", "needle_hip_resample_host", "needle_hip_downmix_host",
+    "needle_hip_fingerprint_debug", "needle_hip_resample_out_len", "needle_hip_resample_host", "needle_hip_resample_plan",
+    "needle_hip_downmix_host",
     "needle_hip_hamming_runs_device", "needle_hip_hamming_runs_host",
     "needle_hip_frame_hashes_new", "needle_hip_frame_hashes_free", "needle_hip_frame_hashes_len",
     "needle_hip_frame_hashes_copy", "needle_hip_frame_hashes_hash_duration_ns", "needle_hip_frame_hashes_md5",
@@ -160,6 +161,21 @@ class CLaneFormat(C.Structure):                          # NeedleHipLaneFormat
     _fields_ = [("channels", C.c_int32), ("sample_rate", C.c_int32), ("format", C.c_int32)]
 
 
+RESAMPLE_FAMILIES = ["identity", "dec", "mfma", "quad", "general", "refused"]   # enum NeedleHipResampleFamily
+RESAMPLE_PLAN_FIELDS = [
+    "family", "L", "M", "T", "tile_outputs", "blocks_per_tile", "threads", "lds_bytes", "n", "row_mode", "rows_in_lds",
+    "vec4", "groups", "pitch", "region_slots", "delta", "mfma_steps", "nblocks", "mf_splits", "mf_waves", "mf_groups",
+    "mf_long_row", "mf_dup_lo", "mf_dup_hi", "quad_splits", "quads_per_split", "quad_threads", "quad_rounds",
+    "quad_small", "quad_steps", "dec_q"]
+
+
+class CResamplePlan(C.Structure):                        # NeedleHipResamplePlan: plain ints
+    _fields_ = [(f, C.c_int) for f in RESAMPLE_PLAN_FIELDS]
+
+
+RESAMPLE_PLAN_DTYPE = np.dtype([(f, "<i4") for f in RESAMPLE_PLAN_FIELDS])
+
+
 def _lane_formats(formats):
     """NeedleHipLaneFormat array of (channels, sample_rate, sample_format) triples."""
     return (CLaneFormat * max(len(formats), 1))(*[CLaneFormat(int(c), int(r), int(f)) for c, r, f in formats])
@@ -238,6 +254,7 @@ def lib():
     L.needle_hip_fingerprint_debug.argtypes = [vp, sz, C.c_int, vp, vp]
     L.needle_hip_resample_out_len.argtypes = [sz, C.c_int]
     L.needle_hip_resample_out_len.restype = sz
+    L.needle_hip_resample_plan.argtypes = [C.c_int, C.POINTER(CResamplePlan)]
     L.needle_hip_resample_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, C.c_int, C.c_int, C.POINTER(vp)]
     L.needle_hip_downmix_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, C.c_int, C.POINTER(vp)]
     L.needle_hip_convert_host.argtypes = [C.POINTER(vp), C.POINTER(sz), sz, C.c_int, C.c_int, C.POINTER(vp)]
@@ -1192,6 +1209,27 @@ def resample(pcms: Sequence[np.ndarray], channels: int, sample_rate: int) -> Lis
     optrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
     check(lib().needle_hip_resample_host(ptrs, lens, n, channels, sample_rate, optrs))
     return [o[:k] for o, k in zip(outs, lens_out)]
+
+
+def resample_plan(sample_rate: int, refused_ok: bool = False) -> dict:
+    """needle_hip_resample_plan: which kernel resamples `sample_rate` and its geometry (host arithmetic, no device);
+    `family` as its name.  A refused rate raises NeedleError_InvalidArgument unless `refused_ok`."""
+    p = CResamplePlan()
+    code = lib().needle_hip_resample_plan(int(sample_rate), C.byref(p))
+    if code != 0 and not (refused_ok and p.family == RESAMPLE_FAMILIES.index("refused")):
+        check(code)
+    out = {f: int(getattr(p, f)) for f in RESAMPLE_PLAN_FIELDS}
+    out["family"] = RESAMPLE_FAMILIES[out["family"]]
+    return out
+
+
+def resample_plans(lo: int, hi: int) -> np.ndarray:
+    """The plans of the rates lo..hi inclusive, as a RESAMPLE_PLAN_DTYPE array (family as its number)."""
+    arr = (CResamplePlan * (hi - lo + 1))()
+    f = lib().needle_hip_resample_plan
+    for i in range(hi - lo + 1):
+        f(lo + i, C.byref(arr[i]))
+    return np.frombuffer(arr, dtype=RESAMPLE_PLAN_DTYPE).copy()
 
 
 def downmix(pcms: Sequence[np.ndarray], channels: int) -> List[np.ndarray]:

@@ -583,6 +583,15 @@ size_t needle_hip_resample_out_len(size_t samples_per_channel, int sample_rate) 
   return sample_rate > 0 ? resample_out_len(samples_per_channel, sample_rate) : 0;
 }
 
+enum NeedleError needle_hip_resample_plan(int sample_rate, NeedleHipResamplePlan *out) {
+  if (!out) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = resample_plan_host(sample_rate, out);
+    if (!s.ok()) set_last_error(s.message);  // (not printed: a refusal is this query's answer, and a sweep asks 766 001 times)
+    return s.code;
+  });
+}
+
 enum NeedleError needle_hip_resample_host(const int16_t *const *pcm, const size_t *num_values, size_t num_streams,
                                           int channels, int sample_rate, int16_t *const *out) {
   if (!pcm || !num_values || !out) return NeedleError_NullArgument;

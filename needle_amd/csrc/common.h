@@ -243,6 +243,8 @@ struct ResampleTiling {
 Status resample_tiling(int rate, int channels, ResampleTiling *out);
 // the same without a device (the kernel's choice and its tiles are host arithmetic on the rate)
 Status resample_tiling_host(int rate, ResampleTiling *out);
+// the whole plan of `rate` as the launch reads it, for needle_hip_resample_plan; no device, no coefficients
+Status resample_plan_host(int rate, NeedleHipResamplePlan *out);
 // the input samples [*p0, *p1) of a stream of n_in samples that tiles [t0, t1) read, p0 rounded down to a multiple of 8
 void resample_piece(const ResampleTiling &t, uint64_t n_in, uint64_t t0, uint64_t t1, uint64_t *p0, uint64_t *p1);
 Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> &spans, int channels, int rate,

@@ -279,6 +279,11 @@ enum NeedleError needle_hip_library_set_sample_rate(NeedleHipLibrary *lib, int s
   if (!lib) return NeedleError_NullArgument;
   if (sample_rate < 2000 || sample_rate > 768000) return NeedleError_InvalidArgument;  // Analyzer::run_pcm's range
   if (lib->have_pcm) return NeedleError_InvalidArgument;  // must precede set_pcm
+  ResampleTiling tiling;  // a rate the resampler has no kernel for is refused here, not at the first set_pcm
+  if (sample_rate != kSampleRate) {
+    Status s = resample_tiling_host(sample_rate, &tiling);
+    if (!s.ok()) return report(s);
+  }
   lib->rate = sample_rate;
   return NeedleError_Ok;
 }

@@ -22,10 +22,15 @@
 //    16 bytes to every lane whatever the addresses (16 cycles of the CU's L1 path per 4 taps), a broadcast LDS
 //    read costs 4.
 //
-// Four kernels, chosen by rate (gpu_resample_device): integer decimation with scalar coefficients (44.1 / 22.05 kHz),
-// the matrix-core kernel of resample_mfma.h (decimation steps M >= 64 with M % 4 == 0 and rows that fit: 48, 32, 24,
-// 16, 8 kHz), the DPP-operand kernel with four outputs per lane (the other row-layout rates: 96 kHz, and the above
-// with NEEDLE_HIP_RESAMPLE_QUAD=1), and the general kernel described above.  All four are the same arithmetic.
+// Four kernels, chosen by rate (plan_kernel; needle_hip_resample_plan tells which, and tests/test_resample_plan_cpu.py
+// counts the rates of each): integer decimation with scalar coefficients (44.1 and 22.05 kHz only); the matrix-core kernel
+// of resample_mfma.h (decimation steps M >= 64 with M % 4 == 0, L >= 16 and windows of at most 208 samples per block of
+// sixteen outputs: 48, 32, 24, 16, 8 kHz, and 11024 Hz with its 690 blocks); the DPP-operand kernel with four outputs per
+// lane (the other rates with M >= 64 whose rows fit: 96, 192, 64 kHz, 12345 Hz, and the above with
+// NEEDLE_HIP_RESAMPLE_QUAD=1); and the general kernel described above for the rest: M < 64 (7350, 8820, 33075 Hz, and
+// 88.2, 176.4, 352.8, 705.6 kHz, whose L is 1), and the rates above about 290 kHz whose rows are too long for the quad
+// kernel (384 kHz), where it reads its coefficients straight from global memory.  All four are the same arithmetic.
+// Three rates in four are refused: their L x M does not fit (every rate coprime to 11025 above 29896 Hz).
 #include "hipctx.h"
 
 #include <algorithm>
@@ -80,20 +85,31 @@ int gcd_i(int a, int b) {
   return a;
 }
 
-void design_filter(int rate, Design *d) {
+// L, M and T of a rate: the ratio in lowest terms and the length of the filter.  Cheap: no coefficient is evaluated, so a
+// rate's plan, and its refusal, cost nothing.
+void design_ratio(int rate, Design *d) {
   if (rate == kTarget) {  // nothing to resample: identity (a single unit tap), only the down-mix applies
     d->L = d->M = 1;
     d->T = 2;
-    d->coef = {1.0f, 0.0f};
     return;
   }
   const int g = gcd_i(kTarget, rate);
   d->L = kTarget / g;
   d->M = rate / g;
   const double ratio = (double)d->L / (double)d->M;
-  const double scale = kRolloff * (ratio < 1.0 ? ratio : 1.0);
   const int half = (int)std::ceil(kZeroCrossings / (ratio < 1.0 ? ratio : 1.0));
   d->T = 2 * half;
+}
+
+// the L x T coefficients of a design whose L, M and T design_ratio has set (oracle/ora_resample.c)
+void design_coefficients(Design *d) {
+  if (d->L == 1 && d->M == 1) {
+    d->coef = {1.0f, 0.0f};
+    return;
+  }
+  const double ratio = (double)d->L / (double)d->M;
+  const double scale = kRolloff * (ratio < 1.0 ? ratio : 1.0);
+  const int half = d->T / 2;
   d->coef.assign((size_t)d->L * d->T, 0.f);
   const double pi = 3.14159265358979323846;
   const double i0b = bessel_i0(kKaiserBeta);
@@ -685,11 +701,11 @@ size_t resample_out_len(size_t n_in, int rate) {
 
 namespace {
 
-// The filter of `rate` and everything about its kernels that is host arithmetic: what get_design uploads tables for, and
-// what plan_kernel reads -- so that the tiling of a rate can be had without a device (resample_tiling_host).  false: the
-// rate ratio is too large for these kernels.
+// The geometry of `rate`'s filter and everything about its kernels that is host arithmetic: what get_design uploads
+// tables for, and what plan_kernel reads -- so that the plan of a rate can be had without a device and without its
+// coefficients (resample_tiling_host, resample_plan_host).  false: the rate ratio is too large for these kernels.
 bool design_geometry(int rate, Design *d) {
-  design_filter(rate, d);
+  design_ratio(rate, d);
   d->G = (((d->T + 3) / 4 + 1) + 3) & ~3;  // 16-byte groups per shifted row, a multiple of 4 for the kernel's unroll
   // lanes per phase: 16 (one LDS lane group) when a tile then has plenty of outputs (L >= 256), more for small L;
   // fewer when M is so large that 16 inputs M apart do not fit the LDS region
@@ -731,6 +747,107 @@ bool design_geometry(int rate, Design *d) {
   return true;
 }
 
+constexpr int kDecThreads = 256;
+
+// which kernel gpu_resample_device launches for a design, and everything its launch reads
+struct KernelPlan {
+  int quad_splits = 1, quads_per_split = 1, quad_pitch = 0, quad_threads = 0;
+  size_t quad_lds = 0;
+  bool quad_vec4 = false, quad_small = false;  // which instantiation of resample_quad_kernel
+  bool quad = false, dec = false, mfma = false;
+  int dec_q = 0;
+  int mf_splits = 1, mf_waves = 1, mf_groups = 0, mf_buffer_floats = 0;
+  size_t mf_lds = 0;
+  int mf_dup_lo = 0, mf_dup_hi = 0;  // mfma_rs::Geom: both 0 when every row fits kCovered groups
+  // resample_kernel (what runs when none of the three above does)
+  int n_log2 = 0, pitch = 0, region_slots = 0, delta = 0, rows_per_wave = 1;
+  bool row_mode = false, rows_in_lds = false, vec4 = false;
+  size_t lds_bytes = 0;
+  bool refused = false;  // resample_kernel would run and its LDS does not fit: the rate ratio is too large
+  uint64_t tile_outputs = 1;  // consecutive outputs of a stream per tile
+  uint64_t blocks_per_tile() const { return dec ? 1 : mfma ? (uint64_t)mf_splits : quad ? (uint64_t)quad_splits : 1; }
+};
+
+KernelPlan plan_kernel(const Design *d) {
+  // Decimation steps of 64 samples or more use the row layout; there the kernel with four consecutive outputs per
+  // lane applies (NEEDLE_HIP_RESAMPLE_V1 forces the first kernel: tests and A/B timing).
+  // a tile's rows are cut into `quad_splits` workgroups (see the kernel); the rows of a workgroup: the groups between
+  // the first reads of its first and last quad, the window, two groups of slack
+  // (measured at 48 kHz, 37 quads: 1 / 2 / 3 / 4 / 6 workgroups per tile 0.77 / 0.72 / 0.64 / 0.72 / 0.81 ms: about
+  // 16 quads = 256 threads per workgroup)
+  const int quads_all = (d->L + 3) / 4;
+  int quad_splits = (quads_all + 15) / 16;
+  if (const char *e = getenv("NEEDLE_HIP_RESAMPLE_SPLITS")) quad_splits = std::max(1, atoi(e));  // tuning
+  quad_splits = std::min(quad_splits, quads_all);
+  const int quads_per_split = (quads_all + quad_splits - 1) / quad_splits;
+  const int row_groups = ((quads_per_split - 1) * 4 * d->M + d->L - 1) / d->L / 4 + 2 + d->steps + 2;
+  const int quad_pitch = row_groups | 1;
+  const size_t quad_lds = (size_t)kQuadRows * quad_pitch * 16;  // (the output tile reuses the start of the region)
+  const int quad_threads = std::min(1024, ((16 * quads_per_split + 63) / 64) * 64);
+  const bool quad = d->M >= kRowModeMinM && d->L >= 4 && quad_lds <= 160 * 1024 &&
+                    (size_t)kQuadRows * 4 * quads_per_split * 2 <= quad_lds &&
+                    quads_per_split <= kQuadMaxRounds * (quad_threads / 16) && getenv("NEEDLE_HIP_RESAMPLE_V1") == nullptr;
+  // integer decimation by 4 or 2 (44.1 / 22.05 kHz): the kernel with scalar coefficients
+  const int dec_q = d->L == 1 && d->T == 32 * d->M ? (d->M == 4 ? 5 : d->M == 2 ? 6 : 0) : 0;
+  const bool dec = dec_q != 0 && getenv("NEEDLE_HIP_RESAMPLE_V1") == nullptr;
+  // matrix-core kernel (resample_mfma.h): one wave per block of sixteen outputs of a row, at most `mf_waves` per
+  // workgroup; a tile's blocks are cut into `mf_splits` workgroups.  NEEDLE_HIP_RESAMPLE_QUAD forces the DPP kernel.
+  const int mf_max_waves = mfma_rs::kConsumers;
+  const int mf_splits = d->mfma_steps ? (d->nblocks + mf_max_waves - 1) / mf_max_waves : 1;
+  const int mf_waves = d->mfma_steps ? (d->nblocks + mf_splits - 1) / mf_splits : 1;
+  int mf_groups = 0;
+  for (int sp = 0; d->mfma_steps && sp < mf_splits; sp++) {
+    const int b0 = sp * mf_waves, b1 = std::min(b0 + mf_waves, d->nblocks);
+    if (b0 >= b1) { mf_groups = 1 << 30; break; }  // an empty split: not this kernel
+    const int start = d->block_k0[b0] & ~3;
+    mf_groups = std::max(mf_groups, (d->block_k0[b1 - 1] + 4 * d->mfma_steps - start + 3) >> 2);
+  }
+  // a row of the LDS image: the groups the staging threads of the row move, or all the groups its blocks read if more
+  const int mf_row_groups = std::max(mfma_rs::kCovered, mf_groups);
+  const int mf_buffer_floats = mf_row_groups * 4 * mfma_rs::kRows;
+  const size_t mf_lds = (size_t)2 * mf_buffer_floats * sizeof(float);  // double-buffered
+  const bool mfma = quad && d->mfma_steps != 0 && (mf_groups <= mfma_rs::kCovered ||  // longer rows: the rest is the start of the next row (one split only)
+                     (mf_splits == 1 && mf_groups - d->M / 4 <= mfma_rs::kCovered && mfma_rs::kCovered >= d->M / 4 &&
+                      mf_groups - mfma_rs::kCovered <= 64 * mfma_rs::kProducers)) &&
+                    mf_lds <= 160 * 1024 && getenv("NEEDLE_HIP_RESAMPLE_QUAD") == nullptr;
+  // the general kernel: lanes per phase, layout of the region, where the coefficient rows come from
+  int n_log2 = 0;
+  while ((1 << n_log2) < d->n) n_log2++;
+  const bool row_mode = d->M >= kRowModeMinM && d->n <= kRowModeMaxN;
+  int pitch = 0, region_slots;
+  if (row_mode) {  // n rows of M + 4G + 4 samples, pitch odd in slots
+    pitch = ((d->M + 4 * d->G + 4 + 3) / 4) | 1;
+    region_slots = d->n * pitch;
+  } else {         // the n M + T - 1 inputs a tile reads, plus the taps the shifted rows add at either end
+    region_slots = (d->n * d->M + 4 * d->G + 4 + 3) / 4;
+  }
+  const int rows_per_wave = d->n >= 64 ? 1 : 64 / d->n;
+  // (very long filters, from rates far above 100 kHz: the per-wave row scratch would not fit; coefficients then
+  // come straight from global memory)
+  const bool rows_in_lds = (row_mode || d->M % 4 == 0) && (size_t)(kThreads / 64) * rows_per_wave * d->G * 16 <= 48 * 1024;
+  // M % 4 == 0: a tile's first tap is a fixed number of samples past a multiple of 4; the region starts at that
+  // multiple, so rows can be staged by aligned groups of four samples
+  const bool vec4 = d->M % 4 == 0;
+  const size_t lds_bytes = (size_t)region_slots * 16 + (((size_t)d->n * d->L * 2 + 15) & ~(size_t)15) +
+                           (rows_in_lds ? (size_t)(kThreads / 64) * rows_per_wave * d->G * 16 : 0);
+  const uint64_t tile_outputs = dec ? (uint64_t)kDecThreads * dec_q : quad ? (uint64_t)kQuadRows * d->L : (uint64_t)d->n * d->L;
+  KernelPlan k;
+  k.quad_splits = quad_splits; k.quads_per_split = quads_per_split; k.quad_pitch = quad_pitch; k.quad_threads = quad_threads;
+  k.quad_lds = quad_lds; k.quad = quad; k.dec = dec; k.mfma = mfma; k.dec_q = dec_q;
+  k.mf_splits = mf_splits; k.mf_waves = mf_waves; k.mf_groups = mf_groups; k.mf_buffer_floats = mf_buffer_floats;
+  k.mf_lds = mf_lds; k.tile_outputs = tile_outputs;
+  k.quad_vec4 = d->M % 4 == 0; k.quad_small = quad_threads <= 640;
+  if (mf_groups > mfma_rs::kCovered) {
+    k.mf_dup_lo = mfma_rs::kCovered - d->M / 4;
+    k.mf_dup_hi = mf_groups - d->M / 4;
+  }
+  k.n_log2 = n_log2; k.pitch = pitch; k.region_slots = region_slots; k.rows_per_wave = rows_per_wave;
+  k.delta = vec4 ? ((1 - d->T / 2) % 4 + 4) % 4 : 0;
+  k.row_mode = row_mode; k.rows_in_lds = rows_in_lds; k.vec4 = vec4; k.lds_bytes = lds_bytes;
+  k.refused = !dec && !quad && lds_bytes > 160 * 1024;
+  return k;
+}
+
 // the filter of `rate` on device `dev` and its tables, built on first use
 Status get_design(int dev, int rate, Design **out) {
   Design *d;
@@ -738,7 +855,11 @@ Status get_design(int dev, int rate, Design **out) {
     std::lock_guard<std::mutex> lock(g_mu);
     d = &g_designs[{dev, rate}];
     if (d->T == 0) {
-      if (!design_geometry(rate, d)) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
+      if (!design_geometry(rate, d) || plan_kernel(d).refused) {  // before any coefficient is evaluated
+        g_designs.erase({dev, rate});
+        return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
+      }
+      design_coefficients(d);
       std::vector<float> shifted((size_t)4 * d->L * 4 * d->G, 0.f);
       for (int a = 0; a < 4; a++)
         for (int p = 0; p < d->L; p++)
@@ -804,71 +925,6 @@ Status get_design(int dev, int rate, Design **out) {
   return Status::Ok();
 }
 
-constexpr int kDecThreads = 256;
-
-// which kernel gpu_resample_device launches for a design, and its geometry
-struct KernelPlan {
-  int quad_splits = 1, quads_per_split = 1, quad_pitch = 0, quad_threads = 0;
-  size_t quad_lds = 0;
-  bool quad = false, dec = false, mfma = false;
-  int dec_q = 0;
-  int mf_splits = 1, mf_waves = 1, mf_groups = 0, mf_buffer_floats = 0;
-  size_t mf_lds = 0;
-  uint64_t tile_outputs = 1;  // consecutive outputs of a stream per tile
-  uint64_t blocks_per_tile() const { return dec ? 1 : mfma ? (uint64_t)mf_splits : quad ? (uint64_t)quad_splits : 1; }
-};
-
-KernelPlan plan_kernel(const Design *d) {
-  // Decimation steps of 64 samples or more use the row layout; there the kernel with four consecutive outputs per
-  // lane applies (NEEDLE_HIP_RESAMPLE_V1 forces the first kernel: tests and A/B timing).
-  // a tile's rows are cut into `quad_splits` workgroups (see the kernel); the rows of a workgroup: the groups between
-  // the first reads of its first and last quad, the window, two groups of slack
-  // (measured at 48 kHz, 37 quads: 1 / 2 / 3 / 4 / 6 workgroups per tile 0.77 / 0.72 / 0.64 / 0.72 / 0.81 ms: about
-  // 16 quads = 256 threads per workgroup)
-  const int quads_all = (d->L + 3) / 4;
-  int quad_splits = (quads_all + 15) / 16;
-  if (const char *e = getenv("NEEDLE_HIP_RESAMPLE_SPLITS")) quad_splits = std::max(1, atoi(e));  // tuning
-  quad_splits = std::min(quad_splits, quads_all);
-  const int quads_per_split = (quads_all + quad_splits - 1) / quad_splits;
-  const int row_groups = ((quads_per_split - 1) * 4 * d->M + d->L - 1) / d->L / 4 + 2 + d->steps + 2;
-  const int quad_pitch = row_groups | 1;
-  const size_t quad_lds = (size_t)kQuadRows * quad_pitch * 16;  // (the output tile reuses the start of the region)
-  const int quad_threads = std::min(1024, ((16 * quads_per_split + 63) / 64) * 64);
-  const bool quad = d->M >= kRowModeMinM && d->L >= 4 && quad_lds <= 160 * 1024 &&
-                    (size_t)kQuadRows * 4 * quads_per_split * 2 <= quad_lds &&
-                    quads_per_split <= kQuadMaxRounds * (quad_threads / 16) && getenv("NEEDLE_HIP_RESAMPLE_V1") == nullptr;
-  // integer decimation by 4 or 2 (44.1 / 22.05 kHz): the kernel with scalar coefficients
-  const int dec_q = d->L == 1 && d->T == 32 * d->M ? (d->M == 4 ? 5 : d->M == 2 ? 6 : 0) : 0;
-  const bool dec = dec_q != 0 && getenv("NEEDLE_HIP_RESAMPLE_V1") == nullptr;
-  // matrix-core kernel (resample_mfma.h): one wave per block of sixteen outputs of a row, at most `mf_waves` per
-  // workgroup; a tile's blocks are cut into `mf_splits` workgroups.  NEEDLE_HIP_RESAMPLE_QUAD forces the DPP kernel.
-  const int mf_max_waves = mfma_rs::kConsumers;
-  const int mf_splits = d->mfma_steps ? (d->nblocks + mf_max_waves - 1) / mf_max_waves : 1;
-  const int mf_waves = d->mfma_steps ? (d->nblocks + mf_splits - 1) / mf_splits : 1;
-  int mf_groups = 0;
-  for (int sp = 0; d->mfma_steps && sp < mf_splits; sp++) {
-    const int b0 = sp * mf_waves, b1 = std::min(b0 + mf_waves, d->nblocks);
-    if (b0 >= b1) { mf_groups = 1 << 30; break; }  // an empty split: not this kernel
-    const int start = d->block_k0[b0] & ~3;
-    mf_groups = std::max(mf_groups, (d->block_k0[b1 - 1] + 4 * d->mfma_steps - start + 3) >> 2);
-  }
-  // a row of the LDS image: the groups the staging threads of the row move, or all the groups its blocks read if more
-  const int mf_row_groups = std::max(mfma_rs::kCovered, mf_groups);
-  const int mf_buffer_floats = mf_row_groups * 4 * mfma_rs::kRows;
-  const size_t mf_lds = (size_t)2 * mf_buffer_floats * sizeof(float);  // double-buffered
-  const bool mfma = quad && d->mfma_steps != 0 && (mf_groups <= mfma_rs::kCovered ||  // longer rows: the rest is the start of the next row (one split only)
-                     (mf_splits == 1 && mf_groups - d->M / 4 <= mfma_rs::kCovered && mfma_rs::kCovered >= d->M / 4 &&
-                      mf_groups - mfma_rs::kCovered <= 64 * mfma_rs::kProducers)) &&
-                    mf_lds <= 160 * 1024 && getenv("NEEDLE_HIP_RESAMPLE_QUAD") == nullptr;
-  const uint64_t tile_outputs = dec ? (uint64_t)kDecThreads * dec_q : quad ? (uint64_t)kQuadRows * d->L : (uint64_t)d->n * d->L;
-  KernelPlan k;
-  k.quad_splits = quad_splits; k.quads_per_split = quads_per_split; k.quad_pitch = quad_pitch; k.quad_threads = quad_threads;
-  k.quad_lds = quad_lds; k.quad = quad; k.dec = dec; k.mfma = mfma; k.dec_q = dec_q;
-  k.mf_splits = mf_splits; k.mf_waves = mf_waves; k.mf_groups = mf_groups; k.mf_buffer_floats = mf_buffer_floats;
-  k.mf_lds = mf_lds; k.tile_outputs = tile_outputs;
-  return k;
-}
-
 }  // namespace
 
 Status resample_tiling(int rate, int channels, ResampleTiling *out) {
@@ -884,29 +940,84 @@ Status resample_tiling(int rate, int channels, ResampleTiling *out) {
   out->L = d->L;
   out->M = d->M;
   out->half = d->T / 2;
-  out->tile_outputs = plan_kernel(d).tile_outputs;
+  const KernelPlan kp = plan_kernel(d);
+  if (kp.refused) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
+  out->tile_outputs = kp.tile_outputs;
   return Status::Ok();
 }
 
 Status resample_tiling_host(int rate, ResampleTiling *out) {
   if (rate < 2000 || rate > 768000) return Status::Make(NeedleError_InvalidArgument, "resample: unsupported sample rate");
-  // the design is a function of the rate alone and is kept; the plan also reads the tuning switches of the environment
-  // and is made afresh, as gpu_resample_device makes it
-  static std::mutex mu;
-  static std::map<int, Design> known;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = known.find(rate);
-  if (it == known.end()) {
-    Design d;
-    if (!design_geometry(rate, &d)) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
-    d.coef = std::vector<float>();  // not needed for the geometry
-    it = known.emplace(rate, std::move(d)).first;
-  }
-  const Design &d = it->second;
+  // nothing is kept: without its coefficients a design is a few hundred integer operations, and the plan also reads the
+  // tuning switches of the environment, as gpu_resample_device's does
+  Design d;
+  KernelPlan kp;
+  if (!design_geometry(rate, &d) || (kp = plan_kernel(&d)).refused)
+    return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
   out->L = d.L;
   out->M = d.M;
   out->half = d.T / 2;
-  out->tile_outputs = plan_kernel(&d).tile_outputs;
+  out->tile_outputs = kp.tile_outputs;
+  return Status::Ok();
+}
+
+Status resample_plan_host(int rate, NeedleHipResamplePlan *out) {
+  std::memset(out, 0, sizeof *out);
+  if (rate < 2000 || rate > 768000) return Status::Make(NeedleError_InvalidArgument, "resample: unsupported sample rate");
+  Design d;
+  const bool fits = design_geometry(rate, &d);
+  out->L = d.L;
+  out->M = d.M;
+  out->T = d.T;
+  out->groups = d.G;
+  out->family = NEEDLE_HIP_RESAMPLE_REFUSED;
+  if (!fits) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
+  const KernelPlan kp = plan_kernel(&d);  // the one gpu_resample_device launches from
+  out->tile_outputs = (int)kp.tile_outputs;
+  out->blocks_per_tile = (int)kp.blocks_per_tile();
+  if (kp.dec) {
+    out->family = NEEDLE_HIP_RESAMPLE_DEC;
+    out->threads = kDecThreads;
+    out->dec_q = kp.dec_q;
+  } else if (kp.mfma) {
+    out->family = NEEDLE_HIP_RESAMPLE_MFMA;
+    out->threads = 1024;
+    out->lds_bytes = (int)kp.mf_lds;
+    out->delta = d.delta;
+    out->mfma_steps = d.mfma_steps;
+    out->nblocks = d.nblocks;
+    out->mf_splits = kp.mf_splits;
+    out->mf_waves = kp.mf_waves;
+    out->mf_groups = kp.mf_groups;
+    out->mf_long_row = kp.mf_dup_hi != 0;
+    out->mf_dup_lo = kp.mf_dup_lo;
+    out->mf_dup_hi = kp.mf_dup_hi;
+  } else if (kp.quad) {
+    out->family = NEEDLE_HIP_RESAMPLE_QUAD;
+    out->threads = kp.quad_threads;
+    out->lds_bytes = (int)kp.quad_lds;
+    out->vec4 = kp.quad_vec4;
+    out->pitch = kp.quad_pitch;
+    out->delta = d.delta;
+    out->quad_splits = kp.quad_splits;
+    out->quads_per_split = kp.quads_per_split;
+    out->quad_threads = kp.quad_threads;
+    out->quad_rounds = (kp.quads_per_split + kp.quad_threads / 16 - 1) / (kp.quad_threads / 16);
+    out->quad_small = kp.quad_small;
+    out->quad_steps = d.steps;
+  } else {
+    out->family = kp.refused ? NEEDLE_HIP_RESAMPLE_REFUSED : rate == kTarget ? NEEDLE_HIP_RESAMPLE_IDENTITY : NEEDLE_HIP_RESAMPLE_GENERAL;
+    out->threads = kThreads;
+    out->lds_bytes = (int)std::min<size_t>(kp.lds_bytes, 0x7FFFFFFF);
+    out->n = d.n;
+    out->row_mode = kp.row_mode;
+    out->rows_in_lds = kp.rows_in_lds;
+    out->vec4 = kp.vec4;
+    out->pitch = kp.pitch;
+    out->region_slots = kp.region_slots;
+    out->delta = kp.delta;
+    if (kp.refused) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
+  }
   return Status::Ok();
 }
 
@@ -943,11 +1054,12 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
   NEEDLE_HIP_TRY(hipGetDevice(&dev));
   Design *d;
   if (!(s = get_design(dev, rate, &d)).ok()) return s;
-  const KernelPlan kp = plan_kernel(d);
+  const KernelPlan kp = plan_kernel(d);  // (made afresh: it also reads the tuning switches of the environment)
+  if (kp.refused) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
   const int quad_splits = kp.quad_splits, quad_pitch = kp.quad_pitch, quad_threads = kp.quad_threads;
   const size_t quad_lds = kp.quad_lds;
   const bool quad = kp.quad, dec = kp.dec, mfma = kp.mfma;
-  const int mf_splits = kp.mf_splits, mf_waves = kp.mf_waves, mf_groups = kp.mf_groups, mf_buffer_floats = kp.mf_buffer_floats;
+  const int mf_splits = kp.mf_splits, mf_waves = kp.mf_waves, mf_buffer_floats = kp.mf_buffer_floats;
   const size_t mf_lds = kp.mf_lds;
   const uint64_t tile_outputs = kp.tile_outputs;
   std::vector<RsStream> meta;
@@ -1006,11 +1118,8 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
       mg.L = d->L; mg.M = d->M; mg.half = d->T / 2; mg.delta = d->delta;
       mg.nblocks = d->nblocks; mg.blocks_per_wg = mf_waves; mg.splits = mf_splits;
       mg.m_groups = d->M / 4;
-      mg.dup_lo = mg.dup_hi = 0;
-      if (mf_groups > mfma_rs::kCovered) {
-        mg.dup_lo = mfma_rs::kCovered - mg.m_groups;
-        mg.dup_hi = mf_groups - mg.m_groups;
-      }
+      mg.dup_lo = kp.mf_dup_lo;
+      mg.dup_hi = kp.mf_dup_hi;
       int cus = 256;
       (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
       // Wave roles.  The waves of a workgroup go to the four SIMDs in turn, so waves w, w + 4, w + 8, w + 12 share one.
@@ -1111,7 +1220,7 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
       geo.n_log2 = 4;
       geo.pitch = quad_pitch;
       geo.region_slots = kQuadRows * quad_pitch;
-      const bool vec4 = d->M % 4 == 0;
+      const bool vec4 = kp.quad_vec4;
       geo.delta = d->delta;
       const void *variants[] = {reinterpret_cast<const void *>(resample_quad_kernel<1, false, false>),
                                   reinterpret_cast<const void *>(resample_quad_kernel<1, true, false>),
@@ -1150,7 +1259,7 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
                            (int)meta.size(), coefq, static_cast<const QuadInfo *>(d->d_quad_info), geo, d->steps, quad_splits,
                            skew_blocks, skew_unit, d_out);
       };
-      const bool small = threads <= 640;
+      const bool small = kp.quad_small;
 #ifdef NEEDLE_HIP_LAB_BUILD
       const int lab = getenv("NEEDLE_HIP_RESAMPLE_LAB") ? atoi(getenv("NEEDLE_HIP_RESAMPLE_LAB")) : 0;
 #else
@@ -1179,27 +1288,12 @@ Status gpu_resample_device(const int16_t *d_in, const std::vector<ResampleSpan> 
       if (sync) NEEDLE_HIP_TRY(hipStreamSynchronize(library_stream()));
       return Status::Ok();
     }
-    geo.n_log2 = 0;
-    while ((1 << geo.n_log2) < d->n) geo.n_log2++;
-    const bool row_mode = d->M >= kRowModeMinM && d->n <= kRowModeMaxN;
-    if (row_mode) {  // n rows of M + 4G + 4 samples, pitch odd in slots
-      geo.pitch = ((d->M + 4 * d->G + 4 + 3) / 4) | 1;
-      geo.region_slots = d->n * geo.pitch;
-    } else {         // the n M + T - 1 inputs a tile reads, plus the taps the shifted rows add at either end
-      geo.pitch = 0;
-      geo.region_slots = (d->n * d->M + 4 * d->G + 4 + 3) / 4;
-    }
-    const int rows_per_wave = d->n >= 64 ? 1 : 64 / d->n;
-    // (very long filters, from rates far above 100 kHz: the per-wave row scratch would not fit; coefficients then
-    // come straight from global memory)
-    const bool rows_in_lds = (row_mode || d->M % 4 == 0) && (size_t)(kThreads / 64) * (d->n >= 64 ? 1 : 64 / d->n) * d->G * 16 <= 48 * 1024;
-    // M % 4 == 0: a tile's first tap is a fixed number of samples past a multiple of 4; the region starts at that
-    // multiple, so rows can be staged by aligned groups of four samples
-    const bool vec4 = d->M % 4 == 0;
-    geo.delta = vec4 ? ((1 - d->T / 2) % 4 + 4) % 4 : 0;
-    const size_t lds_bytes = (size_t)geo.region_slots * 16 + ((tile_outputs * 2 + 15) & ~(size_t)15) +
-                             (rows_in_lds ? (size_t)(kThreads / 64) * rows_per_wave * d->G * 16 : 0);
-    if (lds_bytes > 160 * 1024) return Status::Make(NeedleError_InvalidArgument, "resample: rate ratio too large for this kernel");
+    geo.n_log2 = kp.n_log2;
+    geo.pitch = kp.pitch;
+    geo.region_slots = kp.region_slots;
+    geo.delta = kp.delta;
+    const bool rows_in_lds = kp.rows_in_lds, vec4 = kp.vec4;
+    const size_t lds_bytes = kp.lds_bytes;
     const void *variants[6] = {reinterpret_cast<const void *>(resample_kernel<1, false, false>),
                                reinterpret_cast<const void *>(resample_kernel<1, true, false>),
                                reinterpret_cast<const void *>(resample_kernel<1, true, true>),

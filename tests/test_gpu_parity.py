@@ -704,11 +704,11 @@ def test_resampler_bit_exact_and_analyzer_accepts_decode_rates(tmp_path):
     usual decode rates, mono and stereo, ragged batches; and a 44.1 kHz stereo WAV analysed through the unchanged
     needle-capi call gives the hashes of the oracle chain resample -> fingerprint."""
     rng = np.random.default_rng(99)
-    # 44.1k: contiguous LDS layout, one phase; 48k/32k/16k/8k: row layout; 22.05k and 12345: lanes with different tap
-    # alignment (coefficients straight from global memory); 96k: longest filter; 11025: identity + down-mix
-    # 192k / 176.4k: filters too long for the per-wave coefficient scratch (global-memory coefficient path, fewer rows)
-    # round 2: 44.1k / 22.05k take the integer-decimation kernel (scalar coefficients), the row-layout rates the kernel with
-    # four outputs per lane and DPP-broadcast coefficients, 88.2k / 12345 / 192k / 176.4k / 11025 the first kernel
+    # which kernel each rate takes (needle_hip_resample_plan; tests/test_gpu_resample_plans.py asserts it case by case and
+    # covers the plans these rates do not reach): 44.1k / 22.05k the integer-decimation kernel; 48k / 32k / 16k / 8k the
+    # matrix-core kernel; 96k / 192k / 12345 the kernel with four outputs per lane; 88.2k / 176.4k the general kernel,
+    # contiguous layout, coefficient rows through LDS; 11025 the general kernel with a unit tap (identity + down-mix).
+    # None takes the general kernel with coefficients straight from global memory.
     for rate, ch in [(44100, 2), (44100, 1), (48000, 2), (48000, 1), (22050, 1), (22050, 2), (32000, 2), (8000, 1),
                      (11025, 2), (96000, 2), (16000, 1), (12345, 1), (88200, 2), (192000, 2), (176400, 1)]:
         pcms = []
