@@ -62,7 +62,7 @@ double needle_hip_last_kernel_ms(const char *kernel);
 void needle_hip_set_kernel_timing(const char *kernels);
 /* With "sum": the launches of that name that have been given events since the last needle_hip_set_kernel_timing call;
  * otherwise, and for an unknown name, 0.  Only the first 4096 launches of a name keep events: the count stops there, so a
- * reader that may see more sets the selection again in between.  Further names: "ingest", "feeder_carry". */
+ * reader that may see more sets the selection again in between.  Further names: "ingest", "rematrix", "feeder_carry". */
 size_t needle_hip_kernel_launches(const char *kernel);
 /* Diagnostic for the search roofline: table cells per second this device sustains on the scan's
  * per-cell instruction sequence (xor, popcount, compare, select) with operands in registers -- the integer-VALU
@@ -665,6 +665,55 @@ enum NeedleError needle_hip_feeder_reset_format(NeedleHipFeeder *feeder, const s
  * One kernel launch per batch of at most NEEDLE_HIP_MAX_BATCH_VALUES values, whatever the mixture of formats. */
 enum NeedleError needle_hip_convert_mono_host(const void *const *pcm, const size_t *num_values, const NeedleHipLaneFormat *formats,
                                               size_t num_streams, int16_t *const *out);
+
+/* ---- Channel mixes: a layout-aware fold-down to stereo, then mono, on the device ---------------------------
+ * The reference hands chromaprint stereo only (analyzer.rs:180-187,218): a 5.1 track goes through its resampler's
+ * rematrix first, so a surround episode and a stereo episode of one show hash alike.  The plain average of the C
+ * channels above does not give that; a channel mix does.  It is an OPTION on every path that takes C-channel PCM:
+ * nothing changes for a caller who sets none.
+ *
+ * A mix is a 2 x C matrix of Q15 integers, coef[0][c] to the left output and coef[1][c] to the right.  For one frame of
+ * C samples x_c, each converted to s16 first by the sample format's rule above:
+ *   acc_o  = sum over c of coef[o][c] * x_c                       (o = 0, 1; int32)
+ *   Lo, Ro = clip((acc_o + 16384) >> 15, -32768, 32767)           (arithmetic shift)
+ *   mono   = (Lo + Ro) / 2                                        (C division: the stereo path's own rule)
+ * Limits, each NeedleError_InvalidArgument on the host before any device is asked for: channels outside 1..8; a
+ * coefficient outside [-32768, 32768]; a row whose sum of |coef| exceeds 65535 (the bound that keeps acc in int32); and
+ * channels different from the channel count of the call, the library or the lane the mix is given to.
+ * The arithmetic is this front end's own specification.  The default weights are shaped after swresample's documented
+ * defaults as recalled; swresample itself could not be compared against. */
+typedef struct NeedleHipChannelMix {
+  int32_t channels;
+  int32_t coef[2][NEEDLE_HIP_MAX_CHANNELS];
+} NeedleHipChannelMix;
+/* The default mix of a channel mask (WAVEFORMATEXTENSIBLE / FFmpeg bits: 0x1 FL, 0x2 FR, 0x4 FC, 0x8 LFE, 0x10 BL,
+ * 0x20 BR, 0x40 FLC, 0x80 FRC, 0x100 BC, 0x200 SL, 0x400 SR; channels in ascending bit order).  Weights: FL, FLC 1 to
+ * the left; FR, FRC 1 to the right; FC sqrt(1/2) to both; BL, SL sqrt(1/2) to the left; BR, SR sqrt(1/2) to the right;
+ * BC 1/2 to both; LFE 0.  Both rows are divided by the larger row sum if that exceeds 1, then
+ * coef = floor(m * 32768 + 0.5).  A bit above 0x400, or a popcount outside 1..8, is InvalidArgument.  Host arithmetic. */
+enum NeedleError needle_hip_channel_mix_default(uint32_t channel_mask, NeedleHipChannelMix *out);
+/* The kernel alone, like needle_hip_convert_mono_host: out[i] receives the mono of stream i under mixes[i];
+ * mixes[i].channels == 0 asks for the plain average of stream i.  One launch of the rematrix kernel per batch. */
+enum NeedleError needle_hip_rematrix_host(const void *const *pcm, const size_t *num_values, const NeedleHipLaneFormat *formats,
+                                          const NeedleHipChannelMix *mixes, size_t num_streams, int16_t *const *out);
+/* The drivers.  With a mix set, C-channel input of any format (1 and 2 channels included) is landed as mono by the
+ * rematrix kernel and everything behind it is the mono s16 path on those values.
+ * analyzer: for needle_hip_analyzer_run_pcm / _run_pcm_format, whose `channels` must equal the mix's.  NULL: plain again. */
+enum NeedleError needle_hip_analyzer_set_channel_mix(struct NeedleAudioAnalyzer *analyzer, const NeedleHipChannelMix *mix);
+/* file analyzer (needle_audio_analyzer_run): every WAVE_FORMAT_EXTENSIBLE file whose dwChannelMask is non-zero and is
+ * accepted by needle_hip_channel_mix_default is folded with its own default mix; other files keep the plain average. */
+enum NeedleError needle_hip_analyzer_set_layout_downmix(struct NeedleAudioAnalyzer *analyzer, bool on);
+/* the same for the analyzer that needle_audio_comparator_run makes when asked to `analyze` */
+enum NeedleError needle_hip_comparator_set_layout_downmix(struct NeedleAudioComparator *comparator, bool on);
+/* library: before set_pcm / set_pcm_device / stream_pcm, like set_sample_format; the channel count of those calls must
+ * equal the mix's.  NULL: plain again. */
+enum NeedleError needle_hip_library_set_channel_mix(NeedleHipLibrary *library, const NeedleHipChannelMix *mix);
+/* feeder: lanes[j] takes mixes[j] (channels == 0: none).  Only on a feeder made by needle_hip_feeder_new_lanes, and only
+ * for lanes that hold no samples (new or reset); otherwise InvalidArgument and nothing changes, not for lanes named
+ * earlier in the call either.  reset_format clears a lane's mix.  A feeder any of whose lanes has a mix lands every
+ * staged span of a round with one launch of the rematrix kernel (timer "rematrix"; no "ingest" launch); one without
+ * launches what it always did. */
+enum NeedleError needle_hip_feeder_set_lane_mix(NeedleHipFeeder *feeder, const size_t *lanes, const NeedleHipChannelMix *mixes, size_t k);
 
 /* ---- Streaming comparator: search as the hashes arrive ---------------------------------------------------
  * The search half of the streaming path, the counterpart of the feeder.  A matcher holds S source sequences (the

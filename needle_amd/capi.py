@@ -109,6 +109,9 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
     "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready", "needle_hip_feeder_set_audit", "needle_hip_feeder_audit",
     "needle_hip_feeder_new_lanes", "needle_hip_feeder_lane_format", "needle_hip_feeder_reset_format", "needle_hip_convert_mono_host",
+    "needle_hip_channel_mix_default", "needle_hip_rematrix_host", "needle_hip_analyzer_set_channel_mix",
+    "needle_hip_analyzer_set_layout_downmix", "needle_hip_comparator_set_layout_downmix", "needle_hip_library_set_channel_mix",
+    "needle_hip_feeder_set_lane_mix",
     "needle_hip_matcher_new", "needle_hip_matcher_free", "needle_hip_matcher_feed", "needle_hip_matcher_feed_from_feeder",
     "needle_hip_matcher_finish", "needle_hip_matcher_reset", "needle_hip_matcher_ready", "needle_hip_matcher_runs",
     "needle_hip_matcher_open", "needle_hip_matcher_stats",
@@ -159,6 +162,42 @@ def _format_pointers(pcm, channels: int, sample_format: int):
 
 class CLaneFormat(C.Structure):                          # NeedleHipLaneFormat
     _fields_ = [("channels", C.c_int32), ("sample_rate", C.c_int32), ("format", C.c_int32)]
+
+
+class ChannelMix(C.Structure):                           # NeedleHipChannelMix
+    """A 2 x C matrix of Q15 integers, coef[0][c] to the left output and coef[1][c] to the right (needle_hip.h "Channel
+    mixes").  ChannelMix.of(left, right) builds one from two rows; channels == 0 (ChannelMix()) means "no mix"."""
+    _fields_ = [("channels", C.c_int32), ("coef", (C.c_int32 * MAX_CHANNELS) * 2)]
+
+    @classmethod
+    def of(cls, left: Sequence[int], right: Sequence[int], channels: Optional[int] = None) -> "ChannelMix":
+        if len(left) != len(right) or len(left) > MAX_CHANNELS:
+            raise ValueError(f"two rows of at most {MAX_CHANNELS} coefficients each")
+        m = cls()
+        m.channels = len(left) if channels is None else channels
+        for c, (l, r) in enumerate(zip(left, right)):
+            m.coef[0][c], m.coef[1][c] = int(l), int(r)
+        return m
+
+    def rows(self) -> Tuple[List[int], List[int]]:
+        n = max(0, min(self.channels, MAX_CHANNELS))
+        return list(self.coef[0][:n]), list(self.coef[1][:n])
+
+
+def channel_mix_default(channel_mask: int) -> ChannelMix:
+    """needle_hip_channel_mix_default: the default mix of a WAVEFORMATEXTENSIBLE / FFmpeg channel mask (host arithmetic)."""
+    m = ChannelMix()
+    check(lib().needle_hip_channel_mix_default(channel_mask, C.byref(m)))
+    return m
+
+
+def _channel_mixes(mixes):
+    """NeedleHipChannelMix array; None stands for "no mix" (channels == 0)."""
+    arr = (ChannelMix * max(len(mixes), 1))()
+    for i, m in enumerate(mixes):
+        if m is not None:
+            C.memmove(C.byref(arr[i]), C.byref(m), C.sizeof(ChannelMix))
+    return arr
 
 
 RESAMPLE_FAMILIES = ["identity", "dec", "mfma", "quad", "general", "refused"]   # enum NeedleHipResampleFamily
@@ -340,6 +379,13 @@ def lib():
     L.needle_hip_feeder_lane_format.argtypes = [vp, sz, vp]
     L.needle_hip_feeder_reset_format.argtypes = [vp, C.POINTER(sz), vp, sz]
     L.needle_hip_convert_mono_host.argtypes = [C.POINTER(vp), C.POINTER(sz), vp, sz, C.POINTER(vp)]
+    L.needle_hip_channel_mix_default.argtypes = [u32, vp]
+    L.needle_hip_rematrix_host.argtypes = [C.POINTER(vp), C.POINTER(sz), vp, vp, sz, C.POINTER(vp)]
+    L.needle_hip_analyzer_set_channel_mix.argtypes = [vp, vp]
+    L.needle_hip_analyzer_set_layout_downmix.argtypes = [vp, b]
+    L.needle_hip_comparator_set_layout_downmix.argtypes = [vp, b]
+    L.needle_hip_library_set_channel_mix.argtypes = [vp, vp]
+    L.needle_hip_feeder_set_lane_mix.argtypes = [vp, C.POINTER(sz), vp, sz]
     L.needle_hip_matcher_new.argtypes = [vp, sz, vp, vp, sz, sz, u32, C.POINTER(vp)]
     L.needle_hip_matcher_free.argtypes = [vp]
     L.needle_hip_matcher_free.restype = None
@@ -580,10 +626,29 @@ class Analyzer:
         self._cfg = dict(opening=opening_search_percentage, ending=ending_search_percentage,
                          include_endings=include_endings, threaded=threaded_decoding, force=force)
         self._h = None
+        self._mix: Optional[ChannelMix] = None
+        self._layout_downmix = False
 
     @staticmethod
     def from_files(videos: Sequence[str], threaded_decoding: bool = False, force: bool = False) -> "Analyzer":
         return Analyzer(videos, threaded_decoding, force)
+
+    def set_channel_mix(self, mix: Optional[ChannelMix]) -> "Analyzer":
+        """run_pcm folds its `channels`-channel PCM with `mix` (needle_hip_analyzer_set_channel_mix; None: the plain
+        average again).  The mix's limits are checked here; its channel count against the call's in run_pcm."""
+        old, self._mix = self._mix, mix
+        try:
+            self._handle()
+        except NeedleError:
+            self._mix = old
+            raise
+        return self
+
+    def set_layout_downmix(self, on: bool) -> "Analyzer":
+        """run folds every WAV file that carries a channel mask with that mask's default mix
+        (needle_hip_analyzer_set_layout_downmix); files without one keep the plain average."""
+        self._layout_downmix = bool(on)
+        return self
 
     def with_opening_search_percentage(self, v: float) -> "Analyzer":
         self._cfg["opening"] = v
@@ -614,6 +679,10 @@ class Analyzer:
         check(lib().needle_audio_analyzer_new(ptr, len(self.videos), c["opening"], c["ending"], c["include_endings"],
                                               c["threaded"], c["force"], C.byref(out)))
         self._h = out
+        if self._mix is not None:
+            check(lib().needle_hip_analyzer_set_channel_mix(out, C.byref(self._mix)))
+        if self._layout_downmix:
+            check(lib().needle_hip_analyzer_set_layout_downmix(out, True))
         return out
 
     def _collect(self) -> List[FrameHashes]:
@@ -875,6 +944,15 @@ class Feeder:
         f = CLaneFormat()
         check(lib().needle_hip_feeder_lane_format(self._h, lane, C.byref(f)))
         return f.channels, f.sample_rate, f.format
+
+    def set_lane_mix(self, lanes: Sequence[int], mixes: Sequence[Optional[ChannelMix]]) -> None:
+        """lanes[j] folds its channels with mixes[j] (None: the plain average again); a with_formats feeder only, and only
+        lanes that hold no samples (needle_hip_feeder_set_lane_mix)."""
+        if len(lanes) != len(mixes):
+            raise ValueError("one mix (or None) per lane")
+        k = len(lanes)
+        arr = (C.c_size_t * max(k, 1))(*lanes)
+        check(lib().needle_hip_feeder_set_lane_mix(self._h, arr, _channel_mixes(mixes), k))
 
     def reset_format(self, lanes: Sequence[int], formats: Sequence[Tuple[int, int, int]]) -> None:
         """lanes[j] starts a new stream in formats[j] (needle_hip_feeder_reset_format; a with_formats feeder only)."""
@@ -1286,6 +1364,27 @@ def convert_mono(pcms: Sequence, formats: Sequence[Tuple[int, int, int]], num_va
     return [o[:k] for o, k in zip(outs, lens_out)]
 
 
+def rematrix_host(pcms: Sequence, formats: Sequence[Tuple[int, int, int]], mixes: Sequence[Optional[ChannelMix]],
+                  num_values: Optional[Sequence[int]] = None) -> List[np.ndarray]:
+    """needle_hip_rematrix_host: `convert_mono` with a channel mix per stream (None: the plain average of that stream),
+    one launch of the rematrix kernel whatever the mixture."""
+    formats = [tuple(int(v) for v in f) for f in formats]
+    if len(formats) != len(pcms) or len(mixes) != len(pcms):
+        raise ValueError("one format and one mix (or None) per stream")
+    keep, flat, sizes = _lane_pointers(pcms, formats)
+    n = len(pcms)
+    if num_values is None:
+        num_values = sizes
+    lens_out = [int(v) // max(f[0], 1) for v, f in zip(num_values, formats)]
+    outs = [np.zeros(max(k, 1), dtype=np.int16) for k in lens_out]
+    ptrs = (C.c_void_p * max(len(flat), 1))(*flat)
+    lens = (C.c_size_t * max(n, 1))(*[int(v) for v in num_values])
+    optrs = (C.c_void_p * max(n, 1))(*[o.ctypes.data for o in outs])
+    check(lib().needle_hip_rematrix_host(ptrs, lens, _lane_formats(formats), _channel_mixes(mixes), n, optrs))
+    del keep
+    return [o[:k] for o, k in zip(outs, lens_out)]
+
+
 def hamming_runs(seqs: Sequence[np.ndarray], problems: Sequence[Tuple[int, int, int]], threshold: int) -> np.ndarray:
     """needle_hip_hamming_runs_host.  problems: (src_seq, dst_seq, min_len); returns a structured array of
     (problem, src_end, dst_end, len), problem = index into `problems`."""
@@ -1399,6 +1498,12 @@ class Library:
         """The rate of the PCM set_pcm / set_pcm_device / stream_pcm / rank_videos will be given; resampled to 11025 Hz
         mono on the device on the way in (needle_hip_library_set_sample_rate)."""
         check(lib().needle_hip_library_set_sample_rate(self._h, sample_rate))
+        return self
+
+    def set_channel_mix(self, mix: Optional[ChannelMix]) -> "Library":
+        """The PCM of set_pcm / set_pcm_device / stream_pcm is folded to mono with `mix` on the way in
+        (needle_hip_library_set_channel_mix; before set_pcm; None: the plain average again)."""
+        check(lib().needle_hip_library_set_channel_mix(self._h, None if mix is None else C.byref(mix)))
         return self
 
     def set_sample_format(self, sample_format: int) -> "Library":

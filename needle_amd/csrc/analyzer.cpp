@@ -66,7 +66,7 @@ Status Analyzer::fingerprint_windows(const std::vector<WindowPcm> &win, int chan
   // PCM at another rate than chromaprint's 11025 Hz goes through the device resampler (the reference
   // resamples with swresample first, :180-187); the windows are cut at the stream's own rate
   // (samples in another format than s16 are converted on the device in front of that, convert.hip)
-  Status s = gpu_fingerprint_host_format(ptrs, lens, channels, format, step, &kept, sample_rate);
+  Status s = gpu_fingerprint_host_format(ptrs, lens, channels, format, step, &kept, sample_rate, has_mix_ ? &mix_ : nullptr);
   if (!s.ok()) return s;
   out->assign(win.size(), {});
   const size_t per = include_endings_ ? 2 : 1;
@@ -103,6 +103,10 @@ Status Analyzer::run_pcm_format(const std::vector<const void *> &pcm, const std:
     return Status::Make(NeedleError_InvalidArgument, "unsupported sample rate");
   if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
     return Status::Make(NeedleError_InvalidArgument, "channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
+  if (has_mix_) {
+    Status ms = channel_mix_check(mix_, channels);
+    if (!ms.ok()) return ms;
+  }
   uint32_t step = 0;
   if (!step_for_hash_duration(hash_duration, &step))  // the reference panics in step_by(0), :293-304
     return Status::Make(NeedleError_AnalyzerInvalidHashDuration,
@@ -160,6 +164,7 @@ struct Trace {  // NEEDLE_HIP_TRACE=1: phase times of the file analyzer on stder
 struct Pending {
   size_t index = 0;  // position in videos_
   WavInfo info;
+  uint32_t mask = 0;  // layout down-mix: the file's channel mask if it has a default mix, 0: the plain average
   size_t opening_frames = 0, ending_first = 0;
   ns_t seek = 0;
 };
@@ -217,6 +222,9 @@ Status Analyzer::run(ns_t hash_duration, bool persist, bool threading, std::vect
     s = windows((size_t)p.info.frames, p.info.sample_rate, opening_search_percentage_, ending_search_percentage_,
                 &p.opening_frames, &p.ending_first, &p.seek);
     if (!s.ok()) return s;
+    NeedleHipChannelMix mix;
+    if (layout_downmix_ && p.info.channel_mask && channel_mix_default(p.info.channel_mask, &mix).ok() && mix.channels == p.info.channels)
+      p.mask = p.info.channel_mask;
     pending.push_back(p);
     return Status::Ok();
   };
@@ -226,18 +234,25 @@ Status Analyzer::run(ns_t hash_duration, bool persist, bool threading, std::vect
   }
 
   trace.lap("md5 + cache check + WAV headers", n);
-  // one device pass per distinct (channels, rate), videos in input order
-  std::vector<std::pair<int, int>> keys;
+  // one device pass per distinct (channels, rate, channel mask to fold by), videos in input order
+  struct Key {
+    int first, second;  // channels, rate
+    uint32_t mask;
+    bool operator==(const Key &o) const { return first == o.first && second == o.second && mask == o.mask; }
+  };
+  std::vector<Key> keys;
   for (const Pending &p : pending) {
-    const std::pair<int, int> key{p.info.channels, p.info.sample_rate};
+    const Key key{p.info.channels, p.info.sample_rate, p.mask};
     if (std::find(keys.begin(), keys.end(), key) == keys.end()) keys.push_back(key);
   }
   const unsigned readers = threading ? std::min(host_threads(), 16u) : 1u;
   const size_t per = include_endings_ ? 2 : 1;
-  for (const std::pair<int, int> &key : keys) {
+  for (const Key &key : keys) {
     std::vector<const Pending *> group;
     for (const Pending &p : pending)
-      if (p.info.channels == key.first && p.info.sample_rate == key.second) group.push_back(&p);
+      if (p.info.channels == key.first && p.info.sample_rate == key.second && p.mask == key.mask) group.push_back(&p);
+    NeedleHipChannelMix mix{};
+    if (key.mask) (void)channel_mix_default(key.mask, &mix);  // (accepted when the file was probed)
     const size_t c = (size_t)key.first;
     std::vector<size_t> lens;  // stream 2k (+1) = opening (ending) window of group[k]
     for (const Pending *p : group) {
@@ -250,7 +265,7 @@ Status Analyzer::run(ns_t hash_duration, bool persist, bool threading, std::vect
       return wav_read_frames(videos_[p.index], p.info, window_first + first_value / c, num_values / c, dst);
     };
     std::vector<std::vector<uint32_t>> kept;
-    Status s = gpu_fingerprint_streamed(lens, read, readers, key.first, step, &kept, key.second);
+    Status s = gpu_fingerprint_streamed(lens, read, readers, key.first, step, &kept, key.second, key.mask ? &mix : nullptr);
     if (!s.ok()) return s;
     trace.lap("read + upload + fingerprint", group.size());
     for (size_t k = 0; k < group.size(); k++) {

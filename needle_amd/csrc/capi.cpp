@@ -670,6 +670,45 @@ enum NeedleError needle_hip_convert_mono_host(const void *const *pcm, const size
   });
 }
 
+enum NeedleError needle_hip_channel_mix_default(uint32_t channel_mask, NeedleHipChannelMix *out) {
+  if (!out) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = channel_mix_default(channel_mask, out);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_rematrix_host(const void *const *pcm, const size_t *num_values, const NeedleHipLaneFormat *formats,
+                                          const NeedleHipChannelMix *mixes, size_t num_streams, int16_t *const *out) {
+  if (!pcm || !num_values || !formats || !mixes || !out) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const void *> p;
+    std::vector<size_t> n(num_values, num_values + num_streams);
+    std::vector<int> channels(num_streams), fmts(num_streams);
+    std::vector<int16_t *> o(out, out + num_streams);
+    for (size_t i = 0; i < num_streams; i++) {  // every stream and every mix is checked before any pointer is counted off
+      channels[i] = formats[i].channels;
+      fmts[i] = formats[i].format;
+      if (channels[i] < 1 || channels[i] > NEEDLE_HIP_MAX_CHANNELS || !sample_format_valid(fmts[i])) return NeedleError_InvalidArgument;
+      if (mixes[i].channels) {
+        Status s = channel_mix_check(mixes[i], channels[i]);
+        if (!s.ok()) return report(s);
+      }
+    }
+    for (size_t i = 0; i < num_streams; i++) {
+      const size_t planes = sample_format_planes(fmts[i], channels[i]);
+      if (n[i] >= (size_t)channels[i]) {  // otherwise no whole frame: nothing is read or written
+        if (!o[i]) return NeedleError_NullArgument;
+        for (size_t c = 0; c < planes; c++)
+          if (!pcm[p.size() + c]) return NeedleError_NullArgument;
+      }
+      p.insert(p.end(), pcm + p.size(), pcm + p.size() + planes);
+    }
+    Status s = gpu_convert_mono_host(p, n, channels, fmts, o, mixes);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 // ============================================================================================================
 // search
 // ============================================================================================================
@@ -740,6 +779,14 @@ enum NeedleError needle_hip_feeder_reset_format(NeedleHipFeeder *feeder, const s
   if (!feeder || !lanes || !formats) return NeedleError_NullArgument;
   return guarded([&]() -> NeedleError {
     Status s = feeder->inner->ResetFormat(lanes, formats, k);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_set_lane_mix(NeedleHipFeeder *feeder, const size_t *lanes, const NeedleHipChannelMix *mixes, size_t k) {
+  if (!feeder || !lanes || !mixes) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->SetLaneMix(lanes, mixes, k);
     return s.ok() ? NeedleError_Ok : report(s);
   });
 }
@@ -1181,6 +1228,30 @@ enum NeedleError needle_hip_analyzer_run_pcm_format(struct NeedleAudioAnalyzer *
     for (FrameHashesData &d : out) analyzer->frame_hashes.push_back(FrameHashes{std::move(d)});
     return NeedleError_Ok;
   });
+}
+
+enum NeedleError needle_hip_analyzer_set_channel_mix(struct NeedleAudioAnalyzer *analyzer, const NeedleHipChannelMix *mix) {
+  if (!analyzer) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    if (mix) {
+      Status s = channel_mix_check(*mix, mix->channels);
+      if (!s.ok()) return report(s);
+    }
+    analyzer->inner.with_channel_mix(mix);
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_analyzer_set_layout_downmix(struct NeedleAudioAnalyzer *analyzer, bool on) {
+  if (!analyzer) return NeedleError_NullArgument;
+  analyzer->inner.with_layout_downmix(on);
+  return NeedleError_Ok;
+}
+
+enum NeedleError needle_hip_comparator_set_layout_downmix(struct NeedleAudioComparator *comparator, bool on) {
+  if (!comparator) return NeedleError_NullArgument;
+  comparator->inner.with_layout_downmix(on);
+  return NeedleError_Ok;
 }
 
 enum NeedleError needle_hip_comparator_run_with_frame_hashes(const struct NeedleAudioComparator *comparator,

@@ -23,10 +23,10 @@ const char *kUsage =
     "SUBCOMMANDS:\n"
     "    info       Displays info about needle and its dependencies.\n"
     "    analyze    <PATHS>... [-m|--mode audio] [--opening-search-percentage F] [--ending-search-percentage F]\n"
-    "               [--hash-duration F] [--include-endings] [--threaded-decoding] [--force]\n"
+    "               [--hash-duration F] [--include-endings] [--threaded-decoding] [--force] [--layout-downmix]\n"
     "    search     <PATHS>... [--hash-match-threshold N] [--min-opening-duration N] [--min-ending-duration N]\n"
     "               [--time-padding F] [--analyze] [--use-skip-files] [--write-skip-files] [--include-endings]\n"
-    "               [--no-display]\n";
+    "               [--no-display] [--layout-downmix]\n";
 
 // clap's `cmd.error(kind, msg).exit()`: message + usage on stderr, exit status 2 (main.rs:196-251)
 [[noreturn]] void usage_error(const std::string &msg) {
@@ -58,6 +58,7 @@ struct Args {
   // analyze (audio/mod.rs:14-45 defaults)
   float opening_search_percentage = 0.50f, ending_search_percentage = 0.25f, hash_duration = 0.3f;
   bool include_endings = false, threaded_decoding = false, force = false;
+  bool layout_downmix = false;  // analyze, and search --analyze: fold files that carry a channel mask by their layout
   // search
   uint16_t hash_match_threshold = 10, min_opening_duration = 20, min_ending_duration = 20;
   float time_padding = 0.0f;
@@ -109,6 +110,7 @@ Args parse(int argc, char **argv) {
     else if (an && flag == "ending-search-percentage") a.ending_search_percentage = parse_f32(flag, value_of(i, flag, inline_value));
     else if (an && flag == "hash-duration") a.hash_duration = parse_f32(flag, value_of(i, flag, inline_value));
     else if ((an || se) && flag == "include-endings") a.include_endings = true;
+    else if ((an || se) && flag == "layout-downmix") a.layout_downmix = true;
     else if (an && flag == "threaded-decoding") a.threaded_decoding = true;
     else if (an && flag == "force") a.force = true;
     else if (se && flag == "hash-match-threshold") a.hash_match_threshold = parse_u16(flag, value_of(i, flag, inline_value));
@@ -181,6 +183,7 @@ int main(int argc, char **argv) {
                                               a.ending_search_percentage, a.include_endings, a.threaded_decoding,
                                               a.force, &analyzer);
     if (e != NeedleError_Ok) return fail(e);
+    needle_hip_analyzer_set_layout_downmix(analyzer, a.layout_downmix);
     e = needle_audio_analyzer_run(analyzer, a.hash_duration, /*persist=*/true, !a.no_threading);  // main.rs:288
     needle_audio_analyzer_free(analyzer);
     return e == NeedleError_Ok ? 0 : fail(e);
@@ -194,6 +197,7 @@ int main(int argc, char **argv) {
                                               a.min_opening_duration, a.min_ending_duration, a.time_padding,
                                               &comparator);
   if (e != NeedleError_Ok) return fail(e);
+  needle_hip_comparator_set_layout_downmix(const_cast<NeedleAudioComparator *>(comparator), a.layout_downmix);
   e = needle_audio_comparator_run(comparator, a.analyze, !a.no_display, a.use_skip_files, a.write_skip_files,
                                   !a.no_threading);
   needle_audio_comparator_free(comparator);

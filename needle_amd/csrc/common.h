@@ -106,6 +106,7 @@ Status wav_read(const std::string &path, WavData *out);  // the whole data chunk
 struct WavInfo {
   int channels = 0, sample_rate = 0;
   int format = 0, bits = 0;  // 1 = integer PCM, 3 = IEEE float
+  uint32_t channel_mask = 0; // dwChannelMask of a WAVE_FORMAT_EXTENSIBLE header, 0 otherwise
   uint64_t data_offset = 0;  // byte offset of the first sample in the file
   uint64_t frames = 0;       // samples per channel in the data chunk
 };
@@ -160,7 +161,7 @@ Status gpu_upload_pcm(const std::vector<const int16_t *> &pcm, const std::vector
                       const StreamIssued &issued = nullptr);
 Status gpu_fingerprint_streamed(const std::vector<size_t> &num_values, const PcmReader &read, unsigned readers,
                                 int channels, uint32_t step, std::vector<std::vector<uint32_t>> *items,
-                                int rate = kSampleRate);
+                                int rate = kSampleRate, const NeedleHipChannelMix *mix = nullptr);
 Status gpu_hamming_runs_device(const uint32_t *d_hashes, const NeedleHipSeq *seqs, size_t num_seqs,
                                const NeedleHipProblem *problems, size_t num_problems, uint32_t threshold,
                                NeedleHipRun *d_runs, uint32_t capacity, uint32_t *d_count, bool sync,
@@ -293,10 +294,14 @@ Status gpu_upload_raw(const std::vector<const void *> &src, const std::vector<si
 // gpu_fingerprint_host / gpu_fingerprint_streamed_device with the streams in `format` (fingerprint_host.hip): uploaded as
 // they are, converted on the device group by group under the uploads.  pcm: sample_format_planes() pointers per stream.
 Status gpu_fingerprint_host_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels,
-                                   int format, uint32_t step, std::vector<std::vector<uint32_t>> *items, int rate = kSampleRate);
+                                   int format, uint32_t step, std::vector<std::vector<uint32_t>> *items, int rate = kSampleRate,
+                                   const NeedleHipChannelMix *mix = nullptr);
 Status gpu_fingerprint_streamed_device_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values,
                                               int channels, int format, uint32_t step, uint32_t *d_items,
-                                              const std::vector<uint64_t> &item_off, int rate = kSampleRate);
+                                              const std::vector<uint64_t> &item_off, int rate = kSampleRate,
+                                              const NeedleHipChannelMix *mix = nullptr);
+// (`mix`, in the three above: a channel mix -- the streams of any format and channel count are landed as mono by
+// rematrix.hip, group by group under the uploads, and go on as mono s16)
 // host arrays in and out (pcm: sample_format_planes() pointers per stream; out[i] holds num_values[i] / channels * channels
 // interleaved s16 values, not down-mixed), in batches of bounded device memory
 Status gpu_convert_host(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels, int format,
@@ -310,12 +315,23 @@ struct IngestSpan {
   int16_t *dst;                              // device, a buffer of its own: frames mono values, any 2-byte alignment
   uint64_t frames;
   int channels, format;
+  const NeedleHipChannelMix *mix = nullptr;  // gpu_rematrix_device only; nullptr: the plain average
 };
 // one launch on the library stream for all spans, whatever mixture of formats; returns after enqueueing unless `sync`
 Status gpu_ingest_device(const std::vector<IngestSpan> &spans, bool sync);
 // host arrays in and out (pcm: the concatenation of every stream's sample_format_planes() pointers; out[i] holds
 // num_values[i] / channels[i] values), in batches of bounded device memory
 Status gpu_convert_mono_host(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values,
-                             const std::vector<int> &channels, const std::vector<int> &formats, const std::vector<int16_t *> &out);
+                             const std::vector<int> &channels, const std::vector<int> &formats, const std::vector<int16_t *> &out,
+                             const NeedleHipChannelMix *mixes = nullptr);
+
+// ---- channel mixes: the layout-aware fold-down to stereo, then mono (rematrix.hip; needle_hip.h has the arithmetic) --
+// the limits of a mix, and that it is one for `channels` channels; host arithmetic (hostutil.cpp)
+Status channel_mix_check(const NeedleHipChannelMix &mix, int channels);
+Status channel_mix_default(uint32_t channel_mask, NeedleHipChannelMix *out);
+// gpu_ingest_device with a mix per span: one launch of rematrix_kernel on the library stream for all spans, those
+// without a mix through the shared ingest_block.  gpu_convert_mono_host with `mixes` (one per stream, channels == 0:
+// none) runs this instead of gpu_ingest_device.
+Status gpu_rematrix_device(const std::vector<IngestSpan> &spans, bool sync);
 
 }  // namespace needle

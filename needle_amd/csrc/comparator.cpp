@@ -836,6 +836,7 @@ Status Comparator::run(bool analyze, bool display, bool use_skip_files, bool wri
   } else {
     // data.rs:134-136: default Analyzer (no endings), force, 0.3 s, not persisted — here as one GPU batch
     Analyzer a = Analyzer::from_files(videos_, false, true);
+    a.with_layout_downmix(layout_downmix_);
     bool ok = true;
     const ns_t hd = duration_from_secs_f32(DEFAULT_HASH_DURATION, &ok);
     Status s = a.run(hd, false, threading, &data);

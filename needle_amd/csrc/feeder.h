@@ -21,6 +21,10 @@ class Feeder {
   static Status CreateLanes(const NeedleHipLaneFormat *formats, size_t lanes, uint32_t step, std::unique_ptr<Feeder> *out);
   Status LaneFormat(size_t lane, NeedleHipLaneFormat *format) const;
   Status ResetFormat(const size_t *lanes, const NeedleHipLaneFormat *formats, size_t k);
+  // lanes[j] folds its channels with mixes[j] (channels == 0: the plain average again): CreateLanes' feeder only, and
+  // only lanes that hold no samples; all checked before any lane changes.  ResetFormat clears a lane's mix.  While any
+  // lane has a mix, a round lands its staged spans with rematrix_kernel instead of feeder_ingest_kernel.
+  Status SetLaneMix(const size_t *lanes, const NeedleHipChannelMix *mixes, size_t k);
   ~Feeder();
   size_t lanes() const;
   uint32_t step() const;

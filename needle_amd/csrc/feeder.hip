@@ -20,7 +20,9 @@
 //              chunks copied straight, all others staged raw and reduced by one feeder_ingest_kernel launch whatever
 //              the mixture (convert.hip); the resampler then runs once per distinct rate among the lanes that
 //              complete tiles.  Stereo loses nothing by it: every reader of a stereo tail starts with the same
-//              integer (L + R) / 2.
+//              integer (L + R) / 2.  Lanes of such a feeder may have a channel mix (SetLaneMix); while any has one, the
+//              staged chunks of a round land through one rematrix_kernel launch instead (rematrix.hip), the lanes
+//              without a mix by the same ingest_block.
 //   fingerprint gpu_fingerprint_feed_device (fingerprint.hip): the first pass over the NEW frame pairs only, behind the
 //              carried rows; certification, recomputation and fix-up over carried + new.  Frame pairs are the
 //              one-shot's (2p, 2p + 1): the tail starts at an even frame and a trailing odd frame waits for its partner
@@ -150,6 +152,8 @@ struct Feeder::Impl {
     bool direct = true;  // chunks are copied straight behind the tails: s16 of 1-2 channels (mixed: s16 mono)
     size_t planes = 1, width = 2;
     size_t first_plane = 0;  // the lane's first pointer in feed's array
+    bool has_mix = false;    // SetLaneMix: the lane is folded by `mix` as it lands (never direct then)
+    NeedleHipChannelMix mix{};
   };
   std::vector<Format> fmt;
   std::map<int, ResampleTiling> tilings;  // of the distinct rates other than 11025 Hz, as counted when the lanes were made
@@ -370,6 +374,8 @@ struct Feeder::Impl {
     std::vector<ConvertSpan> cspans;
     std::vector<DownmixSpan> mspans;
     std::vector<IngestSpan> ispans;
+    bool any_mix = false;  // a lane of the feeder has a channel mix: every staged span lands through rematrix.hip
+    for (const Format &f : fmt) any_mix = any_mix || f.has_mix;
     for (size_t i = 0; i < n; i++) {
       const Chunk &c = chunks[i];
       const Plan &p = plan[i];
@@ -396,6 +402,7 @@ struct Feeder::Impl {
         in.frames = c.frames;
         in.channels = f.channels;
         in.format = f.format;
+        in.mix = f.has_mix ? &f.mix : nullptr;
         ispans.push_back(in);
       } else if (f.format == NEEDLE_HIP_SAMPLE_S16) {
         mspans.push_back(DownmixSpan{raw.ptr + p.raw_off, dst, c.frames});
@@ -407,7 +414,7 @@ struct Feeder::Impl {
     // (cspans and mspans: Create's feeder, every lane in the format of lane 0)
     if (!cspans.empty() && !(s = gpu_convert_device(cspans, fmt[0].channels, fmt[0].format, fmt[0].channels > 2, false)).ok()) return s;
     if (!mspans.empty() && !(s = gpu_downmix_device(mspans, fmt[0].channels, false)).ok()) return s;
-    if (!ispans.empty() && !(s = gpu_ingest_device(ispans, false)).ok()) return s;
+    if (!ispans.empty() && !(s = any_mix ? gpu_rematrix_device(ispans, false) : gpu_ingest_device(ispans, false)).ok()) return s;
     // the whole tiles whose taps lie inside the samples fed, behind the 11025 Hz tails: the resampler's plan and tile
     // shape belong to a rate, so one launch per distinct rate among the lanes that complete tiles
     for (const auto &known : tilings) {
@@ -563,6 +570,27 @@ Status Feeder::ResetFormat(const size_t *lanes, const NeedleHipLaneFormat *forma
     for (size_t j = 0; j < k; j++) m.fmt[lanes[j]] = made[j];
   m.use_formats();
   return s;
+}
+
+Status Feeder::SetLaneMix(const size_t *lanes, const NeedleHipChannelMix *mixes, size_t k) {
+  Impl &m = *impl_;
+  if (!lanes || !mixes) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
+  if (!m.mixed) return Status::Make(NeedleError_InvalidArgument, "feeder: one format for all lanes (needle_hip_feeder_new): a lane cannot have a channel mix");
+  if (!m.poison.ok()) return m.poison;
+  Status s;
+  for (size_t j = 0; j < k; j++) {  // every lane and every mix before any lane changes
+    if (lanes[j] >= m.n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+    const Lane &l = m.lanes[lanes[j]];
+    if (l.fed || l.finished) return Status::Make(NeedleError_InvalidArgument, "feeder: a lane's channel mix is set only while it holds no samples");
+    if (mixes[j].channels && !(s = channel_mix_check(mixes[j], m.fmt[lanes[j]].channels)).ok()) return s;
+  }
+  for (size_t j = 0; j < k; j++) {
+    Impl::Format &f = m.fmt[lanes[j]];
+    f.has_mix = mixes[j].channels != 0;
+    f.mix = f.has_mix ? mixes[j] : NeedleHipChannelMix{};
+    f.direct = !f.has_mix && f.format % 5 == NEEDLE_HIP_SAMPLE_S16 && f.channels == 1;  // (make_format's rule of such a feeder)
+  }
+  return Status::Ok();
 }
 
 Status Feeder::Feed(const void *const *pcm, const size_t *num_values) {

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <map>
 #include <mutex>
@@ -66,10 +67,12 @@ OverlapEvents *overlap_events() {
 
 Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channels, uint32_t step,
                               std::vector<std::vector<uint32_t>> *items, int rate, int format, const BatchUpload &upload,
-                              uint32_t *d_items_out = nullptr, const std::vector<uint64_t> *item_off_out = nullptr) {
+                              uint32_t *d_items_out = nullptr, const std::vector<uint64_t> *item_off_out = nullptr,
+                              const NeedleHipChannelMix *remix = nullptr) {
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
-  Status s = ensure_device();
-  if (!s.ok()) return s;
+  Status s;
+  if (remix && !(s = channel_mix_check(*remix, channels)).ok()) return s;  // before any device is asked for
+  if (!(s = ensure_device()).ok()) return s;
   if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
     return Status::Make(NeedleError_InvalidArgument, "fingerprint: channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
   if (step == 0) return Status::Make(NeedleError_InvalidArgument, "fingerprint: step must be >= 1");
@@ -79,9 +82,11 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
   // Another sample format than interleaved s16: the streams are uploaded as they are into d_raw (`upload` is handed
   // that arena and the streams' offsets in it) and each launch group is converted into d_pcm first (convert.hip; 3-8
   // channels with the down-mix fused in), where the s16 path would have found them
+  // A channel mix (`remix`): the streams go the same way whatever their format and channel count, s16 and 1-2 channels
+  // included, and rematrix.hip lands each launch group in d_pcm as mono
   if (!sample_format_valid(format)) return Status::Make(NeedleError_InvalidArgument, "fingerprint: unknown sample format");
-  const bool conv = format != NEEDLE_HIP_SAMPLE_S16;
-  const int pcm_channels = conv && channels > 2 ? 1 : channels;  // of what d_pcm holds
+  const bool conv = format != NEEDLE_HIP_SAMPLE_S16 || remix;
+  const int pcm_channels = conv && (channels > 2 || remix) ? 1 : channels;  // of what d_pcm holds
   const bool mix = !conv && channels > 2;
   const size_t planes = sample_format_planes(format, channels), width = sample_format_width(format);
   const size_t n = num_values.size();
@@ -178,6 +183,7 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
       int src_channels = pcm_channels;
       if (conv) {  // raw samples -> s16 (3-8 channels: mono), into d_pcm (behind the same event as the kernels it feeds)
         std::vector<ConvertSpan> cgroup;
+        std::vector<IngestSpan> rgroup;
         for (size_t k = launched; k < upto; k++) {
           ConvertSpan sp{};
           const uint64_t plane = sample_plane_units(cspans[k].n_in * (planes == 1 ? channels : 1), width);
@@ -185,8 +191,18 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
           sp.dst = d_pcm.ptr + cspans[k].out_off;
           sp.frames = cspans[k].n_in;
           cgroup.push_back(sp);
+          if (remix) {
+            IngestSpan in{};
+            std::memcpy(in.src, sp.src, sizeof(in.src));
+            in.dst = sp.dst;
+            in.frames = sp.frames;
+            in.channels = channels;
+            in.format = format;
+            in.mix = remix;
+            rgroup.push_back(in);
+          }
         }
-        gs = gpu_convert_device(cgroup, channels, format, channels > 2, false);
+        gs = remix ? gpu_rematrix_device(rgroup, false) : gpu_convert_device(cgroup, channels, format, channels > 2, false);
       }
       if (mix) {  // C-channel PCM -> mono, into d_mixed (behind the same event as the kernels it feeds)
         std::vector<DownmixSpan> mgroup;
@@ -252,7 +268,8 @@ Status gpu_fingerprint_host(const std::vector<const int16_t *> &pcm, const std::
 }
 
 Status gpu_fingerprint_streamed(const std::vector<size_t> &num_values, const PcmReader &read, unsigned readers,
-                                int channels, uint32_t step, std::vector<std::vector<uint32_t>> *items, int rate) {
+                                int channels, uint32_t step, std::vector<std::vector<uint32_t>> *items, int rate,
+                                const NeedleHipChannelMix *mix) {
   return fingerprint_in_batches(
       num_values, channels, step, items, rate, NEEDLE_HIP_SAMPLE_S16,
       [&](size_t begin, size_t end, const std::vector<uint64_t> &in_off, int16_t *d_pcm, hipStream_t up,
@@ -262,7 +279,8 @@ Status gpu_fingerprint_streamed(const std::vector<size_t> &num_values, const Pcm
         };
         return gpu_upload_pcm_streamed(std::vector<size_t>(num_values.begin() + begin, num_values.begin() + end), in_off,
                                        shifted, readers, d_pcm, up, issued);
-      });
+      },
+      nullptr, nullptr, mix);
 }
 
 Status gpu_fingerprint_streamed_device(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values,
@@ -299,28 +317,30 @@ BatchUpload raw_upload(const std::vector<const void *> &pcm, const std::vector<s
 }  // namespace
 
 Status gpu_fingerprint_host_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels,
-                                   int format, uint32_t step, std::vector<std::vector<uint32_t>> *items, int rate) {
+                                   int format, uint32_t step, std::vector<std::vector<uint32_t>> *items, int rate,
+                                   const NeedleHipChannelMix *mix) {
   if (!sample_format_valid(format) || channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
     return Status::Make(NeedleError_InvalidArgument, "fingerprint: unknown sample format or channel count");
   if (pcm.size() != num_values.size() * sample_format_planes(format, channels))
     return Status::Make(NeedleError_InvalidArgument, "fingerprint: one length per stream and one pointer per plane are required");
-  if (format == NEEDLE_HIP_SAMPLE_S16) {
+  if (format == NEEDLE_HIP_SAMPLE_S16 && !mix) {
     std::vector<const int16_t *> s16(pcm.size());
     for (size_t i = 0; i < pcm.size(); i++) s16[i] = static_cast<const int16_t *>(pcm[i]);
     return gpu_fingerprint_host(s16, num_values, channels, step, items, rate);
   }
-  return fingerprint_in_batches(num_values, channels, step, items, rate, format, raw_upload(pcm, num_values, channels, format));
+  return fingerprint_in_batches(num_values, channels, step, items, rate, format, raw_upload(pcm, num_values, channels, format), nullptr,
+                                nullptr, mix);
 }
 
 Status gpu_fingerprint_streamed_device_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values,
                                               int channels, int format, uint32_t step, uint32_t *d_items,
-                                              const std::vector<uint64_t> &item_off, int rate) {
+                                              const std::vector<uint64_t> &item_off, int rate, const NeedleHipChannelMix *mix) {
   if (!sample_format_valid(format) || channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
     return Status::Make(NeedleError_InvalidArgument, "fingerprint: unknown sample format or channel count");
   if (pcm.size() != num_values.size() * sample_format_planes(format, channels) || item_off.size() != num_values.size())
     return Status::Make(NeedleError_InvalidArgument, "fingerprint: one length and one item offset per stream, one pointer per plane are required");
   return fingerprint_in_batches(num_values, channels, step, nullptr, rate, format, raw_upload(pcm, num_values, channels, format),
-                                d_items, &item_off);
+                                d_items, &item_off, mix);
 }
 
 }  // namespace needle

@@ -452,7 +452,10 @@ Status wav_probe(const std::string &path, WavInfo *out) {
       out->channels = u16(fmt + 2);
       out->sample_rate = (int)u32(fmt + 4);
       out->bits = u16(fmt + 14);
-      if (out->format == 0xFFFE && len >= 26) out->format = u16(fmt + 24);  // WAVE_FORMAT_EXTENSIBLE sub-format
+      if (out->format == 0xFFFE && len >= 26) {  // WAVE_FORMAT_EXTENSIBLE: dwChannelMask, then the sub-format
+        out->channel_mask = u32(fmt + 20);
+        out->format = u16(fmt + 24);
+      }
       have_fmt = true;
     } else if (std::memcmp(ch, "data", 4) == 0) {
       if (!have_fmt) break;
@@ -504,6 +507,49 @@ Status wav_read(const std::string &path, WavData *out) {
   out->sample_rate = info.sample_rate;
   out->pcm.resize((size_t)info.frames * (size_t)info.channels);
   return wav_read_frames(path, info, 0, info.frames, out->pcm.data());
+}
+
+// ---- channel mixes (include/needle_hip.h "Channel mixes"): the host arithmetic -------------------------------------
+Status channel_mix_check(const NeedleHipChannelMix &mix, int channels) {
+  if (mix.channels < 1 || mix.channels > NEEDLE_HIP_MAX_CHANNELS)
+    return Status::Make(NeedleError_InvalidArgument, "channel mix: channels must be 1 to " + std::to_string(NEEDLE_HIP_MAX_CHANNELS));
+  if (mix.channels != channels)
+    return Status::Make(NeedleError_InvalidArgument, "channel mix: a mix for " + std::to_string(mix.channels) + " channels given to " +
+                                                         std::to_string(channels) + "-channel PCM");
+  for (int o = 0; o < 2; o++) {
+    int64_t sum = 0;
+    for (int c = 0; c < mix.channels; c++) {
+      const int64_t v = mix.coef[o][c];
+      if (v < -32768 || v > 32768) return Status::Make(NeedleError_InvalidArgument, "channel mix: a coefficient must lie in [-32768, 32768]");
+      sum += v < 0 ? -v : v;
+    }
+    if (sum > 65535) return Status::Make(NeedleError_InvalidArgument, "channel mix: a row's sum of |coefficients| must not exceed 65535");
+  }
+  return Status::Ok();
+}
+
+Status channel_mix_default(uint32_t channel_mask, NeedleHipChannelMix *out) {
+  if (!out) return Status::Make(NeedleError_NullArgument, "channel mix: null argument");
+  const int channels = __builtin_popcount(channel_mask);
+  if (channel_mask > 0x7FFu || channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS)
+    return Status::Make(NeedleError_InvalidArgument, "channel mix: no default for this channel mask (bits 0x1..0x400, 1 to 8 of them)");
+  const double h = std::sqrt(0.5);
+  // {to the left, to the right} of FL FR FC LFE BL BR FLC FRC BC SL SR
+  const double weight[11][2] = {{1, 0}, {0, 1}, {h, h}, {0, 0}, {h, 0}, {0, h}, {1, 0}, {0, 1}, {0.5, 0.5}, {h, 0}, {0, h}};
+  double m[2][NEEDLE_HIP_MAX_CHANNELS] = {}, sum[2] = {0, 0};
+  int c = 0;
+  for (int bit = 0; bit < 11; bit++) {
+    if (!(channel_mask >> bit & 1)) continue;
+    for (int o = 0; o < 2; o++) sum[o] += m[o][c] = weight[bit][o];
+    c++;
+  }
+  const double norm = std::max(1.0, std::max(sum[0], sum[1]));
+  NeedleHipChannelMix mix{};
+  mix.channels = channels;
+  for (int o = 0; o < 2; o++)
+    for (c = 0; c < channels; c++) mix.coef[o][c] = (int32_t)std::floor(m[o][c] / norm * 32768.0 + 0.5);
+  *out = mix;
+  return Status::Ok();
 }
 
 unsigned usable_cpus() {

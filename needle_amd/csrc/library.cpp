@@ -54,6 +54,8 @@ struct NeedleHipLibrary {
   int channels = 1;            // of the resident PCM (1 whenever it was down-mixed or resampled on the way in)
   int rate = kSampleRate;      // of the callers' PCM (needle_hip_library_set_sample_rate); the resident PCM is 11025 Hz
   int format = NEEDLE_HIP_SAMPLE_S16;  // of the callers' PCM (needle_hip_library_set_sample_format); the resident PCM is s16
+  bool has_mix = false;                // needle_hip_library_set_channel_mix: the callers' PCM is folded to mono by `mix` on the way in
+  NeedleHipChannelMix mix{};
   bool have_pcm = false;      // windows and arena are set up (set_pcm or stream_pcm)
   bool pcm_resident = false;  // set_pcm: the PCM stays in HBM and analyze can be repeated
   std::vector<Window> win;  // [video * regions() + region]
@@ -296,9 +298,26 @@ enum NeedleError needle_hip_library_set_sample_format(NeedleHipLibrary *lib, int
   return NeedleError_Ok;
 }
 
+enum NeedleError needle_hip_library_set_channel_mix(NeedleHipLibrary *lib, const NeedleHipChannelMix *mix) {
+  if (!lib) return NeedleError_NullArgument;
+  if (lib->have_pcm) return NeedleError_InvalidArgument;  // must precede set_pcm
+  if (mix) {
+    Status s = channel_mix_check(*mix, mix->channels);
+    if (!s.ok()) return report(s);
+    lib->mix = *mix;
+  }
+  lib->has_mix = mix != nullptr;
+  return NeedleError_Ok;
+}
+
 }  // extern "C"
 
 namespace {
+// the channel count of a set_pcm / set_pcm_device / stream_pcm call against the library's mix, before any device is asked for
+Status check_mix_channels(const NeedleHipLibrary *lib, int channels) {
+  return lib->has_mix ? channel_mix_check(lib->mix, channels) : Status::Ok();
+}
+
 // Samples a window of `count` samples at `rate` keeps resident (11025 Hz).
 size_t resident_samples(size_t count, int rate) { return rate == kSampleRate ? count : resample_out_len(count, rate); }
 
@@ -309,19 +328,20 @@ size_t resident_samples(size_t count, int rate) { return rate == kSampleRate ? c
 // at any rate other than 11025 Hz are kept resident as 11025 Hz mono (down-mixed and resampled on the way in), so
 // lib->channels and the windows' `values` describe the arena, not the input; `len` is the input's.  The samples are in
 // lib->format: `pcm` holds one pointer per video, or -- planar -- one per channel of every video, and `src` gets as many
-// per window (anything but interleaved s16 is converted on the way in, 3-8 channels to mono by the same kernel).
+// per window (anything but interleaved s16 is converted on the way in, 3-8 channels to mono by the same kernel; with a
+// channel mix everything goes that way and arrives as mono, rematrix.hip).
 Status plan_windows(NeedleHipLibrary *lib, const void *const *pcm, const size_t *num_values, int channels, bool resident,
                     std::vector<const void *> *src, std::vector<size_t> *len, std::vector<uint64_t> *dst,
                     std::vector<uint64_t> *rows_of_src, uint64_t *total_values) {
   Status s = ensure_device();
   if (!s.ok()) return s;
-  const bool resampled = lib->rate != kSampleRate, converted = lib->format != NEEDLE_HIP_SAMPLE_S16;
+  const bool resampled = lib->rate != kSampleRate, converted = lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix;
   const size_t planes = sample_format_planes(lib->format, channels), width = sample_format_width(lib->format);
   for (size_t v = 0; v < lib->n; v++)  // a video is held with all its planes or with none
     for (size_t c = 1; c < planes; c++)
       if (!pcm[v * planes + c] != !pcm[v * planes])
         return Status::Make(NeedleError_NullArgument, "video " + std::to_string(v) + " has NULL and non-NULL planes");
-  lib->channels = channels > 2 || resampled ? 1 : channels;
+  lib->channels = channels > 2 || resampled || lib->has_mix ? 1 : channels;
   const size_t R = lib->regions();
   lib->win.assign(lib->rows(), Window{});
   uint64_t total = 0;
@@ -542,10 +562,12 @@ std::vector<const int16_t *> as_s16(const std::vector<const void *> &src) {
 // (2 GiB; NEEDLE_HIP_MAX_BATCH_VALUES counts values, for tests): a window is cut into pieces of whole 16-frame groups or,
 // resampled, of whole output tiles with the input their taps read, as upload_resampled does.  `src` holds
 // sample_format_planes() pointers per window.  All in library-stream order; the caller synchronises.
+// With a channel mix (lib->has_mix) this is the way in for every format and channel count, interleaved s16 and 1-2
+// channels included: rematrix.hip takes the conversion's place and its output is mono.
 Status upload_converted(NeedleHipLibrary *lib, const std::vector<const void *> &src, const std::vector<size_t> &len,
                         const std::vector<uint64_t> &dst, int channels, bool from_host, DeviceBuffer<int16_t> *stage) {
   const int format = lib->format, rate = lib->rate;
-  const bool resampled = rate != kSampleRate, mix = channels > 2;
+  const bool resampled = rate != kSampleRate, mix = channels > 2 || lib->has_mix;
   const int out_channels = mix ? 1 : channels;  // of the converted s16
   const uint64_t C = (uint64_t)channels, OC = (uint64_t)out_channels, W = sample_format_width(format);
   const size_t P = sample_format_planes(format, channels);
@@ -603,7 +625,22 @@ Status upload_converted(NeedleHipLibrary *lib, const std::vector<const void *> &
   uint64_t used = 0;
   auto flush = [&]() -> Status {  // the next group's copies follow these kernels in stream order
     Status fs = up_src.empty() ? Status::Ok() : gpu_upload_raw(up_src, up_bytes, up_off, stage->ptr);
-    if (fs.ok() && !convert.empty()) fs = gpu_convert_device(convert, channels, format, mix, false);
+    if (fs.ok() && !convert.empty() && lib->has_mix) {
+      std::vector<IngestSpan> fold;
+      for (const ConvertSpan &cv : convert) {
+        IngestSpan in{};
+        std::memcpy(in.src, cv.src, sizeof(in.src));
+        in.dst = cv.dst;
+        in.frames = cv.frames;
+        in.channels = channels;
+        in.format = format;
+        in.mix = &lib->mix;
+        fold.push_back(in);
+      }
+      fs = gpu_rematrix_device(fold, false);
+    } else if (fs.ok() && !convert.empty()) {
+      fs = gpu_convert_device(convert, channels, format, mix, false);
+    }
     if (fs.ok() && !spans.empty()) fs = gpu_resample_device(nullptr, spans, out_channels, rate, lib->d_pcm.ptr, false);
     up_src.clear();
     up_bytes.clear();
@@ -661,12 +698,13 @@ enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t
     std::vector<size_t> len;
     std::vector<uint64_t> dst;
     uint64_t total = 0;
-    Status s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total);
+    Status s = check_mix_channels(lib, channels);
+    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
     DeviceBuffer<int16_t> stage;  // (3-8 channels, another rate or another sample format; freed after the drain below)
     const std::vector<const int16_t *> src = as_s16(planes);
-    s = lib->format != NEEDLE_HIP_SAMPLE_S16 ? upload_converted(lib, planes, len, dst, channels, true, &stage)
+    s = lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix ? upload_converted(lib, planes, len, dst, channels, true, &stage)
         : lib->rate != kSampleRate           ? upload_resampled(lib, src, len, dst, channels, true, &stage)
         : channels > 2                       ? upload_mixed(lib, src, len, dst, channels, &stage)
                                              : gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
@@ -689,13 +727,14 @@ enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const 
     std::vector<size_t> len;
     std::vector<uint64_t> dst;
     uint64_t total = 0;
-    Status s = plan_windows(lib, reinterpret_cast<const void *const *>(d_pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total);
+    Status s = check_mix_channels(lib, channels);
+    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(d_pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
     hipStream_t stream = library_stream();
     DeviceBuffer<int16_t> stage;  // (3-8 channels at another rate; freed after the drain below)
     const std::vector<const int16_t *> src = as_s16(planes);
-    if (lib->format != NEEDLE_HIP_SAMPLE_S16) {  // converted (down-mixed, resampled) straight out of the caller's buffers
+    if (lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix) {  // converted (down-mixed or folded, resampled) straight out of the caller's buffers
       s = upload_converted(lib, planes, len, dst, channels, false, &stage);
       const bool drained = hipStreamSynchronize(stream) == hipSuccess;
       if (!s.ok()) return report(s);
@@ -730,13 +769,15 @@ enum NeedleError needle_hip_library_stream_pcm(NeedleHipLibrary *lib, const int1
     std::vector<size_t> len;
     std::vector<uint64_t> rows;
     const auto t0 = std::chrono::steady_clock::now();
-    Status s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, false, &planes, &len, nullptr, &rows, nullptr);
+    Status s = check_mix_channels(lib, channels);
+    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, false, &planes, &len, nullptr, &rows, nullptr);
     if (!s.ok()) return report(s);
     for (uint64_t &r : rows) r *= lib->stride;  // kept items of a window go straight to its arena row
     const auto t1 = std::chrono::steady_clock::now();
     const std::vector<const int16_t *> src = as_s16(planes);
-    s = lib->format != NEEDLE_HIP_SAMPLE_S16
-            ? gpu_fingerprint_streamed_device_format(planes, len, channels, lib->format, lib->step, lib->arena, rows, lib->rate)
+    s = lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix
+            ? gpu_fingerprint_streamed_device_format(planes, len, channels, lib->format, lib->step, lib->arena, rows, lib->rate,
+                                                     lib->has_mix ? &lib->mix : nullptr)
             : gpu_fingerprint_streamed_device(src, len, channels, lib->step, lib->arena, rows, lib->rate);
     if (!s.ok()) return report(s);
     if (getenv("NEEDLE_HIP_TRACE"))

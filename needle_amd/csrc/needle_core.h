@@ -40,6 +40,14 @@ class Analyzer {
   Analyzer &with_include_endings(bool v) { include_endings_ = v; return *this; }                       // :136
   Analyzer &with_threaded_decoding(bool v) { threaded_decoding_ = v; return *this; }                   // :142
   Analyzer &with_force(bool v) { force_ = v; return *this; }                                           // :148
+  // Channel mixes (needle_hip.h): run_pcm / run_pcm_format fold their C-channel PCM with `mix` (checked by the caller;
+  // nullptr: the plain average again); run folds every file that carries a channel mask with that mask's default mix.
+  Analyzer &with_channel_mix(const NeedleHipChannelMix *mix) {
+    has_mix_ = mix != nullptr;
+    if (mix) mix_ = *mix;
+    return *this;
+  }
+  Analyzer &with_layout_downmix(bool v) { layout_downmix_ = v; return *this; }
 
   // Analyzer::run (:425): every video is a RIFF/WAVE file here (decode is out of scope).  Only the search
   // windows are read from each file, streamed to the GPU through a fixed ring of pinned slabs, one device
@@ -71,6 +79,8 @@ class Analyzer {
   bool include_endings_ = false;
   bool threaded_decoding_ = false;
   bool force_ = false;
+  bool has_mix_ = false, layout_downmix_ = false;
+  NeedleHipChannelMix mix_{};
 };
 
 struct SearchResult {  // comparator.rs:65-69
@@ -99,6 +109,7 @@ class Comparator {
   static Comparator from_analyzer(const Analyzer &a);                             // :96-104
   const std::vector<std::string> &videos() const { return videos_; }              // :115
   Comparator &with_include_endings(bool v) { include_endings_ = v; return *this; }            // :120
+  Comparator &with_layout_downmix(bool v) { layout_downmix_ = v; return *this; }  // of run's own Analyzer (`analyze`)
   Comparator &with_hash_match_threshold(uint32_t v) { hash_match_threshold_ = v; return *this; }  // :126
   Comparator &with_min_opening_duration(ns_t v) { min_opening_duration_ = v; return *this; }   // :132
   Comparator &with_min_ending_duration(ns_t v) { min_ending_duration_ = v; return *this; }     // :138
@@ -155,6 +166,7 @@ class Comparator {
  private:
   std::vector<std::string> videos_;
   bool include_endings_ = false;
+  bool layout_downmix_ = false;
   uint32_t hash_match_threshold_ = DEFAULT_HASH_MATCH_THRESHOLD;
   ns_t min_opening_duration_ = (ns_t)DEFAULT_MIN_OPENING_DURATION * kNanosPerSec;
   ns_t min_ending_duration_ = (ns_t)DEFAULT_MIN_ENDING_DURATION * kNanosPerSec;

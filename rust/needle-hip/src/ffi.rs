@@ -111,6 +111,33 @@ pub struct NeedleHipLaneFormat {
     pub format: i32,
 }
 
+/// A channel mix: a 2 x C matrix of Q15 integers, `coef[0][c]` to the left output and `coef[1][c]` to the right
+/// (`needle_hip.h`, "Channel mixes").  `channels == 0` stands for "no mix" where an array of mixes is passed.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct NeedleHipChannelMix {
+    pub(crate) channels: i32,
+    pub(crate) coef: [[i32; 8]; 2],
+}
+
+impl NeedleHipChannelMix {
+    /// The mix of `left.len()` channels with these two rows (at most 8 coefficients each).
+    pub fn new(left: &[i32], right: &[i32]) -> Self {
+        assert!(left.len() == right.len() && left.len() <= 8, "two rows of at most 8 coefficients each");
+        let mut m = Self { channels: left.len() as i32, coef: [[0; 8]; 2] };
+        m.coef[0][..left.len()].copy_from_slice(left);
+        m.coef[1][..right.len()].copy_from_slice(right);
+        m
+    }
+    pub fn channels(&self) -> i32 {
+        self.channels
+    }
+    /// The left (0) or right (1) row, `channels` coefficients.
+    pub fn row(&self, output: usize) -> &[i32] {
+        &self.coef[output][..self.channels.clamp(0, 8) as usize]
+    }
+}
+
 extern "C" {
     // ---- needle.h ------------------------------------------------------------------------------------
     pub fn needle_error_to_str(error: NeedleError) -> *const c_char;
@@ -379,6 +406,25 @@ extern "C" {
         formats: *const NeedleHipLaneFormat,
         num_streams: usize,
         out: *const *mut i16,
+    ) -> NeedleError;
+    pub fn needle_hip_channel_mix_default(channel_mask: u32, out: *mut NeedleHipChannelMix) -> NeedleError;
+    pub fn needle_hip_rematrix_host(
+        pcm: *const *const c_void,
+        num_values: *const usize,
+        formats: *const NeedleHipLaneFormat,
+        mixes: *const NeedleHipChannelMix,
+        num_streams: usize,
+        out: *const *mut i16,
+    ) -> NeedleError;
+    pub fn needle_hip_analyzer_set_channel_mix(analyzer: *mut NeedleAudioAnalyzer, mix: *const NeedleHipChannelMix) -> NeedleError;
+    pub fn needle_hip_analyzer_set_layout_downmix(analyzer: *mut NeedleAudioAnalyzer, on: bool) -> NeedleError;
+    pub fn needle_hip_comparator_set_layout_downmix(comparator: *mut NeedleAudioComparator, on: bool) -> NeedleError;
+    pub fn needle_hip_library_set_channel_mix(library: *mut NeedleHipLibrary, mix: *const NeedleHipChannelMix) -> NeedleError;
+    pub fn needle_hip_feeder_set_lane_mix(
+        feeder: *mut NeedleHipFeeder,
+        lanes: *const usize,
+        mixes: *const NeedleHipChannelMix,
+        k: usize,
     ) -> NeedleError;
     pub fn needle_hip_feeder_free(feeder: *mut NeedleHipFeeder);
     pub fn needle_hip_feeder_feed(feeder: *mut NeedleHipFeeder, pcm: *const *const c_void, num_values: *const usize) -> NeedleError;

@@ -500,6 +500,13 @@ impl Feeder {
         Ok(f)
     }
 
+    /// `lanes[j]` folds its channels with `mixes[j]` (`ChannelMix::default()`, channels 0: the plain average again);
+    /// only on a feeder made by `with_formats`, and only lanes that hold no samples (`needle_hip_feeder_set_lane_mix`).
+    pub fn set_lane_mix(&mut self, lanes: &[usize], mixes: &[ChannelMix]) -> Result<()> {
+        assert_eq!(lanes.len(), mixes.len(), "one mix per lane");
+        unsafe { check(ffi::needle_hip_feeder_set_lane_mix(self.raw, lanes.as_ptr(), mixes.as_ptr(), lanes.len())) }
+    }
+
     /// `lanes[j]` starts a new stream in `formats[j]`; only on a feeder made by `with_formats`.
     pub fn reset_format(&mut self, lanes: &[usize], formats: &[LaneFormat]) -> Result<()> {
         assert_eq!(lanes.len(), formats.len(), "one format per lane");
@@ -1047,6 +1054,35 @@ pub fn convert<T: Sample>(pcm: &[&[T]], channels: i32, planar: bool) -> Result<V
     Ok(out)
 }
 
+/// A channel mix (`needle_hip.h`, "Channel mixes"): the layout-aware fold-down to stereo, then mono.
+pub use ffi::NeedleHipChannelMix as ChannelMix;
+
+/// `needle_hip_channel_mix_default`: the default mix of a WAVEFORMATEXTENSIBLE / FFmpeg channel mask (host arithmetic).
+pub fn channel_mix_default(channel_mask: u32) -> Result<ChannelMix> {
+    let mut mix = ChannelMix::default();
+    unsafe { check(ffi::needle_hip_channel_mix_default(channel_mask, &mut mix))? };
+    Ok(mix)
+}
+
+/// `needle_hip_rematrix_host`: `convert_mono` with a channel mix per stream (channels 0: the plain average of that
+/// stream), one launch of the rematrix kernel whatever the mixture.
+pub fn rematrix(pcm: &[&[&[u8]]], formats: &[LaneFormat], mixes: &[ChannelMix]) -> Result<Vec<Vec<i16>>> {
+    assert!(pcm.len() == formats.len() && pcm.len() == mixes.len(), "one format and one mix per stream");
+    let (mut ptrs, mut lens) = (Vec::new(), Vec::with_capacity(pcm.len()));
+    for (planes, f) in pcm.iter().zip(formats) {
+        assert_eq!(planes.len(), format_planes(f), "one slice per plane of the stream");
+        let width = [1usize, 2, 4, 4, 8][(f.format % 5) as usize];
+        ptrs.extend(planes.iter().map(|s| s.as_ptr() as *const std::os::raw::c_void));
+        lens.push(planes.iter().map(|p| p.len() / width).sum::<usize>());
+    }
+    let mut out: Vec<Vec<i16>> = lens.iter().zip(formats).map(|(n, f)| vec![0i16; n / f.channels.max(1) as usize]).collect();
+    let optrs: Vec<*mut i16> = out.iter_mut().map(|o| o.as_mut_ptr()).collect();
+    unsafe {
+        check(ffi::needle_hip_rematrix_host(ptrs.as_ptr(), lens.as_ptr(), formats.as_ptr(), mixes.as_ptr(), formats.len(), optrs.as_ptr()))?;
+    }
+    Ok(out)
+}
+
 /// `needle_hip_convert_mono_host`: streams that each have a format of their own -> mono s16 (`convert`, then `downmix`, in
 /// one kernel whatever the mixture).  Per stream the raw bytes of its planes, as in `Feeder::feed_lanes`; the formats'
 /// sample rates are not looked at.
@@ -1076,7 +1112,7 @@ pub fn frame_hash_path(video: impl AsRef<Path>) -> PathBuf {
 /// (analyzer.rs:437-445 over videos, comparator.rs:549-564 over pairs) is spread over the ranks of a communicator
 /// inside libneedle_capi.so: RCCL all-gathers on the library's own streams, no host round trips inside a job.
 pub mod multi_gpu {
-    use super::{check, ffi, Comparator, Result, Sample, SampleFormat, SearchResult};
+    use super::{check, ffi, ChannelMix, Comparator, Result, Sample, SampleFormat, SearchResult};
     use std::os::raw::c_int;
     use std::time::Duration;
 
@@ -1130,6 +1166,14 @@ pub mod multi_gpu {
         pub fn set_sample_rate(&mut self, sample_rate: u32) -> Result<&mut Self> {
             let rate = c_int::try_from(sample_rate).unwrap_or(c_int::MAX);
             unsafe { check(ffi::needle_hip_library_set_sample_rate(self.raw, rate))? };
+            Ok(self)
+        }
+
+        /// The PCM loaded afterwards is folded to mono with `mix` on the way in (`needle_hip_library_set_channel_mix`;
+        /// `None`: the plain average again).  Call before loading.
+        pub fn set_channel_mix(&mut self, mix: Option<&ChannelMix>) -> Result<&mut Self> {
+            let ptr = mix.map_or(std::ptr::null(), |m| m as *const ChannelMix);
+            unsafe { check(ffi::needle_hip_library_set_channel_mix(self.raw, ptr))? };
             Ok(self)
         }
 
