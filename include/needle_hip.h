@@ -715,6 +715,55 @@ enum NeedleError needle_hip_library_set_channel_mix(NeedleHipLibrary *library, c
  * launches what it always did. */
 enum NeedleError needle_hip_feeder_set_lane_mix(NeedleHipFeeder *feeder, const size_t *lanes, const NeedleHipChannelMix *mixes, size_t k);
 
+/* ---- A lane changes format in mid-stream, the fingerprint goes on ------------------------------------------
+ * A decoder may report another rate, layout or sample format in the middle of a stream (a 5.1 programme among stereo
+ * bumpers, a part muxed from another source); the reference then swaps its resampler and keeps feeding the SAME
+ * chromaprint context (analyzer.rs:231-255, :275).  switch_format is that swap: lanes[j] ends its current SEGMENT and
+ * continues its same stream in formats[j], folded by mixes[j] (mixes NULL, or mixes[j].channels == 0: the plain average;
+ * the previous segment's mix ends with it).  A switch always begins a new segment, even when nothing changes.
+ *
+ * The lane's 11025 Hz mono signal is the concatenation of its segments, each landed and resampled as a whole stream of
+ * its own: needle_hip_convert_host's rule per sample, needle_hip_downmix_host's average or needle_hip_rematrix_host's mix
+ * per frame and, at any rate but 11025 Hz, needle_hip_resample_host -- ceil(n L / M) outputs for the segment's n frames,
+ * the taps before its first and after its last sample zero.  The fingerprinter sees that concatenation as ONE stream:
+ * frames, frame pairs, carried rows, the latency, step, certification, recomputation and the audit run across the
+ * junction, and items emitted before a switch are never revised.  After `finish` the lane's items are bit for bit those
+ * of needle_hip_fingerprint_host over the concatenated mono PCM, however the segments were cut into feeds, also under
+ * NEEDLE_HIP_STFT=f64.  (The reference's swresample drops the old resampler's buffered tail at the swap; this front end
+ * flushes it.  The difference is a fraction of a millisecond of audio and is this front end's own specification, as the
+ * resampler's is.)
+ *
+ * Only on a feeder made by needle_hip_feeder_new_lanes (one made by needle_hip_feeder_new: InvalidArgument).  Before any
+ * lane changes, every entry is checked: the lane's range, the format's limits, that the resampler has a design for the
+ * rate, the mix against the new channel count, that the lane is not finished, and that no lane is named twice -- else
+ * InvalidArgument and nothing has changed, not for lanes named earlier in the call either.  NULL handle, lanes or
+ * formats: NullArgument.  A poisoned feeder returns its error.
+ *
+ * Lanes whose open segment resamples and holds samples are flushed by ONE round for all of them together, without new
+ * chunks: the segment's remaining output tiles are computed with its end known, then its source tail is dropped.  The
+ * lane is not finished by that: a trailing odd frame waits on for its partner, which may come from the next segment.
+ * A switch of lanes at 11025 Hz, or of lanes whose open segment is empty, launches nothing and needs no device.
+ *
+ * Afterwards lane_format answers with the open segment's format; ready's samples_per_channel_fed is the sum of the
+ * segments' frames and its kept_items equals needle_hip_feeder_num_ready_segments(lane_segments, step, finished) after
+ * every call (for a lane that never switched that is needle_hip_feeder_num_ready, unchanged); state_bytes' bytes[0]
+ * stays within the mono bound of the larger of the rates.  reset and reset_format clear the list of segments.  A lane
+ * "holds samples" for set_audit and set_lane_mix while any segment of its current stream does: after a switch both are
+ * refused as in mid-stream, although the open segment is empty (a segment's mix is given to switch_format).  A format
+ * change inside one chunk is the caller's to split: switch between two feeds. */
+enum NeedleError needle_hip_feeder_switch_format(NeedleHipFeeder *feeder, const size_t *lanes, const NeedleHipLaneFormat *formats,
+                                                 const NeedleHipChannelMix *mixes, size_t k);
+typedef struct NeedleHipSegment {
+  NeedleHipLaneFormat format;
+  uint64_t frames; /* samples per channel fed in that format */
+} NeedleHipSegment;
+/* the segments of the lane's current stream, the open one last (always at least one); *count is the number there are,
+ * at most `cap` are written (out may be NULL when cap is 0) */
+enum NeedleError needle_hip_feeder_lane_segments(const NeedleHipFeeder *feeder, size_t lane, NeedleHipSegment *out, size_t cap, size_t *count);
+/* pure host arithmetic, no device: kept items a lane holds after these segments (the last one open unless finished).
+ * 0 for no segments, step 0 or a format outside the limits (channels, sample_rate, format). */
+size_t needle_hip_feeder_num_ready_segments(const NeedleHipSegment *segments, size_t count, uint32_t step, bool finished);
+
 /* ---- Streaming comparator: search as the hashes arrive ---------------------------------------------------
  * The search half of the streaming path, the counterpart of the feeder.  A matcher holds S source sequences (the
  * openings of a season, say: the videos of an index), resident on the device from creation on, a threshold, one

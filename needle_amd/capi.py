@@ -112,6 +112,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_channel_mix_default", "needle_hip_rematrix_host", "needle_hip_analyzer_set_channel_mix",
     "needle_hip_analyzer_set_layout_downmix", "needle_hip_comparator_set_layout_downmix", "needle_hip_library_set_channel_mix",
     "needle_hip_feeder_set_lane_mix",
+    "needle_hip_feeder_switch_format", "needle_hip_feeder_lane_segments", "needle_hip_feeder_num_ready_segments",
     "needle_hip_matcher_new", "needle_hip_matcher_free", "needle_hip_matcher_feed", "needle_hip_matcher_feed_from_feeder",
     "needle_hip_matcher_finish", "needle_hip_matcher_reset", "needle_hip_matcher_ready", "needle_hip_matcher_runs",
     "needle_hip_matcher_open", "needle_hip_matcher_stats",
@@ -162,6 +163,10 @@ def _format_pointers(pcm, channels: int, sample_format: int):
 
 class CLaneFormat(C.Structure):                          # NeedleHipLaneFormat
     _fields_ = [("channels", C.c_int32), ("sample_rate", C.c_int32), ("format", C.c_int32)]
+
+
+class CSegment(C.Structure):                             # NeedleHipSegment
+    _fields_ = [("format", CLaneFormat), ("frames", C.c_uint64)]
 
 
 class ChannelMix(C.Structure):                           # NeedleHipChannelMix
@@ -386,6 +391,10 @@ def lib():
     L.needle_hip_comparator_set_layout_downmix.argtypes = [vp, b]
     L.needle_hip_library_set_channel_mix.argtypes = [vp, vp]
     L.needle_hip_feeder_set_lane_mix.argtypes = [vp, C.POINTER(sz), vp, sz]
+    L.needle_hip_feeder_switch_format.argtypes = [vp, C.POINTER(sz), vp, vp, sz]
+    L.needle_hip_feeder_lane_segments.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
+    L.needle_hip_feeder_num_ready_segments.argtypes = [vp, sz, u32, b]
+    L.needle_hip_feeder_num_ready_segments.restype = sz
     L.needle_hip_matcher_new.argtypes = [vp, sz, vp, vp, sz, sz, u32, C.POINTER(vp)]
     L.needle_hip_matcher_free.argtypes = [vp]
     L.needle_hip_matcher_free.restype = None
@@ -911,6 +920,21 @@ def feeder_num_ready(samples_per_channel_fed: int, sample_rate: int = 11025, cha
     return int(lib().needle_hip_feeder_num_ready(samples_per_channel_fed, sample_rate, channels, step, finished))
 
 
+def _segments(segments):
+    """NeedleHipSegment array of ((channels, sample_rate, sample_format), frames) pairs."""
+    arr = (CSegment * max(len(segments), 1))()
+    for i, ((c, r, f), frames) in enumerate(segments):
+        arr[i].format = CLaneFormat(int(c), int(r), int(f))
+        arr[i].frames = int(frames)
+    return arr
+
+
+def num_ready_segments(segments: Sequence[Tuple[Tuple[int, int, int], int]], step: int = 1, finished: bool = False) -> int:
+    """Kept items a Feeder lane holds after these segments, ((channels, sample_rate, sample_format), frames) each, the
+    last one open unless finished (needle_hip_feeder_num_ready_segments: host arithmetic, no device)."""
+    return int(lib().needle_hip_feeder_num_ready_segments(_segments(segments), len(segments), step, finished))
+
+
 class Feeder:
     """needle_hip_feeder_*: chromaprint's start / feed / finish batched over `lanes`, state on the device."""
 
@@ -962,6 +986,27 @@ class Feeder:
         check(lib().needle_hip_feeder_reset_format(self._h, arr, _lane_formats(formats), k))
         for lane, f in zip(lanes, formats):
             self.formats[lane] = tuple(int(v) for v in f)
+
+    def switch_format(self, lanes: Sequence[int], formats: Sequence[Tuple[int, int, int]],
+                      mixes: Optional[Sequence[Optional[ChannelMix]]] = None) -> None:
+        """lanes[j] ends its current segment and continues ITS SAME STREAM in formats[j], folded by mixes[j] (None: the
+        plain average) -- a decoder that reports another rate, layout or sample format in mid-stream
+        (needle_hip_feeder_switch_format; a with_formats feeder only)."""
+        if len(lanes) != len(formats) or (mixes is not None and len(mixes) != len(lanes)):
+            raise ValueError("one format (and one mix or None) per lane")
+        arr, k = self._lanes(list(lanes))
+        check(lib().needle_hip_feeder_switch_format(self._h, arr, _lane_formats(formats), None if mixes is None else _channel_mixes(mixes), k))
+        for lane, f in zip(lanes, formats):   # (a Feeder(...) of one format has been refused above)
+            self.formats[lane] = tuple(int(v) for v in f)
+
+    def lane_segments(self, lane: int) -> List[Tuple[Tuple[int, int, int], int]]:
+        """The segments of the lane's current stream, ((channels, sample_rate, sample_format), frames) each, the open one
+        last (needle_hip_feeder_lane_segments)."""
+        count = C.c_size_t()
+        check(lib().needle_hip_feeder_lane_segments(self._h, lane, None, 0, C.byref(count)))
+        arr = (CSegment * max(count.value, 1))()
+        check(lib().needle_hip_feeder_lane_segments(self._h, lane, arr, count.value, C.byref(count)))
+        return [((s.format.channels, s.format.sample_rate, s.format.format), int(s.frames)) for s in arr[:count.value]]
 
     def feed(self, pcm: Sequence) -> None:
         """pcm[i]: what lane i has decoded since the last feed (interleaved: one array; planar: `channels` planes), or

@@ -791,6 +791,23 @@ enum NeedleError needle_hip_feeder_set_lane_mix(NeedleHipFeeder *feeder, const s
   });
 }
 
+enum NeedleError needle_hip_feeder_switch_format(NeedleHipFeeder *feeder, const size_t *lanes, const NeedleHipLaneFormat *formats,
+                                                 const NeedleHipChannelMix *mixes, size_t k) {
+  if (!feeder || !lanes || !formats) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->SwitchFormat(lanes, formats, mixes, k);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_feeder_lane_segments(const NeedleHipFeeder *feeder, size_t lane, NeedleHipSegment *out, size_t cap, size_t *count) {
+  if (!feeder || !count || (cap && !out)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    Status s = feeder->inner->LaneSegments(lane, out, cap, count);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 void needle_hip_feeder_free(NeedleHipFeeder *feeder) { delete feeder; }
 
 enum NeedleError needle_hip_feeder_feed(NeedleHipFeeder *feeder, const void *const *pcm, const size_t *num_values) {
@@ -891,6 +908,10 @@ enum NeedleError needle_hip_feeder_audit(NeedleHipFeeder *feeder, size_t lane, N
 
 size_t needle_hip_feeder_num_ready(uint64_t samples_per_channel_fed, int sample_rate, int channels, uint32_t step, bool finished) {
   return feeder_num_ready(samples_per_channel_fed, sample_rate, channels, step, finished);
+}
+
+size_t needle_hip_feeder_num_ready_segments(const NeedleHipSegment *segments, size_t count, uint32_t step, bool finished) {
+  return feeder_num_ready_segments(segments, count, step, finished);
 }
 
 // ============================================================================================================

@@ -11,6 +11,8 @@ namespace needle {
 // Kept items a lane holds after `samples` samples per channel: host arithmetic only.  Unfinished, the first pass has
 // seen the whole frame PAIRS of the samples fed (a trailing odd frame waits for its partner); finished, every frame.
 size_t feeder_num_ready(uint64_t samples, int sample_rate, int channels, uint32_t step, bool finished);
+// The same after a stream of several segments (SwitchFormat): every segment but an open last one is resampled whole.
+size_t feeder_num_ready_segments(const NeedleHipSegment *segments, size_t count, uint32_t step, bool finished);
 
 class Feeder {
  public:
@@ -25,6 +27,13 @@ class Feeder {
   // only lanes that hold no samples; all checked before any lane changes.  ResetFormat clears a lane's mix.  While any
   // lane has a mix, a round lands its staged spans with rematrix_kernel instead of feeder_ingest_kernel.
   Status SetLaneMix(const size_t *lanes, const NeedleHipChannelMix *mixes, size_t k);
+  // lanes[j] ends its open segment and goes on with ITS SAME STREAM in formats[j] (mixes null or channels == 0: the plain
+  // average): CreateLanes' feeder only; every lane, format and mix checked before any lane changes.  The segments that
+  // resample and hold samples are flushed by one round without chunks: their last tiles computed with the end known
+  // (the segment's, not the lane's: frames stay even), then the source tails dropped.  Other switches launch nothing.
+  Status SwitchFormat(const size_t *lanes, const NeedleHipLaneFormat *formats, const NeedleHipChannelMix *mixes, size_t k);
+  // the segments of the lane's current stream, the open one last: *count of them, at most `cap` written
+  Status LaneSegments(size_t lane, NeedleHipSegment *out, size_t cap, size_t *count) const;
   ~Feeder();
   size_t lanes() const;
   uint32_t step() const;

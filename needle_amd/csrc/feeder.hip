@@ -30,6 +30,14 @@
 //   audit      only if asked for (set_audit), two more launches there: the f64 kernel over the new pairs into the audit's
 //              own rows, audit_items_kernel over carried + new; the counts stay on the device until `audit` asks.
 // Every step is one launch over all lanes (tables searched by block, as in downmix.hip / convert.hip).
+//
+// A lane's stream may change format on the way (SwitchFormat): it is then a sequence of SEGMENTS, each landed and
+// resampled as a whole stream of its own, and the fingerprinter sees their 11025 Hz signals laid end to end as one
+// stream.  Lane::seg_base is where the open segment starts in that signal; fed, tiles_done, src_p0, keep_p0 and src_off
+// are the open segment's; a round adds seg_base to `samples` and to the resampler's out_off and is otherwise the round
+// above.  A switch of lanes whose open segment resamples and holds samples is one round without chunks in which those
+// lanes' last tiles are computed with the segment's end known (Chunk::flush: final_outputs as for `finish`, the frames
+// kept even as for a feed); then the lane's source tail is dropped and the next segment begins at sample 0 of its own.
 #include "feeder.h"
 
 #include <algorithm>
@@ -88,7 +96,8 @@ struct BufferSet {
 };
 
 struct Lane {
-  uint64_t fed = 0;          // samples per channel fed (at the source rate)
+  uint64_t fed = 0;          // samples per channel fed (at the source rate) -- of the open segment, as tiles_done, src_p0,
+                             // keep_p0 and src_off below are (a stream that never switched format is one segment)
   uint64_t samples = 0;      // 11025 Hz samples per channel the tail reaches to
   bool finished = false;
   uint64_t frames_done = 0;  // frames through the first pass (even unless finished)
@@ -102,7 +111,14 @@ struct Lane {
   uint64_t src_p0 = 0;       // the source sample the lane's place in the current set starts at
   uint64_t keep_p0 = 0;      // ... and the one its place in the next set will start at (resample_piece of the next tile)
   uint64_t src_off = 0;      // current set, s16 values
+  // SwitchFormat: the 11025 Hz sample of the lane's stream the open segment starts at, and the segments ended before it
+  uint64_t seg_base = 0;
+  uint64_t fed_ended = 0;    // the sum of their frames
+  std::vector<NeedleHipSegment> ended;
   std::vector<uint32_t> items;
+  // of its current stream, in any segment: what SetAudit and SetLaneMix ask (`fed` alone is zero again after a switch,
+  // while the lane still carries a tail and rows)
+  bool holds_samples() const { return fed_ended + fed != 0; }
 };
 
 // 11025 Hz samples of a stream's first `fed` source samples that are final: every tap inside the samples fed (output m
@@ -121,20 +137,32 @@ uint64_t final_outputs(const ResampleTiling &t, uint64_t fed, bool finished, uin
 
 }  // namespace
 
-size_t feeder_num_ready(uint64_t n, int sample_rate, int channels, uint32_t step, bool finished) {
-  if (step == 0 || channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS || sample_rate < 2000 || sample_rate > 768000) return 0;
-  const uint64_t out = resample_out_len((size_t)n, sample_rate);
-  if (finished) return num_kept((size_t)out, step);
-  uint64_t have = n;
-  if (sample_rate != kSampleRate) {
+size_t feeder_num_ready_segments(const NeedleHipSegment *segments, size_t count, uint32_t step, bool finished) {
+  if (!segments || !count || step == 0) return 0;
+  uint64_t have = 0;  // 11025 Hz samples that are final
+  for (size_t i = 0; i < count; i++) {
+    const NeedleHipLaneFormat &f = segments[i].format;
+    if (f.channels < 1 || f.channels > NEEDLE_HIP_MAX_CHANNELS || f.sample_rate < 2000 || f.sample_rate > 768000 || !sample_format_valid(f.format))
+      return 0;
+    const uint64_t n = segments[i].frames;
+    if (i + 1 < count || finished || f.sample_rate == kSampleRate) {  // an ended segment is a whole stream of its own
+      have += resample_out_len((size_t)n, f.sample_rate);
+      continue;
+    }
     ResampleTiling t;
-    if (!resample_tiling_host(sample_rate, &t).ok()) return 0;
+    if (!resample_tiling_host(f.sample_rate, &t).ok()) return 0;
     uint64_t tiles = 0;
-    have = final_outputs(t, n, false, &tiles);
+    have += final_outputs(t, n, false, &tiles);
   }
+  if (finished) return num_kept((size_t)have, step);
   const uint64_t frames = (uint64_t)num_frames((size_t)have) & ~(uint64_t)1;
   const uint64_t raw = frames > kLatency ? frames - kLatency : 0;
   return (size_t)((raw + step - 1) / step);
+}
+
+size_t feeder_num_ready(uint64_t n, int sample_rate, int channels, uint32_t step, bool finished) {
+  const NeedleHipSegment whole{NeedleHipLaneFormat{channels, sample_rate, NEEDLE_HIP_SAMPLE_S16}, n};  // (it has no sample format)
+  return feeder_num_ready_segments(&whole, 1, step, finished);
 }
 
 struct Feeder::Impl {
@@ -199,6 +227,7 @@ struct Feeder::Impl {
     const void *plane[NEEDLE_HIP_MAX_CHANNELS] = {};
     uint64_t frames = 0;  // samples per channel
     bool finish = false;
+    bool flush = false;  // SwitchFormat: the open segment ends here (its last tiles are clamped), the lane's stream does not
   };
 
   // What a lane of the format (its limits checked by the caller) is made of, whole or not at all: a rate the resampler
@@ -281,7 +310,7 @@ struct Feeder::Impl {
       p.new_off = ((cursor + 7) & ~(uint64_t)7) + (p.carried_values ? p.src_off % 8 : 0);
       uint64_t samples = l.samples + c.frames;
       if (f.resample) {
-        samples = final_outputs(*f.tiling, l.fed + c.frames, c.finish, &p.tiles);
+        samples = l.seg_base + final_outputs(*f.tiling, l.fed + c.frames, c.finish || c.flush, &p.tiles);
         p.carried_src = (l.fed - l.keep_p0) * (uint64_t)src_channels;
         p.from_src_off = l.src_off + (l.keep_p0 - l.src_p0) * (uint64_t)src_channels;  // a multiple of 8 values: no skew
         p.new_src_off = (src_cursor + 7) & ~(uint64_t)7;
@@ -425,7 +454,7 @@ struct Feeder::Impl {
         if (fmt[i].rate != known.first || l.finished || p.tiles <= l.tiles_done) continue;
         ResampleSpan sp{};
         sp.n_in = l.fed + chunks[i].frames;
-        sp.out_off = p.new_off - l.keep_frame * kHop;  // of the stream's output 0 (modulo 2^64, common.h)
+        sp.out_off = p.new_off - l.keep_frame * kHop + l.seg_base;  // of the segment's output 0 (modulo 2^64, common.h)
         sp.src = to.src.ptr + p.new_src_off;
         sp.t0 = l.tiles_done;
         sp.t1 = p.tiles;
@@ -572,6 +601,66 @@ Status Feeder::ResetFormat(const size_t *lanes, const NeedleHipLaneFormat *forma
   return s;
 }
 
+Status Feeder::SwitchFormat(const size_t *lanes, const NeedleHipLaneFormat *formats, const NeedleHipChannelMix *mixes, size_t k) {
+  Impl &m = *impl_;
+  if (!lanes || !formats) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
+  if (!m.mixed) return Status::Make(NeedleError_InvalidArgument, "feeder: one format for all lanes (needle_hip_feeder_new): a lane cannot change it");
+  if (!m.poison.ok()) return m.poison;
+  Status s = Status::Ok();
+  std::vector<bool> named(m.n, false);
+  for (size_t j = 0; j < k; j++) {  // every lane, every format and every mix before any lane changes
+    if (lanes[j] >= m.n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+    if (named[lanes[j]]) return Status::Make(NeedleError_InvalidArgument, "feeder: a lane named twice in one switch");
+    named[lanes[j]] = true;
+    if (!(s = check_lane_format(formats[j])).ok()) return s;
+    if (mixes && mixes[j].channels && !(s = channel_mix_check(mixes[j], formats[j].channels)).ok()) return s;
+    if (m.lanes[lanes[j]].finished) return Status::Make(NeedleError_InvalidArgument, "feeder: the lane is finished (reset it first)");
+  }
+  std::vector<Impl::Format> made(k);
+  for (size_t j = 0; j < k && s.ok(); j++) s = m.make_format(formats[j], &made[j]);
+  if (!s.ok()) {
+    m.use_formats();  // (drops a tiling make_format added for a lane named before the refused one)
+    return s;
+  }
+  // the flush round: the open segments that resample end as whole streams do, all lanes of the call in one round
+  std::vector<Impl::Chunk> chunks(m.n);
+  bool any = false;
+  for (size_t j = 0; j < k; j++)
+    if (m.fmt[lanes[j]].resample && m.lanes[lanes[j]].fed) chunks[lanes[j]].flush = any = true;
+  if (any && !(s = m.guarded_round(chunks)).ok()) {
+    m.use_formats();
+    return s;
+  }
+  for (size_t j = 0; j < k; j++) {
+    Lane &l = m.lanes[lanes[j]];
+    Impl::Format &f = m.fmt[lanes[j]];
+    l.ended.push_back(NeedleHipSegment{NeedleHipLaneFormat{f.channels, f.rate, f.format}, l.fed});
+    l.fed_ended += l.fed;
+    l.seg_base = l.samples;
+    l.fed = l.tiles_done = l.src_p0 = l.keep_p0 = l.src_off = 0;  // the source tail is dropped: every output that read it exists
+    f = made[j];
+    f.has_mix = mixes && mixes[j].channels != 0;
+    if (f.has_mix) {
+      f.mix = mixes[j];
+      f.direct = false;
+    }
+  }
+  m.use_formats();
+  return Status::Ok();
+}
+
+Status Feeder::LaneSegments(size_t lane, NeedleHipSegment *out, size_t cap, size_t *count) const {
+  const Impl &m = *impl_;
+  if (!count || (cap && !out)) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
+  if (lane >= m.n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
+  const Lane &l = m.lanes[lane];
+  const Impl::Format &f = m.fmt[lane];
+  *count = l.ended.size() + 1;
+  for (size_t i = 0; i < std::min(cap, l.ended.size()); i++) out[i] = l.ended[i];
+  if (cap > l.ended.size()) out[l.ended.size()] = NeedleHipSegment{NeedleHipLaneFormat{f.channels, f.rate, f.format}, l.fed};
+  return Status::Ok();
+}
+
 Status Feeder::SetLaneMix(const size_t *lanes, const NeedleHipChannelMix *mixes, size_t k) {
   Impl &m = *impl_;
   if (!lanes || !mixes) return Status::Make(NeedleError_NullArgument, "feeder: null argument");
@@ -581,7 +670,7 @@ Status Feeder::SetLaneMix(const size_t *lanes, const NeedleHipChannelMix *mixes,
   for (size_t j = 0; j < k; j++) {  // every lane and every mix before any lane changes
     if (lanes[j] >= m.n) return Status::Make(NeedleError_InvalidArgument, "feeder: lane out of range");
     const Lane &l = m.lanes[lanes[j]];
-    if (l.fed || l.finished) return Status::Make(NeedleError_InvalidArgument, "feeder: a lane's channel mix is set only while it holds no samples");
+    if (l.holds_samples() || l.finished) return Status::Make(NeedleError_InvalidArgument, "feeder: a lane's channel mix is set only while it holds no samples");
     if (mixes[j].channels && !(s = channel_mix_check(mixes[j], m.fmt[lanes[j]].channels)).ok()) return s;
   }
   for (size_t j = 0; j < k; j++) {
@@ -677,7 +766,7 @@ Status Feeder::SetAudit(bool on) {
   Impl &m = *impl_;
   if (!m.poison.ok()) return m.poison;
   for (const Lane &l : m.lanes)
-    if (l.fed || l.finished) return Status::Make(NeedleError_InvalidArgument, "feeder: the audit is switched only while no lane holds samples");
+    if (l.holds_samples() || l.finished) return Status::Make(NeedleError_InvalidArgument, "feeder: the audit is switched only while no lane holds samples");
   if (on && gpu_fingerprint_f64_mode())
     return Status::Make(NeedleError_InvalidArgument, "feeder: NEEDLE_HIP_STFT=f64 has no first pass to audit");
   if (on) {
@@ -725,7 +814,7 @@ Status Feeder::Ready(size_t lane, size_t *kept_items, uint64_t *samples_fed, boo
     if (!s.ok()) return m.poison = s;
   }
   if (kept_items) *kept_items = m.lanes[lane].items.size();
-  if (samples_fed) *samples_fed = m.lanes[lane].fed;
+  if (samples_fed) *samples_fed = m.lanes[lane].fed_ended + m.lanes[lane].fed;
   if (finished) *finished = m.lanes[lane].finished;
   return Status::Ok();
 }

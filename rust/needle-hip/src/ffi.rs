@@ -111,6 +111,27 @@ pub struct NeedleHipLaneFormat {
     pub format: i32,
 }
 
+/// One segment of a feeder lane's stream (`needle_hip_feeder_switch_format`): its format and the frames fed in it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct NeedleHipSegment {
+    pub(crate) format: NeedleHipLaneFormat,
+    pub(crate) frames: u64,
+}
+
+impl NeedleHipSegment {
+    pub fn new(format: NeedleHipLaneFormat, frames: u64) -> Self {
+        Self { format, frames }
+    }
+    pub fn format(&self) -> NeedleHipLaneFormat {
+        self.format
+    }
+    /// Samples per channel fed in that format.
+    pub fn frames(&self) -> u64 {
+        self.frames
+    }
+}
+
 /// A channel mix: a 2 x C matrix of Q15 integers, `coef[0][c]` to the left output and `coef[1][c]` to the right
 /// (`needle_hip.h`, "Channel mixes").  `channels == 0` stands for "no mix" where an array of mixes is passed.
 #[repr(C)]
@@ -426,6 +447,21 @@ extern "C" {
         mixes: *const NeedleHipChannelMix,
         k: usize,
     ) -> NeedleError;
+    pub fn needle_hip_feeder_switch_format(
+        feeder: *mut NeedleHipFeeder,
+        lanes: *const usize,
+        formats: *const NeedleHipLaneFormat,
+        mixes: *const NeedleHipChannelMix,
+        k: usize,
+    ) -> NeedleError;
+    pub fn needle_hip_feeder_lane_segments(
+        feeder: *const NeedleHipFeeder,
+        lane: usize,
+        out: *mut NeedleHipSegment,
+        cap: usize,
+        count: *mut usize,
+    ) -> NeedleError;
+    pub fn needle_hip_feeder_num_ready_segments(segments: *const NeedleHipSegment, count: usize, step: u32, finished: bool) -> usize;
     pub fn needle_hip_feeder_free(feeder: *mut NeedleHipFeeder);
     pub fn needle_hip_feeder_feed(feeder: *mut NeedleHipFeeder, pcm: *const *const c_void, num_values: *const usize) -> NeedleError;
     pub fn needle_hip_feeder_finish(feeder: *mut NeedleHipFeeder, lanes: *const usize, k: usize) -> NeedleError;

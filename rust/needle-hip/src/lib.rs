@@ -464,11 +464,13 @@ pub struct Feeder {
     raw: *mut ffi::NeedleHipFeeder,
     lanes: usize,
     planes: usize,
-    formats: Option<Vec<LaneFormat>>, // `with_formats`: every lane's own, kept up to date by `reset_format`
+    formats: Option<Vec<LaneFormat>>, // `with_formats`: every lane's own, kept up to date by `reset_format` / `switch_format`
 }
 
 /// `(channels, sample rate, NeedleHipSampleFormat)` of a feeder lane.
 pub use ffi::NeedleHipLaneFormat as LaneFormat;
+/// One segment of a lane's stream: a format and the frames fed in it (`Feeder::switch_format`).
+pub use ffi::NeedleHipSegment as Segment;
 
 fn format_planes(f: &LaneFormat) -> usize {
     if f.format >= 5 { f.channels.max(1) as usize } else { 1 }
@@ -517,6 +519,37 @@ impl Feeder {
             }
         }
         Ok(())
+    }
+
+    /// `lanes[j]` ends its current segment and continues ITS SAME STREAM in `formats[j]`, folded by `mixes[j]` (`None`, or
+    /// a mix of 0 channels: the plain average): a decoder that reports another rate, layout or sample format in
+    /// mid-stream.  The fingerprint goes on across the change; only on a feeder made by `with_formats`.
+    pub fn switch_format(&mut self, lanes: &[usize], formats: &[LaneFormat], mixes: Option<&[ChannelMix]>) -> Result<()> {
+        assert_eq!(lanes.len(), formats.len(), "one format per lane");
+        assert!(mixes.map_or(true, |m| m.len() == lanes.len()), "one mix per lane");
+        let mixes = mixes.map_or(ptr::null(), |m| m.as_ptr());
+        unsafe { check(ffi::needle_hip_feeder_switch_format(self.raw, lanes.as_ptr(), formats.as_ptr(), mixes, lanes.len()))? };
+        if let Some(mine) = self.formats.as_mut() {
+            for (&lane, f) in lanes.iter().zip(formats) {
+                mine[lane] = *f;
+            }
+        }
+        Ok(())
+    }
+
+    /// The segments of the lane's current stream, the open one last.
+    pub fn lane_segments(&self, lane: usize) -> Result<Vec<Segment>> {
+        let mut count = 0usize;
+        unsafe { check(ffi::needle_hip_feeder_lane_segments(self.raw, lane, ptr::null_mut(), 0, &mut count))? };
+        let mut out = vec![Segment::default(); count];
+        unsafe { check(ffi::needle_hip_feeder_lane_segments(self.raw, lane, out.as_mut_ptr(), out.len(), &mut count))? };
+        out.truncate(count);
+        Ok(out)
+    }
+
+    /// Kept items a lane holds after these segments, the last one open unless `finished` (host arithmetic, no device).
+    pub fn num_ready_segments(segments: &[Segment], step: u32, finished: bool) -> usize {
+        unsafe { ffi::needle_hip_feeder_num_ready_segments(segments.as_ptr(), segments.len(), step, finished) }
     }
 
     /// The feed of a `with_formats` feeder, whose lanes differ in sample type: per lane the raw bytes of its planes (1 of

@@ -24,10 +24,16 @@
             turn: wall ms per feed, the front end's kernel times and launches (not in the default --only).
   uniform:  with --parent DIR, the audit section's comparison with the parent alone: the uniform 28-lane leg, five
             processes per tree (not in the default --only).
+  switch:   a lane that changes format in mid-stream (needle_hip_feeder_switch_format; not in the default --only).
+            (a) with --parent DIR (built): the uniform leg above and a mixed leg (the 28 lanes of `mixed` through one
+            with_formats feeder), neither of which ever switches, five processes per tree, alternating: this tree's median
+            must stay within the parent's median + the spread of the parent's five.  (b) one switch call on 28 lanes of
+            48 kHz s16 stereo, 7 of them to 44.1 kHz, after 1, 2, ... 10 s of 1-s feeds: wall ms (to the items on the host)
+            and summed kernel-event ms of the call, beside the per-feed wall ms of the same feeder; recorded, no target.
 Sections not asked for with --only keep the figures the output file already holds.
 
 Usage: python tools/bench_feeder.py [--repeats K] [--episodes N] [--out FILE] [--parent DIR]
-                                    [--only chunked,per_feed,state,launches,resources,headline,audit,mixed,uniform]"""
+                                    [--only chunked,per_feed,state,launches,resources,headline,audit,mixed,uniform,switch]"""
 import argparse
 import csv
 import glob
@@ -296,10 +302,35 @@ print(statistics.median(times[10:]))
 """
 
 
-def uniform_vs_parent(root, parent):
-    """The 28-lane 48 kHz planar-float stereo leg in this tree and in the parent commit, five processes each, alternating."""
+# bench_mixed's one_feeder leg as a program of its own, for the same purpose
+MIXED_LEG = """
+import statistics, sys, time
+import numpy as np
+sys.path.insert(0, '.')
+from needle_amd import capi
+rng = np.random.default_rng(4)
+formats = [(6, 48000, capi.SAMPLE_F32P), (2, 44100, capi.SAMPLE_S16), (2, 48000, capi.SAMPLE_F32P), (1, 11025, capi.SAMPLE_S16)]
+def second(ch, rate, fmt):
+    if fmt == capi.SAMPLE_F32P:
+        return [rng.uniform(-0.5, 0.5, rate).astype(np.float32) for _ in range(ch)]
+    return rng.integers(-20000, 20000, rate * ch, dtype=np.int16)
+chunks = [second(*fmt) for fmt in formats for _ in range(7)]
+f = capi.Feeder.with_formats([fmt for fmt in formats for _ in range(7)], 2)
+times = []
+for k in range(40):
+    t0 = time.perf_counter()
+    f.feed(chunks)
+    f.ready(0)
+    times.append((time.perf_counter() - t0) * 1e3)
+print(statistics.median(times[10:]))
+"""
+
+
+def uniform_vs_parent(root, parent, program=AUDIT_LEG):
+    """The 28-lane 48 kHz planar-float stereo leg (or another program) in this tree and in the parent commit, five
+    processes each, alternating."""
     def leg(tree):
-        run = subprocess.run([sys.executable, "-c", AUDIT_LEG], cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
+        run = subprocess.run([sys.executable, "-c", program], cwd=tree, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
                              text=True, timeout=300, check=True)
         return float(run.stdout.strip().splitlines()[-1])
     runs = {"parent": [], "this": []}
@@ -362,6 +393,39 @@ def bench_mixed():
     return out
 
 
+def bench_switch(root, parent):
+    out = {"uniform_vs_parent": uniform_vs_parent(root, parent) if parent else NOT_MEASURED,
+           "mixed_vs_parent": uniform_vs_parent(root, parent, MIXED_LEG) if parent else NOT_MEASURED}
+    rng = np.random.default_rng(6)
+    a, b = (2, 48000, capi.SAMPLE_S16), (2, 44100, capi.SAMPLE_S16)
+    chunk = {fmt: [rng.integers(-20000, 20000, fmt[1] * 2, dtype=np.int16) for _ in range(28)] for fmt in (a, b)}
+    kernels = ["feeder_carry", "resample", "stft_chroma32", "features_cert", "stft_fallback", "fixup_items"]
+    f = capi.Feeder.with_formats([a] * 28, 2)
+    lanes = list(range(0, 28, 4))
+    feeds, calls = [], []
+    for sec in range(10):                                # every second: a feed, then the seven lanes switch (48 <-> 44.1 kHz)
+        now = [f.lane_format(k) for k in range(28)]
+        feeds.append(timed_feed(f, [chunk[fmt][k] for k, fmt in enumerate(now)]))
+        to = b if now[0] == a else a
+        capi.set_kernel_timing(",".join(kernels) + ",sum")
+        t0 = time.perf_counter()
+        f.switch_format(lanes, [to] * len(lanes))
+        f.ready(0)
+        wall = (time.perf_counter() - t0) * 1e3
+        capi.synchronize()
+        calls.append({"wall_ms": wall, "kernel_ms": round(sum(max(capi.last_kernel_ms(k), 0.0) for k in kernels), 5),
+                      "launches": {k: capi.kernel_launches(k) for k in kernels if capi.kernel_launches(k)}})
+        capi.set_kernel_timing(None)
+    assert all(len(f.lane_segments(k)) == (11 if k in lanes else 1) for k in range(28))
+    out["switch_call"] = {"shape": "28 lanes of 48 kHz s16 stereo, 1-s chunks, step 2; after every feed lanes 0, 4, ... 24 switch between 48 and 44.1 kHz",
+                          "target": "none: recorded",
+                          "feed_wall_ms_median": statistics.median(feeds[2:]),
+                          "switch_wall_ms_median": statistics.median(c["wall_ms"] for c in calls[2:]),
+                          "switch_kernel_ms_median": statistics.median(c["kernel_ms"] for c in calls[2:]),
+                          "calls": calls}
+    return out
+
+
 def bench_audit(root, parent):
     chunks = audit_lanes()
     feeders = {}
@@ -406,7 +470,7 @@ def main():
         return trace_child(args.trace_child, args.trace_feeds)
     only = set(args.only.split(","))
     keys = ("device", "chunked", "per_feed", "state_bytes_per_lane", "kernel_launches_per_feed", "resources", "headline_vs_parent", "audit",
-            "mixed", "uniform_vs_parent")
+            "mixed", "uniform_vs_parent", "switch")
     res = {k: NOT_MEASURED for k in keys}
     if os.path.exists(args.out):                         # sections not run now keep their figures
         try:
@@ -442,6 +506,9 @@ def main():
             save()
         if "uniform" in only and args.parent:
             res["uniform_vs_parent"] = uniform_vs_parent(root, args.parent)
+            save()
+        if "switch" in only:
+            res["switch"] = bench_switch(root, args.parent)
             save()
         if "headline" in only and args.parent:
             res["headline_vs_parent"] = bench_headline(root, args.parent, max(args.repeats, 3))
