@@ -415,7 +415,9 @@ size_t needle_hip_library_rows_per_video(const NeedleHipLibrary *library);
 /* Lengths (values per stream, all videos) are metadata every rank holds; pcm[i] may be NULL for
  * videos this rank does not own.  Crops to the opening window and uploads.  `channels` = 1..NEEDLE_HIP_MAX_CHANNELS in
  * set_pcm, set_pcm_device and stream_pcm, num_values in interleaved values; 3-8 channel windows are down-mixed on the
- * device on the way in (set_pcm through a staging buffer of at most 2 GiB), so the resident PCM is mono. */
+ * device on the way in (set_pcm through a staging buffer of at most 2 GiB), so the resident PCM is mono.  `channels` = 0,
+ * here and in needle_hip_library_rank_videos: only for a library with a format per video
+ * (needle_hip_library_set_video_formats, which says what the arrays then hold). */
 enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *library, const int16_t *const *pcm,
                                             const size_t *num_values, int channels);
 /* The same for PCM that is already in HBM (decoded or generated on the device): d_pcm[i] are DEVICE pointers, NULL for
@@ -714,6 +716,49 @@ enum NeedleError needle_hip_library_set_channel_mix(NeedleHipLibrary *library, c
  * staged span of a round with one launch of the rematrix kernel (timer "rematrix"; no "ingest" launch); one without
  * launches what it always did. */
 enum NeedleError needle_hip_feeder_set_lane_mix(NeedleHipFeeder *feeder, const size_t *lanes, const NeedleHipChannelMix *mixes, size_t k);
+
+/* ---- Library and analyzer: a rate, channel count, sample format and mix per video ----------------------------
+ * A season is rarely uniform: stereo 44.1 kHz episodes among 5.1 48 kHz ones, one planar-float rip among s16 ones.  The
+ * batch path takes such a season as it is.
+ *
+ * needle_hip_library_set_video_formats: formats[num_videos]; mixes NULL, or mixes[num_videos] with channels == 0
+ * meaning the plain average for that video.  After needle_hip_library_new (and include_endings), before any PCM call:
+ * later it is InvalidArgument.  It excludes set_sample_rate, set_sample_format and set_channel_mix: calling one of them
+ * after it, or it after one of them, is InvalidArgument.  It may be called again before the PCM arrives; video_format
+ * reports what was last accepted (InvalidArgument on a library without formats, or for a video out of range).
+ * Limits per video are a feeder lane's: channels 1..8, sample_rate 2000..768000, every NeedleHipSampleFormat, a rate the
+ * resampler has a design for, and a mix whose `channels` equals the video's.  Every video is checked before anything
+ * changes, on the host, before a device is asked for; a refused call leaves the library exactly as it was.
+ *
+ * With formats set, set_pcm, set_pcm_device, stream_pcm and rank_videos are called with channels == 0 (any other value:
+ * InvalidArgument; channels == 0 without formats stays InvalidArgument).  The pointer array is the concatenation, video
+ * after video, of each video's planes, as in needle_hip_feeder_feed: an interleaved video gives 1 pointer, a planar one
+ * channels_v pointers.  A video this rank does not hold has all its planes NULL; one with NULL and non-NULL planes is
+ * NullArgument.  num_values[v] counts video v's own values (frames x channels_v).
+ *
+ * Each video's windows are cut at its own rate (the ending's seek included) and each window is resampled as a stream of
+ * its own.  Every video lands as mono: the conversion, then the plain average (2 channels included) or the video's mix
+ * -- exactly what a lane of a needle_hip_feeder_new_lanes feeder does -- so the resident PCM of such a library is
+ * 11025 Hz mono s16 for every video.  Jobs, analyze, audit, frame_hashes, the arena geometry and the multi-rank
+ * exchange do not depend on the formats; rank_videos(channels = 0) is a pure function of the library's parameters, the
+ * formats and the lengths.  Every row of the arena is bit for bit what needle_hip_analyzer_run_pcm_format gives for that
+ * video alone in its format (with the video's mix set on the analyzer, if it has one).
+ *
+ * Per staging batch (2 GiB, or NEEDLE_HIP_MAX_BATCH_VALUES values) set_pcm and set_pcm_device make one upload (host
+ * PCM only; device PCM is read in place), ONE landing launch whatever the mixture (timer "ingest", or "rematrix" when
+ * any video of the library has a mix) and one resampler launch per distinct rate other than 11025 Hz in the batch;
+ * stream_pcm does the same per launch group, under the next group's uploads.  A library without formats launches
+ * exactly what it always did. */
+enum NeedleError needle_hip_library_set_video_formats(NeedleHipLibrary *library, const NeedleHipLaneFormat *formats,
+                                                      const NeedleHipChannelMix *mixes);
+enum NeedleError needle_hip_library_video_format(const NeedleHipLibrary *library, size_t video, NeedleHipLaneFormat *format);
+/* needle_hip_analyzer_run_pcm_format with a format per stream: formats[num_streams]; mixes NULL, or one per stream with
+ * channels == 0 for none; pcm is the concatenation of each stream's planes.  One device pass whatever the mixture; the
+ * result is per video what run_pcm_format gives for it alone.  Per-stream mixes on an analyzer that has a mix of its own
+ * (needle_hip_analyzer_set_channel_mix) are InvalidArgument; without them that mix is applied to every stream. */
+enum NeedleError needle_hip_analyzer_run_pcm_formats(struct NeedleAudioAnalyzer *analyzer, const void *const *pcm,
+                                                     const size_t *num_values, const NeedleHipLaneFormat *formats,
+                                                     const NeedleHipChannelMix *mixes, float hash_duration, bool persist);
 
 /* ---- A lane changes format in mid-stream, the fingerprint goes on ------------------------------------------
  * A decoder may report another rate, layout or sample format in the middle of a stream (a 5.1 programme among stereo

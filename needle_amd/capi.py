@@ -108,6 +108,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_feeder_new", "needle_hip_feeder_free", "needle_hip_feeder_feed", "needle_hip_feeder_finish",
     "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
     "needle_hip_feeder_state_bytes", "needle_hip_feeder_num_ready", "needle_hip_feeder_set_audit", "needle_hip_feeder_audit",
+    "needle_hip_library_set_video_formats", "needle_hip_library_video_format", "needle_hip_analyzer_run_pcm_formats",
     "needle_hip_feeder_new_lanes", "needle_hip_feeder_lane_format", "needle_hip_feeder_reset_format", "needle_hip_convert_mono_host",
     "needle_hip_channel_mix_default", "needle_hip_rematrix_host", "needle_hip_analyzer_set_channel_mix",
     "needle_hip_analyzer_set_layout_downmix", "needle_hip_comparator_set_layout_downmix", "needle_hip_library_set_channel_mix",
@@ -382,6 +383,9 @@ def lib():
     L.needle_hip_feeder_num_ready.restype = sz
     L.needle_hip_feeder_new_lanes.argtypes = [vp, sz, u32, C.POINTER(vp)]
     L.needle_hip_feeder_lane_format.argtypes = [vp, sz, vp]
+    L.needle_hip_library_set_video_formats.argtypes = [vp, vp, vp]
+    L.needle_hip_library_video_format.argtypes = [vp, sz, vp]
+    L.needle_hip_analyzer_run_pcm_formats.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), vp, vp, f32, b]
     L.needle_hip_feeder_reset_format.argtypes = [vp, C.POINTER(sz), vp, sz]
     L.needle_hip_convert_mono_host.argtypes = [C.POINTER(vp), C.POINTER(sz), vp, sz, C.POINTER(vp)]
     L.needle_hip_channel_mix_default.argtypes = [u32, vp]
@@ -730,6 +734,20 @@ class Analyzer:
         ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data for a in arrs])
         lens = (C.c_size_t * max(len(arrs), 1))(*[a.size for a in arrs])
         check(lib().needle_hip_analyzer_run_pcm(h, ptrs, lens, channels, sample_rate, hash_duration, persist))
+        return self._collect()
+
+    def run_pcm_formats(self, pcm, formats: Sequence[Tuple[int, int, int]], mixes: Optional[Sequence[Optional[ChannelMix]]] = None,
+                        hash_duration: float = DEFAULT_HASH_DURATION, persist: bool = False) -> List[FrameHashes]:
+        """run_pcm with a (channels, sample_rate, sample_format) triple per stream and, optionally, a mix per stream
+        (None: the plain average) in one device pass (needle_hip_analyzer_run_pcm_formats); a planar stream is a
+        sequence of its planes."""
+        h = self._handle()
+        keep, flat, sizes = _lane_pointers(pcm, formats)
+        ptrs = (C.c_void_p * max(len(flat), 1))(*flat)
+        lens = (C.c_size_t * max(len(sizes), 1))(*sizes)
+        check(lib().needle_hip_analyzer_run_pcm_formats(h, ptrs, lens, _lane_formats(formats),
+                                                        None if mixes is None else _channel_mixes(mixes), hash_duration, persist))
+        del keep
         return self._collect()
 
     def __del__(self):
@@ -1534,6 +1552,7 @@ class Library:
         self._h = out
         self.n = num_videos
         self._format = SAMPLE_S16
+        self._formats = None
 
     def include_endings(self, ending_search_percentage: float = DEFAULT_ENDING_SEARCH_PERCENTAGE) -> "Library":
         check(lib().needle_hip_library_include_endings(self._h, ending_search_percentage))
@@ -1559,10 +1578,32 @@ class Library:
         self._format = sample_format
         return self
 
+    def set_video_formats(self, formats: Sequence[Tuple[int, int, int]],
+                          mixes: Optional[Sequence[Optional[ChannelMix]]] = None) -> "Library":
+        """A (channels, sample_rate, sample_format) triple per video and, optionally, a mix per video (None: the plain
+        average): needle_hip_library_set_video_formats.  set_pcm / set_pcm_device / stream_pcm / rank_videos are then
+        called with channels=0; every video gives an array of its format's dtype, a planar one a sequence of its planes
+        (set_pcm_device: the concatenation of every video's plane pointers, None for each plane of a video held elsewhere)."""
+        if len(formats) != self.n or (mixes is not None and len(mixes) != self.n):
+            raise ValueError(f"one format (and one mix) per video is required: {self.n}")
+        check(lib().needle_hip_library_set_video_formats(self._h, _lane_formats(formats),
+                                                         None if mixes is None else _channel_mixes(mixes)))
+        self._formats = [tuple(int(x) for x in f) for f in formats]
+        return self
+
+    def video_format(self, video: int) -> Tuple[int, int, int]:
+        """(channels, sample_rate, sample_format) of a video (needle_hip_library_video_format)."""
+        f = CLaneFormat()
+        check(lib().needle_hip_library_video_format(self._h, video, C.byref(f)))
+        return f.channels, f.sample_rate, f.format
+
     def rows_per_video(self) -> int:
         return lib().needle_hip_library_rows_per_video(self._h)
 
     def _host_pointers(self, pcm, channels: int):
+        if self._formats is not None:
+            keep, flat, _ = _lane_pointers(pcm, self._formats)
+            return keep, (C.c_void_p * max(len(flat), 1))(*flat)
         if self._format == SAMPLE_S16:
             arrs = [None if p is None else np.ascontiguousarray(p, dtype=np.int16) for p in pcm]
             return arrs, (C.c_void_p * self.n)(*[None if a is None else a.ctypes.data for a in arrs])

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <fstream>
 
+#include "format_plan.h"
 #include "needle_core.h"
 
 namespace needle {
@@ -147,6 +148,76 @@ Status Analyzer::run_pcm_format(const std::vector<const void *> &pcm, const std:
 }
 
 namespace {
+// The tail of one video's analysis: timestamps on its kept hashes (the ending's with its seek), hash duration, MD5, and
+// the .needle.dat file when asked for (:321,411,414-417).
+Status finish_video(const std::vector<uint32_t> &opening, const std::vector<uint32_t> *ending, uint32_t step, ns_t seek,
+                    ns_t hash_duration, const std::string &md5, bool persist, const std::string &video, FrameHashesData *fh) {
+  attach_timestamps(opening.data(), opening.size(), step, false, 0, &fh->opening);
+  if (ending) attach_timestamps(ending->data(), ending->size(), step, true, seek, &fh->ending);
+  fh->hash_duration = hash_duration;
+  fh->md5 = md5;
+  return persist ? frame_hashes_write(with_extension(video, FRAME_HASH_DATA_FILE_NAME), *fh) : Status::Ok();
+}
+}  // namespace
+
+Status Analyzer::run_pcm_formats(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values,
+                                 const NeedleHipLaneFormat *formats, const NeedleHipChannelMix *mixes, ns_t hash_duration,
+                                 bool persist, std::vector<FrameHashesData> *out) const {
+  if (videos_.empty())  // :431-433
+    return Status::Make(NeedleError_Unknown, "no paths provided to analyzer");
+  const size_t n = videos_.size();
+  if (num_values.size() != n) return Status::Make(NeedleError_InvalidArgument, "one PCM stream per video is required");
+  if (has_mix_ && mixes) return Status::Make(NeedleError_InvalidArgument, "a channel mix per stream and the analyzer's own exclude each other");
+  bool any_mix = has_mix_;
+  for (size_t i = 0; i < n; i++) {  // every stream before a device is asked for, a rate without a resampler design included
+    const NeedleHipChannelMix *mix = has_mix_ ? &mix_ : mixes && mixes[i].channels ? &mixes[i] : nullptr;
+    Status fs = lane_format_check(formats[i], mix, "stream " + std::to_string(i));
+    if (!fs.ok()) return fs;
+    any_mix = any_mix || mix;
+  }
+  uint32_t step = 0;
+  if (!step_for_hash_duration(hash_duration, &step))  // the reference panics in step_by(0), :293-304
+    return Status::Make(NeedleError_AnalyzerInvalidHashDuration,
+                        "hash duration is shorter than one chromaprint item (123 ms)");
+  const std::vector<size_t> first = format_first_planes(formats, n);
+  if (pcm.size() != first[n]) return Status::Make(NeedleError_InvalidArgument, "one pointer per plane of every video is required");
+  const size_t per = include_endings_ ? 2 : 1;
+  std::vector<FormatWindow> streams(n * per);  // stream per * i (+ 1) = opening (ending) window of video i
+  std::vector<ns_t> seeks(n, 0);
+  for (size_t i = 0; i < n; i++) {
+    const NeedleHipLaneFormat &f = formats[i];
+    const size_t total = num_values[i] / (size_t)f.channels, planes = first[i + 1] - first[i], width = sample_format_width(f.format);
+    size_t open_samples = 0, end_first = 0;
+    Status s = windows(total, f.sample_rate, opening_search_percentage_, ending_search_percentage_, &open_samples, &end_first, &seeks[i]);
+    if (!s.ok()) return s;
+    for (size_t r = 0; r < per; r++) {
+      FormatWindow &w = streams[i * per + r];
+      w.channels = f.channels;
+      w.format = f.format;
+      w.rate = f.sample_rate;
+      w.mix = has_mix_ ? &mix_ : mixes && mixes[i].channels ? &mixes[i] : nullptr;
+      w.frames = r == 0 ? open_samples : total - end_first;
+      for (size_t c = 0; c < planes; c++) {  // a plane holds one sample per frame, an interleaved stream `channels`
+        const uint8_t *plane = static_cast<const uint8_t *>(pcm[first[i] + c]);
+        w.src[c] = plane && r ? plane + end_first * (planes == 1 ? (size_t)f.channels : 1) * width : plane;
+      }
+    }
+  }
+  std::vector<std::vector<uint32_t>> kept;
+  Status s = gpu_fingerprint_formats(streams, any_mix, step, &kept);
+  if (!s.ok()) return s;
+  out->assign(n, {});
+  for (size_t i = 0; i < n; i++) {
+    std::string md5;  // (in-memory callers may pass paths that do not exist: the key then stays empty)
+    if (!header_md5(videos_[i], &md5).ok()) md5.clear();
+    s = finish_video(kept[i * per], include_endings_ ? &kept[i * per + 1] : nullptr, step, seeks[i], hash_duration, md5, persist,
+                     videos_[i], &(*out)[i]);
+    if (!s.ok()) return s;
+  }
+  return Status::Ok();
+}
+
+namespace {
 
 struct Trace {  // NEEDLE_HIP_TRACE=1: phase times of the file analyzer on stderr
   const bool on = std::getenv("NEEDLE_HIP_TRACE") != nullptr;
@@ -247,6 +318,43 @@ Status Analyzer::run(ns_t hash_duration, bool persist, bool threading, std::vect
   }
   const unsigned readers = threading ? std::min(host_threads(), 16u) : 1u;
   const size_t per = include_endings_ ? 2 : 1;
+  if (keys.size() > 1) {
+    // files that differ in (channels, rate, mask) go through ONE device pass, every window landed as mono in its own
+    // format (the layout down-mix: a mix per file); videos stay in input order
+    std::vector<NeedleHipChannelMix> mixes(pending.size());
+    std::vector<FormatWindow> streams;  // stream per * k (+ 1) = opening (ending) window of pending[k]
+    bool any_mix = false;
+    for (size_t k = 0; k < pending.size(); k++) {
+      const Pending &p = pending[k];
+      if (p.mask) (void)channel_mix_default(p.mask, &mixes[k]);  // (accepted when the file was probed)
+      any_mix = any_mix || p.mask;
+      for (size_t r = 0; r < per; r++) {
+        FormatWindow w;
+        w.channels = p.info.channels;
+        w.rate = p.info.sample_rate;
+        w.mix = p.mask ? &mixes[k] : nullptr;
+        w.frames = r == 0 ? p.opening_frames : (size_t)p.info.frames - p.ending_first;
+        streams.push_back(w);
+      }
+    }
+    const PcmReader read = [&](size_t stream, uint64_t first_value, uint64_t num_values, int16_t *dst) {
+      const Pending &p = pending[stream / per];
+      const uint64_t c = (uint64_t)p.info.channels, window_first = stream % per ? p.ending_first : 0;
+      return wav_read_frames(videos_[p.index], p.info, window_first + first_value / c, num_values / c, dst);
+    };
+    std::vector<std::vector<uint32_t>> kept;
+    Status s = gpu_fingerprint_formats_streamed(streams, any_mix, read, readers, step, &kept);
+    if (!s.ok()) return s;
+    trace.lap("read + upload + fingerprint", pending.size());
+    for (size_t k = 0; k < pending.size(); k++) {
+      const Pending &p = pending[k];
+      s = finish_video(kept[k * per], include_endings_ ? &kept[k * per + 1] : nullptr, step, p.seek, hash_duration, md5s[p.index],
+                       persist, videos_[p.index], &(*out)[p.index]);
+      if (!s.ok()) return s;
+    }
+    trace.lap("timestamps + persist", pending.size());
+    return deferred;
+  }
   for (const Key &key : keys) {
     std::vector<const Pending *> group;
     for (const Pending &p : pending)
@@ -270,16 +378,9 @@ Status Analyzer::run(ns_t hash_duration, bool persist, bool threading, std::vect
     trace.lap("read + upload + fingerprint", group.size());
     for (size_t k = 0; k < group.size(); k++) {
       const Pending &p = *group[k];
-      FrameHashesData &fh = (*out)[p.index];
-      attach_timestamps(kept[k * per].data(), kept[k * per].size(), step, false, 0, &fh.opening);
-      if (include_endings_)
-        attach_timestamps(kept[k * per + 1].data(), kept[k * per + 1].size(), step, true, p.seek, &fh.ending);
-      fh.hash_duration = hash_duration;  // :321,411
-      fh.md5 = md5s[p.index];
-      if (persist) {  // :414-417
-        s = frame_hashes_write(with_extension(videos_[p.index], FRAME_HASH_DATA_FILE_NAME), fh);
-        if (!s.ok()) return s;
-      }
+      s = finish_video(kept[k * per], include_endings_ ? &kept[k * per + 1] : nullptr, step, p.seek, hash_duration, md5s[p.index],
+                       persist, videos_[p.index], &(*out)[p.index]);
+      if (!s.ok()) return s;
     }
     trace.lap("timestamps + persist", group.size());
   }

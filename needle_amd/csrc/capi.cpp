@@ -1251,6 +1251,35 @@ enum NeedleError needle_hip_analyzer_run_pcm_format(struct NeedleAudioAnalyzer *
   });
 }
 
+enum NeedleError needle_hip_analyzer_run_pcm_formats(struct NeedleAudioAnalyzer *analyzer, const void *const *pcm,
+                                                     const size_t *num_values, const NeedleHipLaneFormat *formats,
+                                                     const NeedleHipChannelMix *mixes, float hash_duration, bool persist) {
+  if (!analyzer || !pcm || !num_values || !formats) return NeedleError_NullArgument;
+  if (!(hash_duration > 0.0f)) return NeedleError_AnalyzerInvalidHashDuration;
+  return guarded([&]() -> NeedleError {
+    bool ok = true;
+    const ns_t hd = duration_from_secs_f32(hash_duration, &ok);
+    if (!ok) return NeedleError_AnalyzerInvalidHashDuration;
+    const size_t n = analyzer->inner.videos().size();
+    size_t planes = 0;
+    for (size_t i = 0; i < n; i++) {
+      // (the planes of a stream cannot be counted without these two; run_pcm_formats checks the rest)
+      if (!sample_format_valid(formats[i].format) || formats[i].channels < 1 || formats[i].channels > NEEDLE_HIP_MAX_CHANNELS)
+        return report(Status::Make(NeedleError_InvalidArgument, "stream " + std::to_string(i) + ": unknown sample format or channel count"));
+      for (size_t c = 0; c < sample_format_planes(formats[i].format, formats[i].channels); c++)
+        if (!pcm[planes++] && num_values[i]) return NeedleError_NullArgument;
+    }
+    std::vector<const void *> p(pcm, pcm + planes);
+    std::vector<size_t> lens(num_values, num_values + n);
+    std::vector<FrameHashesData> out;
+    Status s = analyzer->inner.run_pcm_formats(p, lens, formats, mixes, hd, persist, &out);
+    if (!s.ok()) return report(s);
+    analyzer->frame_hashes.clear();
+    for (FrameHashesData &d : out) analyzer->frame_hashes.push_back(FrameHashes{std::move(d)});
+    return NeedleError_Ok;
+  });
+}
+
 enum NeedleError needle_hip_analyzer_set_channel_mix(struct NeedleAudioAnalyzer *analyzer, const NeedleHipChannelMix *mix) {
   if (!analyzer) return NeedleError_NullArgument;
   return guarded([&]() -> NeedleError {

@@ -1,6 +1,7 @@
 // Host PCM -> kept items: plans device batches over the streams, uploads them and runs the (converter, down-mix,
 // resampler and) fingerprinter group by group underneath the copies that follow.  Nothing here launches a kernel of its
 // own: it calls gpu_fingerprint_device and friends (common.h).
+#include "format_plan.h"
 #include "hipctx.h"
 
 #include <algorithm>
@@ -341,6 +342,185 @@ Status gpu_fingerprint_streamed_device_format(const std::vector<const void *> &p
     return Status::Make(NeedleError_InvalidArgument, "fingerprint: one length and one item offset per stream, one pointer per plane are required");
   return fingerprint_in_batches(num_values, channels, step, nullptr, rate, format, raw_upload(pcm, num_values, channels, format),
                                 d_items, &item_off, mix);
+}
+
+// The plan of fingerprint_in_batches for streams with formats of their own.  Every stream goes on as mono: a batch's
+// streams are uploaded raw into d_raw (every plane 16-byte aligned), a launch group is landed by one launch -- 11025 Hz
+// streams straight into d_mono, where the fingerprinter reads, the others into d_pcm, from where one resampler launch
+// per distinct rate writes them to d_mono -- and fingerprinted, under the uploads of the next group.
+namespace {
+// Uploads streams [begin, end) of a batch: stream i's plane c goes to d_raw + raw_off[i - begin] + c * plane_units[i - begin]
+// on `up`; `issued` is told the stream's index in the batch once its last plane is on its way.
+using FormatUpload = std::function<Status(size_t begin, size_t end, const std::vector<uint64_t> &raw_off,
+                                          const std::vector<uint64_t> &plane_units, int16_t *d_raw, hipStream_t up,
+                                          const StreamIssued &issued)>;
+
+Status fingerprint_formats_in_batches(const std::vector<FormatWindow> &streams, bool any_mix, uint32_t step,
+                                      std::vector<std::vector<uint32_t>> *items, uint32_t *d_items_out,
+                                      const std::vector<uint64_t> *item_off_out, const FormatUpload &upload) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s;
+  const size_t n = streams.size();
+  for (const FormatWindow &w : streams)  // before any device is asked for
+    if (!(s = lane_format_check(NeedleHipLaneFormat{w.channels, w.rate, w.format}, w.mix, "fingerprint")).ok()) return s;
+  if (d_items_out && (!item_off_out || item_off_out->size() != n))
+    return Status::Make(NeedleError_InvalidArgument, "fingerprint: one item offset per stream is required");
+  if (step == 0) return Status::Make(NeedleError_InvalidArgument, "fingerprint: step must be >= 1");
+  if (!(s = ensure_device()).ok()) return s;
+  if (items) items->assign(n, {});
+  uint64_t kMaxBatchValues = 1ull << 30;  // 2 GiB of raw samples, counted in s16 units
+  bool count_values = false;
+  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) {  // tests (counts values whatever their width)
+    kMaxBatchValues = (uint64_t)std::max(1ll, atoll(e));
+    count_values = true;
+  }
+  uint64_t group_values = (32ull << 20) / sizeof(int16_t);
+  if (const char *e = getenv("NEEDLE_HIP_LAUNCH_GROUP_BYTES")) group_values = (uint64_t)std::max(2ll, atoll(e)) / sizeof(int16_t);
+  hipStream_t stream = library_stream(), up = upload_stream();
+  struct DrainUploads {  // every exit waits for the copies already enqueued: they read the caller's buffers
+    hipStream_t s;
+    ~DrainUploads() { (void)hipStreamSynchronize(s); }
+  } drain_uploads{up};
+  OverlapEvents *ev = overlap_events();
+  HostEntryWorkspace *ws = host_entry_workspace();
+  DeviceBuffer<int16_t> &d_pcm = ws->d_pcm, &d_mono = ws->d_mono, &d_raw = ws->d_raw;
+  DeviceBuffer<uint32_t> &d_items = ws->d_items;
+  size_t begin = 0, descriptor_slot = 0;
+  bool first_batch = true;
+  while (begin < n) {
+    struct Place {
+      uint64_t raw, plane_units, staged, mono, out_samples;  // offsets in d_raw, d_pcm (resampled streams) and d_mono
+    };
+    std::vector<Place> place;
+    std::vector<StreamSpan> spans;
+    uint64_t raw = 0, raw_cost = 0, staged = 0, mono = 0, kept = 0;
+    size_t end = begin;
+    while (end < n) {
+      const FormatWindow &w = streams[end];
+      const size_t P = sample_format_planes(w.format, w.channels);
+      const uint64_t plane_units = sample_plane_units(w.frames * (P == 1 ? (uint64_t)w.channels : 1), sample_format_width(w.format));
+      const uint64_t cost = count_values ? w.frames * (uint64_t)w.channels : P * plane_units;
+      if (end > begin && raw_cost + cost > kMaxBatchValues) break;
+      const uint64_t out_samples = w.rate != kSampleRate ? resample_out_len(w.frames, w.rate) : w.frames;
+      place.push_back(Place{raw, plane_units, staged, mono, out_samples});
+      spans.push_back(StreamSpan{mono, out_samples, d_items_out ? (*item_off_out)[end] : kept});
+      raw += P * plane_units;
+      raw_cost += cost;
+      if (w.rate != kSampleRate) staged += (w.frames + 7) & ~(uint64_t)7;
+      mono += (out_samples + 7) & ~(uint64_t)7;
+      kept += num_kept(out_samples, step);
+      end++;
+    }
+    if (!(s = d_raw.reserve(std::max<uint64_t>(raw, 1))).ok()) return s;
+    if (!(s = d_pcm.reserve(std::max<uint64_t>(staged, 1))).ok()) return s;
+    if (!(s = d_mono.reserve(std::max<uint64_t>(mono, 1))).ok()) return s;
+    if (!d_items_out && !(s = d_items.reserve(std::max<uint64_t>(kept, 1))).ok()) return s;
+    uint32_t *const d_out = d_items_out ? d_items_out : d_items.ptr;
+    // the copies must not overtake kernels that still read the arenas: those of the previous batch, or of an earlier call
+    NEEDLE_HIP_TRY(hipEventRecord(first_batch ? ev->entry : ev->batch_done, stream));
+    NEEDLE_HIP_TRY(hipStreamWaitEvent(up, first_batch ? ev->entry : ev->batch_done, 0));
+    first_batch = false;
+    size_t launched = 0;
+    uint64_t pending_values = 0;
+    auto launch_group = [&](size_t upto) -> Status {  // streams [launched, upto) of the batch have been enqueued on `up`
+      if (upto <= launched) return Status::Ok();
+      NEEDLE_HIP_TRY(hipEventRecord(ev->landed, up));
+      NEEDLE_HIP_TRY(hipStreamWaitEvent(stream, ev->landed, 0));
+      std::vector<IngestSpan> land;
+      std::map<int, std::vector<ResampleSpan>> by_rate;
+      for (size_t k = launched; k < upto; k++) {
+        const FormatWindow &w = streams[begin + k];
+        if (w.frames == 0) continue;
+        IngestSpan in{};
+        for (size_t c = 0; c < sample_format_planes(w.format, w.channels); c++) in.src[c] = d_raw.ptr + place[k].raw + c * place[k].plane_units;
+        in.frames = w.frames;
+        in.channels = w.channels;
+        in.format = w.format;
+        in.mix = w.mix;
+        if (w.rate != kSampleRate) {
+          in.dst = d_pcm.ptr + place[k].staged;
+          by_rate[w.rate].push_back(ResampleSpan{place[k].staged, w.frames, place[k].mono});
+        } else {
+          in.dst = d_mono.ptr + place[k].mono;
+        }
+        land.push_back(in);
+      }
+      Status gs = land.empty() ? Status::Ok() : any_mix ? gpu_rematrix_device(land, false) : gpu_ingest_device(land, false);
+      for (const auto &rs : by_rate)
+        if (gs.ok()) gs = gpu_resample_device(d_pcm.ptr, rs.second, 1, rs.first, d_mono.ptr, false);
+      const std::vector<StreamSpan> group(spans.begin() + launched, spans.begin() + upto);
+      if (gs.ok()) gs = gpu_fingerprint_device(d_mono.ptr, group, 1, step, d_out, false, nullptr, nullptr, descriptor_slot++);
+      launched = upto;
+      pending_values = 0;
+      return gs;
+    };
+    std::vector<uint64_t> raw_off, plane_units;
+    for (const Place &p : place) {
+      raw_off.push_back(p.raw);
+      plane_units.push_back(p.plane_units);
+    }
+    const StreamIssued issued = [&](size_t i) -> Status {  // i: index inside the batch
+      const FormatWindow &w = streams[begin + i];
+      pending_values += w.frames * (uint64_t)w.channels;
+      return pending_values >= group_values ? launch_group(i + 1) : Status::Ok();
+    };
+    if (!(s = upload(begin, end, raw_off, plane_units, d_raw.ptr, up, issued)).ok()) return s;
+    if (!(s = launch_group(end - begin)).ok()) return s;
+    if (items) {
+      std::vector<uint32_t> host(std::max<uint64_t>(kept, 1));
+      NEEDLE_HIP_TRY(hipMemcpyAsync(host.data(), d_items.ptr, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+      for (size_t i = begin; i < end; i++) {
+        const size_t k = num_kept(place[i - begin].out_samples, step);
+        (*items)[i].assign(host.begin() + spans[i - begin].item_off, host.begin() + spans[i - begin].item_off + k);
+      }
+    }
+    begin = end;
+  }
+  NEEDLE_HIP_TRY(hipStreamSynchronize(up));
+  return Status::Ok();
+}
+}  // namespace
+
+Status gpu_fingerprint_formats(const std::vector<FormatWindow> &streams, bool any_mix, uint32_t step,
+                               std::vector<std::vector<uint32_t>> *items, uint32_t *d_items_out,
+                               const std::vector<uint64_t> *item_off_out) {
+  const FormatUpload from_pointers = [&](size_t begin, size_t end, const std::vector<uint64_t> &raw_off,
+                                         const std::vector<uint64_t> &plane_units, int16_t *d_raw, hipStream_t up,
+                                         const StreamIssued &issued) -> Status {
+    std::vector<const void *> src;
+    std::vector<size_t> bytes, stream_of_plane;
+    std::vector<uint64_t> off;
+    std::vector<char> last_plane;
+    for (size_t i = begin; i < end; i++) {
+      const FormatWindow &w = streams[i];
+      const size_t P = sample_format_planes(w.format, w.channels);
+      for (size_t c = 0; c < P; c++) {
+        src.push_back(w.src[c]);
+        bytes.push_back(w.frames * (P == 1 ? (uint64_t)w.channels : 1) * sample_format_width(w.format));
+        off.push_back(raw_off[i - begin] + c * plane_units[i - begin]);
+        stream_of_plane.push_back(i - begin);
+        last_plane.push_back(c + 1 == P);
+      }
+    }
+    const StreamIssued plane_issued = [&](size_t k) -> Status { return last_plane[k] ? issued(stream_of_plane[k]) : Status::Ok(); };
+    return gpu_upload_raw(src, bytes, off, d_raw, up, plane_issued);
+  };
+  return fingerprint_formats_in_batches(streams, any_mix, step, items, d_items_out, item_off_out, from_pointers);
+}
+
+Status gpu_fingerprint_formats_streamed(const std::vector<FormatWindow> &streams, bool any_mix, const PcmReader &read, unsigned readers,
+                                        uint32_t step, std::vector<std::vector<uint32_t>> *items) {
+  for (const FormatWindow &w : streams)
+    if (w.format != NEEDLE_HIP_SAMPLE_S16) return Status::Make(NeedleError_InvalidArgument, "fingerprint: a reader produces interleaved s16");
+  const FormatUpload from_reader = [&](size_t begin, size_t end, const std::vector<uint64_t> &raw_off, const std::vector<uint64_t> &,
+                                       int16_t *d_raw, hipStream_t up, const StreamIssued &issued) -> Status {
+    std::vector<size_t> num_values;
+    for (size_t i = begin; i < end; i++) num_values.push_back(streams[i].frames * (size_t)streams[i].channels);
+    const PcmReader shifted = [&](size_t stream, uint64_t first, uint64_t count, int16_t *dst) { return read(begin + stream, first, count, dst); };
+    return gpu_upload_pcm_streamed(num_values, raw_off, shifted, readers, d_raw, up, issued);
+  };
+  return fingerprint_formats_in_batches(streams, any_mix, step, items, nullptr, nullptr, from_reader);
 }
 
 }  // namespace needle

@@ -21,6 +21,7 @@
 
 #include "comm.h"
 #include "epilogue.h"
+#include "format_plan.h"
 #include "hipctx.h"
 #include "needle_core.h"
 
@@ -56,6 +57,13 @@ struct NeedleHipLibrary {
   int format = NEEDLE_HIP_SAMPLE_S16;  // of the callers' PCM (needle_hip_library_set_sample_format); the resident PCM is s16
   bool has_mix = false;                // needle_hip_library_set_channel_mix: the callers' PCM is folded to mono by `mix` on the way in
   NeedleHipChannelMix mix{};
+  bool uniform_set = false;            // one of the three setters above was called: needle_hip_library_set_video_formats is refused
+  // needle_hip_library_set_video_formats: a format and a mix (channels == 0: the plain average) per video.  Every video
+  // lands as 11025 Hz mono s16; rate, format, mix and channels above are not looked at.
+  bool has_formats = false;
+  bool any_mix = false;
+  std::vector<NeedleHipLaneFormat> formats;
+  std::vector<NeedleHipChannelMix> mixes;
   bool have_pcm = false;      // windows and arena are set up (set_pcm or stream_pcm)
   bool pcm_resident = false;  // set_pcm: the PCM stays in HBM and analyze can be repeated
   std::vector<Window> win;  // [video * regions() + region]
@@ -280,33 +288,67 @@ enum NeedleError needle_hip_library_include_endings(NeedleHipLibrary *lib, float
 enum NeedleError needle_hip_library_set_sample_rate(NeedleHipLibrary *lib, int sample_rate) {
   if (!lib) return NeedleError_NullArgument;
   if (sample_rate < 2000 || sample_rate > 768000) return NeedleError_InvalidArgument;  // Analyzer::run_pcm's range
-  if (lib->have_pcm) return NeedleError_InvalidArgument;  // must precede set_pcm
+  if (lib->have_pcm || lib->has_formats) return NeedleError_InvalidArgument;  // must precede set_pcm; not beside set_video_formats
   ResampleTiling tiling;  // a rate the resampler has no kernel for is refused here, not at the first set_pcm
   if (sample_rate != kSampleRate) {
     Status s = resample_tiling_host(sample_rate, &tiling);
     if (!s.ok()) return report(s);
   }
   lib->rate = sample_rate;
+  lib->uniform_set = true;
   return NeedleError_Ok;
 }
 
 enum NeedleError needle_hip_library_set_sample_format(NeedleHipLibrary *lib, int format) {
   if (!lib) return NeedleError_NullArgument;
   if (!sample_format_valid(format)) return NeedleError_InvalidArgument;
-  if (lib->have_pcm) return NeedleError_InvalidArgument;  // must precede set_pcm
+  if (lib->have_pcm || lib->has_formats) return NeedleError_InvalidArgument;  // must precede set_pcm; not beside set_video_formats
   lib->format = format;
+  lib->uniform_set = true;
   return NeedleError_Ok;
 }
 
 enum NeedleError needle_hip_library_set_channel_mix(NeedleHipLibrary *lib, const NeedleHipChannelMix *mix) {
   if (!lib) return NeedleError_NullArgument;
-  if (lib->have_pcm) return NeedleError_InvalidArgument;  // must precede set_pcm
+  if (lib->have_pcm || lib->has_formats) return NeedleError_InvalidArgument;  // must precede set_pcm; not beside set_video_formats
   if (mix) {
     Status s = channel_mix_check(*mix, mix->channels);
     if (!s.ok()) return report(s);
     lib->mix = *mix;
   }
   lib->has_mix = mix != nullptr;
+  lib->uniform_set = true;
+  return NeedleError_Ok;
+}
+
+enum NeedleError needle_hip_library_set_video_formats(NeedleHipLibrary *lib, const NeedleHipLaneFormat *formats,
+                                                      const NeedleHipChannelMix *mixes) {
+  if (!lib || !formats) return NeedleError_NullArgument;
+  if (lib->have_pcm || lib->uniform_set) return NeedleError_InvalidArgument;  // before any PCM; not beside the three setters
+  return guarded([&]() -> NeedleError {
+    // every video is checked before anything changes, on the host
+    bool any_mix = false;
+    for (size_t v = 0; v < lib->n; v++) {
+      const NeedleHipChannelMix *mix = mixes && mixes[v].channels ? &mixes[v] : nullptr;
+      Status s = lane_format_check(formats[v], mix, "video " + std::to_string(v));
+      if (!s.ok()) return report(s);
+      any_mix = any_mix || mix;
+    }
+    std::vector<NeedleHipLaneFormat> fs(formats, formats + lib->n);
+    std::vector<NeedleHipChannelMix> ms(lib->n, NeedleHipChannelMix{});
+    if (mixes) ms.assign(mixes, mixes + lib->n);
+    lib->formats.swap(fs);
+    lib->mixes.swap(ms);
+    lib->any_mix = any_mix;
+    lib->has_formats = true;
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_library_video_format(const NeedleHipLibrary *lib, size_t video, NeedleHipLaneFormat *format) {
+  if (!lib || !format) return NeedleError_NullArgument;
+  if (!lib->has_formats || video >= lib->n) return NeedleError_InvalidArgument;
+  *format = lib->formats[video];
   return NeedleError_Ok;
 }
 
@@ -321,6 +363,33 @@ Status check_mix_channels(const NeedleHipLibrary *lib, int channels) {
 // Samples a window of `count` samples at `rate` keeps resident (11025 Hz).
 size_t resident_samples(size_t count, int rate) { return rate == kSampleRate ? count : resample_out_len(count, rate); }
 
+// What plan_windows and rank_videos read per video: the call's one format, or the video's own (set_video_formats).
+struct VideoLayout {
+  int channels, rate, format;
+  size_t planes, width, first_plane;
+};
+struct VideoLayouts {
+  const NeedleHipLibrary *lib;
+  int channels;
+  std::vector<size_t> first;  // formats: where each video's planes begin in the caller's pointer array
+  VideoLayouts(const NeedleHipLibrary *l, int call_channels) : lib(l), channels(call_channels) {
+    if (lib->has_formats) first = format_first_planes(lib->formats.data(), lib->n);
+  }
+  VideoLayout operator()(size_t v) const {
+    if (lib->has_formats) {
+      const NeedleHipLaneFormat &f = lib->formats[v];
+      return VideoLayout{f.channels, f.sample_rate, f.format, first[v + 1] - first[v], sample_format_width(f.format), first[v]};
+    }
+    const size_t planes = sample_format_planes(lib->format, channels);
+    return VideoLayout{channels, lib->rate, lib->format, planes, sample_format_width(lib->format), v * planes};
+  }
+};
+
+// the `channels` of a PCM call or of rank_videos: 1..8 for a library with one format, 0 for one with a format per video
+bool call_channels_ok(const NeedleHipLibrary *lib, int channels) {
+  return lib->has_formats ? channels == 0 : channels >= 1 && channels <= NEEDLE_HIP_MAX_CHANNELS;
+}
+
 // Search windows of every video (analyzer.rs:378,390) from the stream lengths, arena geometry, and -- for the videos
 // whose PCM this rank holds -- where each window starts in the caller's buffer.  `resident`: the windows get offsets
 // into the device PCM arena (set_pcm); otherwise nothing of the PCM is kept (stream_pcm).  `len` is in the caller's
@@ -330,42 +399,45 @@ size_t resident_samples(size_t count, int rate) { return rate == kSampleRate ? c
 // lib->format: `pcm` holds one pointer per video, or -- planar -- one per channel of every video, and `src` gets as many
 // per window (anything but interleaved s16 is converted on the way in, 3-8 channels to mono by the same kernel; with a
 // channel mix everything goes that way and arrives as mono, rematrix.hip).
+// With a format per video (set_video_formats; channels == 0) rate, channels, format and the number of planes are the
+// video's own: `pcm` is the concatenation of every video's planes, every window is resident as 11025 Hz mono, `len` is in
+// the video's own values and `video_of_src` says whose window each entry is.
 Status plan_windows(NeedleHipLibrary *lib, const void *const *pcm, const size_t *num_values, int channels, bool resident,
                     std::vector<const void *> *src, std::vector<size_t> *len, std::vector<uint64_t> *dst,
-                    std::vector<uint64_t> *rows_of_src, uint64_t *total_values) {
+                    std::vector<uint64_t> *rows_of_src, uint64_t *total_values, std::vector<size_t> *video_of_src = nullptr) {
   Status s = ensure_device();
   if (!s.ok()) return s;
   const bool resampled = lib->rate != kSampleRate, converted = lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix;
-  const size_t planes = sample_format_planes(lib->format, channels), width = sample_format_width(lib->format);
-  for (size_t v = 0; v < lib->n; v++)  // a video is held with all its planes or with none
-    for (size_t c = 1; c < planes; c++)
-      if (!pcm[v * planes + c] != !pcm[v * planes])
-        return Status::Make(NeedleError_NullArgument, "video " + std::to_string(v) + " has NULL and non-NULL planes");
-  lib->channels = channels > 2 || resampled || lib->has_mix ? 1 : channels;
+  const VideoLayouts video(lib, channels);
+  std::vector<size_t> first_planes(lib->n + 1);  // a video is held with all its planes or with none
+  for (size_t v = 0; v <= lib->n; v++) first_planes[v] = v < lib->n ? video(v).first_plane : video(v - 1).first_plane + video(v - 1).planes;
+  if (!(s = format_walk_planes(pcm, first_planes)).ok()) return s;
+  lib->channels = lib->has_formats || channels > 2 || resampled || lib->has_mix ? 1 : channels;
   const size_t R = lib->regions();
   lib->win.assign(lib->rows(), Window{});
   uint64_t total = 0;
   uint32_t max_kept = 0;
   std::vector<size_t> first_sample(lib->rows(), 0), source_samples(lib->rows(), 0);
   for (size_t v = 0; v < lib->n; v++) {
-    const size_t samples = num_values[v] / (size_t)channels;
+    const VideoLayout l = video(v);
+    const size_t samples = num_values[v] / (size_t)l.channels;
     size_t open_samples = 0, end_first = 0;
     ns_t seek = 0;
-    s = Analyzer::windows(samples, lib->rate, lib->opening_pct, lib->ending_pct, &open_samples, &end_first, &seek);
+    s = Analyzer::windows(samples, l.rate, lib->opening_pct, lib->ending_pct, &open_samples, &end_first, &seek);
     if (!s.ok()) return s;
     for (size_t r = 0; r < R; r++) {
       Window &w = lib->win[v * R + r];
       const size_t count = r == 0 ? open_samples : samples - end_first;
-      const size_t kept_samples = resident_samples(count, lib->rate);
+      const size_t kept_samples = resident_samples(count, l.rate);
       first_sample[v * R + r] = r == 0 ? 0 : end_first;
       source_samples[v * R + r] = count;
       w.values = kept_samples * (size_t)lib->channels;
       w.kept = (uint32_t)num_kept(kept_samples, lib->step);
       w.seek = r == 0 ? 0 : seek;
       max_kept = std::max(max_kept, w.kept);
-      if (pcm[v * planes] && resident) {
+      if (pcm[l.first_plane] && resident) {
         w.pcm_off = total;
-        total += channels > 2 || resampled || converted ? (w.values + 7) & ~(uint64_t)7 : (w.values + 1) & ~(uint64_t)1;  // (down-mix: 16-byte stores)
+        total += lib->has_formats || channels > 2 || resampled || converted ? (w.values + 7) & ~(uint64_t)7 : (w.values + 1) & ~(uint64_t)1;  // (down-mix: 16-byte stores)
       }
     }
   }
@@ -389,15 +461,17 @@ Status plan_windows(NeedleHipLibrary *lib, const void *const *pcm, const size_t 
     return Status::Make(NeedleError_InvalidArgument, "the adopted hash arena is too small for these videos");
   }
   for (size_t v = 0; v < lib->n; v++) {
+    const VideoLayout l = video(v);
     for (size_t r = 0; r < R; r++) {
       const Window &w = lib->win[v * R + r];
-      if (!pcm[v * planes] || !w.values) continue;
-      for (size_t c = 0; c < planes; c++)  // a plane holds one sample per frame, an interleaved stream `channels`
-        src->push_back(static_cast<const uint8_t *>(pcm[v * planes + c]) +
-                       first_sample[v * R + r] * (planes == 1 ? (size_t)channels : 1) * width);
-      len->push_back(source_samples[v * R + r] * (size_t)channels);
+      if (!pcm[l.first_plane] || !w.values) continue;
+      for (size_t c = 0; c < l.planes; c++)  // a plane holds one sample per frame, an interleaved stream `channels`
+        src->push_back(static_cast<const uint8_t *>(pcm[l.first_plane + c]) +
+                       first_sample[v * R + r] * (l.planes == 1 ? (size_t)l.channels : 1) * l.width);
+      len->push_back(source_samples[v * R + r] * (size_t)l.channels);
       if (dst) dst->push_back(w.pcm_off);
       if (rows_of_src) rows_of_src->push_back(v * R + r);
+      if (video_of_src) video_of_src->push_back(v);
     }
   }
   if (total_values) *total_values = total;
@@ -685,6 +759,107 @@ Status upload_converted(NeedleHipLibrary *lib, const std::vector<const void *> &
   }
   return flush();
 }
+
+// The windows of a library with a format per video (set_video_formats), as plan_windows lists them: window i belongs to
+// video video_of[i] and `src` holds that video's planes for it.
+std::vector<FormatWindow> format_windows(const NeedleHipLibrary *lib, const std::vector<const void *> &src, const std::vector<size_t> &len,
+                                         const std::vector<uint64_t> *dst, const std::vector<size_t> &video_of) {
+  std::vector<FormatWindow> windows(len.size());
+  size_t plane = 0;
+  for (size_t i = 0; i < len.size(); i++) {
+    const NeedleHipLaneFormat &f = lib->formats[video_of[i]];
+    FormatWindow &w = windows[i];
+    for (size_t c = 0; c < sample_format_planes(f.format, f.channels); c++) w.src[c] = src[plane++];
+    w.frames = len[i] / (uint64_t)f.channels;
+    w.channels = f.channels;
+    w.format = f.format;
+    w.rate = f.sample_rate;
+    w.mix = lib->mixes[video_of[i]].channels ? &lib->mixes[video_of[i]] : nullptr;
+    w.dst = dst ? (*dst)[i] : 0;
+  }
+  return windows;
+}
+
+// set_pcm / set_pcm_device of a library with a format per video: every window lands as mono in its place in the resident
+// PCM, whatever the mixture.  The plan is format_plan.h's -- pieces of whole 16-frame groups or of whole output tiles of
+// the window's own rate, batches of at most 2 GiB of staging (NEEDLE_HIP_MAX_BATCH_VALUES values, for tests).  Host
+// windows are staged raw, every plane 16-byte aligned; device windows are read in place.  Per batch: one upload, ONE
+// landing launch (the feeder's ingest kernel, or the rematrix kernel when any video of the library has a mix) that
+// writes 11025 Hz windows straight into the resident PCM and the others into staging, and one resampler launch per
+// distinct rate among those.  All in library-stream order; the caller synchronises.
+Status upload_formatted(NeedleHipLibrary *lib, const std::vector<FormatWindow> &windows, bool from_host, DeviceBuffer<int16_t> *stage) {
+  std::map<int, ResampleTiling> tilings;
+  Status s;
+  for (const FormatWindow &w : windows)
+    if (w.rate != kSampleRate && !tilings.count(w.rate) && !(s = resample_tiling(w.rate, 1, &tilings[w.rate])).ok()) return s;
+  uint64_t limit = 1ull << 30;  // staging in s16 units
+  bool count_values = false;
+  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) {  // tests
+    limit = (uint64_t)std::max(1ll, atoll(e));
+    count_values = true;
+  }
+  FormatPlan plan;
+  if (!(s = format_plan_pieces(windows, tilings, from_host, limit, count_values, &plan)).ok()) return s;
+  if (plan.capacity && !(s = stage->reserve(plan.capacity)).ok()) return s;
+  std::vector<const void *> up_src;
+  std::vector<size_t> up_bytes;
+  std::vector<uint64_t> up_off;
+  std::vector<IngestSpan> land;
+  std::map<int, std::vector<ResampleSpan>> spans;  // by rate
+  auto flush = [&]() -> Status {  // the next batch's copies follow these kernels in stream order
+    Status fs = up_src.empty() ? Status::Ok() : gpu_upload_raw(up_src, up_bytes, up_off, stage->ptr);
+    if (fs.ok() && !land.empty()) fs = lib->any_mix ? gpu_rematrix_device(land, false) : gpu_ingest_device(land, false);
+    for (auto &rs : spans)
+      if (fs.ok()) fs = gpu_resample_device(nullptr, rs.second, 1, rs.first, lib->d_pcm.ptr, false);
+    up_src.clear();
+    up_bytes.clear();
+    up_off.clear();
+    land.clear();
+    spans.clear();
+    return fs;
+  };
+  size_t batch = 0;
+  for (const FormatPiece &pc : plan.pieces) {
+    if (pc.batch != batch) {
+      if (!(s = flush()).ok()) return s;
+      batch = pc.batch;
+    }
+    const FormatWindow &w = windows[pc.window];
+    const uint64_t n = pc.p1 - pc.p0, W = sample_format_width(w.format);
+    const size_t P = sample_format_planes(w.format, w.channels);
+    const uint64_t per_frame = P == 1 ? (uint64_t)w.channels : 1;  // samples of one plane per frame
+    IngestSpan in{};
+    in.frames = n;
+    in.channels = w.channels;
+    in.format = w.format;
+    in.mix = w.mix;
+    for (size_t c = 0; c < P; c++) {
+      const uint8_t *from = static_cast<const uint8_t *>(w.src[c]) + pc.p0 * per_frame * W;  // the piece in the caller's buffer
+      if (from_host) {
+        up_src.push_back(from);
+        up_bytes.push_back(n * per_frame * W);
+        up_off.push_back(pc.raw_off + c * pc.plane_units);
+        in.src[c] = stage->ptr + pc.raw_off + c * pc.plane_units;
+      } else {
+        in.src[c] = from;
+      }
+    }
+    if (w.rate != kSampleRate) {
+      in.dst = stage->ptr + pc.mono_off;
+      ResampleSpan sp{0, w.frames, w.dst};
+      sp.src = in.dst;
+      sp.t0 = pc.t0;
+      sp.t1 = pc.t1;
+      sp.p0 = pc.p0;
+      sp.p1 = pc.p1;
+      spans[w.rate].push_back(sp);
+    } else {
+      in.dst = lib->d_pcm.ptr + w.dst + pc.p0;
+    }
+    land.push_back(in);
+  }
+  return flush();
+}
 }  // namespace
 
 extern "C" {
@@ -692,19 +867,21 @@ extern "C" {
 enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values,
                                             int channels) {
   if (!lib || !pcm || !num_values) return NeedleError_NullArgument;
-  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
+  if (!call_channels_ok(lib, channels)) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     std::vector<const void *> planes;
     std::vector<size_t> len;
     std::vector<uint64_t> dst;
     uint64_t total = 0;
+    std::vector<size_t> video_of;
     Status s = check_mix_channels(lib, channels);
-    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total);
+    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total, &video_of);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
     DeviceBuffer<int16_t> stage;  // (3-8 channels, another rate or another sample format; freed after the drain below)
     const std::vector<const int16_t *> src = as_s16(planes);
-    s = lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix ? upload_converted(lib, planes, len, dst, channels, true, &stage)
+    s = lib->has_formats ? upload_formatted(lib, format_windows(lib, planes, len, &dst, video_of), true, &stage)
+        : lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix ? upload_converted(lib, planes, len, dst, channels, true, &stage)
         : lib->rate != kSampleRate           ? upload_resampled(lib, src, len, dst, channels, true, &stage)
         : channels > 2                       ? upload_mixed(lib, src, len, dst, channels, &stage)
                                              : gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
@@ -721,20 +898,26 @@ enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t
 enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const int16_t *const *d_pcm,
                                                    const size_t *num_values, int channels) {
   if (!lib || !d_pcm || !num_values) return NeedleError_NullArgument;
-  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
+  if (!call_channels_ok(lib, channels)) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     std::vector<const void *> planes;
     std::vector<size_t> len;
     std::vector<uint64_t> dst;
     uint64_t total = 0;
+    std::vector<size_t> video_of;
     Status s = check_mix_channels(lib, channels);
-    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(d_pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total);
+    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(d_pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total, &video_of);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
     hipStream_t stream = library_stream();
     DeviceBuffer<int16_t> stage;  // (3-8 channels at another rate; freed after the drain below)
     const std::vector<const int16_t *> src = as_s16(planes);
-    if (lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix) {  // converted (down-mixed or folded, resampled) straight out of the caller's buffers
+    if (lib->has_formats) {  // a format per video: landed as mono (resampled) straight out of the caller's buffers
+      s = upload_formatted(lib, format_windows(lib, planes, len, &dst, video_of), false, &stage);
+      const bool drained = hipStreamSynchronize(stream) == hipSuccess;
+      if (!s.ok()) return report(s);
+      if (!drained) return report(Status::Make(NeedleError_Unknown, "PCM conversion failed"));
+    } else if (lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix) {  // converted (down-mixed or folded, resampled) straight out of the caller's buffers
       s = upload_converted(lib, planes, len, dst, channels, false, &stage);
       const bool drained = hipStreamSynchronize(stream) == hipSuccess;
       if (!s.ok()) return report(s);
@@ -763,19 +946,21 @@ enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const 
 enum NeedleError needle_hip_library_stream_pcm(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values,
                                                int channels) {
   if (!lib || !pcm || !num_values) return NeedleError_NullArgument;
-  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS) return NeedleError_InvalidArgument;
+  if (!call_channels_ok(lib, channels)) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     std::vector<const void *> planes;
     std::vector<size_t> len;
     std::vector<uint64_t> rows;
     const auto t0 = std::chrono::steady_clock::now();
+    std::vector<size_t> video_of;
     Status s = check_mix_channels(lib, channels);
-    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, false, &planes, &len, nullptr, &rows, nullptr);
+    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, false, &planes, &len, nullptr, &rows, nullptr, &video_of);
     if (!s.ok()) return report(s);
     for (uint64_t &r : rows) r *= lib->stride;  // kept items of a window go straight to its arena row
     const auto t1 = std::chrono::steady_clock::now();
     const std::vector<const int16_t *> src = as_s16(planes);
-    s = lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix
+    s = lib->has_formats ? gpu_fingerprint_formats(format_windows(lib, planes, len, nullptr, video_of), lib->any_mix, lib->step, nullptr, lib->arena, &rows)
+        : lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix
             ? gpu_fingerprint_streamed_device_format(planes, len, channels, lib->format, lib->step, lib->arena, rows, lib->rate,
                                                      lib->has_mix ? &lib->mix : nullptr)
             : gpu_fingerprint_streamed_device(src, len, channels, lib->step, lib->arena, rows, lib->rate);
@@ -1380,7 +1565,7 @@ void needle_hip_comm_shard(size_t units, int world_size, int rank, size_t *first
 enum NeedleError needle_hip_library_rank_videos(const NeedleHipLibrary *lib, const size_t *num_values, int channels, int world_size,
                                                 int rank, size_t *first_video, size_t *video_count) {
   if (!lib || !num_values || !first_video || !video_count) return NeedleError_NullArgument;
-  if (channels < 1 || channels > NEEDLE_HIP_MAX_CHANNELS || world_size < 1 || rank < 0 || rank >= world_size) return NeedleError_InvalidArgument;
+  if (!call_channels_ok(lib, channels) || world_size < 1 || rank < 0 || rank >= world_size) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     // the geometry plan_windows will arrive at for these lengths, without touching the library
     NeedleHipLibrary plan;
@@ -1390,14 +1575,16 @@ enum NeedleError needle_hip_library_rank_videos(const NeedleHipLibrary *lib, con
     const size_t R = plan.regions();
     plan.win.assign(plan.rows(), Window{});
     uint32_t max_kept = 0;
+    const VideoLayouts video(lib, channels);
     for (size_t v = 0; v < plan.n; v++) {
       size_t open_samples = 0, end_first = 0;
       ns_t seek = 0;
-      const size_t samples = num_values[v] / (size_t)channels;
-      Status s = Analyzer::windows(samples, lib->rate, lib->opening_pct, lib->ending_pct, &open_samples, &end_first, &seek);
+      const VideoLayout l = video(v);
+      const size_t samples = num_values[v] / (size_t)l.channels;
+      Status s = Analyzer::windows(samples, l.rate, lib->opening_pct, lib->ending_pct, &open_samples, &end_first, &seek);
       if (!s.ok()) return report(s);
       for (size_t r = 0; r < R; r++) {
-        plan.win[v * R + r].kept = (uint32_t)num_kept(resident_samples(r == 0 ? open_samples : samples - end_first, lib->rate), lib->step);
+        plan.win[v * R + r].kept = (uint32_t)num_kept(resident_samples(r == 0 ? open_samples : samples - end_first, l.rate), lib->step);
         max_kept = std::max(max_kept, plan.win[v * R + r].kept);
       }
     }

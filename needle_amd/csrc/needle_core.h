@@ -63,6 +63,12 @@ class Analyzer {
   Status run_pcm_format(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, int channels,
                         int sample_rate, int format, ns_t hash_duration, bool persist, std::vector<FrameHashesData> *out) const;
 
+  // Same with a format per video (needle_hip.h NeedleHipLaneFormat) and, optionally, a mix per video (channels == 0:
+  // none): `pcm` is the concatenation of every video's planes.  One device pass whatever the mixture; per video the
+  // result is run_pcm_format's for it alone.  Not beside with_channel_mix when `mixes` is given.
+  Status run_pcm_formats(const std::vector<const void *> &pcm, const std::vector<size_t> &num_values, const NeedleHipLaneFormat *formats,
+                         const NeedleHipChannelMix *mixes, ns_t hash_duration, bool persist, std::vector<FrameHashesData> *out) const;
+
   // Window arithmetic at the PCM boundary (DESIGN.md "PCM boundary"): samples per channel of the
   // opening window and first sample / seek offset of the ending window (:378,390).
   static Status windows(size_t total_samples, int sample_rate, float opening_pct, float ending_pct,

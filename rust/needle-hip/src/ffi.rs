@@ -441,6 +441,21 @@ extern "C" {
     pub fn needle_hip_analyzer_set_layout_downmix(analyzer: *mut NeedleAudioAnalyzer, on: bool) -> NeedleError;
     pub fn needle_hip_comparator_set_layout_downmix(comparator: *mut NeedleAudioComparator, on: bool) -> NeedleError;
     pub fn needle_hip_library_set_channel_mix(library: *mut NeedleHipLibrary, mix: *const NeedleHipChannelMix) -> NeedleError;
+    pub fn needle_hip_library_set_video_formats(
+        library: *mut NeedleHipLibrary,
+        formats: *const NeedleHipLaneFormat,
+        mixes: *const NeedleHipChannelMix,
+    ) -> NeedleError;
+    pub fn needle_hip_library_video_format(library: *const NeedleHipLibrary, video: usize, format: *mut NeedleHipLaneFormat) -> NeedleError;
+    pub fn needle_hip_analyzer_run_pcm_formats(
+        analyzer: *mut NeedleAudioAnalyzer,
+        pcm: *const *const c_void,
+        num_values: *const usize,
+        formats: *const NeedleHipLaneFormat,
+        mixes: *const NeedleHipChannelMix,
+        hash_duration: f32,
+        persist: bool,
+    ) -> NeedleError;
     pub fn needle_hip_feeder_set_lane_mix(
         feeder: *mut NeedleHipFeeder,
         lanes: *const usize,

@@ -308,6 +308,41 @@ impl<P: AsRef<Path>> Analyzer<P> {
         unsafe { ffi::needle_audio_analyzer_free(handle) };
         result
     }
+
+    /// `run_pcm_format` with a format per stream and, optionally, a mix per stream (`channels == 0`: the plain average)
+    /// in one device pass (`needle_hip_analyzer_run_pcm_formats`).  `planes` is the concatenation of every stream's
+    /// planes as raw pointers -- one for an interleaved stream, `channels` for a planar one -- and `num_values[i]` counts
+    /// stream i's values over all its channels.
+    ///
+    /// # Safety
+    /// Every plane must hold the samples `formats` and `num_values` describe.
+    pub unsafe fn run_pcm_formats(
+        &self,
+        planes: &[*const std::os::raw::c_void],
+        num_values: &[usize],
+        formats: &[ffi::NeedleHipLaneFormat],
+        mixes: Option<&[ffi::NeedleHipChannelMix]>,
+        hash_duration: Duration,
+        persist: bool,
+    ) -> Result<Vec<FrameHashes>> {
+        assert!(num_values.len() == self.videos.len() && formats.len() == self.videos.len());
+        assert!(mixes.map_or(true, |m| m.len() == self.videos.len()));
+        let expected: usize = formats.iter().map(|f| if f.format >= 5 { f.channels.max(1) as usize } else { 1 }).sum();
+        assert_eq!(planes.len(), expected, "one pointer per plane of every stream");
+        let handle = self.handle()?;
+        let result = check(ffi::needle_hip_analyzer_run_pcm_formats(
+            handle,
+            planes.as_ptr(),
+            num_values.as_ptr(),
+            formats.as_ptr(),
+            mixes.map_or(std::ptr::null(), |m| m.as_ptr()),
+            hash_duration.as_secs_f32(),
+            persist,
+        ))
+        .and_then(|_| self.collect(handle));
+        ffi::needle_audio_analyzer_free(handle);
+        result
+    }
 }
 
 /// comparator.rs:65-69.  The reference keeps the fields private; accessors are an extension.
@@ -1216,6 +1251,45 @@ pub mod multi_gpu {
             unsafe { check(ffi::needle_hip_library_set_sample_format(self.raw, format as c_int))? };
             self.format = format;
             Ok(self)
+        }
+
+        /// A format per video and, optionally, a mix per video (`channels == 0`: the plain average) instead of the three
+        /// setters above, which it excludes (`needle_hip_library_set_video_formats`).  Call before loading; `rank_videos`
+        /// and `load_pcm_formats` then take `channels == 0`.
+        pub fn set_video_formats(&mut self, formats: &[ffi::NeedleHipLaneFormat], mixes: Option<&[ffi::NeedleHipChannelMix]>) -> Result<&mut Self> {
+            assert!(formats.len() == self.num_videos && mixes.map_or(true, |m| m.len() == self.num_videos));
+            let mix_ptr = mixes.map_or(std::ptr::null(), |m| m.as_ptr());
+            unsafe { check(ffi::needle_hip_library_set_video_formats(self.raw, formats.as_ptr(), mix_ptr))? };
+            Ok(self)
+        }
+
+        /// The format of a video of a library that has formats (`needle_hip_library_video_format`).
+        pub fn video_format(&self, video: usize) -> Result<ffi::NeedleHipLaneFormat> {
+            let mut f = ffi::NeedleHipLaneFormat::default();
+            unsafe { check(ffi::needle_hip_library_video_format(self.raw, video, &mut f))? };
+            Ok(f)
+        }
+
+        /// `load_pcm` of a library with a format per video: `planes` is the concatenation of every video's planes as raw
+        /// pointers (one for an interleaved video, `channels` for a planar one; all null for a video another rank owns)
+        /// and `num_values[v]` counts video v's own values.
+        ///
+        /// # Safety
+        /// Every non-null plane must hold the samples the video's format and `num_values` describe.
+        pub unsafe fn load_pcm_formats(&mut self, planes: &[*const std::os::raw::c_void], num_values: &[usize], resident: bool) -> Result<()> {
+            assert!(num_values.len() == self.num_videos);
+            let mut expected = 0usize;
+            for v in 0..self.num_videos {
+                let f = self.video_format(v)?;
+                expected += if f.format >= 5 { f.channels.max(1) as usize } else { 1 };
+            }
+            assert_eq!(planes.len(), expected, "one pointer per plane of every video");
+            let ptrs = planes.as_ptr() as *const *const i16;
+            if resident {
+                check(ffi::needle_hip_library_set_pcm(self.raw, ptrs, num_values.as_ptr(), 0))
+            } else {
+                check(ffi::needle_hip_library_stream_pcm(self.raw, ptrs, num_values.as_ptr(), 0))
+            }
         }
 
         /// The videos `[first, first + count)` whose PCM rank `rank` of `world_size` has to hold: the fingerprinting
