@@ -93,12 +93,8 @@ Status fingerprint_in_batches(const std::vector<size_t> &num_values, int channel
   const size_t n = num_values.size();
   if (items) items->assign(n, {});
   // Batches bounded by bytes so the device arena stays modest for huge libraries.
-  uint64_t kMaxBatchValues = 1ull << 30;  // 2 GiB of s16 (of raw samples, counted in s16 units, in another format)
   bool count_values = false;
-  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) {  // tests (counts values whatever their width)
-    kMaxBatchValues = (uint64_t)std::max(1ll, atoll(e));
-    count_values = true;
-  }
+  const uint64_t kMaxBatchValues = batch_limit(&count_values);  // 2 GiB of s16 (of raw samples, counted in s16 units, in another format)
   uint64_t group_values = (32ull << 20) / sizeof(int16_t);
   if (const char *e = getenv("NEEDLE_HIP_LAUNCH_GROUP_BYTES")) group_values = (uint64_t)std::max(2ll, atoll(e)) / sizeof(int16_t);
   hipStream_t stream = library_stream(), up = upload_stream();
@@ -368,12 +364,8 @@ Status fingerprint_formats_in_batches(const std::vector<FormatWindow> &streams, 
   if (step == 0) return Status::Make(NeedleError_InvalidArgument, "fingerprint: step must be >= 1");
   if (!(s = ensure_device()).ok()) return s;
   if (items) items->assign(n, {});
-  uint64_t kMaxBatchValues = 1ull << 30;  // 2 GiB of raw samples, counted in s16 units
   bool count_values = false;
-  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) {  // tests (counts values whatever their width)
-    kMaxBatchValues = (uint64_t)std::max(1ll, atoll(e));
-    count_values = true;
-  }
+  const uint64_t kMaxBatchValues = batch_limit(&count_values);  // 2 GiB of raw samples, counted in s16 units
   uint64_t group_values = (32ull << 20) / sizeof(int16_t);
   if (const char *e = getenv("NEEDLE_HIP_LAUNCH_GROUP_BYTES")) group_values = (uint64_t)std::max(2ll, atoll(e)) / sizeof(int16_t);
   hipStream_t stream = library_stream(), up = upload_stream();

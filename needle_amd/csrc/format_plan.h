@@ -1,9 +1,11 @@
-// The host plan of a library whose videos have formats of their own (needle_hip_library_set_video_formats): the walk
-// over the caller's pointer array, and the cut of the windows into staged pieces and batches.  Host arithmetic only --
+// The host plan of a library's PCM on its way in, whether every video has the library's one format or a format of its
+// own (needle_hip_library_set_video_formats): the walk over the caller's pointer array, and the cut of the windows into
+// staged pieces and batches, whatever lands them.  Host arithmetic only --
 // no device, no HIP -- so that it can be driven by a stand-alone program (tests/cpp/format_plan_check.cpp).
 #pragma once
 
 #include <algorithm>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <vector>
@@ -48,18 +50,27 @@ inline Status format_walk_planes(const void *const *pcm, const std::vector<size_
   return Status::Ok();
 }
 
+// What lands a window's raw samples as s16 (library.cpp issues the launch): nothing -- interleaved s16 of 1-2 channels is
+// read by the resampler, or copied into the resident PCM, as it is --, gpu_downmix_device, gpu_convert_device,
+// gpu_rematrix_device or gpu_ingest_device.
+enum class Landing { None, Downmix, Convert, Rematrix, Ingest };
+
 // One window this rank holds, in its video's format.
 struct FormatWindow {
   const void *src[NEEDLE_HIP_MAX_CHANNELS] = {};  // the planes (one if interleaved) at the window's first frame
   uint64_t frames = 0;
   int channels = 1, format = NEEDLE_HIP_SAMPLE_S16, rate = kSampleRate;
   const NeedleHipChannelMix *mix = nullptr;  // nullptr: the plain average
-  uint64_t dst = 0;                          // the window's place in the resident mono PCM, in samples
+  uint64_t dst = 0;                          // the window's place in the resident PCM, in s16 values
+  Landing landing = Landing::Ingest;
+  int out_channels = 1;  // of what the landing writes: 2 only for a 2-channel window of a uniform library without a mix
+                         // (Landing::None: of the raw s16 itself, 1 or 2)
 };
 
 // A piece of a window: input frames [p0, p1), staged at raw_off (host windows: plane c at raw_off + c * plane_units) and
-// landed as mono at mono_off of the staging (resampled windows: output tiles [t0, t1) of the window's rate) or straight
-// in the resident PCM at the window's dst + p0.  Offsets in s16 units of the batch's staging buffer.
+// landed at mono_off of the staging -- mono, or the 1-2 channels a uniform library's conversion keeps -- (resampled
+// windows: output tiles [t0, t1) of the window's rate) or straight in the
+// resident PCM at the window's dst + p0 * out_channels.  Offsets in s16 units of the batch's staging buffer.
 struct FormatPiece {
   size_t window = 0, batch = 0;
   uint64_t t0 = 0, t1 = 0, p0 = 0, p1 = 0;
@@ -72,12 +83,23 @@ struct FormatPlan {
   uint64_t capacity = 0;  // s16 units of staging any batch needs at most (0: nothing is staged)
 };
 
+// The staging limit of a batch in s16 units (2 GiB), or -- NEEDLE_HIP_MAX_BATCH_VALUES, tests -- in values whatever their
+// width (*count_values).
+inline uint64_t batch_limit(bool *count_values) {
+  const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES");
+  *count_values = e != nullptr;
+  return e ? (uint64_t)std::max(1ll, atoll(e)) : 1ull << 30;
+}
+
 // Pieces are whole 16-frame groups or, resampled, whole output tiles of the rate's own tiling (`tilings`: one entry per
 // distinct rate other than 11025 Hz) with the input their taps read.  A batch holds at most `limit` s16 units of
-// staging -- raw planes, each 16-byte aligned, and the mono the resampler reads -- or one piece if that is larger.  A
-// piece is given a quarter of that at most, so that a batch goes on filling behind a window's last piece with the next
-// window's first ones, whatever their formats.
-// `count_values` (tests): the limit counts values whatever their width, as NEEDLE_HIP_MAX_BATCH_VALUES does.
+// staging or one piece if that is larger.  Staged are the raw planes of a host window, each 16-byte aligned (a device
+// window is read in place), and what a landing writes for the resampler to read, out_channels values per frame; a
+// window without a landing is resampled out of its raw samples, so a device window of that kind stages nothing and is
+// one piece of all its tiles.  A piece is given a quarter of the limit at most, so that a batch goes on filling behind a
+// window's last piece with the next window's first ones, whatever their formats.
+// `count_values`: the limit counts values whatever their width (batch_limit).
+// (A window with neither a landing nor a resampler has nothing to stage and no launch to feed: library.cpp copies it.)
 inline Status format_plan_pieces(const std::vector<FormatWindow> &windows, const std::map<int, ResampleTiling> &tilings,
                                  bool from_host, uint64_t limit, bool count_values, FormatPlan *out) {
   out->pieces.clear();
@@ -88,23 +110,24 @@ inline Status format_plan_pieces(const std::vector<FormatWindow> &windows, const
   for (size_t i = 0; i < windows.size(); i++) {
     const FormatWindow &w = windows[i];
     if (w.frames == 0) continue;
-    const bool resampled = w.rate != kSampleRate;
-    const uint64_t C = (uint64_t)w.channels, W = sample_format_width(w.format);
+    const bool resampled = w.rate != kSampleRate, landed = resampled && w.landing != Landing::None;
+    const uint64_t C = (uint64_t)w.channels, OC = (uint64_t)w.out_channels, W = sample_format_width(w.format);
     const uint64_t P = sample_format_planes(w.format, w.channels), per_frame = P == 1 ? C : 1;
     uint64_t budget = ~0ull;  // frames per piece
     const uint64_t piece_limit = std::max<uint64_t>(limit / 4, 1);
-    if (from_host || resampled)
-      budget = count_values ? piece_limit / ((from_host ? C : 0) + (resampled ? 1 : 0))
-                            : 2 * piece_limit / ((from_host ? C * W : 0) + (resampled ? 2 : 0));
+    if (from_host || landed)
+      budget = count_values ? piece_limit / ((from_host ? C : 0) + (landed ? OC : 0))
+                            : 2 * piece_limit / ((from_host ? C * W : 0) + (landed ? 2 * OC : 0));
     const size_t first = out->pieces.size();
     if (resampled) {
       const auto it = tilings.find(w.rate);
       if (it == tilings.end()) return Status::Make(NeedleError_InvalidArgument, "no resampler tiling for rate " + std::to_string(w.rate));
       const ResampleTiling &tl = it->second;
       const uint64_t tile_in = tl.tile_outputs * (uint64_t)tl.M / (uint64_t)tl.L + 2 * (uint64_t)tl.half + 16;  // one tile's input at most
-      const uint64_t piece_tiles = std::max<uint64_t>(1, (std::max(budget, tile_in) - 2 * (uint64_t)tl.half - 16) * (uint64_t)tl.L /
-                                                             (tl.tile_outputs * (uint64_t)tl.M));
       const uint64_t tiles = (resample_out_len(w.frames, w.rate) + tl.tile_outputs - 1) / tl.tile_outputs;
+      const uint64_t piece_tiles = budget == ~0ull ? tiles
+                                                   : std::max<uint64_t>(1, (std::max(budget, tile_in) - 2 * (uint64_t)tl.half - 16) *
+                                                                               (uint64_t)tl.L / (tl.tile_outputs * (uint64_t)tl.M));
       for (uint64_t t0 = 0; t0 < tiles; t0 += std::min(piece_tiles, tiles - t0)) {
         FormatPiece pc;
         pc.window = i;
@@ -127,7 +150,7 @@ inline Status format_plan_pieces(const std::vector<FormatWindow> &windows, const
       FormatPiece &pc = out->pieces[k];
       const uint64_t n = pc.p1 - pc.p0;
       pc.plane_units = from_host ? sample_plane_units(n * per_frame, W) : 0;
-      const uint64_t units = P * pc.plane_units + (resampled ? (n + 7) & ~(uint64_t)7 : 0);
+      const uint64_t units = P * pc.plane_units + (landed ? (n * OC + 7) & ~(uint64_t)7 : 0);
       staged.push_back(units);
       total += units;
       largest = std::max(largest, units);

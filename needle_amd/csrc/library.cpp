@@ -483,334 +483,96 @@ Status plan_windows(NeedleHipLibrary *lib, const void *const *pcm, const size_t 
   return Status::Ok();
 }
 
-// set_pcm of 3-8 channel PCM: the windows go to the device in groups through a staging buffer of at most
-// NEEDLE_HIP_MAX_BATCH_VALUES values (2 GiB) and are down-mixed into their places in the resident mono PCM (a window
-// longer than the buffer in pieces of whole 8-frame groups), all in library-stream order; the caller synchronises.
-Status upload_mixed(NeedleHipLibrary *lib, const std::vector<const int16_t *> &src, const std::vector<size_t> &len,
-                    const std::vector<uint64_t> &dst, int channels, DeviceBuffer<int16_t> *stage) {
-  uint64_t max_values = 1ull << 30;
-  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) max_values = (uint64_t)std::max(1ll, atoll(e));  // tests
-  const uint64_t C = (uint64_t)channels;
-  const uint64_t piece = std::max<uint64_t>(8, max_values / C / 8 * 8);  // frames
-  uint64_t total = 0;
-  for (size_t l : len) total += (l + 7) & ~(uint64_t)7;
-  const uint64_t cap = std::max<uint64_t>(std::min(total, max_values), 8 * C) + 8;
-  Status s = stage->reserve(cap);
-  if (!s.ok()) return s;
-  std::vector<const int16_t *> up_src;
-  std::vector<size_t> up_len;
-  std::vector<uint64_t> up_off;
-  std::vector<DownmixSpan> mix;
-  uint64_t used = 0;
-  auto flush = [&]() -> Status {
-    Status fs = up_src.empty() ? Status::Ok() : gpu_upload_pcm(up_src, up_len, up_off, stage->ptr);
-    if (fs.ok() && !mix.empty()) fs = gpu_downmix_device(mix, channels, false);  // the next group's copies follow it in stream order
-    up_src.clear();
-    up_len.clear();
-    up_off.clear();
-    mix.clear();
-    used = 0;
-    return fs;
-  };
-  for (size_t i = 0; i < src.size(); i++) {
-    const uint64_t frames = len[i] / C;
-    for (uint64_t f = 0; f < frames; f += piece) {
-      const uint64_t n = std::min(piece, frames - f), values = (n * C + 7) & ~(uint64_t)7;
-      if (used + values > cap && !(s = flush()).ok()) return s;
-      up_src.push_back(src[i] + f * C);
-      up_len.push_back(n * C);
-      up_off.push_back(used);
-      mix.push_back(DownmixSpan{stage->ptr + used, lib->d_pcm.ptr + dst[i] + f, n});
-      used += values;
-    }
-  }
-  return flush();
-}
-
-// set_pcm / set_pcm_device at a rate other than 11025 Hz: the windows are resampled on the device (resample.hip) into
-// their places in the resident mono PCM.  1-2 channel device windows are read straight out of the caller's buffers.  Host
-// windows, and 3-8 channel device windows (down-mixed first, at the source rate), go through a staging buffer of at most
-// NEEDLE_HIP_MAX_BATCH_VALUES values (2 GiB): a window is cut into pieces of whole output tiles of the resampler, each
-// staged with the input samples its tiles' taps read (one piece per window unless the window is longer than the buffer;
-// the output is bit for bit the whole window's).  All in library-stream order; the caller synchronises.
-Status upload_resampled(NeedleHipLibrary *lib, const std::vector<const int16_t *> &src, const std::vector<size_t> &len,
-                        const std::vector<uint64_t> &dst, int channels, bool from_host, DeviceBuffer<int16_t> *stage) {
-  const int rate = lib->rate, rs_channels = channels > 2 ? 1 : channels;  // (what the resampler reads)
-  const uint64_t C = (uint64_t)channels;
-  ResampleTiling tl;
-  Status s = resample_tiling(rate, rs_channels, &tl);
-  if (!s.ok()) return s;
-  if (!from_host && channels <= 2) {
-    std::vector<ResampleSpan> spans;
-    for (size_t i = 0; i < src.size(); i++) {
-      ResampleSpan sp{0, len[i] / C, dst[i]};
-      sp.src = src[i];
-      spans.push_back(sp);
-    }
-    return gpu_resample_device(nullptr, spans, channels, rate, lib->d_pcm.ptr, false);
-  }
-  uint64_t max_values = 1ull << 30;
-  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) max_values = (uint64_t)std::max(1ll, atoll(e));  // tests
-  // staged values per input sample: the frame uploaded (host) and its down-mixed sample (3-8 channels)
-  const uint64_t per_sample = (from_host ? C : 0) + (channels > 2 ? 1 : 0);
-  const uint64_t tile_in = tl.tile_outputs * (uint64_t)tl.M / (uint64_t)tl.L + 2 * (uint64_t)tl.half + 16;  // one tile's input at most
-  const uint64_t budget = std::max(max_values / per_sample, tile_in);  // input samples per piece at most
-  const uint64_t piece_tiles = std::max<uint64_t>(1, (budget - 2 * (uint64_t)tl.half - 16) * (uint64_t)tl.L /
-                                                         (tl.tile_outputs * (uint64_t)tl.M));
-  auto staged = [&](uint64_t samples) {  // staging values one piece takes, every part 16-byte aligned
-    return (from_host ? (samples * C + 7) & ~(uint64_t)7 : 0) + (channels > 2 ? (samples + 7) & ~(uint64_t)7 : 0);
-  };
-  struct Piece {
-    size_t i;
-    uint64_t t0, t1, p0, p1;
-  };
-  std::vector<Piece> pieces;
-  uint64_t total = 0, largest = 0;
-  for (size_t i = 0; i < src.size(); i++) {
-    const uint64_t n_in = len[i] / C, tiles = (resample_out_len(n_in, rate) + tl.tile_outputs - 1) / tl.tile_outputs;
-    for (uint64_t t0 = 0; t0 < tiles; t0 += piece_tiles) {
-      Piece pc{i, t0, std::min(tiles, t0 + piece_tiles), 0, 0};
-      resample_piece(tl, n_in, pc.t0, pc.t1, &pc.p0, &pc.p1);
-      pieces.push_back(pc);
-      total += staged(pc.p1 - pc.p0);
-      largest = std::max(largest, staged(pc.p1 - pc.p0));
-    }
-  }
-  const uint64_t cap = std::max(std::min(total, max_values), largest) + 8;
-  if (!(s = stage->reserve(cap)).ok()) return s;
-  std::vector<const int16_t *> up_src;
-  std::vector<size_t> up_len;
-  std::vector<uint64_t> up_off;
-  std::vector<DownmixSpan> mix;
-  std::vector<ResampleSpan> spans;
-  uint64_t used = 0;
-  auto flush = [&]() -> Status {  // the next group's copies follow these kernels in stream order
-    Status fs = up_src.empty() ? Status::Ok() : gpu_upload_pcm(up_src, up_len, up_off, stage->ptr);
-    if (fs.ok() && !mix.empty()) fs = gpu_downmix_device(mix, channels, false);
-    if (fs.ok() && !spans.empty()) fs = gpu_resample_device(nullptr, spans, rs_channels, rate, lib->d_pcm.ptr, false);
-    up_src.clear();
-    up_len.clear();
-    up_off.clear();
-    mix.clear();
-    spans.clear();
-    used = 0;
-    return fs;
-  };
-  for (const Piece &pc : pieces) {
-    const uint64_t n = pc.p1 - pc.p0;
-    if (used + staged(n) > cap && !(s = flush()).ok()) return s;
-    const int16_t *from = src[pc.i] + pc.p0 * C;  // the piece in the caller's buffer
-    if (from_host) {
-      up_src.push_back(from);
-      up_len.push_back(n * C);
-      up_off.push_back(used);
-      from = stage->ptr + used;
-      used += (n * C + 7) & ~(uint64_t)7;
-    }
-    if (channels > 2) {
-      mix.push_back(DownmixSpan{from, stage->ptr + used, n});
-      from = stage->ptr + used;
-      used += (n + 7) & ~(uint64_t)7;
-    }
-    ResampleSpan sp{0, len[pc.i] / C, dst[pc.i]};
-    sp.src = from;
-    sp.t0 = pc.t0;
-    sp.t1 = pc.t1;
-    sp.p0 = pc.p0;
-    sp.p1 = pc.p1;
-    spans.push_back(sp);
-  }
-  return flush();
-}
-
 std::vector<const int16_t *> as_s16(const std::vector<const void *> &src) {
   std::vector<const int16_t *> out(src.size());
   for (size_t i = 0; i < src.size(); i++) out[i] = static_cast<const int16_t *>(src[i]);
   return out;
 }
 
-// set_pcm / set_pcm_device in another sample format than interleaved s16 (lib->format): the windows are converted on the
-// device (convert.hip; 3-8 channels with the down-mix fused in) into their places in the resident PCM or, at another
-// rate than 11025 Hz, into staging from which the resampler writes them there.  Host windows are staged raw, every plane
-// 16-byte aligned; device windows are read straight out of the caller's buffers.  The staging buffer is bounded in BYTES
-// (2 GiB; NEEDLE_HIP_MAX_BATCH_VALUES counts values, for tests): a window is cut into pieces of whole 16-frame groups or,
-// resampled, of whole output tiles with the input their taps read, as upload_resampled does.  `src` holds
-// sample_format_planes() pointers per window.  All in library-stream order; the caller synchronises.
-// With a channel mix (lib->has_mix) this is the way in for every format and channel count, interleaved s16 and 1-2
-// channels included: rematrix.hip takes the conversion's place and its output is mono.
-Status upload_converted(NeedleHipLibrary *lib, const std::vector<const void *> &src, const std::vector<size_t> &len,
-                        const std::vector<uint64_t> &dst, int channels, bool from_host, DeviceBuffer<int16_t> *stage) {
-  const int format = lib->format, rate = lib->rate;
-  const bool resampled = rate != kSampleRate, mix = channels > 2 || lib->has_mix;
-  const int out_channels = mix ? 1 : channels;  // of the converted s16
-  const uint64_t C = (uint64_t)channels, OC = (uint64_t)out_channels, W = sample_format_width(format);
-  const size_t P = sample_format_planes(format, channels);
-  const uint64_t per_frame = P == 1 ? C : 1;  // samples of one plane per frame
-  ResampleTiling tl;
-  Status s = resampled ? resample_tiling(rate, out_channels, &tl) : Status::Ok();
-  if (!s.ok()) return s;
-  uint64_t limit = 1ull << 30, budget = ~0ull;  // staging in s16 units; frames per piece
-  bool count_values = false;
-  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) {  // tests
-    limit = (uint64_t)std::max(1ll, atoll(e));
-    count_values = true;
-  }
-  if (from_host || resampled)
-    budget = count_values ? limit / ((from_host ? C : 0) + (resampled ? OC : 0))
-                          : 2 * limit / ((from_host ? C * W : 0) + (resampled ? 2 * OC : 0));
-  auto staged = [&](uint64_t frames) {  // staging units one piece takes, every part 16-byte aligned
-    return (from_host ? P * sample_plane_units(frames * per_frame, W) : 0) + (resampled ? (frames * OC + 7) & ~(uint64_t)7 : 0);
-  };
-  struct Piece {
-    size_t i;
-    uint64_t t0, t1, p0, p1;
-  };
-  std::vector<Piece> pieces;
-  uint64_t total = 0, largest = 0;
-  for (size_t i = 0; i < len.size(); i++) {
-    const uint64_t frames = len[i] / C;
-    if (resampled) {
-      const uint64_t tile_in = tl.tile_outputs * (uint64_t)tl.M / (uint64_t)tl.L + 2 * (uint64_t)tl.half + 16;  // one tile's input at most
-      const uint64_t piece_tiles = std::max<uint64_t>(1, (std::max(budget, tile_in) - 2 * (uint64_t)tl.half - 16) * (uint64_t)tl.L /
-                                                             (tl.tile_outputs * (uint64_t)tl.M));
-      const uint64_t tiles = (resample_out_len(frames, rate) + tl.tile_outputs - 1) / tl.tile_outputs;
-      for (uint64_t t0 = 0; t0 < tiles; t0 += std::min(piece_tiles, tiles - t0)) {
-        Piece pc{i, t0, std::min(tiles, t0 + piece_tiles), 0, 0};
-        resample_piece(tl, frames, pc.t0, pc.t1, &pc.p0, &pc.p1);
-        pieces.push_back(pc);
-      }
-    } else {
-      const uint64_t piece_frames = std::max<uint64_t>(16, budget / 16 * 16);
-      for (uint64_t f = 0; f < frames; f += std::min(piece_frames, frames - f))
-        pieces.push_back(Piece{i, 0, 0, f, f + std::min(piece_frames, frames - f)});
-    }
-  }
-  for (const Piece &pc : pieces) {
-    total += staged(pc.p1 - pc.p0);
-    largest = std::max(largest, staged(pc.p1 - pc.p0));
-  }
-  const uint64_t cap = std::max(std::min(total, limit), largest) + 8;
-  if (total && !(s = stage->reserve(cap)).ok()) return s;
-  std::vector<const void *> up_src;
-  std::vector<size_t> up_bytes;
-  std::vector<uint64_t> up_off;
-  std::vector<ConvertSpan> convert;
-  std::vector<ResampleSpan> spans;
-  uint64_t used = 0;
-  auto flush = [&]() -> Status {  // the next group's copies follow these kernels in stream order
-    Status fs = up_src.empty() ? Status::Ok() : gpu_upload_raw(up_src, up_bytes, up_off, stage->ptr);
-    if (fs.ok() && !convert.empty() && lib->has_mix) {
-      std::vector<IngestSpan> fold;
-      for (const ConvertSpan &cv : convert) {
-        IngestSpan in{};
-        std::memcpy(in.src, cv.src, sizeof(in.src));
-        in.dst = cv.dst;
-        in.frames = cv.frames;
-        in.channels = channels;
-        in.format = format;
-        in.mix = &lib->mix;
-        fold.push_back(in);
-      }
-      fs = gpu_rematrix_device(fold, false);
-    } else if (fs.ok() && !convert.empty()) {
-      fs = gpu_convert_device(convert, channels, format, mix, false);
-    }
-    if (fs.ok() && !spans.empty()) fs = gpu_resample_device(nullptr, spans, out_channels, rate, lib->d_pcm.ptr, false);
-    up_src.clear();
-    up_bytes.clear();
-    up_off.clear();
-    convert.clear();
-    spans.clear();
-    used = 0;
-    return fs;
-  };
-  for (const Piece &pc : pieces) {
-    const uint64_t n = pc.p1 - pc.p0;
-    if (n == 0) continue;
-    if (total && used + staged(n) > cap && !(s = flush()).ok()) return s;
-    ConvertSpan cv{};
-    cv.frames = n;
-    for (size_t c = 0; c < P; c++) {
-      const uint8_t *from = static_cast<const uint8_t *>(src[pc.i * P + c]) + pc.p0 * per_frame * W;  // the piece in the caller's buffer
-      if (from_host) {
-        up_src.push_back(from);
-        up_bytes.push_back(n * per_frame * W);
-        up_off.push_back(used);
-        cv.src[c] = stage->ptr + used;
-        used += sample_plane_units(n * per_frame, W);
-      } else {
-        cv.src[c] = from;
-      }
-    }
-    if (resampled) {
-      cv.dst = stage->ptr + used;
-      ResampleSpan sp{0, len[pc.i] / C, dst[pc.i]};
-      sp.src = cv.dst;
-      sp.t0 = pc.t0;
-      sp.t1 = pc.t1;
-      sp.p0 = pc.p0;
-      sp.p1 = pc.p1;
-      spans.push_back(sp);
-      used += (n * OC + 7) & ~(uint64_t)7;
-    } else {
-      cv.dst = lib->d_pcm.ptr + dst[pc.i] + pc.p0 * OC;
-    }
-    convert.push_back(cv);
-  }
-  return flush();
-}
-
-// The windows of a library with a format per video (set_video_formats), as plan_windows lists them: window i belongs to
-// video video_of[i] and `src` holds that video's planes for it.
-std::vector<FormatWindow> format_windows(const NeedleHipLibrary *lib, const std::vector<const void *> &src, const std::vector<size_t> &len,
-                                         const std::vector<uint64_t> *dst, const std::vector<size_t> &video_of) {
+// The windows plan_windows lists, as the plan (format_plan.h) and the launches read them: window i belongs to video
+// video_of[i] and `src` holds that video's planes for it.  Rate, channels, format and mix are the video's own
+// (set_video_formats) or the library's, from its setters and the call's `channels`; so is the landing.  A uniform
+// library keeps the kernel its route always had -- the conversion kernels run at 79-81 % of the copy rate, the ingest
+// and rematrix kernels at 42-53 % -- and its 1-2 channels stay 1-2 channels behind it unless a mix folds them.
+std::vector<FormatWindow> format_windows(const NeedleHipLibrary *lib, int channels, const std::vector<const void *> &src,
+                                         const std::vector<size_t> &len, const std::vector<uint64_t> *dst,
+                                         const std::vector<size_t> &video_of) {
   std::vector<FormatWindow> windows(len.size());
   size_t plane = 0;
   for (size_t i = 0; i < len.size(); i++) {
-    const NeedleHipLaneFormat &f = lib->formats[video_of[i]];
+    const size_t v = video_of[i];
+    const NeedleHipLaneFormat f = lib->has_formats ? lib->formats[v] : NeedleHipLaneFormat{channels, lib->rate, lib->format};
     FormatWindow &w = windows[i];
     for (size_t c = 0; c < sample_format_planes(f.format, f.channels); c++) w.src[c] = src[plane++];
     w.frames = len[i] / (uint64_t)f.channels;
     w.channels = f.channels;
     w.format = f.format;
     w.rate = f.sample_rate;
-    w.mix = lib->mixes[video_of[i]].channels ? &lib->mixes[video_of[i]] : nullptr;
     w.dst = dst ? (*dst)[i] : 0;
+    if (lib->has_formats) {
+      w.mix = lib->mixes[v].channels ? &lib->mixes[v] : nullptr;
+      w.landing = lib->any_mix ? Landing::Rematrix : Landing::Ingest;
+    } else {
+      w.mix = lib->has_mix ? &lib->mix : nullptr;
+      w.landing = lib->has_mix                         ? Landing::Rematrix
+                  : f.format != NEEDLE_HIP_SAMPLE_S16  ? Landing::Convert
+                  : channels > 2                       ? Landing::Downmix
+                                                       : Landing::None;
+      w.out_channels = lib->has_mix || channels > 2 ? 1 : channels;
+    }
   }
   return windows;
 }
 
-// set_pcm / set_pcm_device of a library with a format per video: every window lands as mono in its place in the resident
-// PCM, whatever the mixture.  The plan is format_plan.h's -- pieces of whole 16-frame groups or of whole output tiles of
-// the window's own rate, batches of at most 2 GiB of staging (NEEDLE_HIP_MAX_BATCH_VALUES values, for tests).  Host
-// windows are staged raw, every plane 16-byte aligned; device windows are read in place.  Per batch: one upload, ONE
-// landing launch (the feeder's ingest kernel, or the rematrix kernel when any video of the library has a mix) that
-// writes 11025 Hz windows straight into the resident PCM and the others into staging, and one resampler launch per
-// distinct rate among those.  All in library-stream order; the caller synchronises.
-Status upload_formatted(NeedleHipLibrary *lib, const std::vector<FormatWindow> &windows, bool from_host, DeviceBuffer<int16_t> *stage) {
+// One launch of landing kernel `kind` over the spans of a batch (Downmix and Convert: of one channel count and format,
+// a uniform library's).
+Status launch_landing(Landing kind, const std::vector<IngestSpan> &spans) {
+  const int channels = spans.front().channels, format = spans.front().format;
+  if (kind == Landing::Downmix) {
+    std::vector<DownmixSpan> mix;
+    for (const IngestSpan &sp : spans) mix.push_back(DownmixSpan{static_cast<const int16_t *>(sp.src[0]), sp.dst, sp.frames});
+    return gpu_downmix_device(mix, channels, false);
+  }
+  if (kind == Landing::Convert) {
+    std::vector<ConvertSpan> convert(spans.size());
+    for (size_t i = 0; i < spans.size(); i++) {
+      std::memcpy(convert[i].src, spans[i].src, sizeof(convert[i].src));
+      convert[i].dst = spans[i].dst;
+      convert[i].frames = spans[i].frames;
+    }
+    return gpu_convert_device(convert, channels, format, channels > 2, false);  // 3-8 channels: the down-mix fused in
+  }
+  return kind == Landing::Rematrix ? gpu_rematrix_device(spans, false) : gpu_ingest_device(spans, false);
+}
+
+// set_pcm / set_pcm_device: every window that needs a kernel on its way lands in its place in the resident PCM.  The
+// plan is format_plan.h's -- pieces of whole 16-frame groups or of whole output tiles of the window's own rate, batches
+// of at most 2 GiB of staging (NEEDLE_HIP_MAX_BATCH_VALUES values, for tests).  Host windows are staged raw, every plane
+// 16-byte aligned; device windows are read in place.  Per batch: one upload, one landing launch (a library has one kind
+// of landing, format_windows) that writes 11025 Hz windows straight into the resident PCM and the others into staging,
+// and one resampler launch per distinct (rate, channels) among those; a window without a landing is resampled out of
+// its raw samples, staged or the caller's.  All in library-stream order; the caller synchronises.
+Status land_windows(NeedleHipLibrary *lib, const std::vector<FormatWindow> &windows, bool from_host, DeviceBuffer<int16_t> *stage) {
   std::map<int, ResampleTiling> tilings;
   Status s;
   for (const FormatWindow &w : windows)
-    if (w.rate != kSampleRate && !tilings.count(w.rate) && !(s = resample_tiling(w.rate, 1, &tilings[w.rate])).ok()) return s;
-  uint64_t limit = 1ull << 30;  // staging in s16 units
+    if (w.rate != kSampleRate && !tilings.count(w.rate) && !(s = resample_tiling(w.rate, w.out_channels, &tilings[w.rate])).ok()) return s;
   bool count_values = false;
-  if (const char *e = getenv("NEEDLE_HIP_MAX_BATCH_VALUES")) {  // tests
-    limit = (uint64_t)std::max(1ll, atoll(e));
-    count_values = true;
-  }
+  const uint64_t limit = batch_limit(&count_values);
   FormatPlan plan;
   if (!(s = format_plan_pieces(windows, tilings, from_host, limit, count_values, &plan)).ok()) return s;
   if (plan.capacity && !(s = stage->reserve(plan.capacity)).ok()) return s;
   std::vector<const void *> up_src;
   std::vector<size_t> up_bytes;
   std::vector<uint64_t> up_off;
-  std::vector<IngestSpan> land;
-  std::map<int, std::vector<ResampleSpan>> spans;  // by rate
+  std::map<Landing, std::vector<IngestSpan>> land;
+  std::map<std::pair<int, int>, std::vector<ResampleSpan>> spans;  // by (rate, channels)
   auto flush = [&]() -> Status {  // the next batch's copies follow these kernels in stream order
     Status fs = up_src.empty() ? Status::Ok() : gpu_upload_raw(up_src, up_bytes, up_off, stage->ptr);
-    if (fs.ok() && !land.empty()) fs = lib->any_mix ? gpu_rematrix_device(land, false) : gpu_ingest_device(land, false);
+    for (auto &l : land)
+      if (fs.ok()) fs = launch_landing(l.first, l.second);
     for (auto &rs : spans)
-      if (fs.ok()) fs = gpu_resample_device(nullptr, rs.second, 1, rs.first, lib->d_pcm.ptr, false);
+      if (fs.ok()) fs = gpu_resample_device(nullptr, rs.second, rs.first.second, rs.first.first, lib->d_pcm.ptr, false);
     up_src.clear();
     up_bytes.clear();
     up_off.clear();
@@ -844,28 +606,27 @@ Status upload_formatted(NeedleHipLibrary *lib, const std::vector<FormatWindow> &
         in.src[c] = from;
       }
     }
+    const int16_t *landed = static_cast<const int16_t *>(in.src[0]);  // no landing: the raw s16 itself
+    if (w.landing != Landing::None) {
+      in.dst = w.rate != kSampleRate ? stage->ptr + pc.mono_off : lib->d_pcm.ptr + w.dst + pc.p0 * (uint64_t)w.out_channels;
+      landed = in.dst;
+      land[w.landing].push_back(in);
+    }
     if (w.rate != kSampleRate) {
-      in.dst = stage->ptr + pc.mono_off;
       ResampleSpan sp{0, w.frames, w.dst};
-      sp.src = in.dst;
+      sp.src = landed;
       sp.t0 = pc.t0;
       sp.t1 = pc.t1;
       sp.p0 = pc.p0;
       sp.p1 = pc.p1;
-      spans[w.rate].push_back(sp);
-    } else {
-      in.dst = lib->d_pcm.ptr + w.dst + pc.p0;
+      spans[{w.rate, w.out_channels}].push_back(sp);
     }
-    land.push_back(in);
   }
   return flush();
 }
-}  // namespace
 
-extern "C" {
-
-enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values,
-                                            int channels) {
+// needle_hip_library_set_pcm (from_host) and needle_hip_library_set_pcm_device
+NeedleError set_pcm_from(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values, int channels, bool from_host) {
   if (!lib || !pcm || !num_values) return NeedleError_NullArgument;
   if (!call_channels_ok(lib, channels)) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
@@ -878,69 +639,41 @@ enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t
     if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total, &video_of);
     if (!s.ok()) return report(s);
     if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
-    DeviceBuffer<int16_t> stage;  // (3-8 channels, another rate or another sample format; freed after the drain below)
-    const std::vector<const int16_t *> src = as_s16(planes);
-    s = lib->has_formats ? upload_formatted(lib, format_windows(lib, planes, len, &dst, video_of), true, &stage)
-        : lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix ? upload_converted(lib, planes, len, dst, channels, true, &stage)
-        : lib->rate != kSampleRate           ? upload_resampled(lib, src, len, dst, channels, true, &stage)
-        : channels > 2                       ? upload_mixed(lib, src, len, dst, channels, &stage)
-                                             : gpu_upload_pcm(src, len, dst, lib->d_pcm.ptr);
-    // also on the error path: copies already enqueued read the caller's buffers asynchronously
-    const bool drained = hipStreamSynchronize(library_stream()) == hipSuccess;
+    hipStream_t stream = library_stream();
+    DeviceBuffer<int16_t> stage;  // (freed after the drain below)
+    const std::vector<FormatWindow> windows = format_windows(lib, channels, planes, len, &dst, video_of);
+    // 1-2 channel s16 at 11025 Hz without a mix is resident as it is: nothing to stage, nothing to launch
+    const bool as_it_is = !windows.empty() && windows[0].landing == Landing::None && windows[0].rate == kSampleRate;
+    if (!as_it_is) {
+      s = land_windows(lib, windows, from_host, &stage);
+    } else if (from_host) {
+      s = gpu_upload_pcm(as_s16(planes), len, dst, lib->d_pcm.ptr);
+    } else {
+      for (size_t i = 0; i < len.size() && s.ok(); i++)  // the search windows only, device to device, in stream order
+        if (hipMemcpyAsync(lib->d_pcm.ptr + dst[i], planes[i], len[i] * sizeof(int16_t), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+          s = Status::Make(NeedleError_Unknown, "device-to-device PCM copy failed");
+    }
+    // also on the error path: copies and kernels already enqueued read the caller's buffers asynchronously
+    const bool drained = hipStreamSynchronize(stream) == hipSuccess;
     if (!s.ok()) return report(s);
-    if (!drained) return report(Status::Make(NeedleError_Unknown, "PCM upload failed"));
+    if (!drained) return report(Status::Make(NeedleError_Unknown, "PCM transfer failed"));
     lib->have_pcm = true;
     lib->pcm_resident = true;
     return NeedleError_Ok;
   });
 }
+}  // namespace
+
+extern "C" {
+
+enum NeedleError needle_hip_library_set_pcm(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values,
+                                            int channels) {
+  return set_pcm_from(lib, pcm, num_values, channels, true);
+}
 
 enum NeedleError needle_hip_library_set_pcm_device(NeedleHipLibrary *lib, const int16_t *const *d_pcm,
                                                    const size_t *num_values, int channels) {
-  if (!lib || !d_pcm || !num_values) return NeedleError_NullArgument;
-  if (!call_channels_ok(lib, channels)) return NeedleError_InvalidArgument;
-  return guarded([&]() -> NeedleError {
-    std::vector<const void *> planes;
-    std::vector<size_t> len;
-    std::vector<uint64_t> dst;
-    uint64_t total = 0;
-    std::vector<size_t> video_of;
-    Status s = check_mix_channels(lib, channels);
-    if (s.ok()) s = plan_windows(lib, reinterpret_cast<const void *const *>(d_pcm), num_values, channels, true, &planes, &len, &dst, nullptr, &total, &video_of);
-    if (!s.ok()) return report(s);
-    if (!(s = lib->d_pcm.reserve(std::max<uint64_t>(total, 1))).ok()) return report(s);
-    hipStream_t stream = library_stream();
-    DeviceBuffer<int16_t> stage;  // (3-8 channels at another rate; freed after the drain below)
-    const std::vector<const int16_t *> src = as_s16(planes);
-    if (lib->has_formats) {  // a format per video: landed as mono (resampled) straight out of the caller's buffers
-      s = upload_formatted(lib, format_windows(lib, planes, len, &dst, video_of), false, &stage);
-      const bool drained = hipStreamSynchronize(stream) == hipSuccess;
-      if (!s.ok()) return report(s);
-      if (!drained) return report(Status::Make(NeedleError_Unknown, "PCM conversion failed"));
-    } else if (lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix) {  // converted (down-mixed or folded, resampled) straight out of the caller's buffers
-      s = upload_converted(lib, planes, len, dst, channels, false, &stage);
-      const bool drained = hipStreamSynchronize(stream) == hipSuccess;
-      if (!s.ok()) return report(s);
-      if (!drained) return report(Status::Make(NeedleError_Unknown, "PCM conversion failed"));
-    } else if (lib->rate != kSampleRate) {  // resampled out of the caller's buffers (3-8 channels: down-mixed into staging first)
-      s = upload_resampled(lib, src, len, dst, channels, false, &stage);
-      const bool drained = hipStreamSynchronize(stream) == hipSuccess;
-      if (!s.ok()) return report(s);
-      if (!drained) return report(Status::Make(NeedleError_Unknown, "PCM resampling failed"));
-    } else if (channels > 2) {  // the search windows are down-mixed straight out of the caller's buffers into the resident mono PCM
-      std::vector<DownmixSpan> mix;
-      for (size_t i = 0; i < src.size(); i++) mix.push_back(DownmixSpan{src[i], lib->d_pcm.ptr + dst[i], len[i] / (size_t)channels});
-      if (!(s = gpu_downmix_device(mix, channels, false)).ok()) return report(s);
-    } else {
-      for (size_t i = 0; i < src.size(); i++)  // the search windows only, device to device, in stream order
-        if (hipMemcpyAsync(lib->d_pcm.ptr + dst[i], src[i], len[i] * sizeof(int16_t), hipMemcpyDeviceToDevice, stream) != hipSuccess)
-          return report(Status::Make(NeedleError_Unknown, "device-to-device PCM copy failed"));
-    }
-    if (hipStreamSynchronize(stream) != hipSuccess) return report(Status::Make(NeedleError_Unknown, "PCM copy failed"));
-    lib->have_pcm = true;
-    lib->pcm_resident = true;
-    return NeedleError_Ok;
-  });
+  return set_pcm_from(lib, d_pcm, num_values, channels, false);
 }
 
 enum NeedleError needle_hip_library_stream_pcm(NeedleHipLibrary *lib, const int16_t *const *pcm, const size_t *num_values,
@@ -959,7 +692,7 @@ enum NeedleError needle_hip_library_stream_pcm(NeedleHipLibrary *lib, const int1
     for (uint64_t &r : rows) r *= lib->stride;  // kept items of a window go straight to its arena row
     const auto t1 = std::chrono::steady_clock::now();
     const std::vector<const int16_t *> src = as_s16(planes);
-    s = lib->has_formats ? gpu_fingerprint_formats(format_windows(lib, planes, len, nullptr, video_of), lib->any_mix, lib->step, nullptr, lib->arena, &rows)
+    s = lib->has_formats ? gpu_fingerprint_formats(format_windows(lib, channels, planes, len, nullptr, video_of), lib->any_mix, lib->step, nullptr, lib->arena, &rows)
         : lib->format != NEEDLE_HIP_SAMPLE_S16 || lib->has_mix
             ? gpu_fingerprint_streamed_device_format(planes, len, channels, lib->format, lib->step, lib->arena, rows, lib->rate,
                                                      lib->has_mix ? &lib->mix : nullptr)

@@ -1,8 +1,9 @@
-// The host plan of a library whose videos have formats of their own (needle_amd/csrc/format_plan.h), under ASan/UBSan:
-// the walk over the pointer array with planar and NULL videos, and the cut of every window into pieces and batches, per
-// rate, from the host and from the device, whole and with staging limits that force many pieces and one tile per piece.
-// Every source plane and the staging buffer are allocated at exactly their size and the uploads are replayed with memcpy,
-// so a piece that reads past its plane or lands past the staging is an ASan report.  Host code only, no GPU.
+// The host plan of a library's PCM on its way in (needle_amd/csrc/format_plan.h), under ASan/UBSan: the walk over the
+// pointer array with planar and NULL videos, and the cut of every window into pieces and batches, per rate, from the
+// host and from the device, whole and with staging limits that force many pieces and one tile per piece -- for a season
+// with a format per video and for uniform libraries of every landing kind.  Every source plane and the staging buffer
+// are allocated at exactly their size and the uploads and landings are replayed with memcpy / memset, so a piece that
+// reads past its plane or lands past the staging is an ASan report.  Host code only, no GPU.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,13 +47,28 @@ static void check_walk() {
   CHECK(format_walk_planes(pcm.data(), first, &held).code == NeedleError_NullArgument);
 }
 
-static void check_plan(bool from_host, uint64_t limit, bool count_values, size_t *pieces_out, size_t *mixed_batches_out) {
+// The uniform libraries of library.cpp's format_windows, one per landing kind: what the resampler reads is the raw
+// stereo (no landing), the down-mixed or rematrixed mono, or the converted 1-2 channels; two land at 11025 Hz.
+struct Uniform {
+  NeedleHipLaneFormat format;
+  Landing landing;
+  int out_channels;
+};
+static const Uniform kUniform[7] = {
+    {{2, 48000, NEEDLE_HIP_SAMPLE_S16}, Landing::None, 2},     {{6, 11025, NEEDLE_HIP_SAMPLE_S16}, Landing::Downmix, 1},
+    {{6, 48000, NEEDLE_HIP_SAMPLE_S16}, Landing::Downmix, 1},  {{2, 44100, NEEDLE_HIP_SAMPLE_F32}, Landing::Convert, 2},
+    {{2, 11025, NEEDLE_HIP_SAMPLE_S32}, Landing::Convert, 2},  {{6, 48000, NEEDLE_HIP_SAMPLE_F32P}, Landing::Convert, 1},
+    {{2, 32000, NEEDLE_HIP_SAMPLE_S16}, Landing::Rematrix, 1}};
+
+// `uniform`: nullptr for the season of seven formats (every window ingested as mono), or one of kUniform for all videos
+static void check_plan(const Uniform *uniform, bool from_host, uint64_t limit, bool count_values, size_t *pieces_out,
+                       size_t *mixed_batches_out) {
   std::map<int, ResampleTiling> tilings;
   std::vector<FormatWindow> windows;
   std::vector<std::vector<uint8_t *>> planes;
   // an opening and an ending window per video, of odd lengths; one video has none (another rank's)
   for (size_t v = 0; v < 7; v++) {
-    const NeedleHipLaneFormat &f = kSeason[v];
+    const NeedleHipLaneFormat &f = uniform ? uniform->format : kSeason[v];
     if (f.sample_rate != kSampleRate) CHECK(resample_tiling_host(f.sample_rate, &tilings[f.sample_rate]).ok());
     if (v == 4) continue;
     for (int r = 0; r < 2; r++) {
@@ -61,6 +77,10 @@ static void check_plan(bool from_host, uint64_t limit, bool count_values, size_t
       w.channels = f.channels;
       w.format = f.format;
       w.rate = f.sample_rate;
+      if (uniform) {
+        w.landing = uniform->landing;
+        w.out_channels = uniform->out_channels;
+      }
       const size_t P = sample_format_planes(f.format, f.channels);
       const size_t bytes = w.frames * (P == 1 ? f.channels : 1) * sample_format_width(f.format);
       planes.emplace_back();
@@ -76,6 +96,10 @@ static void check_plan(bool from_host, uint64_t limit, bool count_values, size_t
   FormatPlan plan;
   CHECK(format_plan_pieces(windows, tilings, from_host, limit, count_values, &plan).ok());
   CHECK(!plan.pieces.empty() && plan.batches >= 1);
+  if (uniform && uniform->landing == Landing::None && !from_host) {  // resampled out of the caller's buffers: nothing staged,
+    CHECK(plan.capacity == 0 && plan.batches == 1 && plan.pieces.size() == 12);  // one piece of all its tiles per window
+    for (const FormatPiece &pc : plan.pieces) CHECK(pc.t0 == 0 && pc.p0 == 0 && pc.p1 == windows[pc.window].frames);
+  }
   int16_t *stage = plan.capacity ? static_cast<int16_t *>(std::malloc(plan.capacity * sizeof(int16_t))) : nullptr;
   std::vector<uint64_t> next_frame(windows.size(), 0), next_tile(windows.size(), 0);
   size_t batch = 0, mixed_batches = 0;
@@ -124,11 +148,16 @@ static void check_plan(bool from_host, uint64_t limit, bool count_values, size_t
         (void)last;
       }
     }
+    // the raw region [raw_off, mono_off) and the landed one behind it: disjoint, inside the capacity, and the next
+    // piece of the batch begins where they end (CHECK(pc.raw_off == used) above)
     CHECK(pc.mono_off == pc.raw_off + P * pc.plane_units);
     used = pc.mono_off;
-    if (w.rate != kSampleRate) {
-      std::memset(stage + pc.mono_off, 0, n * sizeof(int16_t));  // what the landing kernel writes
-      used += (n + 7) & ~(uint64_t)7;
+    if (w.rate != kSampleRate && w.landing != Landing::None) {
+      const uint64_t values = n * (uint64_t)w.out_channels;
+      std::memset(stage + pc.mono_off, 0, values * sizeof(int16_t));  // what the landing kernel writes
+      used += (values + 7) & ~(uint64_t)7;
+    } else if (w.rate != kSampleRate && from_host) {
+      CHECK(P == 1 && W == 2 && pc.plane_units >= n * (uint64_t)w.out_channels);  // the resampler reads the raw staging
     }
     CHECK(used <= plan.capacity);
   }
@@ -142,7 +171,7 @@ static void check_plan(bool from_host, uint64_t limit, bool count_values, size_t
       CHECK(next_tile[i] == (resample_out_len(w.frames, w.rate) + tl.tile_outputs - 1) / tl.tile_outputs);
     }
   }
-  if (!from_host && !count_values) CHECK(plan.batches == 1);
+  if (!from_host && limit >= 1ull << 30) CHECK(plan.batches == 1);
   *pieces_out = plan.pieces.size();
   *mixed_batches_out = mixed_batches;
   std::free(stage);
@@ -154,16 +183,26 @@ int main() {
   check_walk();
   size_t whole = 0, medium = 0, small = 0, tile = 0, mixed = 0;
   for (int from_host = 0; from_host < 2; from_host++) {
-    check_plan(from_host, 1ull << 30, false, &whole, &mixed);
+    check_plan(nullptr, from_host, 1ull << 30, false, &whole, &mixed);
     CHECK(whole == 12 && mixed == 1);  // one piece per window, one batch of every format
-    check_plan(from_host, 400003, true, &medium, &mixed);
+    check_plan(nullptr, from_host, 400003, true, &medium, &mixed);
     std::printf("from_host %d, 400003 values: %zu pieces, %zu batches of more than one format\n", from_host, medium, mixed);
     CHECK(mixed >= 1);  // batches that hold pieces of different formats
-    check_plan(from_host, 3001, true, &small, &mixed);
+    check_plan(nullptr, from_host, 3001, true, &small, &mixed);
     std::printf("from_host %d, 3001 values: %zu pieces, %zu batches of more than one format\n", from_host, small, mixed);
     CHECK(mixed >= 1);
-    check_plan(from_host, 1, true, &tile, &mixed);
+    check_plan(nullptr, from_host, 1, true, &tile, &mixed);
     CHECK(tile >= small && small > medium && medium > whole);
+    for (const Uniform &u : kUniform) {
+      const bool staged = from_host || (u.landing != Landing::None && u.format.sample_rate != kSampleRate);
+      check_plan(&u, from_host, 1ull << 30, false, &whole, &mixed);
+      CHECK(whole == 12 && mixed == 0);
+      check_plan(&u, from_host, 400003, false, &medium, &mixed);  // the limit in bytes, as without the variable
+      check_plan(&u, from_host, 3001, true, &small, &mixed);
+      check_plan(&u, from_host, 1, true, &tile, &mixed);
+      if (staged) CHECK(tile >= small && small >= medium && medium > whole);  // (one tile per piece may be reached early)
+      else CHECK(tile == whole && small == whole && medium == whole);  // read in place: the limit cuts nothing
+    }
   }
   // a rate the resampler has no tiling for is refused, not planned
   FormatWindow w;
