@@ -843,11 +843,31 @@ size_t needle_hip_feeder_num_ready_segments(const NeedleHipSegment *segments, si
  * finished lane before `reset`, unequal lane counts in feed_from_feeder: InvalidArgument, checked for every lane before
  * any device work.  The sources are uploaded at creation: without a HIP device creation fails (there is no CPU path).
  * A source shorter than 2 hashes has no cells and yields nothing.  On return from `feed` the caller's buffers may be
- * reused.  A device failure poisons the matcher: every later call returns it.  One thread at a time per matcher. */
+ * reused.  A device failure poisons the matcher: every later call returns it.  One thread at a time per matcher.
+ *
+ * Regions: openings against openings, endings against endings, in one object (needle_hip_matcher_new_regions).  regions is
+ * 1 or 2; num_sources and lanes are multiples of it.  Source s is in region s % regions and lane l in region l % regions --
+ * the numbering of the library's arena rows, of the feeder's lanes and of the cross-matcher's -- and a lane meets the
+ * sources of its own region only.  NeedleHipRun.problem stays the source's index among all num_sources.  Everything above
+ * holds per lane: reset, open, feed_from_feeder, the repeat after a slab overflow, strips of 512 columns; a round is still
+ * three launches whatever the regions and whichever lanes have data (the grid is as wide as the larger region's sources; a
+ * workgroup beyond its lane's region leaves after one table read, with no state traffic).  A lane's state holds the run
+ * lengths of its own region's sources only: stats[3] = the sources + 2 sets x (lanes / regions) x the sum over the regions
+ * of that region's source hashes x (2 or 4) + the histories.  Here a min_len of 0 is allowed: such a source, like one
+ * shorter than 2 hashes, keeps its index but has no cells, no workgroups and no state (an index row that can hold no run
+ * long enough); a lane whose region has no source with cells only counts its items.  regions == 1 with every min_len >= 1
+ * is needle_hip_matcher_new, run for run.  regions 0 or > 2, num_sources or lanes not a multiple of regions:
+ * InvalidArgument, before any device work; the other refusals are needle_hip_matcher_new's.
+ * Out of scope: more than two regions, several ranks.  Sources taken from a device arena and runs that reach the index are
+ * what needle_hip_index_matcher_new / needle_hip_index_add_streamed below do. */
 typedef struct NeedleHipMatcher NeedleHipMatcher;
 enum NeedleError needle_hip_matcher_new(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *sources,
                                         const uint32_t *min_len, size_t num_sources, size_t lanes, uint32_t threshold,
                                         NeedleHipMatcher **output);
+/* regions 1..2; num_sources and lanes multiples of it; min_len[s] == 0: source s has no cells */
+enum NeedleError needle_hip_matcher_new_regions(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *sources,
+                                                const uint32_t *min_len, size_t num_sources, size_t regions, size_t lanes,
+                                                uint32_t threshold, NeedleHipMatcher **output);
 void needle_hip_matcher_free(NeedleHipMatcher *matcher);
 /* one entry per lane, host hashes; num_items[i] == 0: nothing for lane i */
 enum NeedleError needle_hip_matcher_feed(NeedleHipMatcher *matcher, const uint32_t *const *items, const size_t *num_items);
@@ -936,13 +956,15 @@ enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint6
  * Limits, checked before a device is asked for (InvalidArgument): regions 1 or 2; N 1..256 when K >= 1 (K = 0 is
  * needle_hip_crossmatcher_new_regions, N 2..256); max_items[r] in [2, 2^31 - 16]; every resident row inside the arena
  * (offset + len <= num_hashes) and len <= 2^31 - 16; min_len[r] >= 1; (K N + N (N - 1) / 2) x regions <= 65 535 live
- * problems (a grid dimension: 1 000 residents + 28 arriving x 2 regions = 56 756 fits, 2 000 + 28 x 2 regions does not);
+ * problems (a grid dimension: 1 000 residents + 28 arriving x 2 regions = 56 756 fits, 2 000 + 28 x 2 regions does not:
+ * beyond it a season goes through needle_hip_index_matcher_new / needle_hip_index_add_streamed below, at any library size);
  * V (V - 1) / 2 x regions < 2^32.  NULL arrays (hashes with num_hashes > 0, resident with num_resident > 0, max_items,
  * min_len) or a NULL output: NullArgument.
  *
  * Out of scope: `reset`, `open`, more than two regions, several ranks.  Feeding the index, refreshed results for the
  * resident videos (their candidate lists also need the old pairs' entries, which the index holds) and resident rows taken
- * from a device arena are what needle_hip_index_crossmatcher_new / needle_hip_index_add_matched below do.
+ * from a device arena are what needle_hip_index_crossmatcher_new / needle_hip_index_add_matched below do; a library too
+ * large for the limit above takes the matcher route, needle_hip_index_matcher_new / needle_hip_index_add_streamed.
  *
  * lanes (videos) must be 2..256 (32 640 pairs: pair * regions + region is a grid dimension).  max_items >= 2 is the
  * capacity of every lane (of the region); state and histories are allocated at creation.  lanes, regions or max_items
@@ -1023,8 +1045,39 @@ enum NeedleError needle_hip_index_crossmatcher_new(NeedleHipIndex *index, size_t
                                                    NeedleHipCrossMatcher **output);
 enum NeedleError needle_hip_index_add_matched(NeedleHipIndex *index, NeedleHipCrossMatcher *matcher,
                                               const FrameHashes *const *frame_hashes, size_t k);
+/* ---- A streamed season into an index of any size: a matcher made from the index, and the arriving pairs' cross-matcher --
+ * The cross-matcher above holds (K N + N (N - 1) / 2) x regions live problems in a grid dimension, so a large index cannot
+ * make one.  The second route splits the new pairs:
+ *   resident x arriving: needle_hip_index_matcher_new makes the object of needle_hip_matcher_new_regions whose sources are
+ *     the index's K x regions rows, in the index's order (source = video * regions + region), gathered on the device from
+ *     the index's hash arena (one launch; only tables are uploaded).  regions and threshold are the index's; a source's
+ *     min_len is the row's own shortest run that can pass the duration test, a lower bound for every pair the row is in (0:
+ *     the row can hold none and has no cells).  It has videos x regions lanes, lane = t * regions + r for arriving video t,
+ *     and remembers the index and its generation.  K is not bounded; videos x regions <= 65 535.  An empty index has nothing
+ *     resident: InvalidArgument (a first season goes through needle_hip_index_crossmatcher_new).
+ *   arriving x arriving: a cross-matcher without residents over the same k videos, needle_hip_crossmatcher_new_regions with
+ *     the index's regions and threshold (k <= 256); NULL only when k == 1.
+ * One feeder of videos x regions lanes feeds both (feed_from_feeder): each takes from its own items_fed on.
+ *
+ * needle_hip_index_add_streamed appends the k arriving videos with both run lists in place of the scan.  One kernel re-tags
+ * them for the store -- a matcher run with problem = resident * regions + r on lane t * regions + r is pair (resident,
+ * K + t), a cross-matcher run of i-major pair (a, b) over the k videos is pair (K + a, K + b) -- and drops what the scan's
+ * problems exclude.  Afterwards the index is what needle_hip_index_add(frame_hashes, k) leaves: the results of all K + k
+ * videos, the same store, the same pairs_searched; pairs_scanned *last = 0.  When to take which: one cross-matcher
+ * (needle_hip_index_add_matched) while its live problems fit, this route beyond.
+ *
+ * Refused, before anything is committed and with the index exactly as it was (NeedleError_InvalidArgument unless noted),
+ * for either object where it applies: a matcher not created from this index; a stale one; another device; an object that is
+ * not complete (every lane finished); lane counts other than k x regions; a row whose length is not its lane's items_fed;
+ * a row whose hashes differ from either object's history for that lane (compared on the device); a run that does not lie
+ * inside its rows; a cross-matcher min_len[r] above the smallest max(min_len) of an arriving pair whose two rows can both
+ * hold a run; a cross-matcher that has residents; a NULL cross-matcher with k > 1; whatever needle_hip_index_add refuses,
+ * in the same words; a poisoned object (its error).  NULL index, matcher, array or output: NeedleError_NullArgument. */
+enum NeedleError needle_hip_index_matcher_new(NeedleHipIndex *index, size_t videos, NeedleHipMatcher **output);
+enum NeedleError needle_hip_index_add_streamed(NeedleHipIndex *index, NeedleHipMatcher *matcher, NeedleHipCrossMatcher *crossmatcher,
+                                               const FrameHashes *const *frame_hashes, size_t k);
 /* Video pairs handed to the one-shot scan: over the index's life (*total) and by the last successful operation (*last: 0
- * after add_matched and remove).  needle_hip_index_pairs_searched counts the pairs that entered the index either way.
+ * after add_matched, add_streamed and remove).  needle_hip_index_pairs_searched counts the pairs that entered the index either way.
  * Either pointer may be NULL. */
 enum NeedleError needle_hip_index_pairs_scanned(const NeedleHipIndex *index, uint64_t *total, uint64_t *last);
 

@@ -116,7 +116,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_feeder_switch_format", "needle_hip_feeder_lane_segments", "needle_hip_feeder_num_ready_segments",
     "needle_hip_matcher_new", "needle_hip_matcher_free", "needle_hip_matcher_feed", "needle_hip_matcher_feed_from_feeder",
     "needle_hip_matcher_finish", "needle_hip_matcher_reset", "needle_hip_matcher_ready", "needle_hip_matcher_runs",
-    "needle_hip_matcher_open", "needle_hip_matcher_stats",
+    "needle_hip_matcher_open", "needle_hip_matcher_stats", "needle_hip_matcher_new_regions",
+    "needle_hip_index_matcher_new", "needle_hip_index_add_streamed",
     "needle_hip_crossmatcher_new", "needle_hip_crossmatcher_free", "needle_hip_crossmatcher_feed",
     "needle_hip_crossmatcher_feed_from_feeder", "needle_hip_crossmatcher_finish", "needle_hip_crossmatcher_ready",
     "needle_hip_crossmatcher_lane", "needle_hip_crossmatcher_runs", "needle_hip_crossmatcher_stats",
@@ -367,6 +368,8 @@ def lib():
     L.needle_hip_index_pairs_scanned.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.needle_hip_index_crossmatcher_new.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(u32), C.POINTER(vp)]
     L.needle_hip_index_add_matched.argtypes = [vp, vp, C.POINTER(vp), sz]
+    L.needle_hip_index_matcher_new.argtypes = [vp, sz, C.POINTER(vp)]
+    L.needle_hip_index_add_streamed.argtypes = [vp, vp, vp, C.POINTER(vp), sz]
     L.needle_hip_feeder_new.argtypes = [sz, C.c_int, C.c_int, C.c_int, u32, C.POINTER(vp)]
     L.needle_hip_feeder_free.argtypes = [vp]
     L.needle_hip_feeder_free.restype = None
@@ -400,6 +403,7 @@ def lib():
     L.needle_hip_feeder_num_ready_segments.argtypes = [vp, sz, u32, b]
     L.needle_hip_feeder_num_ready_segments.restype = sz
     L.needle_hip_matcher_new.argtypes = [vp, sz, vp, vp, sz, sz, u32, C.POINTER(vp)]
+    L.needle_hip_matcher_new_regions.argtypes = [vp, sz, vp, vp, sz, sz, sz, u32, C.POINTER(vp)]
     L.needle_hip_matcher_free.argtypes = [vp]
     L.needle_hip_matcher_free.restype = None
     L.needle_hip_matcher_feed.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
@@ -851,6 +855,7 @@ class Index:
         check(lib().needle_hip_index_new(comparator.handle(), C.byref(out)))
         self._h = out
         self.threshold = comparator._cfg["threshold"]   # copied, as the index copies it
+        self.include_endings = bool(comparator._cfg["include_endings"])
 
     def add(self, frame_hashes: Sequence[FrameHashes]) -> None:
         """Appends the videos; on failure (NeedleError) the index is as it was before the call."""
@@ -897,9 +902,30 @@ class Index:
         ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
         check(lib().needle_hip_index_add_matched(self._h, matcher._h, ptrs, k))
 
+    def matcher(self, videos: int) -> "Matcher":
+        """A Matcher whose sources are this index's rows (gathered from the index's device arena; min_len per row, the
+        index's regions and threshold) with `videos * regions` lanes: the resident x arriving half of a streamed season, at
+        any library size.  Feed it and a CrossMatcher.with_regions over the same videos, then add_streamed."""
+        h = C.c_void_p()
+        check(lib().needle_hip_index_matcher_new(self._h, videos, C.byref(h)))
+        m = Matcher.__new__(Matcher)
+        m._h = h
+        m.regions = 2 if self.include_endings else 1
+        m.lanes, m.num_sources, m.threshold = videos * m.regions, len(self) * m.regions, self.threshold
+        return m
+
+    def add_streamed(self, matcher: "Matcher", crossmatcher: Optional["CrossMatcher"], frame_hashes: Sequence[FrameHashes]) -> None:
+        """Appends the arriving videos with the runs of `matcher` (complete, made by matcher() since the last change) for
+        the resident x arriving pairs and those of `crossmatcher` (complete, no residents, over the same videos; None with
+        one video) for the arriving pairs, in place of a scan; afterwards the index is what add(frame_hashes) leaves.  On
+        failure (NeedleError) the index is as it was before the call."""
+        k = len(frame_hashes)
+        ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
+        check(lib().needle_hip_index_add_streamed(self._h, matcher._h, None if crossmatcher is None else crossmatcher._h, ptrs, k))
+
     def pairs_scanned(self) -> Tuple[int, int]:
         """(total, last): video pairs handed to the one-shot scan over the index's life and by the last operation (0 after
-        add_matched)."""
+        add_matched and add_streamed)."""
         total, last = C.c_uint64(), C.c_uint64()
         check(lib().needle_hip_index_pairs_scanned(self._h, C.byref(total), C.byref(last)))
         return total.value, last.value
@@ -1116,7 +1142,30 @@ class Matcher:
         check(lib().needle_hip_matcher_new(arena.ctypes.data if arena.size else None, arena.size, seqs.ctypes.data, mins.ctypes.data,
                                            len(arrs), lanes, threshold, C.byref(h)))
         self._h = h
-        self.lanes, self.num_sources, self.threshold = lanes, len(arrs), threshold
+        self.lanes, self.num_sources, self.threshold, self.regions = lanes, len(arrs), threshold, 1
+
+    @classmethod
+    def with_regions(cls, sources: Sequence[np.ndarray], min_len: Sequence[int], regions: int, lanes: int,
+                     threshold: int) -> "Matcher":
+        """needle_hip_matcher_new_regions: source s is in region s % regions, lane l in region l % regions, and a lane meets
+        its own region's sources only; `problem` stays the source's index.  A min_len of 0 is allowed: that source has no
+        cells."""
+        arrs = [np.ascontiguousarray(s, dtype=np.uint32) for s in sources]
+        if len(min_len) != len(arrs):
+            raise ValueError("one min_len per source")
+        arena = np.concatenate(arrs) if arrs else np.zeros(0, dtype=np.uint32)
+        seqs = np.zeros((max(len(arrs), 1), 2), dtype=np.uint32)
+        seqs[:len(arrs), 1] = [a.size for a in arrs]
+        seqs[:len(arrs), 0] = np.cumsum([0] + [a.size for a in arrs])[:len(arrs)]
+        mins = np.ascontiguousarray(list(min_len) or [0], dtype=np.uint32)
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().needle_hip_matcher_new_regions(arena.ctypes.data if arena.size else None, arena.size, seqs.ctypes.data,
+                                                   mins.ctypes.data, len(arrs), regions, lanes, threshold, C.byref(h)))
+        self._h = h
+        self.lanes, self.num_sources, self.threshold, self.regions = lanes, len(arrs), threshold, regions
+        return self
 
     def feed(self, items: Sequence) -> None:
         """items[i]: the hashes lane i has received since the last feed, or None / an empty array for nothing."""

@@ -930,6 +930,19 @@ enum NeedleError needle_hip_matcher_new(const uint32_t *hashes, size_t num_hashe
   });
 }
 
+enum NeedleError needle_hip_matcher_new_regions(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *sources,
+                                                const uint32_t *min_len, size_t num_sources, size_t regions, size_t lanes,
+                                                uint32_t threshold, NeedleHipMatcher **output) {
+  if (!output || !sources || !min_len || (num_hashes && !hashes)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipMatcher>();
+    Status s = Matcher::CreateRegions(hashes, num_hashes, sources, min_len, num_sources, regions, lanes, threshold, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
 void needle_hip_matcher_free(NeedleHipMatcher *matcher) { delete matcher; }
 
 enum NeedleError needle_hip_matcher_feed(NeedleHipMatcher *matcher, const uint32_t *const *items, const size_t *num_items) {
@@ -1430,6 +1443,33 @@ enum NeedleError needle_hip_index_add_matched(NeedleHipIndex *index, NeedleHipCr
       fh[i] = &frame_hashes[i]->d;
     }
     Status s = index->inner.add_matched(matcher->inner.get(), fh);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_index_matcher_new(NeedleHipIndex *index, size_t videos, NeedleHipMatcher **output) {
+  if (!index || !output) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipMatcher>();
+    Status s = index->inner.matcher(videos, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_index_add_streamed(NeedleHipIndex *index, NeedleHipMatcher *matcher, NeedleHipCrossMatcher *crossmatcher,
+                                               const FrameHashes *const *frame_hashes, size_t k) {
+  if (!index || !matcher) return NeedleError_NullArgument;
+  if (k == 0) return report(Status::Make(NeedleError_InvalidArgument, "index add: no videos"));
+  if (!frame_hashes) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    Status s = index->inner.add_streamed(matcher->inner.get(), crossmatcher ? crossmatcher->inner.get() : nullptr, fh);
     return s.ok() ? NeedleError_Ok : report(s);
   });
 }

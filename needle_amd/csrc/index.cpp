@@ -160,11 +160,41 @@ Status Index::init() {
   return Status::Ok();
 }
 
-Status Index::add(const std::vector<const FrameHashesData *> &fh) { return append(fh, nullptr); }
+Status Index::add(const std::vector<const FrameHashesData *> &fh) { return append(fh, nullptr, nullptr); }
 
 Status Index::add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &fh) {
   if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_matched: null argument");
-  return append(fh, matcher);
+  return append(fh, matcher, nullptr);
+}
+
+Status Index::add_streamed(Matcher *matcher, CrossMatcher *crossmatcher, const std::vector<const FrameHashesData *> &fh) {
+  if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_streamed: null argument");
+  if (!crossmatcher && fh.size() > 1)
+    return Status::Make(NeedleError_InvalidArgument, "index add_streamed: more than one video needs the cross-matcher of the arriving pairs");
+  return append(fh, crossmatcher, matcher);
+}
+
+// The index's rows as a matcher's sources (matcher.hip, regions): gathered on the device from the store's arena; a row's own
+// min_len is a lower bound for every pair the row is in, and a row that can hold no run (min_len 0) has no cells.
+Status Index::matcher(size_t videos, std::unique_ptr<Matcher> *out) {
+  if (!out) return Status::Make(NeedleError_NullArgument, "index matcher: null argument");
+  if (videos_.empty())
+    return Status::Make(NeedleError_InvalidArgument,
+                        "index matcher: an empty index has nothing resident (needle_hip_index_crossmatcher_new takes a first season)");
+  if (videos == 0 || videos > 65535 / regions_) return Status::Make(NeedleError_InvalidArgument, "matcher: lanes must be 1 to 65535");
+  // the argument checks first, with or without a device ...
+  Status s = Matcher::CheckShape(rows_.hashes, rows_.seqs.data(), rows_.min_len.data(), rows_.seqs.size(), regions_, videos * regions_);
+  if (!s.ok()) return s;
+  // ... then the device, before anything is allocated on another one
+  const uint32_t *d_hashes = nullptr;
+  if (!(s = index_store_arena(store_, &d_hashes)).ok()) return s;
+  std::unique_ptr<Matcher> mt;
+  s = Matcher::CreateRegionsDevice(d_hashes, d_hashes ? rows_.hashes : 0, rows_.seqs.data(), rows_.min_len.data(), rows_.seqs.size(), regions_,
+                                   videos * regions_, cmp_.hash_match_threshold(), &mt);
+  if (!s.ok()) return s;
+  mt->set_origin(Matcher::Origin{id_, generation_});
+  *out = std::move(mt);
+  return Status::Ok();
 }
 
 Status Index::crossmatcher(size_t videos, const size_t *max_items, const uint32_t *min_len, std::unique_ptr<CrossMatcher> *out) {
@@ -185,24 +215,42 @@ Status Index::crossmatcher(size_t videos, const size_t *max_items, const uint32_
   return Status::Ok();
 }
 
-// add and add_matched: with a matcher its runs stand in for the scan of the new pairs; everything else is one path.
-Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatcher *matcher) {
+// add, add_matched and add_streamed: with a cross-matcher (made from the index) its runs stand in for the scan of the new pairs;
+// with a matcher made from the index (`streamed`) its runs stand in for the resident x arriving pairs and those of `matcher`, a
+// cross-matcher over the arriving videos alone (null: one video), for the arriving pairs; everything else is one path.
+Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatcher *matcher, Matcher *streamed) {
   if (fh.empty()) return Status::Make(NeedleError_InvalidArgument, "index add: no videos");
   const size_t k = fh.size(), n0 = videos_.size(), n1 = n0 + k, R = regions_;
-  if (matcher) {
+  const std::string who = streamed ? "index add_streamed: " : "index add_matched: ";
+  auto refuse = [&](const char *what) { return Status::Make(NeedleError_InvalidArgument, who + what); };
+  if (streamed) {
+    Status s = streamed->poisoned();
+    if (!s.ok() || (matcher && !(s = matcher->poisoned()).ok())) return s;
+    const Matcher::Origin from = streamed->origin();
+    if (from.index_id != id_) return refuse("the matcher was not created from this index");
+    if (from.generation != generation_) return refuse("the index has changed since the matcher was created");
+    if (matcher && matcher->residents() != 0)
+      return refuse("the cross-matcher has resident videos (the arriving pairs come from needle_hip_crossmatcher_new_regions)");
+    if (streamed->device() != index_store_device(store_) || (matcher && matcher->device() != index_store_device(store_)))
+      return refuse("the matcher is on another device than the index");
+    bool complete = true;
+    for (size_t lane = 0; lane < streamed->lanes() && complete; lane++)
+      if (!(s = streamed->Ready(lane, nullptr, nullptr, &complete)).ok()) return s;
+    if (complete && matcher && !(s = matcher->Ready(nullptr, &complete)).ok()) return s;
+    if (!complete) return refuse("the matcher is not complete");
+    if (k * R != streamed->lanes() || R != streamed->regions() || (matcher && (k != matcher->videos() || R != matcher->regions())))
+      return refuse("not the matcher's number of videos");
+  } else if (matcher) {
     Status s = matcher->poisoned();
     if (!s.ok()) return s;
     const CrossMatcher::Origin from = matcher->origin();
-    if (from.index_id != id_) return Status::Make(NeedleError_InvalidArgument, "index add_matched: the matcher was not created from this index");
-    if (from.generation != generation_)
-      return Status::Make(NeedleError_InvalidArgument, "index add_matched: the index has changed since the matcher was created");
-    if (matcher->device() != index_store_device(store_))
-      return Status::Make(NeedleError_InvalidArgument, "index add_matched: the matcher is on another device than the index");
+    if (from.index_id != id_) return refuse("the matcher was not created from this index");
+    if (from.generation != generation_) return refuse("the index has changed since the matcher was created");
+    if (matcher->device() != index_store_device(store_)) return refuse("the matcher is on another device than the index");
     bool complete = false;
     if (!(s = matcher->Ready(nullptr, &complete)).ok()) return s;
-    if (!complete) return Status::Make(NeedleError_InvalidArgument, "index add_matched: the matcher is not complete");
-    if (k != matcher->videos() || R != matcher->regions() || n0 != matcher->residents())
-      return Status::Make(NeedleError_InvalidArgument, "index add_matched: not the matcher's number of videos");
+    if (!complete) return refuse("the matcher is not complete");
+    if (k != matcher->videos() || R != matcher->regions() || n0 != matcher->residents()) return refuse("not the matcher's number of videos");
   }
   if (n1 >= 0xFFFFFFFFull) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 videos");
   auto video = [&](size_t v) -> const FrameHashesData & { return v < n0 ? videos_[v] : *fh[v - n0]; };
@@ -215,8 +263,13 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
     uint64_t fed = 0;
     Status s = matcher->Lane(lane, &fed, nullptr);
     if (!s.ok()) return s;
-    if (row_seq(n0 + lane / R, lane % R).size() != fed)
-      return Status::Make(NeedleError_InvalidArgument, "index add_matched: a video's row is not as long as what its lane was fed");
+    if (row_seq(n0 + lane / R, lane % R).size() != fed) return refuse("a video's row is not as long as what its lane was fed");
+  }
+  for (size_t lane = 0; streamed && lane < k * R; lane++) {
+    uint64_t fed = 0;
+    Status s = streamed->Ready(lane, nullptr, &fed, nullptr);
+    if (!s.ok()) return s;
+    if (row_seq(n0 + lane / R, lane % R).size() != fed) return refuse("a video's row is not as long as what its lane was fed");
   }
   IndexRows rows(rows_);
   rows.seqs.resize(n1 * R);
@@ -267,11 +320,40 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
     for (size_t r = 0; r < R; r++) {
       uint32_t least = UINT32_MAX;
       for (size_t j = n0; j < n1; j++)
-        for (size_t i = 0; i < j; i++)
+        for (size_t i = streamed ? n0 : 0; i < j; i++)  // (streamed: the cross-matcher had the arriving pairs only)
           if (rows.min_len[i * R + r] && rows.min_len[j * R + r]) least = std::min(least, std::max(rows.min_len[i * R + r], rows.min_len[j * R + r]));
-      if (matcher->min_len(r) > least)
-        return Status::Make(NeedleError_InvalidArgument, "index add_matched: the matcher's min_len exceeds the shortest run a pair can hold");
+      if (matcher->min_len(r) > least) return refuse("the matcher's min_len exceeds the shortest run a pair can hold");
     }
+  }
+  if (streamed) {
+    // One list, the matcher's lanes first, and each of its runs' lanes; the new rows beside the histories of both objects.
+    std::vector<NeedleHipRun> list;
+    std::vector<uint32_t> run_lane;
+    for (size_t lane = 0; lane < k * R; lane++) {
+      const std::vector<NeedleHipRun> &runs = streamed->run_list(lane);
+      list.insert(list.end(), runs.begin(), runs.end());
+      run_lane.insert(run_lane.end(), runs.size(), (uint32_t)lane);
+    }
+    const size_t from_matcher = list.size();
+    if (matcher) list.insert(list.end(), matcher->run_list().begin(), matcher->run_list().end());
+    std::vector<IndexLaneRow> lanes;
+    for (size_t at = n0 * R; at < n1 * R; at++) {
+      if (!rows.seqs[at].len) continue;
+      if (const uint32_t *history = streamed->history(at - n0 * R)) lanes.push_back(IndexLaneRow{rows.seqs[at].offset, history, rows.seqs[at].len});
+      if (matcher) lanes.push_back(IndexLaneRow{rows.seqs[at].offset, matcher->history(at - n0 * R), rows.seqs[at].len});
+    }
+    IndexStreamed m;
+    m.runs = list.data();
+    m.num_matcher_runs = from_matcher;
+    m.num_cross_runs = list.size() - from_matcher;
+    m.run_lane = run_lane.data();
+    m.min_len = rows.min_len.data();
+    m.lanes = lanes.data();
+    m.num_lanes = lanes.size();
+    if (!(s = gpu_index_append_streamed(store_, a, m, &out)).ok()) return s;
+    if (out.refused & kIngestOtherHashes) return refuse("a video's hashes differ from what its lane was fed");
+    if (out.refused) return refuse("a run of the matcher does not lie inside its rows");
+  } else if (matcher) {
     std::vector<IndexSegment> lanes;
     for (size_t at = n0 * R; at < n1 * R; at++)
       if (rows.seqs[at].len)
@@ -284,14 +366,13 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
     m.lanes = lanes.data();
     m.num_lanes = lanes.size();
     if (!(s = gpu_index_append_matched(store_, a, m, &out)).ok()) return s;
-    if (out.refused & kIngestOtherHashes)
-      return Status::Make(NeedleError_InvalidArgument, "index add_matched: a video's hashes differ from what its lane was fed");
-    if (out.refused) return Status::Make(NeedleError_InvalidArgument, "index add_matched: a run of the matcher does not lie inside its rows");
+    if (out.refused & kIngestOtherHashes) return refuse("a video's hashes differ from what its lane was fed");
+    if (out.refused) return refuse("a run of the matcher does not lie inside its rows");
   } else {
     s = gpu_index_append(store_, a, &out);
     if (!s.ok()) return s;
   }
-  s = settle(cmp_, matcher ? "Index::add_matched" : "Index::add", R, n1, new_pairs * R, [&](uint64_t q, size_t *i, size_t *j) { column_pair(first_pair + q, i, j); }, row_seq, video,
+  s = settle(cmp_, streamed ? "Index::add_streamed" : matcher ? "Index::add_matched" : "Index::add", R, n1, new_pairs * R, [&](uint64_t q, size_t *i, size_t *j) { column_pair(first_pair + q, i, j); }, row_seq, video,
              [&](const auto &...computed) { return gpu_index_append_host_entries(store_, a, computed..., &out); }, out);
   if (!s.ok()) return s;
   // commit: nothing above changed the index
@@ -300,7 +381,7 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
   rows_ = std::move(rows);
   results_.resize(n1, NeedleHipSearchResult{});
   for (size_t q = 0; q < out.videos.size(); q++) results_[out.videos[q]] = out.results[q];
-  changed(searched, matcher ? 0 : searched);
+  changed(searched, matcher || streamed ? 0 : searched);
   return Status::Ok();
 }
 

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "crossmatch.h"
+#include "matcher.h"
 #include "needle_core.h"
 
 namespace needle {
@@ -40,6 +41,14 @@ class Index {
   // add() with the runs of a complete matcher made by crossmatcher() since the last change in place of the scan: the same
   // index afterwards, no pair searched again.  Every check comes before the commit; on failure the index is as it was.
   Status add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &videos);
+  // The second route, for an index too large for one cross-matcher (its live problems are a grid dimension): a matcher whose
+  // sources are the index's rows, region-aware, with `videos` * regions lanes; each source's min_len is the row's own.  It
+  // remembers the index and its generation.  An empty index has nothing resident: InvalidArgument.
+  Status matcher(size_t videos, std::unique_ptr<Matcher> *out);
+  // add() with the runs of a complete matcher made by matcher() since the last change in place of the scan of the resident x
+  // arriving pairs, and those of a complete cross-matcher over the arriving videos alone (no residents; null with one video) in
+  // place of the arriving pairs'.  The same index afterwards; every check comes before the commit.
+  Status add_streamed(Matcher *matcher, CrossMatcher *crossmatcher, const std::vector<const FrameHashesData *> &videos);
   // Removes the videos at these distinct positions (the others keep their order) / replaces them in place (copied).  The
   // results then equal run_with_frame_hashes over the new list; on failure the index is as it was before the call.
   Status remove(const std::vector<size_t> &positions);
@@ -49,7 +58,7 @@ class Index {
   const std::vector<NeedleHipSearchResult> &results() const { return results_; }
   uint64_t pairs_total() const { return pairs_total_; }
   uint64_t pairs_last() const { return pairs_last_; }
-  // pairs handed to the one-shot scan (add_matched hands it none)
+  // pairs handed to the one-shot scan (add_matched and add_streamed hand it none)
   uint64_t scanned_total() const { return scanned_total_; }
   uint64_t scanned_last() const { return scanned_last_; }
 
@@ -65,7 +74,7 @@ class Index {
   const uint64_t id_;        // from a process-wide counter: what a matcher made here remembers, with ...
   uint64_t generation_ = 1;  // ... this, which every successful change advances
 
-  Status append(const std::vector<const FrameHashesData *> &videos, CrossMatcher *matcher);
+  Status append(const std::vector<const FrameHashesData *> &videos, CrossMatcher *matcher, Matcher *streamed);
   void changed(uint64_t searched, uint64_t scanned);  // the counters, at a commit
 
   // remove / replace: the new list is old_of_new[v] (an old position) or, where that is kIndexFresh, *fresh[v]

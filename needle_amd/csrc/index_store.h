@@ -78,6 +78,28 @@ struct IndexMatched {
 constexpr uint32_t kIngestBadRun = 1u;       // a run outside its rows, of an old pair or of no pair
 constexpr uint32_t kIngestOtherHashes = 2u;  // a new row's hashes are not what its lane was fed
 Status gpu_index_append_matched(IndexStore *store, const IndexAppend &append, const IndexMatched &matched, IndexAppendOut *out);
+// The same append fed from TWO run lists (Index::add_streamed), for an index too large for one cross-matcher: the runs of a
+// matcher made from the store's rows (Index::matcher) stand in for the resident x arriving pairs, those of a complete
+// cross-matcher over the k = n1 - n0 arriving videos alone for the arriving x arriving pairs.  `runs` holds the matcher's
+// lanes' lists one after the other (problem = resident video * regions + region; run_lane[q] = the lane of run q, arriving
+// video * regions + region), then the cross-matcher's (problem = the i-major pair over the k videos * regions + region).  One
+// kernel re-tags both for the append (pair_ids.h: (resident, n0 + t, r) and (n0 + a, n0 + b, r)) and drops what the scan's
+// problems exclude, as above; a run outside its rows, of a source or lane that is none, or of another region than its lane's
+// sets kIngestBadRun.  Every new row is compared with the history of each object that has one for its lane.
+struct IndexLaneRow {  // a new row: `len` hashes at `src` in the arena after the append, and on the device at `history`
+  uint64_t src;
+  const uint32_t *history;
+  uint64_t len;
+};
+struct IndexStreamed {
+  const NeedleHipRun *runs = nullptr;
+  size_t num_matcher_runs = 0, num_cross_runs = 0;
+  const uint32_t *run_lane = nullptr;   // [num_matcher_runs]
+  const uint32_t *min_len = nullptr;    // ALL rows after the append
+  const IndexLaneRow *lanes = nullptr;  // up to two per new row (the matcher's history, the cross-matcher's)
+  size_t num_lanes = 0;
+};
+Status gpu_index_append_streamed(IndexStore *store, const IndexAppend &append, const IndexStreamed &streamed, IndexAppendOut *out);
 // The committed hash arena on the device (row offsets: IndexRows::seqs), for a cross-matcher's resident rows; null while empty.
 // Valid until the next operation on the store.
 Status index_store_arena(IndexStore *store, const uint32_t **d_hashes);

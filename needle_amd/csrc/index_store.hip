@@ -52,6 +52,32 @@ __global__ __launch_bounds__(256) void index_list_kernel(uint32_t n0, uint32_t n
 // two rows, or is not of a new pair, sets `error` and is dropped too, so nothing behind this reads outside a row.  The survivors
 // of a wave leave together: one returning atomic per wave (stream_walk.h's push_runs).  A wave's 64 lanes take 64 consecutive
 // runs, so every lane of a wave makes the same number of trips.
+// A wave's survivors into the slab: one returning atomic per wave, a prefix count for the slots.  Every lane of the wave comes
+// through here together.
+__device__ __forceinline__ void ingest_push(const bool keep, const NeedleHipRun &run, NeedleHipRun *__restrict__ out, const uint32_t capacity,
+                                            uint32_t *__restrict__ count) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
+  if (mask == 0ull) return;
+  uint32_t first = 0u;
+  if (lane == 0u) first = atomicAdd(count, (uint32_t)__popcll(mask));
+  first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
+  const uint32_t slot = first + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+  if (keep && slot < capacity) out[slot] = run;
+}
+
+// Pair (a, b, r) of an append onto n0 videos, b >= n0: whether `run` lies inside its two rows (else `error`), whether the scan's
+// problems would have reported it, and its tag for the append.
+__device__ __forceinline__ bool ingest_retag(NeedleHipRun &run, const uint32_t a, const uint32_t b, const uint32_t r, const uint32_t n0,
+                                             const uint32_t regions, const uint32_t *__restrict__ min_len,
+                                             const uint32_t *__restrict__ row_len, bool *good) {
+  const uint64_t row_a = (uint64_t)a * regions + r, row_b = (uint64_t)b * regions + r;
+  *good = run.src_end < row_len[row_a] && run.dst_end < row_len[row_b] && run.len <= min(run.src_end, run.dst_end);
+  const uint32_t min_a = min_len[row_a], min_b = min_len[row_b];
+  run.problem = (uint32_t)append_tag(a, b, r, n0, regions);
+  return *good && min_a != 0u && min_b != 0u && run.len >= max(min_a, min_b);
+}
+
 __global__ __launch_bounds__(256) void index_ingest_runs_kernel(const NeedleHipRun *__restrict__ in, uint32_t num_runs, uint32_t videos,
                                                                 uint32_t n0, uint32_t regions, const uint32_t *__restrict__ min_len,
                                                                 const uint32_t *__restrict__ row_len, NeedleHipRun *__restrict__ out,
@@ -66,22 +92,60 @@ __global__ __launch_bounds__(256) void index_ingest_runs_kernel(const NeedleHipR
       run = in[k];
       uint32_t a = 0, b = 0, r = 0;
       bool good = decode_problem(run.problem, regions, videos, &a, &b, &r) && b >= n0;
-      if (good) {
-        const uint64_t row_a = (uint64_t)a * regions + r, row_b = (uint64_t)b * regions + r;
-        good = run.src_end < row_len[row_a] && run.dst_end < row_len[row_b] && run.len <= min(run.src_end, run.dst_end);
-        const uint32_t min_a = min_len[row_a], min_b = min_len[row_b];
-        keep = good && min_a != 0u && min_b != 0u && run.len >= max(min_a, min_b);
-        run.problem = (uint32_t)append_tag(a, b, r, n0, regions);
-      }
+      if (good) keep = ingest_retag(run, a, b, r, n0, regions, min_len, row_len, &good);
       if (!good) atomicOr(error, kIngestBadRun);
     }
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
-    if (mask == 0ull) continue;
-    uint32_t first = 0u;
-    if (lane == 0u) first = atomicAdd(count, (uint32_t)__popcll(mask));
-    first = (uint32_t)__builtin_amdgcn_readfirstlane((int)first);
-    const uint32_t slot = first + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-    if (keep && slot < capacity) out[slot] = run;
+    ingest_push(keep, run, out, capacity, count);
+  }
+}
+
+// ---- an append fed from a matcher made from the store and a cross-matcher over the arriving videos (gpu_index_append_streamed) --
+// Both lists in one launch, the matcher's first.  A matcher run names its resident row (problem = resident * regions + region)
+// and came from lane run_lane[q] = t * regions + region: pair (resident, n0 + t).  A cross-matcher run names its pair i-major
+// over the k = n1 - n0 arriving videos alone: pair (n0 + a, n0 + b).  Everything else is index_ingest_runs_kernel.
+__global__ __launch_bounds__(256) void index_ingest_streamed_kernel(const NeedleHipRun *__restrict__ in, uint32_t matcher_runs,
+                                                                    uint32_t num_runs, const uint32_t *__restrict__ run_lane, uint32_t n0,
+                                                                    uint32_t n1, uint32_t regions, const uint32_t *__restrict__ min_len,
+                                                                    const uint32_t *__restrict__ row_len, NeedleHipRun *__restrict__ out,
+                                                                    uint32_t capacity, uint32_t *__restrict__ count,
+                                                                    uint32_t *__restrict__ error) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < num_runs; base += stride) {
+    const uint64_t k = base + lane;
+    bool keep = false;
+    NeedleHipRun run{};
+    if (k < num_runs) {
+      run = in[k];
+      uint32_t a = 0, b = 0, r = 0;
+      bool good;
+      if (k < matcher_runs) {
+        const uint32_t from = run_lane[k];
+        r = run.problem % regions;
+        a = run.problem / regions;
+        b = n0 + from / regions;
+        good = a < n0 && b < n1 && from % regions == r;
+      } else {
+        good = decode_problem(run.problem, regions, n1 - n0, &a, &b, &r);
+        a += n0;
+        b += n0;
+      }
+      if (good) keep = ingest_retag(run, a, b, r, n0, regions, min_len, row_len, &good);
+      if (!good) atomicOr(error, kIngestBadRun);
+    }
+    ingest_push(keep, run, out, capacity, count);
+  }
+}
+
+// The new rows in the arena against the hashes their lanes were fed, each history with a device address of its own (a matcher's
+// lanes are separate allocations): a workgroup per row.
+__global__ __launch_bounds__(256) void index_compare_lanes_kernel(const IndexLaneRow *__restrict__ rows, uint32_t num_rows,
+                                                                  const uint32_t *__restrict__ arena, uint32_t *__restrict__ error) {
+  for (uint32_t s = blockIdx.x; s < num_rows; s += gridDim.x) {
+    const IndexLaneRow g = rows[s];
+    bool differ = false;
+    for (uint64_t k = threadIdx.x; k < g.len; k += blockDim.x) differ = differ || arena[g.src + k] != g.history[k];
+    if (differ) atomicOr(error, kIngestOtherHashes);
   }
 }
 
@@ -237,7 +301,8 @@ struct IndexStore {
   DeviceBuffer<EpilogueControl> ctl;
   DeviceBuffer<uint32_t> flag, list, links, run_count;
   DeviceBuffer<NeedleHipRun> runs, matched_runs;  // the run list; a matcher's, as uploaded
-  DeviceBuffer<uint32_t> matched_min_len, matched_error;
+  DeviceBuffer<uint32_t> matched_min_len, matched_error, run_lane;
+  DeviceBuffer<IndexLaneRow> lane_rows;
   DeviceBuffer<Candidate> cand;
   DeviceBuffer<NeedleHipSearchResult> results;
   PinnedHead *pinned = nullptr;
@@ -505,35 +570,28 @@ Status gpu_index_append(IndexStore *st, const IndexAppend &a, IndexAppendOut *ou
   });
 }
 
-Status gpu_index_append_matched(IndexStore *st, const IndexAppend &a, const IndexMatched &m, IndexAppendOut *out) {
-  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
-  Status s = index_enter(st);
-  if (!s.ok()) return s;
-  hipStream_t stream = library_stream();
-  if (m.num_runs > 0x7fffffffu) return Status::Make(NeedleError_InvalidArgument, "index add_matched: more than 2^31 runs");
-  if (!(s = index_append_tables(st, a, stream)).ok()) return s;
+namespace {
+
+// An append whose slab is filled from run lists that were uploaded, not by the scan: `runs` and every row's min_len go up,
+// launch(capacity) enqueues the kernels that compare the rows and ingest the list, and the error word comes back in
+// out->refused once everything behind them has run.
+template <class Launch>
+Status index_append_ingested(IndexStore *st, const IndexAppend &a, const NeedleHipRun *runs, size_t num_runs, const uint32_t *min_len,
+                             hipStream_t stream, IndexAppendOut *out, Launch launch) {
   const size_t rows = (size_t)a.n1 * a.regions;
-  if (!(s = st->matched_runs.reserve(std::max<size_t>(m.num_runs, 1))).ok() || !(s = st->matched_min_len.reserve(rows)).ok() ||
-      !(s = st->matched_error.reserve(1)).ok() || !(s = st->segments.reserve(std::max<size_t>(m.num_lanes, 1))).ok())
+  Status s;
+  if (!(s = st->matched_runs.reserve(std::max<size_t>(num_runs, 1))).ok() || !(s = st->matched_min_len.reserve(rows)).ok() ||
+      !(s = st->matched_error.reserve(1)).ok())
     return s;
-  NEEDLE_HIP_TRY(upload(st->matched_runs.ptr, m.runs, m.num_runs, stream));
-  NEEDLE_HIP_TRY(upload(st->matched_min_len.ptr, m.min_len, rows, stream));
-  NEEDLE_HIP_TRY(upload(st->segments.ptr, m.lanes, m.num_lanes, stream));
+  NEEDLE_HIP_TRY(upload(st->matched_runs.ptr, runs, num_runs, stream));
+  NEEDLE_HIP_TRY(upload(st->matched_min_len.ptr, min_len, rows, stream));
   const uint32_t capacity_before = st->capacity;
-  st->capacity = std::max<uint32_t>(st->capacity, (uint32_t)m.num_runs);  // the survivors are at most the list: one pass
+  st->capacity = std::max<uint32_t>(st->capacity, (uint32_t)num_runs);  // the survivors are at most the list: one pass
   s = index_append_from_slab(st, a, stream, out, [&](uint32_t capacity) -> Status {
     NEEDLE_HIP_TRY(hipMemsetAsync(st->matched_error.ptr, 0, sizeof(uint32_t), stream));
     NEEDLE_HIP_TRY(hipMemsetAsync(st->run_count.ptr, 0, sizeof(uint32_t), stream));
     KernelTimer timer("index_ingest", stream);
-    if (m.num_lanes)
-      hipLaunchKernelGGL(index_compare_rows_kernel, dim3((uint32_t)std::min<size_t>(m.num_lanes, 4096)), dim3(256), 0, stream,
-                         (const IndexSegment *)st->segments.ptr, (uint32_t)m.num_lanes, (const uint32_t *)st->cur->hash.ptr(), m.history,
-                         st->matched_error.ptr);
-    if (m.num_runs)
-      hipLaunchKernelGGL(index_ingest_runs_kernel, dim3((uint32_t)std::min<size_t>(4096, (m.num_runs + 255) / 256)), dim3(256), 0, stream,
-                         (const NeedleHipRun *)st->matched_runs.ptr, (uint32_t)m.num_runs, a.n1, a.n0, a.regions,
-                         (const uint32_t *)st->matched_min_len.ptr, (const uint32_t *)st->cur->row_len.ptr(), st->runs.ptr, capacity,
-                         st->run_count.ptr, st->matched_error.ptr);
+    launch(capacity);
     NEEDLE_HIP_TRY(hipGetLastError());
     return Status::Ok();
   });
@@ -543,6 +601,55 @@ Status gpu_index_append_matched(IndexStore *st, const IndexAppend &a, const Inde
   }
   if (!s.ok() || out->refused) st->capacity = capacity_before;  // a call that commits nothing sizes nothing for the next one
   return s;
+}
+
+}  // namespace
+
+Status gpu_index_append_matched(IndexStore *st, const IndexAppend &a, const IndexMatched &m, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = index_enter(st);
+  if (!s.ok()) return s;
+  hipStream_t stream = library_stream();
+  if (m.num_runs > 0x7fffffffu) return Status::Make(NeedleError_InvalidArgument, "index add_matched: more than 2^31 runs");
+  if (!(s = index_append_tables(st, a, stream)).ok()) return s;
+  if (!(s = st->segments.reserve(std::max<size_t>(m.num_lanes, 1))).ok()) return s;
+  NEEDLE_HIP_TRY(upload(st->segments.ptr, m.lanes, m.num_lanes, stream));
+  return index_append_ingested(st, a, m.runs, m.num_runs, m.min_len, stream, out, [&](uint32_t capacity) {
+    if (m.num_lanes)
+      hipLaunchKernelGGL(index_compare_rows_kernel, dim3((uint32_t)std::min<size_t>(m.num_lanes, 4096)), dim3(256), 0, stream,
+                         (const IndexSegment *)st->segments.ptr, (uint32_t)m.num_lanes, (const uint32_t *)st->cur->hash.ptr(), m.history,
+                         st->matched_error.ptr);
+    if (m.num_runs)
+      hipLaunchKernelGGL(index_ingest_runs_kernel, dim3((uint32_t)std::min<size_t>(4096, (m.num_runs + 255) / 256)), dim3(256), 0, stream,
+                         (const NeedleHipRun *)st->matched_runs.ptr, (uint32_t)m.num_runs, a.n1, a.n0, a.regions,
+                         (const uint32_t *)st->matched_min_len.ptr, (const uint32_t *)st->cur->row_len.ptr(), st->runs.ptr, capacity,
+                         st->run_count.ptr, st->matched_error.ptr);
+  });
+}
+
+Status gpu_index_append_streamed(IndexStore *st, const IndexAppend &a, const IndexStreamed &m, IndexAppendOut *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = index_enter(st);
+  if (!s.ok()) return s;
+  hipStream_t stream = library_stream();
+  const size_t num_runs = m.num_matcher_runs + m.num_cross_runs;
+  if (num_runs > 0x7fffffffu) return Status::Make(NeedleError_InvalidArgument, "index add_streamed: more than 2^31 runs");
+  if (!(s = index_append_tables(st, a, stream)).ok()) return s;
+  if (!(s = st->lane_rows.reserve(std::max<size_t>(m.num_lanes, 1))).ok() || !(s = st->run_lane.reserve(std::max<size_t>(m.num_matcher_runs, 1))).ok())
+    return s;
+  NEEDLE_HIP_TRY(upload(st->lane_rows.ptr, m.lanes, m.num_lanes, stream));
+  NEEDLE_HIP_TRY(upload(st->run_lane.ptr, m.run_lane, m.num_matcher_runs, stream));
+  return index_append_ingested(st, a, m.runs, num_runs, m.min_len, stream, out, [&](uint32_t capacity) {
+    if (m.num_lanes)
+      hipLaunchKernelGGL(index_compare_lanes_kernel, dim3((uint32_t)std::min<size_t>(m.num_lanes, 4096)), dim3(256), 0, stream,
+                         (const IndexLaneRow *)st->lane_rows.ptr, (uint32_t)m.num_lanes, (const uint32_t *)st->cur->hash.ptr(),
+                         st->matched_error.ptr);
+    if (num_runs)
+      hipLaunchKernelGGL(index_ingest_streamed_kernel, dim3((uint32_t)std::min<size_t>(4096, (num_runs + 255) / 256)), dim3(256), 0, stream,
+                         (const NeedleHipRun *)st->matched_runs.ptr, (uint32_t)m.num_matcher_runs, (uint32_t)num_runs,
+                         (const uint32_t *)st->run_lane.ptr, a.n0, a.n1, a.regions, (const uint32_t *)st->matched_min_len.ptr,
+                         (const uint32_t *)st->cur->row_len.ptr(), st->runs.ptr, capacity, st->run_count.ptr, st->matched_error.ptr);
+  });
 }
 
 Status gpu_index_append_host_entries(IndexStore *st, const IndexAppend &a, const std::vector<uint32_t> &start,

@@ -11,6 +11,12 @@
 // three launches whatever N and S -- matcher_land_kernel, matcher_strip_kernel, matcher_simhash_kernel: every kernel finds
 // its lane in the round's lane table (blockIdx.y) and its source in the resident source table (through the resident list of
 // every workgroup's source, blockIdx.x); only the lanes with data are in the grid.
+//
+// Regions (CreateRegions; needle_hip_matcher_new_regions): source s is in region s % regions, lane l in region l % regions,
+// and a lane meets the sources of its own region only.  The source table and the workgroup list are ordered by region; a lane
+// table entry names its region's first workgroup and workgroup count, and its state holds its own region's frontiers alone.
+// The grid's x is the larger workgroup count of the regions in the round: a workgroup beyond its lane's region leaves after
+// the lane table read, so a round stays three launches.  One region is the kernel without any of this (kRegions = false).
 #include "matcher.h"
 
 #include <algorithm>
@@ -31,8 +37,9 @@ constexpr uint32_t kNoHash = 2u;    // the runs keep zero simhashes (open)
 struct MatchSource {
   uint32_t src_off, n;  // arena offset and length (>= 2)
   uint32_t min_len, index;
-  uint32_t row_off;     // of the source's rows inside a lane's state
-  uint32_t block_base, carried_blocks, pad;
+  uint32_t row_off;     // of the source's rows inside a lane's state (its region's part of it)
+  uint32_t block_base, carried_blocks;
+  uint32_t from_off;    // where the row lay in the device arena it was gathered from (matcher_gather_kernel; no round reads it)
 };
 
 struct MatchLane {
@@ -41,7 +48,8 @@ struct MatchLane {
   void *to;          // ... and the one it writes
   uint32_t fed, width;      // J and the strip's columns [J, J + width)
   uint32_t stage_off;       // of the new hashes inside the round's buffer, in words
-  uint32_t flags, pad[2];
+  uint32_t flags;
+  uint32_t block_first, blocks;  // the workgroups of the lane's region in the workgroup list (read with regions only)
 };
 static_assert(sizeof(MatchLane) == 48, "lane table entries are 12 words");
 
@@ -53,7 +61,17 @@ __global__ __launch_bounds__(kThreads) void matcher_land_kernel(const uint32_t *
   land_chunks<MatchLane>(round_buf, count, [](const MatchLane &ln) { return ln.hist; });
 }
 
-template <typename T>
+// Sources from an arena in device memory (the index store's) into the matcher's own, packed in table order: a workgroup per
+// source, consecutive lanes move consecutive words.  Creation checked every source against the arena.
+__global__ __launch_bounds__(kThreads) void matcher_gather_kernel(const uint32_t *__restrict__ from, const MatchSource *__restrict__ sources,
+                                                                  uint32_t num_sources, uint32_t *__restrict__ arena) {
+  for (uint32_t s = blockIdx.x; s < num_sources; s += gridDim.x) {
+    const MatchSource sc = sources[s];
+    for (uint32_t k = threadIdx.x; k < sc.n; k += kThreads) arena[sc.src_off + k] = from[sc.from_off + k];
+  }
+}
+
+template <typename T, bool kRegions>
 __global__ __launch_bounds__(kThreads) void matcher_strip_kernel(const uint32_t *__restrict__ arena,
                                                                  const MatchSource *__restrict__ sources,
                                                                  const uint32_t *__restrict__ block_source,
@@ -62,13 +80,18 @@ __global__ __launch_bounds__(kThreads) void matcher_strip_kernel(const uint32_t 
                                                                  uint32_t *__restrict__ count) {
   __shared__ uint32_t strip[kMaxStrip];                // dst[J .. J + W)
   __shared__ uint32_t rows[kCarriedRows + kMaxStrip];  // the source rows this workgroup's diagonals meet
-  const uint32_t lo = block_source[blockIdx.x];
-  const MatchSource sc = sources[lo];
   const MatchLane ln = lanes[blockIdx.y];
+  uint32_t blk = blockIdx.x;
+  if (kRegions) {  // the workgroups of the lane's region; the grid is as wide as the larger region (the whole workgroup leaves)
+    if (blk >= ln.blocks) return;
+    blk += ln.block_first;
+  }
+  const uint32_t lo = block_source[blk];
+  const MatchSource sc = sources[lo];
   // a lane that holds fewer than two items has no cell yet, whatever a reset left in its sets
   const WalkSide<T> sd{arena + sc.src_off, ln.hist, sc.n, max(ln.fed, 1u), max(ln.fed + ln.width, 1u), sc.n - 1u,
                        ln.fed >= 2u ? static_cast<const T *>(ln.from) + sc.row_off : nullptr, static_cast<T *>(ln.to) + sc.row_off, nullptr, true};
-  stream_walk<T, true>(strip, rows, sd, blockIdx.x - sc.block_base, sc.carried_blocks, (ln.flags & kEmitOpen) != 0u, threshold, sc.min_len, runs,
+  stream_walk<T, true>(strip, rows, sd, blk - sc.block_base, sc.carried_blocks, (ln.flags & kEmitOpen) != 0u, threshold, sc.min_len, runs,
                        capacity, count, [&](const uint32_t src_end, const uint32_t dst_end, const uint32_t len) {
                          return MatchRun{lo, src_end, dst_end, len, 0u, 0u, blockIdx.y, 0u};
                        });
@@ -104,12 +127,18 @@ struct Piece {
 
 struct Matcher::Impl {
   size_t n = 0;
+  size_t regions = 1;
   uint32_t threshold = 0;
   bool narrow = true;       // u16 run lengths
-  uint64_t total_rows = 0;  // of one lane's state
-  uint64_t cells_per_column = 0;  // sum of n_s - 1
+  // Per region: the rows of a lane's state, the sum of n_s - 1, and its workgroups in the list.  A video's lanes lie side by
+  // side in a set: lane l at (l / regions) * total_rows, region 1 behind region 0's rows.
+  uint64_t region_rows[2] = {0, 0}, region_cells[2] = {0, 0};
+  uint32_t region_first_block[2] = {0, 0}, region_blocks[2] = {0, 0};
+  uint64_t total_rows = 0;  // of one video's lanes
   uint32_t total_blocks = 0;
-  std::vector<MatchSource> table;
+  std::vector<MatchSource> table;  // the sources that have cells, region after region
+  Matcher::Origin origin;
+  int device = 0;
   std::vector<LaneState> lanes;
   DeviceBuffer<uint32_t> arena;
   DeviceBuffer<MatchSource> d_table;
@@ -131,6 +160,14 @@ struct Matcher::Impl {
   }
 
   size_t state_elem() const { return narrow ? sizeof(uint16_t) : sizeof(uint32_t); }
+  size_t region_of(size_t lane) const { return lane % regions; }
+  bool has_cells(size_t lane) const { return region_blocks[region_of(lane)] != 0; }  // else the lane only counts
+  uint64_t state_off(size_t lane) const {  // of the lane's frontiers in a set, in bytes
+    return ((uint64_t)(lane / regions) * total_rows + (region_of(lane) ? region_rows[0] : 0)) * state_elem();
+  }
+  uint64_t state_rows() const {  // of all lanes, one set
+    return (uint64_t)(n / regions) * total_rows;
+  }
 
   Status grow_history(LaneState &l, uint64_t need, hipStream_t stream) {
     if (need <= l.hist_cap) return Status::Ok();
@@ -166,19 +203,24 @@ struct Matcher::Impl {
     }
     std::vector<MatchLane> lt(k);
     uint64_t round_cells = 0;
+    uint32_t grid_blocks = 0;  // the most workgroups a lane of the round has
     for (size_t a = 0; a < k; a++) {
       const Piece &p = pieces[a];
       const LaneState &l = lanes[p.lane];
+      const size_t r = region_of(p.lane);
       MatchLane &e = lt[a];
       e.hist = l.hist;
-      e.from = state[l.cur].ptr + (uint64_t)p.lane * total_rows * state_elem();
-      e.to = state[l.cur ^ 1].ptr + (uint64_t)p.lane * total_rows * state_elem();
+      e.from = state[l.cur].ptr + state_off(p.lane);
+      e.to = state[l.cur ^ 1].ptr + state_off(p.lane);
       e.fed = (uint32_t)l.fed;
       e.width = p.width;
       e.stage_off = (uint32_t)words;
       e.flags = p.flags;
+      e.block_first = region_first_block[r];
+      e.blocks = region_blocks[r];
+      grid_blocks = std::max(grid_blocks, region_blocks[r]);
       words += p.width;
-      round_cells += cells_per_column * (uint64_t)(p.width - (l.fed == 0 && p.width ? 1u : 0u));
+      round_cells += region_cells[r] * (uint64_t)(p.width - (l.fed == 0 && p.width ? 1u : 0u));
     }
     if (!(s = upload_round(lt, pieces, words, &d_round, &round_stage, stream)).ok()) return s;
 
@@ -197,12 +239,13 @@ struct Matcher::Impl {
       }
       {
         KernelTimer timer("matcher_strip");
-        if (narrow)
-          hipLaunchKernelGGL(matcher_strip_kernel<uint16_t>, dim3(total_blocks, (uint32_t)k), block, 0, stream, arena.ptr, d_table.ptr,
-                             d_block_source.ptr, d_lanes, threshold, d_runs, slab.capacity, d_count);
-        else
-          hipLaunchKernelGGL(matcher_strip_kernel<uint32_t>, dim3(total_blocks, (uint32_t)k), block, 0, stream, arena.ptr, d_table.ptr,
-                             d_block_source.ptr, d_lanes, threshold, d_runs, slab.capacity, d_count);
+        const dim3 grid(grid_blocks, (uint32_t)k);  // (one region: total_blocks)
+        auto launch = [&](auto kernel) {
+          hipLaunchKernelGGL(kernel, grid, block, 0, stream, arena.ptr, d_table.ptr, d_block_source.ptr, d_lanes, threshold, d_runs,
+                             slab.capacity, d_count);
+        };
+        if (regions == 1) narrow ? launch(matcher_strip_kernel<uint16_t, false>) : launch(matcher_strip_kernel<uint32_t, false>);
+        else narrow ? launch(matcher_strip_kernel<uint16_t, true>) : launch(matcher_strip_kernel<uint32_t, true>);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       {
@@ -247,54 +290,107 @@ size_t Matcher::lanes() const { return impl_->n; }
 
 Status Matcher::Create(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *sources, const uint32_t *min_len,
                        size_t num_sources, size_t lanes, uint32_t threshold, std::unique_ptr<Matcher> *out) {
-  if (!sources || !min_len || !out || (num_hashes && !hashes)) return Status::Make(NeedleError_NullArgument, "matcher: null argument");
+  return CreateFrom(hashes, false, num_hashes, sources, min_len, false, num_sources, 1, lanes, threshold, out);
+}
+
+Status Matcher::CreateRegions(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *sources, const uint32_t *min_len,
+                              size_t num_sources, size_t regions, size_t lanes, uint32_t threshold, std::unique_ptr<Matcher> *out) {
+  return CreateFrom(hashes, false, num_hashes, sources, min_len, true, num_sources, regions, lanes, threshold, out);
+}
+
+Status Matcher::CreateRegionsDevice(const uint32_t *d_hashes, size_t num_hashes, const NeedleHipSeq *sources, const uint32_t *min_len,
+                                    size_t num_sources, size_t regions, size_t lanes, uint32_t threshold, std::unique_ptr<Matcher> *out) {
+  return CreateFrom(d_hashes, true, num_hashes, sources, min_len, true, num_sources, regions, lanes, threshold, out);
+}
+
+Status Matcher::CheckShape(size_t num_hashes, const NeedleHipSeq *sources, const uint32_t *min_len, size_t num_sources, size_t regions,
+                           size_t lanes) {
+  if (!sources || !min_len) return Status::Make(NeedleError_NullArgument, "matcher: null argument");
+  Impl scratch;
+  return Plan(&scratch, false, num_hashes, sources, min_len, true, num_sources, regions, lanes);
+}
+
+// The argument checks and the tables, host arithmetic alone.  `packed`: the arena will hold the sources with cells only, in
+// table order (gathered from a device arena); otherwise it is the caller's, offsets and all.
+Status Matcher::Plan(Impl *impl, bool packed, size_t num_hashes, const NeedleHipSeq *sources, const uint32_t *min_len, bool min_len_zero_ok,
+                     size_t num_sources, size_t regions, size_t lanes) {
+  Impl &m = *impl;
+  if (regions < 1 || regions > 2) return Status::Make(NeedleError_InvalidArgument, "matcher: regions must be 1 or 2");
   if (lanes == 0 || lanes > 65535) return Status::Make(NeedleError_InvalidArgument, "matcher: lanes must be 1 to 65535");
   if (num_sources == 0 || num_sources > 0xFFFFFFFFull || num_hashes > 0xFFFFFFFFull)
     return Status::Make(NeedleError_InvalidArgument, "matcher: 1 to 2^32 - 1 sources inside at most 2^32 - 1 hashes");
-  std::unique_ptr<Matcher> mt(new Matcher());
-  Impl &m = *mt->impl_;
-  uint64_t blocks = 0;
-  for (size_t s = 0; s < num_sources; s++) {
-    if (min_len[s] == 0) return Status::Make(NeedleError_InvalidArgument, "matcher: min_len must be >= 1");
-    if ((uint64_t)sources[s].offset + sources[s].len > num_hashes) return Status::Make(NeedleError_InvalidArgument, "matcher: a source lies outside the hashes");
-    const uint32_t len = sources[s].len;
-    if (len >= 65536) m.narrow = false;
-    if (len >= 2) {  // a shorter source has no cells
-      MatchSource e{};
-      e.src_off = sources[s].offset;
-      e.n = len;
-      e.min_len = min_len[s];
-      e.index = (uint32_t)s;
-      e.row_off = (uint32_t)m.total_rows;
-      e.block_base = (uint32_t)blocks;
-      e.carried_blocks = (len - 1 + kCarriedRows - 1) / kCarriedRows;
-      blocks += e.carried_blocks + kTopBlocks;
-      m.total_rows += len;
-      m.cells_per_column += len - 1;
-      m.block_source.insert(m.block_source.end(), e.carried_blocks + kTopBlocks, (uint32_t)m.table.size());
-      m.table.push_back(e);
+  if (num_sources % regions || lanes % regions)
+    return Status::Make(NeedleError_InvalidArgument, "matcher: the sources and the lanes must be multiples of the regions");
+  uint64_t blocks = 0, packed_hashes = 0;
+  for (size_t r = 0; r < regions; r++) {  // the table and the workgroup list region after region (one region: the sources in order)
+    m.region_first_block[r] = (uint32_t)blocks;
+    for (size_t s = r; s < num_sources; s += regions) {
+      if (min_len[s] == 0 && !min_len_zero_ok) return Status::Make(NeedleError_InvalidArgument, "matcher: min_len must be >= 1");
+      if ((uint64_t)sources[s].offset + sources[s].len > num_hashes) return Status::Make(NeedleError_InvalidArgument, "matcher: a source lies outside the hashes");
+      const uint32_t len = sources[s].len;
+      if (len >= 65536) m.narrow = false;
+      if (len >= 2 && min_len[s] != 0) {  // a shorter source, or one that can hold no run, has no cells
+        MatchSource e{};
+        e.src_off = packed ? (uint32_t)packed_hashes : sources[s].offset;
+        e.from_off = sources[s].offset;
+        e.n = len;
+        e.min_len = min_len[s];
+        e.index = (uint32_t)s;
+        e.row_off = (uint32_t)m.region_rows[r];
+        e.block_base = (uint32_t)blocks;
+        e.carried_blocks = (len - 1 + kCarriedRows - 1) / kCarriedRows;
+        blocks += e.carried_blocks + kTopBlocks;
+        packed_hashes += len;
+        m.region_rows[r] += len;
+        m.region_cells[r] += len - 1;
+        m.total_rows += len;
+        m.block_source.insert(m.block_source.end(), e.carried_blocks + kTopBlocks, (uint32_t)m.table.size());
+        m.table.push_back(e);
+      }
+      if (blocks > 0x7FFFFFFFull || m.total_rows > 0xFFFFFFFFull) return Status::Make(NeedleError_InvalidArgument, "matcher: the sources are too long together");
     }
-    if (blocks > 0x7FFFFFFFull || m.total_rows > 0xFFFFFFFFull) return Status::Make(NeedleError_InvalidArgument, "matcher: the sources are too long together");
+    m.region_blocks[r] = (uint32_t)blocks - m.region_first_block[r];
   }
   m.n = lanes;
-  m.threshold = threshold;
+  m.regions = regions;
   m.total_blocks = (uint32_t)blocks;
+  m.arena_bytes = m.table.empty() ? 0 : (packed ? packed_hashes : (uint64_t)num_hashes) * sizeof(uint32_t);  // (no cells: nothing goes up)
+  return Status::Ok();
+}
+
+// Every way in shares everything but how the sources reach the arena: the caller's host arena uploaded whole, or the sources
+// with cells gathered from a device arena (the index store's), no hashes uploaded.
+Status Matcher::CreateFrom(const uint32_t *hashes, bool on_device, size_t num_hashes, const NeedleHipSeq *sources, const uint32_t *min_len,
+                           bool min_len_zero_ok, size_t num_sources, size_t regions, size_t lanes, uint32_t threshold,
+                           std::unique_ptr<Matcher> *out) {
+  if (!sources || !min_len || !out || (num_hashes && !hashes)) return Status::Make(NeedleError_NullArgument, "matcher: null argument");
+  std::unique_ptr<Matcher> mt(new Matcher());
+  Impl &m = *mt->impl_;
+  Status s = Plan(&m, on_device, num_hashes, sources, min_len, min_len_zero_ok, num_sources, regions, lanes);
+  if (!s.ok()) return s;
+  m.threshold = threshold;
   m.lanes = std::vector<LaneState>(lanes);
   m.slab.capacity_from_env("NEEDLE_HIP_MATCHER_RUN_SLAB");
 
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
-  Status s = ensure_device();
-  if (!s.ok()) return s;
+  if (!(s = ensure_device()).ok()) return s;
+  (void)hipGetDevice(&m.device);
   if (!m.table.empty()) {
     hipStream_t stream = library_stream();
-    const uint64_t state_bytes = (uint64_t)lanes * m.total_rows * m.state_elem();
-    if (!(s = m.arena.reserve(std::max<size_t>(num_hashes, 1))).ok() || !(s = m.d_table.reserve(m.table.size())).ok() ||
+    const uint64_t state_bytes = m.state_rows() * m.state_elem();
+    if (!(s = m.arena.reserve(std::max<size_t>(m.arena_bytes / sizeof(uint32_t), 1))).ok() || !(s = m.d_table.reserve(m.table.size())).ok() ||
         !(s = m.d_block_source.reserve(m.block_source.size())).ok() ||
         !(s = m.state[0].reserve(state_bytes)).ok() || !(s = m.state[1].reserve(state_bytes)).ok())
       return s;
-    m.arena_bytes = num_hashes * sizeof(uint32_t);
-    NEEDLE_HIP_TRY(hipMemcpyAsync(m.arena.ptr, hashes, num_hashes * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_table.ptr, m.table.data(), m.table.size() * sizeof(MatchSource), hipMemcpyHostToDevice, stream));
+    if (on_device) {
+      KernelTimer timer("matcher_gather", stream);
+      hipLaunchKernelGGL(matcher_gather_kernel, dim3((uint32_t)std::min<size_t>(m.table.size(), 4096)), dim3(kThreads), 0, stream, hashes,
+                         (const MatchSource *)m.d_table.ptr, (uint32_t)m.table.size(), m.arena.ptr);
+      NEEDLE_HIP_TRY(hipGetLastError());
+    } else {
+      NEEDLE_HIP_TRY(hipMemcpyAsync(m.arena.ptr, hashes, num_hashes * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    }
     NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_block_source.ptr, m.block_source.data(), m.block_source.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     NEEDLE_HIP_TRY(hipMemsetAsync(m.state[0].ptr, 0, state_bytes, stream));
     NEEDLE_HIP_TRY(hipMemsetAsync(m.state[1].ptr, 0, state_bytes, stream));
@@ -326,7 +422,7 @@ Status Matcher::Feed(const uint32_t *const *items, const size_t *num_items) {
       const size_t take = std::min<size_t>(num_items[i] - done[i], kMaxStrip);
       if (take) {
         LaneState &l = m.lanes[i];
-        if (m.table.empty()) {  // no source has a cell: the lane only counts
+        if (!m.has_cells(i)) {  // no source of its region has a cell: the lane only counts
           l.fed += take;
         } else {
           pieces.push_back(Piece{i, items[i] + done[i], (uint32_t)take, 0u});
@@ -367,12 +463,13 @@ Status Matcher::Finish(const size_t *lanes, size_t k) {
     seen[i] = true;
     pieces.push_back(Piece{i, nullptr, 0u, kEmitOpen});
   }
-  if (pieces.empty()) return Status::Ok();
-  if (m.table.empty()) {
-    for (const Piece &p : pieces) m.lanes[p.lane].finished = true;
-    return Status::Ok();
+  std::vector<Piece> walked;
+  for (const Piece &p : pieces) {
+    if (m.has_cells(p.lane)) walked.push_back(p);
+    else m.lanes[p.lane].finished = true;  // (nothing can be open)
   }
-  return m.guarded_round(pieces, nullptr);
+  if (walked.empty()) return Status::Ok();
+  return m.guarded_round(walked, nullptr);
 }
 
 Status Matcher::Reset(const size_t *lanes, size_t k) {
@@ -414,7 +511,7 @@ Status Matcher::Open(size_t lane, std::vector<NeedleHipRun> *runs) {
   if (lane >= m.n) return Status::Make(NeedleError_InvalidArgument, "matcher: lane out of range");
   if (!m.poison.ok()) return m.poison;
   runs->clear();
-  if (m.lanes[lane].finished || m.lanes[lane].fed == 0 || m.table.empty()) return Status::Ok();  // nothing is open
+  if (m.lanes[lane].finished || m.lanes[lane].fed == 0 || !m.has_cells(lane)) return Status::Ok();  // nothing is open
   return m.guarded_round({Piece{lane, nullptr, 0u, kEmitOpen | kNoHash}}, runs);
 }
 
@@ -425,7 +522,15 @@ void Matcher::Stats(uint64_t stats[4]) const {
   stats[0] = m.feeds;
   stats[1] = m.launches;
   stats[2] = m.cells;
-  stats[3] = m.arena_bytes + 2 * (uint64_t)m.n * m.total_rows * m.state_elem() + history;
+  stats[3] = m.arena_bytes + 2 * m.state_rows() * m.state_elem() + history;
 }
+
+size_t Matcher::regions() const { return impl_->regions; }
+void Matcher::set_origin(const Origin &origin) { impl_->origin = origin; }
+Matcher::Origin Matcher::origin() const { return impl_->origin; }
+int Matcher::device() const { return impl_->device; }
+Status Matcher::poisoned() const { return impl_->poison; }
+const std::vector<NeedleHipRun> &Matcher::run_list(size_t lane) const { return impl_->lanes[lane].runs; }
+const uint32_t *Matcher::history(size_t lane) const { return impl_->lanes[lane].hist; }
 
 }  // namespace needle

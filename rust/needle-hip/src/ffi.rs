@@ -320,6 +320,14 @@ extern "C" {
         frame_hashes: *const *const FrameHashes,
         k: usize,
     ) -> NeedleError;
+    pub fn needle_hip_index_matcher_new(index: *mut NeedleHipIndex, videos: usize, output: *mut *mut NeedleHipMatcher) -> NeedleError;
+    pub fn needle_hip_index_add_streamed(
+        index: *mut NeedleHipIndex,
+        matcher: *mut NeedleHipMatcher,
+        crossmatcher: *mut NeedleHipCrossMatcher,
+        frame_hashes: *const *const FrameHashes,
+        k: usize,
+    ) -> NeedleError;
     pub fn needle_hip_index_pairs_scanned(index: *const NeedleHipIndex, total: *mut u64, last: *mut u64) -> NeedleError;
     /// 1..=MAX_CHANNELS interleaved channels -> mono, `(sum of a frame) / channels` with C truncation; `out[i]` holds
     /// `num_values[i] / channels` values.
@@ -515,6 +523,17 @@ extern "C" {
         sources: *const NeedleHipSeq,
         min_len: *const u32,
         num_sources: usize,
+        lanes: usize,
+        threshold: u32,
+        output: *mut *mut NeedleHipMatcher,
+    ) -> NeedleError;
+    pub fn needle_hip_matcher_new_regions(
+        hashes: *const u32,
+        num_hashes: usize,
+        sources: *const NeedleHipSeq,
+        min_len: *const u32,
+        num_sources: usize,
+        regions: usize,
         lanes: usize,
         threshold: u32,
         output: *mut *mut NeedleHipMatcher,

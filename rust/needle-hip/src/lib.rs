@@ -709,6 +709,26 @@ impl Matcher {
         Ok(Matcher { raw, lanes })
     }
 
+    /// Openings against openings, endings against endings: source `s` is in region `s % regions`, lane `l` in region
+    /// `l % regions`, and a lane meets its own region's sources only.  A `min_len` of 0 is allowed: that source has no cells.
+    pub fn with_regions(sources: &[(&[u32], u32)], regions: usize, lanes: usize, threshold: u32) -> Result<Self> {
+        let mut arena: Vec<u32> = Vec::new();
+        let mut seqs = Vec::with_capacity(sources.len());
+        let mut min_len = Vec::with_capacity(sources.len());
+        for (hashes, min) in sources {
+            seqs.push(ffi::NeedleHipSeq { offset: arena.len() as u32, len: hashes.len() as u32 });
+            arena.extend_from_slice(hashes);
+            min_len.push(*min);
+        }
+        let mut raw = ptr::null_mut();
+        unsafe {
+            check(ffi::needle_hip_matcher_new_regions(
+                arena.as_ptr(), arena.len(), seqs.as_ptr(), min_len.as_ptr(), seqs.len(), regions, lanes, threshold, &mut raw,
+            ))?;
+        }
+        Ok(Matcher { raw, lanes })
+    }
+
     /// The hashes every lane has received since the last feed: one slice per lane, an empty one for nothing.
     pub fn feed(&mut self, items: &[&[u32]]) -> Result<()> {
         assert_eq!(items.len(), self.lanes, "one slice per lane");
@@ -1026,6 +1046,26 @@ impl Index {
     pub fn add_matched(&mut self, matcher: &mut CrossMatcher, frame_hashes: &[&FrameHashes]) -> Result<()> {
         let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
         unsafe { check(ffi::needle_hip_index_add_matched(self.raw, matcher.raw, raw.as_ptr(), raw.len())) }
+    }
+}
+
+impl Index {
+    /// A matcher whose sources are this index's rows (gathered from the index's device arena), with `videos * regions`
+    /// lanes; `regions` is the index's (2 with endings).  The resident x arriving half of a streamed season at any library
+    /// size: feed it and a `CrossMatcher::with_regions` over the same videos, then hand both to `add_streamed`.
+    pub fn matcher(&mut self, videos: usize, regions: usize) -> Result<Matcher> {
+        let mut raw = ptr::null_mut();
+        unsafe { check(ffi::needle_hip_index_matcher_new(self.raw, videos, &mut raw))? };
+        Ok(Matcher { raw, lanes: videos * regions })
+    }
+
+    /// Appends the arriving videos with the runs of `matcher` (made by `matcher` since the index last changed) for the
+    /// resident x arriving pairs and those of `crossmatcher` (no residents; `None` with one video) for the arriving pairs.
+    /// Afterwards the index is what `add(frame_hashes)` leaves; on error it is as it was before the call.
+    pub fn add_streamed(&mut self, matcher: &mut Matcher, crossmatcher: Option<&mut CrossMatcher>, frame_hashes: &[&FrameHashes]) -> Result<()> {
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        let cross = crossmatcher.map_or(ptr::null_mut(), |c| c.raw);
+        unsafe { check(ffi::needle_hip_index_add_streamed(self.raw, matcher.raw, cross, raw.as_ptr(), raw.len())) }
     }
 }
 

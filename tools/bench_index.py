@@ -20,7 +20,12 @@ Medians over --steps calls after --warmup.
   feed_s                : what the search cost while the season "decoded": every lane fed in strips of 512 hashes
 
 Usage: python tools/bench_index.py [--sizes 250,500,1000] [--steps K] [--warmup W] [--out profiles/index_bench.json]
-       python tools/bench_index.py --matched [--resident K] [--arriving N] [--steps K] [--warmup W] [--out ...]"""
+       python tools/bench_index.py --matched [--resident K] [--arriving N] [--steps K] [--warmup W] [--out ...]
+
+--streamed: the same shape through both routes side by side -- one cross-matcher with residents and add_matched, against the
+matcher made from the index, the arriving pairs' cross-matcher and add_streamed (needle_hip_index_matcher_new,
+needle_hip_index_add_streamed): creation, feed time, the final add and the state bytes of each.
+       python tools/bench_index.py --streamed [--resident K] [--arriving N] [--steps K] [--warmup W] [--out ...]"""
 import argparse
 import ctypes as C
 import json
@@ -185,10 +190,68 @@ def bench_matched(fhs, n, k, steps, warmup):
             "crossmatcher_from_index_kernels_ms": gather_k, "feed_s": round(med(feeds), 3)}
 
 
+def bench_streamed(fhs, n, k, steps, warmup):
+    """The two routes of a streamed season at one shape, side by side: one cross-matcher with residents (add_matched) and
+    the matcher made from the index with the arriving pairs' cross-matcher (add_streamed)."""
+    new = fhs[n:n + k]
+    rows = [fh.opening_data()[0] for fh in new]
+    cap = [max(len(x) for x in rows)]
+    ts = new[0].opening_data()[1]
+    min_len = [int(-(-capi.DEFAULT_MIN_OPENING_DURATION * 10 ** 9 // int(ts[1] - ts[0])))]
+    out = {"matched": {"made_ms": [], "feed_s": [], "add_ms": []}, "streamed": {"made_ms": [], "feed_s": [], "add_ms": []}}
+    for rep in range(warmup + steps + 1):
+        timing = rep == warmup + steps          # one more pass with the event timers on
+        a, b = capi.Index(comparator(n)), capi.Index(comparator(n))
+        a.add(fhs[:n])
+        b.add(fhs[:n])
+        m, made_ms, feed_s = fed_matcher(a, rows, cap, min_len)
+        made = []
+        made2_ms = timed(lambda: made.extend([b.matcher(k), capi.CrossMatcher.with_regions(k, cap, min_len, capi.DEFAULT_HASH_MATCH_THRESHOLD)]))
+        mt, cm = made
+        t = time.perf_counter()
+        for at in range(0, cap[0], 512):
+            chunk = [x[at:at + 512] for x in rows]
+            mt.feed(chunk)
+            cm.feed(chunk)
+        mt.finish()
+        cm.finish()
+        feed2_s = time.perf_counter() - t
+        state = {"matched": m.stats()[3], "streamed": mt.stats()[3] + cm.stats()[3]}
+        runs = {"matched": m.ready()[0], "streamed": sum(mt.ready(i)[0] for i in range(k)) + cm.ready()[0]}
+        if timing:
+            capi.set_kernel_timing(",".join(SCAN + MATCHED) + ",sum")
+        a_ms = timed(lambda: a.add_matched(m, new))
+        if timing:
+            out["matched"]["add_kernels_ms"] = kernel_ms(SCAN + MATCHED)
+            capi.set_kernel_timing(",".join(SCAN + MATCHED) + ",sum")
+        b_ms = timed(lambda: b.add_streamed(mt, cm, new))
+        if timing:
+            out["streamed"]["add_kernels_ms"] = kernel_ms(SCAN + MATCHED)
+            capi.set_kernel_timing(None)
+        got = [None if r is None else (r.opening, r.ending) for r in a.results()]
+        assert got == [None if r is None else (r.opening, r.ending) for r in b.results()], "add_matched and add_streamed disagree"
+        assert a.store_sizes() == b.store_sizes() and a.pairs_searched() == b.pairs_searched() and b.pairs_scanned()[1] == 0
+        if warmup <= rep < warmup + steps:
+            for route, row in (("matched", (made_ms, feed_s, a_ms)), ("streamed", (made2_ms, feed2_s, b_ms))):
+                for key, v in zip(("made_ms", "feed_s", "add_ms"), row):
+                    out[route][key].append(v)
+        del m, mt, cm, a, b
+    for route in ("matched", "streamed"):
+        for key in ("made_ms", "feed_s", "add_ms"):
+            out[route][key] = round(statistics.median(out[route][key]), 3)
+        out[route]["state_bytes"] = state[route]
+        out[route]["runs"] = runs[route]
+    out.update({"resident": n, "arriving": k, "regions": 1, "min_len": min_len[0], "items_per_video": cap[0],
+                "what": "matched: index.crossmatcher + add_matched; streamed: index.matcher + CrossMatcher.with_regions + add_streamed; "
+                        "feeds in strips of 512 items, every lane in every feed; medians"})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="250,500,1000")
     ap.add_argument("--matched", action="store_true")
+    ap.add_argument("--streamed", action="store_true")
     ap.add_argument("--resident", type=int, default=1000)
     ap.add_argument("--arriving", type=int, default=28)
     ap.add_argument("--steps", type=int, default=3)
@@ -197,14 +260,17 @@ def main():
     a = ap.parse_args()
     if capi.device_count() < 1:
         raise SystemExit("bench_index.py needs a HIP device")
-    sizes = [int(x) for x in a.sizes.split(",")] if not a.matched else []
+    sizes = [int(x) for x in a.sizes.split(",")] if not (a.matched or a.streamed) else []
     t = time.perf_counter()
-    fhs = analyze(a.resident + a.arriving if a.matched else max(sizes) + 8)
+    fhs = analyze(a.resident + a.arriving if a.matched or a.streamed else max(sizes) + 8)
     doc = {"machine": "AMD Instinct MI355X (gfx950), one GPU", "device": capi.device_pci_bus_id(), "episode_s": EPISODE_S, "window_hashes": len(fhs[0].opening_data()[0]),
            "analyze_s": round(time.perf_counter() - t, 1), "steps": a.steps, "warmup": a.warmup, "sizes": {}}
     if a.matched:
         del doc["sizes"]
         doc["matched"] = bench_matched(fhs, a.resident, a.arriving, a.steps, a.warmup)
+    if a.streamed:
+        doc.pop("sizes", None)
+        doc["two_routes"] = bench_streamed(fhs, a.resident, a.arriving, a.steps, a.warmup)
     for n in sizes:
         row = {}
         for k in (1, 8):
