@@ -347,6 +347,36 @@ enum NeedleError needle_hip_comparator_results_from_runs(const struct NeedleAudi
                                                          const NeedleHipRun *runs, size_t num_runs, size_t first_video,
                                                          size_t video_count, NeedleHipSearchResult *results);
 
+/* ---- Match evidence: why a video got its result ------------------------------------------------------
+ * One record per region of a video: the candidate find_best_match picked (comparator.rs:405-515; ascending (-score,
+ * candidate index), first), the pair it came from and how many of the video's candidates agree with it.  For a region
+ * that has a match, result.start == start_ns + time_padding and result.end == end_ns - time_padding - the video's hash
+ * duration.  A video without a result, a region without a match and, without include_endings, every `ending` read
+ * partner = UINT32_MAX and every other field 0. */
+typedef struct NeedleHipMatchEvidence {
+  uint32_t partner;      /* position of the OTHER video of the winner's pair; UINT32_MAX: this region has no match, every other field 0 */
+  uint32_t is_source;    /* 1: this video is that pair's source (the lower position) */
+  uint32_t candidate;    /* the winner's index in the video's candidate list (comparator.rs:410-432 order) */
+  uint32_t candidates;   /* length of that list (openings and endings together, as the reference builds it) */
+  uint32_t support;      /* `count` of :466 for the winner: candidates with popcount(hash ^ winner.hash) < threshold + threshold / 2, the winner included, both regions (:436-453) */
+  uint32_t partners;     /* distinct partner videos among those `support` candidates */
+  float    score;        /* count * 0.3f + secs * 0.7f in f32, two roundings, no fused multiply-add: the negated key of :469 */
+  uint32_t match_hash, partner_hash;       /* the winner's simhash on this video's side / on the partner's */
+  uint32_t reserved;                       /* 0 */
+  uint64_t start_ns, end_ns;               /* the winner's interval in THIS video before padding (:476) */
+  uint64_t partner_start_ns, partner_end_ns; /* the same run's interval in the partner */
+} NeedleHipMatchEvidence;
+typedef struct NeedleHipSearchEvidence { NeedleHipMatchEvidence opening, ending; } NeedleHipSearchEvidence;
+
+/* needle_hip_comparator_results_from_runs with the evidence beside the results: the same arguments, checks and failures,
+ * no device work.  `evidence` has one slot per video, as `results` (the slots outside [first_video, first_video +
+ * video_count) read "no match"); `results` may be NULL.  What it writes to `results` is what the call above writes. */
+enum NeedleError needle_hip_comparator_results_from_runs_evidence(const struct NeedleAudioComparator *comparator,
+                                                                  const FrameHashes *const *frame_hashes, size_t num_videos,
+                                                                  const NeedleHipRun *runs, size_t num_runs, size_t first_video,
+                                                                  size_t video_count, NeedleHipSearchResult *results,
+                                                                  NeedleHipSearchEvidence *evidence);
+
 /* ---- Incremental index: a growing library searched one append at a time ---------------------------------
  * Results equal needle_hip_comparator_run_with_frame_hashes over ALL videos added so far, in insertion order, bit for
  * bit; an append searches only the pairs it adds (old x new and new x new) and recomputes the best match only of the
@@ -364,6 +394,10 @@ size_t needle_hip_index_len(const NeedleHipIndex *index); /* videos added (0 for
 enum NeedleError needle_hip_index_add(NeedleHipIndex *index, const FrameHashes *const *frame_hashes, size_t k);
 /* One result per video added, in insertion order; n >= needle_hip_index_len(index) (NeedleError_InvalidArgument otherwise). */
 enum NeedleError needle_hip_index_results(const NeedleHipIndex *index, NeedleHipSearchResult *results, size_t n);
+/* One evidence record per video, in insertion order, for the results above (n as there).  Computed on the device from the
+ * committed store when the call is made: `partner` is a current position, whatever was removed or replaced before, and
+ * nothing is kept between calls.  The index is not changed.  One wait. */
+enum NeedleError needle_hip_index_evidence(const NeedleHipIndex *index, NeedleHipSearchEvidence *evidence, size_t n);
 /* Video pairs that entered the index: over its life (*total) and by the last successful add (*last).  A pair none
  * of whose sequences can hold a run long enough is left out, as in the full search.  Either pointer may be NULL.
  * (needle_hip_index_pairs_scanned: those of them the one-shot scan searched.) */

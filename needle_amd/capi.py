@@ -58,6 +58,21 @@ class CSearchResult(C.Structure):
                 ("ending_start_ns", C.c_uint64), ("ending_end_ns", C.c_uint64)]
 
 
+class CMatchEvidence(C.Structure):                     # NeedleHipMatchEvidence
+    _fields_ = [("partner", C.c_uint32), ("is_source", C.c_uint32), ("candidate", C.c_uint32), ("candidates", C.c_uint32),
+                ("support", C.c_uint32), ("partners", C.c_uint32), ("score", C.c_float),
+                ("match_hash", C.c_uint32), ("partner_hash", C.c_uint32), ("reserved", C.c_uint32),
+                ("start_ns", C.c_uint64), ("end_ns", C.c_uint64),
+                ("partner_start_ns", C.c_uint64), ("partner_end_ns", C.c_uint64)]
+
+
+class CSearchEvidence(C.Structure):                    # NeedleHipSearchEvidence
+    _fields_ = [("opening", CMatchEvidence), ("ending", CMatchEvidence)]
+
+
+NO_PARTNER = 0xFFFFFFFF                                # NeedleHipMatchEvidence.partner of a region without a match
+
+
 RUN_DTYPE = np.dtype([("problem", "<u4"), ("src_end", "<u4"), ("dst_end", "<u4"), ("len", "<u4"),
                       ("src_match_hash", "<u4"), ("dst_match_hash", "<u4")])
 RUN_WORDS = 6
@@ -103,7 +118,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_index_new", "needle_hip_index_free", "needle_hip_index_len", "needle_hip_index_add",
     "needle_hip_index_results", "needle_hip_index_pairs_searched", "needle_hip_index_remove", "needle_hip_index_replace",
     "needle_hip_index_store_sizes", "needle_hip_index_crossmatcher_new", "needle_hip_index_add_matched",
-    "needle_hip_index_pairs_scanned",
+    "needle_hip_index_pairs_scanned", "needle_hip_comparator_results_from_runs_evidence", "needle_hip_index_evidence",
     "needle_hip_convert_host", "needle_hip_analyzer_run_pcm_format", "needle_hip_library_set_sample_format",
     "needle_hip_feeder_new", "needle_hip_feeder_free", "needle_hip_feeder_feed", "needle_hip_feeder_finish",
     "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
@@ -326,6 +341,8 @@ def lib():
                                                               C.POINTER(CSearchResult)]
     L.needle_hip_comparator_results_from_runs.argtypes = [vp, C.POINTER(vp), sz, vp, sz, sz, sz,
                                                           C.POINTER(CSearchResult)]
+    L.needle_hip_comparator_results_from_runs_evidence.argtypes = [vp, C.POINTER(vp), sz, vp, sz, sz, sz,
+                                                                   C.POINTER(CSearchResult), C.POINTER(CSearchEvidence)]
     L.needle_hip_library_new.argtypes = [sz, f32, f32, C.POINTER(vp)]
     L.needle_hip_library_free.argtypes = [vp]
     L.needle_hip_library_free.restype = None
@@ -364,6 +381,7 @@ def lib():
     L.needle_hip_index_len.restype = sz
     L.needle_hip_index_add.argtypes = [vp, C.POINTER(vp), sz]
     L.needle_hip_index_results.argtypes = [vp, C.POINTER(CSearchResult), sz]
+    L.needle_hip_index_evidence.argtypes = [vp, C.POINTER(CSearchEvidence), sz]
     L.needle_hip_index_pairs_searched.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.needle_hip_index_pairs_scanned.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.needle_hip_index_crossmatcher_new.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(u32), C.POINTER(vp)]
@@ -620,6 +638,40 @@ class SearchResult:                                      # comparator.rs:65-69 (
     ending: Optional[Tuple[int, int]]
 
 
+@dataclass
+class MatchEvidence:                                     # NeedleHipMatchEvidence of a region that has a match
+    partner: int
+    is_source: bool
+    candidate: int
+    candidates: int
+    support: int
+    partners: int
+    score: np.float32
+    match_hash: int
+    partner_hash: int
+    interval: Tuple[int, int]                            # in this video, before padding (ns)
+    partner_interval: Tuple[int, int]                    # the same run in the partner (ns)
+
+
+@dataclass
+class SearchEvidence:                                    # None: the region has no match
+    opening: Optional[MatchEvidence]
+    ending: Optional[MatchEvidence]
+
+
+def _match_evidence(e) -> Optional[MatchEvidence]:
+    if e.partner == NO_PARTNER:
+        assert bytes(e)[4:] == bytes(C.sizeof(CMatchEvidence) - 4), "a region without a match: every other field is 0"
+        return None
+    assert e.reserved == 0
+    return MatchEvidence(e.partner, bool(e.is_source), e.candidate, e.candidates, e.support, e.partners, np.float32(e.score),
+                         e.match_hash, e.partner_hash, (e.start_ns, e.end_ns), (e.partner_start_ns, e.partner_end_ns))
+
+
+def _evidence(arr, n) -> List[SearchEvidence]:
+    return [SearchEvidence(_match_evidence(arr[i].opening), _match_evidence(arr[i].ending)) for i in range(n)]
+
+
 def _results(arr, n) -> List[Optional[SearchResult]]:
     out: List[Optional[SearchResult]] = []
     for i in range(n):
@@ -832,6 +884,19 @@ class Comparator:
             n - first_video if video_count is None else video_count, res))
         return _results(res, n)
 
+    def results_from_runs_evidence(self, frame_hashes: Sequence[FrameHashes], runs: np.ndarray, first_video: int = 0,
+                                   video_count: Optional[int] = None) -> Tuple[List[Optional[SearchResult]], List[SearchEvidence]]:
+        """results_from_runs with the evidence beside every result (needle_hip_comparator_results_from_runs_evidence)."""
+        n = len(frame_hashes)
+        runs = np.ascontiguousarray(runs, dtype=RUN_DTYPE)
+        arr = (C.c_void_p * max(n, 1))(*[f._h for f in frame_hashes])
+        res = (CSearchResult * max(n, 1))()
+        ev = (CSearchEvidence * max(n, 1))()
+        check(lib().needle_hip_comparator_results_from_runs_evidence(
+            self._h or self.handle(), arr, n, runs.ctypes.data, runs.size, first_video,
+            n - first_video if video_count is None else video_count, res, ev))
+        return _results(res, n), _evidence(ev, n)
+
     def run(self, analyze: bool, display: bool = False, use_skip_files: bool = False,
             write_skip_files: bool = False, threading: bool = True) -> None:   # comparator.rs:637 / lib.rs:612
         h = self.handle()
@@ -941,6 +1006,14 @@ class Index:
         res = (CSearchResult * max(n, 1))()
         check(lib().needle_hip_index_results(self._h, res, n))
         return _results(res, n)
+
+    def evidence(self) -> List[SearchEvidence]:
+        """Why every video got its result (needle_hip_index_evidence): computed on the device when asked, from the
+        committed store; partners are current positions.  Changes nothing."""
+        n = len(self)
+        ev = (CSearchEvidence * max(n, 1))()
+        check(lib().needle_hip_index_evidence(self._h, ev, n))
+        return _evidence(ev, n)
 
     def pairs_searched(self) -> Tuple[int, int]:
         """(total, last): video pairs that entered the index over its life and by the last add."""

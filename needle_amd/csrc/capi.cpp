@@ -1357,6 +1357,32 @@ enum NeedleError needle_hip_comparator_results_from_runs(const struct NeedleAudi
   });
 }
 
+enum NeedleError needle_hip_comparator_results_from_runs_evidence(const struct NeedleAudioComparator *comparator,
+                                                                  const FrameHashes *const *frame_hashes, size_t num_videos,
+                                                                  const NeedleHipRun *runs, size_t num_runs, size_t first_video,
+                                                                  size_t video_count, NeedleHipSearchResult *results,
+                                                                  NeedleHipSearchEvidence *evidence) {
+  if (!comparator || !frame_hashes || !evidence || (!runs && num_runs)) return NeedleError_NullArgument;
+  if (first_video > num_videos || video_count > num_videos - first_video) return NeedleError_InvalidArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(num_videos);
+    for (size_t i = 0; i < num_videos; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    std::vector<VideoResult> res;
+    std::vector<NeedleHipSearchEvidence> ev;
+    Status s = comparator->inner.results_from_runs(fh, runs, num_runs, false, false, false, &res, first_video,
+                                                   first_video + video_count, &ev);
+    if (!s.ok()) return report(s);
+    for (size_t i = 0; i < num_videos; i++) {
+      if (results) fill_result(res[i], &results[i]);
+      evidence[i] = ev[i];
+    }
+    return NeedleError_Ok;
+  });
+}
+
 enum NeedleError needle_hip_index_new(const struct NeedleAudioComparator *comparator, NeedleHipIndex **output) {
   if (!comparator || !output) return NeedleError_NullArgument;
   return guarded([&]() -> NeedleError {
@@ -1403,6 +1429,18 @@ enum NeedleError needle_hip_index_results(const NeedleHipIndex *index, NeedleHip
   if (!results && !have.empty()) return NeedleError_NullArgument;
   if (!have.empty()) std::memcpy(results, have.data(), have.size() * sizeof(NeedleHipSearchResult));
   return NeedleError_Ok;
+}
+
+enum NeedleError needle_hip_index_evidence(const NeedleHipIndex *index, NeedleHipSearchEvidence *evidence, size_t n) {
+  if (!index) return NeedleError_NullArgument;
+  const size_t have = index->inner.size();
+  if (n < have) return report(Status::Make(NeedleError_InvalidArgument, "index evidence: buffer shorter than the index"));
+  if (!evidence && have) return NeedleError_NullArgument;
+  if (!have) return NeedleError_Ok;
+  return guarded([&]() -> NeedleError {
+    Status s = index->inner.evidence(evidence);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
 }
 
 enum NeedleError needle_hip_index_pairs_searched(const NeedleHipIndex *index, uint64_t *total, uint64_t *last) {

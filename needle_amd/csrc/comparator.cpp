@@ -8,6 +8,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <exception>
 #include <functional>
@@ -304,8 +305,15 @@ void Comparator::entries_from_runs(const NeedleHipRun *runs, size_t num_runs, co
 
 Status Comparator::best_matches(size_t num_videos, const PairEntries &pair_entries, bool display,
                                 bool use_skip_files, bool write_skip_files,
-                                std::vector<VideoResult> *per_video, size_t v0, size_t v1) const {
+                                std::vector<VideoResult> *per_video, size_t v0, size_t v1,
+                                std::vector<NeedleHipSearchEvidence> *evidence) const {
   per_video->assign(num_videos, {});
+  if (evidence) {
+    NeedleHipSearchEvidence none;
+    std::memset(&none, 0, sizeof(none));
+    none.opening.partner = none.ending.partner = UINT32_MAX;
+    evidence->assign(num_videos, none);
+  }
   v1 = std::min(v1, num_videos);
   v0 = std::min(v0, v1);
   auto mine = [&](size_t v) { return v >= v0 && v < v1; };
@@ -354,6 +362,42 @@ Status Comparator::best_matches(size_t num_videos, const PairEntries &pair_entri
   // the reference's order.
   // find_best_match (:405-515) of one video
   std::vector<Status> status(num_videos);
+  // The record of a winner (needle_hip.h NeedleHipMatchEvidence): the pair and the entry behind candidate `winner` of video
+  // v, found by walking v's pairs as the candidate list was built, and the partners among the candidates that support it.
+  auto describe = [&](size_t v, const std::vector<Candidate> &cand, size_t winner, uint32_t support, float score, NeedleHipMatchEvidence *ev) {
+    const uint32_t hash = cand[winner].match_hash;
+    size_t k = 0;
+    for (uint64_t q = info_first[v]; q < info_first[v + 1]; q++) {
+      const Info &in = info[q];
+      const uint32_t held = pair_entries.count[in.pair];
+      bool near = false;
+      for (size_t a = k; a < k + held; a++) near = near || (uint32_t)__builtin_popcount(cand[a].match_hash ^ hash) < bound;
+      ev->partners += near ? 1u : 0u;
+      if (winner >= k && winner < k + held) {
+        const HeapEntry *entries = pair_entries.entries.data() + pair_entries.first[in.pair];
+        const HeapEntry *e = nullptr;
+        size_t at = k;
+        for (int pass = 0; pass < 2 && !e; pass++)  // openings first, then endings (:414-431)
+          for (uint32_t x = 0; x < held && !e; x++)
+            if (entries[x].is_opening == (pass == 0) && at++ == winner) e = &entries[x];
+        size_t i = 0, j = 0;
+        pair_at(num_videos, in.pair, &i, &j);
+        ev->partner = (uint32_t)(in.is_source ? j : i);
+        ev->is_source = in.is_source ? 1u : 0u;
+        ev->match_hash = in.is_source ? e->src_match_hash : e->dst_match_hash;
+        ev->partner_hash = in.is_source ? e->dst_match_hash : e->src_match_hash;
+        ev->start_ns = in.is_source ? e->src_start : e->dst_start;
+        ev->end_ns = in.is_source ? e->src_end : e->dst_end;
+        ev->partner_start_ns = in.is_source ? e->dst_start : e->src_start;
+        ev->partner_end_ns = in.is_source ? e->dst_end : e->src_end;
+      }
+      k += held;
+    }
+    ev->candidate = (uint32_t)winner;
+    ev->candidates = (uint32_t)cand.size();
+    ev->support = support;
+    ev->score = score;
+  };
   auto find_best = [&](size_t v) {
     std::vector<Candidate> cand;
     for (uint64_t q = info_first[v]; q < info_first[v + 1]; q++) {
@@ -433,6 +477,7 @@ Status Comparator::best_matches(size_t num_videos, const PairEntries &pair_entri
         vr.result.ending_start = start;
         vr.result.ending_end = end;
       }
+      if (evidence) describe(v, cand, best_idx, links[best_idx], -best_score, want_opening ? &(*evidence)[v].opening : &(*evidence)[v].ending);
     }
   };
   std::vector<size_t> todo;
@@ -684,7 +729,7 @@ Status Comparator::run_with_frame_hashes(const std::vector<const FrameHashesData
 Status Comparator::results_from_runs(const std::vector<const FrameHashesData *> &fh,
                                      const NeedleHipRun *runs, size_t num_runs, bool display, bool use_skip_files,
                                      bool write_skip_files, std::vector<VideoResult> *per_video, size_t v0,
-                                     size_t v1) const {
+                                     size_t v1, std::vector<NeedleHipSearchEvidence> *evidence) const {
   const size_t n = fh.size();
   const size_t regions = include_endings_ ? 2 : 1;
   const size_t np = pair_count(n);
@@ -798,7 +843,7 @@ Status Comparator::results_from_runs(const std::vector<const FrameHashesData *> 
     }
   });
   trace.lap("heap entries per pair", np);
-  Status s = best_matches(n, pair_entries, display, use_skip_files, write_skip_files, per_video, v0, v1);
+  Status s = best_matches(n, pair_entries, display, use_skip_files, write_skip_files, per_video, v0, v1, evidence);
   trace.lap("best match per video", v1 - v0);
   return s;
 }

@@ -416,6 +416,7 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 // Which videos best_match_kernel's workgroups take, where a video's pairs' buckets are and where its result goes.  Built in the
 // kernel from EpilogueParams and the kernel's trailing arguments (none for the library job's form: its code is what it was).
+// winners_out: what the selection knows beside the result; only EvidenceVideos keeps it.
 struct RowMajorVideos {  // the library job: videos [v0, v1), buckets in the i-major pair order over n videos, results[v]
   uint64_t n;
   uint32_t v0;
@@ -428,6 +429,7 @@ struct RowMajorVideos {  // the library job: videos [v0, v1), buckets in the i-m
   }
   __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
   __device__ uint64_t video_hash_duration(uint32_t) const { return hash_duration; }
+  __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}  // (EvidenceVideos')
 };
 struct IndexVideos {  // an index append: the videos listed (*count of them), buckets in the store's j-major order, results[block]
   const uint32_t *list, *count;
@@ -439,6 +441,43 @@ struct IndexVideos {  // an index append: the videos listed (*count of them), bu
   __device__ uint64_t pair(uint32_t q, uint32_t v) const { return q < v ? column_start(v) + q : column_start(q + 1) + v; }
   __device__ uint32_t out(uint32_t block, uint32_t) const { return block; }
   __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
+  __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}
+};
+// What find_best_match knows about its winners and throws away, per video: left for match_evidence_kernel.
+struct DeviceWinners {
+  unsigned long long pool_base;  // the video's candidates in the pool, `candidates` of them
+  uint32_t candidates, pad;
+  struct {
+    uint32_t have, index, support;  // the winner's candidate index and its links (`count` of :466)
+    float weighted;                 // count * 0.3 + secs * 0.7 (:469, before the negation)
+  } region[2];                      // [0] opening, [1] ending
+};
+struct EvidenceVideos {  // the index's evidence: EVERY video of the store, buckets as IndexVideos, results[v], and the winners written out
+  const uint64_t *hash_durations;
+  DeviceWinners *winners;  // zeroed by the host: a video without candidates writes nothing
+  __device__ EvidenceVideos(const EpilogueParams &, const uint64_t *hd, DeviceWinners *w) : hash_durations(hd), winners(w) {}
+  __device__ bool live(uint32_t) const { return true; }
+  __device__ uint32_t video(uint32_t block) const { return block; }
+  __device__ uint64_t pair(uint32_t q, uint32_t v) const { return q < v ? column_start(v) + q : column_start(q + 1) + v; }
+  __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
+  __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
+  // thread 0, behind the selection: where the video's c candidates are, and each region's winner with its links
+  __device__ void winners_out(uint32_t v, unsigned long long pool_base, uint32_t c, const BestKey &opening, const BestKey &ending,
+                              bool include_endings, const uint32_t *links) const {
+    DeviceWinners w;
+    w.pool_base = pool_base;
+    w.candidates = c;
+    w.pad = 0;
+    for (int which = 0; which < 2; which++) {
+      const BestKey &k = which == 0 ? opening : ending;
+      const bool have = k.have && (which == 0 || include_endings);  // :486
+      w.region[which].have = have ? 1u : 0u;
+      w.region[which].index = have ? k.index : 0u;
+      w.region[which].support = have ? links[k.index] : 0u;
+      w.region[which].weighted = have ? -k.score : 0.f;
+    }
+    winners[v] = w;
+  }
 };
 
 // One workgroup per wanted video.
@@ -715,8 +754,129 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
         res.ending_end_ns = e;
       }
     }
+    videos.winners_out(v, pool_base, c, best[0][0], best[1][0], pr.include_endings != 0, links);  // (EvidenceVideos only)
     if (bad) atomicAdd(failed, 1u);
     results[videos.out(blockIdx.x, v)] = res;
+  }
+}
+
+// The evidence of the index's results (needle_hip.h NeedleHipSearchEvidence): one workgroup per video, behind
+// best_match_kernel<EvidenceVideos> on the same stream, whose winners (candidate index, links, score) and candidate pool it
+// reads.  It walks the video's pair slots in the reference's order, 256 at a time, with the prefix sums of their candidate
+// counts, as best_match's pass 2 does: the slot whose range holds a winner's index gives the partner and the role, the offset
+// in it the region and the DeviceEntry with both intervals and both simhashes.  On the same walk a slot counts as a partner of
+// a winner if any of its candidates is within the bound of the winner's hash (both regions, :436-453): its own lane looks while
+// the candidates are few, the workgroup where a slot holds many (a pair of silent stretches).  Any number of slots and of
+// candidates: nothing here is staged by candidate.
+template <class Videos, class... Extra>
+__global__ __launch_bounds__(256) void match_evidence_kernel(EpilogueParams pr, const uint32_t *__restrict__ start,
+                                                             const uint32_t *__restrict__ valid, const DeviceEntry *__restrict__ entries,
+                                                             const Candidate *__restrict__ cand_pool,
+                                                             NeedleHipSearchEvidence *__restrict__ out, Extra... extra) {
+  __shared__ uint32_t scan[256];
+  __shared__ uint32_t carry;
+  __shared__ uint32_t slot_cnt[256], slot_at[256], slot_near[256];
+  __shared__ uint32_t partners[2];
+  __shared__ NeedleHipSearchEvidence rec;
+  const uint32_t v = blockIdx.x, t = threadIdx.x;
+  if (v >= pr.n) return;
+  const Videos videos(pr, extra...);  // (the policy of the launch in front: the same slots, its winners)
+  const DeviceWinners w = videos.winners[v];
+  if (t == 0) {
+    memset(&rec, 0, sizeof(rec));
+    rec.opening.partner = rec.ending.partner = 0xFFFFFFFFu;
+    carry = 0;
+    partners[0] = partners[1] = 0;
+  }
+  __syncthreads();
+  bool have[2];
+  uint32_t hash[2];
+  const Candidate *cand = cand_pool + w.pool_base;
+  for (int which = 0; which < 2; which++) {
+    have[which] = w.region[which].have && w.region[which].index < w.candidates;
+    hash[which] = have[which] ? cand[w.region[which].index].hash : 0u;
+  }
+  if (!have[0] && !have[1]) {  // no candidate at all, or none of either kind (uniform)
+    if (t == 0) out[v] = rec;
+    return;
+  }
+  const uint32_t slots = pr.n - 1;  // (q, v) for q < v, then (v, q + 1)
+  auto bucket_of = [&](uint32_t q) -> uint64_t { return videos.pair(q, v) * pr.regions; };
+  auto near_of = [&](uint32_t h) -> uint32_t {
+    return (have[0] && (uint32_t)__popc(h ^ hash[0]) < pr.bound ? 1u : 0u) | (have[1] && (uint32_t)__popc(h ^ hash[1]) < pr.bound ? 2u : 0u);
+  };
+  constexpr uint32_t kOwnLook = 16;
+  for (uint32_t base = 0; base < slots; base += 256) {
+    const uint32_t q = base + t;
+    uint32_t cnt = 0, openings = 0;
+    uint64_t b = 0;
+    if (q < slots) {
+      b = bucket_of(q);
+      openings = valid[b];
+      cnt = openings + (pr.regions == 2 ? valid[b + 1] : 0u);
+    }
+    scan[t] = cnt;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+      const uint32_t add = (int)t >= d ? scan[t - d] : 0u;
+      __syncthreads();
+      scan[t] += add;
+      __syncthreads();
+    }
+    const uint32_t at = carry + scan[t] - cnt;
+    for (int which = 0; which < 2; which++) {
+      const uint32_t index = w.region[which].index;
+      if (!have[which] || index < at || index - at >= cnt) continue;
+      uint32_t k = index - at;  // openings first, then endings (:414-431)
+      const uint32_t r = k < openings ? 0u : 1u;
+      if (r) k -= openings;
+      const DeviceEntry e = entries[start[b + r] + k];
+      const bool as_source = q >= v;
+      NeedleHipMatchEvidence &ev = which == 0 ? rec.opening : rec.ending;
+      ev.partner = q < v ? q : q + 1;
+      ev.is_source = as_source ? 1u : 0u;
+      ev.match_hash = as_source ? e.src_hash : e.dst_hash;
+      ev.partner_hash = as_source ? e.dst_hash : e.src_hash;
+      ev.start_ns = as_source ? e.src_start : e.dst_start;
+      ev.end_ns = as_source ? e.src_end : e.dst_end;
+      ev.partner_start_ns = as_source ? e.dst_start : e.src_start;
+      ev.partner_end_ns = as_source ? e.dst_end : e.src_end;
+    }
+    uint32_t near = 0;
+    if (cnt <= kOwnLook)
+      for (uint32_t k = 0; k < cnt; k++) near |= near_of(cand[at + k].hash);
+    slot_cnt[t] = cnt;
+    slot_at[t] = at;
+    slot_near[t] = near;
+    __syncthreads();
+    for (uint32_t qq = 0; qq < 256; qq++) {
+      const uint32_t many = slot_cnt[qq];
+      if (many <= kOwnLook) continue;  // (uniform)
+      uint32_t mine = 0;
+      for (uint32_t k = t; k < many; k += 256) mine |= near_of(cand[slot_at[qq] + k].hash);
+      if (mine) atomicOr(&slot_near[qq], mine);
+    }
+    __syncthreads();
+    near = slot_near[t];
+    const unsigned long long near0 = __ballot(near & 1u), near1 = __ballot(near & 2u);
+    if ((t & 63u) == 0) {
+      if (near0) atomicAdd(&partners[0], (uint32_t)__popcll(near0));
+      if (near1) atomicAdd(&partners[1], (uint32_t)__popcll(near1));
+    }
+    if (t == 255) carry += scan[255];
+    __syncthreads();
+  }
+  if (t == 0) {
+    for (int which = 0; which < 2; which++) {
+      if (!have[which]) continue;
+      NeedleHipMatchEvidence &ev = which == 0 ? rec.opening : rec.ending;
+      ev.candidate = w.region[which].index;
+      ev.candidates = w.candidates;
+      ev.support = w.region[which].support;
+      ev.partners = partners[which];
+      ev.score = w.region[which].weighted;
+    }
+    out[v] = rec;
   }
 }
 

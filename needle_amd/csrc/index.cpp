@@ -558,4 +558,12 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
 
 Status Index::store_sizes(uint64_t sizes[4]) const { return index_store_sizes(store_, sizes); }
 
+Status Index::evidence(NeedleHipSearchEvidence *out) const {
+  if (!out) return Status::Make(NeedleError_NullArgument, "index evidence: null argument");
+  if (videos_.empty()) return Status::Ok();
+  IndexOptions o;
+  set_options(cmp_, regions_, rows_.large_ok, &o);
+  return gpu_index_evidence(store_, o, out);
+}
+
 }  // namespace needle

@@ -56,6 +56,9 @@ class Index {
   // heap entries held, entry slots in use, hashes in the arena, timestamps in the table
   Status store_sizes(uint64_t sizes[4]) const;
   const std::vector<NeedleHipSearchResult> &results() const { return results_; }
+  // One evidence record per video (needle_hip.h), size() of them, computed on the device from the committed store when
+  // asked: best_match over every video with the winners written out, then the entries behind them.  Changes nothing.
+  Status evidence(NeedleHipSearchEvidence *out) const;
   uint64_t pairs_total() const { return pairs_total_; }
   uint64_t pairs_last() const { return pairs_last_; }
   // pairs handed to the one-shot scan (add_matched and add_streamed hand it none)

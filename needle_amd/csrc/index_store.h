@@ -141,6 +141,11 @@ Status gpu_index_edit_host_entries(IndexStore *store, const IndexEdit &edit, con
                                    const std::vector<uint32_t> &valid, const std::vector<IndexEntry> &entries, IndexAppendOut *out);
 void index_store_switch(IndexStore *store, const IndexEdit &edit, uint32_t held);
 void index_store_clear(IndexStore *store);  // every video removed (no device work)
+// Match evidence (needle_hip.h NeedleHipSearchEvidence), one record per committed video into evidence[0 .. n): best_match over
+// EVERY video of the committed store with the winners' index, count and score written out (the third video policy,
+// epilogue_kernels.h), then match_evidence_kernel, which finds the entries behind them.  Reads the committed tables, writes
+// the operations' scratch (candidate pool, links, control words) and buffers of its own; one wait.  Nothing is kept.
+Status gpu_index_evidence(IndexStore *store, const IndexOptions &options, NeedleHipSearchEvidence *evidence);
 // [0] heap entries held (sum of the buckets' valid counts: one read of the table), [1] entry slots in use, [2] hashes in
 // the arena, [3] timestamps in the table.
 Status index_store_sizes(IndexStore *store, uint64_t sizes[4]);

@@ -307,11 +307,17 @@ struct IndexStore {
   DeviceBuffer<NeedleHipSearchResult> results;
   PinnedHead *pinned = nullptr;
   size_t pinned_bytes = 0;
+  // gpu_index_evidence's own: the winners best_match leaves, the records, and where they are read back
+  DeviceBuffer<DeviceWinners> winners;
+  DeviceBuffer<NeedleHipSearchEvidence> evidence;
+  NeedleHipSearchEvidence *evidence_pinned = nullptr;
+  size_t evidence_pinned_count = 0;
   uint32_t capacity = 1u << 16;  // of the run list; grows to what an append found
   bool used = false;  // an append has enqueued work (a store made without a device never has)
   int device = 0;
   ~IndexStore() {
     if (pinned) (void)hipHostFree(pinned);
+    if (evidence_pinned) (void)hipHostFree(evidence_pinned);
   }
 };
 
@@ -829,6 +835,53 @@ void index_store_switch(IndexStore *st, const IndexEdit &e, uint32_t held) {
 void index_store_clear(IndexStore *st) {
   st->n = 0;
   st->buckets = st->entries = st->rows = st->ts = st->hashes = 0;
+}
+
+// ---- match evidence -------------------------------------------------------------------------------------------------------
+// best_match over every committed video under EvidenceVideos (the selection itself, with the winners' index, links and score
+// written out), then match_evidence_kernel over the same videos, which reads those and the candidate pool the first launch
+// filled.  The committed tables are only read; the candidate pool, the links, the results slots and the control words are an
+// operation's scratch, which every operation sets up again before it reads it.
+Status gpu_index_evidence(IndexStore *st, const IndexOptions &o, NeedleHipSearchEvidence *evidence) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = ensure_device();
+  if (!s.ok() || !(s = index_check_device(st)).ok()) return s;
+  const uint32_t n = st->n;
+  if (!n) return Status::Ok();
+  hipStream_t stream = library_stream();
+  const uint64_t cand = std::max<uint64_t>(2 * st->entries, 1);  // every entry is a candidate of its two videos
+  if (!(s = st->ctl.reserve(1)).ok() || !(s = st->results.reserve(n)).ok() || !(s = st->cand.reserve(cand)).ok() ||
+      !(s = st->links.reserve(cand)).ok() || !(s = st->winners.reserve(n)).ok() || !(s = st->evidence.reserve(n)).ok())
+    return s;
+  if (n > st->evidence_pinned_count) {
+    if (st->evidence_pinned) (void)hipHostFree(st->evidence_pinned);
+    st->evidence_pinned = nullptr;
+    st->evidence_pinned_count = 0;
+    NEEDLE_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&st->evidence_pinned), 2 * (size_t)n * sizeof(NeedleHipSearchEvidence), hipHostMallocDefault));
+    st->evidence_pinned_count = 2 * (size_t)n;
+  }
+  const StoreTables &t = *st->cur;
+  const EpilogueParams pr = epilogue_params(o, o.large_ok, n, st->buckets);
+  EpilogueControl *ctl = st->ctl.ptr;
+  NEEDLE_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(EpilogueControl), stream));
+  NEEDLE_HIP_TRY(hipMemsetAsync(st->winners.ptr, 0, (size_t)n * sizeof(DeviceWinners), stream));
+  {
+    KernelTimer timer("index_evidence_match", stream);
+    hipLaunchKernelGGL((best_match_kernel<EvidenceVideos, const uint64_t *, DeviceWinners *>), dim3(n), dim3(256), 0, stream, pr, t.start.ptr(),
+                       t.valid.ptr(), t.entry.ptr(), st->cand.ptr, &ctl->cand_cursor, st->links.ptr, st->results.ptr, &ctl->failed,
+                       t.hash_duration.ptr(), st->winners.ptr);
+  }
+  {
+    KernelTimer timer("index_evidence", stream);
+    hipLaunchKernelGGL((match_evidence_kernel<EvidenceVideos, const uint64_t *, DeviceWinners *>), dim3(n), dim3(256), 0, stream, pr,
+                       (const uint32_t *)t.start.ptr(), (const uint32_t *)t.valid.ptr(), (const DeviceEntry *)t.entry.ptr(),
+                       (const Candidate *)st->cand.ptr, st->evidence.ptr, (const uint64_t *)t.hash_duration.ptr(), st->winners.ptr);
+  }
+  NEEDLE_HIP_TRY(hipGetLastError());
+  NEEDLE_HIP_TRY(hipMemcpyAsync(st->evidence_pinned, st->evidence.ptr, (size_t)n * sizeof(NeedleHipSearchEvidence), hipMemcpyDeviceToHost, stream));
+  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  std::memcpy(evidence, st->evidence_pinned, (size_t)n * sizeof(NeedleHipSearchEvidence));
+  return Status::Ok();
 }
 
 int index_store_device(const IndexStore *st) { return st->device; }

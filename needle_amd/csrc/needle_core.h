@@ -149,10 +149,12 @@ class Comparator {
   ns_t time_padding() const { return time_padding_; }
   // Run list of ALL pairs (NeedleHipRun.problem = pair_index * regions + region) -> per-video results.
   // [v0, v1): the videos whose results are wanted (a rank's block in a multi-GPU job; the other slots of
-  // per_video stay empty and only the pairs that touch the block are worked on).
+  // per_video stay empty and only the pairs that touch the block are worked on).  evidence (optional): one record per
+  // video beside its result (needle_hip.h NeedleHipSearchEvidence), written by find_best_match as it picks the winner.
   Status results_from_runs(const std::vector<const FrameHashesData *> &frame_hashes, const NeedleHipRun *runs,
                            size_t num_runs, bool display, bool use_skip_files, bool write_skip_files,
-                           std::vector<VideoResult> *per_video, size_t v0 = 0, size_t v1 = ~(size_t)0) const;
+                           std::vector<VideoResult> *per_video, size_t v0 = 0, size_t v1 = ~(size_t)0,
+                           std::vector<NeedleHipSearchEvidence> *evidence = nullptr) const;
   // Heap entries of every pair, pairs in lexicographic order, in one allocation: those of pair p are
   // entries[first[p] .. first[p] + count[p]) (a library has ~n^2 / 2 pairs: no vector per pair).
   struct PairEntries {
@@ -163,7 +165,7 @@ class Comparator {
   // :583-626 — per video best match from the per-pair entries.
   Status best_matches(size_t num_videos, const PairEntries &pair_entries, bool display, bool use_skip_files,
                       bool write_skip_files, std::vector<VideoResult> *per_video, size_t v0 = 0,
-                      size_t v1 = ~(size_t)0) const;
+                      size_t v1 = ~(size_t)0, std::vector<NeedleHipSearchEvidence> *evidence = nullptr) const;
   // :593-626, the walk with side effects over results that are already there (any[v]: video v has a candidate at all)
   Status walk_results(size_t num_videos, const std::vector<uint8_t> &any, const std::vector<Status> &status, bool display,
                       bool use_skip_files, bool write_skip_files, std::vector<VideoResult> *per_video, size_t v0,

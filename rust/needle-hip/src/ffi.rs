@@ -69,6 +69,44 @@ pub struct NeedleHipSearchResult {
     pub ending_end_ns: u64,
 }
 
+/// Why a region of a video got its match (`NeedleHipMatchEvidence`, include/needle_hip.h): the winner of
+/// `find_best_match`, its pair and the candidates that agree with it.  `partner == u32::MAX`: no match, every other field 0.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct NeedleHipMatchEvidence {
+    pub partner: u32,
+    pub is_source: u32,
+    pub candidate: u32,
+    pub candidates: u32,
+    pub support: u32,
+    pub partners: u32,
+    pub score: f32,
+    pub match_hash: u32,
+    pub partner_hash: u32,
+    pub reserved: u32,
+    pub start_ns: u64,
+    pub end_ns: u64,
+    pub partner_start_ns: u64,
+    pub partner_end_ns: u64,
+}
+
+/// `NeedleHipSearchEvidence`: the opening's record and the ending's.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct NeedleHipSearchEvidence {
+    pub(crate) opening: NeedleHipMatchEvidence,
+    pub(crate) ending: NeedleHipMatchEvidence,
+}
+
+impl NeedleHipSearchEvidence {
+    pub fn opening(&self) -> NeedleHipMatchEvidence {
+        self.opening
+    }
+    pub fn ending(&self) -> NeedleHipMatchEvidence {
+        self.ending
+    }
+}
+
 /// One sequence inside a hash arena (`NeedleHipSeq`, include/needle_hip.h).
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -298,6 +336,18 @@ extern "C" {
     pub fn needle_hip_index_len(index: *const NeedleHipIndex) -> usize;
     pub fn needle_hip_index_add(index: *mut NeedleHipIndex, frame_hashes: *const *const FrameHashes, k: usize) -> NeedleError;
     pub fn needle_hip_index_results(index: *const NeedleHipIndex, results: *mut NeedleHipSearchResult, n: usize) -> NeedleError;
+    pub fn needle_hip_index_evidence(index: *const NeedleHipIndex, evidence: *mut NeedleHipSearchEvidence, n: usize) -> NeedleError;
+    pub fn needle_hip_comparator_results_from_runs_evidence(
+        comparator: *const NeedleAudioComparator,
+        frame_hashes: *const *const FrameHashes,
+        num_videos: usize,
+        runs: *const NeedleHipRun,
+        num_runs: usize,
+        first_video: usize,
+        video_count: usize,
+        results: *mut NeedleHipSearchResult,
+        evidence: *mut NeedleHipSearchEvidence,
+    ) -> NeedleError;
     pub fn needle_hip_index_pairs_searched(index: *const NeedleHipIndex, total: *mut u64, last: *mut u64) -> NeedleError;
     pub fn needle_hip_index_remove(index: *mut NeedleHipIndex, positions: *const usize, k: usize) -> NeedleError;
     pub fn needle_hip_index_replace(

@@ -361,6 +361,22 @@ impl SearchResult {
     }
 }
 
+pub use ffi::NeedleHipMatchEvidence as MatchEvidence;
+
+/// `NeedleHipSearchEvidence` with a region that has no match (`partner == u32::MAX`) as `None`.
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct SearchEvidence {
+    pub opening: Option<MatchEvidence>,
+    pub ending: Option<MatchEvidence>,
+}
+
+impl From<ffi::NeedleHipSearchEvidence> for SearchEvidence {
+    fn from(e: ffi::NeedleHipSearchEvidence) -> Self {
+        let some = |m: MatchEvidence| (m.partner != u32::MAX).then_some(m);
+        SearchEvidence { opening: some(e.opening()), ending: some(e.ending()) }
+    }
+}
+
 /// comparator.rs:74-147.
 pub struct Comparator<P: AsRef<Path>> {
     videos: Vec<P>,
@@ -435,6 +451,49 @@ impl<P: AsRef<Path>> Comparator<P> {
             ))?;
         }
         Ok(out)
+    }
+
+    /// The host epilogue alone, with the evidence beside every result (`needle_hip_comparator_results_from_runs_evidence`):
+    /// from a complete run list of all pairs to one (result, evidence) per video of `[first_video, first_video +
+    /// video_count)`; the other slots are `None` / no match.  No device work.
+    pub fn results_from_runs_evidence(
+        &self,
+        frame_hashes: &[FrameHashes],
+        runs: &[ffi::NeedleHipRun],
+        first_video: usize,
+        video_count: usize,
+    ) -> Result<Vec<(Option<SearchResult>, SearchEvidence)>> {
+        let handle = self.handle()?;
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        let mut results = vec![ffi::NeedleHipSearchResult::default(); raw.len()];
+        let mut evidence = vec![ffi::NeedleHipSearchEvidence::default(); raw.len()];
+        let status = unsafe {
+            check(ffi::needle_hip_comparator_results_from_runs_evidence(
+                handle,
+                raw.as_ptr(),
+                raw.len(),
+                runs.as_ptr(),
+                runs.len(),
+                first_video,
+                video_count,
+                results.as_mut_ptr(),
+                evidence.as_mut_ptr(),
+            ))
+        };
+        unsafe { ffi::needle_audio_comparator_free(handle) };
+        status?;
+        let span = |a: u64, b: u64| (Duration::from_nanos(a), Duration::from_nanos(b));
+        Ok(results
+            .into_iter()
+            .zip(evidence)
+            .map(|(r, e)| {
+                let result = r.has_result.then(|| SearchResult {
+                    opening: r.has_opening.then(|| span(r.opening_start_ns, r.opening_end_ns)),
+                    ending: r.has_ending.then(|| span(r.ending_start_ns, r.ending_end_ns)),
+                });
+                (result, SearchEvidence::from(e))
+            })
+            .collect())
     }
 
     /// comparator.rs:524-629.  One entry per video that matched something, in video order (`:608-617`).
@@ -1013,6 +1072,14 @@ impl Index {
                 })
             })
             .collect())
+    }
+
+    /// Why every video got its result (`needle_hip_index_evidence`): one record per video, computed on the device from the
+    /// committed store when asked; `partner` is a current position.  The index is not changed.
+    pub fn evidence(&self) -> Result<Vec<SearchEvidence>> {
+        let mut evidence = vec![ffi::NeedleHipSearchEvidence::default(); self.len()];
+        unsafe { check(ffi::needle_hip_index_evidence(self.raw, evidence.as_mut_ptr(), evidence.len()))? };
+        Ok(evidence.into_iter().map(SearchEvidence::from).collect())
     }
 
     /// (total, last): video pairs that entered the index over its life and by the last `add`.

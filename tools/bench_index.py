@@ -25,7 +25,13 @@ Usage: python tools/bench_index.py [--sizes 250,500,1000] [--steps K] [--warmup 
 --streamed: the same shape through both routes side by side -- one cross-matcher with residents and add_matched, against the
 matcher made from the index, the arriving pairs' cross-matcher and add_streamed (needle_hip_index_matcher_new,
 needle_hip_index_add_streamed): creation, feed time, the final add and the state bytes of each.
-       python tools/bench_index.py --streamed [--resident K] [--arriving N] [--steps K] [--warmup W] [--out ...]"""
+       python tools/bench_index.py --streamed [--resident K] [--arriving N] [--steps K] [--warmup W] [--out ...]
+
+--evidence: the cost of needle_hip_index_evidence over an index holding N videos of the sizes above: wall time of the call
+(into a buffer made before) and the event times of its two kernels (index_evidence_match = best_match_kernel over every video
+with the winners written out, index_evidence = match_evidence_kernel), medians of 5 calls after one warm-up; beside them
+index_best_match of the append of the N-th video onto N - 1, the figure an append pays for the videos it changed.
+       python tools/bench_index.py --evidence [--sizes 250,500,1000] [--out profiles/index_evidence_bench.json]"""
 import argparse
 import ctypes as C
 import json
@@ -247,11 +253,45 @@ def bench_streamed(fhs, n, k, steps, warmup):
     return out
 
 
+EVIDENCE = ("index_evidence_match", "index_evidence")
+
+
+def bench_evidence(fhs, n, calls=5):
+    index = capi.Index(comparator(n))
+    index.add(fhs[:n - 1])
+    capi.set_kernel_timing("index_best_match,sum")
+    index.add(fhs[n - 1:n])
+    append = kernel_ms(("index_best_match",))
+    capi.set_kernel_timing(None)
+    listed = sum(1 for r in index.results() if r is not None)
+    ev = (capi.CSearchEvidence * n)()
+    call = lambda: capi.check(capi.lib().needle_hip_index_evidence(index._h, ev, n))
+    call()                                                       # warm-up: the buffers of its own, the code objects
+    wall, kernels = [], {k: [] for k in EVIDENCE}
+    for _ in range(calls):
+        wall.append(timed(call))
+    for _ in range(calls):
+        capi.set_kernel_timing(",".join(EVIDENCE) + ",sum")     # a new selection: the sums start again
+        call()
+        for k, v in kernel_ms(EVIDENCE).items():
+            kernels[k].append(v)
+        capi.set_kernel_timing(None)
+    got = capi._evidence(ev, n)
+    results = index.results()
+    assert all((e.opening is None) == (r is None or r.opening is None) for e, r in zip(got, results)), "evidence and results disagree"
+    med = statistics.median
+    return {"videos": n, "videos_with_a_result": listed, "candidates_max": max((e.opening.candidates for e in got if e.opening), default=0),
+            "evidence_wall_ms": round(med(wall), 4), "evidence_wall_ms_min_max": [round(min(wall), 4), round(max(wall), 4)],
+            "evidence_kernels_ms": {k: round(med(v), 4) for k, v in kernels.items()},
+            "append_1_index_best_match_ms": append.get("index_best_match"), "calls": calls}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="250,500,1000")
     ap.add_argument("--matched", action="store_true")
     ap.add_argument("--streamed", action="store_true")
+    ap.add_argument("--evidence", action="store_true")
     ap.add_argument("--resident", type=int, default=1000)
     ap.add_argument("--arriving", type=int, default=28)
     ap.add_argument("--steps", type=int, default=3)
@@ -271,6 +311,10 @@ def main():
     if a.streamed:
         doc.pop("sizes", None)
         doc["two_routes"] = bench_streamed(fhs, a.resident, a.arriving, a.steps, a.warmup)
+    if a.evidence:
+        del doc["sizes"]
+        doc["evidence"] = {str(n): bench_evidence(fhs, n) for n in sizes}
+        sizes = []
     for n in sizes:
         row = {}
         for k in (1, 8):
