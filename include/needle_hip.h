@@ -377,6 +377,46 @@ enum NeedleError needle_hip_comparator_results_from_runs_evidence(const struct N
                                                                   size_t video_count, NeedleHipSearchResult *results,
                                                                   NeedleHipSearchEvidence *evidence);
 
+/* ---- A library of many shows: groups of videos ---------------------------------------------------------
+ * `groups` gives every video a label (any 32-bit value); videos of equal label are one season, and only pairs INSIDE a
+ * season are searched: no scan, no candidate and no result ever crosses a season.  A video's result -- and with `display`
+ * and the skip-file switches what is printed for it and what its skip file holds -- is what the ungrouped call over its own
+ * season's videos, in list order, gives it; the videos are walked in list order, and where several fail the call fails
+ * with the one at the lowest position.  A video alone in its season has no pair and no result.
+ *
+ * The grouped pair numbering: seasons are numbered in the order their first video appears, a season's members are its
+ * list positions in ascending order (they need not be adjacent), n_g of them; base_g = sum over h < g of
+ * n_h (n_h - 1) / 2, and pair (a, b), a < b, of season g with ranks (ra, rb) among its members is base_g +
+ * ra (2 n_g - ra - 1) / 2 + (rb - ra - 1): the i-major order inside the season, and with one season the ungrouped
+ * numbering.  NeedleHipRun.problem = NeedleHipProblem.tag = grouped pair id * regions + region.
+ *
+ * needle_hip_group_pairs: the number of grouped pairs into *num_pairs and, where pair_videos is not NULL, the (a, b) of
+ * pairs 0 .. min(capacity, *num_pairs) - 1 as pair_videos[2 p], pair_videos[2 p + 1]: to size buffers and decode `problem`. */
+enum NeedleError needle_hip_group_pairs(const uint32_t *groups, size_t num_videos, uint32_t *pair_videos, size_t capacity,
+                                        uint64_t *num_pairs);
+/* needle_hip_comparator_run_with_frame_hashes over the seasons of `groups` (num_videos labels); groups == NULL is that
+ * call.  NeedleError_InvalidArgument where grouped pairs x regions, or the hashes, exceed 2^32.  With endings, "no ending
+ * hash data present" only concerns videos that have a pair.  Match evidence, NeedleHipIndex, the library job and the
+ * matchers do not take groups. */
+enum NeedleError needle_hip_comparator_run_with_frame_hashes_grouped(const struct NeedleAudioComparator *comparator,
+                                                                     const FrameHashes *const *frame_hashes, size_t num_videos,
+                                                                     const uint32_t *groups, bool display, bool use_skip_files,
+                                                                     bool write_skip_files, NeedleHipSearchResult *results);
+/* The host half of the grouped call on its own, no device work: from a COMPLETE grouped run list (problem = grouped pair
+ * id * regions + region) to the results of all videos.  NeedleError_InvalidArgument for a run whose problem is beyond the
+ * grouped pairs x regions (a list in another numbering).  groups == NULL: needle_hip_comparator_results_from_runs over
+ * all videos. */
+enum NeedleError needle_hip_comparator_results_from_runs_grouped(const struct NeedleAudioComparator *comparator,
+                                                                 const FrameHashes *const *frame_hashes, size_t num_videos,
+                                                                 const uint32_t *groups, const NeedleHipRun *runs, size_t num_runs,
+                                                                 NeedleHipSearchResult *results);
+/* needle_audio_comparator_run (the file-based call: hashes from the .needle.dat files, or analyzed first) over the seasons
+ * of `groups`, parallel to the comparator's paths: num_groups_entries must be their number (InvalidArgument otherwise).
+ * groups == NULL: the ungrouped call. */
+enum NeedleError needle_hip_comparator_run_grouped(const struct NeedleAudioComparator *comparator, const uint32_t *groups,
+                                                   size_t num_groups_entries, bool analyze, bool display, bool use_skip_files,
+                                                   bool write_skip_files);
+
 /* ---- Incremental index: a growing library searched one append at a time ---------------------------------
  * Results equal needle_hip_comparator_run_with_frame_hashes over ALL videos added so far, in insertion order, bit for
  * bit; an append searches only the pairs it adds (old x new and new x new) and recomputes the best match only of the

@@ -119,6 +119,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_index_results", "needle_hip_index_pairs_searched", "needle_hip_index_remove", "needle_hip_index_replace",
     "needle_hip_index_store_sizes", "needle_hip_index_crossmatcher_new", "needle_hip_index_add_matched",
     "needle_hip_index_pairs_scanned", "needle_hip_comparator_results_from_runs_evidence", "needle_hip_index_evidence",
+    "needle_hip_group_pairs", "needle_hip_comparator_run_with_frame_hashes_grouped",
+    "needle_hip_comparator_results_from_runs_grouped", "needle_hip_comparator_run_grouped",
     "needle_hip_convert_host", "needle_hip_analyzer_run_pcm_format", "needle_hip_library_set_sample_format",
     "needle_hip_feeder_new", "needle_hip_feeder_free", "needle_hip_feeder_feed", "needle_hip_feeder_finish",
     "needle_hip_feeder_reset", "needle_hip_feeder_ready", "needle_hip_feeder_items", "needle_hip_feeder_frame_hashes",
@@ -339,6 +341,10 @@ def lib():
     L.needle_hip_analyzer_run_pcm_format.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.c_int, C.c_int, C.c_int, f32, b]
     L.needle_hip_comparator_run_with_frame_hashes.argtypes = [vp, C.POINTER(vp), sz, b, b, b,
                                                               C.POINTER(CSearchResult)]
+    L.needle_hip_group_pairs.argtypes = [vp, sz, vp, sz, C.POINTER(C.c_uint64)]
+    L.needle_hip_comparator_run_with_frame_hashes_grouped.argtypes = [vp, C.POINTER(vp), sz, vp, b, b, b, C.POINTER(CSearchResult)]
+    L.needle_hip_comparator_results_from_runs_grouped.argtypes = [vp, C.POINTER(vp), sz, vp, vp, sz, C.POINTER(CSearchResult)]
+    L.needle_hip_comparator_run_grouped.argtypes = [vp, vp, sz, b, b, b, b]
     L.needle_hip_comparator_results_from_runs.argtypes = [vp, C.POINTER(vp), sz, vp, sz, sz, sz,
                                                           C.POINTER(CSearchResult)]
     L.needle_hip_comparator_results_from_runs_evidence.argtypes = [vp, C.POINTER(vp), sz, vp, sz, sz, sz,
@@ -813,6 +819,24 @@ class Analyzer:
 
 
 # ---- Comparator ------------------------------------------------------------------------------------------
+def _group_labels(groups: Sequence[int], n: int) -> np.ndarray:
+    labels = np.ascontiguousarray(groups, dtype=np.uint32)
+    if labels.shape != (n,):
+        raise ValueError(f"{labels.size} group labels for {n} videos")
+    return labels
+
+
+def group_pairs(groups: Sequence[int]) -> np.ndarray:
+    """The (a, b) of every grouped pair id in order, as an array of shape (pairs, 2) (needle_hip_group_pairs): what a
+    grouped call searches, and how NeedleHipRun.problem // regions of its run list decodes."""
+    labels = np.ascontiguousarray(groups, dtype=np.uint32)
+    count = C.c_uint64(0)
+    check(lib().needle_hip_group_pairs(labels.ctypes.data, labels.size, None, 0, C.byref(count)))
+    pairs = np.zeros((count.value, 2), dtype=np.uint32)
+    check(lib().needle_hip_group_pairs(labels.ctypes.data, labels.size, pairs.ctypes.data, count.value, C.byref(count)))
+    return pairs
+
+
 class Comparator:
     """needle::audio::Comparator (comparator.rs:74-147) over needle_audio_comparator_* (lib.rs:537-637)."""
 
@@ -861,15 +885,33 @@ class Comparator:
         return out
 
     def run_with_frame_hashes(self, frame_hashes: Sequence[FrameHashes], display: bool = False,
-                              use_skip_files: bool = False, write_skip_files: bool = False
-                              ) -> List[Optional[SearchResult]]:       # comparator.rs:524
-        """One entry per video; None where the reference pushes no result (comparator.rs:608-617)."""
+                              use_skip_files: bool = False, write_skip_files: bool = False,
+                              groups: Optional[Sequence[int]] = None) -> List[Optional[SearchResult]]:       # comparator.rs:524
+        """One entry per video; None where the reference pushes no result (comparator.rs:608-617).  groups: a label per
+        video (any 32-bit value); only videos of equal label are compared (needle_hip.h "A library of many shows")."""
         h = self.handle()
         n = len(frame_hashes)
         ptrs = (C.c_void_p * max(n, 1))(*[f._h for f in frame_hashes])
         res = (CSearchResult * max(n, 1))()
-        check(lib().needle_hip_comparator_run_with_frame_hashes(h, ptrs, n, display, use_skip_files,
-                                                                write_skip_files, res))
+        if groups is None:
+            check(lib().needle_hip_comparator_run_with_frame_hashes(h, ptrs, n, display, use_skip_files,
+                                                                    write_skip_files, res))
+        else:
+            labels = _group_labels(groups, n)
+            check(lib().needle_hip_comparator_run_with_frame_hashes_grouped(h, ptrs, n, labels.ctypes.data, display,
+                                                                            use_skip_files, write_skip_files, res))
+        return _results(res, n)
+
+    def results_from_runs_grouped(self, frame_hashes: Sequence[FrameHashes], groups: Sequence[int],
+                                  runs: np.ndarray) -> List[Optional[SearchResult]]:
+        """The host epilogue alone over a grouped run list (problem = grouped pair id * regions + region): no device work."""
+        n = len(frame_hashes)
+        runs = np.ascontiguousarray(runs, dtype=RUN_DTYPE)
+        labels = _group_labels(groups, n)
+        arr = (C.c_void_p * max(n, 1))(*[f._h for f in frame_hashes])
+        res = (CSearchResult * max(n, 1))()
+        check(lib().needle_hip_comparator_results_from_runs_grouped(self._h or self.handle(), arr, n, labels.ctypes.data,
+                                                                    runs.ctypes.data, runs.size, res))
         return _results(res, n)
 
     def results_from_runs(self, frame_hashes: Sequence[FrameHashes], runs: np.ndarray, first_video: int = 0,
@@ -898,9 +940,14 @@ class Comparator:
         return _results(res, n), _evidence(ev, n)
 
     def run(self, analyze: bool, display: bool = False, use_skip_files: bool = False,
-            write_skip_files: bool = False, threading: bool = True) -> None:   # comparator.rs:637 / lib.rs:612
+            write_skip_files: bool = False, threading: bool = True, groups: Optional[Sequence[int]] = None) -> None:   # comparator.rs:637 / lib.rs:612
         h = self.handle()
-        check(lib().needle_audio_comparator_run(h, analyze, display, use_skip_files, write_skip_files, threading))
+        if groups is None:
+            check(lib().needle_audio_comparator_run(h, analyze, display, use_skip_files, write_skip_files, threading))
+        else:  # a label per path
+            labels = np.ascontiguousarray(groups, dtype=np.uint32)
+            check(lib().needle_hip_comparator_run_grouped(h, labels.ctypes.data, labels.size, analyze, display, use_skip_files,
+                                                          write_skip_files))
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -1383,6 +1383,90 @@ enum NeedleError needle_hip_comparator_results_from_runs_evidence(const struct N
   });
 }
 
+// ---- groups of videos (needle_hip.h "A library of many shows") ----
+enum NeedleError needle_hip_group_pairs(const uint32_t *groups, size_t num_videos, uint32_t *pair_videos, size_t capacity,
+                                        uint64_t *num_pairs) {
+  if (!num_pairs || (!groups && num_videos)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    if (num_videos > UINT32_MAX) return report(Status::Make(NeedleError_InvalidArgument, "group_pairs: more than 2^32 videos"));
+    const GroupTables tables(groups, num_videos);
+    *num_pairs = tables.pairs();
+    if (pair_videos) {
+      const GroupView view = tables.view();
+      for (uint64_t p = 0; p < std::min<uint64_t>(capacity, tables.pairs()); p++)
+        (void)grouped_pair_at(view, p, &pair_videos[2 * p], &pair_videos[2 * p + 1]);
+    }
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_comparator_run_with_frame_hashes_grouped(const struct NeedleAudioComparator *comparator,
+                                                                     const FrameHashes *const *frame_hashes, size_t num_videos,
+                                                                     const uint32_t *groups, bool display, bool use_skip_files,
+                                                                     bool write_skip_files, NeedleHipSearchResult *results) {
+  if (!comparator || !frame_hashes || !results) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(num_videos);
+    for (size_t i = 0; i < num_videos; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    std::vector<VideoResult> res;
+    Status s = comparator->inner.run_with_frame_hashes(fh, display, use_skip_files, write_skip_files, true, &res, groups);
+    if (!s.ok()) return report(s);
+    for (size_t i = 0; i < num_videos; i++) fill_result(res[i], &results[i]);
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_comparator_results_from_runs_grouped(const struct NeedleAudioComparator *comparator,
+                                                                 const FrameHashes *const *frame_hashes, size_t num_videos,
+                                                                 const uint32_t *groups, const NeedleHipRun *runs, size_t num_runs,
+                                                                 NeedleHipSearchResult *results) {
+  if (!comparator || !frame_hashes || !results || (!runs && num_runs)) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(num_videos);
+    for (size_t i = 0; i < num_videos; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    std::unique_ptr<const GroupTables> tables(groups ? new GroupTables(groups, num_videos) : nullptr);
+    if (tables) {
+      const uint64_t buckets = tables->pairs() * (comparator->inner.include_endings() ? 2 : 1);
+      if (buckets > UINT32_MAX)
+        return report(Status::Make(NeedleError_InvalidArgument, "library too large for one search call: more than 2^32 hashes or sequence pairs"));
+      if (comparator->inner.include_endings())
+        for (size_t v = 0; v < num_videos; v++)
+          if (fh[v]->ending.empty() && tables->size[tables->group_of[v]] > 1)
+            return report(Status::Make(NeedleError_Unknown, "no ending hash data present"));
+      for (size_t q = 0; q < num_runs; q++)
+        if (runs[q].problem >= buckets)
+          return report(Status::Make(NeedleError_InvalidArgument, "results_from_runs_grouped: run " + std::to_string(q) + " names problem " +
+                                                                      std::to_string(runs[q].problem) + ", the groups have " +
+                                                                      std::to_string(buckets) + " (a run list in another numbering?)"));
+    }
+    std::vector<VideoResult> res;
+    Status s = comparator->inner.results_from_runs(fh, runs, num_runs, false, false, false, &res, 0, ~(size_t)0, nullptr, tables.get());
+    if (!s.ok()) return report(s);
+    for (size_t i = 0; i < num_videos; i++) fill_result(res[i], &results[i]);
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_comparator_run_grouped(const struct NeedleAudioComparator *comparator, const uint32_t *groups,
+                                                   size_t num_groups_entries, bool analyze, bool display, bool use_skip_files,
+                                                   bool write_skip_files) {
+  if (!comparator) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    if (groups && num_groups_entries != comparator->inner.videos().size())
+      return report(Status::Make(NeedleError_InvalidArgument, "run_grouped: " + std::to_string(num_groups_entries) + " group labels for " +
+                                                                  std::to_string(comparator->inner.videos().size()) + " videos"));
+    std::vector<VideoResult> res;
+    Status s = comparator->inner.run(analyze, display, use_skip_files, write_skip_files, true, &res, groups);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 enum NeedleError needle_hip_index_new(const struct NeedleAudioComparator *comparator, NeedleHipIndex **output) {
   if (!comparator || !output) return NeedleError_NullArgument;
   return guarded([&]() -> NeedleError {

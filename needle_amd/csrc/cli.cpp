@@ -10,8 +10,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
+
+#include <dirent.h>
+#include <sys/stat.h>
 
 #include "../../include/needle_hip.h"
 
@@ -26,7 +30,11 @@ const char *kUsage =
     "               [--hash-duration F] [--include-endings] [--threaded-decoding] [--force] [--layout-downmix]\n"
     "    search     <PATHS>... [--hash-match-threshold N] [--min-opening-duration N] [--min-ending-duration N]\n"
     "               [--time-padding F] [--analyze] [--use-skip-files] [--write-skip-files] [--include-endings]\n"
-    "               [--no-display] [--layout-downmix]\n";
+    "               [--no-display] [--layout-downmix] [--group-by-dir]\n"
+    "               --group-by-dir: a library of many shows -- the files of one directory are one season and only files of\n"
+    "               the same directory are compared; every file's output and skip file are what `needle search <its\n"
+    "               directory>` gives.  A directory in <PATHS> also stands for its sub-directories (a library's root: one\n"
+    "               show each).  A file alone in its directory finds nothing.\n";
 
 // clap's `cmd.error(kind, msg).exit()`: message + usage on stderr, exit status 2 (main.rs:196-251)
 [[noreturn]] void usage_error(const std::string &msg) {
@@ -63,6 +71,7 @@ struct Args {
   uint16_t hash_match_threshold = 10, min_opening_duration = 20, min_ending_duration = 20;
   float time_padding = 0.0f;
   bool analyze = false, use_skip_files = false, write_skip_files = false, no_display = false;
+  bool group_by_dir = false;  // a video's group is its parent directory
 };
 
 Args parse(int argc, char **argv) {
@@ -121,6 +130,7 @@ Args parse(int argc, char **argv) {
     else if (se && flag == "use-skip-files") a.use_skip_files = true;
     else if (se && flag == "write-skip-files") a.write_skip_files = true;
     else if (se && flag == "no-display") a.no_display = true;
+    else if (se && flag == "group-by-dir") a.group_by_dir = true;
     else usage_error("Found argument '" + tok + "' which wasn't expected, or isn't valid in this context");
   }
   if (a.command.empty()) usage_error("'needle' requires a subcommand, but one was not provided");
@@ -139,8 +149,26 @@ Args parse(int argc, char **argv) {
 
 // Cli::find_video_files (main.rs:243-251) + videos.sort() (main.rs:272,305)
 std::vector<std::string> find_videos(const Args &a) {
+  // Discovery looks one level into a directory (util.rs:77-88).  --group-by-dir is given the root of a library: there a
+  // directory stands for itself and for its sub-directories, one show each.
+  std::vector<std::string> paths;
+  for (const std::string &p : a.paths) {
+    paths.push_back(p);
+    if (!a.group_by_dir) continue;
+    std::vector<std::string> below;
+    if (DIR *d = opendir(p.c_str())) {
+      while (dirent *ent = readdir(d)) {
+        const std::string name = ent->d_name, child = (!p.empty() && p.back() == '/' ? p : p + "/") + name;
+        struct stat st;
+        if (name != "." && name != ".." && stat(child.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) below.push_back(child);
+      }
+      closedir(d);
+    }
+    std::sort(below.begin(), below.end());
+    paths.insert(paths.end(), below.begin(), below.end());
+  }
   std::vector<const char *> raw;
-  for (const std::string &p : a.paths) raw.push_back(p.c_str());
+  for (const std::string &p : paths) raw.push_back(p.c_str());
   const char *const *videos = nullptr;
   size_t n = 0;
   const NeedleError e = needle_util_find_video_files(raw.data(), raw.size(), !a.file_headers_only, true, &videos, &n);
@@ -198,8 +226,20 @@ int main(int argc, char **argv) {
                                               &comparator);
   if (e != NeedleError_Ok) return fail(e);
   needle_hip_comparator_set_layout_downmix(const_cast<NeedleAudioComparator *>(comparator), a.layout_downmix);
-  e = needle_audio_comparator_run(comparator, a.analyze, !a.no_display, a.use_skip_files, a.write_skip_files,
-                                  !a.no_threading);
+  if (a.group_by_dir) {  // groups numbered as their directories first appear in the sorted list
+    std::map<std::string, uint32_t> seen;
+    std::vector<uint32_t> groups;
+    for (const std::string &v : videos) {
+      const size_t slash = v.find_last_of('/');
+      const std::string dir = slash == std::string::npos ? std::string() : v.substr(0, slash);
+      groups.push_back(seen.emplace(dir, (uint32_t)seen.size()).first->second);
+    }
+    e = needle_hip_comparator_run_grouped(comparator, groups.data(), groups.size(), a.analyze, !a.no_display, a.use_skip_files,
+                                          a.write_skip_files);
+  } else {
+    e = needle_audio_comparator_run(comparator, a.analyze, !a.no_display, a.use_skip_files, a.write_skip_files,
+                                    !a.no_threading);
+  }
   needle_audio_comparator_free(comparator);
   return e == NeedleError_Ok ? 0 : fail(e);
 }

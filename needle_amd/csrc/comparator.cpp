@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <exception>
 #include <functional>
 #include <mutex>
@@ -253,6 +254,47 @@ void binary_heap_push(std::vector<HeapEntry> *heap, const HeapEntry &e) {
   }
 }
 
+// The pairs of a call in id order, from pair p on: (i, j) of each.  Without groups the reference's i-major walk over n
+// videos (:537-545); with them the grouped order (pair_ids.h): group after group, i-major over each group's members.
+struct PairWalk {
+  size_t i = 0, j = 1;
+  PairWalk(size_t n, const GroupTables *groups, size_t p) : n_(n), groups_(groups) {
+    if (!groups_) {
+      if (p < pair_count(n)) pair_at(n, p, &i, &j);
+      return;
+    }
+    uint32_t a = 0, b = 0;
+    if (!grouped_pair_at(groups_->view(), p, &a, &b)) return;  // (no pair from p on: nothing is walked)
+    g_ = groups_->group_of[a];
+    ra_ = groups_->rank_of[a];
+    rb_ = groups_->rank_of[b];
+    i = a;
+    j = b;
+  }
+  void next() {
+    if (!groups_) {
+      if (++j == n_) j = ++i + 1;
+      return;
+    }
+    if (++rb_ == groups_->size[g_]) rb_ = ++ra_ + 1;
+    if (rb_ >= groups_->size[g_]) {  // the group's last pair is behind: on to the next group that has one
+      do g_++;
+      while (g_ < groups_->size.size() && groups_->size[g_] < 2);
+      if (g_ == groups_->size.size()) return;
+      ra_ = 0;
+      rb_ = 1;
+    }
+    i = groups_->members[groups_->first[g_] + ra_];
+    j = groups_->members[groups_->first[g_] + rb_];
+  }
+
+ private:
+  size_t n_;
+  const GroupTables *groups_;
+  size_t g_ = 0;
+  uint32_t ra_ = 0, rb_ = 1;
+};
+
 struct Candidate {  // comparator.rs:410-432
   ns_t start, end, hash_duration;
   uint32_t match_hash;
@@ -306,7 +348,7 @@ void Comparator::entries_from_runs(const NeedleHipRun *runs, size_t num_runs, co
 Status Comparator::best_matches(size_t num_videos, const PairEntries &pair_entries, bool display,
                                 bool use_skip_files, bool write_skip_files,
                                 std::vector<VideoResult> *per_video, size_t v0, size_t v1,
-                                std::vector<NeedleHipSearchEvidence> *evidence) const {
+                                std::vector<NeedleHipSearchEvidence> *evidence, const GroupTables *groups) const {
   per_video->assign(num_videos, {});
   if (evidence) {
     NeedleHipSearchEvidence none;
@@ -323,15 +365,13 @@ Status Comparator::best_matches(size_t num_videos, const PairEntries &pair_entri
   static thread_local std::vector<uint64_t> tl_info_first;  // scratch kept across calls, as in results_from_runs
   std::vector<uint64_t> &info_first = tl_info_first;
   info_first.assign(num_videos + 1, 0);
-  {
-    size_t i = 0, j = 1;
-    for (size_t p = 0; p < np; p++) {
+  {  // (a video meets its pairs in id order: in the grouped order too that is the reference's order over its season)
+    PairWalk w(num_videos, groups, 0);
+    for (size_t p = 0; p < np; p++, w.next())
       if (pair_entries.count[p]) {
-        if (mine(i)) info_first[i + 1]++;
-        if (mine(j)) info_first[j + 1]++;
+        if (mine(w.i)) info_first[w.i + 1]++;
+        if (mine(w.j)) info_first[w.j + 1]++;
       }
-      if (++j == num_videos) j = ++i + 1;
-    }
   }
   for (size_t v = 0; v < num_videos; v++) info_first[v + 1] += info_first[v];
   struct Info {
@@ -343,14 +383,12 @@ Status Comparator::best_matches(size_t num_videos, const PairEntries &pair_entri
   info.resize(info_first[num_videos]);  // every element is written below
   {
     std::vector<uint64_t> fill(info_first.begin(), info_first.end() - 1);
-    size_t i = 0, j = 1;
-    for (size_t p = 0; p < np; p++) {
+    PairWalk w(num_videos, groups, 0);
+    for (size_t p = 0; p < np; p++, w.next())
       if (pair_entries.count[p]) {
-        if (mine(i)) info[fill[i]++] = Info{p, true};
-        if (mine(j)) info[fill[j]++] = Info{p, false};
+        if (mine(w.i)) info[fill[w.i]++] = Info{p, true};
+        if (mine(w.j)) info[fill[w.j]++] = Info{p, false};
       }
-      if (++j == num_videos) j = ++i + 1;
-    }
   }
   auto info_count = [&](size_t v) { return info_first[v + 1] - info_first[v]; };
   const uint32_t bound = hash_match_threshold_ + hash_match_threshold_ / 2;  // :441
@@ -567,8 +605,11 @@ Status Comparator::walk_results(size_t num_videos, const std::vector<uint8_t> &a
 
 Status Comparator::run_with_frame_hashes(const std::vector<const FrameHashesData *> &fh, bool display,
                                          bool use_skip_files, bool write_skip_files, bool /*threading*/,
-                                         std::vector<VideoResult> *per_video) const {
+                                         std::vector<VideoResult> *per_video, const uint32_t *group_labels) const {
   const size_t n = fh.size();
+  // the seasons of a grouped call (pair_ids.h): only their pairs exist from here on
+  std::unique_ptr<const GroupTables> group_tables(group_labels ? new GroupTables(group_labels, n) : nullptr);
+  const GroupTables *groups = group_tables.get();
   const size_t regions = include_endings_ ? 2 : 1;
   EpilogueTrace trace;
   // hash arena: [video][region] sequences back to back; filled, and the minimum run lengths derived, on host threads
@@ -610,12 +651,12 @@ Status Comparator::run_with_frame_hashes(const std::vector<const FrameHashesData
       }
   });
   if (arena.pinned) gpu_prefetch_hashes(arena.pinned, total);  // goes up while the pair table is built
-  const size_t np = pair_count(n);
+  const size_t np = groups ? (size_t)groups->pairs() : pair_count(n);
   if (np * regions > UINT32_MAX)  // problem tags are 32-bit on the device (NeedleHipProblem.tag)
     return Status::Make(NeedleError_InvalidArgument, "library too large for one search call: more than 2^32 hashes or sequence pairs");
   if (include_endings_)
     for (size_t v = 0; v < n && n > 1; v++)
-      if (fh[v]->ending.empty())  // :271-273; the caller unwrap()s (every video is in some pair)
+      if (fh[v]->ending.empty() && (!groups || groups->size[groups->group_of[v]] > 1))  // :271-273; the caller unwrap()s (every video that is in some pair)
         return Status::Make(NeedleError_Unknown, "no ending hash data present");
   // (i, j) in the reference's i-major order (:537-545).  A pair one of whose sequences can hold no run long enough is
   // left out; when there is none such (the usual case) slot p * regions + r of the table is known up front and the
@@ -625,27 +666,23 @@ Status Comparator::run_with_frame_hashes(const std::vector<const FrameHashesData
   if (dense) {
     problems.resize(np * regions);
     parallel_chunks(np, 8192, host_workers((uint64_t)np * 256), [&](size_t p0, size_t p1) {
-      size_t i, j;
-      pair_at(n, p0, &i, &j);
-      for (size_t p = p0; p < p1; p++) {
+      PairWalk w(n, groups, p0);
+      for (size_t p = p0; p < p1; p++, w.next())
         for (size_t r = 0; r < regions; r++)
-          problems[p * regions + r] = NeedleHipProblem{(uint32_t)(i * regions + r), (uint32_t)(j * regions + r),
-                                                       std::max(min_len[i * regions + r], min_len[j * regions + r]),
+          problems[p * regions + r] = NeedleHipProblem{(uint32_t)(w.i * regions + r), (uint32_t)(w.j * regions + r),
+                                                       std::max(min_len[w.i * regions + r], min_len[w.j * regions + r]),
                                                        (uint32_t)(p * regions + r)};
-        if (++j == n) j = ++i + 1;
-      }
     });
   } else {
     problems.reserve(np * regions);
-    for (size_t p = 0, i = 0, j = 1; p < np; p++) {
+    PairWalk w(n, groups, 0);
+    for (size_t p = 0; p < np; p++, w.next())
       for (size_t r = 0; r < regions; r++) {
-        const uint32_t a = min_len[i * regions + r], b = min_len[j * regions + r];
+        const uint32_t a = min_len[w.i * regions + r], b = min_len[w.j * regions + r];
         if (a == 0 || b == 0) continue;  // no run of this pair can satisfy the duration test
-        problems.push_back(NeedleHipProblem{(uint32_t)(i * regions + r), (uint32_t)(j * regions + r), std::max(a, b),
+        problems.push_back(NeedleHipProblem{(uint32_t)(w.i * regions + r), (uint32_t)(w.j * regions + r), std::max(a, b),
                                             (uint32_t)(p * regions + r)});
       }
-      if (++j == n) j = ++i + 1;
-    }
   }
   trace.lap("arena + pair table", problems.size());
   std::vector<NeedleHipRun> runs;
@@ -653,7 +690,7 @@ Status Comparator::run_with_frame_hashes(const std::vector<const FrameHashesData
   // Library scale: scan AND per-video epilogue on the device (epilogue.hip), only the n results come back.  The arena's
   // rows are the videos' windows with their own timestamps; identical timestamp tables (videos of equal length) go up once.
   bool on_device = (uint64_t)np * regions >= kDeviceEpiloguePairs && n >= 2;
-  if (const char *e = std::getenv("NEEDLE_HIP_DEVICE_EPILOGUE")) on_device = std::atoi(e) != 0 && n >= 2;
+  if (const char *e = std::getenv("NEEDLE_HIP_DEVICE_EPILOGUE")) on_device = std::atoi(e) != 0 && n >= 2 && np >= 1;  // (groups: seasons of one video each have no pair)
   if (on_device) {
     std::vector<uint32_t> row_len(n * regions), row_ts(n * regions);
     std::vector<uint64_t> row_seek(n * regions, 0), ts;
@@ -685,6 +722,12 @@ Status Comparator::run_with_frame_hashes(const std::vector<const FrameHashesData
     job.row_ts = &row_ts;
     job.row_seek = &row_seek;
     job.ts = &ts;
+    std::vector<uint64_t> hash_durations;
+    if (groups) {
+      for (size_t v = 0; v < n; v++) hash_durations.push_back(fh[v]->hash_duration);
+      job.groups = groups;
+      job.hash_durations = &hash_durations;
+    }
     std::vector<NeedleHipSearchResult> results;
     uint32_t failed = 0;
     size_t found = 0;
@@ -714,7 +757,7 @@ Status Comparator::run_with_frame_hashes(const std::vector<const FrameHashesData
         return w;
       }
       if (failed & kEpilogueBucketTooLarge) note_epilogue_host_fallback("Comparator::run_with_frame_hashes", runs.size(), n);
-      return results_from_runs(fh, runs.data(), runs.size(), display, use_skip_files, write_skip_files, per_video);
+      return results_from_runs(fh, runs.data(), runs.size(), display, use_skip_files, write_skip_files, per_video, 0, ~(size_t)0, nullptr, groups);
     }
   }
 #endif
@@ -723,16 +766,18 @@ Status Comparator::run_with_frame_hashes(const std::vector<const FrameHashesData
                                    problems.size(), hash_match_threshold_, &runs);
   if (!s.ok()) return s;
   trace.lap("upload + scan + simhash + download", runs.size());
-  return results_from_runs(fh, runs.data(), runs.size(), display, use_skip_files, write_skip_files, per_video);
+  return results_from_runs(fh, runs.data(), runs.size(), display, use_skip_files, write_skip_files, per_video, 0, ~(size_t)0, nullptr, groups);
 }
 
 Status Comparator::results_from_runs(const std::vector<const FrameHashesData *> &fh,
                                      const NeedleHipRun *runs, size_t num_runs, bool display, bool use_skip_files,
                                      bool write_skip_files, std::vector<VideoResult> *per_video, size_t v0,
-                                     size_t v1, std::vector<NeedleHipSearchEvidence> *evidence) const {
+                                     size_t v1, std::vector<NeedleHipSearchEvidence> *evidence, const GroupTables *groups) const {
   const size_t n = fh.size();
   const size_t regions = include_endings_ ? 2 : 1;
-  const size_t np = pair_count(n);
+  if (groups && (evidence || groups->group_of.size() != n))
+    return Status::Make(NeedleError_InvalidArgument, "results_from_runs: grouped run lists carry no evidence, and the groups are one label per video");
+  const size_t np = groups ? (size_t)groups->pairs() : pair_count(n);
   v1 = std::min(v1, n);
   v0 = std::min(v0, v1);
   // A rank that owns videos [v0, v1) needs the pairs with at least one end in that block, nothing else.
@@ -740,11 +785,8 @@ Status Comparator::results_from_runs(const std::vector<const FrameHashesData *> 
   std::vector<uint8_t> relevant;
   if (partial) {
     relevant.assign(np, 0);
-    size_t i = 0, j = 1;
-    for (size_t p = 0; p < np; p++) {
-      relevant[p] = (i >= v0 && i < v1) || (j >= v0 && j < v1);
-      if (++j == n) j = ++i + 1;
-    }
+    PairWalk w(n, groups, 0);
+    for (size_t p = 0; p < np; p++, w.next()) relevant[p] = (w.i >= v0 && w.i < v1) || (w.j >= v0 && w.j < v1);
   }
   auto wanted = [&](uint32_t problem) { return problem < np * regions && (!partial || relevant[problem / regions]); };
   // Bucket the runs by problem (NeedleHipRun.problem = pair * regions + region) with a counting sort, then order
@@ -821,9 +863,9 @@ Status Comparator::results_from_runs(const std::vector<const FrameHashesData *> 
   pair_entries.count.resize(np);  // every element is written below
   parallel_chunks(np, 4096, host_workers((uint64_t)sorted.size() * 64), [&](size_t p0, size_t p1) {
     std::vector<HeapEntry> tmp;
-    size_t i, j;
-    pair_at(n, p0, &i, &j);
-    for (size_t p = p0; p < p1; p++) {
+    PairWalk w(n, groups, p0);
+    for (size_t p = p0; p < p1; p++, w.next()) {
+      const size_t i = w.i, j = w.j;
       uint64_t out = start[p * regions];
       pair_entries.first[p] = out;
       for (size_t r = 0; r < regions; r++) {
@@ -839,17 +881,16 @@ Status Comparator::results_from_runs(const std::vector<const FrameHashesData *> 
         for (const HeapEntry &e : tmp) pair_entries.entries[out++] = e;
       }
       pair_entries.count[p] = (uint32_t)(out - pair_entries.first[p]);
-      if (++j == n) j = ++i + 1;
     }
   });
   trace.lap("heap entries per pair", np);
-  Status s = best_matches(n, pair_entries, display, use_skip_files, write_skip_files, per_video, v0, v1, evidence);
+  Status s = best_matches(n, pair_entries, display, use_skip_files, write_skip_files, per_video, v0, v1, evidence, groups);
   trace.lap("best match per video", v1 - v0);
   return s;
 }
 
 Status Comparator::run(bool analyze, bool display, bool use_skip_files, bool write_skip_files, bool threading,
-                       std::vector<VideoResult> *per_video) const {
+                       std::vector<VideoResult> *per_video, const uint32_t *groups) const {
   // The videos' hashes of a search-only call live in objects kept between calls (up to kPoolBytes of them): allocating and
   // releasing 280 vectors of 46 KB each call was 0.3 of a 2 ms call.  One call at a time owns the pool; another one running
   // beside it finds it empty and allocates as before.
@@ -890,7 +931,7 @@ Status Comparator::run(bool analyze, bool display, bool use_skip_files, bool wri
   trace.lap(analyze ? "analyze" : "read .needle.dat files", videos_.size());
   std::vector<const FrameHashesData *> ptrs;
   for (const FrameHashesData &d : data) ptrs.push_back(&d);
-  Status s = run_with_frame_hashes(ptrs, display, use_skip_files, write_skip_files, threading, per_video);
+  Status s = run_with_frame_hashes(ptrs, display, use_skip_files, write_skip_files, threading, per_video, groups);
   trace.lap("search (the phases above) + release of its tables", ptrs.size());
   // The videos' hash vectors were allocated on the pool's threads; released one after the other by this thread they cost
   // 0.25 ms of a 2.1 ms call over 280 files (a lock and a consolidation per 46 KB chunk): release them where they came from.

@@ -9,6 +9,7 @@
 
 #include "../../include/needle_hip.h"
 #include "common.h"
+#include "pair_ids.h"
 
 namespace needle {
 
@@ -37,6 +38,12 @@ struct EpilogueJob : EpilogueOptions {
   // per arena row: hashes kept, offset of its (un-seeked) timestamps in `ts`, seek added to each of them
   const std::vector<uint32_t> *row_len = nullptr, *row_ts = nullptr;
   const std::vector<uint64_t> *row_seek = nullptr, *ts = nullptr;
+  // The grouped form (a library of seasons, pair_ids.h): with `groups` set only pairs inside a group exist, problem =
+  // grouped pair id * regions + region, there are groups->pairs() * regions buckets and every one of the n videos gets a
+  // result (v0, v1 and hash_duration are not read; hash_durations has one value per video).  The same number of launches
+  // as the form above, whatever the groups are.
+  const GroupTables *groups = nullptr;
+  const std::vector<uint64_t> *hash_durations = nullptr;
 };
 
 // The device form gives a pair's runs to ONE lane (insertion order + heap): a pair with more runs than this (silence against

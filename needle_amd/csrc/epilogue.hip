@@ -70,6 +70,11 @@ struct EpilogueWorkspace {
   bool large_checked = false;
   bool large_ok = false;  // of the resident row tables: every row under 65 536 hashes, timestamps strictly increasing
   DeviceBuffer<uint64_t> row_seek, ts;
+  // the grouped form's tables (pair_ids.h GroupView) and the videos' hash durations, and what they hold
+  DeviceBuffer<uint32_t> group_of, rank_of, group_size, group_first, members;
+  DeviceBuffer<uint64_t> group_base, hash_durations;
+  std::vector<uint32_t> h_group_of, h_rank_of, h_group_size, h_group_first, h_members;
+  std::vector<uint64_t> h_group_base, h_hash_durations;
   DeviceBuffer<DeviceEntry> entries;
   DeviceBuffer<Candidate> cand;
   DeviceBuffer<NeedleHipSearchResult> results;
@@ -134,7 +139,10 @@ Status gpu_epilogue_enqueue(const EpilogueJob &job, hipStream_t stream, NeedleHi
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());  // the per-device workspaces are shared, as everywhere else
   if (job.num_segments < 1 || job.num_segments > kMaxSegments)
     return Status::Make(NeedleError_InvalidArgument, "device epilogue: too many run segments");
-  const uint64_t np = (uint64_t)job.n * (job.n - 1) / 2;
+  const GroupTables *groups = job.groups;
+  if (groups && (!job.hash_durations || job.hash_durations->size() != job.n || groups->group_of.size() != job.n || groups->pairs() == 0))
+    return Status::Make(NeedleError_InvalidArgument, "device epilogue: grouped job without pairs, or tables of another size");
+  const uint64_t np = groups ? groups->pairs() : (uint64_t)job.n * (job.n - 1) / 2;
   const uint64_t buckets = np * job.regions;
   if (job.n < 2 || buckets >= 0xFFFFFFF0ull || job.max_runs >= 0xFFFFFFF0ull)
     return Status::Make(NeedleError_InvalidArgument, "device epilogue: library too large");
@@ -165,6 +173,19 @@ Status gpu_epilogue_enqueue(const EpilogueJob &job, hipStream_t stream, NeedleHi
       !(s = upload_if_changed(&ws->row_seek, &ws->h_row_seek, *job.row_seek, stream)).ok() ||
       !(s = upload_if_changed(&ws->ts, &ws->h_ts, *job.ts, stream)).ok())
     return s;
+  GroupView view{};
+  if (groups) {  // small, and the same from call to call while a library stands: re-uploaded when they change
+    if (!(s = upload_if_changed(&ws->group_of, &ws->h_group_of, groups->group_of, stream)).ok() ||
+        !(s = upload_if_changed(&ws->rank_of, &ws->h_rank_of, groups->rank_of, stream)).ok() ||
+        !(s = upload_if_changed(&ws->group_size, &ws->h_group_size, groups->size, stream)).ok() ||
+        !(s = upload_if_changed(&ws->group_first, &ws->h_group_first, groups->first, stream)).ok() ||
+        !(s = upload_if_changed(&ws->members, &ws->h_members, groups->members, stream)).ok() ||
+        !(s = upload_if_changed(&ws->group_base, &ws->h_group_base, groups->base, stream)).ok() ||
+        !(s = upload_if_changed(&ws->hash_durations, &ws->h_hash_durations, *job.hash_durations, stream)).ok())
+      return s;
+    view = GroupView{ws->group_of.ptr, ws->rank_of.ptr, ws->group_size.ptr, ws->group_first.ptr, ws->group_base.ptr, ws->members.ptr,
+                     (uint32_t)groups->size.size()};
+  }
   const size_t runs = std::max<uint64_t>(job.max_runs, 1);
   if (!(s = ws->scratch.reserve(buckets, runs)).ok() || !(s = ws->entries.reserve(runs)).ok() || !(s = ws->cand.reserve(2 * runs)).ok() ||
       !(s = ws->links.reserve(2 * runs)).ok() || !(s = ws->ctl.reserve(1)).ok() || !(s = ws->results.reserve(job.n)).ok())
@@ -182,17 +203,28 @@ Status gpu_epilogue_enqueue(const EpilogueJob &job, hipStream_t stream, NeedleHi
   pr.v0 = job.v0;
   pr.v1 = job.v1;
   pr.hash_duration = job.hash_duration;
+  if (groups) {
+    pr.v0 = 0;
+    pr.v1 = job.n;
+  }
   EpilogueControl *ctl = ws->ctl.ptr;
   NEEDLE_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(*ctl), stream));
   NEEDLE_HIP_TRY(hipMemsetAsync(ws->results.ptr, 0, (size_t)job.n * sizeof(NeedleHipSearchResult), stream));
   if (!(s = enqueue_bucket_sort("epilogue_buckets", segs, pr.buckets, runs, &ws->scratch, stream)).ok()) return s;
   {
     KernelTimer timer("epilogue_entries", stream);
-    if (!(s = enqueue_pair_entries<RowMajorPairs>(ws->device, pr, ws->scratch, ws->row_len.ptr, ws->row_ts.ptr, ws->row_seek.ptr, ws->ts.ptr,
-                                                  ws->entries.ptr, ctl, stream)).ok())
-      return s;
+    s = groups ? enqueue_pair_entries<GroupedPairs>(ws->device, pr, ws->scratch, ws->row_len.ptr, ws->row_ts.ptr, ws->row_seek.ptr, ws->ts.ptr,
+                                                    ws->entries.ptr, ctl, stream, view)
+               : enqueue_pair_entries<RowMajorPairs>(ws->device, pr, ws->scratch, ws->row_len.ptr, ws->row_ts.ptr, ws->row_seek.ptr, ws->ts.ptr,
+                                                     ws->entries.ptr, ctl, stream);
+    if (!s.ok()) return s;
   }
-  if (pr.v1 > pr.v0) {
+  if (groups) {
+    KernelTimer timer("epilogue_best_match", stream);
+    hipLaunchKernelGGL((best_match_kernel<GroupedVideos, GroupView, const uint64_t *>), dim3(job.n), dim3(256), 0, stream, pr, ws->scratch.start.ptr,
+                       ws->scratch.valid.ptr, ws->entries.ptr, ws->cand.ptr, &ctl->cand_cursor, ws->links.ptr, ws->results.ptr, &ctl->failed, view,
+                       (const uint64_t *)ws->hash_durations.ptr);
+  } else if (pr.v1 > pr.v0) {
     KernelTimer timer("epilogue_best_match", stream);
     hipLaunchKernelGGL(best_match_kernel<RowMajorVideos>, dim3(pr.v1 - pr.v0), dim3(256), 0, stream, pr, ws->scratch.start.ptr, ws->scratch.valid.ptr,
                        ws->entries.ptr, ws->cand.ptr, &ctl->cand_cursor, ws->links.ptr, ws->results.ptr, &ctl->failed);

@@ -13,6 +13,7 @@
 #include "../../include/needle_hip.h"
 #include "epilogue.h"
 #include "hipctx.h"
+#include "pair_ids.h"
 
 namespace needle {
 
@@ -192,6 +193,15 @@ struct ListedPairs {  // an index edit: problem / regions = a listed pair, table
   const uint32_t *table;
   __device__ ListedPairs(const EpilogueParams &, const uint32_t *pair_ids) : table(pair_ids) {}
   __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const { column_pair_at(table[p], i, j); }
+};
+struct GroupedPairs {  // a library of seasons: problem / regions = a grouped pair id (pair_ids.h), the tables in device memory
+  GroupView groups;
+  __device__ GroupedPairs(const EpilogueParams &, const GroupView &g) : groups(g) {}
+  // once per bucket that has runs: a bisection over the groups' bases, then over the group's rows.  (The buckets are sized
+  // by the same tables, so every bucket is a pair; were one not, it reads video 0's rows, inside the tables.)
+  __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const {
+    if (!grouped_pair_at(groups, p, i, j)) *i = *j = 0;
+  }
 };
 
 // #[derive(Ord)] over (score, src_start, src_end, dst_start, dst_end, src_match_hash, dst_match_hash, ...): the rest of
@@ -428,6 +438,8 @@ struct RowMajorVideos {  // the library job: videos [v0, v1), buckets in the i-m
     return q < v ? row_start(n, q) + (v - q - 1) : row_start(n, v) + (q - v);
   }
   __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
+  __device__ uint32_t slots(const EpilogueParams &pr, uint32_t) const { return pr.n - 1; }
+  __device__ bool is_source(uint32_t q, uint32_t v) const { return q >= v; }
   __device__ uint64_t video_hash_duration(uint32_t) const { return hash_duration; }
   __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}  // (EvidenceVideos')
 };
@@ -440,6 +452,8 @@ struct IndexVideos {  // an index append: the videos listed (*count of them), bu
   __device__ uint32_t video(uint32_t block) const { return list[block]; }
   __device__ uint64_t pair(uint32_t q, uint32_t v) const { return q < v ? column_start(v) + q : column_start(q + 1) + v; }
   __device__ uint32_t out(uint32_t block, uint32_t) const { return block; }
+  __device__ uint32_t slots(const EpilogueParams &pr, uint32_t) const { return pr.n - 1; }
+  __device__ bool is_source(uint32_t q, uint32_t v) const { return q >= v; }
   __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
   __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}
 };
@@ -460,6 +474,8 @@ struct EvidenceVideos {  // the index's evidence: EVERY video of the store, buck
   __device__ uint32_t video(uint32_t block) const { return block; }
   __device__ uint64_t pair(uint32_t q, uint32_t v) const { return q < v ? column_start(v) + q : column_start(q + 1) + v; }
   __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
+  __device__ uint32_t slots(const EpilogueParams &pr, uint32_t) const { return pr.n - 1; }
+  __device__ bool is_source(uint32_t q, uint32_t v) const { return q >= v; }
   __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
   // thread 0, behind the selection: where the video's c candidates are, and each region's winner with its links
   __device__ void winners_out(uint32_t v, unsigned long long pool_base, uint32_t c, const BestKey &opening, const BestKey &ending,
@@ -478,6 +494,30 @@ struct EvidenceVideos {  // the index's evidence: EVERY video of the store, buck
     }
     winners[v] = w;
   }
+};
+
+// A library of seasons: EVERY video is a workgroup, its pairs are its group's -- size - 1 slots, none for a video alone in its
+// group, which writes "no result" -- buckets in the grouped pair order (pair_ids.h), results[v].  The workgroup's video is
+// its block, so what the slot passes need of the tables (rank, group size, base) is read once, at addresses every lane
+// shares: scalar loads into scalar registers, and a slot's pair id is arithmetic on them -- the member list is not read here.
+struct GroupedVideos {
+  uint64_t base;
+  uint32_t rank, size;
+  const uint64_t *hash_durations;
+  __device__ GroupedVideos(const EpilogueParams &, const GroupView &g, const uint64_t *hd) : hash_durations(hd) {
+    const uint32_t group = g.group_of[blockIdx.x];
+    rank = g.rank_of[blockIdx.x];
+    size = g.size[group];
+    base = g.base[group];
+  }
+  __device__ bool live(uint32_t) const { return true; }
+  __device__ uint32_t video(uint32_t block) const { return block; }
+  __device__ uint64_t pair(uint32_t q, uint32_t) const { return grouped_rank_slot_pair(base, rank, size, q); }
+  __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
+  __device__ uint32_t slots(const EpilogueParams &, uint32_t) const { return size - 1; }
+  __device__ bool is_source(uint32_t q, uint32_t) const { return q >= rank; }  // slot q is (lower member, v) below v's rank
+  __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
+  __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}
 };
 
 // One workgroup per wanted video.
@@ -502,7 +542,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
   const Videos videos(pr, extra...);
   if (!videos.live(blockIdx.x)) return;
   const uint32_t v = videos.video(blockIdx.x), t = threadIdx.x;
-  const uint32_t slots = pr.n - 1;  // the video's pairs in lexicographic order: (q, v) for q < v, then (v, q + 1)
+  const uint32_t slots = videos.slots(pr, v);  // the video's pairs in lexicographic order: (q, v) for q < v, then (v, q + 1)
   auto bucket_of = [&](uint32_t q) -> uint64_t { return videos.pair(q, v) * pr.regions; };
   // pass 1: candidates per pair slot -> total
   if (t == 0) carry = 0;
@@ -568,12 +608,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void b
     constexpr uint32_t kOwnCopy = 16;
     slot_cnt[t] = cnt;
     slot_at[t] = at;
-    if (cnt && cnt <= kOwnCopy) copy_entries(b, q >= v, at, 0u, 1u);
+    if (cnt && cnt <= kOwnCopy) copy_entries(b, videos.is_source(q, v), at, 0u, 1u);
     __syncthreads();
     for (uint32_t qq = 0; qq < 256; qq++) {
       if (slot_cnt[qq] <= kOwnCopy) continue;  // (uniform)
       const uint32_t q2 = base + qq;
-      copy_entries(bucket_of(q2), q2 >= v, slot_at[qq], t, 256u);
+      copy_entries(bucket_of(q2), videos.is_source(q2, v), slot_at[qq], t, 256u);
     }
     __syncthreads();
     if (t == 255) carry += scan[255];

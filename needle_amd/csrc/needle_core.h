@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "common.h"
+#include "pair_ids.h"
 
 namespace needle {
 
@@ -126,12 +127,15 @@ class Comparator {
 
   // comparator.rs:524.  per_video gets one slot per input video; results (optional) gets the
   // reference's compacted Vec<SearchResult>.
+  // groups (optional): a label per video; equal labels are one season and only pairs inside a season are searched
+  // (pair_ids.h).  A video's result, what is printed for it and its skip file are what the call over its own season's
+  // sub-list gives; the videos are walked in list order.  nullptr: every video against every other, the reference's call.
   Status run_with_frame_hashes(const std::vector<const FrameHashesData *> &frame_hashes, bool display,
                                bool use_skip_files, bool write_skip_files, bool threading,
-                               std::vector<VideoResult> *per_video) const;
+                               std::vector<VideoResult> *per_video, const uint32_t *groups = nullptr) const;
   // comparator.rs:637
   Status run(bool analyze, bool display, bool use_skip_files, bool write_skip_files, bool threading,
-             std::vector<VideoResult> *per_video) const;
+             std::vector<VideoResult> *per_video, const uint32_t *groups = nullptr) const;
 
   // ---- pieces shared with the multi-GPU Library path ----
   // Smallest run length L for which some window ts[i] - ts[i-L] reaches min_duration (0 = never).
@@ -154,7 +158,9 @@ class Comparator {
   Status results_from_runs(const std::vector<const FrameHashesData *> &frame_hashes, const NeedleHipRun *runs,
                            size_t num_runs, bool display, bool use_skip_files, bool write_skip_files,
                            std::vector<VideoResult> *per_video, size_t v0 = 0, size_t v1 = ~(size_t)0,
-                           std::vector<NeedleHipSearchEvidence> *evidence = nullptr) const;
+                           std::vector<NeedleHipSearchEvidence> *evidence = nullptr, const GroupTables *groups = nullptr) const;
+  // (groups: the run list is a grouped call's -- problem = grouped pair id * regions + region -- and a video owns its
+  // season's pairs only; evidence is not written for such a list)
   // Heap entries of every pair, pairs in lexicographic order, in one allocation: those of pair p are
   // entries[first[p] .. first[p] + count[p]) (a library has ~n^2 / 2 pairs: no vector per pair).
   struct PairEntries {
@@ -165,7 +171,8 @@ class Comparator {
   // :583-626 — per video best match from the per-pair entries.
   Status best_matches(size_t num_videos, const PairEntries &pair_entries, bool display, bool use_skip_files,
                       bool write_skip_files, std::vector<VideoResult> *per_video, size_t v0 = 0,
-                      size_t v1 = ~(size_t)0, std::vector<NeedleHipSearchEvidence> *evidence = nullptr) const;
+                      size_t v1 = ~(size_t)0, std::vector<NeedleHipSearchEvidence> *evidence = nullptr,
+                      const GroupTables *groups = nullptr) const;
   // :593-626, the walk with side effects over results that are already there (any[v]: video v has a candidate at all)
   Status walk_results(size_t num_videos, const std::vector<uint8_t> &any, const std::vector<Status> &status, bool display,
                       bool use_skip_files, bool write_skip_files, std::vector<VideoResult> *per_video, size_t v0,

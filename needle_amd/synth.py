@@ -152,9 +152,10 @@ class DeviceLibrary:
     (csrc/synth_hip.hip); a checker reads the PCM it wants back with episode()."""
 
     def __init__(self, n: int, samples: int, intro_s: float, first_episode: int = 0, seed_base: int = EPISODE_SEED,
-                 hostile: bool = False):
+                 hostile: bool = False, intro_seed: int = INTRO_SEED):
         """hostile: the round-6 corpus of csrc/synth_hip.hip -- broadband speech-like bodies, noise 20 dB under the programme,
-        stretches of digital silence and of one sustained chord (hostile_segments) -- instead of note sequences."""
+        stretches of digital silence and of one sustained chord (hostile_segments) -- instead of note sequences.
+        intro_seed: which intro the episodes share (a library of several shows: one per show)."""
         from . import capi
         self.n, self.samples = n, samples
         self.stride = (samples + 7) & ~7                       # every episode 16-byte aligned
@@ -173,10 +174,10 @@ class DeviceLibrary:
             seg = capi.DeviceBuffer(16 * n)
             capi.check(capi.lib().needle_hip_memcpy_h2d(seg.ptr, self.segments.ctypes.data, self.segments.nbytes))
             rc = _hip_lib().needle_synth_hip_library_hostile(self._buf.ptr, self.stride, n, first_episode, samples, off.ptr,
-                                                             self.intro_len, seg.ptr, seed_base, INTRO_SEED, capi.stream_ptr())
+                                                             self.intro_len, seg.ptr, seed_base, intro_seed, capi.stream_ptr())
         else:
             rc = _hip_lib().needle_synth_hip_library(self._buf.ptr, self.stride, n, first_episode, samples, off.ptr,
-                                                     self.intro_len, seed_base, INTRO_SEED, capi.stream_ptr())
+                                                     self.intro_len, seed_base, intro_seed, capi.stream_ptr())
         if rc != 0:
             raise RuntimeError(f"needle_synth_hip_library: HIP error {rc}")
         capi.synchronize()

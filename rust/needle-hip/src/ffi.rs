@@ -348,6 +348,42 @@ extern "C" {
         results: *mut NeedleHipSearchResult,
         evidence: *mut NeedleHipSearchEvidence,
     ) -> NeedleError;
+    // ---- groups of videos (include/needle_hip.h "A library of many shows") ----
+    pub fn needle_hip_group_pairs(
+        groups: *const u32,
+        num_videos: usize,
+        pair_videos: *mut u32,
+        capacity: usize,
+        num_pairs: *mut u64,
+    ) -> NeedleError;
+    pub fn needle_hip_comparator_run_with_frame_hashes_grouped(
+        comparator: *const NeedleAudioComparator,
+        frame_hashes: *const *const FrameHashes,
+        num_videos: usize,
+        groups: *const u32,
+        display: bool,
+        use_skip_files: bool,
+        write_skip_files: bool,
+        results: *mut NeedleHipSearchResult,
+    ) -> NeedleError;
+    pub fn needle_hip_comparator_results_from_runs_grouped(
+        comparator: *const NeedleAudioComparator,
+        frame_hashes: *const *const FrameHashes,
+        num_videos: usize,
+        groups: *const u32,
+        runs: *const NeedleHipRun,
+        num_runs: usize,
+        results: *mut NeedleHipSearchResult,
+    ) -> NeedleError;
+    pub fn needle_hip_comparator_run_grouped(
+        comparator: *const NeedleAudioComparator,
+        groups: *const u32,
+        num_groups_entries: usize,
+        analyze: bool,
+        display: bool,
+        use_skip_files: bool,
+        write_skip_files: bool,
+    ) -> NeedleError;
     pub fn needle_hip_index_pairs_searched(index: *const NeedleHipIndex, total: *mut u64, last: *mut u64) -> NeedleError;
     pub fn needle_hip_index_remove(index: *mut NeedleHipIndex, positions: *const usize, k: usize) -> NeedleError;
     pub fn needle_hip_index_replace(

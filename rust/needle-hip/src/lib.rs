@@ -496,6 +496,95 @@ impl<P: AsRef<Path>> Comparator<P> {
             .collect())
     }
 
+    /// `run_with_frame_hashes` over groups of videos (`needle_hip_comparator_run_with_frame_hashes_grouped`): `groups` has a
+    /// label per video, and only videos of equal label are compared.  One entry per video, `None` where it matched nothing
+    /// (a video alone in its group always).
+    pub fn run_with_frame_hashes_grouped(
+        &self,
+        frame_hashes: &[FrameHashes],
+        groups: &[u32],
+        display: bool,
+        use_skip_files: bool,
+        write_skip_files: bool,
+    ) -> Result<Vec<Option<SearchResult>>> {
+        if groups.len() != frame_hashes.len() {
+            return Err(Error {
+                code: ffi::NeedleError::InvalidArgument,
+                message: "grouped search: one group label per video".into(),
+            });
+        }
+        let handle = self.handle()?;
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        let mut results = vec![ffi::NeedleHipSearchResult::default(); raw.len()];
+        let status = unsafe {
+            check(ffi::needle_hip_comparator_run_with_frame_hashes_grouped(
+                handle,
+                raw.as_ptr(),
+                raw.len(),
+                groups.as_ptr(),
+                display,
+                use_skip_files,
+                write_skip_files,
+                results.as_mut_ptr(),
+            ))
+        };
+        unsafe { ffi::needle_audio_comparator_free(handle) };
+        status?;
+        Ok(results.into_iter().map(optional_result).collect())
+    }
+
+    /// The host epilogue alone over a grouped run list (`needle_hip_comparator_results_from_runs_grouped`; `problem` =
+    /// grouped pair id * regions + region, see [`group_pairs`]).  No device work.
+    pub fn results_from_runs_grouped(
+        &self,
+        frame_hashes: &[FrameHashes],
+        groups: &[u32],
+        runs: &[ffi::NeedleHipRun],
+    ) -> Result<Vec<Option<SearchResult>>> {
+        if groups.len() != frame_hashes.len() {
+            return Err(Error {
+                code: ffi::NeedleError::InvalidArgument,
+                message: "grouped search: one group label per video".into(),
+            });
+        }
+        let handle = self.handle()?;
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        let mut results = vec![ffi::NeedleHipSearchResult::default(); raw.len()];
+        let status = unsafe {
+            check(ffi::needle_hip_comparator_results_from_runs_grouped(
+                handle,
+                raw.as_ptr(),
+                raw.len(),
+                groups.as_ptr(),
+                runs.as_ptr(),
+                runs.len(),
+                results.as_mut_ptr(),
+            ))
+        };
+        unsafe { ffi::needle_audio_comparator_free(handle) };
+        status?;
+        Ok(results.into_iter().map(optional_result).collect())
+    }
+
+    /// The file-based `run` over groups of videos (`needle_hip_comparator_run_grouped`): `groups` is parallel to the
+    /// comparator's paths.
+    pub fn run_grouped(&self, groups: &[u32], analyze: bool, display: bool, use_skip_files: bool, write_skip_files: bool) -> Result<()> {
+        let handle = self.handle()?;
+        let status = unsafe {
+            check(ffi::needle_hip_comparator_run_grouped(
+                handle,
+                groups.as_ptr(),
+                groups.len(),
+                analyze,
+                display,
+                use_skip_files,
+                write_skip_files,
+            ))
+        };
+        unsafe { ffi::needle_audio_comparator_free(handle) };
+        status
+    }
+
     /// comparator.rs:524-629.  One entry per video that matched something, in video order (`:608-617`).
     pub fn run_with_frame_hashes(
         &self,
@@ -1140,6 +1229,25 @@ impl Drop for Index {
     fn drop(&mut self) {
         unsafe { ffi::needle_hip_index_free(self.raw) };
     }
+}
+
+fn optional_result(r: ffi::NeedleHipSearchResult) -> Option<SearchResult> {
+    let span = |a: u64, b: u64| (Duration::from_nanos(a), Duration::from_nanos(b));
+    r.has_result.then(|| SearchResult {
+        opening: r.has_opening.then(|| span(r.opening_start_ns, r.opening_end_ns)),
+        ending: r.has_ending.then(|| span(r.ending_start_ns, r.ending_end_ns)),
+    })
+}
+
+/// The pairs a grouped search compares, in the order of their ids (`needle_hip_group_pairs`): `groups` has a label per
+/// video, only videos of equal label form a pair, and `NeedleHipRun.problem / regions` of a grouped run list indexes
+/// this list.
+pub fn group_pairs(groups: &[u32]) -> Result<Vec<(u32, u32)>> {
+    let mut count = 0u64;
+    unsafe { check(ffi::needle_hip_group_pairs(groups.as_ptr(), groups.len(), std::ptr::null_mut(), 0, &mut count))? };
+    let mut flat = vec![0u32; 2 * count as usize];
+    unsafe { check(ffi::needle_hip_group_pairs(groups.as_ptr(), groups.len(), flat.as_mut_ptr(), count as usize, &mut count))? };
+    Ok(flat.chunks_exact(2).map(|p| (p[0], p[1])).collect())
 }
 
 /// Number of HIP devices the library sees (0 on a host without a GPU: every compute call then fails loudly).
