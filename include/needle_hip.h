@@ -457,6 +457,27 @@ enum NeedleError needle_hip_index_replace(NeedleHipIndex *index, const size_t *p
  * device arena, sizes[3] timestamps in the device table.  After a remove or replace sizes[0] == sizes[1]. */
 enum NeedleError needle_hip_index_store_sizes(const NeedleHipIndex *index, uint64_t sizes[4]);
 
+/* ---- A grouped index: a library of many shows that grows in place ---------------------------------------------
+ * The incremental index over groups of videos (above, "A library of many shows").  A grouped index is made as such; every
+ * video is added with a label (any values: they are only compared, equal labels are one season) and only pairs inside a
+ * season are searched.  Results equal needle_hip_comparator_run_with_frame_hashes over each season's own sub-list of the
+ * current list, bit for bit -- what needle_hip_comparator_run_with_frame_hashes_grouped gives over the current list -- and a
+ * video alone in its season has no result.  An append searches only the arriving videos' pairs with the members of their
+ * seasons before them in the list (pairs_searched and pairs_scanned count those), whatever the size of the library; every
+ * other season's results and stored entries stay where they are.
+ * needle_hip_index_results, _evidence (`partner` is a current position of the same season), _remove, _replace (the new video
+ * keeps the label of the position it replaces; only its season's pairs are scanned), _pairs_searched, _pairs_scanned,
+ * _store_sizes and _len work on a grouped index as on a plain one.  "no ending hash data present" concerns only a video that
+ * has a pair.  Refused with NeedleError_InvalidArgument, before any device work: needle_hip_index_add on a grouped index,
+ * needle_hip_index_add_grouped on a plain one, and needle_hip_index_crossmatcher_new, _matcher_new, _add_matched and
+ * _add_streamed on a grouped one. */
+enum NeedleError needle_hip_index_new_grouped(const struct NeedleAudioComparator *comparator, NeedleHipIndex **output);
+/* Appends k >= 1 videos, groups[i] the label of frame_hashes[i].  Otherwise as needle_hip_index_add. */
+enum NeedleError needle_hip_index_add_grouped(NeedleHipIndex *index, const FrameHashes *const *frame_hashes, const uint32_t *groups,
+                                              size_t k);
+/* The current list's labels, one per video; n >= needle_hip_index_len(index).  A plain index: NeedleError_InvalidArgument. */
+enum NeedleError needle_hip_index_groups(const NeedleHipIndex *index, uint32_t *labels, size_t n);
+
 /* ---- Library: an HBM-resident analyze+search job, shardable across GPUs ----------------------------
  * One object per process/GPU describing ALL videos of a job.  PCM of the videos this rank owns is
  * uploaded once and stays in HBM; hashes live in a padded device arena [video * rows_per_video][stride] so a

@@ -135,6 +135,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_matcher_finish", "needle_hip_matcher_reset", "needle_hip_matcher_ready", "needle_hip_matcher_runs",
     "needle_hip_matcher_open", "needle_hip_matcher_stats", "needle_hip_matcher_new_regions",
     "needle_hip_index_matcher_new", "needle_hip_index_add_streamed",
+    "needle_hip_index_new_grouped", "needle_hip_index_add_grouped", "needle_hip_index_groups",
     "needle_hip_crossmatcher_new", "needle_hip_crossmatcher_free", "needle_hip_crossmatcher_feed",
     "needle_hip_crossmatcher_feed_from_feeder", "needle_hip_crossmatcher_finish", "needle_hip_crossmatcher_ready",
     "needle_hip_crossmatcher_lane", "needle_hip_crossmatcher_runs", "needle_hip_crossmatcher_stats",
@@ -394,6 +395,9 @@ def lib():
     L.needle_hip_index_add_matched.argtypes = [vp, vp, C.POINTER(vp), sz]
     L.needle_hip_index_matcher_new.argtypes = [vp, sz, C.POINTER(vp)]
     L.needle_hip_index_add_streamed.argtypes = [vp, vp, vp, C.POINTER(vp), sz]
+    L.needle_hip_index_new_grouped.argtypes = [vp, C.POINTER(vp)]
+    L.needle_hip_index_add_grouped.argtypes = [vp, C.POINTER(vp), C.POINTER(u32), sz]
+    L.needle_hip_index_groups.argtypes = [vp, C.POINTER(u32), sz]
     L.needle_hip_feeder_new.argtypes = [sz, C.c_int, C.c_int, C.c_int, u32, C.POINTER(vp)]
     L.needle_hip_feeder_free.argtypes = [vp]
     L.needle_hip_feeder_free.restype = None
@@ -959,21 +963,41 @@ class Index:
     """An incremental search index (needle_hip_index_*): results() equals Comparator.run_with_frame_hashes over the
     index's current list of videos; add() searches only the pairs it adds, remove() none, replace() those of the videos
     replaced.  The comparator's parameters are copied at
-    creation.  One GPU: the device current at creation."""
+    creation.  One GPU: the device current at creation.
+    grouped=True: a library of many seasons (needle_hip_index_new_grouped) -- every video is added with a label, equal
+    labels are one season, only pairs inside a season are searched, and results() equals
+    Comparator.run_with_frame_hashes(groups=...) over the current list."""
 
-    def __init__(self, comparator: Comparator):
+    def __init__(self, comparator: Comparator, grouped: bool = False):
         self._h = None
         out = C.c_void_p()
-        check(lib().needle_hip_index_new(comparator.handle(), C.byref(out)))
+        new = lib().needle_hip_index_new_grouped if grouped else lib().needle_hip_index_new
+        check(new(comparator.handle(), C.byref(out)))
         self._h = out
+        self.grouped = bool(grouped)
         self.threshold = comparator._cfg["threshold"]   # copied, as the index copies it
         self.include_endings = bool(comparator._cfg["include_endings"])
 
-    def add(self, frame_hashes: Sequence[FrameHashes]) -> None:
-        """Appends the videos; on failure (NeedleError) the index is as it was before the call."""
+    def add(self, frame_hashes: Sequence[FrameHashes], groups: Optional[Sequence[int]] = None) -> None:
+        """Appends the videos; on failure (NeedleError) the index is as it was before the call.  groups: a label per
+        video (0 .. 2^32 - 1, only compared), for a grouped index -- which refuses an add without them, as a plain index
+        refuses one with them."""
         k = len(frame_hashes)
         ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
-        check(lib().needle_hip_index_add(self._h, ptrs, k))
+        if groups is None:
+            check(lib().needle_hip_index_add(self._h, ptrs, k))
+            return
+        if len(groups) != k:
+            raise ValueError("add: one group label per video")
+        labels = (C.c_uint32 * max(k, 1))(*[int(g) for g in groups])
+        check(lib().needle_hip_index_add_grouped(self._h, ptrs, labels, k))
+
+    def groups(self) -> List[int]:
+        """The current list's labels, one per video (a grouped index; a plain one: NeedleError)."""
+        n = len(self)
+        labels = (C.c_uint32 * max(n, 1))()
+        check(lib().needle_hip_index_groups(self._h, labels, n))
+        return list(labels[:n])
 
     def remove(self, positions: Sequence[int]) -> None:
         """Removes the videos at these distinct positions; the others keep their order.  On failure (NeedleError) the

@@ -46,7 +46,7 @@ struct NeedleHipCrossMatcher {
   std::unique_ptr<CrossMatcher> inner;
 };
 struct NeedleHipIndex {
-  explicit NeedleHipIndex(const Comparator &c) : inner(c) {}
+  explicit NeedleHipIndex(const Comparator &c, bool grouped = false) : inner(c, grouped) {}
   Index inner;
 };
 
@@ -1625,6 +1625,47 @@ enum NeedleError needle_hip_index_store_sizes(const NeedleHipIndex *index, uint6
     Status s = index->inner.store_sizes(sizes);
     return s.ok() ? NeedleError_Ok : report(s);
   });
+}
+
+// ---- a grouped index (needle_hip.h "A grouped index") ----
+enum NeedleError needle_hip_index_new_grouped(const struct NeedleAudioComparator *comparator, NeedleHipIndex **output) {
+  if (!comparator || !output) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    NeedleHipIndex *index = new NeedleHipIndex(comparator->inner, true);
+    Status s = index->inner.init();
+    if (!s.ok()) {
+      delete index;
+      return report(s);
+    }
+    *output = index;
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_index_add_grouped(NeedleHipIndex *index, const FrameHashes *const *frame_hashes, const uint32_t *groups,
+                                              size_t k) {
+  if (!index) return NeedleError_NullArgument;
+  if (k == 0) return report(Status::Make(NeedleError_InvalidArgument, "index add: no videos"));
+  if (!frame_hashes || !groups) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    Status s = index->inner.add_grouped(fh, groups);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_index_groups(const NeedleHipIndex *index, uint32_t *labels, size_t n) {
+  if (!index) return NeedleError_NullArgument;
+  if (!index->inner.grouped()) return report(Status::Make(NeedleError_InvalidArgument, "index groups: not a grouped index"));
+  const std::vector<uint32_t> &have = index->inner.labels();
+  if (n < have.size()) return report(Status::Make(NeedleError_InvalidArgument, "index groups: buffer shorter than the index"));
+  if (!labels && !have.empty()) return NeedleError_NullArgument;
+  if (!have.empty()) std::memcpy(labels, have.data(), have.size() * sizeof(uint32_t));
+  return NeedleError_Ok;
 }
 
 }  // extern "C"

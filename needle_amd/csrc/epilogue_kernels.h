@@ -203,6 +203,25 @@ struct GroupedPairs {  // a library of seasons: problem / regions = a grouped pa
     if (!grouped_pair_at(groups, p, i, j)) *i = *j = 0;
   }
 };
+// The grouped index (pair_ids.h IndexGroupView: append-stable ids, the tables in device memory).  An append: problem / regions
+// = id - first, first = the append's first new id.  Once per bucket that has runs: a bisection over the videos' vbase.  (The
+// buckets are sized by the same tables, so every bucket is a pair; were one not, it reads video 0's rows, inside the tables.)
+struct IndexGroupAppendPairs {
+  IndexGroupView groups;
+  uint64_t first;
+  __device__ IndexGroupAppendPairs(const EpilogueParams &, const IndexGroupView &g, uint64_t first_pair) : groups(g), first(first_pair) {}
+  __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const {
+    if (!index_group_pair_at(groups, first + p, i, j)) *i = *j = 0;
+  }
+};
+struct IndexGroupListedPairs {  // an edit of the grouped index: table[listed] = the pair's id in the rebuilt store
+  IndexGroupView groups;
+  const uint32_t *table;
+  __device__ IndexGroupListedPairs(const EpilogueParams &, const IndexGroupView &g, const uint32_t *pair_ids) : groups(g), table(pair_ids) {}
+  __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const {
+    if (!index_group_pair_at(groups, table[p], i, j)) *i = *j = 0;
+  }
+};
 
 // #[derive(Ord)] over (score, src_start, src_end, dst_start, dst_end, src_match_hash, dst_match_hash, ...): the rest of
 // the fields are equal for all entries of one bucket.  true: a > b.
@@ -440,6 +459,7 @@ struct RowMajorVideos {  // the library job: videos [v0, v1), buckets in the i-m
   __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
   __device__ uint32_t slots(const EpilogueParams &pr, uint32_t) const { return pr.n - 1; }
   __device__ bool is_source(uint32_t q, uint32_t v) const { return q >= v; }
+  __device__ uint32_t partner(uint32_t q, uint32_t v) const { return q < v ? q : q + 1; }
   __device__ uint64_t video_hash_duration(uint32_t) const { return hash_duration; }
   __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}  // (EvidenceVideos')
 };
@@ -454,6 +474,7 @@ struct IndexVideos {  // an index append: the videos listed (*count of them), bu
   __device__ uint32_t out(uint32_t block, uint32_t) const { return block; }
   __device__ uint32_t slots(const EpilogueParams &pr, uint32_t) const { return pr.n - 1; }
   __device__ bool is_source(uint32_t q, uint32_t v) const { return q >= v; }
+  __device__ uint32_t partner(uint32_t q, uint32_t v) const { return q < v ? q : q + 1; }
   __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
   __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}
 };
@@ -476,6 +497,7 @@ struct EvidenceVideos {  // the index's evidence: EVERY video of the store, buck
   __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
   __device__ uint32_t slots(const EpilogueParams &pr, uint32_t) const { return pr.n - 1; }
   __device__ bool is_source(uint32_t q, uint32_t v) const { return q >= v; }
+  __device__ uint32_t partner(uint32_t q, uint32_t v) const { return q < v ? q : q + 1; }
   __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
   // thread 0, behind the selection: where the video's c candidates are, and each region's winner with its links
   __device__ void winners_out(uint32_t v, unsigned long long pool_base, uint32_t c, const BestKey &opening, const BestKey &ending,
@@ -518,6 +540,88 @@ struct GroupedVideos {
   __device__ bool is_source(uint32_t q, uint32_t) const { return q >= rank; }  // slot q is (lower member, v) below v's rank
   __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
   __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}
+};
+
+// The grouped index: what a workgroup's video needs of the tables (pair_ids.h IndexGroupView) -- rank, group size, its own vbase,
+// where its group's members start -- read once, at addresses every lane shares.  Slot q below the rank is (q-th member, v), in
+// v's own column: arithmetic.  A slot at or above it is (v, member q + 1), in that member's column: one read of the member
+// list and one of that member's vbase.  A video alone in its group has no slot and writes "no result".
+struct IndexGroupSlots {
+  const uint32_t *members;  // the video's group's
+  const uint64_t *vbase;
+  uint64_t own;             // vbase[v]
+  uint32_t rank, size;
+  __device__ void load(const IndexGroupView &g, uint32_t v) {
+    const uint32_t group = g.group_of[v];
+    rank = g.rank_of[v];
+    size = g.size[group];
+    members = g.members + g.first[group];
+    vbase = g.vbase;
+    own = g.vbase[v];
+  }
+  __device__ void none() {
+    members = nullptr;
+    vbase = nullptr;
+    own = 0;
+    rank = 0;
+    size = 1;
+  }
+  __device__ uint64_t pair(uint32_t q) const { return q < rank ? own + q : vbase[members[q + 1]] + rank; }
+  __device__ uint32_t partner(uint32_t q) const { return members[q < rank ? q : q + 1]; }
+};
+struct IndexGroupVideos {  // an append or an edit: the videos listed (*count of them), results[block] -- IndexVideos' grouped counterpart
+  IndexGroupSlots slot;
+  const uint32_t *list, *count;
+  const uint64_t *hash_durations;
+  __device__ IndexGroupVideos(const EpilogueParams &, const IndexGroupView &g, const uint32_t *l, const uint32_t *c, const uint64_t *hd)
+      : list(l), count(c), hash_durations(hd) {
+    if (blockIdx.x < *c) slot.load(g, l[blockIdx.x]);  // (a workgroup beyond the list returns at once: nothing of the tables is read)
+    else slot.none();
+  }
+  __device__ bool live(uint32_t block) const { return block < *count; }
+  __device__ uint32_t video(uint32_t block) const { return list[block]; }
+  __device__ uint64_t pair(uint32_t q, uint32_t) const { return slot.pair(q); }
+  __device__ uint32_t out(uint32_t block, uint32_t) const { return block; }
+  __device__ uint32_t slots(const EpilogueParams &, uint32_t) const { return slot.size - 1; }
+  __device__ bool is_source(uint32_t q, uint32_t) const { return q >= slot.rank; }
+  __device__ uint32_t partner(uint32_t q, uint32_t) const { return slot.partner(q); }
+  __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
+  __device__ void winners_out(uint32_t, unsigned long long, uint32_t, const BestKey &, const BestKey &, bool, const uint32_t *) const {}
+};
+struct IndexGroupEvidenceVideos {  // the grouped index's evidence: EVERY video, its group's slots, results[v], the winners written out
+  IndexGroupSlots slot;
+  const uint64_t *hash_durations;
+  DeviceWinners *winners;  // zeroed by the host: a video without candidates writes nothing
+  __device__ IndexGroupEvidenceVideos(const EpilogueParams &, const IndexGroupView &g, const uint64_t *hd, DeviceWinners *w)
+      : hash_durations(hd), winners(w) {
+    if (blockIdx.x < g.videos) slot.load(g, blockIdx.x);
+    else slot.none();
+  }
+  __device__ bool live(uint32_t) const { return true; }
+  __device__ uint32_t video(uint32_t block) const { return block; }
+  __device__ uint64_t pair(uint32_t q, uint32_t) const { return slot.pair(q); }
+  __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
+  __device__ uint32_t slots(const EpilogueParams &, uint32_t) const { return slot.size - 1; }
+  __device__ bool is_source(uint32_t q, uint32_t) const { return q >= slot.rank; }
+  __device__ uint32_t partner(uint32_t q, uint32_t) const { return slot.partner(q); }
+  __device__ uint64_t video_hash_duration(uint32_t v) const { return hash_durations[v]; }
+  // as EvidenceVideos' (a function of its own: that one stays the single caller's it was, and its kernel's code what it was)
+  __device__ void winners_out(uint32_t v, unsigned long long pool_base, uint32_t c, const BestKey &opening, const BestKey &ending,
+                              bool include_endings, const uint32_t *links) const {
+    DeviceWinners w;
+    w.pool_base = pool_base;
+    w.candidates = c;
+    w.pad = 0;
+    for (int which = 0; which < 2; which++) {
+      const BestKey &k = which == 0 ? opening : ending;
+      const bool have = k.have && (which == 0 || include_endings);  // :486
+      w.region[which].have = have ? 1u : 0u;
+      w.region[which].index = have ? k.index : 0u;
+      w.region[which].support = have ? links[k.index] : 0u;
+      w.region[which].weighted = have ? -k.score : 0.f;
+    }
+    winners[v] = w;
+  }
 };
 
 // One workgroup per wanted video.
@@ -840,7 +944,7 @@ __global__ __launch_bounds__(256) void match_evidence_kernel(EpilogueParams pr, 
     if (t == 0) out[v] = rec;
     return;
   }
-  const uint32_t slots = pr.n - 1;  // (q, v) for q < v, then (v, q + 1)
+  const uint32_t slots = videos.slots(pr, v);  // (q, v) for q < v, then (v, q + 1); a grouped index: the video's group's
   auto bucket_of = [&](uint32_t q) -> uint64_t { return videos.pair(q, v) * pr.regions; };
   auto near_of = [&](uint32_t h) -> uint32_t {
     return (have[0] && (uint32_t)__popc(h ^ hash[0]) < pr.bound ? 1u : 0u) | (have[1] && (uint32_t)__popc(h ^ hash[1]) < pr.bound ? 2u : 0u);
@@ -871,9 +975,9 @@ __global__ __launch_bounds__(256) void match_evidence_kernel(EpilogueParams pr, 
       const uint32_t r = k < openings ? 0u : 1u;
       if (r) k -= openings;
       const DeviceEntry e = entries[start[b + r] + k];
-      const bool as_source = q >= v;
+      const bool as_source = videos.is_source(q, v);
       NeedleHipMatchEvidence &ev = which == 0 ? rec.opening : rec.ending;
-      ev.partner = q < v ? q : q + 1;
+      ev.partner = videos.partner(q, v);
       ev.is_source = as_source ? 1u : 0u;
       ev.match_hash = as_source ? e.src_hash : e.dst_hash;
       ev.partner_hash = as_source ? e.dst_hash : e.src_hash;

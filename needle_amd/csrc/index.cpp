@@ -7,6 +7,10 @@
 // the new pairs only and re-running best_match for the videos whose candidate list changed is bit-identical to
 // Comparator::run_with_frame_hashes over all videos in insertion order.  The entries live on the device (index_store.hip,
 // IndexStore) under column-major pair ids p(i, j) = j (j - 1) / 2 + i, which do not depend on the number of videos.
+//
+// A GROUPED index holds a label per video and only the pairs inside a group: the same argument per group, since
+// restricting a candidate list to a group keeps the relative order of what is left.  Its ids are pair_ids.h's IndexGroupView
+// ids, the column-major id generalised so that an append still adds ids only at the end, whichever group grows.
 #include "index.h"
 
 #include <algorithm>
@@ -142,8 +146,12 @@ std::atomic<uint64_t> next_index_id{1};
 
 }  // namespace
 
-Index::Index(const Comparator &comparator)
-    : cmp_(comparator), include_endings_(comparator.include_endings()), regions_(comparator.include_endings() ? 2u : 1u), id_(next_index_id++) {}
+Index::Index(const Comparator &comparator, bool grouped)
+    : cmp_(comparator),
+      include_endings_(comparator.include_endings()),
+      regions_(comparator.include_endings() ? 2u : 1u),
+      grouped_(grouped),
+      id_(next_index_id++) {}
 
 void Index::changed(uint64_t searched, uint64_t scanned) {
   pairs_last_ = searched;
@@ -160,14 +168,32 @@ Status Index::init() {
   return Status::Ok();
 }
 
-Status Index::add(const std::vector<const FrameHashesData *> &fh) { return append(fh, nullptr, nullptr); }
+Status Index::add(const std::vector<const FrameHashesData *> &fh) {
+  if (grouped_)
+    return Status::Make(NeedleError_InvalidArgument, "index add: a grouped index takes a label per video (needle_hip_index_add_grouped)");
+  return append(fh, nullptr, nullptr);
+}
+
+Status Index::add_grouped(const std::vector<const FrameHashesData *> &fh, const uint32_t *labels) {
+  if (!labels) return Status::Make(NeedleError_NullArgument, "index add_grouped: null argument");
+  if (!grouped_)
+    return Status::Make(NeedleError_InvalidArgument, "index add_grouped: not a grouped index (needle_hip_index_new_grouped makes one)");
+  return append(fh, nullptr, nullptr, labels);
+}
+
+// Groups in the matcher and the cross-matcher are out of scope: their runs name pairs across groups.
+Status Index::refuse_grouped(const char *route) const {
+  return Status::Make(NeedleError_InvalidArgument, std::string("index ") + route + ": a grouped index has no streamed routes (use needle_hip_index_add_grouped)");
+}
 
 Status Index::add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &fh) {
+  if (grouped_) return refuse_grouped("add_matched");
   if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_matched: null argument");
   return append(fh, matcher, nullptr);
 }
 
 Status Index::add_streamed(Matcher *matcher, CrossMatcher *crossmatcher, const std::vector<const FrameHashesData *> &fh) {
+  if (grouped_) return refuse_grouped("add_streamed");
   if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_streamed: null argument");
   if (!crossmatcher && fh.size() > 1)
     return Status::Make(NeedleError_InvalidArgument, "index add_streamed: more than one video needs the cross-matcher of the arriving pairs");
@@ -177,6 +203,7 @@ Status Index::add_streamed(Matcher *matcher, CrossMatcher *crossmatcher, const s
 // The index's rows as a matcher's sources (matcher.hip, regions): gathered on the device from the store's arena; a row's own
 // min_len is a lower bound for every pair the row is in, and a row that can hold no run (min_len 0) has no cells.
 Status Index::matcher(size_t videos, std::unique_ptr<Matcher> *out) {
+  if (grouped_) return refuse_grouped("matcher");
   if (!out) return Status::Make(NeedleError_NullArgument, "index matcher: null argument");
   if (videos_.empty())
     return Status::Make(NeedleError_InvalidArgument,
@@ -198,6 +225,7 @@ Status Index::matcher(size_t videos, std::unique_ptr<Matcher> *out) {
 }
 
 Status Index::crossmatcher(size_t videos, const size_t *max_items, const uint32_t *min_len, std::unique_ptr<CrossMatcher> *out) {
+  if (grouped_) return refuse_grouped("crossmatcher");
   if (!out || !max_items || !min_len) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
   // The argument checks first, with or without a device (no state is asked for: StateBytesResident is host arithmetic) ...
   if (const char *what = CrossMatcher::ShapeError(rows_.seqs.data(), videos_.size(), videos, regions_, max_items, min_len))
@@ -218,9 +246,18 @@ Status Index::crossmatcher(size_t videos, const size_t *max_items, const uint32_
 // add, add_matched and add_streamed: with a cross-matcher (made from the index) its runs stand in for the scan of the new pairs;
 // with a matcher made from the index (`streamed`) its runs stand in for the resident x arriving pairs and those of `matcher`, a
 // cross-matcher over the arriving videos alone (null: one video), for the arriving pairs; everything else is one path.
-Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatcher *matcher, Matcher *streamed) {
+// A grouped index (`labels`, one per arriving video): the new pairs are each arriving video's with the lower-ranked members of
+// its group, old and arriving alike, under the append-stable ids of pair_ids.h (IndexGroupView); the scan only.
+Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatcher *matcher, Matcher *streamed, const uint32_t *labels) {
   if (fh.empty()) return Status::Make(NeedleError_InvalidArgument, "index add: no videos");
   const size_t k = fh.size(), n0 = videos_.size(), n1 = n0 + k, R = regions_;
+  std::vector<uint32_t> all_labels;
+  std::unique_ptr<const IndexGroupTables> groups;
+  if (labels) {
+    all_labels = labels_;
+    all_labels.insert(all_labels.end(), labels, labels + k);
+    groups.reset(new IndexGroupTables(all_labels.data(), n1));
+  }
   const std::string who = streamed ? "index add_streamed: " : "index add_matched: ";
   auto refuse = [&](const char *what) { return Status::Make(NeedleError_InvalidArgument, who + what); };
   if (streamed) {
@@ -257,7 +294,7 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
   auto row_seq = [&](size_t v, size_t r) -> const std::vector<HashTs> & { return r == 0 ? video(v).opening : video(v).ending; };
   if (include_endings_ && n1 > 1)
     for (size_t v = 0; v < n1; v++)
-      if (video(v).ending.empty())  // comparator.rs:271-273 (every video is in some pair)
+      if (video(v).ending.empty() && (!groups || groups->size[groups->group_of[v]] > 1))  // comparator.rs:271-273 (every video that is in some pair)
         return Status::Make(NeedleError_Unknown, "no ending hash data present");
   for (size_t lane = 0; matcher && lane < k * R; lane++) {
     uint64_t fed = 0;
@@ -288,16 +325,26 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
     }
   }
   // the new pairs (i, j), j in [n0, n1), i < j, in column-major order
-  const uint64_t first_pair = (uint64_t)n0 * (n0 ? n0 - 1 : 0) / 2;
-  const uint64_t new_pairs = (uint64_t)n1 * (n1 - 1) / 2 - first_pair;
-  if (((uint64_t)n1 * (n1 - 1) / 2) * R >= 0xFFFFFFF0ull)  // problem tags and bucket ids are 32-bit on the device
+  // (a grouped index: video j's column is its pairs with the members of its group before it, ids vbase[j] + their rank)
+  const uint64_t all_pairs = groups ? groups->pairs() : (uint64_t)n1 * (n1 - 1) / 2;
+  const uint64_t first_pair = groups ? groups->vbase[n0] : (uint64_t)n0 * (n0 ? n0 - 1 : 0) / 2;
+  const uint64_t new_pairs = all_pairs - first_pair;
+  if (all_pairs * R >= 0xFFFFFFF0ull)  // problem tags and bucket ids are 32-bit on the device
     return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
   std::vector<NeedleHipProblem> problems;
   problems.reserve(new_pairs * R);
   uint64_t searched = 0;
-  for (size_t j = n0; j < n1; j++)
+  for (size_t j = n0; j < n1; j++) {
+    if (groups) {
+      const uint32_t *members = groups->members.data() + groups->first[groups->group_of[j]];
+      for (size_t ra = 0; ra < groups->rank_of[j]; ra++)
+        searched += pair_problems(rows.min_len, R, members[ra], j, (groups->vbase[j] + ra - first_pair) * R, &problems);
+      continue;
+    }
     for (size_t i = 0; i < j; i++) searched += pair_problems(rows.min_len, R, i, j, ((uint64_t)j * (j - 1) / 2 + i - first_pair) * R, &problems);
+  }
   IndexAppend a;
+  a.groups = groups.get();
   a.n0 = (uint32_t)n0;
   a.n1 = (uint32_t)n1;
   set_options(cmp_, R, rows.large_ok, &a);
@@ -372,12 +419,23 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
     s = gpu_index_append(store_, a, &out);
     if (!s.ok()) return s;
   }
-  s = settle(cmp_, streamed ? "Index::add_streamed" : matcher ? "Index::add_matched" : "Index::add", R, n1, new_pairs * R, [&](uint64_t q, size_t *i, size_t *j) { column_pair(first_pair + q, i, j); }, row_seq, video,
-             [&](const auto &...computed) { return gpu_index_append_host_entries(store_, a, computed..., &out); }, out);
+  s = settle(cmp_, streamed ? "Index::add_streamed" : matcher ? "Index::add_matched" : "Index::add", R, n1, new_pairs * R,
+             [&](uint64_t q, size_t *i, size_t *j) {
+               if (!groups) return column_pair(first_pair + q, i, j);
+               uint32_t gi = 0, gj = 0;
+               (void)index_group_pair_at(groups->view(), first_pair + q, &gi, &gj);
+               *i = gi;
+               *j = gj;
+             },
+             row_seq, video, [&](const auto &...computed) { return gpu_index_append_host_entries(store_, a, computed..., &out); }, out);
   if (!s.ok()) return s;
   // commit: nothing above changed the index
   index_store_commit(store_, a, out.found);
   for (const FrameHashesData *d : fh) videos_.push_back(*d);
+  if (groups) {
+    labels_.swap(all_labels);
+    groups_ = std::move(groups);
+  }
   rows_ = std::move(rows);
   results_.resize(n1, NeedleHipSearchResult{});
   for (size_t q = 0; q < out.videos.size(); q++) results_[out.videos[q]] = out.results[q];
@@ -427,6 +485,8 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   if (n1 == 0) {  // every video removed: nothing is left to search or to hold
     index_store_clear(store_);
     videos_.clear();
+    labels_.clear();
+    groups_.reset();
     rows_ = IndexRows();
     results_.clear();
     changed(0, 0);
@@ -435,11 +495,20 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   auto is_fresh = [&](size_t v) { return old_of_new[v] == kIndexFresh; };
   auto video = [&](size_t v) -> const FrameHashesData & { return is_fresh(v) ? *fresh[v] : videos_[old_of_new[v]]; };
   auto row_seq = [&](size_t v, size_t r) -> const std::vector<HashTs> & { return r == 0 ? video(v).opening : video(v).ending; };
+  // A grouped index: a kept video keeps its label, a replacement the label of the position it replaces; groups are numbered
+  // and ranked again over the new list (a group that is emptied renumbers the later ones, a removed member lowers the ranks
+  // behind it), and the committed tables give a kept pair's old id.
+  std::vector<uint32_t> labels;
+  std::unique_ptr<const IndexGroupTables> groups;
+  if (grouped_) {
+    for (size_t v = 0; v < n1; v++) labels.push_back(labels_[is_fresh(v) ? v : old_of_new[v]]);
+    groups.reset(new IndexGroupTables(labels.data(), n1));
+  }
   if (include_endings_ && n1 > 1)
     for (size_t v = 0; v < n1; v++)
-      if (video(v).ending.empty())  // comparator.rs:271-273 (every video is in some pair)
+      if (video(v).ending.empty() && (!groups || groups->size[groups->group_of[v]] > 1))  // comparator.rs:271-273 (every video that is in some pair)
         return Status::Make(NeedleError_Unknown, "no ending hash data present");
-  if (((uint64_t)n1 * (n1 - 1) / 2) * R >= 0xFFFFFFF0ull)
+  if ((groups ? groups->pairs() : (uint64_t)n1 * (n1 - 1) / 2) * R >= 0xFFFFFFF0ull)
     return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
   std::vector<uint32_t> new_of_old(n0, kIndexFresh), gone;
   for (size_t v = 0; v < n1; v++)
@@ -495,15 +564,25 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   uint64_t searched = 0;
   auto list_pair = [&](size_t i, size_t j) {
     searched += pair_problems(rows.min_len, R, i, j, (uint64_t)pair_ids.size() * R, &problems);
-    pair_ids.push_back((uint32_t)((uint64_t)j * (j - 1) / 2 + i));
+    pair_ids.push_back((uint32_t)(groups ? groups->vbase[j] + groups->rank_of[i] : (uint64_t)j * (j - 1) / 2 + i));
   };
   for (size_t f = 0; f < n1; f++) {
     if (!is_fresh(f)) continue;
+    if (groups) {  // its pairs inside its group only
+      const uint32_t g = groups->group_of[f];
+      for (uint32_t m = 0; m < groups->size[g]; m++) {
+        const size_t q = groups->members[groups->first[g] + m];
+        if (q < f) list_pair(q, f);
+        else if (q > f && !is_fresh(q)) list_pair(f, q);
+      }
+      continue;
+    }
     for (size_t q = 0; q < f; q++) list_pair(q, f);
     for (size_t q = f + 1; q < n1; q++)
       if (!is_fresh(q)) list_pair(f, q);
   }
   IndexEdit e;
+  e.groups = groups.get();
   e.n_old = (uint32_t)n0;
   e.n_new = (uint32_t)n1;
   set_options(cmp_, R, rows.large_ok, &e);
@@ -532,7 +611,14 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   IndexAppendOut out;
   Status s = gpu_index_edit(store_, e, &out);
   if (!s.ok()) return s;
-  s = settle(cmp_, "Index::replace", R, n1, (uint64_t)pair_ids.size() * R, [&](uint64_t l, size_t *i, size_t *j) { column_pair(pair_ids[l], i, j); },
+  s = settle(cmp_, "Index::replace", R, n1, (uint64_t)pair_ids.size() * R,
+             [&](uint64_t l, size_t *i, size_t *j) {
+               if (!groups) return column_pair(pair_ids[l], i, j);
+               uint32_t gi = 0, gj = 0;
+               (void)index_group_pair_at(groups->view(), pair_ids[l], &gi, &gj);
+               *i = gi;
+               *j = gj;
+             },
              row_seq, video, [&](const auto &...computed) { return gpu_index_edit_host_entries(store_, e, computed..., &out); }, out);
   if (!s.ok()) return s;
   // commit: nothing above changed the index
@@ -551,6 +637,10 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   for (size_t q = 0; q < out.videos.size(); q++) results[out.videos[q]] = out.results[q];
   videos_.swap(videos);
   results_.swap(results);
+  if (groups) {
+    labels_.swap(labels);
+    groups_ = std::move(groups);
+  }
   rows_ = std::move(rows);
   changed(searched, searched);
   return Status::Ok();
@@ -563,6 +653,7 @@ Status Index::evidence(NeedleHipSearchEvidence *out) const {
   if (videos_.empty()) return Status::Ok();
   IndexOptions o;
   set_options(cmp_, regions_, rows_.large_ok, &o);
+  o.groups = groups_.get();
   return gpu_index_evidence(store_, o, out);
 }
 

@@ -7,6 +7,7 @@
 #include "crossmatch.h"
 #include "matcher.h"
 #include "needle_core.h"
+#include "pair_ids.h"
 
 namespace needle {
 
@@ -25,9 +26,13 @@ struct IndexRows {  // per row (video * regions + region), and the sizes of the 
 // Results equal Comparator::run_with_frame_hashes over the index's current list: the videos added, in insertion order, less
 // those removed, with replacements in place.  The index runs on
 // the device that was current when it was created; one GPU only (no sharding across ranks).
+// A GROUPED index holds a library of many seasons: every video has a label, equal labels are one season, only
+// pairs inside a season are searched, and the results equal run_with_frame_hashes over each season's own sub-list of the
+// current list.  It is made as such: labels are given with every add and kept by remove and replace.
 class Index {
  public:
-  explicit Index(const Comparator &comparator);  // copies the comparator's parameters: later changes to it do not matter
+  // copies the comparator's parameters: later changes to it do not matter
+  explicit Index(const Comparator &comparator, bool grouped = false);
   ~Index();
   Index(const Index &) = delete;
   Index &operator=(const Index &) = delete;
@@ -35,6 +40,12 @@ class Index {
   size_t size() const { return videos_.size(); }
   // Appends the videos (copied); on failure the index is as it was before the call.
   Status add(const std::vector<const FrameHashesData *> &videos);
+  // ... with a label per video (any values: they are only compared), on a grouped index: the pairs searched are each arriving
+  // video's with the members of its group before it in the list.  add() without labels on a grouped index, labels on a plain
+  // one and the four streamed routes below on a grouped one are InvalidArgument, before any device work.
+  Status add_grouped(const std::vector<const FrameHashesData *> &videos, const uint32_t *labels);
+  bool grouped() const { return grouped_; }
+  const std::vector<uint32_t> &labels() const { return labels_; }  // the current list's (a grouped index)
   // A cross-matcher over the index's videos (its resident rows, gathered from the store's arena on the device) and `videos`
   // arriving ones, with the index's regions and threshold.  It remembers the index and its generation.
   Status crossmatcher(size_t videos, const size_t *max_items, const uint32_t *min_len, std::unique_ptr<CrossMatcher> *out);
@@ -70,6 +81,9 @@ class Index {
   bool include_endings_;
   uint32_t regions_;
   IndexStore *store_ = nullptr;
+  const bool grouped_;
+  std::vector<uint32_t> labels_;                    // a grouped index: the current list's labels ...
+  std::unique_ptr<const IndexGroupTables> groups_;  // ... and their tables (null while plain or empty)
   std::vector<FrameHashesData> videos_;
   IndexRows rows_;
   std::vector<NeedleHipSearchResult> results_;
@@ -77,7 +91,8 @@ class Index {
   const uint64_t id_;        // from a process-wide counter: what a matcher made here remembers, with ...
   uint64_t generation_ = 1;  // ... this, which every successful change advances
 
-  Status append(const std::vector<const FrameHashesData *> &videos, CrossMatcher *matcher, Matcher *streamed);
+  Status append(const std::vector<const FrameHashesData *> &videos, CrossMatcher *matcher, Matcher *streamed, const uint32_t *labels = nullptr);
+  Status refuse_grouped(const char *route) const;  // the streamed routes on a grouped index
   void changed(uint64_t searched, uint64_t scanned);  // the counters, at a commit
 
   // remove / replace: the new list is old_of_new[v] (an old position) or, where that is kIndexFresh, *fresh[v]

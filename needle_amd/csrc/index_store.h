@@ -4,12 +4,15 @@
 #include <vector>
 
 #include "epilogue.h"
+#include "pair_ids.h"
 
 namespace needle {
 
 // A store in HBM, owned by one NeedleHipIndex: the heap entries of every pair searched so far, per bucket
 // b = p(i, j) * regions + r with the column-major pair id p(i, j) = j (j - 1) / 2 + i (an append adds ids at the end), the
-// buckets' start / valid counts, the videos' row tables (length, timestamps), hash durations and the hash arena.
+// buckets' start / valid counts, the videos' row tables (length, timestamps), hash durations and the hash arena.  A grouped
+// index (IndexOptions::groups) holds only the pairs inside a group, under pair_ids.h's IndexGroupView ids, and the tables of
+// its current list beside the others.
 struct IndexStore;
 IndexStore *index_store_new();  // on the current device
 void index_store_free(IndexStore *store);
@@ -26,6 +29,11 @@ struct IndexSegment {  // `len` elements at `src` of one table and at `dst` of a
 
 struct IndexOptions : EpilogueOptions {  // of an append or an edit
   bool large_ok = false;  // after it, every row is under 65 536 hashes and its timestamps strictly increase
+  // A grouped index: the tables of the list AFTER the operation, built by the caller.  Pair ids are then
+  // pair_ids.h's IndexGroupView ids -- only pairs inside a group exist, an append's new ids are [vbase[n0], vbase[n1]) -- and
+  // the store uploads the tables beside its own and makes them the committed ones with index_store_commit / _switch.  Null: a
+  // plain index, column-major ids, none of the grouped kernels.
+  const IndexGroupTables *groups = nullptr;
 };
 
 // One append: videos [n0, n1) join the n0 the store holds.  Rows are video * regions + region.
@@ -35,7 +43,7 @@ struct IndexAppend : IndexOptions {
   size_t num_hashes = 0;
   const NeedleHipSeq *seqs = nullptr;  // ALL rows, offsets into the arena after the append
   size_t num_seqs = 0;
-  const NeedleHipProblem *problems = nullptr;  // the new pairs only; tag = (p(i, j) - p(0, n0)) * regions + region
+  const NeedleHipProblem *problems = nullptr;  // the new pairs only; tag = (p(i, j) - p(0, n0)) * regions + region (grouped: id - vbase[n0])
   size_t num_problems = 0;
   const uint32_t *row_len = nullptr, *row_ts = nullptr;  // the new rows: length, offset of their timestamps in the store's table
   size_t num_rows = 0;
@@ -129,7 +137,7 @@ struct IndexEdit : IndexOptions {
   const uint64_t *hash_duration = nullptr;               // every new video
   const NeedleHipProblem *problems = nullptr;  // the pairs with a fresh video; tag = listed pair * regions + region
   size_t num_problems = 0;
-  const uint32_t *pair_ids = nullptr;  // listed pair -> its new id p(i, j)
+  const uint32_t *pair_ids = nullptr;  // listed pair -> its new id p(i, j) (grouped: its id under `groups`)
   size_t num_pairs = 0;
 };
 // As gpu_index_append: upload, the new tables gathered, the scan of the listed pairs, their entries behind the committed
@@ -143,7 +151,8 @@ void index_store_switch(IndexStore *store, const IndexEdit &edit, uint32_t held)
 void index_store_clear(IndexStore *store);  // every video removed (no device work)
 // Match evidence (needle_hip.h NeedleHipSearchEvidence), one record per committed video into evidence[0 .. n): best_match over
 // EVERY video of the committed store with the winners' index, count and score written out (the third video policy,
-// epilogue_kernels.h), then match_evidence_kernel, which finds the entries behind them.  Reads the committed tables, writes
+// epilogue_kernels.h; a grouped index: its grouped counterpart over the committed tables, options.groups only says so), then
+// match_evidence_kernel, which finds the entries behind them.  Reads the committed tables, writes
 // the operations' scratch (candidate pool, links, control words) and buffers of its own; one wait.  Nothing is kept.
 Status gpu_index_evidence(IndexStore *store, const IndexOptions &options, NeedleHipSearchEvidence *evidence);
 // [0] heap entries held (sum of the buckets' valid counts: one read of the table), [1] entry slots in use, [2] hashes in

@@ -3,7 +3,9 @@
 // adds theirs behind, an edit (removal / replacement) rebuilds the store under the new pair ids into a second set of
 // tables.  The entries come from the library job's pipeline (epilogue_kernels.h) under the store's pair numberings.
 // Nothing committed is written before index_store_commit / index_store_switch: an operation that fails leaves the store
-// as it was.  tests: test_gpu_index.py, test_gpu_index_edit.py.
+// as it was.  A grouped index goes the same ways under pair_ids.h's grouped ids: its own policies of the entry
+// and best-match kernels and grouped forms of the small kernels here; a plain index launches none of them.
+// tests: test_gpu_index.py, test_gpu_index_edit.py, test_gpu_index_grouped.py.
 #include <mutex>
 #include <string>
 
@@ -248,6 +250,66 @@ __global__ __launch_bounds__(256) void index_fresh_partners_kernel(uint32_t list
   }
 }
 
+// ---- the grouped index (pair_ids.h IndexGroupView): the kernels above that hard-wire the column-major id, under
+// the grouped one.  index_edit_fresh_kernel reads its ids from the listed pairs' table and serves both.
+// The videos whose candidate list a grouped append changed: the lower member i of a new pair (i, j) with an entry (old or
+// arriving alike; every arriving video is listed anyway).  One bisection per bucket that has entries.
+__global__ __launch_bounds__(256) void index_group_changed_kernel(uint32_t buckets, uint32_t regions, uint64_t first, IndexGroupView groups,
+                                                                  const uint32_t *__restrict__ valid, uint32_t *__restrict__ flag) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < buckets; b += gridDim.x * blockDim.x) {
+    if (valid[b] == 0) continue;
+    uint32_t i, j;
+    if (index_group_pair_at(groups, first + b / regions, &i, &j)) flag[i] = 1u;
+  }
+}
+// A kept pair's new bucket -> its old bucket: the pair under the new tables, its two videos' old positions, their id under the
+// old tables (removal keeps the relative order and the labels, so the two are of one old group with the same roles).
+__global__ __launch_bounds__(256) void index_group_edit_buckets_kernel(uint32_t buckets, uint32_t regions, IndexGroupView groups,
+                                                                       IndexGroupView old_groups, const uint32_t *__restrict__ old_of_new,
+                                                                       const uint32_t *__restrict__ old_start,
+                                                                       const uint32_t *__restrict__ old_valid, uint32_t *__restrict__ src,
+                                                                       uint32_t *__restrict__ count) {
+  for (uint32_t b = blockIdx.x * blockDim.x + threadIdx.x; b < buckets; b += gridDim.x * blockDim.x) {
+    uint32_t i, j;
+    if (!index_group_pair_at(groups, b / regions, &i, &j)) continue;
+    const uint32_t oi = old_of_new[i], oj = old_of_new[j];
+    if (oi == kIndexFresh || oj == kIndexFresh) continue;
+    uint64_t op;
+    if (!index_group_pair(old_groups, oi, oj, &op)) continue;
+    const uint64_t ob = op * regions + b % regions;
+    src[b] = old_start[ob];
+    count[b] = old_valid[ob];
+  }
+}
+// Every kept video with an entry in a pair of a video removed or replaced: the committed store, old ids, the gone video's group only.
+__global__ __launch_bounds__(256) void index_group_gone_partners_kernel(uint32_t n_old, uint32_t regions, IndexGroupView old_groups,
+                                                                        const uint32_t *__restrict__ gone, uint32_t num_gone,
+                                                                        const uint32_t *__restrict__ valid,
+                                                                        const uint32_t *__restrict__ new_of_old, uint32_t *__restrict__ flag) {
+  const uint64_t total = (uint64_t)num_gone * n_old;
+  for (uint64_t t = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t x = gone[t / n_old], q = (uint32_t)(t % n_old);
+    if (q == x || new_of_old[q] == kIndexFresh) continue;
+    uint64_t p;
+    if (!index_group_pair(old_groups, min(q, x), max(q, x), &p)) continue;  // (of another group: no pair)
+    bool any = false;
+    for (uint32_t r = 0; r < regions; r++) any = any || valid[p * regions + r] != 0;
+    if (any) flag[new_of_old[q]] = 1u;
+  }
+}
+// ... and every video with an entry in a listed pair
+__global__ __launch_bounds__(256) void index_group_fresh_partners_kernel(uint32_t listed, uint32_t regions, IndexGroupView groups,
+                                                                         const uint32_t *__restrict__ pair_ids,
+                                                                         const uint32_t *__restrict__ lvalid, uint32_t *__restrict__ flag) {
+  for (uint32_t l = blockIdx.x * blockDim.x + threadIdx.x; l < listed; l += gridDim.x * blockDim.x) {
+    if (lvalid[l] == 0) continue;
+    uint32_t i, j;
+    if (!index_group_pair_at(groups, pair_ids[l / regions], &i, &j)) continue;
+    flag[i] = 1u;
+    flag[j] = 1u;
+  }
+}
+
 // A device array that keeps its contents when it grows (amortised doubling, a device-to-device copy on `stream`).
 template <class T>
 struct GrowBuffer {
@@ -281,6 +343,15 @@ struct StoreTables {
   GrowBuffer<uint64_t> row_seek, ts_table, hash_duration;
 };
 
+// A grouped index's tables on the device (pair_ids.h IndexGroupView): the 32-bit ones in one buffer -- group_of[n], rank_of[n],
+// members[n], size[groups], first[groups] -- and vbase[n + 1].  The store holds two: the committed list's, and the one an
+// operation uploads the new list's into (committed with everything else).
+struct DeviceGroupTables {
+  DeviceBuffer<uint32_t> words;
+  DeviceBuffer<uint64_t> vbase;
+  IndexGroupView view{};
+};
+
 struct PinnedHead {  // what an operation reads back, in pinned memory: followed by list[n] and results[n]
   uint32_t found, failed, listed, held;
 };
@@ -294,6 +365,8 @@ struct IndexStore {
   uint64_t buckets = 0, entries = 0, rows = 0, ts = 0, hashes = 0;
   StoreTables tables[2];
   StoreTables *cur = &tables[0], *next = &tables[1];  // (index_store_switch swaps the two)
+  DeviceGroupTables group_tables[2];  // a grouped index's: [group_cur] the committed list's, the other an operation's
+  int group_cur = 0;
   DeviceBuffer<uint32_t> src, old_of_new, new_of_old, gone, pair_ids;  // an edit's maps
   DeviceBuffer<IndexSegment> segments;
   // an operation's scratch
@@ -344,14 +417,38 @@ void index_store_free(IndexStore *st) {
 
 namespace {
 
-uint64_t append_first_pair(const IndexAppend &a) { return (uint64_t)a.n0 * (a.n0 - (a.n0 ? 1 : 0)) / 2; }
-uint64_t append_buckets(const IndexAppend &a) { return ((uint64_t)a.n1 * (a.n1 - 1) / 2 - append_first_pair(a)) * a.regions; }
-uint64_t edit_buckets(const IndexEdit &e) { return (uint64_t)e.n_new * (e.n_new ? e.n_new - 1 : 0) / 2 * e.regions; }
+uint64_t append_first_pair(const IndexAppend &a) { return a.groups ? a.groups->vbase[a.n0] : (uint64_t)a.n0 * (a.n0 - (a.n0 ? 1 : 0)) / 2; }
+uint64_t append_buckets(const IndexAppend &a) {
+  return ((a.groups ? a.groups->pairs() : (uint64_t)a.n1 * (a.n1 - 1) / 2) - append_first_pair(a)) * a.regions;
+}
+uint64_t edit_buckets(const IndexEdit &e) {
+  return (e.groups ? e.groups->pairs() : (uint64_t)e.n_new * (e.n_new ? e.n_new - 1 : 0) / 2) * e.regions;
+}
 
 template <class T>
 hipError_t upload(T *dst, const T *src, size_t count, hipStream_t stream) {  // (pageable source: staged before the call returns)
   return count ? hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, stream) : hipSuccess;
 }
+
+// A grouped operation's tables (the list after it) into the store's spare set: not the committed ones, which an edit reads
+// beside them and a failing operation keeps.
+Status index_upload_groups(IndexStore *st, const IndexGroupTables &g, hipStream_t stream) {
+  DeviceGroupTables &d = st->group_tables[1 - st->group_cur];
+  const size_t n = g.group_of.size(), groups = g.size.size();
+  Status s;
+  if (!(s = d.words.reserve(std::max<size_t>(3 * n + 2 * groups, 1))).ok() || !(s = d.vbase.reserve(n + 1)).ok()) return s;
+  uint32_t *w = d.words.ptr;
+  NEEDLE_HIP_TRY(upload(w, g.group_of.data(), n, stream));
+  NEEDLE_HIP_TRY(upload(w + n, g.rank_of.data(), n, stream));
+  NEEDLE_HIP_TRY(upload(w + 2 * n, g.members.data(), n, stream));
+  NEEDLE_HIP_TRY(upload(w + 3 * n, g.size.data(), groups, stream));
+  NEEDLE_HIP_TRY(upload(w + 3 * n + groups, g.first.data(), groups, stream));
+  NEEDLE_HIP_TRY(upload(d.vbase.ptr, g.vbase.data(), n + 1, stream));
+  d.view = IndexGroupView{w, w + n, w + 3 * n, w + 3 * n + groups, w + 2 * n, d.vbase.ptr, (uint32_t)n};
+  return Status::Ok();
+}
+const IndexGroupView &operation_groups(const IndexStore *st) { return st->group_tables[1 - st->group_cur].view; }
+const IndexGroupView &committed_groups(const IndexStore *st) { return st->group_tables[st->group_cur].view; }
 
 Status index_check_device(const IndexStore *st) {
   int dev = 0;
@@ -431,9 +528,15 @@ Status index_entries(IndexStore *st, const EpilogueParams &pr, const StoreTables
 
 // Inside the caller's "index_best_match" timer, behind the kernels that flag the videos whose candidate list changed: those
 // and every video from `from` on listed, and best_match over the list in the tables `t`.
-void enqueue_list_and_match(IndexStore *st, const EpilogueParams &pr, uint32_t from, const StoreTables &t, hipStream_t stream) {
+void enqueue_list_and_match(IndexStore *st, const EpilogueParams &pr, uint32_t from, const StoreTables &t, bool grouped, hipStream_t stream) {
   EpilogueControl *ctl = st->ctl.ptr;
   hipLaunchKernelGGL(index_list_kernel, dim3((pr.n + 255) / 256), dim3(256), 0, stream, from, pr.n, st->flag.ptr, &ctl->listed, st->list.ptr);
+  if (grouped) {  // the operation's tables: the listed videos' groups
+    hipLaunchKernelGGL((best_match_kernel<IndexGroupVideos, IndexGroupView, const uint32_t *, const uint32_t *, const uint64_t *>), dim3(pr.n),
+                       dim3(256), 0, stream, pr, t.start.ptr(), t.valid.ptr(), t.entry.ptr(), st->cand.ptr, &ctl->cand_cursor, st->links.ptr,
+                       st->results.ptr, &ctl->failed, operation_groups(st), st->list.ptr, &ctl->listed, t.hash_duration.ptr());
+    return;
+  }
   // one workgroup per video at most; those beyond the list's length return at once
   hipLaunchKernelGGL((best_match_kernel<IndexVideos, const uint32_t *, const uint32_t *, const uint64_t *>), dim3(pr.n), dim3(256), 0, stream, pr,
                      t.start.ptr(), t.valid.ptr(), t.entry.ptr(), st->cand.ptr, &ctl->cand_cursor, st->links.ptr, st->results.ptr, &ctl->failed,
@@ -495,10 +598,14 @@ Status index_best_and_copy(IndexStore *st, const IndexAppend &a, hipStream_t str
     KernelTimer timer("index_best_match", stream);
     if (new_buckets) {
       const uint32_t grid = (uint32_t)std::min<uint64_t>(4096, (new_buckets + 255) / 256);
-      hipLaunchKernelGGL(index_changed_kernel, dim3(grid), dim3(256), 0, stream, (uint32_t)new_buckets, a.regions, append_first_pair(a),
-                         st->cur->valid.ptr() + st->buckets, st->flag.ptr);
+      if (a.groups)
+        hipLaunchKernelGGL(index_group_changed_kernel, dim3(grid), dim3(256), 0, stream, (uint32_t)new_buckets, a.regions, append_first_pair(a),
+                           operation_groups(st), (const uint32_t *)(st->cur->valid.ptr() + st->buckets), st->flag.ptr);
+      else
+        hipLaunchKernelGGL(index_changed_kernel, dim3(grid), dim3(256), 0, stream, (uint32_t)new_buckets, a.regions, append_first_pair(a),
+                           st->cur->valid.ptr() + st->buckets, st->flag.ptr);
     }
-    enqueue_list_and_match(st, pr, a.n0, *st->cur, stream);
+    enqueue_list_and_match(st, pr, a.n0, *st->cur, a.groups != nullptr, stream);
   }
   NEEDLE_HIP_TRY(hipGetLastError());
   return index_copy_out(st, a.n1, nullptr, stream, out);
@@ -512,6 +619,8 @@ namespace {
 Status index_append_tables(IndexStore *st, const IndexAppend &a, hipStream_t stream) {
   if (a.n0 != st->n || a.n1 <= a.n0 || a.regions < 1 || a.regions > 2)
     return Status::Make(NeedleError_InvalidArgument, "index append: inconsistent sizes");
+  if (a.groups && (a.groups->group_of.size() != a.n1 || a.groups->vbase[a.n0] * a.regions != st->buckets))
+    return Status::Make(NeedleError_InvalidArgument, "index append: the group tables are not the store's list and the new videos");
   StoreTables &t = *st->cur;
   const uint64_t new_buckets = append_buckets(a), buckets1 = st->buckets + new_buckets;
   const uint64_t rows1 = st->rows + a.num_rows, ts1 = st->ts + a.num_ts, hashes1 = st->hashes + a.num_hashes;
@@ -530,7 +639,7 @@ Status index_append_tables(IndexStore *st, const IndexAppend &a, hipStream_t str
   NEEDLE_HIP_TRY(hipMemsetAsync(t.row_seek.ptr() + st->rows, 0, a.num_rows * sizeof(uint64_t), stream));
   NEEDLE_HIP_TRY(upload(t.ts_table.ptr() + st->ts, a.ts, a.num_ts, stream));
   NEEDLE_HIP_TRY(upload(t.hash_duration.ptr() + st->n, a.hash_duration, a.n1 - a.n0, stream));
-  return Status::Ok();
+  return a.groups ? index_upload_groups(st, *a.groups, stream) : Status::Ok();
 }
 
 // The second half, behind the slab: fill(capacity) leaves the new pairs' runs, tagged for the append, in st->runs and their
@@ -549,7 +658,9 @@ Status index_append_from_slab(IndexStore *st, const IndexAppend &a, hipStream_t 
       if (!(s = index_sort_runs(st, pr.buckets, capacity, stream)).ok()) return s;
       {
         KernelTimer timer("index_entries", stream);
-        if (!(s = index_entries<ColumnMajorPairs, uint64_t>(st, pr, t, stream, append_first_pair(a))).ok()) return s;
+        s = a.groups ? index_entries<IndexGroupAppendPairs, IndexGroupView, uint64_t>(st, pr, t, stream, operation_groups(st), append_first_pair(a))
+                     : index_entries<ColumnMajorPairs, uint64_t>(st, pr, t, stream, append_first_pair(a));
+        if (!s.ok()) return s;
         // into the store's tables: start = where the entries were written
         hipLaunchKernelGGL(index_store_buckets_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (new_buckets + 255) / 256)), dim3(256), 0,
                            stream, pr.buckets, st->scratch.start.ptr, st->scratch.valid.ptr, (uint32_t)st->entries, t.start.ptr() + st->buckets,
@@ -676,6 +787,7 @@ void index_store_commit(IndexStore *st, const IndexAppend &a, uint32_t found) {
   st->ts += a.num_ts;
   st->hashes += a.num_hashes;
   st->n = a.n1;
+  if (a.groups) st->group_cur = 1 - st->group_cur;
 }
 
 // ---- an edit: removal / replacement --------------------------------------------------------------------------------------
@@ -725,7 +837,9 @@ Status index_edit_tables(IndexStore *st, const IndexEdit &e, uint32_t capacity, 
   if (!s.ok()) return s;
   {
     KernelTimer timer("index_entries", stream);
-    if (!(s = index_entries<ListedPairs, const uint32_t *>(st, pr, next, stream, st->pair_ids.ptr)).ok()) return s;
+    s = e.groups ? index_entries<IndexGroupListedPairs, IndexGroupView, const uint32_t *>(st, pr, next, stream, operation_groups(st), st->pair_ids.ptr)
+                 : index_entries<ListedPairs, const uint32_t *>(st, pr, next, stream, st->pair_ids.ptr);
+    if (!s.ok()) return s;
   }
   NEEDLE_HIP_TRY(hipGetLastError());
   return Status::Ok();
@@ -741,9 +855,14 @@ Status index_edit_rebuild(IndexStore *st, const IndexEdit &e, hipStream_t stream
   {
     KernelTimer timer("index_rebuild", stream);
     if (buckets) {
-      hipLaunchKernelGGL(index_edit_buckets_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (buckets + 255) / 256)), dim3(256), 0, stream,
-                         (uint32_t)buckets, R, (const uint32_t *)st->old_of_new.ptr, (const uint32_t *)cur.start.ptr(),
-                         (const uint32_t *)cur.valid.ptr(), st->src.ptr, next.valid.ptr());
+      if (e.groups)
+        hipLaunchKernelGGL(index_group_edit_buckets_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (buckets + 255) / 256)), dim3(256), 0, stream,
+                           (uint32_t)buckets, R, operation_groups(st), committed_groups(st), (const uint32_t *)st->old_of_new.ptr,
+                           (const uint32_t *)cur.start.ptr(), (const uint32_t *)cur.valid.ptr(), st->src.ptr, next.valid.ptr());
+      else
+        hipLaunchKernelGGL(index_edit_buckets_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (buckets + 255) / 256)), dim3(256), 0, stream,
+                           (uint32_t)buckets, R, (const uint32_t *)st->old_of_new.ptr, (const uint32_t *)cur.start.ptr(),
+                           (const uint32_t *)cur.valid.ptr(), st->src.ptr, next.valid.ptr());
       if (listed)
         hipLaunchKernelGGL(index_edit_fresh_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (listed + 255) / 256)), dim3(256), 0, stream,
                            (uint32_t)listed, R, (const uint32_t *)st->pair_ids.ptr, (const uint32_t *)st->scratch.start.ptr,
@@ -769,14 +888,25 @@ Status index_edit_rebuild(IndexStore *st, const IndexEdit &e, hipStream_t stream
     hipLaunchKernelGGL(index_fresh_flags_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, (const uint32_t *)st->old_of_new.ptr, st->flag.ptr);
     if (e.num_gone && e.n_old > 1) {
       const uint64_t work = (uint64_t)e.num_gone * e.n_old;
-      hipLaunchKernelGGL(index_gone_partners_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (work + 255) / 256)), dim3(256), 0, stream, e.n_old,
-                         R, (const uint32_t *)st->gone.ptr, (uint32_t)e.num_gone, (const uint32_t *)cur.valid.ptr(),
-                         (const uint32_t *)st->new_of_old.ptr, st->flag.ptr);
+      const dim3 grid((uint32_t)std::min<uint64_t>(4096, (work + 255) / 256));
+      if (e.groups)
+        hipLaunchKernelGGL(index_group_gone_partners_kernel, grid, dim3(256), 0, stream, e.n_old, R, committed_groups(st),
+                           (const uint32_t *)st->gone.ptr, (uint32_t)e.num_gone, (const uint32_t *)cur.valid.ptr(),
+                           (const uint32_t *)st->new_of_old.ptr, st->flag.ptr);
+      else
+        hipLaunchKernelGGL(index_gone_partners_kernel, grid, dim3(256), 0, stream, e.n_old, R, (const uint32_t *)st->gone.ptr,
+                           (uint32_t)e.num_gone, (const uint32_t *)cur.valid.ptr(), (const uint32_t *)st->new_of_old.ptr, st->flag.ptr);
     }
-    if (listed)
-      hipLaunchKernelGGL(index_fresh_partners_kernel, dim3((uint32_t)std::min<uint64_t>(4096, (listed + 255) / 256)), dim3(256), 0, stream,
-                         (uint32_t)listed, R, (const uint32_t *)st->pair_ids.ptr, (const uint32_t *)st->scratch.valid.ptr, st->flag.ptr);
-    enqueue_list_and_match(st, pr, n, next, stream);
+    if (listed) {
+      const dim3 grid((uint32_t)std::min<uint64_t>(4096, (listed + 255) / 256));
+      if (e.groups)
+        hipLaunchKernelGGL(index_group_fresh_partners_kernel, grid, dim3(256), 0, stream, (uint32_t)listed, R, operation_groups(st),
+                           (const uint32_t *)st->pair_ids.ptr, (const uint32_t *)st->scratch.valid.ptr, st->flag.ptr);
+      else
+        hipLaunchKernelGGL(index_fresh_partners_kernel, grid, dim3(256), 0, stream, (uint32_t)listed, R, (const uint32_t *)st->pair_ids.ptr,
+                           (const uint32_t *)st->scratch.valid.ptr, st->flag.ptr);
+    }
+    enqueue_list_and_match(st, pr, n, next, e.groups != nullptr, stream);
   }
   NEEDLE_HIP_TRY(hipGetLastError());
   return index_copy_out(st, n, next.start.ptr() + buckets, stream, out);
@@ -790,7 +920,10 @@ Status gpu_index_edit(IndexStore *st, const IndexEdit &e, IndexAppendOut *out) {
   if (!s.ok()) return s;
   if (e.n_old != st->n || e.n_new < 1 || e.regions < 1 || e.regions > 2)
     return Status::Make(NeedleError_InvalidArgument, "index edit: inconsistent sizes");
+  if (e.groups && (e.groups->group_of.size() != e.n_new || committed_groups(st).videos != e.n_old))
+    return Status::Make(NeedleError_InvalidArgument, "index edit: the group tables are not the new list's, or the store is not a grouped one");
   hipStream_t stream = library_stream();
+  if (e.groups && !(s = index_upload_groups(st, *e.groups, stream)).ok()) return s;
   StoreTables &next = *st->next;
   const uint64_t buckets = edit_buckets(e), listed = (uint64_t)e.num_pairs * e.regions, rows = (uint64_t)e.n_new * e.regions;
   if (buckets >= 0xFFFFFFF0ull || e.total_hashes > UINT32_MAX || e.total_ts > UINT32_MAX)
@@ -830,11 +963,13 @@ void index_store_switch(IndexStore *st, const IndexEdit &e, uint32_t held) {
   st->rows = (uint64_t)e.n_new * e.regions;
   st->ts = e.total_ts;
   st->hashes = e.total_hashes;
+  if (e.groups) st->group_cur = 1 - st->group_cur;
 }
 
 void index_store_clear(IndexStore *st) {
   st->n = 0;
   st->buckets = st->entries = st->rows = st->ts = st->hashes = 0;
+  st->group_tables[st->group_cur].view = IndexGroupView{};  // (a grouped index: no video, no table is read)
 }
 
 // ---- match evidence -------------------------------------------------------------------------------------------------------
@@ -865,17 +1000,29 @@ Status gpu_index_evidence(IndexStore *st, const IndexOptions &o, NeedleHipSearch
   EpilogueControl *ctl = st->ctl.ptr;
   NEEDLE_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(EpilogueControl), stream));
   NEEDLE_HIP_TRY(hipMemsetAsync(st->winners.ptr, 0, (size_t)n * sizeof(DeviceWinners), stream));
+  const IndexGroupView groups = o.groups ? committed_groups(st) : IndexGroupView{};  // a grouped index: both launches under the committed tables
+  if (o.groups && groups.videos != n) return Status::Make(NeedleError_InvalidArgument, "index evidence: the store holds no group tables for its videos");
   {
     KernelTimer timer("index_evidence_match", stream);
-    hipLaunchKernelGGL((best_match_kernel<EvidenceVideos, const uint64_t *, DeviceWinners *>), dim3(n), dim3(256), 0, stream, pr, t.start.ptr(),
-                       t.valid.ptr(), t.entry.ptr(), st->cand.ptr, &ctl->cand_cursor, st->links.ptr, st->results.ptr, &ctl->failed,
-                       t.hash_duration.ptr(), st->winners.ptr);
+    if (o.groups)
+      hipLaunchKernelGGL((best_match_kernel<IndexGroupEvidenceVideos, IndexGroupView, const uint64_t *, DeviceWinners *>), dim3(n), dim3(256), 0,
+                         stream, pr, t.start.ptr(), t.valid.ptr(), t.entry.ptr(), st->cand.ptr, &ctl->cand_cursor, st->links.ptr, st->results.ptr,
+                         &ctl->failed, groups, t.hash_duration.ptr(), st->winners.ptr);
+    else
+      hipLaunchKernelGGL((best_match_kernel<EvidenceVideos, const uint64_t *, DeviceWinners *>), dim3(n), dim3(256), 0, stream, pr, t.start.ptr(),
+                         t.valid.ptr(), t.entry.ptr(), st->cand.ptr, &ctl->cand_cursor, st->links.ptr, st->results.ptr, &ctl->failed,
+                         t.hash_duration.ptr(), st->winners.ptr);
   }
   {
     KernelTimer timer("index_evidence", stream);
-    hipLaunchKernelGGL((match_evidence_kernel<EvidenceVideos, const uint64_t *, DeviceWinners *>), dim3(n), dim3(256), 0, stream, pr,
-                       (const uint32_t *)t.start.ptr(), (const uint32_t *)t.valid.ptr(), (const DeviceEntry *)t.entry.ptr(),
-                       (const Candidate *)st->cand.ptr, st->evidence.ptr, (const uint64_t *)t.hash_duration.ptr(), st->winners.ptr);
+    if (o.groups)
+      hipLaunchKernelGGL((match_evidence_kernel<IndexGroupEvidenceVideos, IndexGroupView, const uint64_t *, DeviceWinners *>), dim3(n), dim3(256), 0,
+                         stream, pr, (const uint32_t *)t.start.ptr(), (const uint32_t *)t.valid.ptr(), (const DeviceEntry *)t.entry.ptr(),
+                         (const Candidate *)st->cand.ptr, st->evidence.ptr, groups, (const uint64_t *)t.hash_duration.ptr(), st->winners.ptr);
+    else
+      hipLaunchKernelGGL((match_evidence_kernel<EvidenceVideos, const uint64_t *, DeviceWinners *>), dim3(n), dim3(256), 0, stream, pr,
+                         (const uint32_t *)t.start.ptr(), (const uint32_t *)t.valid.ptr(), (const DeviceEntry *)t.entry.ptr(),
+                         (const Candidate *)st->cand.ptr, st->evidence.ptr, (const uint64_t *)t.hash_duration.ptr(), st->winners.ptr);
   }
   NEEDLE_HIP_TRY(hipGetLastError());
   NEEDLE_HIP_TRY(hipMemcpyAsync(st->evidence_pinned, st->evidence.ptr, (size_t)n * sizeof(NeedleHipSearchEvidence), hipMemcpyDeviceToHost, stream));

@@ -3,7 +3,8 @@
 //   i-major (the comparator's, NeedleHipRun.problem of a cross-matcher over V videos): pair (a, b), a < b, is
 //     a (2 V - a - 1) / 2 + (b - a - 1); it depends on V.
 //   column-major (the index store's): p(a, b) = b (b - 1) / 2 + a; it does not, so an append adds ids at the end.
-//   grouped (a library of many seasons, the end of this file): only pairs inside one group of videos have an id.
+//   grouped (a library of many seasons, further down): only pairs inside one group of videos have an id.
+//   grouped and append-stable (the grouped index's store, the end of this file): the column-major id over groups.
 #pragma once
 
 #include <cstddef>
@@ -134,6 +135,74 @@ struct GroupTables {
   uint64_t pairs() const { return base.back(); }
   GroupView view() const {
     return GroupView{group_of.data(), rank_of.data(), size.data(), first.data(), base.data(), members.data(), (uint32_t)size.size()};
+  }
+};
+
+// ---- grouped and append-stable: the index store's numbering of a library of many seasons ----------------------------------
+// base[g] above moves when an earlier group grows, so a store that is appended to cannot keep it.  The column-major id,
+// generalised: vbase[v] = sum over u < v of rank_of[u], and pair (a, b), a < b, both of one group, is vbase[b] + rank_of[a] --
+// video b's column holds its pairs with the lower-ranked members of its group, rank_of[b] of them.  A video appended to the
+// list changes no rank and no vbase of a video already present, so it adds ids only at the end; with one group the rank is the
+// position and the id is column_major_pair(a, b).  Groups, ranks and members are GroupTables'.
+struct IndexGroupView {
+  const uint32_t *group_of, *rank_of;  // per video
+  const uint32_t *size, *first;        // per group: n_g, where its members start in `members`
+  const uint32_t *members;             // list positions, group after group
+  const uint64_t *vbase;               // per video, and vbase[videos] = all pairs
+  uint32_t videos;
+};
+
+NEEDLE_HOST_DEVICE inline uint64_t index_group_pair_count(const IndexGroupView &t) { return t.vbase[t.videos]; }
+
+// id of (a, b), a < b; false where the two are not of one group
+NEEDLE_HOST_DEVICE inline bool index_group_pair(const IndexGroupView &t, uint32_t a, uint32_t b, uint64_t *pair) {
+  if (a >= b || b >= t.videos || t.group_of[a] != t.group_of[b]) return false;
+  *pair = t.vbase[b] + t.rank_of[a];
+  return true;
+}
+
+// (a, b) of pair `pair`; false where there is no such pair.  The last video whose vbase is at or before `pair`, by bisection (a
+// video of rank 0 has no column and shares its vbase with the next video, so that is the video that holds it).
+NEEDLE_HOST_DEVICE inline bool index_group_pair_at(const IndexGroupView &t, uint64_t pair, uint32_t *a, uint32_t *b) {
+  if (t.videos == 0 || pair >= index_group_pair_count(t)) return false;
+  uint32_t lo = 0, hi = t.videos - 1;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo + 1) / 2;
+    if (t.vbase[mid] <= pair) lo = mid;
+    else hi = mid - 1;
+  }
+  const uint64_t ra = pair - t.vbase[lo];
+  if (ra >= t.rank_of[lo]) return false;
+  *a = t.members[t.first[t.group_of[lo]] + ra];
+  *b = lo;
+  return true;
+}
+
+// a video's pairs: n_g - 1 slots, in the reference's order over its group.  Slot q below v's rank is (q-th member, v), in v's
+// own column; a slot at or above it is (v, member q + 1), in that member's column.
+NEEDLE_HOST_DEVICE inline uint32_t index_group_slots(const IndexGroupView &t, uint32_t v) { return t.size[t.group_of[v]] - 1; }
+NEEDLE_HOST_DEVICE inline uint64_t index_group_slot_pair(const IndexGroupView &t, uint32_t q, uint32_t v, uint32_t *a, uint32_t *b) {
+  const uint32_t rank = t.rank_of[v];
+  const uint32_t other = t.members[t.first[t.group_of[v]] + (q < rank ? q : q + 1)];
+  *a = q < rank ? other : v;
+  *b = q < rank ? v : other;
+  return q < rank ? t.vbase[v] + q : t.vbase[other] + rank;
+}
+
+// The tables of an index's current list, built on the host at every operation (a few words per video).
+struct IndexGroupTables : GroupTables {
+  std::vector<uint64_t> vbase;
+  IndexGroupTables(const uint32_t *labels, size_t n) : GroupTables(labels, n), vbase(n + 1) {
+    uint64_t pairs = 0;
+    for (size_t v = 0; v < n; v++) {
+      vbase[v] = pairs;
+      pairs += rank_of[v];
+    }
+    vbase[n] = pairs;
+  }
+  uint64_t pairs() const { return vbase.back(); }
+  IndexGroupView view() const {
+    return IndexGroupView{group_of.data(), rank_of.data(), size.data(), first.data(), members.data(), vbase.data(), (uint32_t)group_of.size()};
   }
 };
 

@@ -415,6 +415,14 @@ extern "C" {
         k: usize,
     ) -> NeedleError;
     pub fn needle_hip_index_pairs_scanned(index: *const NeedleHipIndex, total: *mut u64, last: *mut u64) -> NeedleError;
+    pub fn needle_hip_index_new_grouped(comparator: *const NeedleAudioComparator, output: *mut *mut NeedleHipIndex) -> NeedleError;
+    pub fn needle_hip_index_add_grouped(
+        index: *mut NeedleHipIndex,
+        frame_hashes: *const *const FrameHashes,
+        groups: *const u32,
+        k: usize,
+    ) -> NeedleError;
+    pub fn needle_hip_index_groups(index: *const NeedleHipIndex, labels: *mut u32, n: usize) -> NeedleError;
     /// 1..=MAX_CHANNELS interleaved channels -> mono, `(sum of a frame) / channels` with C truncation; `out[i]` holds
     /// `num_values[i] / channels` values.
     pub fn needle_hip_downmix_host(

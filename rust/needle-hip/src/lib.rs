@@ -1114,6 +1114,37 @@ impl Index {
         unsafe { check(ffi::needle_hip_index_add(self.raw, raw.as_ptr(), raw.len())) }
     }
 
+    /// A grouped index (include/needle_hip.h "A grouped index"): a library of many seasons.  Videos are added with a label
+    /// each (`add_grouped`), only pairs inside a season are searched, and `results()` equals
+    /// `Comparator::run_with_frame_hashes_grouped` over the current list.
+    pub fn new_grouped<P: AsRef<Path>>(comparator: &Comparator<P>) -> Result<Self> {
+        let handle = comparator.handle()?;
+        let mut raw = ptr::null_mut();
+        let status = unsafe { check(ffi::needle_hip_index_new_grouped(handle, &mut raw)) };
+        unsafe { ffi::needle_audio_comparator_free(handle) };
+        status?;
+        Ok(Index { raw })
+    }
+
+    /// Appends the videos to a grouped index, `groups[i]` the label of `frame_hashes[i]` (any values: they are only compared).
+    pub fn add_grouped(&mut self, frame_hashes: &[&FrameHashes], groups: &[u32]) -> Result<()> {
+        if groups.len() != frame_hashes.len() {
+            return Err(Error {
+                code: ffi::NeedleError::InvalidArgument,
+                message: "index add_grouped: one group label per video".into(),
+            });
+        }
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        unsafe { check(ffi::needle_hip_index_add_grouped(self.raw, raw.as_ptr(), groups.as_ptr(), raw.len())) }
+    }
+
+    /// The current list's labels, one per video (a grouped index; an error on a plain one).
+    pub fn groups(&self) -> Result<Vec<u32>> {
+        let mut labels = vec![0u32; self.len()];
+        unsafe { check(ffi::needle_hip_index_groups(self.raw, labels.as_mut_ptr(), labels.len()))? };
+        Ok(labels)
+    }
+
     /// Removes the videos at these distinct positions; the others keep their order.  No pair is searched.  On error the
     /// index is as it was before the call.
     pub fn remove(&mut self, positions: &[usize]) -> Result<()> {
