@@ -156,6 +156,44 @@ enum NeedleError needle_hip_fingerprint_audit_device(const int16_t *d_pcm, const
 enum NeedleError needle_hip_fingerprint_debug(const int16_t *pcm, size_t num_values, int channels,
                                               double *chroma, double *features);
 
+/* Test hook: what each of the four kernels of the certified chain wrote (f32 first pass -> certification -> f64
+ * recomputation of the listed chunks -> fix-up of the listed items), copied to the host.  Host PCM streams as
+ * needle_hip_fingerprint_host takes them; the hook runs the product's own chain over them as ONE batch -- the same
+ * planning, launch sizes, schedule and kernels as needle_hip_fingerprint_device, with device-to-device copies between
+ * the launches -- after filling the chain's chroma and energy rows with a NaN bit pattern (bytes 0xFF), so that a row no
+ * kernel wrote shows.  Differences from the product's call: a batch without one kept item still runs its first pass,
+ * and flags bit 0 picks the recomputation kernel's "beside" form (the one pipelined library jobs use).
+ * NEEDLE_HIP_CERT_K, NEEDLE_STFT_PAIRS and NEEDLE_HIP_ITEMS_PER_TILE act as in the product; NEEDLE_HIP_STFT=f64 (no
+ * chain to look at) and a batch the product would cut into more than one chunk are refused with InvalidArgument.
+ * Frames, pairs, chunks and items are numbered over the whole batch, stream after stream; streams[i] says where stream
+ * i's begin.  Any output pointer may be NULL.  A batch without a frame launches nothing and reports zeros. */
+typedef struct NeedleHipStageStream {
+  uint32_t frames, frame_base; /* rows [frame_base, frame_base + frames) of the chroma and energy outputs */
+  uint32_t pair_base;          /* its frame pairs: [pair_base, pair_base + ceil(frames / 2)); pair p is in chunk p / chunk_pairs */
+  uint32_t kept, kept_base;    /* its kept items: [kept_base, kept_base + kept); item k starts at the stream's frame k * step */
+  uint32_t tile_base;          /* its tiles of items_per_tile items in the certification's launch */
+} NeedleHipStageStream;
+typedef struct NeedleHipStages {
+  /* in: where to copy (NULL: not wanted) */
+  double *first_chroma;   /* [frames][12]: the first pass's rows (f32 values held as doubles), before the certification */
+  float *energy;          /* [frames][4]: its energy partials; both frames of a pair carry the pair's */
+  uint32_t *first_items;  /* [kept]: as the certification wrote them, before the fix-up */
+  uint8_t *item_listed;   /* [kept]: times the item is in the list of refused items (0 or 1) */
+  uint8_t *chunk_listed;  /* [chunks] (room for max(pairs, 1) always suffices): times the chunk is in the list (0 or 1) */
+  double *final_chroma;   /* [frames][12]: after the recomputation */
+  uint32_t *items;        /* [kept]: after the fix-up, what the product emits */
+  NeedleHipStageStream *streams; /* [num_streams] */
+  /* out */
+  uint64_t frames, pairs, kept, chunks;
+  uint64_t items_listed, chunks_listed;      /* the certification's own counters */
+  uint32_t chunk_pairs, items_per_tile;
+  uint32_t compute_units, pairs_per_block;   /* of the device; of the first pass's launch */
+  uint32_t pairs_per_xcd, blocks_per_xcd;    /* the first pass's schedule: every XCD walks its part of the pairs in */
+  uint32_t block_size[4], block_count[4];    /* block_count[k] workgroups of block_size[k] pairs, k = 0..3 in turn */
+} NeedleHipStages;
+enum NeedleError needle_hip_fingerprint_stages_debug(const int16_t *const *pcm, const size_t *num_values, size_t num_streams,
+                                                     int channels, uint32_t step, uint32_t flags, NeedleHipStages *stages);
+
 /* ---- resampler + down-mix: the step in FRONT of the path ---------------------------------------------
  * The reference converts decoded audio to s16 @ 11025 Hz with FFmpeg's swresample before feeding chromaprint
  * (analyzer.rs:180-187,231-282).  That library is out of scope and not bit-reproducible; this front-end is this

@@ -92,7 +92,7 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_host_free", "needle_hip_last_kernel_ms", "needle_hip_set_kernel_timing", "needle_hip_kernel_launches", "needle_hip_fingerprint_sample_rate",
     "needle_hip_fingerprint_delay_ms", "needle_hip_fingerprint_item_duration_ms", "needle_hip_fingerprint_num_items",
     "needle_hip_fingerprint_num_kept", "needle_hip_fingerprint_host", "needle_hip_fingerprint_device",
-    "needle_hip_fingerprint_debug", "needle_hip_resample_out_len", "needle_hip_resample_host", "needle_hip_resample_plan",
+    "needle_hip_fingerprint_debug", "needle_hip_fingerprint_stages_debug", "needle_hip_resample_out_len", "needle_hip_resample_host", "needle_hip_resample_plan",
     "needle_hip_downmix_host",
     "needle_hip_hamming_runs_device", "needle_hip_hamming_runs_host",
     "needle_hip_frame_hashes_new", "needle_hip_frame_hashes_free", "needle_hip_frame_hashes_len",
@@ -1530,6 +1530,53 @@ def fingerprint_debug(pcm: np.ndarray, channels: int = 1):
     feats = np.zeros((max(frames - 4, 1), 12))
     check(lib().needle_hip_fingerprint_debug(a.ctypes.data, a.size, channels, chroma.ctypes.data, feats.ctypes.data))
     return chroma[:frames], feats[:max(frames - 4, 0)]
+
+
+class _StageStream(C.Structure):
+    _fields_ = [(k, C.c_uint32) for k in ("frames", "frame_base", "pair_base", "kept", "kept_base", "tile_base")]
+
+
+class _Stages(C.Structure):
+    _fields_ = ([(k, C.c_void_p) for k in ("first_chroma", "energy", "first_items", "item_listed", "chunk_listed", "final_chroma",
+                                           "items", "streams")] +
+                [(k, C.c_uint64) for k in ("frames", "pairs", "kept", "chunks", "items_listed", "chunks_listed")] +
+                [(k, C.c_uint32) for k in ("chunk_pairs", "items_per_tile", "compute_units", "pairs_per_block", "pairs_per_xcd",
+                                           "blocks_per_xcd")] +
+                [("block_size", C.c_uint32 * 4), ("block_count", C.c_uint32 * 4)])
+
+
+def fingerprint_stages(pcms: Sequence[np.ndarray], channels: int = 1, step: int = 1, beside: bool = False) -> dict:
+    """needle_hip_fingerprint_stages_debug (test hook): the product's certified chain over `pcms` as one batch, and what
+    each of its kernels wrote.  Rows, pairs, chunks and items are numbered over the batch; `streams` (one dict per stream:
+    frames, frame_base, pair_base, kept, kept_base, tile_base) says where each stream's begin.  `schedule` is the first
+    pass's: per XCD part of `pairs_per_xcd` pairs, counts[k] workgroups of sizes[k] pairs, in turn."""
+    arrs = [np.ascontiguousarray(p, dtype=np.int16) for p in pcms]
+    n = len(arrs)
+    frames = [0 if a.size // channels < 4096 else (a.size // channels - 4096) // 1365 + 1 for a in arrs]
+    kept = [int(lib().needle_hip_fingerprint_num_kept(a.size // channels, step)) for a in arrs]
+    nf, nk, pairs = sum(frames), sum(kept), sum((f + 1) // 2 for f in frames)
+    out = {"first_chroma": np.zeros((max(nf, 1), 12)), "energy": np.zeros((max(nf, 1), 4), dtype=np.float32),
+           "first_items": np.zeros(max(nk, 1), dtype=np.uint32), "item_listed": np.zeros(max(nk, 1), dtype=np.uint8),
+           "chunk_listed": np.zeros(max(pairs, 1), dtype=np.uint8), "final_chroma": np.zeros((max(nf, 1), 12)),
+           "items": np.zeros(max(nk, 1), dtype=np.uint32)}
+    streams = (_StageStream * max(n, 1))()
+    st = _Stages(streams=C.addressof(streams), **{k: v.ctypes.data for k, v in out.items()})
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+    lens = (C.c_size_t * max(n, 1))(*[a.size for a in arrs])
+    lib().needle_hip_fingerprint_stages_debug.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p]
+    check(lib().needle_hip_fingerprint_stages_debug(ptrs, lens, n, channels, step, 1 if beside else 0, C.byref(st)))
+    ran = st.frames > 0
+    assert not ran or (st.frames, st.kept, st.pairs) == (nf, nk, pairs), (st.frames, st.kept, st.pairs, nf, nk, pairs)
+    rows = {"first_chroma": st.frames, "energy": st.frames, "final_chroma": st.frames, "first_items": st.kept,
+            "item_listed": st.kept, "items": st.kept, "chunk_listed": st.chunks}
+    res = {k: v[:rows[k]] for k, v in out.items()}
+    for k in ("frames", "pairs", "kept", "chunks", "items_listed", "chunks_listed", "chunk_pairs", "items_per_tile", "compute_units",
+              "pairs_per_block"):
+        res[k] = int(getattr(st, k))
+    res["streams"] = [{k: int(getattr(streams[i], k)) for k, _ in _StageStream._fields_} for i in range(n)]
+    res["schedule"] = {"pairs_per_xcd": int(st.pairs_per_xcd), "blocks_per_xcd": int(st.blocks_per_xcd),
+                       "sizes": [int(x) for x in st.block_size], "counts": [int(x) for x in st.block_count]}
+    return res
 
 
 def resample(pcms: Sequence[np.ndarray], channels: int, sample_rate: int) -> List[np.ndarray]:

@@ -576,6 +576,19 @@ enum NeedleError needle_hip_fingerprint_debug(const int16_t *pcm, size_t num_val
   });
 }
 
+enum NeedleError needle_hip_fingerprint_stages_debug(const int16_t *const *pcm, const size_t *num_values, size_t num_streams,
+                                                     int channels, uint32_t step, uint32_t flags, NeedleHipStages *stages) {
+  if (!stages || (num_streams && (!pcm || !num_values))) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const int16_t *> p(pcm, pcm + num_streams);
+    std::vector<size_t> n(num_values, num_values + num_streams);
+    for (size_t i = 0; i < num_streams; i++)
+      if (!p[i] && n[i]) return NeedleError_NullArgument;
+    Status s = gpu_fingerprint_stages_debug(p, n, channels, step, flags, stages);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
 // ============================================================================================================
 // resampler front-end
 // ============================================================================================================

@@ -215,6 +215,9 @@ Status gpu_fingerprint_feed_device(const int16_t *d_pcm, const std::vector<FeedL
                                    double *d_chroma, float *d_energy, double *d_chroma64, uint32_t *d_items,
                                    const FeedAudit *audit = nullptr);
 bool gpu_fingerprint_f64_mode();  // NEEDLE_HIP_STFT=f64: no first pass, nothing to audit
+// test hook: the certified chain of gpu_fingerprint_device over host PCM, with what each kernel wrote (needle_hip.h)
+Status gpu_fingerprint_stages_debug(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values, int channels,
+                                    uint32_t step, uint32_t flags, NeedleHipStages *out);
 
 // ---- resampler front-end (resample.hip) -------------------------------------------------------------------
 struct ResampleSpan {

@@ -334,6 +334,31 @@ Status plan_feed(const std::vector<FeedLane> &lanes, int channels, uint32_t step
   return Status::Ok();
 }
 
+// ---- taps (test hook) --------------------------------------------------------------------------------------------------
+// needle_hip_fingerprint_stages_debug: a certified call that is given taps fills its chroma and energy rows with a NaN
+// bit pattern in front of the first pass and copies, device to device and in stream order BETWEEN the launches it makes
+// anyway, what each of its four kernels wrote.  No launch, grid or argument differs from the call without taps, except
+// that `beside` picks the listed kernel's other form and that a batch without a single kept item still runs its first pass.
+struct FpTaps {
+  bool beside = false;  // in: the recomputation in the form that fits beside a first pass (stft_variant(channels, true, true))
+  DeviceBuffer<double> first_chroma, final_chroma;  // [frames][12] behind the first pass / behind the recomputation
+  DeviceBuffer<float> energy;                       // [frames][kEnergyParts] behind the first pass
+  DeviceBuffer<uint32_t> first_items;               // [kept] behind the certification, in front of the fix-up
+  DeviceBuffer<uint32_t> ctl, chunk_list;           // the control block (CertLayout) and the chunk list behind the certification
+  DeviceBuffer<CertItem> item_list;
+  std::vector<FpStream> streams;                    // the call's one chunk, as plan_chunk numbered it
+  uint64_t frames = 0, pairs = 0, kept = 0, nchunks = 0;
+  size_t ctl_words = 0;
+  uint32_t items_per_tile = 0, pairs_per_block = 0;
+  Stft32Schedule schedule;
+  bool ran = false;  // false: a batch without a frame, nothing was launched
+};
+template <typename T>
+Status tap_copy(T *dst, const T *src, uint64_t count, hipStream_t stream) {
+  if (count) NEEDLE_HIP_TRY(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToDevice, stream));
+  return Status::Ok();
+}
+
 // ---- launches ----------------------------------------------------------------------------------------------------------
 // what every launch of a call is given
 struct Job {
@@ -420,6 +445,7 @@ struct CertChain {
   bool beside;           // the recomputation in the form that fits beside the next job's first pass
   uint32_t *zero_word;   // cleared by the fix-up, or nullptr
   uint64_t count_chunks; // added to the chunks the recomputed ones are a fraction of
+  FpTaps *taps = nullptr;  // test hook: copies between the launches (FpTaps); the product passes none
 };
 Status enqueue_certified(const Job &j, FpWorkspace *ws, const CertChain &c, bool *zeroed) {
   hipStream_t stream = j.stream;
@@ -429,9 +455,18 @@ Status enqueue_certified(const Job &j, FpWorkspace *ws, const CertChain &c, bool
     NEEDLE_HIP_TRY(hipMemsetAsync(ws->stats, 0, sizeof(CertStats), stream));
   }
   CertWork *work = CertLayout::work(c.first.ctl);
+  FpTaps *tap = c.taps;
+  Status ts;
+  if (tap) {  // a row no kernel writes stays a NaN
+    NEEDLE_HIP_TRY(hipMemsetAsync(c.first.chroma, 0xFF, tap->frames * kBands * sizeof(double), c.first.on));
+    NEEDLE_HIP_TRY(hipMemsetAsync(c.first.energy, 0xFF, tap->frames * stft::kEnergyParts * sizeof(float), c.first.on));
+  }
   if (c.first.table.pairs) {
     Status s = enqueue_first_pass(j, c.first);
     if (!s.ok()) return s;
+    if (tap && (!(ts = tap_copy(tap->first_chroma.ptr, c.first.chroma, tap->frames * kBands, c.first.on)).ok() ||
+                !(ts = tap_copy(tap->energy.ptr, c.first.energy, tap->frames * stft::kEnergyParts, c.first.on)).ok()))
+      return ts;
   } else {
     NEEDLE_HIP_TRY(hipMemsetAsync(c.first.ctl, 0, c.first.ctl_words * sizeof(uint32_t), stream));
   }
@@ -451,11 +486,16 @@ Status enqueue_certified(const Job &j, FpWorkspace *ws, const CertChain &c, bool
                          c.first.energy, c.tail.streams, c.tail.n, j.tab.thr, j.step, j.items_per_tile, j.d_items, (uint32_t)c.tiles,
                          cert_k(), kChunkPairs, work, CertLayout::bitmap(c.first.ctl), c.bufs->chunk_list.ptr, c.bufs->item_list.ptr);
     }
+    if (tap && (!(ts = tap_copy(tap->first_items.ptr, j.d_items, tap->kept, stream)).ok() ||
+                !(ts = tap_copy(tap->chunk_list.ptr, c.bufs->chunk_list.ptr, tap->nchunks, stream)).ok() ||
+                !(ts = tap_copy(tap->item_list.ptr, c.bufs->item_list.ptr, tap->kept, stream)).ok()))
+      return ts;
     {
       KernelTimer timer("stft_fallback");
       launch_stft_chroma(j, stft_variant(j.channels, true, c.beside), c.fallback_grid, c.tail, c.recomputed, kChunkPairs,
                          stft::ChunkList{c.bufs->chunk_list.ptr, &work->chunk_count});
     }
+    if (tap && !(ts = tap_copy(tap->final_chroma.ptr, c.recomputed, tap->frames * kBands, stream)).ok()) return ts;
     if (pp) NEEDLE_HIP_TRY(hipEventRecord(pp->recomputed, stream));
 #ifndef NEEDLE_LAB_NO_FIXUP   // (timing laboratory, WRONG results: the job without the fix-up's dispatch -- the most that folding it into the recomputation kernel could save)
     {
@@ -470,7 +510,10 @@ Status enqueue_certified(const Job &j, FpWorkspace *ws, const CertChain &c, bool
       pp->consumed_valid = true;
     }
     ws->items_total += c.kept;
+  } else if (tap && !(ts = tap_copy(tap->final_chroma.ptr, c.recomputed, tap->frames * kBands, stream)).ok()) {
+    return ts;  // (no item: the first pass's rows are the call's last)
   }
+  if (tap && !(ts = tap_copy(tap->ctl.ptr, c.first.ctl, tap->ctl_words, stream)).ok()) return ts;  // nothing behind the certification writes it
   NEEDLE_HIP_TRY(hipGetLastError());
   return Status::Ok();
 }
@@ -565,11 +608,10 @@ Status begin_call(int channels, uint32_t step, FpTables *tab) {
   return Status::Ok();
 }
 
-}  // namespace
-
-Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan> &spans, int channels,
-                              uint32_t step, uint32_t *d_items, bool sync, double *d_chroma_dbg,
-                              double *d_feat_dbg, size_t descriptor_slot, int pipe, uint32_t *zero_word, bool *zeroed_out) {
+// gpu_fingerprint_device, and the same call with taps (gpu_fingerprint_stages_debug)
+Status fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan> &spans, int channels, uint32_t step, uint32_t *d_items,
+                          bool sync, double *d_chroma_dbg, double *d_feat_dbg, size_t descriptor_slot, int pipe, uint32_t *zero_word,
+                          bool *zeroed_out, FpTaps *taps) {
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
   bool zeroed = false;  // *zero_word was cleared by the LAST kernel enqueued here (only then is it still zero for the caller)
   if (zeroed_out) *zeroed_out = false;
@@ -589,15 +631,17 @@ Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan
   // The f64 kernel over everything also when a caller asks for the intermediate stages
   const bool separate = d_feat_dbg != nullptr || getenv("NEEDLE_HIP_SEPARATE_CLASSIFY") != nullptr;
   const bool certifiable = !f64_mode() && d_chroma_dbg == nullptr && !separate;
+  if (taps && !certifiable) return Status::Make(NeedleError_InvalidArgument, "fingerprint: the stages of the certified chain were asked for, and this call does not run it");
   size_t begin = 0, chunk = descriptor_slot;
   while (begin < spans.size()) {
     ChunkPlan plan;
     if (!(s = plan_chunk(spans, begin, channels, step, items_per_tile, max_frames, &plan)).ok()) return s;
     const bool whole = begin == 0 && plan.end == spans.size();
+    if (taps && !whole) return Status::Make(NeedleError_InvalidArgument, "fingerprint: the stages of a batch of more than one chunk were asked for");
     begin = plan.end;
     const uint64_t frames = plan.frames, pairs = plan.pairs, tiles = plan.tiles;
     if (frames == 0) continue;
-    const bool certified = certifiable && tiles > 0;
+    const bool certified = certifiable && (tiles > 0 || taps);
     // Pipelined call (pipe 0 / 1) small enough to be ONE chunk, with a CU-masked stream available: its f32 STFT goes
     // to that stream and its own workspace; otherwise everything stays on the library stream.
     hipStream_t stft = certified && (pipe == 0 || pipe == 1) && whole && frames <= (1u << 21) ? stft_stream() : nullptr;
@@ -635,13 +679,26 @@ Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan
       // A pipelined call runs BESIDE the next call's first pass (shared-CU overlap): then the 168-VGPR form, whose
       // workgroup fits the hole one retiring first-pass workgroup leaves (the 229-VGPR form needs two and waited a whole
       // first pass for them), on a quarter of the workgroups (each holds its slot for its whole, latency-bound life).
-      const bool beside = pp != nullptr && share_mode() == 2 && stft_stream() != nullptr;
+      const bool beside = (pp != nullptr && share_mode() == 2 && stft_stream() != nullptr) || (taps && taps->beside);
       uint32_t grid = (uint32_t)std::min<uint64_t>((beside ? 1ull : 4ull) * cus / 2, layout.nchunks);
       if (const char *e = getenv("NEEDLE_HIP_FALLBACK_GRID")) grid = (uint32_t)std::min<uint64_t>((uint64_t)std::max(1, atoi(e)), layout.nchunks);  // tuning
       const FirstPass first{table, stft32_schedule(pairs, ppb, (slots + 7) / 8, guided > 0, (uint32_t)std::max(guided, 1)),
                             chroma_buf.ptr, bufs.energy.ptr, bufs.ctl.ptr, (uint32_t)layout.ctl_words, pp ? stft : stream, pp, true};
+      if (taps) {
+        taps->streams = plan.streams;
+        taps->frames = frames, taps->pairs = pairs, taps->kept = plan.kept, taps->nchunks = layout.nchunks;
+        taps->ctl_words = layout.ctl_words;
+        taps->items_per_tile = items_per_tile, taps->pairs_per_block = ppb;
+        taps->schedule = first.schedule;
+        taps->ran = true;
+        if (!(s = taps->first_chroma.reserve(frames * kBands)).ok() || !(s = taps->final_chroma.reserve(frames * kBands)).ok() ||
+            !(s = taps->energy.reserve(frames * stft::kEnergyParts)).ok() || !(s = taps->first_items.reserve(plan.kept)).ok() ||
+            !(s = taps->item_list.reserve(plan.kept)).ok() || !(s = taps->ctl.reserve(layout.ctl_words)).ok() ||
+            !(s = taps->chunk_list.reserve(layout.nchunks)).ok())
+          return s;
+      }
       if (!(s = enqueue_certified(job, ws, CertChain{first, table, tiles, plan.kept, false, chroma_buf.ptr, &bufs, grid, beside,
-                                                     zero_word, layout.nchunks}, &zeroed)).ok())
+                                                     zero_word, layout.nchunks, taps}, &zeroed)).ok())
         return s;
       continue;
     }
@@ -672,6 +729,99 @@ Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan
   }
   if (zeroed_out) *zeroed_out = zeroed;
   if (sync) NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  return Status::Ok();
+}
+
+}  // namespace
+
+Status gpu_fingerprint_device(const int16_t *d_pcm, const std::vector<StreamSpan> &spans, int channels,
+                              uint32_t step, uint32_t *d_items, bool sync, double *d_chroma_dbg,
+                              double *d_feat_dbg, size_t descriptor_slot, int pipe, uint32_t *zero_word, bool *zeroed_out) {
+  return fingerprint_device(d_pcm, spans, channels, step, d_items, sync, d_chroma_dbg, d_feat_dbg, descriptor_slot, pipe, zero_word,
+                            zeroed_out, nullptr);
+}
+
+// Test hook (include/needle_hip.h needle_hip_fingerprint_stages_debug): host PCM into an arena of its own, the product's
+// certified chain over it as ONE chunk with taps, and what the taps hold copied to the host.
+Status gpu_fingerprint_stages_debug(const std::vector<const int16_t *> &pcm, const std::vector<size_t> &num_values, int channels,
+                                    uint32_t step, uint32_t flags, NeedleHipStages *out) {
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  if (flags & ~1u) return Status::Make(NeedleError_InvalidArgument, "fingerprint: unknown stage flags");
+  if (channels != 1 && channels != 2) return Status::Make(NeedleError_InvalidArgument, "fingerprint: channels must be 1 or 2");
+  if (step == 0) return Status::Make(NeedleError_InvalidArgument, "fingerprint: step must be >= 1");
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  const size_t n = pcm.size();
+  std::vector<StreamSpan> spans(n);
+  uint64_t values = 0, kept = 0;
+  for (size_t i = 0; i < n; i++) {  // streams 16-byte aligned in the arena and items back to back, as fingerprint_in_batches lays them
+    spans[i] = StreamSpan{values, num_values[i], kept};
+    values += (num_values[i] + 7) & ~(uint64_t)7;
+    kept += num_kept(num_values[i] / (size_t)channels, step);
+  }
+  DeviceBuffer<int16_t> d_pcm;
+  DeviceBuffer<uint32_t> d_items;
+  if (!(s = d_pcm.reserve(std::max<uint64_t>(values, 1))).ok() || !(s = d_items.reserve(std::max<uint64_t>(kept, 1))).ok()) return s;
+  for (size_t i = 0; i < n; i++)
+    if (num_values[i]) NEEDLE_HIP_TRY(hipMemcpy(d_pcm.ptr + spans[i].pcm_off, pcm[i], num_values[i] * sizeof(int16_t), hipMemcpyHostToDevice));
+  FpTaps taps;
+  taps.beside = (flags & 1u) != 0;
+  if (!(s = fingerprint_device(d_pcm.ptr, spans, channels, step, d_items.ptr, true, nullptr, nullptr, 0, -1, nullptr, nullptr, &taps)).ok())
+    return s;
+  out->frames = out->pairs = out->kept = out->chunks = out->items_listed = out->chunks_listed = 0;
+  out->chunk_pairs = kChunkPairs;
+  out->items_per_tile = taps.items_per_tile;
+  out->pairs_per_block = taps.pairs_per_block;
+  out->compute_units = (uint32_t)device_cu_count();
+  out->pairs_per_xcd = out->blocks_per_xcd = 0;
+  for (int k = 0; k < 4; k++) out->block_size[k] = 0, out->block_count[k] = 0;
+  if (out->streams)
+    for (size_t i = 0; i < n; i++) out->streams[i] = NeedleHipStageStream{0, 0, 0, 0, 0, 0};
+  if (!taps.ran) return Status::Ok();  // not one frame in the batch
+  out->frames = taps.frames, out->pairs = taps.pairs, out->kept = taps.kept, out->chunks = taps.nchunks;
+  out->pairs_per_xcd = taps.schedule.pairs_per_xcd, out->blocks_per_xcd = taps.schedule.blocks_per_xcd;
+  for (int k = 0; k < 4; k++) out->block_size[k] = taps.schedule.size[k];
+  for (int k = 0; k < 3; k++) out->block_count[k] = taps.schedule.count[k];
+  out->block_count[3] = taps.schedule.blocks_per_xcd - (taps.schedule.count[0] + taps.schedule.count[1] + taps.schedule.count[2]);
+  if (out->streams)
+    for (size_t i = 0; i < n; i++) {
+      const FpStream &m = taps.streams[i];
+      out->streams[i] = NeedleHipStageStream{m.frames, m.frame_base, m.pair_base, m.kept, m.kept_base, m.tile_base};
+    }
+  auto download = [](auto *dst, const auto *src, uint64_t count) -> Status {
+    if (dst && count) NEEDLE_HIP_TRY(hipMemcpy(dst, src, count * sizeof(*dst), hipMemcpyDeviceToHost));
+    return Status::Ok();
+  };
+  if (!(s = download(out->first_chroma, taps.first_chroma.ptr, taps.frames * kBands)).ok() ||
+      !(s = download(out->energy, taps.energy.ptr, taps.frames * stft::kEnergyParts)).ok() ||
+      !(s = download(out->final_chroma, taps.final_chroma.ptr, taps.frames * kBands)).ok() ||
+      !(s = download(out->first_items, taps.first_items.ptr, taps.kept)).ok() || !(s = download(out->items, d_items.ptr, taps.kept)).ok())
+    return s;
+  // the two lists as counts per item and per chunk: 1 where listed, and more than 1 would be a double listing
+  std::vector<uint32_t> ctl(taps.ctl_words), chunk_list(taps.nchunks);
+  std::vector<CertItem> item_list(taps.kept);
+  if (!(s = download(ctl.data(), taps.ctl.ptr, taps.ctl_words)).ok() || !(s = download(chunk_list.data(), taps.chunk_list.ptr, taps.nchunks)).ok() ||
+      !(s = download(item_list.data(), taps.item_list.ptr, taps.kept)).ok())
+    return s;
+  const CertWork *work = CertLayout::work(ctl.data());
+  const uint32_t *bitmap = CertLayout::bitmap(ctl.data());
+  if (work->item_count > taps.kept || work->chunk_count > taps.nchunks)
+    return Status::Make(NeedleError_Unknown, "fingerprint: the certification listed more items or chunks than there are");
+  out->items_listed = work->item_count, out->chunks_listed = work->chunk_count;
+  std::vector<uint8_t> per_item(taps.kept, 0), per_chunk(taps.nchunks, 0);
+  for (uint32_t i = 0; i < work->item_count; i++) {
+    if (item_list[i].out >= taps.kept) return Status::Make(NeedleError_Unknown, "fingerprint: a listed item lies outside the batch");
+    if (per_item[item_list[i].out] < 255) per_item[item_list[i].out]++;
+  }
+  for (uint32_t i = 0; i < work->chunk_count; i++) {
+    if (chunk_list[i] >= taps.nchunks) return Status::Make(NeedleError_Unknown, "fingerprint: a listed chunk lies outside the batch");
+    if (per_chunk[chunk_list[i]] < 255) per_chunk[chunk_list[i]]++;
+  }
+  for (uint64_t c = 0; c < taps.nchunks; c++)
+    if (((bitmap[c >> 5] >> (c & 31u)) & 1u) != (per_chunk[c] ? 1u : 0u))
+      return Status::Make(NeedleError_Unknown, "fingerprint: the chunk bitmap and the chunk list disagree");
+  if (out->item_listed && taps.kept) std::memcpy(out->item_listed, per_item.data(), taps.kept);
+  if (out->chunk_listed && taps.nchunks) std::memcpy(out->chunk_listed, per_chunk.data(), taps.nchunks);
   return Status::Ok();
 }
 
