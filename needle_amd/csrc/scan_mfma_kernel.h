@@ -1,5 +1,7 @@
 // The sampled scan's first stage on the matrix pipe (round 5; FP4 products since the second half of that round).  Included
-// by search.hip inside its anonymous namespace, after SearchProblem, mfma_windows() and the mfma_v4i / _v8i / _v16f types.
+// by search.hip inside its anonymous namespace, after the mfma_v4i / _v8i / _v16f types.  SearchProblem, mfma_windows() and
+// the geometry that decides what fits a workgroup (kM2Members, kM2Pitch, the kCtl* table, m2_lds_words(), ...) are scan_plan.h's,
+// shared with the host's planner; search.hip includes it at file scope, ahead of this file.
 //
 // Same aligned windows, same candidates and same runs as hamming_runs_sampled_kernel (comparator.rs:176-200 is what all of
 // them reproduce).  The Hamming distances of a window's head rows against every destination position are matrix products:
@@ -36,7 +38,7 @@
 //    windows (A image rows + sixteen hashes each) are built once per launch (m2_window_images_kernel) and copied in; an A
 //    fragment read serves both column blocks of a unit; waves take units from a counter in LDS, so none idles while another
 //    still has units; a workgroup finds its group with one load (round 4: a binary search of the table, 17 dependent loads).
-//  * Default shape (mfma_waves(), search.hip): workgroups of 8 waves, two per CU, four waves per SIMD, ~100 registers, one
+//  * Default shape (ScanSwitches::mfma_waves, scan_plan.h): workgroups of 8 waves, two per CU, four waves per SIMD, ~100 registers, one
 //    accumulator pair, a tile folded before the next is multiplied.  Measured against it: 16 waves x 1 (3.2 against 2.8 ms
 //    at 79 800 pairs of 45-minute windows), 12 x 1 and 4 x 3 (slower still).
 //  * Columns outside the table get all-zero B fragments and rows beyond the last window read a row of zeros
@@ -55,47 +57,16 @@ __device__ unsigned long long m2_dbg[8];
 #define M2_COUNT(i) do { } while (0)
 #define M2_COUNT_LANES(i, n) do { } while (0)
 #endif
-constexpr int kM2Heads = 4;
-#ifndef NEEDLE_M2_MEMBERS
-#define NEEDLE_M2_MEMBERS 12
-#endif
-constexpr int kM2Members = NEEDLE_M2_MEMBERS; // sources a workgroup takes at most (of one destination; its share of the CU's LDS decides: nine 24-minute
-                                              // windows, four 45-minute ones); < 16: a window's member rides in 4 bits.  (8 until round 6: the ninth -- room
-                                              // made by a run buffer of 32 instead of 64 -- is 2.2 % at 39 060 pairs of 24-minute windows: one more pair per setup,
-                                              // 98 instead of 94 % of the row tiles' rows in use)
-constexpr int kM2Pitch = kM2Heads * 4 + 4;    // words of a window's row in the A image: 4 x 32 FP4 nibbles of +-1, the window's member << 28 | w0, 3 spare
-                                              // (20: sixteen lanes' 16-byte reads of one instruction fall into sixteen different groups of four banks)
-#ifndef NEEDLE_M2_RUNBUF
-#define NEEDLE_M2_RUNBUF 32
-#endif
-constexpr int kM2RunBuf = NEEDLE_M2_RUNBUF;   // runs a workgroup collects in LDS before it asks for room in the run list (one atomic)
+#include "scan_plan.h"                        // (a no-op here: see above)
 #ifndef NEEDLE_M2_OVERFLOW
 #define NEEDLE_M2_OVERFLOW 16                  // (0: measurements -- one atomic per run beyond the workgroup's buffer, as before round 6)
 #endif
-constexpr int kM2Overflow = NEEDLE_M2_OVERFLOW;  // ... and beyond those, runs a WAVE collects before it asks (round 6: stretches of one repeated hash --
+constexpr int kM2Overflow = NEEDLE_M2_OVERFLOW;  // beyond the workgroup's kM2RunBuf, runs a WAVE collects before it asks (round 6: stretches of one repeated hash --
                                               // silence against silence -- give a workgroup thousands of runs; one returning atomic per run on the
                                               // list's one counter was 46 of 52 ms at 39 060 pairs of the hostile corpus, 4.65 M runs).  They lie in the
                                               // 64 words of the wave's item queue whose items process() has just taken: no LDS of their own (a buffer of
                                               // 4 KB per workgroup cost 45-minute windows a source per workgroup and the scan 6 %)
-constexpr int kM2Table = 256;                 // a byte of hash bits -> its eight FP4 nibbles (bit set: +1 = 0x2, clear: -1 = 0xA)
-constexpr int kM2Probe = 4;                   // rows looked at on either side of a whole window
-constexpr int kM2Rows = kSampleW + 2 * kM2Probe;  // source hashes kept per window: its W rows and four probes on either side (m2_probe_offset)
-constexpr int kM2ColBlocks = 2;               // column blocks of 32 positions a wave takes per unit
 constexpr int kM2Batch = 4;                   // row tiles (x 2 column blocks = 8 tiles = 32 flag bits) between two looks at the flags
-constexpr int kM2Queue = 128;                 // items a wave can hold: < 64 waiting + the <= 64 one turn adds
-// The workgroup's control words (one table in LDS)
-constexpr int kCtlUnits = 0;                              // units handed out
-constexpr int kCtlRows = 1;                               // [+ g] first row (window) of member g; [+ members]: all rows
-constexpr int kCtlSrc = kCtlRows + kM2Members + 1;        // [+ g] member g's source offset in the hash arena
-constexpr int kCtlLen = kCtlSrc + kM2Members;             // [+ g] its length
-constexpr int kCtlImage = kCtlLen + kM2Members;           // [+ g] first window of its image
-constexpr int kCtlRuns = kCtlImage + kM2Members;          // runs collected in the workgroup's buffer
-constexpr int kCtlSlot = kCtlRuns + 1;                    // their first slot in the run list
-constexpr int kCtlTaken = kCtlSlot + 1;                   // chain queue: chains taken,
-constexpr int kCtlPushed = kCtlTaken + 1;                 // chains pushed,
-constexpr int kCtlLock = kCtlPushed + 1;                  // its lock
-constexpr int kCtlThrough = kCtlLock + 1;                 // waves that have flushed their items
-constexpr int kM2CtlWords = (kCtlThrough + 1 + 3) & ~3;   // (a multiple of 4: what follows stays 16-byte aligned)
 // The workgroup's CHAIN QUEUE (round 6).  The chains of a destination's intro against its eight or nine sources end within one
 // or two column units: ONE wave found them all and resolved them one after the other, a trip to global memory each.  While the
 // workgroup has units to hand out that costs nothing (the other waves take them); near its end the other seven ran out of
@@ -110,11 +81,6 @@ constexpr int kM2CtlWords = (kCtlThrough + 1 + 3) & ~3;   // (a multiple of 4: w
 #define NEEDLE_M2_LATE_UNITS 2
 #endif
 constexpr int kM2LateUnits = NEEDLE_M2_LATE_UNITS;
-#ifndef NEEDLE_M2_CHAINS
-#define NEEDLE_M2_CHAINS 32
-#endif
-constexpr int kM2Chains = NEEDLE_M2_CHAINS;   // entries of the ring
-static_assert((kM2Chains & (kM2Chains - 1)) == 0, "");
 #ifndef NEEDLE_M2_CROWD
 #define NEEDLE_M2_CROWD 4
 #endif
@@ -137,29 +103,17 @@ __host__ __device__ constexpr int m2_probe_offset(int s, int min_len) {
 __host__ __device__ constexpr int m2_row_offset(int s, int min_len) { return s >= 0 && s < kSampleW ? s : m2_probe_offset(s, min_len); }
 static_assert(m2_probe_offset(-1, 23) == -1 && m2_probe_offset(-4, 23) == -8 && m2_probe_offset(8, 67) == 8 && m2_probe_offset(11, 67) == 37, "");
 
-// LDS words of a workgroup: staged destination (+ 64 zeros), tables, per-window source hashes, A image
-__host__ __device__ constexpr size_t m2_round4(size_t x) { return (x + 3) & ~(size_t)3; }
-__host__ __device__ constexpr size_t m2_lds_words(uint64_t m, uint64_t windows, int waves) {
-  return m2_round4(m + 64) + kM2CtlWords + kM2Table + 4 * kM2RunBuf + 2 * kM2Chains + (size_t)waves * kM2Queue + (size_t)(windows + 1) * (kM2Pitch + kM2Rows);
-}
-
 // A source sequence's windows as a workgroup wants them in LDS -- per window kM2Pitch words of the A image (its four head
 // hashes as 32 negated +-1 nibbles each, then w0) and kM2Rows source hashes around it -- built ONCE per launch in global
 // memory (m2_window_images_kernel) instead of by every workgroup that takes the sequence as a source: at 2000 videos a
 // sequence is a source 1999 times, and gathering + expanding its windows was a tenth of the scan (a workgroup's setup
 // alone: 0.44 of 4.0 ms at 79 800 pairs).  A workgroup copies its members' images with 16-byte loads.
-constexpr int kM2ImageWords = kM2Pitch + kM2Rows;   // per window
 // the eight low bits of x as FP4 (e2m1) nibbles: bit i set -> +1.0 (0x2), clear -> -1.0 (0xA), in nibble i
 __host__ __device__ constexpr uint32_t m2_nibbles(uint32_t x) {
   uint32_t w = 0;
   for (int i = 0; i < 8; i++) w |= (((x >> i) & 1u) ? 0x2u : 0xAu) << (4 * i);
   return w;
 }
-struct M2ImageSeq {
-  uint32_t src_off, n;     // the sequence in the hash arena
-  uint32_t first_window;   // of its image, in windows
-  uint32_t windows;
-};
 template <int W>
 __global__ __launch_bounds__(256) void m2_window_images_kernel(const uint32_t *__restrict__ hashes, const M2ImageSeq *__restrict__ seqs,
                                                                int num_seqs, uint32_t total_windows, uint32_t min_len,
@@ -205,14 +159,14 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(PER_
   constexpr int H = kM2Heads, HP = H / 2, PITCH = kM2Pitch, STRIDE = kM2ImageWords, CB = kM2ColBlocks, E = kM2Probe, NR = kM2Rows;
   extern __shared__ uint32_t lds[];
   __builtin_amdgcn_s_setprio(3);
-  // Which group: workgroup / splits.  Its first entry's index lies in the pad field (bits 8 .. 30) of the table entry whose
-  // POSITION is the group's number (build_plan) -- one load, not a binary search of the table (17 dependent trips to
+  // Which group: workgroup / splits.  Its first entry's index lies in the directory field of the table entry whose
+  // POSITION is the group's number (scan_plan.h) -- one load, not a binary search of the table (17 dependent trips to
   // global memory at 80 000 pairs: half the life of a workgroup of 24-minute windows).
   const int group = (int)(blockIdx.x / (uint32_t)splits);
-  const int lo = (int)((problems[group].pad >> 8) & 0x7FFFFFu);
+  const int lo = (int)pad_directory(problems[group].pad);
   (void)num_problems;
   const SearchProblem pr = problems[lo];
-  const int members = min((int)(pr.pad & 0xFFu), kM2Members - 1) + 1;  // pad of a group's first entry: how many followers (build_plan)
+  const int members = min((int)pad_followers(pr.pad), kM2Members - 1) + 1;  // a group's first entry says how many followers it has
   const int m = (int)pr.m, min_len = (int)pr.min_len;
   const int P = min_len - W + 1;
   const uint32_t *__restrict__ dst = hashes + pr.dst_off;
@@ -248,7 +202,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(PER_
       ctl[kCtlRows + g] = (uint32_t)rows;
       ctl[kCtlSrc + g] = problems[lo + g].src_off;
       ctl[kCtlLen + g] = problems[lo + g].n;
-      ctl[kCtlImage + g] = problems[lo + g].block_base;
+      ctl[kCtlImage + g] = image_first_window(problems[lo + g]);
       rows += mfma_windows((int)problems[lo + g].n, min_len, W);
     }
     ctl[kCtlRows + members] = (uint32_t)rows;
@@ -270,8 +224,8 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(PER_
   }
   __syncthreads();
   if (images != nullptr) {
-    // the members' window images, built once per launch (m2_window_images_kernel): SearchProblem::block_base of an entry =
-    // first window of its source's image.  16-byte pieces: 9 of a window's A-image row, 4 of its source hashes.
+    // the members' window images, built once per launch (m2_window_images_kernel): image_first_window() of an entry says
+    // where its source's begins.  16-byte pieces: 9 of a window's A-image row, 4 of its source hashes.
     constexpr int kPieces = kM2ImageWords / 4;
     static_assert(kM2ImageWords % 4 == 0 && PITCH % 4 == 0, "");
     constexpr int kU = 4;                         // pieces in flight per thread
@@ -676,7 +630,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(PER_
   // (ONE call site, and one of process() inside: the rare paths' code, inlined at three sites each, had grown to where the
   // waves waited for instructions -- the same head tests took 0.12 instead of 0.08 ms.  flush: the wave's last call.)
   auto enqueue = [&](uint32_t flags, const int rt0, const int unit, const bool flush) __attribute__((always_inline)) {
-    // (unit < 32768 and rt0 / kM2Batch < 64: m < 65536 and fewer than 8192 windows per group -- search.hip build_plan stages nothing else)
+    // (unit < 32768 and rt0 / kM2Batch < 64: m < 65536 and fewer than 8192 windows per group -- scan_plan.h m2_packable(): nothing else is staged)
     const uint32_t mine = ((uint32_t)unit << 17) | ((uint32_t)(rt0 / kM2Batch) << 11) | ((uint32_t)lane << 5);
     for (;;) {
       const bool act = flags != 0u;

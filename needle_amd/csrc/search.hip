@@ -12,6 +12,7 @@
 // Integer-only (xor, popcount, compare, add): results are exact by construction.
 #include "epilogue.h"
 #include "hipctx.h"
+#include "scan_plan.h"
 #include "simhash_wave.h"
 
 #include <algorithm>
@@ -19,19 +20,17 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <climits>
+#include <map>
 #include <mutex>
-#include <unordered_map>
+#include <set>
 
 namespace needle {
 
 namespace {
 
-constexpr int kDiagsPerBlock = 256;
-constexpr int kBandR = 7, kBandU = 3;          // band kernel: 7 diagonals per lane, checkpoint every 21 rows
-constexpr int kBandB = 64 * kBandR;
-constexpr int kSampleW = 8;                     // sampled kernel: rows per aligned window
-constexpr int kSampleHead = 3;                  // rows of a window evaluated before the first early-out
-// Which rows: the first, a middle and the last one of the window.  Neighbouring rows of a diagonal are correlated in
+// (The scan's shape constants, its table entry SearchProblem and its launch plan: scan_plan.h.)
+// Which rows of a window are its head rows (kSampleHead of kSampleW): the first, a middle and the last one of the window.  Neighbouring rows of a diagonal are correlated in
 // audio (a note lasts several hashes): between unrelated synthetic episodes three CONSECUTIVE cells all match with
 // probability 0.7 %, the cells of rows {0, W/2, W-1} with 0.15 % -- 4.5 times fewer diagonals to finish afterwards.
 // H head rows of a window of W: H = 3 (the default) takes rows {0, W/2, W-1}; other counts are spread evenly over the
@@ -54,14 +53,6 @@ __host__ __device__ constexpr int tail_row(int k, int W, int H = kSampleHead) {
   }
   return W - 1;
 }
-
-struct SearchProblem {
-  uint32_t src_off, n;  // hash arena offset + length of the source sequence
-  uint32_t dst_off, m;
-  uint32_t min_len, tag;
-  uint32_t block_base;  // first workgroup of this problem in the grid
-  uint32_t pad;
-};
 
 // One workgroup = 256 consecutive diagonals of one problem; both sequences staged in LDS.
 // STAGED = false: the sequences are read where they lie in HBM (lanes of a wave read consecutive destination hashes,
@@ -536,9 +527,6 @@ __global__ __launch_bounds__(256) void hamming_runs_sampled_kernel(const uint32_
 // The same aligned windows, the same head test and the same candidates as hamming_runs_sampled_kernel, with the first stage
 // as int8 matrix products: scan_mfma_kernel.h (round 5; round 4's form -- one product per head row, OR of the four results,
 // survivors queued -- is in the history: commit 76713c3, and what was measured on the way in profiles/NOTES.md).
-__host__ __device__ constexpr int mfma_windows(int n, int min_len, int W) {
-  return (n - 1 - W) >= 0 && min_len - W + 1 > 0 ? (n - 1 - W) / (min_len - W + 1) + 1 : 0;  // w0 = 1 + k P, w0 + W - 1 <= n - 1
-}
 typedef int mfma_v4i __attribute__((ext_vector_type(4)));
 typedef int mfma_v8i __attribute__((ext_vector_type(8)));
 typedef float mfma_v16f __attribute__((ext_vector_type(16)));
@@ -582,8 +570,6 @@ __global__ __launch_bounds__(256) void simhash_runs_kernel(const uint32_t *__res
   }
 }
 
-// What a launch needs besides its inputs: the device descriptors, the grid and the kernel choice.  Kept with the
-// inputs it was derived from, so that a job that is run again (a library has ~n^2 / 2 pairs) rebuilds nothing.
 // The sampled scan's window shape: rows per aligned window W and head rows H.  (8, 3) unless NEEDLE_HIP_SCAN_SHAPE="W,H"
 // names another of the instantiated ones (tools/scan_shape_sweep.py; every shape tests the same cells of a candidate
 // and emits the same runs -- the shapes differ in how many cells they look at before giving a window up).
@@ -603,6 +589,9 @@ ScanShape scan_shape() {
 }
 using SampledKernel = void (*)(const uint32_t *, const SearchProblem *, int, uint32_t, NeedleHipRun *, uint32_t, uint32_t *, int, int,
                                unsigned long long *);
+// The instantiated shapes.  (8, 3), the default, is not in the list below: it alone has both forms, the one that finishes
+// survivors from registers and the LEGACY one (`legacy`: NEEDLE_HIP_SPARSE_MAX is set); every other shape is a tuning run
+// and has the LEGACY form only.
 template <bool COUNT>
 SampledKernel sampled_kernel(ScanShape sh, bool legacy) {
 #define NEEDLE_SHAPE(W_, H_) \
@@ -610,35 +599,8 @@ SampledKernel sampled_kernel(ScanShape sh, bool legacy) {
   NEEDLE_SHAPE(4, 2) NEEDLE_SHAPE(4, 3) NEEDLE_SHAPE(8, 2) NEEDLE_SHAPE(8, 4) NEEDLE_SHAPE(16, 2) NEEDLE_SHAPE(16, 3) NEEDLE_SHAPE(16, 4)
 #undef NEEDLE_SHAPE
   if (legacy) return hamming_runs_sampled_kernel<kBandR, kSampleW, COUNT, kSampleHead, true>;
-  return hamming_runs_sampled_kernel<kBandR, kSampleW, COUNT, kSampleHead, false>;   // (the other shapes are tuning runs: LEGACY form)
+  return hamming_runs_sampled_kernel<kBandR, kSampleW, COUNT, kSampleHead, false>;
 }
-
-struct SearchPlan {
-  std::vector<NeedleHipSeq> seqs;          // inputs ...
-  std::vector<NeedleHipProblem> problems;
-  int mode[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // ... and the switches that steer the choice ([3]: threshold beyond the sampled kernel's bit trick,
-                                           // [4]: the sampled path's first stage on the matrix pipe, [5]: LDS limit of a staged pair in bytes
-                                           // (NEEDLE_HIP_SEARCH_LDS_LIMIT), [6]: the matrix-pipe form's waves per workgroup, [7]: its test
-                                           // switches -- bits 0..6 NEEDLE_HIP_MFMA_SPLITS, bit 8 _SINGLE, bit 9 _NO_IMAGES).  EVERY switch
-                                           // build_plan looks at is in here: the cached plan is keyed by it
-  std::vector<SearchProblem> meta;         // derived: the pairs the chosen kernel can stage, then the oversize ones
-  size_t staged = 0;                       // how many of meta go to the chosen kernel
-  uint64_t oversize_blocks = 0;            // grid of the unstaged kernel over meta[staged..]
-  uint64_t blocks = 0;
-  size_t lds_bytes = 0;
-  bool sampled = false, fast = false, mfma = false;
-  int mfma_waves = 0, mfma_splits = 1;      // scan_mfma_kernel.h: waves per workgroup, workgroups per group
-  std::vector<M2ImageSeq> image_seqs;       // ... and the source sequences whose window images a pre-pass builds (empty: workgroups build their own)
-  uint32_t image_windows = 0, image_min_len = 0;
-  uint64_t mfma_products = 0;                 // v_mfma instructions a launch of the matrix-pipe form issues
-  int bands_per_wave = 1;
-  bool valid = false;
-  bool matches(const NeedleHipSeq *s, size_t ns, const NeedleHipProblem *p, size_t np, const int *m) const {
-    return valid && seqs.size() == ns && problems.size() == np && std::memcmp(mode, m, sizeof(mode)) == 0 &&
-           std::memcmp(seqs.data(), s, ns * sizeof(NeedleHipSeq)) == 0 &&
-           std::memcmp(problems.data(), p, np * sizeof(NeedleHipProblem)) == 0;
-  }
-};
 
 int device_cus() {  // compute units of the current device (256 on MI355X)
   int cus = 256, dev = 0;
@@ -646,265 +608,56 @@ int device_cus() {  // compute units of the current device (256 on MI355X)
   return cus > 0 ? cus : 256;
 }
 
-Status build_plan(const NeedleHipSeq *seqs, size_t num_seqs, const NeedleHipProblem *problems, size_t num_problems,
-                  const int *mode, SearchPlan *plan) {
-  plan->valid = false;
-  std::vector<SearchProblem> &meta = plan->meta;
-  meta.clear();
-  meta.reserve(num_problems);
-  uint64_t blocks = 0;
-  for (size_t p = 0; p < num_problems; p++) {
-    const NeedleHipProblem &pr = problems[p];
-    if (pr.src_seq >= num_seqs || pr.dst_seq >= num_seqs)
-      return Status::Make(NeedleError_InvalidArgument, "hamming_runs: problem references a missing sequence");
-    if (pr.min_len == 0) return Status::Make(NeedleError_InvalidArgument, "hamming_runs: min_len must be >= 1");
-    const NeedleHipSeq &a = seqs[pr.src_seq], &b = seqs[pr.dst_seq];
-    if (a.len < 2 || b.len < 2) continue;  // no cell with i >= 1 and j >= 1 (comparator.rs:165-167,179)
-    SearchProblem m;
-    m.src_off = a.offset;
-    m.n = a.len;
-    m.dst_off = b.offset;
-    m.m = b.len;
-    m.min_len = pr.min_len;
-    m.tag = pr.tag;
-    m.block_base = 0;
-    m.pad = 0;
-    meta.push_back(m);
-  }
-  plan->staged = 0;
-  plan->oversize_blocks = 0;
-  if (!meta.empty()) {
-    // The band kernel needs min_len >= its checkpoint spacing for every problem; otherwise (tiny minimum
-    // durations) the general one-lane-per-diagonal kernel handles the launch.
-    uint32_t smallest = 0xFFFFFFFFu;
-    for (const SearchProblem &m : meta) smallest = std::min(smallest, m.min_len);
-    const bool generic_only = mode[0] != 0;
-    const bool sampled = !generic_only && smallest >= (uint32_t)(2 * scan_shape().w - 1 + 8) && mode[1] == 0 && mode[3] == 0;
-    const bool fast = !generic_only && !sampled && smallest >= (uint32_t)(kBandR * kBandU);
-    // What a pair needs in LDS under the chosen kernel.  A pair beyond the CU's 160 KiB (a window of more than ~2.7 h
-    // of audio at step 1) goes to the end of the table and is scanned from HBM by the unstaged kernel: one such
-    // video must not fail the search of the whole library (the reference has no bound).
-    const size_t lds_limit = (size_t)mode[5];  // 160 KiB, or NEEDLE_HIP_SEARCH_LDS_LIMIT (tests)
-    // The matrix-pipe form of the sampled scan pays on large launches whose windows fill their row tiles of 32 (two sources
-    // of one destination share a workgroup's tiles): measured against the vector form, scan kernel, 1.41 x at 39 060 pairs of
-    // 24-minute windows (2 x 39 windows in 3 tiles), 1.66 x at 499 500 pairs of 45-minute ones (2 x 73 in 5); 0.97 x on the
-    // headline's 378 pairs, where the scan hides beside the next job's first pass anyway.
-    auto windows_of = [&](const SearchProblem &m) { return (uint64_t)mfma_windows((int)m.n, (int)m.min_len, kSampleW); };
-    auto same_group = [](const SearchProblem &a, const SearchProblem &b) {
-      return a.dst_off == b.dst_off && a.m == b.m && a.min_len == b.min_len;
-    };
-    // The matrix-pipe form gives neighbours of the (sorted) table that share destination and minimum length to ONE
-    // workgroup -- up to eight sources -- while its LDS still lets the intended number of workgroups share a CU (LDS comes
-    // in granules of 1280 bytes: 53 760 is a third of a CU's, 81 920 half).
-    const int waves = mode[6];
-    const size_t group_budget = waves == 4 ? 53760 : waves == 8 ? 81920 : 163840;
-    const size_t max_members = (size_t)kM2Members;
-    auto group_need = [&](const SearchProblem &a, uint64_t windows) { return m2_lds_words(a.m, windows, waves) * sizeof(uint32_t); };
-    bool mfma = sampled && mode[4] == 1;
-    // From how many sequence pairs: with FP4 products the matrix-pipe kernel is the faster kernel from ~2000 pairs of
-    // 24-minute windows up (0.127 against 0.142 ms at 2016, 0.19 / 0.33 at 4950, 0.26 / 0.62 at 9730, 0.38 / 0.83 at 16 110)
-    // and jobs are no slower with it from there on either (two in flight, the scan beside the next job's first pass: 1.56 /
-    // 1.56, 2.65 / 2.71, 4.08 / 4.12, 5.66 / 5.96 ms).  (The int8 form lost inside jobs below 16 384 pairs -- the vector
-    // form's small workgroups fit the holes beside the first pass better -- and a job took it only from there; mode[5], "a
-    // call with nothing beside it", is not looked at any more.)
-    const size_t mfma_from = 2048;
-    const bool candidate = sampled && (mode[4] == 1 || (mode[4] == 2 && meta.size() >= mfma_from));
-    if (candidate) {  // the table sorted by destination (the runs carry the index of their own entry: its order is free)
-      std::stable_sort(meta.begin(), meta.end(), [](const SearchProblem &a, const SearchProblem &b) {
-        if (a.dst_off != b.dst_off) return a.dst_off < b.dst_off;
-        if (a.m != b.m) return a.m < b.m;
-        return a.min_len < b.min_len;
-      });
-      if (!mfma) {  // automatic: where the windows of a group fill at least 70 % of its row tiles of 32
-        uint64_t windows = 0, rows = 0;
-        for (size_t i = 0; i < meta.size(); i++) {
-          uint64_t w = windows_of(meta[i]);
-          for (size_t k = 1; k < max_members && i + 1 < meta.size() && same_group(meta[i], meta[i + 1]) &&
-                             group_need(meta[i], w + windows_of(meta[i + 1])) <= group_budget; k++)
-            w += windows_of(meta[++i]);
-          windows += w;
-          rows += (w + 31) / 32 * 32;
-        }
-        mfma = rows > 0 && 10 * windows >= 7 * rows;
-      }
-    }
-    auto lds_need = [&](const SearchProblem &m) {
-      if (mfma) return group_need(m, windows_of(m));
-      return ((fast || sampled) ? (size_t)m.m + 2 * kBandB : (size_t)m.n + m.m) * sizeof(uint32_t);
-    };
-    // The matrix-pipe kernel packs its queue items as unit << 17 | batch of row tiles << 11 | lane << 5 | flag bit and a window /
-    // member word as w0 | member << 28 (scan_mfma_kernel.h): a staged entry needs m < 65536, fewer than 8192 windows (per group) and n < 2^28.  The 160 KiB of LDS imply
-    // the first two (m <= ~40 900) only while the limit is the hardware's; checked here so that an overridden limit or a
-    // future layout cannot break the packing silently -- such an entry goes to the oversize partition.
-    auto mfma_packable = [&](const SearchProblem &m) { return m.m < 65536u && windows_of(m) < 8192u && m.n < (1u << 28); };
-    auto stageable = [&](const SearchProblem &m) { return lds_need(m) <= lds_limit && (!mfma || mfma_packable(m)); };
-    std::stable_partition(meta.begin(), meta.end(), stageable);
-    size_t staged = 0;
-    while (staged < meta.size() && stageable(meta[staged])) staged++;
-    size_t lds_bytes = 0;
-    int bands_per_wave = 1;
-    // pad of a group's first entry = how many followers; a follower (pad bit 31) owns no workgroups
-    size_t groups = 0;
-    if (mfma) {
-      const bool single = (mode[7] & 0x100) != 0;  // NEEDLE_HIP_MFMA_SINGLE (tests, measurements): one source per workgroup
-      for (size_t i = 0; i < staged;) {
-        SearchProblem &a = meta[i];
-        a.pad = 0;
-        uint64_t windows = windows_of(a);
-        size_t k = 1;
-        while (!single && k < max_members && i + k < staged && same_group(a, meta[i + k]) &&
-               windows + windows_of(meta[i + k]) < 8192 &&
-               group_need(a, windows + windows_of(meta[i + k])) <= group_budget) {
-          windows += windows_of(meta[i + k]);
-          meta[i + k].pad = 0x80000000u;
-          k++;
-        }
-        a.pad = (uint32_t)(k - 1);
-        i += k;
-        groups++;
-      }
-    }
-    // the index of group G's first entry rides in the pad field of the table's G-th entry (bits 8 .. 30), so a workgroup
-    // finds its group with one load
-    if (mfma) {
-      if (staged >= ((size_t)1 << 23)) return Status::Make(NeedleError_InvalidArgument, "hamming_runs: too many problems for one launch");
-      size_t g = 0;
-      for (size_t i = 0; i < staged; i++)
-        if (!(meta[i].pad & 0x80000000u)) meta[g++].pad |= (uint32_t)i << 8;
-    }
-    // one workgroup per group; a launch of few groups splits each over several workgroups (column units strided)
-    int splits = 1;
-    if (mfma && groups > 0) {
-      const uint64_t slots = (uint64_t)device_cus() * (uint64_t)(waves == 4 ? 3 : waves == 8 ? 2 : 1);
-      splits = (int)std::min<uint64_t>(8, std::max<uint64_t>(1, (2 * slots + groups - 1) / groups));
-      if (mode[7] & 0x7F) splits = mode[7] & 0x7F;  // NEEDLE_HIP_MFMA_SPLITS (tests, tuning), 1 .. 64
-    }
-    if (fast || sampled) {
-      uint64_t fb = 0, total_bands = 0;
-      for (size_t i = 0; i < staged; i++) total_bands += ((uint64_t)meta[i].n + meta[i].m - 3 + kBandB - 1) / kBandB;
-      // enough workgroups to fill the chip several times over with one band per wave; beyond that, more bands
-      // per wave so that each workgroup's staging of the destination sequence serves more of its pair
-      if (sampled)
-        while (bands_per_wave < 8 && total_bands / (4 * (uint64_t)bands_per_wave * 2) >= 16384) bands_per_wave *= 2;
-      if (mode[2] > 0) bands_per_wave = mode[2];  // NEEDLE_HIP_BANDS_PER_WAVE: tests, tuning
-      for (size_t i = 0; i < staged; i++) {
-        SearchProblem &m = meta[i];
-        m.block_base = (uint32_t)fb;
-        if (mfma && (m.pad & 0x80000000u)) continue;  // its workgroups are its group's (same base as the entry after it)
-        const uint64_t diags = (uint64_t)m.n + m.m - 3;
-        const uint64_t bands = (diags + kBandB - 1) / kBandB;
-        const uint64_t per_block = 4 * (uint64_t)(sampled ? bands_per_wave : 1);
-        fb += mfma ? (uint64_t)splits : (bands + per_block - 1) / per_block;
-        if (mfma) {
-          uint64_t windows = windows_of(m);
-          for (uint32_t f = 1; f <= (m.pad & 0xFFu); f++) windows += windows_of(meta[i + f]);
-          lds_bytes = std::max(lds_bytes, group_need(m, windows));
-        } else {
-          lds_bytes = std::max(lds_bytes, lds_need(m));
-        }
-      }
-      blocks = fb;
-    } else {
-      for (size_t i = 0; i < staged; i++) {
-        SearchProblem &m = meta[i];
-        m.block_base = (uint32_t)blocks;
-        blocks += ((uint64_t)m.n + m.m - 3 + kDiagsPerBlock - 1) / kDiagsPerBlock;
-        lds_bytes = std::max(lds_bytes, lds_need(m));
-      }
-    }
-    uint64_t ob = 0;
-    for (size_t i = staged; i < meta.size(); i++) {  // one workgroup = 256 consecutive diagonals, as in the staged form
-      meta[i].block_base = (uint32_t)ob;
-      ob += ((uint64_t)meta[i].n + meta[i].m - 3 + kDiagsPerBlock - 1) / kDiagsPerBlock;
-    }
-    if (blocks > 0x7FFFFFFFull || ob > 0x7FFFFFFFull)
-      return Status::Make(NeedleError_InvalidArgument, "hamming_runs: too many problems for one launch");
-    plan->staged = staged;
-    plan->oversize_blocks = ob;
-    plan->sampled = sampled;
-    plan->mfma = mfma;
-    plan->mfma_products = 0;
-    if (mfma)
-      for (size_t i = 0; i < staged; i++) {
-        const SearchProblem &m = meta[i];
-        if (m.pad & 0x80000000u) continue;
-        uint64_t w = windows_of(m);
-        for (uint32_t f = 1; f <= (m.pad & 0xFFu); f++) w += windows_of(meta[i + f]);
-        if (w > 0 && m.m >= (uint32_t)kSampleW + 1) {
-          uint64_t col_blocks = ((uint64_t)m.m - kSampleW) / 32 + 1;
-          col_blocks = (col_blocks + kM2ColBlocks - 1) / kM2ColBlocks * kM2ColBlocks;  // whole units are multiplied
-          plan->mfma_products += (w + 31) / 32 * col_blocks * (kM2Heads / 2);
-        }
-      }
-    // The matrix-pipe form's window images (scan_mfma_kernel.h): one per distinct source sequence, when the launch has ONE
-    // minimum length (a library of equal-length videos; otherwise the window positions differ per pair and workgroups
-    // build their own).  block_base of a staged entry -- not read by that kernel otherwise -- = first window of its source's image.
-    plan->image_seqs.clear();
-    plan->image_windows = plan->image_min_len = 0;
-    if (mfma && staged > 0 && !(mode[7] & 0x200)) {  // (bit 9: NEEDLE_HIP_MFMA_NO_IMAGES)
-      bool one = true;
-      for (size_t i = 1; i < staged && one; i++) one = meta[i].min_len == meta[0].min_len;
-      if (one) {
-        std::unordered_map<uint64_t, uint32_t> first_of;   // (src_off, n) -> first window
-        uint64_t total = 0;
-        for (size_t i = 0; i < staged; i++) {
-          const uint64_t key = ((uint64_t)meta[i].src_off << 32) | meta[i].n;
-          auto it = first_of.find(key);
-          if (it == first_of.end()) {
-            const uint32_t w = (uint32_t)windows_of(meta[i]);
-            it = first_of.emplace(key, (uint32_t)total).first;
-            plan->image_seqs.push_back(M2ImageSeq{meta[i].src_off, meta[i].n, (uint32_t)total, w});
-            total += w;
-          }
-          meta[i].block_base = it->second;
-        }
-        if (total == 0 || total * kM2ImageWords * sizeof(uint32_t) > ((uint64_t)1 << 31)) {
-          plan->image_seqs.clear();           // (nothing to build, or more than 2 GB of images: built in place)
-        } else {
-          plan->image_windows = (uint32_t)total;
-          plan->image_min_len = meta[0].min_len;
-        }
-      }
-    }
-    plan->fast = fast;
-    plan->mfma_waves = waves;
-    plan->mfma_splits = splits;
-    plan->bands_per_wave = bands_per_wave;
-    plan->lds_bytes = lds_bytes;
-  }
-  plan->blocks = blocks;
-  plan->seqs.assign(seqs, seqs + num_seqs);
-  plan->problems.assign(problems, problems + num_problems);
-  std::memcpy(plan->mode, mode, sizeof(plan->mode));
-  plan->valid = true;
-  return Status::Ok();
-}
-
-// NEEDLE_HIP_SCAN_MFMA: 1 = the matrix-pipe form of the sampled scan wherever it applies, 0 = never, unset = where it pays
-// (build_plan).  It applies to thresholds <= 15 and the default window shape.  -> mode[4]: 0 off, 1 forced, 2 automatic
-int mfma_request(uint32_t threshold) {
-  if (threshold > 15u || scan_shape().w != kSampleW || getenv("NEEDLE_HIP_SCAN_SHAPE") || getenv("NEEDLE_HIP_SCAN_COUNT")) return 0;
-  // (a counting launch and a launch of another window shape are the vector form's by definition)
-  const char *e = getenv("NEEDLE_HIP_SCAN_MFMA");
-  if (!e) return 2;
-  return atoi(e) != 0 ? 1 : 0;
-}
-
-// The matrix-pipe form's workgroup shape (measurements; the default is what won, profiles/NOTES.md round 5):
-// NEEDLE_HIP_MFMA_WAVES 4 / 8 / 12 / 16 waves per workgroup (3 / 2 / 1 / 1 workgroups per CU; 8 and 16: four waves per
-// SIMD, one accumulator pair).
-int mfma_waves() {
-  int waves = 8;
-  if (const char *e = getenv("NEEDLE_HIP_MFMA_WAVES")) {
-    const int w = atoi(e);
-    if (w == 4 || w == 8 || w == 12 || w == 16) waves = w;
-  }
-  return waves;
+// The planner's switches (scan_plan.h ScanSwitches says what each is), from the threshold and the environment.
+//  * NEEDLE_HIP_SCAN_MFMA: 1 = the matrix-pipe form of the sampled scan wherever it applies, 0 = never, unset = where it pays.
+//    It applies to thresholds <= 15 and the default window shape; a counting launch and a launch of another window shape are
+//    the vector form's by definition.
+//  * NEEDLE_HIP_MFMA_WAVES: the matrix-pipe form's workgroup shape (measurements; the default is what won, profiles/NOTES.md
+//    round 5): 4 / 8 / 12 / 16 waves per workgroup (3 / 2 / 1 / 1 workgroups per CU; 8 and 16: four waves per SIMD, one
+//    accumulator pair).
+ScanSwitches scan_switches(uint32_t threshold) {
+  auto number = [](const char *name, int lo, int hi, int unset) {
+    const char *e = getenv(name);
+    return e ? std::max(lo, std::min(hi, atoi(e))) : unset;
+  };
+  ScanSwitches sw;
+  sw.generic_only = getenv("NEEDLE_HIP_GENERIC_SEARCH") != nullptr;
+  sw.band_only = getenv("NEEDLE_HIP_BAND_SEARCH") != nullptr;
+  sw.bands_per_wave = number("NEEDLE_HIP_BANDS_PER_WAVE", 1, INT_MAX, 0);
+  sw.beyond_bit_trick = threshold > 31u;
+  sw.window_w = scan_shape().w;
+  const char *mfma = getenv("NEEDLE_HIP_SCAN_MFMA");
+  if (threshold > 15u || sw.window_w != kSampleW || getenv("NEEDLE_HIP_SCAN_SHAPE") || getenv("NEEDLE_HIP_SCAN_COUNT"))
+    sw.mfma = MfmaRequest::Off;
+  else if (mfma)
+    sw.mfma = atoi(mfma) != 0 ? MfmaRequest::Forced : MfmaRequest::Off;
+  sw.lds_limit = (size_t)number("NEEDLE_HIP_SEARCH_LDS_LIMIT", 1, INT_MAX, 160 * 1024);
+  const int waves = number("NEEDLE_HIP_MFMA_WAVES", 0, INT_MAX, 8);
+  if (waves == 4 || waves == 8 || waves == 12 || waves == 16) sw.mfma_waves = waves;
+  sw.mfma_splits = number("NEEDLE_HIP_MFMA_SPLITS", 1, 64, 0);
+  sw.mfma_single = getenv("NEEDLE_HIP_MFMA_SINGLE") != nullptr;
+  sw.mfma_no_images = getenv("NEEDLE_HIP_MFMA_NO_IMAGES") != nullptr;
+  return sw;
 }
 using Mfma2Kernel = void (*)(const uint32_t *, const SearchProblem *, int, uint32_t, NeedleHipRun *, uint32_t, uint32_t *, int, const uint32_t *);
 Mfma2Kernel mfma2_kernel(int waves) {
   return waves == 4 ? hamming_runs_mfma2_kernel<kSampleW, 4, 3> : waves == 16 ? hamming_runs_mfma2_kernel<kSampleW, 16, 4>
        : waves == 12 ? hamming_runs_mfma2_kernel<kSampleW, 12, 3> : hamming_runs_mfma2_kernel<kSampleW, 8, 4>;
+}
+
+// What the staged part of a plan launches.  `counting`: NEEDLE_HIP_SCAN_COUNT's diagnostic form of the sampled kernel (such a
+// launch is never the matrix pipe's: scan_switches()); `lds_forms`: NEEDLE_HIP_SPARSE_MAX is set, the sampled kernel's LEGACY form.
+struct StagedLaunch {
+  int form;         // gpu_scan_last_launch's number: 1 generic, 2 band, 3 sampled, 4 sampled on the matrix pipe
+  void *kernel;
+  unsigned threads;
+};
+StagedLaunch staged_launch(const SearchPlan &plan, bool counting, bool lds_forms) {
+  if (plan.sampled && counting) return {3, (void *)sampled_kernel<true>(scan_shape(), lds_forms), 256u};
+  if (plan.sampled && plan.mfma) return {4, (void *)mfma2_kernel(plan.mfma_waves), 64u * (unsigned)plan.mfma_waves};
+  if (plan.sampled) return {3, (void *)sampled_kernel<false>(scan_shape(), lds_forms), 256u};
+  if (plan.fast) return {2, (void *)hamming_runs_band_kernel<kBandR, kBandU>, 256u};
+  return {1, (void *)hamming_runs_kernel<true>, 256u};
 }
 
 std::atomic<int32_t> g_last_form{0};
@@ -919,7 +672,7 @@ struct SearchWorkspace {
   PinnedStage image_stage;
   DescriptorUpload<M2ImageSeq> image_upload;
   DeviceBuffer<uint32_t> images;         // ... and the images
-  bool lds_attr_set = false;  // > 64 KiB of dynamic LDS needs an explicit opt-in, per device
+  std::set<const void *> lds_opted;  // > 64 KiB of dynamic LDS needs an explicit opt-in, per kernel and device: those that have it
   unsigned long long *eval_groups = nullptr;  // device; NEEDLE_HIP_SCAN_COUNT=1 launches add to it
 };
 std::mutex g_ws_mu;
@@ -952,100 +705,69 @@ Status gpu_hamming_runs_device(const uint32_t *d_hashes, const NeedleHipSeq *seq
   if (!s.ok()) return s;
   hipStream_t stream = library_stream();
   if (!count_is_zero) NEEDLE_HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint32_t), stream));
-  const int mode[8] = {getenv("NEEDLE_HIP_GENERIC_SEARCH") != nullptr, getenv("NEEDLE_HIP_BAND_SEARCH") != nullptr,
-                       getenv("NEEDLE_HIP_BANDS_PER_WAVE") ? std::max(1, atoi(getenv("NEEDLE_HIP_BANDS_PER_WAVE"))) : 0,
-                       threshold > 31u,   // every cell matches at 32: the band / generic kernels take such a launch
-                       mfma_request(threshold),
-                       getenv("NEEDLE_HIP_SEARCH_LDS_LIMIT") ? std::max(1, atoi(getenv("NEEDLE_HIP_SEARCH_LDS_LIMIT"))) : 160 * 1024,
-                       mfma_waves(),
-                       (getenv("NEEDLE_HIP_MFMA_SPLITS") ? std::max(1, std::min(64, atoi(getenv("NEEDLE_HIP_MFMA_SPLITS")))) : 0) |
-                           (getenv("NEEDLE_HIP_MFMA_SINGLE") ? 0x100 : 0) | (getenv("NEEDLE_HIP_MFMA_NO_IMAGES") ? 0x200 : 0)};
+  const ScanSwitches switches = scan_switches(threshold);
   SearchWorkspace *ws = workspace();
   SearchPlan &plan = ws->plan;
-  const bool reuse = plan.matches(seqs, num_seqs, problems, num_problems, mode);
-  if (!reuse && !(s = build_plan(seqs, num_seqs, problems, num_problems, mode, &plan)).ok()) return s;
+  const bool reuse = plan.matches(seqs, num_seqs, problems, num_problems, switches);
+  if (!reuse && !(s = build_plan(seqs, num_seqs, problems, num_problems, switches, device_cus(), &plan)).ok()) return s;
   const std::vector<SearchProblem> &meta = plan.meta;
-  const uint64_t blocks = plan.blocks;
-  const size_t lds_bytes = plan.lds_bytes;
-  const bool sampled = plan.sampled, fast = plan.fast;
-  const int bands_per_wave = plan.bands_per_wave;
   if (!meta.empty()) {
     // same inputs as last time and the table still where it was put: nothing to compare or upload
     if (!(reuse && ws->upload.resident_at == ws->problems.ptr && ws->problems.ptr) &&
         !(s = ws->upload.put(&ws->problems, &ws->stage, meta, stream)).ok())
       return s;
-    if (lds_bytes > 64 * 1024 && !ws->lds_attr_set) {
-      NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_runs_kernel<true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(hamming_runs_band_kernel<kBandR, kBandU>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      for (int w : {4, 8, 12, 16})
-        NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mfma2_kernel(w)),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      for (int w : {4, 8, 16})
-        for (int h : {2, 3, 4}) {
-          if (h >= w) continue;
-          for (bool legacy : {false, true}) {
-            NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(sampled_kernel<false>(ScanShape{w, h}, legacy)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            NEEDLE_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(sampled_kernel<true>(ScanShape{w, h}, legacy)),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-          }
-        }
-      ws->lds_attr_set = true;
-    }
     const int staged = (int)plan.staged, oversize = (int)(meta.size() - plan.staged);
-    g_last_form.store(staged > 0 ? (sampled ? (plan.mfma ? 4 : 3) : fast ? 2 : 1) : 1);
+    int sparse_max = -1;  // sampled: survivors of the head rows finished from registers (the kernel's default path)
+    if (const char *e = getenv("NEEDLE_HIP_SPARSE_MAX")) sparse_max = std::max(0, atoi(e));  // tests, tuning: the LDS forms; 0 = row by row
+    const bool counting = getenv("NEEDLE_HIP_SCAN_COUNT") != nullptr;  // diagnostic: the same sampled scan, counting what it issues
+    const StagedLaunch launch = staged_launch(plan, counting, sparse_max >= 0);
+    g_last_form.store(staged > 0 ? launch.form : 1);
     g_last_products.store(staged > 0 && plan.mfma ? plan.mfma_products : 0);
     if (staged > 0) {
-      KernelTimer timer("hamming_runs");
-      if (sampled) {
-        int sparse_max = -1;  // survivors of the head rows finished from registers (the kernel's default path)
-        if (const char *e = getenv("NEEDLE_HIP_SPARSE_MAX")) sparse_max = std::max(0, atoi(e));  // tests, tuning: the LDS forms; 0 = row by row
-        if (getenv("NEEDLE_HIP_SCAN_COUNT")) {  // diagnostic: the same scan, counting what it issues
-          if (!ws->eval_groups) {
-            NEEDLE_HIP_TRY(hipMalloc((void **)&ws->eval_groups, 2 * sizeof(unsigned long long)));
-            NEEDLE_HIP_TRY(hipMemsetAsync(ws->eval_groups, 0, 2 * sizeof(unsigned long long), stream));
-          }
-          hipLaunchKernelGGL(sampled_kernel<true>(scan_shape(), sparse_max >= 0), dim3((uint32_t)blocks), dim3(256), lds_bytes, stream, d_hashes,
-                             ws->problems.ptr, staged, threshold, d_runs, capacity, d_count, bands_per_wave, sparse_max,
-                             ws->eval_groups);
-        } else if (plan.mfma) {
-          const uint32_t *images = nullptr;
-          if (!plan.image_seqs.empty()) {   // the sources' window images, once per launch (the hashes are this job's)
-            if (!(s = ws->image_upload.put(&ws->image_seqs, &ws->image_stage, plan.image_seqs, stream)).ok() ||
-                !(s = ws->images.reserve((size_t)plan.image_windows * kM2ImageWords)).ok())
-              return s;
-            const uint32_t grid = (uint32_t)std::min<uint64_t>(8192, ((uint64_t)plan.image_windows * kM2Rows + 255) / 256);
-            hipLaunchKernelGGL(m2_window_images_kernel<kSampleW>, dim3(grid), dim3(256), 0, stream, d_hashes, ws->image_seqs.ptr,
-                               (int)plan.image_seqs.size(), plan.image_windows, plan.image_min_len, ws->images.ptr);
-            images = ws->images.ptr;
-          }
-          hipLaunchKernelGGL(mfma2_kernel(plan.mfma_waves), dim3((uint32_t)blocks), dim3(64 * plan.mfma_waves),
-                             lds_bytes, stream, d_hashes, ws->problems.ptr, staged, threshold, d_runs, capacity, d_count,
-                             plan.mfma_splits, images);
-#if NEEDLE_M2_LAB & 8
-          {
-            unsigned long long c[8], z[8] = {};
-            (void)hipStreamSynchronize(stream);
-            (void)hipMemcpyFromSymbol(c, HIP_SYMBOL(m2_dbg), sizeof c);
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(m2_dbg), z, sizeof z);
-            fprintf(stderr, "m2 counts: resolve calls %llu, trips %llu, mismatches handled %llu, walks continued %llu, extra forward trips %llu, "
-                            "windows past the tail rows %llu, items %llu, windows past the head rows %llu\n", c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
-          }
-#endif
-        } else {
-          hipLaunchKernelGGL(sampled_kernel<false>(scan_shape(), sparse_max >= 0), dim3((uint32_t)blocks), dim3(256), lds_bytes, stream, d_hashes,
-                             ws->problems.ptr, staged, threshold, d_runs, capacity, d_count, bands_per_wave, sparse_max,
-                             (unsigned long long *)nullptr);
-        }
+      if (plan.lds_bytes > 64 * 1024 && !ws->lds_opted.count(launch.kernel)) {
+        NEEDLE_HIP_TRY(hipFuncSetAttribute(launch.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ws->lds_opted.insert(launch.kernel);
       }
-      else if (fast)
-        hipLaunchKernelGGL((hamming_runs_band_kernel<kBandR, kBandU>), dim3((uint32_t)blocks), dim3(256), lds_bytes,
-                           stream, d_hashes, ws->problems.ptr, staged, threshold, d_runs, capacity, d_count);
-      else
-        hipLaunchKernelGGL(hamming_runs_kernel<true>, dim3((uint32_t)blocks), dim3(256), lds_bytes, stream, d_hashes,
-                           ws->problems.ptr, staged, 0u, threshold, d_runs, capacity, d_count);
+      KernelTimer timer("hamming_runs");
+      const dim3 grid((uint32_t)plan.blocks), block(launch.threads);
+      if (launch.form == 3) {
+        if (counting && !ws->eval_groups) {
+          NEEDLE_HIP_TRY(hipMalloc((void **)&ws->eval_groups, 2 * sizeof(unsigned long long)));
+          NEEDLE_HIP_TRY(hipMemsetAsync(ws->eval_groups, 0, 2 * sizeof(unsigned long long), stream));
+        }
+        hipLaunchKernelGGL(reinterpret_cast<SampledKernel>(launch.kernel), grid, block, plan.lds_bytes, stream, d_hashes, ws->problems.ptr,
+                           staged, threshold, d_runs, capacity, d_count, plan.bands_per_wave, sparse_max,
+                           counting ? ws->eval_groups : (unsigned long long *)nullptr);
+      } else if (launch.form == 4) {
+        const uint32_t *images = nullptr;
+        if (!plan.image_seqs.empty()) {   // the sources' window images, once per launch (the hashes are this job's)
+          if (!(s = ws->image_upload.put(&ws->image_seqs, &ws->image_stage, plan.image_seqs, stream)).ok() ||
+              !(s = ws->images.reserve((size_t)plan.image_windows * kM2ImageWords)).ok())
+            return s;
+          const uint32_t image_grid = (uint32_t)std::min<uint64_t>(8192, ((uint64_t)plan.image_windows * kM2Rows + 255) / 256);
+          hipLaunchKernelGGL(m2_window_images_kernel<kSampleW>, dim3(image_grid), dim3(256), 0, stream, d_hashes, ws->image_seqs.ptr,
+                             (int)plan.image_seqs.size(), plan.image_windows, plan.image_min_len, ws->images.ptr);
+          images = ws->images.ptr;
+        }
+        hipLaunchKernelGGL(reinterpret_cast<Mfma2Kernel>(launch.kernel), grid, block, plan.lds_bytes, stream, d_hashes, ws->problems.ptr,
+                           staged, threshold, d_runs, capacity, d_count, plan.mfma_splits, images);
+#if NEEDLE_M2_LAB & 8
+        {
+          unsigned long long c[8], z[8] = {};
+          (void)hipStreamSynchronize(stream);
+          (void)hipMemcpyFromSymbol(c, HIP_SYMBOL(m2_dbg), sizeof c);
+          (void)hipMemcpyToSymbol(HIP_SYMBOL(m2_dbg), z, sizeof z);
+          fprintf(stderr, "m2 counts: resolve calls %llu, trips %llu, mismatches handled %llu, walks continued %llu, extra forward trips %llu, "
+                          "windows past the tail rows %llu, items %llu, windows past the head rows %llu\n", c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7]);
+        }
+#endif
+      } else if (launch.form == 2) {
+        hipLaunchKernelGGL((hamming_runs_band_kernel<kBandR, kBandU>), grid, block, plan.lds_bytes, stream, d_hashes, ws->problems.ptr,
+                           staged, threshold, d_runs, capacity, d_count);
+      } else {
+        hipLaunchKernelGGL(hamming_runs_kernel<true>, grid, block, plan.lds_bytes, stream, d_hashes, ws->problems.ptr, staged, 0u,
+                           threshold, d_runs, capacity, d_count);
+      }
     }
     if (oversize > 0) {  // pairs too long to stage: scanned from HBM, behind the others in the table
       KernelTimer timer("hamming_runs_unstaged");

@@ -2,7 +2,7 @@
 (comparator.rs:178-183), and three parts of the scan encode t in arithmetic rather than compare with it: the matrix-pipe
 form's accumulator preset 63 - 4 t (its sign bit: d + d' <= 2 t over two head rows, scan_mfma_kernel.h), the bias 31 - t of
 the vector and matrix-pipe exact tests (bit 5 of popcount + bias: a cell that does NOT match, search.hip), and the host's
-routing (search.hip mfma_request / build_plan: the matrix pipe up to t = 15, the band or generic kernel from t = 32).  An
+routing (search.hip scan_switches / scan_plan.h build_plan: the matrix pipe up to t = 15, the band or generic kernel from t = 32).  An
 off-by-one in any of them shows only on cells at distance exactly t or t + 1, which random hashes with single-bit noise never
 line up into runs.  So the tables here are planted cell by cell at EXACT distances -- runs of cells at t, the same broken by
 single cells at t + 1 on every kind of row an aligned window has, head-row pairs whose sum passes the matrix pipe's filter
