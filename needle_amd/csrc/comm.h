@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "shard.h"
 
 namespace needle {
 
@@ -52,13 +53,6 @@ Status comm_all_to_all_v(CommChannel ch, const void *d_send, const size_t *send_
 Status comm_all_gather_host(const void *send, void *recv, size_t bytes);
 Status comm_barrier();
 
-// Contiguous block plan: `units` split into `world` blocks of ceil(units / world); rank's [first, first + count).
-inline size_t shard_block(size_t units, int world) { return world > 0 ? (units + (size_t)world - 1) / (size_t)world : units; }
-inline void shard_range(size_t units, int world, int rank, size_t *first, size_t *count) {
-  const size_t b = shard_block(units, world);
-  const size_t f = std::min(units, (size_t)rank * b);
-  *first = f;
-  *count = std::min(b, units - f);
-}
+// (shard_block / shard_range, the contiguous block plan of videos and pairs: shard.h)
 
 }  // namespace needle

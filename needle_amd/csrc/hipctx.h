@@ -59,6 +59,27 @@ struct DeviceBuffer {
   }
 };
 
+// Pinned host memory that grows (never shrinks) to hold `bytes`; contents are not preserved.
+struct PinnedBuffer {
+  void *ptr = nullptr;
+  size_t bytes = 0;
+  PinnedBuffer() = default;
+  PinnedBuffer(const PinnedBuffer &) = delete;
+  PinnedBuffer &operator=(const PinnedBuffer &) = delete;
+  ~PinnedBuffer() {
+    if (ptr) (void)hipHostFree(ptr);
+  }
+  Status reserve(size_t n) {
+    if (n <= bytes) return Status::Ok();
+    if (ptr) (void)hipHostFree(ptr);
+    ptr = nullptr;
+    bytes = 0;
+    NEEDLE_HIP_TRY(hipHostMalloc(&ptr, n, hipHostMallocDefault));
+    bytes = n;
+    return Status::Ok();
+  }
+};
+
 // Pinned host staging for small descriptor uploads: acquire() waits until the previous async copy out
 // of the buffer has executed, mark() records that point on the stream.
 struct PinnedStage {

@@ -23,6 +23,7 @@
 #include "epilogue.h"
 #include "format_plan.h"
 #include "hipctx.h"
+#include "job_plan.h"
 #include "needle_core.h"
 
 struct FrameHashes;
@@ -92,58 +93,48 @@ struct NeedleHipLibrary {
     const uint32_t *d_count = nullptr;
     bool pending = false;
   } fetch[2];
-  // One slot of the job pipeline (needle_hip_library_job_begin / _end): the run slabs of all ranks, device side and
-  // pinned host side.  Rank r's slab = 32-byte header (word 0: runs found) + slab_runs runs; the scan writes straight
-  // into this rank's slab and the all-gather fills in the others in place.
+  // One slot of the job pipeline (needle_hip_library_job_begin / _end).  Rank r's slab = 32-byte header (word 0: runs found) +
+  // slab_runs runs (job_plan.h); the scan writes straight into this rank's slab, the other ranks' runs arrive as heads or
+  // as the blocks of the owner-directed exchange.
   struct Job {
-    DeviceBuffer<uint8_t> d_slabs;
-    DeviceBuffer<uint8_t> d_heads;  // world > 1: [world][head_bytes], what the all-gather of run lists fills
-    uint32_t slab_runs = 0, head_runs = 0;
-    int world = 0;
-    void *host = nullptr;
-    size_t host_bytes = 0;
-    hipEvent_t searched = nullptr, done = nullptr;
     bool pending = false;
-    std::vector<NeedleHipRun> merged;
-    // device epilogue (epilogue.hip): per-video results + failure count land here (pinned) behind the run download
-    void *host_results = nullptr;
-    size_t host_results_bytes = 0;
-    bool device_epilogue = false, sharded = false;
-    bool shape_fixed = false;  // `sharded` was decided when the job was enqueued (device epilogue requested): job_end keeps it even if the
-                               // device form then failed on THIS rank alone -- the other ranks enter the collective that decision implies
-    const NeedleHipRun *last_runs = nullptr;  // the complete run list of the job that finished last in this slot
-    size_t last_total = 0;
-    // Owner-directed run exchange (round 6; world > 1 with the sharded device epilogue): a run of pair (i, j) travels to
-    // the owners of videos i and j only (comparator.rs:583-588: a video's epilogue needs its own pairs), not to every rank.
-    // d_dir_send = this rank's runs sorted into one block per destination (epilogue.h DirectPlan), d_dir_recv = the blocks
-    // received, in rank order, = the device epilogue's segments.  Block sizes are host values on every rank: cap[r * world + q]
-    // comes from the count matrix of the library's last finished job (every rank has all of it: d_dir_counts, one row of
-    // [slab count, runs directed to rank 0, 1, ...] per rank, all-gathered) plus a margin; a count beyond its block is the
-    // head overflow's case (job_end: sizes grow, the exchange is repeated).  A library's first job has no matrix yet: it
-    // counts, and travels as heads.
-    DeviceBuffer<uint8_t> d_dir_send, d_dir_recv;
-    DeviceBuffer<uint32_t> d_dir_counts;
-    void *host_counts = nullptr;
-    size_t host_counts_bytes = 0;
-    std::vector<uint32_t> cap;      // of this job's exchange (empty: this job travels as heads)
-    bool ran_device_epilogue = false, ran_sharded = false;  // what job_end found (needle_hip_library_job_form)
-    uint32_t scan_form = 0;
-    bool counted = false;           // host_counts holds this job's count matrix
-    bool directed = false;          // this job's runs travelled owner-directed
-    std::vector<NeedleHipRun> fetched;  // directed: the received runs, downloaded on demand (job_runs, a host fallback)
-    bool fetched_valid = false;
-    static size_t count_words(int world) { return ((size_t)world + 1 + 3) & ~(size_t)3; }
-    uint64_t comm_bytes[4] = {0, 0, 0, 0};  // received per rank in this job: hash rows, run heads, results; scans repeated
-    size_t slab_bytes() const { return kSlabHeader + (size_t)slab_runs * sizeof(NeedleHipRun); }
-    size_t head_bytes() const { return kSlabHeader + (size_t)head_runs * sizeof(NeedleHipRun); }
+    // What was planned when the job -- or its repeat -- was enqueued (job_plan.h plan_job), and what the enqueue made of it.
+    struct Planned {
+      JobPlan plan;
+      bool device_epilogue = false;  // plan.device_epilogue, unless the device form failed on THIS rank at the enqueue
+      bool counted = false;          // host_counts holds this job's count matrix
+      bool directed = false;         // this job's runs travelled owner-directed (plan.directed.sized and a transport that can)
+      uint32_t scan_form = 0;
+    } planned;
+    // What job_end found (needle_hip_library_job_runs / _form / _comm_bytes).
+    struct Found {
+      std::vector<NeedleHipRun> merged;
+      const NeedleHipRun *last_runs = nullptr;  // the complete run list of the job that finished last in this slot
+      size_t last_total = 0;
+      std::vector<NeedleHipRun> fetched;  // directed: the received runs, downloaded on demand (job_runs, a host fallback)
+      bool fetched_valid = false;
+      bool ran_device_epilogue = false, ran_sharded = false;
+      uint64_t comm_bytes[4] = {0, 0, 0, 0};  // received per rank in this job: hash rows, run heads, results; scans repeated
+    } found;
+    // Owner-directed run exchange (world > 1 with the sharded device epilogue): a run of pair (i, j) travels to the owners of
+    // videos i and j only (comparator.rs:583-588: a video's epilogue needs its own pairs), not to every rank.  d_dir_send =
+    // this rank's runs sorted into one block per destination (epilogue.h DirectPlan), d_dir_recv = the blocks received, in
+    // rank order, = the device epilogue's segments; d_dir_counts = the count matrix (job_plan.h), all-gathered, host_counts
+    // its download.  A count beyond its block is the head overflow's case (job_end: sizes grow, the job is repeated).
+    struct Buffers {
+      DeviceBuffer<uint8_t> d_slabs;  // this rank's slab only
+      DeviceBuffer<uint8_t> d_heads;  // world > 1: [world][head_bytes], what the all-gather of run lists fills
+      DeviceBuffer<uint8_t> d_dir_send, d_dir_recv;
+      DeviceBuffer<uint32_t> d_dir_counts;
+      uint32_t slab_runs = 0;  // what d_slabs was allocated for
+      int world = 0;
+      PinnedBuffer host;          // the heads of all ranks, in one copy
+      PinnedBuffer host_counts;   // the count matrix
+      PinnedBuffer host_results;  // device epilogue: per-video results + failure count land here behind the run download
+      hipEvent_t searched = nullptr, done = nullptr;
+    } buf;
   } job[2];
-  static constexpr size_t kSlabHeader = 32;
-  uint32_t slab_runs = 0;      // per-rank run capacity of the next job (grows on overflow)
-  uint32_t last_max_count = 0;  // largest per-rank run count of the last finished job: sizes the one-trip download
-  std::vector<uint32_t> dir_counts;  // [world][world]: runs rank r directed to rank q in the last finished job (Job::cap's source)
-  int dir_world = 0;
-  bool dir_unsupported = false;      // the communicator has no point-to-point transfers: every job travels as heads
-  bool dir_cap_forced = false;       // (tests: NEEDLE_HIP_TEST_DIRECTED_CAP applied once)
+  JobHistory history;  // what the last finished job leaves the next one (job_plan.h): every rank holds the same
   size_t arena_rows = 0;       // rows the arena was allocated with
   const uint32_t *count_zeroed = nullptr;  // a run counter the last kernel of this job's analyze has just cleared (job_begin)
   // what the device epilogue needs to know about the arena's rows (built once per geometry: plan_windows clears them)
@@ -175,11 +166,8 @@ struct NeedleHipLibrary {
       if (f.ready) (void)hipEventDestroy(f.ready);
     }
     for (Job &j : job) {
-      if (j.host_results) (void)hipHostFree(j.host_results);
-      if (j.host_counts) (void)hipHostFree(j.host_counts);
-      if (j.host) (void)hipHostFree(j.host);
-      if (j.done) (void)hipEventDestroy(j.done);
-      if (j.searched) (void)hipEventDestroy(j.searched);
+      if (j.buf.done) (void)hipEventDestroy(j.buf.done);
+      if (j.buf.searched) (void)hipEventDestroy(j.buf.searched);
     }
   }
 
@@ -974,277 +962,388 @@ NeedleError analyze_flat_block(NeedleHipLibrary *lib, int world, int rank, int s
   return s.ok() ? NeedleError_Ok : report(s);
 }
 
-uint32_t round_up4(uint64_t v) { return (uint32_t)std::min<uint64_t>((v + 3) & ~(uint64_t)3, 0xfffffffcu); }
+// ---- A library job: stages that execute a plan.  What the ranks send each other is decided in job_plan.h (plan_job, judge);
+// nothing below decides a size, an offset or a form.
 
-Status job_buffers(NeedleHipLibrary *lib, NeedleHipLibrary::Job &j, int world) {
-  if (!j.searched) NEEDLE_HIP_TRY(hipEventCreateWithFlags(&j.searched, hipEventDisableTiming));
-  if (!j.done) NEEDLE_HIP_TRY(hipEventCreateWithFlags(&j.done, hipEventDisableTiming));
-  if (j.slab_runs != lib->slab_runs || j.world != world) {
-    j.slab_runs = lib->slab_runs;
-    j.world = world;
-    j.d_slabs.release();
-    Status s = j.d_slabs.reserve(j.slab_bytes());  // this rank's slab only: the other ranks' runs arrive as heads
-    if (!s.ok()) return s;
-  }
-  // the one-trip download: everything the last job needed plus a margin, the whole slab while that is small
-  uint32_t head = lib->last_max_count ? round_up4((uint64_t)lib->last_max_count + lib->last_max_count / 8 + 64) : 4096u;
-  const char *forced = lib->last_max_count ? nullptr : getenv("NEEDLE_HIP_HEAD_RUNS");  // tests: a first head that overflows
-  if (forced) head = round_up4((uint64_t)std::max(4, atoi(forced)));
-  head = std::min(head, j.slab_runs);
-  if (!forced && j.slab_bytes() * (size_t)world <= (1u << 20)) head = j.slab_runs;
-  j.head_runs = head;
-  const size_t want = j.head_bytes() * (size_t)world;
-  if (world > 1) {
-    Status s = j.d_heads.reserve(want);
-    if (!s.ok()) return s;
-  }
-  if (want > j.host_bytes) {
-    if (j.host) (void)hipHostFree(j.host);
-    j.host = nullptr;
-    j.host_bytes = 0;
-    NEEDLE_HIP_TRY(hipHostMalloc(&j.host, want + want / 4, hipHostMallocDefault));
-    j.host_bytes = want + want / 4;
-  }
-  return Status::Ok();
+// Every environment hook of the job path.  Read again at every job_begin, every repeat and every job_end: the tests change
+// them between the jobs of one process.
+JobHook hook(const char *name) {
+  const char *e = getenv(name);
+  return JobHook{e != nullptr, e ? atoi(e) : 0};
+}
+JobSwitches job_switches() {
+  JobSwitches sw;
+  sw.device_epilogue = hook("NEEDLE_HIP_DEVICE_EPILOGUE");
+  sw.shard_epilogue = hook("NEEDLE_HIP_SHARD_EPILOGUE");
+  sw.shard_epilogue_pairs = hook("NEEDLE_HIP_SHARD_EPILOGUE_PAIRS");
+  sw.directed_runs = hook("NEEDLE_HIP_DIRECTED_RUNS");
+  sw.head_runs = hook("NEEDLE_HIP_HEAD_RUNS");
+  sw.slab_runs = hook("NEEDLE_HIP_SLAB_RUNS");
+  sw.test_directed_cap = hook("NEEDLE_HIP_TEST_DIRECTED_CAP");
+  sw.test_epilogue_fail_rank = hook("NEEDLE_HIP_TEST_EPILOGUE_FAIL_RANK");
+  return sw;
 }
 
-// The per-video epilogue on the device (epilogue.hip) instead of on host threads: at library scale, where the host form
-// takes tens of milliseconds and every rank of a node has only its share of the CPUs.  Decided when the job is enqueued
-// (the run count is not known yet): by the number of sequence pairs, or NEEDLE_HIP_DEVICE_EPILOGUE=1 / 0.
-bool device_epilogue_wanted(const NeedleHipLibrary *lib, size_t comparator_regions) {
-  if (const char *e = getenv("NEEDLE_HIP_DEVICE_EPILOGUE")) return atoi(e) != 0;
-  // ... or by what the library's last finished job found (round 6): content decides the run count -- 28 episodes with
-  // stretches of silence give their 378 pairs 41 528 runs instead of 852, and the host form 2.5 ms of a 0.5 ms job.
-  // (Every rank sees every rank's count: the same decision everywhere.)
-  return (uint64_t)pair_count(lib->n) * comparator_regions >= kDeviceEpiloguePairs || lib->last_max_count >= kDeviceEpilogueRuns;
+using Job = NeedleHipLibrary::Job;
+uint32_t *slab_count_word(uint8_t *slab) { return reinterpret_cast<uint32_t *>(slab); }
+NeedleHipRun *slab_runs_of(uint8_t *slab) { return reinterpret_cast<NeedleHipRun *>(slab + kSlabHeader); }
+const NeedleHipRun *slab_runs_of(const void *slab) {
+  return reinterpret_cast<const NeedleHipRun *>(static_cast<const uint8_t *>(slab) + kSlabHeader);
 }
 
-// Owner-directed job: the runs this rank received (its own videos' pairs), downloaded once, on demand.
-Status fetch_directed(NeedleHipLibrary::Job &j, int world, int rank) {
-  if (j.fetched_valid) return Status::Ok();
-  const size_t W = (size_t)world, cw = NeedleHipLibrary::Job::count_words(world);
-  const uint32_t *m = static_cast<const uint32_t *>(j.host_counts);
-  size_t total = 0, off = 0;
-  for (size_t r = 0; r < W; r++) total += std::min(m[r * cw + 1 + (size_t)rank], j.cap[r * W + (size_t)rank]);
-  j.fetched.resize(total);
-  size_t at = 0;
-  for (size_t r = 0; r < W; r++) {
-    const uint32_t cap = j.cap[r * W + (size_t)rank], have = std::min(m[r * cw + 1 + (size_t)rank], cap);
-    if (have)
-      NEEDLE_HIP_TRY(hipMemcpyAsync(j.fetched.data() + at, j.d_dir_recv.ptr + off + NeedleHipLibrary::kSlabHeader,
-                                    (size_t)have * sizeof(NeedleHipRun), hipMemcpyDeviceToHost, download_stream()));
-    at += have;
-    off += NeedleHipLibrary::kSlabHeader + (size_t)cap * sizeof(NeedleHipRun);
+// Events and buffers for a plan: this rank's slab, the heads of all ranks on the device and pinned.  Grow only.
+Status job_buffers(Job::Buffers &b, const JobPlan &p) {
+  if (!b.searched) NEEDLE_HIP_TRY(hipEventCreateWithFlags(&b.searched, hipEventDisableTiming));
+  if (!b.done) NEEDLE_HIP_TRY(hipEventCreateWithFlags(&b.done, hipEventDisableTiming));
+  Status s;
+  if (b.slab_runs != p.slab_runs || b.world != p.shape.world) {
+    b.slab_runs = p.slab_runs;
+    b.world = p.shape.world;
+    b.d_slabs.release();
+    if (!(s = b.d_slabs.reserve(slab_bytes(p.slab_runs))).ok()) return s;
   }
-  NEEDLE_HIP_TRY(hipStreamSynchronize(download_stream()));
-  j.fetched_valid = true;
-  return Status::Ok();
+  if (p.shape.world > 1 && !(s = b.d_heads.reserve(p.pinned_bytes)).ok()) return s;
+  if (p.pinned_bytes > b.host.bytes) s = b.host.reserve(p.pinned_bytes + p.pinned_bytes / 4);
+  return s;
 }
 
-// scan of this rank's pair range into its slab, gather of the slabs, download of their heads: all asynchronous
-NeedleError job_search_and_gather(NeedleHipLibrary *lib, const NeedleAudioComparator *comparator, NeedleHipLibrary::Job &j) {
-  const int world = comm_world(), rank = comm_rank();
-  size_t pfirst = 0, pcount = 0;
-  shard_range(pair_count(lib->n), world, rank, &pfirst, &pcount);
-  uint8_t *mine = j.d_slabs.ptr;
-  NeedleError e = needle_hip_library_search(lib, comparator, pfirst, pcount,
-                                            reinterpret_cast<NeedleHipRun *>(mine + NeedleHipLibrary::kSlabHeader), j.slab_runs,
-                                            reinterpret_cast<uint32_t *>(mine), false);
+// Stage 1: the plan of this attempt, from what the last finished job -- or this job's last attempt -- left, and buffers for it.
+// On a repeat the WHOLE plan is made again, so the form can change between a job's first attempt and its repeat.
+NeedleError job_plan_stage(NeedleHipLibrary *lib, const NeedleAudioComparator *comparator, Job &j, uint32_t keep_head = 0) {
+  JobShape shape;
+  shape.n = lib->n;
+  shape.arena_regions = lib->regions();
+  shape.comparator_regions = comparator_of(comparator).include_endings() ? 2 : 1;
+  shape.world = comm_world();
+  shape.rank = comm_rank();
+  j.planned.plan = plan_job(shape, job_switches(), lib->history, keep_head);
+  const JobPlan &p = j.planned.plan;
+  lib->history.slab_runs = p.slab_runs;  // (a first slab sticks)
+  if (p.directed.cap_consumed) lib->history.dir_cap_forced = true;
+  Status s = job_buffers(j.buf, p);
+  return s.ok() ? NeedleError_Ok : report(s);
+}
+
+// Stage 2: the scan of this rank's pair range into its slab; the download stream waits for it.
+NeedleError job_scan(NeedleHipLibrary *lib, const NeedleAudioComparator *comparator, Job &j) {
+  const JobPlan &p = j.planned.plan;
+  uint8_t *mine = j.buf.d_slabs.ptr;
+  NeedleError e = needle_hip_library_search(lib, comparator, p.pair_first, p.pair_count, slab_runs_of(mine), p.slab_runs,
+                                            slab_count_word(mine), false);
   if (e != NeedleError_Ok) return e;
-  {
-    // the form of THIS job's scan, taken as it is enqueued: by job_end the process's last launch may be another job's,
-    // with another comparator (threshold) and so another form
-    int32_t form = 0;
-    uint64_t products = 0;
-    gpu_scan_last_launch(&form, &products);
-    j.scan_form = (uint32_t)form;
-  }
-  hipStream_t stream = library_stream(), down = download_stream();
-  if (hipEventRecord(j.searched, stream) != hipSuccess || hipStreamWaitEvent(down, j.searched, 0) != hipSuccess)
+  // the form of THIS job's scan, taken as it is enqueued: by job_end the process's last launch may be another job's,
+  // with another comparator (threshold) and so another form
+  int32_t form = 0;
+  uint64_t products = 0;
+  gpu_scan_last_launch(&form, &products);
+  j.planned.scan_form = (uint32_t)form;
+  if (hipEventRecord(j.buf.searched, library_stream()) != hipSuccess || hipStreamWaitEvent(download_stream(), j.buf.searched, 0) != hipSuccess)
     return report(Status::Make(NeedleError_Unknown, "stream ordering failed"));
-  // The epilogue's form first (the exchange depends on it): on the device or on host threads, every rank for all videos
-  // or -- more than one rank and a library large enough to pay for one more collective -- each for its own block (the
-  // decision cannot wait for the run count: the pairs stand in for it).
-  const Comparator &cmp = comparator_of(comparator);
-  const size_t Rc = cmp.include_endings() ? 2 : 1;
-  j.device_epilogue = device_epilogue_wanted(lib, Rc) && lib->n >= 2;
-  j.shape_fixed = j.device_epilogue;
-  if (j.device_epilogue) {
-    uint64_t shard_from = 1u << 16;
-    if (const char *e = getenv("NEEDLE_HIP_SHARD_EPILOGUE_PAIRS")) shard_from = (uint64_t)std::max(1, atoi(e));  // tests
-    j.sharded = world > 1 && (getenv("NEEDLE_HIP_SHARD_EPILOGUE") ? atoi(getenv("NEEDLE_HIP_SHARD_EPILOGUE")) != 0
-                                                                   : (uint64_t)pair_count(lib->n) * Rc >= shard_from);
-  }
-  // Owner-directed exchange (Job): with the sharded device epilogue a rank needs the runs of its own videos' pairs only.
-  j.counted = j.directed = false;
-  j.cap.clear();
-  j.fetched_valid = false;
-  const char *dir_env = getenv("NEEDLE_HIP_DIRECTED_RUNS");  // 0: every job travels as heads (measurements, tests)
-  const bool want_directed = world > 1 && world <= 64 && j.device_epilogue && j.sharded && !lib->dir_unsupported &&
-                             !(dir_env && atoi(dir_env) == 0);
-  std::vector<size_t> recv_off((size_t)world, 0), recv_bytes((size_t)world, 0);
-  if (want_directed) {
-    const size_t W = (size_t)world;
-    const bool have = lib->dir_world == world && lib->dir_counts.size() == W * W;
-    std::vector<uint32_t> cap(W * W, 0u);
-    if (have)
-      for (size_t k = 0; k < W * W; k++) cap[k] = round_up4((uint64_t)lib->dir_counts[k] + lib->dir_counts[k] / 8 + 64);
-    if (const char *e = getenv("NEEDLE_HIP_TEST_DIRECTED_CAP"))  // tests: the library's first directed job gets blocks that overflow
-      if (have && !lib->dir_cap_forced) {
-        std::fill(cap.begin(), cap.end(), round_up4((uint64_t)std::max(4, atoi(e))));
-        lib->dir_cap_forced = true;
-      }
-    DirectPlan plan;
-    std::memset(&plan, 0, sizeof(plan));
-    std::vector<size_t> send_off(W), send_bytes(W);
-    size_t off = 0, largest = 0;
-    for (size_t q = 0; q < W; q++) {
-      plan.offset[q] = (uint32_t)off;
-      plan.capacity[q] = cap[(size_t)rank * W + q];
-      send_off[q] = off;
-      send_bytes[q] = NeedleHipLibrary::kSlabHeader + (size_t)plan.capacity[q] * sizeof(NeedleHipRun);
-      off += send_bytes[q];
-    }
-    for (size_t k = 0; k < W * W; k++) largest = std::max(largest, NeedleHipLibrary::kSlabHeader + (size_t)cap[k] * sizeof(NeedleHipRun));
-    if (off >= 0xFFFFFFF0ull) return report(Status::Make(NeedleError_InvalidArgument, "directed run exchange: blocks beyond 4 GiB"));
-    const size_t cw = NeedleHipLibrary::Job::count_words(world);
-    Status s = j.d_dir_send.reserve(off);
-    if (s.ok()) s = j.d_dir_counts.reserve(cw * W);
-    if (s.ok() && cw * W * sizeof(uint32_t) > j.host_counts_bytes) {
-      if (j.host_counts) (void)hipHostFree(j.host_counts);
-      j.host_counts = nullptr;
-      j.host_counts_bytes = 0;
-      if (hipHostMalloc(&j.host_counts, cw * W * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
-        s = Status::Make(NeedleError_Unknown, "pinned allocation failed");
-      else
-        j.host_counts_bytes = cw * W * sizeof(uint32_t);
-    }
-    if (s.ok())
-      s = gpu_direct_runs(reinterpret_cast<const uint32_t *>(mine), reinterpret_cast<const NeedleHipRun *>(mine + NeedleHipLibrary::kSlabHeader),
-                          j.slab_runs, (uint32_t)lib->n, (uint32_t)Rc, (uint32_t)shard_block(lib->n, world), world, j.d_dir_send.ptr, plan, down);
-    if (!s.ok()) return report(s);
-    // this rank's row of the count matrix: [runs in its slab, runs directed to rank 0, 1, ...]; every rank gets every row
-    uint32_t *row = j.d_dir_counts.ptr + (size_t)rank * cw;
-    bool ok = hipMemsetAsync(row, 0, cw * sizeof(uint32_t), down) == hipSuccess &&
-              hipMemcpyAsync(row, mine, sizeof(uint32_t), hipMemcpyDeviceToDevice, down) == hipSuccess;
-    for (size_t q = 0; q < W && ok; q++)
-      ok = hipMemcpyAsync(row + 1 + q, j.d_dir_send.ptr + send_off[q], sizeof(uint32_t), hipMemcpyDeviceToDevice, down) == hipSuccess;
-    if (!ok) return report(Status::Make(NeedleError_Unknown, "directed run exchange: count row failed"));
-    s = comm_all_gather(kSide, row, j.d_dir_counts.ptr, cw * sizeof(uint32_t), down);
-    if (!s.ok()) return report(s);
-    if (hipMemcpyAsync(j.host_counts, j.d_dir_counts.ptr, cw * W * sizeof(uint32_t), hipMemcpyDeviceToHost, down) != hipSuccess)
-      return report(Status::Make(NeedleError_Unknown, "directed run exchange: count download failed"));
-    j.counted = true;
-    j.comm_bytes[1] += cw * W * sizeof(uint32_t);
-    if (have) {
-      size_t roff = 0;
-      for (size_t r = 0; r < W; r++) {
-        recv_off[r] = roff;
-        recv_bytes[r] = NeedleHipLibrary::kSlabHeader + (size_t)cap[r * W + (size_t)rank] * sizeof(NeedleHipRun);
-        roff += recv_bytes[r];
-      }
-      if (!(s = j.d_dir_recv.reserve(roff)).ok()) return report(s);
-      s = comm_all_to_all_v(kSide, j.d_dir_send.ptr, send_off.data(), send_bytes.data(), j.d_dir_recv.ptr, recv_off.data(), recv_bytes.data(),
-                            largest, down);
-      if (s.ok()) {
-        j.directed = true;
-        j.cap = cap;
-        j.comm_bytes[1] += roff;
-      } else if (s.message.find("unsupported") != std::string::npos) {
-        lib->dir_unsupported = true;  // (every rank loads the same librccl: every rank lands here, before any transfer)
-        (void)hipGetLastError();
-      } else {
-        return report(s);
-      }
-    }
-  }
-  // What travels otherwise is the HEAD of every rank's slab -- its count and as many runs as the last job needed plus a margin
-  // (job_buffers) -- not the slab's capacity: at BASELINE.json configs[4] on 8 GPUs a slab is 24 MB per rank and the
-  // runs found 13 MB.  The heads land side by side in d_heads and come down in ONE copy; a rank whose count exceeds the
-  // head is handled like a slab overflow in job_end (every rank sees every count): the head grows, the job's scan
-  // and gather are repeated, the size sticks.  One rank: the head is copied straight out of the slab.
-  const uint8_t *src = mine;
-  if (!j.directed) {
-    if (world > 1) {
-      Status s = comm_all_gather(kSide, mine, j.d_heads.ptr, j.head_bytes(), down);
-      if (!s.ok()) return report(s);
-      src = j.d_heads.ptr;
-      j.comm_bytes[1] += j.head_bytes() * (uint64_t)world;
-    }
-    if (hipMemcpyAsync(j.host, src, j.head_bytes() * (size_t)world, hipMemcpyDeviceToHost, down) != hipSuccess)
-      return report(Status::Make(NeedleError_Unknown, "asynchronous run download failed"));
-  }
-  if (j.device_epilogue) {
-    const size_t want = (lib->n + 1) * sizeof(NeedleHipSearchResult);
-    if (want > j.host_results_bytes) {
-      if (j.host_results) (void)hipHostFree(j.host_results);
-      j.host_results = nullptr;
-      j.host_results_bytes = 0;
-      if (hipHostMalloc(&j.host_results, want, hipHostMallocDefault) != hipSuccess)
-        return report(Status::Make(NeedleError_Unknown, "pinned allocation failed"));
-      j.host_results_bytes = want;
-    }
-    lib->ensure_row_tables();
-    EpilogueJob ej;
-    ej.slot = (int)(&j - lib->job);
-    ej.n = (uint32_t)lib->n;
-    ej.regions = (uint32_t)Rc;
-    ej.rows_per_video = (uint32_t)lib->regions();
-    size_t v0 = 0, vcount = lib->n;
-    if (j.sharded) shard_range(lib->n, world, rank, &v0, &vcount);
-    ej.v0 = (uint32_t)v0;
-    ej.v1 = (uint32_t)(v0 + vcount);
-    ej.threshold = cmp.hash_match_threshold();
-    ej.include_endings = cmp.include_endings();
-    ej.min_opening_duration = cmp.min_opening_duration();
-    ej.min_ending_duration = cmp.min_ending_duration();
-    ej.time_padding = cmp.time_padding();
-    ej.hash_duration = lib->hash_duration;
-    ej.num_segments = world;
-    auto segment = [&](int k, const uint8_t *slab) {  // a slab: 32-byte header (word 0 = runs found), then the runs
-      ej.segment_count[k] = reinterpret_cast<const uint32_t *>(slab);
-      ej.segment_runs[k] = reinterpret_cast<const NeedleHipRun *>(slab + NeedleHipLibrary::kSlabHeader);
-    };
-    if (j.directed) {  // the blocks received: one segment per source rank, each of its own capacity
-      ej.max_runs = 0;
-      for (int r = 0; r < world; r++) {
-        segment(r, j.d_dir_recv.ptr + recv_off[(size_t)r]);
-        ej.segment_capacities[r] = j.cap[(size_t)r * (size_t)world + (size_t)rank];
-        ej.max_runs += ej.segment_capacities[r];
-      }
-      ej.segment_capacity = 0;
-    } else if (world > 1) {
-      for (int r = 0; r < world && r < 64; r++) segment(r, j.d_heads.ptr + (size_t)r * j.head_bytes());
-      ej.segment_capacity = j.head_runs;
-      ej.max_runs = (uint64_t)ej.segment_capacity * (uint64_t)world;
-    } else {
-      segment(0, mine);
-      ej.segment_capacity = j.slab_runs;
-      ej.max_runs = (uint64_t)ej.segment_capacity * (uint64_t)world;
-    }
-    ej.row_len = &lib->row_len;
-    ej.row_ts = &lib->row_ts;
-    ej.row_seek = &lib->row_seek;
-    ej.ts = &lib->ts_tables;
-    NeedleHipSearchResult *hr = static_cast<NeedleHipSearchResult *>(j.host_results);
-    Status s = world <= 64 ? gpu_epilogue_enqueue(ej, down, hr, reinterpret_cast<uint32_t *>(hr + lib->n))
-                           : Status::Make(NeedleError_InvalidArgument, "device epilogue: more than 64 ranks");
-    if (const char *e = getenv("NEEDLE_HIP_TEST_EPILOGUE_FAIL_RANK"))  // tests: the device form "fails" on one rank alone
-      if (atoi(e) == rank) s = Status::Make(NeedleError_Unknown, "device epilogue: failure injected by the test");
-    if (!s.ok()) {  // (workspaces that do not fit: the host form computes the same results from the downloaded run list --
-      j.device_epilogue = false;  // for the same block of videos, j.sharded stands: a rank that fell back alone must still
-      (void)hipGetLastError();    // meet the others in the collective they enter, or not enter one they skip)
-    }
-  }
-  if (hipEventRecord(j.done, down) != hipSuccess)
-    return report(Status::Make(NeedleError_Unknown, "asynchronous run download failed"));
   return NeedleError_Ok;
 }
 
-bool shard_epilogue(size_t total_runs) {
-  // Sharding the per-video epilogue costs one more (small) collective; it pays once the epilogue is milliseconds.
-  if (const char *e = getenv("NEEDLE_HIP_SHARD_EPILOGUE")) return atoi(e) != 0;
-  return total_runs >= (1u << 17);
+// Stage 3a, directed exchange: this rank's runs sorted into one block per destination, and the count matrix -- this rank's
+// row [runs in its slab, runs directed to rank 0, 1, ...] gathered from every rank and downloaded.  A job without block
+// sizes (plan.directed.sized) does this much: it counts, and travels as heads.
+Status job_count_directed(Job &j) {
+  const JobPlan &p = j.planned.plan;
+  const DirectedPlan &d = p.directed;
+  const int world = p.shape.world;
+  const size_t W = (size_t)world, cw = count_words(world);
+  hipStream_t down = download_stream();
+  uint8_t *mine = j.buf.d_slabs.ptr;
+  if (d.refused) return Status::Make(NeedleError_InvalidArgument, "directed run exchange: blocks beyond 4 GiB");
+  DirectPlan blocks;
+  std::memset(&blocks, 0, sizeof(blocks));
+  for (size_t q = 0; q < W; q++) {
+    blocks.offset[q] = (uint32_t)d.send_off[q];
+    blocks.capacity[q] = d.send_capacity[q];
+  }
+  Status s = j.buf.d_dir_send.reserve(d.send_total);
+  if (s.ok()) s = j.buf.d_dir_counts.reserve(cw * W);
+  if (s.ok()) s = j.buf.host_counts.reserve(count_matrix_bytes(world));
+  if (s.ok())
+    s = gpu_direct_runs(slab_count_word(mine), slab_runs_of(mine), p.slab_runs, (uint32_t)p.shape.n, (uint32_t)p.shape.comparator_regions,
+                        (uint32_t)shard_block(p.shape.n, world), world, j.buf.d_dir_send.ptr, blocks, down);
+  if (!s.ok()) return s;
+  uint32_t *row = j.buf.d_dir_counts.ptr + (size_t)p.shape.rank * cw;
+  bool ok = hipMemsetAsync(row, 0, cw * sizeof(uint32_t), down) == hipSuccess &&
+            hipMemcpyAsync(row, mine, sizeof(uint32_t), hipMemcpyDeviceToDevice, down) == hipSuccess;
+  for (size_t q = 0; q < W && ok; q++)
+    ok = hipMemcpyAsync(row + 1 + q, j.buf.d_dir_send.ptr + d.send_off[q], sizeof(uint32_t), hipMemcpyDeviceToDevice, down) == hipSuccess;
+  if (!ok) return Status::Make(NeedleError_Unknown, "directed run exchange: count row failed");
+  if (!(s = comm_all_gather(kSide, row, j.buf.d_dir_counts.ptr, cw * sizeof(uint32_t), down)).ok()) return s;
+  if (hipMemcpyAsync(j.buf.host_counts.ptr, j.buf.d_dir_counts.ptr, count_matrix_bytes(world), hipMemcpyDeviceToHost, down) != hipSuccess)
+    return Status::Make(NeedleError_Unknown, "directed run exchange: count download failed");
+  j.planned.counted = true;
+  j.found.comm_bytes[1] += count_matrix_bytes(world);
+  return Status::Ok();
+}
+
+// Stage 3b: the all-to-all of the blocks.  A librccl without point-to-point transfers says "unsupported" before any transfer,
+// on every rank (every rank loads the same library): from here on this library's jobs travel as heads, this one included.
+Status job_exchange_directed(NeedleHipLibrary *lib, Job &j) {
+  JobPlan &p = j.planned.plan;
+  const DirectedPlan &d = p.directed;
+  Status s = j.buf.d_dir_recv.reserve(d.recv_total);
+  if (!s.ok()) return s;
+  s = comm_all_to_all_v(kSide, j.buf.d_dir_send.ptr, d.send_off.data(), d.send_bytes.data(), j.buf.d_dir_recv.ptr, d.recv_off.data(),
+                        d.recv_bytes.data(), d.max_block_bytes, download_stream());
+  if (s.ok()) {
+    j.planned.directed = true;
+    j.found.comm_bytes[1] += d.recv_total;
+  } else if (s.message.find("unsupported") != std::string::npos) {
+    lib->history.dir_unsupported = true;
+    p.segments = segment_layout(p, false);
+    (void)hipGetLastError();
+    return Status::Ok();
+  }
+  return s;
+}
+
+// Stage 4, a job that does not travel directed: what travels is the HEAD of every rank's slab -- its count and as many runs as
+// the last job needed plus a margin -- not the slab's capacity: at BASELINE.json configs[4] on 8 GPUs a slab is 24 MB per
+// rank and the runs found 13 MB.  The heads land side by side in d_heads and come down in ONE copy; a rank whose count
+// exceeds the head is job_end's case (every rank sees every count).  One rank: the head is copied straight out of the slab.
+Status job_gather_heads(Job &j) {
+  const JobPlan &p = j.planned.plan;
+  const uint8_t *src = j.buf.d_slabs.ptr;
+  if (p.shape.world > 1) {
+    Status s = comm_all_gather(kSide, j.buf.d_slabs.ptr, j.buf.d_heads.ptr, p.head_bytes(), download_stream());
+    if (!s.ok()) return s;
+    src = j.buf.d_heads.ptr;
+    j.found.comm_bytes[1] += p.head_bytes() * (uint64_t)p.shape.world;
+  }
+  if (hipMemcpyAsync(j.buf.host.ptr, src, p.head_bytes() * (size_t)p.shape.world, hipMemcpyDeviceToHost, download_stream()) != hipSuccess)
+    return Status::Make(NeedleError_Unknown, "asynchronous run download failed");
+  return Status::Ok();
+}
+
+// Stage 5: the device epilogue behind the exchange, its segments as the plan lays them out.  A rank on which it fails
+// (workspaces that do not fit, more than 64 ranks) computes the same results on the host from the downloaded run list, for
+// the same block of videos: plan.sharded stands (shape_fixed) -- a rank that fell back alone must still meet the others in
+// the collective they enter, or not enter one they skip.
+Status job_device_epilogue(NeedleHipLibrary *lib, const Comparator &cmp, Job &j) {
+  const JobPlan &p = j.planned.plan;
+  const int world = p.shape.world;
+  Status s = j.buf.host_results.reserve((lib->n + 1) * sizeof(NeedleHipSearchResult));
+  if (!s.ok()) return s;
+  lib->ensure_row_tables();
+  EpilogueJob ej;
+  ej.slot = (int)(&j - lib->job);
+  ej.n = (uint32_t)lib->n;
+  ej.regions = (uint32_t)p.shape.comparator_regions;
+  ej.rows_per_video = (uint32_t)lib->regions();
+  ej.v0 = (uint32_t)p.video_first;
+  ej.v1 = (uint32_t)(p.video_first + p.video_count);
+  ej.threshold = cmp.hash_match_threshold();
+  ej.include_endings = cmp.include_endings();
+  ej.min_opening_duration = cmp.min_opening_duration();
+  ej.min_ending_duration = cmp.min_ending_duration();
+  ej.time_padding = cmp.time_padding();
+  ej.hash_duration = lib->hash_duration;
+  ej.num_segments = world;
+  const SegmentLayout &seg = p.segments;
+  for (int r = 0; r < world && r < 64; r++) {  // (EpilogueJob has 64 segments; a larger world is refused below)
+    const uint8_t *slab = seg.kind == SegmentKind::Blocks  ? j.buf.d_dir_recv.ptr + p.directed.recv_off[(size_t)r]
+                          : seg.kind == SegmentKind::Heads ? j.buf.d_heads.ptr + (size_t)r * p.head_bytes()
+                                                           : j.buf.d_slabs.ptr;
+    ej.segment_count[r] = reinterpret_cast<const uint32_t *>(slab);
+    ej.segment_runs[r] = slab_runs_of(slab);
+    if (seg.kind == SegmentKind::Blocks) ej.segment_capacities[r] = seg.capacities[(size_t)r];
+  }
+  ej.segment_capacity = seg.capacity;
+  ej.max_runs = seg.max_runs;
+  ej.row_len = &lib->row_len;
+  ej.row_ts = &lib->row_ts;
+  ej.row_seek = &lib->row_seek;
+  ej.ts = &lib->ts_tables;
+  NeedleHipSearchResult *hr = static_cast<NeedleHipSearchResult *>(j.buf.host_results.ptr);
+  s = world <= 64 ? gpu_epilogue_enqueue(ej, download_stream(), hr, reinterpret_cast<uint32_t *>(hr + lib->n))
+                  : Status::Make(NeedleError_InvalidArgument, "device epilogue: more than 64 ranks");
+  if (p.inject_epilogue_failure) s = Status::Make(NeedleError_Unknown, "device epilogue: failure injected by the test");
+  if (!s.ok()) {
+    j.planned.device_epilogue = false;
+    (void)hipGetLastError();
+  }
+  return Status::Ok();
+}
+
+// Stages 2 to 5 of the planned job: scan, exchange of the runs, download of the counts, epilogue -- all asynchronous.
+NeedleError job_enqueue(NeedleHipLibrary *lib, const NeedleAudioComparator *comparator, Job &j) {
+  const JobPlan &p = j.planned.plan;
+  NeedleError e = job_scan(lib, comparator, j);
+  if (e != NeedleError_Ok) return e;
+  j.planned.device_epilogue = p.device_epilogue;
+  j.planned.counted = j.planned.directed = false;
+  j.found.fetched_valid = false;
+  Status s;
+  if (p.directed.wanted) s = job_count_directed(j);
+  if (s.ok() && p.directed.wanted && p.directed.sized) s = job_exchange_directed(lib, j);
+  if (s.ok() && !j.planned.directed) s = job_gather_heads(j);
+  if (s.ok() && p.device_epilogue) s = job_device_epilogue(lib, comparator_of(comparator), j);
+  if (s.ok() && hipEventRecord(j.buf.done, download_stream()) != hipSuccess) s = Status::Make(NeedleError_Unknown, "asynchronous run download failed");
+  return s.ok() ? NeedleError_Ok : report(s);
+}
+
+// Owner-directed job: the runs this rank received (its own videos' pairs), downloaded once, on demand.
+Status fetch_directed(Job &j) {
+  if (j.found.fetched_valid) return Status::Ok();
+  const JobPlan &p = j.planned.plan;
+  const size_t W = (size_t)p.shape.world, rank = (size_t)p.shape.rank;
+  const uint32_t *m = static_cast<const uint32_t *>(j.buf.host_counts.ptr);
+  auto have = [&](size_t r) { return std::min(directed_count(m, p.shape.world, r, rank), p.directed.cap[r * W + rank]); };
+  size_t total = 0, at = 0;
+  for (size_t r = 0; r < W; r++) total += have(r);
+  j.found.fetched.resize(total);
+  for (size_t r = 0; r < W; r++) {
+    if (have(r))
+      NEEDLE_HIP_TRY(hipMemcpyAsync(j.found.fetched.data() + at, slab_runs_of(j.buf.d_dir_recv.ptr + p.directed.recv_off[r]),
+                                    (size_t)have(r) * sizeof(NeedleHipRun), hipMemcpyDeviceToHost, download_stream()));
+    at += have(r);
+  }
+  NEEDLE_HIP_TRY(hipStreamSynchronize(download_stream()));
+  j.found.fetched_valid = true;
+  return Status::Ok();
+}
+
+// job_end, first part: wait for the counts, judge them (job_plan.h), and while something overflowed repeat the job under a new
+// plan -- every rank sees the same counts, so every rank repeats or none does.  The scan is deterministic and the arena
+// still holds the hashes, whether or not the next job's analyze has run in between (same PCM, same rows).
+NeedleError job_settle(NeedleHipLibrary *lib, const NeedleAudioComparator *comparator, Job &j, std::vector<uint32_t> *counts) {
+  for (;;) {
+    if (hipEventSynchronize(j.buf.done) != hipSuccess) return report(Status::Make(NeedleError_Unknown, "run download failed"));
+    const JobPlan &p = j.planned.plan;
+    const int world = p.shape.world;
+    JobCounts c;
+    if (j.planned.counted) c = counts_from_matrix(static_cast<const uint32_t *>(j.buf.host_counts.ptr), world, j.planned.directed);
+    if (!j.planned.directed) {  // the heads came down: word 0 of each
+      c.slab.resize((size_t)world);
+      for (size_t r = 0; r < (size_t)world; r++)
+        c.slab[r] = *reinterpret_cast<const uint32_t *>(static_cast<const char *>(j.buf.host.ptr) + r * p.head_bytes());
+    }
+    JobVerdict v = judge(p, c, lib->history);
+    lib->history = std::move(v.history);
+    switch (v.next) {
+      case JobNext::Done:
+        *counts = std::move(c.slab);
+        return NeedleError_Ok;
+      case JobNext::GrowHead:    // some rank's list is longer than the head that was gathered: head_runs follows last_max_count
+      case JobNext::GrowBlocks:  // a block overflowed: the sizes follow the matrix just taken.  (The slab is intact; the scan is repeated all
+                                 // the same.  The head alone stays as it was: v.keep_head.)
+      case JobNext::GrowSlab:    // some rank found more runs than a slab holds: history.slab_runs grew
+        break;
+    }
+    NeedleError e = job_plan_stage(lib, comparator, j, v.keep_head);
+    if (e == NeedleError_Ok) e = job_enqueue(lib, comparator, j);
+    if (e != NeedleError_Ok) return e;
+    j.found.comm_bytes[3]++;
+  }
+}
+
+// The run list of all ranks: heads from the pinned buffer, tails (rare: one rank, the first job of a library) straight out of
+// its own slab.  A directed job's runs stayed on the devices: each rank holds its own videos' (fetch_directed, on demand),
+// and needle_hip_library_job_runs returns that share although job_end's count is the global total.
+Status job_collect_runs(Job &j, const std::vector<uint32_t> &counts, const NeedleHipRun **run_list, size_t *total) {
+  const JobPlan &p = j.planned.plan;
+  const int world = p.shape.world;
+  const char *host = static_cast<const char *>(j.buf.host.ptr);
+  *total = 0;
+  for (int r = 0; r < world; r++) *total += counts[r];
+  *run_list = nullptr;
+  j.found.merged.clear();
+  if (j.planned.directed) return Status::Ok();
+  if (world == 1 && counts[0] <= p.head_runs) {  // one rank, everything in the pinned head: no copy of ~100 MB at library scale
+    *run_list = slab_runs_of(host);
+    return Status::Ok();
+  }
+  j.found.merged.resize(*total);
+  size_t at = 0;
+  bool tails = false;
+  for (int r = 0; r < world; r++) {
+    const uint32_t head = std::min(counts[r], p.head_runs);
+    std::memcpy(j.found.merged.data() + at, slab_runs_of(host + (size_t)r * p.head_bytes()), (size_t)head * sizeof(NeedleHipRun));
+    if (counts[r] > head) {
+      tails = true;
+      if (hipMemcpyAsync(j.found.merged.data() + at + head, slab_runs_of(j.buf.d_slabs.ptr + (size_t)r * slab_bytes(p.slab_runs)) + head,
+                         (size_t)(counts[r] - head) * sizeof(NeedleHipRun), hipMemcpyDeviceToHost, download_stream()) != hipSuccess)
+        return Status::Make(NeedleError_Unknown, "run download failed");
+    }
+    at += counts[r];
+  }
+  if (tails && hipStreamSynchronize(download_stream()) != hipSuccess) return Status::Make(NeedleError_Unknown, "run download failed");
+  *run_list = j.found.merged.data();
+  return Status::Ok();
+}
+
+// The order-sensitive per-video epilogue (comparator.rs:583-626) for videos [v0, v0 + vcount): what the device computed
+// behind the gather (*device_results), else the host form from the run list -- of a directed job, from the runs this rank
+// received.  *epilogue is the epilogue's own outcome: sharded, it travels with the results.  What is returned is a failure
+// to fetch the received runs, which ends job_end at once (before the gather of result blocks, as it always did).
+Status job_results(NeedleHipLibrary *lib, const Comparator &cmp, Job &j, const NeedleHipRun *run_list, size_t total, size_t v0, size_t vcount,
+                   const NeedleHipSearchResult **device_results, std::vector<VideoResult> *res, Status *epilogue) {
+  *epilogue = Status::Ok();
+  *device_results = nullptr;
+  if (j.planned.device_epilogue) {  // (j.buf.done covers its copies)
+    *device_results = static_cast<const NeedleHipSearchResult *>(j.buf.host_results.ptr);
+    const uint32_t fail = *reinterpret_cast<const uint32_t *>(*device_results + lib->n);
+    if (fail & kEpilogueBucketTooLarge) {
+      *device_results = nullptr;  // a pair with more runs than one lane should order: the host form below, same block of videos
+      note_epilogue_host_fallback("library job", total, vcount);
+    } else if (fail != 0) {
+      *epilogue = Status::Make(NeedleError_Unknown, "overflow when subtracting durations (time_padding / hash_duration exceed the match end)");
+    }
+  }
+  if (*device_results) return Status::Ok();
+  const std::vector<const FrameHashesData *> fh = lib->shell_pointers();
+  if (j.planned.directed) {  // this rank's videos' runs are what it received: down they come, once
+    Status f = fetch_directed(j);
+    if (!f.ok()) return f;
+    run_list = j.found.fetched.data();
+    total = j.found.fetched.size();
+  }
+  *epilogue = cmp.results_from_runs(fh, run_list, total, false, false, false, res, v0, v0 + vcount);
+  return Status::Ok();
+}
+
+// Sharded epilogue: every rank's block of results, gathered.  An error on one rank must not leave the others waiting in
+// the collective: it travels with the results.
+Status job_gather_results(NeedleHipLibrary *lib, Job &j, const Status &mine_status, const NeedleHipSearchResult *device_results,
+                          const std::vector<VideoResult> &res, NeedleHipSearchResult *results) {
+  const JobPlan &p = j.planned.plan;
+  const int world = p.shape.world;
+  size_t v0 = 0, vcount = 0;
+  shard_range(lib->n, world, p.shape.rank, &v0, &vcount);
+  struct Block {
+    uint64_t failed;
+  };
+  const size_t block_bytes = sizeof(Block) + shard_block(lib->n, world) * sizeof(NeedleHipSearchResult);
+  std::vector<uint8_t> mine(block_bytes, 0), all(block_bytes * (size_t)world, 0);
+  reinterpret_cast<Block *>(mine.data())->failed = mine_status.ok() ? 0 : 1;
+  if (mine_status.ok() && device_results)
+    std::memcpy(mine.data() + sizeof(Block), device_results + v0, vcount * sizeof(NeedleHipSearchResult));
+  else if (mine_status.ok())
+    for (size_t k = 0; k < vcount; k++) fill_c_result(res[v0 + k], reinterpret_cast<NeedleHipSearchResult *>(mine.data() + sizeof(Block)) + k);
+  Status g = comm_all_gather_host(mine.data(), all.data(), block_bytes);
+  j.found.comm_bytes[2] += block_bytes * (uint64_t)world;
+  if (!mine_status.ok()) return mine_status;
+  if (!g.ok()) return g;
+  for (int r = 0; r < world; r++) {
+    const uint8_t *blk = all.data() + (size_t)r * block_bytes;
+    if (reinterpret_cast<const Block *>(blk)->failed) return Status::Make(NeedleError_Unknown, "the epilogue failed on rank " + std::to_string(r));
+    size_t f = 0, c = 0;
+    shard_range(lib->n, world, r, &f, &c);
+    std::memcpy(results + f, blk + sizeof(Block), c * sizeof(NeedleHipSearchResult));
+  }
+  return Status::Ok();
+}
+
+template <typename F>
+NeedleError guarded_status(F &&f) {
+  return guarded([&]() -> NeedleError {
+    Status s = f();
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
 }
 
 }  // namespace
@@ -1257,35 +1356,23 @@ const char *needle_hip_comm_backend(void) { return comm_backend(); }
 
 enum NeedleError needle_hip_comm_create_id(uint8_t id[NEEDLE_HIP_COMM_ID_BYTES]) {
   if (!id) return NeedleError_NullArgument;
-  return guarded([&]() -> NeedleError {
-    Status s = comm_create_id(id);
-    return s.ok() ? NeedleError_Ok : report(s);
-  });
+  return guarded_status([&] { return comm_create_id(id); });
 }
 
 enum NeedleError needle_hip_comm_init(const uint8_t id[NEEDLE_HIP_COMM_ID_BYTES], int rank, int world_size) {
   if (!id) return NeedleError_NullArgument;
-  return guarded([&]() -> NeedleError {
-    Status s = comm_init(id, rank, world_size);
-    return s.ok() ? NeedleError_Ok : report(s);
-  });
+  return guarded_status([&] { return comm_init(id, rank, world_size); });
 }
 
 void needle_hip_comm_finalize(void) { comm_finalize(); }
 
 enum NeedleError needle_hip_comm_barrier(void) {
-  return guarded([&]() -> NeedleError {
-    Status s = comm_barrier();
-    return s.ok() ? NeedleError_Ok : report(s);
-  });
+  return guarded_status([&] { return comm_barrier(); });
 }
 
 enum NeedleError needle_hip_comm_all_gather_host(const void *send, void *recv, size_t bytes_per_rank) {
   if ((!send || !recv) && bytes_per_rank) return NeedleError_NullArgument;
-  return guarded([&]() -> NeedleError {
-    Status s = comm_all_gather_host(send, recv, bytes_per_rank);
-    return s.ok() ? NeedleError_Ok : report(s);
-  });
+  return guarded_status([&] { return comm_all_gather_host(send, recv, bytes_per_rank); });
 }
 
 void needle_hip_comm_shard(size_t units, int world_size, int rank, size_t *first, size_t *count) {
@@ -1344,29 +1431,24 @@ enum NeedleError needle_hip_library_job_begin(NeedleHipLibrary *lib, const struc
   if (!lib || !comparator) return NeedleError_NullArgument;
   if (slot < 0 || slot > 1 || !lib->have_pcm) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
-    NeedleHipLibrary::Job &j = lib->job[slot];
+    Job &j = lib->job[slot];
     if (j.pending) return report(Status::Make(NeedleError_InvalidArgument, "job slot still pending"));
     const int world = comm_world(), rank = comm_rank();
-    j.last_runs = nullptr;
-    j.last_total = 0;
-    std::fill(j.comm_bytes, j.comm_bytes + 4, 0);
+    j.found.last_runs = nullptr;
+    j.found.last_total = 0;
+    std::fill(j.found.comm_bytes, j.found.comm_bytes + 4, 0);
     if (!lib->flat_shardable(world))
       return report(Status::Make(NeedleError_InvalidArgument,
                                  "the hash arena does not divide into this communicator's blocks: call needle_hip_library_set_pcm "
                                  "after needle_hip_comm_init (or adopt an arena of rows x stride with rows * stride / 64 a multiple of the world size)"));
-    // (the run slabs first: the analyze step's last kernel clears this job's run counter)
-    if (lib->slab_runs == 0 && getenv("NEEDLE_HIP_SLAB_RUNS"))  // tests: a slab that overflows
-      lib->slab_runs = round_up4((uint64_t)std::max(4, atoi(getenv("NEEDLE_HIP_SLAB_RUNS"))));
-    if (lib->slab_runs == 0)
-      lib->slab_runs = round_up4(std::max<uint64_t>(1024, 4 * (uint64_t)shard_block(pair_count(lib->n), world) * lib->regions()));
-    Status sb = job_buffers(lib, j, world);
-    if (!sb.ok()) return report(sb);
+    // (the plan and the run slabs first: the analyze step's last kernel clears this job's run counter)
+    NeedleError e = job_plan_stage(lib, comparator, j);
+    if (e != NeedleError_Ok) return e;
     // 1. fingerprint this rank's block of HASHES (NeedleHipLibrary::flat_block) into the arena (analyzer.rs:437-445
     // across GPUs).  (After needle_hip_library_stream_pcm the rows are already there: the PCM was fingerprinted as it
     // was uploaded.)
     lib->count_zeroed = nullptr;
-    NeedleError e = lib->pcm_resident ? analyze_flat_block(lib, world, rank, slot, reinterpret_cast<uint32_t *>(j.d_slabs.ptr))
-                                      : NeedleError_Ok;
+    e = lib->pcm_resident ? analyze_flat_block(lib, world, rank, slot, slab_count_word(j.buf.d_slabs.ptr)) : NeedleError_Ok;
     if (e != NeedleError_Ok) return e;
     // 2. every rank gets every hash: one in-place all-gather of the equal blocks, in stream order
     if (comm_get()) {
@@ -1374,10 +1456,10 @@ enum NeedleError needle_hip_library_job_begin(NeedleHipLibrary *lib, const struc
       Status s = comm_all_gather(kData, reinterpret_cast<const uint8_t *>(lib->arena) + (size_t)rank * block_bytes, lib->arena,
                                  block_bytes, library_stream());
       if (!s.ok()) return report(s);
-      j.comm_bytes[0] += block_bytes * (uint64_t)world;
+      j.found.comm_bytes[0] += block_bytes * (uint64_t)world;
     }
-    // 3. + 4. scan this rank's pair range (comparator.rs:549-564 across GPUs), gather the run lists
-    if ((e = job_search_and_gather(lib, comparator, j)) != NeedleError_Ok) return e;
+    // 3. + 4. scan this rank's pair range (comparator.rs:549-564 across GPUs), exchange the run lists, enqueue the epilogue
+    if ((e = job_enqueue(lib, comparator, j)) != NeedleError_Ok) return e;
     j.pending = true;
     return NeedleError_Ok;
   });
@@ -1388,172 +1470,39 @@ enum NeedleError needle_hip_library_job_end(NeedleHipLibrary *lib, const struct 
   if (!lib || !comparator || !results) return NeedleError_NullArgument;
   if (slot < 0 || slot > 1 || !lib->job[slot].pending) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
-    NeedleHipLibrary::Job &j = lib->job[slot];
-    const int world = comm_world(), rank = comm_rank();
-    const Comparator &cmp = comparator_of(comparator);
-    std::vector<uint32_t> counts((size_t)world);
-    const size_t W = (size_t)world, cw = NeedleHipLibrary::Job::count_words(world);
-    auto take_matrix = [&]() {  // the job's count matrix becomes the next job's block sizes (every rank holds the same one)
-      const uint32_t *m = static_cast<const uint32_t *>(j.host_counts);
-      lib->dir_counts.assign(W * W, 0u);
-      for (size_t r = 0; r < W; r++)
-        for (size_t q = 0; q < W; q++) lib->dir_counts[r * W + q] = m[r * cw + 1 + q];
-      lib->dir_world = world;
-    };
-    for (;;) {
-      if (hipEventSynchronize(j.done) != hipSuccess) return report(Status::Make(NeedleError_Unknown, "run download failed"));
-      uint32_t most = 0;
-      if (j.directed) {  // nothing but the counts came down
-        const uint32_t *m = static_cast<const uint32_t *>(j.host_counts);
-        for (size_t r = 0; r < W; r++) {
-          counts[r] = m[r * cw];
-          most = std::max(most, counts[r]);
-        }
-        if (most <= j.slab_runs) {
-          bool fits = true;
-          for (size_t r = 0; r < W && fits; r++)
-            for (size_t q = 0; q < W && fits; q++) fits = m[r * cw + 1 + q] <= j.cap[r * W + q];
-          take_matrix();
-          lib->last_max_count = most;
-          if (fits) break;
-          // a block overflowed (every rank sees it): the sizes follow the matrix just taken, scan and exchange are repeated
-          NeedleError e = job_search_and_gather(lib, comparator, j);
-          if (e != NeedleError_Ok) return e;
-          j.comm_bytes[3]++;
-          continue;
-        }
-      } else {
-        for (int r = 0; r < world; r++) {
-          counts[r] = *reinterpret_cast<const uint32_t *>(static_cast<const char *>(j.host) + (size_t)r * j.head_bytes());
-          most = std::max(most, counts[r]);
-        }
-        if (most <= j.slab_runs && (world == 1 || most <= j.head_runs)) {
-          lib->last_max_count = most;
-          if (j.counted) take_matrix();  // (a job that travelled as heads and counted: the next one can be directed)
-          break;
-        }
-        if (most <= j.slab_runs) {  // world > 1 and some rank's list is longer than the head that was gathered
-          lib->last_max_count = most;
-          Status s = job_buffers(lib, j, world);  // head_runs from last_max_count
-          if (!s.ok()) return report(s);
-          NeedleError e = job_search_and_gather(lib, comparator, j);
-          if (e != NeedleError_Ok) return e;
-          j.comm_bytes[3]++;
-          continue;
-        }
-      }
-      // Some rank found more runs than a slab holds (every rank sees the same counts, so every rank takes this
-      // branch): grow and repeat the scan of this job -- the scan is deterministic and the arena still holds the
-      // hashes, whether or not the next job's analyze has run in between (same PCM, same rows).
-      lib->slab_runs = round_up4((uint64_t)most + most / 4 + 64);
-      lib->last_max_count = most;
-      lib->dir_counts.clear();  // (counted over a clamped slab)
-      Status s = job_buffers(lib, j, world);
-      if (!s.ok()) return report(s);
-      NeedleError e = job_search_and_gather(lib, comparator, j);
-      if (e != NeedleError_Ok) return e;
-      j.comm_bytes[3]++;
-    }
+    Job &j = lib->job[slot];
+    std::vector<uint32_t> counts;
+    NeedleError e = job_settle(lib, comparator, j, &counts);
+    if (e != NeedleError_Ok) return e;
     j.pending = false;
-    // run list of all ranks: heads from the pinned buffer, tails (rare: the first job of a library) straight from HBM
-    size_t total = 0;
-    for (int r = 0; r < world; r++) total += counts[r];
+    const JobPlan &p = j.planned.plan;
     const NeedleHipRun *run_list = nullptr;
-    if (j.directed)  // the runs stayed on the devices: each rank holds its own videos' (fetch_directed, on demand)
-      j.merged.clear();
-    else if (world == 1 && counts[0] <= j.head_runs)  // one rank, everything in the pinned head: no copy of ~100 MB at library scale
-      run_list = reinterpret_cast<const NeedleHipRun *>(static_cast<const char *>(j.host) + NeedleHipLibrary::kSlabHeader);
-    else
-      j.merged.resize(total);
-    size_t at = 0;
-    bool tails = false;
-    for (int r = 0; r < world && !run_list && !j.directed; r++) {  // (tails beyond the head: one rank only, out of its own slab)
-      const uint32_t head = std::min(counts[r], j.head_runs);
-      std::memcpy(j.merged.data() + at, static_cast<const char *>(j.host) + (size_t)r * j.head_bytes() + NeedleHipLibrary::kSlabHeader,
-                  (size_t)head * sizeof(NeedleHipRun));
-      if (counts[r] > head) {
-        tails = true;
-        if (hipMemcpyAsync(j.merged.data() + at + head,
-                           j.d_slabs.ptr + (size_t)r * j.slab_bytes() + NeedleHipLibrary::kSlabHeader + (size_t)head * sizeof(NeedleHipRun),
-                           (size_t)(counts[r] - head) * sizeof(NeedleHipRun), hipMemcpyDeviceToHost, download_stream()) != hipSuccess)
-          return report(Status::Make(NeedleError_Unknown, "run download failed"));
-      }
-      at += counts[r];
-    }
-    if (tails && hipStreamSynchronize(download_stream()) != hipSuccess)
-      return report(Status::Make(NeedleError_Unknown, "run download failed"));
-    if (num_runs) *num_runs = total;
-
-    // 5. the order-sensitive per-video epilogue (comparator.rs:583-626): every rank for all videos while that is
-    // cheaper than another collective, otherwise each rank for its own block of videos + one all-gather of results
-    std::vector<VideoResult> res;
-    const bool sharded = j.shape_fixed ? j.sharded : (world > 1 && shard_epilogue(total));
-    size_t v0 = 0, vcount = lib->n;
-    if (sharded) shard_range(lib->n, world, rank, &v0, &vcount);
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!run_list && !j.directed) run_list = j.merged.data();
-    j.last_runs = run_list;
-    j.last_total = total;
-    Status s;
-    const NeedleHipSearchResult *device_results = nullptr;
-    if (j.device_epilogue) {  // computed on the device behind the gather (epilogue.hip); j.done covers its copies
-      device_results = static_cast<const NeedleHipSearchResult *>(j.host_results);
-      const uint32_t fail = *reinterpret_cast<const uint32_t *>(device_results + lib->n);
-      if (fail & kEpilogueBucketTooLarge) {
-        device_results = nullptr;  // a pair with more runs than one lane should order: the host form below, same block of videos
-        note_epilogue_host_fallback("library job", total, vcount);
-      }
-      else if (fail != 0)
-        s = Status::Make(NeedleError_Unknown, "overflow when subtracting durations (time_padding / hash_duration exceed the match end)");
-    }
-    j.ran_device_epilogue = device_results != nullptr;
-    j.ran_sharded = sharded;
-    if (!device_results) {
-      const std::vector<const FrameHashesData *> fh = lib->shell_pointers();
-      if (j.directed) {  // this rank's videos' runs are what it received: down they come, once
-        Status f = fetch_directed(j, world, rank);
-        if (!f.ok()) return report(f);
-        s = cmp.results_from_runs(fh, j.fetched.data(), j.fetched.size(), false, false, false, &res, v0, v0 + vcount);
-      } else {
-        s = cmp.results_from_runs(fh, run_list, total, false, false, false, &res, v0, v0 + vcount);
-      }
-    }
-    if (getenv("NEEDLE_HIP_TRACE"))
-      std::fprintf(stderr, "[needle_hip] rank %d epilogue %zu runs, videos [%zu, %zu): %.1f us\n", rank, total, v0, v0 + vcount,
-                   std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
-    // an error on one rank must not leave the others waiting in the collective below: it travels with the results
-    if (!sharded) {
-      if (!s.ok()) return report(s);
-      if (device_results)
-        std::memcpy(results, device_results, lib->n * sizeof(NeedleHipSearchResult));
-      else
-        for (size_t v = 0; v < lib->n; v++) fill_c_result(res[v], &results[v]);
-      return NeedleError_Ok;
-    }
-    const size_t b = shard_block(lib->n, world);
-    struct Block {
-      uint64_t failed;
-    };
-    const size_t block_bytes = sizeof(Block) + b * sizeof(NeedleHipSearchResult);
-    std::vector<uint8_t> mine(block_bytes, 0), all(block_bytes * (size_t)world, 0);
-    reinterpret_cast<Block *>(mine.data())->failed = s.ok() ? 0 : 1;
-    if (s.ok() && device_results)
-      std::memcpy(mine.data() + sizeof(Block), device_results + v0, vcount * sizeof(NeedleHipSearchResult));
-    else if (s.ok())
-      for (size_t k = 0; k < vcount; k++)
-        fill_c_result(res[v0 + k], reinterpret_cast<NeedleHipSearchResult *>(mine.data() + sizeof(Block)) + k);
-    Status g = comm_all_gather_host(mine.data(), all.data(), block_bytes);
-    j.comm_bytes[2] += block_bytes * (uint64_t)world;
+    size_t total = 0;
+    Status s = job_collect_runs(j, counts, &run_list, &total);
     if (!s.ok()) return report(s);
-    if (!g.ok()) return report(g);
-    for (int r = 0; r < world; r++) {
-      const uint8_t *blk = all.data() + (size_t)r * block_bytes;
-      if (reinterpret_cast<const Block *>(blk)->failed)
-        return report(Status::Make(NeedleError_Unknown, "the epilogue failed on rank " + std::to_string(r)));
-      size_t f = 0, c = 0;
-      shard_range(lib->n, world, r, &f, &c);
-      std::memcpy(results + f, blk + sizeof(Block), c * sizeof(NeedleHipSearchResult));
-    }
+    if (num_runs) *num_runs = total;
+    j.found.last_runs = run_list;
+    j.found.last_total = total;
+    // 5. the per-video epilogue: every rank for all videos while that is cheaper than another collective, otherwise each
+    // rank for its own block of videos + one all-gather of results
+    const bool sharded = sharded_at_end(p, hook("NEEDLE_HIP_SHARD_EPILOGUE"), total);
+    size_t v0 = 0, vcount = lib->n;
+    if (sharded) shard_range(lib->n, p.shape.world, p.shape.rank, &v0, &vcount);
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<VideoResult> res;
+    const NeedleHipSearchResult *device_results = nullptr;
+    Status fetched = job_results(lib, comparator_of(comparator), j, run_list, total, v0, vcount, &device_results, &res, &s);
+    j.found.ran_device_epilogue = device_results != nullptr;
+    j.found.ran_sharded = sharded;
+    if (!fetched.ok()) return report(fetched);
+    if (getenv("NEEDLE_HIP_TRACE"))
+      std::fprintf(stderr, "[needle_hip] rank %d epilogue %zu runs, videos [%zu, %zu): %.1f us\n", p.shape.rank, total, v0, v0 + vcount,
+                   std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    if (sharded) s = job_gather_results(lib, j, s, device_results, res, results);
+    if (!s.ok()) return report(s);
+    if (!sharded && device_results) std::memcpy(results, device_results, lib->n * sizeof(NeedleHipSearchResult));
+    if (!sharded && !device_results)
+      for (size_t v = 0; v < lib->n; v++) fill_c_result(res[v], &results[v]);
     return NeedleError_Ok;
   });
 }
@@ -1561,35 +1510,36 @@ enum NeedleError needle_hip_library_job_end(NeedleHipLibrary *lib, const struct 
 enum NeedleError needle_hip_library_job_runs(const NeedleHipLibrary *lib, int slot, const NeedleHipRun **runs, size_t *num_runs) {
   if (!lib || !runs || !num_runs) return NeedleError_NullArgument;
   if (slot < 0 || slot > 1 || lib->job[slot].pending) return NeedleError_InvalidArgument;
-  if (lib->job[slot].directed) {  // owner-directed exchange: a rank holds the runs of its own videos' pairs, nothing else
-    NeedleHipLibrary::Job &j = const_cast<NeedleHipLibrary *>(lib)->job[slot];
-    Status s = fetch_directed(j, comm_world(), comm_rank());
+  if (lib->job[slot].planned.directed) {  // owner-directed exchange: a rank holds the runs of its own videos' pairs, nothing else
+    Job &j = const_cast<NeedleHipLibrary *>(lib)->job[slot];
+    Status s = fetch_directed(j);
     if (!s.ok()) return report(s);
-    *runs = j.fetched.data();
-    *num_runs = j.fetched.size();
+    *runs = j.found.fetched.data();
+    *num_runs = j.found.fetched.size();
     return NeedleError_Ok;
   }
-  if (!lib->job[slot].last_runs && lib->job[slot].last_total) return NeedleError_InvalidArgument;
-  *runs = lib->job[slot].last_runs;
-  *num_runs = lib->job[slot].last_total;
+  const Job::Found &found = lib->job[slot].found;
+  if (!found.last_runs && found.last_total) return NeedleError_InvalidArgument;
+  *runs = found.last_runs;
+  *num_runs = found.last_total;
   return NeedleError_Ok;
 }
 
 enum NeedleError needle_hip_library_job_form(const NeedleHipLibrary *lib, int slot, uint32_t form[4]) {
   if (!lib || !form) return NeedleError_NullArgument;
   if (slot < 0 || slot > 1 || lib->job[slot].pending) return NeedleError_InvalidArgument;
-  const NeedleHipLibrary::Job &j = lib->job[slot];
-  form[0] = j.ran_device_epilogue ? 1u : 0u;
-  form[1] = j.ran_sharded ? 1u : 0u;
-  form[2] = j.directed ? 1u : 0u;
-  form[3] = j.scan_form;
+  const Job &j = lib->job[slot];
+  form[0] = j.found.ran_device_epilogue ? 1u : 0u;
+  form[1] = j.found.ran_sharded ? 1u : 0u;
+  form[2] = j.planned.directed ? 1u : 0u;
+  form[3] = j.planned.scan_form;
   return NeedleError_Ok;
 }
 
 enum NeedleError needle_hip_library_job_comm_bytes(const NeedleHipLibrary *lib, int slot, uint64_t bytes[4]) {
   if (!lib || !bytes) return NeedleError_NullArgument;
   if (slot < 0 || slot > 1) return NeedleError_InvalidArgument;
-  std::copy(lib->job[slot].comm_bytes, lib->job[slot].comm_bytes + 4, bytes);
+  std::copy(lib->job[slot].found.comm_bytes, lib->job[slot].found.comm_bytes + 4, bytes);
   return NeedleError_Ok;
 }
 
