@@ -508,7 +508,8 @@ enum NeedleError needle_hip_index_store_sizes(const NeedleHipIndex *index, uint6
  * _store_sizes and _len work on a grouped index as on a plain one.  "no ending hash data present" concerns only a video that
  * has a pair.  Refused with NeedleError_InvalidArgument, before any device work: needle_hip_index_add on a grouped index,
  * needle_hip_index_add_grouped on a plain one, and needle_hip_index_crossmatcher_new, _matcher_new, _add_matched and
- * _add_streamed on a grouped one. */
+ * _add_streamed on a grouped one.  A season streamed into a grouped index goes through
+ * needle_hip_index_crossmatcher_new_grouped / needle_hip_index_add_matched_grouped (further down). */
 enum NeedleError needle_hip_index_new_grouped(const struct NeedleAudioComparator *comparator, NeedleHipIndex **output);
 /* Appends k >= 1 videos, groups[i] the label of frame_hashes[i].  Otherwise as needle_hip_index_add. */
 enum NeedleError needle_hip_index_add_grouped(NeedleHipIndex *index, const FrameHashes *const *frame_hashes, const uint32_t *groups,
@@ -1094,6 +1095,25 @@ enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint6
  * V (V - 1) / 2 x regions < 2^32.  NULL arrays (hashes with num_hashes > 0, resident with num_resident > 0, max_items,
  * min_len) or a NULL output: NullArgument.
  *
+ * Groups of videos: several shows decoded at once (needle_hip_crossmatcher_new_grouped).  The K resident and the N arriving
+ * videos carry a 32-bit label each (any values: they are only compared; K may be 0 with the resident arguments NULL), the
+ * video list is the residents first, and the live pairs are (a, b), a < b in list order, b >= K, with EQUAL labels.  Nothing
+ * else is evaluated and no run of any other pair is ever reported, however alike two shows' jingles are.  Lanes, feeds,
+ * finish, ready, lane, runs, stats, feed_from_feeder and the regions layout (lane = t * regions + r) are those above, and so
+ * are exactness and the reporting rule, restricted to live pairs.  NeedleHipRun.problem = (grouped pair id over the V
+ * labels) * regions + region: the numbering needle_hip_group_pairs decodes (groups in order of first appearance, inside a
+ * group the i-major order over its members), so with K = 0 the complete list goes straight into
+ * needle_hip_comparator_results_from_runs_grouped, and with one label and K = 0 the ids are those of
+ * needle_hip_crossmatcher_new_regions.  A round is still three launches with nothing per pair uploaded: a live-pair table --
+ * per live problem its two rows, its id and the place of its state -- is built on the host and uploaded once at creation,
+ * next to the resident table.  State and hashes exist for live pairs only: an arriving pair's four frontier sets by its
+ * number among the live arriving pairs; an (arriving t, resident k) col frontier only where the labels agree; a resident no
+ * arriving video shares a label with has no hashes uploaded or gathered, no state, and is never read (it still counts in the
+ * numbering, which is over all V).  Limits (InvalidArgument, before a device is asked for): regions 1 or 2; N 1..256; the
+ * LIVE problems (same-label pairs with an arriving end, x regions) <= 65 535, whatever K is; the grouped pairs x regions
+ * < 2^32; max_items, min_len and the resident rows as above.  A labelling without any live pair is allowed and reports
+ * nothing.  NULL groups, or NULL resident / resident_groups with num_resident > 0: NullArgument.
+ *
  * Out of scope: `reset`, `open`, more than two regions, several ranks.  Feeding the index, refreshed results for the
  * resident videos (their candidate lists also need the old pairs' entries, which the index holds) and resident rows taken
  * from a device arena are what needle_hip_index_crossmatcher_new / needle_hip_index_add_matched below do; a library too
@@ -1118,6 +1138,12 @@ enum NeedleError needle_hip_crossmatcher_new_regions(size_t videos, size_t regio
 enum NeedleError needle_hip_crossmatcher_new_resident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident,
                                                       size_t num_resident, size_t videos, size_t regions, const size_t *max_items,
                                                       const uint32_t *min_len, uint32_t threshold, NeedleHipCrossMatcher **output);
+/* groups of videos: resident_groups[k] and groups[t] are the labels of resident k and of arriving video t; only same-label
+ * pairs with an arriving end are live; num_resident == 0: resident and resident_groups may be NULL */
+enum NeedleError needle_hip_crossmatcher_new_grouped(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident,
+                                                     size_t num_resident, const uint32_t *resident_groups, size_t videos,
+                                                     const uint32_t *groups, size_t regions, const size_t *max_items,
+                                                     const uint32_t *min_len, uint32_t threshold, NeedleHipCrossMatcher **output);
 void needle_hip_crossmatcher_free(NeedleHipCrossMatcher *matcher);
 /* one entry per lane, host hashes; num_items[i] == 0: nothing for lane i */
 enum NeedleError needle_hip_crossmatcher_feed(NeedleHipCrossMatcher *matcher, const uint32_t *const *items, const size_t *num_items);
@@ -1146,6 +1172,16 @@ size_t needle_hip_crossmatcher_state_bytes_regions(size_t videos, size_t regions
  * needle_hip_crossmatcher_state_bytes_regions.  stats[3] is this plus the resident table and the run slab. */
 size_t needle_hip_crossmatcher_state_bytes_resident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions,
                                                     const size_t *max_items);
+/* what needle_hip_crossmatcher_new_grouped allocates for frontiers and hashes, by host arithmetic: with P the live arriving
+ * pairs, the sum over the regions of P x 4 x max_items[r] x w + N x max_items[r] x 4, plus per live (arriving t, resident k)
+ * 2 x len(k, r) x w, plus 4 bytes per hash of a resident that is in a live pair; w = 2 where every max_items[r] and every
+ * such resident's rows are below 65 536, else 4.  0 where the arguments are refused.  stats[3] of a grouped object is this
+ * plus the live-pair table (24 bytes per live problem), the resident table and the run slab. */
+size_t needle_hip_crossmatcher_state_bytes_grouped(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups,
+                                                   size_t videos, const uint32_t *groups, size_t regions, const size_t *max_items);
+/* the labels a grouped object was made with, residents first: n >= its residents + videos.  An ungrouped object:
+ * NeedleError_InvalidArgument. */
+enum NeedleError needle_hip_crossmatcher_groups(const NeedleHipCrossMatcher *matcher, uint32_t *labels, size_t n);
 /* the resident videos the object was created with; 0 for needle_hip_crossmatcher_new and _new_regions */
 enum NeedleError needle_hip_crossmatcher_resident(const NeedleHipCrossMatcher *matcher, size_t *num_resident);
 /* what the object was created with (regions = 1 for needle_hip_crossmatcher_new): the arriving videos and the regions; it
@@ -1178,6 +1214,24 @@ enum NeedleError needle_hip_index_crossmatcher_new(NeedleHipIndex *index, size_t
                                                    NeedleHipCrossMatcher **output);
 enum NeedleError needle_hip_index_add_matched(NeedleHipIndex *index, NeedleHipCrossMatcher *matcher,
                                               const FrameHashes *const *frame_hashes, size_t k);
+/* ---- The same route into a grouped index: several shows' seasons streamed at once ---------------------------------
+ * needle_hip_index_crossmatcher_new_grouped takes a grouped index, which may be empty, and makes the object of
+ * needle_hip_crossmatcher_new_grouped: the residents are the index's videos in index order under the index's labels,
+ * groups[t] is the label of arriving video t, and only the rows of the groups that arrive are gathered from the index's
+ * arena.  The live problems are bounded by the arriving shows' sizes, not by the library's: (same-label pairs with an
+ * arriving end) x regions <= 65 535.  needle_hip_index_add_matched_grouped appends the matcher's k arriving videos under the
+ * matcher's labels with its runs in place of the scan; one kernel decodes each run's grouped id over all K + k videos and
+ * re-tags it to the store's append-stable id, with the filter of needle_hip_index_add_matched.  Afterwards the index is
+ * what needle_hip_index_add_grouped(frame_hashes, groups, k) leaves: results of all videos, evidence, store sizes,
+ * pairs_searched, groups; pairs_scanned *last = 0.
+ * Refused as needle_hip_index_add_matched refuses, in the same words, the index exactly as it was; and a plain index
+ * (either call), a matcher without groups, a matcher whose resident labels are not the index's.
+ * needle_hip_index_crossmatcher_new, _add_matched, _matcher_new and _add_streamed stay refused on a grouped index; the
+ * matcher / add_streamed pair with groups is out of scope. */
+enum NeedleError needle_hip_index_crossmatcher_new_grouped(NeedleHipIndex *index, size_t videos, const uint32_t *groups, const size_t *max_items,
+                                                           const uint32_t *min_len, NeedleHipCrossMatcher **output);
+enum NeedleError needle_hip_index_add_matched_grouped(NeedleHipIndex *index, NeedleHipCrossMatcher *matcher,
+                                                      const FrameHashes *const *frame_hashes, size_t k);
 /* ---- A streamed season into an index of any size: a matcher made from the index, and the arriving pairs' cross-matcher --
  * The cross-matcher above holds (K N + N (N - 1) / 2) x regions live problems in a grid dimension, so a large index cannot
  * make one.  The second route splits the new pairs:

@@ -141,7 +141,9 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_crossmatcher_lane", "needle_hip_crossmatcher_runs", "needle_hip_crossmatcher_stats",
     "needle_hip_crossmatcher_state_bytes", "needle_hip_crossmatcher_new_regions",
     "needle_hip_crossmatcher_state_bytes_regions", "needle_hip_crossmatcher_shape",
-    "needle_hip_crossmatcher_new_resident", "needle_hip_crossmatcher_state_bytes_resident", "needle_hip_crossmatcher_resident"]
+    "needle_hip_crossmatcher_new_resident", "needle_hip_crossmatcher_state_bytes_resident", "needle_hip_crossmatcher_resident",
+    "needle_hip_crossmatcher_new_grouped", "needle_hip_crossmatcher_state_bytes_grouped", "needle_hip_crossmatcher_groups",
+    "needle_hip_index_crossmatcher_new_grouped", "needle_hip_index_add_matched_grouped"]
 
 # enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
 SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
@@ -393,6 +395,8 @@ def lib():
     L.needle_hip_index_pairs_scanned.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.needle_hip_index_crossmatcher_new.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(u32), C.POINTER(vp)]
     L.needle_hip_index_add_matched.argtypes = [vp, vp, C.POINTER(vp), sz]
+    L.needle_hip_index_crossmatcher_new_grouped.argtypes = [vp, sz, C.POINTER(u32), C.POINTER(sz), C.POINTER(u32), C.POINTER(vp)]
+    L.needle_hip_index_add_matched_grouped.argtypes = [vp, vp, C.POINTER(vp), sz]
     L.needle_hip_index_matcher_new.argtypes = [vp, sz, C.POINTER(vp)]
     L.needle_hip_index_add_streamed.argtypes = [vp, vp, vp, C.POINTER(vp), sz]
     L.needle_hip_index_new_grouped.argtypes = [vp, C.POINTER(vp)]
@@ -462,6 +466,10 @@ def lib():
     L.needle_hip_crossmatcher_state_bytes_resident.argtypes = [vp, sz, sz, sz, C.POINTER(sz)]
     L.needle_hip_crossmatcher_state_bytes_resident.restype = sz
     L.needle_hip_crossmatcher_resident.argtypes = [vp, C.POINTER(sz)]
+    L.needle_hip_crossmatcher_new_grouped.argtypes = [vp, sz, vp, sz, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(u32), u32, C.POINTER(vp)]
+    L.needle_hip_crossmatcher_state_bytes_grouped.argtypes = [vp, sz, vp, sz, vp, sz, C.POINTER(sz)]
+    L.needle_hip_crossmatcher_state_bytes_grouped.restype = sz
+    L.needle_hip_crossmatcher_groups.argtypes = [vp, C.POINTER(u32), sz]
     _LIB = L
     return L
 
@@ -1015,17 +1023,28 @@ class Index:
         ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
         check(lib().needle_hip_index_replace(self._h, pos, ptrs, C.c_size_t(k)))
 
-    def crossmatcher(self, videos: int, max_items: Sequence[int], min_len: Sequence[int]) -> "CrossMatcher":
+    def crossmatcher(self, videos: int, max_items: Sequence[int], min_len: Sequence[int],
+                     groups: Optional[Sequence[int]] = None) -> "CrossMatcher":
         """A CrossMatcher whose resident videos are this index's (their rows copied from the index's device arena) with
-        `videos` arriving ones; one max_items and one min_len per region of the index.  Feed it, then add_matched."""
+        `videos` arriving ones; one max_items and one min_len per region of the index.  Feed it, then add_matched.
+        `groups` (a grouped index): the arriving videos' labels; the residents carry the index's, and only same-label pairs
+        are live.  Without `groups` a grouped index refuses."""
         if len(max_items) != len(min_len):
             raise ValueError(f"one max_items and one min_len per region: {len(max_items)} and {len(min_len)}")
         regions = len(max_items)
         h = C.c_void_p()
-        check(lib().needle_hip_index_crossmatcher_new(self._h, videos, (C.c_size_t * max(regions, 1))(*max_items),
-                                                      (C.c_uint32 * max(regions, 1))(*min_len), C.byref(h)))
+        if groups is not None:
+            if len(groups) != videos:
+                raise ValueError(f"one label per arriving video: {videos}, got {len(groups)}")
+            check(lib().needle_hip_index_crossmatcher_new_grouped(self._h, videos, (C.c_uint32 * max(videos, 1))(*groups),
+                                                                  (C.c_size_t * max(regions, 1))(*max_items),
+                                                                  (C.c_uint32 * max(regions, 1))(*min_len), C.byref(h)))
+        else:
+            check(lib().needle_hip_index_crossmatcher_new(self._h, videos, (C.c_size_t * max(regions, 1))(*max_items),
+                                                          (C.c_uint32 * max(regions, 1))(*min_len), C.byref(h)))
         m = CrossMatcher.__new__(CrossMatcher)
         m._h = h
+        m._grouped = groups is not None
         videos, regions = m.shape()
         m.lanes, m.max_items, m.min_len, m.threshold = videos * regions, tuple(max_items), tuple(min_len), self.threshold
         return m
@@ -1033,10 +1052,14 @@ class Index:
     def add_matched(self, matcher: "CrossMatcher", frame_hashes: Sequence[FrameHashes]) -> None:
         """Appends the matcher's arriving videos (complete, made by crossmatcher() since the last change) with the runs it
         holds in place of a scan; afterwards the index is what add(frame_hashes) leaves.  On failure (NeedleError) the
-        index is as it was before the call."""
+        index is as it was before the call.  A matcher with groups (crossmatcher(groups=...)) goes to
+        needle_hip_index_add_matched_grouped: the videos are appended under the matcher's labels, as add(groups=...) would."""
         k = len(frame_hashes)
         ptrs = (C.c_void_p * max(k, 1))(*[f._h for f in frame_hashes])
-        check(lib().needle_hip_index_add_matched(self._h, matcher._h, ptrs, k))
+        if getattr(matcher, "_grouped", False):
+            check(lib().needle_hip_index_add_matched_grouped(self._h, matcher._h, ptrs, k))
+        else:
+            check(lib().needle_hip_index_add_matched(self._h, matcher._h, ptrs, k))
 
     def matcher(self, videos: int) -> "Matcher":
         """A Matcher whose sources are this index's rows (gathered from the index's device arena; min_len per row, the
@@ -1378,7 +1401,8 @@ class CrossMatcher:
     comparator's i-major order, so it goes straight into Comparator.results_from_runs.  `with_regions`: openings and endings
     in one object, lane = video * regions + region, `problem` = pair * regions + region.  `with_resident`: K known videos in
     front of the arriving ones; only the arriving videos have lanes, `problem` numbers the pairs over all K + N videos, and
-    the list goes into Comparator.results_from_runs(first_video=K)."""
+    the list goes into Comparator.results_from_runs(first_video=K).  `with_groups`: a label per video, only same-label pairs
+    with an arriving end are live, `problem` = grouped pair id * regions + region (Comparator.results_from_runs_grouped)."""
 
     def __init__(self, lanes: int, max_items: int, min_len: int, threshold: int):
         self._h = None
@@ -1427,6 +1451,75 @@ class CrossMatcher:
         self._h = h
         self.lanes, self.max_items, self.min_len, self.threshold = videos * regions, tuple(max_items), tuple(min_len), threshold
         return self
+
+    @staticmethod
+    def _rows(resident: Sequence[np.ndarray]):
+        arrs = [np.ascontiguousarray(s, dtype=np.uint32) for s in resident]
+        arena = np.concatenate(arrs) if arrs else np.zeros(0, dtype=np.uint32)
+        seqs = np.zeros((max(len(arrs), 1), 2), dtype=np.uint32)
+        seqs[:len(arrs), 1] = [a.size for a in arrs]
+        seqs[:len(arrs), 0] = np.cumsum([0] + [a.size for a in arrs])[:len(arrs)]
+        return arrs, arena, seqs
+
+    @classmethod
+    def with_groups(cls, groups: Sequence[int], max_items: Sequence[int], min_len: Sequence[int], threshold: int,
+                    videos: Optional[int] = None, resident: Sequence[np.ndarray] = (),
+                    resident_groups: Sequence[int] = ()) -> "CrossMatcher":
+        """Groups of videos: groups[t] is the label of arriving video t (`videos` = len(groups) of them, `videos * regions`
+        lanes), resident_groups[k] that of resident k, whose rows are `resident` as in with_resident.  Only same-label pairs
+        with an arriving end are live; `problem` = (grouped pair id over all K + N labels) * regions + region, the numbering
+        group_pairs() decodes, so without residents the list goes into Comparator.results_from_runs_grouped."""
+        if len(max_items) != len(min_len):
+            raise ValueError(f"one max_items and one min_len per region: {len(max_items)} and {len(min_len)}")
+        regions = len(max_items)
+        videos = len(groups) if videos is None else videos
+        if videos != len(groups):
+            raise ValueError(f"one label per arriving video: {videos}, got {len(groups)}")
+        if len(resident) != len(resident_groups) * regions:
+            raise ValueError(f"one resident row per video and region: {len(resident)} rows, {len(resident_groups)} labels, {regions} regions")
+        arrs, arena, seqs = cls._rows(resident)
+        labels = np.ascontiguousarray(groups, dtype=np.uint32)
+        res_labels = np.ascontiguousarray(resident_groups, dtype=np.uint32)
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().needle_hip_crossmatcher_new_grouped(arena.ctypes.data if arena.size else None, arena.size,
+                                                        seqs.ctypes.data if arrs else None, len(res_labels),
+                                                        res_labels.ctypes.data if res_labels.size else None, videos,
+                                                        labels.ctypes.data if labels.size else None, regions,
+                                                        (C.c_size_t * max(regions, 1))(*max_items),
+                                                        (C.c_uint32 * max(regions, 1))(*min_len), threshold, C.byref(h)))
+        self._h = h
+        self._grouped = True
+        self.lanes, self.max_items, self.min_len, self.threshold = videos * regions, tuple(max_items), tuple(min_len), threshold
+        return self
+
+    @property
+    def groups(self) -> Optional[np.ndarray]:
+        """The labels of all K + N videos, residents first; None for an object without groups."""
+        if not getattr(self, "_grouped", False):
+            return None
+        n = self.resident + self.shape()[0]
+        out = np.zeros(max(n, 1), dtype=np.uint32)
+        check(lib().needle_hip_crossmatcher_groups(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), n))
+        return out[:n]
+
+    @staticmethod
+    def state_bytes_grouped(groups: Sequence[int], max_items: Sequence[int], resident: Sequence[int] = (),
+                            resident_groups: Sequence[int] = ()) -> int:
+        """needle_hip_crossmatcher_state_bytes_grouped: `resident` the lengths of the K * regions resident rows in row order;
+        0 where creation would refuse."""
+        regions = len(max_items)
+        seqs = np.zeros((max(len(resident), 1), 2), dtype=np.uint32)
+        seqs[:len(resident), 1] = list(resident)
+        labels = np.ascontiguousarray(groups, dtype=np.uint32)
+        res_labels = np.ascontiguousarray(resident_groups, dtype=np.uint32)
+        if len(resident) != len(res_labels) * regions:
+            raise ValueError(f"one resident row per video and region: {len(resident)} rows, {len(res_labels)} labels, {regions} regions")
+        return int(lib().needle_hip_crossmatcher_state_bytes_grouped(seqs.ctypes.data if len(resident) else None, len(res_labels),
+                                                                     res_labels.ctypes.data if res_labels.size else None, labels.size,
+                                                                     labels.ctypes.data if labels.size else None, regions,
+                                                                     (C.c_size_t * max(regions, 1))(*max_items)))
 
     @property
     def resident(self) -> int:

@@ -1068,6 +1068,37 @@ enum NeedleError needle_hip_crossmatcher_new_resident(const uint32_t *hashes, si
   });
 }
 
+enum NeedleError needle_hip_crossmatcher_new_grouped(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident,
+                                                     size_t num_resident, const uint32_t *resident_groups, size_t videos,
+                                                     const uint32_t *groups, size_t regions, const size_t *max_items,
+                                                     const uint32_t *min_len, uint32_t threshold, NeedleHipCrossMatcher **output) {
+  if (!output || !max_items || !min_len || !groups || (num_resident && (!resident || !resident_groups)) || (num_hashes && !hashes))
+    return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipCrossMatcher>();
+    Status s = CrossMatcher::CreateGrouped(hashes, num_hashes, resident, num_resident, resident_groups, videos, groups, regions, max_items,
+                                           min_len, threshold, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
+size_t needle_hip_crossmatcher_state_bytes_grouped(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups,
+                                                   size_t videos, const uint32_t *groups, size_t regions, const size_t *max_items) {
+  return CrossMatcher::StateBytesGrouped(resident, num_resident, resident_groups, videos, groups, regions, max_items);
+}
+
+enum NeedleError needle_hip_crossmatcher_groups(const NeedleHipCrossMatcher *matcher, uint32_t *labels, size_t n) {
+  if (!matcher || !labels) return NeedleError_NullArgument;
+  if (!matcher->inner->grouped())
+    return report(Status::Make(NeedleError_InvalidArgument, "crossmatcher groups: not a grouped cross-matcher (needle_hip_crossmatcher_new_grouped makes one)"));
+  const std::vector<uint32_t> &have = matcher->inner->labels();
+  if (n < have.size()) return report(Status::Make(NeedleError_InvalidArgument, "crossmatcher groups: the array is shorter than the video list"));
+  std::copy(have.begin(), have.end(), labels);
+  return NeedleError_Ok;
+}
+
 void needle_hip_crossmatcher_free(NeedleHipCrossMatcher *matcher) { delete matcher; }
 
 enum NeedleError needle_hip_crossmatcher_feed(NeedleHipCrossMatcher *matcher, const uint32_t *const *items, const size_t *num_items) {
@@ -1578,6 +1609,34 @@ enum NeedleError needle_hip_index_add_matched(NeedleHipIndex *index, NeedleHipCr
       fh[i] = &frame_hashes[i]->d;
     }
     Status s = index->inner.add_matched(matcher->inner.get(), fh);
+    return s.ok() ? NeedleError_Ok : report(s);
+  });
+}
+
+enum NeedleError needle_hip_index_crossmatcher_new_grouped(NeedleHipIndex *index, size_t videos, const uint32_t *groups, const size_t *max_items,
+                                                           const uint32_t *min_len, NeedleHipCrossMatcher **output) {
+  if (!index || !groups || !max_items || !min_len || !output) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    auto m = std::make_unique<NeedleHipCrossMatcher>();
+    Status s = index->inner.crossmatcher_grouped(videos, groups, max_items, min_len, &m->inner);
+    if (!s.ok()) return report(s);
+    *output = m.release();
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_index_add_matched_grouped(NeedleHipIndex *index, NeedleHipCrossMatcher *matcher,
+                                                      const FrameHashes *const *frame_hashes, size_t k) {
+  if (!index || !matcher) return NeedleError_NullArgument;
+  if (k == 0) return report(Status::Make(NeedleError_InvalidArgument, "index add: no videos"));
+  if (!frame_hashes) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<const FrameHashesData *> fh(k);
+    for (size_t i = 0; i < k; i++) {
+      if (!frame_hashes[i]) return NeedleError_NullArgument;
+      fh[i] = &frame_hashes[i]->d;
+    }
+    Status s = index->inner.add_matched_grouped(matcher->inner.get(), fh);
     return s.ok() ? NeedleError_Ok : report(s);
   });
 }

@@ -30,6 +30,16 @@ class CrossMatcher {
   static Status CreateResidentDevice(const uint32_t *d_hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
                                      size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
                                      std::unique_ptr<CrossMatcher> *out);
+  // Groups: a label per resident and per arriving video (any values, only compared); the live pairs are the same-label ones
+  // with an arriving end, and NeedleHipRun.problem is the grouped pair id of pair_ids.h over the K + N labels, x regions +
+  // region.  The live-pair table (cross_pairs.h) is uploaded here; state and hashes exist for live pairs only.
+  static Status CreateGrouped(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                              const uint32_t *resident_groups, size_t videos, const uint32_t *groups, size_t regions, const size_t *max_items,
+                              const uint32_t *min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out);
+  // ... with `hashes` an arena in DEVICE memory, as CreateResidentDevice
+  static Status CreateGroupedDevice(const uint32_t *d_hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                                    const uint32_t *resident_groups, size_t videos, const uint32_t *groups, size_t regions,
+                                    const size_t *max_items, const uint32_t *min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out);
   ~CrossMatcher();
   size_t lanes() const;  // videos * regions
   size_t residents() const;
@@ -54,6 +64,15 @@ class CrossMatcher {
   static const char *ShapeError(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items,
                                 const uint32_t *min_len);
 
+  // what CreateGrouped allocates for frontiers and hashes (cross_pairs.h); 0 where the arguments are refused
+  static size_t StateBytesGrouped(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
+                                  const uint32_t *groups, size_t regions, const size_t *max_items);
+  // ShapeError for CreateGrouped
+  static const char *GroupedShapeError(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
+                                       const uint32_t *groups, size_t regions, const size_t *max_items, const uint32_t *min_len);
+  bool grouped() const;
+  const std::vector<uint32_t> &labels() const;  // a grouped object's, of all K + N videos, residents first
+
   // What an index needs of a matcher it made (Index::crossmatcher, Index::add_matched).
   struct Origin {  // the index and its generation at creation; index_id 0: not made from an index
     uint64_t index_id = 0, generation = 0;
@@ -70,6 +89,9 @@ class CrossMatcher {
   static Status CreateFrom(const uint32_t *hashes, bool on_device, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
                            size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
                            std::unique_ptr<CrossMatcher> *out);
+  static Status CreateGroupedFrom(const uint32_t *hashes, bool on_device, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                                  const uint32_t *resident_groups, size_t videos, const uint32_t *groups, size_t regions,
+                                  const size_t *max_items, const uint32_t *min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out);
   CrossMatcher();
   struct Impl;
   std::unique_ptr<Impl> impl_;

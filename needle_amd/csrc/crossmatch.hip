@@ -34,12 +34,21 @@
 // arriving pairs' frontiers (S_r = the region's resident hashes).  A resident is a complete X (stream_walk.h): a run that
 // reaches its last row leaves with the round's runs, and the host holds it back until the arriving lane finishes, which is
 // when the reporting rule hands out what is open on a frontier.  K = 0 is the object above.
+//
+// Groups of videos (needle_hip_crossmatcher_new_grouped): every resident and every arriving video carries a label, and the live
+// problems are the same-label pairs with an arriving end only.  Which they are, their NeedleHipRun.problem (the grouped id of
+// pair_ids.h over all V labels, x R + region) and where their state lies is decided on the host (cross_pairs.h) and uploaded
+// once as the live-pair table, next to the resident table; blockIdx.y of the walk is an index into it, and the walk takes
+// its pair lookup as a policy: ClosedFormPairs (the arithmetic above, the objects above) or ListedLivePairs (one table entry
+// at an address the workgroup shares).  State and hashes exist for live pairs only; a round is still three launches and
+// uploads nothing per pair.  The land and the simhash kernel do not know about groups: the rows travel in the run.
 #include "crossmatch.h"
 
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
+#include "cross_pairs.h"
 #include "stream_round.h"
 #include "stream_walk.h"
 
@@ -121,41 +130,77 @@ __global__ __launch_bounds__(kThreads) void crossmatch_gather_resident_kernel(co
   }
 }
 
-template <typename T>
+// How crossmatch_walk_kernel finds its live problem blockIdx.y = q * regions + r: the two videos (of all V), whether the source
+// is a resident, NeedleHipRun.problem and the first entry of the problem's state.  Built in the kernel from its arguments and
+// its trailing ones (none for the closed form: its code is what it was), the way epilogue_kernels.h's pair policies are.
+struct ClosedFormPairs {  // every pair with an arriving end: q = t * K + k for resident k against arriving video t, then the
+  uint32_t a, b, pair;    // arriving pairs i-major as the comparator numbers them (pair_at in comparator.cpp): row ta holds
+  bool res, live;         // videos - 1 - ta pairs
+  __device__ ClosedFormPairs(const CrossRegions &rg, const uint32_t videos, const uint32_t q, const uint32_t) : pair(0u), live(true) {
+    const uint32_t K = rg.residents;
+    res = q < K * videos;
+    if (res) {
+      const uint32_t t = q / K;
+      a = q - t * K;
+      b = K + t;
+    } else {
+      pair = q - K * videos;
+      uint32_t ta = 0u, first = 0u;
+      while (pair - first >= videos - 1u - ta) {
+        first += videos - 1u - ta;
+        ta++;
+      }
+      a = K + ta;
+      b = a + 1u + (pair - first);
+    }
+  }
+  // the comparator's problem over V videos: row a of its pair numbering starts at a (2 V - a - 1) / 2
+  __device__ uint32_t problem(const CrossRegions &rg, const uint32_t V, const uint32_t r) const {
+    return (uint32_t)((uint64_t)a * (2u * V - a - 1u) / 2u + (b - a - 1u)) * rg.regions + r;
+  }
+  // an arriving pair's four sets by its number; a resident one's two at 2 * (t * S_r + prefix)
+  __device__ uint64_t state_at(const CrossRegions &rg, const uint32_t r, const uint64_t prefix, const uint32_t max_items) const {
+    return res ? (r ? rg.res_state1 : rg.res_state0) + 2u * ((uint64_t)(b - rg.residents) * (r ? rg.res_total1 : rg.res_total0) + prefix)
+               : (r ? rg.state1 : rg.state0) + (uint64_t)pair * 4u * max_items;
+  }
+};
+struct ListedLivePairs {  // the same-label pairs of a grouped object: one entry of the live-pair table (cross_pairs.h), at an address
+  CrossLive e;        // every lane of the workgroup shares
+  uint32_t a, b;
+  bool res, live;
+  __device__ ListedLivePairs(const CrossRegions &rg, const uint32_t, const uint32_t, const uint32_t problem_index,
+                         const CrossLive *__restrict__ table, const uint32_t count)
+      : live(problem_index < count) {  // (a labelling without live pairs still launches one row of workgroups)
+    e = live ? table[problem_index] : CrossLive{};
+    a = rg.regions == 2u ? e.row_a >> 1 : e.row_a;
+    b = rg.regions == 2u ? e.row_b >> 1 : e.row_b;
+    res = a < rg.residents;
+  }
+  __device__ uint32_t problem(const CrossRegions &, const uint32_t, const uint32_t) const { return e.problem; }
+  __device__ uint64_t state_at(const CrossRegions &, const uint32_t, const uint64_t, const uint32_t) const { return e.state; }
+};
+
+template <typename T, class Pairs, class... Extra>
 __global__ __launch_bounds__(kThreads) void crossmatch_walk_kernel(const uint32_t *__restrict__ hist, T *__restrict__ state,
                                                                    const CrossLane *__restrict__ lanes,
                                                                    const CrossResident *__restrict__ resident, uint32_t videos,
                                                                    CrossRegions rg, uint32_t side_blocks, uint32_t threshold,
                                                                    NeedleHipRun *__restrict__ runs, uint32_t capacity,
-                                                                   uint32_t *__restrict__ count) {
+                                                                   uint32_t *__restrict__ count, Extra... extra) {
   __shared__ uint32_t strip[kMaxStrip];                // Y's new items
   __shared__ uint32_t rows[kCarriedRows + kMaxStrip];  // the X items this workgroup's diagonals meet
-  // the live problem of this workgroup: q * regions + region; q = t * K + k for resident k against arriving video t, then
-  // the arriving pairs i-major as the comparator numbers them (pair_at in comparator.cpp): row ta holds videos - 1 - ta pairs
+  // the live problem of this workgroup: q * regions + region, its videos by the policy
   const uint32_t per_side = side_blocks + kTopBlocks;
   const bool col_dir = blockIdx.x < per_side;
   const bool two = rg.regions == 2u;
   const uint32_t q = two ? blockIdx.y >> 1 : blockIdx.y, r = two ? blockIdx.y & 1u : 0u;
   const uint32_t K = rg.residents, V = K + videos, first_lane = two ? 2u * K : K;
-  const bool res = q < K * videos;
-  uint32_t a, b, pair = 0u;  // videos of all V; the pair among the arriving ones
-  if (res) {
-    if (!col_dir) return;  // a resident gains no rows
-    const uint32_t t = q / K;
-    a = q - t * K;
-    b = K + t;
-  } else {
-    pair = q - K * videos;
-    uint32_t ta = 0u, first = 0u;
-    while (pair - first >= videos - 1u - ta) {
-      first += videos - 1u - ta;
-      ta++;
-    }
-    a = K + ta;
-    b = a + 1u + (pair - first);
-  }
-  // the comparator's problem over V videos: row a of its pair numbering starts at a (2 V - a - 1) / 2
-  const uint32_t problem = (uint32_t)((uint64_t)a * (2u * V - a - 1u) / 2u + (b - a - 1u)) * rg.regions + r;
+  const Pairs lp(rg, videos, q, blockIdx.y, extra...);
+  if (!lp.live) return;
+  const bool res = lp.res;
+  if (res && !col_dir) return;  // a resident gains no rows
+  const uint32_t a = lp.a, b = lp.b;  // videos of all V
+  const uint32_t problem = lp.problem(rg, V, r);
   const uint32_t row_a = two ? 2u * a + r : a, row_b = two ? 2u * b + r : b;
   const CrossLane lb = lanes[row_b - first_lane];
   // a resident is a lane that holds all its items, finished long ago
@@ -176,8 +221,7 @@ __global__ __launch_bounds__(kThreads) void crossmatch_walk_kernel(const uint32_
   const uint32_t max_items = region_max_items(rg, r), min_len = r ? rg.min_len1 : rg.min_len0;
   // an arriving pair: col set 0, row set 0, col set 1, row set 1, each of max_items; a resident one: col set 0, col set 1,
   // each of the row's own length
-  const uint64_t at = res ? (r ? rg.res_state1 : rg.res_state0) + 2u * ((uint64_t)(b - K) * (r ? rg.res_total1 : rg.res_total0) + prefix)
-                          : (r ? rg.state1 : rg.state0) + (uint64_t)pair * 4u * max_items;
+  const uint64_t at = lp.state_at(rg, r, prefix, max_items);
   const uint64_t col_stride = res ? (uint64_t)la.fed : 2u * (uint64_t)max_items;
   T *base = state + at;
   const uint32_t cs = lb.flags & kParity, rs = la.flags & kParity;
@@ -259,6 +303,13 @@ struct CrossMatcher::Impl {
   uint64_t res_cell_rows[2] = {0, 0};               // per region: the sum over its rows of max(len, 1) - 1
   uint64_t res_longest = 0;
   std::vector<std::vector<NeedleHipRun>> held;      // per lane: runs into a resident's last row, held back until it finishes
+  // groups: a label per video of all V, residents first; the live problems are the table's (cross_pairs.h), uploaded once
+  bool grouped = false;
+  std::vector<uint32_t> labels;
+  std::unique_ptr<const GroupTables> group_tables;
+  std::vector<CrossLive> live;
+  size_t grouped_state_bytes = 0;
+  DeviceBuffer<CrossLive> d_live;
   DeviceBuffer<CrossResident> d_resident;
   DeviceBuffer<uint32_t> hist, d_round;
   DeviceBuffer<uint8_t> state;
@@ -282,6 +333,12 @@ struct CrossMatcher::Impl {
   // numbering over all videos: row a starts at a (2 V - a - 1) / 2, so a resident source is a pair before row K's start.
   bool into_a_residents_last_row(const NeedleHipRun &run, size_t *lane) const {
     if (!residents) return false;
+    if (grouped) {  // the grouped id over the V labels (pair_ids.h): a resident source is a video below K
+      uint32_t a = 0, b = 0;
+      if (!grouped_pair_at(group_tables->view(), run.problem / regions, &a, &b) || a >= residents) return false;
+      *lane = (size_t)((b - residents) * regions + run.problem % regions);
+      return (uint64_t)run.src_end + 1 == res_rows[a * regions + run.problem % regions].len;
+    }
     const uint64_t all = residents + videos, pair = run.problem / regions, r = run.problem % regions;
     auto row_start = [&](uint64_t a) { return a * (2 * all - a - 1) / 2; };
     if (pair >= row_start(residents)) return false;
@@ -301,6 +358,16 @@ struct CrossMatcher::Impl {
   // x = max(items, 1) - 1, and every resident row against every lane
   uint64_t cells_of(const std::vector<Piece> *pieces) const {
     uint64_t total = 0;
+    if (grouped) {  // the live problems one by one: x_a x_b of its two rows
+      const size_t first_lane = residents * regions;
+      auto x_of = [&](size_t row) -> uint64_t {
+        if (row < first_lane) return std::max<uint64_t>(res_rows[row].len, 1) - 1;
+        const size_t i = row - first_lane;
+        return std::max<uint64_t>(lanes[i].fed + (pieces ? (*pieces)[i].width : 0u), 1) - 1;
+      };
+      for (const CrossLive &e : live) total += x_of(e.row_a) * x_of(e.row_b);
+      return total;
+    }
     for (size_t r = 0; r < regions; r++) {
       uint64_t sum = 0, squares = 0;
       for (size_t i = r; i < n; i += regions) {
@@ -334,7 +401,7 @@ struct CrossMatcher::Impl {
     const CrossLane *d_lanes = reinterpret_cast<const CrossLane *>(d_round.ptr);
     const dim3 block(kThreads);
     const uint32_t side_blocks = (uint32_t)((longest + kCarriedRows - 1) / kCarriedRows);  // of the longest lane or resident row of any region: the others' leave at once
-    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), (uint32_t)(live_pairs() * regions));
+    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), grouped ? (uint32_t)std::max<size_t>(live.size(), 1) : (uint32_t)(live_pairs() * regions));
     std::vector<NeedleHipRun> got;
     for (;;) {
       uint32_t *d_count = nullptr;
@@ -348,12 +415,22 @@ struct CrossMatcher::Impl {
       }
       {
         KernelTimer timer("crossmatch_walk");
-        if (narrow)
-          hipLaunchKernelGGL(crossmatch_walk_kernel<uint16_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint16_t *>(state.ptr),
-                             d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs, slab.capacity, d_count);
+        if (grouped && narrow)
+          hipLaunchKernelGGL((crossmatch_walk_kernel<uint16_t, ListedLivePairs, const CrossLive *, uint32_t>), walk_grid, block, 0, stream, hist.ptr,
+                             reinterpret_cast<uint16_t *>(state.ptr), d_lanes, (const CrossResident *)d_resident.ptr, (uint32_t)videos, rg,
+                             side_blocks, threshold, d_runs, slab.capacity, d_count, (const CrossLive *)d_live.ptr, (uint32_t)live.size());
+        else if (grouped)
+          hipLaunchKernelGGL((crossmatch_walk_kernel<uint32_t, ListedLivePairs, const CrossLive *, uint32_t>), walk_grid, block, 0, stream, hist.ptr,
+                             reinterpret_cast<uint32_t *>(state.ptr), d_lanes, (const CrossResident *)d_resident.ptr, (uint32_t)videos, rg,
+                             side_blocks, threshold, d_runs, slab.capacity, d_count, (const CrossLive *)d_live.ptr, (uint32_t)live.size());
+        else if (narrow)
+          hipLaunchKernelGGL((crossmatch_walk_kernel<uint16_t, ClosedFormPairs>), walk_grid, block, 0, stream, hist.ptr,
+                             reinterpret_cast<uint16_t *>(state.ptr), d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs,
+                             slab.capacity, d_count);
         else
-          hipLaunchKernelGGL(crossmatch_walk_kernel<uint32_t>, walk_grid, block, 0, stream, hist.ptr, reinterpret_cast<uint32_t *>(state.ptr),
-                             d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs, slab.capacity, d_count);
+          hipLaunchKernelGGL((crossmatch_walk_kernel<uint32_t, ClosedFormPairs>), walk_grid, block, 0, stream, hist.ptr,
+                             reinterpret_cast<uint32_t *>(state.ptr), d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs,
+                             slab.capacity, d_count);
         NEEDLE_HIP_TRY(hipGetLastError());
       }
       {
@@ -547,6 +624,150 @@ Status CrossMatcher::CreateFrom(const uint32_t *hashes, bool on_device, size_t n
   return Status::Ok();
 }
 
+// ---- groups: the live pairs are the same-label ones, by the table of cross_pairs.h ----------------------------------------------
+
+namespace {
+
+// The plan of a grouped creation from the C arguments; the resident rows' lengths are all it needs of them.
+CrossPairsPlan grouped_plan(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
+                            const uint32_t *groups, size_t regions, const size_t *max_items) {
+  std::vector<uint32_t> lens;
+  if (regions >= 1 && regions <= kMaxRegions && resident)  // (other regions are refused before a length is read)
+    for (size_t i = 0; i < num_resident * regions; i++) lens.push_back(resident[i].len);
+  CrossPairsShape sh;
+  sh.residents = num_resident;
+  sh.arriving = videos;
+  sh.regions = regions;
+  sh.resident_len = resident ? lens.data() : nullptr;
+  sh.resident_groups = resident_groups;
+  sh.groups = groups;
+  sh.max_items = max_items;
+  return plan_cross_pairs(sh);
+}
+
+}  // namespace
+
+size_t CrossMatcher::StateBytesGrouped(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
+                                       const uint32_t *groups, size_t regions, const size_t *max_items) {
+  const CrossPairsPlan plan = grouped_plan(resident, num_resident, resident_groups, videos, groups, regions, max_items);
+  return plan.error ? 0 : plan.state_bytes();
+}
+
+const char *CrossMatcher::GroupedShapeError(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
+                                            const uint32_t *groups, size_t regions, const size_t *max_items, const uint32_t *min_len) {
+  const CrossPairsPlan plan = grouped_plan(resident, num_resident, resident_groups, videos, groups, regions, max_items);
+  if (plan.error) return plan.error;
+  for (size_t r = 0; r < regions; r++)
+    if (min_len[r] == 0) return "crossmatcher: min_len must be >= 1";
+  return nullptr;
+}
+
+Status CrossMatcher::CreateGrouped(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                                   const uint32_t *resident_groups, size_t videos, const uint32_t *groups, size_t regions,
+                                   const size_t *max_items, const uint32_t *min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out) {
+  return CreateGroupedFrom(hashes, false, num_hashes, resident, num_resident, resident_groups, videos, groups, regions, max_items, min_len,
+                           threshold, out);
+}
+
+Status CrossMatcher::CreateGroupedDevice(const uint32_t *d_hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
+                                         const uint32_t *resident_groups, size_t videos, const uint32_t *groups, size_t regions,
+                                         const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                                         std::unique_ptr<CrossMatcher> *out) {
+  return CreateGroupedFrom(d_hashes, true, num_hashes, resident, num_resident, resident_groups, videos, groups, regions, max_items, min_len,
+                           threshold, out);
+}
+
+// CreateFrom with the layout of cross_pairs.h: the live-pair table goes up next to the resident table, and only the residents
+// that are in a live pair have hashes here (the device table says len 0 for the others: nothing of them is copied or gathered).
+Status CrossMatcher::CreateGroupedFrom(const uint32_t *hashes, bool on_device, size_t num_hashes, const NeedleHipSeq *resident,
+                                       size_t num_resident, const uint32_t *resident_groups, size_t videos, const uint32_t *groups,
+                                       size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
+                                       std::unique_ptr<CrossMatcher> *out) {
+  if (!out || !max_items || !min_len || !groups || (num_resident && (!resident || !resident_groups)) || (num_hashes && !hashes))
+    return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  if (const char *what = GroupedShapeError(resident, num_resident, resident_groups, videos, groups, regions, max_items, min_len))
+    return Status::Make(NeedleError_InvalidArgument, what);
+  for (size_t i = 0; i < num_resident * regions; i++)
+    if ((uint64_t)resident[i].offset + resident[i].len > num_hashes)
+      return Status::Make(NeedleError_InvalidArgument, "crossmatcher: a resident row lies outside the hash arena");
+  CrossPairsPlan plan = grouped_plan(resident, num_resident, resident_groups, videos, groups, regions, max_items);
+  std::unique_ptr<CrossMatcher> cm(new CrossMatcher());
+  Impl &m = *cm->impl_;
+  m.grouped = true;
+  m.videos = videos;
+  m.regions = regions;
+  m.residents = num_resident;
+  m.n = videos * regions;
+  m.threshold = threshold;
+  m.lanes = std::vector<LaneState>(m.n);
+  m.held.resize(m.n);
+  m.res_rows.assign(resident, resident + num_resident * regions);
+  m.narrow = plan.narrow;
+  m.res_longest = plan.longest_resident;
+  m.grouped_state_bytes = plan.state_bytes();
+  m.labels = plan.labels;
+  m.group_tables.reset(new GroupTables(m.labels.data(), m.labels.size()));
+  m.live.swap(plan.live);
+  std::vector<CrossResident> table(num_resident * regions);
+  for (size_t i = 0; i < table.size(); i++)
+    table[i] = CrossResident{plan.resident_prefix[i], plan.resident_live[i / regions] ? resident[i].len : 0u, resident[i].offset};
+  for (size_t r = 0; r < regions; r++) {
+    m.max_items[r] = max_items[r];
+    m.min_len[r] = min_len[r];
+  }
+  m.rg.regions = (uint32_t)regions;
+  m.rg.residents = (uint32_t)num_resident;
+  m.rg.max_items0 = (uint32_t)m.max_items[0];
+  m.rg.max_items1 = (uint32_t)m.max_items[regions - 1];
+  m.rg.min_len0 = m.min_len[0];
+  m.rg.min_len1 = m.min_len[regions - 1];
+  m.rg.hist0 = plan.hist[0];
+  m.rg.hist1 = plan.hist[regions - 1];
+  m.rg.res_hist0 = plan.res_hist[0];
+  m.rg.res_hist1 = plan.res_hist[regions - 1];
+  // (state0/1, res_state0/1 and res_total0/1 are the closed form's: a live problem's state is in its table entry)
+  m.slab.capacity_from_env("NEEDLE_HIP_CROSSMATCHER_RUN_SLAB");
+
+  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
+  Status s = ensure_device();
+  if (!s.ok()) return s;
+  hipStream_t stream = library_stream();
+  const size_t state_bytes = (size_t)plan.state_entries * plan.entry_bytes(), first_resident_word = (size_t)plan.res_hist[0];
+  if (!(s = m.hist.reserve(std::max<size_t>(plan.hist_words, 1))).ok() || !(s = m.state.reserve(std::max<size_t>(state_bytes, 1))).ok() ||
+      !(s = m.d_live.reserve(std::max<size_t>(m.live.size(), 1))).ok())
+    return s;
+  if (state_bytes) NEEDLE_HIP_TRY(hipMemsetAsync(m.state.ptr, 0, state_bytes, stream));
+  (void)hipGetDevice(&m.device);
+  if (!m.live.empty())
+    NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_live.ptr, m.live.data(), m.live.size() * sizeof(CrossLive), hipMemcpyHostToDevice, stream));
+  if (num_resident) {
+    if (!(s = m.d_resident.reserve(table.size())).ok()) return s;
+    NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_resident.ptr, table.data(), table.size() * sizeof(CrossResident), hipMemcpyHostToDevice, stream));
+    if (on_device) {
+      KernelTimer timer("crossmatch_gather_resident", stream);
+      if (plan.hist_words > first_resident_word)
+        hipLaunchKernelGGL(crossmatch_gather_resident_kernel, dim3((uint32_t)std::min<size_t>(table.size(), 4096)), dim3(kThreads), 0, stream,
+                           hashes, (const CrossResident *)m.d_resident.ptr, (uint32_t)table.size(), m.rg, m.hist.ptr);
+      NEEDLE_HIP_TRY(hipGetLastError());
+    } else {
+      std::vector<uint32_t> packed(plan.hist_words - first_resident_word);
+      for (size_t i = 0; i < table.size(); i++)
+        if (table[i].len)
+          std::memcpy(packed.data() + (plan.res_hist[i % regions] - first_resident_word) + table[i].prefix, hashes + resident[i].offset,
+                      (size_t)table[i].len * sizeof(uint32_t));
+      if (!packed.empty())
+        NEEDLE_HIP_TRY(hipMemcpyAsync(m.hist.ptr + first_resident_word, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+      NEEDLE_HIP_TRY(hipStreamSynchronize(stream));  // (before `packed` goes)
+    }
+  }
+  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
+  *out = std::move(cm);
+  return Status::Ok();
+}
+
+bool CrossMatcher::grouped() const { return impl_->grouped; }
+const std::vector<uint32_t> &CrossMatcher::labels() const { return impl_->labels; }
+
 Status CrossMatcher::Feed(const uint32_t *const *items, const size_t *num_items) {
   Impl &m = *impl_;
   if (!items || !num_items) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
@@ -647,6 +868,10 @@ void CrossMatcher::Stats(uint64_t stats[4]) const {
   stats[0] = m.feeds;
   stats[1] = m.launches;
   stats[2] = m.cells;
+  if (m.grouped) {  // frontiers and hashes by the live pairs' rule, the two tables, the run slab
+    stats[3] = m.grouped_state_bytes + m.live.size() * sizeof(CrossLive) + m.res_rows.size() * sizeof(CrossResident) + m.slab.bytes();
+    return;
+  }
   stats[3] = StateBytesResident(m.res_rows.data(), m.residents, m.videos, m.regions, m.max_items) + m.res_rows.size() * sizeof(CrossResident) +
              m.slab.bytes();
 }

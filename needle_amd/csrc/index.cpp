@@ -181,7 +181,8 @@ Status Index::add_grouped(const std::vector<const FrameHashesData *> &fh, const 
   return append(fh, nullptr, nullptr, labels);
 }
 
-// Groups in the matcher and the cross-matcher are out of scope: their runs name pairs across groups.
+// The plain streamed routes on a grouped index: their objects' runs name pairs across groups.  (A grouped cross-matcher has
+// entry points of its own, crossmatcher_grouped / add_matched_grouped: DESIGN.md 6h; groups in the matcher are out of scope.)
 Status Index::refuse_grouped(const char *route) const {
   return Status::Make(NeedleError_InvalidArgument, std::string("index ") + route + ": a grouped index has no streamed routes (use needle_hip_index_add_grouped)");
 }
@@ -189,6 +190,15 @@ Status Index::refuse_grouped(const char *route) const {
 Status Index::add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &fh) {
   if (grouped_) return refuse_grouped("add_matched");
   if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_matched: null argument");
+  return append(fh, matcher, nullptr);
+}
+
+// The grouped index's streamed route: a grouped cross-matcher made by crossmatcher_grouped, whose labels name
+// the arriving videos' groups.
+Status Index::add_matched_grouped(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &fh) {
+  if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_matched_grouped: null argument");
+  if (!grouped_)
+    return Status::Make(NeedleError_InvalidArgument, "index add_matched_grouped: not a grouped index (needle_hip_index_add_matched takes a plain one)");
   return append(fh, matcher, nullptr);
 }
 
@@ -243,6 +253,29 @@ Status Index::crossmatcher(size_t videos, const size_t *max_items, const uint32_
   return Status::Ok();
 }
 
+// The grouped index's cross-matcher: the residents are the index's videos in index order under the index's labels, `groups` the
+// arriving videos' labels; only the rows of the groups that arrive are gathered from the arena (crossmatch.hip).
+Status Index::crossmatcher_grouped(size_t videos, const uint32_t *groups, const size_t *max_items, const uint32_t *min_len,
+                                   std::unique_ptr<CrossMatcher> *out) {
+  if (!out || !groups || !max_items || !min_len) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
+  if (!grouped_)
+    return Status::Make(NeedleError_InvalidArgument,
+                        "index crossmatcher_grouped: not a grouped index (needle_hip_index_crossmatcher_new takes a plain one)");
+  if (const char *what =
+          CrossMatcher::GroupedShapeError(rows_.seqs.data(), videos_.size(), labels_.data(), videos, groups, regions_, max_items, min_len))
+    return Status::Make(NeedleError_InvalidArgument, what);
+  const uint32_t *d_hashes = nullptr;
+  Status s = index_store_arena(store_, &d_hashes);
+  if (!s.ok()) return s;
+  std::unique_ptr<CrossMatcher> cm;
+  s = CrossMatcher::CreateGroupedDevice(d_hashes, d_hashes ? rows_.hashes : 0, rows_.seqs.data(), videos_.size(), labels_.data(), videos, groups,
+                                        regions_, max_items, min_len, cmp_.hash_match_threshold(), &cm);
+  if (!s.ok()) return s;
+  cm->set_origin(CrossMatcher::Origin{id_, generation_});
+  *out = std::move(cm);
+  return Status::Ok();
+}
+
 // add, add_matched and add_streamed: with a cross-matcher (made from the index) its runs stand in for the scan of the new pairs;
 // with a matcher made from the index (`streamed`) its runs stand in for the resident x arriving pairs and those of `matcher`, a
 // cross-matcher over the arriving videos alone (null: one video), for the arriving pairs; everything else is one path.
@@ -253,11 +286,6 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
   const size_t k = fh.size(), n0 = videos_.size(), n1 = n0 + k, R = regions_;
   std::vector<uint32_t> all_labels;
   std::unique_ptr<const IndexGroupTables> groups;
-  if (labels) {
-    all_labels = labels_;
-    all_labels.insert(all_labels.end(), labels, labels + k);
-    groups.reset(new IndexGroupTables(all_labels.data(), n1));
-  }
   const std::string who = streamed ? "index add_streamed: " : "index add_matched: ";
   auto refuse = [&](const char *what) { return Status::Make(NeedleError_InvalidArgument, who + what); };
   if (streamed) {
@@ -288,6 +316,18 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
     if (!(s = matcher->Ready(nullptr, &complete)).ok()) return s;
     if (!complete) return refuse("the matcher is not complete");
     if (k != matcher->videos() || R != matcher->regions() || n0 != matcher->residents()) return refuse("not the matcher's number of videos");
+    if (grouped_ != matcher->grouped())
+      return refuse(grouped_ ? "the matcher has no groups (needle_hip_index_crossmatcher_new_grouped makes one)" : "the matcher has groups");
+    if (grouped_) {  // the arriving videos' labels are the matcher's
+      if (matcher->labels().size() != n1 || !std::equal(labels_.begin(), labels_.end(), matcher->labels().begin()))
+        return refuse("the matcher's labels are not the index's");
+      labels = matcher->labels().data() + n0;
+    }
+  }
+  if (labels) {
+    all_labels = labels_;
+    all_labels.insert(all_labels.end(), labels, labels + k);
+    groups.reset(new IndexGroupTables(all_labels.data(), n1));
   }
   if (n1 >= 0xFFFFFFFFull) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 videos");
   auto video = [&](size_t v) -> const FrameHashesData & { return v < n0 ? videos_[v] : *fh[v - n0]; };
@@ -368,7 +408,7 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
       uint32_t least = UINT32_MAX;
       for (size_t j = n0; j < n1; j++)
         for (size_t i = streamed ? n0 : 0; i < j; i++)  // (streamed: the cross-matcher had the arriving pairs only)
-          if (rows.min_len[i * R + r] && rows.min_len[j * R + r]) least = std::min(least, std::max(rows.min_len[i * R + r], rows.min_len[j * R + r]));
+          if ((!groups || groups->group_of[i] == groups->group_of[j]) && rows.min_len[i * R + r] && rows.min_len[j * R + r]) least = std::min(least, std::max(rows.min_len[i * R + r], rows.min_len[j * R + r]));
       if (matcher->min_len(r) > least) return refuse("the matcher's min_len exceeds the shortest run a pair can hold");
     }
   }

@@ -52,6 +52,12 @@ class Index {
   // add() with the runs of a complete matcher made by crossmatcher() since the last change in place of the scan: the same
   // index afterwards, no pair searched again.  Every check comes before the commit; on failure the index is as it was.
   Status add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &videos);
+  // The grouped index's forms of the two: a grouped cross-matcher (crossmatch.h CreateGroupedDevice) whose residents are the
+  // index's videos under the index's labels and whose `videos` arriving ones carry `groups`; add_matched_grouped appends them
+  // under those labels and leaves what add_grouped would.  A plain index: InvalidArgument.
+  Status crossmatcher_grouped(size_t videos, const uint32_t *groups, const size_t *max_items, const uint32_t *min_len,
+                              std::unique_ptr<CrossMatcher> *out);
+  Status add_matched_grouped(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &videos);
   // The second route, for an index too large for one cross-matcher (its live problems are a grid dimension): a matcher whose
   // sources are the index's rows, region-aware, with `videos` * regions lanes; each source's min_len is the row's own.  It
   // remembers the index and its generation.  An empty index has nothing resident: InvalidArgument.

@@ -101,6 +101,38 @@ __global__ __launch_bounds__(256) void index_ingest_runs_kernel(const NeedleHipR
   }
 }
 
+// The grouped index's form: the list is a grouped cross-matcher's, whose runs name their pair by the grouped id over the V
+// labels (`from`: pair_ids.h GroupView, base[] moves as groups grow), and the store wants the append-stable id (`to`:
+// IndexGroupView) less the append's first.  Both views are over the same list, so they share every table but base / vbase.
+// The same filter and the same kIngestBadRun rule: ingest_retag decides, and only the tag is replaced.
+__global__ __launch_bounds__(256) void index_ingest_runs_grouped_kernel(const NeedleHipRun *__restrict__ in, uint32_t num_runs, GroupView from,
+                                                                        IndexGroupView to, uint64_t first_pair, uint32_t n0, uint32_t regions,
+                                                                        const uint32_t *__restrict__ min_len,
+                                                                        const uint32_t *__restrict__ row_len, NeedleHipRun *__restrict__ out,
+                                                                        uint32_t capacity, uint32_t *__restrict__ count,
+                                                                        uint32_t *__restrict__ error) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); base < num_runs; base += stride) {
+    const uint64_t k = base + lane;
+    bool keep = false;
+    NeedleHipRun run{};
+    if (k < num_runs) {
+      run = in[k];
+      uint32_t a = 0, b = 0;
+      const uint32_t r = run.problem % regions;
+      uint64_t id = 0;
+      bool good = grouped_pair_at(from, run.problem / regions, &a, &b) && b >= n0 && index_group_pair(to, a, b, &id) && id >= first_pair;
+      if (good) {
+        keep = ingest_retag(run, a, b, r, n0, regions, min_len, row_len, &good);
+        run.problem = (uint32_t)((id - first_pair) * regions + r);
+      }
+      if (!good) atomicOr(error, kIngestBadRun);
+    }
+    ingest_push(keep, run, out, capacity, count);
+  }
+}
+
 // ---- an append fed from a matcher made from the store and a cross-matcher over the arriving videos (gpu_index_append_streamed) --
 // Both lists in one launch, the matcher's first.  A matcher run names its resident row (problem = resident * regions + region)
 // and came from lane run_lane[q] = t * regions + region: pair (resident, n0 + t).  A cross-matcher run names its pair i-major
@@ -375,6 +407,7 @@ struct IndexStore {
   DeviceBuffer<uint32_t> flag, list, links, run_count;
   DeviceBuffer<NeedleHipRun> runs, matched_runs;  // the run list; a matcher's, as uploaded
   DeviceBuffer<uint32_t> matched_min_len, matched_error, run_lane;
+  DeviceBuffer<uint64_t> matched_base;  // a grouped matcher's list: base[] of pair_ids.h GroupView over the operation's list
   DeviceBuffer<IndexLaneRow> lane_rows;
   DeviceBuffer<Candidate> cand;
   DeviceBuffer<NeedleHipSearchResult> results;
@@ -731,12 +764,24 @@ Status gpu_index_append_matched(IndexStore *st, const IndexAppend &a, const Inde
   if (!(s = index_append_tables(st, a, stream)).ok()) return s;
   if (!(s = st->segments.reserve(std::max<size_t>(m.num_lanes, 1))).ok()) return s;
   NEEDLE_HIP_TRY(upload(st->segments.ptr, m.lanes, m.num_lanes, stream));
+  GroupView from{};  // a grouped index: the matcher's numbering over the operation's list, its tables the ones just uploaded
+  if (a.groups) {
+    if (!(s = st->matched_base.reserve(a.groups->base.size())).ok()) return s;
+    NEEDLE_HIP_TRY(upload(st->matched_base.ptr, a.groups->base.data(), a.groups->base.size(), stream));
+    const IndexGroupView &to = operation_groups(st);
+    from = GroupView{to.group_of, to.rank_of, to.size, to.first, st->matched_base.ptr, to.members, (uint32_t)a.groups->size.size()};
+  }
   return index_append_ingested(st, a, m.runs, m.num_runs, m.min_len, stream, out, [&](uint32_t capacity) {
     if (m.num_lanes)
       hipLaunchKernelGGL(index_compare_rows_kernel, dim3((uint32_t)std::min<size_t>(m.num_lanes, 4096)), dim3(256), 0, stream,
                          (const IndexSegment *)st->segments.ptr, (uint32_t)m.num_lanes, (const uint32_t *)st->cur->hash.ptr(), m.history,
                          st->matched_error.ptr);
-    if (m.num_runs)
+    if (m.num_runs && a.groups)
+      hipLaunchKernelGGL(index_ingest_runs_grouped_kernel, dim3((uint32_t)std::min<size_t>(4096, (m.num_runs + 255) / 256)), dim3(256), 0, stream,
+                         (const NeedleHipRun *)st->matched_runs.ptr, (uint32_t)m.num_runs, from, operation_groups(st), append_first_pair(a), a.n0,
+                         a.regions, (const uint32_t *)st->matched_min_len.ptr, (const uint32_t *)st->cur->row_len.ptr(), st->runs.ptr, capacity,
+                         st->run_count.ptr, st->matched_error.ptr);
+    else if (m.num_runs)
       hipLaunchKernelGGL(index_ingest_runs_kernel, dim3((uint32_t)std::min<size_t>(4096, (m.num_runs + 255) / 256)), dim3(256), 0, stream,
                          (const NeedleHipRun *)st->matched_runs.ptr, (uint32_t)m.num_runs, a.n1, a.n0, a.regions,
                          (const uint32_t *)st->matched_min_len.ptr, (const uint32_t *)st->cur->row_len.ptr(), st->runs.ptr, capacity,

@@ -406,6 +406,20 @@ extern "C" {
         frame_hashes: *const *const FrameHashes,
         k: usize,
     ) -> NeedleError;
+    pub fn needle_hip_index_crossmatcher_new_grouped(
+        index: *mut NeedleHipIndex,
+        videos: usize,
+        groups: *const u32,
+        max_items: *const usize,
+        min_len: *const u32,
+        output: *mut *mut NeedleHipCrossMatcher,
+    ) -> NeedleError;
+    pub fn needle_hip_index_add_matched_grouped(
+        index: *mut NeedleHipIndex,
+        matcher: *mut NeedleHipCrossMatcher,
+        frame_hashes: *const *const FrameHashes,
+        k: usize,
+    ) -> NeedleError;
     pub fn needle_hip_index_matcher_new(index: *mut NeedleHipIndex, videos: usize, output: *mut *mut NeedleHipMatcher) -> NeedleError;
     pub fn needle_hip_index_add_streamed(
         index: *mut NeedleHipIndex,
@@ -694,5 +708,29 @@ extern "C" {
         max_items: *const usize,
     ) -> usize;
     pub fn needle_hip_crossmatcher_resident(matcher: *const NeedleHipCrossMatcher, num_resident: *mut usize) -> NeedleError;
+    pub fn needle_hip_crossmatcher_new_grouped(
+        hashes: *const u32,
+        num_hashes: usize,
+        resident: *const NeedleHipSeq,
+        num_resident: usize,
+        resident_groups: *const u32,
+        videos: usize,
+        groups: *const u32,
+        regions: usize,
+        max_items: *const usize,
+        min_len: *const u32,
+        threshold: u32,
+        output: *mut *mut NeedleHipCrossMatcher,
+    ) -> NeedleError;
+    pub fn needle_hip_crossmatcher_state_bytes_grouped(
+        resident: *const NeedleHipSeq,
+        num_resident: usize,
+        resident_groups: *const u32,
+        videos: usize,
+        groups: *const u32,
+        regions: usize,
+        max_items: *const usize,
+    ) -> usize;
+    pub fn needle_hip_crossmatcher_groups(matcher: *const NeedleHipCrossMatcher, labels: *mut u32, n: usize) -> NeedleError;
     pub fn needle_hip_host_free(ptr: *mut c_void);
 }

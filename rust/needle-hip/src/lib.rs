@@ -1003,6 +1003,71 @@ impl CrossMatcher {
         Ok(CrossMatcher { raw, lanes: videos * regions })
     }
 
+    /// Groups of videos: `groups[t]` is the label of arriving video t, `resident_groups[k]` that of resident k, whose rows are
+    /// `resident` as in `with_resident` (both may be empty).  Only same-label pairs with an arriving end are live; `problem`
+    /// of a run is (the grouped pair id over all K + N labels) * regions + region, the numbering `group_pairs` decodes.
+    pub fn with_groups(
+        resident: &[&[u32]],
+        resident_groups: &[u32],
+        groups: &[u32],
+        max_items: &[usize],
+        min_len: &[u32],
+        threshold: u32,
+    ) -> Result<Self> {
+        assert_eq!(max_items.len(), min_len.len(), "one max_items and one min_len per region");
+        let regions = max_items.len();
+        assert!(regions > 0 && resident.len() == resident_groups.len() * regions, "one resident row per video and region");
+        let mut arena: Vec<u32> = Vec::new();
+        let mut seqs = Vec::with_capacity(resident.len());
+        for hashes in resident {
+            seqs.push(ffi::NeedleHipSeq { offset: arena.len() as u32, len: hashes.len() as u32 });
+            arena.extend_from_slice(hashes);
+        }
+        let mut raw = ptr::null_mut();
+        unsafe {
+            check(ffi::needle_hip_crossmatcher_new_grouped(
+                arena.as_ptr(),
+                arena.len(),
+                seqs.as_ptr(),
+                resident_groups.len(),
+                resident_groups.as_ptr(),
+                groups.len(),
+                groups.as_ptr(),
+                regions,
+                max_items.as_ptr(),
+                min_len.as_ptr(),
+                threshold,
+                &mut raw,
+            ))?
+        };
+        Ok(CrossMatcher { raw, lanes: groups.len() * regions })
+    }
+
+    /// The labels of all K + N videos of a grouped object, residents first; an error for an object without groups.
+    pub fn groups(&self) -> Result<Vec<u32>> {
+        let (videos, _) = self.shape()?;
+        let mut labels = vec![0u32; self.resident()? + videos];
+        unsafe { check(ffi::needle_hip_crossmatcher_groups(self.raw, labels.as_mut_ptr(), labels.len()))? };
+        Ok(labels)
+    }
+
+    /// Bytes of frontiers and hashes a grouped object allocates (resident rows of these lengths, row order); 0 where
+    /// creation would refuse.
+    pub fn state_bytes_grouped(resident_len: &[u32], resident_groups: &[u32], groups: &[u32], max_items: &[usize]) -> usize {
+        let seqs: Vec<ffi::NeedleHipSeq> = resident_len.iter().map(|&len| ffi::NeedleHipSeq { offset: 0, len }).collect();
+        unsafe {
+            ffi::needle_hip_crossmatcher_state_bytes_grouped(
+                seqs.as_ptr(),
+                resident_groups.len(),
+                resident_groups.as_ptr(),
+                groups.len(),
+                groups.as_ptr(),
+                max_items.len(),
+                max_items.as_ptr(),
+            )
+        }
+    }
+
     /// The known videos the object was created with (0 without `with_resident`).
     pub fn resident(&self) -> Result<usize> {
         let mut k = 0usize;
@@ -1233,6 +1298,31 @@ impl Index {
     pub fn add_matched(&mut self, matcher: &mut CrossMatcher, frame_hashes: &[&FrameHashes]) -> Result<()> {
         let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
         unsafe { check(ffi::needle_hip_index_add_matched(self.raw, matcher.raw, raw.as_ptr(), raw.len())) }
+    }
+
+    /// `crossmatcher` for a grouped index: the residents carry the index's labels, `groups[t]` is the label of arriving video
+    /// t, and only same-label pairs are live.  Hand it to `add_matched_grouped`.
+    pub fn crossmatcher_grouped(&mut self, groups: &[u32], max_items: &[usize], min_len: &[u32]) -> Result<CrossMatcher> {
+        assert_eq!(max_items.len(), min_len.len(), "one max_items and one min_len per region");
+        let mut raw = ptr::null_mut();
+        unsafe {
+            check(ffi::needle_hip_index_crossmatcher_new_grouped(
+                self.raw,
+                groups.len(),
+                groups.as_ptr(),
+                max_items.as_ptr(),
+                min_len.as_ptr(),
+                &mut raw,
+            ))?
+        };
+        Ok(CrossMatcher { raw, lanes: groups.len() * max_items.len() })
+    }
+
+    /// Appends the arriving videos of a grouped `matcher` under its labels, with its runs in place of a scan: afterwards the
+    /// index is what `add_grouped` leaves.  On error the index is as it was before the call.
+    pub fn add_matched_grouped(&mut self, matcher: &mut CrossMatcher, frame_hashes: &[&FrameHashes]) -> Result<()> {
+        let raw: Vec<*const ffi::FrameHashes> = frame_hashes.iter().map(|f| f.raw as *const _).collect();
+        unsafe { check(ffi::needle_hip_index_add_matched_grouped(self.raw, matcher.raw, raw.as_ptr(), raw.len())) }
     }
 }
 
