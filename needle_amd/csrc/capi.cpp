@@ -1031,41 +1031,55 @@ enum NeedleError needle_hip_matcher_stats(const NeedleHipMatcher *matcher, uint6
 // ============================================================================================================
 // Streaming all-pairs comparator (crossmatch.hip)
 // ============================================================================================================
-enum NeedleError needle_hip_crossmatcher_new(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold,
-                                             NeedleHipCrossMatcher **output) {
-  if (!output) return NeedleError_NullArgument;
+// The four ways in fill one spec (crossmatch.h): what a call does not take stays absent.
+static CrossMatcher::Spec crossmatcher_spec(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
+                                            const uint32_t *groups, size_t regions, const size_t *max_items, const uint32_t *min_len,
+                                            uint32_t threshold) {
+  CrossMatcher::Spec spec;
+  spec.resident = resident;
+  spec.residents = num_resident;
+  spec.resident_groups = resident_groups;
+  spec.arriving = videos;
+  spec.groups = groups;
+  spec.regions = regions;
+  spec.max_items = max_items;
+  spec.min_len = min_len;
+  spec.threshold = threshold;
+  return spec;
+}
+
+// ... and every way to a cross-matcher, the index's two included, wraps what `make` made.
+static NeedleError crossmatcher_from(NeedleHipCrossMatcher **output, const std::function<Status(std::unique_ptr<CrossMatcher> *)> &make) {
   return guarded([&]() -> NeedleError {
     auto m = std::make_unique<NeedleHipCrossMatcher>();
-    Status s = CrossMatcher::Create(lanes, max_items, min_len, threshold, &m->inner);
+    Status s = make(&m->inner);
     if (!s.ok()) return report(s);
     *output = m.release();
     return NeedleError_Ok;
   });
 }
+static NeedleError crossmatcher_new(const CrossMatcher::Spec &spec, const uint32_t *hashes, size_t num_hashes, NeedleHipCrossMatcher **output) {
+  return crossmatcher_from(output, [&](std::unique_ptr<CrossMatcher> *out) { return CrossMatcher::Create(spec, hashes, num_hashes, false, out); });
+}
+
+enum NeedleError needle_hip_crossmatcher_new(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold,
+                                             NeedleHipCrossMatcher **output) {
+  if (!output) return NeedleError_NullArgument;
+  return crossmatcher_new(crossmatcher_spec(nullptr, 0, nullptr, lanes, nullptr, 1, &max_items, &min_len, threshold), nullptr, 0, output);
+}
 
 enum NeedleError needle_hip_crossmatcher_new_regions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len,
                                                      uint32_t threshold, NeedleHipCrossMatcher **output) {
   if (!output || !max_items || !min_len) return NeedleError_NullArgument;
-  return guarded([&]() -> NeedleError {
-    auto m = std::make_unique<NeedleHipCrossMatcher>();
-    Status s = CrossMatcher::CreateRegions(videos, regions, max_items, min_len, threshold, &m->inner);
-    if (!s.ok()) return report(s);
-    *output = m.release();
-    return NeedleError_Ok;
-  });
+  return crossmatcher_new(crossmatcher_spec(nullptr, 0, nullptr, videos, nullptr, regions, max_items, min_len, threshold), nullptr, 0, output);
 }
 
 enum NeedleError needle_hip_crossmatcher_new_resident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident,
                                                       size_t num_resident, size_t videos, size_t regions, const size_t *max_items,
                                                       const uint32_t *min_len, uint32_t threshold, NeedleHipCrossMatcher **output) {
   if (!output || !max_items || !min_len || (num_resident && !resident) || (num_hashes && !hashes)) return NeedleError_NullArgument;
-  return guarded([&]() -> NeedleError {
-    auto m = std::make_unique<NeedleHipCrossMatcher>();
-    Status s = CrossMatcher::CreateResident(hashes, num_hashes, resident, num_resident, videos, regions, max_items, min_len, threshold, &m->inner);
-    if (!s.ok()) return report(s);
-    *output = m.release();
-    return NeedleError_Ok;
-  });
+  return crossmatcher_new(crossmatcher_spec(resident, num_resident, nullptr, videos, nullptr, regions, max_items, min_len, threshold), hashes,
+                          num_hashes, output);
 }
 
 enum NeedleError needle_hip_crossmatcher_new_grouped(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident,
@@ -1074,19 +1088,14 @@ enum NeedleError needle_hip_crossmatcher_new_grouped(const uint32_t *hashes, siz
                                                      const uint32_t *min_len, uint32_t threshold, NeedleHipCrossMatcher **output) {
   if (!output || !max_items || !min_len || !groups || (num_resident && (!resident || !resident_groups)) || (num_hashes && !hashes))
     return NeedleError_NullArgument;
-  return guarded([&]() -> NeedleError {
-    auto m = std::make_unique<NeedleHipCrossMatcher>();
-    Status s = CrossMatcher::CreateGrouped(hashes, num_hashes, resident, num_resident, resident_groups, videos, groups, regions, max_items,
-                                           min_len, threshold, &m->inner);
-    if (!s.ok()) return report(s);
-    *output = m.release();
-    return NeedleError_Ok;
-  });
+  return crossmatcher_new(crossmatcher_spec(resident, num_resident, resident_groups, videos, groups, regions, max_items, min_len, threshold),
+                          hashes, num_hashes, output);
 }
 
 size_t needle_hip_crossmatcher_state_bytes_grouped(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups,
                                                    size_t videos, const uint32_t *groups, size_t regions, const size_t *max_items) {
-  return CrossMatcher::StateBytesGrouped(resident, num_resident, resident_groups, videos, groups, regions, max_items);
+  if (!groups) return 0;  // (without labels it would be another object's size)
+  return CrossMatcher::StateBytes(crossmatcher_spec(resident, num_resident, resident_groups, videos, groups, regions, max_items, nullptr, 0));
 }
 
 enum NeedleError needle_hip_crossmatcher_groups(const NeedleHipCrossMatcher *matcher, uint32_t *labels, size_t n) {
@@ -1155,15 +1164,15 @@ enum NeedleError needle_hip_crossmatcher_stats(const NeedleHipCrossMatcher *matc
   return NeedleError_Ok;
 }
 
-size_t needle_hip_crossmatcher_state_bytes(size_t lanes, size_t max_items) { return CrossMatcher::StateBytes(lanes, max_items); }
+size_t needle_hip_crossmatcher_state_bytes(size_t lanes, size_t max_items) { return needle_hip_crossmatcher_state_bytes_regions(lanes, 1, &max_items); }
 
 size_t needle_hip_crossmatcher_state_bytes_regions(size_t videos, size_t regions, const size_t *max_items) {
-  return CrossMatcher::StateBytesRegions(videos, regions, max_items);
+  return needle_hip_crossmatcher_state_bytes_resident(nullptr, 0, videos, regions, max_items);
 }
 
 size_t needle_hip_crossmatcher_state_bytes_resident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions,
                                                     const size_t *max_items) {
-  return CrossMatcher::StateBytesResident(resident, num_resident, videos, regions, max_items);
+  return CrossMatcher::StateBytes(crossmatcher_spec(resident, num_resident, nullptr, videos, nullptr, regions, max_items, nullptr, 0));
 }
 
 enum NeedleError needle_hip_crossmatcher_resident(const NeedleHipCrossMatcher *matcher, size_t *num_resident) {
@@ -1588,13 +1597,7 @@ enum NeedleError needle_hip_index_pairs_scanned(const NeedleHipIndex *index, uin
 enum NeedleError needle_hip_index_crossmatcher_new(NeedleHipIndex *index, size_t videos, const size_t *max_items, const uint32_t *min_len,
                                                    NeedleHipCrossMatcher **output) {
   if (!index || !max_items || !min_len || !output) return NeedleError_NullArgument;
-  return guarded([&]() -> NeedleError {
-    auto m = std::make_unique<NeedleHipCrossMatcher>();
-    Status s = index->inner.crossmatcher(videos, max_items, min_len, &m->inner);
-    if (!s.ok()) return report(s);
-    *output = m.release();
-    return NeedleError_Ok;
-  });
+  return crossmatcher_from(output, [&](std::unique_ptr<CrossMatcher> *out) { return index->inner.crossmatcher(videos, max_items, min_len, out); });
 }
 
 enum NeedleError needle_hip_index_add_matched(NeedleHipIndex *index, NeedleHipCrossMatcher *matcher, const FrameHashes *const *frame_hashes,
@@ -1616,12 +1619,8 @@ enum NeedleError needle_hip_index_add_matched(NeedleHipIndex *index, NeedleHipCr
 enum NeedleError needle_hip_index_crossmatcher_new_grouped(NeedleHipIndex *index, size_t videos, const uint32_t *groups, const size_t *max_items,
                                                            const uint32_t *min_len, NeedleHipCrossMatcher **output) {
   if (!index || !groups || !max_items || !min_len || !output) return NeedleError_NullArgument;
-  return guarded([&]() -> NeedleError {
-    auto m = std::make_unique<NeedleHipCrossMatcher>();
-    Status s = index->inner.crossmatcher_grouped(videos, groups, max_items, min_len, &m->inner);
-    if (!s.ok()) return report(s);
-    *output = m.release();
-    return NeedleError_Ok;
+  return crossmatcher_from(output, [&](std::unique_ptr<CrossMatcher> *out) {
+    return index->inner.crossmatcher_grouped(videos, groups, max_items, min_len, out);
   });
 }
 

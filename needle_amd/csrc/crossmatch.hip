@@ -17,38 +17,33 @@
 //
 // Regions (needle_hip_crossmatcher_new_regions): the lanes are videos x R, lane = video * R + region (R = 1 or 2: openings
 // and endings, the numbering of the library's arena rows and of comparator.cpp's seqs), and only lanes of one region are
-// matched against each other.  blockIdx.y of the walk is pair * R + region, which is also NeedleHipRun.problem; the
-// workgroup reads lane-table entries a * R + r and b * R + r.  The regions have capacities and min_len of their own: the
-// histories (videos x max_items[r] words) and the frontiers (pairs x 4 x max_items[r] entries) lie region after region,
-// and a region's max_items, min_len and two bases travel by value in the kernels' arguments (CrossRegions).  Still three
+// matched against each other, each region with a capacity and a min_len of its own.  blockIdx.y of the walk is live pair * R
+// + region; a region's max_items, min_len and bases travel by value in the kernels' arguments (CrossRegions).  Still three
 // launches, one upload and one download per round; R = 1 is the same code with the second region's fields unused.
 //
 // Resident videos (needle_hip_crossmatcher_new_resident): K videos that are complete at creation come before the N arriving
 // ones in the video list, V = K + N.  Only the arriving videos have lanes; a resident row (k, r) is a row of the resident
-// table (CrossResident: its length and the sum of the lengths before it in its region, uploaded once) and its hashes lie
-// behind the histories in the same buffer.  The live problems are (a, b, r) with b >= K.  blockIdx.y of the walk is the
-// live numbering q * R + r: q = t * K + k for resident k against arriving t, then the arriving pairs i-major; the
-// comparator's index over V videos, NeedleHipRun.problem, comes from (a, b) in closed form.  A resident is a lane that
-// holds all its items, finished before the first round, with no new items ever: only the column direction has cells, and the
-// state of (k, t, r) is the col frontier alone, two sets of len(k, r) entries at 2 * (t * S_r + prefix(k, r)) behind the
-// arriving pairs' frontiers (S_r = the region's resident hashes).  A resident is a complete X (stream_walk.h): a run that
-// reaches its last row leaves with the round's runs, and the host holds it back until the arriving lane finishes, which is
-// when the reporting rule hands out what is open on a frontier.  K = 0 is the object above.
+// table (CrossResident: its length and the sum of the lengths before it in its region, uploaded once), and the live problems
+// are (a, b, r) with b >= K.  A resident is a lane that holds all its items, finished before the first round, with no new items
+// ever: only the column direction has cells, and its state is the col frontier alone.  A resident is a complete X
+// (stream_walk.h): a run that reaches its last row leaves with the round's runs, and the host holds it back until the arriving
+// lane finishes, which is when the reporting rule hands out what is open on a frontier.
 //
 // Groups of videos (needle_hip_crossmatcher_new_grouped): every resident and every arriving video carries a label, and the live
-// problems are the same-label pairs with an arriving end only.  Which they are, their NeedleHipRun.problem (the grouped id of
-// pair_ids.h over all V labels, x R + region) and where their state lies is decided on the host (cross_pairs.h) and uploaded
-// once as the live-pair table, next to the resident table; blockIdx.y of the walk is an index into it, and the walk takes
-// its pair lookup as a policy: ClosedFormPairs (the arithmetic above, the objects above) or ListedLivePairs (one table entry
-// at an address the workgroup shares).  State and hashes exist for live pairs only; a round is still three launches and
-// uploads nothing per pair.  The land and the simhash kernel do not know about groups: the rows travel in the run.
+// problems are the same-label pairs with an arriving end only.  State and hashes exist for live pairs only; the land and the
+// simhash kernel do not know about groups: the rows travel in the run.
+//
+// Which problems are live, their order, NeedleHipRun.problem, where the hashes and every problem's state lie, what is
+// allocated and every refusal are decided once for all these objects, on the host, by plan_cross_pairs (cross_pairs.h, which
+// describes the layout); Create below executes that plan.  The walk takes its pair lookup as a policy: ClosedFormPairs (an
+// object without labels: the plan's one-label layout by arithmetic, nothing uploaded) or ListedLivePairs (one entry of the
+// plan's live-pair table, uploaded once next to the resident table, at an address the workgroup shares).
 #include "crossmatch.h"
 
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
-#include "cross_pairs.h"
 #include "stream_round.h"
 #include "stream_walk.h"
 
@@ -59,10 +54,6 @@ namespace {
 constexpr uint32_t kParity = 1u;     // lane flags: the set that holds the state this lane's feeds flip
 constexpr uint32_t kFinished = 2u;   // finished before this round
 constexpr uint32_t kFinishing = 4u;  // finished by this round
-constexpr size_t kMaxLanes = 256;     // videos: 32 640 pairs, and pair * regions + region is a grid dimension (65 280 <= 65 535)
-constexpr size_t kMaxRegions = 2;
-constexpr size_t kMaxProblems = 65535;  // live problems (with residents: K N + N (N - 1) / 2 pairs) x regions: gridDim.y
-constexpr uint64_t kMaxRowItems = 0x7FFFFFF0ull;
 
 struct CrossLane {
   uint32_t fed, width;  // J and the new items [J, J + width)
@@ -116,8 +107,8 @@ __global__ __launch_bounds__(kThreads) void crossmatch_land_kernel(const uint32_
   land_chunks<CrossLane>(round_buf, count, [&](const CrossLane &) { return hist + lane_row(rg, blockIdx.y); });
 }
 
-// Resident rows from an arena in device memory (the index store's) to where CreateResident packs them: a workgroup per row,
-// consecutive lanes move consecutive words.  Creation checked every row against the arena (shape_error).
+// Resident rows from an arena in device memory (the index store's) to where Create packs them: a workgroup per row,
+// consecutive lanes move consecutive words.  Creation checked every row against the arena (plan_cross_pairs).
 __global__ __launch_bounds__(kThreads) void crossmatch_gather_resident_kernel(const uint32_t *__restrict__ arena,
                                                                               const CrossResident *__restrict__ resident, uint32_t rows,
                                                                               CrossRegions rg, uint32_t *__restrict__ hist) {
@@ -267,48 +258,22 @@ struct Piece {
   bool finishing = false;
 };
 
-// Shape checks shared by the state size and creation; nullptr: fine.  `resident` holds num_resident * regions rows.
-const char *shape_error(const NeedleHipSeq *resident, size_t num_resident, size_t num_hashes, bool check_arena, size_t videos, size_t regions,
-                        const size_t *max_items) {
-  if (regions < 1 || regions > kMaxRegions) return "crossmatcher: regions must be 1 or 2";
-  if (videos < (num_resident ? 1u : 2u) || videos > kMaxLanes)
-    return num_resident ? "crossmatcher: arriving videos must be 1 to 256" : "crossmatcher: lanes (videos) must be 2 to 256";
-  for (size_t r = 0; r < regions; r++)
-    if (max_items[r] < 2 || max_items[r] > kMaxRowItems) return "crossmatcher: max_items must be 2 to 2^31 - 16";
-  // (videos <= 256 and the first test bound num_resident before anything is multiplied)
-  if (num_resident > kMaxProblems || (num_resident * videos + videos * (videos - 1) / 2) * regions > kMaxProblems)
-    return "crossmatcher: more than 65 535 live problems ((K N + N (N - 1) / 2) x regions)";
-  const uint64_t all = num_resident + videos;
-  if (all * (all - 1) / 2 * regions >= (1ull << 32)) return "crossmatcher: the problem index over all videos does not fit 32 bits";
-  for (size_t i = 0; i < num_resident * regions; i++) {
-    if (resident[i].len > kMaxRowItems) return "crossmatcher: a resident row holds more than 2^31 - 16 hashes";
-    if (check_arena && (uint64_t)resident[i].offset + resident[i].len > num_hashes) return "crossmatcher: a resident row lies outside the hash arena";
-  }
-  return nullptr;
-}
-
 }  // namespace
 
 struct CrossMatcher::Impl {
   size_t n = 0, videos = 0, regions = 1;  // n = videos * regions lanes; lane = video * regions + region
   size_t max_items[2] = {0, 0};
   uint32_t min_len[2] = {0, 0}, threshold = 0;
-  bool narrow = true;  // u16 run lengths: one width for every region
+  // what creation executed (cross_pairs.h): the layout, the pair tables, the labels, the entry width; its live-pair table is
+  // kept, and was uploaded, for a labelled object only
+  CrossPairsPlan plan;
   CrossRegions rg{};
   std::vector<LaneState> lanes;
   std::vector<NeedleHipRun> runs;
   // resident videos: K of them in front of the arriving ones; rows k * regions + r
   size_t residents = 0;
   std::vector<NeedleHipSeq> res_rows;               // (the offsets are the caller's arena's: only the lengths are used)
-  uint64_t res_cell_rows[2] = {0, 0};               // per region: the sum over its rows of max(len, 1) - 1
-  uint64_t res_longest = 0;
   std::vector<std::vector<NeedleHipRun>> held;      // per lane: runs into a resident's last row, held back until it finishes
-  // groups: a label per video of all V, residents first; the live problems are the table's (cross_pairs.h), uploaded once
-  bool grouped = false;
-  std::vector<uint32_t> labels;
-  std::unique_ptr<const GroupTables> group_tables;
-  std::vector<CrossLive> live;
-  size_t grouped_state_bytes = 0;
   DeviceBuffer<CrossLive> d_live;
   DeviceBuffer<CrossResident> d_resident;
   DeviceBuffer<uint32_t> hist, d_round;
@@ -326,58 +291,19 @@ struct CrossMatcher::Impl {
     slab.head_stage.release();
   }
 
-  size_t pairs() const { return videos * (videos - 1) / 2; }
-  size_t live_pairs() const { return residents * videos + pairs(); }
-
-  // Is this run one into a resident's last row (crossmatch_walk_kernel hands those out early)?  The comparator's pair
-  // numbering over all videos: row a starts at a (2 V - a - 1) / 2, so a resident source is a pair before row K's start.
+  // Is this run one into a resident's last row (crossmatch_walk_kernel hands those out early)?  A resident source is a video
+  // below K of the pair that NeedleHipRun.problem names (pair_ids.h, through the plan's tables).
   bool into_a_residents_last_row(const NeedleHipRun &run, size_t *lane) const {
-    if (!residents) return false;
-    if (grouped) {  // the grouped id over the V labels (pair_ids.h): a resident source is a video below K
-      uint32_t a = 0, b = 0;
-      if (!grouped_pair_at(group_tables->view(), run.problem / regions, &a, &b) || a >= residents) return false;
-      *lane = (size_t)((b - residents) * regions + run.problem % regions);
-      return (uint64_t)run.src_end + 1 == res_rows[a * regions + run.problem % regions].len;
-    }
-    const uint64_t all = residents + videos, pair = run.problem / regions, r = run.problem % regions;
-    auto row_start = [&](uint64_t a) { return a * (2 * all - a - 1) / 2; };
-    if (pair >= row_start(residents)) return false;
-    uint64_t lo = 0, hi = residents - 1;  // the last a whose row starts at or before `pair`
-    while (lo < hi) {
-      const uint64_t mid = (lo + hi + 1) / 2;
-      if (row_start(mid) <= pair) lo = mid;
-      else hi = mid - 1;
-    }
-    const uint64_t b = lo + 1 + (pair - row_start(lo));
+    uint32_t a = 0, b = 0, r = 0;
+    if (!residents || !plan.problem_at(run.problem, &a, &b, &r) || a >= residents) return false;
     *lane = (size_t)((b - residents) * regions + r);
-    return (uint64_t)run.src_end + 1 == res_rows[lo * regions + r].len;
+    return (uint64_t)run.src_end + 1 == res_rows[a * regions + r].len;
   }
   size_t capacity_of(size_t lane) const { return max_items[lane % regions]; }
 
-  // cells of all live pairs of every region when the lanes hold `fed` (+ `pieces`): per region the sum over a < b of x_a x_b,
-  // x = max(items, 1) - 1, and every resident row against every lane
+  // cells of all live problems when the lanes hold `fed` (+ `pieces`)
   uint64_t cells_of(const std::vector<Piece> *pieces) const {
-    uint64_t total = 0;
-    if (grouped) {  // the live problems one by one: x_a x_b of its two rows
-      const size_t first_lane = residents * regions;
-      auto x_of = [&](size_t row) -> uint64_t {
-        if (row < first_lane) return std::max<uint64_t>(res_rows[row].len, 1) - 1;
-        const size_t i = row - first_lane;
-        return std::max<uint64_t>(lanes[i].fed + (pieces ? (*pieces)[i].width : 0u), 1) - 1;
-      };
-      for (const CrossLive &e : live) total += x_of(e.row_a) * x_of(e.row_b);
-      return total;
-    }
-    for (size_t r = 0; r < regions; r++) {
-      uint64_t sum = 0, squares = 0;
-      for (size_t i = r; i < n; i += regions) {
-        const uint64_t x = std::max<uint64_t>(lanes[i].fed + (pieces ? (*pieces)[i].width : 0u), 1) - 1;
-        sum += x;
-        squares += x * x;
-      }
-      total += (sum * sum - squares) / 2 + res_cell_rows[r] * sum;
-    }
-    return total;
+    return plan.cells([&](size_t i) { return std::max<uint64_t>(lanes[i].fed + (pieces ? (*pieces)[i].width : 0u), 1) - 1; });
   }
 
   // One round over `pieces` (one per lane).
@@ -387,7 +313,7 @@ struct CrossMatcher::Impl {
     if (!s.ok()) return s;
     hipStream_t stream = library_stream();
     std::vector<CrossLane> lt(n);
-    uint64_t words = n * (sizeof(CrossLane) / 4), longest = std::max<uint64_t>(res_longest, 1);
+    uint64_t words = n * (sizeof(CrossLane) / 4), longest = std::max<uint64_t>(plan.longest_resident, 1);
     for (size_t i = 0; i < n; i++) {
       const LaneState &l = lanes[i];
       lt[i] = CrossLane{(uint32_t)l.fed, pieces[i].width, (uint32_t)words,
@@ -401,7 +327,8 @@ struct CrossMatcher::Impl {
     const CrossLane *d_lanes = reinterpret_cast<const CrossLane *>(d_round.ptr);
     const dim3 block(kThreads);
     const uint32_t side_blocks = (uint32_t)((longest + kCarriedRows - 1) / kCarriedRows);  // of the longest lane or resident row of any region: the others' leave at once
-    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), grouped ? (uint32_t)std::max<size_t>(live.size(), 1) : (uint32_t)(live_pairs() * regions));
+    const uint32_t problems = (uint32_t)plan.problems();  // (a labelling without live pairs still launches one row of workgroups)
+    const dim3 walk_grid(2u * (side_blocks + kTopBlocks), std::max(problems, 1u));
     std::vector<NeedleHipRun> got;
     for (;;) {
       uint32_t *d_count = nullptr;
@@ -415,15 +342,15 @@ struct CrossMatcher::Impl {
       }
       {
         KernelTimer timer("crossmatch_walk");
-        if (grouped && narrow)
+        if (plan.labelled && plan.narrow)
           hipLaunchKernelGGL((crossmatch_walk_kernel<uint16_t, ListedLivePairs, const CrossLive *, uint32_t>), walk_grid, block, 0, stream, hist.ptr,
                              reinterpret_cast<uint16_t *>(state.ptr), d_lanes, (const CrossResident *)d_resident.ptr, (uint32_t)videos, rg,
-                             side_blocks, threshold, d_runs, slab.capacity, d_count, (const CrossLive *)d_live.ptr, (uint32_t)live.size());
-        else if (grouped)
+                             side_blocks, threshold, d_runs, slab.capacity, d_count, (const CrossLive *)d_live.ptr, problems);
+        else if (plan.labelled)
           hipLaunchKernelGGL((crossmatch_walk_kernel<uint32_t, ListedLivePairs, const CrossLive *, uint32_t>), walk_grid, block, 0, stream, hist.ptr,
                              reinterpret_cast<uint32_t *>(state.ptr), d_lanes, (const CrossResident *)d_resident.ptr, (uint32_t)videos, rg,
-                             side_blocks, threshold, d_runs, slab.capacity, d_count, (const CrossLive *)d_live.ptr, (uint32_t)live.size());
-        else if (narrow)
+                             side_blocks, threshold, d_runs, slab.capacity, d_count, (const CrossLive *)d_live.ptr, problems);
+        else if (plan.narrow)
           hipLaunchKernelGGL((crossmatch_walk_kernel<uint16_t, ClosedFormPairs>), walk_grid, block, 0, stream, hist.ptr,
                              reinterpret_cast<uint16_t *>(state.ptr), d_lanes, d_resident.ptr, (uint32_t)videos, rg, side_blocks, threshold, d_runs,
                              slab.capacity, d_count);
@@ -478,282 +405,87 @@ size_t CrossMatcher::regions() const { return impl_->regions; }
 
 size_t CrossMatcher::residents() const { return impl_->residents; }
 
-size_t CrossMatcher::StateBytes(size_t lanes, size_t max_items) { return StateBytesRegions(lanes, 1, &max_items); }
-
-size_t CrossMatcher::StateBytesRegions(size_t videos, size_t regions, const size_t *max_items) {
-  return StateBytesResident(nullptr, 0, videos, regions, max_items);
-}
-
-size_t CrossMatcher::StateBytesResident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items) {
-  if (!max_items || (num_resident && !resident) || shape_error(resident, num_resident, 0, false, videos, regions, max_items)) return 0;
-  bool narrow = true;
-  for (size_t r = 0; r < regions; r++) narrow = narrow && max_items[r] < 65536;
-  for (size_t i = 0; i < num_resident * regions; i++) narrow = narrow && resident[i].len < 65536;
-  const size_t pairs = videos * (videos - 1) / 2, width = narrow ? sizeof(uint16_t) : sizeof(uint32_t);
-  size_t bytes = 0;
-  for (size_t r = 0; r < regions; r++) {
-    size_t hashes = 0;  // S_r
-    for (size_t k = 0; k < num_resident; k++) hashes += resident[k * regions + r].len;
-    bytes += pairs * 2 * 2 * max_items[r] * width + videos * max_items[r] * sizeof(uint32_t)  // the arriving pairs' L frontiers, the histories
-             + videos * 2 * hashes * width + hashes * sizeof(uint32_t);                        // the resident col frontiers, the resident hashes
-  }
-  return bytes;
-}
-
-const char *CrossMatcher::ShapeError(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items,
-                                     const uint32_t *min_len) {
-  if (const char *what = shape_error(resident, num_resident, 0, false, videos, regions, max_items)) return what;
-  for (size_t r = 0; r < regions; r++)
-    if (min_len[r] == 0) return "crossmatcher: min_len must be >= 1";
-  return nullptr;
-}
-
-Status CrossMatcher::Create(size_t lanes, size_t max_items, uint32_t min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out) {
-  return CreateRegions(lanes, 1, &max_items, &min_len, threshold, out);
-}
-
-Status CrossMatcher::CreateRegions(size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
-                                   std::unique_ptr<CrossMatcher> *out) {
-  return CreateResident(nullptr, 0, nullptr, 0, videos, regions, max_items, min_len, threshold, out);
-}
-
-Status CrossMatcher::CreateResident(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident, size_t videos,
-                                    size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
-                                    std::unique_ptr<CrossMatcher> *out) {
-  return CreateFrom(hashes, false, num_hashes, resident, num_resident, videos, regions, max_items, min_len, threshold, out);
-}
-
-Status CrossMatcher::CreateResidentDevice(const uint32_t *d_hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
-                                          size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
-                                          std::unique_ptr<CrossMatcher> *out) {
-  return CreateFrom(d_hashes, true, num_hashes, resident, num_resident, videos, regions, max_items, min_len, threshold, out);
-}
-
-// Both ways in share everything but how the resident hashes reach the histories: packed on the host and uploaded, or
-// gathered from a device arena.
-Status CrossMatcher::CreateFrom(const uint32_t *hashes, bool on_device, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
-                                size_t videos, size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
-                                std::unique_ptr<CrossMatcher> *out) {
-  if (!out || !max_items || !min_len || (num_resident && !resident) || (num_hashes && !hashes))
-    return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
-  if (const char *what = shape_error(resident, num_resident, num_hashes, true, videos, regions, max_items))
-    return Status::Make(NeedleError_InvalidArgument, what);
-  if (const char *what = ShapeError(resident, num_resident, videos, regions, max_items, min_len)) return Status::Make(NeedleError_InvalidArgument, what);
-  std::unique_ptr<CrossMatcher> cm(new CrossMatcher());
-  Impl &m = *cm->impl_;
-  m.videos = videos;
-  m.regions = regions;
-  m.residents = num_resident;
-  m.n = videos * regions;
-  m.threshold = threshold;
-  m.lanes = std::vector<LaneState>(m.n);
-  m.held.resize(m.n);
-  m.res_rows.assign(resident, resident + num_resident * regions);
-  // the resident table: per region, a row's place among the region's resident hashes
-  std::vector<CrossResident> table(num_resident * regions);
-  size_t res_total[2] = {0, 0};
-  for (size_t k = 0; k < num_resident; k++)
-    for (size_t r = 0; r < regions; r++) {
-      const NeedleHipSeq &row = resident[k * regions + r];
-      table[k * regions + r] = CrossResident{res_total[r], row.len, row.offset};
-      res_total[r] += row.len;
-      m.res_cell_rows[r] += std::max<uint64_t>(row.len, 1) - 1;
-      m.res_longest = std::max<uint64_t>(m.res_longest, row.len);
-      m.narrow = m.narrow && row.len < 65536;
-    }
-  // histories and frontiers region after region, then the resident hashes and the resident frontiers region after region:
-  // the bases in words and in entries
-  size_t hist_words = 0, state_entries = 0;
-  for (size_t r = 0; r < regions; r++) {
-    m.max_items[r] = max_items[r];
-    m.min_len[r] = min_len[r];
-    m.narrow = m.narrow && max_items[r] < 65536;
-    (r ? m.rg.hist1 : m.rg.hist0) = hist_words;
-    (r ? m.rg.state1 : m.rg.state0) = state_entries;
-    hist_words += videos * max_items[r];
-    state_entries += m.pairs() * 4 * max_items[r];
-  }
-  const size_t first_resident_word = hist_words;
-  for (size_t r = 0; r < regions; r++) {
-    (r ? m.rg.res_hist1 : m.rg.res_hist0) = hist_words;
-    (r ? m.rg.res_state1 : m.rg.res_state0) = state_entries;
-    (r ? m.rg.res_total1 : m.rg.res_total0) = res_total[r];
-    hist_words += res_total[r];
-    state_entries += videos * 2 * res_total[r];
-  }
-  m.rg.regions = (uint32_t)regions;
-  m.rg.residents = (uint32_t)num_resident;
-  m.rg.max_items0 = (uint32_t)m.max_items[0];
-  m.rg.max_items1 = (uint32_t)m.max_items[regions - 1];
-  m.rg.min_len0 = m.min_len[0];
-  m.rg.min_len1 = m.min_len[regions - 1];
-  m.slab.capacity_from_env("NEEDLE_HIP_CROSSMATCHER_RUN_SLAB");
-
-  std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
-  Status s = ensure_device();
-  if (!s.ok()) return s;
-  hipStream_t stream = library_stream();
-  const size_t state_bytes = state_entries * (m.narrow ? sizeof(uint16_t) : sizeof(uint32_t));
-  if (!(s = m.hist.reserve(hist_words)).ok() || !(s = m.state.reserve(state_bytes)).ok()) return s;
-  NEEDLE_HIP_TRY(hipMemsetAsync(m.state.ptr, 0, state_bytes, stream));
-  (void)hipGetDevice(&m.device);
-  if (num_resident) {  // the table, and the rows in table order behind the histories: this once
-    if (!(s = m.d_resident.reserve(table.size())).ok()) return s;
-    NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_resident.ptr, table.data(), table.size() * sizeof(CrossResident), hipMemcpyHostToDevice, stream));
-    if (on_device) {
-      KernelTimer timer("crossmatch_gather_resident", stream);
-      if (hist_words > first_resident_word)
-        hipLaunchKernelGGL(crossmatch_gather_resident_kernel, dim3((uint32_t)std::min<size_t>(table.size(), 4096)), dim3(kThreads), 0, stream,
-                           hashes, (const CrossResident *)m.d_resident.ptr, (uint32_t)table.size(), m.rg, m.hist.ptr);
-      NEEDLE_HIP_TRY(hipGetLastError());
-    } else {
-      std::vector<uint32_t> packed(hist_words - first_resident_word);
-      for (size_t i = 0; i < table.size(); i++) {
-        const size_t r = i % regions;
-        if (table[i].len)
-          std::memcpy(packed.data() + ((r ? m.rg.res_hist1 : m.rg.res_hist0) - first_resident_word) + table[i].prefix, hashes + resident[i].offset,
-                      (size_t)table[i].len * sizeof(uint32_t));
-      }
-      if (!packed.empty())
-        NEEDLE_HIP_TRY(hipMemcpyAsync(m.hist.ptr + first_resident_word, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-      NEEDLE_HIP_TRY(hipStreamSynchronize(stream));  // (before `packed` goes)
-    }
-  }
-  NEEDLE_HIP_TRY(hipStreamSynchronize(stream));
-  *out = std::move(cm);
-  return Status::Ok();
-}
-
-// ---- groups: the live pairs are the same-label ones, by the table of cross_pairs.h ----------------------------------------------
-
-namespace {
-
-// The plan of a grouped creation from the C arguments; the resident rows' lengths are all it needs of them.
-CrossPairsPlan grouped_plan(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
-                            const uint32_t *groups, size_t regions, const size_t *max_items) {
-  std::vector<uint32_t> lens;
-  if (regions >= 1 && regions <= kMaxRegions && resident)  // (other regions are refused before a length is read)
-    for (size_t i = 0; i < num_resident * regions; i++) lens.push_back(resident[i].len);
-  CrossPairsShape sh;
-  sh.residents = num_resident;
-  sh.arriving = videos;
-  sh.regions = regions;
-  sh.resident_len = resident ? lens.data() : nullptr;
-  sh.resident_groups = resident_groups;
-  sh.groups = groups;
-  sh.max_items = max_items;
-  return plan_cross_pairs(sh);
-}
-
-}  // namespace
-
-size_t CrossMatcher::StateBytesGrouped(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
-                                       const uint32_t *groups, size_t regions, const size_t *max_items) {
-  const CrossPairsPlan plan = grouped_plan(resident, num_resident, resident_groups, videos, groups, regions, max_items);
+size_t CrossMatcher::StateBytes(const Spec &spec) {
+  const CrossPairsPlan plan = plan_cross_pairs(spec);
   return plan.error ? 0 : plan.state_bytes();
 }
 
-const char *CrossMatcher::GroupedShapeError(const NeedleHipSeq *resident, size_t num_resident, const uint32_t *resident_groups, size_t videos,
-                                            const uint32_t *groups, size_t regions, const size_t *max_items, const uint32_t *min_len) {
-  const CrossPairsPlan plan = grouped_plan(resident, num_resident, resident_groups, videos, groups, regions, max_items);
-  if (plan.error) return plan.error;
-  for (size_t r = 0; r < regions; r++)
-    if (min_len[r] == 0) return "crossmatcher: min_len must be >= 1";
-  return nullptr;
-}
+const char *CrossMatcher::ShapeError(const Spec &spec) { return plan_cross_pairs(spec).error; }
 
-Status CrossMatcher::CreateGrouped(const uint32_t *hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
-                                   const uint32_t *resident_groups, size_t videos, const uint32_t *groups, size_t regions,
-                                   const size_t *max_items, const uint32_t *min_len, uint32_t threshold, std::unique_ptr<CrossMatcher> *out) {
-  return CreateGroupedFrom(hashes, false, num_hashes, resident, num_resident, resident_groups, videos, groups, regions, max_items, min_len,
-                           threshold, out);
-}
-
-Status CrossMatcher::CreateGroupedDevice(const uint32_t *d_hashes, size_t num_hashes, const NeedleHipSeq *resident, size_t num_resident,
-                                         const uint32_t *resident_groups, size_t videos, const uint32_t *groups, size_t regions,
-                                         const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
-                                         std::unique_ptr<CrossMatcher> *out) {
-  return CreateGroupedFrom(d_hashes, true, num_hashes, resident, num_resident, resident_groups, videos, groups, regions, max_items, min_len,
-                           threshold, out);
-}
-
-// CreateFrom with the layout of cross_pairs.h: the live-pair table goes up next to the resident table, and only the residents
-// that are in a live pair have hashes here (the device table says len 0 for the others: nothing of them is copied or gathered).
-Status CrossMatcher::CreateGroupedFrom(const uint32_t *hashes, bool on_device, size_t num_hashes, const NeedleHipSeq *resident,
-                                       size_t num_resident, const uint32_t *resident_groups, size_t videos, const uint32_t *groups,
-                                       size_t regions, const size_t *max_items, const uint32_t *min_len, uint32_t threshold,
-                                       std::unique_ptr<CrossMatcher> *out) {
-  if (!out || !max_items || !min_len || !groups || (num_resident && (!resident || !resident_groups)) || (num_hashes && !hashes))
+// The one way in: the plan of cross_pairs.h, executed.  The resident hashes reach the histories packed on the host and uploaded,
+// or gathered from a device arena; only the residents that are in a live pair have hashes here (the device table says len 0 for
+// the others: nothing of them is copied or gathered), and a labelled object's live-pair table goes up next to the resident table.
+Status CrossMatcher::Create(Spec spec, const uint32_t *hashes, size_t num_hashes, bool on_device, std::unique_ptr<CrossMatcher> *out) {
+  const size_t K = spec.residents, regions = spec.regions;
+  if (!out || !spec.max_items || !spec.min_len || (K && (!spec.resident || (spec.groups && !spec.resident_groups))) || (num_hashes && !hashes))
     return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
-  if (const char *what = GroupedShapeError(resident, num_resident, resident_groups, videos, groups, regions, max_items, min_len))
-    return Status::Make(NeedleError_InvalidArgument, what);
-  for (size_t i = 0; i < num_resident * regions; i++)
-    if ((uint64_t)resident[i].offset + resident[i].len > num_hashes)
-      return Status::Make(NeedleError_InvalidArgument, "crossmatcher: a resident row lies outside the hash arena");
-  CrossPairsPlan plan = grouped_plan(resident, num_resident, resident_groups, videos, groups, regions, max_items);
+  spec.arena_hashes = num_hashes;
+  CrossPairsPlan plan = plan_cross_pairs(spec);
+  if (plan.error) return Status::Make(NeedleError_InvalidArgument, plan.error);
   std::unique_ptr<CrossMatcher> cm(new CrossMatcher());
   Impl &m = *cm->impl_;
-  m.grouped = true;
-  m.videos = videos;
+  m.videos = spec.arriving;
   m.regions = regions;
-  m.residents = num_resident;
-  m.n = videos * regions;
-  m.threshold = threshold;
+  m.residents = K;
+  m.n = spec.arriving * regions;
+  m.threshold = spec.threshold;
   m.lanes = std::vector<LaneState>(m.n);
   m.held.resize(m.n);
-  m.res_rows.assign(resident, resident + num_resident * regions);
-  m.narrow = plan.narrow;
-  m.res_longest = plan.longest_resident;
-  m.grouped_state_bytes = plan.state_bytes();
-  m.labels = plan.labels;
-  m.group_tables.reset(new GroupTables(m.labels.data(), m.labels.size()));
-  m.live.swap(plan.live);
-  std::vector<CrossResident> table(num_resident * regions);
+  m.res_rows.assign(spec.resident, spec.resident + K * regions);
+  std::vector<CrossResident> table(K * regions);
   for (size_t i = 0; i < table.size(); i++)
-    table[i] = CrossResident{plan.resident_prefix[i], plan.resident_live[i / regions] ? resident[i].len : 0u, resident[i].offset};
+    table[i] = CrossResident{plan.resident_prefix[i], plan.resident_live[i / regions] ? spec.resident[i].len : 0u, spec.resident[i].offset};
   for (size_t r = 0; r < regions; r++) {
-    m.max_items[r] = max_items[r];
-    m.min_len[r] = min_len[r];
+    m.max_items[r] = spec.max_items[r];
+    m.min_len[r] = spec.min_len[r];
   }
   m.rg.regions = (uint32_t)regions;
-  m.rg.residents = (uint32_t)num_resident;
+  m.rg.residents = (uint32_t)K;
   m.rg.max_items0 = (uint32_t)m.max_items[0];
   m.rg.max_items1 = (uint32_t)m.max_items[regions - 1];
   m.rg.min_len0 = m.min_len[0];
   m.rg.min_len1 = m.min_len[regions - 1];
   m.rg.hist0 = plan.hist[0];
   m.rg.hist1 = plan.hist[regions - 1];
+  m.rg.state0 = plan.state[0];
+  m.rg.state1 = plan.state[regions - 1];
   m.rg.res_hist0 = plan.res_hist[0];
   m.rg.res_hist1 = plan.res_hist[regions - 1];
-  // (state0/1, res_state0/1 and res_total0/1 are the closed form's: a live problem's state is in its table entry)
+  m.rg.res_state0 = plan.res_state[0];  // (the closed form's, as res_total: a listed problem's state is in its table entry)
+  m.rg.res_state1 = plan.res_state[regions - 1];
+  m.rg.res_total0 = plan.resident_hashes[0];
+  m.rg.res_total1 = plan.resident_hashes[regions - 1];
+  if (!plan.labelled) std::vector<CrossLive>().swap(plan.live);  // the closed form finds them by arithmetic
+  m.plan = std::move(plan);
+  const CrossPairsPlan &pl = m.plan;
   m.slab.capacity_from_env("NEEDLE_HIP_CROSSMATCHER_RUN_SLAB");
 
   std::lock_guard<std::recursive_mutex> gpu_lock(gpu_mutex());
   Status s = ensure_device();
   if (!s.ok()) return s;
   hipStream_t stream = library_stream();
-  const size_t state_bytes = (size_t)plan.state_entries * plan.entry_bytes(), first_resident_word = (size_t)plan.res_hist[0];
-  if (!(s = m.hist.reserve(std::max<size_t>(plan.hist_words, 1))).ok() || !(s = m.state.reserve(std::max<size_t>(state_bytes, 1))).ok() ||
-      !(s = m.d_live.reserve(std::max<size_t>(m.live.size(), 1))).ok())
+  const size_t state_bytes = (size_t)pl.state_entries * pl.entry_bytes(), first_resident_word = (size_t)pl.res_hist[0];
+  if (!(s = m.hist.reserve(std::max<size_t>(pl.hist_words, 1))).ok() || !(s = m.state.reserve(std::max<size_t>(state_bytes, 1))).ok() ||
+      !(s = m.d_live.reserve(pl.labelled ? std::max<size_t>(pl.live.size(), 1) : 0)).ok())
     return s;
   if (state_bytes) NEEDLE_HIP_TRY(hipMemsetAsync(m.state.ptr, 0, state_bytes, stream));
   (void)hipGetDevice(&m.device);
-  if (!m.live.empty())
-    NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_live.ptr, m.live.data(), m.live.size() * sizeof(CrossLive), hipMemcpyHostToDevice, stream));
-  if (num_resident) {
+  if (!pl.live.empty())
+    NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_live.ptr, pl.live.data(), pl.live.size() * sizeof(CrossLive), hipMemcpyHostToDevice, stream));
+  if (K) {  // the table, and the rows in table order behind the histories: this once
     if (!(s = m.d_resident.reserve(table.size())).ok()) return s;
     NEEDLE_HIP_TRY(hipMemcpyAsync(m.d_resident.ptr, table.data(), table.size() * sizeof(CrossResident), hipMemcpyHostToDevice, stream));
     if (on_device) {
       KernelTimer timer("crossmatch_gather_resident", stream);
-      if (plan.hist_words > first_resident_word)
+      if (pl.hist_words > first_resident_word)
         hipLaunchKernelGGL(crossmatch_gather_resident_kernel, dim3((uint32_t)std::min<size_t>(table.size(), 4096)), dim3(kThreads), 0, stream,
                            hashes, (const CrossResident *)m.d_resident.ptr, (uint32_t)table.size(), m.rg, m.hist.ptr);
       NEEDLE_HIP_TRY(hipGetLastError());
     } else {
-      std::vector<uint32_t> packed(plan.hist_words - first_resident_word);
+      std::vector<uint32_t> packed(pl.hist_words - first_resident_word);
       for (size_t i = 0; i < table.size(); i++)
         if (table[i].len)
-          std::memcpy(packed.data() + (plan.res_hist[i % regions] - first_resident_word) + table[i].prefix, hashes + resident[i].offset,
+          std::memcpy(packed.data() + (pl.res_hist[i % regions] - first_resident_word) + table[i].prefix, hashes + spec.resident[i].offset,
                       (size_t)table[i].len * sizeof(uint32_t));
       if (!packed.empty())
         NEEDLE_HIP_TRY(hipMemcpyAsync(m.hist.ptr + first_resident_word, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
@@ -765,8 +497,8 @@ Status CrossMatcher::CreateGroupedFrom(const uint32_t *hashes, bool on_device, s
   return Status::Ok();
 }
 
-bool CrossMatcher::grouped() const { return impl_->grouped; }
-const std::vector<uint32_t> &CrossMatcher::labels() const { return impl_->labels; }
+bool CrossMatcher::grouped() const { return impl_->plan.labelled; }
+const std::vector<uint32_t> &CrossMatcher::labels() const { return impl_->plan.labels; }
 
 Status CrossMatcher::Feed(const uint32_t *const *items, const size_t *num_items) {
   Impl &m = *impl_;
@@ -854,7 +586,7 @@ Status CrossMatcher::Runs(size_t first, size_t count, NeedleHipRun *runs) {
 void CrossMatcher::set_origin(const Origin &origin) { impl_->origin = origin; }
 CrossMatcher::Origin CrossMatcher::origin() const { return impl_->origin; }
 int CrossMatcher::device() const { return impl_->device; }
-uint32_t CrossMatcher::min_len(size_t region) const { return impl_->min_len[region < kMaxRegions ? region : 0]; }
+uint32_t CrossMatcher::min_len(size_t region) const { return impl_->min_len[region < kCrossMaxRegions ? region : 0]; }
 Status CrossMatcher::poisoned() const { return impl_->poison; }
 const std::vector<NeedleHipRun> &CrossMatcher::run_list() const { return impl_->runs; }
 const uint32_t *CrossMatcher::history(size_t lane) const {
@@ -868,12 +600,8 @@ void CrossMatcher::Stats(uint64_t stats[4]) const {
   stats[0] = m.feeds;
   stats[1] = m.launches;
   stats[2] = m.cells;
-  if (m.grouped) {  // frontiers and hashes by the live pairs' rule, the two tables, the run slab
-    stats[3] = m.grouped_state_bytes + m.live.size() * sizeof(CrossLive) + m.res_rows.size() * sizeof(CrossResident) + m.slab.bytes();
-    return;
-  }
-  stats[3] = StateBytesResident(m.res_rows.data(), m.residents, m.videos, m.regions, m.max_items) + m.res_rows.size() * sizeof(CrossResident) +
-             m.slab.bytes();
+  // frontiers and hashes by the plan's rule, the two tables as uploaded, the run slab
+  stats[3] = m.plan.state_bytes() + m.plan.live.size() * sizeof(CrossLive) + m.res_rows.size() * sizeof(CrossResident) + m.slab.bytes();
 }
 
 }  // namespace needle

@@ -237,20 +237,7 @@ Status Index::matcher(size_t videos, std::unique_ptr<Matcher> *out) {
 Status Index::crossmatcher(size_t videos, const size_t *max_items, const uint32_t *min_len, std::unique_ptr<CrossMatcher> *out) {
   if (grouped_) return refuse_grouped("crossmatcher");
   if (!out || !max_items || !min_len) return Status::Make(NeedleError_NullArgument, "crossmatcher: null argument");
-  // The argument checks first, with or without a device (no state is asked for: StateBytesResident is host arithmetic) ...
-  if (const char *what = CrossMatcher::ShapeError(rows_.seqs.data(), videos_.size(), videos, regions_, max_items, min_len))
-    return Status::Make(NeedleError_InvalidArgument, what);
-  // ... then the device, before anything is allocated on another one
-  const uint32_t *d_hashes = nullptr;
-  Status s = index_store_arena(store_, &d_hashes);
-  if (!s.ok()) return s;
-  std::unique_ptr<CrossMatcher> cm;
-  s = CrossMatcher::CreateResidentDevice(d_hashes, d_hashes ? rows_.hashes : 0, rows_.seqs.data(), videos_.size(), videos, regions_, max_items,
-                                         min_len, cmp_.hash_match_threshold(), &cm);
-  if (!s.ok()) return s;
-  cm->set_origin(CrossMatcher::Origin{id_, generation_});
-  *out = std::move(cm);
-  return Status::Ok();
+  return make_crossmatcher(videos, nullptr, max_items, min_len, out);
 }
 
 // The grouped index's cross-matcher: the residents are the index's videos in index order under the index's labels, `groups` the
@@ -261,19 +248,30 @@ Status Index::crossmatcher_grouped(size_t videos, const uint32_t *groups, const 
   if (!grouped_)
     return Status::Make(NeedleError_InvalidArgument,
                         "index crossmatcher_grouped: not a grouped index (needle_hip_index_crossmatcher_new takes a plain one)");
-  if (const char *what =
-          CrossMatcher::GroupedShapeError(rows_.seqs.data(), videos_.size(), labels_.data(), videos, groups, regions_, max_items, min_len))
-    return Status::Make(NeedleError_InvalidArgument, what);
+  return make_crossmatcher(videos, groups, max_items, min_len, out);
+}
+
+Status Index::make_crossmatcher(size_t videos, const uint32_t *groups, const size_t *max_items, const uint32_t *min_len,
+                                std::unique_ptr<CrossMatcher> *out) {
+  CrossMatcher::Spec spec;
+  spec.residents = videos_.size();
+  spec.resident = rows_.seqs.data();
+  spec.resident_groups = labels_.data();
+  spec.arriving = videos;
+  spec.groups = groups;
+  spec.regions = regions_;
+  spec.max_items = max_items;
+  spec.min_len = min_len;
+  spec.threshold = cmp_.hash_match_threshold();
+  // The argument checks first, with or without a device (no state is asked for: the plan is host arithmetic) ...
+  if (const char *what = CrossMatcher::ShapeError(spec)) return Status::Make(NeedleError_InvalidArgument, what);
+  // ... then the device, before anything is allocated on another one
   const uint32_t *d_hashes = nullptr;
   Status s = index_store_arena(store_, &d_hashes);
   if (!s.ok()) return s;
-  std::unique_ptr<CrossMatcher> cm;
-  s = CrossMatcher::CreateGroupedDevice(d_hashes, d_hashes ? rows_.hashes : 0, rows_.seqs.data(), videos_.size(), labels_.data(), videos, groups,
-                                        regions_, max_items, min_len, cmp_.hash_match_threshold(), &cm);
-  if (!s.ok()) return s;
-  cm->set_origin(CrossMatcher::Origin{id_, generation_});
-  *out = std::move(cm);
-  return Status::Ok();
+  s = CrossMatcher::Create(spec, d_hashes, d_hashes ? rows_.hashes : 0, true, out);  // (which leaves *out alone where it fails)
+  if (s.ok()) (*out)->set_origin(CrossMatcher::Origin{id_, generation_});
+  return s;
 }
 
 // add, add_matched and add_streamed: with a cross-matcher (made from the index) its runs stand in for the scan of the new pairs;

@@ -52,7 +52,7 @@ class Index {
   // add() with the runs of a complete matcher made by crossmatcher() since the last change in place of the scan: the same
   // index afterwards, no pair searched again.  Every check comes before the commit; on failure the index is as it was.
   Status add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &videos);
-  // The grouped index's forms of the two: a grouped cross-matcher (crossmatch.h CreateGroupedDevice) whose residents are the
+  // The grouped index's forms of the two: a grouped cross-matcher (crossmatch.h: a Spec with labels) whose residents are the
   // index's videos under the index's labels and whose `videos` arriving ones carry `groups`; add_matched_grouped appends them
   // under those labels and leaves what add_grouped would.  A plain index: InvalidArgument.
   Status crossmatcher_grouped(size_t videos, const uint32_t *groups, const size_t *max_items, const uint32_t *min_len,
@@ -98,6 +98,9 @@ class Index {
   uint64_t generation_ = 1;  // ... this, which every successful change advances
 
   Status append(const std::vector<const FrameHashesData *> &videos, CrossMatcher *matcher, Matcher *streamed, const uint32_t *labels = nullptr);
+  // crossmatcher (groups null) and crossmatcher_grouped after their own refusals
+  Status make_crossmatcher(size_t videos, const uint32_t *groups, const size_t *max_items, const uint32_t *min_len,
+                           std::unique_ptr<CrossMatcher> *out);
   Status refuse_grouped(const char *route) const;  // the streamed routes on a grouped index
   void changed(uint64_t searched, uint64_t scanned);  // the counters, at a commit
 

@@ -1,9 +1,15 @@
-// The live-pair table of a grouped cross-matcher (needle_amd/csrc/cross_pairs.h) against brute force, on the CPU: every
-// assignment of <= 3 labels to V <= 7 videos, every K <= V - 1 residents, regions 1 and 2.  Checked: the live pairs and their
-// order; the two rows; the ids against an independent restatement of the grouped numbering AND against grouped_pair of
-// pair_ids.h; the state regions pairwise disjoint, inside the stated total and filling it; the hashes' places likewise; a
-// resident without a live pair owning nothing; the byte count; with one label the closed forms of the ungrouped object; every
-// refusal as a string.  Prints "cross pairs ok" and the number of cases.
+// The host plan of every cross-matcher (needle_amd/csrc/cross_pairs.h) on the CPU.
+// Against brute force: every assignment of <= 3 labels to V <= 7 videos, every K <= V - 1 residents, regions 1 and 2.  Checked:
+// the live pairs and their order; the two rows; the ids against an independent restatement of the grouped numbering AND against
+// grouped_pair of pair_ids.h; the state regions pairwise disjoint, inside the stated total and filling it; the hashes' places
+// likewise; a resident without a live pair owning nothing; the byte count; with one label the closed forms of the unlabelled
+// object's walk; the cells of a round (CrossPairsPlan::cells) against the sum over the live problems at two sets of lane fill
+// levels; the host's decode of NeedleHipRun.problem (CrossPairsPlan::problem_at) for every live problem; every refusal as a
+// string.
+// Against the object without labels as it was before one plan served both (namespace before: its argument checks, its layout
+// loop and its byte count, verbatim): the plan of a shape without labels agrees field by field for every K <= 4, N <= 5,
+// regions 1 and 2 and row lengths that include 0 and 1, and refusal by refusal at the boundary shapes.
+// Prints the number of cases and "cross pairs ok".
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +55,37 @@ static uint64_t brute_id(const std::vector<uint32_t> &labels, size_t a, size_t b
   return ~0ull;
 }
 
+// rows of these lengths, one after the other in an arena
+static std::vector<NeedleHipSeq> rows_of(const std::vector<uint32_t> &len) {
+  std::vector<NeedleHipSeq> rows(len.size());
+  uint32_t at = 0;
+  for (size_t i = 0; i < len.size(); i++) {
+    rows[i] = NeedleHipSeq{at, len[i]};
+    at += len[i];  // (may wrap where a test asks for rows no arena holds: nothing reads the offsets then)
+  }
+  return rows;
+}
+
+// The cells of a round and the decode of a problem, for any plan: lane i holds fill[i] items.
+static void check_cells_and_decode(const CrossPairsPlan &p, const std::vector<CrossLive> &live, const std::vector<uint32_t> &len, size_t K,
+                                   size_t N, size_t R) {
+  for (size_t level = 0; level < 2; level++) {
+    std::vector<uint64_t> x(N * R);  // max(items, 1) - 1; the first level leaves lanes empty and at one item
+    for (size_t i = 0; i < x.size(); i++) x[i] = level == 0 ? (i % 3 == 0 ? 0 : (i * 7 + 2) % 5) : (i * 5 + 3) % 11 + (i % 4 == 1 ? 0 : 1);
+    auto x_of_row = [&](size_t row) -> uint64_t { return row < K * R ? std::max<uint64_t>(len[row], 1) - 1 : x[row - K * R]; };
+    uint64_t want = 0;
+    for (const CrossLive &e : live) want += x_of_row(e.row_a) * x_of_row(e.row_b);
+    CHECK(p.cells([&](size_t i) { return x[i]; }) == want);
+  }
+  for (const CrossLive &e : live) {
+    uint32_t a = 0, b = 0, r = 0;
+    CHECK(p.problem_at(e.problem, &a, &b, &r));
+    CHECK(a * R + r == e.row_a && b * R + r == e.row_b);
+  }
+  uint32_t a, b, r;
+  CHECK(!p.problem_at((uint32_t)(p.tables->pairs() * R), &a, &b, &r));  // one past the last id
+}
+
 struct Interval {
   uint64_t lo, hi;
 };
@@ -70,11 +107,12 @@ static size_t one_case(const std::vector<uint32_t> &labels, size_t K, size_t R) 
   std::vector<uint32_t> len(K * R);
   for (size_t k = 0; k < K; k++)
     for (size_t r = 0; r < R; r++) len[k * R + r] = (uint32_t)((k * 3 + r * 5 + labels[k]) % 7);  // 0 .. 6, above and below max_items
+  const std::vector<NeedleHipSeq> rows = rows_of(len);
   CrossPairsShape sh;
   sh.residents = K;
   sh.arriving = N;
   sh.regions = R;
-  sh.resident_len = len.data();
+  sh.resident = rows.data();
   sh.resident_groups = labels.data();
   sh.groups = labels.data() + K;
   sh.max_items = max_items;
@@ -138,6 +176,8 @@ static size_t one_case(const std::vector<uint32_t> &labels, size_t K, size_t R) 
   check_disjoint(hashes, 0, p.hist_words);
   CHECK(p.narrow == narrow);
   CHECK(p.state_bytes() == want_entries * 2 + want_words * 4);
+  CHECK(p.labelled && p.problems() == p.live.size());
+  check_cells_and_decode(p, p.live, len, K, N, R);
 
   // one label: the ungrouped object's closed forms (crossmatch.hip ClosedFormPairs)
   if (std::count(labels.begin(), labels.end(), labels[0]) == (long)V) {
@@ -182,7 +222,9 @@ static const char *error_of(size_t K, size_t N, size_t R, const uint32_t *len, c
   sh.residents = K;
   sh.arriving = N;
   sh.regions = R;
-  sh.resident_len = len;
+  std::vector<NeedleHipSeq> rows;
+  for (size_t i = 0; len && i < K * R; i++) rows.push_back(NeedleHipSeq{0, len[i]});
+  sh.resident = len ? rows.data() : nullptr;
   sh.resident_groups = res_groups;
   sh.groups = groups;
   sh.max_items = max_items;
@@ -203,7 +245,7 @@ static void refusals() {
   for (size_t i = 0; i < distinct.size(); i++) distinct[i] = (uint32_t)i;
   CHECK(says(error_of(0, 2, 0, nullptr, nullptr, zeros.data(), mi), "regions must be 1 or 2"));
   CHECK(says(error_of(0, 2, 3, nullptr, nullptr, zeros.data(), mi), "regions must be 1 or 2"));
-  CHECK(says(error_of(0, 2, 1, nullptr, nullptr, nullptr, mi), "null argument"));
+  CHECK(says(error_of(2, 2, 1, lens.data(), nullptr, nullptr, nullptr), "null argument"));
   CHECK(says(error_of(0, 2, 1, nullptr, nullptr, zeros.data(), nullptr), "null argument"));
   CHECK(says(error_of(2, 2, 1, nullptr, zeros.data(), zeros.data(), mi), "null argument"));
   CHECK(says(error_of(2, 2, 1, lens.data(), nullptr, zeros.data(), mi), "null argument"));
@@ -229,13 +271,218 @@ static void refusals() {
   sh.residents = 300;
   sh.arriving = 256;
   sh.regions = 1;
-  sh.resident_len = lens.data();
+  const std::vector<NeedleHipSeq> rows = rows_of(std::vector<uint32_t>(300, 2));
+  sh.resident = rows.data();
   sh.resident_groups = res_groups.data();
   sh.groups = groups.data();
   sh.max_items = mi;
   const CrossPairsPlan p = plan_cross_pairs(sh);
   CHECK(p.error == nullptr && p.resident_pairs == 256 && p.arriving_pairs == 64 * 6 && p.live.size() == 640);
   CHECK(p.resident_hashes[0] == 64 * 2);  // only the 64 residents whose show arrives own hashes
+}
+
+// ---- the object without labels as it was planned before cross_pairs.h planned it: crossmatch.hip's own expressions ---------------
+namespace before {
+
+constexpr size_t kMaxLanes = 256;
+constexpr size_t kMaxRegions = 2;
+constexpr size_t kMaxProblems = 65535;
+constexpr uint64_t kMaxRowItems = 0x7FFFFFF0ull;
+
+const char *shape_error(const NeedleHipSeq *resident, size_t num_resident, size_t num_hashes, bool check_arena, size_t videos, size_t regions,
+                        const size_t *max_items) {
+  if (regions < 1 || regions > kMaxRegions) return "crossmatcher: regions must be 1 or 2";
+  if (videos < (num_resident ? 1u : 2u) || videos > kMaxLanes)
+    return num_resident ? "crossmatcher: arriving videos must be 1 to 256" : "crossmatcher: lanes (videos) must be 2 to 256";
+  for (size_t r = 0; r < regions; r++)
+    if (max_items[r] < 2 || max_items[r] > kMaxRowItems) return "crossmatcher: max_items must be 2 to 2^31 - 16";
+  // (videos <= 256 and the first test bound num_resident before anything is multiplied)
+  if (num_resident > kMaxProblems || (num_resident * videos + videos * (videos - 1) / 2) * regions > kMaxProblems)
+    return "crossmatcher: more than 65 535 live problems ((K N + N (N - 1) / 2) x regions)";
+  const uint64_t all = num_resident + videos;
+  if (all * (all - 1) / 2 * regions >= (1ull << 32)) return "crossmatcher: the problem index over all videos does not fit 32 bits";
+  for (size_t i = 0; i < num_resident * regions; i++) {
+    if (resident[i].len > kMaxRowItems) return "crossmatcher: a resident row holds more than 2^31 - 16 hashes";
+    if (check_arena && (uint64_t)resident[i].offset + resident[i].len > num_hashes) return "crossmatcher: a resident row lies outside the hash arena";
+  }
+  return nullptr;
+}
+
+// creation's checks in creation's order: the shape with the arena, then min_len
+const char *creation_error(const NeedleHipSeq *resident, size_t num_resident, size_t num_hashes, size_t videos, size_t regions,
+                           const size_t *max_items, const uint32_t *min_len) {
+  if (const char *what = shape_error(resident, num_resident, num_hashes, true, videos, regions, max_items)) return what;
+  for (size_t r = 0; r < regions; r++)
+    if (min_len[r] == 0) return "crossmatcher: min_len must be >= 1";
+  return nullptr;
+}
+
+size_t StateBytesResident(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items) {
+  if (!max_items || (num_resident && !resident) || shape_error(resident, num_resident, 0, false, videos, regions, max_items)) return 0;
+  bool narrow = true;
+  for (size_t r = 0; r < regions; r++) narrow = narrow && max_items[r] < 65536;
+  for (size_t i = 0; i < num_resident * regions; i++) narrow = narrow && resident[i].len < 65536;
+  const size_t pairs = videos * (videos - 1) / 2, width = narrow ? sizeof(uint16_t) : sizeof(uint32_t);
+  size_t bytes = 0;
+  for (size_t r = 0; r < regions; r++) {
+    size_t hashes = 0;  // S_r
+    for (size_t k = 0; k < num_resident; k++) hashes += resident[k * regions + r].len;
+    bytes += pairs * 2 * 2 * max_items[r] * width + videos * max_items[r] * sizeof(uint32_t)  // the arriving pairs' L frontiers, the histories
+             + videos * 2 * hashes * width + hashes * sizeof(uint32_t);                        // the resident col frontiers, the resident hashes
+  }
+  return bytes;
+}
+
+struct CrossRegions {  // the fields of the kernels' argument that the layout fills
+  uint64_t hist0, hist1, state0, state1, res_hist0, res_hist1, res_state0, res_state1, res_total0, res_total1;
+};
+struct CrossResident {
+  uint64_t prefix;
+  uint32_t len, src;
+};
+struct Layout {
+  size_t videos = 0;
+  bool narrow = true;
+  CrossRegions rg{};
+  uint64_t res_cell_rows[2] = {0, 0}, res_longest = 0;
+  std::vector<CrossResident> table;
+  size_t hist_words = 0, state_entries = 0, first_resident_word = 0;
+  size_t pairs() const { return videos * (videos - 1) / 2; }
+};
+
+// the layout loop of creation
+Layout layout(const NeedleHipSeq *resident, size_t num_resident, size_t videos, size_t regions, const size_t *max_items) {
+  Layout m;
+  m.videos = videos;
+  std::vector<CrossResident> table(num_resident * regions);
+  size_t res_total[2] = {0, 0};
+  for (size_t k = 0; k < num_resident; k++)
+    for (size_t r = 0; r < regions; r++) {
+      const NeedleHipSeq &row = resident[k * regions + r];
+      table[k * regions + r] = CrossResident{res_total[r], row.len, row.offset};
+      res_total[r] += row.len;
+      m.res_cell_rows[r] += std::max<uint64_t>(row.len, 1) - 1;
+      m.res_longest = std::max<uint64_t>(m.res_longest, row.len);
+      m.narrow = m.narrow && row.len < 65536;
+    }
+  size_t hist_words = 0, state_entries = 0;
+  for (size_t r = 0; r < regions; r++) {
+    m.narrow = m.narrow && max_items[r] < 65536;
+    (r ? m.rg.hist1 : m.rg.hist0) = hist_words;
+    (r ? m.rg.state1 : m.rg.state0) = state_entries;
+    hist_words += videos * max_items[r];
+    state_entries += m.pairs() * 4 * max_items[r];
+  }
+  const size_t first_resident_word = hist_words;
+  for (size_t r = 0; r < regions; r++) {
+    (r ? m.rg.res_hist1 : m.rg.res_hist0) = hist_words;
+    (r ? m.rg.res_state1 : m.rg.res_state0) = state_entries;
+    (r ? m.rg.res_total1 : m.rg.res_total0) = res_total[r];
+    hist_words += res_total[r];
+    state_entries += videos * 2 * res_total[r];
+  }
+  m.table.swap(table);
+  m.hist_words = hist_words;
+  m.state_entries = state_entries;
+  m.first_resident_word = first_resident_word;
+  return m;
+}
+
+}  // namespace before
+
+static bool same_words(const char *x, const char *y) { return (!x && !y) || (x && y && std::strcmp(x, y) == 0); }
+
+// One shape without labels: the plan's refusal is the old object's, word for word; where it is accepted, its layout is.
+// Returns whether it was accepted.
+static bool unlabelled_case(const std::vector<NeedleHipSeq> &rows, size_t K, size_t N, size_t R, const size_t *max_items, const uint32_t *min_len,
+                            size_t arena) {
+  CrossPairsShape sh;
+  sh.residents = K;
+  sh.arriving = N;
+  sh.regions = R;
+  sh.resident = rows.data();
+  sh.max_items = max_items;
+  sh.min_len = min_len;
+  sh.arena_hashes = arena;
+  const CrossPairsPlan p = plan_cross_pairs(sh);
+  CHECK(same_words(p.error, before::creation_error(rows.data(), K, arena, N, R, max_items, min_len)));
+  sh.min_len = nullptr;  // the question about sizes: no min_len, no arena
+  sh.arena_hashes = ~0ull;
+  const CrossPairsPlan sizes = plan_cross_pairs(sh);
+  CHECK(same_words(sizes.error, before::shape_error(rows.data(), K, 0, false, N, R, max_items)));
+  CHECK((sizes.error ? 0 : sizes.state_bytes()) == before::StateBytesResident(rows.data(), K, N, R, max_items));
+  if (p.error) {
+    CHECK(p.live.empty() && !p.state_entries && !p.hist_words && !p.tables);
+    return false;
+  }
+  const before::Layout m = before::layout(rows.data(), K, N, R, max_items);
+  CHECK(!p.labelled && p.labels.empty() && p.regions == R);
+  CHECK(p.hist[0] == m.rg.hist0 && p.state[0] == m.rg.state0 && p.res_hist[0] == m.rg.res_hist0 && p.res_state[0] == m.rg.res_state0 &&
+        p.resident_hashes[0] == m.rg.res_total0);
+  if (R == 2)
+    CHECK(p.hist[1] == m.rg.hist1 && p.state[1] == m.rg.state1 && p.res_hist[1] == m.rg.res_hist1 && p.res_state[1] == m.rg.res_state1 &&
+          p.resident_hashes[1] == m.rg.res_total1);
+  CHECK(p.hist_words == m.hist_words && p.state_entries == m.state_entries && p.res_hist[0] == m.first_resident_word);
+  CHECK(p.narrow == m.narrow && p.longest_resident == m.res_longest);
+  CHECK(p.state_bytes() == before::StateBytesResident(rows.data(), K, N, R, max_items));
+  CHECK(p.problems() == (K * N + m.pairs()) * R);  // gridDim.y of the walk
+  for (size_t i = 0; i < K * R; i++)  // the resident table as it is uploaded: every resident is live
+    CHECK(p.resident_live[i / R] && p.resident_prefix[i] == m.table[i].prefix);
+  CHECK(p.resident_cell_rows.size() == R && p.lane_group == std::vector<uint32_t>(N, 0u));
+  for (size_t r = 0; r < R; r++) CHECK(p.resident_cell_rows[r] == m.res_cell_rows[r]);
+  // the problems the closed form of the walk numbers, which the plan lists without being asked to
+  CHECK(p.live.size() == p.problems());
+  std::vector<uint32_t> len(K * R);
+  for (size_t i = 0; i < K * R; i++) len[i] = rows[i].len;
+  if (p.live.size() <= 4096) check_cells_and_decode(p, p.live, len, K, N, R);
+  return true;
+}
+
+// every K <= 4, N <= 5, regions 1 and 2, rows of 0, 1 and more hashes, a capacity and a row on either side of the entry width,
+// min_len with a zero, an arena that is too small
+static size_t unlabelled_layouts() {
+  size_t accepted = 0;
+  static const uint32_t kLens[6] = {0u, 1u, 6u, 3u, 1u, 0u};
+  for (size_t K = 0; K <= 4; K++)
+    for (size_t N = 0; N <= 5; N++)
+      for (size_t R = 1; R <= 2; R++)
+        for (size_t variant = 0; variant < 12; variant++) {
+          g_case = "unlabelled K=" + std::to_string(K) + " N=" + std::to_string(N) + " R=" + std::to_string(R) + " variant=" + std::to_string(variant);
+          std::vector<uint32_t> len(K * R);
+          for (size_t i = 0; i < len.size(); i++) len[i] = variant == 6 ? 0u : variant == 7 ? 1u : kLens[(i + variant) % 6];
+          if (variant == 8 && !len.empty()) len.back() = 65536;   // one wide row
+          if (variant == 9 && !len.empty()) len.front() = 65535;  // ... and the longest narrow one
+          const size_t max_items[2] = {variant == 10 ? (size_t)65536 : 5, variant == 11 ? (size_t)65536 : 3};
+          const std::vector<NeedleHipSeq> rows = rows_of(len);
+          size_t arena = 0;
+          for (uint32_t l : len) arena += l;
+          static const uint32_t kMinLen[3][2] = {{1, 1}, {0, 1}, {3, 0}};
+          for (size_t m = 0; m < 3; m++) accepted += unlabelled_case(rows, K, N, R, max_items, kMinLen[m], arena);
+          if (arena) accepted += unlabelled_case(rows, K, N, R, max_items, kMinLen[0], arena - 1);
+        }
+  return accepted;
+}
+
+// the refusals, string for string, where a bound is met exactly and passed by one
+static size_t unlabelled_boundaries() {
+  size_t shapes = 0;
+  static const size_t kK[8] = {0, 1, 255, 256, 32767, 32768, 65535, 65536}, kN[5] = {0, 1, 2, 256, 257};
+  static const size_t kItems[6] = {1, 2, 65535, 65536, 0x7FFFFFF0, 0x7FFFFFF1};
+  const uint32_t min_len[2] = {1, 1};
+  std::vector<NeedleHipSeq> rows(2 * 65536, NeedleHipSeq{0, 2}), long_row = rows;
+  for (size_t i = 0; i < long_row.size(); i += 255) long_row[i].len = 0x7FFFFFF1u;  // (row 0 of every shape among them)
+  for (size_t K : kK)
+    for (size_t N : kN)
+      for (size_t R = 0; R <= 3; R++)
+        for (size_t items : kItems)
+          for (size_t which = 0; which < 2; which++) {
+            g_case = "boundary K=" + std::to_string(K) + " N=" + std::to_string(N) + " R=" + std::to_string(R) + " max_items=" + std::to_string(items) +
+                     (which ? " with a long row" : "");
+            const size_t max_items[3] = {items, R == 2 && which ? 2 : items, items};
+            (void)unlabelled_case(which ? long_row : rows, K, N, R, max_items, min_len, 2);
+            shapes++;
+          }
+  return shapes;
 }
 
 int main() {
@@ -256,6 +503,7 @@ int main() {
     }
   }
   refusals();
-  std::printf("%zu cases\ncross pairs ok\n", cases);
+  const size_t layouts = unlabelled_layouts(), boundaries = unlabelled_boundaries();
+  std::printf("%zu cases\n%zu unlabelled layouts\n%zu boundary shapes\ncross pairs ok\n", cases, layouts, boundaries);
   return 0;
 }

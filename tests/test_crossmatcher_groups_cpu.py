@@ -32,6 +32,10 @@ def test_the_live_pair_table_against_brute_force(tmp_path, flags):
     assert out.returncode == 0 and out.stdout.strip().endswith("cross pairs ok"), out.stdout[-2000:] + out.stderr[-4000:]
     cases = sum(3 ** v * v * 2 for v in range(1, 8))                             # V videos: 3^V labellings x K = 0 .. V - 1 x 2
     assert out.stdout.splitlines()[0] == f"{cases} cases"
+    # ... and the plan of a shape without labels against the object as it was before one plan served both: accepted layouts
+    # field by field (K <= 4, N <= 5), and 8 K x 5 N x 4 regions x 6 max_items x 2 rows boundary shapes refusal by refusal
+    layouts, boundaries = out.stdout.splitlines()[1:3]
+    assert re.fullmatch(r"[1-9]\d* unlabelled layouts", layouts) and boundaries == f"{8 * 5 * 4 * 6 * 2} boundary shapes"
 
 
 def test_symbols_in_every_layer():

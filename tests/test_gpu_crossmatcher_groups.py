@@ -332,6 +332,61 @@ def test_bounds_are_on_the_live_problems():
     assert e.value.code == INVALID and "65 535 live problems" in str(e.value)
 
 
+# ---- 7. one label is the object without labels ---------------------------------------------------------------------------------------------
+def test_one_label_is_the_object_without_labels():
+    """One plan (cross_pairs.h) lays out both: the same data through an object made without labels (the walk finds its problems
+    by arithmetic) and one made with a single label (the walk reads the uploaded table).  Two residents, one with a row of one
+    hash; three arriving videos; two regions with capacities and min_len of their own; ragged feeds; one lane finished early; a
+    run into resident 0's last row that arrives long before its lane finishes.  After every step the two hold the same runs
+    under the same problems, and the same feeds, launches and cells; the state differs by the table: 24 bytes a live problem."""
+    rng = np.random.default_rng(41)
+    k, videos, max_items, min_len, t = 2, 3, [48, 20], [3, 2], 10
+    lens = [30, 14, 1, 9] + [48, 20, 40, 17, 33, 20]                              # rows video * 2 + region, residents first
+    rows = [rand_hashes(rng, n) for n in lens]
+    copy = lambda a, ra, b, cb, n: rows[b].__setitem__(slice(cb, cb + n), rows[a][ra: ra + n] ^ _masks([2] * n, rng, 0))
+    copy(0, 30 - 10, 4, 5, 10)                                                   # region 0: into resident 0's LAST row, lane 0's items 5 .. 14
+    copy(0, 3, 6, 20, 12)                                                        # ... resident 0 -> arriving 1
+    copy(4, 30, 8, 10, 15)                                                       # ... arriving 0 -> arriving 2
+    copy(1, 14 - 6, 7, 2, 6)                                                     # region 1: into resident 0's last row, lane 3
+    copy(3, 1, 9, 11, 7)                                                         # ... resident 1 -> arriving 2
+    copy(5, 4, 7, 9, 8)                                                          # ... arriving 0 -> arriving 1
+    labels = [7] * (k + videos)
+    live = G.live_pairs(labels, k)
+    assert list(live.values()) == [pair_index(a, b, k + videos) for a, b in live] and len(live) == 9   # one label: the comparator's ids
+    want = oracle_live(rows, labels, k, t, min_len, 2)
+    last_row = {prob: [r for r in runs if r[0] == lens[0 + prob % 2] - 1] for prob, runs in want.items()
+                if prob // 2 in (live[(0, 2)], live[(0, 3)])}
+    assert last_row[live[(0, 2)] * 2] and last_row[live[(0, 3)] * 2 + 1] and len(want) >= 6
+    plain = capi.CrossMatcher.with_resident(rows[:4], videos, max_items, min_len, t)
+    one = new(rows, labels, k, max_items, min_len, t)
+    assert plain.groups is None
+    lanes = rows[4:]
+    steps = [[(0, 20), (0, 9), None, (0, 17), (0, 1), None],                     # lane 3 whole; lane 4 one item: no cells yet
+             ("finish", [3]),                                                    # ... and finished early
+             [(20, 21), None, (0, 33), None, (1, 30), (0, 20)],
+             [(21, 48), (9, 20), (33, 40), None, None, None],
+             ("finish", [1, 2]),
+             [None, None, None, None, (30, 33), None]]
+    held = lambda m, prob: [r for r in by_pair(m.runs()).get(prob, []) if r in last_row[prob]]
+    for n, step in enumerate(steps):
+        for m in (plain, one):
+            if step[0] == "finish":
+                m.finish(step[1])
+            else:
+                m.feed([None if part is None else lanes[q][part[0]: part[1]] for q, part in enumerate(step)])
+        assert by_pair(plain.runs()) == by_pair(one.runs()) and len(plain.runs()) == len(one.runs()), n
+        assert plain.stats()[:3] == one.stats()[:3], n
+        assert not held(one, live[(0, 2)] * 2), n                                # lane 0 is not finished: its run into the last row waits
+        assert held(one, live[(0, 3)] * 2 + 1) == ([] if n == 0 else last_row[live[(0, 3)] * 2 + 1]), n   # lane 3's came with its finish
+    for m in (plain, one):
+        m.finish()
+        assert m.ready()[1] is True
+    assert by_pair(plain.runs()) == by_pair(one.runs()) == want
+    assert plain.stats()[:3] == one.stats()[:3] and plain.stats()[2] == live_cells(rows, labels, k, 2)
+    assert one.stats()[3] - plain.stats()[3] == 24 * len(live) * 2
+    assert plain.stats()[3] == capi.CrossMatcher.state_bytes(videos, max_items, lens[:4]) + 16 * 4 + SLAB
+
+
 # ---- 9. the existing objects launch what they launched ---------------------------------------------------------------------------------------
 def test_a_plain_cross_matcher_launches_what_it_launched():
     rng = np.random.default_rng(25)
