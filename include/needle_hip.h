@@ -434,8 +434,9 @@ enum NeedleError needle_hip_group_pairs(const uint32_t *groups, size_t num_video
                                         uint64_t *num_pairs);
 /* needle_hip_comparator_run_with_frame_hashes over the seasons of `groups` (num_videos labels); groups == NULL is that
  * call.  NeedleError_InvalidArgument where grouped pairs x regions, or the hashes, exceed 2^32.  With endings, "no ending
- * hash data present" only concerns videos that have a pair.  Match evidence, NeedleHipIndex, the library job and the
- * matchers do not take groups. */
+ * hash data present" only concerns videos that have a pair.  The library job takes groups through
+ * needle_hip_library_set_groups, the index and the cross-matcher through their own calls (further down); match evidence
+ * and NeedleHipMatcher do not take groups. */
 enum NeedleError needle_hip_comparator_run_with_frame_hashes_grouped(const struct NeedleAudioComparator *comparator,
                                                                      const FrameHashes *const *frame_hashes, size_t num_videos,
                                                                      const uint32_t *groups, bool display, bool use_skip_files,
@@ -521,7 +522,9 @@ enum NeedleError needle_hip_index_groups(const NeedleHipIndex *index, uint32_t *
  * One object per process/GPU describing ALL videos of a job.  PCM of the videos this rank owns is
  * uploaded once and stays in HBM; hashes live in a padded device arena [video * rows_per_video][stride] so a
  * plain all-gather over contiguous video blocks fills the rows other ranks computed; pairs are
- * addressed by their index in the reference's lexicographic pair list (comparator.rs:534-545). */
+ * addressed by their index in the reference's lexicographic pair list (comparator.rs:534-545) -- or, in a library with
+ * groups of videos (needle_hip_library_set_groups), by their grouped pair id ("A library of many shows" above): only pairs
+ * inside a group exist, and every pair range, pair count and NeedleHipRun.problem of this section is in that numbering. */
 typedef struct NeedleHipLibrary NeedleHipLibrary;
 
 enum NeedleError needle_hip_library_new(size_t num_videos, float opening_search_percentage, float hash_duration,
@@ -537,6 +540,21 @@ enum NeedleError needle_hip_library_include_endings(NeedleHipLibrary *library, f
  * needle_hip_analyzer_run_pcm's at that rate.  At 11025 nothing is resampled.  A rate the resampler refuses (see
  * needle_hip_resample_plan) is NeedleError_InvalidArgument here, the library unchanged. */
 enum NeedleError needle_hip_library_set_sample_rate(NeedleHipLibrary *library, int sample_rate);
+/* A library of many shows: groups[v] is the label of video v (any 32-bit value, only compared); videos of equal label are
+ * one season and only pairs INSIDE a season are searched.  Call after library_new and before set_pcm / set_pcm_device /
+ * stream_pcm (InvalidArgument afterwards, and for a num_videos other than the library's; the library unchanged).  Every
+ * rank passes the same labels.  On a grouped library needle_hip_library_num_pairs is the grouped pair count (what
+ * needle_hip_group_pairs gives), needle_hip_library_search takes a range of grouped pair ids and writes
+ * NeedleHipRun.problem = grouped pair id * comparator regions + region (what
+ * needle_hip_comparator_results_from_runs_grouped takes), and finalize, job_begin / job_end and job_runs work over that
+ * numbering: a video's result is what the ungrouped job over its own season's videos, in list order, gives it; a video
+ * alone in its season has no result, and "no ending hash data present" concerns only a video that has a pair.  The size
+ * limit of set_pcm (2^32 sequence pairs) counts grouped pairs.  One label for all videos is the plain library, run for run
+ * and id for id.  A labelling without any pair is allowed: jobs succeed, every result is empty, *num_runs is 0 and nothing
+ * is scanned.  rank_videos, analyze, audit, frame_hashes and the staging of PCM do not depend on the labels.
+ * needle_hip_library_groups copies the labels out (n >= the library's videos); a plain library: InvalidArgument. */
+enum NeedleError needle_hip_library_set_groups(NeedleHipLibrary *library, const uint32_t *groups, size_t num_videos);
+enum NeedleError needle_hip_library_groups(const NeedleHipLibrary *library, uint32_t *labels, size_t n);
 /* The sample format (enum NeedleHipSampleFormat, default NEEDLE_HIP_SAMPLE_S16) of the PCM that set_pcm, set_pcm_device
  * and stream_pcm will be given.  Call after library_new and before set_pcm (InvalidArgument afterwards, the library
  * unchanged).  Those three calls then read their pointer arrays in that format -- callers cast; for a planar format the
@@ -579,9 +597,10 @@ enum NeedleError needle_hip_library_hash_arena(NeedleHipLibrary *library, uint32
  * set_pcm and before analyze; the caller keeps the memory alive and zero-initialised. */
 enum NeedleError needle_hip_library_use_hash_arena(NeedleHipLibrary *library, uint32_t *d_arena, size_t rows,
                                                    size_t stride);
+/* All pairs of the videos, or the grouped pair count of a library with groups. */
 size_t needle_hip_library_num_pairs(const NeedleHipLibrary *library);
 /* Runs of pairs [first_pair, first_pair+num_pairs) into caller-provided device buffers
- * (NeedleHipRun.problem = global pair index * comparator regions + region).  The fast scan kernels stage a pair's
+ * (NeedleHipRun.problem = global pair index * comparator regions + region; the grouped pair id in a library with groups).  The fast scan kernels stage a pair's
  * destination window in LDS: up to ~39 000 hashes (2.7 h of audio at step 1, 5.3 h at the default step 2).  Pairs
  * with a longer window are scanned from HBM by a slower kernel in the same call; nothing fails (the reference has no
  * bound). */

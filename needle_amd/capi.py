@@ -143,7 +143,8 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_crossmatcher_state_bytes_regions", "needle_hip_crossmatcher_shape",
     "needle_hip_crossmatcher_new_resident", "needle_hip_crossmatcher_state_bytes_resident", "needle_hip_crossmatcher_resident",
     "needle_hip_crossmatcher_new_grouped", "needle_hip_crossmatcher_state_bytes_grouped", "needle_hip_crossmatcher_groups",
-    "needle_hip_index_crossmatcher_new_grouped", "needle_hip_index_add_matched_grouped"]
+    "needle_hip_index_crossmatcher_new_grouped", "needle_hip_index_add_matched_grouped",
+    "needle_hip_library_set_groups", "needle_hip_library_groups"]
 
 # enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
 SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
@@ -358,6 +359,8 @@ def lib():
     L.needle_hip_library_include_endings.argtypes = [vp, f32]
     L.needle_hip_library_set_sample_rate.argtypes = [vp, C.c_int]
     L.needle_hip_library_set_sample_format.argtypes = [vp, C.c_int]
+    L.needle_hip_library_set_groups.argtypes = [vp, C.POINTER(u32), sz]
+    L.needle_hip_library_groups.argtypes = [vp, C.POINTER(u32), sz]
     L.needle_hip_library_rows_per_video.argtypes = [vp]
     L.needle_hip_library_rows_per_video.restype = sz
     L.needle_hip_library_set_pcm.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.c_int]
@@ -1896,6 +1899,20 @@ class Library:
         mono on the device on the way in (needle_hip_library_set_sample_rate)."""
         check(lib().needle_hip_library_set_sample_rate(self._h, sample_rate))
         return self
+
+    def set_groups(self, labels: Sequence[int]) -> "Library":
+        """A label per video (0 .. 2^32 - 1, only compared): only pairs inside a group are searched, and pair ids, pair
+        ranges and NeedleHipRun.problem are grouped pair ids (needle_hip_library_set_groups; before set_pcm)."""
+        k = len(labels)
+        arr = (C.c_uint32 * max(k, 1))(*[int(g) for g in labels])
+        check(lib().needle_hip_library_set_groups(self._h, arr, k))
+        return self
+
+    def groups(self) -> List[int]:
+        """The labels of a grouped library, one per video (a plain one: NeedleError)."""
+        labels = (C.c_uint32 * max(self.n, 1))()
+        check(lib().needle_hip_library_groups(self._h, labels, self.n))
+        return list(labels[:self.n])
 
     def set_channel_mix(self, mix: Optional[ChannelMix]) -> "Library":
         """The PCM of set_pcm / set_pcm_device / stream_pcm is folded to mono with `mix` on the way in

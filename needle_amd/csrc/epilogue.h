@@ -44,6 +44,10 @@ struct EpilogueJob : EpilogueOptions {
   // as the form above, whatever the groups are.
   const GroupTables *groups = nullptr;
   const std::vector<uint64_t> *hash_durations = nullptr;
+  // A grouped job of more than one rank (the library job, sharded): block_wanted says that v0 and v1 ARE read -- the
+  // results of videos [v0, v1) only, each at its own slot, one workgroup per video of the block.  The comparator call and
+  // the index leave it unset and keep getting all n videos.  Without groups it is not looked at.
+  bool block_wanted = false;
 };
 
 // The device form gives a pair's runs to ONE lane (insertion order + heap): a pair with more runs than this (silence against
@@ -78,8 +82,11 @@ struct DirectPlan {
   uint32_t offset[64];    // bytes
   uint32_t capacity[64];  // runs
 };
+// `groups`: tables in DEVICE memory of a library with groups of videos (pair_ids.h) -- the runs' problems are then grouped
+// pair ids x regions, decoded by two bisections over those tables per run; NULL: the i-major numbering over n videos.
 Status gpu_direct_runs(const uint32_t *d_found, const NeedleHipRun *d_runs, uint32_t slab_capacity, uint32_t n, uint32_t regions,
-                       uint32_t videos_per_rank, int world, uint8_t *d_send, const DirectPlan &plan, hipStream_t stream);
+                       uint32_t videos_per_rank, int world, uint8_t *d_send, const DirectPlan &plan, hipStream_t stream,
+                       const GroupView *groups = nullptr);
 
 // Enqueues the epilogue kernels on `stream` behind whatever fills the segments, then the copies of results[n] and of the
 // failure count (videos whose padding / hash duration exceed the match end: the reference panics) into HOST memory

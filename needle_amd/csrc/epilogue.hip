@@ -28,8 +28,23 @@ namespace {
 
 // A slab's runs into one block per destination rank (gpu_direct_runs).  A wave asks a block's counter once per destination
 // for all its lanes' runs (a returning atomic per run on `world` addresses would be the kernel).
+// How a run's pair becomes its two videos: the i-major numbering over n videos, or a library of seasons' grouped one
+// (pair_ids.h; the tables in device memory: two bisections of global loads per run, over tables of a few KB -- this kernel
+// runs once per job over the run list, not per cell).
+struct DirectRowMajor {
+  uint32_t n;
+  __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const { pair_at_device(n, p, i, j); }
+};
+struct DirectGrouped {
+  GroupView groups;
+  // (every run of a grouped scan names a grouped pair; were one not to, it goes to video 0's owner and the epilogue drops it)
+  __device__ void at(uint64_t p, uint32_t *i, uint32_t *j) const {
+    if (!grouped_pair_at(groups, p, i, j)) *i = *j = 0;
+  }
+};
+template <class Pairs>
 __global__ __launch_bounds__(256) void direct_runs_kernel(const uint32_t *__restrict__ found, const NeedleHipRun *__restrict__ runs,
-                                                          uint32_t slab_capacity, uint32_t n, uint32_t regions, uint32_t videos_per_rank,
+                                                          uint32_t slab_capacity, Pairs pairs, uint32_t regions, uint32_t videos_per_rank,
                                                           int world, uint8_t *__restrict__ send, DirectPlan plan) {
   const uint32_t total = min(*found, slab_capacity);
   const uint32_t lane = threadIdx.x & 63;
@@ -41,7 +56,7 @@ __global__ __launch_bounds__(256) void direct_runs_kernel(const uint32_t *__rest
     if (g < total) {
       r = runs[g];
       uint32_t vi, vj;
-      pair_at_device(n, r.problem / regions, &vi, &vj);
+      pairs.at(r.problem / regions, &vi, &vj);
       oi = vi / videos_per_rank;
       oj = vj / videos_per_rank;
       if (oj == oi) oj = 0xFFFFFFFFu;
@@ -124,13 +139,18 @@ void note_epilogue_host_fallback(const char *where, size_t runs, size_t videos) 
 }
 
 Status gpu_direct_runs(const uint32_t *d_found, const NeedleHipRun *d_runs, uint32_t slab_capacity, uint32_t n, uint32_t regions,
-                       uint32_t videos_per_rank, int world, uint8_t *d_send, const DirectPlan &plan, hipStream_t stream) {
+                       uint32_t videos_per_rank, int world, uint8_t *d_send, const DirectPlan &plan, hipStream_t stream,
+                       const GroupView *groups) {
   if (world < 1 || world > 64 || n < 2 || regions < 1 || videos_per_rank < 1)
     return Status::Make(NeedleError_InvalidArgument, "directed run exchange: invalid plan");
   for (int q = 0; q < world; q++) NEEDLE_HIP_TRY(hipMemsetAsync(d_send + plan.offset[q], 0, 32, stream));
   const uint32_t grid = (uint32_t)std::min<uint64_t>(2048, ((uint64_t)slab_capacity + 255) / 256);
-  hipLaunchKernelGGL(direct_runs_kernel, dim3(std::max(grid, 1u)), dim3(256), 0, stream, d_found, d_runs, slab_capacity, n, regions,
-                     videos_per_rank, world, d_send, plan);
+  if (groups)
+    hipLaunchKernelGGL(direct_runs_kernel<DirectGrouped>, dim3(std::max(grid, 1u)), dim3(256), 0, stream, d_found, d_runs, slab_capacity,
+                       DirectGrouped{*groups}, regions, videos_per_rank, world, d_send, plan);
+  else
+    hipLaunchKernelGGL(direct_runs_kernel<DirectRowMajor>, dim3(std::max(grid, 1u)), dim3(256), 0, stream, d_found, d_runs, slab_capacity,
+                       DirectRowMajor{n}, regions, videos_per_rank, world, d_send, plan);
   NEEDLE_HIP_TRY(hipGetLastError());
   return Status::Ok();
 }
@@ -203,10 +223,11 @@ Status gpu_epilogue_enqueue(const EpilogueJob &job, hipStream_t stream, NeedleHi
   pr.v0 = job.v0;
   pr.v1 = job.v1;
   pr.hash_duration = job.hash_duration;
-  if (groups) {
+  if (groups && !job.block_wanted) {  // the comparator call, the index: every video
     pr.v0 = 0;
     pr.v1 = job.n;
   }
+  if (pr.v0 > pr.v1 || pr.v1 > job.n) return Status::Make(NeedleError_InvalidArgument, "device epilogue: a block of videos outside the list");
   EpilogueControl *ctl = ws->ctl.ptr;
   NEEDLE_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(*ctl), stream));
   NEEDLE_HIP_TRY(hipMemsetAsync(ws->results.ptr, 0, (size_t)job.n * sizeof(NeedleHipSearchResult), stream));
@@ -219,12 +240,12 @@ Status gpu_epilogue_enqueue(const EpilogueJob &job, hipStream_t stream, NeedleHi
                                                      ws->entries.ptr, ctl, stream);
     if (!s.ok()) return s;
   }
-  if (groups) {
+  if (groups && pr.v1 > pr.v0) {  // workgroup b is video v0 + b
     KernelTimer timer("epilogue_best_match", stream);
-    hipLaunchKernelGGL((best_match_kernel<GroupedVideos, GroupView, const uint64_t *>), dim3(job.n), dim3(256), 0, stream, pr, ws->scratch.start.ptr,
+    hipLaunchKernelGGL((best_match_kernel<GroupedVideos, GroupView, const uint64_t *>), dim3(pr.v1 - pr.v0), dim3(256), 0, stream, pr, ws->scratch.start.ptr,
                        ws->scratch.valid.ptr, ws->entries.ptr, ws->cand.ptr, &ctl->cand_cursor, ws->links.ptr, ws->results.ptr, &ctl->failed, view,
                        (const uint64_t *)ws->hash_durations.ptr);
-  } else if (pr.v1 > pr.v0) {
+  } else if (!groups && pr.v1 > pr.v0) {
     KernelTimer timer("epilogue_best_match", stream);
     hipLaunchKernelGGL(best_match_kernel<RowMajorVideos>, dim3(pr.v1 - pr.v0), dim3(256), 0, stream, pr, ws->scratch.start.ptr, ws->scratch.valid.ptr,
                        ws->entries.ptr, ws->cand.ptr, &ctl->cand_cursor, ws->links.ptr, ws->results.ptr, &ctl->failed);

@@ -522,18 +522,21 @@ struct EvidenceVideos {  // the index's evidence: EVERY video of the store, buck
 // group, which writes "no result" -- buckets in the grouped pair order (pair_ids.h), results[v].  The workgroup's video is
 // its block, so what the slot passes need of the tables (rank, group size, base) is read once, at addresses every lane
 // shares: scalar loads into scalar registers, and a slot's pair id is arithmetic on them -- the member list is not read here.
+// A job of several ranks takes a block of the videos: workgroup b is video pr.v0 + b (pr.v0 = 0 where all videos are wanted),
+// and writes results[v] all the same.
 struct GroupedVideos {
   uint64_t base;
-  uint32_t rank, size;
+  uint32_t rank, size, v0;
   const uint64_t *hash_durations;
-  __device__ GroupedVideos(const EpilogueParams &, const GroupView &g, const uint64_t *hd) : hash_durations(hd) {
-    const uint32_t group = g.group_of[blockIdx.x];
-    rank = g.rank_of[blockIdx.x];
+  __device__ GroupedVideos(const EpilogueParams &pr, const GroupView &g, const uint64_t *hd) : v0(pr.v0), hash_durations(hd) {
+    const uint32_t v = pr.v0 + blockIdx.x;
+    const uint32_t group = g.group_of[v];
+    rank = g.rank_of[v];
     size = g.size[group];
     base = g.base[group];
   }
   __device__ bool live(uint32_t) const { return true; }
-  __device__ uint32_t video(uint32_t block) const { return block; }
+  __device__ uint32_t video(uint32_t block) const { return v0 + block; }
   __device__ uint64_t pair(uint32_t q, uint32_t) const { return grouped_rank_slot_pair(base, rank, size, q); }
   __device__ uint32_t out(uint32_t, uint32_t v) const { return v; }
   __device__ uint32_t slots(const EpilogueParams &, uint32_t) const { return size - 1; }

@@ -71,6 +71,11 @@ struct JobShape {
   size_t arena_regions = 1;       // rows per video in the library's arena
   size_t comparator_regions = 1;  // NeedleHipRun.problem = pair * comparator_regions + region
   int world = 1, rank = 0;
+  // The job's pairs where they are not all pairs of the n videos: a library with groups of videos (pair_ids.h) searches
+  // the pairs inside its groups only, in the grouped numbering.  kAllPairs: job_pairs(n).
+  static constexpr uint64_t kAllPairs = ~(uint64_t)0;
+  uint64_t pairs = kAllPairs;
+  uint64_t pair_total() const { return pairs == kAllPairs ? job_pairs(n) : pairs; }
 };
 
 // ---- the plan
@@ -99,7 +104,7 @@ struct SegmentLayout {
 
 struct JobPlan {
   JobShape shape;
-  size_t pair_first = 0, pair_count = 0;    // this rank's range of the lexicographic pair list
+  size_t pair_first = 0, pair_count = 0;    // this rank's range of the pair ids (lexicographic, or grouped)
   size_t video_first = 0, video_count = 0;  // the videos whose results this rank computes (all of them unless sharded)
   // the form of the epilogue
   bool device_epilogue = false;  // on the device, enqueued behind the gather (else on host threads in job_end)
@@ -137,7 +142,7 @@ inline SegmentLayout segment_layout(const JobPlan &p, bool directed) {
 // and the host form 2.5 ms of a 0.5 ms job.  (Every rank sees every rank's count: the same decision everywhere.)
 inline bool device_epilogue_wanted(const JobShape &sh, const JobSwitches &sw, const JobHistory &h) {
   if (sw.device_epilogue.set) return sw.device_epilogue.value != 0;
-  return job_pairs(sh.n) * sh.comparator_regions >= kDeviceEpiloguePairs || h.last_max_count >= kDeviceEpilogueRuns;
+  return sh.pair_total() * sh.comparator_regions >= kDeviceEpiloguePairs || h.last_max_count >= kDeviceEpilogueRuns;
 }
 
 // The sizes: the slab of a library's first job, and the one-trip download -- everything the last job needed plus a
@@ -147,7 +152,7 @@ inline void plan_sizes(const JobSwitches &sw, const JobHistory &h, uint32_t keep
   p->slab_runs = h.slab_runs;
   if (p->slab_runs == 0 && sw.slab_runs.set) p->slab_runs = round_up4((uint64_t)std::max(4, sw.slab_runs.value));
   if (p->slab_runs == 0)
-    p->slab_runs = round_up4(std::max<uint64_t>(1024, 4 * (uint64_t)shard_block((size_t)job_pairs(sh.n), sh.world) * sh.arena_regions));
+    p->slab_runs = round_up4(std::max<uint64_t>(1024, 4 * (uint64_t)shard_block((size_t)sh.pair_total(), sh.world) * sh.arena_regions));
   uint32_t head = h.last_max_count ? with_head_margin(h.last_max_count) : 4096u;
   const bool forced = !h.last_max_count && sw.head_runs.set;  // a first head only
   if (forced) head = round_up4((uint64_t)std::max(4, sw.head_runs.value));
@@ -162,14 +167,14 @@ inline void plan_sizes(const JobSwitches &sw, const JobHistory &h, uint32_t keep
 // cannot wait for the run count: the pairs stand in for it).
 inline void plan_form(const JobSwitches &sw, const JobHistory &h, JobPlan *p) {
   const JobShape &sh = p->shape;
-  p->device_epilogue = device_epilogue_wanted(sh, sw, h) && sh.n >= 2;
+  p->device_epilogue = device_epilogue_wanted(sh, sw, h) && sh.n >= 2 && sh.pair_total() > 0;  // (no pair: the host form)
   // A rank whose device epilogue then fails alone keeps `sharded`: the other ranks enter the collective that decision implies.
   p->shape_fixed = p->device_epilogue;
   p->sharded = false;
   if (p->device_epilogue) {
     uint64_t shard_from = 1u << 16;
     if (sw.shard_epilogue_pairs.set) shard_from = (uint64_t)std::max(1, sw.shard_epilogue_pairs.value);
-    p->sharded = sh.world > 1 && (sw.shard_epilogue.set ? sw.shard_epilogue.value != 0 : job_pairs(sh.n) * sh.comparator_regions >= shard_from);
+    p->sharded = sh.world > 1 && (sw.shard_epilogue.set ? sw.shard_epilogue.value != 0 : sh.pair_total() * sh.comparator_regions >= shard_from);
   }
   p->inject_epilogue_failure = p->device_epilogue && sw.test_epilogue_fail_rank.set && sw.test_epilogue_fail_rank.value == sh.rank;
   p->video_first = 0;
@@ -224,7 +229,7 @@ inline void plan_directed(const JobSwitches &sw, const JobHistory &h, JobPlan *p
 inline JobPlan plan_job(const JobShape &shape, const JobSwitches &sw, const JobHistory &h, uint32_t keep_head = 0) {
   JobPlan p;
   p.shape = shape;
-  shard_range((size_t)job_pairs(shape.n), shape.world, shape.rank, &p.pair_first, &p.pair_count);
+  shard_range((size_t)shape.pair_total(), shape.world, shape.rank, &p.pair_first, &p.pair_count);
   plan_sizes(sw, h, keep_head, &p);
   plan_form(sw, h, &p);
   plan_directed(sw, h, &p);

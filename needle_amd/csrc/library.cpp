@@ -7,7 +7,8 @@
 // endings are enabled), the pair search reads that arena in place, and only the short run list crosses
 // PCIe — the runs carry their simhashes, so the host epilogue needs timestamps only.  Rows computed by
 // other ranks are filled by the caller with one all-gather over contiguous row blocks (RCCL over xGMI);
-// pairs are sharded by index in the lexicographic pair list.
+// pairs are sharded by index in the lexicographic pair list -- or, in a library with groups of videos
+// (needle_hip_library_set_groups), by grouped pair id (pair_ids.h): only pairs inside a group exist.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <new>
 #include <tuple>
 
@@ -25,6 +27,7 @@
 #include "hipctx.h"
 #include "job_plan.h"
 #include "needle_core.h"
+#include "pair_ids.h"
 
 struct FrameHashes;
 struct NeedleAudioComparator;
@@ -65,6 +68,19 @@ struct NeedleHipLibrary {
   bool any_mix = false;
   std::vector<NeedleHipLaneFormat> formats;
   std::vector<NeedleHipChannelMix> mixes;
+  // needle_hip_library_set_groups: a label per video; only pairs inside a group are searched, numbered as pair_ids.h
+  // numbers them (GroupTables, built once).  Null: a plain library, all pairs in the i-major numbering.
+  std::vector<uint32_t> group_labels;
+  std::unique_ptr<const GroupTables> groups;
+  std::vector<uint64_t> hash_durations;  // grouped: the device epilogue's one value per video (all the library's own)
+  // the tables in device memory for the owner-directed exchange's kernel, uploaded once per library (ensure_device_groups)
+  struct DeviceGroups {
+    DeviceBuffer<uint32_t> group_of, rank_of, size, first, members;
+    DeviceBuffer<uint64_t> base;
+    bool uploaded = false;
+    GroupView view{};
+  } d_groups;
+  size_t pairs() const { return groups ? (size_t)groups->pairs() : pair_count(n); }
   bool have_pcm = false;      // windows and arena are set up (set_pcm or stream_pcm)
   bool pcm_resident = false;  // set_pcm: the PCM stays in HBM and analyze can be repeated
   std::vector<Window> win;  // [video * regions() + region]
@@ -340,6 +356,28 @@ enum NeedleError needle_hip_library_video_format(const NeedleHipLibrary *lib, si
   return NeedleError_Ok;
 }
 
+enum NeedleError needle_hip_library_set_groups(NeedleHipLibrary *lib, const uint32_t *groups, size_t num_videos) {
+  if (!lib || !groups) return NeedleError_NullArgument;
+  if (lib->have_pcm || num_videos != lib->n || num_videos > UINT32_MAX) return NeedleError_InvalidArgument;  // must precede set_pcm
+  return guarded([&]() -> NeedleError {
+    std::vector<uint32_t> labels(groups, groups + num_videos);
+    std::unique_ptr<const GroupTables> tables(new GroupTables(groups, num_videos));
+    std::vector<uint64_t> durations(num_videos, lib->hash_duration);
+    lib->group_labels.swap(labels);
+    lib->groups = std::move(tables);
+    lib->hash_durations.swap(durations);
+    lib->d_groups.uploaded = false;
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_library_groups(const NeedleHipLibrary *lib, uint32_t *labels, size_t n) {
+  if (!lib || !labels) return NeedleError_NullArgument;
+  if (!lib->groups || n < lib->n) return NeedleError_InvalidArgument;  // a plain library has none
+  std::copy(lib->group_labels.begin(), lib->group_labels.end(), labels);
+  return NeedleError_Ok;
+}
+
 }  // extern "C"
 
 namespace {
@@ -376,6 +414,29 @@ struct VideoLayouts {
 // the `channels` of a PCM call or of rank_videos: 1..8 for a library with one format, 0 for one with a format per video
 bool call_channels_ok(const NeedleHipLibrary *lib, int channels) {
   return lib->has_formats ? channels == 0 : channels >= 1 && channels <= NEEDLE_HIP_MAX_CHANNELS;
+}
+
+// A grouped library's tables in device memory (pair_ids.h GroupView), for the kernel that sorts the runs by destination:
+// uploaded once per library, when its PCM is set (a few words per video; no job waits for it).
+template <class T>
+Status upload_table(DeviceBuffer<T> *dst, const std::vector<T> &src) {
+  Status s = dst->reserve(std::max<size_t>(src.size(), 1));
+  if (!s.ok()) return s;
+  if (!src.empty()) NEEDLE_HIP_TRY(hipMemcpy(dst->ptr, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return Status::Ok();
+}
+Status ensure_device_groups(NeedleHipLibrary *lib) {
+  NeedleHipLibrary::DeviceGroups &d = lib->d_groups;
+  if (d.uploaded) return Status::Ok();
+  const GroupTables &t = *lib->groups;
+  Status s;
+  if (!(s = upload_table(&d.group_of, t.group_of)).ok() || !(s = upload_table(&d.rank_of, t.rank_of)).ok() ||
+      !(s = upload_table(&d.size, t.size)).ok() || !(s = upload_table(&d.first, t.first)).ok() ||
+      !(s = upload_table(&d.members, t.members)).ok() || !(s = upload_table(&d.base, t.base)).ok())
+    return s;
+  d.view = GroupView{d.group_of.ptr, d.rank_of.ptr, d.size.ptr, d.first.ptr, d.base.ptr, d.members.ptr, (uint32_t)t.size.size()};
+  d.uploaded = true;
+  return Status::Ok();
 }
 
 // Search windows of every video (analyzer.rs:378,390) from the stream lengths, arena geometry, and -- for the videos
@@ -435,7 +496,7 @@ Status plan_windows(NeedleHipLibrary *lib, const void *const *pcm, const size_t 
   size_t stride = 64 * tiles_per_row;
   const size_t arena_rows = lib->rows();
   // NeedleHipSeq.offset and NeedleHipProblem.tag are 32-bit on the device
-  if ((uint64_t)arena_rows * stride > UINT32_MAX || (uint64_t)pair_count(lib->n) * R > UINT32_MAX)
+  if ((uint64_t)arena_rows * stride > UINT32_MAX || (uint64_t)lib->pairs() * R > UINT32_MAX)
     return Status::Make(NeedleError_InvalidArgument, "library too large for one job: more than 2^32 arena hashes or sequence pairs");
   const bool own_arena = lib->arena == lib->d_arena.ptr;
   if (!lib->arena || (own_arena && (stride != lib->stride || arena_rows != lib->arena_rows))) {
@@ -463,6 +524,7 @@ Status plan_windows(NeedleHipLibrary *lib, const void *const *pcm, const size_t 
     }
   }
   if (total_values) *total_values = total;
+  if (lib->groups && !(s = ensure_device_groups(lib)).ok()) return s;
   lib->min_len.clear();
   lib->row_len.clear();
   lib->shells.clear();
@@ -734,13 +796,13 @@ enum NeedleError needle_hip_library_use_hash_arena(NeedleHipLibrary *lib, uint32
   return NeedleError_Ok;
 }
 
-size_t needle_hip_library_num_pairs(const NeedleHipLibrary *lib) { return lib ? pair_count(lib->n) : 0; }
+size_t needle_hip_library_num_pairs(const NeedleHipLibrary *lib) { return lib ? lib->pairs() : 0; }
 
 enum NeedleError needle_hip_library_search(NeedleHipLibrary *lib, const struct NeedleAudioComparator *comparator,
                                            size_t first_pair, size_t num_pairs, NeedleHipRun *d_runs,
                                            uint32_t capacity, uint32_t *d_count, bool sync) {
   if (!lib || !comparator || !d_runs || !d_count) return NeedleError_NullArgument;
-  const size_t np = pair_count(lib->n);
+  const size_t np = lib->pairs();
   if (!lib->have_pcm || first_pair > np || num_pairs > np - first_pair) return NeedleError_InvalidArgument;
   return guarded([&]() -> NeedleError {
     const auto t_enter = std::chrono::steady_clock::now();
@@ -772,8 +834,21 @@ enum NeedleError needle_hip_library_search(NeedleHipLibrary *lib, const struct N
       lib->problems_for[0] = ~(size_t)0;  // not valid until it is complete
       problems.clear();
       problems.reserve(num_pairs * Rc);
+      // (i, j) of the range's first pair, then stepped: i-major over the videos, or -- grouped -- over a group's members
+      // (ranks ra < rb of group g) and on to the next group that has a pair
+      const GroupTables *gt = lib->groups.get();
       size_t i = 0, j = 0;
-      if (num_pairs) pair_at(lib->n, first_pair, &i, &j);
+      uint32_t g = 0, ra = 0, rb = 1;
+      if (num_pairs && !gt) pair_at(lib->n, first_pair, &i, &j);
+      if (num_pairs && gt) {
+        uint32_t a = 0, b = 0;
+        if (!grouped_pair_at(gt->view(), first_pair, &a, &b)) return report(Status::Make(NeedleError_Unknown, "internal error: no such grouped pair"));
+        i = a;
+        j = b;
+        g = gt->group_of[a];
+        ra = gt->rank_of[a];
+        rb = gt->rank_of[b];
+      }
       for (size_t p = first_pair; p < first_pair + num_pairs; p++) {
         for (size_t r = 0; r < Rc; r++) {
           if (r == 1 && (lib->win[i * R + 1].kept == 0 || lib->win[j * R + 1].kept == 0))  // comparator.rs:271-273
@@ -783,7 +858,20 @@ enum NeedleError needle_hip_library_search(NeedleHipLibrary *lib, const struct N
           problems.push_back(NeedleHipProblem{(uint32_t)(i * R + r), (uint32_t)(j * R + r), std::max(a, b),
                                               (uint32_t)(p * Rc + r)});
         }
-        if (++j == lib->n) j = ++i + 1;  // next pair in i-major order
+        if (!gt) {
+          if (++j == lib->n) j = ++i + 1;  // next pair in i-major order
+          continue;
+        }
+        if (p + 1 == first_pair + num_pairs) break;
+        if (++rb == gt->size[g]) rb = ++ra + 1;
+        if (rb >= gt->size[g]) {  // the group's last pair is behind (p + 1 is a pair: there is a next group with one)
+          do g++;
+          while (gt->size[g] < 2);
+          ra = 0;
+          rb = 1;
+        }
+        i = gt->members[gt->first[g] + ra];
+        j = gt->members[gt->first[g] + rb];
       }
       lib->problems_for[0] = first_pair;
       lib->problems_for[1] = num_pairs;
@@ -797,6 +885,12 @@ enum NeedleError needle_hip_library_search(NeedleHipLibrary *lib, const struct N
     const auto t_built = std::chrono::steady_clock::now();
     const bool count_is_zero = lib->count_zeroed == d_count;
     lib->count_zeroed = nullptr;
+    if (lib->groups && lib->pairs() == 0) {  // a labelling without any pair: nothing is scanned, the count is cleared
+      if ((!count_is_zero && hipMemsetAsync(d_count, 0, sizeof(uint32_t), library_stream()) != hipSuccess) ||
+          (sync && hipStreamSynchronize(library_stream()) != hipSuccess))
+        return report(Status::Make(NeedleError_Unknown, "clearing the run count failed"));
+      return NeedleError_Ok;
+    }
     Status s = gpu_hamming_runs_device(lib->arena, seqs.data(), seqs.size(), problems.data(), problems.size(),
                                        cmp.hash_match_threshold(), d_runs, capacity, d_count, sync, count_is_zero);
     if (getenv("NEEDLE_HIP_TRACE"))
@@ -865,7 +959,7 @@ enum NeedleError needle_hip_library_finalize(NeedleHipLibrary *lib, const struct
     const std::vector<const FrameHashesData *> fh = lib->shell_pointers();
     std::vector<VideoResult> res;
     const auto t0 = std::chrono::steady_clock::now();
-    Status s = cmp.results_from_runs(fh, runs, num_runs, false, false, false, &res);
+    Status s = cmp.results_from_runs(fh, runs, num_runs, false, false, false, &res, 0, ~(size_t)0, nullptr, lib->groups.get());
     if (getenv("NEEDLE_HIP_TRACE"))
       std::fprintf(stderr, "[needle_hip] epilogue %zu runs: %.1f us\n", num_runs,
                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
@@ -1016,6 +1110,7 @@ NeedleError job_plan_stage(NeedleHipLibrary *lib, const NeedleAudioComparator *c
   shape.comparator_regions = comparator_of(comparator).include_endings() ? 2 : 1;
   shape.world = comm_world();
   shape.rank = comm_rank();
+  if (lib->groups) shape.pairs = lib->groups->pairs();
   j.planned.plan = plan_job(shape, job_switches(), lib->history, keep_head);
   const JobPlan &p = j.planned.plan;
   lib->history.slab_runs = p.slab_runs;  // (a first slab sticks)
@@ -1045,7 +1140,7 @@ NeedleError job_scan(NeedleHipLibrary *lib, const NeedleAudioComparator *compara
 // Stage 3a, directed exchange: this rank's runs sorted into one block per destination, and the count matrix -- this rank's
 // row [runs in its slab, runs directed to rank 0, 1, ...] gathered from every rank and downloaded.  A job without block
 // sizes (plan.directed.sized) does this much: it counts, and travels as heads.
-Status job_count_directed(Job &j) {
+Status job_count_directed(NeedleHipLibrary *lib, Job &j) {
   const JobPlan &p = j.planned.plan;
   const DirectedPlan &d = p.directed;
   const int world = p.shape.world;
@@ -1062,9 +1157,11 @@ Status job_count_directed(Job &j) {
   Status s = j.buf.d_dir_send.reserve(d.send_total);
   if (s.ok()) s = j.buf.d_dir_counts.reserve(cw * W);
   if (s.ok()) s = j.buf.host_counts.reserve(count_matrix_bytes(world));
+  if (s.ok() && lib->groups) s = ensure_device_groups(lib);
   if (s.ok())
     s = gpu_direct_runs(slab_count_word(mine), slab_runs_of(mine), p.slab_runs, (uint32_t)p.shape.n, (uint32_t)p.shape.comparator_regions,
-                        (uint32_t)shard_block(p.shape.n, world), world, j.buf.d_dir_send.ptr, blocks, down);
+                        (uint32_t)shard_block(p.shape.n, world), world, j.buf.d_dir_send.ptr, blocks, down,
+                        lib->groups ? &lib->d_groups.view : nullptr);
   if (!s.ok()) return s;
   uint32_t *row = j.buf.d_dir_counts.ptr + (size_t)p.shape.rank * cw;
   bool ok = hipMemsetAsync(row, 0, cw * sizeof(uint32_t), down) == hipSuccess &&
@@ -1158,6 +1255,11 @@ Status job_device_epilogue(NeedleHipLibrary *lib, const Comparator &cmp, Job &j)
   ej.row_ts = &lib->row_ts;
   ej.row_seek = &lib->row_seek;
   ej.ts = &lib->ts_tables;
+  if (lib->groups) {  // the grouped form, for this rank's block of videos (all of them unless sharded)
+    ej.groups = lib->groups.get();
+    ej.hash_durations = &lib->hash_durations;
+    ej.block_wanted = true;
+  }
   NeedleHipSearchResult *hr = static_cast<NeedleHipSearchResult *>(j.buf.host_results.ptr);
   s = world <= 64 ? gpu_epilogue_enqueue(ej, download_stream(), hr, reinterpret_cast<uint32_t *>(hr + lib->n))
                   : Status::Make(NeedleError_InvalidArgument, "device epilogue: more than 64 ranks");
@@ -1178,7 +1280,7 @@ NeedleError job_enqueue(NeedleHipLibrary *lib, const NeedleAudioComparator *comp
   j.planned.counted = j.planned.directed = false;
   j.found.fetched_valid = false;
   Status s;
-  if (p.directed.wanted) s = job_count_directed(j);
+  if (p.directed.wanted) s = job_count_directed(lib, j);
   if (s.ok() && p.directed.wanted && p.directed.sized) s = job_exchange_directed(lib, j);
   if (s.ok() && !j.planned.directed) s = job_gather_heads(j);
   if (s.ok() && p.device_epilogue) s = job_device_epilogue(lib, comparator_of(comparator), j);
@@ -1302,7 +1404,7 @@ Status job_results(NeedleHipLibrary *lib, const Comparator &cmp, Job &j, const N
     run_list = j.found.fetched.data();
     total = j.found.fetched.size();
   }
-  *epilogue = cmp.results_from_runs(fh, run_list, total, false, false, false, res, v0, v0 + vcount);
+  *epilogue = cmp.results_from_runs(fh, run_list, total, false, false, false, res, v0, v0 + vcount, nullptr, lib->groups.get());
   return Status::Ok();
 }
 

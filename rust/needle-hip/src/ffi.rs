@@ -460,6 +460,8 @@ extern "C" {
     pub fn needle_hip_library_set_sample_format(library: *mut NeedleHipLibrary, format: c_int) -> NeedleError;
     pub fn needle_hip_library_include_endings(library: *mut NeedleHipLibrary, ending_search_percentage: f32) -> NeedleError;
     pub fn needle_hip_library_set_sample_rate(library: *mut NeedleHipLibrary, sample_rate: c_int) -> NeedleError;
+    pub fn needle_hip_library_set_groups(library: *mut NeedleHipLibrary, groups: *const u32, num_videos: usize) -> NeedleError;
+    pub fn needle_hip_library_groups(library: *const NeedleHipLibrary, labels: *mut u32, n: usize) -> NeedleError;
     pub fn needle_hip_library_set_pcm(
         library: *mut NeedleHipLibrary,
         pcm: *const *const i16,

@@ -1573,6 +1573,21 @@ pub mod multi_gpu {
             Ok(self)
         }
 
+        /// A library of many shows: a label per video (only compared); only pairs inside a group are searched, and pair
+        /// counts, pair ranges and `NeedleHipRun.problem` are grouped pair ids (`needle_hip_library_set_groups`).  Call
+        /// before loading PCM; every rank passes the same labels.
+        pub fn set_groups(&mut self, labels: &[u32]) -> Result<&mut Self> {
+            unsafe { check(ffi::needle_hip_library_set_groups(self.raw, labels.as_ptr(), labels.len()))? };
+            Ok(self)
+        }
+
+        /// The labels of a grouped library, one per video (an error on a plain one).
+        pub fn groups(&self) -> Result<Vec<u32>> {
+            let mut labels = vec![0u32; self.num_videos];
+            unsafe { check(ffi::needle_hip_library_groups(self.raw, labels.as_mut_ptr(), labels.len()))? };
+            Ok(labels)
+        }
+
         /// The PCM loaded afterwards is folded to mono with `mix` on the way in (`needle_hip_library_set_channel_mix`;
         /// `None`: the plain average again).  Call before loading.
         pub fn set_channel_mix(&mut self, mix: Option<&ChannelMix>) -> Result<&mut Self> {
