@@ -11,11 +11,14 @@
 // A GROUPED index holds a label per video and only the pairs inside a group: the same argument per group, since
 // restricting a candidate list to a group keeps the relative order of what is left.  Its ids are pair_ids.h's IndexGroupView
 // ids, the column-major id generalised so that an append still adds ids only at the end, whichever group grows.
+//
+// What an operation lists, under which ids and tags, what it refuses on counts alone and whether a streamed route's objects
+// are accepted is decided in index_plan.h, where a plain index is one label; this file makes the row tables,
+// calls the store and commits.
 #include "index.h"
 
 #include <algorithm>
 #include <atomic>
-#include <cmath>
 #include <cstring>
 #include <unordered_map>
 
@@ -26,20 +29,18 @@ namespace needle {
 
 namespace {
 
-void column_pair(uint64_t p, size_t *pi, size_t *pj) {  // p(i, j) = j (j - 1) / 2 + i, inverted
-  size_t j = (size_t)((1.0 + std::sqrt(1.0 + 8.0 * (double)p)) / 2.0);
-  while (j > 1 && (uint64_t)j * (j - 1) / 2 > p) j--;
-  while ((uint64_t)(j + 1) * j / 2 <= p) j++;
-  *pi = (size_t)(p - (uint64_t)j * (j - 1) / 2);
-  *pj = j;
-}
+static_assert(kIndexPlanFresh == kIndexFresh, "the plan and the store mark a replacement alike");
+
+Status refused(const IndexRefusal &r) { return Status::Make(r.code, r.text); }
+IndexRefusal standing(const Status &s) { return IndexRefusal{s.code, s.message}; }
 
 // A bucket the device does not order (beyond kEpilogueLargeLimit runs, or rows the packed keys cannot stand for): the entries
 // of an operation's `buckets` buckets (tag = listed pair * R + region) from its run list, with the host form's own functions.
-// pair_of(listed pair) gives its two videos.  start[b] is relative to the operation's first entry.
-template <class PairOf, class RowSeq, class Video>
-void host_entries(const Comparator &cmp, size_t R, uint64_t buckets, const std::vector<NeedleHipRun> &runs, PairOf pair_of, RowSeq row_seq,
-                  Video video, std::vector<uint32_t> *start_out, std::vector<uint32_t> *valid_out, std::vector<IndexEntry> *entries_out) {
+// id_of(listed pair) gives its id under `ids`.  start[b] is relative to the operation's first entry.
+template <class IdOf, class RowSeq, class Video>
+void host_entries(const Comparator &cmp, size_t R, uint64_t buckets, const std::vector<NeedleHipRun> &runs, const IndexPairIds &ids, IdOf id_of,
+                  RowSeq row_seq, Video video, std::vector<uint32_t> *start_out, std::vector<uint32_t> *valid_out,
+                  std::vector<IndexEntry> *entries_out) {
   std::vector<uint32_t> start(buckets + 1, 0), valid(buckets, 0);
   for (const NeedleHipRun &r : runs)
     if (r.problem < buckets) start[r.problem + 1]++;
@@ -60,7 +61,7 @@ void host_entries(const Comparator &cmp, size_t R, uint64_t buckets, const std::
     });
     const size_t r = b % R;
     size_t i = 0, j = 0;
-    pair_of(b / R, &i, &j);
+    (void)ids.at(id_of(b / R), &i, &j);
     cmp.entries_from_runs(&sorted[lo], hi - lo, row_seq(i, r), row_seq(j, r), video(i).hash_duration, video(j).hash_duration, r == 0, &tmp);
     for (size_t q = 0; q < tmp.size(); q++) {
       const HeapEntry &e = tmp[q];
@@ -76,14 +77,14 @@ void host_entries(const Comparator &cmp, size_t R, uint64_t buckets, const std::
 
 // After gpu_index_append / gpu_index_edit.  A bucket the device does not order: the operation's entries are computed here from
 // its run list and given back through upload(start, valid, entries), which runs its second half again.  Then the failure count.
-template <class PairOf, class RowSeq, class Video, class Upload>
-Status settle(const Comparator &cmp, const char *where, size_t R, size_t videos, uint64_t buckets, PairOf pair_of, RowSeq row_seq, Video video,
-              Upload upload, const IndexAppendOut &out) {
+template <class IdOf, class RowSeq, class Video, class Upload>
+Status settle(const Comparator &cmp, const char *where, size_t R, uint64_t buckets, const IndexPairIds &ids, IdOf id_of, RowSeq row_seq,
+              Video video, Upload upload, const IndexAppendOut &out) {
   if (out.failed & kEpilogueBucketTooLarge) {
-    note_epilogue_host_fallback(where, out.runs.size(), videos);
+    note_epilogue_host_fallback(where, out.runs.size(), ids.videos());
     std::vector<uint32_t> start, valid;
     std::vector<IndexEntry> entries;
-    host_entries(cmp, R, buckets, out.runs, pair_of, row_seq, video, &start, &valid, &entries);
+    host_entries(cmp, R, buckets, out.runs, ids, id_of, row_seq, video, &start, &valid, &entries);
     Status s = upload(start, valid, entries);  // (writes `out`)
     if (!s.ok()) return s;
   }
@@ -92,7 +93,9 @@ Status settle(const Comparator &cmp, const char *where, size_t R, size_t videos,
   return Status::Ok();
 }
 
-void set_options(const Comparator &cmp, size_t R, bool large_ok, IndexOptions *o) {
+// `ids`: of the list after the operation (evidence: the committed one's).  A plain list's store_groups() is null.
+void set_options(const Comparator &cmp, size_t R, bool large_ok, const IndexPairIds &ids, IndexOptions *o) {
+  o->groups = ids.store_groups();
   o->regions = (uint32_t)R;
   o->threshold = cmp.hash_match_threshold();
   o->include_endings = cmp.include_endings();
@@ -129,17 +132,54 @@ Status fresh_row(const Comparator &cmp, const std::vector<HashTs> &seq, const st
   return Status::Ok();
 }
 
-// The problems of pair (i, j), tagged from `tag` on; min_len and the regions left out as in run_with_frame_hashes (one of
-// whose sequences can hold no run long enough).  Whether any region is searched.
-bool pair_problems(const std::vector<uint32_t> &min_len, size_t R, size_t i, size_t j, uint64_t tag, std::vector<NeedleHipProblem> *problems) {
-  bool any = false;
-  for (size_t r = 0; r < R; r++) {
-    const uint32_t a = min_len[i * R + r], b = min_len[j * R + r];
-    if (a == 0 || b == 0) continue;
-    problems->push_back(NeedleHipProblem{(uint32_t)(i * R + r), (uint32_t)(j * R + r), std::max(a, b), (uint32_t)(tag + r)});
-    any = true;
+// The append fed from the route's objects in place of the scan.  Streamed: one list, the matcher's lanes first, and each of
+// its runs' lanes; the new rows beside the histories of both objects.
+Status append_streamed(IndexStore *store, const IndexAppend &a, const IndexRows &rows, Matcher *matcher, CrossMatcher *cross, IndexAppendOut *out) {
+  const size_t first = (size_t)a.n0 * a.regions;
+  std::vector<NeedleHipRun> list;
+  std::vector<uint32_t> run_lane;
+  for (size_t lane = 0; lane < a.num_rows; lane++) {
+    const std::vector<NeedleHipRun> &runs = matcher->run_list(lane);
+    list.insert(list.end(), runs.begin(), runs.end());
+    run_lane.insert(run_lane.end(), runs.size(), (uint32_t)lane);
   }
-  return any;
+  const size_t from_matcher = list.size();
+  if (cross) list.insert(list.end(), cross->run_list().begin(), cross->run_list().end());
+  std::vector<IndexLaneRow> lanes;
+  for (size_t at = first; at < rows.seqs.size(); at++) {
+    if (!rows.seqs[at].len) continue;
+    if (const uint32_t *history = matcher->history(at - first)) lanes.push_back(IndexLaneRow{rows.seqs[at].offset, history, rows.seqs[at].len});
+    if (cross) lanes.push_back(IndexLaneRow{rows.seqs[at].offset, cross->history(at - first), rows.seqs[at].len});
+  }
+  IndexStreamed m;
+  m.runs = list.data();
+  m.num_matcher_runs = from_matcher;
+  m.num_cross_runs = list.size() - from_matcher;
+  m.run_lane = run_lane.data();
+  m.min_len = rows.min_len.data();
+  m.lanes = lanes.data();
+  m.num_lanes = lanes.size();
+  return gpu_index_append_streamed(store, a, m, out);
+}
+
+Status append_matched(IndexStore *store, const IndexAppend &a, const IndexRows &rows, CrossMatcher *cross, IndexAppendOut *out) {
+  const size_t first = (size_t)a.n0 * a.regions;
+  std::vector<IndexSegment> lanes;
+  for (size_t at = first; at < rows.seqs.size(); at++)
+    if (rows.seqs[at].len)
+      lanes.push_back(IndexSegment{rows.seqs[at].offset, (uint64_t)(cross->history(at - first) - cross->history(0)), rows.seqs[at].len});
+  IndexMatched m;
+  m.runs = cross->run_list().data();
+  m.num_runs = cross->run_list().size();
+  m.min_len = rows.min_len.data();
+  m.history = cross->history(0);
+  m.lanes = lanes.data();
+  m.num_lanes = lanes.size();
+  return gpu_index_append_matched(store, a, m, out);
+}
+
+const char *route_name(IndexRoute route) {
+  return route == IndexRoute::Streamed ? "Index::add_streamed" : route == IndexRoute::Scan ? "Index::add" : "Index::add_matched";
 }
 
 std::atomic<uint64_t> next_index_id{1};
@@ -171,14 +211,14 @@ Status Index::init() {
 Status Index::add(const std::vector<const FrameHashesData *> &fh) {
   if (grouped_)
     return Status::Make(NeedleError_InvalidArgument, "index add: a grouped index takes a label per video (needle_hip_index_add_grouped)");
-  return append(fh, nullptr, nullptr);
+  return append(fh, nullptr);
 }
 
 Status Index::add_grouped(const std::vector<const FrameHashesData *> &fh, const uint32_t *labels) {
   if (!labels) return Status::Make(NeedleError_NullArgument, "index add_grouped: null argument");
   if (!grouped_)
     return Status::Make(NeedleError_InvalidArgument, "index add_grouped: not a grouped index (needle_hip_index_new_grouped makes one)");
-  return append(fh, nullptr, nullptr, labels);
+  return append(fh, labels);
 }
 
 // The plain streamed routes on a grouped index: their objects' runs name pairs across groups.  (A grouped cross-matcher has
@@ -190,7 +230,7 @@ Status Index::refuse_grouped(const char *route) const {
 Status Index::add_matched(CrossMatcher *matcher, const std::vector<const FrameHashesData *> &fh) {
   if (grouped_) return refuse_grouped("add_matched");
   if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_matched: null argument");
-  return append(fh, matcher, nullptr);
+  return append(fh, nullptr, IndexRoute::Matched, matcher);
 }
 
 // The grouped index's streamed route: a grouped cross-matcher made by crossmatcher_grouped, whose labels name
@@ -199,7 +239,7 @@ Status Index::add_matched_grouped(CrossMatcher *matcher, const std::vector<const
   if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_matched_grouped: null argument");
   if (!grouped_)
     return Status::Make(NeedleError_InvalidArgument, "index add_matched_grouped: not a grouped index (needle_hip_index_add_matched takes a plain one)");
-  return append(fh, matcher, nullptr);
+  return append(fh, nullptr, IndexRoute::MatchedGrouped, matcher);
 }
 
 Status Index::add_streamed(Matcher *matcher, CrossMatcher *crossmatcher, const std::vector<const FrameHashesData *> &fh) {
@@ -207,7 +247,7 @@ Status Index::add_streamed(Matcher *matcher, CrossMatcher *crossmatcher, const s
   if (!matcher) return Status::Make(NeedleError_NullArgument, "index add_streamed: null argument");
   if (!crossmatcher && fh.size() > 1)
     return Status::Make(NeedleError_InvalidArgument, "index add_streamed: more than one video needs the cross-matcher of the arriving pairs");
-  return append(fh, crossmatcher, matcher);
+  return append(fh, nullptr, IndexRoute::Streamed, crossmatcher, matcher);
 }
 
 // The index's rows as a matcher's sources (matcher.hip, regions): gathered on the device from the store's arena; a row's own
@@ -274,78 +314,83 @@ Status Index::make_crossmatcher(size_t videos, const uint32_t *groups, const siz
   return s;
 }
 
-// add, add_matched and add_streamed: with a cross-matcher (made from the index) its runs stand in for the scan of the new pairs;
-// with a matcher made from the index (`streamed`) its runs stand in for the resident x arriving pairs and those of `matcher`, a
-// cross-matcher over the arriving videos alone (null: one video), for the arriving pairs; everything else is one path.
-// A grouped index (`labels`, one per arriving video): the new pairs are each arriving video's with the lower-ranked members of
-// its group, old and arriving alike, under the append-stable ids of pair_ids.h (IndexGroupView); the scan only.
-Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatcher *matcher, Matcher *streamed, const uint32_t *labels) {
-  if (fh.empty()) return Status::Make(NeedleError_InvalidArgument, "index add: no videos");
-  const size_t k = fh.size(), n0 = videos_.size(), n1 = n0 + k, R = regions_;
-  std::vector<uint32_t> all_labels;
-  std::unique_ptr<const IndexGroupTables> groups;
-  const std::string who = streamed ? "index add_streamed: " : "index add_matched: ";
-  auto refuse = [&](const char *what) { return Status::Make(NeedleError_InvalidArgument, who + what); };
-  if (streamed) {
-    Status s = streamed->poisoned();
-    if (!s.ok() || (matcher && !(s = matcher->poisoned()).ok())) return s;
-    const Matcher::Origin from = streamed->origin();
-    if (from.index_id != id_) return refuse("the matcher was not created from this index");
-    if (from.generation != generation_) return refuse("the index has changed since the matcher was created");
-    if (matcher && matcher->residents() != 0)
-      return refuse("the cross-matcher has resident videos (the arriving pairs come from needle_hip_crossmatcher_new_regions)");
-    if (streamed->device() != index_store_device(store_) || (matcher && matcher->device() != index_store_device(store_)))
-      return refuse("the matcher is on another device than the index");
-    bool complete = true;
-    for (size_t lane = 0; lane < streamed->lanes() && complete; lane++)
-      if (!(s = streamed->Ready(lane, nullptr, nullptr, &complete)).ok()) return s;
-    if (complete && matcher && !(s = matcher->Ready(nullptr, &complete)).ok()) return s;
-    if (!complete) return refuse("the matcher is not complete");
-    if (k * R != streamed->lanes() || R != streamed->regions() || (matcher && (k != matcher->videos() || R != matcher->regions())))
-      return refuse("not the matcher's number of videos");
-  } else if (matcher) {
-    Status s = matcher->poisoned();
-    if (!s.ok()) return s;
-    const CrossMatcher::Origin from = matcher->origin();
-    if (from.index_id != id_) return refuse("the matcher was not created from this index");
-    if (from.generation != generation_) return refuse("the index has changed since the matcher was created");
-    if (matcher->device() != index_store_device(store_)) return refuse("the matcher is on another device than the index");
-    bool complete = false;
-    if (!(s = matcher->Ready(nullptr, &complete)).ok()) return s;
-    if (!complete) return refuse("the matcher is not complete");
-    if (k != matcher->videos() || R != matcher->regions() || n0 != matcher->residents()) return refuse("not the matcher's number of videos");
-    if (grouped_ != matcher->grouped())
-      return refuse(grouped_ ? "the matcher has no groups (needle_hip_index_crossmatcher_new_grouped makes one)" : "the matcher has groups");
-    if (grouped_) {  // the arriving videos' labels are the matcher's
-      if (matcher->labels().size() != n1 || !std::equal(labels_.begin(), labels_.end(), matcher->labels().begin()))
-        return refuse("the matcher's labels are not the index's");
-      labels = matcher->labels().data() + n0;
+// The facts index_accept() judges (index_plan.h).  A poisoned object says nothing but its standing error; otherwise no call
+// below can fail: every lane asked for is one of the object's own.
+IndexAcceptance Index::acceptance(IndexRoute route, size_t k, CrossMatcher *cross, Matcher *matcher) const {
+  IndexAcceptance f;
+  f.route = route;
+  f.index_id = id_;
+  f.generation = generation_;
+  f.device = index_store_device(store_);
+  f.n0 = videos_.size();
+  f.k = k;
+  f.regions = regions_;
+  f.labels = labels_.data();
+  if (matcher) {
+    IndexSource &m = f.matcher;
+    m.present = true;
+    m.poison = standing(matcher->poisoned());
+    if (m.poison.ok()) {
+      m.origin_id = matcher->origin().index_id;
+      m.origin_generation = matcher->origin().generation;
+      m.device = matcher->device();
+      m.lanes = matcher->lanes();
+      m.regions = matcher->regions();
+      m.fed.resize(m.lanes);
+      m.complete = true;
+      for (size_t lane = 0; lane < m.lanes; lane++) {
+        bool finished = false;
+        (void)matcher->Ready(lane, nullptr, &m.fed[lane], &finished);
+        m.complete = m.complete && finished;
+      }
     }
   }
-  if (labels) {
-    all_labels = labels_;
-    all_labels.insert(all_labels.end(), labels, labels + k);
-    groups.reset(new IndexGroupTables(all_labels.data(), n1));
+  if (cross) {
+    IndexSource &c = f.cross;
+    c.present = true;
+    c.poison = standing(cross->poisoned());
+    if (c.poison.ok()) {
+      c.origin_id = cross->origin().index_id;
+      c.origin_generation = cross->origin().generation;
+      c.device = cross->device();
+      c.regions = cross->regions();
+      c.lanes = cross->videos() * c.regions;
+      c.residents = cross->residents();
+      c.grouped = cross->grouped();
+      c.labels = cross->labels().data();
+      c.num_labels = cross->labels().size();
+      (void)cross->Ready(nullptr, &c.complete);
+      c.fed.resize(c.lanes);
+      for (size_t lane = 0; lane < c.lanes; lane++) (void)cross->Lane(lane, &c.fed[lane], nullptr);
+      for (size_t r = 0; r < c.regions && r < 2; r++) c.min_len[r] = cross->min_len(r);
+    }
   }
-  if (n1 >= 0xFFFFFFFFull) return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 videos");
+  return f;
+}
+
+// Every add: facts -> plan -> rows -> IndexAppend -> the route's store call -> settle -> commit.  With a cross-matcher made from
+// the index its runs stand in for the scan of the new pairs; with a matcher made from the index its runs stand in for the
+// resident x arriving pairs and those of `cross`, a cross-matcher over the arriving videos alone (null: one video), for the
+// arriving pairs.  `labels` (one per arriving video; MatchedGrouped: the cross-matcher's): a grouped index.
+Status Index::append(const std::vector<const FrameHashesData *> &fh, const uint32_t *labels, IndexRoute route, CrossMatcher *cross,
+                     Matcher *matcher) {
+  if (fh.empty()) return Status::Make(NeedleError_InvalidArgument, "index add: no videos");
+  const size_t k = fh.size(), n0 = videos_.size(), n1 = n0 + k, R = regions_;
+  const IndexAcceptance from = acceptance(route, k, cross, matcher);
+  IndexRefusal no = index_accept(from, &labels);
+  if (!no.ok()) return refused(no);
+  IndexAppendPlan plan = plan_index_append(n0, k, R, labels_, labels);
+  if (!plan.refusal.ok()) return refused(plan.refusal);
+  const IndexPairIds &ids = *plan.ids;
   auto video = [&](size_t v) -> const FrameHashesData & { return v < n0 ? videos_[v] : *fh[v - n0]; };
   auto row_seq = [&](size_t v, size_t r) -> const std::vector<HashTs> & { return r == 0 ? video(v).opening : video(v).ending; };
   if (include_endings_ && n1 > 1)
     for (size_t v = 0; v < n1; v++)
-      if (video(v).ending.empty() && (!groups || groups->size[groups->group_of[v]] > 1))  // comparator.rs:271-273 (every video that is in some pair)
+      if (video(v).ending.empty() && ids.paired(v))  // comparator.rs:271-273 (every video that is in some pair)
         return Status::Make(NeedleError_Unknown, "no ending hash data present");
-  for (size_t lane = 0; matcher && lane < k * R; lane++) {
-    uint64_t fed = 0;
-    Status s = matcher->Lane(lane, &fed, nullptr);
-    if (!s.ok()) return s;
-    if (row_seq(n0 + lane / R, lane % R).size() != fed) return refuse("a video's row is not as long as what its lane was fed");
-  }
-  for (size_t lane = 0; streamed && lane < k * R; lane++) {
-    uint64_t fed = 0;
-    Status s = streamed->Ready(lane, nullptr, &fed, nullptr);
-    if (!s.ok()) return s;
-    if (row_seq(n0 + lane / R, lane % R).size() != fed) return refuse("a video's row is not as long as what its lane was fed");
-  }
+  std::vector<uint64_t> arriving_len;
+  for (size_t lane = 0; lane < k * R; lane++) arriving_len.push_back(row_seq(n0 + lane / R, lane % R).size());
+  if (!(no = index_accept_rows(from, arriving_len.data())).ok()) return refused(no);
   IndexRows rows(rows_);
   rows.seqs.resize(n1 * R);
   rows.min_len.resize(n1 * R);
@@ -362,36 +407,18 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
       rows.large_ok = rows.large_ok && rows.row_ok[at];
     }
   }
-  // the new pairs (i, j), j in [n0, n1), i < j, in column-major order
-  // (a grouped index: video j's column is its pairs with the members of its group before it, ids vbase[j] + their rank)
-  const uint64_t all_pairs = groups ? groups->pairs() : (uint64_t)n1 * (n1 - 1) / 2;
-  const uint64_t first_pair = groups ? groups->vbase[n0] : (uint64_t)n0 * (n0 ? n0 - 1 : 0) / 2;
-  const uint64_t new_pairs = all_pairs - first_pair;
-  if (all_pairs * R >= 0xFFFFFFF0ull)  // problem tags and bucket ids are 32-bit on the device
-    return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
-  std::vector<NeedleHipProblem> problems;
-  problems.reserve(new_pairs * R);
-  uint64_t searched = 0;
-  for (size_t j = n0; j < n1; j++) {
-    if (groups) {
-      const uint32_t *members = groups->members.data() + groups->first[groups->group_of[j]];
-      for (size_t ra = 0; ra < groups->rank_of[j]; ra++)
-        searched += pair_problems(rows.min_len, R, members[ra], j, (groups->vbase[j] + ra - first_pair) * R, &problems);
-      continue;
-    }
-    for (size_t i = 0; i < j; i++) searched += pair_problems(rows.min_len, R, i, j, ((uint64_t)j * (j - 1) / 2 + i - first_pair) * R, &problems);
-  }
+  if (!(no = list_index_append(&plan, rows.min_len.data(), route)).ok()) return refused(no);
+  if (!(no = index_accept_min_len(from, plan.least)).ok()) return refused(no);
   IndexAppend a;
-  a.groups = groups.get();
   a.n0 = (uint32_t)n0;
   a.n1 = (uint32_t)n1;
-  set_options(cmp_, R, rows.large_ok, &a);
+  set_options(cmp_, R, rows.large_ok, ids, &a);
   a.hashes = hashes.data();
   a.num_hashes = hashes.size();
   a.seqs = rows.seqs.data();
   a.num_seqs = rows.seqs.size();
-  a.problems = problems.data();
-  a.num_problems = problems.size();
+  a.problems = plan.problems.data();
+  a.num_problems = plan.problems.size();
   a.row_len = new_row_len.data();
   a.row_ts = rows.row_ts.data() + n0 * R;
   a.num_rows = new_row_len.size();
@@ -399,88 +426,26 @@ Status Index::append(const std::vector<const FrameHashesData *> &fh, CrossMatche
   a.num_ts = ts.size();
   a.hash_duration = hash_duration.data();
   IndexAppendOut out;
-  Status s;
-  if (matcher) {
-    // The matcher had one min_len per region, a lower bound: beyond the smallest bound of a live pair it has lost runs.
-    for (size_t r = 0; r < R; r++) {
-      uint32_t least = UINT32_MAX;
-      for (size_t j = n0; j < n1; j++)
-        for (size_t i = streamed ? n0 : 0; i < j; i++)  // (streamed: the cross-matcher had the arriving pairs only)
-          if ((!groups || groups->group_of[i] == groups->group_of[j]) && rows.min_len[i * R + r] && rows.min_len[j * R + r]) least = std::min(least, std::max(rows.min_len[i * R + r], rows.min_len[j * R + r]));
-      if (matcher->min_len(r) > least) return refuse("the matcher's min_len exceeds the shortest run a pair can hold");
-    }
-  }
-  if (streamed) {
-    // One list, the matcher's lanes first, and each of its runs' lanes; the new rows beside the histories of both objects.
-    std::vector<NeedleHipRun> list;
-    std::vector<uint32_t> run_lane;
-    for (size_t lane = 0; lane < k * R; lane++) {
-      const std::vector<NeedleHipRun> &runs = streamed->run_list(lane);
-      list.insert(list.end(), runs.begin(), runs.end());
-      run_lane.insert(run_lane.end(), runs.size(), (uint32_t)lane);
-    }
-    const size_t from_matcher = list.size();
-    if (matcher) list.insert(list.end(), matcher->run_list().begin(), matcher->run_list().end());
-    std::vector<IndexLaneRow> lanes;
-    for (size_t at = n0 * R; at < n1 * R; at++) {
-      if (!rows.seqs[at].len) continue;
-      if (const uint32_t *history = streamed->history(at - n0 * R)) lanes.push_back(IndexLaneRow{rows.seqs[at].offset, history, rows.seqs[at].len});
-      if (matcher) lanes.push_back(IndexLaneRow{rows.seqs[at].offset, matcher->history(at - n0 * R), rows.seqs[at].len});
-    }
-    IndexStreamed m;
-    m.runs = list.data();
-    m.num_matcher_runs = from_matcher;
-    m.num_cross_runs = list.size() - from_matcher;
-    m.run_lane = run_lane.data();
-    m.min_len = rows.min_len.data();
-    m.lanes = lanes.data();
-    m.num_lanes = lanes.size();
-    if (!(s = gpu_index_append_streamed(store_, a, m, &out)).ok()) return s;
-    if (out.refused & kIngestOtherHashes) return refuse("a video's hashes differ from what its lane was fed");
-    if (out.refused) return refuse("a run of the matcher does not lie inside its rows");
-  } else if (matcher) {
-    std::vector<IndexSegment> lanes;
-    for (size_t at = n0 * R; at < n1 * R; at++)
-      if (rows.seqs[at].len)
-        lanes.push_back(IndexSegment{rows.seqs[at].offset, (uint64_t)(matcher->history(at - n0 * R) - matcher->history(0)), rows.seqs[at].len});
-    IndexMatched m;
-    m.runs = matcher->run_list().data();
-    m.num_runs = matcher->run_list().size();
-    m.min_len = rows.min_len.data();
-    m.history = matcher->history(0);
-    m.lanes = lanes.data();
-    m.num_lanes = lanes.size();
-    if (!(s = gpu_index_append_matched(store_, a, m, &out)).ok()) return s;
-    if (out.refused & kIngestOtherHashes) return refuse("a video's hashes differ from what its lane was fed");
-    if (out.refused) return refuse("a run of the matcher does not lie inside its rows");
-  } else {
-    s = gpu_index_append(store_, a, &out);
-    if (!s.ok()) return s;
-  }
-  s = settle(cmp_, streamed ? "Index::add_streamed" : matcher ? "Index::add_matched" : "Index::add", R, n1, new_pairs * R,
-             [&](uint64_t q, size_t *i, size_t *j) {
-               if (!groups) return column_pair(first_pair + q, i, j);
-               uint32_t gi = 0, gj = 0;
-               (void)index_group_pair_at(groups->view(), first_pair + q, &gi, &gj);
-               *i = gi;
-               *j = gj;
-             },
-             row_seq, video, [&](const auto &...computed) { return gpu_index_append_host_entries(store_, a, computed..., &out); }, out);
+  Status s = matcher ? append_streamed(store_, a, rows, matcher, cross, &out)
+             : cross ? append_matched(store_, a, rows, cross, &out)
+                     : gpu_index_append(store_, a, &out);
+  if (!s.ok()) return s;
+  if (out.refused & kIngestOtherHashes) return refused(index_route_refusal(route, "a video's hashes differ from what its lane was fed"));
+  if (out.refused) return refused(index_route_refusal(route, "a run of the matcher does not lie inside its rows"));
+  s = settle(cmp_, route_name(route), R, plan.new_pairs * R, ids, [&](uint64_t q) { return plan.first_pair + q; }, row_seq, video,
+             [&](const auto &...computed) { return gpu_index_append_host_entries(store_, a, computed..., &out); }, out);
   if (!s.ok()) return s;
   // commit: nothing above changed the index
   index_store_commit(store_, a, out.found);
   for (const FrameHashesData *d : fh) videos_.push_back(*d);
-  if (groups) {
-    labels_.swap(all_labels);
-    groups_ = std::move(groups);
-  }
+  labels_.swap(plan.labels);
+  ids_ = std::move(plan.ids);
   rows_ = std::move(rows);
   results_.resize(n1, NeedleHipSearchResult{});
   for (size_t q = 0; q < out.videos.size(); q++) results_[out.videos[q]] = out.results[q];
-  changed(searched, matcher || streamed ? 0 : searched);
+  changed(plan.searched, route == IndexRoute::Scan ? plan.searched : 0);
   return Status::Ok();
 }
-
 
 // Removal and replacement (DESIGN.md "Incremental index").  A pair's heap entries depend on the pair alone (its two sequences
 // and which of them is the source: the one first in the list), and removal keeps the others' relative order, so every kept
@@ -518,13 +483,15 @@ Status Index::replace(const std::vector<size_t> &positions, const std::vector<co
   return rebuild(old_of_new, fresh);
 }
 
+// remove and replace: plan -> rows -> IndexEdit -> the store call -> settle -> commit.  The committed ids give a kept pair's
+// old id (on the device: index_store.hip).
 Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector<const FrameHashesData *> &fresh) {
   const size_t n0 = videos_.size(), n1 = old_of_new.size(), R = regions_;
   if (n1 == 0) {  // every video removed: nothing is left to search or to hold
     index_store_clear(store_);
     videos_.clear();
     labels_.clear();
-    groups_.reset();
+    ids_.reset();
     rows_ = IndexRows();
     results_.clear();
     changed(0, 0);
@@ -533,26 +500,14 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   auto is_fresh = [&](size_t v) { return old_of_new[v] == kIndexFresh; };
   auto video = [&](size_t v) -> const FrameHashesData & { return is_fresh(v) ? *fresh[v] : videos_[old_of_new[v]]; };
   auto row_seq = [&](size_t v, size_t r) -> const std::vector<HashTs> & { return r == 0 ? video(v).opening : video(v).ending; };
-  // A grouped index: a kept video keeps its label, a replacement the label of the position it replaces; groups are numbered
-  // and ranked again over the new list (a group that is emptied renumbers the later ones, a removed member lowers the ranks
-  // behind it), and the committed tables give a kept pair's old id.
-  std::vector<uint32_t> labels;
-  std::unique_ptr<const IndexGroupTables> groups;
-  if (grouped_) {
-    for (size_t v = 0; v < n1; v++) labels.push_back(labels_[is_fresh(v) ? v : old_of_new[v]]);
-    groups.reset(new IndexGroupTables(labels.data(), n1));
-  }
+  IndexEditPlan plan = plan_index_edit(*ids_, labels_, old_of_new, R);
+  const IndexPairIds &ids = *plan.ids;
   if (include_endings_ && n1 > 1)
     for (size_t v = 0; v < n1; v++)
-      if (video(v).ending.empty() && (!groups || groups->size[groups->group_of[v]] > 1))  // comparator.rs:271-273 (every video that is in some pair)
+      if (video(v).ending.empty() && ids.paired(v))  // comparator.rs:271-273 (every video that is in some pair)
         return Status::Make(NeedleError_Unknown, "no ending hash data present");
-  if ((groups ? groups->pairs() : (uint64_t)n1 * (n1 - 1) / 2) * R >= 0xFFFFFFF0ull)
-    return Status::Make(NeedleError_InvalidArgument, "index too large: more than 2^32 hashes or sequence pairs");
-  std::vector<uint32_t> new_of_old(n0, kIndexFresh), gone;
-  for (size_t v = 0; v < n1; v++)
-    if (!is_fresh(v)) new_of_old[old_of_new[v]] = (uint32_t)v;
-  for (size_t q = 0; q < n0; q++)
-    if (new_of_old[q] == kIndexFresh) gone.push_back((uint32_t)q);
+  IndexRefusal no = ids.too_large(R);  // (before a row is made, as ever)
+  if (!no.ok()) return refused(no);
   // The new rows.  Kept rows first, gathered on the device: their hashes in order, and each distinct run of the timestamp
   // table they read once (rows that shared video 0's timestamps keep sharing them, whichever video is removed).  Then the
   // fresh rows behind them, sharing the new video 0's timestamps where equal, as an append does.
@@ -562,11 +517,10 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   std::vector<IndexSegment> hash_rows, ts_rows;
   std::unordered_map<uint32_t, uint32_t> ts_at;  // a committed timestamp offset -> its offset in the new table
   for (size_t v = 0; v < n1; v++) {
+    hash_duration[v] = video(v).hash_duration;
     if (is_fresh(v)) continue;
-    const size_t o = old_of_new[v];
-    hash_duration[v] = videos_[o].hash_duration;
     for (size_t r = 0; r < R; r++) {
-      const size_t row = v * R + r, orow = o * R + r;
+      const size_t row = v * R + r, orow = old_of_new[v] * R + r;
       const uint32_t len = rows_.seqs[orow].len;
       rows.seqs[row] = NeedleHipSeq{(uint32_t)rows.hashes, len};
       if (len) hash_rows.push_back(IndexSegment{rows_.seqs[orow].offset, rows.hashes, len});
@@ -588,7 +542,6 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   }
   for (size_t v = 0; v < n1; v++) {
     if (!is_fresh(v)) continue;
-    hash_duration[v] = fresh[v]->hash_duration;
     for (size_t at = v * R; at < (v + 1) * R; at++) {
       Status s = fresh_row(cmp_, row_seq(v, at % R), v > 0 ? &row_seq(0, at % R) : nullptr, R, at, &rows, &hashes, &ts);
       if (!s.ok()) return s;
@@ -596,38 +549,15 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
     }
   }
   for (uint8_t ok : rows.row_ok) rows.large_ok = rows.large_ok && ok;
-  // the pairs with a fresh video, each once (two fresh videos: under the later one), listed; their problems as in add
-  std::vector<uint32_t> pair_ids;
-  std::vector<NeedleHipProblem> problems;
-  uint64_t searched = 0;
-  auto list_pair = [&](size_t i, size_t j) {
-    searched += pair_problems(rows.min_len, R, i, j, (uint64_t)pair_ids.size() * R, &problems);
-    pair_ids.push_back((uint32_t)(groups ? groups->vbase[j] + groups->rank_of[i] : (uint64_t)j * (j - 1) / 2 + i));
-  };
-  for (size_t f = 0; f < n1; f++) {
-    if (!is_fresh(f)) continue;
-    if (groups) {  // its pairs inside its group only
-      const uint32_t g = groups->group_of[f];
-      for (uint32_t m = 0; m < groups->size[g]; m++) {
-        const size_t q = groups->members[groups->first[g] + m];
-        if (q < f) list_pair(q, f);
-        else if (q > f && !is_fresh(q)) list_pair(f, q);
-      }
-      continue;
-    }
-    for (size_t q = 0; q < f; q++) list_pair(q, f);
-    for (size_t q = f + 1; q < n1; q++)
-      if (!is_fresh(q)) list_pair(f, q);
-  }
+  list_index_edit(&plan, old_of_new, rows.min_len.data());
   IndexEdit e;
-  e.groups = groups.get();
   e.n_old = (uint32_t)n0;
   e.n_new = (uint32_t)n1;
-  set_options(cmp_, R, rows.large_ok, &e);
+  set_options(cmp_, R, rows.large_ok, ids, &e);
   e.old_of_new = old_of_new.data();
-  e.new_of_old = new_of_old.data();
-  e.gone = gone.data();
-  e.num_gone = gone.size();
+  e.new_of_old = plan.new_of_old.data();
+  e.gone = plan.gone.data();
+  e.num_gone = plan.gone.size();
   e.hash_rows = hash_rows.data();
   e.num_hash_rows = hash_rows.size();
   e.ts_rows = ts_rows.data();
@@ -642,22 +572,15 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   e.row_len = row_len.data();
   e.row_ts = rows.row_ts.data();
   e.hash_duration = hash_duration.data();
-  e.problems = problems.data();
-  e.num_problems = problems.size();
-  e.pair_ids = pair_ids.data();
-  e.num_pairs = pair_ids.size();
+  e.problems = plan.problems.data();
+  e.num_problems = plan.problems.size();
+  e.pair_ids = plan.pair_ids.data();
+  e.num_pairs = plan.pair_ids.size();
   IndexAppendOut out;
   Status s = gpu_index_edit(store_, e, &out);
   if (!s.ok()) return s;
-  s = settle(cmp_, "Index::replace", R, n1, (uint64_t)pair_ids.size() * R,
-             [&](uint64_t l, size_t *i, size_t *j) {
-               if (!groups) return column_pair(pair_ids[l], i, j);
-               uint32_t gi = 0, gj = 0;
-               (void)index_group_pair_at(groups->view(), pair_ids[l], &gi, &gj);
-               *i = gi;
-               *j = gj;
-             },
-             row_seq, video, [&](const auto &...computed) { return gpu_index_edit_host_entries(store_, e, computed..., &out); }, out);
+  s = settle(cmp_, "Index::replace", R, (uint64_t)plan.pair_ids.size() * R, ids, [&](uint64_t l) { return plan.pair_ids[l]; }, row_seq, video,
+             [&](const auto &...computed) { return gpu_index_edit_host_entries(store_, e, computed..., &out); }, out);
   if (!s.ok()) return s;
   // commit: nothing above changed the index
   index_store_switch(store_, e, out.held);
@@ -675,12 +598,10 @@ Status Index::rebuild(const std::vector<uint32_t> &old_of_new, const std::vector
   for (size_t q = 0; q < out.videos.size(); q++) results[out.videos[q]] = out.results[q];
   videos_.swap(videos);
   results_.swap(results);
-  if (groups) {
-    labels_.swap(labels);
-    groups_ = std::move(groups);
-  }
+  labels_.swap(plan.labels);
+  ids_ = std::move(plan.ids);
   rows_ = std::move(rows);
-  changed(searched, searched);
+  changed(plan.searched, plan.searched);
   return Status::Ok();
 }
 
@@ -690,8 +611,7 @@ Status Index::evidence(NeedleHipSearchEvidence *out) const {
   if (!out) return Status::Make(NeedleError_NullArgument, "index evidence: null argument");
   if (videos_.empty()) return Status::Ok();
   IndexOptions o;
-  set_options(cmp_, regions_, rows_.large_ok, &o);
-  o.groups = groups_.get();
+  set_options(cmp_, regions_, rows_.large_ok, *ids_, &o);
   return gpu_index_evidence(store_, o, out);
 }
 

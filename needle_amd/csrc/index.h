@@ -6,8 +6,8 @@
 
 #include "crossmatch.h"
 #include "matcher.h"
+#include "index_plan.h"
 #include "needle_core.h"
-#include "pair_ids.h"
 
 namespace needle {
 
@@ -88,8 +88,8 @@ class Index {
   uint32_t regions_;
   IndexStore *store_ = nullptr;
   const bool grouped_;
-  std::vector<uint32_t> labels_;                    // a grouped index: the current list's labels ...
-  std::unique_ptr<const IndexGroupTables> groups_;  // ... and their tables (null while plain or empty)
+  std::vector<uint32_t> labels_;            // a grouped index: the current list's labels
+  std::unique_ptr<const IndexPairIds> ids_;  // the current list's pair ids (index_plan.h; null while empty)
   std::vector<FrameHashesData> videos_;
   IndexRows rows_;
   std::vector<NeedleHipSearchResult> results_;
@@ -97,7 +97,11 @@ class Index {
   const uint64_t id_;        // from a process-wide counter: what a matcher made here remembers, with ...
   uint64_t generation_ = 1;  // ... this, which every successful change advances
 
-  Status append(const std::vector<const FrameHashesData *> &videos, CrossMatcher *matcher, Matcher *streamed, const uint32_t *labels = nullptr);
+  // every add: `labels` null on a plain index; `cross` and `matcher` as the route has them (index_plan.h)
+  Status append(const std::vector<const FrameHashesData *> &videos, const uint32_t *labels, IndexRoute route = IndexRoute::Scan,
+                CrossMatcher *cross = nullptr, Matcher *matcher = nullptr);
+  // what the route's objects say of themselves, and the index of itself
+  IndexAcceptance acceptance(IndexRoute route, size_t k, CrossMatcher *cross, Matcher *matcher) const;
   // crossmatcher (groups null) and crossmatcher_grouped after their own refusals
   Status make_crossmatcher(size_t videos, const uint32_t *groups, const size_t *max_items, const uint32_t *min_len,
                            std::unique_ptr<CrossMatcher> *out);
