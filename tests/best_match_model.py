@@ -5,8 +5,8 @@ NeedleHipMatchEvidence in tests/test_evidence_cpu.py and tests/test_gpu_index_ev
 Precondition: EVERY (pair, region) bucket holds AT MOST ONE run (assert_one_run_per_bucket).  Then no heap order is involved:
 the candidate list of video v is one entry per partner q in the reference's pair order -- (q, v) for q < v, where v is the
 destination, then (v, q) for q > v, where v is the source (:534-545) -- openings before endings within a pair (:414-431).
-Links, count and score are np.float32 with a separate multiply and add (:469); argmin breaks ties to the lower index
-(:473-475).
+Links, count and score are np.float32 with a separate multiply and add (:469); a candidate nobody links to, itself included
+(`count == 0`: only at threshold 0), is skipped; argmin breaks ties to the lower index (:473-475).
 
 Also here: the oracle's run list of a library in the form the host epilogue takes (oracle_runs), and the planted library both
 test files use (planted_library)."""
@@ -87,7 +87,6 @@ def evidence_model(ts, runs: np.ndarray, threshold: int, min_ns: Tuple[int, int]
     assert_one_run_per_bucket(runs)
     n, regions = len(ts), len(ts[0])
     pairs = [(i, j) for i in range(n) for j in range(i + 1, n)]
-    pair_id = {ij: p for p, ij in enumerate(pairs)}
     bucket: Dict[int, dict] = {}
     for run in runs:
         p, r = divmod(int(run["problem"]), regions)
@@ -99,20 +98,18 @@ def evidence_model(ts, runs: np.ndarray, threshold: int, min_ns: Tuple[int, int]
             continue
         bucket[int(run["problem"])] = dict(src=src, dst=dst, src_hash=int(run["src_match_hash"]), dst_hash=int(run["dst_match_hash"]))
     bound = threshold + threshold // 2                   # :441
+    # per video (partner, is_source, region, mine, theirs, my hash, their hash) in (partner, region) order: partners below v
+    # are its sources, those above its destinations, so this is the reference's pair order
+    lists = [[] for _ in range(n)]
+    for problem in sorted(bucket):
+        e = bucket[problem]
+        p, r = divmod(problem, regions)
+        i, j = pairs[p]
+        lists[i].append((j, True, r, e["src"], e["dst"], e["src_hash"], e["dst_hash"]))
+        lists[j].append((i, False, r, e["dst"], e["src"], e["dst_hash"], e["src_hash"]))
     results, evidence = [], []
     for v in range(n):
-        cand = []                                        # (partner, is_source, region, mine, theirs, my hash, their hash)
-        for q in range(n):
-            if q == v:
-                continue
-            is_source = v < q
-            p = pair_id[(v, q) if is_source else (q, v)]
-            for r in range(regions):
-                e = bucket.get(p * regions + r)
-                if e is None:
-                    continue
-                mine, theirs = ("src", "dst") if is_source else ("dst", "src")
-                cand.append((q, is_source, r, e[mine], e[theirs], e[mine + "_hash"], e[theirs + "_hash"]))
+        cand = sorted(lists[v], key=lambda c: (c[0], c[2]))
         if not cand:
             results.append(None)
             evidence.append((None, None))
@@ -125,7 +122,7 @@ def evidence_model(ts, runs: np.ndarray, threshold: int, min_ns: Tuple[int, int]
             best: Optional[int] = None
             best_key = None
             for k, c in enumerate(cand):
-                if c[2] != which:
+                if c[2] != which or links[k] == 0:       # `count == 0`: nobody within the bound, not even itself (t = 0)
                     continue
                 weighted = np.float32(links[k]) * np.float32(0.3) + as_secs_f32(c[3][1] - c[3][0]) * np.float32(0.7)
                 key = -weighted

@@ -91,6 +91,29 @@ def test_evidence_is_consistent_with_the_oracles_results(library):
     assert matched >= 6 + (3 if library.endings else 0)
 
 
+def test_threshold_zero_nobody_links_and_the_model_skips_them():
+    """t = 0: bound = 0, no candidate is within it of any other or of itself, and find_best_match skips a candidate without
+    links (comparator.rs `count == 0`): a video with candidates has a result with neither side.  The model against the oracle's
+    full search, and the host definition's evidence against the model's."""
+    from tests import link_tables as T
+    case = T.edge_case(0, rotations=2)
+    rows = case.rows()
+    ts = M.timestamps(rows)
+    pairs = lambda v, r: list(zip(rows[v][r].tolist(), ts[v][r]))
+    c = [capi.FrameHashes.new(pairs(v, 0), [], M.HD) for v in range(len(rows))]
+    o = [O.FrameHashes(pairs(v, 0), [], M.HD) for v in range(len(rows))]
+    runs = M.oracle_runs(rows, 0, case.min_len)
+    assert len(runs) == 32, "two hubs of sixteen exact copies"
+    want = O.run_with_frame_hashes(O.Comparator(hash_match_threshold=0, min_opening_duration=case.min_s * NS), o)
+    assert all(r is not None and r.opening is None and r.ending is None for r in want)
+    model_res, model_ev = M.evidence_model(ts, runs, 0, (case.min_s * NS, case.min_s * NS), False)
+    assert model_res == [(None, None)] * len(rows) and model_ev == [(None, None)] * len(rows)
+    cmp = capi.Comparator([f"v{k}.mkv" for k in range(len(rows))], hash_match_threshold=0, min_opening_duration=case.min_s)
+    results, evidence = cmp.results_from_runs_evidence(c, runs)
+    assert [(r.opening, r.ending) for r in results] == model_res
+    assert all(e.opening is None and e.ending is None for e in evidence)
+
+
 def test_no_match_reads_uint32_max_and_zeros(library):
     n = library.n
     arr = (C.c_void_p * n)(*[f._h for f in library.c])
