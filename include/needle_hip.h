@@ -1287,6 +1287,41 @@ enum NeedleError needle_hip_index_add_streamed(NeedleHipIndex *index, NeedleHipM
  * Either pointer may be NULL. */
 enum NeedleError needle_hip_index_pairs_scanned(const NeedleHipIndex *index, uint64_t *total, uint64_t *last);
 
+/* ---- Compressed fingerprints: chromaprint 1.5's FingerprintCompressor / FingerprintDecompressor on the device ----
+ * The string `fpcalc` prints and databases store.  x[i] = item[i] ^ item[i-1] (item[-1] = 0); the set bits of x from bit 0
+ * up, at 1-based positions p, as gaps to the previous one: gap < 7 is the 3-bit symbol gap, gap >= 7 the symbol 7 and a
+ * 5-bit exceptional symbol gap - 7; the symbol 0 ends the item.  A blob is [algorithm & 0xFF] [n >> 16] [n >> 8] [n], the
+ * 3-bit symbols packed LSB first into ceil(3 S / 8) bytes, then the 5-bit ones into ceil(5 E / 8) bytes, padding bits 0.
+ * The text form is base64 with the URL-safe alphabet and no padding.
+ *
+ * The codec is batched: fingerprint b is items[item_offsets[b] .. item_offsets[b + 1]), blob b is
+ * blobs[blob_offsets[b] .. blob_offsets[b + 1]); offsets rows have count + 1 entries and must not decrease
+ * (InvalidArgument).  Output buffers are malloc'd (needle_hip_host_free); the offsets rows, `algorithms` and `status`
+ * are the caller's.  There is no CPU codec: without a device the compute calls fail as every other one does.
+ *
+ * compress: a fingerprint of 2^24 items or more is InvalidArgument with nothing done (the header has 24 bits).
+ * decompress: status[b] is 0 ok; 1 the blob is shorter than a header; 2 the 3-bit stream ends before n terminators, or
+ * the header claims more items than the blob's bytes can hold (floor(8 (L - 4) / 3): refused before anything is
+ * allocated); 3 the exceptional stream ends early; 4 a bit position above 32.  A refused blob has an empty slot
+ * (item_offsets[b + 1] == item_offsets[b]) and the call returns Ok.  Bytes behind the exceptional stream are ignored, as
+ * upstream ignores them.  algorithms[b] is the blob's first byte (0 for an empty blob).  A blob longer than 2^30 bytes
+ * is InvalidArgument.
+ * feeder_compressed: the blob of a finished lane's kept items; an unfinished lane is InvalidArgument.
+ * compressed_bound, base64_encode / _decode, codec_tiles and simhash are pure host.  base64_decode refuses (InvalidArgument)
+ * characters outside the alphabet and a length of 1 mod 4; encode's text is NUL-terminated, *size excludes the NUL.
+ * codec_tiles: the items of a compress tile and the 3-bit symbols of a decompress tile, for tests that sit on their edges.
+ * simhash: chromaprint's 32-bit simhash of a fingerprint (what the run reports carry), 0 for an empty one. */
+size_t needle_hip_fingerprint_compressed_bound(size_t items); /* 4 + ceil(99 n / 8) + ceil(20 n / 8) */
+enum NeedleError needle_hip_fingerprint_compress_host(const uint32_t *items, const uint64_t *item_offsets, size_t count, int algorithm,
+                                                      uint8_t **blobs, uint64_t *blob_offsets);
+enum NeedleError needle_hip_fingerprint_decompress_host(const uint8_t *blobs, const uint64_t *blob_offsets, size_t count, uint32_t **items,
+                                                        uint64_t *item_offsets, int32_t *algorithms, int32_t *status);
+enum NeedleError needle_hip_feeder_compressed(NeedleHipFeeder *feeder, size_t lane, int algorithm, uint8_t **blob, size_t *size);
+enum NeedleError needle_hip_fingerprint_base64_encode(const uint8_t *data, size_t size, char **text, size_t *text_size);
+enum NeedleError needle_hip_fingerprint_base64_decode(const char *text, size_t text_size, uint8_t **data, size_t *size);
+enum NeedleError needle_hip_fingerprint_codec_tiles(size_t *compress_items, size_t *decompress_symbols);
+enum NeedleError needle_hip_fingerprint_simhash(const uint32_t *items, size_t count, uint32_t *hash);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,7 +144,10 @@ NEEDLE_HIP_H_SYMBOLS = [
     "needle_hip_crossmatcher_new_resident", "needle_hip_crossmatcher_state_bytes_resident", "needle_hip_crossmatcher_resident",
     "needle_hip_crossmatcher_new_grouped", "needle_hip_crossmatcher_state_bytes_grouped", "needle_hip_crossmatcher_groups",
     "needle_hip_index_crossmatcher_new_grouped", "needle_hip_index_add_matched_grouped",
-    "needle_hip_library_set_groups", "needle_hip_library_groups"]
+    "needle_hip_library_set_groups", "needle_hip_library_groups",
+    "needle_hip_fingerprint_compressed_bound", "needle_hip_fingerprint_compress_host", "needle_hip_fingerprint_decompress_host",
+    "needle_hip_feeder_compressed", "needle_hip_fingerprint_base64_encode", "needle_hip_fingerprint_base64_decode",
+    "needle_hip_fingerprint_codec_tiles", "needle_hip_fingerprint_simhash"]
 
 # enum NeedleHipSampleFormat (FFmpeg's AVSampleFormat numbering): interleaved 0-4, planar (one plane per channel) 5-9
 SAMPLE_U8, SAMPLE_S16, SAMPLE_S32, SAMPLE_F32, SAMPLE_F64 = 0, 1, 2, 3, 4
@@ -420,6 +423,15 @@ def lib():
     L.needle_hip_feeder_num_ready.argtypes = [u64, C.c_int, C.c_int, u32, b]
     L.needle_hip_feeder_num_ready.restype = sz
     L.needle_hip_feeder_new_lanes.argtypes = [vp, sz, u32, C.POINTER(vp)]
+    L.needle_hip_fingerprint_compressed_bound.argtypes = [sz]
+    L.needle_hip_fingerprint_compressed_bound.restype = sz
+    L.needle_hip_fingerprint_compress_host.argtypes = [vp, C.POINTER(u64), sz, C.c_int, C.POINTER(vp), C.POINTER(u64)]
+    L.needle_hip_fingerprint_decompress_host.argtypes = [vp, C.POINTER(u64), sz, C.POINTER(vp), C.POINTER(u64), vp, vp]
+    L.needle_hip_feeder_compressed.argtypes = [vp, sz, C.c_int, C.POINTER(vp), C.POINTER(sz)]
+    L.needle_hip_fingerprint_base64_encode.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz)]
+    L.needle_hip_fingerprint_base64_decode.argtypes = [vp, sz, C.POINTER(vp), C.POINTER(sz)]
+    L.needle_hip_fingerprint_codec_tiles.argtypes = [C.POINTER(sz), C.POINTER(sz)]
+    L.needle_hip_fingerprint_simhash.argtypes = [vp, sz, C.POINTER(u32)]
     L.needle_hip_feeder_lane_format.argtypes = [vp, sz, vp]
     L.needle_hip_library_set_video_formats.argtypes = [vp, vp, vp]
     L.needle_hip_library_video_format.argtypes = [vp, sz, vp]
@@ -584,6 +596,81 @@ def kernel_launches(name: str) -> int:
 def set_kernel_timing(kernels: Optional[str]) -> None:
     """"all", a comma-separated list of kernel names, or None: which launches get HIP timing events."""
     lib().needle_hip_set_kernel_timing(kernels.encode() if kernels else None)
+
+
+# ---- compressed fingerprints (chromaprint's codec, fp_codec.hip) ----------------------------------------
+def _take_bytes(ptr, size: int) -> bytes:
+    """The bytes of an array the library malloc'd, which is freed."""
+    out = C.string_at(ptr, size) if size else b""
+    lib().needle_hip_host_free(ptr)
+    return out
+
+
+def fingerprint_compressed_bound(items: int) -> int:
+    """The most bytes a fingerprint of `items` items compresses to (pure host)."""
+    return int(lib().needle_hip_fingerprint_compressed_bound(items))
+
+
+def fingerprint_codec_tiles() -> Tuple[int, int]:
+    """(items of a compress tile, 3-bit symbols of a decompress tile) of the device codec (pure host)."""
+    t, d = C.c_size_t(), C.c_size_t()
+    check(lib().needle_hip_fingerprint_codec_tiles(C.byref(t), C.byref(d)))
+    return t.value, d.value
+
+
+def fingerprint_base64_encode(data: bytes) -> str:
+    text, size = C.c_void_p(), C.c_size_t()
+    data = bytes(data)
+    check(lib().needle_hip_fingerprint_base64_encode(data, len(data), C.byref(text), C.byref(size)))
+    return _take_bytes(text, size.value).decode()
+
+
+def fingerprint_base64_decode(text) -> bytes:
+    raw = text.encode("latin-1") if isinstance(text, str) else bytes(text)
+    data, size = C.c_void_p(), C.c_size_t()
+    check(lib().needle_hip_fingerprint_base64_decode(raw, len(raw), C.byref(data), C.byref(size)))
+    return _take_bytes(data, size.value)
+
+
+def fingerprint_simhash(items) -> int:
+    """chromaprint's 32-bit simhash of a fingerprint (pure host); 0 for an empty one."""
+    arr = np.ascontiguousarray(items, dtype=np.uint32)
+    h = C.c_uint32()
+    check(lib().needle_hip_fingerprint_simhash(arr.ctypes.data if arr.size else None, arr.size, C.byref(h)))
+    return h.value
+
+
+def compress_fingerprints(fingerprints: Sequence, algorithm: int = 1, base64: bool = False) -> list:
+    """Each fingerprint (uint32 items) in chromaprint's compressed form, on the device, all in one call: a list of bytes,
+    or of base64 strings (URL-safe, unpadded: what fpcalc prints)."""
+    arrays = [np.ascontiguousarray(f, dtype=np.uint32).ravel() for f in fingerprints]
+    items = np.concatenate(arrays) if arrays else np.zeros(0, np.uint32)
+    off = (C.c_uint64 * (len(arrays) + 1))(*np.concatenate([[0], np.cumsum([a.size for a in arrays])]).astype(np.uint64).tolist())
+    blob_off = (C.c_uint64 * (len(arrays) + 1))()
+    blobs = C.c_void_p()
+    check(lib().needle_hip_fingerprint_compress_host(items.ctypes.data if items.size else None, off, len(arrays), algorithm,
+                                                     C.byref(blobs), blob_off))
+    data = _take_bytes(blobs, blob_off[len(arrays)])
+    out = [data[blob_off[b]:blob_off[b + 1]] for b in range(len(arrays))]
+    return [fingerprint_base64_encode(b) for b in out] if base64 else out
+
+
+def decompress_fingerprints(blobs: Sequence, base64: bool = False):
+    """(arrays, algorithms, status) of compressed fingerprints, on the device, all in one call.  status[b]: 0 ok, 1 shorter
+    than a header, 2 the normal stream ends early, 3 the exceptional stream ends early, 4 a bit position above 32; a
+    refused blob's array is empty.  base64: strings in; text that is not base64 raises NeedleError (InvalidArgument)."""
+    raw = [fingerprint_base64_decode(b) if base64 else bytes(b) for b in blobs]
+    data = b"".join(raw)
+    off = (C.c_uint64 * (len(raw) + 1))(*np.concatenate([[0], np.cumsum([len(r) for r in raw])]).astype(np.uint64).tolist())
+    item_off = (C.c_uint64 * (len(raw) + 1))()
+    algorithms = np.zeros(max(len(raw), 1), np.int32)
+    status = np.zeros(max(len(raw), 1), np.int32)
+    items = C.c_void_p()
+    check(lib().needle_hip_fingerprint_decompress_host(data if data else None, off, len(raw), C.byref(items), item_off,
+                                                       algorithms.ctypes.data, status.ctypes.data))
+    flat = np.frombuffer(_take_bytes(items, 4 * item_off[len(raw)]), dtype=np.uint32)
+    arrays = [flat[item_off[b]:item_off[b + 1]].copy() for b in range(len(raw))]
+    return arrays, algorithms[:len(raw)].tolist(), status[:len(raw)].tolist()
 
 
 def _paths(paths: Sequence[str]):
@@ -1263,6 +1350,13 @@ class Feeder:
         out = np.zeros(max(count, 0), dtype=np.uint32)
         check(lib().needle_hip_feeder_items(self._h, lane, first, count, out.ctypes.data if count else None))
         return out
+
+    def compressed(self, lane: int, algorithm: int = 1, base64: bool = False):
+        """A finished lane's kept items in chromaprint's compressed form (bytes, or the base64 string fpcalc prints)."""
+        blob, size = C.c_void_p(), C.c_size_t()
+        check(lib().needle_hip_feeder_compressed(self._h, lane, algorithm, C.byref(blob), C.byref(size)))
+        data = _take_bytes(blob, size.value)
+        return fingerprint_base64_encode(data) if base64 else data
 
     def frame_hashes(self, opening_lane: int, ending_lane: Optional[int] = None, ending_seek_ns: int = 0,
                      hash_duration: float = DEFAULT_HASH_DURATION, md5: str = "") -> "FrameHashes":

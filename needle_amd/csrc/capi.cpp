@@ -19,6 +19,7 @@
 #include "epilogue.h"
 #include "hipctx.h"
 #include "feeder.h"
+#include "fp_codec.h"
 #include "index.h"
 #include "matcher.h"
 #include "needle_core.h"
@@ -1736,6 +1737,118 @@ enum NeedleError needle_hip_index_groups(const NeedleHipIndex *index, uint32_t *
   if (n < have.size()) return report(Status::Make(NeedleError_InvalidArgument, "index groups: buffer shorter than the index"));
   if (!labels && !have.empty()) return NeedleError_NullArgument;
   if (!have.empty()) std::memcpy(labels, have.data(), have.size() * sizeof(uint32_t));
+  return NeedleError_Ok;
+}
+
+// ============================================================================================================
+// Compressed fingerprints (fp_codec.hip)
+// ============================================================================================================
+extern "C++" {
+namespace {
+template <class T>
+T *malloc_copy(const T *src, size_t n, size_t extra = 0) {
+  T *arr = static_cast<T *>(std::malloc(std::max<size_t>(n + extra, 1) * sizeof(T)));
+  if (arr && n) std::memcpy(arr, src, n * sizeof(T));
+  return arr;
+}
+}  // namespace
+}  // extern "C++"
+
+size_t needle_hip_fingerprint_compressed_bound(size_t items) { return (size_t)fpc_compressed_bound(items); }
+
+enum NeedleError needle_hip_fingerprint_compress_host(const uint32_t *items, const uint64_t *item_offsets, size_t count, int algorithm,
+                                                      uint8_t **blobs, uint64_t *blob_offsets) {
+  if (!item_offsets || !blobs || !blob_offsets || (!items && item_offsets[count] > item_offsets[0])) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<uint8_t> out;
+    std::vector<uint64_t> off;
+    Status s = gpu_fp_compress_host(items, item_offsets, count, algorithm, &out, &off);
+    if (!s.ok()) return report(s);
+    uint8_t *arr = malloc_copy(out.data(), out.size());
+    if (!arr) return report(Status::Make(NeedleError_Unknown, "out of memory"));
+    *blobs = arr;
+    std::memcpy(blob_offsets, off.data(), (count + 1) * sizeof(uint64_t));
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_fingerprint_decompress_host(const uint8_t *blobs, const uint64_t *blob_offsets, size_t count, uint32_t **items,
+                                                        uint64_t *item_offsets, int32_t *algorithms, int32_t *status) {
+  if (!blob_offsets || !items || !item_offsets || (count && (!algorithms || !status)) || (!blobs && blob_offsets[count] > blob_offsets[0]))
+    return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<uint32_t> out;
+    std::vector<uint64_t> off;
+    std::vector<int32_t> alg, st;
+    Status s = gpu_fp_decompress_host(blobs, blob_offsets, count, &out, &off, &alg, &st);
+    if (!s.ok()) return report(s);
+    uint32_t *arr = malloc_copy(out.data(), out.size());
+    if (!arr) return report(Status::Make(NeedleError_Unknown, "out of memory"));
+    *items = arr;
+    std::memcpy(item_offsets, off.data(), (count + 1) * sizeof(uint64_t));
+    if (count) {
+      std::memcpy(algorithms, alg.data(), count * sizeof(int32_t));
+      std::memcpy(status, st.data(), count * sizeof(int32_t));
+    }
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_feeder_compressed(NeedleHipFeeder *feeder, size_t lane, int algorithm, uint8_t **blob, size_t *size) {
+  if (!feeder || !blob || !size) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    const std::vector<uint32_t> *kept = nullptr;
+    Status s = feeder->inner->FinishedItems(lane, &kept);
+    if (!s.ok()) return report(s);
+    const uint64_t item_off[2] = {0, kept->size()};
+    std::vector<uint8_t> out;
+    std::vector<uint64_t> off;
+    if (!(s = gpu_fp_compress_host(kept->data(), item_off, 1, algorithm, &out, &off)).ok()) return report(s);
+    uint8_t *arr = malloc_copy(out.data(), out.size());
+    if (!arr) return report(Status::Make(NeedleError_Unknown, "out of memory"));
+    *blob = arr;
+    *size = out.size();
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_fingerprint_base64_encode(const uint8_t *data, size_t size, char **text, size_t *text_size) {
+  if ((!data && size) || !text || !text_size) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    const std::string out = fp_base64_encode(data, size);
+    char *arr = malloc_copy(out.data(), out.size(), 1);
+    if (!arr) return report(Status::Make(NeedleError_Unknown, "out of memory"));
+    arr[out.size()] = 0;
+    *text = arr;
+    *text_size = out.size();
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_fingerprint_base64_decode(const char *text, size_t text_size, uint8_t **data, size_t *size) {
+  if ((!text && text_size) || !data || !size) return NeedleError_NullArgument;
+  return guarded([&]() -> NeedleError {
+    std::vector<uint8_t> out;
+    if (!fp_base64_decode(text, text_size, &out))
+      return report(Status::Make(NeedleError_InvalidArgument, "base64: a character outside the URL-safe alphabet, or a length of 1 mod 4"));
+    uint8_t *arr = malloc_copy(out.data(), out.size());
+    if (!arr) return report(Status::Make(NeedleError_Unknown, "out of memory"));
+    *data = arr;
+    *size = out.size();
+    return NeedleError_Ok;
+  });
+}
+
+enum NeedleError needle_hip_fingerprint_codec_tiles(size_t *compress_items, size_t *decompress_symbols) {
+  if (!compress_items || !decompress_symbols) return NeedleError_NullArgument;
+  *compress_items = kFpcTileItems;
+  *decompress_symbols = kFpdTileSymbols;
+  return NeedleError_Ok;
+}
+
+enum NeedleError needle_hip_fingerprint_simhash(const uint32_t *items, size_t count, uint32_t *hash) {
+  if ((!items && count) || !hash) return NeedleError_NullArgument;
+  *hash = simhash32(items, count);
   return NeedleError_Ok;
 }
 

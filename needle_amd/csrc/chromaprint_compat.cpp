@@ -1,7 +1,8 @@
 // libneedle_chromaprint.so: libchromaprint's streaming C API (the part needle uses) over the streaming GPU
 // fingerprinter: a context owns a one-lane feeder (needle_hip_feeder_*), chromaprint_feed gathers at most one block of
 // PCM on the host (4 s; NEEDLE_CHROMAPRINT_FEED_BLOCK: samples per channel) and feeds every full block,
-// chromaprint_finish flushes.  See include/needle_chromaprint.h.
+// chromaprint_finish flushes.  The compressed forms (chromaprint_get_fingerprint, _encode_fingerprint, _decode_fingerprint)
+// go through the device codec (needle_hip_fingerprint_*, needle_hip_feeder_compressed).  See include/needle_chromaprint.h.
 #include "../../include/needle_chromaprint.h"
 
 #include <cstdlib>
@@ -16,6 +17,7 @@ struct ChromaprintContextPrivate {
   int channels = 1;
   int rate = 11025;
   bool started = false, finished = false;
+  bool cleared = false;            // chromaprint_clear_fingerprint since finish()
   NeedleHipFeeder *feeder = nullptr;
   size_t block_frames = 0;         // samples per channel gathered before they go to the feeder
   std::vector<int16_t> block;      // at most that many, not yet fed
@@ -68,6 +70,7 @@ int chromaprint_start(ChromaprintContext *ctx, int sample_rate, int num_channels
   ctx->raw.clear();
   ctx->started = true;
   ctx->finished = false;
+  ctx->cleared = false;
   return 1;
 }
 
@@ -127,7 +130,85 @@ int chromaprint_get_raw_fingerprint_size(ChromaprintContext *ctx, int *size) {
 int chromaprint_clear_fingerprint(ChromaprintContext *ctx) {
   if (!ctx) return 0;
   ctx->raw.clear();
+  ctx->cleared = true;
   return 1;
+}
+
+// a malloc'd copy the caller frees with chromaprint_dealloc; bytes from this library's own allocator are released here
+static void *take(void *from, size_t n, size_t extra) {
+  void *out = std::malloc(n + extra ? n + extra : 1);
+  if (out && n) std::memcpy(out, from, n);
+  if (out && extra) std::memset(static_cast<char *>(out) + n, 0, extra);
+  needle_hip_host_free(from);
+  return out;
+}
+
+// blob -> *encoded (NUL-terminated either way), base64 or as it is
+static int hand_over(uint8_t *blob, size_t size, int base64, char **encoded, int *encoded_size) {
+  if (!base64) {
+    *encoded = static_cast<char *>(take(blob, size, 1));
+    if (encoded_size) *encoded_size = (int)size;
+    return *encoded != nullptr;
+  }
+  char *text = nullptr;
+  size_t text_size = 0;
+  const bool ok = needle_hip_fingerprint_base64_encode(blob, size, &text, &text_size) == NeedleError_Ok;
+  needle_hip_host_free(blob);
+  if (!ok) return 0;
+  *encoded = static_cast<char *>(take(text, text_size, 1));
+  if (encoded_size) *encoded_size = (int)text_size;
+  return *encoded != nullptr;
+}
+
+int chromaprint_get_fingerprint(ChromaprintContext *ctx, char **fingerprint) {
+  if (!ctx || !fingerprint || !ctx->finished || ctx->cleared) return 0;
+  uint8_t *blob = nullptr;
+  size_t size = 0;
+  if (needle_hip_feeder_compressed(ctx->feeder, 0, ctx->algorithm, &blob, &size) != NeedleError_Ok) return 0;
+  return hand_over(blob, size, 1, fingerprint, nullptr);
+}
+
+int chromaprint_get_fingerprint_hash(ChromaprintContext *ctx, uint32_t *hash) {
+  if (!ctx || !hash || !ctx->finished) return 0;
+  return needle_hip_fingerprint_simhash(ctx->raw.data(), ctx->raw.size(), hash) == NeedleError_Ok;
+}
+
+int chromaprint_encode_fingerprint(const uint32_t *fp, int size, int algorithm, char **encoded_fp, int *encoded_size, int base64) {
+  if (size < 0 || (size && !fp) || !encoded_fp || !encoded_size) return 0;
+  const uint64_t item_off[2] = {0, (uint64_t)size};
+  uint64_t blob_off[2] = {0, 0};
+  uint8_t *blob = nullptr;
+  if (needle_hip_fingerprint_compress_host(fp, item_off, 1, algorithm, &blob, blob_off) != NeedleError_Ok) return 0;
+  return hand_over(blob, (size_t)blob_off[1], base64, encoded_fp, encoded_size);
+}
+
+int chromaprint_decode_fingerprint(const char *encoded_fp, int encoded_size, uint32_t **fp, int *size, int *algorithm, int base64) {
+  if (encoded_size < 0 || (encoded_size && !encoded_fp) || !fp || !size) return 0;
+  uint8_t *bytes = nullptr;
+  size_t n = (size_t)encoded_size;
+  if (base64 && needle_hip_fingerprint_base64_decode(encoded_fp, (size_t)encoded_size, &bytes, &n) != NeedleError_Ok) return 0;
+  const uint64_t blob_off[2] = {0, n};
+  uint64_t item_off[2] = {0, 0};
+  uint32_t *items = nullptr;
+  int32_t alg = 0, status = 0;
+  const bool ok = needle_hip_fingerprint_decompress_host(base64 ? bytes : reinterpret_cast<const uint8_t *>(encoded_fp), blob_off, 1, &items,
+                                                         item_off, &alg, &status) == NeedleError_Ok;
+  needle_hip_host_free(bytes);
+  if (!ok) return 0;
+  if (status != 0) {  // refused: shorter than a header, a stream that ends early, a bit position above 32
+    needle_hip_host_free(items);
+    return 0;
+  }
+  *fp = static_cast<uint32_t *>(take(items, (size_t)item_off[1] * sizeof(uint32_t), 0));
+  if (!*fp) return 0;
+  *size = (int)item_off[1];
+  if (algorithm) *algorithm = alg;
+  return 1;
+}
+
+int chromaprint_hash_fingerprint(const uint32_t *fp, int size, uint32_t *hash) {
+  if (size < 0 || (size && !fp) || !hash) return 0;
+  return needle_hip_fingerprint_simhash(fp, (size_t)size, hash) == NeedleError_Ok;
 }
 
 void chromaprint_dealloc(void *ptr) { std::free(ptr); }

@@ -735,4 +735,28 @@ extern "C" {
     ) -> usize;
     pub fn needle_hip_crossmatcher_groups(matcher: *const NeedleHipCrossMatcher, labels: *mut u32, n: usize) -> NeedleError;
     pub fn needle_hip_host_free(ptr: *mut c_void);
+    // compressed fingerprints: chromaprint's codec on the device
+    pub fn needle_hip_fingerprint_compressed_bound(items: usize) -> usize;
+    pub fn needle_hip_fingerprint_compress_host(
+        items: *const u32,
+        item_offsets: *const u64,
+        count: usize,
+        algorithm: c_int,
+        blobs: *mut *mut u8,
+        blob_offsets: *mut u64,
+    ) -> NeedleError;
+    pub fn needle_hip_fingerprint_decompress_host(
+        blobs: *const u8,
+        blob_offsets: *const u64,
+        count: usize,
+        items: *mut *mut u32,
+        item_offsets: *mut u64,
+        algorithms: *mut i32,
+        status: *mut i32,
+    ) -> NeedleError;
+    pub fn needle_hip_feeder_compressed(feeder: *mut NeedleHipFeeder, lane: usize, algorithm: c_int, blob: *mut *mut u8, size: *mut usize) -> NeedleError;
+    pub fn needle_hip_fingerprint_base64_encode(data: *const u8, size: usize, text: *mut *mut c_char, text_size: *mut usize) -> NeedleError;
+    pub fn needle_hip_fingerprint_base64_decode(text: *const c_char, text_size: usize, data: *mut *mut u8, size: *mut usize) -> NeedleError;
+    pub fn needle_hip_fingerprint_codec_tiles(compress_items: *mut usize, decompress_symbols: *mut usize) -> NeedleError;
+    pub fn needle_hip_fingerprint_simhash(items: *const u32, count: usize, hash: *mut u32) -> NeedleError;
 }

@@ -785,6 +785,15 @@ impl Feeder {
         Ok(out)
     }
 
+    /// A finished lane's kept items in chromaprint's compressed form; [`base64_encode`] gives the string `fpcalc` prints.
+    pub fn compressed(&mut self, lane: usize, algorithm: i32) -> Result<Vec<u8>> {
+        let (mut blob, mut size) = (ptr::null_mut(), 0usize);
+        unsafe {
+            check(ffi::needle_hip_feeder_compressed(self.raw, lane, algorithm, &mut blob, &mut size))?;
+            Ok(take_host(blob, size))
+        }
+    }
+
     /// The `FrameHashes` of one video from its finished opening lane and, optionally, its ending lane with the seek offset of
     /// the ending window (analyzer.rs:314-318).
     pub fn frame_hashes(&mut self, opening_lane: usize, ending: Option<(usize, Duration)>, hash_duration: Duration, md5: &str) -> Result<FrameHashes> {
@@ -1369,6 +1378,101 @@ pub fn group_pairs(groups: &[u32]) -> Result<Vec<(u32, u32)>> {
     let mut flat = vec![0u32; 2 * count as usize];
     unsafe { check(ffi::needle_hip_group_pairs(groups.as_ptr(), groups.len(), flat.as_mut_ptr(), count as usize, &mut count))? };
     Ok(flat.chunks_exact(2).map(|p| (p[0], p[1])).collect())
+}
+
+/// A copy of `n` values the library malloc'd at `p`, which is freed.
+unsafe fn take_host<T: Copy>(p: *mut T, n: usize) -> Vec<T> {
+    let out = if n == 0 { Vec::new() } else { std::slice::from_raw_parts(p as *const T, n).to_vec() };
+    ffi::needle_hip_host_free(p as *mut std::os::raw::c_void);
+    out
+}
+
+/// The most bytes a fingerprint of `items` items compresses to.
+pub fn fingerprint_compressed_bound(items: usize) -> usize {
+    unsafe { ffi::needle_hip_fingerprint_compressed_bound(items) }
+}
+
+/// `(items of a compress tile, 3-bit symbols of a decompress tile)` of the device codec.
+pub fn fingerprint_codec_tiles() -> Result<(usize, usize)> {
+    let (mut t, mut d) = (0usize, 0usize);
+    unsafe { check(ffi::needle_hip_fingerprint_codec_tiles(&mut t, &mut d))? };
+    Ok((t, d))
+}
+
+/// Each fingerprint in chromaprint's compressed form (`FingerprintCompressor`), on the device, all in one call.
+pub fn compress_fingerprints(fingerprints: &[&[u32]], algorithm: i32) -> Result<Vec<Vec<u8>>> {
+    let items: Vec<u32> = fingerprints.iter().flat_map(|f| f.iter().copied()).collect();
+    let mut off = vec![0u64; fingerprints.len() + 1];
+    for (b, f) in fingerprints.iter().enumerate() {
+        off[b + 1] = off[b] + f.len() as u64;
+    }
+    let mut blob_off = vec![0u64; fingerprints.len() + 1];
+    let mut blobs = ptr::null_mut();
+    unsafe {
+        check(ffi::needle_hip_fingerprint_compress_host(items.as_ptr(), off.as_ptr(), fingerprints.len(), algorithm, &mut blobs, blob_off.as_mut_ptr()))?;
+        let data = take_host(blobs, blob_off[fingerprints.len()] as usize);
+        Ok(blob_off.windows(2).map(|w| data[w[0] as usize..w[1] as usize].to_vec()).collect())
+    }
+}
+
+/// One decompressed fingerprint: `status` 0 ok, 1 shorter than a header, 2 the normal stream ends early, 3 the exceptional
+/// stream ends early, 4 a bit position above 32; the items of a refused blob are empty.
+pub struct Decompressed {
+    pub items: Vec<u32>,
+    pub algorithm: i32,
+    pub status: i32,
+}
+
+/// Compressed fingerprints back to items (`FingerprintDecompressor`), on the device, all in one call.
+pub fn decompress_fingerprints(blobs: &[&[u8]]) -> Result<Vec<Decompressed>> {
+    let data: Vec<u8> = blobs.iter().flat_map(|b| b.iter().copied()).collect();
+    let mut off = vec![0u64; blobs.len() + 1];
+    for (b, blob) in blobs.iter().enumerate() {
+        off[b + 1] = off[b] + blob.len() as u64;
+    }
+    let mut item_off = vec![0u64; blobs.len() + 1];
+    let (mut algorithms, mut status) = (vec![0i32; blobs.len()], vec![0i32; blobs.len()]);
+    let mut items = ptr::null_mut();
+    unsafe {
+        check(ffi::needle_hip_fingerprint_decompress_host(
+            data.as_ptr(),
+            off.as_ptr(),
+            blobs.len(),
+            &mut items,
+            item_off.as_mut_ptr(),
+            algorithms.as_mut_ptr(),
+            status.as_mut_ptr(),
+        ))?;
+        let flat = take_host(items, item_off[blobs.len()] as usize);
+        Ok((0..blobs.len())
+            .map(|b| Decompressed { items: flat[item_off[b] as usize..item_off[b + 1] as usize].to_vec(), algorithm: algorithms[b], status: status[b] })
+            .collect())
+    }
+}
+
+/// base64 with the URL-safe alphabet and no padding: the text form of a compressed fingerprint.
+pub fn base64_encode(data: &[u8]) -> Result<String> {
+    let (mut text, mut size) = (ptr::null_mut(), 0usize);
+    unsafe {
+        check(ffi::needle_hip_fingerprint_base64_encode(data.as_ptr(), data.len(), &mut text, &mut size))?;
+        Ok(String::from_utf8_lossy(&take_host(text as *mut u8, size)).into_owned())
+    }
+}
+
+/// Refuses characters outside the alphabet and a length of 1 mod 4.
+pub fn base64_decode(text: &str) -> Result<Vec<u8>> {
+    let (mut data, mut size) = (ptr::null_mut(), 0usize);
+    unsafe {
+        check(ffi::needle_hip_fingerprint_base64_decode(text.as_ptr() as *const std::os::raw::c_char, text.len(), &mut data, &mut size))?;
+        Ok(take_host(data, size))
+    }
+}
+
+/// chromaprint's 32-bit simhash of a fingerprint; 0 for an empty one.
+pub fn fingerprint_simhash(items: &[u32]) -> Result<u32> {
+    let mut hash = 0u32;
+    unsafe { check(ffi::needle_hip_fingerprint_simhash(items.as_ptr(), items.len(), &mut hash))? };
+    Ok(hash)
 }
 
 /// Number of HIP devices the library sees (0 on a host without a GPU: every compute call then fails loudly).
